@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GP log-lik+grad evaluations/s at N=8192, D=10 (fp64) on MI355X.
 
-    python bench.py [--steps K] [--warmup W]                    (one GPU)
+    python bench.py [--steps K] [--warmup W] [--dump-outputs DIR] [--full]      (one GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W   (N > 1: one rank per GPU; under torchrun
                                                                   --gpus defaults to WORLD_SIZE)
@@ -13,7 +13,14 @@ reference's cg_solve calls at every probe, covkernel.cpp:500-501).  Inputs are s
 With N ranks every rank owns one N=8192 expert (BCM sharding: experts are independent, weak scaling)
 and the per-evaluation exchange is one all-reduce of K x 4 doubles over RCCL.
 
-The run is made of passes (--passes, default all three, in this order):
+A plain run sets up, makes W warm-up and K timed evaluations on the default path (the `timed` pass below),
+writes the outputs if asked and prints the line: `value`, `ms_per_step` (ms of one timed evaluation) and what
+the evaluations returned.  --dump-outputs DIR writes what the last timed evaluation returned to its caller, as
+float64 arrays: DIR/ll.npy (1,), DIR/grad.npy (3,), DIR/ll_per_expert.npy (K,); the inputs depend only on the
+arguments, so two builds can be compared output for output.  Everything else moves behind --full: the
+profiled and isolated passes, prediction, the BCM sub-runs of configs 4 and 5 and the CPU baseline.
+
+With --full the run is made of passes (--passes, default all three, in this order):
   timed      W warm-up + K evaluations on the DEFAULT path (no per-launch events, no instrumentation): `value`
   profiled   the same K evaluations with every launch of every MFMA kernel (and the covariance build) timed by its own
              workgroups (cugp_set_profiling 5: first workgroup's start / last workgroup's end on the chip-wide 100 MHz
@@ -24,7 +31,7 @@ The run is made of passes (--passes, default all three, in this order):
 tools/make_profiles.sh runs rocprofv3 --kernel-trace --stats once per pass (--passes timed | profiled | isolated), so
 the average duration of a kernel in the CSV named in roofline.dominant_by reproduces roofline.achieved.
 
-Rank 0 prints ONE JSON line; besides the driver's contract it carries
+Rank 0 prints ONE JSON line; with --full, besides the driver's contract it carries
   roofline        the MFMA kernel with the largest share of kernel time in the profiled pass (HIP events around its
                   launches on the stream they run on; algorithmic flop / duration against the fp64 MFMA peak)
   roofline_kernels  the same record for every timed kernel, named as rocprofv3 names them
@@ -169,13 +176,20 @@ def main():
                     help="strong-scaling BCM workload: this many experts in total, expert k on rank k mod N "
                          "(e.g. --experts-total 16 --rows 1500 = the si24000 16-shard shape); value = BCM objective "
                          "evaluations/s (all experts + all-reduce per evaluation)")
-    ap.add_argument("--cpu-sample", type=int, default=2560, help="rows for the CPU baseline (0 = skip)")
-    ap.add_argument("--sub-steps", type=int, default=10, help="timed evaluations of each BCM sub-run (configs 4, 5); 0 = skip")
+    ap.add_argument("--full", action="store_true", help="besides the headline, measure everything else: the profiled "
+                    "and isolated passes (roofline*, cholesky_gflops), prediction, the BCM sub-runs of configs 4 and 5 and "
+                    "the CPU baseline (see the module docstring); a plain run only times the default path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed evaluation returned "
+                    "(ll, grad, ll_per_expert; float64) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="rows for the CPU baseline (0 = skip; --full only, "
+                    "default there 2560)")
+    ap.add_argument("--sub-steps", type=int, default=None, help="timed evaluations of each BCM sub-run (configs 4, 5); "
+                    "0 = skip (--full only, default there 10)")
     ap.add_argument("--overlap", type=int, default=1, help="0: build the inverse after the factorisation on one stream "
                     "(every kernel has the chip to itself: the per-kernel roofline of the whole run is the isolated one "
                     "and no extra pass is made)")
-    ap.add_argument("--passes", default="timed,profiled,isolated", help="comma list of timed, profiled, isolated (see the "
-                    "module docstring); the contract line needs `timed`")
+    ap.add_argument("--passes", default=None, help="comma list of timed, profiled, isolated (see the module docstring); "
+                    "the contract line needs `timed`; profiled and isolated need --full (default there: all three)")
     ap.add_argument("--prof-level", type=int, default=5, help="profiling level of the profiled / isolated passes: 5 = every "
                     "timed launch's own workgroups stamp their first start / last end (s_memrealtime) into a device buffer -- "
                     "nothing is added to the streams, the schedule is the timed pass's; 4 = every MFMA launch carries its own "
@@ -191,6 +205,18 @@ def main():
                     "multi-GPU run take: a 1-rank RCCL process group, the expert's row written into the device tensor and "
                     "all-reduced there (cugp_bcm_loglik_grad_rows_device)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.full:
+        args.passes = "timed,profiled,isolated" if args.passes is None else args.passes
+        args.cpu_sample = 2560 if args.cpu_sample is None else args.cpu_sample
+        args.sub_steps = 10 if args.sub_steps is None else args.sub_steps
+    else:
+        args.passes = "timed" if args.passes is None else args.passes
+        args.cpu_sample = args.cpu_sample or 0
+        args.sub_steps = args.sub_steps or 0
+        if set(p for p in args.passes.split(",") if p) != {"timed"} or args.cpu_sample > 0 or args.sub_steps > 0:
+            ap.error("the profiled / isolated passes, the CPU baseline and the BCM sub-runs need --full")
 
     # stdout carries ONE line, the JSON record.  Whatever the libraries underneath print while they initialise (RCCL
     # writes a version banner to stdout when its first communicator is created) goes to stderr: file descriptor 1 points
@@ -265,7 +291,8 @@ def main():
         torch.cuda.synchronize()
 
     def timed_steps(nwarm, nsteps):
-        """nwarm untimed + nsteps timed evaluations; -> (max-over-ranks seconds, last ll, last gradient)"""
+        """nwarm untimed + nsteps timed evaluations; -> (max-over-ranks seconds, last ll, last gradient, last
+        per-expert ll)"""
         for i in range(nwarm):
             step(i)
         fence()
@@ -279,17 +306,17 @@ def main():
         tm_ = torch.tensor([dt_], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
         if collective:
             dist.all_reduce(tm_, op=dist.ReduceOp.MAX)
-        return float(tm_.item()), r_[0], r_[1]
+        return float(tm_.item()), r_[0], r_[1], r_[2]
 
     first = next(iter(bcm.local.values()), None)      # None: a rank that owns no expert
     empty = {"launches": 0, "sum_ms": 0.0, "flop": 0.0, "disp_ms": 0.0}
     nanph = {"potrf": float("nan"), "kbuild": float("nan")}
 
     # ---- pass 1, timed: the default path, nothing instrumented -> `value`
-    dt, ll, g = float("nan"), float("nan"), np.full(3, np.nan)
+    dt, ll, g, per_ll = float("nan"), float("nan"), np.full(3, np.nan), np.full(K, np.nan)
     exchange = None
     if "timed" in passes:
-        dt, ll, g = timed_steps(args.warmup, args.steps)
+        dt, ll, g, per_ll = timed_steps(args.warmup, args.steps)
         # this rank's split of an evaluation on the host clock: its experts (enqueue -> rows in device memory), the
         # exchange (collective + read-back into pinned memory + synchronise), and what is left (hyper-parameter
         # update, Python) -- the record a rehearsal of one rank of an 8-GPU run is read from
@@ -309,12 +336,12 @@ def main():
         step(0)                                       # event pools, first profiled enqueue
         for kd in KINDS:
             first.kernel_stats(reset=True, kind=kd)
-        dt_prof, ll_p, g_p = timed_steps(0, args.steps)
+        dt_prof, ll_p, g_p, per_p = timed_steps(0, args.steps)
         kst = {kd: first.kernel_stats(kind=kd) for kd in KINDS}
         kb_st = first.kernel_stats(kind=10) if args.prof_level >= 5 else None
         ph = first.phase_ms()
         if "timed" not in passes:
-            dt, ll, g = dt_prof, ll_p, g_p
+            dt, ll, g, per_ll = dt_prof, ll_p, g_p, per_p
     npad = -(-args.n // 128) * 128
 
     # ---- pass 3, isolated: the same kernels with the chip to themselves.  In the other passes the inverse blocks
@@ -343,7 +370,7 @@ def main():
 
     # prediction (covkernel.cpp:277-323): 1000 test points against the resident model, factor and inverse valid
     predict = None
-    if rank == 0 and world == 1 and len(bcm.local) == 1 and not strong:
+    if args.full and rank == 0 and world == 1 and len(bcm.local) == 1 and not strong:
         Xt = synth(1000, args.d, 99)[0]
         first.set_profiling(0)
         first.set_loghyperparam(HP0)
@@ -433,35 +460,37 @@ def main():
                        else "gp_loglik_grad_N%d_D%d" % (args.n, args.d), "experts": K,
                        "experts_per_gpu": (K + world - 1) // world if strong else args.experts_per_gpu,
                        "sharding": "bcm-experts-per-gpu", "overlap": bool(args.overlap) and can_profile,
-                       "hp": HP0.tolist(), "passes": passes, "tune": args.tune or None,
+                       "hp": HP0.tolist(), "passes": passes, "full": args.full, "tune": args.tune or None,
                        "value_from": "timed pass: default path, no per-launch events" if "timed" in passes
                        else "profiled pass (no timed pass was run)"},
-            "cholesky_gflops": (npad ** 3 / 3.0) / ((iso_ph or ph)["potrf"] * 1e-3) / 1e9,   # factorisation alone (overlap off)
             "eval_tflops_n3": (float(args.n) ** 3) * (K if strong else world * args.experts_per_gpu) / world
                               / (dt / args.steps) / 1e12,
-            "phase_ms_last": {k: round(v, 4) for k, v in ph.items()},
-            "ms_per_step_profiled": (1e3 * dt_prof / args.steps) if dt_prof else None,
             "ll_last": ll, "grad_last": [float(v) for v in g],
         }
+        if args.full:
+            out["cholesky_gflops"] = (npad ** 3 / 3.0) / ((iso_ph or ph)["potrf"] * 1e-3) / 1e9   # factorisation alone (overlap off)
+            out["phase_ms_last"] = {k: round(v, 4) for k, v in ph.items()}
+            out["ms_per_step_profiled"] = (1e3 * dt_prof / args.steps) if dt_prof else None
         if exchange:
             out["exchange"] = exchange
         if predict:
             out["predict"] = predict
         out.update(subs)
+        from cugp_amd import capi as _capi
+        build_id = (_capi.lib().cugp_build_id() or b"unknown").decode()
+        out["library_build_id"] = build_id
         # HBM bytes per launch from the rocprofv3 --pmc passes of this same command, committed under profiles/
         # (tools/make_profiles.sh, tools/pmc_summary.py: 2 x FETCH_SIZE + WRITE_SIZE per launch; counters cannot be
         # read in-process, so the figure is a committed measurement).  It is only reported when it was measured on the
         # library that is loaded now: the summary carries the hash of the sources it was built from (cugp_build_id);
-        # otherwise traffic is null and traffic_source says why.
-        from cugp_amd import capi as _capi
-        build_id = (_capi.lib().cugp_build_id() or b"unknown").decode()
-        out["library_build_id"] = build_id
-        ROUND, PMC_SUMMARY, pmc = pmc_summary_for(build_id)
-        pmc_reason = None
-        if ROUND is None:
-            pmc_reason, pmc = pmc, {}
-        elif args.n != N_METRIC:
-            pmc_reason, pmc = "counter summary is of the N=%d workload" % N_METRIC, {}
+        # otherwise traffic is null and traffic_source says why.  Only the --full records carry it.
+        ROUND, PMC_SUMMARY, pmc, pmc_reason = None, None, {}, None
+        if args.full:
+            ROUND, PMC_SUMMARY, pmc = pmc_summary_for(build_id)
+            if ROUND is None:
+                pmc_reason, pmc = pmc, {}
+            elif args.n != N_METRIC:
+                pmc_reason, pmc = "counter summary is of the N=%d workload" % N_METRIC, {}
 
         def dur(st):
             # level 5: from the end of the launch in front of it on its stream (where rocprofv3 puts an in-order
@@ -540,6 +569,11 @@ def main():
                                               "the exponential): rocprofv3 --pmc SQ_INSTS_VALU ... SQ_VMEM_WR_TA_DATA_FIFO_FULL"}
         if world == 1 and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(min(args.cpu_sample, args.n), args.n, args.d)
+        if args.dump_outputs:
+            # what the caller of the measured path received from its last evaluation (the ranks agree on it)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in (("ll", [ll]), ("grad", g), ("ll_per_expert", per_ll)):
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
         sys.stdout.flush()
         os.dup2(fd_stdout, 1)
         print(json.dumps(out), flush=True)

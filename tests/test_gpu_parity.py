@@ -929,7 +929,7 @@ def test_bench_multi_rank_code_path_on_one_rank():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_PORT="29547")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-rccl", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--rehearse-rccl", "--steps", "2", "--warmup", "1",
                         "--cpu-sample", "0", "--rows", "2048"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -937,7 +937,7 @@ def test_bench_multi_rank_code_path_on_one_rank():
     assert line["roofline"]["launches_timed"] > 0 and line["roofline"]["kernel"].startswith("k_")
     # the metric workload carries BASELINE configs 5 and 4 as sub-runs through the same process group (here one rank:
     # 16 and 4 experts on this GPU), so that an N-GPU run of the driver yields the strong-scaling curve
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rehearse-rccl", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--rehearse-rccl", "--steps", "2", "--warmup", "1",
                         "--cpu-sample", "0", "--sub-steps", "2"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -7,29 +7,29 @@ O=$R/gpurun_out/profiles_$tag
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 set -x
-python3 $R/bench.py > $O/${tag}_bench_line.json 2> $O/bench.err || exit 1
+python3 $R/bench.py --full > $O/${tag}_bench_line.json 2> $O/bench.err || exit 1
 # one rocprofv3 --kernel-trace --stats run PER PASS of bench.py (timed = the default path `value` is measured on,
 # profiled = the same schedule with HIP events around the MFMA launches (what roofline* is computed from),
 # isolated = overlap off): a kernel's AverageNs in the CSV of a pass is then that pass's figure, nothing mixed
 for pass in timed profiled isolated; do
   rm -rf /tmp/prof_$pass
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$pass -- python3 $R/bench.py --passes $pass --cpu-sample 0 --sub-steps 0 > $O/${tag}_bench_${pass}_line_under_rocprof.json 2> $O/bench_$pass.err || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$pass -- python3 $R/bench.py --full --passes $pass --cpu-sample 0 --sub-steps 0 > $O/${tag}_bench_${pass}_line_under_rocprof.json 2> $O/bench_$pass.err || exit 1
   cp $(find /tmp/prof_$pass -name '*kernel_stats.csv' | head -1) $O/${tag}_bench_${pass}_n8192_kernel_stats.csv
 done
 # BASELINE config 3's shape (siproper_10000: 79 tiles, 16 rows of identity padding): the bench line and the kernel statistics of its timed pass
-python3 $R/bench.py --rows 10000 --sub-steps 0 --cpu-sample 0 --steps 10 > $O/${tag}_bench_n10000_line.json 2>> $O/bench.err
+python3 $R/bench.py --full --rows 10000 --sub-steps 0 --cpu-sample 0 --steps 10 > $O/${tag}_bench_n10000_line.json 2>> $O/bench.err
 rm -rf /tmp/prof_n10000
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_n10000 -- python3 $R/bench.py --rows 10000 --passes timed --steps 10 --cpu-sample 0 --sub-steps 0 > $O/${tag}_bench_n10000_line_under_rocprof.json 2>> $O/bench.err || exit 1
 cp $(find /tmp/prof_n10000 -name '*kernel_stats.csv' | head -1) $O/${tag}_bench_n10000_kernel_stats.csv
-python3 $R/bench.py --rows 1500 --experts-total 16 --cpu-sample 0 > $O/${tag}_bench_bcm16_line.json 2>> $O/bench.err
-python3 $R/bench.py --rows 6000 --experts-total 4 --cpu-sample 0 --steps 10 > $O/${tag}_bench_bcm4_line.json 2>> $O/bench.err
-python3 $R/bench.py --experts-per-gpu 2 --cpu-sample 0 --steps 10 > $O/${tag}_bench_2x8192_line.json 2>> $O/bench.err
+python3 $R/bench.py --full --rows 1500 --experts-total 16 --cpu-sample 0 > $O/${tag}_bench_bcm16_line.json 2>> $O/bench.err
+python3 $R/bench.py --full --rows 6000 --experts-total 4 --cpu-sample 0 --steps 10 > $O/${tag}_bench_bcm4_line.json 2>> $O/bench.err
+python3 $R/bench.py --full --experts-per-gpu 2 --cpu-sample 0 --steps 10 > $O/${tag}_bench_2x8192_line.json 2>> $O/bench.err
 # one rank of the 8-GPU BCM runs behind a real (one-rank) RCCL communicator: the library's exchange against the two
 # torch.distributed forms (device_ms / collective_ms / host time between evaluations, bench.py `exchange`)
 for form in library allgather allreduce; do
-  CUGP_BCM_EXCHANGE=$form python3 $R/bench.py --rehearse-rccl --experts-total 2 --rows 1500 --cpu-sample 0 --passes timed --steps 300 --warmup 30 2>> $O/bench.err | tail -1 > $O/${tag}_rehearse_2x1500_$form.json
-  CUGP_BCM_EXCHANGE=$form python3 $R/bench.py --rehearse-rccl --experts-total 1 --rows 6000 --cpu-sample 0 --passes timed --steps 40 --warmup 5 2>> $O/bench.err | tail -1 > $O/${tag}_rehearse_1x6000_$form.json
-  CUGP_BCM_EXCHANGE=$form python3 $R/bench.py --rehearse-rccl --cpu-sample 0 --passes timed --sub-steps 0 2>> $O/bench.err | tail -1 > $O/${tag}_rehearse_1x8192_$form.json
+  CUGP_BCM_EXCHANGE=$form python3 $R/bench.py --full --rehearse-rccl --experts-total 2 --rows 1500 --cpu-sample 0 --passes timed --steps 300 --warmup 30 2>> $O/bench.err | tail -1 > $O/${tag}_rehearse_2x1500_$form.json
+  CUGP_BCM_EXCHANGE=$form python3 $R/bench.py --full --rehearse-rccl --experts-total 1 --rows 6000 --cpu-sample 0 --passes timed --steps 40 --warmup 5 2>> $O/bench.err | tail -1 > $O/${tag}_rehearse_1x6000_$form.json
+  CUGP_BCM_EXCHANGE=$form python3 $R/bench.py --full --rehearse-rccl --cpu-sample 0 --passes timed --sub-steps 0 2>> $O/bench.err | tail -1 > $O/${tag}_rehearse_1x8192_$form.json
 done
 python3 $R/tools/la_bench.py > $O/${tag}_la_bench.txt 2>> $O/bench.err
 python3 $R/tools/ll_only_probe.py > $O/${tag}_ll_only.txt 2>> $O/bench.err
@@ -50,12 +50,12 @@ done
 # PMC passes (separate passes; counters only with --kernel-trace)
 for pass in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_LDS_BANK_CONFLICT" "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VMEM_WR SQ_VMEM_WR_TA_DATA_FIFO_FULL SQ_WAVES"; do
   t=$(echo $pass | cut -d' ' -f1)
-  rm -rf $R/gpurun_out/pmc_$t
-  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $R/gpurun_out/pmc_$t -- python3 $R/bench.py --steps 2 --warmup 1 --cpu-sample 0 --sub-steps 0 --passes timed > $R/gpurun_out/pmc_$t.log 2>&1 || echo "pass $t failed"
+  rm -rf $O/pmc_$t
+  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $O/pmc_$t -- python3 $R/bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --sub-steps 0 --passes timed > $O/pmc_$t.log 2>&1 || echo "pass $t failed"
 done
-cd $R && python3 tools/pmc_summary.py $R/gpurun_out $tag && cp profiles/${tag}_pmc_summary.json $O/
+cd $R && python3 tools/pmc_summary.py $O $tag && cp profiles/${tag}_pmc_summary.json $O/
 # HBM-side bytes of a whole evaluation (the run above holds 3 + 1 evaluations: warm-up, 2 steps, 1 in front of predict)
-python3 tools/pmc_total.py $R/gpurun_out 4 > $O/${tag}_pmc_total_traffic.txt 2>&1
+python3 tools/pmc_total.py $O 4 > $O/${tag}_pmc_total_traffic.txt 2>&1
 # per-workgroup start / end / shader-clock stamps of the chain and tile kernels (diagnostic build, see tools/wgtimes.hip)
 [ -x $R/tools/bin/wgtimes ] && $R/tools/bin/wgtimes 8192 1 > $O/${tag}_wgtimes_n8192.txt 2>&1
 [ -x $R/tools/bin/wgtimes ] && $R/tools/bin/wgtimes 1500 1 > $O/${tag}_wgtimes_n1500.txt 2>&1
