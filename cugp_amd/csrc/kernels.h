@@ -28,7 +28,7 @@ enum { TUNE_LAUUM_WM2_MAX = 0,   // K^-1 product: use 64x64 tiles when there are
        TUNE_STEP_QUARTER_MAX = 14, // step kernel: launches of at most this many 64x64 workgroups run ALL their tiles as quarters (chain-bound tail)
        TUNE_STREAM_PRIO = 15,    // read when a handle is created: bit 0 = the factorisation's stream at the highest priority, bit 1 = the inverse streams at the lowest (default 0: prioritised streams serialised grouped experts in round 3)
        TUNE_BARRIER_SPIN = 16,   // polls a workgroup of k_trtri_block spends at a stage barrier before it gives up (the evaluation then fails with CUGP_ERR_DEVICE instead of hanging); 0 = give up at once (test hook)
-       TUNE_SUBPANEL = 17,       // near window in sub-panels of this many steps (1, 2 or 4; must divide the panel): the step launch of a sub-panel's last step
+       TUNE_SUBPANEL = 17,       // near window in sub-panels of this many steps (1 to 4; must divide the panel, else 1): the step launch of a sub-panel's last step
                                  // updates the window with K = 128*this in ONE pass over its C tiles, the steps before it only the next column (left-looking inside the sub-panel)
        TUNE_ZFUSE = 18,          // LL-only evaluations: the forward substitution L z = y inside the factorisation's launches (1) or as 2 nt launches behind it (0)
        TUNE_COUNT = 19 };

@@ -288,7 +288,8 @@ def test_forward_substitution_inside_the_factorisation(gp_mod, oracle, n):
     workgroup per panel solve, nt - kb - 1 more per step launch; TUNE_ZFUSE = 1) instead of by 2 nt small launches behind
     it.  Same quadratic form and log-determinant as the launch-by-launch substitution to rounding (the diagonal blocks
     are applied as two 64x64 inverses instead of one 128x128 inverse), the same as the gradient path's z = L^-1 y, and the
-    oracle's to 1e-8.  1 tile, 2 tiles, ragged, config-5 size, many hand-over blocks, the two-speed factorisation."""
+    oracle's to 1e-8.  1 tile, 2 tiles, ragged, config-5 size, many hand-over blocks (4200 rows: 33 tiles, classic
+    schedule; the two-speed one, from 48 tiles, is tests/test_gpu_launch_paths.py's)."""
     X, y = synth(n, d=6, seed=n)
     g = gp_mod.Covsum(n, 6)
     g.set_data(X, y)

@@ -522,8 +522,8 @@ def test_gradient_continues_from_a_valid_factor(gp_mod, oracle, n):
     """compute_loglikelihood() then compute_gradient_loghyperparam() (the reference's canonical pair,
     cpp_serial_gp/covkernel.cpp:118-129 then :162-263, and every gradient probe of the evaluation-sparing CG): the
     gradient continues from the factor the value call left -- on a padded multi-tile handle (1100 rows: 9 tiles, 52
-    rows of identity padding; 4200 rows: 33 tiles, two-speed schedule, doubling levels) it must give what one
-    loglik_grad() gives, to rounding."""
+    rows of identity padding; 4200 rows: 33 tiles, classic schedule -- the two-speed one starts at 48 tiles --, doubling
+    levels) it must give what one loglik_grad() gives, to rounding."""
     X, y = synth(n, seed=n)
     hp = [np.log(3.0), 0.0, np.log(0.1)]
     a = gp_mod.Covsum(n, 10)
@@ -845,11 +845,11 @@ def test_potrf_ill_conditioned(gp_mod, oracle, n, ridge):
     assert abs(ld - ldo) <= max(1e-9 * abs(ldo), 10 * cond * 2.2e-16) and abs(q - qo) <= 100 * cond * 2.2e-16 * abs(qo)
 
 
-@pytest.mark.parametrize("n", [2049, 4200])
+@pytest.mark.parametrize("n", [2049, 4200, 6100])
 def test_results_do_not_depend_on_timing(gp_mod, n):
     """Everything a block of inverse rows does is ordered on its streams and every tile sees its updates in a fixed
-    order (classic steps below 32 tiles, near window + far passes above): the same evaluation repeated -- whatever
-    the streams' relative timing -- returns the same bits, with the inverse beside the factorisation or after it."""
+    order (classic steps below 48 tiles -- 2049 and 4200 rows --, near window + far passes from there -- 6100 rows):
+    the same evaluation repeated -- whatever the streams' relative timing -- returns the same bits."""
     X, y = synth(n, d=6, seed=n)
     hp = np.array([1.0, 0.2, -1.1])
     g = gp_mod.Covsum(n, 6)

@@ -204,7 +204,7 @@ def test_potrf_plan_covers_every_update_exactly_once_in_order():
         for near in (1, 40, 300, 500, 700, 5000):
             for nt in list(range(2, 30)) + [40, 63, 64, 79]:
                 _replay_potrf_plan(nt, P, near)
-                for S in (2, 4):                             # sub-panelled near window (tuning key 17)
+                for S in (2, 3, 4):                          # sub-panelled near window (tuning key 17)
                     _replay_potrf_plan(nt, P, near, S)
 
 
@@ -229,3 +229,41 @@ def test_cg_sparing_takes_the_default_trajectory_with_fewer_gradients(oracle, si
     assert ng == calls["g"] and ng <= tr1.shape[0]
     print("sparing CG: %d probes, %d gradients" % (tr1.shape[0], ng))
     assert ng < tr1.shape[0]                          # this run has rejected probes (f above the starting value)
+
+
+# ---------------------------------------------------------------------------------------------
+# the A/B tools' tables of launch-shape keys
+# ---------------------------------------------------------------------------------------------
+
+
+def _int_expr(node):
+    """Integer literal, possibly negated or shifted (`-1`, `1 << 20`): the forms the tables use."""
+    import ast
+    if isinstance(node, ast.Constant) and isinstance(node.value, int):
+        return node.value
+    if isinstance(node, ast.UnaryOp) and isinstance(node.op, ast.USub):
+        return -_int_expr(node.operand)
+    if isinstance(node, ast.BinOp) and isinstance(node.op, ast.LShift):
+        return _int_expr(node.left) << _int_expr(node.right)
+    raise ValueError("not an integer literal: %s" % ast.dump(node))
+
+
+def test_ab_tool_tables_hold_todays_defaults():
+    """tools/ab.py, ab2.py and bcm_ab2.py set every key of their DEFAULT table before each variant: a value that is not
+    today's default (kernels.hip g_tune_init) silently changes the baseline of every A/B run they make."""
+    import ast
+    src = open(os.path.join(ROOT, "cugp_amd", "csrc", "kernels.hip")).read()
+    m = re.search(r"g_tune_init\[TUNE_COUNT\]\s*=\s*\{([^}]*)\}", src)
+    assert m, "g_tune_init not found in kernels.hip"
+    init = [_int_expr(ast.parse(v.strip(), mode="eval").body) for v in m.group(1).split(",")]
+    count = re.search(r"TUNE_COUNT\s*=\s*(\d+)", open(os.path.join(ROOT, "cugp_amd", "csrc", "kernels.h")).read())
+    assert len(init) == int(count.group(1))
+    for tool in ("ab.py", "ab2.py", "bcm_ab2.py"):
+        tree = ast.parse(open(os.path.join(ROOT, "tools", tool)).read())
+        tables = [n.value for n in ast.walk(tree) if isinstance(n, ast.Assign) and isinstance(n.value, ast.Dict)
+                  and any(isinstance(t, ast.Name) and t.id == "DEFAULT" for t in n.targets)]
+        assert len(tables) == 1, tool
+        table = {_int_expr(k): _int_expr(v) for k, v in zip(tables[0].keys, tables[0].values)}
+        wrong = {k: (v, init[k]) for k, v in table.items() if not 0 <= k < len(init) or v != init[k]}
+        assert not wrong, (tool, "key: (table, g_tune_init)", wrong)
+    assert len(table) == len(init), "tools/bcm_ab2.py lists every key"
