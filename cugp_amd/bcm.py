@@ -76,6 +76,7 @@ class ShardedBCM:
                 e.set_data(X, y)
                 self.local[k] = e
         self.hp = np.zeros(3)
+        self.predict_form = None          # "library" / "torch": the path the last predict() took
         # host-clock seconds spent in this rank's evaluations (enqueue -> rows in place) and in the exchange
         # (staging copy, all-reduce, copy back), summed since reset_timers(): what a multi-GPU run is diagnosed from
         self.t_device = self.t_collective = 0.0
@@ -256,8 +257,16 @@ class ShardedBCM:
         return float(ll), g, out[:, 0].copy()
 
     def predict(self, Xt):
-        """Product of experts (BCM.cpp:45-83): all-reduce of per-expert precision and precision*mean."""
+        """Product of experts (BCM.cpp:45-83).  Library form (a library communicator): the whole exchange inside
+        libcugp -- batched prediction kernels, one all-gather of every rank's per-expert precision and precision*mean,
+        the product on the device (cugp_bcm_predict_allgather).  Otherwise an all-reduce of those rows through
+        torch.distributed (expert by expert; the same bits once the experts are up to date -- stale ones are evaluated
+        alone there, as a group by the library).  self.predict_form says which path ran."""
         Xt = np.ascontiguousarray(Xt, dtype=np.float64)
+        if self._comm is not None:
+            self.predict_form = "library"
+            return self._comm.predict_allgather(self._group, self._per, self.K, Xt)
+        self.predict_form = "torch"
         nt = Xt.shape[0]
         buf = np.zeros((self.K, 2, nt))
         for k in self.mine:

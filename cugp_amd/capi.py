@@ -95,6 +95,7 @@ SIGNATURES = {
     "cugp_bcm_predict_partial": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     "cugp_poe_finish": (C.c_int, [_dp, _dp, C.c_int, _dp, _dp]),
     "cugp_bcm_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
+    "cugp_bcm_predict_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "cugp_bcm_cg_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),

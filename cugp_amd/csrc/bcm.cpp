@@ -35,6 +35,7 @@ struct cugp_bcm {
     double hp[3] = {0, 0, 0};
     double* pred_host = nullptr;     // pinned: [expert][mean nt | variance nt] of the prediction in flight
     size_t pred_cap = 0;             // ... in doubles
+    std::vector<hipEvent_t> pred_ev; // cugp_bcm_predict_rows_enqueue: "rows written" per stream that wrote some
 };
 
 extern "C" {
@@ -126,6 +127,7 @@ int cugp_bcm_destroy(cugp_bcm* b)
     for (DeviceSet& ds : b->sets) cugp_group_destroy(ds.group);
     for (cugp_gp* g : b->experts) cugp_destroy(g);
     if (b->pred_host) (void)hipHostFree(b->pred_host);
+    for (hipEvent_t e : b->pred_ev) (void)hipEventDestroy(e);
     delete b;
     return CUGP_OK;
 }
@@ -392,6 +394,63 @@ int cugp_bcm_predict_partial(cugp_bcm* b, const double* Xt, int nt, double* sum_
         }
     }
     return CUGP_OK;
+}
+
+// The rows of cugp_bcm_predict_allgather (comm.cpp) for the experts of this handle, local order = global order of the
+// handle.  As cugp_bcm_predict_partial: stale experts first brought up to date by ONE evaluation of the whole model.
+// Then the experts of the device predict as ONE group of batched launches where they can, else each on its own stream
+// (the cugp_bcm_enqueue_rows_packed pattern); wait_stream is ordered behind every stream that writes rows by events.
+int cugp_bcm_predict_rows_enqueue(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend, size_t slot_stride,
+                                  void* wait_stream)
+{
+    if (!b || !Xt || nt <= 0 || !dsend || !wait_stream) return CUGP_ERR_INVALID;
+    if (b->sets.size() != 1 || b->sets[0].device != device)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_allgather: the BCM's experts are not all on the communicator's device");
+    int rc;
+    bool stale = false;
+    for (cugp_gp* e : b->experts) stale = stale || !cugp_has_inverse(e);
+    if (stale) {
+        double ll, g3[3];
+        if ((rc = cugp_bcm_loglik_grad(b, &ll, g3, nullptr))) return rc;
+    }
+    DeviceSet& ds = b->sets[0];
+    const size_t n = ds.idx.size();
+    if (hipSetDevice(device) != hipSuccess) return cugp_internal_fail(CUGP_ERR_DEVICE, "hipSetDevice");
+    auto order_after = [&](size_t slot, void* stream) -> int {
+        while (b->pred_ev.size() <= slot) {
+            hipEvent_t ev = nullptr;
+            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+                return cugp_internal_fail(CUGP_ERR_DEVICE, "hipEventCreateWithFlags");
+            b->pred_ev.push_back(ev);
+        }
+        if (hipEventRecord(b->pred_ev[slot], (hipStream_t)stream) != hipSuccess ||
+            hipStreamWaitEvent((hipStream_t)wait_stream, b->pred_ev[slot], 0) != hipSuccess)
+            return cugp_internal_fail(CUGP_ERR_DEVICE, "hipEventRecord / hipStreamWaitEvent (prediction rows)");
+        return CUGP_OK;
+    };
+    if (ds.group) {
+        void* s = nullptr;
+        rc = cugp_group_predict_enqueue(ds.group, Xt, nt, dsend, slot_stride, &s);
+        if (rc == CUGP_OK) return order_after(0, s);
+        if (rc != CUGP_ERR_INVALID) return rc;               // INVALID: not possible as a group right now
+    }
+    for (size_t i = 0; i < n; i++) {
+        void* s = nullptr;
+        if ((rc = cugp_predict_rows_enqueue(b->experts[ds.idx[i]], Xt, nt, dsend + i * slot_stride, &s))) return rc;
+        if ((rc = order_after(i, s))) return rc;
+    }
+    return CUGP_OK;
+}
+
+int cugp_bcm_predict_rows_finish(cugp_bcm* b)
+{
+    if (!b) return CUGP_ERR_INVALID;
+    int rc = CUGP_OK;
+    for (cugp_gp* e : b->experts) {
+        const int r = cugp_predict_fetch(e);
+        if (r && rc == CUGP_OK) rc = r;
+    }
+    return rc;
 }
 
 int cugp_poe_finish(const double* sum_prec, const double* sum_prec_mean, int nt, double* mean, double* var)

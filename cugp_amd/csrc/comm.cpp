@@ -13,6 +13,8 @@
 // process that has torch loaded the handle is torch's own copy of the library (same SONAME).
 #include <dlfcn.h>
 
+#include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -81,6 +83,11 @@ struct cugp_comm {
     double *dsend = nullptr, *drecv = nullptr;   // [per][4] this rank's rows, [world * per][4] everybody's
     double* hrecv = nullptr;                     // pinned copy of drecv
     int per = 0;
+    // product-of-experts prediction (cugp_bcm_predict_allgather), grow-only: this rank's block, everybody's, the reduced
+    // [mean | var | status words] on the device and pinned, the pinned header {status, local count}
+    hipStream_t stream = nullptr;                // the exchange's own stream on `device`
+    double *pdsend = nullptr, *pdrecv = nullptr, *pdout = nullptr, *phout = nullptr, *phdr = nullptr;
+    size_t pcap_send = 0, pcap_out = 0;          // doubles per rank's block, doubles of pdout
 };
 
 extern "C" {
@@ -127,6 +134,13 @@ int cugp_comm_destroy(cugp_comm* c)
     if (c->dsend) (void)hipFree(c->dsend);
     if (c->drecv) (void)hipFree(c->drecv);
     if (c->hrecv) (void)hipHostFree(c->hrecv);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->pdsend) (void)hipFree(c->pdsend);
+    if (c->pdrecv) (void)hipFree(c->pdrecv);
+    if (c->pdout) (void)hipFree(c->pdout);
+    if (c->phout) (void)hipHostFree(c->phout);
+    if (c->phdr) (void)hipHostFree(c->phdr);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return CUGP_OK;
 }
@@ -185,6 +199,129 @@ int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* r
     }
     if (rc) return rc;
     memcpy(rows_out, c->hrecv, nall * sizeof(double));
+    return CUGP_OK;
+}
+
+static int pred_buffers(cugp_comm* c, size_t rstride, size_t nout)
+{
+    hipError_t e = hipSuccess;
+    if (!c->stream) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e == hipSuccess && !c->phdr) e = hipHostMalloc((void**)&c->phdr, 2 * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess && rstride > c->pcap_send) {
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+        if (c->pdsend) (void)hipFree(c->pdsend);
+        if (c->pdrecv) (void)hipFree(c->pdrecv);
+        c->pdsend = c->pdrecv = nullptr;
+        c->pcap_send = 0;
+        e = hipMalloc((void**)&c->pdsend, rstride * sizeof(double));
+        if (e == hipSuccess && c->comm) e = hipMalloc((void**)&c->pdrecv, (size_t)c->world * rstride * sizeof(double));
+        if (e == hipSuccess) e = hipMemset(c->pdsend, 0, rstride * sizeof(double));
+        if (e == hipSuccess) c->pcap_send = rstride;
+    }
+    if (e == hipSuccess && nout > c->pcap_out) {
+        if (c->stream) (void)hipStreamSynchronize(c->stream);
+        if (c->pdout) (void)hipFree(c->pdout);
+        if (c->phout) (void)hipHostFree(c->phout);
+        c->pdout = c->phout = nullptr;
+        c->pcap_out = 0;
+        e = hipMalloc((void**)&c->pdout, nout * sizeof(double));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&c->phout, nout * sizeof(double), hipHostMallocDefault);
+        if (e == hipSuccess) c->pcap_out = nout;
+    }
+    if (e != hipSuccess) return hip_fail("prediction exchange buffers", e);
+    return CUGP_OK;
+}
+
+static void fill_nan(double* mean, double* var, int nt)
+{
+    for (int i = 0; i < nt; i++) mean[i] = var[i] = NAN;
+}
+
+// Product-of-experts prediction of a BCM sharded one process per GPU (include/cugp.h).  Every rank sends
+// {status, local expert count, [per][2][nt] rows (1/v, m/v of its i-th expert in slot i)} -- the same count on every
+// rank -- by ONE ncclAllGather on the communicator's own stream, which the prediction kernels' streams are ordered in
+// front of by events; k_poe_reduce sums every test point over the experts in global order, one copy brings mean,
+// variance and the ranks' status words into pinned memory, and the host waits ONCE.  A local failure still joins the
+// collective (nonzero status, NaN rows), so every rank reads every rank's status and all return the same code.
+int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt, double* mean,
+                               double* var)
+{
+    // what every rank detects identically from the shared arguments: no collective
+    if (!c || per <= 0 || nexperts <= 0 || nt <= 0 || !Xt || !mean || !var || (long long)per * c->world < nexperts)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_allgather: bad argument");
+    hipError_t e = hipSetDevice(c->device);
+    if (e != hipSuccess) return hip_fail("hipSetDevice", e);
+    const size_t rstride = 2 + (size_t)per * 2 * nt, nout = 2 * (size_t)nt + 2 * (size_t)c->world;
+    int rc = pred_buffers(c, rstride, nout);
+    if (rc) return rc;                                 // (no send buffer: this rank cannot take part)
+    // ---- this rank's block; from here on every failure becomes the status word
+    const int expect = c->rank < nexperts ? (nexperts - c->rank + c->world - 1) / c->world : 0;
+    int nlocal = 0, status = CUGP_OK;
+    bool enqueued = false;
+    if (b && cugp_bcm_num_experts(b, &nlocal)) status = CUGP_ERR_INVALID;
+    if (status == CUGP_OK && nlocal != expect) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: rank %d holds %d experts, %d of %d expected", c->rank,
+                 nlocal, expect, nexperts);
+        status = cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    if (status == CUGP_OK && nlocal > 0) {
+        enqueued = true;
+        status = cugp_bcm_predict_rows_enqueue(b, c->device, Xt, nt, c->pdsend + 2, 2 * (size_t)nt, c->stream);
+    }
+    if (status != CUGP_OK) {
+        if (enqueued) (void)cugp_bcm_predict_rows_finish(b);   // nothing enqueued still writes into the send buffer
+        e = hipMemsetAsync(c->pdsend + 2, 0xff, (rstride - 2) * sizeof(double), c->stream);   // all-ones: NaN rows
+        (void)e;
+    }
+    c->phdr[0] = (double)status;                       // (pinned, read by the copy below before the host waits)
+    c->phdr[1] = (double)nlocal;
+    e = hipMemcpyAsync(c->pdsend, c->phdr, 2 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess && status == CUGP_OK) status = hip_fail("hipMemcpyAsync (status word)", e);
+    // ---- the exchange
+    const double* src = c->pdsend;                     // a world of one without an id: this rank's block is all of them
+    if (c->comm) {
+        const ncclResult_t r = rccl().AllGather(c->pdsend, c->pdrecv, rstride, ncclDouble, c->comm, c->stream);
+        if (r != ncclSuccess) {
+            if (enqueued) (void)cugp_bcm_predict_rows_finish(b);
+            (void)hipStreamSynchronize(c->stream);
+            fill_nan(mean, var, nt);
+            return nccl_fail("ncclAllGather", r);
+        }
+        src = c->pdrecv;
+    }
+    rc = cugp_poe_reduce_enqueue(src, rstride, c->world, nexperts, nt, c->pdout, c->stream);
+    if (rc == CUGP_OK) {
+        e = hipMemcpyAsync(c->phout, c->pdout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) rc = hip_fail("hipMemcpyAsync (prediction)", e);
+    }
+    e = hipStreamSynchronize(c->stream);               // the one host wait: prediction, collective, reduction, copy
+    if (e != hipSuccess && rc == CUGP_OK) rc = hip_fail("hipStreamSynchronize", e);
+    if (enqueued && status == CUGP_OK) status = cugp_bcm_predict_rows_finish(b);   // (streams already done: closes them)
+    if (rc) { fill_nan(mean, var, nt); return rc; }
+    // ---- every rank reads every rank's status word: the same verdict everywhere
+    const double* h = c->phout;
+    long long total = 0;
+    for (int r = 0; r < c->world; r++) {
+        const int st = (int)h[2 * (size_t)nt + 2 * r];
+        if (st != CUGP_OK) {
+            char buf[512];
+            if (r == c->rank) snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: rank %d failed (%d): %s", r, st, cugp_last_error());
+            else snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: rank %d failed (%d)", r, st);
+            fill_nan(mean, var, nt);
+            return cugp_internal_fail(st, buf);
+        }
+        total += (long long)h[2 * (size_t)nt + 2 * r + 1];
+    }
+    if (total != nexperts) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: the ranks hold %lld experts, %d expected", total, nexperts);
+        fill_nan(mean, var, nt);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    if (status != CUGP_OK) { fill_nan(mean, var, nt); return status; }   // (a failure while closing this rank's streams)
+    memcpy(mean, h, (size_t)nt * sizeof(double));
+    memcpy(var, h + nt, (size_t)nt * sizeof(double));
     return CUGP_OK;
 }
 

@@ -1280,6 +1280,68 @@ int cugp_predict_fetch(cugp_gp* g)
     return CUGP_OK;
 }
 
+// Test points per pass of a prediction that writes product-of-experts rows (cugp_predict_rows_enqueue,
+// cugp_group_predict_enqueue): tuning key TUNE_PRED_CHUNK in 64-row tiles, or (0) as many as keep the Ks and W scratch
+// of `count` experts within 1 GiB, in whole 128-row tiles.  Every test row is computed on its own, so the bits do not
+// depend on the chunk.
+static int pred_chunk_rows(const cugp_gp* g, int count, int nt)
+{
+    long long rows = (long long)g->tune[TUNE_PRED_CHUNK] * 64;
+    if (rows <= 0) {
+        rows = (long long)((((size_t)1 << 30) / ((size_t)count * 2 * g->npad * sizeof(double))) / TILE) * TILE;
+        if (rows < TILE) rows = TILE;
+    }
+    const long long ntr = ((long long)nt + 63) / 64 * 64;
+    return (int)(rows < ntr ? rows : ntr);
+}
+
+// Fallback half of cugp_bcm_predict_allgather for an expert that cannot share launches: the expert's prediction on its
+// own stream (returned in *stream), in passes of pred_chunk_rows test points, writing 1/v to drows[0, nt) and m/v to
+// drows[nt, 2 nt) (device memory of the expert's device) instead of mean / variance.  The same kernels and arithmetic as
+// cugp_predict.  cugp_predict_fetch waits for it.
+int cugp_predict_rows_enqueue(cugp_gp* g, const double* Xt, int nt, double* drows, void** stream)
+{
+    if (!g || !Xt || nt <= 0 || !drows || !stream) return fail(CUGP_ERR_INVALID, "cugp_predict_rows_enqueue: bad argument");
+    int rc;
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // factor, T, alpha for the current hp
+    if ((rc = use_device(g))) return rc;
+    TuneScope ts(g);
+    const int chunk = pred_chunk_rows(g, 1, nt);
+    const int ntpad = ((chunk + TILE - 1) / TILE) * TILE;
+    const HyperScalars h = scalars(g);
+    const size_t nxt = (((size_t)nt * g->d + 15) / 16) * 16, nks = (size_t)ntpad * g->npad;
+    const size_t need = nxt + 2 * nks;
+    if (need > g->pred_cap) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->pred_buf) (void)hipFree(g->pred_buf);
+        g->pred_buf = nullptr;
+        g->pred_cap = 0;
+        HIPCHK(hipMalloc((void**)&g->pred_buf, need * sizeof(double)));
+        g->pred_cap = need;
+    }
+    double* dXt = g->pred_buf;
+    double* dKs = dXt + nxt;
+    double* dW = dKs + nks;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    if ((rc = reset_stamps(g))) return rc;
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int c = nt - t0 < chunk ? nt - t0 : chunk;
+        const int cpad = ((c + TILE - 1) / TILE) * TILE;
+        launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream);
+        {
+            TimedLaunch tl(g, g->stream, g->prof >= 3);
+            launch_predict_gemm(dKs, g->dT, dW, g->npad, cpad / TILE, g->nt, g->stream);
+            double kt = 0;
+            for (int ti = 0; ti < g->nt; ti++) kt += ti + 0.5;
+            tl.done(KIND_PREDICT, kt * (cpad / TILE) * 2.0 * TILE * TILE * TILE);
+        }
+        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, h, nullptr, nullptr, g->stream, drows + t0, 0, nt);
+    }
+    HIPCHK(hipGetLastError());
+    *stream = (void*)g->stream;
+    return CUGP_OK;
+}
+
 // ---------------------------------------------------------------- intermediates
 int cugp_compute_K_train(cugp_gp* g, double* K)
 {
@@ -1783,6 +1845,8 @@ struct cugp_group {
     hipGraphExec_t gexec[2] = {nullptr, nullptr};
     unsigned gepoch[2] = {0, 0};
     bool pending = false, pending_grad = false;   // an evaluation is enqueued and not yet fetched
+    double* pred_buf = nullptr;     // grouped prediction scratch (test inputs, [expert][ntpad][npad] Ks and W), grow-only
+    size_t pred_cap = 0;            // ... in doubles
 };
 
 int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
@@ -1825,7 +1889,26 @@ void cugp_group_destroy(cugp_group* gr)
     if (gr->ctx.tickets) (void)hipFree(gr->ctx.tickets);
     if (gr->ctx.dout) (void)hipFree(gr->ctx.dout);
     if (gr->ctx.hout) (void)hipHostFree(gr->ctx.hout);
+    if (gr->pred_buf) (void)hipFree(gr->pred_buf);
     delete gr;
+}
+
+// the experts' device buffers into the group's table (after a buffer was allocated)
+static int write_group_table(cugp_group* gr)
+{
+    cugp_gp* lead = gr->experts[0];
+    const int k = (int)gr->experts.size(), nt = lead->nt;
+    std::vector<ExpertPtrs> tab(k);
+    for (int i = 0; i < k; i++) {
+        cugp_gp* e = gr->experts[i];
+        tab[i] = ExpertPtrs{e->dA, e->dT, e->dU, e->dKinv, e->d16, e->d64, e->dlogdet, e->dy, e->dz, e->dalpha,
+                            e->dw, e->dpart, gr->ctx.dout + (size_t)i * 8, e->dX,
+                            gr->ctx.tickets + (size_t)i * ticket_count(nt), e->n};
+    }
+    HIPCHK(hipStreamSynchronize(lead->stream));           // a captured graph may still be reading the old table
+    HIPCHK(hipMemcpy(gr->dtab, tab.data(), tab.size() * sizeof(ExpertPtrs), hipMemcpyHostToDevice));
+    gr->tab_valid = true;
+    return CUGP_OK;
 }
 
 // Enqueue one evaluation of all experts of the group on the lead expert's stream(s); results stay on the device
@@ -1834,7 +1917,7 @@ int cugp_group_enqueue(cugp_group* gr, int want_grad)
 {
     if (!gr) return CUGP_ERR_INVALID;
     cugp_gp* lead = gr->experts[0];
-    const int k = (int)gr->experts.size(), nt = lead->nt;
+    const int nt = lead->nt;
     int rc;
     if (gr->pending) return fail(CUGP_ERR_BUSY, "cugp_group_enqueue: an evaluation is already in flight");
     TuneScope ts(lead);                                       // the group runs on the lead expert's tuning
@@ -1855,18 +1938,7 @@ int cugp_group_enqueue(cugp_group* gr, int want_grad)
     }
     if (const int pe = prepare_kernels())
         return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
-    if (!gr->tab_valid) {
-        std::vector<ExpertPtrs> tab(k);
-        for (int i = 0; i < k; i++) {
-            cugp_gp* e = gr->experts[i];
-            tab[i] = ExpertPtrs{e->dA, e->dT, e->dU, e->dKinv, e->d16, e->d64, e->dlogdet, e->dy, e->dz, e->dalpha,
-                                e->dw, e->dpart, gr->ctx.dout + (size_t)i * 8, e->dX,
-                                gr->ctx.tickets + (size_t)i * ticket_count(nt), e->n};
-        }
-        HIPCHK(hipStreamSynchronize(lead->stream));           // a captured graph may still be reading the old table
-        HIPCHK(hipMemcpy(gr->dtab, tab.data(), tab.size() * sizeof(ExpertPtrs), hipMemcpyHostToDevice));
-        gr->tab_valid = true;
-    }
+    if (!gr->tab_valid && (rc = write_group_table(gr))) return rc;
     for (cugp_gp* e : gr->experts) e->factor_valid = e->inverse_valid = false;
     *lead->hhs = scalars(lead);
     gr->ctx.overlap = lead->tune[TUNE_GROUP_OVERLAP] != 0;
@@ -1974,6 +2046,65 @@ int cugp_copy_result_row(cugp_gp* g, double* dst)
     int rc;
     if ((rc = use_device(g))) return rc;
     return cugp_copy_device_row(dst, g->dout, g->stream);
+}
+
+// The prediction of every expert of the group by ONE sequence of launches on the lead expert's stream (returned in
+// *stream): Xt copied to the device once, then per pass of pred_chunk_rows test points k_cross, k_predict_gemm and
+// k_predict_finish, each one launch for all experts (blockIdx.y = expert).  Expert i's rows go to drows + i * row_stride:
+// 1/v at [t], m/v at [nt + t].  Returns CUGP_ERR_INVALID without touching anything when the experts cannot predict as a
+// group right now (an inverse missing or stale, different hyper-parameters, profiling level >= 3): the caller then
+// enqueues them one by one (cugp_predict_rows_enqueue).
+int cugp_group_predict_enqueue(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride, void** stream)
+{
+    if (!gr || !Xt || nt <= 0 || !drows || !stream) return CUGP_ERR_INVALID;
+    cugp_gp* lead = gr->experts[0];
+    const int k = (int)gr->experts.size();
+    int rc;
+    if (gr->pending) return fail(CUGP_ERR_BUSY, "cugp_group_predict_enqueue: an evaluation is in flight");
+    for (cugp_gp* e : gr->experts) {
+        if (!cugp_has_inverse(e) || e->prof >= 3) return CUGP_ERR_INVALID;
+        if (e->hp[0] != lead->hp[0] || e->hp[1] != lead->hp[1] || e->hp[2] != lead->hp[2]) return CUGP_ERR_INVALID;
+    }
+    if ((rc = use_device(lead))) return rc;
+    TuneScope ts(lead);                                       // the group runs on the lead expert's tuning
+    if (!gr->tab_valid && (rc = write_group_table(gr))) return rc;
+    const int chunk = pred_chunk_rows(lead, k, nt);
+    const int ntpad = ((chunk + TILE - 1) / TILE) * TILE;
+    const HyperScalars h = scalars(lead);
+    const size_t nxt = (((size_t)nt * lead->d + 15) / 16) * 16, nks = (size_t)k * ntpad * lead->npad;
+    const size_t need = nxt + 2 * nks;
+    if (need > gr->pred_cap) {
+        HIPCHK(hipStreamSynchronize(lead->stream));
+        if (gr->pred_buf) (void)hipFree(gr->pred_buf);
+        gr->pred_buf = nullptr;
+        gr->pred_cap = 0;
+        HIPCHK(hipMalloc((void**)&gr->pred_buf, need * sizeof(double)));
+        gr->pred_cap = need;
+    }
+    double* dXt = gr->pred_buf;
+    double* dKs = dXt + nxt;
+    double* dW = dKs + nks;
+    const Batch bt = gr->ctx.bt;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * lead->d * sizeof(double), hipMemcpyHostToDevice, lead->stream));
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int c = nt - t0 < chunk ? nt - t0 : chunk;
+        const int cpad = ((c + TILE - 1) / TILE) * TILE;
+        launch_kcross(nullptr, 0, lead->d, lead->npad, dXt + (size_t)t0 * lead->d, c, cpad, h, dKs, lead->stream, bt);
+        launch_predict_gemm(dKs, nullptr, dW, lead->npad, cpad / TILE, lead->nt, lead->stream, bt);
+        launch_predict_finish(dKs, dW, nullptr, 0, lead->npad, c, h, nullptr, nullptr, lead->stream, drows + t0,
+                              row_stride, nt, cpad, bt);
+    }
+    HIPCHK(hipGetLastError());
+    *stream = (void*)lead->stream;
+    return CUGP_OK;
+}
+
+int cugp_poe_reduce_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, double* dout,
+                            void* stream)
+{
+    launch_poe_reduce(gathered, rstride, world, nexperts, nt, dout, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return CUGP_OK;
 }
 
 int cugp_group_eval(cugp_group* gr, int want_grad, double* ll, double* g)

@@ -42,4 +42,22 @@ int cugp_has_inverse(const cugp_gp* gp);
 // hold its inverse quantities (cugp_has_inverse), or enqueue evaluates them first like cugp_predict.
 int cugp_predict_enqueue(cugp_gp* gp, const double* Xt, int nt, double* host_mv);
 int cugp_predict_fetch(cugp_gp* gp);
+
+// ---- product-of-experts prediction across ranks (cugp_bcm_predict_allgather, comm.cpp) ----
+// Rows of the exchange, left on the device: expert i's 1/v at drows[i * row_stride + t], m/v at [i * row_stride + nt + t].
+// group: one sequence of batched launches on the lead expert's stream (*stream); CUGP_ERR_INVALID without touching anything
+// when the experts cannot predict as a group right now (the caller then enqueues them one by one)
+int cugp_group_predict_enqueue(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride, void** stream);
+// one expert on its own stream (*stream); cugp_predict_fetch waits for it
+int cugp_predict_rows_enqueue(cugp_gp* gp, const double* Xt, int nt, double* drows, void** stream);
+// the BCM's side: every local expert's rows into dsend (slot i at dsend + i * slot_stride, slots of 2 nt doubles) with
+// `wait_stream` (hipStream_t) ordered behind all of them by events -- no host wait.  Stale experts are brought up to date
+// by one cugp_bcm_loglik_grad first.  Only a BCM whose experts are on `device` (else CUGP_ERR_INVALID).
+int cugp_bcm_predict_rows_enqueue(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend, size_t slot_stride,
+                                  void* wait_stream);
+// waits for every local expert's stream (after the rows were used, or after a failed enqueue)
+int cugp_bcm_predict_rows_finish(cugp_bcm* b);
+// k_poe_reduce on `stream`: gathered [world][rstride] -> dout [mean nt | var nt | world x {status, count}]
+int cugp_poe_reduce_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, double* dout,
+                            void* stream);
 }  // extern "C"

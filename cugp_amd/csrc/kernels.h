@@ -31,7 +31,9 @@ enum { TUNE_LAUUM_WM2_MAX = 0,   // K^-1 product: use 64x64 tiles when there are
        TUNE_SUBPANEL = 17,       // near window in sub-panels of this many steps (1 to 4; must divide the panel, else 1): the step launch of a sub-panel's last step
                                  // updates the window with K = 128*this in ONE pass over its C tiles, the steps before it only the next column (left-looking inside the sub-panel)
        TUNE_ZFUSE = 18,          // LL-only evaluations: the forward substitution L z = y inside the factorisation's launches (1) or as 2 nt launches behind it (0)
-       TUNE_COUNT = 19 };
+       TUNE_PRED_CHUNK = 19,     // grouped prediction (cugp_group_predict_enqueue): test points per pass, in 64-row tiles; 0 = as many as keep the
+                                 // passes' cross-covariance and product scratch within 1 GiB per group (the bits do not depend on it)
+       TUNE_COUNT = 20 };
 extern const int g_tune_init[TUNE_COUNT];     // built-in defaults
 extern thread_local const int* t_tune;        // the tuning the launchers on this thread read (a handle's copy, or the built-in defaults)
 inline int tune(int key) { return t_tune[key]; }
@@ -67,8 +69,9 @@ void launch_kbuild(const double* X, int n, int d, int npad, HyperScalars h, doub
 // S[i][j] = |x_i - x_j|^2 / c, zero diagonal, full symmetric (N2, covkernel.cpp:130-157)
 void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S, hipStream_t s);
 // Ks[t][i] = sf2 * exp(-0.5*|x_i - xt_t|^2 / l^2), row-major nt_pad x npad (pad = 0)   (N12)
+// bt (batched): blockIdx.y = expert, X and n from the table, Ks[expert][ntpad][npad]
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
-                   HyperScalars h, double* Ks, hipStream_t s);
+                   HyperScalars h, double* Ks, hipStream_t s, Batch bt = {});
 
 // ---- blocked right-looking Cholesky (N4) on the lower triangle of A (npad x npad, ld = npad) ----
 // d16: 16x16 diagonal inverses [nt][8][256]; d64: the two 64x64 diagonal inverses of each block [nt][2][4096]
@@ -118,9 +121,18 @@ int launch_lauum(const double* U, double* Kinv, int ld, int a, int w, hipStream_
 
 // ---- prediction products ----
 // W[t][i] = sum_{k<=i} Ks[t][k] T[i][k]   (nt_pad x npad, row-major)
-void launch_predict_gemm(const double* Ks, const double* T, double* W, int ld, int ntt, int nt, hipStream_t s);
+// batched: blockIdx.y = expert, T from the table, Ks and W [expert][ntt * 128][ld]; every expert's tiles sum the same k
+// range in the same order as its single launch, so each expert's bits are those of cugp_predict
+void launch_predict_gemm(const double* Ks, const double* T, double* W, int ld, int ntt, int nt, hipStream_t s,
+                         Batch bt = {});
+// mean / var (may be null) and, when rows is given, the product-of-experts exchange rows: 1/var at rows[t], mean/var at
+// rows[rhalf + t] (batched: expert e's at rows + e * rstride; alpha from the table, Ks and W [expert][ntpad][npad])
 void launch_predict_finish(const double* Ks, const double* W, const double* alpha, int n, int npad, int ntest,
-                           HyperScalars h, double* mean, double* var, hipStream_t s);
+                           HyperScalars h, double* mean, double* var, hipStream_t s, double* rows = nullptr,
+                           size_t rstride = 0, int rhalf = 0, int ntpad = 0, Batch bt = {});
+// product of experts over a gathered exchange buffer ([world][rstride]: {status, count, [per][2][nt]}): out = [mean nt |
+// var nt | world x {status, count}], experts summed in global order (expert k = rank k mod world's slot k / world)
+void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s);
 
 // ---- vector kernels ----
 void launch_trmv_lower(const double* T, int ld, int npad, const double* x, double* z, hipStream_t s,

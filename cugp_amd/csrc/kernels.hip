@@ -592,11 +592,16 @@ __global__ __launch_bounds__(256, 2) void k_trtri_border(const double* __restric
 // first): every workgroup does K = (n64 + 1) * 64 in all, 1024 equal workgroups, four per CU.  The same per-element
 // sums in the same order (the k range of a tile ends at its own diagonal; what the 128-tile form added beyond it were
 // exact zeros of T): bit-identical results.
+// bt (batched): blockIdx.y selects the expert -- T from its table entry, Ks and W its [ntt64 * 64][ld] slices
 __global__ __launch_bounds__(256, 2) void k_predict_gemm(const double* __restrict__ Ks, const double* __restrict__ T,
                                                          double* __restrict__ W, int ld, int ntt64, int n64,
-                                                         unsigned long long* stamp)
+                                                         unsigned long long* stamp, const ExpertPtrs* __restrict__ bt)
 {
     LaunchStamp stamp_(stamp);
+    if (bt) {
+        const size_t off = (size_t)blockIdx.y * ntt64 * 64 * ld;
+        T = GP(bt[blockIdx.y].T); Ks += off; W += off;
+    }
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tt = blockIdx.x % ntt64, p = blockIdx.x / ntt64;
 #pragma unroll 1
@@ -999,10 +1004,15 @@ __global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int
 }
 
 // Ks[t][i] = sf2 * exp(-0.5 |xt_t - x_i|^2 / l^2) (no noise, covkernel.cpp:105-116); zero padding
+// bt (batched): blockIdx.y selects the expert -- X, n from its table entry, Ks = the expert's [ntpad][npad] slice
 __global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int n, int d, int npad,
                                                const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h,
-                                               double* __restrict__ Ks)
+                                               double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
 {
+    if (bt) {
+        X = GP(bt[blockIdx.y].X); n = bt[blockIdx.y].n;
+        Ks += (size_t)blockIdx.y * ntpad * npad;
+    }
     __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
     const int tiles_i = npad / KT;
     const int tt = blockIdx.x / tiles_i, ti = blockIdx.x % tiles_i;
@@ -2315,14 +2325,34 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize(const double* __restri
     finalize_sums<FIN_THREADS, false>(z, npad, n, logdet_part, nt, part, nblocks, h, out, hout, red);
 }
 
+// one expert's row of the product-of-experts exchange (BCM.cpp:51-55): 1/v and (1/v) m, rounded separately as the host
+// loop of cugp_bcm_predict_partial does (IEEE division, no contraction)
+__device__ __forceinline__ void poe_row(double m, double v, double* __restrict__ p, double* __restrict__ pm)
+{
+#pragma clang fp contract(off)
+    const double inv = 1.0 / v;
+    *p = inv;
+    *pm = inv * m;
+}
+
 // mean[t] = Ks[t] . alpha ; var[t] = sf2 + sn2 - |W[t]|^2        covkernel.cpp:314-319
+// mean / var may be null; rows (when given): 1/var[t] -> rows[t], mean[t]/var[t] -> rows[rhalf + t] (poe_row).
+// bt (batched): blockIdx.y selects the expert -- alpha from its table entry, Ks and W its [ntpad][npad] slices,
+// rows + blockIdx.y * rstride its rows
 __global__ __launch_bounds__(256) void k_predict_finish(const double* __restrict__ Ks, const double* __restrict__ W,
                                                         const double* __restrict__ alpha, int n, int npad,
                                                         int ntest, HyperScalars h, double* __restrict__ mean,
-                                                        double* __restrict__ var)
+                                                        double* __restrict__ var, double* __restrict__ rows,
+                                                        size_t rstride, int rhalf, int ntpad,
+                                                        const ExpertPtrs* __restrict__ bt)
 {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= ntest) return;
+    if (bt) {
+        const size_t off = (size_t)blockIdx.y * ntpad * npad;
+        alpha = GP(bt[blockIdx.y].alpha); Ks += off; W += off;
+        rows += (size_t)blockIdx.y * rstride;
+    }
     const double* kr = Ks + (size_t)row * npad;
     const double* wr = W + (size_t)row * npad;
     double m = 0.0, q = 0.0;
@@ -2332,7 +2362,38 @@ __global__ __launch_bounds__(256) void k_predict_finish(const double* __restrict
         q += wv[0] * wv[0] + wv[1] * wv[1];
     }
     m = wave_sum(m); q = wave_sum(q);
-    if (lane == 0) { mean[row] = m; var[row] = h.signal_var + h.noise_var - q; }
+    if (lane == 0) {
+        const double v = h.signal_var + h.noise_var - q;
+        if (mean) { mean[row] = m; var[row] = v; }
+        if (rows) poe_row(m, v, rows + row, rows + rhalf + row);
+    }
+}
+
+// Product of experts over the gathered exchange buffer (comm.cpp: cugp_bcm_predict_allgather).  g: [world][rstride]
+// doubles, rank r's block = {status, local expert count, [per][2][nt] rows: 1/v, m/v}.  Test point t sums over the
+// experts k = 0..K-1 in GLOBAL order -- expert k is rank k mod world's (k / world)-th -- then var = 1/sum, mean =
+// var * sum (BCM.cpp:51-60), the same operations in the same order as cugp_bcm_predict_partial + cugp_poe_finish.
+// out: [mean nt | var nt | world x {status, count}].
+__global__ __launch_bounds__(256) void k_poe_reduce(const double* __restrict__ g, size_t rstride, int world, int K,
+                                                    int nt, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x == 0)
+        for (int r = threadIdx.x; r < world; r += 256) {
+            out[2 * (size_t)nt + 2 * r] = g[(size_t)r * rstride];
+            out[2 * (size_t)nt + 2 * r + 1] = g[(size_t)r * rstride + 1];
+        }
+    if (t >= nt) return;
+    double sp = 0.0, spm = 0.0;
+    for (int k = 0; k < K; k++) {
+        const double* b = g + (size_t)(k % world) * rstride + 2 + (size_t)(k / world) * 2 * nt;
+        sp = sp + b[t];
+        spm = spm + b[nt + t];
+    }
+    const double tv = 1.0 / sp;
+    out[t] = tv * spm;
+    out[nt + t] = tv;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2360,7 +2421,7 @@ static inline unsigned long long* take_stamp() { unsigned long long* p = t_stamp
         }                                                                                           \
     } while (0)
 
-const int g_tune_init[TUNE_COUNT] = {768, 1200, 384, -1, 511, 1, 1, 1 << 20, 16, 500, 32, 1, 2100, 256, 1536, 0, 1 << 21, 1, 1};   // defaults chosen by interleaved A/B runs (tools/ab.py)
+const int g_tune_init[TUNE_COUNT] = {768, 1200, 384, -1, 511, 1, 1, 1 << 20, 16, 500, 32, 1, 2100, 256, 1536, 0, 1 << 21, 1, 1, 0};   // defaults chosen by interleaved A/B runs (tools/ab.py)
 thread_local const int* t_tune = g_tune_init;
 
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
@@ -2381,10 +2442,10 @@ void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S,
 }
 
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad, HyperScalars h,
-                   double* Ks, hipStream_t s)
+                   double* Ks, hipStream_t s, Batch bt)
 {
-    hipLaunchKernelGGL(k_cross, dim3((ntpad / KT) * (npad / KT)), dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, h,
-                       Ks);
+    hipLaunchKernelGGL(k_cross, dim3((ntpad / KT) * (npad / KT), bt.count), dim3(256), 0, s, X, n, d, npad, Xt, nt,
+                       ntpad, h, Ks, bt.tab);
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
@@ -2585,18 +2646,26 @@ int launch_lauum(const double* U, double* Kinv, int ld, int a, int w, hipStream_
     }
 }
 
-void launch_predict_gemm(const double* Ks, const double* T, double* W, int ld, int ntt, int nt, hipStream_t s)
+void launch_predict_gemm(const double* Ks, const double* T, double* W, int ld, int ntt, int nt, hipStream_t s,
+                         Batch bt)
 {
     set_big_lds();
     // (ntt, nt in 128-row tiles; the kernel works on 64-row tiles in pairs)
-    CUGP_LAUNCH(k_predict_gemm, dim3(2 * ntt * nt), dim3(256), Geo<2>::LDS, s, Ks, T, W, ld, 2 * ntt, 2 * nt, take_stamp());
+    CUGP_LAUNCH(k_predict_gemm, dim3(2 * ntt * nt, bt.count), dim3(256), Geo<2>::LDS, s, Ks, T, W, ld, 2 * ntt, 2 * nt,
+                take_stamp(), bt.tab);
 }
 
 void launch_predict_finish(const double* Ks, const double* W, const double* alpha, int n, int npad, int ntest,
-                           HyperScalars h, double* mean, double* var, hipStream_t s)
+                           HyperScalars h, double* mean, double* var, hipStream_t s, double* rows, size_t rstride,
+                           int rhalf, int ntpad, Batch bt)
 {
-    hipLaunchKernelGGL(k_predict_finish, dim3((ntest + 3) / 4), dim3(256), 0, s, Ks, W, alpha, n, npad, ntest, h,
-                       mean, var);
+    hipLaunchKernelGGL(k_predict_finish, dim3((ntest + 3) / 4, bt.count), dim3(256), 0, s, Ks, W, alpha, n, npad,
+                       ntest, h, mean, var, rows, rstride, rhalf, ntpad, bt.tab);
+}
+
+void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_poe_reduce, dim3((nt + 255) / 256), dim3(256), 0, s, g, rstride, world, K, nt, out);
 }
 
 void launch_trmv_lower(const double* T, int ld, int npad, const double* x, double* z, hipStream_t s, Batch bt)

@@ -245,6 +245,17 @@ class Comm:
         check(capi.lib().cugp_bcm_loglik_grad_allgather(bcm._h if bcm is not None else None, self._h, int(per), ptr(out)))
         return out
 
+    def predict_allgather(self, bcm, per, nexperts, Xt):
+        """Product-of-experts prediction across the ranks (cugp_bcm_predict_allgather): this rank's experts (`bcm`, or
+        None on a rank that owns none) predict Xt, one all-gather moves every rank's rows, the product of experts over
+        all `nexperts` experts in expert order -> (mean, var).  Every rank passes the same per, nexperts and Xt."""
+        Xt = f64(Xt)
+        nt = Xt.shape[0]
+        m, v = np.empty(nt), np.empty(nt)
+        check(capi.lib().cugp_bcm_predict_allgather(bcm._h if bcm is not None else None, self._h, int(per),
+                                                    int(nexperts), ptr(Xt), nt, ptr(m), ptr(v)))
+        return m, v
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             capi.lib().cugp_comm_destroy(self._h)

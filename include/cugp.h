@@ -219,6 +219,27 @@ int cugp_bcm_loglik_grad_allgather(cugp_bcm *b, cugp_comm *c, int per, double *r
 int cugp_bcm_predict_partial(cugp_bcm *b, const double *Xt, int nt, double *sum_prec, double *sum_prec_mean);
 int cugp_poe_finish(const double *sum_prec, const double *sum_prec_mean, int nt, double *mean, double *var);
 int cugp_bcm_predict(cugp_bcm *b, const double *Xt, int nt, double *mean, double *var); /* BCM.cpp:64-83 */
+/* cugp_bcm_predict_allgather: product-of-experts prediction of a BCM sharded one process per GPU --
+ * distributed_gp/BCM.cpp:45-83 (sum_k 1/v_k and sum_k mu_k/v_k in expert order k = 0..nexperts-1, then v = 1/sum,
+ * mu = v * sum) across ranks; the reference never runs it multi-process (cuda_scalingdist/main.cpp:309 comments its
+ * testing_phase out).  b: this rank's experts (global experts rank, rank + W, ... in that order; NULL on a rank that
+ * owns none), all on c's device.  Every rank predicts its experts (one group of batched launches where their shapes
+ * allow it; stale experts first brought up to date by one evaluation) and sends {status, local expert count,
+ * [per][2][nt] rows} by ONE ncclAllGather on a stream the communicator owns; the product of experts is taken on the
+ * device and copied to mean[nt], var[nt] with one host wait.  Bit-identical to cugp_bcm_predict over the same experts in
+ * one process.  A world of one without an id: no RCCL.
+ * Callers MUST pass the same per, nexperts, nt and Xt on every rank: the library cannot check that without a collective.
+ * Errors:
+ *  - c NULL, nt <= 0, Xt / mean / var NULL, per <= 0, nexperts <= 0 or per * world < nexperts: CUGP_ERR_INVALID on
+ *    every rank alike, before any collective;
+ *  - every other failure of a rank (a local expert count that is not ceil((nexperts - rank) / world), a BCM on another
+ *    device, an evaluation or HIP error) still joins the collective with a nonzero status word and NaN rows; every rank
+ *    reads every rank's status word and the sum of the local counts, and ALL ranks return the same code (the first
+ *    failing rank's), with mean / var set to NaN and cugp_last_error naming the failing rank;
+ *  - only a failure to allocate the exchange buffers themselves (first call, or a larger nt / per) returns at once,
+ *    without joining the collective. */
+int cugp_bcm_predict_allgather(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt,
+                               double *mean, double *var);
 int cugp_bcm_cg_solve(cugp_bcm *b, int budget, double *trace, int trace_cap, int *nevals);
 
 /* ---- test / bench hooks ---- */
