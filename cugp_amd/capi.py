@@ -52,6 +52,8 @@ SIGNATURES = {
     "cugp_loglik_grad_fetch": (C.c_int, [C.c_void_p, _dp, _dp]),
     "cugp_last_quad_logdet": (C.c_int, [C.c_void_p, _dp, _dp]),
     "cugp_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
+    "cugp_predict_cov": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_predict_sample": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp]),
     "cugp_nlpp": (C.c_int, [_dp, _dp, _dp, C.c_int, _dp]),
     "cugp_compute_K_train": (C.c_int, [C.c_void_p, _dp]),
     "cugp_compute_squared_dist": (C.c_int, [C.c_void_p, C.c_double, _dp]),

@@ -55,7 +55,8 @@ constexpr int PROF_STRIDE = 16; // profiling level 2 times every 16th step launc
                                 // level 3 times EVERY launch of the MFMA kernels (bench.py's profiled pass: averages comparable with rocprofv3's)
 // kinds of timed launches (cugp_get_kernel_stats_kind): the kernels as rocprofv3 names them
 enum { KIND_STEP = 0, KIND_WIDE = 1, KIND_BORDER4 = 2, KIND_BORDER2 = 3, KIND_LAUUM4 = 4, KIND_LAUUM2 = 5,
-       KIND_LEVEL4 = 6, KIND_LEVEL2 = 7, KIND_BLOCK = 8, KIND_PREDICT = 9, KIND_BUILD = 10, KIND_TRSM = 11, KIND_COUNT = 12 };
+       KIND_LEVEL4 = 6, KIND_LEVEL2 = 7, KIND_BLOCK = 8, KIND_PREDICT = 9, KIND_BUILD = 10, KIND_TRSM = 11, KIND_COV = 12,
+       KIND_COUNT = 13 };
 
 // One hardware queue per stream up to 16 (the runtime default is 4): the experts of a BCM on one device each
 // drive their own stream, and 16 experts on 4 queues serialise (5.8 ms vs 4.6 ms per evaluation of 16 x 1500
@@ -135,6 +136,14 @@ struct cugp_gp {
     long long kst_launches[KIND_COUNT] = {};
     std::vector<int> kev_prev;     // level 5, per pair: the pair of the launch directly in front of it on the same stream, or -1
     int last_main = -1;            // ... the main stream's latest timed launch while the factorisation is being enqueued
+    // joint predictive covariance (cugp_predict_cov / cugp_predict_sample), all created on first use
+    cugp_gp* cov_f = nullptr;      // factor handle: its A receives Sigma (ld = its npad), its own stream factors it
+    int cov_tiles = 0;             // ... tile rows it was created for (it serves any smaller count)
+    hipEvent_t cov_ev = nullptr;   // "Sigma written" (this handle's stream -> cov_f's)
+    double* cov_scr = nullptr;     // split-k partial products of k_predict_cov, grow-only ...
+    size_t cov_scr_cap = 0;        // ... in doubles
+    double* samp_buf = nullptr;    // draws: normals Z, F = Z C^T (both [ns pad][ntpad]), packed samples, grow-only ...
+    size_t samp_cap = 0;           // ... in doubles
 };
 
 namespace {
@@ -1042,6 +1051,10 @@ int cugp_destroy(cugp_gp* g)
     if (g->aux) (void)hipStreamSynchronize(g->aux);
     if (g->aux2) (void)hipStreamSynchronize(g->aux2);
     if (g->lq) (void)hipStreamSynchronize(g->lq);
+    if (g->cov_f) (void)cugp_destroy(g->cov_f);           // (synchronises its own stream first)
+    if (g->cov_ev) (void)hipEventDestroy(g->cov_ev);
+    if (g->cov_scr) (void)hipFree(g->cov_scr);
+    if (g->samp_buf) (void)hipFree(g->samp_buf);
     double* bufs[] = {g->dX, g->dy, g->dA, g->dT, g->dU, g->dKinv, g->dz, g->dalpha, g->dw, g->d16, g->dlogdet,
                       g->dpart, g->dout, g->d64};
     for (double* p : bufs)
@@ -1193,8 +1206,9 @@ int cugp_nlpp(const double* actual, const double* mean, const double* var, int n
     return CUGP_OK;
 }
 
+// dxt_out / dw_out (when given): the test inputs and W = Ks L^-T on the device (the joint covariance reads them)
 static int predict_device(cugp_gp* g, const double* Xt, int nt, double** dmean_out, double** dvar_out,
-                          std::vector<double*>& to_free)
+                          std::vector<double*>& to_free, double** dxt_out = nullptr, double** dw_out = nullptr)
 {
     int rc;
     if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // factor, T, alpha for the current hp
@@ -1235,6 +1249,8 @@ static int predict_device(cugp_gp* g, const double* Xt, int nt, double** dmean_o
     HIPCHK(hipGetLastError());
     *dmean_out = dm;
     *dvar_out = dv;
+    if (dxt_out) *dxt_out = dXt;
+    if (dw_out) *dw_out = dW;
     return CUGP_OK;
 }
 
@@ -1339,6 +1355,150 @@ int cugp_predict_rows_enqueue(cugp_gp* g, const double* Xt, int nt, double* drow
     }
     HIPCHK(hipGetLastError());
     *stream = (void*)g->stream;
+    return CUGP_OK;
+}
+
+// ---------------------------------------------------------------- joint predictive distribution
+// The shared half of cugp_predict_cov and cugp_predict_sample: the marginal prediction (predict_device: the same launches
+// as cugp_predict, a stale handle re-evaluated first), then on the handle's stream
+//   Sigma = k(Xt,Xt) (+ sn2 I) + jitter I - W W^T,   W = Ks L^-T
+// into the lower tiles of the factor handle's A (k_predict_cov: the product, split over k when the tiles are few;
+// k_predict_cov_finish: the kernel function and the fixed-order sum of the chunks; it also zeroes the factor handle's
+// arrival tickets).  *fout: the factor handle (nt test points as its rows), *dmean: the device mean.
+static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_noise, double jitter, double** dmean,
+                              cugp_gp** fout)
+{
+    std::vector<double*> tmp;
+    double *dm = nullptr, *dv = nullptr, *dXt = nullptr, *dW = nullptr;
+    int rc;
+    if ((rc = predict_device(g, Xt, nt, &dm, &dv, tmp, &dXt, &dW))) return rc;
+    TuneScope ts(g);
+    const int tiles = (nt + TILE - 1) / TILE, ntpad = tiles * TILE;
+    if (!g->cov_f || g->cov_tiles < tiles) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->cov_f) (void)cugp_destroy(g->cov_f);
+        g->cov_f = nullptr;
+        g->cov_tiles = 0;
+        cugp_gp* f = nullptr;
+        if ((rc = cugp_create(nt, 1, g->device, &f))) return rc;
+        // it never builds an inverse, so it launches no barrier grid: it takes no part in the device's budget of them
+        g_live[f->device < 64 ? f->device : 63].fetch_sub(1, std::memory_order_relaxed);
+        f->counted = false;
+        f->overlap = false;
+        if ((rc = ensure_factor_bufs(f))) { cugp_destroy(f); return rc; }
+        g->cov_f = f;
+        g->cov_tiles = tiles;
+        if ((rc = use_device(g))) return rc;
+    }
+    if (!g->cov_ev) HIPCHK(hipEventCreateWithFlags(&g->cov_ev, hipEventDisableTiming));
+    cugp_gp* f = g->cov_f;
+    f->n = nt;                                                       // (a smaller problem in the handle's buffers)
+    f->nt = tiles;
+    f->npad = ntpad;
+    const CovShape cs = predict_cov_shape(ntpad, g->n);
+    const size_t need = (size_t)(cs.split - 1) * ntpad * ntpad;
+    if (need > g->cov_scr_cap) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->cov_scr) (void)hipFree(g->cov_scr);
+        g->cov_scr = nullptr;
+        g->cov_scr_cap = 0;
+        HIPCHK(hipMalloc((void**)&g->cov_scr, need * sizeof(double)));
+        g->cov_scr_cap = need;
+    }
+    {
+        TimedLaunch tl(g, g->stream, g->prof >= 3);
+        launch_predict_cov(dW, g->npad, ntpad, cs, f->dA, g->cov_scr, g->stream);
+        tl.done(KIND_COV, 2.0 * cs.tiles * (32.0 * cs.wm) * (32.0 * cs.wm) * cs.kend);
+    }
+    launch_predict_cov_finish(dXt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr, cs.split - 1,
+                              f->dtickets, g->stream);
+    HIPCHK(hipGetLastError());
+    *dmean = dm;
+    *fout = f;
+    return CUGP_OK;
+}
+
+int cugp_predict_cov(cugp_gp* g, const double* Xt, int nt, int with_noise, double* mean, double* cov)
+{
+    if (!g || !Xt || !cov || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict_cov: bad argument");
+    double* dm = nullptr;
+    cugp_gp* f = nullptr;
+    int rc = predict_cov_device(g, Xt, nt, with_noise != 0, 0.0, &dm, &f);
+    if (rc) { (void)hipStreamSynchronize(g->stream); return rc; }
+    hipError_t e = hipSuccess;
+    if (mean) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(cov, (size_t)nt * sizeof(double), f->dA, (size_t)f->npad * sizeof(double),
+                             (size_t)nt * sizeof(double), nt, hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(g->stream); return fail(CUGP_ERR_DEVICE, "cugp_predict_cov copy", e); }
+    if (g->prof >= 2) drain_kernel_events(g);
+    for (int i = 0; i < nt; i++)                                     // lower triangle, mirrored (cugp_get_K_inverse)
+        for (int j = i + 1; j < nt; j++) cov[(size_t)i * nt + j] = cov[(size_t)j * nt + i];
+    return CUGP_OK;
+}
+
+int cugp_predict_cov_device(cugp_gp* g, const double* Xt, int nt, int with_noise, const double** dcov, int* ld)
+{
+    if (!g || !Xt || !dcov || !ld || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict_cov_device: bad argument");
+    double* dm = nullptr;
+    cugp_gp* f = nullptr;
+    int rc = predict_cov_device(g, Xt, nt, with_noise != 0, 0.0, &dm, &f);
+    const hipError_t e = hipStreamSynchronize(g->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(CUGP_ERR_DEVICE, "cugp_predict_cov_device", e);
+    if (g->prof >= 2) drain_kernel_events(g);
+    *dcov = f->dA;
+    *ld = f->npad;
+    return CUGP_OK;
+}
+
+int cugp_predict_sample(cugp_gp* g, const double* Xt, int nt, int with_noise, double jitter, int nsamples,
+                        const double* normals, double* samples)
+{
+    if (!g || !Xt || !normals || !samples || nt <= 0 || nsamples <= 0 || !std::isfinite(jitter) || !(jitter >= 0.0))
+        return fail(CUGP_ERR_INVALID, "cugp_predict_sample: bad argument");
+    double* dm = nullptr;
+    cugp_gp* f = nullptr;
+    int rc = predict_cov_device(g, Xt, nt, with_noise != 0, jitter, &dm, &f);
+    if (rc) { (void)hipStreamSynchronize(g->stream); return rc; }
+    const int ntpad = f->npad, nspad = (nsamples + TILE - 1) / TILE * TILE;
+    const size_t nz = (size_t)nspad * ntpad, need = 2 * nz + (size_t)nsamples * nt;
+    if (need > g->samp_cap) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->samp_buf) (void)hipFree(g->samp_buf);
+        g->samp_buf = nullptr;
+        g->samp_cap = 0;
+        HIPCHK(hipMalloc((void**)&g->samp_buf, need * sizeof(double)));
+        g->samp_cap = need;
+    }
+    double* dZ = g->samp_buf;
+    double* dF = dZ + nz;
+    double* dS = dF + nz;
+    // the factor handle's stream goes on behind Sigma (an event, no host wait): C = chol(Sigma), F = Z C^T, + mean
+    HIPCHK(hipEventRecord(g->cov_ev, g->stream));
+    hipStream_t fs = f->stream;
+    HIPCHK(hipStreamWaitEvent(fs, g->cov_ev, 0));
+    {
+        TuneScope tf(f);
+        if ((rc = enqueue_potrf(f, false, false, f->dtickets))) { (void)hipStreamSynchronize(fs); return rc; }
+    }
+    launch_zero_upper_diag(f->dA, ntpad, f->nt, fs);
+    HIPCHK(hipMemsetAsync(dZ, 0, nz * sizeof(double), fs));
+    HIPCHK(hipMemcpy2DAsync(dZ, (size_t)ntpad * sizeof(double), normals, (size_t)nt * sizeof(double),
+                            (size_t)nt * sizeof(double), nsamples, hipMemcpyHostToDevice, fs));
+    launch_predict_gemm(dZ, f->dA, dF, ntpad, nspad / TILE, f->nt, fs);     // F[s][t] = sum_{k <= t} Z[s][k] C[t][k]
+    launch_sample_finish(dF, ntpad, dm, nt, nsamples, dS, fs);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(samples, dS, (size_t)nsamples * nt * sizeof(double), hipMemcpyDeviceToHost, fs);
+    if (e == hipSuccess) e = hipStreamSynchronize(fs);                     // (behind everything of g->stream too)
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(fs);
+        (void)hipStreamSynchronize(g->stream);
+        return fail(CUGP_ERR_DEVICE, "cugp_predict_sample", e);
+    }
+    if (g->prof >= 2) drain_kernel_events(g);
     return CUGP_OK;
 }
 

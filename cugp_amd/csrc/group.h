@@ -34,6 +34,10 @@ int cugp_bcm_finish_rows(cugp_bcm* b);
 // device copy of a single expert's result row ([8] doubles, valid once its stream -- cugp_get_stream -- has run)
 const double* cugp_result_row_device(cugp_gp* gp);
 int cugp_copy_result_row(cugp_gp* gp, double* dst);
+// cugp_predict_cov without the copy to the host (tools/pred_joint_probe.py times the device part with it): Sigma is
+// computed, the handle's stream is waited for, and *dcov / *ld give the device matrix (lower tiles valid, row-major,
+// leading dimension *ld), which stays valid until the next joint call on the handle
+int cugp_predict_cov_device(cugp_gp* gp, const double* Xt, int nt, int with_noise, const double** dcov, int* ld);
 // the handle holds L^-1, K^-1, alpha for its current data and hyper-parameters (what a prediction needs)
 int cugp_has_inverse(const cugp_gp* gp);
 // prediction in two halves, so that the experts of a BCM are all in flight before the first result is read: enqueue

@@ -33,7 +33,10 @@ enum { TUNE_LAUUM_WM2_MAX = 0,   // K^-1 product: use 64x64 tiles when there are
        TUNE_ZFUSE = 18,          // LL-only evaluations: the forward substitution L z = y inside the factorisation's launches (1) or as 2 nt launches behind it (0)
        TUNE_PRED_CHUNK = 19,     // grouped prediction (cugp_group_predict_enqueue): test points per pass, in 64-row tiles; 0 = as many as keep the
                                  // passes' cross-covariance and product scratch within 1 GiB per group (the bits do not depend on it)
-       TUNE_COUNT = 20 };
+       TUNE_COV_SPLIT = 20,      // joint predictive covariance (k_predict_cov): 64x64 workgroup slots the launch aims to fill by splitting each
+                                 // output tile's k range (128x128 workgroups count as two); 64x64 output tiles while the lower 128-tiles
+                                 // are at most a quarter of it; 0 = 128x128 tiles, no split
+       TUNE_COUNT = 21 };
 extern const int g_tune_init[TUNE_COUNT];     // built-in defaults
 extern thread_local const int* t_tune;        // the tuning the launchers on this thread read (a handle's copy, or the built-in defaults)
 inline int tune(int key) { return t_tune[key]; }
@@ -125,6 +128,21 @@ int launch_lauum(const double* U, double* Kinv, int ld, int a, int w, hipStream_
 // range in the same order as its single launch, so each expert's bits are those of cugp_predict
 void launch_predict_gemm(const double* Ks, const double* T, double* W, int ld, int ntt, int nt, hipStream_t s,
                          Batch bt = {});
+// joint predictive covariance (cugp_predict_cov / cugp_predict_sample).  Shape of the product P = W W^T over the lower
+// tiles of an ntpad x ntpad result against n training rows: output tiles of 32 * wm (tiles of them), the k range [0, kend)
+// in split chunks of kstep (tuning key TUNE_COV_SPLIT); the caller provides split - 1 scratch slots of ntpad^2 doubles
+struct CovShape { int wm, tiles, kend, kstep, split; };
+CovShape predict_cov_shape(int ntpad, int n);
+// chunk 0 of every tile -> A (ld = ntpad), chunk s > 0 -> scr + (s - 1) * ntpad^2; W: [ntpad][ld]
+void launch_predict_cov(const double* W, int ld, int ntpad, const CovShape& c, double* A, double* scr, hipStream_t s);
+// A (lower 64x64 tiles, in place) = k(Xt,Xt) (+ sn2 on the diagonal when with_noise) + jitter I - (A + scr[0] + ...
+// + scr[nscr - 1]), identity beyond nt; tickets (when given): the factorisation's arrival counters, zeroed
+void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, HyperScalars h, bool with_noise, double jitter,
+                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s);
+// strict upper triangle of the nt diagonal 128x128 tiles of A := 0
+void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s);
+// out[s * nt + t] = mean[t] + F[s * ld + t]   (s < ns, t < nt)
+void launch_sample_finish(const double* F, int ld, const double* mean, int nt, int ns, double* out, hipStream_t s);
 // mean / var (may be null) and, when rows is given, the product-of-experts exchange rows: 1/var at rows[t], mean/var at
 // rows[rhalf + t] (batched: expert e's at rows + e * rstride; alpha from the table, Ks and W [expert][ntpad][npad])
 void launch_predict_finish(const double* Ks, const double* W, const double* alpha, int n, int npad, int ntest,

@@ -1037,6 +1037,100 @@ __global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int
     }
 }
 
+// ---- joint predictive covariance (cugp_predict_cov): Sigma = k(Xt,Xt) (+ sn2 I) - W W^T, W = Ks L^-T ----
+// Product: P = W W^T over the lower BT-tiles of the nt x nt result.  W ([ntpad][ld], k_predict_gemm's output) is exactly
+// zero in its columns >= n (Ks is zero there and the padding rows of L^-1 are identity) and its rows >= nt (Ks rows are
+// zero there): no masking, and the k range ends at kend = n rounded up to BK.  Few tiles cannot fill the chip, so the k
+// range of a tile is split into `split` chunks of kstep: workgroup (tile, s) writes its partial product to P (s = 0, the
+// factor handle's A, ld = ldp) or to scratch slot s - 1 (pstride doubles apart, same layout).  k_predict_cov_finish adds
+// the chunks in index order: the bits do not depend on which workgroup ends first.
+template <int WM>
+__global__ __launch_bounds__(256, 2) void k_predict_cov(const double* __restrict__ W, int ld, int kend, int kstep,
+                                                        int split, double* __restrict__ P, double* __restrict__ scr,
+                                                        size_t pstride, int ldp, unsigned long long* stamp)
+{
+    LaunchStamp stamp_(stamp);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int BT = 32 * WM;
+    const int tile = blockIdx.x / split, s = blockIdx.x % split;
+    int ti, tj;
+    tri_index(tile, ti, tj);
+    const int k0 = s * kstep, k1 = k0 + kstep < kend ? k0 + kstep : kend;
+    d4 acc[WM][WM];
+    acc_zero(acc);
+    tile_nt<false>(W + (size_t)ti * BT * ld, ld, W + (size_t)tj * BT * ld, ld, k0, k1, acc, smem);
+    double* C = s == 0 ? P : scr + (size_t)(s - 1) * pstride;
+    tile_store(C + (size_t)ti * BT * ldp + tj * BT, ldp, acc, 1.0);
+}
+
+// Epilogue, on the lower 64x64 tiles that k_build writes (the layout the Cholesky reads): A = kss (+ sn2 + jitter on the
+// diagonal) - (P_0 + P_1 + ...), in place over P_0; kss = sf2 exp(-|xt_i - xt_j|^2 / (2 l^2)) by k_build's formula and
+// squared-distance order; padding rows / columns >= nt become identity.  tickets (when given): the factorisation's
+// arrival counters, zeroed as k_build does.
+__global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __restrict__ Xt, int nt, int d, int ntpad,
+                                                            HyperScalars h, int with_noise, double jitter,
+                                                            double* __restrict__ A, const double* __restrict__ scr,
+                                                            size_t pstride, int nscr, unsigned* __restrict__ tickets)
+{
+#pragma clang fp contract(off)
+    if (tickets && blockIdx.x == 0)
+        for (int i = threadIdx.x; i < ticket_count(ntpad / TILE); i += 256) tickets[i] = 0u;
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    int ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    const int i0 = ti * KT, j0 = tj * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    double d2v[4][4];
+    sqdist_4x4(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v);
+    const DivBy dl = div_prepare(h.ell_sq);
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int i = i0 + ty * 4 + a;
+        const size_t off = (size_t)i * ntpad + j0 + tx * 2;
+        d2 p01 = *(const d2*)(A + off), p23 = *(const d2*)(A + off + 32);
+        for (int s = 0; s < nscr; s++) {
+            const double* q = scr + (size_t)s * pstride + off;
+            p01 = p01 + *(const d2*)q;
+            p23 = p23 + *(const d2*)(q + 32);
+        }
+        const double p[4] = {p01[0], p01[1], p23[0], p23[1]};
+        double o[4];
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = j0 + col4(tx, b);
+            double v = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
+            if (i == j) {
+                if (with_noise) v += h.noise_var;
+                v += jitter;
+            }
+            o[b] = (i < nt && j < nt) ? v - p[b] : ((i == j) ? 1.0 : 0.0);
+        }
+        *(d2*)(A + off) = (d2){o[0], o[1]};
+        *(d2*)(A + off + 32) = (d2){o[2], o[3]};
+    }
+}
+
+// The Cholesky writes the lower triangle only: the strict upper part of every 128x128 diagonal tile still holds Sigma,
+// and k_predict_gemm reads its diagonal 64-tiles whole.  Zeroed here, one workgroup per diagonal tile.
+__global__ __launch_bounds__(256) void k_zero_upper_diag(double* __restrict__ A, int ld)
+{
+    double* T = A + (size_t)blockIdx.x * TILE * ld + (size_t)blockIdx.x * TILE;
+    for (int e = threadIdx.x; e < TILE * TILE; e += 256) {
+        const int r = e / TILE, c = e % TILE;
+        if (c > r) T[(size_t)r * ld + c] = 0.0;
+    }
+}
+
+// posterior draws: out[s * nt + t] = mean[t] + F[s][t]   (F = Z C^T, k_predict_gemm over the factor)
+__global__ __launch_bounds__(256) void k_sample_finish(const double* __restrict__ F, int ld, const double* __restrict__ mean,
+                                                       int nt, int ns, double* __restrict__ out)
+{
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)nt * ns) return;
+    const size_t s = idx / nt, t = idx % nt;
+    out[idx] = mean[t] + F[s * ld + t];
+}
+
 // ------------------------------------------------------------------------------------------
 // diagonal block: 128x128 Cholesky in LDS (one workgroup), 16-wide inner blocks
 // ------------------------------------------------------------------------------------------
@@ -2421,7 +2515,8 @@ static inline unsigned long long* take_stamp() { unsigned long long* p = t_stamp
         }                                                                                           \
     } while (0)
 
-const int g_tune_init[TUNE_COUNT] = {768, 1200, 384, -1, 511, 1, 1, 1 << 20, 16, 500, 32, 1, 2100, 256, 1536, 0, 1 << 21, 1, 1, 0};   // defaults chosen by interleaved A/B runs (tools/ab.py)
+const int g_tune_init[TUNE_COUNT] = {768, 1200, 384, -1, 511, 1, 1, 1 << 20, 16, 500, 32, 1, 2100, 256, 1536, 0, 1 << 21, 1, 1, 0,
+                                      1024};   // defaults chosen by interleaved A/B runs (tools/ab.py)
 thread_local const int* t_tune = g_tune_init;
 
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
@@ -2466,7 +2561,7 @@ static void set_big_lds()
     attr((const void*)k_syrk_step, STEP_LDS);
     attr((const void*)k_syrk_wide, GEMM_LDS);
     const void* gemm4[] = {(const void*)k_trtri_level<4>, (const void*)k_trtri_border<4>, (const void*)k_lauum<4>,
-                           (const void*)k_test_gemm};
+                           (const void*)k_test_gemm, (const void*)k_predict_cov<4>};
     for (const void* f : gemm4) attr(f, GEMM_LDS);
     attr((const void*)k_trtri_diag, TRTRI_LDS);
     attr((const void*)k_trtri_block, TRTRI_BLOCK_LDS);
@@ -2653,6 +2748,57 @@ void launch_predict_gemm(const double* Ks, const double* T, double* W, int ld, i
     // (ntt, nt in 128-row tiles; the kernel works on 64-row tiles in pairs)
     CUGP_LAUNCH(k_predict_gemm, dim3(2 * ntt * nt, bt.count), dim3(256), Geo<2>::LDS, s, Ks, T, W, ld, 2 * ntt, 2 * nt,
                 take_stamp(), bt.tab);
+}
+
+CovShape predict_cov_shape(int ntpad, int n)
+{
+    CovShape c;
+    const int aim = tune(TUNE_COV_SPLIT);                 // 64x64 workgroup slots to fill (four per CU); 0 = no split
+    const int t128 = tri_count(ntpad / TILE);
+    c.wm = (aim > 0 && 4 * t128 <= aim) ? 2 : 4;
+    c.tiles = c.wm == 2 ? tri_count(ntpad / 64) : t128;
+    c.kend = (n + BK - 1) / BK * BK;
+    int split = aim / (c.wm == 2 ? 1 : 2) / c.tiles;      // (128x128 workgroups: two per CU)
+    const int kmax = c.kend / 256;                        // chunks of at least 256 k
+    if (split > kmax) split = kmax;
+    if (split > 64) split = 64;
+    const size_t pstride = (size_t)ntpad * ntpad;
+    while (split > 1 && (size_t)(split - 1) * pstride * sizeof(double) > ((size_t)1 << 30)) split--;   // scratch <= 1 GiB
+    if (split < 1) split = 1;
+    c.kstep = ((c.kend + split - 1) / split + BK - 1) / BK * BK;
+    c.split = c.kstep > 0 ? (c.kend + c.kstep - 1) / c.kstep : 1;
+    if (c.split < 1) c.split = 1;
+    return c;
+}
+
+void launch_predict_cov(const double* W, int ld, int ntpad, const CovShape& c, double* A, double* scr, hipStream_t s)
+{
+    set_big_lds();
+    const size_t pstride = (size_t)ntpad * ntpad;
+    if (c.wm == 2)
+        CUGP_LAUNCH(k_predict_cov<2>, dim3(c.tiles * c.split), dim3(256), Geo<2>::LDS, s, W, ld, c.kend, c.kstep,
+                    c.split, A, scr, pstride, ntpad, take_stamp());
+    else
+        CUGP_LAUNCH(k_predict_cov<4>, dim3(c.tiles * c.split), dim3(256), GEMM_LDS, s, W, ld, c.kend, c.kstep,
+                    c.split, A, scr, pstride, ntpad, take_stamp());
+}
+
+void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, HyperScalars h, bool with_noise, double jitter,
+                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_predict_cov_finish, dim3(tri_count(ntpad / KT)), dim3(256), 0, s, Xt, nt, d, ntpad, h,
+                       with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+}
+
+void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_zero_upper_diag, dim3(nt), dim3(256), 0, s, A, ld);
+}
+
+void launch_sample_finish(const double* F, int ld, const double* mean, int nt, int ns, double* out, hipStream_t s)
+{
+    const size_t total = (size_t)nt * ns;
+    hipLaunchKernelGGL(k_sample_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, F, ld, mean, nt, ns, out);
 }
 
 void launch_predict_finish(const double* Ks, const double* W, const double* alpha, int n, int npad, int ntest,

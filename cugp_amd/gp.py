@@ -151,6 +151,34 @@ class Covsum:
         check(capi.lib().cugp_predict(self._h, ptr(Xt), Xt.shape[0], ptr(m), ptr(v)))
         return m, v
 
+    def compute_test_joint(self, X, y, Xtest, with_noise=True):
+        """Joint predictive distribution at the test points (cugp_predict_cov): (mean [nt], cov [nt, nt]), cov =
+        k(Xt,Xt) - Ks K^-1 Ks^T (+ sigma_n^2 I with noise), exactly symmetric; mean has cugp_predict's bits."""
+        self._bind(X, y)
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        m, cov = np.empty(nt), np.empty((nt, nt))
+        check(capi.lib().cugp_predict_cov(self._h, ptr(Xt), nt, 1 if with_noise else 0, ptr(m), ptr(cov)))
+        return m, cov
+
+    def sample_posterior(self, X, y, Xtest, nsamples, with_noise=False, jitter=None, rng=None, normals=None):
+        """Posterior draws at the test points (cugp_predict_sample): [nsamples, nt] = mean + normals C^T, C the lower
+        Cholesky factor of cov + jitter I (cov as compute_test_joint).  normals [nsamples, nt] default to
+        rng.standard_normal (rng: a numpy Generator or a seed); jitter None: 1e-8 sf2 for latent draws, 0 with noise."""
+        self._bind(X, y)
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt, ns = Xt.shape[0], int(nsamples)
+        if normals is None:
+            gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+            normals = gen.standard_normal((ns, nt))
+        Z = f64(normals).reshape(ns, nt)
+        if jitter is None:
+            jitter = 0.0 if with_noise else 1e-8 * float(np.exp(2.0 * self.get_loghyperparam()[1]))
+        out = np.empty((ns, nt))
+        check(capi.lib().cugp_predict_sample(self._h, ptr(Xt), nt, 1 if with_noise else 0, float(jitter), ns, ptr(Z),
+                                             ptr(out)))
+        return out
+
     @staticmethod
     def get_negative_log_predprob(actual, predmean, predvar):
         a, m, v = f64(actual), f64(predmean), f64(predvar)

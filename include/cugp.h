@@ -88,6 +88,24 @@ int cugp_last_quad_logdet(const cugp_gp *gp, double *quad, double *logdet);
  *      noise term, :316) ; compute_k_test :105-116 ; get_negative_log_predprob :649-659 ; testing_phase
  *      cuda_src/cuda_gp.cu:2063 ---- */
 int cugp_predict(cugp_gp *gp, const double *Xt, int nt, double *mean, double *var);
+/* ---- joint predictive distribution: extends the marginal form of Covsum::compute_test_means_and_variances
+ *      covkernel.cpp:277-323 (the noise term as at :316) to the covariance between the test points; the reference has
+ *      no joint counterpart.  Both work on every handle cugp_predict works on (padded handles, BCM experts), at the
+ *      current data and hyper-parameters (a stale handle is evaluated first, as for cugp_predict); an evaluation in
+ *      flight is fetched first, as cugp_predict does.
+ * cugp_predict_cov: joint predictive distribution at nt test points.
+ *   mean : nt, the same bits as cugp_predict (may be NULL)
+ *   cov  : nt x nt row-major, full symmetric (mirrored, exactly symmetric):
+ *          k(Xt,Xt) - Ks K^-1 Ks^T, plus sigma_n^2 I when with_noise (then diag(cov) is cugp_predict's var up to rounding)
+ * cugp_predict_sample: posterior draws: samples[s*nt + t] = mean[t] + sum_{k<=t} C[t][k] * normals[s*nt + k],
+ *   C = lower Cholesky factor of (cov + jitter I), cov as above, computed by the library's blocked Cholesky;
+ *   normals: caller-supplied standard normals [nsamples][nt] (the library has no RNG: results are reproducible);
+ *   jitter >= 0; a matrix that is not positive definite gives NaN samples, not an error (header convention)
+ * Errors: CUGP_ERR_INVALID for a NULL gp, Xt, cov, normals or samples, nt <= 0, nsamples <= 0, or a jitter that is
+ * negative or not finite -- before any device call. */
+int cugp_predict_cov(cugp_gp *gp, const double *Xt, int nt, int with_noise, double *mean, double *cov);
+int cugp_predict_sample(cugp_gp *gp, const double *Xt, int nt, int with_noise, double jitter,
+                        int nsamples, const double *normals, double *samples);
 int cugp_nlpp(const double *actual, const double *mean, const double *var, int nt, double *nlpp);
 
 /* ---- intermediates (parity tests; each copies device -> host) ----
@@ -134,7 +152,8 @@ int cugp_get_kernel_stats(cugp_gp *gp, double *sum_ms, long long *launches, doub
  * timed for every fourth block of inverse rows, 6 / 7 = k_trtri_level<4> / <2> (doubling inside a block of rows; timed
  * one launch in 16), 8 = k_trtri_block (a hand-over block's own inverse in one launch; every fourth block), 9 =
  * k_predict_gemm (W = Ks L^-T of cugp_predict; levels 3 to 5 only), 10 = k_build (level 5 only; its `flop` is BYTES: the
- * lower 64x64 tiles of K written once + X read).  The
+ * lower 64x64 tiles of K written once + X read), 12 = k_predict_cov<4> / <2> (W W^T of cugp_predict_cov and
+ * cugp_predict_sample; levels 3 to 5 only; flop: every launched output tile over the whole k range).  The
  * sampling rates are those of level 2; levels 3 to 5 time every launch.  flop = algorithmic
  * (entries on or below the diagonal, a triangular k tile counted half), multiply + add */
 int cugp_get_kernel_stats_kind(cugp_gp *gp, int kind, double *sum_ms, long long *launches, double *flop, int reset);
