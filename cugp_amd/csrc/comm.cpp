@@ -80,14 +80,13 @@ int hip_fail(const char* what, hipError_t e)
 struct cugp_comm {
     ncclComm_t comm = nullptr;   // null: a world of one without a communicator (nothing to exchange)
     int rank = 0, world = 1, device = 0;
-    double *dsend = nullptr, *drecv = nullptr;   // [per][4] this rank's rows, [world * per][4] everybody's
-    double* hrecv = nullptr;                     // pinned copy of drecv
-    int per = 0;
-    // product-of-experts prediction (cugp_bcm_predict_allgather), grow-only: this rank's block, everybody's, the reduced
+    Scratch dsend, drecv;                        // [per][4] this rank's rows, [world * per][4] everybody's
+    Scratch hrecv{nullptr, 0, true};             // pinned copy of drecv
+    // product-of-experts prediction (cugp_bcm_predict_allgather): this rank's block, everybody's, the reduced
     // [mean | var | status words] on the device and pinned, the pinned header {status, local count}
     hipStream_t stream = nullptr;                // the exchange's own stream on `device`
-    double *pdsend = nullptr, *pdrecv = nullptr, *pdout = nullptr, *phout = nullptr, *phdr = nullptr;
-    size_t pcap_send = 0, pcap_out = 0;          // doubles per rank's block, doubles of pdout
+    Scratch pdsend, pdrecv, pdout, phout{nullptr, 0, true};
+    double* phdr = nullptr;
 };
 
 extern "C" {
@@ -131,34 +130,26 @@ int cugp_comm_destroy(cugp_comm* c)
     if (!c) return CUGP_OK;
     (void)hipSetDevice(c->device);
     if (c->comm) (void)rccl().CommDestroy(c->comm);
-    if (c->dsend) (void)hipFree(c->dsend);
-    if (c->drecv) (void)hipFree(c->drecv);
-    if (c->hrecv) (void)hipHostFree(c->hrecv);
+    for (Scratch* b : {&c->dsend, &c->drecv, &c->hrecv}) b->release();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->pdsend) (void)hipFree(c->pdsend);
-    if (c->pdrecv) (void)hipFree(c->pdrecv);
-    if (c->pdout) (void)hipFree(c->pdout);
-    if (c->phout) (void)hipHostFree(c->phout);
+    for (Scratch* b : {&c->pdsend, &c->pdrecv, &c->pdout, &c->phout}) b->release();
     if (c->phdr) (void)hipHostFree(c->phdr);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return CUGP_OK;
 }
 
+// grow-only; nothing of the exchange is in flight between calls
 static int comm_buffers(cugp_comm* c, int per)
 {
-    if (c->per >= per) return CUGP_OK;
-    if (c->dsend) (void)hipFree(c->dsend);
-    if (c->drecv) (void)hipFree(c->drecv);
-    if (c->hrecv) (void)hipHostFree(c->hrecv);
-    c->dsend = c->drecv = c->hrecv = nullptr;
-    c->per = 0;
-    hipError_t e = hipMalloc((void**)&c->dsend, (size_t)per * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->drecv, (size_t)c->world * per * 4 * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->hrecv, (size_t)c->world * per * 4 * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMemset(c->dsend, 0, (size_t)per * 4 * sizeof(double));   // unused slots: exact zeros, for good
-    if (e != hipSuccess) return hip_fail("exchange buffers", e);
-    c->per = per;
+    const size_t nsend = (size_t)per * 4;
+    int rc;
+    if (nsend > c->dsend.cap) {
+        if ((rc = c->dsend.grow(nsend, nullptr))) return rc;
+        const hipError_t e = hipMemset(c->dsend.p, 0, nsend * sizeof(double));   // unused slots: exact zeros, for good
+        if (e != hipSuccess) { c->dsend.release(); return hip_fail("exchange buffers", e); }
+    }
+    if ((rc = c->drecv.grow(c->world * nsend, nullptr)) || (rc = c->hrecv.grow(c->world * nsend, nullptr))) return rc;
     return CUGP_OK;
 }
 
@@ -179,18 +170,18 @@ int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* r
     hipStream_t s = nullptr;
     if (nlocal > 0) {
         void* sv = nullptr;
-        if ((rc = cugp_bcm_enqueue_rows_packed(b, c->dsend, &sv))) return rc;   // rows packed behind the evaluation, on its stream
+        if ((rc = cugp_bcm_enqueue_rows_packed(b, c->dsend.p, &sv))) return rc;   // rows packed behind the evaluation, on its stream
         s = (hipStream_t)sv;
     }
     const size_t nsend = (size_t)per * 4, nall = nsend * c->world;
-    const double* src = c->drecv;
+    const double* src = c->drecv.p;
     if (c->comm) {
-        const ncclResult_t r = rccl().AllGather(c->dsend, c->drecv, nsend, ncclDouble, c->comm, s);
+        const ncclResult_t r = rccl().AllGather(c->dsend.p, c->drecv.p, nsend, ncclDouble, c->comm, s);
         if (r != ncclSuccess) { if (nlocal > 0) (void)cugp_bcm_finish_rows(b); return nccl_fail("ncclAllGather", r); }
     } else {
-        src = c->dsend;                                // a world of one: this rank's rows are all the rows
+        src = c->dsend.p;                              // a world of one: this rank's rows are all the rows
     }
-    e = hipMemcpyAsync(c->hrecv, src, nall * sizeof(double), hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(c->hrecv.p, src, nall * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) { if (nlocal > 0) (void)cugp_bcm_finish_rows(b); return hip_fail("hipMemcpyAsync (gathered rows)", e); }
     if (nlocal > 0) rc = cugp_bcm_finish_rows(b);      // waits for the stream: evaluation, collective and copy
     else {
@@ -198,7 +189,7 @@ int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* r
         if (e != hipSuccess) return hip_fail("hipStreamSynchronize", e);
     }
     if (rc) return rc;
-    memcpy(rows_out, c->hrecv, nall * sizeof(double));
+    memcpy(rows_out, c->hrecv.p, nall * sizeof(double));
     return CUGP_OK;
 }
 
@@ -207,28 +198,16 @@ static int pred_buffers(cugp_comm* c, size_t rstride, size_t nout)
     hipError_t e = hipSuccess;
     if (!c->stream) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess && !c->phdr) e = hipHostMalloc((void**)&c->phdr, 2 * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess && rstride > c->pcap_send) {
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        if (c->pdsend) (void)hipFree(c->pdsend);
-        if (c->pdrecv) (void)hipFree(c->pdrecv);
-        c->pdsend = c->pdrecv = nullptr;
-        c->pcap_send = 0;
-        e = hipMalloc((void**)&c->pdsend, rstride * sizeof(double));
-        if (e == hipSuccess && c->comm) e = hipMalloc((void**)&c->pdrecv, (size_t)c->world * rstride * sizeof(double));
-        if (e == hipSuccess) e = hipMemset(c->pdsend, 0, rstride * sizeof(double));
-        if (e == hipSuccess) c->pcap_send = rstride;
-    }
-    if (e == hipSuccess && nout > c->pcap_out) {
-        if (c->stream) (void)hipStreamSynchronize(c->stream);
-        if (c->pdout) (void)hipFree(c->pdout);
-        if (c->phout) (void)hipHostFree(c->phout);
-        c->pdout = c->phout = nullptr;
-        c->pcap_out = 0;
-        e = hipMalloc((void**)&c->pdout, nout * sizeof(double));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&c->phout, nout * sizeof(double), hipHostMallocDefault);
-        if (e == hipSuccess) c->pcap_out = nout;
-    }
     if (e != hipSuccess) return hip_fail("prediction exchange buffers", e);
+    int rc;
+    if (rstride > c->pdsend.cap) {
+        if ((rc = c->pdsend.grow(rstride, c->stream))) return rc;
+        e = hipMemset(c->pdsend.p, 0, rstride * sizeof(double));
+        if (e != hipSuccess) { c->pdsend.release(); return hip_fail("prediction exchange buffers", e); }
+    }
+    if ((c->comm && (rc = c->pdrecv.grow((size_t)c->world * rstride, c->stream))) || (rc = c->pdout.grow(nout, c->stream)) ||
+        (rc = c->phout.grow(nout, c->stream)))
+        return rc;
     return CUGP_OK;
 }
 
@@ -267,32 +246,32 @@ int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts,
     }
     if (status == CUGP_OK && nlocal > 0) {
         enqueued = true;
-        status = cugp_bcm_predict_rows_enqueue(b, c->device, Xt, nt, c->pdsend + 2, 2 * (size_t)nt, c->stream);
+        status = cugp_bcm_predict_rows_enqueue(b, c->device, Xt, nt, c->pdsend.p + 2, 2 * (size_t)nt, c->stream);
     }
     if (status != CUGP_OK) {
         if (enqueued) (void)cugp_bcm_predict_rows_finish(b);   // nothing enqueued still writes into the send buffer
-        e = hipMemsetAsync(c->pdsend + 2, 0xff, (rstride - 2) * sizeof(double), c->stream);   // all-ones: NaN rows
+        e = hipMemsetAsync(c->pdsend.p + 2, 0xff, (rstride - 2) * sizeof(double), c->stream);   // all-ones: NaN rows
         (void)e;
     }
     c->phdr[0] = (double)status;                       // (pinned, read by the copy below before the host waits)
     c->phdr[1] = (double)nlocal;
-    e = hipMemcpyAsync(c->pdsend, c->phdr, 2 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    e = hipMemcpyAsync(c->pdsend.p, c->phdr, 2 * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess && status == CUGP_OK) status = hip_fail("hipMemcpyAsync (status word)", e);
     // ---- the exchange
-    const double* src = c->pdsend;                     // a world of one without an id: this rank's block is all of them
+    const double* src = c->pdsend.p;                   // a world of one without an id: this rank's block is all of them
     if (c->comm) {
-        const ncclResult_t r = rccl().AllGather(c->pdsend, c->pdrecv, rstride, ncclDouble, c->comm, c->stream);
+        const ncclResult_t r = rccl().AllGather(c->pdsend.p, c->pdrecv.p, rstride, ncclDouble, c->comm, c->stream);
         if (r != ncclSuccess) {
             if (enqueued) (void)cugp_bcm_predict_rows_finish(b);
             (void)hipStreamSynchronize(c->stream);
             fill_nan(mean, var, nt);
             return nccl_fail("ncclAllGather", r);
         }
-        src = c->pdrecv;
+        src = c->pdrecv.p;
     }
-    rc = cugp_poe_reduce_enqueue(src, rstride, c->world, nexperts, nt, c->pdout, c->stream);
+    rc = cugp_poe_reduce_enqueue(src, rstride, c->world, nexperts, nt, c->pdout.p, c->stream);
     if (rc == CUGP_OK) {
-        e = hipMemcpyAsync(c->phout, c->pdout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(c->phout.p, c->pdout.p, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) rc = hip_fail("hipMemcpyAsync (prediction)", e);
     }
     e = hipStreamSynchronize(c->stream);               // the one host wait: prediction, collective, reduction, copy
@@ -300,7 +279,7 @@ int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts,
     if (enqueued && status == CUGP_OK) status = cugp_bcm_predict_rows_finish(b);   // (streams already done: closes them)
     if (rc) { fill_nan(mean, var, nt); return rc; }
     // ---- every rank reads every rank's status word: the same verdict everywhere
-    const double* h = c->phout;
+    const double* h = c->phout.p;
     long long total = 0;
     for (int r = 0; r < c->world; r++) {
         const int st = (int)h[2 * (size_t)nt + 2 * r];

@@ -67,6 +67,27 @@ struct QueueDefault {
 
 }  // namespace
 
+int Scratch::grow(size_t count, void* stream)
+{
+    if (count <= cap) return CUGP_OK;
+    if (stream) HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    release();
+    double* q = nullptr;
+    const hipError_t e = pinned ? hipHostMalloc((void**)&q, count * sizeof(double), hipHostMallocDefault)
+                                : hipMalloc((void**)&q, count * sizeof(double));
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, "scratch allocation", e);
+    p = q;
+    cap = count;
+    return CUGP_OK;
+}
+
+void Scratch::release()
+{
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+}
+
 // set on the lead expert while a group evaluation is being enqueued: every launch then serves all experts
 struct GroupCtx {
     Batch bt;                       // device table of the experts' buffers, expert count
@@ -102,8 +123,7 @@ struct cugp_gp {
     bool vec_early = false;        // record_eval: z = L^-1 y, alpha = L^-T z go behind the last block's bordering
     bool vec_done = false;         // ... and were enqueued there
     const GroupCtx* grp = nullptr;  // non-null only inside cugp_group_eval
-    double* pred_buf = nullptr;     // prediction scratch (test inputs, cross-covariance, its product with L^-T, results)
-    size_t pred_cap = 0;            // ... in doubles, grow-only
+    Scratch pred;                   // prediction scratch (predict_passes: test inputs, cross-covariance, its product with L^-T, results)
     bool overlap = true;           // hand inverse blocks to the other streams while the factorisation runs
     // a single-stream evaluation is captured once as a HIP graph and replayed: one launch call instead of
     // ~60 (1500 rows) -- with 16 experts on a GPU the host's launch rate was the bound, not the device
@@ -140,10 +160,8 @@ struct cugp_gp {
     cugp_gp* cov_f = nullptr;      // factor handle: its A receives Sigma (ld = its npad), its own stream factors it
     int cov_tiles = 0;             // ... tile rows it was created for (it serves any smaller count)
     hipEvent_t cov_ev = nullptr;   // "Sigma written" (this handle's stream -> cov_f's)
-    double* cov_scr = nullptr;     // split-k partial products of k_predict_cov, grow-only ...
-    size_t cov_scr_cap = 0;        // ... in doubles
-    double* samp_buf = nullptr;    // draws: normals Z, F = Z C^T (both [ns pad][ntpad]), packed samples, grow-only ...
-    size_t samp_cap = 0;           // ... in doubles
+    Scratch cov_scr;               // split-k partial products of k_predict_cov
+    Scratch samp;                  // draws: normals Z, F = Z C^T (both [ns pad][ntpad]), packed samples
 };
 
 namespace {
@@ -834,6 +852,31 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
     return CUGP_OK;
 }
 
+// The evaluation as a captured HIP graph on g's stream (g->grp's group while that is set, with the group's graphs):
+// captured once per launch-shape epoch -- gexec / gepoch [0] log-likelihood only, [1] with gradient -- then replayed.
+// The kernels read the hyper-scalars from g->dhs, which the graph's first node refreshes from g->hhs.
+int replay_eval(cugp_gp* g, hipGraphExec_t gexec[2], unsigned gepoch[2], bool want_grad)
+{
+    const int gi = want_grad ? 1 : 0;
+    if (!gexec[gi] || gepoch[gi] != g->cfg_epoch) {
+        if (gexec[gi]) (void)hipGraphExecDestroy(gexec[gi]);
+        gexec[gi] = nullptr;
+        hipGraph_t graph = nullptr;
+        HIPCHK(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
+        const int rc = record_eval(g, want_grad, g->dhs);
+        hipError_t e = hipStreamEndCapture(g->stream, &graph);   // always leave capture mode
+        if (rc == CUGP_OK && e == hipSuccess) e = hipGraphInstantiate(&gexec[gi], graph, nullptr, nullptr, 0);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (rc || e != hipSuccess) {
+            gexec[gi] = nullptr;
+            return rc ? rc : fail(CUGP_ERR_DEVICE, "graph capture", e);
+        }
+        gepoch[gi] = g->cfg_epoch;
+    }
+    HIPCHK(hipGraphLaunch(gexec[gi], g->stream));
+    return CUGP_OK;
+}
+
 int enqueue_eval(cugp_gp* g, bool want_grad)
 {
     int rc;
@@ -852,30 +895,8 @@ int enqueue_eval(cugp_gp* g, bool want_grad)
     // (measured: 16 x 1500 rows 4.7 -> 4.1 ms, 2 x 1500 rows 1.25 -> 1.18 ms; nothing to gain above ~3000 rows)
     const bool graph = g->tune[TUNE_GRAPHS] != 0 && g->prof == 0 && g->nt <= GRAPH_MAX_TILES &&
                        pipe_block(g, want_grad) == 0;
-    if (!graph) {
-        if ((rc = record_eval(g, want_grad, nullptr))) return rc;
-    } else {
-        const int gi = want_grad ? 1 : 0;
-        *g->hhs = scalars(g);
-        if (!g->gexec[gi] || g->gepoch[gi] != g->cfg_epoch) {
-            if (g->gexec[gi]) (void)hipGraphExecDestroy(g->gexec[gi]);
-            g->gexec[gi] = nullptr;
-            prepare_kernels();
-            hipGraph_t graph_obj = nullptr;
-            HIPCHK(hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal));
-            rc = record_eval(g, want_grad, g->dhs);
-            const hipError_t e = hipStreamEndCapture(g->stream, &graph_obj);   // always leave capture mode
-            if (rc || e != hipSuccess) {
-                if (graph_obj) (void)hipGraphDestroy(graph_obj);
-                return rc ? rc : fail(CUGP_ERR_DEVICE, "hipStreamEndCapture", e);
-            }
-            const hipError_t ei = hipGraphInstantiate(&g->gexec[gi], graph_obj, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph_obj);
-            if (ei != hipSuccess) { g->gexec[gi] = nullptr; return fail(CUGP_ERR_DEVICE, "hipGraphInstantiate", ei); }
-            g->gepoch[gi] = g->cfg_epoch;
-        }
-        HIPCHK(hipGraphLaunch(g->gexec[gi], g->stream));
-    }
+    if (graph) *g->hhs = scalars(g);
+    if ((rc = graph ? replay_eval(g, g->gexec, g->gepoch, want_grad) : record_eval(g, want_grad, nullptr))) return rc;
     g->pending = true;
     g->pending_grad = want_grad;
     g->pev_valid = g->prof >= 1;
@@ -914,11 +935,38 @@ int enqueue_continue(cugp_gp* g)
 }
 
 // After a synchronise that follows ANY launch sequence with k_trtri_block in it: did one of its bounded stage waits
-// run out?  (pinned status word, entry 6 of the handle's result row.)  Reads and clears it.
-bool barrier_expired(cugp_gp* g)
+// run out?  (pinned status word, entry 6 of a result row.)  Reads and clears it.
+bool barrier_expired(double* row)
 {
-    if (g->hout[6] == 0.0) return false;
-    g->hout[6] = 0.0;
+    if (row[6] == 0.0) return false;
+    row[6] = 0.0;
+    return true;
+}
+
+// nothing of the evaluation is kept: NaN results, and the next call starts from the covariance build
+void discard_eval(cugp_gp* g)
+{
+    g->factor_valid = g->inverse_valid = false;
+    g->last_ll = g->last_quad = g->last_logdet = NAN;
+    g->last_g[0] = g->last_g[1] = g->last_g[2] = NAN;
+}
+
+// The results of g's evaluation from its 8-double host row (host_out) -- or, when a bounded wait inside a kernel ran out
+// (k_trtri_block's stage barrier), none: nothing of that evaluation is to be trusted, and it is discarded (false).
+bool read_result_row(cugp_gp* g, double* row, bool grad)
+{
+    if (barrier_expired(row)) {
+        discard_eval(g);
+        return false;
+    }
+    g->last_ll = row[0];
+    g->last_quad = row[4];
+    g->last_logdet = row[5];
+    g->factor_valid = true;
+    if (grad) {
+        for (int i = 0; i < 3; i++) g->last_g[i] = row[1 + i];
+        g->inverse_valid = true;
+    }
     return true;
 }
 
@@ -929,24 +977,9 @@ int fetch_eval(cugp_gp* g)
     if ((rc = use_device(g))) return rc;
     HIPCHK(hipStreamSynchronize(g->stream));
     g->pending = false;
-    if (barrier_expired(g)) {
-        // a bounded wait inside a kernel ran out (k_trtri_block's stage barrier): nothing of this evaluation is to be
-        // trusted, and nothing of it is kept -- the next call starts from the covariance build
-        g->factor_valid = g->inverse_valid = false;
-        g->last_ll = g->last_quad = g->last_logdet = NAN;
-        g->last_g[0] = g->last_g[1] = g->last_g[2] = NAN;
-        if (g->prof >= 2) drain_kernel_events(g);
-        return fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls (the evaluation was abandoned; results NaN)");
-    }
-    g->last_ll = g->hout[0];
-    g->last_quad = g->hout[4];
-    g->last_logdet = g->hout[5];
-    g->factor_valid = true;
-    if (g->pending_grad) {
-        for (int i = 0; i < 3; i++) g->last_g[i] = g->hout[1 + i];
-        g->inverse_valid = true;
-    }
+    const bool ok = read_result_row(g, g->hout, g->pending_grad);
     if (g->prof >= 2) drain_kernel_events(g);
+    if (!ok) return fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls (the evaluation was abandoned; results NaN)");
     return CUGP_OK;
 }
 
@@ -1044,24 +1077,24 @@ int cugp_create_padded(int n, int d, int device, int npad_min, cugp_gp** out)
 int cugp_destroy(cugp_gp* g)
 {
     if (!g) return CUGP_OK;
-    barrier_release(g);
-    if (g->counted) g_live[g->device >= 0 && g->device < 64 ? g->device : 63].fetch_sub(1, std::memory_order_relaxed);
     (void)hipSetDevice(g->device);
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->aux) (void)hipStreamSynchronize(g->aux);
     if (g->aux2) (void)hipStreamSynchronize(g->aux2);
     if (g->lq) (void)hipStreamSynchronize(g->lq);
+    barrier_release(g);                                   // (no barrier grid of this handle runs any more)
+    if (g->counted) g_live[g->device >= 0 && g->device < 64 ? g->device : 63].fetch_sub(1, std::memory_order_relaxed);
     if (g->cov_f) (void)cugp_destroy(g->cov_f);           // (synchronises its own stream first)
     if (g->cov_ev) (void)hipEventDestroy(g->cov_ev);
-    if (g->cov_scr) (void)hipFree(g->cov_scr);
-    if (g->samp_buf) (void)hipFree(g->samp_buf);
+    g->cov_scr.release();
+    g->samp.release();
     double* bufs[] = {g->dX, g->dy, g->dA, g->dT, g->dU, g->dKinv, g->dz, g->dalpha, g->dw, g->d16, g->dlogdet,
                       g->dpart, g->dout, g->d64};
     for (double* p : bufs)
         if (p) (void)hipFree(p);
     if (g->dtickets) (void)hipFree(g->dtickets);
     if (g->dstamps) (void)hipFree(g->dstamps);
-    if (g->pred_buf) (void)hipFree(g->pred_buf);
+    g->pred.release();
     if (g->hout) (void)hipHostFree(g->hout);
     if (g->hhs) (void)hipHostFree(g->hhs);
     if (g->dhs) (void)hipFree(g->dhs);
@@ -1206,69 +1239,73 @@ int cugp_nlpp(const double* actual, const double* mean, const double* var, int n
     return CUGP_OK;
 }
 
-// dxt_out / dw_out (when given): the test inputs and W = Ks L^-T on the device (the joint covariance reads them)
-static int predict_device(cugp_gp* g, const double* Xt, int nt, double** dmean_out, double** dvar_out,
-                          std::vector<double*>& to_free, double** dxt_out = nullptr, double** dw_out = nullptr)
+// where predict_passes left the test inputs, W = Ks L^-T and the means / variances on the device
+struct PredBufs { double *xt, *w, *mean, *var; };
+
+// The prediction at nt test points on g's stream: of g alone (bt = {}), or of every expert of g's group by ONE sequence
+// of batched launches (bt: the group's table; blockIdx.y = expert).  Xt goes into the scratch `scr` (test inputs, then
+// Ks and W of one pass, [expert][cpad][npad] each), then per pass of `chunk` test points k_cross, k_predict_gemm and
+// k_predict_finish.  rows null: means and variances into the scratch behind W (one pass, chunk >= nt; *pb).  Else
+// product-of-experts rows: expert i's 1/v at rows[i * rstride + t], m/v at rows[i * rstride + nt + t].
+static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int chunk, Scratch& scr, double* rows,
+                          size_t rstride, PredBufs* pb = nullptr)
+{
+    int rc;
+    const int cmax = chunk < nt ? chunk : nt, ntpad = ((cmax + TILE - 1) / TILE) * TILE;
+    const HyperScalars h = scalars(g);
+    const size_t nxt = (((size_t)nt * g->d + 15) / 16) * 16, nks = (size_t)bt.count * ntpad * g->npad;
+    if ((rc = scr.grow(nxt + 2 * nks + (rows ? 0 : 2 * (size_t)ntpad), g->stream))) return rc;
+    double* dXt = scr.p;
+    double* dKs = dXt + nxt;
+    double* dW = dKs + nks;
+    double* dm = rows ? nullptr : dW + nks;
+    double* dv = rows ? nullptr : dm + ntpad;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    if (!bt.tab && (rc = reset_stamps(g))) return rc;
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int c = nt - t0 < chunk ? nt - t0 : chunk;
+        const int cpad = ((c + TILE - 1) / TILE) * TILE;
+        // (batched: X, n, T, alpha come from the table; k_predict_finish reads rstride and its cpad only then)
+        launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream, bt);
+        {
+            // W = Ks L^-T: test tile tt, row tile ti sums k <= ti (the diagonal k tile of T is triangular: counted half)
+            TimedLaunch tl(g, g->stream, !bt.tab && g->prof >= 3);
+            launch_predict_gemm(dKs, g->dT, dW, g->npad, cpad / TILE, g->nt, g->stream, bt);
+            double kt = 0;
+            for (int ti = 0; ti < g->nt; ti++) kt += ti + 0.5;
+            tl.done(KIND_PREDICT, kt * (cpad / TILE) * 2.0 * TILE * TILE * TILE);
+        }
+        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, h, dm, dv, g->stream, rows ? rows + t0 : nullptr,
+                              rstride, nt, cpad, bt);
+    }
+    HIPCHK(hipGetLastError());
+    if (pb) *pb = PredBufs{dXt, dW, dm, dv};
+    return CUGP_OK;
+}
+
+// means and variances at the nt test points in one pass (*pb), a stale handle re-evaluated first
+static int predict_device(cugp_gp* g, const double* Xt, int nt, PredBufs* pb)
 {
     int rc;
     if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // factor, T, alpha for the current hp
     if ((rc = use_device(g))) return rc;                             // (a BCM over several devices predicts expert by expert)
     TuneScope ts(g);
-    const int ntpad = ((nt + TILE - 1) / TILE) * TILE;
-    const HyperScalars h = scalars(g);
-    // prediction scratch lives with the handle and only grows (the allocations cost more than the kernels
-    // for a few hundred test points)
-    (void)to_free;
-    const size_t nxt = (((size_t)nt * g->d + 15) / 16) * 16, nks = (size_t)ntpad * g->npad, nv = (size_t)ntpad;
-    const size_t need = nxt + 2 * nks + 2 * nv;
-    if (need > g->pred_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->pred_buf) (void)hipFree(g->pred_buf);
-        g->pred_buf = nullptr;
-        g->pred_cap = 0;
-        HIPCHK(hipMalloc((void**)&g->pred_buf, need * sizeof(double)));
-        g->pred_cap = need;
-    }
-    double* dXt = g->pred_buf;
-    double* dKs = dXt + nxt;
-    double* dW = dKs + nks;
-    double* dm = dW + nks;
-    double* dv = dm + nv;
-    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, g->stream));
-    if ((rc = reset_stamps(g))) return rc;
-    launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, h, dKs, g->stream);
-    {
-        // W = Ks L^-T: test tile tt, row tile ti sums k <= ti (the diagonal k tile of T is triangular: counted half)
-        TimedLaunch tl(g, g->stream, g->prof >= 3);
-        launch_predict_gemm(dKs, g->dT, dW, g->npad, ntpad / TILE, g->nt, g->stream);
-        double kt = 0;
-        for (int ti = 0; ti < g->nt; ti++) kt += ti + 0.5;
-        tl.done(KIND_PREDICT, kt * (ntpad / TILE) * 2.0 * TILE * TILE * TILE);
-    }
-    launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, nt, h, dm, dv, g->stream);
-    HIPCHK(hipGetLastError());
-    *dmean_out = dm;
-    *dvar_out = dv;
-    if (dxt_out) *dxt_out = dXt;
-    if (dw_out) *dw_out = dW;
-    return CUGP_OK;
+    return predict_passes(g, {}, Xt, nt, ((nt + TILE - 1) / TILE) * TILE, g->pred, nullptr, 0, pb);
 }
 
 int cugp_predict(cugp_gp* g, const double* Xt, int nt, double* mean, double* var)
 {
     if (!g || !Xt || !mean || !var || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict: bad argument");
-    std::vector<double*> tmp;
-    double *dm = nullptr, *dv = nullptr;
-    int rc = predict_device(g, Xt, nt, &dm, &dv, tmp);
+    PredBufs pb;
+    int rc = predict_device(g, Xt, nt, &pb);
     if (rc == CUGP_OK) {
-        hipError_t e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
+        hipError_t e = hipMemcpyAsync(mean, pb.mean, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(var, pb.var, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
         if (e != hipSuccess) rc = fail(CUGP_ERR_DEVICE, "cugp_predict copy", e);
         else if (g->prof >= 2) drain_kernel_events(g);
     }
     (void)hipStreamSynchronize(g->stream);
-    for (double* p : tmp) (void)hipFree(p);
     return rc;
 }
 
@@ -1277,12 +1314,11 @@ int cugp_has_inverse(const cugp_gp* g) { return g && !g->pending && g->inverse_v
 int cugp_predict_enqueue(cugp_gp* g, const double* Xt, int nt, double* host_mv)
 {
     if (!g || !Xt || !host_mv || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict_enqueue: bad argument");
-    std::vector<double*> tmp;
-    double *dm = nullptr, *dv = nullptr;
-    int rc = predict_device(g, Xt, nt, &dm, &dv, tmp);
+    PredBufs pb;
+    int rc = predict_device(g, Xt, nt, &pb);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(host_mv, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIPCHK(hipMemcpyAsync(host_mv + nt, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(host_mv, pb.mean, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipMemcpyAsync(host_mv + nt, pb.var, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     return CUGP_OK;
 }
 
@@ -1322,38 +1358,7 @@ int cugp_predict_rows_enqueue(cugp_gp* g, const double* Xt, int nt, double* drow
     if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // factor, T, alpha for the current hp
     if ((rc = use_device(g))) return rc;
     TuneScope ts(g);
-    const int chunk = pred_chunk_rows(g, 1, nt);
-    const int ntpad = ((chunk + TILE - 1) / TILE) * TILE;
-    const HyperScalars h = scalars(g);
-    const size_t nxt = (((size_t)nt * g->d + 15) / 16) * 16, nks = (size_t)ntpad * g->npad;
-    const size_t need = nxt + 2 * nks;
-    if (need > g->pred_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->pred_buf) (void)hipFree(g->pred_buf);
-        g->pred_buf = nullptr;
-        g->pred_cap = 0;
-        HIPCHK(hipMalloc((void**)&g->pred_buf, need * sizeof(double)));
-        g->pred_cap = need;
-    }
-    double* dXt = g->pred_buf;
-    double* dKs = dXt + nxt;
-    double* dW = dKs + nks;
-    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, g->stream));
-    if ((rc = reset_stamps(g))) return rc;
-    for (int t0 = 0; t0 < nt; t0 += chunk) {
-        const int c = nt - t0 < chunk ? nt - t0 : chunk;
-        const int cpad = ((c + TILE - 1) / TILE) * TILE;
-        launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream);
-        {
-            TimedLaunch tl(g, g->stream, g->prof >= 3);
-            launch_predict_gemm(dKs, g->dT, dW, g->npad, cpad / TILE, g->nt, g->stream);
-            double kt = 0;
-            for (int ti = 0; ti < g->nt; ti++) kt += ti + 0.5;
-            tl.done(KIND_PREDICT, kt * (cpad / TILE) * 2.0 * TILE * TILE * TILE);
-        }
-        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, h, nullptr, nullptr, g->stream, drows + t0, 0, nt);
-    }
-    HIPCHK(hipGetLastError());
+    if ((rc = predict_passes(g, {}, Xt, nt, pred_chunk_rows(g, 1, nt), g->pred, drows, 0))) return rc;
     *stream = (void*)g->stream;
     return CUGP_OK;
 }
@@ -1368,10 +1373,9 @@ int cugp_predict_rows_enqueue(cugp_gp* g, const double* Xt, int nt, double* drow
 static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_noise, double jitter, double** dmean,
                               cugp_gp** fout)
 {
-    std::vector<double*> tmp;
-    double *dm = nullptr, *dv = nullptr, *dXt = nullptr, *dW = nullptr;
+    PredBufs pb;
     int rc;
-    if ((rc = predict_device(g, Xt, nt, &dm, &dv, tmp, &dXt, &dW))) return rc;
+    if ((rc = predict_device(g, Xt, nt, &pb))) return rc;
     TuneScope ts(g);
     const int tiles = (nt + TILE - 1) / TILE, ntpad = tiles * TILE;
     if (!g->cov_f || g->cov_tiles < tiles) {
@@ -1396,24 +1400,16 @@ static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_no
     f->nt = tiles;
     f->npad = ntpad;
     const CovShape cs = predict_cov_shape(ntpad, g->n);
-    const size_t need = (size_t)(cs.split - 1) * ntpad * ntpad;
-    if (need > g->cov_scr_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->cov_scr) (void)hipFree(g->cov_scr);
-        g->cov_scr = nullptr;
-        g->cov_scr_cap = 0;
-        HIPCHK(hipMalloc((void**)&g->cov_scr, need * sizeof(double)));
-        g->cov_scr_cap = need;
-    }
+    if ((rc = g->cov_scr.grow((size_t)(cs.split - 1) * ntpad * ntpad, g->stream))) return rc;
     {
         TimedLaunch tl(g, g->stream, g->prof >= 3);
-        launch_predict_cov(dW, g->npad, ntpad, cs, f->dA, g->cov_scr, g->stream);
+        launch_predict_cov(pb.w, g->npad, ntpad, cs, f->dA, g->cov_scr.p, g->stream);
         tl.done(KIND_COV, 2.0 * cs.tiles * (32.0 * cs.wm) * (32.0 * cs.wm) * cs.kend);
     }
-    launch_predict_cov_finish(dXt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr, cs.split - 1,
+    launch_predict_cov_finish(pb.xt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr.p, cs.split - 1,
                               f->dtickets, g->stream);
     HIPCHK(hipGetLastError());
-    *dmean = dm;
+    *dmean = pb.mean;
     *fout = f;
     return CUGP_OK;
 }
@@ -1463,16 +1459,9 @@ int cugp_predict_sample(cugp_gp* g, const double* Xt, int nt, int with_noise, do
     int rc = predict_cov_device(g, Xt, nt, with_noise != 0, jitter, &dm, &f);
     if (rc) { (void)hipStreamSynchronize(g->stream); return rc; }
     const int ntpad = f->npad, nspad = (nsamples + TILE - 1) / TILE * TILE;
-    const size_t nz = (size_t)nspad * ntpad, need = 2 * nz + (size_t)nsamples * nt;
-    if (need > g->samp_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->samp_buf) (void)hipFree(g->samp_buf);
-        g->samp_buf = nullptr;
-        g->samp_cap = 0;
-        HIPCHK(hipMalloc((void**)&g->samp_buf, need * sizeof(double)));
-        g->samp_cap = need;
-    }
-    double* dZ = g->samp_buf;
+    const size_t nz = (size_t)nspad * ntpad;
+    if ((rc = g->samp.grow(2 * nz + (size_t)nsamples * nt, g->stream))) return rc;
+    double* dZ = g->samp.p;
     double* dF = dZ + nz;
     double* dS = dF + nz;
     // the factor handle's stream goes on behind Sigma (an event, no host wait): C = chol(Sigma), F = Z C^T, + mean
@@ -1636,7 +1625,7 @@ int la_factor_inverse(cugp_gp* g, bool inverse)
     TuneScope ts(g);
     if ((rc = enqueue_potrf(g, inverse))) return rc;
     HIPCHK(hipStreamSynchronize(g->stream));
-    if (barrier_expired(g)) return fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls");
+    if (barrier_expired(g->hout)) return fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls");
     g->factor_valid = true;
     g->inverse_valid = inverse;
     return CUGP_OK;
@@ -1681,7 +1670,7 @@ static int la_solve(int n, const double* K, const double* y, double* x, double* 
             e = hipMemcpyAsync(x, g->dalpha, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
         if (e != hipSuccess) rc = fail(CUGP_ERR_DEVICE, "la_solve", e);
-        else if (barrier_expired(g)) rc = fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls");
+        else if (barrier_expired(g->hout)) rc = fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls");
         else {
             if (quad) *quad = g->hout[4];
             if (logdet) *logdet = g->hout[5];
@@ -1774,7 +1763,6 @@ int cugp_get_kernel_stats(cugp_gp* g, double* sum_ms, long long* launches, doubl
 }
 
 void* cugp_get_stream(cugp_gp* g) { return g ? (void*)g->stream : nullptr; }
-const double* cugp_result_row_device(cugp_gp* g) { return g ? g->dout : nullptr; }
 
 // ---------------------------------------------------------------- optimiser glue
 namespace {
@@ -1950,7 +1938,7 @@ int cugp_bench_la_check(int op, int n, int device, int reps, double* ms, double*
         float t = 0;
         if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
         if (r > 0 && t < best) best = t;                          // first round warms up
-        if (e == hipSuccess && barrier_expired(g)) rc = fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls");
+        if (e == hipSuccess && barrier_expired(g->hout)) rc = fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls");
     }
     if (logdet && rc == CUGP_OK && e == hipSuccess) {
         *logdet = NAN;
@@ -2005,8 +1993,7 @@ struct cugp_group {
     hipGraphExec_t gexec[2] = {nullptr, nullptr};
     unsigned gepoch[2] = {0, 0};
     bool pending = false, pending_grad = false;   // an evaluation is enqueued and not yet fetched
-    double* pred_buf = nullptr;     // grouped prediction scratch (test inputs, [expert][ntpad][npad] Ks and W), grow-only
-    size_t pred_cap = 0;            // ... in doubles
+    Scratch pred;                   // grouped prediction scratch (predict_passes: test inputs, [expert][ntpad][npad] Ks and W)
 };
 
 int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
@@ -2049,7 +2036,7 @@ void cugp_group_destroy(cugp_group* gr)
     if (gr->ctx.tickets) (void)hipFree(gr->ctx.tickets);
     if (gr->ctx.dout) (void)hipFree(gr->ctx.dout);
     if (gr->ctx.hout) (void)hipHostFree(gr->ctx.hout);
-    if (gr->pred_buf) (void)hipFree(gr->pred_buf);
+    gr->pred.release();
     delete gr;
 }
 
@@ -2071,6 +2058,15 @@ static int write_group_table(cugp_group* gr)
     return CUGP_OK;
 }
 
+// the experts share launches only at one set of hyper-parameters (a NaN matches none)
+static bool same_loghyper(const cugp_group* gr)
+{
+    const cugp_gp* lead = gr->experts[0];
+    for (const cugp_gp* e : gr->experts)
+        if (e->hp[0] != lead->hp[0] || e->hp[1] != lead->hp[1] || e->hp[2] != lead->hp[2]) return false;
+    return true;
+}
+
 // Enqueue one evaluation of all experts of the group on the lead expert's stream(s); results stay on the device
 // (ctx.dout, [k][8]) and travel to the pinned ctx.hout behind it.  cugp_group_fetch waits and reads them.
 int cugp_group_enqueue(cugp_group* gr, int want_grad)
@@ -2084,10 +2080,9 @@ int cugp_group_enqueue(cugp_group* gr, int want_grad)
     if (nt > lead->tune[TUNE_GROUP_MAX_TILES]) return CUGP_ERR_INVALID;
     // the batched step kernel puts its workgroups on gridDim.y (65535 at most): larger experts go one by one
     if ((long long)nt * (nt + 1) / 2 + 16 > 65535) return CUGP_ERR_INVALID;
-    for (cugp_gp* e : gr->experts) {
+    if (!same_loghyper(gr)) return CUGP_ERR_INVALID;
+    for (cugp_gp* e : gr->experts)
         if (!e->have_data || e->prof != 0 || pipe_block(e, want_grad != 0) != 0) return CUGP_ERR_INVALID;   // (experts of a BCM have their own overlap off)
-        if (e->hp[0] != lead->hp[0] || e->hp[1] != lead->hp[1] || e->hp[2] != lead->hp[2]) return CUGP_ERR_INVALID;
-    }
     if ((rc = use_device(lead))) return rc;
     for (cugp_gp* e : gr->experts) {
         if ((rc = fetch_eval(e))) return rc;
@@ -2108,33 +2103,10 @@ int cugp_group_enqueue(cugp_group* gr, int want_grad)
         gr->ctx.gcap = gr->ctx.overlap && cap >= 16 ? cap / 2 : cap;
     }
     lead->grp = &gr->ctx;
-    const int gi = want_grad ? 1 : 0;
     // (with the hand-over the sequence spans several streams: enqueued launch by launch, not replayed)
-    if (lead->tune[TUNE_GRAPHS] != 0 && nt <= GRAPH_MAX_TILES && pipe_block(lead, want_grad != 0) == 0 &&
-        panel_width(lead) == 1) {
-        if (!gr->gexec[gi] || gr->gepoch[gi] != lead->cfg_epoch) {
-            if (gr->gexec[gi]) (void)hipGraphExecDestroy(gr->gexec[gi]);
-            gr->gexec[gi] = nullptr;
-            hipGraph_t graph_obj = nullptr;
-            hipError_t e = hipStreamBeginCapture(lead->stream, hipStreamCaptureModeThreadLocal);
-            if (e != hipSuccess) { lead->grp = nullptr; return fail(CUGP_ERR_DEVICE, "hipStreamBeginCapture", e); }
-            rc = record_eval(lead, want_grad != 0, lead->dhs);
-            e = hipStreamEndCapture(lead->stream, &graph_obj);   // always leave capture mode
-            if (rc == CUGP_OK && e == hipSuccess) e = hipGraphInstantiate(&gr->gexec[gi], graph_obj, nullptr, nullptr, 0);
-            if (graph_obj) (void)hipGraphDestroy(graph_obj);
-            if (rc || e != hipSuccess) {
-                gr->gexec[gi] = nullptr;
-                lead->grp = nullptr;
-                return rc ? rc : fail(CUGP_ERR_DEVICE, "group graph capture", e);
-            }
-            gr->gepoch[gi] = lead->cfg_epoch;
-        }
-        rc = CUGP_OK;
-        const hipError_t e = hipGraphLaunch(gr->gexec[gi], lead->stream);
-        if (e != hipSuccess) rc = fail(CUGP_ERR_DEVICE, "hipGraphLaunch", e);
-    } else {
-        rc = record_eval(lead, want_grad != 0, lead->dhs);
-    }
+    const bool graph = lead->tune[TUNE_GRAPHS] != 0 && nt <= GRAPH_MAX_TILES && pipe_block(lead, want_grad != 0) == 0 &&
+                       panel_width(lead) == 1;
+    rc = graph ? replay_eval(lead, gr->gexec, gr->gepoch, want_grad != 0) : record_eval(lead, want_grad != 0, lead->dhs);
     lead->grp = nullptr;
     if (rc) return rc;
     gr->pending = true;
@@ -2152,32 +2124,17 @@ int cugp_group_fetch(cugp_group* gr, double* ll, double* g)
     if ((rc = use_device(lead))) return rc;
     HIPCHK(hipStreamSynchronize(lead->stream));
     gr->pending = false;
-    bool timed_out = false;
-    for (int i = 0; i < k; i++)
-        if (gr->ctx.hout[(size_t)i * 8 + 6] != 0.0) { gr->ctx.hout[(size_t)i * 8 + 6] = 0.0; timed_out = true; }
-    if (timed_out) {                                          // (see fetch_eval)
-        for (cugp_gp* e : gr->experts) {
-            e->factor_valid = e->inverse_valid = false;
-            e->last_ll = e->last_quad = e->last_logdet = NAN;
-            e->last_g[0] = e->last_g[1] = e->last_g[2] = NAN;
-        }
+    bool ok = true;                                           // (every expert's row is read: every status word cleared)
+    for (int i = 0; i < k; i++) ok = read_result_row(gr->experts[i], gr->ctx.hout + (size_t)i * 8, gr->pending_grad) && ok;
+    if (!ok) {                                                // (see fetch_eval)
+        for (cugp_gp* e : gr->experts) discard_eval(e);
         return fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls (the group's evaluation was abandoned)");
     }
     for (int i = 0; i < k; i++) {
-        cugp_gp* e = gr->experts[i];
-        const double* h = gr->ctx.hout + (size_t)i * 8;
-        e->last_ll = h[0];
-        e->last_quad = h[4];
-        e->last_logdet = h[5];
-        e->factor_valid = true;
-        ll[i] = h[0];
-        if (gr->pending_grad) {
-            for (int j = 0; j < 3; j++) {
-                e->last_g[j] = h[1 + j];
-                if (g) g[3 * i + j] = h[1 + j];
-            }
-            e->inverse_valid = true;
-        }
+        const cugp_gp* e = gr->experts[i];
+        ll[i] = e->last_ll;
+        if (gr->pending_grad && g)
+            for (int j = 0; j < 3; j++) g[3 * i + j] = e->last_g[j];
     }
     return CUGP_OK;
 }
@@ -2221,40 +2178,13 @@ int cugp_group_predict_enqueue(cugp_group* gr, const double* Xt, int nt, double*
     const int k = (int)gr->experts.size();
     int rc;
     if (gr->pending) return fail(CUGP_ERR_BUSY, "cugp_group_predict_enqueue: an evaluation is in flight");
-    for (cugp_gp* e : gr->experts) {
+    if (!same_loghyper(gr)) return CUGP_ERR_INVALID;
+    for (cugp_gp* e : gr->experts)
         if (!cugp_has_inverse(e) || e->prof >= 3) return CUGP_ERR_INVALID;
-        if (e->hp[0] != lead->hp[0] || e->hp[1] != lead->hp[1] || e->hp[2] != lead->hp[2]) return CUGP_ERR_INVALID;
-    }
     if ((rc = use_device(lead))) return rc;
     TuneScope ts(lead);                                       // the group runs on the lead expert's tuning
     if (!gr->tab_valid && (rc = write_group_table(gr))) return rc;
-    const int chunk = pred_chunk_rows(lead, k, nt);
-    const int ntpad = ((chunk + TILE - 1) / TILE) * TILE;
-    const HyperScalars h = scalars(lead);
-    const size_t nxt = (((size_t)nt * lead->d + 15) / 16) * 16, nks = (size_t)k * ntpad * lead->npad;
-    const size_t need = nxt + 2 * nks;
-    if (need > gr->pred_cap) {
-        HIPCHK(hipStreamSynchronize(lead->stream));
-        if (gr->pred_buf) (void)hipFree(gr->pred_buf);
-        gr->pred_buf = nullptr;
-        gr->pred_cap = 0;
-        HIPCHK(hipMalloc((void**)&gr->pred_buf, need * sizeof(double)));
-        gr->pred_cap = need;
-    }
-    double* dXt = gr->pred_buf;
-    double* dKs = dXt + nxt;
-    double* dW = dKs + nks;
-    const Batch bt = gr->ctx.bt;
-    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * lead->d * sizeof(double), hipMemcpyHostToDevice, lead->stream));
-    for (int t0 = 0; t0 < nt; t0 += chunk) {
-        const int c = nt - t0 < chunk ? nt - t0 : chunk;
-        const int cpad = ((c + TILE - 1) / TILE) * TILE;
-        launch_kcross(nullptr, 0, lead->d, lead->npad, dXt + (size_t)t0 * lead->d, c, cpad, h, dKs, lead->stream, bt);
-        launch_predict_gemm(dKs, nullptr, dW, lead->npad, cpad / TILE, lead->nt, lead->stream, bt);
-        launch_predict_finish(dKs, dW, nullptr, 0, lead->npad, c, h, nullptr, nullptr, lead->stream, drows + t0,
-                              row_stride, nt, cpad, bt);
-    }
-    HIPCHK(hipGetLastError());
+    if ((rc = predict_passes(lead, gr->ctx.bt, Xt, nt, pred_chunk_rows(lead, k, nt), gr->pred, drows, row_stride))) return rc;
     *stream = (void*)lead->stream;
     return CUGP_OK;
 }

@@ -6,6 +6,17 @@
 
 struct cugp_group;
 
+// Scratch of doubles that only grows (the allocations cost more than the kernels using it): device memory, or pinned host
+// memory when `pinned`.  grow() first synchronises `stream` (hipStream_t; none when null), which may still read the old
+// buffer; a failed allocation leaves {nullptr, 0} and returns CUGP_ERR_NOMEM / CUGP_ERR_DEVICE (cugp_last_error).
+struct Scratch {
+    double* p = nullptr;
+    size_t cap = 0;                  // in doubles
+    bool pinned = false;
+    int grow(size_t count, void* stream);
+    void release();
+};
+
 extern "C" {
 
 // experts must live on one device and agree in padded size and dimension (else CUGP_ERR_INVALID)
@@ -31,8 +42,7 @@ int cugp_internal_fail(int code, const char* what);
 // halves of cugp_bcm_loglik_grad_allgather (comm.cpp; defined in bcm.cpp)
 int cugp_bcm_enqueue_rows_packed(cugp_bcm* b, double* dsend, void** stream);
 int cugp_bcm_finish_rows(cugp_bcm* b);
-// device copy of a single expert's result row ([8] doubles, valid once its stream -- cugp_get_stream -- has run)
-const double* cugp_result_row_device(cugp_gp* gp);
+// {LL, g0, g1, g2} of the evaluation a single expert has in flight -> dst (device), on the expert's stream
 int cugp_copy_result_row(cugp_gp* gp, double* dst);
 // cugp_predict_cov without the copy to the host (tools/pred_joint_probe.py times the device part with it): Sigma is
 // computed, the handle's stream is waited for, and *dcov / *ld give the device matrix (lower tiles valid, row-major,
