@@ -17,6 +17,7 @@ _ip = C.POINTER(C.c_int)
 OBJECTIVE = C.CFUNCTYPE(None, C.c_void_p, _dp, _dp, _dp)
 VALUE_FN = C.CFUNCTYPE(None, C.c_void_p, _dp, _dp)
 GRADIENT_FN = C.CFUNCTYPE(None, C.c_void_p, _dp, _dp)
+OBJECTIVE_N = C.CFUNCTYPE(None, C.c_void_p, _dp, C.c_int, _dp, _dp)
 
 CUGP_OK = 0
 CUGP_ERR_INVALID, CUGP_ERR_NOMEM, CUGP_ERR_DEVICE, CUGP_ERR_NODEVICE = -1, -2, -3, -4
@@ -45,6 +46,12 @@ SIGNATURES = {
     "cugp_set_data_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cugp_set_loghyper": (C.c_int, [C.c_void_p, _dp]),
     "cugp_get_loghyper": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_create_ard": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_num_hyper": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_loglik_grad_ard": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
+    "cugp_loglik_grad_fetch_ard": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
     "cugp_loglik": (C.c_int, [C.c_void_p, _dp]),
     "cugp_loglik_grad": (C.c_int, [C.c_void_p, _dp, _dp]),
     "cugp_grad": (C.c_int, [C.c_void_p, _dp]),
@@ -77,6 +84,8 @@ SIGNATURES = {
     "cugp_cg_minimize_sparing": (C.c_int, [VALUE_FN, GRADIENT_FN, C.c_void_p, _dp, C.c_int, _dp, C.c_int, _ip, _ip]),
     "cugp_cg_solve_sparing": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip, _ip]),
     "cugp_rprop_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_cg_minimize_n": (C.c_int, [OBJECTIVE_N, C.c_void_p, _dp, C.c_int, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_cg_solve_ard": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_bcm_create": (C.c_int, [C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_bcm_create_split": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_bcm_create_multi": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_void_p)]),

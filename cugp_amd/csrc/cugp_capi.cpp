@@ -112,9 +112,14 @@ struct cugp_gp {
     double* dout = nullptr;
     unsigned* dtickets = nullptr;  // [0, nt): one arrival counter per factorisation step (k_syrk_step); [nt, 2 nt): the stage
                                    // counter of the hand-over block that starts at that tile row (k_trtri_block)
-    double* hout = nullptr;        // pinned, 8 doubles
+    double* hout = nullptr;        // pinned, 8 doubles (ARD: 8 + d + 2)
     int nblocks_trace = 0;
     double hp[3] = {0, 0, 0};
+    // ARD handle (cugp_create_ard; for life): theta = [log l_1 .. log l_d, log sigma_f, log sigma_n] in hpa; hp[] mirrors
+    // {0, hpa[d], hpa[d + 1]} so that scalars() gives {1, sf2, sn2}.  hhs / dhs then hold the hyper-scalars FOLLOWED by
+    // the d weights exp(-theta_c); result rows are 8 + d + 2 doubles (kernels.h: ARD_ROW_GRAD)
+    bool ard = false;
+    std::vector<double> hpa, last_ga;
     bool have_data = false;
     bool factor_valid = false;     // A holds L for (data, hp)
     bool inverse_valid = false;    // T, U, Kinv, alpha hold the inverse quantities for (data, hp)
@@ -170,6 +175,31 @@ HyperScalars scalars(const cugp_gp* g)
 {
     // covkernel.cpp:65-67 -- exp(2*theta) on the host
     return HyperScalars{std::exp(g->hp[0] * 2), std::exp(g->hp[1] * 2), std::exp(g->hp[2] * 2)};
+}
+
+size_t hs_bytes(const cugp_gp* g) { return sizeof(HyperScalars) + (g->ard ? (size_t)g->d * sizeof(double) : 0); }
+
+// ARD: the pinned staging area always holds the current theta's scalars and weights (written where theta is set, with
+// the handle's stream idle), so every user of the ARD kernels only has to enqueue the copy in front of its launches
+void stage_ard(cugp_gp* g)
+{
+    *g->hhs = scalars(g);
+    double* w = (double*)(g->hhs + 1);
+    for (int c = 0; c < g->d; c++) w[c] = std::exp(-g->hpa[c]);
+}
+
+int upload_hs(cugp_gp* g, hipStream_t s)
+{
+    HIPCHK(hipMemcpyAsync(g->dhs, g->hhs, hs_bytes(g), hipMemcpyHostToDevice, s));
+    return CUGP_OK;
+}
+
+int refuse_ard(const cugp_gp* g, const char* call, const char* use)
+{
+    if (!g->ard) return CUGP_OK;
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: the handle is ARD (d + 2 hyper-parameters); use %s", call, use);
+    return fail(CUGP_ERR_INVALID, buf);
 }
 
 int use_device(const cugp_gp* g)
@@ -803,13 +833,14 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
     int rc;
     const HyperScalars h = scalars(g);
     hipStream_t s = g->stream;
-    if (hd) HIPCHK(hipMemcpyAsync(g->dhs, g->hhs, sizeof(HyperScalars), hipMemcpyHostToDevice, s));
+    if (hd && (rc = upload_hs(g, s))) return rc;
     if ((rc = phase_mark(g, 0))) return rc;
     unsigned* const tickets = g->grp ? g->grp->tickets : g->dtickets;
     if ((rc = reset_stamps(g))) return rc;
     {
         TimedLaunch tl(g, s, g->prof >= 5);
-        launch_kbuild(g->dX, g->n, g->d, g->npad, h, g->dA, false, s, hd, B(g), tickets);   // also zeroes the step tickets
+        if (g->ard) launch_kbuild_ard(g->dX, g->n, g->d, g->npad, hd, g->dA, false, s, tickets);
+        else launch_kbuild(g->dX, g->n, g->d, g->npad, h, g->dA, false, s, hd, B(g), tickets);   // also zeroes the step tickets
         // (bytes, not flop: the lower 64x64 tiles of K written once + X read)
         tl.done(KIND_BUILD, (double)trace_num_blocks(g->npad) * 64 * 64 * 8 + (double)g->n * g->d * 8);
     }
@@ -834,8 +865,12 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
             launch_trmv_upper(g->dU, g->npad, g->npad, g->dz, g->dalpha, s, B(g));    // alpha = L^-T z
         }
         // traces and the final sums in ONE launch: the last block of k_trace finishes the evaluation (kernels.hip)
-        launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, hd, B(g), g->dz, g->dlogdet, g->dout,
-                     host_out(g), tickets + 2 * g->nt);
+        if (g->ard)
+            launch_trace_ard(g->dX, g->n, g->d, g->npad, hd, g->dKinv, g->dalpha, g->dpart, g->dz, g->dlogdet, g->dout,
+                             g->hout, s);
+        else
+            launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, hd, B(g), g->dz, g->dlogdet,
+                         g->dout, host_out(g), tickets + 2 * g->nt);
     } else {
         if ((rc = phase_mark(g, 3))) return rc;
         if ((rc = phase_mark(g, 4))) return rc;
@@ -895,8 +930,9 @@ int enqueue_eval(cugp_gp* g, bool want_grad)
     // (measured: 16 x 1500 rows 4.7 -> 4.1 ms, 2 x 1500 rows 1.25 -> 1.18 ms; nothing to gain above ~3000 rows)
     const bool graph = g->tune[TUNE_GRAPHS] != 0 && g->prof == 0 && g->nt <= GRAPH_MAX_TILES &&
                        pipe_block(g, want_grad) == 0;
-    if (graph) *g->hhs = scalars(g);
-    if ((rc = graph ? replay_eval(g, g->gexec, g->gepoch, want_grad) : record_eval(g, want_grad, nullptr))) return rc;
+    if (graph && !g->ard) *g->hhs = scalars(g);              // (ARD: staged where theta was set, weights included)
+    if ((rc = graph ? replay_eval(g, g->gexec, g->gepoch, want_grad)
+                    : record_eval(g, want_grad, g->ard ? g->dhs : nullptr))) return rc;
     g->pending = true;
     g->pending_grad = want_grad;
     g->pev_valid = g->prof >= 1;
@@ -925,8 +961,14 @@ int enqueue_continue(cugp_gp* g)
     if ((rc = enqueue_inverse_block(g, 0, g->nt, true, s, nullptr, nullptr))) return rc;
     launch_trmv_lower(g->dT, g->npad, g->npad, g->dy, g->dz, s);
     launch_trmv_upper(g->dU, g->npad, g->npad, g->dz, g->dalpha, s);
-    launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, nullptr, {}, g->dz, g->dlogdet, g->dout, g->hout,
-                 g->dtickets + 2 * g->nt);
+    if (g->ard) {
+        if ((rc = upload_hs(g, s))) return rc;
+        launch_trace_ard(g->dX, g->n, g->d, g->npad, g->dhs, g->dKinv, g->dalpha, g->dpart, g->dz, g->dlogdet, g->dout,
+                         g->hout, s);
+    } else {
+        launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, nullptr, {}, g->dz, g->dlogdet, g->dout,
+                     g->hout, g->dtickets + 2 * g->nt);
+    }
     HIPCHK(hipGetLastError());
     g->pending = true;
     g->pending_grad = true;
@@ -949,6 +991,7 @@ void discard_eval(cugp_gp* g)
     g->factor_valid = g->inverse_valid = false;
     g->last_ll = g->last_quad = g->last_logdet = NAN;
     g->last_g[0] = g->last_g[1] = g->last_g[2] = NAN;
+    for (double& v : g->last_ga) v = NAN;
 }
 
 // The results of g's evaluation from its 8-double host row (host_out) -- or, when a bounded wait inside a kernel ran out
@@ -964,7 +1007,10 @@ bool read_result_row(cugp_gp* g, double* row, bool grad)
     g->last_logdet = row[5];
     g->factor_valid = true;
     if (grad) {
-        for (int i = 0; i < 3; i++) g->last_g[i] = row[1 + i];
+        if (g->ard)
+            for (size_t i = 0; i < g->last_ga.size(); i++) g->last_ga[i] = row[ARD_ROW_GRAD + i];
+        else
+            for (int i = 0; i < 3; i++) g->last_g[i] = row[1 + i];
         g->inverse_valid = true;
     }
     return true;
@@ -1008,7 +1054,16 @@ int cugp_device_count(int* count)
 
 int cugp_create(int n, int d, int device, cugp_gp** out) { return cugp_create_padded(n, d, device, 0, out); }
 
+static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out);
+
 int cugp_create_padded(int n, int d, int device, int npad_min, cugp_gp** out)
+{
+    return create_handle(n, d, device, npad_min, false, out);
+}
+
+int cugp_create_ard(int n, int d, int device, cugp_gp** out) { return create_handle(n, d, device, 0, true, out); }
+
+static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out)
 {
     if (!out || n <= 0 || d <= 0) return fail(CUGP_ERR_INVALID, "cugp_create: n, d must be positive");
     int cnt = 0;
@@ -1018,6 +1073,9 @@ int cugp_create_padded(int n, int d, int device, int npad_min, cugp_gp** out)
     cugp_gp* g = new (std::nothrow) cugp_gp;
     if (!g) return fail(CUGP_ERR_NOMEM, "host allocation");
     g->n = n; g->d = d; g->device = device;
+    g->ard = ard;
+    if (ard) { g->hpa.assign((size_t)d + 2, 0.0); g->last_ga.assign((size_t)d + 2, NAN); }
+    const size_t nrow = ard ? (size_t)ARD_ROW_GRAD + d + 2 : 8, ncol = ard ? (size_t)d + 2 : 3;
     g->nt = ((n > npad_min ? n : npad_min) + TILE - 1) / TILE;
     g->npad = g->nt * TILE;
     g->nblocks_trace = trace_num_blocks(g->npad);
@@ -1057,13 +1115,14 @@ int cugp_create_padded(int n, int d, int device, int npad_min, cugp_gp** out)
     if (e == hipSuccess) e = hipMalloc((void**)&g->d16, (size_t)g->nt * 8 * 256 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&g->d64, (size_t)g->nt * 8192 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&g->dlogdet, (size_t)g->nt * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->dpart, (size_t)g->nblocks_trace * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->dout, 8 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->dpart, (size_t)g->nblocks_trace * ncol * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&g->dout, nrow * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&g->dtickets, (size_t)ticket_count(g->nt) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&g->hout, 8 * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) memset(g->hout, 0, 8 * sizeof(double));   // (entry 6 is the status word fetch_eval reads)
-    if (e == hipSuccess) e = hipHostMalloc((void**)&g->hhs, sizeof(HyperScalars), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->dhs, sizeof(HyperScalars));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&g->hout, nrow * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) memset(g->hout, 0, nrow * sizeof(double));   // (entry 6 is the status word fetch_eval reads)
+    if (e == hipSuccess) e = hipHostMalloc((void**)&g->hhs, hs_bytes(g), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&g->dhs, hs_bytes(g));
+    if (e == hipSuccess && ard) stage_ard(g);
     for (int i = 0; i <= NPHASE && e == hipSuccess; i++) e = hipEventCreate(&g->pev[i]);
     if (e != hipSuccess) {
         int code = fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, "cugp_create", e);
@@ -1156,6 +1215,7 @@ int cugp_set_loghyper(cugp_gp* g, const double hp[3])
 {
     if (!g || !hp) return CUGP_ERR_INVALID;
     int rc;
+    if ((rc = refuse_ard(g, "cugp_set_loghyper", "cugp_set_loghyper_ard"))) return rc;
     if ((rc = fetch_eval(g))) return rc;
     if (hp[0] != g->hp[0] || hp[1] != g->hp[1] || hp[2] != g->hp[2] || std::isnan(hp[0] + hp[1] + hp[2]))
         g->factor_valid = g->inverse_valid = false;
@@ -1166,7 +1226,60 @@ int cugp_set_loghyper(cugp_gp* g, const double hp[3])
 int cugp_get_loghyper(const cugp_gp* g, double hp[3])
 {
     if (!g || !hp) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard(g, "cugp_get_loghyper", "cugp_get_loghyper_ard")) return rc;
     for (int i = 0; i < 3; i++) hp[i] = g->hp[i];
+    return CUGP_OK;
+}
+
+// the _ard calls' common argument check, before any device call: no null argument and a possible nh (the handle is not
+// looked at before that), then an ARD handle and nh == d + 2
+static int want_ard(const cugp_gp* g, int nh, const char* call, bool pointers_ok = true)
+{
+    char buf[256];
+    if (!g || !pointers_ok || nh < 3) {
+        snprintf(buf, sizeof buf, "%s: null argument or nh < 3", call);
+        return fail(CUGP_ERR_INVALID, buf);
+    }
+    if (!g->ard) {
+        snprintf(buf, sizeof buf, "%s: the handle is isotropic (3 hyper-parameters); create it with cugp_create_ard", call);
+        return fail(CUGP_ERR_INVALID, buf);
+    }
+    if (nh != g->d + 2) {
+        snprintf(buf, sizeof buf, "%s: nh = %d, the handle has d + 2 = %d hyper-parameters", call, nh, g->d + 2);
+        return fail(CUGP_ERR_INVALID, buf);
+    }
+    return CUGP_OK;
+}
+
+int cugp_num_hyper(const cugp_gp* g, int* nh)
+{
+    if (!g || !nh) return fail(CUGP_ERR_INVALID, "cugp_num_hyper: null argument");
+    *nh = g->ard ? g->d + 2 : 3;
+    return CUGP_OK;
+}
+
+int cugp_set_loghyper_ard(cugp_gp* g, const double* hp, int nh)
+{
+    int rc;
+    if ((rc = want_ard(g, nh, "cugp_set_loghyper_ard", hp != nullptr))) return rc;
+    if ((rc = fetch_eval(g))) return rc;
+    bool changed = false;
+    for (int i = 0; i < nh; i++) changed = changed || hp[i] != g->hpa[i] || std::isnan(hp[i]);
+    if (!changed) return CUGP_OK;
+    // the staging area may still be read by a copy enqueued for a prediction: let the stream run dry before it changes
+    if ((rc = use_device(g))) return rc;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    g->factor_valid = g->inverse_valid = false;
+    for (int i = 0; i < nh; i++) g->hpa[i] = hp[i];
+    g->hp[0] = 0.0; g->hp[1] = hp[g->d]; g->hp[2] = hp[g->d + 1];
+    stage_ard(g);
+    return CUGP_OK;
+}
+
+int cugp_get_loghyper_ard(const cugp_gp* g, double* hp, int nh)
+{
+    if (const int rc = want_ard(g, nh, "cugp_get_loghyper_ard", hp != nullptr)) return rc;
+    for (int i = 0; i < nh; i++) hp[i] = g->hpa[i];
     return CUGP_OK;
 }
 
@@ -1182,6 +1295,7 @@ int cugp_loglik_grad_fetch(cugp_gp* g, double* ll, double gr[3])
 {
     if (!g) return CUGP_ERR_INVALID;
     int rc;
+    if (gr && (rc = refuse_ard(g, "cugp_loglik_grad_fetch", "cugp_loglik_grad_fetch_ard"))) return rc;
     if ((rc = fetch_eval(g))) return rc;
     if (ll) *ll = g->last_ll;
     if (gr)
@@ -1206,6 +1320,7 @@ int cugp_loglik_grad(cugp_gp* g, double* ll, double gr[3])
 {
     if (!g) return CUGP_ERR_INVALID;
     int rc;
+    if (gr && (rc = refuse_ard(g, "cugp_loglik_grad", "cugp_loglik_grad_ard"))) return rc;
     if ((rc = fetch_eval(g))) return rc;
     if (!g->inverse_valid) {
         // a valid factor (cugp_loglik came first at the same point) is continued, not recomputed
@@ -1218,7 +1333,33 @@ int cugp_loglik_grad(cugp_gp* g, double* ll, double gr[3])
     return CUGP_OK;
 }
 
-int cugp_grad(cugp_gp* g, double gr[3]) { return cugp_loglik_grad(g, nullptr, gr); }
+int cugp_grad(cugp_gp* g, double gr[3])
+{
+    if (!g) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard(g, "cugp_grad", "cugp_loglik_grad_ard")) return rc;
+    return cugp_loglik_grad(g, nullptr, gr);
+}
+
+int cugp_loglik_grad_fetch_ard(cugp_gp* g, double* ll, double* gr, int nh)
+{
+    int rc;
+    if ((rc = want_ard(g, nh, "cugp_loglik_grad_fetch_ard"))) return rc;
+    if ((rc = fetch_eval(g))) return rc;
+    if (ll) *ll = g->last_ll;
+    if (gr)
+        for (int i = 0; i < nh; i++) gr[i] = g->last_ga[i];
+    return CUGP_OK;
+}
+
+int cugp_loglik_grad_ard(cugp_gp* g, double* ll, double* gr, int nh)
+{
+    int rc;
+    if ((rc = want_ard(g, nh, "cugp_loglik_grad_ard", ll && gr))) return rc;
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // (the evaluation itself is shared)
+    *ll = g->last_ll;
+    for (int i = 0; i < nh; i++) gr[i] = g->last_ga[i];
+    return CUGP_OK;
+}
 
 int cugp_last_quad_logdet(const cugp_gp* g, double* quad, double* logdet)
 {
@@ -1266,7 +1407,12 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
         const int c = nt - t0 < chunk ? nt - t0 : chunk;
         const int cpad = ((c + TILE - 1) / TILE) * TILE;
         // (batched: X, n, T, alpha come from the table; k_predict_finish reads rstride and its cpad only then)
-        launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream, bt);
+        if (g->ard) {
+            if ((rc = upload_hs(g, g->stream))) return rc;
+            launch_kcross_ard(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, g->dhs, dKs, g->stream);
+        } else {
+            launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream, bt);
+        }
         {
             // W = Ks L^-T: test tile tt, row tile ti sums k <= ti (the diagonal k tile of T is triangular: counted half)
             TimedLaunch tl(g, g->stream, !bt.tab && g->prof >= 3);
@@ -1406,8 +1552,14 @@ static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_no
         launch_predict_cov(pb.w, g->npad, ntpad, cs, f->dA, g->cov_scr.p, g->stream);
         tl.done(KIND_COV, 2.0 * cs.tiles * (32.0 * cs.wm) * (32.0 * cs.wm) * cs.kend);
     }
-    launch_predict_cov_finish(pb.xt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr.p, cs.split - 1,
-                              f->dtickets, g->stream);
+    if (g->ard) {
+        if ((rc = upload_hs(g, g->stream))) return rc;
+        launch_predict_cov_finish_ard(pb.xt, nt, g->d, ntpad, g->dhs, with_noise, jitter, f->dA, g->cov_scr.p,
+                                      cs.split - 1, f->dtickets, g->stream);
+    } else {
+        launch_predict_cov_finish(pb.xt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr.p,
+                                  cs.split - 1, f->dtickets, g->stream);
+    }
     HIPCHK(hipGetLastError());
     *dmean = pb.mean;
     *fout = f;
@@ -1502,7 +1654,12 @@ int cugp_compute_K_train(cugp_gp* g, double* K)
     if ((rc = ensure(&g->dA, (size_t)g->npad * g->npad))) return rc;
     g->factor_valid = g->inverse_valid = false;
     TuneScope ts(g);
-    launch_kbuild(g->dX, g->n, g->d, g->npad, scalars(g), g->dA, true, g->stream);
+    if (g->ard) {
+        if ((rc = upload_hs(g, g->stream))) return rc;
+        launch_kbuild_ard(g->dX, g->n, g->d, g->npad, g->dhs, g->dA, true, g->stream);
+    } else {
+        launch_kbuild(g->dX, g->n, g->d, g->npad, scalars(g), g->dA, true, g->stream);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2DAsync(K, (size_t)g->n * sizeof(double), g->dA, (size_t)g->npad * sizeof(double),
                             (size_t)g->n * sizeof(double), g->n, hipMemcpyDeviceToHost, g->stream));
@@ -1515,6 +1672,8 @@ int cugp_compute_squared_dist(cugp_gp* g, double c, double* S)
     if (!g || !S) return CUGP_ERR_INVALID;
     if (!g->have_data) return fail(CUGP_ERR_INVALID, "no training data set");
     int rc;
+    if ((rc = refuse_ard(g, "cugp_compute_squared_dist", "cugp_compute_K_train (an ARD handle has no single length scale to divide by)")))
+        return rc;
     if ((rc = use_device(g))) return rc;
     if ((rc = fetch_eval(g))) return rc;
     if ((rc = ensure(&g->dA, (size_t)g->npad * g->npad))) return rc;
@@ -1540,7 +1699,12 @@ int cugp_compute_k_test(cugp_gp* g, const double* Xt, int nt, double* Ks)
     if (e == hipSuccess) e = hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) {
         TuneScope ts(g);
-        launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, scalars(g), dKs, g->stream);
+        if (g->ard) {
+            e = hipMemcpyAsync(g->dhs, g->hhs, hs_bytes(g), hipMemcpyHostToDevice, g->stream);
+            launch_kcross_ard(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, g->dhs, dKs, g->stream);
+        } else {
+            launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, scalars(g), dKs, g->stream);
+        }
         e = hipMemcpy2DAsync(Ks, (size_t)g->n * sizeof(double), dKs, (size_t)g->npad * sizeof(double),
                              (size_t)g->n * sizeof(double), nt, hipMemcpyDeviceToHost, g->stream);
     }
@@ -1779,6 +1943,7 @@ void gp_objective(void* ctx, const double th[3], double* f, double gr[3])
 int cugp_cg_solve(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
 {
     if (!g) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard(g, "cugp_cg_solve", "cugp_cg_solve_ard")) return rc;
     double th[3] = {g->hp[0], g->hp[1], g->hp[2]};
     int rc = cugp_cg_minimize(gp_objective, g, th, budget, trace, trace_cap, nevals);
     if (rc) return rc;
@@ -1802,9 +1967,34 @@ void gp_gradient(void* ctx, const double th[3], double gr[3])
 }
 }  // namespace
 
+namespace {
+void gp_objective_ard(void* ctx, const double* th, int nh, double* f, double* gr)
+{
+    cugp_gp* g = (cugp_gp*)ctx;
+    double ll = NAN;
+    if (cugp_set_loghyper_ard(g, th, nh) != CUGP_OK || cugp_loglik_grad_ard(g, &ll, gr, nh) != CUGP_OK) {
+        ll = NAN;
+        for (int i = 0; i < nh; i++) gr[i] = NAN;
+    }
+    *f = -1.0 * ll;
+}
+}  // namespace
+
+int cugp_cg_solve_ard(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
+{
+    if (!g) return fail(CUGP_ERR_INVALID, "cugp_cg_solve_ard: null handle");
+    int rc;
+    if ((rc = want_ard(g, g->d + 2, "cugp_cg_solve_ard"))) return rc;
+    std::vector<double> th(g->hpa);
+    const int nh = (int)th.size();
+    if ((rc = cugp_cg_minimize_n(gp_objective_ard, g, th.data(), nh, budget, trace, trace_cap, nevals))) return rc;
+    return cugp_set_loghyper_ard(g, th.data(), nh);
+}
+
 int cugp_cg_solve_sparing(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals, int* ngrads)
 {
     if (!g) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard(g, "cugp_cg_solve_sparing", "cugp_cg_solve_ard")) return rc;
     double th[3] = {g->hp[0], g->hp[1], g->hp[2]};
     int rc = cugp_cg_minimize_sparing(gp_value, gp_gradient, g, th, budget, trace, trace_cap, nevals, ngrads);
     if (rc) return rc;
@@ -1814,6 +2004,7 @@ int cugp_cg_solve_sparing(cugp_gp* g, int budget, double* trace, int trace_cap, 
 int cugp_rprop_solve(cugp_gp* g, int iters, double* trace, int trace_cap, int* nevals)
 {
     if (!g) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard(g, "cugp_rprop_solve", "cugp_cg_solve_ard")) return rc;
     double th[3] = {g->hp[0], g->hp[1], g->hp[2]};
     int rc = cugp_rprop_minimize(gp_objective, g, th, iters, trace, trace_cap, nevals);
     if (rc) return rc;
@@ -2003,6 +2194,8 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
         if (!experts[i] || experts[i]->npad != experts[0]->npad || experts[i]->d != experts[0]->d ||
             experts[i]->device != experts[0]->device)
             return CUGP_ERR_INVALID;
+    for (int i = 0; i < k; i++)
+        if (experts[i]->ard) return fail(CUGP_ERR_INVALID, "cugp_group_create: ARD handles cannot be grouped (the exchange rows hold 3 gradients)");
     cugp_group* gr = new (std::nothrow) cugp_group;
     if (!gr) return fail(CUGP_ERR_NOMEM, "host allocation");
     gr->experts.assign(experts, experts + k);

@@ -76,6 +76,26 @@ void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S,
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
                    HyperScalars h, double* Ks, hipStream_t s, Batch bt = {});
 
+// ---- ARD: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart) ----
+// k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd: DEVICE
+// memory, the hyper-scalars (ell_sq unused) directly followed by the d weights -- one staging area, one copy, so a
+// replayed graph sees new length scales the way it sees new exp(2 theta).  Same tiles, stores and padding as the
+// isotropic launches above; single handles only (no batched experts).
+void launch_kbuild_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, double* K, bool full,
+                       hipStream_t s, unsigned* tickets = nullptr);
+void launch_kcross_ard(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
+                       const HyperScalars* hd, double* Ks, hipStream_t s);
+void launch_predict_cov_finish_ard(const double* Xt, int nt, int d, int ntpad, const HyperScalars* hd, bool with_noise,
+                                   double jitter, double* A, const double* scr, int nscr, unsigned* tickets,
+                                   hipStream_t s);
+// gradient traces and the final sums: part[(d + 2) * trace_num_blocks(npad)]; results row out / hout (8 + d + 2 doubles):
+// [0] LL, [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row), [8 + c] g_c, c = 0 .. d + 1.
+// Two launches (k_trace_ard, k_finalize_ard): there is no fused form of the final sums.
+constexpr int ARD_ROW_GRAD = 8;
+void launch_trace_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, const double* Kinv,
+                      const double* alpha, double* part, const double* z, const double* logdet_part, double* out,
+                      double* hout, hipStream_t s);
+
 // ---- blocked right-looking Cholesky (N4) on the lower triangle of A (npad x npad, ld = npad) ----
 // d16: 16x16 diagonal inverses [nt][8][256]; d64: the two 64x64 diagonal inverses of each block [nt][2][4096]
 void launch_potf2(double* A, int ld, int kb, double* d16, double* d64, double* logdet_part, hipStream_t s,

@@ -892,9 +892,14 @@ __device__ __forceinline__ int col4(int tx, int b) { return (b >> 1) * 32 + tx *
 
 // squared distances of a 4x4 micro-tile, accumulated over d in index order without FMA
 // contraction so that the value matches the reference's sub / mul / add sequence bit for bit
+// ARD: every difference is multiplied by its dimension's weight w_c = 1 / l_c before it is squared (the DIFFERENCE, not
+// the coordinates: x_a - y_b of nearby points stays exact); wts: the d weights in device memory, ws: LDS for the
+// current chunk's.  The isotropic instantiation is the code it was before the flag existed.
+template <bool ARD = false>
 __device__ __forceinline__ void sqdist_4x4(const double* __restrict__ X, const double* __restrict__ Y, int nx,
                                            int ny, int d, int i0, int j0, double (&xs)[KT][DC + 1],
-                                           double (&ys)[KT][DC + 1], double (&acc)[4][4])
+                                           double (&ys)[KT][DC + 1], double (&acc)[4][4],
+                                           const double* __restrict__ wts = nullptr, double* ws = nullptr)
 {
 #pragma clang fp contract(off)
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
@@ -910,16 +915,19 @@ __device__ __forceinline__ void sqdist_4x4(const double* __restrict__ X, const d
             xs[r][c] = (i0 + r < nx) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
             ys[r][c] = (j0 + r < ny) ? Y[(size_t)(j0 + r) * d + c0 + c] : 0.0;
         }
+        if (ARD && t < dc) ws[t] = wts[c0 + t];
         __syncthreads();
         for (int c = 0; c < dc; c++) {
             double xv[4], yv[4];
 #pragma unroll
             for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+            const double wc = ARD ? ws[c] : 1.0;
 #pragma unroll
             for (int a = 0; a < 4; a++)
 #pragma unroll
                 for (int b = 0; b < 4; b++) {
                     double df = xv[a] - yv[b];
+                    if (ARD) df = df * wc;
                     acc[a][b] = acc[a][b] + df * df;
                 }
         }
@@ -932,6 +940,8 @@ __device__ __forceinline__ void sqdist_4x4(const double* __restrict__ X, const d
 // from the ends of the exponent range (the optimisers do walk l^2 = exp(2 theta) to infinity: a / inf must stay 0,
 // 0 * inf is NaN): DivBy::y == 0 selects the real division (uniform over the launch).
 struct DivBy { double b, y; };
+// ARD handles keep the d per-dimension weights directly behind the hyper-scalars (one staging area, one copy)
+__device__ __forceinline__ const double* ard_weights(const HyperScalars* hd) { return (const double*)(hd + 1); }
 __device__ __forceinline__ DivBy div_prepare(double b)
 {
     return DivBy{b, (b > 1e-100 && b < 1e100) ? 1.0 / b : 0.0};
@@ -946,10 +956,13 @@ __device__ __forceinline__ double div_by(double a, const DivBy& d)
 
 // hd (when given): hyper-scalars resident in device memory -- a captured graph of the evaluation is replayed
 // with new hyper-parameters by refreshing that one buffer instead of every kernel's arguments
-__global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int n, int d, int npad,
-                                               HyperScalars h_arg, const HyperScalars* __restrict__ hd,
-                                               double* __restrict__ K, int full, unsigned* __restrict__ tickets,
-                                               const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
+// ARD (k_build_ard): per-dimension weights behind the hyper-scalars in device memory (hd is then always given, and
+// ell_sq is not read: K = sf2 exp(-acc / 2) of the weighted squared distance, no division); K only (full < 2)
+template <bool ARD>
+__device__ __forceinline__ void build_body(const double* __restrict__ X, int n, int d, int npad,
+                                           HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                           double* __restrict__ K, int full, unsigned* __restrict__ tickets,
+                                           const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
 {
     LaunchStamp stamp_(stamp, 16);
     if (bt) {
@@ -964,12 +977,14 @@ __global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int
         for (int i = threadIdx.x; i < ticket_count(npad / TILE); i += 256) tickets[i] = 0u;
     const HyperScalars h = hd ? *hd : h_arg;
     __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ double ws[DC];
     int ti, tj;
     tri_index(blockIdx.x, ti, tj);
     const int i0 = ti * KT, j0 = tj * KT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double d2v[4][4];
-    sqdist_4x4(X, X, n, n, d, i0, j0, xs, ys, d2v);
+    if (ARD) sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, d2v, ard_weights(hd), ws);
+    else sqdist_4x4(X, X, n, n, d, i0, j0, xs, ys, d2v);
     double out[4][4];
     const DivBy dl = div_prepare(h.ell_sq);
 #pragma unroll
@@ -979,7 +994,10 @@ __global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int
             const int i = i0 + ty * 4 + a, j = j0 + col4(tx, b);
             const bool in = i < n && j < n;
             double v;
-            if (full == 2) {
+            if (ARD) {
+                v = h.signal_var * exp(-0.5 * d2v[a][b]);
+                if (i == j) v += h.noise_var;
+            } else if (full == 2) {
                 v = (i == j) ? 0.0 : div_by(d2v[a][b], dl);    // covkernel.cpp:143-151 (squared distance / c)
             } else {
                 v = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));   // covkernel.cpp:89
@@ -1003,11 +1021,28 @@ __global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int
     }
 }
 
+__global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int n, int d, int npad,
+                                               HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                               double* __restrict__ K, int full, unsigned* __restrict__ tickets,
+                                               const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
+{
+    build_body<false>(X, n, d, npad, h_arg, hd, K, full, tickets, bt, stamp);
+}
+
+__global__ __launch_bounds__(256) void k_build_ard(const double* __restrict__ X, int n, int d, int npad,
+                                                   const HyperScalars* __restrict__ hd, double* __restrict__ K,
+                                                   int full, unsigned* __restrict__ tickets, unsigned long long* stamp)
+{
+    build_body<true>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, nullptr, stamp);
+}
+
 // Ks[t][i] = sf2 * exp(-0.5 |xt_t - x_i|^2 / l^2) (no noise, covkernel.cpp:105-116); zero padding
 // bt (batched): blockIdx.y selects the expert -- X, n from its table entry, Ks = the expert's [ntpad][npad] slice
-__global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int n, int d, int npad,
-                                               const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h,
-                                               double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
+template <bool ARD>
+__device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, int d, int npad,
+                                           const double* __restrict__ Xt, int nt, int ntpad, const HyperScalars& h,
+                                           const double* __restrict__ wts,
+                                           double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
 {
     if (bt) {
         X = GP(bt[blockIdx.y].X); n = bt[blockIdx.y].n;
@@ -1020,7 +1055,9 @@ __global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double d2v[4][4];
     // the reference subtracts X[i] - xtest (covkernel.cpp:112); squares are sign-independent but keep the order
-    sqdist_4x4(Xt, X, nt, n, d, t0, i0, xs, ys, d2v);
+    __shared__ double ws[DC];
+    if (ARD) sqdist_4x4<true>(Xt, X, nt, n, d, t0, i0, xs, ys, d2v, wts, ws);
+    else sqdist_4x4(Xt, X, nt, n, d, t0, i0, xs, ys, d2v);
     const DivBy dl = div_prepare(h.ell_sq);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
@@ -1029,12 +1066,27 @@ __global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int i = i0 + col4(tx, b);
-            o[b] = (tr < nt && i < n) ? h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl)) : 0.0;
+            o[b] = (tr < nt && i < n)
+                       ? h.signal_var * (ARD ? exp(-0.5 * d2v[a][b]) : exp(div_by(-d2v[a][b] * 0.5, dl))) : 0.0;
         }
         double* p = Ks + (size_t)tr * npad + i0 + tx * 2;
         *(d2*)p = (d2){o[0], o[1]};
         *(d2*)(p + 32) = (d2){o[2], o[3]};
     }
+}
+
+__global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int n, int d, int npad,
+                                               const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h,
+                                               double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
+{
+    cross_body<false>(X, n, d, npad, Xt, nt, ntpad, h, nullptr, Ks, bt);
+}
+
+__global__ __launch_bounds__(256) void k_cross_ard(const double* __restrict__ X, int n, int d, int npad,
+                                                   const double* __restrict__ Xt, int nt, int ntpad,
+                                                   const HyperScalars* __restrict__ hd, double* __restrict__ Ks)
+{
+    cross_body<true>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, nullptr);
 }
 
 // ---- joint predictive covariance (cugp_predict_cov): Sigma = k(Xt,Xt) (+ sn2 I) - W W^T, W = Ks L^-T ----
@@ -1067,10 +1119,12 @@ __global__ __launch_bounds__(256, 2) void k_predict_cov(const double* __restrict
 // diagonal) - (P_0 + P_1 + ...), in place over P_0; kss = sf2 exp(-|xt_i - xt_j|^2 / (2 l^2)) by k_build's formula and
 // squared-distance order; padding rows / columns >= nt become identity.  tickets (when given): the factorisation's
 // arrival counters, zeroed as k_build does.
-__global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __restrict__ Xt, int nt, int d, int ntpad,
-                                                            HyperScalars h, int with_noise, double jitter,
-                                                            double* __restrict__ A, const double* __restrict__ scr,
-                                                            size_t pstride, int nscr, unsigned* __restrict__ tickets)
+template <bool ARD>
+__device__ __forceinline__ void predict_cov_finish_body(const double* __restrict__ Xt, int nt, int d, int ntpad,
+                                                        const HyperScalars& h, const double* __restrict__ wts,
+                                                        int with_noise, double jitter,
+                                                        double* __restrict__ A, const double* __restrict__ scr,
+                                                        size_t pstride, int nscr, unsigned* __restrict__ tickets)
 {
 #pragma clang fp contract(off)
     if (tickets && blockIdx.x == 0)
@@ -1081,7 +1135,9 @@ __global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __rest
     const int i0 = ti * KT, j0 = tj * KT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double d2v[4][4];
-    sqdist_4x4(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v);
+    __shared__ double ws[DC];
+    if (ARD) sqdist_4x4<true>(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v, wts, ws);
+    else sqdist_4x4(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v);
     const DivBy dl = div_prepare(h.ell_sq);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
@@ -1098,7 +1154,7 @@ __global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __rest
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int j = j0 + col4(tx, b);
-            double v = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
+            double v = h.signal_var * (ARD ? exp(-0.5 * d2v[a][b]) : exp(div_by(-d2v[a][b] * 0.5, dl)));
             if (i == j) {
                 if (with_noise) v += h.noise_var;
                 v += jitter;
@@ -1108,6 +1164,24 @@ __global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __rest
         *(d2*)(A + off) = (d2){o[0], o[1]};
         *(d2*)(A + off + 32) = (d2){o[2], o[3]};
     }
+}
+
+__global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __restrict__ Xt, int nt, int d, int ntpad,
+                                                            HyperScalars h, int with_noise, double jitter,
+                                                            double* __restrict__ A, const double* __restrict__ scr,
+                                                            size_t pstride, int nscr, unsigned* __restrict__ tickets)
+{
+    predict_cov_finish_body<false>(Xt, nt, d, ntpad, h, nullptr, with_noise, jitter, A, scr, pstride, nscr, tickets);
+}
+
+__global__ __launch_bounds__(256) void k_predict_cov_finish_ard(const double* __restrict__ Xt, int nt, int d, int ntpad,
+                                                                const HyperScalars* __restrict__ hd, int with_noise,
+                                                                double jitter, double* __restrict__ A,
+                                                                const double* __restrict__ scr, size_t pstride,
+                                                                int nscr, unsigned* __restrict__ tickets)
+{
+    predict_cov_finish_body<true>(Xt, nt, d, ntpad, *hd, ard_weights(hd), with_noise, jitter, A, scr, pstride, nscr,
+                                  tickets);
 }
 
 // The Cholesky writes the lower triangle only: the strict upper part of every 128x128 diagonal tile still holds Sigma,
@@ -2419,6 +2493,138 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize(const double* __restri
     finalize_sums<FIN_THREADS, false>(z, npad, n, logdet_part, nt, part, nblocks, h, out, hout, red);
 }
 
+// ---- ARD (one length scale per input dimension; GPML covSEard's convention; no reference counterpart) ----
+// Gradient pass: g_c = 1/2 sum_ij W_ij Kf_ij ((x_ic - x_jc) w_c)^2 for every dimension c, beside the two sums k_trace takes
+// (sum W o K and tr W).  Per lower 64x64 tile: (1) the weighted squared distances over all feature chunks, K^-1 read
+// once, and the thread's 4x4 entries of W o K kept in registers (off-diagonal tiles doubled, entries outside the lower
+// triangle or the data zero); (2) a second sweep over the feature chunks, the X tiles staged again, DC per-dimension
+// sums at a time in registers; wave sums by shuffles, the four waves added in a fixed order.
+// Partials: part[c * nblocks + block], c = 0 .. d - 1 the dimensions, d: sum W o K, d + 1: tr W (column-major, so that
+// k_finalize_ard's lanes read a column contiguously).  No fused final sums: k_finalize_ard always follows.
+__global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X, int n, int d, int npad,
+                                                   const HyperScalars* __restrict__ hd,
+                                                   const double* __restrict__ Kinv, const double* __restrict__ alpha,
+                                                   double* __restrict__ part)
+{
+#pragma clang fp contract(off)
+    const HyperScalars h = *hd;
+    const double* __restrict__ wts = ard_weights(hd);
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ double ws[DC];
+    __shared__ double red[DC][4];
+    int ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    const int i0 = ti * KT, j0 = tj * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const size_t nblocks = gridDim.x;
+    double wk[4][4];
+    sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, wk, wts, ws);
+    double s2 = 0.0, s3 = 0.0;
+    double aj[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) aj[b] = alpha[j0 + col4(tx, b)];
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int i = i0 + ty * 4 + a;
+        const double ai = alpha[i];
+        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
+        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
+        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = j0 + col4(tx, b);
+            double e = 0.0;
+            if (i < n && j < n && (ti != tj || j <= i)) {
+                const double w = kv[b] - ai * aj[b];
+                double kse = h.signal_var * exp(-0.5 * wk[a][b]);
+                if (i == j) {
+                    kse += h.noise_var;
+                    s2 += w * kse;
+                    s3 += w;
+                } else {
+                    e = 2.0 * (w * kse);     // (the diagonal's differences are zero: it has no share in any g_c)
+                    s2 += e;
+                }
+            }
+            wk[a][b] = e;
+        }
+    }
+    s2 = wave_sum(s2); s3 = wave_sum(s3);
+    if ((t & 63) == 0) { red[0][t >> 6] = s2; red[1][t >> 6] = s3; }
+    __syncthreads();
+    if (t < 2) part[(size_t)(d + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    for (int c0 = 0; c0 < d; c0 += DC) {
+        const int dc = (d - c0 < DC) ? (d - c0) : DC;
+        __syncthreads();
+        for (int e = t; e < KT * dc; e += 256) {
+            int r = e / dc, c = e - r * dc;
+            xs[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
+            ys[r][c] = (j0 + r < n) ? X[(size_t)(j0 + r) * d + c0 + c] : 0.0;
+        }
+        if (t < dc) ws[t] = wts[c0 + t];
+        __syncthreads();
+        double gs[DC];
+#pragma unroll
+        for (int c = 0; c < DC; c++) {
+            gs[c] = 0.0;
+            if (c < dc) {
+                double xv[4], yv[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+                const double wc = ws[c];
+                double acc = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        const double df = (xv[a] - yv[b]) * wc;
+                        acc = acc + wk[a][b] * (df * df);
+                    }
+                gs[c] = wave_sum(acc);
+            }
+        }
+        if ((t & 63) == 0) {
+#pragma unroll
+            for (int c = 0; c < DC; c++) red[c][t >> 6] = gs[c];
+        }
+        __syncthreads();
+        if (t < dc) part[(size_t)(c0 + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    }
+}
+
+// Final sums of an ARD gradient evaluation, one workgroup.  LL, y'K^-1y and log|K| by finalize_sums (the isotropic
+// order and bits); then wave w takes the columns w, w + 16, ... of the trace partials: lane l adds the blocks l, l + 64,
+// ... ascending, the lanes by wave_sum -- a fixed order whatever the timing.  Results row (out, hout): [0] LL, [4] quad,
+// [5] log|K|, [6] status word, [8 + c] the d + 2 gradient components:
+//   g_c = S_c / 2 (c < d), g_d = (2 s2 - 2 sn2 s3) / 2, g_{d+1} = (2 sn2 s3) / 2   (the last two as k_finalize's g1, g2)
+__global__ __launch_bounds__(FIN_THREADS) void k_finalize_ard(const double* __restrict__ z, int npad, int n, int d,
+                                                              const double* __restrict__ logdet_part, int nt,
+                                                              const double* __restrict__ part, int nblocks,
+                                                              const HyperScalars* __restrict__ hd,
+                                                              double* __restrict__ out, double* __restrict__ hout)
+{
+    const HyperScalars h = *hd;
+    __shared__ double red[5 * FIN_THREADS];
+    finalize_sums<FIN_THREADS, false>(z, npad, n, logdet_part, nt, nullptr, 0, h, out, hout, red);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __syncthreads();
+    for (int c = wave; c < d + 2; c += FIN_THREADS / 64) {
+        const double* col = part + (size_t)c * nblocks;
+        double s = 0.0;
+        for (int i = lane; i < nblocks; i += 64) s += col[i];
+        s = wave_sum(s);
+        if (lane == 0 && c < d) { out[8 + c] = s / 2.0; hout[8 + c] = s / 2.0; }
+        if (lane == 0 && c >= d) red[16 + (c - d)] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double s2 = red[16], s3 = red[17];
+        const double gf = (2.0 * s2 - 2.0 * h.noise_var * s3) / 2.0, gn = (2.0 * h.noise_var * s3) / 2.0;
+        out[8 + d] = gf; out[9 + d] = gn;
+        hout[8 + d] = gf; hout[9 + d] = gn;
+    }
+}
+
 // one expert's row of the product-of-experts exchange (BCM.cpp:51-55): 1/v and (1/v) m, rounded separately as the host
 // loop of cugp_bcm_predict_partial does (IEEE division, no contraction)
 __device__ __forceinline__ void poe_row(double m, double v, double* __restrict__ p, double* __restrict__ pm)
@@ -2534,6 +2740,20 @@ void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S,
     hipLaunchKernelGGL(k_build, dim3(tri_count(npad / KT)), dim3(256), 0, s, X, n, d, npad, h,
                        (const HyperScalars*)nullptr, S, 2, (unsigned*)nullptr, (const ExpertPtrs*)nullptr,
                        (unsigned long long*)nullptr);
+}
+
+void launch_kbuild_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, double* K, bool full,
+                       hipStream_t s, unsigned* tickets)
+{
+    hipLaunchKernelGGL(k_build_ard, dim3(tri_count(npad / KT)), dim3(256), 0, s, X, n, d, npad, hd, K, full ? 1 : 0,
+                       tickets, take_stamp());
+}
+
+void launch_kcross_ard(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
+                       const HyperScalars* hd, double* Ks, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cross_ard, dim3((ntpad / KT) * (npad / KT)), dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, hd,
+                       Ks);
 }
 
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad, HyperScalars h,
@@ -2790,6 +3010,14 @@ void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, Hyper
                        with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
 }
 
+void launch_predict_cov_finish_ard(const double* Xt, int nt, int d, int ntpad, const HyperScalars* hd, bool with_noise,
+                                   double jitter, double* A, const double* scr, int nscr, unsigned* tickets,
+                                   hipStream_t s)
+{
+    hipLaunchKernelGGL(k_predict_cov_finish_ard, dim3(tri_count(ntpad / KT)), dim3(256), 0, s, Xt, nt, d, ntpad, hd,
+                       with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+}
+
 void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s)
 {
     hipLaunchKernelGGL(k_zero_upper_diag, dim3(nt), dim3(256), 0, s, A, ld);
@@ -2858,6 +3086,16 @@ void launch_trace(const double* X, int n, int d, int npad, HyperScalars h, const
                        alpha, part, bt.tab, fin);
     if (out != nullptr && !fuse)
         launch_finalize(z, npad, n, logdet_part, npad / TILE, part, nblocks, h, out, hout, s, hd, bt);
+}
+
+void launch_trace_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, const double* Kinv,
+                      const double* alpha, double* part, const double* z, const double* logdet_part, double* out,
+                      double* hout, hipStream_t s)
+{
+    const int nblocks = tri_count(npad / KT);
+    hipLaunchKernelGGL(k_trace_ard, dim3(nblocks), dim3(256), 0, s, X, n, d, npad, hd, Kinv, alpha, part);
+    hipLaunchKernelGGL(k_finalize_ard, dim3(1), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part, npad / TILE, part,
+                       nblocks, hd, out, hout);
 }
 
 void launch_finalize(const double* z, int npad, int n, const double* logdet_part, int nt, const double* part,

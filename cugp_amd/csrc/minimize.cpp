@@ -1,4 +1,6 @@
-// minimize.cpp -- host-side optimisers of the GP objective (3 log-hyper-parameters).
+// minimize.cpp -- host-side optimisers of the GP objective (3 log-hyper-parameters; cugp_cg_minimize_n: nh of them, for
+// ARD handles -- the same loop, every sum over the entries taken in index order, so that with nh = 3 it is the 3-entry
+// trajectory bit for bit: the 3-entry entry points run the very same code).
 //
 // cugp_cg_minimize follows the reference's Rasmussen-style "minimize" exactly in its arithmetic
 // and control flow (cpp_serial_gp/covkernel.cpp:405-647, identical in
@@ -21,6 +23,7 @@
 // expert, the experts of one GPU, or an all-reduced sum over ranks.
 #include <cfloat>
 #include <cmath>
+#include <vector>
 
 #include "../../include/cugp.h"
 
@@ -33,34 +36,74 @@ struct Vec3 {
 };
 
 inline double dot(const Vec3& a, const Vec3& b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-inline Vec3 axpy(const Vec3& x, const Vec3& s, double t) { return Vec3{{x[0] + s[0] * t, x[1] + s[1] * t, x[2] + s[2] * t}}; }
-inline Vec3 neg(const Vec3& a) { return Vec3{{-a[0], -a[1], -a[2]}}; }
-inline bool any_nan(const Vec3& a) { return std::isnan(a[0]) || std::isnan(a[1]) || std::isnan(a[2]); }
+
+// nh entries (the CG loop); sums left to right in index order
+struct Vec {
+    std::vector<double> v;
+    Vec() = default;
+    explicit Vec(int n) : v((size_t)n, 0.0) {}
+    Vec(const double* p, int n) : v(p, p + n) {}
+    int size() const { return (int)v.size(); }
+    double& operator[](int i) { return v[(size_t)i]; }
+    double operator[](int i) const { return v[(size_t)i]; }
+};
+
+inline double dot(const Vec& a, const Vec& b)
+{
+    double s = a[0] * b[0];
+    for (int i = 1; i < a.size(); i++) s = s + a[i] * b[i];
+    return s;
+}
+inline Vec axpy(const Vec& x, const Vec& s, double t)
+{
+    Vec r(x.size());
+    for (int i = 0; i < x.size(); i++) r[i] = x[i] + s[i] * t;
+    return r;
+}
+inline Vec neg(const Vec& a)
+{
+    Vec r(a.size());
+    for (int i = 0; i < a.size(); i++) r[i] = -a[i];
+    return r;
+}
+inline bool any_nan(const Vec& a)
+{
+    for (int i = 0; i < a.size(); i++)
+        if (std::isnan(a[i])) return true;
+    return false;
+}
 
 class Probe {   // evaluates the objective and keeps the optional trace
 public:
     Probe(cugp_objective_fn fn, void* ctx, double* trace, int cap) : fn_(fn), ctx_(ctx), trace_(trace), cap_(cap) {}
     Probe(cugp_value_fn vf, cugp_gradient_fn gf, void* ctx, double* trace, int cap)
         : vf_(vf), gf_(gf), ctx_(ctx), trace_(trace), cap_(cap) {}
+    Probe(cugp_objective_n_fn nf, void* ctx, double* trace, int cap) : nf_(nf), ctx_(ctx), trace_(trace), cap_(cap) {}
     // fref: the value the current line search started from (a probe above it never needs its gradient)
-    void at(const Vec3& th, double& f, Vec3& g, double fref)
+    void at(const Vec3& th, double& f, Vec3& g, double fref) { at_n(th.v, 3, f, g.v, fref); }
+    void at(const Vec& th, double& f, Vec& g, double fref) { at_n(th.v.data(), th.size(), f, g.v.data(), fref); }
+    void at_n(const double* th, int nh, double& f, double* g, double fref)
     {
-        if (fn_) {
-            fn_(ctx_, th.v, &f, g.v);
+        if (nf_) {
+            nf_(ctx_, th, nh, &f, g);
+        } else if (fn_) {
+            fn_(ctx_, th, &f, g);
         } else {
-            vf_(ctx_, th.v, &f);
-            if (std::isnan(f) || std::isinf(f) || f > fref) g = Vec3{{0.0, 0.0, 0.0}};   // never read (see header)
-            else { gf_(ctx_, th.v, g.v); ++grads_; }
+            vf_(ctx_, th, &f);
+            if (std::isnan(f) || std::isinf(f) || f > fref) g[0] = g[1] = g[2] = 0.0;   // never read (see header)
+            else { gf_(ctx_, th, g); ++grads_; }
         }
         if (trace_ && count_ < cap_) {
-            double* r = trace_ + 4 * (long)count_;
-            r[0] = th[0]; r[1] = th[1]; r[2] = th[2]; r[3] = f;
+            double* r = trace_ + (nh + 1) * (long)count_;
+            for (int i = 0; i < nh; i++) r[i] = th[i];
+            r[nh] = f;
         }
         ++count_;
     }
     int count() const { return count_; }
-    int grads() const { return fn_ ? count_ : grads_; }
+    int grads() const { return (fn_ || nf_) ? count_ : grads_; }
 private:
+    cugp_objective_n_fn nf_ = nullptr;
     cugp_objective_fn fn_ = nullptr;
     cugp_value_fn vf_ = nullptr;
     cugp_gradient_fn gf_ = nullptr;
@@ -73,14 +116,24 @@ private:
 
 }  // namespace
 
-static int cg_loop(Probe& probe, double theta[3], int budget);
+static int cg_loop(Probe& probe, double* theta, int nh, int budget);
 
 extern "C" int cugp_cg_minimize(cugp_objective_fn fn, void* ctx, double theta[3], int budget, double* trace,
                                 int trace_cap, int* nevals)
 {
     if (!fn || !theta || budget < 0) return CUGP_ERR_INVALID;
     Probe probe(fn, ctx, trace, trace_cap);
-    const int rc = cg_loop(probe, theta, budget);
+    const int rc = cg_loop(probe, theta, 3, budget);
+    if (nevals) *nevals = probe.count();
+    return rc;
+}
+
+extern "C" int cugp_cg_minimize_n(cugp_objective_n_fn fn, void* ctx, double* theta, int nh, int budget, double* trace,
+                                  int trace_cap, int* nevals)
+{
+    if (!fn || !theta || nh <= 0 || budget < 0) return CUGP_ERR_INVALID;
+    Probe probe(fn, ctx, trace, trace_cap);
+    const int rc = cg_loop(probe, theta, nh, budget);
     if (nevals) *nevals = probe.count();
     return rc;
 }
@@ -90,21 +143,21 @@ extern "C" int cugp_cg_minimize_sparing(cugp_value_fn value, cugp_gradient_fn gr
 {
     if (!value || !gradient || !theta || budget < 0) return CUGP_ERR_INVALID;
     Probe probe(value, gradient, ctx, trace, trace_cap);
-    const int rc = cg_loop(probe, theta, budget);
+    const int rc = cg_loop(probe, theta, 3, budget);
     if (nevals) *nevals = probe.count();
     if (ngrads) *ngrads = probe.grads();
     return rc;
 }
 
-static int cg_loop(Probe& probe, double theta[3], int budget)
+static int cg_loop(Probe& probe, double* theta, int nh, int budget)
 {
     // constants: covkernel.cpp:407-411
     const double kInt = 0.1, kExt = 3.0, kRatio = 10, kSig = 0.1, kRho = kSig / 2;
     const int kMaxPerSearch = 20;
     const int n = budget;
 
-    Vec3 X{{theta[0], theta[1], theta[2]}};
-    Vec3 df0, df3, s;
+    Vec X(theta, nh);
+    Vec df0(nh), df3(nh), s(nh);
     double f0;
     probe.at(X, f0, df0, INFINITY);          // covkernel.cpp:438-439
     s = neg(df0);
@@ -115,7 +168,7 @@ static int cg_loop(Probe& probe, double theta[3], int budget)
     bool prev_failed = false;
 
     for (int i = 0; i < n; ++i) {
-        Vec3 bestX = X, bestG = df0;
+        Vec bestX = X, bestG = df0;
         double bestF = f0;
         unsigned left = (unsigned)(kMaxPerSearch < (n - i) ? kMaxPerSearch : (n - i));
 
@@ -167,7 +220,7 @@ static int cg_loop(Probe& probe, double theta[3], int budget)
             X = axpy(X, s, x3);
             f0 = f3;
             const double beta = (dot(df3, df3) - dot(df0, df3)) / (dot(df0, df0));
-            s = Vec3{{beta * s[0] - df3[0], beta * s[1] - df3[1], beta * s[2] - df3[2]}};
+            for (int j = 0; j < nh; j++) s[j] = beta * s[j] - df3[j];
             df0 = df3;
             d3 = d0;
             d0 = dot(df0, s);
@@ -184,7 +237,7 @@ static int cg_loop(Probe& probe, double theta[3], int budget)
             prev_failed = true;
         }
     }
-    theta[0] = X[0]; theta[1] = X[1]; theta[2] = X[2];
+    for (int j = 0; j < nh; j++) theta[j] = X[j];
     return CUGP_OK;
 }
 

@@ -16,12 +16,20 @@ class Covsum:
     """One GP expert on one GPU.  Covsum(n, d) as covkernel.cpp:14-37; X, y are given per call as in
     the reference and uploaded whenever their CONTENTS differ from what the GPU holds (the reference
     recomputes K from the arguments on every call; comparing n*d doubles is nothing beside an O(n^3)
-    evaluation, and an in-place edit of y or a recycled array address can not go unnoticed)."""
+    evaluation, and an in-place edit of y or a recycled array address can not go unnoticed).
+    ard=True: one length scale per input dimension (cugp_create_ard; GPML covSEard's order): the hyper-parameter
+    vector is [log l_1 .. log l_d, log sigma_f, log sigma_n], gradients and cg_solve traces have d + 2 (+ 1) entries."""
 
-    def __init__(self, n, d, device=0, npad_min=0):
-        self.n, self.d, self.device = int(n), int(d), int(device)
+    def __init__(self, n, d, device=0, npad_min=0, ard=False):
+        self.n, self.d, self.device, self.ard = int(n), int(d), int(device), bool(ard)
+        self.nh = self.d + 2 if self.ard else 3
         self._h = C.c_void_p()
-        check(capi.lib().cugp_create_padded(self.n, self.d, self.device, int(npad_min), C.byref(self._h)))
+        if self.ard:
+            if npad_min:
+                raise ValueError("an ARD handle cannot be padded (it cannot join a BCM group)")
+            check(capi.lib().cugp_create_ard(self.n, self.d, self.device, C.byref(self._h)))
+        else:
+            check(capi.lib().cugp_create_padded(self.n, self.d, self.device, int(npad_min), C.byref(self._h)))
         self._data_key = None
 
     # -- lifetime --
@@ -63,17 +71,26 @@ class Covsum:
 
     # -- hyper-parameters --
     def set_loghyperparam(self, hp):
-        check(capi.lib().cugp_set_loghyper(self._h, ptr(f64(hp))))
+        hp = f64(hp)
+        if self.ard:
+            if hp.shape != (self.nh,):
+                raise ValueError("expected %d log-hyper-parameters" % self.nh)
+            check(capi.lib().cugp_set_loghyper_ard(self._h, ptr(hp), self.nh))
+        else:
+            check(capi.lib().cugp_set_loghyper(self._h, ptr(hp)))
 
     set_loghyper_eigen = set_loghyperparam
 
     def get_loghyperparam(self):
-        out = np.empty(3)
-        check(capi.lib().cugp_get_loghyper(self._h, ptr(out)))
+        out = np.empty(self.nh)
+        if self.ard:
+            check(capi.lib().cugp_get_loghyper_ard(self._h, ptr(out), self.nh))
+        else:
+            check(capi.lib().cugp_get_loghyper(self._h, ptr(out)))
         return out
 
     def get_param_dim(self):
-        return self.d            # covkernel.cpp:661-663 returns numdim
+        return self.d + 2 if self.ard else self.d   # covkernel.cpp:661-663 returns numdim; ARD: the number of hyper-parameters
 
     # -- objective --
     def compute_loglikelihood(self, X=None, y=None):
@@ -84,6 +101,8 @@ class Covsum:
 
     def compute_gradient_loghyperparam(self, X=None, y=None):
         self._bind(X, y)
+        if self.ard:
+            return self.loglik_grad()[1]
         g = np.empty(3)
         check(capi.lib().cugp_grad(self._h, ptr(g)))
         return g
@@ -91,8 +110,11 @@ class Covsum:
     def loglik_grad(self, X=None, y=None):
         self._bind(X, y)
         ll = C.c_double()
-        g = np.empty(3)
-        check(capi.lib().cugp_loglik_grad(self._h, C.byref(ll), ptr(g)))
+        g = np.empty(self.nh)
+        if self.ard:
+            check(capi.lib().cugp_loglik_grad_ard(self._h, C.byref(ll), ptr(g), self.nh))
+        else:
+            check(capi.lib().cugp_loglik_grad(self._h, C.byref(ll), ptr(g)))
         return ll.value, g
 
     def enqueue(self, want_grad=True):
@@ -100,8 +122,11 @@ class Covsum:
 
     def fetch(self):
         ll = C.c_double()
-        g = np.empty(3)
-        check(capi.lib().cugp_loglik_grad_fetch(self._h, C.byref(ll), ptr(g)))
+        g = np.empty(self.nh)
+        if self.ard:
+            check(capi.lib().cugp_loglik_grad_fetch_ard(self._h, C.byref(ll), ptr(g), self.nh))
+        else:
+            check(capi.lib().cugp_loglik_grad_fetch(self._h, C.byref(ll), ptr(g)))
         return ll.value, g
 
     def last_quad_logdet(self):
@@ -173,7 +198,7 @@ class Covsum:
             normals = gen.standard_normal((ns, nt))
         Z = f64(normals).reshape(ns, nt)
         if jitter is None:
-            jitter = 0.0 if with_noise else 1e-8 * float(np.exp(2.0 * self.get_loghyperparam()[1]))
+            jitter = 0.0 if with_noise else 1e-8 * float(np.exp(2.0 * self.get_loghyperparam()[-2]))
         out = np.empty((ns, nt))
         check(capi.lib().cugp_predict_sample(self._h, ptr(Xt), nt, 1 if with_noise else 0, float(jitter), ns, ptr(Z),
                                              ptr(out)))
@@ -188,11 +213,12 @@ class Covsum:
 
     # -- optimisers --
     def cg_solve(self, X=None, y=None, budget=100):
-        """Covsum::cg_solve; returns the evaluation trace [n_evals, 4] = (hp0, hp1, hp2, -LL)."""
+        """Covsum::cg_solve; returns the evaluation trace [n_evals, 4] = (hp0, hp1, hp2, -LL); ARD: [n_evals, d + 3]."""
         self._bind(X, y)
-        tr = np.zeros((4 * budget + 8, 4))
+        tr = np.zeros((4 * budget + 8, self.nh + 1))
         ne = C.c_int()
-        check(capi.lib().cugp_cg_solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        solve = capi.lib().cugp_cg_solve_ard if self.ard else capi.lib().cugp_cg_solve
+        check(solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
         return tr[: ne.value]
 
     def cg_solve_sparing(self, X=None, y=None, budget=100):
@@ -374,6 +400,7 @@ class BCM:
         check(capi.lib().cugp_bcm_expert(self._h, int(k), C.byref(h)))
         e = Covsum.__new__(Covsum)
         e.n, e.d, e.device, e._h, e._data_key = self.rows[k], self.d, self.devices[k % len(self.devices)], h, None
+        e.ard, e.nh = False, 3
         e.close = lambda: None                    # not ours to destroy
         return e
 
@@ -423,6 +450,24 @@ def cg_minimize(fn, theta, budget=100):
     ne = C.c_int()
     check(capi.lib().cugp_cg_minimize(capi.OBJECTIVE(cb), None, ptr(th), budget, ptr(tr), tr.shape[0],
                                       C.byref(ne)))
+    return th, tr[: ne.value]
+
+
+def cg_minimize_n(fn, theta, budget=100):
+    """The same loop over len(theta) entries (cugp_cg_minimize_n) on a Python objective fn(theta)->(f, g);
+    -> (theta, trace [n_evals, nh + 1])."""
+    th = f64(theta).copy()
+    nh = th.shape[0]
+
+    def cb(_ctx, t, n, f, g):
+        fv, gv = fn(np.array([t[i] for i in range(n)]))
+        f[0] = fv
+        for i in range(n):
+            g[i] = gv[i]
+    tr = np.zeros((4 * budget + 8, nh + 1))
+    ne = C.c_int()
+    check(capi.lib().cugp_cg_minimize_n(capi.OBJECTIVE_N(cb), None, ptr(th), nh, budget, ptr(tr), tr.shape[0],
+                                        C.byref(ne)))
     return th, tr[: ne.value]
 
 

@@ -69,6 +69,29 @@ int cugp_set_data_device(cugp_gp *gp, const double *dX, const double *dy);   /* 
 int cugp_set_loghyper(cugp_gp *gp, const double hp[3]);
 int cugp_get_loghyper(const cugp_gp *gp, double hp[3]);
 
+/* ---- ARD: one length scale per input dimension (automatic relevance determination).  The reference has no
+ *      counterpart (its Covsum has ONE length scale, covkernel.cpp:64-102); the convention is GPML's covSEard:
+ *        theta = [log l_1 .. log l_d, log sigma_f, log sigma_n]     (nh = d + 2 entries: the order above, first entry widened)
+ *        k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) / l_c)^2) + sn2 delta,   sf2 = exp(2 theta_d), sn2 = exp(2 theta_{d+1})
+ *      with 1 / l_c = exp(-theta_c) evaluated on the host and every DIFFERENCE x_c - x'_c weighted before it is squared.
+ *      Gradients are of -LL: g_c = 1/2 sum_ij W_ij Kf_ij ((x_ic - x_jc) / l_c)^2 (W = K^-1 - alpha alpha', Kf = K - sn2 I),
+ *      then the signal and the noise component as g[1], g[2] of the isotropic form.
+ * A handle made by the create call below is ARD for life.  Data, overlap, the log-likelihood, the split enqueue, the
+ * predictions (marginal, joint, draws), K, k_test, factor, inverse, alpha, profiling and tuning work on it unchanged; the
+ * 3-entry calls (set / get of the hyper-parameters, the gradient calls, the optimisers, the squared-distance
+ * intermediate) return CUGP_ERR_INVALID on it and name the call to use.  ARD handles cannot be experts of a BCM group.
+ * The calls below return CUGP_ERR_INVALID -- before any device call -- for a NULL argument, an isotropic handle, or
+ * nh != d + 2.  A theta_c so large that 1 / l_c underflows simply drops dimension c (g_c = 0); one so small that it
+ * overflows gives NaN results (the header's convention for a covariance that cannot be factored), not an error.
+ * The number of hyper-parameters of any handle (3, or d + 2) is reported through *nh; set / get copy nh entries;
+ * the combined and the fetch form return LL and the nh gradient components (fetch: g may be NULL). */
+int cugp_create_ard(int n, int d, int device, cugp_gp **out);
+int cugp_num_hyper(const cugp_gp *gp, int *nh);
+int cugp_set_loghyper_ard(cugp_gp *gp, const double *hp, int nh);
+int cugp_get_loghyper_ard(const cugp_gp *gp, double *hp, int nh);
+int cugp_loglik_grad_ard(cugp_gp *gp, double *ll, double *g, int nh);
+int cugp_loglik_grad_fetch_ard(cugp_gp *gp, double *ll, double *g /* may be NULL */, int nh);
+
 /* ---- objective ----
  * cugp_loglik       : Covsum::compute_loglikelihood covkernel.cpp:118-129 ; compute_log_likelihood cuda_gp.cu:838-855
  * cugp_loglik_grad  : the pair compute_loglikelihood + compute_gradient_loghyperparam (covkernel.cpp:162-263 ;
@@ -184,6 +207,16 @@ typedef void (*cugp_gradient_fn)(void *ctx, const double theta[3], double g[3]);
 int cugp_cg_minimize_sparing(cugp_value_fn value, cugp_gradient_fn gradient, void *ctx, double theta[3], int budget,
                              double *trace, int trace_cap, int *nevals, int *ngrads);
 int cugp_cg_solve_sparing(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals, int *ngrads);
+/* The same conjugate-gradient loop over nh hyper-parameters (no reference counterpart; used for ARD handles, theta
+ * ordered as GPML's covSEard above): same constants and control flow, every sum over the entries in index order, so
+ * with nh == 3 it takes the 3-entry trajectory bit for bit.  The objective fills f = -LL and the nh entries of g.
+ * trace (may be NULL): rows of nh + 1 doubles [theta_0 .. theta_{nh-1}, f].  CUGP_ERR_INVALID for a NULL fn or theta,
+ * nh <= 0 or budget < 0.  The solve form below runs it on an ARD handle from its current hyper-parameters and leaves
+ * the end point set (CUGP_ERR_INVALID on an isotropic handle). */
+typedef void (*cugp_objective_n_fn)(void *ctx, const double *theta, int nh, double *f, double *g);
+int cugp_cg_minimize_n(cugp_objective_n_fn fn, void *ctx, double *theta, int nh, int budget, double *trace,
+                       int trace_cap, int *nevals);
+int cugp_cg_solve_ard(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals);
 int cugp_cg_solve(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals);
 int cugp_rprop_solve(cugp_gp *gp, int iters, double *trace, int trace_cap, int *nevals);
 
