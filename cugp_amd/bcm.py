@@ -43,19 +43,23 @@ def gather_row_index(k, world, per):
     return expert_owner(k, world) * per + k // world
 
 
-def _default_factory(n, d, device):
-    return _gp.Covsum(n, d, device)
+def _default_factory(n, d, device, kernel="se"):
+    return _gp.Covsum(n, d, device, kernel=kernel)
 
 
 class ShardedBCM:
     """K experts over `world` ranks.  `experts` is a list of K (X_k, y_k) pairs; only the ones this
-    rank owns are touched (the rest may be None).  group=None with world==1 needs no process group."""
+    rank owns are touched (the rest may be None).  group=None with world==1 needs no process group.
+    kernel: "se" | "matern32" | "matern52" for the library's experts -- every rank must pass the same one (the library
+    cannot check that without a collective); an injected expert_factory makes its own experts and is not told."""
 
-    def __init__(self, experts, rank=0, world=1, device=0, group=None, expert_factory=None, comm_device=None):
+    def __init__(self, experts, rank=0, world=1, device=0, group=None, expert_factory=None, comm_device=None,
+                 kernel="se"):
         self.K = len(experts)
+        self.kernel = _gp.KERNEL_NAMES[_gp.kernel_kind(kernel)]
         self.rank, self.world, self.group = rank, world, group
         self.mine = [k for k in range(self.K) if expert_owner(k, world) == rank]
-        factory = expert_factory or _default_factory
+        factory = expert_factory or (lambda n, d, dev: _default_factory(n, d, dev, self.kernel))
         self.local = {}
         self._group = None
         if expert_factory is None and len(self.mine) > 1:
@@ -63,7 +67,7 @@ class ShardedBCM:
             # (csrc/bcm.cpp, group.h); self.local holds borrowed per-expert views for prediction
             data = [(np.ascontiguousarray(experts[k][0], dtype=np.float64),
                      np.ascontiguousarray(experts[k][1], dtype=np.float64)) for k in self.mine]
-            self._group = _gp.BCM([X.shape[0] for X, _ in data], data[0][0].shape[1], device)
+            self._group = _gp.BCM([X.shape[0] for X, _ in data], data[0][0].shape[1], device, kernel=self.kernel)
             for i, (X, y) in enumerate(data):
                 self._group.set_expert_data(i, X, y)
                 self.local[self.mine[i]] = self._group.expert(i)
@@ -95,7 +99,7 @@ class ShardedBCM:
             X, y = (np.ascontiguousarray(a, dtype=np.float64) for a in experts[self.mine[0]])
             for e in self.local.values():
                 e.close()
-            self._group = _gp.BCM([X.shape[0]], X.shape[1], device)
+            self._group = _gp.BCM([X.shape[0]], X.shape[1], device, kernel=self.kernel)
             self._group.set_expert_data(0, X, y)
             self.local = {self.mine[0]: self._group.expert(0)}
         # Lean exchange (round 6): the library writes this rank's rows into a compact [per, 4] device tensor, ONE

@@ -20,6 +20,7 @@ GRADIENT_FN = C.CFUNCTYPE(None, C.c_void_p, _dp, _dp)
 OBJECTIVE_N = C.CFUNCTYPE(None, C.c_void_p, _dp, C.c_int, _dp, _dp)
 
 CUGP_OK = 0
+CUGP_KERNEL_SE, CUGP_KERNEL_MATERN32, CUGP_KERNEL_MATERN52 = 0, 1, 2
 CUGP_ERR_INVALID, CUGP_ERR_NOMEM, CUGP_ERR_DEVICE, CUGP_ERR_NODEVICE = -1, -2, -3, -4
 ERR_NAMES = {-1: "CUGP_ERR_INVALID", -2: "CUGP_ERR_NOMEM", -3: "CUGP_ERR_DEVICE", -4: "CUGP_ERR_NODEVICE",
              -5: "CUGP_ERR_BUSY"}
@@ -39,6 +40,8 @@ SIGNATURES = {
     "cugp_device_count": (C.c_int, [_ip]),
     "cugp_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_create_padded": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_create_kernel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_kernel_kind": (C.c_int, [C.c_void_p, _ip]),
     "cugp_destroy": (C.c_int, [C.c_void_p]),
     "cugp_dims": (C.c_int, [C.c_void_p, _ip, _ip, _ip]),
     "cugp_set_overlap": (C.c_int, [C.c_void_p, C.c_int]),
@@ -90,6 +93,10 @@ SIGNATURES = {
     "cugp_bcm_create_split": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_bcm_create_multi": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_bcm_create_split_multi": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_kernel": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_split_kernel": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int,
+                                               C.POINTER(C.c_void_p)]),
+    "cugp_bcm_kernel_kind": (C.c_int, [C.c_void_p, _ip]),
     "cugp_bcm_destroy": (C.c_int, [C.c_void_p]),
     "cugp_bcm_num_experts": (C.c_int, [C.c_void_p, _ip]),
     "cugp_bcm_expert": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),

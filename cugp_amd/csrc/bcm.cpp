@@ -33,6 +33,7 @@ struct cugp_bcm {
     std::vector<int> rows;
     int d = 0;
     double hp[3] = {0, 0, 0};
+    int kernel = 0;                  // CUGP_KERNEL_* of every expert, for life
     Scratch pred_host{nullptr, 0, true};   // pinned: [expert][mean nt | variance nt] of the prediction in flight
     std::vector<hipEvent_t> pred_ev; // cugp_bcm_predict_rows_enqueue: "rows written" per stream that wrote some
 };
@@ -46,10 +47,19 @@ extern "C" {
 // BCM bit for bit whatever the device list (distributed_gp/BCM.cpp:153-198).
 int cugp_bcm_create_multi(int ndev, const int* devices, int nexperts, const int* rows, int d, cugp_bcm** out)
 {
+    return cugp_bcm_create_kernel(ndev, devices, nexperts, rows, d, CUGP_KERNEL_SE, out);
+}
+
+// the same with every expert of one covariance family (cugp_create_kernel); kind 0 is the call above
+int cugp_bcm_create_kernel(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel,
+                           cugp_bcm** out)
+{
     if (!out || ndev <= 0 || !devices || nexperts <= 0 || !rows || d <= 0) return CUGP_ERR_INVALID;
+    if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52) return CUGP_ERR_INVALID;
     cugp_bcm* b = new (std::nothrow) cugp_bcm;
     if (!b) return CUGP_ERR_NOMEM;
     b->d = d;
+    b->kernel = kernel;
     // Common padded size (identity padding) so that the experts can share launches -- unless their row counts
     // differ by more than a tile or ~6 %: then padding the small ones would cost more than it gains.
     int nmax = 0, nmin = rows[0];
@@ -66,7 +76,7 @@ int cugp_bcm_create_multi(int ndev, const int* devices, int nexperts, const int*
     for (int k = 0; k < nexperts; k++) {
         DeviceSet& ds = b->sets[k % nsets];
         cugp_gp* g = nullptr;
-        int rc = cugp_create_padded(rows[k], d, ds.device, pad_to, &g);
+        int rc = cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
         if (rc) { cugp_bcm_destroy(b); return rc; }
         // several experts on one device already fill each other's idle time; the extra streams only cost launches
         if (nexperts > nsets) cugp_set_overlap(g, 0);
@@ -97,7 +107,14 @@ int cugp_bcm_create(int nexperts, const int* rows, int d, int device, cugp_bcm**
 int cugp_bcm_create_split_multi(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
                                 cugp_bcm** out)
 {
+    return cugp_bcm_create_split_kernel(X, y, N, D, K, ndev, devices, CUGP_KERNEL_SE, out);
+}
+
+int cugp_bcm_create_split_kernel(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
+                                 int kernel, cugp_bcm** out)
+{
     if (!X || !y || N <= 0 || D <= 0 || K <= 0 || K > N) return CUGP_ERR_INVALID;
+    if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52) return CUGP_ERR_INVALID;
     std::vector<int> rows(K), off(K);
     const int part = N / K;
     int start = 0;
@@ -106,7 +123,7 @@ int cugp_bcm_create_split_multi(const double* X, const double* y, int N, int D, 
         rows[k] = (k == K - 1) ? (N - start) : part;
         start += part;
     }
-    int rc = cugp_bcm_create_multi(ndev, devices, K, rows.data(), D, out);
+    int rc = cugp_bcm_create_kernel(ndev, devices, K, rows.data(), D, kernel, out);
     if (rc) return rc;
     for (int k = 0; k < K; k++) {
         rc = cugp_bcm_set_expert_data(*out, k, X + (size_t)off[k] * D, y + off[k]);
@@ -128,6 +145,13 @@ int cugp_bcm_destroy(cugp_bcm* b)
     b->pred_host.release();
     for (hipEvent_t e : b->pred_ev) (void)hipEventDestroy(e);
     delete b;
+    return CUGP_OK;
+}
+
+int cugp_bcm_kernel_kind(const cugp_bcm* b, int* kernel)
+{
+    if (!b || !kernel) return CUGP_ERR_INVALID;
+    *kernel = b->kernel;
     return CUGP_OK;
 }
 

@@ -120,6 +120,9 @@ struct cugp_gp {
     // the d weights exp(-theta_c); result rows are 8 + d + 2 doubles (kernels.h: ARD_ROW_GRAD)
     bool ard = false;
     std::vector<double> hpa, last_ga;
+    // covariance family (cugp.h CUGP_KERNEL_*, kernels.h KERNEL_*), for life; ARD handles are SE.  Read wherever one of
+    // the four passes that evaluate the kernel function is launched; nothing else depends on it.
+    int kernel = KERNEL_SE;
     bool have_data = false;
     bool factor_valid = false;     // A holds L for (data, hp)
     bool inverse_valid = false;    // T, U, Kinv, alpha hold the inverse quantities for (data, hp)
@@ -840,7 +843,7 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
     {
         TimedLaunch tl(g, s, g->prof >= 5);
         if (g->ard) launch_kbuild_ard(g->dX, g->n, g->d, g->npad, hd, g->dA, false, s, tickets);
-        else launch_kbuild(g->dX, g->n, g->d, g->npad, h, g->dA, false, s, hd, B(g), tickets);   // also zeroes the step tickets
+        else launch_kbuild(g->dX, g->n, g->d, g->npad, h, g->dA, false, s, hd, B(g), tickets, g->kernel);   // also zeroes the step tickets
         // (bytes, not flop: the lower 64x64 tiles of K written once + X read)
         tl.done(KIND_BUILD, (double)trace_num_blocks(g->npad) * 64 * 64 * 8 + (double)g->n * g->d * 8);
     }
@@ -870,7 +873,7 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
                              g->hout, s);
         else
             launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, hd, B(g), g->dz, g->dlogdet,
-                         g->dout, host_out(g), tickets + 2 * g->nt);
+                         g->dout, host_out(g), tickets + 2 * g->nt, g->kernel);
     } else {
         if ((rc = phase_mark(g, 3))) return rc;
         if ((rc = phase_mark(g, 4))) return rc;
@@ -967,7 +970,7 @@ int enqueue_continue(cugp_gp* g)
                          g->hout, s);
     } else {
         launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, nullptr, {}, g->dz, g->dlogdet, g->dout,
-                     g->hout, g->dtickets + 2 * g->nt);
+                     g->hout, g->dtickets + 2 * g->nt, g->kernel);
     }
     HIPCHK(hipGetLastError());
     g->pending = true;
@@ -1054,16 +1057,30 @@ int cugp_device_count(int* count)
 
 int cugp_create(int n, int d, int device, cugp_gp** out) { return cugp_create_padded(n, d, device, 0, out); }
 
-static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out);
+static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel = KERNEL_SE);
 
 int cugp_create_padded(int n, int d, int device, int npad_min, cugp_gp** out)
 {
     return create_handle(n, d, device, npad_min, false, out);
 }
 
+int cugp_create_kernel(int n, int d, int device, int npad_min, int kernel, cugp_gp** out)
+{
+    if (kernel < 0 || kernel >= KERNEL_COUNT)
+        return fail(CUGP_ERR_INVALID, "cugp_create_kernel: unknown kernel kind (0 SE, 1 Matern 3/2, 2 Matern 5/2)");
+    return create_handle(n, d, device, npad_min, false, out, kernel);
+}
+
+int cugp_kernel_kind(const cugp_gp* g, int* kernel)
+{
+    if (!g || !kernel) return fail(CUGP_ERR_INVALID, "cugp_kernel_kind: null argument");
+    *kernel = g->kernel;
+    return CUGP_OK;
+}
+
 int cugp_create_ard(int n, int d, int device, cugp_gp** out) { return create_handle(n, d, device, 0, true, out); }
 
-static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out)
+static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel)
 {
     if (!out || n <= 0 || d <= 0) return fail(CUGP_ERR_INVALID, "cugp_create: n, d must be positive");
     int cnt = 0;
@@ -1074,6 +1091,7 @@ static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_
     if (!g) return fail(CUGP_ERR_NOMEM, "host allocation");
     g->n = n; g->d = d; g->device = device;
     g->ard = ard;
+    g->kernel = kernel;
     if (ard) { g->hpa.assign((size_t)d + 2, 0.0); g->last_ga.assign((size_t)d + 2, NAN); }
     const size_t nrow = ard ? (size_t)ARD_ROW_GRAD + d + 2 : 8, ncol = ard ? (size_t)d + 2 : 3;
     g->nt = ((n > npad_min ? n : npad_min) + TILE - 1) / TILE;
@@ -1411,7 +1429,7 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
             if ((rc = upload_hs(g, g->stream))) return rc;
             launch_kcross_ard(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, g->dhs, dKs, g->stream);
         } else {
-            launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream, bt);
+            launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream, bt, g->kernel);
         }
         {
             // W = Ks L^-T: test tile tt, row tile ti sums k <= ti (the diagonal k tile of T is triangular: counted half)
@@ -1558,7 +1576,7 @@ static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_no
                                       cs.split - 1, f->dtickets, g->stream);
     } else {
         launch_predict_cov_finish(pb.xt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr.p,
-                                  cs.split - 1, f->dtickets, g->stream);
+                                  cs.split - 1, f->dtickets, g->stream, g->kernel);
     }
     HIPCHK(hipGetLastError());
     *dmean = pb.mean;
@@ -1658,7 +1676,7 @@ int cugp_compute_K_train(cugp_gp* g, double* K)
         if ((rc = upload_hs(g, g->stream))) return rc;
         launch_kbuild_ard(g->dX, g->n, g->d, g->npad, g->dhs, g->dA, true, g->stream);
     } else {
-        launch_kbuild(g->dX, g->n, g->d, g->npad, scalars(g), g->dA, true, g->stream);
+        launch_kbuild(g->dX, g->n, g->d, g->npad, scalars(g), g->dA, true, g->stream, nullptr, {}, nullptr, g->kernel);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2DAsync(K, (size_t)g->n * sizeof(double), g->dA, (size_t)g->npad * sizeof(double),
@@ -1703,7 +1721,7 @@ int cugp_compute_k_test(cugp_gp* g, const double* Xt, int nt, double* Ks)
             e = hipMemcpyAsync(g->dhs, g->hhs, hs_bytes(g), hipMemcpyHostToDevice, g->stream);
             launch_kcross_ard(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, g->dhs, dKs, g->stream);
         } else {
-            launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, scalars(g), dKs, g->stream);
+            launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, scalars(g), dKs, g->stream, {}, g->kernel);
         }
         e = hipMemcpy2DAsync(Ks, (size_t)g->n * sizeof(double), dKs, (size_t)g->npad * sizeof(double),
                              (size_t)g->n * sizeof(double), nt, hipMemcpyDeviceToHost, g->stream);
@@ -2194,6 +2212,9 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
         if (!experts[i] || experts[i]->npad != experts[0]->npad || experts[i]->d != experts[0]->d ||
             experts[i]->device != experts[0]->device)
             return CUGP_ERR_INVALID;
+    for (int i = 0; i < k; i++)
+        if (experts[i]->kernel != experts[0]->kernel)
+            return fail(CUGP_ERR_INVALID, "cugp_group_create: the experts have different kernel kinds (one launch serves them all)");
     for (int i = 0; i < k; i++)
         if (experts[i]->ard) return fail(CUGP_ERR_INVALID, "cugp_group_create: ARD handles cannot be grouped (the exchange rows hold 3 gradients)");
     cugp_group* gr = new (std::nothrow) cugp_group;

@@ -43,6 +43,13 @@ inline int tune(int key) { return t_tune[key]; }
 
 struct HyperScalars;
 
+// covariance family of a handle (cugp.h: CUGP_KERNEL_*), fixed when it is created.  The four passes that evaluate the
+// kernel function (build, cross-covariance, joint-covariance epilogue, gradient trace) take it as their last argument
+// and launch the instantiation for it -- k_build / k_cross / k_predict_cov_finish / k_trace for SE, the same bodies as
+// k_*_matern<KIND> otherwise, with everything SE's launches carry (batched experts, ticket zeroing, device-resident
+// hyper-scalars, stamps, the fused final sums).  ARD handles are SE only.
+enum { KERNEL_SE = 0, KERNEL_MATERN32 = 1, KERNEL_MATERN52 = 2, KERNEL_COUNT = 3 };
+
 // Batched launches: the experts of a BCM on one device have the same shapes, so one launch can serve all of
 // them -- blockIdx.y picks the expert and the kernel takes its buffers from a device-resident table instead
 // of its pointer arguments.  (16 experts x ~45 launches per evaluation from 16 streams were bounded by the
@@ -66,7 +73,8 @@ struct HyperScalars {              // exp(2*theta) evaluated on the host, as the
 // lower 64x64 tiles of K (+ mirror when `full`), padding rows/cols >= n set to identity
 // hd (optional, also below): read the hyper-scalars from device memory instead of the argument
 void launch_kbuild(const double* X, int n, int d, int npad, HyperScalars h, double* K, bool full,
-                   hipStream_t s, const HyperScalars* hd = nullptr, Batch bt = {}, unsigned* tickets = nullptr);
+                   hipStream_t s, const HyperScalars* hd = nullptr, Batch bt = {}, unsigned* tickets = nullptr,
+                   int kind = KERNEL_SE);
                    // tickets: the factorisation's arrival counters -- 2 * npad/128 per expert ([0, nt) the step tickets of
                    // k_syrk_step, [nt, 2 nt) the stage counters of k_trtri_block) --, zeroed by the launch when given
 // S[i][j] = |x_i - x_j|^2 / c, zero diagonal, full symmetric (N2, covkernel.cpp:130-157)
@@ -74,7 +82,7 @@ void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S,
 // Ks[t][i] = sf2 * exp(-0.5*|x_i - xt_t|^2 / l^2), row-major nt_pad x npad (pad = 0)   (N12)
 // bt (batched): blockIdx.y = expert, X and n from the table, Ks[expert][ntpad][npad]
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
-                   HyperScalars h, double* Ks, hipStream_t s, Batch bt = {});
+                   HyperScalars h, double* Ks, hipStream_t s, Batch bt = {}, int kind = KERNEL_SE);
 
 // ---- ARD: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart) ----
 // k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd: DEVICE
@@ -158,7 +166,8 @@ void launch_predict_cov(const double* W, int ld, int ntpad, const CovShape& c, d
 // A (lower 64x64 tiles, in place) = k(Xt,Xt) (+ sn2 on the diagonal when with_noise) + jitter I - (A + scr[0] + ...
 // + scr[nscr - 1]), identity beyond nt; tickets (when given): the factorisation's arrival counters, zeroed
 void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, HyperScalars h, bool with_noise, double jitter,
-                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s);
+                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s,
+                               int kind = KERNEL_SE);
 // strict upper triangle of the nt diagonal 128x128 tiles of A := 0
 void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s);
 // out[s * nt + t] = mean[t] + F[s * ld + t]   (s < ns, t < nt)
@@ -188,7 +197,7 @@ int trace_num_blocks(int npad);
 void launch_trace(const double* X, int n, int d, int npad, HyperScalars h, const double* Kinv,
                   const double* alpha, double* part, hipStream_t s, const HyperScalars* hd = nullptr,
                   Batch bt = {}, const double* z = nullptr, const double* logdet_part = nullptr, double* out = nullptr,
-                  double* hout = nullptr, unsigned* ticket = nullptr);
+                  double* hout = nullptr, unsigned* ticket = nullptr, int kind = KERNEL_SE);
 // arrival counters per expert: [0, nt) step tickets, [nt, 2 nt) stage counters of k_trtri_block, [2 nt] k_trace's fused finalize
 constexpr int ticket_count(int nt) { return 2 * nt + 1; }
 // out[0..3] = LL, g0, g1, g2  (LL only when part == nullptr)

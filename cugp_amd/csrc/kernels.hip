@@ -954,11 +954,56 @@ __device__ __forceinline__ double div_by(double a, const DivBy& d)
     return __builtin_fma(rem, d.y, q0);
 }
 
+// ---- Matern 3/2 and 5/2 (GPML covMaterniso, d = 3 and 5): KIND as kernels.h's KERNEL_* ----
+// One entry from s = |x - x'|^2 / l^2 (by div_by, as SE's): r = sqrt(s) correctly rounded, a = c r with c = RN(sqrt 3) or
+// RN(sqrt 5), ONE exp(-a), then  kf = sf2 (p e),  dk = dkf / dlog l = sf2 (q e)  with
+//   3/2:  p = 1 + a,               q = a a
+//   5/2:  p = (1 + a) + t,         q = t (1 + a),   t = (a a) RN(1/3)
+// a a / 3 as a multiply by the rounded constant: an fp64 division is ~18 VALU instructions per entry where the multiply
+// is one, and it adds one rounding (of the constant) to a polynomial without cancellation.  No FMA contraction: the
+// CPU copy of these lines (tests/truth_matern.py) takes the same roundings.
+// Extremes: s = 0 -> a = 0, e = 1: kf = sf2 exactly, dk = 0.  s = +inf (l^2 = 0) -> e = 0, and so for a finite a whose
+// exp underflows: both are 0 exactly (the guard: (1 + inf) * 0 and, for a > 1e154, (a a) * 0 would be NaN).
+template <int KIND>
+__device__ __forceinline__ void matern_entry(double s, double sf2, double& kf, double& dk)
+{
+#pragma clang fp contract(off)
+    static_assert(KIND == KERNEL_MATERN32 || KIND == KERNEL_MATERN52, "Matern kinds only");
+    const double c = KIND == KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979;
+    const double a = c * __builtin_sqrt(s);
+    const double e = exp(-a);
+    const double p1 = 1.0 + a;
+    double p, q;
+    if (KIND == KERNEL_MATERN32) {
+        p = p1;
+        q = a * a;
+    } else {
+        const double t = (a * a) * 0.3333333333333333;
+        p = p1 + t;
+        q = t * p1;
+    }
+    const bool dead = e == 0.0;
+    kf = dead ? 0.0 : sf2 * (p * e);
+    dk = dead ? 0.0 : sf2 * (q * e);
+}
+// the SE / Matern value of one entry without the noise term (the three passes that need no derivative)
+template <int KIND>
+__device__ __forceinline__ double kernel_value(double d2, const DivBy& dl, double sf2)
+{
+    if constexpr (KIND == KERNEL_SE) {
+        return sf2 * exp(div_by(-d2 * 0.5, dl));                  // covkernel.cpp:89
+    } else {
+        double kf, dk;
+        matern_entry<KIND>(div_by(d2, dl), sf2, kf, dk);
+        return kf;
+    }
+}
+
 // hd (when given): hyper-scalars resident in device memory -- a captured graph of the evaluation is replayed
 // with new hyper-parameters by refreshing that one buffer instead of every kernel's arguments
 // ARD (k_build_ard): per-dimension weights behind the hyper-scalars in device memory (hd is then always given, and
 // ell_sq is not read: K = sf2 exp(-acc / 2) of the weighted squared distance, no division); K only (full < 2)
-template <bool ARD>
+template <bool ARD, int KIND = KERNEL_SE>
 __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, int d, int npad,
                                            HyperScalars h_arg, const HyperScalars* __restrict__ hd,
                                            double* __restrict__ K, int full, unsigned* __restrict__ tickets,
@@ -1000,7 +1045,7 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
             } else if (full == 2) {
                 v = (i == j) ? 0.0 : div_by(d2v[a][b], dl);    // covkernel.cpp:143-151 (squared distance / c)
             } else {
-                v = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));   // covkernel.cpp:89
+                v = kernel_value<KIND>(d2v[a][b], dl, h.signal_var);   // covkernel.cpp:89
                 if (i == j) v += h.noise_var;                            // covkernel.cpp:93-94
             }
             out[a][b] = in ? v : ((i == j) ? 1.0 : 0.0);                // identity padding
@@ -1036,9 +1081,20 @@ __global__ __launch_bounds__(256) void k_build_ard(const double* __restrict__ X,
     build_body<true>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, nullptr, stamp);
 }
 
+// Matern instantiations: k_build's arguments and everything that rides with it (batched experts, ticket zeroing,
+// device-resident hyper-scalars, stamps); full < 2 (the squared-distance intermediate does not depend on the kind)
+template <int KIND>
+__global__ __launch_bounds__(256) void k_build_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                      HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                                      double* __restrict__ K, int full, unsigned* __restrict__ tickets,
+                                                      const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
+{
+    build_body<false, KIND>(X, n, d, npad, h_arg, hd, K, full, tickets, bt, stamp);
+}
+
 // Ks[t][i] = sf2 * exp(-0.5 |xt_t - x_i|^2 / l^2) (no noise, covkernel.cpp:105-116); zero padding
 // bt (batched): blockIdx.y selects the expert -- X, n from its table entry, Ks = the expert's [ntpad][npad] slice
-template <bool ARD>
+template <bool ARD, int KIND = KERNEL_SE>
 __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, int d, int npad,
                                            const double* __restrict__ Xt, int nt, int ntpad, const HyperScalars& h,
                                            const double* __restrict__ wts,
@@ -1067,7 +1123,8 @@ __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, 
         for (int b = 0; b < 4; b++) {
             const int i = i0 + col4(tx, b);
             o[b] = (tr < nt && i < n)
-                       ? h.signal_var * (ARD ? exp(-0.5 * d2v[a][b]) : exp(div_by(-d2v[a][b] * 0.5, dl))) : 0.0;
+                       ? (ARD ? h.signal_var * exp(-0.5 * d2v[a][b]) : kernel_value<KIND>(d2v[a][b], dl, h.signal_var))
+                       : 0.0;
         }
         double* p = Ks + (size_t)tr * npad + i0 + tx * 2;
         *(d2*)p = (d2){o[0], o[1]};
@@ -1087,6 +1144,14 @@ __global__ __launch_bounds__(256) void k_cross_ard(const double* __restrict__ X,
                                                    const HyperScalars* __restrict__ hd, double* __restrict__ Ks)
 {
     cross_body<true>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, nullptr);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cross_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                      const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h,
+                                                      double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
+{
+    cross_body<false, KIND>(X, n, d, npad, Xt, nt, ntpad, h, nullptr, Ks, bt);
 }
 
 // ---- joint predictive covariance (cugp_predict_cov): Sigma = k(Xt,Xt) (+ sn2 I) - W W^T, W = Ks L^-T ----
@@ -1119,7 +1184,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_cov(const double* __restrict
 // diagonal) - (P_0 + P_1 + ...), in place over P_0; kss = sf2 exp(-|xt_i - xt_j|^2 / (2 l^2)) by k_build's formula and
 // squared-distance order; padding rows / columns >= nt become identity.  tickets (when given): the factorisation's
 // arrival counters, zeroed as k_build does.
-template <bool ARD>
+template <bool ARD, int KIND = KERNEL_SE>
 __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict__ Xt, int nt, int d, int ntpad,
                                                         const HyperScalars& h, const double* __restrict__ wts,
                                                         int with_noise, double jitter,
@@ -1154,7 +1219,7 @@ __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int j = j0 + col4(tx, b);
-            double v = h.signal_var * (ARD ? exp(-0.5 * d2v[a][b]) : exp(div_by(-d2v[a][b] * 0.5, dl)));
+            double v = ARD ? h.signal_var * exp(-0.5 * d2v[a][b]) : kernel_value<KIND>(d2v[a][b], dl, h.signal_var);
             if (i == j) {
                 if (with_noise) v += h.noise_var;
                 v += jitter;
@@ -1182,6 +1247,17 @@ __global__ __launch_bounds__(256) void k_predict_cov_finish_ard(const double* __
 {
     predict_cov_finish_body<true>(Xt, nt, d, ntpad, *hd, ard_weights(hd), with_noise, jitter, A, scr, pstride, nscr,
                                   tickets);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_predict_cov_finish_matern(const double* __restrict__ Xt, int nt, int d,
+                                                                   int ntpad, HyperScalars h, int with_noise,
+                                                                   double jitter, double* __restrict__ A,
+                                                                   const double* __restrict__ scr, size_t pstride,
+                                                                   int nscr, unsigned* __restrict__ tickets)
+{
+    predict_cov_finish_body<false, KIND>(Xt, nt, d, ntpad, h, nullptr, with_noise, jitter, A, scr, pstride, nscr,
+                                         tickets);
 }
 
 // The Cholesky writes the lower triangle only: the strict upper part of every 128x128 diagonal tile still holds Sigma,
@@ -2387,11 +2463,14 @@ struct FinalizeArgs {
 
 // gradient traces, fused: for every lower 64x64 tile recompute k(xi,xj) and |xi-xj|^2/l^2, read K^-1 once,
 // W = K^-1 - alpha alpha^T, accumulate  s1 = sum W*K*S, s2 = sum W*K, s3 = sum_i W_ii  (off-diagonal tiles x2)
-__global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int n, int d, int npad,
-                                               HyperScalars h_arg, const HyperScalars* __restrict__ hd,
-                                               const double* __restrict__ Kinv, const double* __restrict__ alpha,
-                                               double* __restrict__ part, const ExpertPtrs* __restrict__ bt,
-                                               FinalizeArgs fin)
+// KIND: s1 is sum W o dK/dlog l -- SE's K o S, or a Matern kind's dk of matern_entry (one exp(-a) for k and dk; zero on
+// the diagonal, where a = 0); s2, s3 and everything behind the sums keep their meaning
+template <int KIND>
+__device__ __forceinline__ void trace_body(const double* __restrict__ X, int n, int d, int npad,
+                                           HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                           const double* __restrict__ Kinv, const double* __restrict__ alpha,
+                                           double* __restrict__ part, const ExpertPtrs* __restrict__ bt,
+                                           FinalizeArgs fin)
 {
     if (bt) {
         const ExpertPtrs& e = bt[blockIdx.y];
@@ -2431,16 +2510,30 @@ __global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int
             const int j = j0 + col4(tx, b);
             if (i < n && j < n && (ti != tj || j <= i)) {
                 const double w = kv[b] - ai * aj[b];
-                double kse = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
-                const double sd = div_by(d2v[a][b], dl);
-                if (i == j) {
-                    kse += h.noise_var;
-                    s1 += w * (kse * sd);
-                    s2 += w * kse;
-                    s3 += w;
+                if constexpr (KIND == KERNEL_SE) {
+                    double kse = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
+                    const double sd = div_by(d2v[a][b], dl);
+                    if (i == j) {
+                        kse += h.noise_var;
+                        s1 += w * (kse * sd);
+                        s2 += w * kse;
+                        s3 += w;
+                    } else {
+                        s1 += 2.0 * (w * (kse * sd));
+                        s2 += 2.0 * (w * kse);
+                    }
                 } else {
-                    s1 += 2.0 * (w * (kse * sd));
-                    s2 += 2.0 * (w * kse);
+                    double kf, dk;
+                    matern_entry<KIND>(div_by(d2v[a][b], dl), h.signal_var, kf, dk);
+                    if (i == j) {
+                        kf += h.noise_var;
+                        s1 += w * dk;
+                        s2 += w * kf;
+                        s3 += w;
+                    } else {
+                        s1 += 2.0 * (w * dk);
+                        s2 += 2.0 * (w * kf);
+                    }
                 }
             }
         }
@@ -2468,6 +2561,25 @@ __global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (t == 0) *fin.ticket = 0u;                          // (ready for the next evaluation; nobody else touches it any more)
     finalize_sums<256, true>(fin.z, npad, n, fin.logdet_part, fin.nt, part, (int)gridDim.x, h, fin.out, fin.hout, lds);
+}
+
+__global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int n, int d, int npad,
+                                               HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                               const double* __restrict__ Kinv, const double* __restrict__ alpha,
+                                               double* __restrict__ part, const ExpertPtrs* __restrict__ bt,
+                                               FinalizeArgs fin)
+{
+    trace_body<KERNEL_SE>(X, n, d, npad, h_arg, hd, Kinv, alpha, part, bt, fin);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_trace_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                      HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                                      const double* __restrict__ Kinv,
+                                                      const double* __restrict__ alpha, double* __restrict__ part,
+                                                      const ExpertPtrs* __restrict__ bt, FinalizeArgs fin)
+{
+    trace_body<KIND>(X, n, d, npad, h_arg, hd, Kinv, alpha, part, bt, fin);
 }
 
 // single workgroup: deterministic final sums and the scalar formulas
@@ -2728,10 +2840,12 @@ thread_local const int* t_tune = g_tune_init;
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
 
 void launch_kbuild(const double* X, int n, int d, int npad, HyperScalars h, double* K, bool full, hipStream_t s,
-                   const HyperScalars* hd, Batch bt, unsigned* tickets)
+                   const HyperScalars* hd, Batch bt, unsigned* tickets, int kind)
 {
-    hipLaunchKernelGGL(k_build, dim3(tri_count(npad / KT), bt.count), dim3(256), 0, s, X, n, d, npad, h, hd, K,
-                       full ? 1 : 0, tickets, bt.tab, take_stamp());
+    const dim3 grid(tri_count(npad / KT), bt.count);
+    auto* k = kind == KERNEL_MATERN32 ? k_build_matern<KERNEL_MATERN32>
+              : kind == KERNEL_MATERN52 ? k_build_matern<KERNEL_MATERN52> : k_build;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, X, n, d, npad, h, hd, K, full ? 1 : 0, tickets, bt.tab, take_stamp());
 }
 
 void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S, hipStream_t s)
@@ -2757,10 +2871,12 @@ void launch_kcross_ard(const double* X, int n, int d, int npad, const double* Xt
 }
 
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad, HyperScalars h,
-                   double* Ks, hipStream_t s, Batch bt)
+                   double* Ks, hipStream_t s, Batch bt, int kind)
 {
-    hipLaunchKernelGGL(k_cross, dim3((ntpad / KT) * (npad / KT), bt.count), dim3(256), 0, s, X, n, d, npad, Xt, nt,
-                       ntpad, h, Ks, bt.tab);
+    auto* k = kind == KERNEL_MATERN32 ? k_cross_matern<KERNEL_MATERN32>
+              : kind == KERNEL_MATERN52 ? k_cross_matern<KERNEL_MATERN52> : k_cross;
+    hipLaunchKernelGGL(k, dim3((ntpad / KT) * (npad / KT), bt.count), dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, h,
+                       Ks, bt.tab);
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
@@ -3004,10 +3120,12 @@ void launch_predict_cov(const double* W, int ld, int ntpad, const CovShape& c, d
 }
 
 void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, HyperScalars h, bool with_noise, double jitter,
-                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s)
+                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s, int kind)
 {
-    hipLaunchKernelGGL(k_predict_cov_finish, dim3(tri_count(ntpad / KT)), dim3(256), 0, s, Xt, nt, d, ntpad, h,
-                       with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+    auto* k = kind == KERNEL_MATERN32 ? k_predict_cov_finish_matern<KERNEL_MATERN32>
+              : kind == KERNEL_MATERN52 ? k_predict_cov_finish_matern<KERNEL_MATERN52> : k_predict_cov_finish;
+    hipLaunchKernelGGL(k, dim3(tri_count(ntpad / KT)), dim3(256), 0, s, Xt, nt, d, ntpad, h, with_noise ? 1 : 0, jitter,
+                       A, scr, (size_t)ntpad * ntpad, nscr, tickets);
 }
 
 void launch_predict_cov_finish_ard(const double* Xt, int nt, int d, int ntpad, const HyperScalars* hd, bool with_noise,
@@ -3075,15 +3193,16 @@ int trace_num_blocks(int npad) { return tri_count(npad / KT); }
 
 void launch_trace(const double* X, int n, int d, int npad, HyperScalars h, const double* Kinv, const double* alpha,
                   double* part, hipStream_t s, const HyperScalars* hd, Batch bt, const double* z, const double* logdet_part,
-                  double* out, double* hout, unsigned* ticket)
+                  double* out, double* hout, unsigned* ticket, int kind)
 {
     // the last block takes the final sums where the launch is small (its 256 threads against k_finalize's 1024: at 8192
     // rows -- 8256 blocks -- the separate launch is as fast and keeps the blocks' stores plain); TUNE_FINALIZE_FUSE_MAX
     const int nblocks = tri_count(npad / KT);
     const bool fuse = out != nullptr && nblocks <= tune(TUNE_FINALIZE_FUSE_MAX);
     const FinalizeArgs fin{z, logdet_part, npad / TILE, fuse ? out : nullptr, hout, ticket};
-    hipLaunchKernelGGL(k_trace, dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, h, hd, Kinv,
-                       alpha, part, bt.tab, fin);
+    auto* k = kind == KERNEL_MATERN32 ? k_trace_matern<KERNEL_MATERN32>
+              : kind == KERNEL_MATERN52 ? k_trace_matern<KERNEL_MATERN52> : k_trace;
+    hipLaunchKernelGGL(k, dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, h, hd, Kinv, alpha, part, bt.tab, fin);
     if (out != nullptr && !fuse)
         launch_finalize(z, npad, n, logdet_part, npad / TILE, part, nblocks, h, out, hout, s, hd, bt);
 }

@@ -12,19 +12,42 @@ from . import capi
 from .capi import check, f64, ptr
 
 
+KERNELS = {"se": capi.CUGP_KERNEL_SE, "matern32": capi.CUGP_KERNEL_MATERN32, "matern52": capi.CUGP_KERNEL_MATERN52}
+KERNEL_NAMES = {v: k for k, v in KERNELS.items()}
+
+
+def kernel_kind(kernel):
+    """"se" | "matern32" | "matern52" (or the C ABI's CUGP_KERNEL_* number) -> the number."""
+    if isinstance(kernel, str):
+        if kernel.lower() not in KERNELS:
+            raise ValueError("kernel must be one of %s, not %r" % (sorted(KERNELS), kernel))
+        return KERNELS[kernel.lower()]
+    if int(kernel) not in KERNEL_NAMES:
+        raise ValueError("unknown kernel kind %r" % (kernel,))
+    return int(kernel)
+
+
 class Covsum:
     """One GP expert on one GPU.  Covsum(n, d) as covkernel.cpp:14-37; X, y are given per call as in
     the reference and uploaded whenever their CONTENTS differ from what the GPU holds (the reference
     recomputes K from the arguments on every call; comparing n*d doubles is nothing beside an O(n^3)
     evaluation, and an in-place edit of y or a recycled array address can not go unnoticed).
     ard=True: one length scale per input dimension (cugp_create_ard; GPML covSEard's order): the hyper-parameter
-    vector is [log l_1 .. log l_d, log sigma_f, log sigma_n], gradients and cg_solve traces have d + 2 (+ 1) entries."""
+    vector is [log l_1 .. log l_d, log sigma_f, log sigma_n], gradients and cg_solve traces have d + 2 (+ 1) entries.
+    kernel="se" | "matern32" | "matern52": the covariance family (cugp_create_kernel; GPML covMaterniso with d = 3, 5),
+    same three hyper-parameters; fixed for the life of the handle.  ARD is squared-exponential only."""
 
-    def __init__(self, n, d, device=0, npad_min=0, ard=False):
+    def __init__(self, n, d, device=0, npad_min=0, ard=False, kernel="se"):
         self.n, self.d, self.device, self.ard = int(n), int(d), int(device), bool(ard)
         self.nh = self.d + 2 if self.ard else 3
+        self._kind = kernel_kind(kernel)
+        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
+            raise ValueError("ard=True is squared-exponential only (ARD x Matern is not built)")
         self._h = C.c_void_p()
-        if self.ard:
+        if self._kind != capi.CUGP_KERNEL_SE:
+            check(capi.lib().cugp_create_kernel(self.n, self.d, self.device, int(npad_min), self._kind,
+                                                C.byref(self._h)))
+        elif self.ard:
             if npad_min:
                 raise ValueError("an ARD handle cannot be padded (it cannot join a BCM group)")
             check(capi.lib().cugp_create_ard(self.n, self.d, self.device, C.byref(self._h)))
@@ -47,6 +70,13 @@ class Covsum:
     @property
     def handle(self):
         return self._h
+
+    @property
+    def kernel(self):
+        """The handle's covariance family as the library reports it: "se", "matern32" or "matern52"."""
+        k = C.c_int()
+        check(capi.lib().cugp_kernel_kind(self._h, C.byref(k)))
+        return KERNEL_NAMES[k.value]
 
     # -- data --
     def set_data(self, X, y):
@@ -327,21 +357,34 @@ class BCM:
     GPUs (expert k on devices[k mod len], cg_solver.cpp:93; default: the one `device`).  `BCM.split` reproduces
     the reference constructor's row partition (BCM.cpp:85-110)."""
 
-    def __init__(self, rows, d, device=0, devices=None):
+    def __init__(self, rows, d, device=0, devices=None, kernel="se"):
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         devs = np.ascontiguousarray([device] if devices is None else list(devices), dtype=np.int32)
         self.rows, self.d, self.device, self.devices = rows.tolist(), int(d), int(devs[0]), devs.tolist()
+        self._kind = kernel_kind(kernel)
         self._h = C.c_void_p()
-        check(capi.lib().cugp_bcm_create_multi(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
-                                               rows.ctypes.data_as(capi._ip), self.d, C.byref(self._h)))
+        if self._kind != capi.CUGP_KERNEL_SE:
+            check(capi.lib().cugp_bcm_create_kernel(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
+                                                    rows.ctypes.data_as(capi._ip), self.d, self._kind,
+                                                    C.byref(self._h)))
+        else:
+            check(capi.lib().cugp_bcm_create_multi(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
+                                                   rows.ctypes.data_as(capi._ip), self.d, C.byref(self._h)))
+
+    @property
+    def kernel(self):
+        """The covariance family of every expert: "se", "matern32" or "matern52"."""
+        k = C.c_int()
+        check(capi.lib().cugp_bcm_kernel_kind(self._h, C.byref(k)))
+        return KERNEL_NAMES[k.value]
 
     @classmethod
-    def split(cls, X, y, K, device=0, devices=None):
+    def split(cls, X, y, K, device=0, devices=None, kernel="se"):
         X, y = f64(X), f64(y)
         N, D = X.shape
         part = N // K
         rows = [part] * (K - 1) + [N - part * (K - 1)]
-        b = cls(rows, D, device, devices)
+        b = cls(rows, D, device, devices, kernel=kernel)
         off = 0
         for k in range(K):
             b.set_expert_data(k, X[off: off + rows[k]], y[off: off + rows[k]])
@@ -400,7 +443,7 @@ class BCM:
         check(capi.lib().cugp_bcm_expert(self._h, int(k), C.byref(h)))
         e = Covsum.__new__(Covsum)
         e.n, e.d, e.device, e._h, e._data_key = self.rows[k], self.d, self.devices[k % len(self.devices)], h, None
-        e.ard, e.nh = False, 3
+        e.ard, e.nh, e._kind = False, 3, self._kind
         e.close = lambda: None                    # not ours to destroy
         return e
 

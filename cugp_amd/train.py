@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--budget", type=int, default=100)
     ap.add_argument("--test-rows", type=int, default=0, help="rows after --rows in chunk 0 used as a held-out set")
     ap.add_argument("--backend", default="nccl")
+    ap.add_argument("--kernel", default="se", choices=["se", "matern32", "matern52"],
+                    help="covariance family of every expert (the same on every rank)")
     args = ap.parse_args()
 
     import torch
@@ -49,7 +51,7 @@ def main():
     mine = {k for k in range(args.numchunks) if expert_owner(k, world) == rank}
     shards = dataset.load_shards(args.inputs, args.labels, args.numchunks, rows=None, only=mine)
     experts = [None if s is None else (s[0][:args.rows], s[1][:args.rows]) for s in shards]
-    bcm = ShardedBCM(experts, rank=rank, world=world, device=local)
+    bcm = ShardedBCM(experts, rank=rank, world=world, device=local, kernel=args.kernel)
     bcm.set_loghyper(args.hp)
     t0 = time.perf_counter()
     trace = bcm.cg_solve(args.budget)

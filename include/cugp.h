@@ -92,6 +92,29 @@ int cugp_get_loghyper_ard(const cugp_gp *gp, double *hp, int nh);
 int cugp_loglik_grad_ard(cugp_gp *gp, double *ll, double *g, int nh);
 int cugp_loglik_grad_fetch_ard(cugp_gp *gp, double *ll, double *g /* may be NULL */, int nh);
 
+/* ---- covariance families: Matern 3/2 and 5/2 beside the squared exponential.  The reference has no counterpart; the
+ *      convention is GPML's covMaterniso with d = 3 and d = 5.  The hyper-parameters are the isotropic three,
+ *      theta = [log l, log sigma_f, log sigma_n], so every 3-entry call, the exchange rows and the optimisers carry over.
+ *      With s = |x - x'|^2 / l^2, r = sqrt(s), sf2 = exp(2 theta_1), sn2 = exp(2 theta_2):
+ *        CUGP_KERNEL_SE       k = sf2 exp(-s / 2) + sn2 delta                      (every other create call)
+ *        CUGP_KERNEL_MATERN32 a = sqrt(3) r:  k = sf2 (1 + a) exp(-a) + sn2 delta,          dk/dtheta_0 = sf2 a^2 exp(-a)
+ *        CUGP_KERNEL_MATERN52 a = sqrt(5) r:  k = sf2 (1 + a + a^2/3) exp(-a) + sn2 delta,  dk/dtheta_0 = sf2 (a^2/3)(1 + a) exp(-a)
+ *      Gradients are of -LL as everywhere: g0 = 1/2 sum W o dK/dtheta_0, g1 = sum W o Kf, g2 = sn2 tr W
+ *      (W = K^-1 - alpha alpha', Kf = K - sn2 I).  k(x, x) = sf2 + sn2 for every kind.  l -> inf (s = 0) gives exactly sf2;
+ *      l^2 = 0 (s = +inf) and an exp(-a) that underflows give exactly 0 for k and dk/dtheta_0 off the diagonal.
+ * The kind is fixed when the handle is created.  Kind 0 through cugp_create_kernel is cugp_create_padded's handle, bit for
+ * bit; an unknown kind is CUGP_ERR_INVALID before any device call.  Every call that works on an isotropic handle works
+ * on a Matern one: data, overlap, LL / gradient in all forms, the continuation from a valid factor, the predictions
+ * (marginal, joint, draws), K, k_test, the squared-distance intermediate (which does not depend on the kind), factor,
+ * inverse, alpha, profiling, tuning, the optimisers, groups and every cugp_bcm_* call.  cugp_create_ard stays SE:
+ * ARD x Matern is not built.  Experts of one group (and so of one BCM) must have the same kind; the ranks of a BCM
+ * sharded one process per GPU must be created with the same kind -- the caller's duty, like passing the same Xt. */
+#define CUGP_KERNEL_SE 0
+#define CUGP_KERNEL_MATERN32 1
+#define CUGP_KERNEL_MATERN52 2
+int cugp_create_kernel(int n, int d, int device, int npad_min, int kernel, cugp_gp **out);
+int cugp_kernel_kind(const cugp_gp *gp, int *kernel);
+
 /* ---- objective ----
  * cugp_loglik       : Covsum::compute_loglikelihood covkernel.cpp:118-129 ; compute_log_likelihood cuda_gp.cu:838-855
  * cugp_loglik_grad  : the pair compute_loglikelihood + compute_gradient_loghyperparam (covkernel.cpp:162-263 ;
@@ -238,6 +261,12 @@ int cugp_bcm_create_multi(int ndev, const int *devices, int nexperts, const int 
 int cugp_bcm_create_split_multi(const double *X, const double *y, int N, int D, int K, int ndev, const int *devices,
                                 cugp_bcm **out);
 int cugp_bcm_create_split(const double *X, const double *y, int N, int D, int K, int device, cugp_bcm **out);
+/* the two _multi forms with every expert of covariance family `kernel` (CUGP_KERNEL_*; 0 = the calls above, bit for
+ * bit; an unknown kind: CUGP_ERR_INVALID before any device call); cugp_bcm_kernel_kind reports it */
+int cugp_bcm_create_kernel(int ndev, const int *devices, int nexperts, const int *rows, int d, int kernel, cugp_bcm **out);
+int cugp_bcm_create_split_kernel(const double *X, const double *y, int N, int D, int K, int ndev, const int *devices,
+                                 int kernel, cugp_bcm **out);
+int cugp_bcm_kernel_kind(const cugp_bcm *b, int *kernel);
 int cugp_bcm_destroy(cugp_bcm *b);
 int cugp_bcm_num_experts(const cugp_bcm *b, int *k);
 int cugp_bcm_expert(cugp_bcm *b, int k, cugp_gp **gp);
