@@ -12,6 +12,7 @@
 // T, U, Kinv are allocated on first use (gradient / prediction), A on first evaluation.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdio>
@@ -114,12 +115,12 @@ struct cugp_gp {
                                    // counter of the hand-over block that starts at that tile row (k_trtri_block)
     double* hout = nullptr;        // pinned, 8 doubles (ARD: 8 + d + 2)
     int nblocks_trace = 0;
-    double hp[3] = {0, 0, 0};
-    // ARD handle (cugp_create_ard; for life): theta = [log l_1 .. log l_d, log sigma_f, log sigma_n] in hpa; hp[] mirrors
-    // {0, hpa[d], hpa[d + 1]} so that scalars() gives {1, sf2, sn2}.  hhs / dhs then hold the hyper-scalars FOLLOWED by
-    // the d weights exp(-theta_c); result rows are 8 + d + 2 doubles (kernels.h: ARD_ROW_GRAD)
+    // the nh log hyper-parameters and the gradient of the last evaluation: {log l, log sigma_f, log sigma_n}, or on an ARD
+    // handle (cugp_create_ard; for life) [log l_1 .. log l_d, log sigma_f, log sigma_n].  hhs / dhs then hold the
+    // hyper-scalars FOLLOWED by the d weights exp(-theta_c); result rows are 8 + d + 2 doubles (kernels.h: ARD_ROW_GRAD)
     bool ard = false;
-    std::vector<double> hpa, last_ga;
+    int nh = 3;
+    std::vector<double> theta = {0, 0, 0}, last_g = {NAN, NAN, NAN};
     // covariance family (cugp.h CUGP_KERNEL_*, kernels.h KERNEL_*), for life; ARD handles are SE.  Read wherever one of
     // the four passes that evaluate the kernel function is launched; nothing else depends on it.
     int kernel = KERNEL_SE;
@@ -146,7 +147,7 @@ struct cugp_gp {
     unsigned cfg_epoch = 1;        // bumped when a launch shape of this handle changed: captured graphs carry launch shapes
     bool counted = false;          // this handle is in g_live[device] (the budget of barrier grids, barrier_cap)
     int bar_quota = -1;            // barrier workgroups reserved for this handle from the device's pool; < 0: not yet asked for
-    double last_ll = NAN, last_g[3] = {NAN, NAN, NAN}, last_quad = NAN, last_logdet = NAN;
+    double last_ll = NAN, last_quad = NAN, last_logdet = NAN;
     // profiling
     int prof = 0;
     hipEvent_t pev[NPHASE + 1] = {};
@@ -176,8 +177,9 @@ namespace {
 
 HyperScalars scalars(const cugp_gp* g)
 {
-    // covkernel.cpp:65-67 -- exp(2*theta) on the host
-    return HyperScalars{std::exp(g->hp[0] * 2), std::exp(g->hp[1] * 2), std::exp(g->hp[2] * 2)};
+    // covkernel.cpp:65-67 -- exp(2*theta) on the host; ARD: no single length scale (ell_sq = 1, not read by its kernels)
+    const double* sf = &g->theta[g->nh - 2];
+    return HyperScalars{g->ard ? 1.0 : std::exp(g->theta[0] * 2), std::exp(sf[0] * 2), std::exp(sf[1] * 2)};
 }
 
 size_t hs_bytes(const cugp_gp* g) { return sizeof(HyperScalars) + (g->ard ? (size_t)g->d * sizeof(double) : 0); }
@@ -188,13 +190,23 @@ void stage_ard(cugp_gp* g)
 {
     *g->hhs = scalars(g);
     double* w = (double*)(g->hhs + 1);
-    for (int c = 0; c < g->d; c++) w[c] = std::exp(-g->hpa[c]);
+    for (int c = 0; c < g->d; c++) w[c] = std::exp(-g->theta[c]);
 }
 
 int upload_hs(cugp_gp* g, hipStream_t s)
 {
     HIPCHK(hipMemcpyAsync(g->dhs, g->hhs, hs_bytes(g), hipMemcpyHostToDevice, s));
     return CUGP_OK;
+}
+
+// g's covariance function for launches on s.  hd: the device-resident hyper-scalars the launches are to read, if any (a
+// captured evaluation, a group's); an ARD handle always reads its own (scalars and weights).  Where they are read, the
+// copy that refreshes them from the staging area goes onto s here, in front of the caller's launches.
+int cov_fn(cugp_gp* g, hipStream_t s, const HyperScalars* hd, CovFn* cf)
+{
+    if (g->ard) hd = g->dhs;
+    *cf = CovFn{g->kernel, g->ard, scalars(g), hd};
+    return hd ? upload_hs(g, s) : CUGP_OK;
 }
 
 int refuse_ard(const cugp_gp* g, const char* call, const char* use)
@@ -834,16 +846,15 @@ int phase_mark(cugp_gp* g, int i)
 int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
 {
     int rc;
-    const HyperScalars h = scalars(g);
     hipStream_t s = g->stream;
-    if (hd && (rc = upload_hs(g, s))) return rc;
+    CovFn cf;
+    if ((rc = cov_fn(g, s, hd, &cf))) return rc;
     if ((rc = phase_mark(g, 0))) return rc;
     unsigned* const tickets = g->grp ? g->grp->tickets : g->dtickets;
     if ((rc = reset_stamps(g))) return rc;
     {
         TimedLaunch tl(g, s, g->prof >= 5);
-        if (g->ard) launch_kbuild_ard(g->dX, g->n, g->d, g->npad, hd, g->dA, false, s, tickets);
-        else launch_kbuild(g->dX, g->n, g->d, g->npad, h, g->dA, false, s, hd, B(g), tickets, g->kernel);   // also zeroes the step tickets
+        launch_kbuild(g->dX, g->n, g->d, g->npad, cf, g->dA, false, s, B(g), tickets);   // also zeroes the step tickets
         // (bytes, not flop: the lower 64x64 tiles of K written once + X read)
         tl.done(KIND_BUILD, (double)trace_num_blocks(g->npad) * 64 * 64 * 8 + (double)g->n * g->d * 8);
     }
@@ -868,12 +879,8 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
             launch_trmv_upper(g->dU, g->npad, g->npad, g->dz, g->dalpha, s, B(g));    // alpha = L^-T z
         }
         // traces and the final sums in ONE launch: the last block of k_trace finishes the evaluation (kernels.hip)
-        if (g->ard)
-            launch_trace_ard(g->dX, g->n, g->d, g->npad, hd, g->dKinv, g->dalpha, g->dpart, g->dz, g->dlogdet, g->dout,
-                             g->hout, s);
-        else
-            launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, hd, B(g), g->dz, g->dlogdet,
-                         g->dout, host_out(g), tickets + 2 * g->nt, g->kernel);
+        launch_trace(g->dX, g->n, g->d, g->npad, cf, g->dKinv, g->dalpha, g->dpart, s, B(g), g->dz, g->dlogdet, g->dout,
+                     host_out(g), tickets + 2 * g->nt);
     } else {
         if ((rc = phase_mark(g, 3))) return rc;
         if ((rc = phase_mark(g, 4))) return rc;
@@ -882,7 +889,7 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
             else HIPCHK(hipMemcpyAsync(g->dw, g->dy, (size_t)g->npad * sizeof(double), hipMemcpyDeviceToDevice, s));
             launch_trsv_lower(g->dA, g->dT, g->npad, g->nt, g->dw, g->dz, s, B(g));   // L z = y
         }
-        launch_finalize(g->dz, g->npad, g->n, g->dlogdet, g->nt, nullptr, 0, h, g->dout, host_out(g), s, hd, B(g));
+        launch_finalize(g->dz, g->npad, g->n, g->dlogdet, g->nt, nullptr, 0, cf.h, g->dout, host_out(g), s, cf.hd, B(g));
     }
     if ((rc = phase_mark(g, 5))) return rc;
     HIPCHK(hipGetLastError());
@@ -935,7 +942,7 @@ int enqueue_eval(cugp_gp* g, bool want_grad)
                        pipe_block(g, want_grad) == 0;
     if (graph && !g->ard) *g->hhs = scalars(g);              // (ARD: staged where theta was set, weights included)
     if ((rc = graph ? replay_eval(g, g->gexec, g->gepoch, want_grad)
-                    : record_eval(g, want_grad, g->ard ? g->dhs : nullptr))) return rc;
+                    : record_eval(g, want_grad, nullptr))) return rc;
     g->pending = true;
     g->pending_grad = want_grad;
     g->pev_valid = g->prof >= 1;
@@ -956,7 +963,6 @@ int enqueue_continue(cugp_gp* g)
     if ((rc = ensure_inverse_bufs(g))) return rc;
     if (const int pe = prepare_kernels())
         return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
-    const HyperScalars h = scalars(g);
     hipStream_t s = g->stream;
     g->inverse_valid = false;
     HIPCHK(hipMemsetAsync(g->dtickets + g->nt, 0, (size_t)(g->nt + 1) * sizeof(unsigned), s));     // k_trtri_block's stage counters, k_trace's arrival counter
@@ -964,14 +970,10 @@ int enqueue_continue(cugp_gp* g)
     if ((rc = enqueue_inverse_block(g, 0, g->nt, true, s, nullptr, nullptr))) return rc;
     launch_trmv_lower(g->dT, g->npad, g->npad, g->dy, g->dz, s);
     launch_trmv_upper(g->dU, g->npad, g->npad, g->dz, g->dalpha, s);
-    if (g->ard) {
-        if ((rc = upload_hs(g, s))) return rc;
-        launch_trace_ard(g->dX, g->n, g->d, g->npad, g->dhs, g->dKinv, g->dalpha, g->dpart, g->dz, g->dlogdet, g->dout,
-                         g->hout, s);
-    } else {
-        launch_trace(g->dX, g->n, g->d, g->npad, h, g->dKinv, g->dalpha, g->dpart, s, nullptr, {}, g->dz, g->dlogdet, g->dout,
-                     g->hout, g->dtickets + 2 * g->nt, g->kernel);
-    }
+    CovFn cf;
+    if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+    launch_trace(g->dX, g->n, g->d, g->npad, cf, g->dKinv, g->dalpha, g->dpart, s, {}, g->dz, g->dlogdet, g->dout, g->hout,
+                 g->dtickets + 2 * g->nt);
     HIPCHK(hipGetLastError());
     g->pending = true;
     g->pending_grad = true;
@@ -993,8 +995,7 @@ void discard_eval(cugp_gp* g)
 {
     g->factor_valid = g->inverse_valid = false;
     g->last_ll = g->last_quad = g->last_logdet = NAN;
-    g->last_g[0] = g->last_g[1] = g->last_g[2] = NAN;
-    for (double& v : g->last_ga) v = NAN;
+    for (double& v : g->last_g) v = NAN;
 }
 
 // The results of g's evaluation from its 8-double host row (host_out) -- or, when a bounded wait inside a kernel ran out
@@ -1010,10 +1011,8 @@ bool read_result_row(cugp_gp* g, double* row, bool grad)
     g->last_logdet = row[5];
     g->factor_valid = true;
     if (grad) {
-        if (g->ard)
-            for (size_t i = 0; i < g->last_ga.size(); i++) g->last_ga[i] = row[ARD_ROW_GRAD + i];
-        else
-            for (int i = 0; i < 3; i++) g->last_g[i] = row[1 + i];
+        const double* gr = row + (g->ard ? ARD_ROW_GRAD : 1);
+        for (int i = 0; i < g->nh; i++) g->last_g[i] = gr[i];
         g->inverse_valid = true;
     }
     return true;
@@ -1092,8 +1091,8 @@ static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_
     g->n = n; g->d = d; g->device = device;
     g->ard = ard;
     g->kernel = kernel;
-    if (ard) { g->hpa.assign((size_t)d + 2, 0.0); g->last_ga.assign((size_t)d + 2, NAN); }
-    const size_t nrow = ard ? (size_t)ARD_ROW_GRAD + d + 2 : 8, ncol = ard ? (size_t)d + 2 : 3;
+    if (ard) { g->nh = d + 2; g->theta.assign(g->nh, 0.0); g->last_g.assign(g->nh, NAN); }
+    const size_t nrow = ard ? (size_t)ARD_ROW_GRAD + g->nh : 8, ncol = g->nh;
     g->nt = ((n > npad_min ? n : npad_min) + TILE - 1) / TILE;
     g->npad = g->nt * TILE;
     g->nblocks_trace = trace_num_blocks(g->npad);
@@ -1229,23 +1228,48 @@ int cugp_set_data_device(cugp_gp* g, const double* dX, const double* dy)
     return set_data_common(g, dX, dy, hipMemcpyDeviceToDevice);
 }
 
+// ---- hyper-parameters and results: the 3-entry calls and their _ard twins are argument checks (refuse_ard / want_ard)
+// in front of one body over the handle's nh entries ----
+// A set that changes nothing (and holds no NaN) keeps the factor.  ARD: the staging area may still be read by a copy
+// enqueued for a prediction, so the stream runs dry before it is written again.
+static int set_theta(cugp_gp* g, const double* th)
+{
+    int rc;
+    if ((rc = fetch_eval(g))) return rc;
+    bool changed = false;
+    for (int i = 0; i < g->nh; i++) changed = changed || th[i] != g->theta[i] || std::isnan(th[i]);
+    if (!changed) return CUGP_OK;
+    if (g->ard) {
+        if ((rc = use_device(g))) return rc;
+        HIPCHK(hipStreamSynchronize(g->stream));
+    }
+    g->factor_valid = g->inverse_valid = false;
+    g->theta.assign(th, th + g->nh);
+    if (g->ard) stage_ard(g);
+    return CUGP_OK;
+}
+
+static void get_theta(const cugp_gp* g, double* th) { std::copy(g->theta.begin(), g->theta.end(), th); }
+
+// the last evaluation's results (either pointer may be null)
+static void copy_grad(const cugp_gp* g, double* ll, double* gr)
+{
+    if (ll) *ll = g->last_ll;
+    if (gr) std::copy(g->last_g.begin(), g->last_g.end(), gr);
+}
+
 int cugp_set_loghyper(cugp_gp* g, const double hp[3])
 {
     if (!g || !hp) return CUGP_ERR_INVALID;
-    int rc;
-    if ((rc = refuse_ard(g, "cugp_set_loghyper", "cugp_set_loghyper_ard"))) return rc;
-    if ((rc = fetch_eval(g))) return rc;
-    if (hp[0] != g->hp[0] || hp[1] != g->hp[1] || hp[2] != g->hp[2] || std::isnan(hp[0] + hp[1] + hp[2]))
-        g->factor_valid = g->inverse_valid = false;
-    for (int i = 0; i < 3; i++) g->hp[i] = hp[i];
-    return CUGP_OK;
+    if (const int rc = refuse_ard(g, "cugp_set_loghyper", "cugp_set_loghyper_ard")) return rc;
+    return set_theta(g, hp);
 }
 
 int cugp_get_loghyper(const cugp_gp* g, double hp[3])
 {
     if (!g || !hp) return CUGP_ERR_INVALID;
     if (const int rc = refuse_ard(g, "cugp_get_loghyper", "cugp_get_loghyper_ard")) return rc;
-    for (int i = 0; i < 3; i++) hp[i] = g->hp[i];
+    get_theta(g, hp);
     return CUGP_OK;
 }
 
@@ -1272,32 +1296,20 @@ static int want_ard(const cugp_gp* g, int nh, const char* call, bool pointers_ok
 int cugp_num_hyper(const cugp_gp* g, int* nh)
 {
     if (!g || !nh) return fail(CUGP_ERR_INVALID, "cugp_num_hyper: null argument");
-    *nh = g->ard ? g->d + 2 : 3;
+    *nh = g->nh;
     return CUGP_OK;
 }
 
 int cugp_set_loghyper_ard(cugp_gp* g, const double* hp, int nh)
 {
-    int rc;
-    if ((rc = want_ard(g, nh, "cugp_set_loghyper_ard", hp != nullptr))) return rc;
-    if ((rc = fetch_eval(g))) return rc;
-    bool changed = false;
-    for (int i = 0; i < nh; i++) changed = changed || hp[i] != g->hpa[i] || std::isnan(hp[i]);
-    if (!changed) return CUGP_OK;
-    // the staging area may still be read by a copy enqueued for a prediction: let the stream run dry before it changes
-    if ((rc = use_device(g))) return rc;
-    HIPCHK(hipStreamSynchronize(g->stream));
-    g->factor_valid = g->inverse_valid = false;
-    for (int i = 0; i < nh; i++) g->hpa[i] = hp[i];
-    g->hp[0] = 0.0; g->hp[1] = hp[g->d]; g->hp[2] = hp[g->d + 1];
-    stage_ard(g);
-    return CUGP_OK;
+    if (const int rc = want_ard(g, nh, "cugp_set_loghyper_ard", hp != nullptr)) return rc;
+    return set_theta(g, hp);
 }
 
 int cugp_get_loghyper_ard(const cugp_gp* g, double* hp, int nh)
 {
     if (const int rc = want_ard(g, nh, "cugp_get_loghyper_ard", hp != nullptr)) return rc;
-    for (int i = 0; i < nh; i++) hp[i] = g->hpa[i];
+    get_theta(g, hp);
     return CUGP_OK;
 }
 
@@ -1315,9 +1327,7 @@ int cugp_loglik_grad_fetch(cugp_gp* g, double* ll, double gr[3])
     int rc;
     if (gr && (rc = refuse_ard(g, "cugp_loglik_grad_fetch", "cugp_loglik_grad_fetch_ard"))) return rc;
     if ((rc = fetch_eval(g))) return rc;
-    if (ll) *ll = g->last_ll;
-    if (gr)
-        for (int i = 0; i < 3; i++) gr[i] = g->last_g[i];
+    copy_grad(g, ll, gr);
     return CUGP_OK;
 }
 
@@ -1345,9 +1355,7 @@ int cugp_loglik_grad(cugp_gp* g, double* ll, double gr[3])
         if ((rc = (g->factor_valid && g->prof == 0) ? enqueue_continue(g) : enqueue_eval(g, true))) return rc;
         if ((rc = fetch_eval(g))) return rc;
     }
-    if (ll) *ll = g->last_ll;
-    if (gr)
-        for (int i = 0; i < 3; i++) gr[i] = g->last_g[i];
+    copy_grad(g, ll, gr);
     return CUGP_OK;
 }
 
@@ -1363,9 +1371,7 @@ int cugp_loglik_grad_fetch_ard(cugp_gp* g, double* ll, double* gr, int nh)
     int rc;
     if ((rc = want_ard(g, nh, "cugp_loglik_grad_fetch_ard"))) return rc;
     if ((rc = fetch_eval(g))) return rc;
-    if (ll) *ll = g->last_ll;
-    if (gr)
-        for (int i = 0; i < nh; i++) gr[i] = g->last_ga[i];
+    copy_grad(g, ll, gr);
     return CUGP_OK;
 }
 
@@ -1374,8 +1380,7 @@ int cugp_loglik_grad_ard(cugp_gp* g, double* ll, double* gr, int nh)
     int rc;
     if ((rc = want_ard(g, nh, "cugp_loglik_grad_ard", ll && gr))) return rc;
     if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // (the evaluation itself is shared)
-    *ll = g->last_ll;
-    for (int i = 0; i < nh; i++) gr[i] = g->last_ga[i];
+    copy_grad(g, ll, gr);
     return CUGP_OK;
 }
 
@@ -1411,7 +1416,6 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
 {
     int rc;
     const int cmax = chunk < nt ? chunk : nt, ntpad = ((cmax + TILE - 1) / TILE) * TILE;
-    const HyperScalars h = scalars(g);
     const size_t nxt = (((size_t)nt * g->d + 15) / 16) * 16, nks = (size_t)bt.count * ntpad * g->npad;
     if ((rc = scr.grow(nxt + 2 * nks + (rows ? 0 : 2 * (size_t)ntpad), g->stream))) return rc;
     double* dXt = scr.p;
@@ -1425,12 +1429,9 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
         const int c = nt - t0 < chunk ? nt - t0 : chunk;
         const int cpad = ((c + TILE - 1) / TILE) * TILE;
         // (batched: X, n, T, alpha come from the table; k_predict_finish reads rstride and its cpad only then)
-        if (g->ard) {
-            if ((rc = upload_hs(g, g->stream))) return rc;
-            launch_kcross_ard(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, g->dhs, dKs, g->stream);
-        } else {
-            launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, h, dKs, g->stream, bt, g->kernel);
-        }
+        CovFn cf;
+        if ((rc = cov_fn(g, g->stream, nullptr, &cf))) return rc;
+        launch_kcross(g->dX, g->n, g->d, g->npad, dXt + (size_t)t0 * g->d, c, cpad, cf, dKs, g->stream, bt);
         {
             // W = Ks L^-T: test tile tt, row tile ti sums k <= ti (the diagonal k tile of T is triangular: counted half)
             TimedLaunch tl(g, g->stream, !bt.tab && g->prof >= 3);
@@ -1439,7 +1440,7 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
             for (int ti = 0; ti < g->nt; ti++) kt += ti + 0.5;
             tl.done(KIND_PREDICT, kt * (cpad / TILE) * 2.0 * TILE * TILE * TILE);
         }
-        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, h, dm, dv, g->stream, rows ? rows + t0 : nullptr,
+        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, cf.h, dm, dv, g->stream, rows ? rows + t0 : nullptr,
                               rstride, nt, cpad, bt);
     }
     HIPCHK(hipGetLastError());
@@ -1570,14 +1571,10 @@ static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_no
         launch_predict_cov(pb.w, g->npad, ntpad, cs, f->dA, g->cov_scr.p, g->stream);
         tl.done(KIND_COV, 2.0 * cs.tiles * (32.0 * cs.wm) * (32.0 * cs.wm) * cs.kend);
     }
-    if (g->ard) {
-        if ((rc = upload_hs(g, g->stream))) return rc;
-        launch_predict_cov_finish_ard(pb.xt, nt, g->d, ntpad, g->dhs, with_noise, jitter, f->dA, g->cov_scr.p,
-                                      cs.split - 1, f->dtickets, g->stream);
-    } else {
-        launch_predict_cov_finish(pb.xt, nt, g->d, ntpad, scalars(g), with_noise, jitter, f->dA, g->cov_scr.p,
-                                  cs.split - 1, f->dtickets, g->stream, g->kernel);
-    }
+    CovFn cf;
+    if ((rc = cov_fn(g, g->stream, nullptr, &cf))) return rc;
+    launch_predict_cov_finish(pb.xt, nt, g->d, ntpad, cf, with_noise, jitter, f->dA, g->cov_scr.p, cs.split - 1,
+                              f->dtickets, g->stream);
     HIPCHK(hipGetLastError());
     *dmean = pb.mean;
     *fout = f;
@@ -1672,12 +1669,9 @@ int cugp_compute_K_train(cugp_gp* g, double* K)
     if ((rc = ensure(&g->dA, (size_t)g->npad * g->npad))) return rc;
     g->factor_valid = g->inverse_valid = false;
     TuneScope ts(g);
-    if (g->ard) {
-        if ((rc = upload_hs(g, g->stream))) return rc;
-        launch_kbuild_ard(g->dX, g->n, g->d, g->npad, g->dhs, g->dA, true, g->stream);
-    } else {
-        launch_kbuild(g->dX, g->n, g->d, g->npad, scalars(g), g->dA, true, g->stream, nullptr, {}, nullptr, g->kernel);
-    }
+    CovFn cf;
+    if ((rc = cov_fn(g, g->stream, nullptr, &cf))) return rc;
+    launch_kbuild(g->dX, g->n, g->d, g->npad, cf, g->dA, true, g->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy2DAsync(K, (size_t)g->n * sizeof(double), g->dA, (size_t)g->npad * sizeof(double),
                             (size_t)g->n * sizeof(double), g->n, hipMemcpyDeviceToHost, g->stream));
@@ -1717,18 +1711,18 @@ int cugp_compute_k_test(cugp_gp* g, const double* Xt, int nt, double* Ks)
     if (e == hipSuccess) e = hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) {
         TuneScope ts(g);
-        if (g->ard) {
-            e = hipMemcpyAsync(g->dhs, g->hhs, hs_bytes(g), hipMemcpyHostToDevice, g->stream);
-            launch_kcross_ard(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, g->dhs, dKs, g->stream);
-        } else {
-            launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, scalars(g), dKs, g->stream, {}, g->kernel);
+        CovFn cf;
+        // (e: HIP errors of this function, reported below; rc: an error cov_fn has already reported -- both pass the frees)
+        if ((rc = cov_fn(g, g->stream, nullptr, &cf)) == CUGP_OK) {
+            launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, cf, dKs, g->stream);
+            e = hipMemcpy2DAsync(Ks, (size_t)g->n * sizeof(double), dKs, (size_t)g->npad * sizeof(double),
+                                 (size_t)g->n * sizeof(double), nt, hipMemcpyDeviceToHost, g->stream);
         }
-        e = hipMemcpy2DAsync(Ks, (size_t)g->n * sizeof(double), dKs, (size_t)g->npad * sizeof(double),
-                             (size_t)g->n * sizeof(double), nt, hipMemcpyDeviceToHost, g->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
     (void)hipFree(dXt);
     if (dKs) (void)hipFree(dKs);
+    if (rc) return rc;
     if (e != hipSuccess) return fail(CUGP_ERR_DEVICE, "cugp_compute_k_test", e);
     return CUGP_OK;
 }
@@ -1948,13 +1942,23 @@ void* cugp_get_stream(cugp_gp* g) { return g ? (void*)g->stream : nullptr; }
 
 // ---------------------------------------------------------------- optimiser glue
 namespace {
-void gp_objective(void* ctx, const double th[3], double* f, double gr[3])
+// f = -LL and its gradient at th, over the handle's nh entries (NaN where the evaluation fails)
+void gp_objective(void* ctx, const double* th, int nh, double* f, double* gr)
 {
     cugp_gp* g = (cugp_gp*)ctx;
     double ll = NAN;
-    cugp_set_loghyper(g, th);
-    if (cugp_loglik_grad(g, &ll, gr) != CUGP_OK) { ll = NAN; gr[0] = gr[1] = gr[2] = NAN; }
+    if (set_theta(g, th) == CUGP_OK && cugp_loglik_grad(g, nullptr, nullptr) == CUGP_OK) copy_grad(g, &ll, gr);
+    else std::fill(gr, gr + nh, NAN);
     *f = -1.0 * ll;
+}
+void gp_objective3(void* ctx, const double th[3], double* f, double gr[3]) { gp_objective(ctx, th, 3, f, gr); }
+
+// conjugate gradients from the current hyper-parameters; the end point stays set (covkernel.cpp:646)
+int cg_solve(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
+{
+    std::vector<double> th(g->theta);
+    if (const int rc = cugp_cg_minimize_n(gp_objective, g, th.data(), g->nh, budget, trace, trace_cap, nevals)) return rc;
+    return set_theta(g, th.data());
 }
 }  // namespace
 
@@ -1962,10 +1966,7 @@ int cugp_cg_solve(cugp_gp* g, int budget, double* trace, int trace_cap, int* nev
 {
     if (!g) return CUGP_ERR_INVALID;
     if (const int rc = refuse_ard(g, "cugp_cg_solve", "cugp_cg_solve_ard")) return rc;
-    double th[3] = {g->hp[0], g->hp[1], g->hp[2]};
-    int rc = cugp_cg_minimize(gp_objective, g, th, budget, trace, trace_cap, nevals);
-    if (rc) return rc;
-    return cugp_set_loghyper(g, th);       // covkernel.cpp:646
+    return cg_solve(g, budget, trace, trace_cap, nevals);
 }
 
 namespace {
@@ -1985,35 +1986,18 @@ void gp_gradient(void* ctx, const double th[3], double gr[3])
 }
 }  // namespace
 
-namespace {
-void gp_objective_ard(void* ctx, const double* th, int nh, double* f, double* gr)
-{
-    cugp_gp* g = (cugp_gp*)ctx;
-    double ll = NAN;
-    if (cugp_set_loghyper_ard(g, th, nh) != CUGP_OK || cugp_loglik_grad_ard(g, &ll, gr, nh) != CUGP_OK) {
-        ll = NAN;
-        for (int i = 0; i < nh; i++) gr[i] = NAN;
-    }
-    *f = -1.0 * ll;
-}
-}  // namespace
-
 int cugp_cg_solve_ard(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
 {
     if (!g) return fail(CUGP_ERR_INVALID, "cugp_cg_solve_ard: null handle");
-    int rc;
-    if ((rc = want_ard(g, g->d + 2, "cugp_cg_solve_ard"))) return rc;
-    std::vector<double> th(g->hpa);
-    const int nh = (int)th.size();
-    if ((rc = cugp_cg_minimize_n(gp_objective_ard, g, th.data(), nh, budget, trace, trace_cap, nevals))) return rc;
-    return cugp_set_loghyper_ard(g, th.data(), nh);
+    if (const int rc = want_ard(g, g->d + 2, "cugp_cg_solve_ard")) return rc;
+    return cg_solve(g, budget, trace, trace_cap, nevals);
 }
 
 int cugp_cg_solve_sparing(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals, int* ngrads)
 {
     if (!g) return CUGP_ERR_INVALID;
     if (const int rc = refuse_ard(g, "cugp_cg_solve_sparing", "cugp_cg_solve_ard")) return rc;
-    double th[3] = {g->hp[0], g->hp[1], g->hp[2]};
+    double th[3] = {g->theta[0], g->theta[1], g->theta[2]};
     int rc = cugp_cg_minimize_sparing(gp_value, gp_gradient, g, th, budget, trace, trace_cap, nevals, ngrads);
     if (rc) return rc;
     return cugp_set_loghyper(g, th);
@@ -2023,8 +2007,8 @@ int cugp_rprop_solve(cugp_gp* g, int iters, double* trace, int trace_cap, int* n
 {
     if (!g) return CUGP_ERR_INVALID;
     if (const int rc = refuse_ard(g, "cugp_rprop_solve", "cugp_cg_solve_ard")) return rc;
-    double th[3] = {g->hp[0], g->hp[1], g->hp[2]};
-    int rc = cugp_rprop_minimize(gp_objective, g, th, iters, trace, trace_cap, nevals);
+    double th[3] = {g->theta[0], g->theta[1], g->theta[2]};
+    int rc = cugp_rprop_minimize(gp_objective3, g, th, iters, trace, trace_cap, nevals);
     if (rc) return rc;
     return cugp_set_loghyper(g, th);
 }
@@ -2132,7 +2116,7 @@ int cugp_bench_la_check(int op, int n, int device, int reps, double* ms, double*
     double best = 1e300;
     TuneScope ts(g);
     for (int r = 0; r < reps + 1 && e == hipSuccess && rc == CUGP_OK; r++) {
-        launch_kbuild(g->dX, g->n, g->d, g->npad, scalars(g), g->dA, op == 4, g->stream);
+        launch_kbuild(g->dX, g->n, g->d, g->npad, CovFn{KERNEL_SE, false, scalars(g), nullptr}, g->dA, op == 4, g->stream);
         if (op == 1 || op == 2) rc = enqueue_potrf(g, false);
         if (op == 2 && !rc) rc = enqueue_trtri(g);
         if (rc) break;
@@ -2277,7 +2261,7 @@ static bool same_loghyper(const cugp_group* gr)
 {
     const cugp_gp* lead = gr->experts[0];
     for (const cugp_gp* e : gr->experts)
-        if (e->hp[0] != lead->hp[0] || e->hp[1] != lead->hp[1] || e->hp[2] != lead->hp[2]) return false;
+        if (e->theta != lead->theta) return false;
     return true;
 }
 

@@ -41,13 +41,7 @@ extern const int g_tune_init[TUNE_COUNT];     // built-in defaults
 extern thread_local const int* t_tune;        // the tuning the launchers on this thread read (a handle's copy, or the built-in defaults)
 inline int tune(int key) { return t_tune[key]; }
 
-struct HyperScalars;
-
-// covariance family of a handle (cugp.h: CUGP_KERNEL_*), fixed when it is created.  The four passes that evaluate the
-// kernel function (build, cross-covariance, joint-covariance epilogue, gradient trace) take it as their last argument
-// and launch the instantiation for it -- k_build / k_cross / k_predict_cov_finish / k_trace for SE, the same bodies as
-// k_*_matern<KIND> otherwise, with everything SE's launches carry (batched experts, ticket zeroing, device-resident
-// hyper-scalars, stamps, the fused final sums).  ARD handles are SE only.
+// covariance family of a handle (cugp.h: CUGP_KERNEL_*), fixed when it is created
 enum { KERNEL_SE = 0, KERNEL_MATERN32 = 1, KERNEL_MATERN52 = 2, KERNEL_COUNT = 3 };
 
 // Batched launches: the experts of a BCM on one device have the same shapes, so one launch can serve all of
@@ -69,12 +63,31 @@ struct HyperScalars {              // exp(2*theta) evaluated on the host, as the
     double ell_sq, signal_var, noise_var;
 };
 
-// ---- SE covariance (N1) ----
+// The covariance function of a handle as the launchers see it.  The four passes that evaluate it (build, cross-covariance,
+// joint-covariance epilogue, gradient trace) take one of these and launch the instantiation it names: k_build / k_cross /
+// k_predict_cov_finish / k_trace for SE, the same bodies as k_*_matern<KIND> for the Matern kinds -- with everything SE's
+// launches carry (batched experts, ticket zeroing, device-resident hyper-scalars, stamps, the fused final sums) -- and
+// k_*_ard for ARD.
+//   h:   the hyper-scalars by value
+//   hd:  (optional) the same in device memory, read INSTEAD of h by the passes a captured graph replays (build, trace,
+//        k_finalize): the graph sees new hyper-parameters by one copy into that buffer
+//   ard: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart):
+//        k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd is
+//        then mandatory and read by every pass: the hyper-scalars (ell_sq unused) directly followed by the d weights --
+//        one staging area, one copy.  Same tiles, stores and padding as the isotropic launches; SE only, and single
+//        handles only: an ARD descriptor with batched experts or without hd is a programming error -- asserted, so
+//        checked only in builds without NDEBUG (the library's own build has none); cugp_group_create refuses ARD handles.
+struct CovFn {
+    int kind = KERNEL_SE;
+    bool ard = false;
+    HyperScalars h = {};
+    const HyperScalars* hd = nullptr;
+};
+
+// ---- covariance (N1) ----
 // lower 64x64 tiles of K (+ mirror when `full`), padding rows/cols >= n set to identity
-// hd (optional, also below): read the hyper-scalars from device memory instead of the argument
-void launch_kbuild(const double* X, int n, int d, int npad, HyperScalars h, double* K, bool full,
-                   hipStream_t s, const HyperScalars* hd = nullptr, Batch bt = {}, unsigned* tickets = nullptr,
-                   int kind = KERNEL_SE);
+void launch_kbuild(const double* X, int n, int d, int npad, const CovFn& cf, double* K, bool full, hipStream_t s,
+                   Batch bt = {}, unsigned* tickets = nullptr);
                    // tickets: the factorisation's arrival counters -- 2 * npad/128 per expert ([0, nt) the step tickets of
                    // k_syrk_step, [nt, 2 nt) the stage counters of k_trtri_block) --, zeroed by the launch when given
 // S[i][j] = |x_i - x_j|^2 / c, zero diagonal, full symmetric (N2, covkernel.cpp:130-157)
@@ -82,27 +95,7 @@ void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S,
 // Ks[t][i] = sf2 * exp(-0.5*|x_i - xt_t|^2 / l^2), row-major nt_pad x npad (pad = 0)   (N12)
 // bt (batched): blockIdx.y = expert, X and n from the table, Ks[expert][ntpad][npad]
 void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
-                   HyperScalars h, double* Ks, hipStream_t s, Batch bt = {}, int kind = KERNEL_SE);
-
-// ---- ARD: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart) ----
-// k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd: DEVICE
-// memory, the hyper-scalars (ell_sq unused) directly followed by the d weights -- one staging area, one copy, so a
-// replayed graph sees new length scales the way it sees new exp(2 theta).  Same tiles, stores and padding as the
-// isotropic launches above; single handles only (no batched experts).
-void launch_kbuild_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, double* K, bool full,
-                       hipStream_t s, unsigned* tickets = nullptr);
-void launch_kcross_ard(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
-                       const HyperScalars* hd, double* Ks, hipStream_t s);
-void launch_predict_cov_finish_ard(const double* Xt, int nt, int d, int ntpad, const HyperScalars* hd, bool with_noise,
-                                   double jitter, double* A, const double* scr, int nscr, unsigned* tickets,
-                                   hipStream_t s);
-// gradient traces and the final sums: part[(d + 2) * trace_num_blocks(npad)]; results row out / hout (8 + d + 2 doubles):
-// [0] LL, [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row), [8 + c] g_c, c = 0 .. d + 1.
-// Two launches (k_trace_ard, k_finalize_ard): there is no fused form of the final sums.
-constexpr int ARD_ROW_GRAD = 8;
-void launch_trace_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, const double* Kinv,
-                      const double* alpha, double* part, const double* z, const double* logdet_part, double* out,
-                      double* hout, hipStream_t s);
+                   const CovFn& cf, double* Ks, hipStream_t s, Batch bt = {});
 
 // ---- blocked right-looking Cholesky (N4) on the lower triangle of A (npad x npad, ld = npad) ----
 // d16: 16x16 diagonal inverses [nt][8][256]; d64: the two 64x64 diagonal inverses of each block [nt][2][4096]
@@ -165,9 +158,8 @@ CovShape predict_cov_shape(int ntpad, int n);
 void launch_predict_cov(const double* W, int ld, int ntpad, const CovShape& c, double* A, double* scr, hipStream_t s);
 // A (lower 64x64 tiles, in place) = k(Xt,Xt) (+ sn2 on the diagonal when with_noise) + jitter I - (A + scr[0] + ...
 // + scr[nscr - 1]), identity beyond nt; tickets (when given): the factorisation's arrival counters, zeroed
-void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, HyperScalars h, bool with_noise, double jitter,
-                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s,
-                               int kind = KERNEL_SE);
+void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, const CovFn& cf, bool with_noise,
+                               double jitter, double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s);
 // strict upper triangle of the nt diagonal 128x128 tiles of A := 0
 void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s);
 // out[s * nt + t] = mean[t] + F[s * ld + t]   (s < ns, t < nt)
@@ -194,10 +186,14 @@ int trace_num_blocks(int npad);
 // out (when given): the launch also FINISHES the evaluation -- its last block (an arrival ticket, zero before the launch)
 // takes the final sums and writes out[0..5] (and hout) as launch_finalize would: z, logdet_part as there; batched:
 // taken from the experts' table, ticket = tickets[2 nt] of every expert
-void launch_trace(const double* X, int n, int d, int npad, HyperScalars h, const double* Kinv,
-                  const double* alpha, double* part, hipStream_t s, const HyperScalars* hd = nullptr,
-                  Batch bt = {}, const double* z = nullptr, const double* logdet_part = nullptr, double* out = nullptr,
-                  double* hout = nullptr, unsigned* ticket = nullptr, int kind = KERNEL_SE);
+// ARD: part[(d + 2) * trace_num_blocks(npad)]; results row out / hout (both mandatory, ARD_ROW_GRAD + d + 2 doubles): [0] LL,
+// [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row), [ARD_ROW_GRAD + c] g_c, c = 0 .. d + 1.  Always two
+// launches (k_trace_ard, k_finalize_ard): there is no fused form of the final sums, and ticket is not used.
+constexpr int ARD_ROW_GRAD = 8;
+void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* alpha,
+                  double* part, hipStream_t s, Batch bt = {}, const double* z = nullptr,
+                  const double* logdet_part = nullptr, double* out = nullptr, double* hout = nullptr,
+                  unsigned* ticket = nullptr);
 // arrival counters per expert: [0, nt) step tickets, [nt, 2 nt) stage counters of k_trtri_block, [2 nt] k_trace's fused finalize
 constexpr int ticket_count(int nt) { return 2 * nt + 1; }
 // out[0..3] = LL, g0, g1, g2  (LL only when part == nullptr)

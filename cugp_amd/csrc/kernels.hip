@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <cassert>
 #include <cstdlib>
 
 namespace cugp {
@@ -986,11 +987,15 @@ __device__ __forceinline__ void matern_entry(double s, double sf2, double& kf, d
     kf = dead ? 0.0 : sf2 * (p * e);
     dk = dead ? 0.0 : sf2 * (q * e);
 }
-// the SE / Matern value of one entry without the noise term (the three passes that need no derivative)
-template <int KIND>
+// the value of one entry without the noise term (the three passes that need no derivative).  ARD (SE only): d2 is the
+// WEIGHTED squared distance, so there is no division and dl is not read
+template <bool ARD, int KIND>
 __device__ __forceinline__ double kernel_value(double d2, const DivBy& dl, double sf2)
 {
-    if constexpr (KIND == KERNEL_SE) {
+    if constexpr (ARD) {
+        static_assert(KIND == KERNEL_SE, "ARD handles are SE");
+        return sf2 * exp(-0.5 * d2);
+    } else if constexpr (KIND == KERNEL_SE) {
         return sf2 * exp(div_by(-d2 * 0.5, dl));                  // covkernel.cpp:89
     } else {
         double kf, dk;
@@ -1028,8 +1033,7 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
     const int i0 = ti * KT, j0 = tj * KT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double d2v[4][4];
-    if (ARD) sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, d2v, ard_weights(hd), ws);
-    else sqdist_4x4(X, X, n, n, d, i0, j0, xs, ys, d2v);
+    sqdist_4x4<ARD>(X, X, n, n, d, i0, j0, xs, ys, d2v, ARD ? ard_weights(hd) : nullptr, ws);
     double out[4][4];
     const DivBy dl = div_prepare(h.ell_sq);
 #pragma unroll
@@ -1039,13 +1043,10 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
             const int i = i0 + ty * 4 + a, j = j0 + col4(tx, b);
             const bool in = i < n && j < n;
             double v;
-            if (ARD) {
-                v = h.signal_var * exp(-0.5 * d2v[a][b]);
-                if (i == j) v += h.noise_var;
-            } else if (full == 2) {
+            if (!ARD && full == 2) {
                 v = (i == j) ? 0.0 : div_by(d2v[a][b], dl);    // covkernel.cpp:143-151 (squared distance / c)
             } else {
-                v = kernel_value<KIND>(d2v[a][b], dl, h.signal_var);   // covkernel.cpp:89
+                v = kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var);   // covkernel.cpp:89
                 if (i == j) v += h.noise_var;                            // covkernel.cpp:93-94
             }
             out[a][b] = in ? v : ((i == j) ? 1.0 : 0.0);                // identity padding
@@ -1112,8 +1113,7 @@ __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, 
     double d2v[4][4];
     // the reference subtracts X[i] - xtest (covkernel.cpp:112); squares are sign-independent but keep the order
     __shared__ double ws[DC];
-    if (ARD) sqdist_4x4<true>(Xt, X, nt, n, d, t0, i0, xs, ys, d2v, wts, ws);
-    else sqdist_4x4(Xt, X, nt, n, d, t0, i0, xs, ys, d2v);
+    sqdist_4x4<ARD>(Xt, X, nt, n, d, t0, i0, xs, ys, d2v, wts, ws);
     const DivBy dl = div_prepare(h.ell_sq);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
@@ -1122,9 +1122,7 @@ __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, 
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int i = i0 + col4(tx, b);
-            o[b] = (tr < nt && i < n)
-                       ? (ARD ? h.signal_var * exp(-0.5 * d2v[a][b]) : kernel_value<KIND>(d2v[a][b], dl, h.signal_var))
-                       : 0.0;
+            o[b] = (tr < nt && i < n) ? kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var) : 0.0;
         }
         double* p = Ks + (size_t)tr * npad + i0 + tx * 2;
         *(d2*)p = (d2){o[0], o[1]};
@@ -1201,8 +1199,7 @@ __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     double d2v[4][4];
     __shared__ double ws[DC];
-    if (ARD) sqdist_4x4<true>(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v, wts, ws);
-    else sqdist_4x4(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v);
+    sqdist_4x4<ARD>(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v, wts, ws);
     const DivBy dl = div_prepare(h.ell_sq);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
@@ -1219,7 +1216,7 @@ __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int j = j0 + col4(tx, b);
-            double v = ARD ? h.signal_var * exp(-0.5 * d2v[a][b]) : kernel_value<KIND>(d2v[a][b], dl, h.signal_var);
+            double v = kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var);
             if (i == j) {
                 if (with_noise) v += h.noise_var;
                 v += jitter;
@@ -2839,13 +2836,27 @@ thread_local const int* t_tune = g_tune_init;
 
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
 
-void launch_kbuild(const double* X, int n, int d, int npad, HyperScalars h, double* K, bool full, hipStream_t s,
-                   const HyperScalars* hd, Batch bt, unsigned* tickets, int kind)
+// The four passes that evaluate the covariance function launch the instantiation its descriptor names: k_<pass>_ard (its
+// own argument list: everything from cf.hd, no batched experts), else k_<pass> or k_<pass>_matern<KIND>, which share one.
+// The table of isotropic instantiations is this macro and nothing else.
+#define CUGP_ISO_KERNEL(cf, stem)                                                        \
+    ((cf).kind == KERNEL_MATERN32   ? stem##_matern<KERNEL_MATERN32>                     \
+     : (cf).kind == KERNEL_MATERN52 ? stem##_matern<KERNEL_MATERN52> : stem)
+static inline bool ard_single(const CovFn& cf, const Batch& bt)
+{
+    assert(!cf.ard || (cf.hd && !bt.tab && cf.kind == KERNEL_SE));   // (cugp_group_create refuses ARD handles)
+    return cf.ard;
+}
+
+void launch_kbuild(const double* X, int n, int d, int npad, const CovFn& cf, double* K, bool full, hipStream_t s,
+                   Batch bt, unsigned* tickets)
 {
     const dim3 grid(tri_count(npad / KT), bt.count);
-    auto* k = kind == KERNEL_MATERN32 ? k_build_matern<KERNEL_MATERN32>
-              : kind == KERNEL_MATERN52 ? k_build_matern<KERNEL_MATERN52> : k_build;
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, X, n, d, npad, h, hd, K, full ? 1 : 0, tickets, bt.tab, take_stamp());
+    if (ard_single(cf, bt))
+        hipLaunchKernelGGL(k_build_ard, grid, dim3(256), 0, s, X, n, d, npad, cf.hd, K, full ? 1 : 0, tickets, take_stamp());
+    else
+        hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, K, full ? 1 : 0,
+                           tickets, bt.tab, take_stamp());
 }
 
 void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S, hipStream_t s)
@@ -2856,27 +2867,15 @@ void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S,
                        (unsigned long long*)nullptr);
 }
 
-void launch_kbuild_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, double* K, bool full,
-                       hipStream_t s, unsigned* tickets)
+void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad, const CovFn& cf,
+                   double* Ks, hipStream_t s, Batch bt)
 {
-    hipLaunchKernelGGL(k_build_ard, dim3(tri_count(npad / KT)), dim3(256), 0, s, X, n, d, npad, hd, K, full ? 1 : 0,
-                       tickets, take_stamp());
-}
-
-void launch_kcross_ard(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad,
-                       const HyperScalars* hd, double* Ks, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_cross_ard, dim3((ntpad / KT) * (npad / KT)), dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, hd,
-                       Ks);
-}
-
-void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, int nt, int ntpad, HyperScalars h,
-                   double* Ks, hipStream_t s, Batch bt, int kind)
-{
-    auto* k = kind == KERNEL_MATERN32 ? k_cross_matern<KERNEL_MATERN32>
-              : kind == KERNEL_MATERN52 ? k_cross_matern<KERNEL_MATERN52> : k_cross;
-    hipLaunchKernelGGL(k, dim3((ntpad / KT) * (npad / KT), bt.count), dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, h,
-                       Ks, bt.tab);
+    const dim3 grid((ntpad / KT) * (npad / KT), bt.count);
+    if (ard_single(cf, bt))
+        hipLaunchKernelGGL(k_cross_ard, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.hd, Ks);
+    else
+        hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.h, Ks,
+                           bt.tab);
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
@@ -3119,21 +3118,16 @@ void launch_predict_cov(const double* W, int ld, int ntpad, const CovShape& c, d
                     c.split, A, scr, pstride, ntpad, take_stamp());
 }
 
-void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, HyperScalars h, bool with_noise, double jitter,
-                               double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s, int kind)
+void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, const CovFn& cf, bool with_noise,
+                               double jitter, double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s)
 {
-    auto* k = kind == KERNEL_MATERN32 ? k_predict_cov_finish_matern<KERNEL_MATERN32>
-              : kind == KERNEL_MATERN52 ? k_predict_cov_finish_matern<KERNEL_MATERN52> : k_predict_cov_finish;
-    hipLaunchKernelGGL(k, dim3(tri_count(ntpad / KT)), dim3(256), 0, s, Xt, nt, d, ntpad, h, with_noise ? 1 : 0, jitter,
-                       A, scr, (size_t)ntpad * ntpad, nscr, tickets);
-}
-
-void launch_predict_cov_finish_ard(const double* Xt, int nt, int d, int ntpad, const HyperScalars* hd, bool with_noise,
-                                   double jitter, double* A, const double* scr, int nscr, unsigned* tickets,
-                                   hipStream_t s)
-{
-    hipLaunchKernelGGL(k_predict_cov_finish_ard, dim3(tri_count(ntpad / KT)), dim3(256), 0, s, Xt, nt, d, ntpad, hd,
-                       with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+    const dim3 grid(tri_count(ntpad / KT));
+    if (ard_single(cf, {}))
+        hipLaunchKernelGGL(k_predict_cov_finish_ard, grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.hd, with_noise ? 1 : 0,
+                           jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+    else
+        hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_predict_cov_finish), grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.h,
+                           with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
 }
 
 void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s)
@@ -3191,30 +3185,26 @@ void launch_trsv_lower(const double* A, const double* T, int ld, int nt, const d
 
 int trace_num_blocks(int npad) { return tri_count(npad / KT); }
 
-void launch_trace(const double* X, int n, int d, int npad, HyperScalars h, const double* Kinv, const double* alpha,
-                  double* part, hipStream_t s, const HyperScalars* hd, Batch bt, const double* z, const double* logdet_part,
-                  double* out, double* hout, unsigned* ticket, int kind)
+void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* alpha,
+                  double* part, hipStream_t s, Batch bt, const double* z, const double* logdet_part, double* out,
+                  double* hout, unsigned* ticket)
 {
+    const int nblocks = tri_count(npad / KT);
+    if (ard_single(cf, bt)) {                  // always both launches: there is no fused form of the ARD final sums
+        assert(out && hout);
+        hipLaunchKernelGGL(k_trace_ard, dim3(nblocks), dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, alpha, part);
+        hipLaunchKernelGGL(k_finalize_ard, dim3(1), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part, npad / TILE, part,
+                           nblocks, cf.hd, out, hout);
+        return;
+    }
     // the last block takes the final sums where the launch is small (its 256 threads against k_finalize's 1024: at 8192
     // rows -- 8256 blocks -- the separate launch is as fast and keeps the blocks' stores plain); TUNE_FINALIZE_FUSE_MAX
-    const int nblocks = tri_count(npad / KT);
     const bool fuse = out != nullptr && nblocks <= tune(TUNE_FINALIZE_FUSE_MAX);
     const FinalizeArgs fin{z, logdet_part, npad / TILE, fuse ? out : nullptr, hout, ticket};
-    auto* k = kind == KERNEL_MATERN32 ? k_trace_matern<KERNEL_MATERN32>
-              : kind == KERNEL_MATERN52 ? k_trace_matern<KERNEL_MATERN52> : k_trace;
-    hipLaunchKernelGGL(k, dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, h, hd, Kinv, alpha, part, bt.tab, fin);
+    hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_trace), dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd,
+                       Kinv, alpha, part, bt.tab, fin);
     if (out != nullptr && !fuse)
-        launch_finalize(z, npad, n, logdet_part, npad / TILE, part, nblocks, h, out, hout, s, hd, bt);
-}
-
-void launch_trace_ard(const double* X, int n, int d, int npad, const HyperScalars* hd, const double* Kinv,
-                      const double* alpha, double* part, const double* z, const double* logdet_part, double* out,
-                      double* hout, hipStream_t s)
-{
-    const int nblocks = tri_count(npad / KT);
-    hipLaunchKernelGGL(k_trace_ard, dim3(nblocks), dim3(256), 0, s, X, n, d, npad, hd, Kinv, alpha, part);
-    hipLaunchKernelGGL(k_finalize_ard, dim3(1), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part, npad / TILE, part,
-                       nblocks, hd, out, hout);
+        launch_finalize(z, npad, n, logdet_part, npad / TILE, part, nblocks, cf.h, out, hout, s, cf.hd, bt);
 }
 
 void launch_finalize(const double* z, int npad, int n, const double* logdet_part, int nt, const double* part,

@@ -66,7 +66,7 @@ if la:
             res[vi][key].append(ms.value)
 apply({})
 for a, r, v in zip(names, res, vals):
-    print("%-22s eval wall %.3f (min %.3f) dev %.3f  potrf-phase %.3f | alone: potrf %s  all3 %s | ll %.10f g %s" % (
-        a, statistics.median(r["wall"]), min(r["wall"]), statistics.median(r["total"]), statistics.median(r["potrf"]),
+    print("%-22s eval wall %.4f (min %.4f max %.4f) dev %.3f  potrf-phase %.3f | alone: potrf %s  all3 %s | ll %.17g g %s" % (
+        a, statistics.median(r["wall"]), min(r["wall"]), max(r["wall"]), statistics.median(r["total"]), statistics.median(r["potrf"]),
         "%.3f" % r["la0"][0] if r["la0"] else "-", "%.3f" % r["la3"][0] if r["la3"] else "-",
         v[0], np.array2string(v[1], precision=10)), flush=True)

@@ -1,7 +1,11 @@
 """Registers, LDS and scratch of every kernel of libcugp.so, from the code-object notes hipcc writes for gfx950
 (no GPU needed):  python tools/kernel_resources.py > profiles/r03_kernel_resources.txt
 Workgroups per CU = min over the limits: 512 unified VGPRs per SIMD lane (VGPR + AGPR, allocation granule 8),
-160 KiB LDS per CU (static + the dynamic size the launcher asks for), 32 waves per CU."""
+160 KiB LDS per CU (static + the dynamic size the launcher asks for), 32 waves per CU.
+--digest: instead of the table, one line per kernel with a sha256 of its instructions (label to .Lfunc_end, without
+comments, .loc / .file lines and blank lines, block labels .LBB<n>_ normalised) -- equal digests before and after a
+refactor of kernels.hip mean that no kernel's code changed:  python tools/kernel_resources.py --digest [kernels.hip]"""
+import hashlib
 import os
 import re
 import subprocess
@@ -20,8 +24,19 @@ DYN = {"k_lauum<4>": GEMM4, "k_lauum<2>": GEMM2, "k_trtri_level<4>": GEMM4, "k_t
 with tempfile.TemporaryDirectory() as td:
     out = os.path.join(td, "k.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-S",
-                           "--cuda-device-only", "-o", out, SRC], stderr=subprocess.DEVNULL)
+                           "--cuda-device-only", "-o", out, sys.argv[-1] if sys.argv[-1].endswith(".hip") else SRC],
+                          stderr=subprocess.DEVNULL)
     txt = open(out).read()
+if "--digest" in sys.argv:
+    names = sorted(re.findall(r"^    \.name:\s+(\S+)$", txt[txt.index("amdhsa.kernels:"):], re.M))
+    dems = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
+    for name, dem in zip(names, dems):
+        body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(name), txt, re.M | re.S).group(1)
+        lines = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r";.*", "", ln)).strip() for ln in body.split("\n")]
+        lines = [ln for ln in lines if ln and not ln.startswith((".loc", ".file"))]
+        print("%s  %5d  %s" % (hashlib.sha256("\n".join(lines).encode()).hexdigest()[:32], len(lines),
+                               re.sub(r"^void |cugp::|\(.*$", "", dem)))
+    sys.exit(0)
 blocks = re.split(r"\n  - \.agpr_count:", txt[txt.index("amdhsa.kernels:"):])
 print("%-22s %5s %5s %5s %8s %8s %8s %7s %6s" % ("kernel", "vgpr", "agpr", "sgpr", "lds_stat", "lds_dyn", "scratch", "threads", "wg/CU"))
 for b in blocks[1:]:
