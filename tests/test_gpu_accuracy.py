@@ -175,7 +175,7 @@ def test_fixture_bcm(gp_mod):
 (PANEL, NEAR, PANEL_MIN_NT, SUBPANEL) = (8, 9, 10, 17)             # kernels.h TUNE_*, as tests/test_gpu_launch_paths.py
 SCHED = {PANEL_MIN_NT: 1, PANEL: 4, NEAR: 12, SUBPANEL: 2}
 TILE = 128
-EXTRA_ULPS = 15        # gamma_(n + 15) where Higham has gamma_(n + 1): see test_factor_residual
+EXTRA_ULPS = truth.POTRF_EXTRA_ULPS        # gamma_(n + 15) where Higham has gamma_(n + 1): see test_factor_residual
 
 
 @pytest.mark.parametrize("n,cfg", [(515, {}), (1300, {}), (1500, SCHED), (2049, {}), (4200, {}), (6100, {}),

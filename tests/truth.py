@@ -364,3 +364,113 @@ def solve_errors(a, Ki, t, rows):
     """alpha and the chosen rows of K^-1 against the truth: largest absolute error relative to the largest entry."""
     return dict(alpha=float(np.max(np.abs(np.asarray(a).astype(LD) - t.alpha)) / np.max(np.abs(t.alpha))),
                 kinv=float(np.max(np.abs(np.asarray(Ki)[rows].astype(LD) - t.Kinv[rows])) / np.max(np.abs(t.Kinv))))
+
+
+# ---------------------------------------------------------------------------------------- beyond one test tile
+# tests/test_gpu_predict_wide.py: the prediction side pads to 128-row tiles, and NT = 64 runs exactly one of them.  The
+# wide cases predict at two and three test tiles; the draws and their factor are held to derived bounds.
+WIDE_NTS = (129, 200, 257)        # two tiles, one row into the second; two tiles, ragged; three tiles
+# case of LIVE_CASES -> the nt it runs at (small on purpose: truths and yardsticks are computed live)
+WIDE_CASES = {
+    "n65": WIDE_NTS,                   # nt > n; the covariance product's k range is one block
+    "n300_d17": WIDE_NTS,              # two feature chunks through k_cross
+    "n384_cond1e6": WIDE_NTS,
+    "n515_dense": WIDE_NTS,            # the covariance product splits in two over k
+    "n1025_dense": (200,),             # ... in four
+}
+WIDE_NT_FAMILY = 200                   # the one size of the ARD, Matern and BCM cases
+WIDE_TRAINING_ROW = -2                 # the test row that is a training row: beyond the first tile at every size
+POTRF_EXTRA_ULPS = 15                  # gamma_(n + 15) for the library's Cholesky: derived in test_gpu_accuracy.test_factor_residual,
+                                       # the one constant behind every factor bound (GPU and CPU counterpart)
+
+
+def wide_points(X, nt, scale):
+    """nt test points in the box of the case (synth's seed 7, as live_inputs), the last but one a training row."""
+    Xt = synth(nt, d=X.shape[1], seed=7, scale=scale)[0]
+    Xt[WIDE_TRAINING_ROW] = X[len(X) // 2]
+    return np.ascontiguousarray(Xt)
+
+
+def wide_inputs(name, nt):
+    """-> (X, y, Xt, hp): live_inputs' data and hyper-parameters with nt test points."""
+    X, y, _, hp = live_inputs(name)
+    return X, y, wide_points(X, nt, LIVE_CASES[name][3]), hp
+
+
+def se_fp64(hp):
+    """The stand-in's fp64 squared-exponential kernel function (no noise) -> kf(A, B)."""
+    l2, sf2 = np.exp(2 * np.asarray(hp[:2], dtype=np.float64))
+
+    def kf(A, B):
+        S = np.zeros((A.shape[0], B.shape[0]))
+        for k in range(A.shape[1]):
+            D = A[:, k][:, None] - B[:, k][None, :]
+            S += D * D
+        return sf2 * np.exp(-S / l2 / 2)
+    return kf
+
+
+def standin_joint(kf, X, y, Xt, sf2, sn2):
+    """`standin`'s prediction for any fp64 kernel function kf(A, B), with the joint covariance: LAPACK's Cholesky, a
+    triangular solve against I, BLAS products.  -> (mean, var, latent covariance); with noise: + sn2 on the diagonal."""
+    import scipy.linalg as sl
+    n = len(y)
+    L = np.linalg.cholesky(kf(X, X) + sn2 * np.eye(n))
+    T = sl.solve_triangular(L, np.eye(n), lower=True)
+    a = (T.T @ T) @ y
+    Ks = kf(Xt, X)
+    Wt = Ks @ T.T
+    return Ks @ a, sf2 + sn2 - (Wt * Wt).sum(1), kf(Xt, Xt) - Wt @ Wt.T
+
+
+def joint_errors(mean, var, cov_noise, cov_latent, tmean, tvar, tcov_latent, sn2):
+    """Largest absolute error of the means, the variances, and of any entry of the joint covariance with and without
+    noise (the true covariance with noise is the latent one + sn2 on its diagonal, added in longdouble)."""
+    tcn = tcov_latent.copy()
+    tcn[np.arange(len(tcn)), np.arange(len(tcn))] += sn2
+    e = errors_pred(mean, var, tmean, tvar)
+    e["cov_noise"] = float(np.max(np.abs(np.asarray(cov_noise).astype(LD) - tcn)))
+    e["cov_latent"] = float(np.max(np.abs(np.asarray(cov_latent).astype(LD) - tcov_latent)))
+    return e
+
+
+def factor_rule(worst):
+    """The project's rule for a factor F: the next power of two at or above twice the largest stand-in ratio."""
+    F = 1
+    while F < 2 * worst:
+        F *= 2
+    return F
+
+
+def factor_bound_worst(S, C, index, diag_allow=0.0):
+    """The componentwise bound on a computed Cholesky factor, on ALL rows of the lower triangle:
+        |S - C C^T|_ij <= gamma_index (|C||C^T|)_ij   (+ diag_allow on diagonal entries)
+    S: the matrix that was factored (fp64, or longdouble where it was never formed in fp64), C: its fp64 factor.
+    -> (largest residual / bound, (i, j), that residual, that bound)."""
+    nt = len(C)
+    res, mag = potrf_residual_rows(S, C, range(nt))
+    worst = (-1.0, None, 0.0, 0.0)
+    for i in range(nt):
+        b = gamma(index) * mag[i]
+        b[i] += diag_allow
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.where(res[i] == 0, LD(0), res[i] / b)          # (0 <= 0 holds; anything over a zero bound is inf)
+        j = int(np.argmax(r))
+        if not float(r[j]) <= worst[0]:
+            worst = (float(r[j]), (i, j), float(res[i][j]), float(b[j]))
+    return worst
+
+
+def draw_bound_worst(s, m, Z, C):
+    """Draws s = m + Z C^T in fp64, any order of summation, with or without fma, plus the one rounding of the final sum:
+        |s_st - (m_t + sum_k z_sk C_tk)| <= gamma_(nt+1) (|m_t| + sum_k |z_sk||C_tk|)
+    with the right-hand sides in longdouble from the fp64 m, Z, C.  -> (largest error / bound, (s, t), error, bound)."""
+    Zl, Cl, ml = np.asarray(Z).astype(LD), np.asarray(C).astype(LD), np.asarray(m).astype(LD)
+    nt = len(ml)
+    Ct = np.ascontiguousarray(Cl.T)
+    err = np.abs(np.asarray(s).astype(LD) - (ml[None, :] + _mm(Zl, Ct)))
+    bnd = gamma(nt + 1) * (np.abs(ml)[None, :] + _mm(np.abs(Zl), np.abs(Ct)))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(err == 0, LD(0), err / bnd)
+    k = np.unravel_index(int(np.argmax(r)), r.shape)
+    return float(r[k]), (int(k[0]), int(k[1])), float(err[k]), float(bnd[k])
