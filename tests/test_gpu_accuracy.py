@@ -1,5 +1,5 @@
 """GPU accuracy: the HIP path held to fp64 ROUNDING against an extended-precision truth (tests/truth.py), not to the
-1e-8 / 1e-6 of the parity suite.  For every case and checked quantity q
+1e-8 / 1e-6 of the parity suite.  For every case and checked quantity q (tests/accuracy.py holds the shared harness)
 
     err_gpu(q) <= F * max(noise(q), floor(q))
 
@@ -22,7 +22,9 @@ import sys
 import numpy as np
 import pytest
 
+import accuracy
 import truth
+from accuracy import Report
 from conftest import GOLDEN, synth
 
 sys.path.insert(0, GOLDEN)
@@ -31,9 +33,6 @@ import make_truth  # noqa: E402
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not truth.EXTENDED, reason="numpy.longdouble is not an extended-precision type here")]
 
-LD = truth.LD
-U4 = 4 * 2.0 ** -52
-
 
 @pytest.fixture(scope="module")
 def gp_mod():
@@ -41,133 +40,47 @@ def gp_mod():
     return gp
 
 
-class Report:
-    """Collects (quantity, error, yardstick) of one case, prints each, asserts all at the end."""
-
-    def __init__(self, case):
-        self.case, self.bad = case, []
-
-    def add(self, q, err, noise, floor, F=truth.F):
-        yard = max(noise, floor)
-        ratio = float(err) / yard
-        print("ACC %-14s %-18s err %.3e  noise %.3e  floor %.3e  ratio %6.2f" % (self.case, q, float(err), noise, floor, ratio))
-        if not ratio <= F:                           # NaN fails
-            self.bad.append((q, float(err), yard, ratio, F))
-
-    def check(self):
-        assert not self.bad, "%s: (quantity, error, yardstick, ratio, F) beyond F yardsticks: %s" % (self.case, self.bad)
-
-
-def add_six(rep, tag, e, noise, fl):
-    for q in truth.QUANTITIES:
-        if q in e:
-            rep.add(tag + q, e[q], noise[q], fl[q])
+def handle(gp_mod, X, cov, overlap=None):
+    g = gp_mod.Covsum(*X.shape)
+    if overlap is not None:
+        g.set_overlap(overlap)
+    g.set_loghyperparam(cov.hp)
+    return g
 
 
 # ------------------------------------------------------------------ live cases
-_CASE = {}
-
-
-def live(oracle, name):
-    """Inputs, truth and yardsticks of a live case, computed once per module."""
-    if name not in _CASE:
-        X, y, Xt, hp = truth.live_inputs(name)
-        t = truth.Truth(X, y, hp)
-        tm, tv = t.predict(Xt)
-        noise, _, _ = truth.noise_level(oracle, X, y, hp, Xt, t.ll, t.grad, tm, tv)
-        rows = truth.solve_rows(len(y))
-        solve = truth.noise_level_solve(oracle, X, y, hp, t, rows)
-        _CASE[name] = dict(X=X, y=y, Xt=Xt, hp=hp, t=t, tm=tm, tv=tv, noise=noise, solve=solve, rows=rows,
-                           floor=truth.floors(truth.scales(hp, t.ll, t.grad, tm)))
-    return _CASE[name]
-
-
 @pytest.mark.parametrize("name", list(truth.LIVE_CASES))
 def test_live_case(gp_mod, oracle, name):
     """loglik_grad, the LL-only path (forward substitution inside the factorisation), prediction at 64 test points (one
     of them a training row), alpha, 64 rows of K^-1, and on the three smallest and two largest cases the joint
     covariance with and without noise.  n1025_dense also on a handle of its own with the inverse streams off."""
-    c = live(oracle, name)
-    X, y, Xt, hp, t = c["X"], c["y"], c["Xt"], c["hp"], c["t"]
-    n, d = X.shape
-    rep = Report(name)
-
-    g = gp_mod.Covsum(n, d)
-    g.set_loghyperparam(hp)
-    ll_only = g.compute_loglikelihood(X, y)                       # first call on a fresh handle: nothing to reuse
-    rep.add("ll_only", abs(LD(ll_only) - t.ll) / abs(t.ll), c["noise"]["ll"], c["floor"]["ll"])
-    g.close()
-
-    # a fresh handle per overlap setting, set before its first evaluation: a handle that has evaluated this point
-    # answers from what it holds, whatever the setting says by then
-    for overlap in ((False, True) if name == "n1025_dense" else (True,)):
-        g = gp_mod.Covsum(n, d)
-        g.set_overlap(overlap)
-        g.set_loghyperparam(hp)
-        tag = "" if overlap else "nooverlap_"
-        ll, gr = g.loglik_grad(X, y)
-        add_six(rep, tag, truth.errors_ll_grad(ll, gr, t.ll, t.grad), c["noise"], c["floor"])
-        Ki = g.get_K_inverse()
-        assert np.array_equal(Ki, Ki.T)
-        es = truth.solve_errors(g.get_alpha(), Ki, t, c["rows"])
-        for q in truth.SOLVE_QUANTITIES:
-            rep.add(tag + q, es[q], c["solve"][q], U4, truth.F_SOLVE)
-        m, v = g.compute_test_means_and_variances(X, y, Xt)
-        add_six(rep, tag, truth.errors_pred(m, v, c["tm"], c["tv"]), c["noise"], c["floor"])
-        if not overlap:
-            g.close()
-    if name in truth.JOINT_CASES:
-        for with_noise in (True, False):
-            tmj, tcov = t.joint(Xt, with_noise)
-            mj, cov = g.compute_test_joint(X, y, Xt, with_noise=with_noise)
-            tag = "joint_noise_" if with_noise else "joint_latent_"
-            rep.add(tag + "mean", np.max(np.abs(mj.astype(LD) - tmj)), c["noise"]["mean"], c["floor"]["mean"])
-            rep.add(tag + "cov", np.max(np.abs(cov.astype(LD) - tcov)), c["noise"]["var"], c["floor"]["cov"])
-    g.close()
-    rep.check()
+    c = accuracy.live(oracle, "se", name)
+    accuracy.hold_live_case(Report(name, c["cov"]), c, lambda overlap=None: handle(gp_mod, c["X"], c["cov"], overlap),
+                            overlaps=(False, True) if name == "n1025_dense" else (True,), joint=name in truth.JOINT_CASES)
 
 
 # ------------------------------------------------------------------ fixture cases
-def fixture_yardsticks(f):
-    fl = truth.floors(truth.scales(f["hp"], f["ll"], f["grad"], f["mean"]))
-    return f["noise"], fl
-
-
 @pytest.mark.parametrize("name", ["n2049", "n4200"])
 def test_fixture_case(gp_mod, name):
     """17 tiles and 33 tiles (the largest size of the classic schedule) against the committed truth."""
-    f = make_truth.load(name)
-    X, y, Xt, hp, _ = make_truth.inputs(name)
-    noise, fl = fixture_yardsticks(f)
-    rep = Report(name)
-    g = gp_mod.Covsum(*X.shape)
-    g.set_loghyperparam(hp)
-    ll_only = g.compute_loglikelihood(X, y)
-    rep.add("ll_only", abs(LD(ll_only) - f["ll"]) / abs(f["ll"]), noise["ll"], fl["ll"])
-    g.close()
-    g = gp_mod.Covsum(*X.shape)
-    g.set_loghyperparam(hp)
-    ll, gr = g.loglik_grad(X, y)
-    m, v = g.compute_test_means_and_variances(X, y, Xt)
-    g.close()
-    add_six(rep, "", truth.errors(ll, gr, m, v, f["ll"], f["grad"], f["mean"], f["var"]), noise, fl)
-    rep.check()
+    X, y, Xt, cov, _ = make_truth.inputs(name)
+    accuracy.hold_fixture_case(Report(name, cov), make_truth.load(name), X, y, Xt, cov, lambda: handle(gp_mod, X, cov))
 
 
 def test_fixture_bcm(gp_mod):
     """Three 1500-row experts of the si24000 data at HP_BCM, factored as one group: summed LL and gradient
     (cugp_bcm_loglik_grad) and the product-of-experts prediction (cugp_bcm_predict)."""
     f = make_truth.load("bcm3x1500")
-    X, y, Xt, hp, experts = make_truth.inputs("bcm3x1500")
-    noise, fl = fixture_yardsticks(f)
-    rep = Report("bcm3x1500")
+    X, y, Xt, cov, experts = make_truth.inputs("bcm3x1500")
+    fl = truth.floors(cov, truth.scales(cov, f["ll"], f["grad"], f["mean"]))
+    rep = Report("bcm3x1500", cov)
     b = gp_mod.BCM.split(X, y, experts)
     assert b.rows == [r for _, r in truth.bcm_rows(len(y), experts)]
-    b.set_BCM_log_hyperparam(hp)
+    b.set_BCM_log_hyperparam(cov.hp)
     ll, gr, _ = b.loglik_grad()
     m, v = b.compute_BCM_test_means_and_var(Xt)
     b.close()
-    add_six(rep, "", truth.errors(ll, gr, m, v, f["ll"], f["grad"], f["mean"], f["var"]), noise, fl)
+    rep.add_all("", truth.errors(cov, ll, gr, m, v, f["ll"], f["grad"], f["mean"], f["var"]), f["noise"], fl)
     rep.check()
 
 

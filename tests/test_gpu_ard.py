@@ -1,12 +1,13 @@
 """GPU tests of the ARD kernel (one length scale per input dimension; cugp_create_ard and the _ard calls).
 
-Accuracy is held to fp64 rounding against the extended-precision truth of tests/truth_ard.py:
+Accuracy is held to fp64 rounding against the extended-precision truth of tests/truth.py (the truth.ARD descriptor),
+through the harness of tests/accuracy.py:
 
     err_gpu(q) <= F_ARD * max(noise(q), floor(q))
 
-with errors and floors as in tests/truth.py (every gradient component relative to the largest of the d + 2 true ones),
-the yardstick from the CPU oracle on the scaled copy X / l (every per-dimension component uses the yardstick of their
-sum) and F_ARD = 32 set from the CPU stand-in (tests/test_truth_ard_cpu.py, docs/ACCURACY.md) -- never from the GPU.
+with every gradient component relative to the largest of the d + 2 true ones, the yardstick from the CPU oracle on
+the scaled copy X / l (every per-dimension component uses the yardstick of their sum) and F_ARD = 32 set from the
+CPU stand-in (tests/test_truth_ard_cpu.py, docs/ACCURACY.md) -- never from the GPU.
 Every figure is printed before it is asserted ("ACC <case> <quantity> err noise floor ratio"; run with -s).
 One process, one device (test 9 starts one fresh child process); nothing outside the tree is read.
 """
@@ -19,47 +20,26 @@ import sys
 import numpy as np
 import pytest
 
+import accuracy
+import golden_jobs
 import truth
-import truth_ard as ta
+from accuracy import Report
 from conftest import GOLDEN, ROOT, synth
 from cugp_amd import capi
 
 sys.path.insert(0, GOLDEN)
-import make_truth_ard  # noqa: E402
+import make_truth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 extended = pytest.mark.skipif(not truth.EXTENDED, reason="numpy.longdouble is not an extended-precision type here")
 
 LD = truth.LD
-U4 = 4 * 2.0 ** -52
 
 
 @pytest.fixture(scope="module")
 def gp_mod():
     import cugp_amd.gp as gp
     return gp
-
-
-class Report:
-    """Collects (quantity, error, yardstick) of one case, prints each, asserts all at the end."""
-
-    def __init__(self, case):
-        self.case, self.bad = case, []
-
-    def add(self, q, err, noise, floor, F=ta.F_ARD):
-        yard = max(noise, floor)
-        ratio = float(err) / yard
-        print("ACC %-14s %-18s err %.3e  noise %.3e  floor %.3e  ratio %6.2f" % (self.case, q, float(err), noise, floor, ratio))
-        if not ratio <= F:                           # NaN fails
-            self.bad.append((q, float(err), yard, ratio, F))
-
-    def add_all(self, tag, e, noise, fl, F=ta.F_ARD):
-        for q in ta.QUANTITIES:
-            if q in e:
-                self.add(tag + q, e[q], noise[q], fl[q], F)
-
-    def check(self):
-        assert not self.bad, "%s: (quantity, error, yardstick, ratio, F) beyond F yardsticks: %s" % (self.case, self.bad)
 
 
 def ard(gp_mod, X, y, hp, overlap=None):
@@ -73,67 +53,26 @@ def ard(gp_mod, X, y, hp, overlap=None):
 
 # ------------------------------------------------------------------ 1. accuracy
 @extended
-@pytest.mark.parametrize("name", list(ta.ARD_CASES))
+@pytest.mark.parametrize("name", list(truth.ARD_CASES))
 def test_accuracy_live(gp_mod, oracle, name):
     """loglik_grad, the LL-only path, prediction at 64 points, alpha and 64 rows of K^-1 (F_SOLVE), the joint covariance
     with and without noise on the two smallest and two largest cases; n1025_dense also with the inverse streams off."""
-    X, y, Xt, hp = ta.ard_inputs(name)
-    t = ta.TruthARD(X, y, hp)
-    tm, tv = t.predict(Xt)
-    noise, _, _ = ta.noise_level_ard(oracle, X, y, hp, Xt, t.ll, t.grad, tm, tv)
-    fl = ta.floors_ard(ta.scales_ard(hp, t.ll, t.grad, tm))
-    rows = truth.solve_rows(len(y))
-    solve = ta.noise_level_solve_ard(oracle, X, y, hp, t, rows)
-    rep = Report(name)
+    c = accuracy.live(oracle, "ard", name)
+    X, y, cov = c["X"], c["y"], c["cov"]
 
-    g = ard(gp_mod, X, y, hp)
-    assert g.get_param_dim() == X.shape[1] + 2
-    ll_only = g.compute_loglikelihood()                          # first call on a fresh handle: nothing to reuse
-    rep.add("ll_only", abs(LD(ll_only) - t.ll) / abs(t.ll), noise["ll"], fl["ll"])
-    g.close()
-    for overlap in ((False, True) if name == "n1025_dense" else (True,)):
-        g = ard(gp_mod, X, y, hp, overlap)
-        tag = "" if overlap else "nooverlap_"
-        ll, gr = g.loglik_grad()
-        assert gr.shape == (X.shape[1] + 2,)
-        rep.add_all(tag, ta.errors_ll_grad_ard(ll, gr, t.ll, t.grad), noise, fl)
-        Ki = g.get_K_inverse()
-        assert np.array_equal(Ki, Ki.T)
-        es = truth.solve_errors(g.get_alpha(), Ki, t, rows)
-        for q in truth.SOLVE_QUANTITIES:
-            rep.add(tag + q, es[q], solve[q], U4, ta.F_SOLVE)
-        m, v = g.compute_test_means_and_variances(X, y, Xt)
-        rep.add_all(tag, truth.errors_pred(m, v, tm, tv), noise, fl)
-        if not overlap:
-            g.close()
-    if name in ta.JOINT_CASES:
-        for with_noise in (True, False):
-            tmj, tcov = t.joint(Xt, with_noise)
-            mj, cov = g.compute_test_joint(X, y, Xt, with_noise=with_noise)
-            tag = "joint_noise_" if with_noise else "joint_latent_"
-            rep.add(tag + "mean", np.max(np.abs(mj.astype(LD) - tmj)), noise["mean"], fl["mean"])
-            rep.add(tag + "cov", np.max(np.abs(cov.astype(LD) - tcov)), noise["var"], fl["cov"])
-    g.close()
-    rep.check()
+    def fresh(g):
+        assert g.get_param_dim() == X.shape[1] + 2
+    accuracy.hold_live_case(Report(name, cov), c, lambda overlap=None: ard(gp_mod, X, y, cov.hp, overlap),
+                            overlaps=(False, True) if name == "n1025_dense" else (True,),
+                            joint=name in truth.JOINT_CASES_ARD, fresh=fresh)
 
 
 @extended
 def test_accuracy_fixture_n2049_d10(gp_mod):
-    """17 tiles, ten unequal length scales, against the committed truth (tests/golden/make_truth_ard.py)."""
-    f = make_truth_ard.load("n2049_d10")                          # a missing fixture fails, it does not skip
-    X, y, Xt, hp = make_truth_ard.inputs("n2049_d10")
-    fl = ta.floors_ard(ta.scales_ard(hp, f["ll"], f["grad"], f["mean"]))
-    rep = Report("n2049_d10")
-    g = ard(gp_mod, X, y, hp)
-    ll_only = g.compute_loglikelihood()
-    rep.add("ll_only", abs(LD(ll_only) - f["ll"]) / abs(f["ll"]), f["noise"]["ll"], fl["ll"])
-    g.close()
-    g = ard(gp_mod, X, y, hp)
-    ll, gr = g.loglik_grad()
-    m, v = g.compute_test_means_and_variances(X, y, Xt)
-    g.close()
-    rep.add_all("", ta.errors_ard(ll, gr, m, v, f["ll"], f["grad"], f["mean"], f["var"]), f["noise"], fl)
-    rep.check()
+    """17 tiles, ten unequal length scales, against the committed truth (tests/golden/make_truth.py)."""
+    X, y, Xt, cov, _ = make_truth.inputs("n2049_d10")
+    accuracy.hold_fixture_case(Report("n2049_d10", cov), make_truth.load("n2049_d10"),       # a missing fixture fails, it does not skip
+                               X, y, Xt, cov, lambda: ard(gp_mod, X, y, cov.hp))
 
 
 # ------------------------------------------------------------------ 2. a dropped dimension drops out exactly
@@ -160,20 +99,19 @@ def test_nearly_dropped_and_overflowing_dimension(gp_mod, oracle):
     """theta_2 = 40 (w_2 = 4e-18): finite, and the 3-column model within the accuracy bound.  theta_2 = -800 (w_2
     overflows): LL is NaN and the call still returns CUGP_OK (the header's convention), no error, fault or hang."""
     X, y = synth(200, d=4, seed=11, scale=3.0)
-    Xt = synth(ta.NT, d=4, seed=7, scale=3.0)[0]
+    Xt = synth(truth.NT, d=4, seed=7, scale=3.0)[0]
     keep = [0, 1, 3]
     hp3 = [0.5, 0.7, 0.9, 0.3, -1.0]
     X3, Xt3 = np.ascontiguousarray(X[:, keep]), np.ascontiguousarray(Xt[:, keep])
-    t = ta.TruthARD(X3, y, hp3)
-    tm, tv = t.predict(Xt3)
-    noise, _, _ = ta.noise_level_ard(oracle, X3, y, hp3, Xt3, t.ll, t.grad, tm, tv)
-    fl = ta.floors_ard(ta.scales_ard(hp3, t.ll, t.grad, tm))
+    cov = truth.ARD(hp3)
+    c = accuracy.case_at(oracle, cov, X3, y, Xt3, truth.Truth(X3, y, cov))
+    t, noise, fl = c["t"], c["noise"], c["floor"]
     g = ard(gp_mod, X, y, [0.5, 0.7, 40.0, 0.9, 0.3, -1.0])
     ll, gr = g.loglik_grad()
     m, v = g.compute_test_means_and_variances(X, y, Xt)
     assert np.isfinite(ll) and np.all(np.isfinite(gr)) and np.all(np.isfinite(m)) and np.all(np.isfinite(v))
-    rep = Report("theta2=40")
-    rep.add_all("", ta.errors_ard(ll, gr[[0, 1, 3, 4, 5]], m, v, t.ll, t.grad, tm, tv), noise, fl)
+    rep = Report("theta2=40", cov)
+    rep.add_all("", truth.errors(cov, ll, gr[[0, 1, 3, 4, 5]], m, v, t.ll, t.grad, c["tm"], c["tv"]), noise, fl)
     rep.add("g_2", abs(gr[2]) / float(np.max(np.abs(t.grad))), noise["gc"], fl["gc"])
     g.set_loghyperparam([0.5, 0.7, -800.0, 0.9, 0.3, -1.0])
     ll, gr = g.loglik_grad()                                      # raises on any return code but CUGP_OK
@@ -190,12 +128,9 @@ def test_nearly_dropped_and_overflowing_dimension(gp_mod, oracle):
 @pytest.mark.parametrize("name", ["n257_d3", "n515_dense"])
 def test_equal_length_scales_meet_the_isotropic_handle(gp_mod, oracle, name):
     """Both handles are within their bounds of the same truth, so they differ by at most (F + F_ARD) yardsticks."""
-    X, y, Xt, hp = truth.live_inputs(name)
+    c = accuracy.live(oracle, "se", name)
+    X, y, Xt, cov, hp = c["X"], c["y"], c["Xt"], c["cov"], c["cov"].hp
     d = X.shape[1]
-    t = truth.Truth(X, y, hp, keep=False)
-    tm, tv = t.predict(Xt)
-    noise, _, _ = truth.noise_level(oracle, X, y, hp, Xt, t.ll, t.grad, tm, tv)
-    fl = truth.floors(truth.scales(hp, t.ll, t.grad, tm))
     gi = gp_mod.Covsum(*X.shape)
     gi.set_loghyperparam(hp)
     lli, gri = gi.loglik_grad(X, y)
@@ -205,10 +140,9 @@ def test_equal_length_scales_meet_the_isotropic_handle(gp_mod, oracle, name):
     lla, gra = ga.loglik_grad()
     ma, va = ga.compute_test_means_and_variances(X, y, Xt)
     ga.close()
-    e = truth.errors(lla, [gra[:d].sum(), gra[d], gra[d + 1]], ma, va, LD(lli), gri.astype(LD), mi.astype(LD), vi.astype(LD))
-    rep = Report(name + "_iso")
-    for q in truth.QUANTITIES:
-        rep.add(q, e[q], noise[q], fl[q], truth.F + ta.F_ARD)
+    e = truth.errors(cov, lla, [gra[:d].sum(), gra[d], gra[d + 1]], ma, va, LD(lli), gri.astype(LD), mi.astype(LD), vi.astype(LD))
+    rep = Report(name + "_iso", cov)
+    rep.add_all("", e, c["noise"], c["floor"], truth.F + truth.F_ARD)
     rep.check()
 
 
@@ -216,20 +150,19 @@ def test_dense_8192_golden_with_ten_equal_length_scales(gp_mod):
     """The dense 8192-row golden of tests/test_gpu_golden_configs.py through an ARD handle with ten equal theta_c = hp[0]:
     the reference's LL and gradient at that file's tolerances, with the gradient and -- on a fresh handle -- through the
     LL-only path.  The only test of the two-speed schedule and the 8256-block trace under ARD."""
-    import test_gpu_golden_configs as gc
-    c = gc.job("d8192_ll")                                        # a missing fixture fails, it does not skip
+    c = golden_jobs.job("d8192_ll")                                        # a missing fixture fails, it does not skip
     z = np.load(os.path.join(GOLDEN, "data_siproper_9192.npz"))
     X, y = np.ascontiguousarray(z["X"][:8192]), np.ascontiguousarray(z["y"][:8192])
     hp = [c["hp"][0]] * 10 + [c["hp"][1], c["hp"][2]]
     g = ard(gp_mod, X, y, hp)
     ll, gr = g.loglik_grad()
-    assert gc.ll_close(ll, c["ll"]), (ll, c["ll"])
-    cg = gc.job("d8192_grad")
+    assert golden_jobs.ll_close(ll, c["ll"]), (ll, c["ll"])
+    cg = golden_jobs.job("d8192_grad")
     g3 = [gr[:10].sum(), gr[10], gr[11]]
-    assert gc.grad_close(g3, cg["grad"]), (g3, cg["grad"])
+    assert golden_jobs.grad_close(g3, cg["grad"]), (g3, cg["grad"])
     g.close()
     g = ard(gp_mod, X, y, hp)
-    assert gc.ll_close(g.compute_loglikelihood(), c["ll"])
+    assert golden_jobs.ll_close(g.compute_loglikelihood(), c["ll"])
     g.close()
 
 
@@ -287,10 +220,11 @@ def test_feature_chunks_against_the_standin(gp_mod, d):
     n = 130
     X, y = synth(n, d=d, seed=100 + d, scale=2.0)
     hp = np.linspace(0.8, 1.6, d).tolist() + [0.3, -0.8]
-    sll, sg, _, _ = ta.standin_ard(X, y, hp)
+    cov = truth.ARD(hp)
+    sll, sg, _, _ = truth.standin(cov, X, y, X[:1])
     if truth.EXTENDED:
-        t = ta.TruthARD(X, y, hp)
-        e = ta.errors_ll_grad_ard(sll, sg, t.ll, t.grad)
+        t = truth.Truth(X, y, cov, keep=False)
+        e = truth.errors_ll_grad(cov, sll, sg, t.ll, t.grad)
         print("d=%d stand-in against the truth: %s" % (d, e))
         assert max(e.values()) <= 1e-13, e
     g = ard(gp_mod, X, y, hp)
@@ -313,7 +247,7 @@ def test_cg_solve_ard_finds_the_relevant_dimension(gp_mod):
     start = [0.5] * 4 + [0.5, 0.5]
 
     def fn(th):
-        ll, g, _, _ = ta.standin_ard(X, y, th)
+        ll, g, _, _ = truth.standin(truth.ARD(th), X, y, X[:1])
         return -ll, g
     th_cpu, tr_cpu = gp_mod.cg_minimize_n(fn, start, 60)
     g = ard(gp_mod, X, y, start)

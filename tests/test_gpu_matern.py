@@ -1,10 +1,11 @@
 """GPU tests of the Matern 3/2 and 5/2 kernels (cugp_create_kernel, Covsum(kernel=), BCM(kernel=)).
 
-Accuracy is held to fp64 rounding against the extended-precision truth of tests/truth_matern.py:
+Accuracy is held to fp64 rounding against the extended-precision truth of tests/truth.py (the truth.Matern descriptor),
+through the harness of tests/accuracy.py:
 
     err_gpu(q) <= F_MATERN * max(noise(q), floor(q))
 
-with errors and floors as in tests/truth.py, the yardstick from the CPU oracle's linear algebra on the fp64 Matern K
+with the yardstick from the CPU oracle's linear algebra on the fp64 Matern K
 (data as given and seven permutations) and F_MATERN = 16 set from the CPU stand-in (tests/test_truth_matern_cpu.py,
 docs/ACCURACY.md) -- never from the GPU.  K and k_test entries are held to the rounding count of
 truth_matern.k_entry_bound.  Every figure is printed before it is asserted ("ACC <case> <quantity> err noise floor
@@ -21,19 +22,20 @@ import sys
 import numpy as np
 import pytest
 
+import accuracy
 import truth
 import truth_matern as tm
+from accuracy import Report
 from conftest import GOLDEN, ROOT, synth
 from cugp_amd import capi
 
 sys.path.insert(0, GOLDEN)
-import make_truth_matern  # noqa: E402
+import make_truth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 extended = pytest.mark.skipif(not truth.EXTENDED, reason="numpy.longdouble is not an extended-precision type here")
 
 LD = truth.LD
-U4 = 4 * 2.0 ** -52
 KINDS = [pytest.param(k, id=tm.KIND_NAMES[k]) for k in tm.KINDS]
 TUNE_GRAPHS, TUNE_FINALIZE_FUSE_MAX = 5, 12                      # kernels.h TUNE_*
 HP = [0.9, 0.2, -1.0]
@@ -43,28 +45,6 @@ HP = [0.9, 0.2, -1.0]
 def gp_mod():
     import cugp_amd.gp as gp
     return gp
-
-
-class Report:
-    """Collects (quantity, error, yardstick) of one case, prints each, asserts all at the end."""
-
-    def __init__(self, case):
-        self.case, self.bad = case, []
-
-    def add(self, q, err, noise, floor, F=tm.F_MATERN):
-        yard = max(noise, floor)
-        ratio = float(err) / yard
-        print("ACC %-22s %-18s err %.3e  noise %.3e  floor %.3e  ratio %6.2f" % (self.case, q, float(err), noise, floor, ratio))
-        if not ratio <= F:                           # NaN fails
-            self.bad.append((q, float(err), yard, ratio, F))
-
-    def add_all(self, tag, e, noise, fl, F=tm.F_MATERN):
-        for q in tm.QUANTITIES:
-            if q in e:
-                self.add(tag + q, e[q], noise[q], fl[q], F)
-
-    def check(self):
-        assert not self.bad, "%s: (quantity, error, yardstick, ratio, F) beyond F yardsticks: %s" % (self.case, self.bad)
 
 
 def handle(gp_mod, X, y, hp, kind, overlap=None, tuning=None):
@@ -87,56 +67,26 @@ def same_bits(a, b):
 # ------------------------------------------------------------------ 1. accuracy
 @extended
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("name", list(tm.MATERN_CASES))
+@pytest.mark.parametrize("name", list(truth.MATERN_CASES))
 def test_accuracy_live(gp_mod, oracle, name, kind):
     """loglik_grad, the LL-only path, prediction at 64 points, alpha and 64 rows of K^-1 (F_SOLVE); n1025_dense also
     with the inverse streams off."""
-    X, y, Xt, hp = tm.matern_inputs(name)
-    t = tm.TruthMatern(X, y, hp, kind)
-    tmean, tvar = t.predict(Xt)
-    rows = truth.solve_rows(len(y))
-    noise, _, _, solve = tm.noise_level_matern(oracle, X, y, hp, Xt, kind, t, tmean, tvar, rows)
-    fl = truth.floors(truth.scales(hp, t.ll, t.grad, tmean))
-    rep = Report("%s/%s" % (name, tm.KIND_NAMES[kind]))
+    c = accuracy.live(oracle, tm.KIND_NAMES[kind], name)
+    X, y, cov = c["X"], c["y"], c["cov"]
 
-    g = handle(gp_mod, X, y, hp, kind)
-    assert g.kernel == tm.KIND_NAMES[kind]
-    ll_only = g.compute_loglikelihood()                          # first call on a fresh handle: nothing to reuse
-    rep.add("ll_only", abs(LD(ll_only) - t.ll) / abs(t.ll), noise["ll"], fl["ll"])
-    g.close()
-    for overlap in ((False, True) if name == "n1025_dense" else (True,)):
-        g = handle(gp_mod, X, y, hp, kind, overlap)
-        tag = "" if overlap else "nooverlap_"
-        ll, gr = g.loglik_grad()
-        rep.add_all(tag, truth.errors_ll_grad(ll, gr, t.ll, t.grad), noise, fl)
-        Ki = g.get_K_inverse()
-        assert np.array_equal(Ki, Ki.T)
-        es = truth.solve_errors(g.get_alpha(), Ki, t, rows)
-        for q in truth.SOLVE_QUANTITIES:
-            rep.add(tag + q, es[q], solve[q], U4, tm.F_SOLVE)
-        m, v = g.compute_test_means_and_variances(X, y, Xt)
-        rep.add_all(tag, truth.errors_pred(m, v, tmean, tvar), noise, fl)
-        g.close()
-    rep.check()
+    def fresh(g):
+        assert g.kernel == tm.KIND_NAMES[kind]
+    accuracy.hold_live_case(Report("%s/%s" % (name, tm.KIND_NAMES[kind]), cov), c,
+                            lambda overlap=None: handle(gp_mod, X, y, cov.hp, kind, overlap),
+                            overlaps=(False, True) if name == "n1025_dense" else (True,), fresh=fresh)
 
 
 @extended
 def test_accuracy_fixture_n2049_m52(gp_mod):
-    """17 tiles, nu = 5/2, against the committed truth (tests/golden/make_truth_matern.py)."""
-    f = make_truth_matern.load("n2049_m52")                       # a missing fixture fails, it does not skip
-    X, y, Xt, hp, kind = make_truth_matern.inputs("n2049_m52")
-    fl = truth.floors(truth.scales(hp, f["ll"], f["grad"], f["mean"]))
-    rep = Report("n2049_m52")
-    g = handle(gp_mod, X, y, hp, kind)
-    ll_only = g.compute_loglikelihood()
-    rep.add("ll_only", abs(LD(ll_only) - f["ll"]) / abs(f["ll"]), f["noise"]["ll"], fl["ll"])
-    g.close()
-    g = handle(gp_mod, X, y, hp, kind)
-    ll, gr = g.loglik_grad()
-    m, v = g.compute_test_means_and_variances(X, y, Xt)
-    g.close()
-    rep.add_all("", truth.errors(ll, gr, m, v, f["ll"], f["grad"], f["mean"], f["var"]), f["noise"], fl)
-    rep.check()
+    """17 tiles, nu = 5/2, against the committed truth (tests/golden/make_truth.py)."""
+    X, y, Xt, cov, _ = make_truth.inputs("n2049_m52")
+    accuracy.hold_fixture_case(Report("n2049_m52", cov), make_truth.load("n2049_m52"),       # a missing fixture fails, it does not skip
+                               X, y, Xt, cov, lambda: handle(gp_mod, X, y, cov.hp, cov.kind))
 
 
 # ------------------------------------------------------------------ 2. K and k_test
@@ -147,7 +97,7 @@ def test_K_and_k_test_entries(gp_mod, name, kind):
     """cugp_compute_K_train and cugp_compute_k_test entry by entry against the truth, inside the derived K-entry bound
     (truth_matern.k_entry_bound; relative to the true entry); K exactly symmetric, its diagonal bit-equal to
     sf2 + sn2 as fp64 forms it."""
-    X, y, Xt, hp = tm.matern_inputs(name)
+    X, y, Xt, hp = truth.live_inputs(name)
     n, d = X.shape
     l2, sf2, sn2 = truth.hyper(hp)
     g = handle(gp_mod, X, y, hp, kind)
@@ -159,7 +109,7 @@ def test_K_and_k_test_entries(gp_mod, name, kind):
     off = ~np.eye(n, dtype=bool)
     worst = {}
     for tag, got, A, mask in (("K", K, X, off), ("k_test", Ks, Xt, np.ones(Ks.shape, dtype=bool))):
-        true = tm.kernel_ld(truth.sqdist(A, X) / l2, sf2, kind)[0]
+        true = truth.matern_kernel(truth.sqdist(A, X) / l2, sf2, kind)[0]
         bound = tm.k_entry_bound(tm.a_of(A, X, hp, kind), d, kind)
         rel = (np.abs(got.astype(LD) - true) / true)[mask]
         worst[tag] = float(np.max(rel / bound[mask]))
@@ -350,10 +300,11 @@ def test_feature_chunks_against_the_standin(gp_mod, d, kind):
     n = 130
     X, y = synth(n, d=d, seed=100 + d, scale=2.0)
     hp = [0.5 * np.log(d) + 1.2, 0.3, -0.8]
-    sll, sg, _, _ = tm.standin_matern(X, y, hp, X[:1], kind)
+    cov = truth.Matern(hp, kind)
+    sll, sg, _, _ = truth.standin(cov, X, y, X[:1])
     if truth.EXTENDED:
-        t = tm.TruthMatern(X, y, hp, kind, keep=False)
-        e = truth.errors_ll_grad(sll, sg, t.ll, t.grad)
+        t = truth.Truth(X, y, cov, keep=False)
+        e = truth.errors_ll_grad(cov, sll, sg, t.ll, t.grad)
         print("d=%d stand-in against the truth: %s" % (d, e))
         assert max(e.values()) <= 1e-13, e
     g = handle(gp_mod, X, y, hp, kind)
@@ -386,19 +337,16 @@ def test_fused_and_separate_final_sums_1300(gp_mod, kind):
 # ------------------------------------------------------------------ 7. joint covariance and draws
 @extended
 @pytest.mark.parametrize("kind", KINDS)
-@pytest.mark.parametrize("name", list(tm.JOINT_CASES))
+@pytest.mark.parametrize("name", list(truth.JOINT_CASES))
 def test_joint_covariance_and_draws(gp_mod, oracle, name, kind):
-    """cugp_predict_cov with and without noise against TruthMatern.joint, at the bound tests/test_gpu_accuracy.py and
-    tests/test_gpu_predict_joint.py hold the SE joint covariance to (the variance's yardstick, the covariance floor)
+    """cugp_predict_cov with and without noise against the truth's joint covariance, at the bound tests/test_gpu_accuracy.py
+    and tests/test_gpu_predict_joint.py hold the SE joint covariance to (the variance's yardstick, the covariance floor)
     with F_MATERN; cov exactly symmetric, the mean cugp_predict's bits.  Draws: zero normals give the mean's bits, unit
     normals pick columns of the Cholesky factor of the library's own covariance (against LAPACK's factor of the same
     fp64 matrix: two backward-stable factorisations differ by about nt eps cond(cov) relative to the factor's scale)."""
-    X, y, Xt, hp = truth.live_inputs(name)
-    t = tm.TruthMatern(X, y, hp, kind)
-    tmean, tvar = t.predict(Xt)
-    noise, _, _, _ = tm.noise_level_matern(oracle, X, y, hp, Xt, kind, t, tmean, tvar)
-    fl = truth.floors(truth.scales(hp, t.ll, t.grad, tmean))
-    rep = Report("%s/%s" % (name, tm.KIND_NAMES[kind]))
+    c = accuracy.live(oracle, tm.KIND_NAMES[kind], name)
+    X, y, Xt, hp, t, noise, fl = c["X"], c["y"], c["Xt"], c["cov"].hp, c["t"], c["noise"], c["floor"]
+    rep = Report("%s/%s" % (name, tm.KIND_NAMES[kind]), c["cov"])
     g = handle(gp_mod, X, y, hp, kind)
     m, _ = g.compute_test_means_and_variances(X, y, Xt)
     for with_noise in (True, False):
@@ -425,19 +373,6 @@ def test_joint_covariance_and_draws(gp_mod, oracle, name, kind):
 
 
 # ------------------------------------------------------------------ 8. BCM
-def bcm_yardstick(oracle, X, y, hp, K, Xt, kind, tb):
-    """truth.noise_level over the experts: every expert through the oracle's linear algebra (oracle_eval), LL and gradient
-    summed in expert order, product of experts; rows permuted inside their own expert."""
-    def evaluate(Xp, yp):
-        ll, g, sp, spm = 0.0, np.zeros(3), 0.0, 0.0
-        for off, rows in truth.bcm_rows(len(yp), K):
-            l, gr, m, v = tm.oracle_eval(oracle, Xp[off: off + rows], yp[off: off + rows], hp, Xt, kind)
-            ll, g, sp, spm = ll + l, g + gr, sp + 1 / v, spm + m / v
-        return ll, g, spm / sp, 1 / sp
-    return truth.noise_level(oracle, X, y, hp, Xt, tb["ll"], tb["grad"], tb["mean"], tb["var"], evaluate=evaluate,
-                             parts=truth.bcm_rows(len(y), K))[0]
-
-
 @extended
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("N, K", [(3 * 300, 3), (5 * 261 + 2, 5)], ids=["3x300", "5-uneven"])
@@ -448,10 +383,11 @@ def test_bcm_against_the_truth(gp_mod, oracle, N, K, kind):
     combined in expert order by cugp_poe_finish, bit for bit."""
     d = 5
     X, y = synth(N, d=d, seed=N + K, scale=3.0)
-    Xt = synth(tm.NT, d=d, seed=7, scale=3.0)[0]
-    tb = tm.bcm_truth_matern(X, y, HP, K, Xt, kind)
-    noise = bcm_yardstick(oracle, X, y, HP, K, Xt, kind, tb)
-    fl = truth.floors(truth.scales(HP, tb["ll"], tb["grad"], tb["mean"]))
+    Xt = synth(truth.NT, d=d, seed=7, scale=3.0)[0]
+    cov = truth.Matern(HP, kind)
+    tb = truth.bcm_truth(X, y, cov, K, Xt)
+    noise = truth.bcm_yardstick(oracle, cov, X, y, K, Xt, tb)[0]       # every expert through the oracle's linear algebra
+    fl = truth.floors(cov, truth.scales(cov, tb["ll"], tb["grad"], tb["mean"]))
     parts = truth.bcm_rows(N, K)
     if K == 3:
         b = gp_mod.BCM([r for _, r in parts], d, kernel=kind)
@@ -464,9 +400,9 @@ def test_bcm_against_the_truth(gp_mod, oracle, N, K, kind):
     b.set_BCM_log_hyperparam(HP)
     ll, gr, per = b.loglik_grad()
     m, v = b.compute_BCM_test_means_and_var(Xt)
-    rep = Report("bcm%dx/%s" % (K, tm.KIND_NAMES[kind]))
-    rep.add_all("", truth.errors(ll, gr, m, v, tb["ll"], tb["grad"], tb["mean"], tb["var"]), noise, fl)
-    sp, spm = np.zeros(tm.NT), np.zeros(tm.NT)
+    rep = Report("bcm%dx/%s" % (K, tm.KIND_NAMES[kind]), cov)
+    rep.add_all("", truth.errors(cov, ll, gr, m, v, tb["ll"], tb["grad"], tb["mean"], tb["var"]), noise, fl)
+    sp, spm = np.zeros(truth.NT), np.zeros(truth.NT)
     for k in range(K):
         mk, vk = b.expert(k).compute_test_means_and_variances(None, None, Xt)
         sp, spm = sp + 1.0 / vk, spm + (1.0 / vk) * mk

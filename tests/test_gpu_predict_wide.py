@@ -29,12 +29,10 @@ outside the tree is read.
 import numpy as np
 import pytest
 
+import accuracy
 import truth
-import truth_ard as ta
-import truth_matern as tm
-from conftest import synth
+from accuracy import Report
 from cugp_amd import capi
-from test_gpu_accuracy import Report
 
 pytestmark = [pytest.mark.gpu,
               pytest.mark.skipif(not truth.EXTENDED, reason="numpy.longdouble is not an extended-precision type here")]
@@ -42,7 +40,6 @@ pytestmark = [pytest.mark.gpu,
 LD = truth.LD
 TILE = 128
 TUNE_PRED_CHUNK, TUNE_COV_SPLIT = 19, 20                            # kernels.h TUNE_*
-HP_BCM_WIDE = [0.9, 0.2, -1.0]
 
 
 @pytest.fixture(scope="module")
@@ -69,42 +66,45 @@ def tile_rows(nt):
     return [(r, slice(r * TILE, min(nt, (r + 1) * TILE))) for r in range(-(-nt // TILE))]
 
 
-def hold_prediction(rep, tag, g, X, y, Xt, tmean, tvar, tcov, sn2, noise, fl, F):
-    """cugp_predict and cugp_predict_cov (with and without noise, every tile form) at the wide test points against
-    the truth, reported per 128-row test tile."""
+def hold_prediction(rep, g, c):
+    """cugp_predict and cugp_predict_cov (with and without noise, every tile form) at the wide test points of the
+    case c (accuracy.wide) against the truth, reported per 128-row test tile."""
+    X, y, Xt, tmean, tvar, tcov, noise, fl = c["X"], c["y"], c["Xt"], c["tm"], c["tv"], c["tcov"], c["noise"], c["floor"]
     nt = len(Xt)
     tcn = tcov.copy()
-    tcn[np.arange(nt), np.arange(nt)] += sn2
+    tcn[np.arange(nt), np.arange(nt)] += c["cov"].sn2
     m, v = g.compute_test_means_and_variances(X, y, Xt)
     for r, sl in tile_rows(nt):
-        rep.add("%smean_r%d" % (tag, r), np.max(np.abs(m[sl].astype(LD) - tmean[sl])), noise["mean"], fl["mean"], F)
-        rep.add("%svar_r%d" % (tag, r), np.max(np.abs(v[sl].astype(LD) - tvar[sl])), noise["var"], fl["var"], F)
+        rep.add("mean_r%d" % r, np.max(np.abs(m[sl].astype(LD) - tmean[sl])), noise["mean"], fl["mean"])
+        rep.add("var_r%d" % r, np.max(np.abs(v[sl].astype(LD) - tvar[sl])), noise["var"], fl["var"])
     try:
         for form, value in cov_forms(nt):
             if value is not None:
                 g.set_tuning(TUNE_COV_SPLIT, value)
             for with_noise, tc in ((True, tcn), (False, tcov)):
                 mj, cov = g.compute_test_joint(X, y, Xt, with_noise=with_noise)
-                assert same_bits(mj, m), (tag, form, with_noise)        # the mean has cugp_predict's bits
-                assert np.array_equal(cov, cov.T), (tag, form, with_noise)
+                assert same_bits(mj, m), (form, with_noise)             # the mean has cugp_predict's bits
+                assert np.array_equal(cov, cov.T), (form, with_noise)
                 err = np.abs(cov.astype(LD) - tc)
                 for r, sl in tile_rows(nt):
-                    rep.add("%scov_%s_%s_r%d" % (tag, "noise" if with_noise else "latent", form, r), np.max(err[sl]),
-                            noise["var"], fl["cov"], F)
+                    rep.add("cov_%s_%s_r%d" % ("noise" if with_noise else "latent", form, r), np.max(err[sl]),
+                            noise["var"], fl["cov"])
     finally:
         g.set_tuning(TUNE_COV_SPLIT, 0, own=False)                  # back to the process default (test_tuning_key_forms)
 
 
 # ------------------------------------------------------------------ 1. prediction and joint covariance
-_TRUTH = {}
-
-
-def se_truth(name):
-    """The longdouble truth of a live case, once per module (it does not depend on the test points)."""
-    if name not in _TRUTH:
-        X, y, _, hp = truth.live_inputs(name)
-        _TRUTH[name] = truth.Truth(X, y, hp, keep=False)
-    return _TRUTH[name]
+def hold_wide(gp_mod, oracle, tag, family, name, nt, **handle):
+    """One family's wide case on a handle Covsum(n, d, **handle): the shared body of the three tests below."""
+    c = accuracy.wide(oracle, family, name, nt)
+    rep = Report("%s/nt%d" % (tag, nt), c["cov"])
+    g = gp_mod.Covsum(*c["X"].shape, **handle)
+    if handle:                                                      # as the family's own tests create their handles:
+        g.set_data(c["X"], c["y"])                                  # data first; the SE handle binds it on first use
+    g.set_loghyperparam(c["cov"].hp)
+    hold_prediction(rep, g, c)
+    g.close()
+    rep.check()
 
 
 @pytest.mark.parametrize("name,nt", [(c, nt) for c, nts in truth.WIDE_CASES.items() for nt in nts])
@@ -112,82 +112,38 @@ def test_wide_se(gp_mod, oracle, name, nt):
     """truth.WIDE_CASES: n65 (nt > n, the covariance product's k range is one block), n300_d17 (two feature chunks
     through k_cross), n384_cond1e6, n515_dense (the product splits in two over k) at 129 / 200 / 257 test points, and
     n1025_dense (a split of four) at 200."""
-    X, y, Xt, hp = truth.wide_inputs(name, nt)
-    t = se_truth(name)
-    tmean, tvar = t.predict(Xt)
-    tcov = t.joint(Xt, with_noise=False)[1]
-    noise, _, _ = truth.noise_level(oracle, X, y, hp, Xt, t.ll, t.grad, tmean, tvar)
-    fl = truth.floors(truth.scales(hp, t.ll, t.grad, tmean))
-    rep = Report("%s/nt%d" % (name, nt))
-    g = gp_mod.Covsum(*X.shape)
-    g.set_loghyperparam(hp)
-    hold_prediction(rep, "", g, X, y, Xt, tmean, tvar, tcov, t.sn2, noise, fl, truth.F)
-    g.close()
-    rep.check()
+    hold_wide(gp_mod, oracle, name, "se", name, nt)
 
 
 def test_wide_ard(gp_mod, oracle):
-    """cross_body<ARD> and predict_cov_finish_body<ARD>: n257_d3 with truth_ard's length scales, 200 test points."""
-    X, y, _, hp = ta.ard_inputs("n257_d3")
-    Xt = truth.wide_points(X, truth.WIDE_NT_FAMILY, ta.ARD_CASES["n257_d3"][5])
-    t = ta.TruthARD(X, y, hp)
-    tmean, tvar = t.predict(Xt)
-    tcov = t.joint(Xt, with_noise=False)[1]
-    noise, _, _ = ta.noise_level_ard(oracle, X, y, hp, Xt, t.ll, t.grad, tmean, tvar)
-    fl = ta.floors_ard(ta.scales_ard(hp, t.ll, t.grad, tmean))
-    rep = Report("ard_n257_d3/nt%d" % len(Xt))
-    g = gp_mod.Covsum(X.shape[0], X.shape[1], ard=True)
-    g.set_data(X, y)
-    g.set_loghyperparam(hp)
-    hold_prediction(rep, "", g, X, y, Xt, tmean, tvar, tcov, t.sn2, noise, fl, ta.F_ARD)
-    g.close()
-    rep.check()
+    """cross_body<ARD> and predict_cov_finish_body<ARD>: n257_d3 with ARD_CASES' length scales, 200 test points."""
+    name = truth.WIDE_FAMILY_CASES["ard"]
+    hold_wide(gp_mod, oracle, "ard_" + name, "ard", name, truth.WIDE_NT_FAMILY, ard=True)
 
 
 def test_wide_matern52(gp_mod, oracle):
     """cross_body<., MATERN52> and predict_cov_finish_body<., MATERN52>: n300_d17 at nu = 5/2, 200 test points."""
-    kind = tm.MATERN52
-    X, y, Xt, hp = truth.wide_inputs("n300_d17", truth.WIDE_NT_FAMILY)
-    t = tm.TruthMatern(X, y, hp, kind)
-    tmean, tvar = t.predict(Xt)
-    tcov = t.joint(Xt, with_noise=False)[1]
-    noise = tm.noise_level_matern(oracle, X, y, hp, Xt, kind, t, tmean, tvar)[0]
-    fl = truth.floors(truth.scales(hp, t.ll, t.grad, tmean))
-    rep = Report("matern52_n300_d17/nt%d" % len(Xt))
-    g = gp_mod.Covsum(X.shape[0], X.shape[1], kernel=kind)
-    g.set_data(X, y)
-    g.set_loghyperparam(hp)
-    hold_prediction(rep, "", g, X, y, Xt, tmean, tvar, tcov, t.sn2, noise, fl, tm.F_MATERN)
-    g.close()
-    rep.check()
+    name = truth.WIDE_FAMILY_CASES["matern52"]
+    hold_wide(gp_mod, oracle, "matern52_" + name, "matern52", name, truth.WIDE_NT_FAMILY, kernel=truth.MATERN52)
 
 
-@pytest.mark.parametrize("N,K", [(3 * 300, 3), (5 * 261 + 2, 5)], ids=["3x300", "5-uneven-1307"])
+@pytest.mark.parametrize("N,K", truth.WIDE_BCM, ids=["3x300", "5-uneven-1307"])
 def test_wide_bcm(gp_mod, oracle, N, K):
     """Three 300-row experts as a group and the uneven 5-expert split of 1307 rows at 200 test points: the batched
     (blockIdx.y) launches of k_cross, k_predict_gemm and k_predict_finish through cugp_bcm_predict, and once more in
     passes of 64 test points (tuning key 19 = 1: passes at t0 > 0) through cugp_bcm_predict_allgather in a world of
     one -- both against truth.bcm_truth, the yardstick from the oracle's BCM with the rows permuted inside each expert
     (as tests/golden/make_truth.py does for bcm3x1500)."""
-    d, hp, nt = 5, HP_BCM_WIDE, truth.WIDE_NT_FAMILY
-    X, y = synth(N, d=d, seed=N + K, scale=3.0)
-    Xt = truth.wide_points(X, nt, 3.0)
-    tb = truth.bcm_truth(X, y, hp, K, Xt)
-
-    def evaluate(Xp, yp):
-        b = oracle.bcm(Xp, yp, K, hp)
-        try:
-            return (b.loglik()[0], b.grad()) + tuple(b.predict(Xt))
-        finally:
-            b.close()
-    noise, _, _ = truth.noise_level(oracle, X, y, hp, Xt, tb["ll"], tb["grad"], tb["mean"], tb["var"],
-                                    evaluate=evaluate, parts=truth.bcm_rows(N, K))
-    fl = truth.floors(truth.scales(hp, tb["ll"], tb["grad"], tb["mean"]))
-    rep = Report("bcm%dx%d/nt%d" % (K, N, nt))
+    X, y, Xt, cov = truth.wide_bcm_inputs(N, K)
+    nt = len(Xt)
+    tb = truth.bcm_truth(X, y, cov, K, Xt)
+    noise, _, _ = truth.bcm_yardstick(oracle, cov, X, y, K, Xt, tb)
+    fl = truth.floors(cov, truth.scales(cov, tb["ll"], tb["grad"], tb["mean"]))
+    rep = Report("bcm%dx%d/nt%d" % (K, N, nt), cov)
     b = gp_mod.BCM.split(X, y, K)
     try:
         assert b.rows == [r for _, r in truth.bcm_rows(N, K)]
-        b.set_BCM_log_hyperparam(hp)
+        b.set_BCM_log_hyperparam(cov.hp)
         m, v = b.compute_BCM_test_means_and_var(Xt)
         comm = gp_mod.Comm(None, 0, 1, 0)
         try:
@@ -242,7 +198,8 @@ def test_draws(gp_mod, name, with_noise):
     holds C' to Sigma_f (|Sigma_f - C' C'^T|); the draw bound sees what is not linear in Z: a wrong tile read for other
     rows of normals, the mean, the final sum.
     (n515_dense latent: cond(Sigma_f) ~ 1e8 with the default jitter; the bounds are componentwise and hold there.)"""
-    X, y, Xt_all, hp = truth.wide_inputs(name, 257)
+    X, y, Xt_all, cov = truth.wide_inputs(name, 257)
+    hp = cov.hp
     sf2 = float(np.exp(2.0 * hp[1]))
     jitter = 0.0 if with_noise else 1e-8 * sf2                      # sample_posterior's default
     rep = Report("%s/%s" % (name, "noise" if with_noise else "latent"))

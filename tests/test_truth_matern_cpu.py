@@ -1,8 +1,8 @@
-"""CPU checks of the Matern truth (tests/truth_matern.py), of its yardstick, of the factor F_MATERN and of the K-entry
-bound -- everything tests/test_gpu_matern.py leans on.
+"""CPU checks of the Matern truth (truth.Truth with the truth.Matern descriptor), of its yardstick, of the factor
+F_MATERN and of the K-entry bound (tests/truth_matern.py) -- everything tests/test_gpu_matern.py leans on.
 
-  1. the closed forms of TruthMatern against the general Matern expression through scipy.special.kv;
-  2. TruthMatern.grad against a central difference of TruthMatern.ll in longdouble: the only independent check of the
+  1. the closed forms of truth.matern_kernel against the general Matern expression through scipy.special.kv;
+  2. the truth's gradient against a central difference of its LL in longdouble: the only independent check of the
      derivative formulas;
   3. F_MATERN = the next power of two at or above twice the largest stand-in ratio over the case list, both kinds;
   4. every case's yardstick under the cap;
@@ -11,6 +11,7 @@ bound -- everything tests/test_gpu_matern.py leans on.
 import numpy as np
 import pytest
 
+import accuracy
 import truth
 import truth_matern as tm
 from conftest import synth
@@ -32,14 +33,14 @@ def test_closed_forms_agree_with_the_bessel_expression(kind):
     r = np.geomspace(0.1, 10.0, 200)
     a = np.sqrt(2 * nu) * r
     sf2 = 1.7
-    kf, dk = tm.kernel_ld((r.astype(LD)) ** 2, LD(sf2), kind)
+    kf, dk = truth.matern_kernel((r.astype(LD)) ** 2, LD(sf2), kind)
     c = sf2 * 2.0 ** (1 - nu) / gamma(nu)
     kb, db = c * a ** nu * kv(nu, a), c * a ** (nu + 1) * kv(nu - 1, a)
     tol = (10.0 ** np.maximum(1.0, np.abs(np.log10(a))) + 8) * EPS
     ek, ed = np.abs(kb - kf) / kf, np.abs(db - dk) / dk
     print("kind %d: k %.3e, dk %.3e of tolerance (largest ratio)" % (kind, float(np.max(ek / tol)), float(np.max(ed / tol))))
     assert np.all(ek <= tol) and np.all(ed <= tol)
-    k0, d0 = tm.kernel_ld(np.zeros(1, dtype=LD), LD(sf2), kind)
+    k0, d0 = truth.matern_kernel(np.zeros(1, dtype=LD), LD(sf2), kind)
     assert k0[0] == LD(sf2) and d0[0] == 0
 
 
@@ -54,13 +55,13 @@ def test_gradient_is_the_derivative_of_ll(kind):
     X, y = synth(n, d=d, seed=n, scale=4.0)
     hp = [0.9, 0.3, -1.0]
     h = 2.0 ** -20
-    t = tm.TruthMatern(X, y, hp, kind)
+    t = truth.Truth(X, y, truth.Matern(hp, kind))
     gs = np.max(np.abs(t.grad))
     tol = 100 * (h * h + truth.EPS_LD / h * float(abs(t.ll) / gs))
     for k in range(3):
         lo, hi = list(hp), list(hp)
         lo[k], hi[k] = hp[k] - h, hp[k] + h
-        num = (tm.TruthMatern(X, y, lo, kind).ll - tm.TruthMatern(X, y, hi, kind).ll) / (LD(hi[k]) - LD(lo[k]))
+        num = (truth.Truth(X, y, truth.Matern(lo, kind)).ll - truth.Truth(X, y, truth.Matern(hi, kind)).ll) / (LD(hi[k]) - LD(lo[k]))
         err = float(abs(num - t.grad[k]) / gs)
         print("kind %d g%d: formula %.15g, central difference %.15g, |diff| / max|g| %.3e (tolerance %.3e)"
               % (kind, k, float(t.grad[k]), float(num), err, tol))
@@ -71,30 +72,21 @@ def test_gradient_is_the_derivative_of_ll(kind):
 def table(oracle):
     """Stand-in ratios and yardsticks of every case and kind, all eight orderings -- computed once."""
     out = {}
-    for name in tm.MATERN_CASES:
+    for name in truth.MATERN_CASES:
         for kind in tm.KINDS:
-            X, y, Xt, hp = tm.matern_inputs(name)
-            t = tm.TruthMatern(X, y, hp, kind)
-            m, v = t.predict(Xt)
-            rows = truth.solve_rows(len(y))
-            noise, first, rest, ns = tm.noise_level_matern(oracle, X, y, hp, Xt, kind, t, m, v, rows)
-            fl = truth.floors(truth.scales(hp, t.ll, t.grad, m))
-            st = tm.standin_matern(X, y, hp, Xt, kind, solve=True)
-            se = truth.errors(*st[:4], t.ll, t.grad, m, v)
-            ss = truth.solve_errors(st[4], st[5], t, rows)
-            ratio = {q: se[q] / max(noise[q], fl[q]) for q in tm.QUANTITIES}
-            rs = {q: ss[q] / max(ns[q], 4 * EPS) for q in truth.SOLVE_QUANTITIES}
+            c = out[name, kind] = accuracy.live(oracle, tm.KIND_NAMES[kind], name)
+            ratio, rs = accuracy.standin_ratios(c)
             print("STANDIN-MATERN %-13s %-8s " % (name, tm.KIND_NAMES[kind])
                   + "  ".join("%s %.2f" % kv for kv in list(ratio.items()) + list(rs.items()))
-                  + "  | yardstick " + " ".join("%s %.1e" % kv for kv in noise.items()))
-            out[name, kind] = dict(ratio=ratio, rs=rs, noise=noise, first=first, rest=rest, fl=fl)
+                  + "  | yardstick " + " ".join("%s %.1e" % kv for kv in c["noise"].items()))
     return out
 
 
 def test_case_list_is_live_cases_from_n65_up():
-    assert tm.MATERN_CASES == ("n65", "n257_d3", "n300_d17", "n515_d33", "n515_dense", "n384_cond1e6", "n1025_dense",
-                               "n1300_d6")
-    assert all(tm.matern_inputs(c)[0].shape[0] == truth.LIVE_CASES[c][0] for c in tm.MATERN_CASES)
+    assert truth.MATERN_CASES == ("n65", "n257_d3", "n300_d17", "n515_d33", "n515_dense", "n384_cond1e6", "n1025_dense",
+                                  "n1300_d6")
+    assert all(truth.family_inputs(f, c)[0].shape[0] == truth.LIVE_CASES[c][0] for c in truth.MATERN_CASES
+               for f in tm.KIND_NAMES.values())
 
 
 def test_F_MATERN_is_what_the_rule_gives(table):
@@ -102,25 +94,20 @@ def test_F_MATERN_is_what_the_rule_gives(table):
     yardstick ratio over the case list, both kinds, all eight orderings -- measured here, on the CPU; F_SOLVE covers
     alpha and K^-1 likewise.  The ratios are those of the BLAS this runs on (docs/ACCURACY.md has the table of the build
     it was measured with)."""
-    worst = max(max(c["ratio"].values()) for c in table.values())
-    worst_solve = max(max(c["rs"].values()) for c in table.values())
-    rule = 1
-    while rule < 2 * worst:
-        rule *= 2
+    worst = max(max(accuracy.standin_ratios(c)[0].values()) for c in table.values())
+    worst_solve = max(max(accuracy.standin_ratios(c)[1].values()) for c in table.values())
+    rule = truth.factor_rule(worst)
     print("largest stand-in ratio %.2f -> F_MATERN by the rule %d (set: %d); alpha / K^-1 %.2f (F_SOLVE %d)"
-          % (worst, rule, tm.F_MATERN, worst_solve, tm.F_SOLVE))
-    assert tm.F_MATERN == rule, (worst, rule, tm.F_MATERN)
-    assert 2 * worst_solve <= tm.F_SOLVE, (worst_solve, tm.F_SOLVE)
+          % (worst, rule, truth.F_MATERN, worst_solve, truth.F_SOLVE))
+    assert truth.F_MATERN == rule, (worst, rule, truth.F_MATERN)
+    assert 2 * worst_solve <= truth.F_SOLVE, (worst_solve, truth.F_SOLVE)
 
 
 def test_yardsticks_under_the_cap(table):
     """No case has to be left out: every yardstick is far under truth.YARDSTICK_CAP, and the oracle on the data as given
     is no outlier among the permuted evaluations."""
     for (name, kind), c in table.items():
-        for q in tm.QUANTITIES:
-            scale = c["fl"][q] / (4 * EPS)
-            assert c["noise"][q] <= tm.YARDSTICK_CAP * scale, (name, kind, q, c["noise"][q], scale)
-            assert c["first"][q] <= tm.F_MATERN * max(c["rest"][q], c["fl"][q]), (name, kind, q, c["first"][q], c["rest"][q])
+        accuracy.assert_yardstick_is_sane(c, (name, kind))
 
 
 @pytest.mark.parametrize("kind", tm.KINDS)
@@ -143,12 +130,12 @@ def test_fp64_entry_formula_inside_the_bound(kind):
     mantissa left, do not occur in the cases; asserted.)"""
     assert tm.K_BOUND == {tm.MATERN32: (7.0, 0.5, 11.0), tm.MATERN52: (10.0, 1.0, 11.0)}
     worst = 0.0
-    for name in tm.MATERN_CASES:
-        X, y, Xt, hp = tm.matern_inputs(name)
+    for name in truth.MATERN_CASES:
+        X, y, Xt, hp = truth.live_inputs(name)
         l2, sf2, _ = truth.hyper(hp)
         d = X.shape[1]
         for A in (X, Xt):
-            true = tm.kernel_ld(truth.sqdist(A, X) / l2, sf2, kind)[0]
+            true = truth.matern_kernel(truth.sqdist(A, X) / l2, sf2, kind)[0]
             got = tm.entry_fp64(tm.sqdist64(A, X), np.exp(2 * hp[0]), np.exp(2 * hp[1]), kind)[0]
             bound = tm.k_entry_bound(tm.a_of(A, X, hp, kind), d, kind)
             assert float(true.min()) > 1e-290
