@@ -39,27 +39,47 @@ def gather_rows_per_rank(K, world):
 
 
 def gather_row_index(k, world, per):
-    """Row of expert k in the gathered [W * per, 4] tensor: rank k mod W owns it as its (k // W)-th expert."""
+    """Row of expert k in the gathered [W * per, 1 + nh] tensor: rank k mod W owns it as its (k // W)-th expert."""
     return expert_owner(k, world) * per + k // world
 
 
-def _default_factory(n, d, device, kernel="se"):
-    return _gp.Covsum(n, d, device, kernel=kernel)
+def _default_factory(n, d, device, kernel="se", ard=False):
+    return _gp.Covsum(n, d, device, kernel=kernel, ard=ard)
 
 
 class ShardedBCM:
     """K experts over `world` ranks.  `experts` is a list of K (X_k, y_k) pairs; only the ones this
     rank owns are touched (the rest may be None).  group=None with world==1 needs no process group.
     kernel: "se" | "matern32" | "matern52" for the library's experts -- every rank must pass the same one (the library
-    cannot check that without a collective); an injected expert_factory makes its own experts and is not told."""
+    cannot check that without a collective); an injected expert_factory makes its own experts and is not told.
+    ard=True (every rank alike): ARD experts, nh = d + 2 shared hyper-parameters, every row buffer 1 + nh wide; an
+    injected expert_factory is then called as factory(n, d, device, ard=True).  d: the input dimension, only needed on
+    a rank that sees none of the experts' data (it sizes the rows)."""
 
     def __init__(self, experts, rank=0, world=1, device=0, group=None, expert_factory=None, comm_device=None,
-                 kernel="se"):
+                 kernel="se", ard=False, d=None):
         self.K = len(experts)
         self.kernel = _gp.KERNEL_NAMES[_gp.kernel_kind(kernel)]
+        self.ard = bool(ard)
+        if self.ard and self.kernel != "se":
+            raise ValueError("ard=True is squared-exponential only (ARD x Matern is not built)")
+        self.nh = 3
+        if self.ard:
+            if d is None:
+                seen = [e for e in experts if e is not None]
+                if not seen:
+                    raise ValueError("ard=True on a rank without any expert's data needs d")
+                d = np.asarray(seen[0][0]).shape[1]
+            self.nh = int(d) + 2
+        self._w = 1 + self.nh
         self.rank, self.world, self.group = rank, world, group
         self.mine = [k for k in range(self.K) if expert_owner(k, world) == rank]
-        factory = expert_factory or (lambda n, d, dev: _default_factory(n, d, dev, self.kernel))
+        if expert_factory is None:
+            factory = lambda n, d, dev: _default_factory(n, d, dev, self.kernel, self.ard)
+        elif self.ard:
+            factory = lambda n, d, dev: expert_factory(n, d, dev, ard=True)
+        else:
+            factory = expert_factory
         self.local = {}
         self._group = None
         if expert_factory is None and len(self.mine) > 1:
@@ -67,7 +87,8 @@ class ShardedBCM:
             # (csrc/bcm.cpp, group.h); self.local holds borrowed per-expert views for prediction
             data = [(np.ascontiguousarray(experts[k][0], dtype=np.float64),
                      np.ascontiguousarray(experts[k][1], dtype=np.float64)) for k in self.mine]
-            self._group = _gp.BCM([X.shape[0] for X, _ in data], data[0][0].shape[1], device, kernel=self.kernel)
+            self._group = _gp.BCM([X.shape[0] for X, _ in data], data[0][0].shape[1], device, kernel=self.kernel,
+                                  ard=self.ard)
             for i, (X, y) in enumerate(data):
                 self._group.set_expert_data(i, X, y)
                 self.local[self.mine[i]] = self._group.expert(i)
@@ -79,7 +100,7 @@ class ShardedBCM:
                 e = factory(X.shape[0], X.shape[1], device)
                 e.set_data(X, y)
                 self.local[k] = e
-        self.hp = np.zeros(3)
+        self.hp = np.zeros(self.nh)
         self.predict_form = None          # "library" / "torch": the path the last predict() took
         # host-clock seconds spent in this rank's evaluations (enqueue -> rows in place) and in the exchange
         # (staging copy, all-reduce, copy back), summed since reset_timers(): what a multi-GPU run is diagnosed from
@@ -88,8 +109,8 @@ class ShardedBCM:
             comm_device = torch.device("cuda", device) if (world > 1 and dist.get_backend(group) == "nccl") \
                 else torch.device("cpu")
         self.comm_device = comm_device
-        self._rows = torch.zeros((self.K, 4), dtype=torch.float64, device=comm_device)
-        self._send = torch.zeros((self.K, 4), dtype=torch.float64, device=comm_device)
+        self._rows = torch.zeros((self.K, self._w), dtype=torch.float64, device=comm_device)
+        self._send = torch.zeros((self.K, self._w), dtype=torch.float64, device=comm_device)
         if comm_device.type == "cuda":
             torch.cuda.current_stream(comm_device).synchronize()      # the zeros are there before the library writes rows
         # RCCL path: the per-expert rows go from the evaluation's result buffer straight into this device tensor
@@ -99,7 +120,7 @@ class ShardedBCM:
             X, y = (np.ascontiguousarray(a, dtype=np.float64) for a in experts[self.mine[0]])
             for e in self.local.values():
                 e.close()
-            self._group = _gp.BCM([X.shape[0]], X.shape[1], device, kernel=self.kernel)
+            self._group = _gp.BCM([X.shape[0]], X.shape[1], device, kernel=self.kernel, ard=self.ard)
             self._group.set_expert_data(0, X, y)
             self.local = {self.mine[0]: self._group.expert(0)}
         # Lean exchange (round 6): the library writes this rank's rows into a compact [per, 4] device tensor, ONE
@@ -158,11 +179,11 @@ class ShardedBCM:
                 raise self._comm_error
         self._lean = form == "allgather"
         if self._lean:
-            self._mine_dev = torch.zeros((self._per, 4), dtype=torch.float64, device=comm_device)
-            self._all_dev = torch.zeros((world * self._per, 4), dtype=torch.float64, device=comm_device)
+            self._mine_dev = torch.zeros((self._per, self._w), dtype=torch.float64, device=comm_device)
+            self._all_dev = torch.zeros((world * self._per, self._w), dtype=torch.float64, device=comm_device)
             self._slots = list(range(len(self.mine)))               # expert mine[i] -> row i of _mine_dev
             if comm_device.type == "cuda":
-                self._all_host = torch.zeros((world * self._per, 4), dtype=torch.float64).pin_memory()
+                self._all_host = torch.zeros((world * self._per, self._w), dtype=torch.float64).pin_memory()
                 torch.cuda.current_stream(comm_device).synchronize()
             else:
                 self._all_host = self._all_dev
@@ -192,14 +213,14 @@ class ShardedBCM:
         self.t_device = self.t_collective = 0.0
 
     def loglik_grad(self):
-        """-> (sum_k LL_k, sum_k grad_k, per-expert LL[K]); one collective of K x 4 doubles."""
+        """-> (sum_k LL_k, sum_k grad_k, per-expert LL[K]); one collective of K x (1 + nh) doubles."""
         t0 = time.perf_counter()
         if self._comm is not None:
             # (device and collective time are not separable on the host clock here: they are one stream sequence;
             #  t_collective keeps what the host spends beyond the call)
-            g = self._comm.loglik_grad_allgather(self._group, self._per)
+            g = self._comm.loglik_grad_allgather(self._group, self._per, self.nh)
             t1 = time.perf_counter()
-            out = np.stack([g[gather_row_index(k, self.world, self._per)] for k in range(self.K)]) if self.K else np.zeros((0, 4))
+            out = np.stack([g[gather_row_index(k, self.world, self._per)] for k in range(self.K)]) if self.K else np.zeros((0, self._w))
             self.t_device += t1 - t0
             self.t_collective += time.perf_counter() - t1
             return self._ordered_sum(out)
@@ -216,7 +237,7 @@ class ShardedBCM:
                 self._all_host.copy_(self._all_dev, non_blocking=True)
                 torch.cuda.current_stream(self.comm_device).synchronize()
             g = self._all_host.numpy()
-            out = np.stack([g[gather_row_index(k, self.world, self._per)] for k in range(self.K)]) if self.K else np.zeros((0, 4))
+            out = np.stack([g[gather_row_index(k, self.world, self._per)] for k in range(self.K)]) if self.K else np.zeros((0, self._w))
             self.t_device += t1 - t0
             self.t_collective += time.perf_counter() - t1
             return self._ordered_sum(out)
@@ -240,8 +261,8 @@ class ShardedBCM:
         return self._ordered_sum(out)
 
     def _local_rows(self):
-        """[K, 4] host rows: this rank's experts' (LL, gradient), zeros elsewhere."""
-        rows = np.zeros((self.K, 4))
+        """[K, 1 + nh] host rows: this rank's experts' (LL, gradient), zeros elsewhere."""
+        rows = np.zeros((self.K, self._w))
         if self._group is not None:
             rows[self.mine] = self._group.loglik_grad_rows()
         else:
@@ -254,7 +275,7 @@ class ShardedBCM:
         return rows
 
     def _ordered_sum(self, out):
-        ll, g = 0.0, np.zeros(3)
+        ll, g = 0.0, np.zeros(self.nh)
         for k in range(self.K):                   # expert order, as BCM.cpp:161-197
             ll = ll + out[k, 0]
             g = out[k, 1:].copy() if k == 0 else g + out[k, 1:]
@@ -293,7 +314,7 @@ class ShardedBCM:
     def cg_solve(self, budget=100):
         """cg_solve(BCM) (distributed_ver1.cpp:13-232) -- the library's host loop on the all-reduced
         objective; every rank runs it on identical numbers, so no hyper-parameter broadcast."""
-        theta, trace = _gp.cg_minimize(self.objective, self.hp, budget)
+        theta, trace = (_gp.cg_minimize_n if self.ard else _gp.cg_minimize)(self.objective, self.hp, budget)
         self.set_loghyper(theta)
         return trace
 

@@ -115,6 +115,16 @@ SIGNATURES = {
     "cugp_bcm_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     "cugp_bcm_predict_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp]),
     "cugp_bcm_cg_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_bcm_create_ard": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_split_ard": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_num_hyper": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_bcm_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_bcm_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_bcm_loglik_grad_ard": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
+    "cugp_bcm_loglik_grad_rows_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_bcm_loglik_grad_rows_device_ard": (C.c_int, [C.c_void_p, C.c_void_p, _ip, C.c_int]),
+    "cugp_bcm_loglik_grad_allgather_ard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp]),
+    "cugp_bcm_cg_solve_ard": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

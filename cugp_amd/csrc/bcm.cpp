@@ -10,6 +10,7 @@
 // first result is fetched.  Sums are taken in expert order on the host either way, so the result does
 // not depend on completion order.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -32,11 +33,55 @@ struct cugp_bcm {
     std::vector<cugp_gp*> experts;   // global order k = 0..K-1
     std::vector<int> rows;
     int d = 0;
-    double hp[3] = {0, 0, 0};
+    // ARD (cugp_bcm_create_ard; for life): every expert is an ARD handle, nh = d + 2, and the rows of an evaluation are
+    // {LL, g[nh]}.  Every body below runs at the row width 1 + nh -- 4 for the isotropic calls, whose bits it keeps.
+    bool ard = false;
+    int nh = 3;
+    std::vector<double> hp = {0, 0, 0};
     int kernel = 0;                  // CUGP_KERNEL_* of every expert, for life
     Scratch pred_host{nullptr, 0, true};   // pinned: [expert][mean nt | variance nt] of the prediction in flight
     std::vector<hipEvent_t> pred_ev; // cugp_bcm_predict_rows_enqueue: "rows written" per stream that wrote some
 };
+
+namespace {
+
+// the argument checks of the 3-entry calls and their _ard twins, before any device call (cugp_capi.cpp: refuse_ard /
+// want_ard are the handles' counterparts)
+int refuse_ard_bcm(const cugp_bcm* b, const char* call, const char* use)
+{
+    if (!b->ard) return CUGP_OK;
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: the BCM is ARD (d + 2 hyper-parameters); use %s", call, use);
+    return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+}
+
+int want_ard_bcm(const cugp_bcm* b, int nh, const char* call, bool pointers_ok = true)
+{
+    char buf[256];
+    if (!b || !pointers_ok || nh < 3) {
+        snprintf(buf, sizeof buf, "%s: null argument or nh < 3", call);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    if (!b->ard) {
+        snprintf(buf, sizeof buf, "%s: the BCM is isotropic (3 hyper-parameters); create it with cugp_bcm_create_ard, or use %.*s",
+                 call, (int)strlen(call) - 4, call);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    if (nh != b->nh) {
+        snprintf(buf, sizeof buf, "%s: nh = %d, the BCM has d + 2 = %d hyper-parameters", call, nh, b->nh);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    return CUGP_OK;
+}
+
+int expert_fetch(cugp_bcm* b, cugp_gp* e, double* ll, double* g)
+{
+    return b->ard ? cugp_loglik_grad_fetch_ard(e, ll, g, b->nh) : cugp_loglik_grad_fetch(e, ll, g);
+}
+
+int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel, bool ard, cugp_bcm** out);
+
+}  // namespace
 
 extern "C" {
 
@@ -54,12 +99,28 @@ int cugp_bcm_create_multi(int ndev, const int* devices, int nexperts, const int*
 int cugp_bcm_create_kernel(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel,
                            cugp_bcm** out)
 {
+    return bcm_create(ndev, devices, nexperts, rows, d, kernel, false, out);
+}
+
+// every expert an ARD handle (cugp_create_ard, SE): nh = d + 2 hyper-parameters, the _ard calls below
+int cugp_bcm_create_ard(int ndev, const int* devices, int nexperts, const int* rows, int d, cugp_bcm** out)
+{
+    return bcm_create(ndev, devices, nexperts, rows, d, CUGP_KERNEL_SE, true, out);
+}
+
+}  // extern "C"
+
+namespace {
+int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel, bool ard, cugp_bcm** out)
+{
     if (!out || ndev <= 0 || !devices || nexperts <= 0 || !rows || d <= 0) return CUGP_ERR_INVALID;
     if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52) return CUGP_ERR_INVALID;
     cugp_bcm* b = new (std::nothrow) cugp_bcm;
     if (!b) return CUGP_ERR_NOMEM;
     b->d = d;
     b->kernel = kernel;
+    b->ard = ard;
+    if (ard) { b->nh = d + 2; b->hp.assign(b->nh, 0.0); }
     // Common padded size (identity padding) so that the experts can share launches -- unless their row counts
     // differ by more than a tile or ~6 %: then padding the small ones would cost more than it gains.
     int nmax = 0, nmin = rows[0];
@@ -76,7 +137,8 @@ int cugp_bcm_create_kernel(int ndev, const int* devices, int nexperts, const int
     for (int k = 0; k < nexperts; k++) {
         DeviceSet& ds = b->sets[k % nsets];
         cugp_gp* g = nullptr;
-        int rc = cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
+        int rc = ard ? cugp_create_ard_padded(rows[k], d, ds.device, pad_to, &g)
+                     : cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
         if (rc) { cugp_bcm_destroy(b); return rc; }
         // several experts on one device already fill each other's idle time; the extra streams only cost launches
         if (nexperts > nsets) cugp_set_overlap(g, 0);
@@ -98,20 +160,9 @@ int cugp_bcm_create_kernel(int ndev, const int* devices, int nexperts, const int
     return CUGP_OK;
 }
 
-int cugp_bcm_create(int nexperts, const int* rows, int d, int device, cugp_bcm** out)
-{
-    return cugp_bcm_create_multi(1, &device, nexperts, rows, d, out);
-}
-
 // BCM.cpp:85-110 -- expert k gets rows [k*floor(N/K), ...), the last one also the remainder
-int cugp_bcm_create_split_multi(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
-                                cugp_bcm** out)
-{
-    return cugp_bcm_create_split_kernel(X, y, N, D, K, ndev, devices, CUGP_KERNEL_SE, out);
-}
-
-int cugp_bcm_create_split_kernel(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
-                                 int kernel, cugp_bcm** out)
+int bcm_create_split(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices, int kernel,
+                     bool ard, cugp_bcm** out)
 {
     if (!X || !y || N <= 0 || D <= 0 || K <= 0 || K > N) return CUGP_ERR_INVALID;
     if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52) return CUGP_ERR_INVALID;
@@ -123,13 +174,39 @@ int cugp_bcm_create_split_kernel(const double* X, const double* y, int N, int D,
         rows[k] = (k == K - 1) ? (N - start) : part;
         start += part;
     }
-    int rc = cugp_bcm_create_kernel(ndev, devices, K, rows.data(), D, kernel, out);
+    int rc = bcm_create(ndev, devices, K, rows.data(), D, kernel, ard, out);
     if (rc) return rc;
     for (int k = 0; k < K; k++) {
         rc = cugp_bcm_set_expert_data(*out, k, X + (size_t)off[k] * D, y + off[k]);
         if (rc) { cugp_bcm_destroy(*out); *out = nullptr; return rc; }
     }
     return CUGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int cugp_bcm_create(int nexperts, const int* rows, int d, int device, cugp_bcm** out)
+{
+    return cugp_bcm_create_multi(1, &device, nexperts, rows, d, out);
+}
+
+int cugp_bcm_create_split_multi(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
+                                cugp_bcm** out)
+{
+    return cugp_bcm_create_split_kernel(X, y, N, D, K, ndev, devices, CUGP_KERNEL_SE, out);
+}
+
+int cugp_bcm_create_split_kernel(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
+                                 int kernel, cugp_bcm** out)
+{
+    return bcm_create_split(X, y, N, D, K, ndev, devices, kernel, false, out);
+}
+
+int cugp_bcm_create_split_ard(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices,
+                              cugp_bcm** out)
+{
+    return bcm_create_split(X, y, N, D, K, ndev, devices, CUGP_KERNEL_SE, true, out);
 }
 
 int cugp_bcm_create_split(const double* X, const double* y, int N, int D, int K, int device, cugp_bcm** out)
@@ -175,21 +252,53 @@ int cugp_bcm_set_expert_data(cugp_bcm* b, int k, const double* X, const double* 
     return cugp_set_data(b->experts[k], X, y);
 }
 
-int cugp_bcm_set_loghyper(cugp_bcm* b, const double hp[3])
+// ---- hyper-parameters and evaluation: the 3-entry calls and their _ard twins are argument checks (refuse_ard_bcm /
+// want_ard_bcm) in front of one body over the BCM's nh entries and rows of 1 + nh doubles ----
+static int bcm_set_theta(cugp_bcm* b, const double* hp)
 {
-    if (!b || !hp) return CUGP_ERR_INVALID;
-    for (int i = 0; i < 3; i++) b->hp[i] = hp[i];
+    b->hp.assign(hp, hp + b->nh);
     for (cugp_gp* g : b->experts) {
-        int rc = cugp_set_loghyper(g, b->hp);
+        int rc = b->ard ? cugp_set_loghyper_ard(g, b->hp.data(), b->nh) : cugp_set_loghyper(g, b->hp.data());
         if (rc) return rc;
     }
     return CUGP_OK;
 }
 
+int cugp_bcm_set_loghyper(cugp_bcm* b, const double hp[3])
+{
+    if (!b || !hp) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard_bcm(b, "cugp_bcm_set_loghyper", "cugp_bcm_set_loghyper_ard")) return rc;
+    return bcm_set_theta(b, hp);
+}
+
 int cugp_bcm_get_loghyper(const cugp_bcm* b, double hp[3])
 {
     if (!b || !hp) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard_bcm(b, "cugp_bcm_get_loghyper", "cugp_bcm_get_loghyper_ard")) return rc;
     for (int i = 0; i < 3; i++) hp[i] = b->hp[i];
+    return CUGP_OK;
+}
+
+int cugp_bcm_num_hyper(const cugp_bcm* b, int* nh)
+{
+    if (!b || !nh) return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_num_hyper: null argument");
+    *nh = b->nh;
+    return CUGP_OK;
+}
+
+int cugp_bcm_nh(const cugp_bcm* b) { return b ? b->nh : 0; }
+int cugp_bcm_is_ard(const cugp_bcm* b) { return b && b->ard ? 1 : 0; }
+
+int cugp_bcm_set_loghyper_ard(cugp_bcm* b, const double* hp, int nh)
+{
+    if (const int rc = want_ard_bcm(b, nh, "cugp_bcm_set_loghyper_ard", hp != nullptr)) return rc;
+    return bcm_set_theta(b, hp);
+}
+
+int cugp_bcm_get_loghyper_ard(const cugp_bcm* b, double* hp, int nh)
+{
+    if (const int rc = want_ard_bcm(b, nh, "cugp_bcm_get_loghyper_ard", hp != nullptr)) return rc;
+    for (int i = 0; i < nh; i++) hp[i] = b->hp[i];
     return CUGP_OK;
 }
 
@@ -202,11 +311,11 @@ static void bcm_drain(cugp_bcm* b)
     for (DeviceSet& ds : b->sets) {
         if (ds.grouped_now && ds.group) {
             lk.assign(ds.idx.size(), 0.0);
-            gk3.assign(3 * ds.idx.size(), 0.0);
+            gk3.assign((size_t)b->nh * ds.idx.size(), 0.0);
             (void)cugp_group_fetch(ds.group, lk.data(), gk3.data());
         } else {
-            double l, g3[3];
-            for (int k : ds.idx) (void)cugp_loglik_grad_fetch(b->experts[k], &l, g3);
+            double l;
+            for (int k : ds.idx) (void)expert_fetch(b, b->experts[k], &l, nullptr);
         }
         ds.grouped_now = false;
     }
@@ -233,40 +342,54 @@ static int bcm_enqueue_all(cugp_bcm* b)
 
 // rows[k] = {LL_k, g_k[0..2]} for every expert of this handle, k in global order (what a multi-process BCM
 // all-reduces across ranks)
-int cugp_bcm_loglik_grad_rows(cugp_bcm* b, double* rows)
+static int bcm_rows(cugp_bcm* b, double* rows)
 {
-    if (!b || !rows) return CUGP_ERR_INVALID;
     int rc = bcm_enqueue_all(b);
     if (rc) return rc;
+    const size_t nh = (size_t)b->nh, w = 1 + nh;
     std::vector<double> lk, gk3;
     for (DeviceSet& ds : b->sets) {
         const size_t n = ds.idx.size();
         lk.assign(n, 0.0);
-        gk3.assign(3 * n, 0.0);
+        gk3.assign(nh * n, 0.0);
         if (ds.grouped_now) {
             if ((rc = cugp_group_fetch(ds.group, lk.data(), gk3.data()))) { ds.grouped_now = false; bcm_drain(b); return rc; }
             ds.grouped_now = false;
         } else {
             for (size_t i = 0; i < n; i++)
-                if ((rc = cugp_loglik_grad_fetch(b->experts[ds.idx[i]], &lk[i], &gk3[3 * i]))) { bcm_drain(b); return rc; }
+                if ((rc = expert_fetch(b, b->experts[ds.idx[i]], &lk[i], &gk3[nh * i]))) { bcm_drain(b); return rc; }
         }
         for (size_t i = 0; i < n; i++) {
             const size_t k = (size_t)ds.idx[i];
-            rows[4 * k] = lk[i];
-            for (int j = 0; j < 3; j++) rows[4 * k + 1 + j] = gk3[3 * i + j];
+            rows[w * k] = lk[i];
+            for (size_t j = 0; j < nh; j++) rows[w * k + 1 + j] = gk3[nh * i + j];
         }
     }
     return CUGP_OK;
+}
+
+int cugp_bcm_loglik_grad_rows(cugp_bcm* b, double* rows)
+{
+    if (!b || !rows) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard_bcm(b, "cugp_bcm_loglik_grad_rows", "cugp_bcm_loglik_grad_rows_ard")) return rc;
+    return bcm_rows(b, rows);
+}
+
+// rows[k] = {LL_k, g_k[0 .. nh - 1]}
+int cugp_bcm_loglik_grad_rows_ard(cugp_bcm* b, double* rows, int nh)
+{
+    if (const int rc = want_ard_bcm(b, nh, "cugp_bcm_loglik_grad_rows_ard", rows != nullptr)) return rc;
+    return bcm_rows(b, rows);
 }
 
 // The same payload left ON THE DEVICE for a collective that never touches the host (RCCL all-reduce over
 // xGMI in cugp_amd/bcm.py): row slot[k] of dev_rows ([.][4] doubles, device memory of the handle's first device,
 // e.g. a zeroed buffer with one row per expert of the WHOLE model) receives {LL_k, g_k} of local expert k.
 // Returns when the rows are in place (the evaluation itself is the wait); single-device handles only.
-int cugp_bcm_loglik_grad_rows_device(cugp_bcm* b, double* dev_rows, const int* slot)
+static int bcm_rows_device(cugp_bcm* b, double* dev_rows, const int* slot)
 {
-    if (!b || !dev_rows || !slot) return CUGP_ERR_INVALID;
     if (b->sets.size() != 1) return CUGP_ERR_INVALID;
+    const size_t nh = (size_t)b->nh, w = 1 + nh, srow = b->ard ? 8 + nh : 8;
     {   // dev_rows must be device memory of the handle's device (a host pointer or another GPU's buffer would fault
         // inside the copy kernels, or silently land elsewhere)
         hipPointerAttribute_t at;
@@ -287,8 +410,9 @@ int cugp_bcm_loglik_grad_rows_device(cugp_bcm* b, double* dev_rows, const int* s
         void* stream = nullptr;
         if ((rc = cugp_group_device_results(ds.group, &dout, &stream))) { bcm_drain(b); return rc; }   // (the group is still in flight: drained as a group)
         for (size_t i = 0; i < n; i++)
-            if ((rc = cugp_copy_device_row(dev_rows + 4 * (size_t)slot[ds.idx[i]], dout + 8 * i, stream))) { bcm_drain(b); return rc; }
-        std::vector<double> lk(n), gk3(3 * n);
+            if ((rc = b->ard ? cugp_pack_result_rows_n(dev_rows + w * (size_t)slot[ds.idx[i]], dout + srow * i, 1, b->nh, 1, stream)
+                             : cugp_copy_device_row(dev_rows + 4 * (size_t)slot[ds.idx[i]], dout + 8 * i, stream))) { bcm_drain(b); return rc; }
+        std::vector<double> lk(n), gk3(nh * n);
         rc = cugp_group_fetch(ds.group, lk.data(), gk3.data());       // waits for the stream: rows are in place
         ds.grouped_now = false;
         if (rc) bcm_drain(b);
@@ -296,17 +420,31 @@ int cugp_bcm_loglik_grad_rows_device(cugp_bcm* b, double* dev_rows, const int* s
     }
     for (size_t i = 0; i < n; i++) {
         cugp_gp* e = b->experts[ds.idx[i]];
-        if ((rc = cugp_copy_result_row(e, dev_rows + 4 * (size_t)slot[ds.idx[i]]))) { bcm_drain(b); return rc; }
+        if ((rc = cugp_copy_result_row(e, dev_rows + w * (size_t)slot[ds.idx[i]]))) { bcm_drain(b); return rc; }
     }
     for (size_t i = 0; i < n; i++) {
-        double l, g3[3];
-        if ((rc = cugp_loglik_grad_fetch(b->experts[ds.idx[i]], &l, g3))) { bcm_drain(b); return rc; }
+        double l;
+        if ((rc = expert_fetch(b, b->experts[ds.idx[i]], &l, nullptr))) { bcm_drain(b); return rc; }
     }
     return CUGP_OK;
 }
 
+int cugp_bcm_loglik_grad_rows_device(cugp_bcm* b, double* dev_rows, const int* slot)
+{
+    if (!b || !dev_rows || !slot) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard_bcm(b, "cugp_bcm_loglik_grad_rows_device", "cugp_bcm_loglik_grad_rows_device_ard")) return rc;
+    return bcm_rows_device(b, dev_rows, slot);
+}
+
+// dev_rows: [.][1 + nh] doubles
+int cugp_bcm_loglik_grad_rows_device_ard(cugp_bcm* b, double* dev_rows, const int* slot, int nh)
+{
+    if (const int rc = want_ard_bcm(b, nh, "cugp_bcm_loglik_grad_rows_device_ard", dev_rows && slot)) return rc;
+    return bcm_rows_device(b, dev_rows, slot);
+}
+
 // The two halves of cugp_bcm_loglik_grad_allgather (comm.cpp) on the BCM's side.  enqueue: all experts in flight, their
-// rows {LL, g} packed into dsend[i][4] (local order) BEHIND the evaluation on ITS stream, which is returned -- whatever
+// rows {LL, g} packed into dsend[i][1 + nh] (local order; 4 doubles for an isotropic BCM) BEHIND the evaluation on ITS stream, which is returned -- whatever
 // the caller enqueues there next (the collective, the copy to the host) needs no host wait in between.  finish: waits
 // for that stream and closes the evaluation (results into the handles, status word checked).
 int cugp_bcm_enqueue_rows_packed(cugp_bcm* b, double* dsend, void** stream)
@@ -320,16 +458,16 @@ int cugp_bcm_enqueue_rows_packed(cugp_bcm* b, double* dsend, void** stream)
     if (ds.grouped_now) {
         const double* dout = nullptr;
         if ((rc = cugp_group_device_results(ds.group, &dout, stream)) ||
-            (rc = cugp_pack_result_rows(dsend, dout, (int)n, *stream))) { bcm_drain(b); return rc; }
+            (rc = cugp_pack_result_rows_n(dsend, dout, (int)n, b->nh, b->ard ? 1 : 0, *stream))) { bcm_drain(b); return rc; }
         return CUGP_OK;
     }
     // experts on streams of their own: every row behind its expert's evaluation; all but the first are waited for
     // here, so that what follows on the first expert's stream finds every row in place
     for (size_t i = 0; i < n; i++)
-        if ((rc = cugp_copy_result_row(b->experts[ds.idx[i]], dsend + 4 * i))) { bcm_drain(b); return rc; }
+        if ((rc = cugp_copy_result_row(b->experts[ds.idx[i]], dsend + (size_t)(1 + b->nh) * i))) { bcm_drain(b); return rc; }
     for (size_t i = 1; i < n; i++) {
-        double l, g3[3];
-        if ((rc = cugp_loglik_grad_fetch(b->experts[ds.idx[i]], &l, g3))) { bcm_drain(b); return rc; }
+        double l;
+        if ((rc = expert_fetch(b, b->experts[ds.idx[i]], &l, nullptr))) { bcm_drain(b); return rc; }
     }
     *stream = cugp_get_stream(b->experts[ds.idx[0]]);
     return CUGP_OK;
@@ -341,36 +479,48 @@ int cugp_bcm_finish_rows(cugp_bcm* b)
     DeviceSet& ds = b->sets[0];
     int rc;
     if (ds.grouped_now) {
-        std::vector<double> lk(ds.idx.size()), gk3(3 * ds.idx.size());
+        std::vector<double> lk(ds.idx.size()), gk3((size_t)b->nh * ds.idx.size());
         rc = cugp_group_fetch(ds.group, lk.data(), gk3.data());
         ds.grouped_now = false;
         if (rc) bcm_drain(b);
         return rc;
     }
-    double l, g3[3];
-    if ((rc = cugp_loglik_grad_fetch(b->experts[ds.idx[0]], &l, g3))) bcm_drain(b);
+    double l;
+    if ((rc = expert_fetch(b, b->experts[ds.idx[0]], &l, nullptr))) bcm_drain(b);
     return rc;
+}
+
+static int bcm_sums(cugp_bcm* b, double* ll, double* g, double* per_expert_ll)
+{
+    const size_t K = b->experts.size(), nh = (size_t)b->nh, w = 1 + nh;
+    std::vector<double> rows(w * K), sg(nh, 0.0);
+    int rc = bcm_rows(b, rows.data());
+    if (rc) return rc;
+    double sll = 0.0;
+    for (size_t k = 0; k < K; k++) {
+        const double l = rows[w * k];
+        const double* gk = &rows[w * k + 1];
+        sll = sll + l;                                   // BCM.cpp:190-194
+        for (size_t i = 0; i < nh; i++) sg[i] = (k == 0) ? gk[i] : sg[i] + gk[i];   // BCM.cpp:161-173
+        if (per_expert_ll) per_expert_ll[k] = l;
+    }
+    if (ll) *ll = sll;
+    if (g)
+        for (size_t i = 0; i < nh; i++) g[i] = sg[i];
+    return CUGP_OK;
 }
 
 int cugp_bcm_loglik_grad(cugp_bcm* b, double* ll, double g[3], double* per_expert_ll)
 {
     if (!b) return CUGP_ERR_INVALID;
-    const size_t K = b->experts.size();
-    std::vector<double> rows(4 * K);
-    int rc = cugp_bcm_loglik_grad_rows(b, rows.data());
-    if (rc) return rc;
-    double sll = 0.0, sg[3] = {0, 0, 0};
-    for (size_t k = 0; k < K; k++) {
-        const double l = rows[4 * k];
-        const double* gk = &rows[4 * k + 1];
-        sll = sll + l;                                   // BCM.cpp:190-194
-        for (int i = 0; i < 3; i++) sg[i] = (k == 0) ? gk[i] : sg[i] + gk[i];   // BCM.cpp:161-173
-        if (per_expert_ll) per_expert_ll[k] = l;
-    }
-    if (ll) *ll = sll;
-    if (g)
-        for (int i = 0; i < 3; i++) g[i] = sg[i];
-    return CUGP_OK;
+    if (const int rc = refuse_ard_bcm(b, "cugp_bcm_loglik_grad", "cugp_bcm_loglik_grad_ard")) return rc;
+    return bcm_sums(b, ll, g, per_expert_ll);
+}
+
+int cugp_bcm_loglik_grad_ard(cugp_bcm* b, double* ll, double* g, int nh, double* per_expert_ll)
+{
+    if (const int rc = want_ard_bcm(b, nh, "cugp_bcm_loglik_grad_ard")) return rc;
+    return bcm_sums(b, ll, g, per_expert_ll);
 }
 
 // Round 5: experts whose inverse quantities are not valid for the current hyper-parameters (a prediction right after
@@ -381,8 +531,8 @@ static int bcm_refresh(cugp_bcm* b)
 {
     for (cugp_gp* e : b->experts)
         if (!cugp_has_inverse(e)) {
-            double ll, g3[3];
-            return cugp_bcm_loglik_grad(b, &ll, g3, nullptr);
+            double ll;
+            return bcm_sums(b, &ll, nullptr, nullptr);   // (at the BCM's own row width: an ARD BCM's nh-wide evaluation)
         }
     return CUGP_OK;
 }
@@ -498,11 +648,33 @@ void bcm_objective(void* ctx, const double th[3], double* f, double g[3])
     if (cugp_bcm_loglik_grad(b, &ll, g, nullptr) != CUGP_OK) { ll = NAN; g[0] = g[1] = g[2] = NAN; }
     *f = -1.0 * ll;
 }
+void bcm_objective_n(void* ctx, const double* th, int nh, double* f, double* g)
+{
+    cugp_bcm* b = (cugp_bcm*)ctx;
+    double ll = NAN;
+    if (bcm_set_theta(b, th) != CUGP_OK || bcm_sums(b, &ll, g, nullptr) != CUGP_OK) {
+        ll = NAN;
+        for (int i = 0; i < nh; i++) g[i] = NAN;
+    }
+    *f = -1.0 * ll;
+}
 }  // namespace
+
+// conjugate gradients over the nh entries of an ARD BCM from its current hyper-parameters; the end point stays set.
+// trace (may be NULL): rows of nh + 1 doubles [theta_0 .. theta_{nh-1}, f]
+int cugp_bcm_cg_solve_ard(cugp_bcm* b, int budget, double* trace, int trace_cap, int* nevals)
+{
+    if (!b) return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_cg_solve_ard: null handle");
+    if (const int rc = want_ard_bcm(b, b->ard ? b->nh : 3, "cugp_bcm_cg_solve_ard")) return rc;
+    std::vector<double> th(b->hp);
+    if (const int rc = cugp_cg_minimize_n(bcm_objective_n, b, th.data(), b->nh, budget, trace, trace_cap, nevals)) return rc;
+    return bcm_set_theta(b, th.data());
+}
 
 int cugp_bcm_cg_solve(cugp_bcm* b, int budget, double* trace, int trace_cap, int* nevals)
 {
     if (!b) return CUGP_ERR_INVALID;
+    if (const int rc = refuse_ard_bcm(b, "cugp_bcm_cg_solve", "cugp_bcm_cg_solve_ard")) return rc;
     double th[3] = {b->hp[0], b->hp[1], b->hp[2]};
     int rc = cugp_cg_minimize(bcm_objective, b, th, budget, trace, trace_cap, nevals);
     if (rc) return rc;

@@ -80,7 +80,8 @@ int hip_fail(const char* what, hipError_t e)
 struct cugp_comm {
     ncclComm_t comm = nullptr;   // null: a world of one without a communicator (nothing to exchange)
     int rank = 0, world = 1, device = 0;
-    Scratch dsend, drecv;                        // [per][4] this rank's rows, [world * per][4] everybody's
+    Scratch dsend, drecv;                        // [per][w] this rank's rows, [world * per][w] everybody's; w = 1 + nh (4, or an ARD BCM's d + 3)
+    size_t send_rows = 0, send_w = 0;            // shape dsend was last zeroed for
     Scratch hrecv{nullptr, 0, true};             // pinned copy of drecv
     // product-of-experts prediction (cugp_bcm_predict_allgather): this rank's block, everybody's, the reduced
     // [mean | var | status words] on the device and pinned, the pinned header {status, local count}
@@ -140,14 +141,17 @@ int cugp_comm_destroy(cugp_comm* c)
 }
 
 // grow-only; nothing of the exchange is in flight between calls
-static int comm_buffers(cugp_comm* c, int per)
+static int comm_buffers(cugp_comm* c, int per, int w)
 {
-    const size_t nsend = (size_t)per * 4;
+    const size_t nsend = (size_t)per * w;
     int rc;
-    if (nsend > c->dsend.cap) {
+    if (nsend > c->dsend.cap || (size_t)w != c->send_w || (size_t)per != c->send_rows) {
         if ((rc = c->dsend.grow(nsend, nullptr))) return rc;
-        const hipError_t e = hipMemset(c->dsend.p, 0, nsend * sizeof(double));   // unused slots: exact zeros, for good
-        if (e != hipSuccess) { c->dsend.release(); return hip_fail("exchange buffers", e); }
+        // unused slots: exact zeros -- for good while the rows keep their shape (an ARD BCM's are wider)
+        const hipError_t e = hipMemset(c->dsend.p, 0, nsend * sizeof(double));
+        if (e != hipSuccess) { c->dsend.release(); c->send_w = c->send_rows = 0; return hip_fail("exchange buffers", e); }
+        c->send_w = (size_t)w;
+        c->send_rows = (size_t)per;
     }
     if ((rc = c->drecv.grow(c->world * nsend, nullptr)) || (rc = c->hrecv.grow(c->world * nsend, nullptr))) return rc;
     return CUGP_OK;
@@ -157,15 +161,15 @@ static int comm_buffers(cugp_comm* c, int per)
 // none), all-gather everybody's rows, -> rows_out[world * per][4]: rank r's i-th expert (global expert r + i * world)
 // in row r * per + i, {LL, g0, g1, g2}; slots beyond a rank's experts are zero.  Everything between the first kernel of
 // the evaluation and the pinned copy of the gathered rows is ONE in-order sequence on the evaluation's stream.
-int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* rows_out)
+// nh: the gradient's entries -- rows of 1 + nh doubles (3 from the isotropic call, d + 2 from the _ard call)
+static int allgather_rows(cugp_bcm* b, cugp_comm* c, int per, int nh, double* rows_out)
 {
-    if (!c || per <= 0 || !rows_out) return CUGP_ERR_INVALID;
     int nlocal = 0;
     if (b && cugp_bcm_num_experts(b, &nlocal)) return CUGP_ERR_INVALID;
     if (nlocal > per) return CUGP_ERR_INVALID;
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail("hipSetDevice", e);
-    int rc = comm_buffers(c, per);
+    int rc = comm_buffers(c, per, 1 + nh);
     if (rc) return rc;
     hipStream_t s = nullptr;
     if (nlocal > 0) {
@@ -173,7 +177,7 @@ int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* r
         if ((rc = cugp_bcm_enqueue_rows_packed(b, c->dsend.p, &sv))) return rc;   // rows packed behind the evaluation, on its stream
         s = (hipStream_t)sv;
     }
-    const size_t nsend = (size_t)per * 4, nall = nsend * c->world;
+    const size_t nsend = (size_t)per * (1 + nh), nall = nsend * c->world;
     const double* src = c->drecv.p;
     if (c->comm) {
         const ncclResult_t r = rccl().AllGather(c->dsend.p, c->drecv.p, nsend, ncclDouble, c->comm, s);
@@ -191,6 +195,29 @@ int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* r
     if (rc) return rc;
     memcpy(rows_out, c->hrecv.p, nall * sizeof(double));
     return CUGP_OK;
+}
+
+int cugp_bcm_loglik_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, double* rows_out)
+{
+    if (!c || per <= 0 || !rows_out) return CUGP_ERR_INVALID;
+    if (cugp_bcm_is_ard(b))
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_loglik_grad_allgather: the BCM is ARD (d + 2 hyper-parameters); use cugp_bcm_loglik_grad_allgather_ard");
+    return allgather_rows(b, c, per, 3, rows_out);
+}
+
+// the same for an ARD BCM: rows {LL, g[nh]}.  nh is explicit because a rank that owns no expert passes b == NULL.
+int cugp_bcm_loglik_grad_allgather_ard(cugp_bcm* b, cugp_comm* c, int per, int nh, double* rows_out)
+{
+    if (!c || per <= 0 || !rows_out || nh < 3)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_loglik_grad_allgather_ard: null argument, per <= 0 or nh < 3");
+    if (b && !cugp_bcm_is_ard(b))
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_loglik_grad_allgather_ard: the BCM is isotropic (3 hyper-parameters); use cugp_bcm_loglik_grad_allgather");
+    if (b && cugp_bcm_nh(b) != nh) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "cugp_bcm_loglik_grad_allgather_ard: nh = %d, the BCM has d + 2 = %d hyper-parameters", nh, cugp_bcm_nh(b));
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    return allgather_rows(b, c, per, nh, rows_out);
 }
 
 static int pred_buffers(cugp_comm* c, size_t rstride, size_t nout)

@@ -93,8 +93,13 @@ void Scratch::release()
 struct GroupCtx {
     Batch bt;                       // device table of the experts' buffers, expert count
     unsigned* tickets = nullptr;    // the experts' step tickets and block-inverse stage counters, contiguous [k][2 nt]
-    double* dout = nullptr;         // results [k][8] on the device ...
-    double* hout = nullptr;         // ... and pinned
+    double* dout = nullptr;         // results [k][row] on the device ...
+    double* hout = nullptr;         // ... and pinned, [k][8]: what k_finalize / the fused k_trace write, and every status word
+    // ARD groups: row = ARD_ROW_GRAD + nh, and hrows is the pinned [k][row] copy k_finalize_ard writes (gradient
+    // evaluations).  The batched k_trtri_block and k_finalize address the pinned rows in 8s, so hout keeps that shape: it
+    // holds the status words of every evaluation and the results of the LL-only ones.
+    int row = 8;
+    double* hrows = nullptr;
     bool overlap = false;           // hand the group's inverse blocks to the lead expert's other streams
     int gcap = 0;                   // barrier workgroups per expert of ONE batched k_trtri_block launch (the experts' smallest share; halved with the overlap)
 };
@@ -282,6 +287,8 @@ Batch B(const cugp_gp* g) { return g->grp ? g->grp->bt : Batch{}; }
 // pinned host buffer the evaluation's results land in: the group's ([expert][8]) or the handle's.  Entries 0..5: LL, the
 // three gradients, y'K^-1y, log|K| (k_finalize); entry 6: set by a kernel whose bounded wait ran out (k_trtri_block)
 double* host_out(const cugp_gp* g) { return g->grp ? g->grp->hout : g->hout; }
+// ... and the one a gradient evaluation's final sums land in: an ARD group's rows are wider than its status rows
+double* host_grad_out(const cugp_gp* g) { return g->grp && g->grp->hrows ? g->grp->hrows : host_out(g); }
 
 // ---- tuning: process defaults (cugp_set_tuning) under a lock, one copy per handle ----
 std::mutex g_tune_mu;
@@ -880,7 +887,7 @@ int record_eval(cugp_gp* g, bool want_grad, const HyperScalars* hd)
         }
         // traces and the final sums in ONE launch: the last block of k_trace finishes the evaluation (kernels.hip)
         launch_trace(g->dX, g->n, g->d, g->npad, cf, g->dKinv, g->dalpha, g->dpart, s, B(g), g->dz, g->dlogdet, g->dout,
-                     host_out(g), tickets + 2 * g->nt);
+                     host_grad_out(g), tickets + 2 * g->nt);
     } else {
         if ((rc = phase_mark(g, 3))) return rc;
         if ((rc = phase_mark(g, 4))) return rc;
@@ -1078,6 +1085,10 @@ int cugp_kernel_kind(const cugp_gp* g, int* kernel)
 }
 
 int cugp_create_ard(int n, int d, int device, cugp_gp** out) { return create_handle(n, d, device, 0, true, out); }
+int cugp_create_ard_padded(int n, int d, int device, int npad_min, cugp_gp** out)
+{
+    return create_handle(n, d, device, npad_min, true, out);
+}
 
 static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel)
 {
@@ -2200,17 +2211,23 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
         if (experts[i]->kernel != experts[0]->kernel)
             return fail(CUGP_ERR_INVALID, "cugp_group_create: the experts have different kernel kinds (one launch serves them all)");
     for (int i = 0; i < k; i++)
-        if (experts[i]->ard) return fail(CUGP_ERR_INVALID, "cugp_group_create: ARD handles cannot be grouped (the exchange rows hold 3 gradients)");
+        if (experts[i]->ard != experts[0]->ard)
+            return fail(CUGP_ERR_INVALID, "cugp_group_create: ARD and isotropic handles in one group (the experts of a group are all ARD or all isotropic)");
     cugp_group* gr = new (std::nothrow) cugp_group;
     if (!gr) return fail(CUGP_ERR_NOMEM, "host allocation");
     gr->experts.assign(experts, experts + k);
     const int nt = experts[0]->nt;
+    const bool ard = experts[0]->ard;
+    const size_t row = ard ? (size_t)ARD_ROW_GRAD + experts[0]->nh : 8;
+    gr->ctx.row = (int)row;
     hipError_t e = hipSetDevice(experts[0]->device);
     if (e == hipSuccess) e = hipMalloc((void**)&gr->dtab, (size_t)k * sizeof(ExpertPtrs));
     if (e == hipSuccess) e = hipMalloc((void**)&gr->ctx.tickets, (size_t)k * ticket_count(nt) * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMalloc((void**)&gr->ctx.dout, (size_t)k * 8 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&gr->ctx.dout, (size_t)k * row * sizeof(double));
     if (e == hipSuccess) e = hipHostMalloc((void**)&gr->ctx.hout, (size_t)k * 8 * sizeof(double), hipHostMallocDefault);
     if (e == hipSuccess) memset(gr->ctx.hout, 0, (size_t)k * 8 * sizeof(double));   // (entry 6 of a row: status word)
+    if (e == hipSuccess && ard) e = hipHostMalloc((void**)&gr->ctx.hrows, (size_t)k * row * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess && ard) memset(gr->ctx.hrows, 0, (size_t)k * row * sizeof(double));
     if (e != hipSuccess) {
         cugp_group_destroy(gr);
         return fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, "cugp_group_create", e);
@@ -2234,6 +2251,7 @@ void cugp_group_destroy(cugp_group* gr)
     if (gr->ctx.tickets) (void)hipFree(gr->ctx.tickets);
     if (gr->ctx.dout) (void)hipFree(gr->ctx.dout);
     if (gr->ctx.hout) (void)hipHostFree(gr->ctx.hout);
+    if (gr->ctx.hrows) (void)hipHostFree(gr->ctx.hrows);
     gr->pred.release();
     delete gr;
 }
@@ -2247,7 +2265,7 @@ static int write_group_table(cugp_group* gr)
     for (int i = 0; i < k; i++) {
         cugp_gp* e = gr->experts[i];
         tab[i] = ExpertPtrs{e->dA, e->dT, e->dU, e->dKinv, e->d16, e->d64, e->dlogdet, e->dy, e->dz, e->dalpha,
-                            e->dw, e->dpart, gr->ctx.dout + (size_t)i * 8, e->dX,
+                            e->dw, e->dpart, gr->ctx.dout + (size_t)i * gr->ctx.row, e->dX,
                             gr->ctx.tickets + (size_t)i * ticket_count(nt), e->n};
     }
     HIPCHK(hipStreamSynchronize(lead->stream));           // a captured graph may still be reading the old table
@@ -2266,7 +2284,9 @@ static bool same_loghyper(const cugp_group* gr)
 }
 
 // Enqueue one evaluation of all experts of the group on the lead expert's stream(s); results stay on the device
-// (ctx.dout, [k][8]) and travel to the pinned ctx.hout behind it.  cugp_group_fetch waits and reads them.
+// (ctx.dout, [k][8], an ARD group's [k][8 + nh]) and travel to the pinned ctx.hout (ctx.hrows) behind it.
+// cugp_group_fetch waits and reads them.  An ARD group reads the lead expert's scalars AND weights (hs_bytes(lead)): the
+// copy in front of the launches -- the node at the head of a captured graph -- takes them from the lead's staging area.
 int cugp_group_enqueue(cugp_group* gr, int want_grad)
 {
     if (!gr) return CUGP_ERR_INVALID;
@@ -2293,7 +2313,7 @@ int cugp_group_enqueue(cugp_group* gr, int want_grad)
         return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
     if (!gr->tab_valid && (rc = write_group_table(gr))) return rc;
     for (cugp_gp* e : gr->experts) e->factor_valid = e->inverse_valid = false;
-    *lead->hhs = scalars(lead);
+    if (!lead->ard) *lead->hhs = scalars(lead);             // (ARD: staged where theta was set, weights included)
     gr->ctx.overlap = lead->tune[TUNE_GROUP_OVERLAP] != 0;
     {   // one batched k_trtri_block launch holds count x G workgroups: G = the experts' smallest reserved share
         int cap = TRTRI_BLOCK_MAXWG;
@@ -2323,7 +2343,16 @@ int cugp_group_fetch(cugp_group* gr, double* ll, double* g)
     HIPCHK(hipStreamSynchronize(lead->stream));
     gr->pending = false;
     bool ok = true;                                           // (every expert's row is read: every status word cleared)
-    for (int i = 0; i < k; i++) ok = read_result_row(gr->experts[i], gr->ctx.hout + (size_t)i * 8, gr->pending_grad) && ok;
+    for (int i = 0; i < k; i++) {
+        double* row = gr->ctx.hout + (size_t)i * 8;
+        if (gr->ctx.hrows && gr->pending_grad) {              // ARD: the gradient row, with the status word of the 8-row
+            double* wide = gr->ctx.hrows + (size_t)i * gr->ctx.row;
+            wide[6] = row[6];
+            row[6] = 0.0;
+            row = wide;
+        }
+        ok = read_result_row(gr->experts[i], row, gr->pending_grad) && ok;
+    }
     if (!ok) {                                                // (see fetch_eval)
         for (cugp_gp* e : gr->experts) discard_eval(e);
         return fail(CUGP_ERR_DEVICE, "a stage barrier of k_trtri_block ran out of polls (the group's evaluation was abandoned)");
@@ -2332,7 +2361,7 @@ int cugp_group_fetch(cugp_group* gr, double* ll, double* g)
         const cugp_gp* e = gr->experts[i];
         ll[i] = e->last_ll;
         if (gr->pending_grad && g)
-            for (int j = 0; j < 3; j++) g[3 * i + j] = e->last_g[j];
+            for (int j = 0; j < e->nh; j++) g[(size_t)e->nh * i + j] = e->last_g[j];
     }
     return CUGP_OK;
 }
@@ -2349,6 +2378,20 @@ int cugp_pack_result_rows(double* dst, const double* src, int count, void* strea
     return CUGP_OK;
 }
 
+// the nh-wide form: rows [count][1 + nh] <- {LL, g[nh]} of every result row of src.  nh = 3: the isotropic [8] rows (the
+// call above); else ARD rows of ARD_ROW_GRAD + nh doubles -- LL from entry 0, the gradient from entry ARD_ROW_GRAD, two 2D
+// copies on `stream`
+int cugp_pack_result_rows_n(double* dst, const double* src, int count, int nh, int ard, void* stream)
+{
+    if (!ard) return nh == 3 ? cugp_pack_result_rows(dst, src, count, stream) : CUGP_ERR_INVALID;
+    if (count <= 0) return CUGP_OK;
+    const size_t dp = (size_t)(1 + nh) * sizeof(double), sp = (size_t)(ARD_ROW_GRAD + nh) * sizeof(double);
+    HIPCHK(hipMemcpy2DAsync(dst, dp, src, sp, sizeof(double), (size_t)count, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpy2DAsync(dst + 1, dp, src + ARD_ROW_GRAD, sp, (size_t)nh * sizeof(double), (size_t)count,
+                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return CUGP_OK;
+}
+
 int cugp_copy_device_row(double* dst, const double* src, void* stream)
 {
     HIPCHK(hipMemcpyAsync(dst, src, 4 * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -2360,6 +2403,7 @@ int cugp_copy_result_row(cugp_gp* g, double* dst)
     if (!g || !dst || !g->pending) return CUGP_ERR_INVALID;
     int rc;
     if ((rc = use_device(g))) return rc;
+    if (g->ard) return cugp_pack_result_rows_n(dst, g->dout, 1, g->nh, 1, g->stream);
     return cugp_copy_device_row(dst, g->dout, g->stream);
 }
 
@@ -2402,8 +2446,8 @@ int cugp_group_eval(cugp_group* gr, int want_grad, double* ll, double* g)
     return rc ? rc : cugp_group_fetch(gr, ll, g);
 }
 
-// device side of the results of the evaluation in flight: [k][8] doubles, row i = {LL, g0, g1, g2, ...} of expert i,
-// valid once everything enqueued on *stream so far has run
+// device side of the results of the evaluation in flight: [k][8] doubles, row i = {LL, g0, g1, g2, ...} of expert i (an
+// ARD group: [k][8 + nh], LL at 0 and the gradient from entry 8), valid once everything enqueued on *stream so far has run
 int cugp_group_device_results(cugp_group* gr, const double** dout, void** stream)
 {
     if (!gr || !dout || !stream) return CUGP_ERR_INVALID;

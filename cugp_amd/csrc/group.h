@@ -19,30 +19,41 @@ struct Scratch {
 
 extern "C" {
 
-// experts must live on one device and agree in padded size and dimension (else CUGP_ERR_INVALID)
+// experts must live on one device and agree in padded size, dimension and kernel kind, and be all ARD or all isotropic
+// (else CUGP_ERR_INVALID)
 int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out);
+// cugp_create_ard with the matrices padded to at least npad_min rows (cugp_create_padded's rule): the experts of an ARD BCM
+int cugp_create_ard_padded(int n, int d, int device, int npad_min, cugp_gp** out);
 void cugp_group_destroy(cugp_group* gr);
 
-// Evaluate all experts at their (common) hyper-parameters; ll[k], g[3k..3k+2] (g may be null when !want_grad).
+// Evaluate all experts at their (common) hyper-parameters; ll[k], g[nh k .. nh k + nh - 1] with nh = 3, or d + 2 for ARD
+// experts (g may be null when !want_grad).
 // Returns CUGP_ERR_INVALID without touching anything when the experts cannot be evaluated as a group right now
 // (different hyper-parameters, profiling on, missing data): the caller then evaluates them one by one.
 int cugp_group_eval(cugp_group* gr, int want_grad, double* ll, double* g);
 // the same in two halves, so the groups of several devices are all in flight before the first result is read
 int cugp_group_enqueue(cugp_group* gr, int want_grad);
 int cugp_group_fetch(cugp_group* gr, double* ll, double* g);
-// device copy of the results of the evaluation in flight ([k][8] doubles: LL, g0, g1, g2, ...) and the stream
+// device copy of the results of the evaluation in flight ([k][8] doubles: LL, g0, g1, g2, ...; ARD experts: [k][8 + nh],
+// LL at 0, the gradient from entry 8) and the stream
 // (hipStream_t) they are ordered on -- for a reduction that stays on the device (RCCL all-reduce)
 int cugp_group_device_results(cugp_group* gr, const double** dout, void** stream);
 // 4 doubles device -> device on `stream` (hipStream_t); the result row of the evaluation a single expert has in flight
 int cugp_copy_device_row(double* dst, const double* src, void* stream);
 // [count][4] <- {LL, g0, g1, g2} of every [8]-double result row of src (a group's device results), one 2D copy on `stream`
 int cugp_pack_result_rows(double* dst, const double* src, int count, void* stream);
+// [count][1 + nh] <- {LL, g[nh]}: the call above for isotropic rows (nh = 3), ARD rows ([8 + nh]) by two 2D copies
+int cugp_pack_result_rows_n(double* dst, const double* src, int count, int nh, int ard, void* stream);
 // error text for cugp_last_error from the other translation units; returns `code`
 int cugp_internal_fail(int code, const char* what);
 // halves of cugp_bcm_loglik_grad_allgather (comm.cpp; defined in bcm.cpp)
+// (dsend: [local expert][1 + nh], nh = the BCM's)
 int cugp_bcm_enqueue_rows_packed(cugp_bcm* b, double* dsend, void** stream);
+int cugp_bcm_nh(const cugp_bcm* b);              // 3, or d + 2 for an ARD BCM; 0 for null
+int cugp_bcm_is_ard(const cugp_bcm* b);
 int cugp_bcm_finish_rows(cugp_bcm* b);
-// {LL, g0, g1, g2} of the evaluation a single expert has in flight -> dst (device), on the expert's stream
+// {LL, g0, g1, g2} of the evaluation a single expert has in flight -> dst (device), on the expert's stream (an ARD
+// expert: {LL, g[nh]}, 1 + nh doubles)
 int cugp_copy_result_row(cugp_gp* gp, double* dst);
 // cugp_predict_cov without the copy to the host (tools/pred_joint_probe.py times the device part with it): Sigma is
 // computed, the handle's stream is waited for, and *dcov / *ld give the device matrix (lower tiles valid, row-major,

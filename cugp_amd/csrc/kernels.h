@@ -74,9 +74,10 @@ struct HyperScalars {              // exp(2*theta) evaluated on the host, as the
 //   ard: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart):
 //        k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd is
 //        then mandatory and read by every pass: the hyper-scalars (ell_sq unused) directly followed by the d weights --
-//        one staging area, one copy.  Same tiles, stores and padding as the isotropic launches; SE only, and single
-//        handles only: an ARD descriptor with batched experts or without hd is a programming error -- asserted, so
-//        checked only in builds without NDEBUG (the library's own build has none); cugp_group_create refuses ARD handles.
+//        one staging area, one copy.  Same tiles, stores and padding as the isotropic launches; SE only.  Batched
+//        experts (build, cross-covariance, trace; not the joint-covariance epilogue) read the GROUP's one copy -- the lead
+//        expert's hd -- since the experts of a group share their hyper-parameters.  An ARD descriptor without hd is a
+//        programming error -- asserted, so checked only in builds without NDEBUG (the library's own build has none).
 struct CovFn {
     int kind = KERNEL_SE;
     bool ard = false;
@@ -188,7 +189,8 @@ int trace_num_blocks(int npad);
 // taken from the experts' table, ticket = tickets[2 nt] of every expert
 // ARD: part[(d + 2) * trace_num_blocks(npad)]; results row out / hout (both mandatory, ARD_ROW_GRAD + d + 2 doubles): [0] LL,
 // [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row), [ARD_ROW_GRAD + c] g_c, c = 0 .. d + 1.  Always two
-// launches (k_trace_ard, k_finalize_ard): there is no fused form of the final sums, and ticket is not used.
+// launches (k_trace_ard, k_finalize_ard): there is no fused form of the final sums, and ticket is not used.  Batched:
+// grids (blocks, experts) and (1, experts); part and out from the table, hout[expert][ARD_ROW_GRAD + d + 2].
 constexpr int ARD_ROW_GRAD = 8;
 void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* alpha,
                   double* part, hipStream_t s, Batch bt = {}, const double* z = nullptr,

@@ -1077,9 +1077,10 @@ __global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int
 
 __global__ __launch_bounds__(256) void k_build_ard(const double* __restrict__ X, int n, int d, int npad,
                                                    const HyperScalars* __restrict__ hd, double* __restrict__ K,
-                                                   int full, unsigned* __restrict__ tickets, unsigned long long* stamp)
+                                                   int full, unsigned* __restrict__ tickets,
+                                                   const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
 {
-    build_body<true>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, nullptr, stamp);
+    build_body<true>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, bt, stamp);
 }
 
 // Matern instantiations: k_build's arguments and everything that rides with it (batched experts, ticket zeroing,
@@ -1139,9 +1140,10 @@ __global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int
 
 __global__ __launch_bounds__(256) void k_cross_ard(const double* __restrict__ X, int n, int d, int npad,
                                                    const double* __restrict__ Xt, int nt, int ntpad,
-                                                   const HyperScalars* __restrict__ hd, double* __restrict__ Ks)
+                                                   const HyperScalars* __restrict__ hd, double* __restrict__ Ks,
+                                                   const ExpertPtrs* __restrict__ bt)
 {
-    cross_body<true>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, nullptr);
+    cross_body<true>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, bt);
 }
 
 template <int KIND>
@@ -2610,12 +2612,18 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize(const double* __restri
 // sums at a time in registers; wave sums by shuffles, the four waves added in a fixed order.
 // Partials: part[c * nblocks + block], c = 0 .. d - 1 the dimensions, d: sum W o K, d + 1: tr W (column-major, so that
 // k_finalize_ard's lanes read a column contiguously).  No fused final sums: k_finalize_ard always follows.
+// bt (batched): blockIdx.y selects the expert -- X, n, K^-1, alpha and the expert's OWN partials from its table entry;
+// hyper-scalars and weights are the group's one copy (hd).  The arithmetic and its order per expert are the single launch's.
 __global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X, int n, int d, int npad,
                                                    const HyperScalars* __restrict__ hd,
                                                    const double* __restrict__ Kinv, const double* __restrict__ alpha,
-                                                   double* __restrict__ part)
+                                                   double* __restrict__ part, const ExpertPtrs* __restrict__ bt)
 {
 #pragma clang fp contract(off)
+    if (bt) {
+        const ExpertPtrs& e = bt[blockIdx.y];
+        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); alpha = GP(e.alpha); part = GP(e.part);
+    }
     const HyperScalars h = *hd;
     const double* __restrict__ wts = ard_weights(hd);
     __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
@@ -2706,12 +2714,19 @@ __global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X,
 // ... ascending, the lanes by wave_sum -- a fixed order whatever the timing.  Results row (out, hout): [0] LL, [4] quad,
 // [5] log|K|, [6] status word, [8 + c] the d + 2 gradient components:
 //   g_c = S_c / 2 (c < d), g_d = (2 s2 - 2 sn2 s3) / 2, g_{d+1} = (2 sn2 s3) / 2   (the last two as k_finalize's g1, g2)
+// bt (batched): grid (1, experts) -- z, n, logdet_part, part and out from the expert's table entry, hout + expert * hstride
 __global__ __launch_bounds__(FIN_THREADS) void k_finalize_ard(const double* __restrict__ z, int npad, int n, int d,
                                                               const double* __restrict__ logdet_part, int nt,
                                                               const double* __restrict__ part, int nblocks,
                                                               const HyperScalars* __restrict__ hd,
-                                                              double* __restrict__ out, double* __restrict__ hout)
+                                                              double* __restrict__ out, double* __restrict__ hout,
+                                                              size_t hstride, const ExpertPtrs* __restrict__ bt)
 {
+    if (bt) {
+        const ExpertPtrs& e = bt[blockIdx.y];
+        z = GP(e.z); n = e.n; logdet_part = GP(e.logdet); part = GP(e.part); out = GP(e.out);
+        hout += (size_t)blockIdx.y * hstride;
+    }
     const HyperScalars h = *hd;
     __shared__ double red[5 * FIN_THREADS];
     finalize_sums<FIN_THREADS, false>(z, npad, n, logdet_part, nt, nullptr, 0, h, out, hout, red);
@@ -2837,14 +2852,14 @@ thread_local const int* t_tune = g_tune_init;
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
 
 // The four passes that evaluate the covariance function launch the instantiation its descriptor names: k_<pass>_ard (its
-// own argument list: everything from cf.hd, no batched experts), else k_<pass> or k_<pass>_matern<KIND>, which share one.
+// own argument list: everything from cf.hd), else k_<pass> or k_<pass>_matern<KIND>, which share one.
 // The table of isotropic instantiations is this macro and nothing else.
 #define CUGP_ISO_KERNEL(cf, stem)                                                        \
     ((cf).kind == KERNEL_MATERN32   ? stem##_matern<KERNEL_MATERN32>                     \
      : (cf).kind == KERNEL_MATERN52 ? stem##_matern<KERNEL_MATERN52> : stem)
-static inline bool ard_single(const CovFn& cf, const Batch& bt)
+static inline bool is_ard(const CovFn& cf)
 {
-    assert(!cf.ard || (cf.hd && !bt.tab && cf.kind == KERNEL_SE));   // (cugp_group_create refuses ARD handles)
+    assert(!cf.ard || (cf.hd && cf.kind == KERNEL_SE));
     return cf.ard;
 }
 
@@ -2852,8 +2867,9 @@ void launch_kbuild(const double* X, int n, int d, int npad, const CovFn& cf, dou
                    Batch bt, unsigned* tickets)
 {
     const dim3 grid(tri_count(npad / KT), bt.count);
-    if (ard_single(cf, bt))
-        hipLaunchKernelGGL(k_build_ard, grid, dim3(256), 0, s, X, n, d, npad, cf.hd, K, full ? 1 : 0, tickets, take_stamp());
+    if (is_ard(cf))
+        hipLaunchKernelGGL(k_build_ard, grid, dim3(256), 0, s, X, n, d, npad, cf.hd, K, full ? 1 : 0, tickets, bt.tab,
+                           take_stamp());
     else
         hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, K, full ? 1 : 0,
                            tickets, bt.tab, take_stamp());
@@ -2871,8 +2887,8 @@ void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, in
                    double* Ks, hipStream_t s, Batch bt)
 {
     const dim3 grid((ntpad / KT) * (npad / KT), bt.count);
-    if (ard_single(cf, bt))
-        hipLaunchKernelGGL(k_cross_ard, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.hd, Ks);
+    if (is_ard(cf))
+        hipLaunchKernelGGL(k_cross_ard, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.hd, Ks, bt.tab);
     else
         hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.h, Ks,
                            bt.tab);
@@ -3122,7 +3138,7 @@ void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, const
                                double jitter, double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s)
 {
     const dim3 grid(tri_count(ntpad / KT));
-    if (ard_single(cf, {}))
+    if (is_ard(cf))
         hipLaunchKernelGGL(k_predict_cov_finish_ard, grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.hd, with_noise ? 1 : 0,
                            jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
     else
@@ -3190,11 +3206,12 @@ void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, cons
                   double* hout, unsigned* ticket)
 {
     const int nblocks = tri_count(npad / KT);
-    if (ard_single(cf, bt)) {                  // always both launches: there is no fused form of the ARD final sums
-        assert(out && hout);
-        hipLaunchKernelGGL(k_trace_ard, dim3(nblocks), dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, alpha, part);
-        hipLaunchKernelGGL(k_finalize_ard, dim3(1), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part, npad / TILE, part,
-                           nblocks, cf.hd, out, hout);
+    if (is_ard(cf)) {                          // always both launches: there is no fused form of the ARD final sums
+        assert(hout && (out || bt.tab));
+        hipLaunchKernelGGL(k_trace_ard, dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, alpha, part,
+                           bt.tab);
+        hipLaunchKernelGGL(k_finalize_ard, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part,
+                           npad / TILE, part, nblocks, cf.hd, out, hout, (size_t)(ARD_ROW_GRAD + d + 2), bt.tab);
         return;
     }
     // the last block takes the final sums where the launch is small (its 256 threads against k_finalize's 1024: at 8192

@@ -49,7 +49,7 @@ class Covsum:
                                                 C.byref(self._h)))
         elif self.ard:
             if npad_min:
-                raise ValueError("an ARD handle cannot be padded (it cannot join a BCM group)")
+                raise ValueError("an ARD handle cannot be padded (BCM(ard=True) pads its own experts)")
             check(capi.lib().cugp_create_ard(self.n, self.d, self.device, C.byref(self._h)))
         else:
             check(capi.lib().cugp_create_padded(self.n, self.d, self.device, int(npad_min), C.byref(self._h)))
@@ -322,11 +322,20 @@ class Comm:
         check(capi.lib().cugp_comm_create(idbuf, Comm.ID_BYTES if unique_id is not None else 0, self.rank, self.world,
                                           self.device, C.byref(self._h)))
 
-    def loglik_grad_allgather(self, bcm, per):
+    def loglik_grad_allgather(self, bcm, per, nh=3):
         """One sharded objective evaluation: this rank's experts (`bcm`: a BCM, or None on a rank that owns none)
-        evaluated, everybody's rows gathered -> [world * per, 4] (rank r's i-th expert in row r * per + i)."""
-        out = np.empty((self.world * int(per), 4))
-        check(capi.lib().cugp_bcm_loglik_grad_allgather(bcm._h if bcm is not None else None, self._h, int(per), ptr(out)))
+        evaluated, everybody's rows gathered -> [world * per, 1 + nh] (rank r's i-th expert in row r * per + i).
+        nh: 3, or an ARD BCM's d + 2 -- explicit, since a rank without experts has no BCM to ask; the _ard call is
+        taken for an ARD BCM and, without a BCM, for nh != 3."""
+        nh = int(nh)
+        out = np.empty((self.world * int(per), 1 + nh))
+        h = bcm._h if bcm is not None else None
+        if bcm.ard if bcm is not None else nh != 3:
+            check(capi.lib().cugp_bcm_loglik_grad_allgather_ard(h, self._h, int(per), nh, ptr(out)))
+        else:
+            if nh != 3:
+                raise ValueError("an isotropic BCM has 3 hyper-parameters, not nh = %d" % nh)
+            check(capi.lib().cugp_bcm_loglik_grad_allgather(h, self._h, int(per), ptr(out)))
         return out
 
     def predict_allgather(self, bcm, per, nexperts, Xt):
@@ -355,15 +364,25 @@ class Comm:
 class BCM:
     """Experts resident on the GPU(s) of this process (class BCM, distributed_gp/BCM.h).  `devices` lists the
     GPUs (expert k on devices[k mod len], cg_solver.cpp:93; default: the one `device`).  `BCM.split` reproduces
-    the reference constructor's row partition (BCM.cpp:85-110)."""
+    the reference constructor's row partition (BCM.cpp:85-110).
+    ard=True: every expert an ARD handle (cugp_bcm_create_ard): the shared hyper-parameter vector is [log l_1 .. log l_d,
+    log sigma_f, log sigma_n] (nh = d + 2), gradients have nh entries, rows and cg_solve traces 1 + nh columns.
+    Squared-exponential only, as Covsum."""
 
-    def __init__(self, rows, d, device=0, devices=None, kernel="se"):
+    def __init__(self, rows, d, device=0, devices=None, kernel="se", ard=False):
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         devs = np.ascontiguousarray([device] if devices is None else list(devices), dtype=np.int32)
         self.rows, self.d, self.device, self.devices = rows.tolist(), int(d), int(devs[0]), devs.tolist()
         self._kind = kernel_kind(kernel)
+        self.ard = bool(ard)
+        self.nh = self.d + 2 if self.ard else 3
+        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
+            raise ValueError("ard=True is squared-exponential only (ARD x Matern is not built)")
         self._h = C.c_void_p()
-        if self._kind != capi.CUGP_KERNEL_SE:
+        if self.ard:
+            check(capi.lib().cugp_bcm_create_ard(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
+                                                 rows.ctypes.data_as(capi._ip), self.d, C.byref(self._h)))
+        elif self._kind != capi.CUGP_KERNEL_SE:
             check(capi.lib().cugp_bcm_create_kernel(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
                                                     rows.ctypes.data_as(capi._ip), self.d, self._kind,
                                                     C.byref(self._h)))
@@ -379,12 +398,12 @@ class BCM:
         return KERNEL_NAMES[k.value]
 
     @classmethod
-    def split(cls, X, y, K, device=0, devices=None, kernel="se"):
+    def split(cls, X, y, K, device=0, devices=None, kernel="se", ard=False):
         X, y = f64(X), f64(y)
         N, D = X.shape
         part = N // K
         rows = [part] * (K - 1) + [N - part * (K - 1)]
-        b = cls(rows, D, device, devices, kernel=kernel)
+        b = cls(rows, D, device, devices, kernel=kernel, ard=ard)
         off = 0
         for k in range(K):
             b.set_expert_data(k, X[off: off + rows[k]], y[off: off + rows[k]])
@@ -407,35 +426,54 @@ class BCM:
         check(capi.lib().cugp_bcm_set_expert_data(self._h, k, ptr(X), ptr(y)))
 
     def set_BCM_log_hyperparam(self, hp):
-        check(capi.lib().cugp_bcm_set_loghyper(self._h, ptr(f64(hp))))
+        hp = f64(hp)
+        if self.ard:
+            if hp.shape != (self.nh,):
+                raise ValueError("expected %d log-hyper-parameters" % self.nh)
+            check(capi.lib().cugp_bcm_set_loghyper_ard(self._h, ptr(hp), self.nh))
+        else:
+            check(capi.lib().cugp_bcm_set_loghyper(self._h, ptr(hp)))
 
     set_BCM_loghyper_eigen = set_BCM_log_hyperparam
 
     def get_loghyperparam(self):
-        out = np.empty(3)
-        check(capi.lib().cugp_bcm_get_loghyper(self._h, ptr(out)))
+        out = np.empty(self.nh)
+        if self.ard:
+            check(capi.lib().cugp_bcm_get_loghyper_ard(self._h, ptr(out), self.nh))
+        else:
+            check(capi.lib().cugp_bcm_get_loghyper(self._h, ptr(out)))
         return out
 
     def loglik_grad(self):
-        """-> (sum LL, sum grad[3], per-expert LL) over the experts of this GPU."""
+        """-> (sum LL, sum grad[nh], per-expert LL) over the experts of this GPU."""
         ll = C.c_double()
-        g = np.empty(3)
+        g = np.empty(self.nh)
         per = np.empty(len(self.rows))
-        check(capi.lib().cugp_bcm_loglik_grad(self._h, C.byref(ll), ptr(g), ptr(per)))
+        if self.ard:
+            check(capi.lib().cugp_bcm_loglik_grad_ard(self._h, C.byref(ll), ptr(g), self.nh, ptr(per)))
+        else:
+            check(capi.lib().cugp_bcm_loglik_grad(self._h, C.byref(ll), ptr(g), ptr(per)))
         return ll.value, g, per
 
     def loglik_grad_rows(self):
-        """-> [K, 4] rows (LL_k, gradient of -LL_k): what a multi-GPU BCM all-reduces."""
-        rows = np.empty((len(self.rows), 4))
-        check(capi.lib().cugp_bcm_loglik_grad_rows(self._h, ptr(rows)))
+        """-> [K, 1 + nh] rows (LL_k, gradient of -LL_k): what a multi-GPU BCM all-reduces."""
+        rows = np.empty((len(self.rows), 1 + self.nh))
+        if self.ard:
+            check(capi.lib().cugp_bcm_loglik_grad_rows_ard(self._h, ptr(rows), self.nh))
+        else:
+            check(capi.lib().cugp_bcm_loglik_grad_rows(self._h, ptr(rows)))
         return rows
 
     def loglik_grad_rows_device(self, dev_rows_ptr, slots):
-        """Leave every local expert's (LL_k, gradient) row in DEVICE memory: row slots[k] of the [., 4] buffer at
+        """Leave every local expert's (LL_k, gradient) row in DEVICE memory: row slots[k] of the [., 1 + nh] buffer at
         dev_rows_ptr (same GPU) -- the payload of an all-reduce that never touches the host."""
         slots = np.ascontiguousarray(slots, dtype=np.int32)
-        check(capi.lib().cugp_bcm_loglik_grad_rows_device(self._h, C.c_void_p(dev_rows_ptr),
-                                                          slots.ctypes.data_as(capi._ip)))
+        if self.ard:
+            check(capi.lib().cugp_bcm_loglik_grad_rows_device_ard(self._h, C.c_void_p(dev_rows_ptr),
+                                                                  slots.ctypes.data_as(capi._ip), self.nh))
+        else:
+            check(capi.lib().cugp_bcm_loglik_grad_rows_device(self._h, C.c_void_p(dev_rows_ptr),
+                                                              slots.ctypes.data_as(capi._ip)))
 
     def expert(self, k):
         """Borrowed view of expert k as a Covsum-like object (prediction, intermediates); owned by the BCM."""
@@ -443,7 +481,7 @@ class BCM:
         check(capi.lib().cugp_bcm_expert(self._h, int(k), C.byref(h)))
         e = Covsum.__new__(Covsum)
         e.n, e.d, e.device, e._h, e._data_key = self.rows[k], self.d, self.devices[k % len(self.devices)], h, None
-        e.ard, e.nh, e._kind = False, 3, self._kind
+        e.ard, e.nh, e._kind = self.ard, self.nh, self._kind
         e.close = lambda: None                    # not ours to destroy
         return e
 
@@ -468,9 +506,11 @@ class BCM:
     get_BCM_negative_log_predprob = staticmethod(Covsum.get_negative_log_predprob)
 
     def cg_solve(self, budget=100):
-        tr = np.zeros((4 * budget + 8, 4))
+        """-> the evaluation trace [n_evals, 1 + nh] = (theta, -LL)."""
+        tr = np.zeros((4 * budget + 8, 1 + self.nh))
         ne = C.c_int()
-        check(capi.lib().cugp_bcm_cg_solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        solve = capi.lib().cugp_bcm_cg_solve_ard if self.ard else capi.lib().cugp_bcm_cg_solve
+        check(solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
         return tr[: ne.value]
 
 

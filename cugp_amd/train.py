@@ -29,6 +29,9 @@ def main():
     ap.add_argument("--backend", default="nccl")
     ap.add_argument("--kernel", default="se", choices=["se", "matern32", "matern52"],
                     help="covariance family of every expert (the same on every rank)")
+    ap.add_argument("--ard", action="store_true",
+                    help="one length scale per input dimension (squared exponential only): the start is "
+                         "[hp0] * d + [hp1, hp2]")
     args = ap.parse_args()
 
     import torch
@@ -51,14 +54,14 @@ def main():
     mine = {k for k in range(args.numchunks) if expert_owner(k, world) == rank}
     shards = dataset.load_shards(args.inputs, args.labels, args.numchunks, rows=None, only=mine)
     experts = [None if s is None else (s[0][:args.rows], s[1][:args.rows]) for s in shards]
-    bcm = ShardedBCM(experts, rank=rank, world=world, device=local, kernel=args.kernel)
-    bcm.set_loghyper(args.hp)
+    bcm = ShardedBCM(experts, rank=rank, world=world, device=local, kernel=args.kernel, ard=args.ard)
+    bcm.set_loghyper([args.hp[0]] * (bcm.nh - 2) + list(args.hp[1:]) if args.ard else args.hp)
     t0 = time.perf_counter()
     trace = bcm.cg_solve(args.budget)
     dt = time.perf_counter() - t0
     if rank == 0:
-        print("\n\n PLEASE-SEE 3 : %f, %f, %f\n" % tuple(bcm.hp))
-        print("TOTAL training time = %f  (%d evaluations, final -LL %.9g)" % (dt, trace.shape[0], trace[-1, 3]))
+        print("\n\n PLEASE-SEE %d : %s\n" % (bcm.nh, ", ".join("%f" % v for v in bcm.hp)))
+        print("TOTAL training time = %f  (%d evaluations, final -LL %.9g)" % (dt, trace.shape[0], trace[-1, -1]))
     if args.test_rows > 0:
         s0 = dataset.load_chunk("%s0.txt" % args.inputs, "%s0.txt" % args.labels)
         Xt, yt = s0[0][args.rows:args.rows + args.test_rows], s0[1][args.rows:args.rows + args.test_rows]

@@ -79,7 +79,8 @@ int cugp_get_loghyper(const cugp_gp *gp, double hp[3]);
  * A handle made by the create call below is ARD for life.  Data, overlap, the log-likelihood, the split enqueue, the
  * predictions (marginal, joint, draws), K, k_test, factor, inverse, alpha, profiling and tuning work on it unchanged; the
  * 3-entry calls (set / get of the hyper-parameters, the gradient calls, the optimisers, the squared-distance
- * intermediate) return CUGP_ERR_INVALID on it and name the call to use.  ARD handles cannot be experts of a BCM group.
+ * intermediate) return CUGP_ERR_INVALID on it and name the call to use.  ARD handles are the experts of an ARD BCM
+ * (cugp_bcm_create_ard below): evaluated as a group of shared launches like isotropic experts.
  * The calls below return CUGP_ERR_INVALID -- before any device call -- for a NULL argument, an isotropic handle, or
  * nh != d + 2.  A theta_c so large that 1 / l_c underflows simply drops dimension c (g_c = 0); one so small that it
  * overflows gives NaN results (the header's convention for a covariance that cannot be factored), not an error.
@@ -322,6 +323,29 @@ int cugp_bcm_predict(cugp_bcm *b, const double *Xt, int nt, double *mean, double
 int cugp_bcm_predict_allgather(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt,
                                double *mean, double *var);
 int cugp_bcm_cg_solve(cugp_bcm *b, int budget, double *trace, int trace_cap, int *nevals);
+/* ---- ARD BCM: every expert an ARD handle (squared exponential, theta as cugp_create_ard's: nh = d + 2 entries shared by
+ *      all experts).  The reference has no counterpart.  The experts run as groups of shared launches, over several
+ *      devices of one process, or sharded one process per GPU, exactly like isotropic experts; only the rows of an
+ *      evaluation are wider: {LL_k, g_k[nh]}, 1 + nh doubles, sums in expert order on the host.
+ * An ARD BCM is ARD for life.  cugp_bcm_num_hyper reports nh (3, or d + 2) for any BCM.  Data, cugp_bcm_expert, the
+ * three predict calls (their rows do not depend on nh) and cugp_bcm_kernel_kind (SE) work on it unchanged.
+ * cugp_bcm_cg_solve_ard: the loop of cugp_cg_minimize_n from the current hyper-parameters; trace rows of nh + 1 doubles.
+ * cugp_bcm_loglik_grad_allgather_ard: rows_out[world * per][1 + nh]; nh is explicit because a rank that owns no expert
+ *      passes b == NULL; still one all-gather on the evaluation's stream and one host wait.
+ * Refusals, all CUGP_ERR_INVALID before any device call, with the call to use in cugp_last_error: the 3-entry calls
+ * (set / get of the hyper-parameters, cugp_bcm_loglik_grad, the rows calls, the all-gather, cugp_bcm_cg_solve) on an ARD
+ * BCM; the _ard calls on an isotropic BCM; a NULL argument; nh != d + 2.  The BCM stays usable after each of them. */
+int cugp_bcm_create_ard(int ndev, const int *devices, int nexperts, const int *rows, int d, cugp_bcm **out);
+int cugp_bcm_create_split_ard(const double *X, const double *y, int N, int D, int K, int ndev, const int *devices,
+                              cugp_bcm **out);
+int cugp_bcm_num_hyper(const cugp_bcm *b, int *nh);
+int cugp_bcm_set_loghyper_ard(cugp_bcm *b, const double *hp, int nh);
+int cugp_bcm_get_loghyper_ard(const cugp_bcm *b, double *hp, int nh);
+int cugp_bcm_loglik_grad_ard(cugp_bcm *b, double *ll, double *g, int nh, double *per_expert_ll /* may be NULL */);
+int cugp_bcm_loglik_grad_rows_ard(cugp_bcm *b, double *rows, int nh);
+int cugp_bcm_loglik_grad_rows_device_ard(cugp_bcm *b, double *dev_rows, const int *slot, int nh);
+int cugp_bcm_loglik_grad_allgather_ard(cugp_bcm *b, cugp_comm *c, int per, int nh, double *rows_out);
+int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap, int *nevals);
 
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);
