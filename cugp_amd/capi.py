@@ -71,6 +71,12 @@ SIGNATURES = {
     "cugp_get_cholesky": (C.c_int, [C.c_void_p, _dp]),
     "cugp_get_K_inverse": (C.c_int, [C.c_void_p, _dp]),
     "cugp_get_alpha": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_set_targets": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_num_targets": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_loglik_grad_targets": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
+    "cugp_predict_targets": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
+    "cugp_get_alpha_targets": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_cg_solve_targets": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_potrf": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_potri": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_chol_and_det": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_int]),

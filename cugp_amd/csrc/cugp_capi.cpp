@@ -176,6 +176,15 @@ struct cugp_gp {
     hipEvent_t cov_ev = nullptr;   // "Sigma written" (this handle's stream -> cov_f's)
     Scratch cov_scr;               // split-k partial products of k_predict_cov
     Scratch samp;                  // draws: normals Z, F = Z C^T (both [ns pad][ntpad]), packed samples
+    // multi-target regression (cugp_set_targets): m further target vectors over the same X and hyper-parameters, all
+    // target-major [tg_mpad][npad] and zero beyond n and beyond m; tg_mpad = m rounded up to 128 (k_predict_gemm's tiles)
+    int tg_m = 0, tg_mpad = 0;
+    double *tg_y = nullptr, *tg_z = nullptr, *tg_a = nullptr;   // Y, Z = Y L^-T, A = Z L^-1 (row t = alpha_t)
+    double *tg_part = nullptr;     // trace partials of the multi-target gradient pass (dpart's size)
+    double *tg_out = nullptr, *tg_hout = nullptr;   // results row [LL, g (nh), LL_t (m)], device and pinned
+    bool tg_valid = false;         // Z, A and tg_row hold for (data, hp, targets) -- read together with inverse_valid
+    std::vector<double> tg_row;
+    Scratch tg_pred;               // cugp_predict_targets: test inputs, Ks, W, variance, partial means, means
 };
 
 namespace {
@@ -1021,6 +1030,7 @@ bool read_result_row(cugp_gp* g, double* row, bool grad)
         const double* gr = row + (g->ard ? ARD_ROW_GRAD : 1);
         for (int i = 0; i < g->nh; i++) g->last_g[i] = gr[i];
         g->inverse_valid = true;
+        g->tg_valid = false;                                 // (a new inverse: the multi-target results are stale)
     }
     return true;
 }
@@ -1175,8 +1185,10 @@ int cugp_destroy(cugp_gp* g)
     if (g->cov_ev) (void)hipEventDestroy(g->cov_ev);
     g->cov_scr.release();
     g->samp.release();
+    g->tg_pred.release();
+    if (g->tg_hout) (void)hipHostFree(g->tg_hout);
     double* bufs[] = {g->dX, g->dy, g->dA, g->dT, g->dU, g->dKinv, g->dz, g->dalpha, g->dw, g->d16, g->dlogdet,
-                      g->dpart, g->dout, g->d64};
+                      g->dpart, g->dout, g->d64, g->tg_y, g->tg_z, g->tg_a, g->tg_part, g->tg_out};
     for (double* p : bufs)
         if (p) (void)hipFree(p);
     if (g->dtickets) (void)hipFree(g->dtickets);
@@ -1782,6 +1794,203 @@ int cugp_get_alpha(cugp_gp* g, double* alpha)
     HIPCHK(hipMemcpyAsync(alpha, g->dalpha, (size_t)g->n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipStreamSynchronize(g->stream));
     return CUGP_OK;
+}
+
+// ---------------------------------------------------------------- multi-target regression
+// m target vectors over the handle's inputs and hyper-parameters: everything that depends on the targets is N^2 work
+// behind ONE factorisation and inverse (the handle's own evaluation, untouched).  Argument errors come first, then "no
+// device" (a process without a GPU never looks into the handle), then what only the handle can tell.
+namespace {
+int tg_invalid(const char* call, const char* what)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", call, what);
+    return fail(CUGP_ERR_INVALID, buf);
+}
+
+int tg_device(const char* call)
+{
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) == hipSuccess && cnt > 0) return CUGP_OK;
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: no HIP device visible (libcugp has no CPU fallback)", call);
+    return fail(CUGP_ERR_NODEVICE, buf);
+}
+
+// the checks every evaluating call shares, behind its own argument checks
+int tg_ready(const cugp_gp* g, const char* call)
+{
+    if (const int rc = tg_device(call)) return rc;
+    if (g->tg_m <= 0) return tg_invalid(call, "no targets set (cugp_set_targets)");
+    return CUGP_OK;
+}
+
+// Z, A, the gradient of the summed objective and the final sums for the current (data, hp, targets): the handle's own
+// evaluation first (whichever route cugp_loglik_grad takes; nothing of it is touched), then four launches on its stream
+// and ONE host wait.
+int eval_targets(cugp_gp* g)
+{
+    int rc;
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;
+    if (g->tg_valid && g->inverse_valid) return CUGP_OK;
+    if ((rc = use_device(g))) return rc;
+    TuneScope ts(g);
+    hipStream_t s = g->stream;
+    launch_predict_gemm(g->tg_y, g->dT, g->tg_z, g->npad, g->tg_mpad / TILE, g->nt, s);       // Z = Y L^-T
+    launch_targets_alpha(g->tg_z, g->dU, g->tg_a, g->npad, g->tg_m, s);                        // A = Z L^-1
+    CovFn cf;
+    if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+    launch_trace_targets(g->dX, g->n, g->d, g->npad, cf, g->dKinv, g->tg_a, g->tg_m, g->tg_part, s);
+    launch_finalize_targets(g->tg_z, g->npad, g->n, g->d, g->tg_m, g->last_logdet, g->tg_part, cf, g->tg_out, g->tg_hout, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    g->tg_row.assign(g->tg_hout, g->tg_hout + 1 + g->nh + g->tg_m);
+    g->tg_valid = true;
+    return CUGP_OK;
+}
+
+// f = -sum_t LL_t and its gradient at th (NaN where the evaluation fails)
+void targets_objective(void* ctx, const double* th, int nh, double* f, double* gr)
+{
+    cugp_gp* g = (cugp_gp*)ctx;
+    if (set_theta(g, th) == CUGP_OK && eval_targets(g) == CUGP_OK) {
+        *f = -1.0 * g->tg_row[0];
+        std::copy(g->tg_row.begin() + 1, g->tg_row.begin() + 1 + nh, gr);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nh, NAN);
+    }
+}
+}  // namespace
+
+int cugp_set_targets(cugp_gp* g, const double* Y, int m)
+{
+    const char* call = "cugp_set_targets";
+    if (!g || !Y) return tg_invalid(call, "null argument");
+    if (m <= 0) return tg_invalid(call, "m must be positive");
+    int rc;
+    if ((rc = tg_device(call))) return rc;
+    if (!g->have_data) return tg_invalid(call, "no training data set (cugp_set_data comes first: it supplies X)");
+    if ((rc = use_device(g))) return rc;
+    if ((rc = fetch_eval(g))) return rc;
+    HIPCHK(hipStreamSynchronize(g->stream));
+    g->tg_valid = false;
+    const int mpad = (m + TILE - 1) / TILE * TILE;
+    const size_t cnt = (size_t)mpad * g->npad, row = (size_t)1 + g->nh + mpad;
+    if (mpad != g->tg_mpad) {
+        for (double** p : {&g->tg_y, &g->tg_z, &g->tg_a, &g->tg_out}) {
+            if (*p) (void)hipFree(*p);
+            *p = nullptr;
+        }
+        if (g->tg_hout) (void)hipHostFree(g->tg_hout);
+        g->tg_hout = nullptr;
+        g->tg_m = g->tg_mpad = 0;
+        if ((rc = ensure(&g->tg_y, cnt)) || (rc = ensure(&g->tg_z, cnt)) || (rc = ensure(&g->tg_a, cnt)) ||
+            (rc = ensure(&g->tg_out, row)))
+            return rc;
+        HIPCHK(hipHostMalloc((void**)&g->tg_hout, row * sizeof(double), hipHostMallocDefault));
+        g->tg_mpad = mpad;
+    }
+    if ((rc = ensure(&g->tg_part, (size_t)g->nblocks_trace * g->nh))) return rc;
+    hipStream_t s = g->stream;
+    HIPCHK(hipMemsetAsync(g->tg_y, 0, cnt * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(g->tg_z, 0, cnt * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(g->tg_a, 0, cnt * sizeof(double), s));
+    HIPCHK(hipMemcpy2DAsync(g->tg_y, (size_t)g->npad * sizeof(double), Y, (size_t)g->n * sizeof(double),
+                            (size_t)g->n * sizeof(double), m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    g->tg_m = m;
+    return CUGP_OK;
+}
+
+int cugp_num_targets(const cugp_gp* g, int* m)
+{
+    if (!g || !m) return tg_invalid("cugp_num_targets", "null argument");
+    *m = g->tg_m;
+    return CUGP_OK;
+}
+
+int cugp_loglik_grad_targets(cugp_gp* g, double* ll, double* gr, int nh, double* ll_each)
+{
+    const char* call = "cugp_loglik_grad_targets";
+    if (!g) return tg_invalid(call, "null handle");
+    if (nh < 3) return tg_invalid(call, "nh is not the handle's (cugp_num_hyper)");
+    int rc;
+    if ((rc = tg_ready(g, call))) return rc;
+    if (nh != g->nh) return tg_invalid(call, "nh is not the handle's (cugp_num_hyper)");
+    if ((rc = eval_targets(g))) return rc;
+    const double* r = g->tg_row.data();
+    if (ll) *ll = r[0];
+    if (gr) std::copy(r + 1, r + 1 + nh, gr);
+    if (ll_each) std::copy(r + 1 + nh, r + 1 + nh + g->tg_m, ll_each);
+    return CUGP_OK;
+}
+
+int cugp_get_alpha_targets(cugp_gp* g, double* alpha)
+{
+    const char* call = "cugp_get_alpha_targets";
+    if (!g || !alpha) return tg_invalid(call, "null argument");
+    int rc;
+    if ((rc = tg_ready(g, call))) return rc;
+    if ((rc = eval_targets(g))) return rc;
+    HIPCHK(hipMemcpy2DAsync(alpha, (size_t)g->n * sizeof(double), g->tg_a, (size_t)g->npad * sizeof(double),
+                            (size_t)g->n * sizeof(double), g->tg_m, hipMemcpyDeviceToHost, g->stream));
+    HIPCHK(hipStreamSynchronize(g->stream));
+    return CUGP_OK;
+}
+
+// Means of every target and (var given) the variance, which no target enters: cugp_predict's own k_cross, k_predict_gemm
+// and k_predict_finish launches, unchanged, give it; the means are A Ks^T (launch_targets_mean).  One pass over the nt test
+// points, as cugp_predict.
+int cugp_predict_targets(cugp_gp* g, const double* Xt, int nt, double* mean, double* var)
+{
+    const char* call = "cugp_predict_targets";
+    if (!g || !Xt || !mean) return tg_invalid(call, "null argument");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    int rc;
+    if ((rc = tg_ready(g, call))) return rc;
+    if ((rc = eval_targets(g))) return rc;                          // (a stale handle is re-evaluated first)
+    TuneScope ts(g);
+    const int m = g->tg_m, ntpad = (nt + TILE - 1) / TILE * TILE, split = targets_mean_split(g->npad);
+    const size_t nxt = (((size_t)nt * g->d + 15) / 16) * 16, nks = (size_t)ntpad * g->npad;
+    const size_t np = (size_t)split * ((m + 63) / 64 * 64) * ntpad, nm = (size_t)m * nt;
+    hipStream_t s = g->stream;
+    if ((rc = g->tg_pred.grow(nxt + 2 * nks + 2 * (size_t)ntpad + np + nm, s))) return rc;
+    double* dXt = g->tg_pred.p;
+    double* dKs = dXt + nxt;
+    double* dW = dKs + nks;
+    double* dm1 = dW + nks;
+    double* dv = dm1 + ntpad;
+    double* dP = dv + ntpad;
+    double* dM = dP + np;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * g->d * sizeof(double), hipMemcpyHostToDevice, s));
+    CovFn cf;
+    if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+    launch_kcross(g->dX, g->n, g->d, g->npad, dXt, nt, ntpad, cf, dKs, s);
+    if (var) {
+        launch_predict_gemm(dKs, g->dT, dW, g->npad, ntpad / TILE, g->nt, s);
+        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, nt, cf.h, dm1, dv, s);
+    }
+    launch_targets_mean(g->tg_a, dKs, dP, g->npad, m, nt, ntpad, dM, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(mean, dM, nm * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return fail(CUGP_ERR_DEVICE, "cugp_predict_targets", e); }
+    return CUGP_OK;
+}
+
+// conjugate gradients on the multi-target objective from the current hyper-parameters (cugp_cg_minimize_n over the handle's
+// nh entries; trace rows of 1 + nh); the end point stays set, as cugp_cg_solve leaves it
+int cugp_cg_solve_targets(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
+{
+    const char* call = "cugp_cg_solve_targets";
+    if (!g) return tg_invalid(call, "null handle");
+    int rc;
+    if ((rc = tg_ready(g, call))) return rc;
+    std::vector<double> th(g->theta);
+    if ((rc = cugp_cg_minimize_n(targets_objective, g, th.data(), g->nh, budget, trace, trace_cap, nevals))) return rc;
+    return set_theta(g, th.data());
 }
 
 // ---------------------------------------------------------------- stand-alone LA

@@ -202,6 +202,25 @@ constexpr int ticket_count(int nt) { return 2 * nt + 1; }
 void launch_finalize(const double* z, int npad, int n, const double* logdet_part, int nt, const double* part,
                      int nblocks, HyperScalars h, double* out, double* hout, hipStream_t s,
                      const HyperScalars* hd = nullptr, Batch bt = {});   // hout: pinned host copy of the results ([expert][8]) or null
+// ---- multi-target regression (cugp_set_targets): everything target-major [mpad][npad], zero beyond n and beyond m ----
+// Z = Y L^-T is launch_predict_gemm(Y, T, Z, ...) as it stands (mpad a multiple of 128).
+// A[t][j] = sum_{k >= j} Z[t][k] U[j][k]: row t = alpha_t = K^-1 y_t (64-row target tiles: the first (m + 63) / 64 of them)
+void launch_targets_alpha(const double* Z, const double* U, double* A, int npad, int m, hipStream_t s);
+// gradient traces of the summed objective, W = m K^-1 - sum_t alpha_t alpha_t^T, K^-1 read once: partial sums per block in
+// launch_trace's layouts (isotropic part[3 * nblocks], ARD part[(d + 2) * nblocks]; nblocks = trace_num_blocks(npad))
+void launch_trace_targets(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* A,
+                          int m, double* part, hipStream_t s);
+// one workgroup: out / hout (pinned) [0] LL = sum_t LL_t, [1 + c] the nh components of the gradient of -LL (nh = 3, ARD
+// d + 2), [1 + nh + t] LL_t = -0.5 (z_t'z_t + logdet + n * 1.83787); logdet NaN (no factor): every entry NaN
+void launch_finalize_targets(const double* Z, int npad, int n, int d, int m, double logdet, const double* part,
+                             const CovFn& cf, double* out, double* hout, hipStream_t s);
+// mean[t * nt + i] = sum_k A[t][k] Ks[i][k] (Ks [ntpad][npad], pad = 0): 64x64 output tiles, the k range in chunks of
+// TARGETS_MEAN_KSTEP whatever m is, partial products in P (targets_mean_split(npad) * ((m + 63) / 64 * 64) * ntpad doubles),
+// added in chunk order by a second launch
+constexpr int TARGETS_MEAN_KSTEP = 512;
+int targets_mean_split(int npad);
+void launch_targets_mean(const double* A, const double* Ks, double* P, int npad, int m, int nt, int ntpad, double* mean,
+                         hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

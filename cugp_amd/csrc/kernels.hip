@@ -2821,6 +2821,342 @@ __global__ __launch_bounds__(256) void k_poe_reduce(const double* __restrict__ g
 }
 
 // ------------------------------------------------------------------------------------------
+// Multi-target regression: m target vectors over the handle's one factorisation (cugp_set_targets).  Everything is
+// target-major, [mpad][npad] with zeros beyond n and beyond m: Y the targets, Z = Y L^-T (k_predict_gemm as it stands),
+// A = Z L^-1 (row t = alpha_t, k_targets_alpha), then ONE pass over K^-1 for the gradient of the summed objective
+// (k_trace_targets / k_trace_targets_ard), the final sums (k_finalize_targets) and the means A Ks^T (k_targets_mean).
+// The kernels have bodies of their own: the single-target kernels above keep their instructions.
+// ------------------------------------------------------------------------------------------
+
+// A[t][j] = sum_{k >= j} Z[t][k] U[j][k], U = L^-T row-major and upper triangular.  Column tile tj (64 wide) takes the k
+// range from its own diagonal, tj * 64, to npad: U's diagonal 128x128 tiles hold exact zeros below the diagonal
+// (trtri_diag_body writes every entry of them, 0.0 where the row index exceeds the column's), so the second 64-column half
+// of a 128-tile may start at its own first column; tiles LEFT of the diagonal tile are never written and never read here.
+// The work of a column tile falls linearly with tj, so the tiles run in pairs (tj = p, the long one, then n64 - 1 - p):
+// every workgroup sums (n64 + 1) * 64 k in all, as k_predict_gemm's pairs do.  Grid: m64 * n64 / 2.
+__global__ __launch_bounds__(256, 2) void k_targets_alpha(const double* __restrict__ Z, const double* __restrict__ U,
+                                                          double* __restrict__ A, int ld, int m64, int n64)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tt = blockIdx.x % m64, p = blockIdx.x / m64;
+#pragma unroll 1
+    for (int h = 0; h < 2; h++) {
+        const int tj = h == 0 ? p : n64 - 1 - p;
+        d4 acc[2][2];
+        acc_zero(acc);
+        tile_nt<false>(Z + (size_t)tt * 64 * ld, ld, U + (size_t)tj * 64 * ld, ld, tj * 64, n64 * 64, acc, smem);
+        tile_store(A + (size_t)tt * 64 * ld + tj * 64, ld, acc, 1.0);
+    }
+}
+
+// Partial means P_s[t][i] = sum_{k in chunk s} A[t][k] Ks[i][k]: an NT product of two k-contiguous operands, 64x64 output
+// tiles, the k range in chunks of kstep (a function of nothing but the launch's npad, so that a target's bits do not
+// depend on how many targets there are).  P: [split][m64 * 64][ntpad].  Grid: m64 * nt64 * split.
+__global__ __launch_bounds__(256, 2) void k_targets_mean(const double* __restrict__ A, const double* __restrict__ Ks,
+                                                         double* __restrict__ P, int ld, int m64, int nt64, int kstep,
+                                                         size_t pstride, int ntpad)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tt = blockIdx.x % m64, r = blockIdx.x / m64, ii = r % nt64, s = r / nt64;
+    const int k0 = s * kstep, k1 = k0 + kstep < ld ? k0 + kstep : ld;
+    d4 acc[2][2];
+    acc_zero(acc);
+    tile_nt<false>(A + (size_t)tt * 64 * ld, ld, Ks + (size_t)ii * 64 * ld, ld, k0, k1, acc, smem);
+    tile_store(P + (size_t)s * pstride + (size_t)tt * 64 * ntpad + ii * 64, ntpad, acc, 1.0);
+}
+
+// mean[t * nt + i] = P_0[t][i] + P_1[t][i] + ... in chunk order, packed [m][nt]
+__global__ __launch_bounds__(256) void k_targets_mean_finish(const double* __restrict__ P, size_t pstride, int split,
+                                                             int ntpad, int m, int nt, double* __restrict__ mean)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)m * nt) return;
+    const size_t t = e / nt, i = e - t * nt;
+    const double* p = P + t * ntpad + i;
+    double s = p[0];
+    for (int c = 1; c < split; c++) s = s + p[(size_t)c * pstride];
+    mean[e] = s;
+}
+
+// S[a][b] = sum_t A[t][i0 + 4 ty + a] A[t][j0 + col4(tx, b)] of the thread's 4x4 micro-tile, t ascending, no contraction.
+// The two 64-entry runs of A per target (contiguous, 512 B each) go through LDS, TGT_CHUNK targets at a time.
+constexpr int TGT_CHUNK = 16;
+__device__ __forceinline__ void targets_outer_4x4(const double* __restrict__ A, int ld, int m, int i0, int j0,
+                                                  double (&la)[TGT_CHUNK][KT], double (&lb)[TGT_CHUNK][KT],
+                                                  double (&S)[4][4])
+{
+#pragma clang fp contract(off)
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) S[a][b] = 0.0;
+    for (int t0 = 0; t0 < m; t0 += TGT_CHUNK) {
+        const int tc = (m - t0 < TGT_CHUNK) ? (m - t0) : TGT_CHUNK;
+        __syncthreads();
+        for (int e = t; e < tc * 64; e += 256) {              // 16-byte pieces: 32 of the row run, 32 of the column run
+            const int r = e >> 6, q = e & 63;
+            const double* row = A + (size_t)(t0 + r) * ld;
+            if (q < 32) *(d2*)&la[r][2 * q] = *(const d2*)(row + i0 + 2 * q);
+            else *(d2*)&lb[r][2 * (q - 32)] = *(const d2*)(row + j0 + 2 * (q - 32));
+        }
+        __syncthreads();
+        for (int r = 0; r < tc; r++) {
+            const d2 a01 = *(const d2*)&la[r][ty * 4], a23 = *(const d2*)&la[r][ty * 4 + 2];
+            const d2 b01 = *(const d2*)&lb[r][tx * 2], b23 = *(const d2*)&lb[r][32 + tx * 2];
+            const double ai[4] = {a01[0], a01[1], a23[0], a23[1]}, aj[4] = {b01[0], b01[1], b23[0], b23[1]};
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+#pragma unroll
+                for (int b = 0; b < 4; b++) S[a][b] = S[a][b] + ai[a] * aj[b];
+        }
+    }
+}
+
+// Gradient pass of the summed objective, isotropic families: k_trace's tile, thread layout, entry formulas, doubling of
+// the off-diagonal entries, diagonal handling and partial sums (part[3 * block + c]) with
+//   W = m K^-1 - sum_t alpha_t alpha_t^T
+// in place of K^-1 - alpha alpha^T.  K^-1 is read once whatever m is; no N x N intermediate is written.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_trace_targets(const double* __restrict__ X, int n, int d, int npad,
+                                                       HyperScalars h, const double* __restrict__ Kinv,
+                                                       const double* __restrict__ A, int m, double* __restrict__ part)
+{
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ __attribute__((aligned(16))) double la[TGT_CHUNK][KT], lb[TGT_CHUNK][KT];
+    __shared__ double red[3][4];
+    int ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    const int i0 = ti * KT, j0 = tj * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    double d2v[4][4], S[4][4];
+    sqdist_4x4(X, X, n, n, d, i0, j0, xs, ys, d2v);
+    targets_outer_4x4(A, npad, m, i0, j0, la, lb, S);
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    const DivBy dl = div_prepare(h.ell_sq);
+    const double dm = (double)m;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int i = i0 + ty * 4 + a;
+        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
+        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
+        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = j0 + col4(tx, b);
+            if (i < n && j < n && (ti != tj || j <= i)) {
+                const double w = dm * kv[b] - S[a][b];
+                if constexpr (KIND == KERNEL_SE) {
+                    double kse = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
+                    const double sd = div_by(d2v[a][b], dl);
+                    if (i == j) {
+                        kse += h.noise_var;
+                        s1 += w * (kse * sd);
+                        s2 += w * kse;
+                        s3 += w;
+                    } else {
+                        s1 += 2.0 * (w * (kse * sd));
+                        s2 += 2.0 * (w * kse);
+                    }
+                } else {
+                    double kf, dk;
+                    matern_entry<KIND>(div_by(d2v[a][b], dl), h.signal_var, kf, dk);
+                    if (i == j) {
+                        kf += h.noise_var;
+                        s1 += w * dk;
+                        s2 += w * kf;
+                        s3 += w;
+                    } else {
+                        s1 += 2.0 * (w * dk);
+                        s2 += 2.0 * (w * kf);
+                    }
+                }
+            }
+        }
+    }
+    s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
+    if ((t & 63) == 0) { red[0][t >> 6] = s1; red[1][t >> 6] = s2; red[2][t >> 6] = s3; }
+    __syncthreads();
+    if (t < 3) part[(size_t)blockIdx.x * 3 + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+}
+
+// The same for ARD: k_trace_ard's two sweeps and partial layout (part[c * nblocks + block]) with the summed W.
+__global__ __launch_bounds__(256) void k_trace_targets_ard(const double* __restrict__ X, int n, int d, int npad,
+                                                           const HyperScalars* __restrict__ hd,
+                                                           const double* __restrict__ Kinv, const double* __restrict__ A,
+                                                           int m, double* __restrict__ part)
+{
+#pragma clang fp contract(off)
+    const HyperScalars h = *hd;
+    const double* __restrict__ wts = ard_weights(hd);
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ __attribute__((aligned(16))) double la[TGT_CHUNK][KT], lb[TGT_CHUNK][KT];
+    __shared__ double ws[DC];
+    __shared__ double red[DC][4];
+    int ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    const int i0 = ti * KT, j0 = tj * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const size_t nblocks = gridDim.x;
+    double wk[4][4], S[4][4];
+    sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, wk, wts, ws);
+    targets_outer_4x4(A, npad, m, i0, j0, la, lb, S);
+    double s2 = 0.0, s3 = 0.0;
+    const double dm = (double)m;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int i = i0 + ty * 4 + a;
+        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
+        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
+        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = j0 + col4(tx, b);
+            double e = 0.0;
+            if (i < n && j < n && (ti != tj || j <= i)) {
+                const double w = dm * kv[b] - S[a][b];
+                double kse = h.signal_var * exp(-0.5 * wk[a][b]);
+                if (i == j) {
+                    kse += h.noise_var;
+                    s2 += w * kse;
+                    s3 += w;
+                } else {
+                    e = 2.0 * (w * kse);     // (the diagonal's differences are zero: it has no share in any g_c)
+                    s2 += e;
+                }
+            }
+            wk[a][b] = e;
+        }
+    }
+    s2 = wave_sum(s2); s3 = wave_sum(s3);
+    if ((t & 63) == 0) { red[0][t >> 6] = s2; red[1][t >> 6] = s3; }
+    __syncthreads();
+    if (t < 2) part[(size_t)(d + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    for (int c0 = 0; c0 < d; c0 += DC) {
+        const int dc = (d - c0 < DC) ? (d - c0) : DC;
+        __syncthreads();
+        for (int e = t; e < KT * dc; e += 256) {
+            int r = e / dc, c = e - r * dc;
+            xs[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
+            ys[r][c] = (j0 + r < n) ? X[(size_t)(j0 + r) * d + c0 + c] : 0.0;
+        }
+        if (t < dc) ws[t] = wts[c0 + t];
+        __syncthreads();
+        double gs[DC];
+#pragma unroll
+        for (int c = 0; c < DC; c++) {
+            gs[c] = 0.0;
+            if (c < dc) {
+                double xv[4], yv[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+                const double wc = ws[c];
+                double acc = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        const double df = (xv[a] - yv[b]) * wc;
+                        acc = acc + wk[a][b] * (df * df);
+                    }
+                gs[c] = wave_sum(acc);
+            }
+        }
+        if ((t & 63) == 0) {
+#pragma unroll
+            for (int c = 0; c < DC; c++) red[c][t >> 6] = gs[c];
+        }
+        __syncthreads();
+        if (t < dc) part[(size_t)(c0 + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    }
+}
+
+// Final sums of a multi-target evaluation, one workgroup.  Results row (out, and hout pinned): [0] LL = sum_t LL_t added
+// in target order, [1 + c] the nh gradient components of -LL, [1 + nh + t] LL_t.
+//   quad_t = z_t'z_t: wave t mod 16 takes target t -- lane l adds the squares l, l + 64, ... of row t of Z ascending, the
+//     lanes by wave_sum: an order that depends neither on m nor on where the target stands
+//   LL_t = -0.5 (quad_t + log|K| + n * 1.83787), log|K| the handle's own (by value: the host holds it after the evaluation)
+//   isotropic (d_ard < 0): the three trace sums in finalize_sums' order (thread v adds the blocks v, v + 1024, ...
+//     ascending, then the halving tree) and k_finalize's formulas; ARD: k_finalize_ard's columns, order and formulas
+// A covariance that could not be factored has log|K| = NaN: every result is then NaN (the header's convention).
+__global__ __launch_bounds__(FIN_THREADS) void k_finalize_targets(const double* __restrict__ Z, int npad, int n, int m,
+                                                                  double logdet, const double* __restrict__ part,
+                                                                  int nblocks, int d_ard, HyperScalars h_arg,
+                                                                  const HyperScalars* __restrict__ hd,
+                                                                  double* __restrict__ out, double* __restrict__ hout)
+{
+#pragma clang fp contract(off)
+    const HyperScalars h = hd ? *hd : h_arg;
+    const int nh = d_ard >= 0 ? d_ard + 2 : 3;
+    __shared__ double red[3 * FIN_THREADS];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const bool dead = logdet != logdet;
+    double* ll_each = out + 1 + nh;
+    for (int tg = wave; tg < m; tg += FIN_THREADS / 64) {
+        const double* zr = Z + (size_t)tg * npad;
+        double q = 0.0;
+        for (int i = lane; i < npad; i += 64) q = q + zr[i] * zr[i];
+        q = wave_sum(q);
+        if (lane == 0) ll_each[tg] = -0.5 * (q + logdet + n * 1.83787);
+    }
+    if (d_ard < 0) {
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int i = t; i < nblocks; i += FIN_THREADS)
+#pragma unroll
+            for (int c = 0; c < 3; c++) s[c] = s[c] + part[(size_t)i * 3 + c];
+#pragma unroll
+        for (int c = 0; c < 3; c++) red[c * FIN_THREADS + t] = s[c];
+        __syncthreads();
+        for (int w = FIN_THREADS / 2; w > 0; w >>= 1) {
+            if (t < w)
+                for (int c = 0; c < 3; c++) red[c * FIN_THREADS + t] += red[c * FIN_THREADS + t + w];
+            __syncthreads();
+        }
+        if (t == 0) {
+            const double s1 = red[0], s2 = red[FIN_THREADS], s3 = red[2 * FIN_THREADS];
+            out[1] = dead ? logdet : s1 / 2.0;
+            out[2] = dead ? logdet : (2.0 * s2 - 2.0 * h.noise_var * s3) / 2.0;
+            out[3] = dead ? logdet : (2.0 * h.noise_var * s3) / 2.0;
+        }
+    } else {
+        const int d = d_ard;
+        for (int c = wave; c < d + 2; c += FIN_THREADS / 64) {
+            const double* col = part + (size_t)c * nblocks;
+            double s = 0.0;
+            for (int i = lane; i < nblocks; i += 64) s += col[i];
+            s = wave_sum(s);
+            if (lane == 0 && c < d) out[1 + c] = dead ? logdet : s / 2.0;
+            if (lane == 0 && c >= d) red[c - d] = s;
+        }
+        __syncthreads();
+        if (t == 0) {
+            const double s2 = red[0], s3 = red[1];
+            out[1 + d] = dead ? logdet : (2.0 * s2 - 2.0 * h.noise_var * s3) / 2.0;
+            out[2 + d] = dead ? logdet : (2.0 * h.noise_var * s3) / 2.0;
+        }
+    }
+    __syncthreads();
+    // (the row was written by other waves of this workgroup: agent-scope loads, past the vector cache)
+    double ll = 0.0;
+    for (int t0 = 0; t0 < m; t0 += FIN_THREADS) {          // LL_t through LDS, FIN_THREADS at a time; thread 0 adds in target order
+        __syncthreads();
+        if (t0 + t < m) red[t] = __hip_atomic_load(ll_each + t0 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (t == 0) {
+            const int cnt = (m - t0 < FIN_THREADS) ? (m - t0) : FIN_THREADS;
+            for (int i = 0; i < cnt; i++) ll = ll + red[i];
+        }
+    }
+    if (t == 0) {
+        out[0] = ll;
+        hout[0] = ll;
+    }
+    for (int i = 1 + t; i < 1 + nh + m; i += FIN_THREADS)
+        hout[i] = __hip_atomic_load(out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 // Per-launch timing without extra packets on the stream (profiling level 4, cugp_capi.cpp TimedLaunch): the next launch
@@ -2857,6 +3193,10 @@ static inline int tri_count(int n) { return n * (n + 1) / 2; }
 #define CUGP_ISO_KERNEL(cf, stem)                                                        \
     ((cf).kind == KERNEL_MATERN32   ? stem##_matern<KERNEL_MATERN32>                     \
      : (cf).kind == KERNEL_MATERN52 ? stem##_matern<KERNEL_MATERN52> : stem)
+// (the multi-target gradient pass is one template over the three kinds)
+#define CUGP_ISO_KERNEL_T(cf, stem)                                                      \
+    ((cf).kind == KERNEL_MATERN32   ? stem<KERNEL_MATERN32>                              \
+     : (cf).kind == KERNEL_MATERN52 ? stem<KERNEL_MATERN52> : stem<KERNEL_SE>)
 static inline bool is_ard(const CovFn& cf)
 {
     assert(!cf.ard || (cf.hd && cf.kind == KERNEL_SE));
@@ -3230,6 +3570,44 @@ void launch_finalize(const double* z, int npad, int n, const double* logdet_part
 {
     hipLaunchKernelGGL(k_finalize, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, logdet_part, nt, part, nblocks, h,
                        hd, out, hout, bt.tab);
+}
+
+void launch_targets_alpha(const double* Z, const double* U, double* A, int npad, int m, hipStream_t s)
+{
+    const int m64 = (m + 63) / 64, n64 = npad / 64;
+    hipLaunchKernelGGL(k_targets_alpha, dim3(m64 * (n64 / 2)), dim3(256), Geo<2>::LDS, s, Z, U, A, npad, m64, n64);
+}
+
+void launch_trace_targets(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* A,
+                          int m, double* part, hipStream_t s)
+{
+    const dim3 grid(tri_count(npad / KT));
+    if (is_ard(cf))
+        hipLaunchKernelGGL(k_trace_targets_ard, grid, dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, A, m, part);
+    else
+        hipLaunchKernelGGL(CUGP_ISO_KERNEL_T(cf, k_trace_targets), grid, dim3(256), 0, s, X, n, d, npad, cf.h, Kinv, A, m,
+                           part);
+}
+
+void launch_finalize_targets(const double* Z, int npad, int n, int d, int m, double logdet, const double* part,
+                             const CovFn& cf, double* out, double* hout, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_finalize_targets, dim3(1), dim3(FIN_THREADS), 0, s, Z, npad, n, m, logdet, part,
+                       tri_count(npad / KT), is_ard(cf) ? d : -1, cf.h, is_ard(cf) ? cf.hd : nullptr, out, hout);
+}
+
+int targets_mean_split(int npad) { return (npad + TARGETS_MEAN_KSTEP - 1) / TARGETS_MEAN_KSTEP; }
+
+void launch_targets_mean(const double* A, const double* Ks, double* P, int npad, int m, int nt, int ntpad, double* mean,
+                         hipStream_t s)
+{
+    const int m64 = (m + 63) / 64, nt64 = (nt + 63) / 64, split = targets_mean_split(npad);
+    const size_t pstride = (size_t)m64 * 64 * ntpad;
+    hipLaunchKernelGGL(k_targets_mean, dim3(m64 * nt64 * split), dim3(256), Geo<2>::LDS, s, A, Ks, P, npad, m64, nt64,
+                       TARGETS_MEAN_KSTEP, pstride, ntpad);
+    const size_t total = (size_t)m * nt;
+    hipLaunchKernelGGL(k_targets_mean_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P, pstride, split,
+                       ntpad, m, nt, mean);
 }
 
 void launch_test_gemm_nt(const double* A, const double* B, double* C, int m, int n, int k, hipStream_t s)

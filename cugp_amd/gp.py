@@ -198,6 +198,50 @@ class Covsum:
         check(capi.lib().cugp_get_alpha(self._h, ptr(a)))
         return a
 
+    # -- multi-target regression: m target vectors over the same X and hyper-parameters, one factorisation --
+    def set_targets(self, Y):
+        """Y [n, m], one column per target (cugp_set_targets; handed over target-major).  set_data is still required:
+        it supplies X, and its y is unrelated to the targets."""
+        Y = f64(Y)
+        if Y.ndim != 2 or Y.shape[0] != self.n or Y.shape[1] < 1:
+            raise ValueError("expected Y of shape (%d, m), m >= 1" % self.n)
+        Yt = f64(Y.T)
+        check(capi.lib().cugp_set_targets(self._h, ptr(Yt), Yt.shape[0]))
+
+    @property
+    def num_targets(self):
+        m = C.c_int()
+        check(capi.lib().cugp_num_targets(self._h, C.byref(m)))
+        return m.value
+
+    def loglik_grad_targets(self):
+        """(LL = sum_t LL_t, gradient of -LL [nh], LL_t [m]) from one factorisation (cugp_loglik_grad_targets)."""
+        ll = C.c_double()
+        g, each = np.empty(self.nh), np.empty(self.num_targets)
+        check(capi.lib().cugp_loglik_grad_targets(self._h, C.byref(ll), ptr(g), self.nh, ptr(each)))
+        return ll.value, g, each
+
+    def predict_targets(self, Xtest):
+        """(mean [nt, m], var [nt]) at the test points; the variance is compute_test_means_and_variances' own."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        mean, var = np.empty((self.num_targets, nt)), np.empty(nt)
+        check(capi.lib().cugp_predict_targets(self._h, ptr(Xt), nt, ptr(mean), ptr(var)))
+        return f64(mean.T), var
+
+    def get_alpha_targets(self):
+        """K^-1 Y, [n, m]."""
+        a = np.empty((self.num_targets, self.n))
+        check(capi.lib().cugp_get_alpha_targets(self._h, ptr(a)))
+        return f64(a.T)
+
+    def cg_solve_targets(self, budget=100):
+        """Conjugate gradients on -sum_t LL_t (cugp_cg_solve_targets); the trace [n_evals, nh + 1] = (theta, -LL)."""
+        tr = np.zeros((4 * budget + 8, self.nh + 1))
+        ne = C.c_int()
+        check(capi.lib().cugp_cg_solve_targets(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        return tr[: ne.value]
+
     # -- prediction --
     def compute_test_means_and_variances(self, X, y, Xtest):
         self._bind(X, y)

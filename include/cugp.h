@@ -169,6 +169,42 @@ int cugp_get_cholesky(cugp_gp *gp, double *L);
 int cugp_get_K_inverse(cugp_gp *gp, double *Kinv);
 int cugp_get_alpha(cugp_gp *gp, double *alpha);
 
+/* ---- multi-target regression: m target vectors y_t over the handle's inputs and hyper-parameters share ONE
+ *      factorisation.  The reference has no counterpart (its Covsum holds one y); the model is scikit-learn's
+ *      GaussianProcessRegressor with a 2-d y: independent outputs, shared kernel and theta.  Everything that costs N^3
+ *      (K, its factor, L^-1, K^-1) depends on X and theta alone and is the handle's own evaluation, untouched; what
+ *      depends on the targets is N^2 work per target behind it:
+ *        z_t = L^-1 y_t,  alpha_t = L^-T z_t = K^-1 y_t,  LL_t = -1/2 (z_t'z_t + log|K| + n * 1.83787),  LL = sum_t LL_t
+ *        gradient of -LL in the handle's convention, component order and nh:  W = m K^-1 - sum_t alpha_t alpha_t',
+ *        g_theta = 1/2 sum_ij W_ij dK_ij/dtheta  (noise component sn2 tr W) -- each family's own per-entry formulas
+ *        mean of target t at the test points: Ks alpha_t; the variance does not depend on the targets (cugp_predict's).
+ *      log|K| is the handle's own (cugp_last_quad_logdet), LL_t are added in target order.
+ * The targets are an ADDITIONAL data set on the handle: cugp_set_data is still required (it supplies X) and its y, with
+ * every call above, is unchanged by and unrelated to them.  Targets persist until replaced; a second cugp_set_targets
+ * may change m.  The calls work on an isotropic handle of any kernel kind and on an ARD handle.
+ * cugp_set_targets        : Y is [m][n], target-major (row t = y_t), host memory
+ * cugp_num_targets        : *m <- the number of targets, 0 before cugp_set_targets
+ * cugp_loglik_grad_targets: *ll <- LL, g <- the nh gradient components (nh must equal cugp_num_hyper), ll_each <- the m
+ *                           LL_t; any of the three may be NULL.  A stale handle is evaluated first (cugp_loglik_grad).
+ * cugp_predict_targets    : mean [m][nt] target-major, var (may be NULL) nt -- cugp_predict's launches and bits
+ * cugp_get_alpha_targets  : alpha [m][n], row t = K^-1 y_t
+ * cugp_cg_solve_targets   : cugp_cg_minimize_n over the handle's nh entries on f = -LL; trace rows of 1 + nh doubles; the
+ *                           end point stays set, as cugp_cg_solve leaves it
+ * The results of one (data, theta, targets) are kept: a repeated call costs no device work.
+ * Errors: CUGP_ERR_INVALID, with the call's name in cugp_last_error, for a NULL gp, Y, Xt, mean or alpha, m <= 0,
+ * nt <= 0, an nh that is not the handle's, an evaluation or prediction before cugp_set_targets, cugp_set_targets before
+ * cugp_set_data; argument errors come before any device call.  CUGP_ERR_NODEVICE without a GPU.  A covariance that is not
+ * positive definite gives NaN results with CUGP_OK (the header's convention).
+ * Not built: targets on BCM experts and groups, joint covariance and draws per target, an LL-only form. */
+int cugp_set_targets(cugp_gp *gp, const double *Y /* [m][n], target-major, host */, int m);
+int cugp_num_targets(const cugp_gp *gp, int *m);
+int cugp_loglik_grad_targets(cugp_gp *gp, double *ll /* sum */, double *g /* nh, may be NULL */, int nh,
+                             double *ll_each /* m, may be NULL */);
+int cugp_predict_targets(cugp_gp *gp, const double *Xt, int nt, double *mean /* [m][nt] */,
+                         double *var /* nt, may be NULL */);
+int cugp_get_alpha_targets(cugp_gp *gp, double *alpha /* [m][n] */);
+int cugp_cg_solve_targets(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals);
+
 /* ---- stand-alone dense LA on a caller matrix (common/matrixops.h:5-25) ----
  * cugp_potrf        : get_cholesky            (L lower, upper zeroed)
  * cugp_potri        : compute_K_inverse
