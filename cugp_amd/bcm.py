@@ -281,25 +281,41 @@ class ShardedBCM:
             g = out[k, 1:].copy() if k == 0 else g + out[k, 1:]
         return float(ll), g, out[:, 0].copy()
 
-    def predict(self, Xt):
-        """Product of experts (BCM.cpp:45-83).  Library form (a library communicator): the whole exchange inside
+    def predict(self, Xt, combine=None, with_noise=True):
+        """combine=None: today's product of the experts' noisy predictions, described below.  combine = "poe" | "gpoe" |
+        "bcm" | "rbcm": the rule on the experts' LATENT distributions (include/cugp.h: CUGP_COMBINE_*), var with sn2
+        added when with_noise.  Library form: cugp_bcm_predict_allgather_mode (the same exchange, the rule on the
+        device).  Torch forms: every local expert's predict_latent fills its zero-padded [K][2][nt] rows (1/var_f,
+        m/var_f), the same all-reduce, then cugp_poe_combine on the host -- which needs no GPU.
+
+        Product of experts (BCM.cpp:45-83).  Library form (a library communicator): the whole exchange inside
         libcugp -- batched prediction kernels, one all-gather of every rank's per-expert precision and precision*mean,
         the product on the device (cugp_bcm_predict_allgather).  Otherwise an all-reduce of those rows through
         torch.distributed (expert by expert; the same bits once the experts are up to date -- stale ones are evaluated
         alone there, as a group by the library).  self.predict_form says which path ran."""
+        if combine is not None:
+            _gp.combine_mode(combine)                     # an unknown name: ValueError before any library call
         Xt = np.ascontiguousarray(Xt, dtype=np.float64)
+        sf2, sn2 = _gp.prior_scalars(self.hp)
         if self._comm is not None:
             self.predict_form = "library"
+            if combine is not None:
+                return self._comm.predict_allgather(self._group, self._per, self.K, Xt, combine, with_noise, sf2, sn2)
             return self._comm.predict_allgather(self._group, self._per, self.K, Xt)
         self.predict_form = "torch"
         nt = Xt.shape[0]
         buf = np.zeros((self.K, 2, nt))
         for k in self.mine:
-            m, v = self.local[k].compute_test_means_and_variances(None, None, Xt)
+            if combine is not None:
+                m, v = self.local[k].predict_latent(Xt)
+            else:
+                m, v = self.local[k].compute_test_means_and_variances(None, None, Xt)
             buf[k, 0] = 1.0 / v
             buf[k, 1] = (1.0 / v) * m
         t = torch.from_numpy(buf).to(self.comm_device)
         out = self._allreduce(t).cpu().numpy()
+        if combine is not None:
+            return _gp.poe_combine(out, combine, sf2, sn2, with_noise)
         sp, spm = np.zeros(nt), np.zeros(nt)
         for k in range(self.K):
             sp += out[k, 0]

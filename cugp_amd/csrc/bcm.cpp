@@ -40,6 +40,10 @@ struct cugp_bcm {
     std::vector<double> hp = {0, 0, 0};
     int kernel = 0;                  // CUGP_KERNEL_* of every expert, for life
     Scratch pred_host{nullptr, 0, true};   // pinned: [expert][mean nt | variance nt] of the prediction in flight
+    // cugp_bcm_predict_mode on one device set: {status, count, [K][2][nt] latent rows} (k_poe_reduce_mode's block of a
+    // world of one), its output [mean nt | var nt | status, count] on the device and pinned, the stream they run on
+    Scratch mode_rows, mode_out, mode_hout{nullptr, 0, true};
+    hipStream_t mode_stream = nullptr;
     std::vector<hipEvent_t> pred_ev; // cugp_bcm_predict_rows_enqueue: "rows written" per stream that wrote some
 };
 
@@ -221,6 +225,9 @@ int cugp_bcm_destroy(cugp_bcm* b)
     for (cugp_gp* g : b->experts) cugp_destroy(g);
     b->pred_host.release();
     for (hipEvent_t e : b->pred_ev) (void)hipEventDestroy(e);
+    if (b->mode_stream) (void)hipStreamSynchronize(b->mode_stream);
+    for (Scratch* sc : {&b->mode_rows, &b->mode_out, &b->mode_hout}) sc->release();
+    if (b->mode_stream) (void)hipStreamDestroy(b->mode_stream);
     delete b;
     return CUGP_OK;
 }
@@ -574,6 +581,12 @@ int cugp_bcm_predict_partial(cugp_bcm* b, const double* Xt, int nt, double* sum_
 int cugp_bcm_predict_rows_enqueue(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend, size_t slot_stride,
                                   void* wait_stream)
 {
+    return cugp_bcm_predict_rows_enqueue_form(b, device, Xt, nt, dsend, slot_stride, wait_stream, 0);
+}
+
+int cugp_bcm_predict_rows_enqueue_form(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend,
+                                       size_t slot_stride, void* wait_stream, int latent)
+{
     if (!b || !Xt || nt <= 0 || !dsend || !wait_stream) return CUGP_ERR_INVALID;
     if (b->sets.size() != 1 || b->sets[0].device != device)
         return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_allgather: the BCM's experts are not all on the communicator's device");
@@ -596,13 +609,14 @@ int cugp_bcm_predict_rows_enqueue(cugp_bcm* b, int device, const double* Xt, int
     };
     if (ds.group) {
         void* s = nullptr;
-        rc = cugp_group_predict_enqueue(ds.group, Xt, nt, dsend, slot_stride, &s);
+        rc = cugp_group_predict_enqueue_form(ds.group, Xt, nt, dsend, slot_stride, &s, latent);
         if (rc == CUGP_OK) return order_after(0, s);
         if (rc != CUGP_ERR_INVALID) return rc;               // INVALID: not possible as a group right now
     }
     for (size_t i = 0; i < n; i++) {
         void* s = nullptr;
-        if ((rc = cugp_predict_rows_enqueue(b->experts[ds.idx[i]], Xt, nt, dsend + i * slot_stride, &s))) return rc;
+        if ((rc = cugp_predict_rows_enqueue_form(b->experts[ds.idx[i]], Xt, nt, dsend + i * slot_stride, &s, latent)))
+            return rc;
         if ((rc = order_after(i, s))) return rc;
     }
     return CUGP_OK;
@@ -637,6 +651,107 @@ int cugp_bcm_predict(cugp_bcm* b, const double* Xt, int nt, double* mean, double
     int rc = cugp_bcm_predict_partial(b, Xt, nt, sp.data(), spm.data());
     if (rc) return rc;
     return cugp_poe_finish(sp.data(), spm.data(), nt, mean, var);
+}
+
+// ---- combination rules on latent expert distributions (include/cugp.h: CUGP_COMBINE_*) ----
+// Host twin of k_poe_reduce_mode (kernels.hip): the same operations in the same order, every one rounded on its own.
+int cugp_poe_combine(const double* rows, int K, int nt, int mode, double sf2, double sn2, int with_noise, double* mean,
+                     double* var)
+{
+#pragma clang fp contract(off)
+    if (!rows || !mean || !var || K <= 0 || nt <= 0 || mode < CUGP_COMBINE_POE || mode > CUGP_COMBINE_RBCM)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_poe_combine: null argument, K <= 0, nt <= 0 or an unknown mode");
+    const double bg = 1.0 / (double)K;
+    for (int t = 0; t < nt; t++) {
+        double sp = 0.0, spm = 0.0, sb = 0.0;
+        for (int k = 0; k < K; k++) {
+            const double* r = rows + (size_t)k * 2 * nt;
+            const double p = r[t], pm = r[nt + t];
+            double beta = 1.0;
+            if (mode == CUGP_COMBINE_GPOE) beta = bg;
+            else if (mode == CUGP_COMBINE_RBCM) beta = 0.5 * std::log(sf2 * p);
+            sp = sp + beta * p;
+            spm = spm + beta * pm;
+            sb = sb + beta;
+        }
+        double prec = sp;
+        if (mode >= CUGP_COMBINE_BCM) prec = sp + (1.0 - sb) / sf2;
+        const double tv = 1.0 / prec;
+        mean[t] = tv * spm;
+        var[t] = with_noise ? tv + sn2 : tv;
+    }
+    return CUGP_OK;
+}
+
+int cugp_bcm_prior_scalars(const cugp_bcm* b, double* sf2, double* sn2)
+{
+    if (!b || !sf2 || !sn2) return CUGP_ERR_INVALID;
+    *sf2 = std::exp(b->hp[b->nh - 2] * 2);          // (cugp_capi.cpp: scalars)
+    *sn2 = std::exp(b->hp[b->nh - 1] * 2);
+    return CUGP_OK;
+}
+
+// One device set: the experts' latent rows as one group of batched launches (else expert by expert) into the BCM's own
+// buffer, laid out as the block of a world of one, k_poe_reduce_mode behind them on the BCM's stream, one copy, one host
+// wait.  Several device sets: every expert's latent mean and variance into pinned host memory, all in flight before the
+// first is read (cugp_bcm_predict_partial's pattern), the rows formed as poe_row forms them, then cugp_poe_combine.
+int cugp_bcm_predict_mode(cugp_bcm* b, const double* Xt, int nt, int mode, int with_noise, double* mean, double* var)
+{
+    if (!b || !Xt || nt <= 0 || !mean || !var || mode < CUGP_COMBINE_POE || mode > CUGP_COMBINE_RBCM)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_mode: null argument, nt <= 0 or an unknown mode");
+    const size_t K = b->experts.size();
+    double sf2, sn2;
+    int rc;
+    if ((rc = cugp_bcm_prior_scalars(b, &sf2, &sn2)) || (rc = bcm_refresh(b))) return rc;
+    if (b->sets.size() == 1) {
+        const int device = b->sets[0].device;
+        if (hipSetDevice(device) != hipSuccess) return cugp_internal_fail(CUGP_ERR_DEVICE, "hipSetDevice");
+        if (!b->mode_stream && hipStreamCreateWithFlags(&b->mode_stream, hipStreamNonBlocking) != hipSuccess)
+            return cugp_internal_fail(CUGP_ERR_DEVICE, "hipStreamCreateWithFlags (cugp_bcm_predict_mode)");
+        const size_t rstride = 2 + K * 2 * (size_t)nt, nout = 2 * (size_t)nt + 2;
+        if ((rc = b->mode_rows.grow(rstride, b->mode_stream)) || (rc = b->mode_out.grow(nout, b->mode_stream)) ||
+            (rc = b->mode_hout.grow(nout, b->mode_stream)))
+            return rc;
+        // the block's header {status, count}: zeros -- nothing reads them here, but the kernel copies them to its output
+        if (hipMemsetAsync(b->mode_rows.p, 0, 2 * sizeof(double), b->mode_stream) != hipSuccess)
+            return cugp_internal_fail(CUGP_ERR_DEVICE, "hipMemsetAsync (cugp_bcm_predict_mode)");
+        rc = cugp_bcm_predict_rows_enqueue_form(b, device, Xt, nt, b->mode_rows.p + 2, 2 * (size_t)nt, b->mode_stream, 1);
+        if (rc == CUGP_OK)
+            rc = cugp_poe_reduce_mode_enqueue(b->mode_rows.p, rstride, 1, (int)K, nt, mode, sf2, sn2, with_noise ? 1 : 0,
+                                              b->mode_out.p, b->mode_stream);
+        if (rc == CUGP_OK && hipMemcpyAsync(b->mode_hout.p, b->mode_out.p, nout * sizeof(double), hipMemcpyDeviceToHost,
+                                            b->mode_stream) != hipSuccess)
+            rc = cugp_internal_fail(CUGP_ERR_DEVICE, "hipMemcpyAsync (cugp_bcm_predict_mode)");
+        if (hipStreamSynchronize(b->mode_stream) != hipSuccess && rc == CUGP_OK)     // the one host wait
+            rc = cugp_internal_fail(CUGP_ERR_DEVICE, "hipStreamSynchronize (cugp_bcm_predict_mode)");
+        const int rf = cugp_bcm_predict_rows_finish(b);        // (streams already done: closes them)
+        if (rc == CUGP_OK) rc = rf;
+        if (rc) return rc;
+        memcpy(mean, b->mode_hout.p, (size_t)nt * sizeof(double));
+        memcpy(var, b->mode_hout.p + nt, (size_t)nt * sizeof(double));
+        return CUGP_OK;
+    }
+    if ((rc = b->pred_host.grow(K * 2 * (size_t)nt, nullptr))) return rc;
+    size_t enq = 0;
+    for (; enq < K && rc == CUGP_OK; enq++)
+        rc = cugp_predict_enqueue_form(b->experts[enq], Xt, nt, b->pred_host.p + enq * 2 * nt, 1);
+    if (rc) enq--;                                          // (the failing one enqueued nothing that needs a fetch)
+    for (size_t k = 0; k < enq; k++) {
+        const int rf = cugp_predict_fetch(b->experts[k]);
+        if (rf && rc == CUGP_OK) rc = rf;
+    }
+    if (rc) return rc;
+    for (size_t k = 0; k < K; k++) {                        // (m, var_f) -> (1/var_f, m/var_f) in place: poe_row's operations
+#pragma clang fp contract(off)
+        double* m = b->pred_host.p + k * 2 * nt;
+        double* v = m + nt;
+        for (int i = 0; i < nt; i++) {
+            const double inv = 1.0 / v[i], pm = inv * m[i];
+            m[i] = inv;
+            v[i] = pm;
+        }
+    }
+    return cugp_poe_combine(b->pred_host.p, (int)K, nt, mode, sf2, sn2, with_noise, mean, var);
 }
 
 namespace {

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <string>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -249,12 +250,18 @@ static void fill_nan(double* mean, double* var, int nt)
 // front of by events; k_poe_reduce sums every test point over the experts in global order, one copy brings mean,
 // variance and the ranks' status words into pinned memory, and the host waits ONCE.  A local failure still joins the
 // collective (nonzero status, NaN rows), so every rank reads every rank's status and all return the same code.
-int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt, double* mean,
-                               double* var)
+// The body of both public calls (`call`: the name in the error texts).  mode < 0: cugp_bcm_predict_allgather -- noisy rows,
+// k_poe_reduce.  mode >= 0 (CUGP_COMBINE_*): cugp_bcm_predict_allgather_mode -- latent rows (the same launches, noise_var
+// = 0 in the finish), k_poe_reduce_mode with sf2, sn2, with_noise; everything else is the same sequence.
+static int predict_allgather(const char* call, cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt,
+                             int mode, int with_noise, double sf2, double sn2, double* mean, double* var)
 {
+    char buf[512];
     // what every rank detects identically from the shared arguments: no collective
-    if (!c || per <= 0 || nexperts <= 0 || nt <= 0 || !Xt || !mean || !var || (long long)per * c->world < nexperts)
-        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_allgather: bad argument");
+    if (!c || per <= 0 || nexperts <= 0 || nt <= 0 || !Xt || !mean || !var || (long long)per * c->world < nexperts) {
+        snprintf(buf, sizeof buf, "%s: bad argument", call);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail("hipSetDevice", e);
     const size_t rstride = 2 + (size_t)per * 2 * nt, nout = 2 * (size_t)nt + 2 * (size_t)c->world;
@@ -266,14 +273,14 @@ int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts,
     bool enqueued = false;
     if (b && cugp_bcm_num_experts(b, &nlocal)) status = CUGP_ERR_INVALID;
     if (status == CUGP_OK && nlocal != expect) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: rank %d holds %d experts, %d of %d expected", c->rank,
+        snprintf(buf, sizeof buf, "%s: rank %d holds %d experts, %d of %d expected", call, c->rank,
                  nlocal, expect, nexperts);
         status = cugp_internal_fail(CUGP_ERR_INVALID, buf);
     }
     if (status == CUGP_OK && nlocal > 0) {
         enqueued = true;
-        status = cugp_bcm_predict_rows_enqueue(b, c->device, Xt, nt, c->pdsend.p + 2, 2 * (size_t)nt, c->stream);
+        status = cugp_bcm_predict_rows_enqueue_form(b, c->device, Xt, nt, c->pdsend.p + 2, 2 * (size_t)nt, c->stream,
+                                                    mode >= 0 ? 1 : 0);
     }
     if (status != CUGP_OK) {
         if (enqueued) (void)cugp_bcm_predict_rows_finish(b);   // nothing enqueued still writes into the send buffer
@@ -296,7 +303,9 @@ int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts,
         }
         src = c->pdrecv.p;
     }
-    rc = cugp_poe_reduce_enqueue(src, rstride, c->world, nexperts, nt, c->pdout.p, c->stream);
+    rc = mode < 0 ? cugp_poe_reduce_enqueue(src, rstride, c->world, nexperts, nt, c->pdout.p, c->stream)
+                  : cugp_poe_reduce_mode_enqueue(src, rstride, c->world, nexperts, nt, mode, sf2, sn2, with_noise ? 1 : 0,
+                                                 c->pdout.p, c->stream);
     if (rc == CUGP_OK) {
         e = hipMemcpyAsync(c->phout.p, c->pdout.p, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) rc = hip_fail("hipMemcpyAsync (prediction)", e);
@@ -311,17 +320,17 @@ int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts,
     for (int r = 0; r < c->world; r++) {
         const int st = (int)h[2 * (size_t)nt + 2 * r];
         if (st != CUGP_OK) {
-            char buf[512];
-            if (r == c->rank) snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: rank %d failed (%d): %s", r, st, cugp_last_error());
-            else snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: rank %d failed (%d)", r, st);
+            if (r == c->rank) {
+                const std::string last = cugp_last_error();
+                snprintf(buf, sizeof buf, "%s: rank %d failed (%d): %s", call, r, st, last.c_str());
+            } else snprintf(buf, sizeof buf, "%s: rank %d failed (%d)", call, r, st);
             fill_nan(mean, var, nt);
             return cugp_internal_fail(st, buf);
         }
         total += (long long)h[2 * (size_t)nt + 2 * r + 1];
     }
     if (total != nexperts) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "cugp_bcm_predict_allgather: the ranks hold %lld experts, %d expected", total, nexperts);
+        snprintf(buf, sizeof buf, "%s: the ranks hold %lld experts, %d expected", call, total, nexperts);
         fill_nan(mean, var, nt);
         return cugp_internal_fail(CUGP_ERR_INVALID, buf);
     }
@@ -329,6 +338,22 @@ int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts,
     memcpy(mean, h, (size_t)nt * sizeof(double));
     memcpy(var, h + nt, (size_t)nt * sizeof(double));
     return CUGP_OK;
+}
+
+int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt, double* mean,
+                               double* var)
+{
+    return predict_allgather("cugp_bcm_predict_allgather", b, c, per, nexperts, Xt, nt, -1, 0, 0.0, 0.0, mean, var);
+}
+
+// the same exchange with latent rows and k_poe_reduce_mode; sf2, sn2 are arguments: a rank without experts has no BCM
+int cugp_bcm_predict_allgather_mode(cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt, int mode,
+                                    int with_noise, double sf2, double sn2, double* mean, double* var)
+{
+    if (mode < CUGP_COMBINE_POE || mode > CUGP_COMBINE_RBCM)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_allgather_mode: unknown mode");
+    return predict_allgather("cugp_bcm_predict_allgather_mode", b, c, per, nexperts, Xt, nt, mode, with_noise, sf2, sn2,
+                             mean, var);
 }
 
 }  // extern "C"

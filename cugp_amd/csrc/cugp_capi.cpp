@@ -1434,8 +1434,10 @@ struct PredBufs { double *xt, *w, *mean, *var; };
 // Ks and W of one pass, [expert][cpad][npad] each), then per pass of `chunk` test points k_cross, k_predict_gemm and
 // k_predict_finish.  rows null: means and variances into the scratch behind W (one pass, chunk >= nt; *pb).  Else
 // product-of-experts rows: expert i's 1/v at rows[i * rstride + t], m/v at rows[i * rstride + nt + t].
+// latent: the same launches with noise_var = 0 in the scalars k_predict_finish takes by value -- the variance of the
+// latent function, sf2 - |W_t|^2, computed directly; nothing else reads them.
 static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int chunk, Scratch& scr, double* rows,
-                          size_t rstride, PredBufs* pb = nullptr)
+                          size_t rstride, PredBufs* pb = nullptr, bool latent = false)
 {
     int rc;
     const int cmax = chunk < nt ? chunk : nt, ntpad = ((cmax + TILE - 1) / TILE) * TILE;
@@ -1463,7 +1465,9 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
             for (int ti = 0; ti < g->nt; ti++) kt += ti + 0.5;
             tl.done(KIND_PREDICT, kt * (cpad / TILE) * 2.0 * TILE * TILE * TILE);
         }
-        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, cf.h, dm, dv, g->stream, rows ? rows + t0 : nullptr,
+        HyperScalars hf = cf.h;
+        if (latent) hf.noise_var = 0.0;
+        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, hf, dm, dv, g->stream, rows ? rows + t0 : nullptr,
                               rstride, nt, cpad, bt);
     }
     HIPCHK(hipGetLastError());
@@ -1472,20 +1476,19 @@ static int predict_passes(cugp_gp* g, Batch bt, const double* Xt, int nt, int ch
 }
 
 // means and variances at the nt test points in one pass (*pb), a stale handle re-evaluated first
-static int predict_device(cugp_gp* g, const double* Xt, int nt, PredBufs* pb)
+static int predict_device(cugp_gp* g, const double* Xt, int nt, PredBufs* pb, bool latent = false)
 {
     int rc;
     if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // factor, T, alpha for the current hp
     if ((rc = use_device(g))) return rc;                             // (a BCM over several devices predicts expert by expert)
     TuneScope ts(g);
-    return predict_passes(g, {}, Xt, nt, ((nt + TILE - 1) / TILE) * TILE, g->pred, nullptr, 0, pb);
+    return predict_passes(g, {}, Xt, nt, ((nt + TILE - 1) / TILE) * TILE, g->pred, nullptr, 0, pb, latent);
 }
 
-int cugp_predict(cugp_gp* g, const double* Xt, int nt, double* mean, double* var)
+static int predict_host(cugp_gp* g, const double* Xt, int nt, double* mean, double* var, bool latent)
 {
-    if (!g || !Xt || !mean || !var || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict: bad argument");
     PredBufs pb;
-    int rc = predict_device(g, Xt, nt, &pb);
+    int rc = predict_device(g, Xt, nt, &pb, latent);
     if (rc == CUGP_OK) {
         hipError_t e = hipMemcpyAsync(mean, pb.mean, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(var, pb.var, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream);
@@ -1497,13 +1500,31 @@ int cugp_predict(cugp_gp* g, const double* Xt, int nt, double* mean, double* var
     return rc;
 }
 
+int cugp_predict(cugp_gp* g, const double* Xt, int nt, double* mean, double* var)
+{
+    if (!g || !Xt || !mean || !var || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict: bad argument");
+    return predict_host(g, Xt, nt, mean, var, false);
+}
+
+// cugp_predict's launches with noise_var = 0 in the finish: the same mean bits, var = sf2 - |W_t|^2
+int cugp_predict_latent(cugp_gp* g, const double* Xt, int nt, double* mean, double* var)
+{
+    if (!g || !Xt || !mean || !var || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict_latent: bad argument");
+    return predict_host(g, Xt, nt, mean, var, true);
+}
+
 int cugp_has_inverse(const cugp_gp* g) { return g && !g->pending && g->inverse_valid ? 1 : 0; }
 
 int cugp_predict_enqueue(cugp_gp* g, const double* Xt, int nt, double* host_mv)
 {
+    return cugp_predict_enqueue_form(g, Xt, nt, host_mv, 0);
+}
+
+int cugp_predict_enqueue_form(cugp_gp* g, const double* Xt, int nt, double* host_mv, int latent)
+{
     if (!g || !Xt || !host_mv || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict_enqueue: bad argument");
     PredBufs pb;
-    int rc = predict_device(g, Xt, nt, &pb);
+    int rc = predict_device(g, Xt, nt, &pb, latent != 0);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(host_mv, pb.mean, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     HIPCHK(hipMemcpyAsync(host_mv + nt, pb.var, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, g->stream));
@@ -1541,12 +1562,18 @@ static int pred_chunk_rows(const cugp_gp* g, int count, int nt)
 // cugp_predict.  cugp_predict_fetch waits for it.
 int cugp_predict_rows_enqueue(cugp_gp* g, const double* Xt, int nt, double* drows, void** stream)
 {
+    return cugp_predict_rows_enqueue_form(g, Xt, nt, drows, stream, 0);
+}
+
+// latent != 0: the rows of the latent function, 1/var_f and m/var_f (the same launches, noise_var = 0 in the finish)
+int cugp_predict_rows_enqueue_form(cugp_gp* g, const double* Xt, int nt, double* drows, void** stream, int latent)
+{
     if (!g || !Xt || nt <= 0 || !drows || !stream) return fail(CUGP_ERR_INVALID, "cugp_predict_rows_enqueue: bad argument");
     int rc;
     if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // factor, T, alpha for the current hp
     if ((rc = use_device(g))) return rc;
     TuneScope ts(g);
-    if ((rc = predict_passes(g, {}, Xt, nt, pred_chunk_rows(g, 1, nt), g->pred, drows, 0))) return rc;
+    if ((rc = predict_passes(g, {}, Xt, nt, pred_chunk_rows(g, 1, nt), g->pred, drows, 0, nullptr, latent != 0))) return rc;
     *stream = (void*)g->stream;
     return CUGP_OK;
 }
@@ -2624,6 +2651,12 @@ int cugp_copy_result_row(cugp_gp* g, double* dst)
 // enqueues them one by one (cugp_predict_rows_enqueue).
 int cugp_group_predict_enqueue(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride, void** stream)
 {
+    return cugp_group_predict_enqueue_form(gr, Xt, nt, drows, row_stride, stream, 0);
+}
+
+int cugp_group_predict_enqueue_form(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride,
+                                    void** stream, int latent)
+{
     if (!gr || !Xt || nt <= 0 || !drows || !stream) return CUGP_ERR_INVALID;
     cugp_gp* lead = gr->experts[0];
     const int k = (int)gr->experts.size();
@@ -2635,7 +2668,9 @@ int cugp_group_predict_enqueue(cugp_group* gr, const double* Xt, int nt, double*
     if ((rc = use_device(lead))) return rc;
     TuneScope ts(lead);                                       // the group runs on the lead expert's tuning
     if (!gr->tab_valid && (rc = write_group_table(gr))) return rc;
-    if ((rc = predict_passes(lead, gr->ctx.bt, Xt, nt, pred_chunk_rows(lead, k, nt), gr->pred, drows, row_stride))) return rc;
+    if ((rc = predict_passes(lead, gr->ctx.bt, Xt, nt, pred_chunk_rows(lead, k, nt), gr->pred, drows, row_stride, nullptr,
+                             latent != 0)))
+        return rc;
     *stream = (void*)lead->stream;
     return CUGP_OK;
 }
@@ -2644,6 +2679,14 @@ int cugp_poe_reduce_enqueue(const double* gathered, size_t rstride, int world, i
                             void* stream)
 {
     launch_poe_reduce(gathered, rstride, world, nexperts, nt, dout, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return CUGP_OK;
+}
+
+int cugp_poe_reduce_mode_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, int mode,
+                                 double sf2, double sn2, int with_noise, double* dout, void* stream)
+{
+    launch_poe_reduce_mode(gathered, rstride, world, nexperts, nt, mode, sf2, sn2, with_noise, dout, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return CUGP_OK;
 }

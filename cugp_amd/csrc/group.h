@@ -85,4 +85,20 @@ int cugp_bcm_predict_rows_finish(cugp_bcm* b);
 // k_poe_reduce on `stream`: gathered [world][rstride] -> dout [mean nt | var nt | world x {status, count}]
 int cugp_poe_reduce_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, double* dout,
                             void* stream);
+
+// ---- combination rules on latent rows (cugp_bcm_predict_mode, cugp_bcm_predict_allgather_mode) ----
+// The _form twins of the row producers above: latent == 0 is the call above, the same launches and bits; latent != 0 runs
+// the same launches with noise_var = 0 in k_predict_finish's by-value scalars, so an expert's rows are 1/var_f and
+// m/var_f (var_f = sf2 - |W_t|^2, computed directly).  Layout, batching, passes (tuning key 19) and scratch unchanged.
+int cugp_predict_enqueue_form(cugp_gp* gp, const double* Xt, int nt, double* host_mv, int latent);
+int cugp_predict_rows_enqueue_form(cugp_gp* gp, const double* Xt, int nt, double* drows, void** stream, int latent);
+int cugp_group_predict_enqueue_form(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride,
+                                    void** stream, int latent);
+int cugp_bcm_predict_rows_enqueue_form(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend,
+                                       size_t slot_stride, void* wait_stream, int latent);
+// k_poe_reduce_mode on `stream`: cugp_poe_reduce_enqueue's buffers, the rows latent, rule `mode` (CUGP_COMBINE_*)
+int cugp_poe_reduce_mode_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, int mode,
+                                 double sf2, double sn2, int with_noise, double* dout, void* stream);
+// sf2 = exp(2 theta_f), sn2 = exp(2 theta_n) of the BCM's shared hyper-parameters, as the experts' kernels take them
+int cugp_bcm_prior_scalars(const cugp_bcm* b, double* sf2, double* sn2);
 }  // extern "C"

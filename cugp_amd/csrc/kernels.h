@@ -173,6 +173,10 @@ void launch_predict_finish(const double* Ks, const double* W, const double* alph
 // product of experts over a gathered exchange buffer ([world][rstride]: {status, count, [per][2][nt]}): out = [mean nt |
 // var nt | world x {status, count}], experts summed in global order (expert k = rank k mod world's slot k / world)
 void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s);
+// the same buffer and output with LATENT rows (1/var_f, mean/var_f) combined by rule `mode` (CUGP_COMBINE_*: 0 PoE, 1 gPoE,
+// 2 BCM, 3 rBCM); sf2: the latent prior variance at a test point, sn2 added to the variance when with_noise
+void launch_poe_reduce_mode(const double* g, size_t rstride, int world, int K, int nt, int mode, double sf2, double sn2,
+                            int with_noise, double* out, hipStream_t s);
 
 // ---- vector kernels ----
 void launch_trmv_lower(const double* T, int ld, int npad, const double* x, double* z, hipStream_t s,

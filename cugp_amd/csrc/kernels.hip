@@ -2820,6 +2820,44 @@ __global__ __launch_bounds__(256) void k_poe_reduce(const double* __restrict__ g
     out[nt + t] = tv;
 }
 
+// The weighted combinations of LATENT expert distributions (include/cugp.h: CUGP_COMBINE_*; comm.cpp, bcm.cpp).  g and
+// out as k_poe_reduce's, the rows here p_k = 1/var_f,k and pm_k = m_k/var_f,k (k_predict_finish with noise_var = 0).  Per
+// test point, experts in global order, every operation rounded on its own:
+//   beta_k = 1 (mode 0 POE, 2 BCM) | RN(1 / K) (1 gPoE) | 1/2 log(sf2 p_k) (3 rBCM)
+//   sp += beta_k p_k, spm += beta_k pm_k, sb += beta_k;   prec = sp (+ (1 - sb) / sf2 for modes 2, 3)
+//   var_f = 1 / prec, mean = var_f spm, var = var_f (+ sn2 when with_noise)
+// cugp_poe_combine (bcm.cpp) is the host twin: the same operations in the same order.
+__global__ __launch_bounds__(256) void k_poe_reduce_mode(const double* __restrict__ g, size_t rstride, int world, int K,
+                                                         int nt, int mode, double sf2, double sn2, int with_noise,
+                                                         double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x == 0)
+        for (int r = threadIdx.x; r < world; r += 256) {
+            out[2 * (size_t)nt + 2 * r] = g[(size_t)r * rstride];
+            out[2 * (size_t)nt + 2 * r + 1] = g[(size_t)r * rstride + 1];
+        }
+    if (t >= nt) return;
+    const double bg = 1.0 / (double)K;
+    double sp = 0.0, spm = 0.0, sb = 0.0;
+    for (int k = 0; k < K; k++) {
+        const double* b = g + (size_t)(k % world) * rstride + 2 + (size_t)(k / world) * 2 * nt;
+        const double p = b[t], pm = b[nt + t];
+        double beta = 1.0;
+        if (mode == 1) beta = bg;
+        else if (mode == 3) beta = 0.5 * log(sf2 * p);
+        sp = sp + beta * p;
+        spm = spm + beta * pm;
+        sb = sb + beta;
+    }
+    double prec = sp;
+    if (mode >= 2) prec = sp + (1.0 - sb) / sf2;
+    const double tv = 1.0 / prec;
+    out[t] = tv * spm;
+    out[nt + t] = with_noise ? tv + sn2 : tv;
+}
+
 // ------------------------------------------------------------------------------------------
 // Multi-target regression: m target vectors over the handle's one factorisation (cugp_set_targets).  Everything is
 // target-major, [mpad][npad] with zeros beyond n and beyond m: Y the targets, Z = Y L^-T (k_predict_gemm as it stands),
@@ -3508,6 +3546,13 @@ void launch_predict_finish(const double* Ks, const double* W, const double* alph
 void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s)
 {
     hipLaunchKernelGGL(k_poe_reduce, dim3((nt + 255) / 256), dim3(256), 0, s, g, rstride, world, K, nt, out);
+}
+
+void launch_poe_reduce_mode(const double* g, size_t rstride, int world, int K, int nt, int mode, double sf2, double sn2,
+                            int with_noise, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_poe_reduce_mode, dim3((nt + 255) / 256), dim3(256), 0, s, g, rstride, world, K, nt, mode, sf2,
+                       sn2, with_noise, out);
 }
 
 void launch_trmv_lower(const double* T, int ld, int npad, const double* x, double* z, hipStream_t s, Batch bt)

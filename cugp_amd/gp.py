@@ -5,6 +5,7 @@
 thin call into libcugp.so -- no arithmetic happens in Python.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -14,6 +15,24 @@ from .capi import check, f64, ptr
 
 KERNELS = {"se": capi.CUGP_KERNEL_SE, "matern32": capi.CUGP_KERNEL_MATERN32, "matern52": capi.CUGP_KERNEL_MATERN52}
 KERNEL_NAMES = {v: k for k, v in KERNELS.items()}
+
+
+COMBINE = {"poe": capi.CUGP_COMBINE_POE, "gpoe": capi.CUGP_COMBINE_GPOE, "bcm": capi.CUGP_COMBINE_BCM,
+           "rbcm": capi.CUGP_COMBINE_RBCM}
+
+
+def combine_mode(combine):
+    """"poe" | "gpoe" | "bcm" | "rbcm" -> the C ABI's CUGP_COMBINE_* number; anything else raises ValueError (before any
+    library call)."""
+    if not isinstance(combine, str) or combine.lower() not in COMBINE:
+        raise ValueError("combine must be None or one of %s, not %r" % (sorted(COMBINE), combine))
+    return COMBINE[combine.lower()]
+
+
+def prior_scalars(hp):
+    """(sf2, sn2) = (exp(2 theta_f), exp(2 theta_n)) from a log-hyper vector, by the C library's exp -- the bits the
+    library's own kernels are given (numpy's exp may round differently)."""
+    return math.exp(float(hp[-2]) * 2), math.exp(float(hp[-1]) * 2)
 
 
 def kernel_kind(kernel):
@@ -250,6 +269,14 @@ class Covsum:
         check(capi.lib().cugp_predict(self._h, ptr(Xt), Xt.shape[0], ptr(m), ptr(v)))
         return m, v
 
+    def predict_latent(self, Xtest):
+        """The latent function at the test points (cugp_predict_latent), on the data the handle holds: (mean, var_f) --
+        cugp_predict's mean bit for bit, var_f = sf2 - |W_t|^2 without the noise term."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        m, v = np.empty(Xt.shape[0]), np.empty(Xt.shape[0])
+        check(capi.lib().cugp_predict_latent(self._h, ptr(Xt), Xt.shape[0], ptr(m), ptr(v)))
+        return m, v
+
     def compute_test_joint(self, X, y, Xtest, with_noise=True):
         """Joint predictive distribution at the test points (cugp_predict_cov): (mean [nt], cov [nt, nt]), cov =
         k(Xt,Xt) - Ks K^-1 Ks^T (+ sigma_n^2 I with noise), exactly symmetric; mean has cugp_predict's bits."""
@@ -382,13 +409,26 @@ class Comm:
             check(capi.lib().cugp_bcm_loglik_grad_allgather(h, self._h, int(per), ptr(out)))
         return out
 
-    def predict_allgather(self, bcm, per, nexperts, Xt):
+    def predict_allgather(self, bcm, per, nexperts, Xt, combine=None, with_noise=True, sf2=None, sn2=None):
         """Product-of-experts prediction across the ranks (cugp_bcm_predict_allgather): this rank's experts (`bcm`, or
         None on a rank that owns none) predict Xt, one all-gather moves every rank's rows, the product of experts over
-        all `nexperts` experts in expert order -> (mean, var).  Every rank passes the same per, nexperts and Xt."""
+        all `nexperts` experts in expert order -> (mean, var).  Every rank passes the same per, nexperts and Xt.
+        combine: None, or "poe" | "gpoe" | "bcm" | "rbcm" -- the rule on the experts' latent distributions
+        (cugp_bcm_predict_allgather_mode); then sf2 = exp(2 theta_f) and sn2 = exp(2 theta_n) are needed on every rank
+        (a rank without experts has no BCM to read them from; with a BCM they default to its hyper-parameters')."""
+        mode = None if combine is None else combine_mode(combine)
         Xt = f64(Xt)
         nt = Xt.shape[0]
         m, v = np.empty(nt), np.empty(nt)
+        if mode is not None:
+            if sf2 is None or sn2 is None:
+                if bcm is None:
+                    raise ValueError("a rank without experts must pass sf2 and sn2")
+                sf2, sn2 = bcm.prior_scalars()
+            check(capi.lib().cugp_bcm_predict_allgather_mode(bcm._h if bcm is not None else None, self._h, int(per),
+                                                             int(nexperts), ptr(Xt), nt, mode, 1 if with_noise else 0,
+                                                             float(sf2), float(sn2), ptr(m), ptr(v)))
+            return m, v
         check(capi.lib().cugp_bcm_predict_allgather(bcm._h if bcm is not None else None, self._h, int(per),
                                                     int(nexperts), ptr(Xt), nt, ptr(m), ptr(v)))
         return m, v
@@ -547,6 +587,25 @@ class BCM:
         check(capi.lib().cugp_bcm_predict(self._h, ptr(Xt), Xt.shape[0], ptr(m), ptr(v)))
         return m, v
 
+    def prior_scalars(self):
+        """(sf2, sn2) = (exp(2 theta_f), exp(2 theta_n)) of the shared hyper-parameters, as the library forms them."""
+        hp = self.get_loghyperparam()
+        return prior_scalars(hp)
+
+    def predict(self, Xt, combine=None, with_noise=True):
+        """(mean, var) at Xt.  combine=None: the reference's product of the experts' noisy predictions
+        (compute_BCM_test_means_and_var, its bits; with_noise is not read).  "poe" | "gpoe" | "bcm" | "rbcm": the rule on
+        the experts' latent distributions (cugp_bcm_predict_mode; include/cugp.h: CUGP_COMBINE_*), var with sn2 added
+        when with_noise."""
+        if combine is None:
+            return self.compute_BCM_test_means_and_var(Xt)
+        mode = combine_mode(combine)
+        Xt = f64(Xt).reshape(-1, self.d)
+        m, v = np.empty(Xt.shape[0]), np.empty(Xt.shape[0])
+        check(capi.lib().cugp_bcm_predict_mode(self._h, ptr(Xt), Xt.shape[0], mode, 1 if with_noise else 0, ptr(m),
+                                               ptr(v)))
+        return m, v
+
     get_BCM_negative_log_predprob = staticmethod(Covsum.get_negative_log_predprob)
 
     def cg_solve(self, budget=100):
@@ -562,6 +621,19 @@ def poe_finish(sum_prec, sum_prec_mean):
     sp, spm = f64(sum_prec), f64(sum_prec_mean)
     m, v = np.empty_like(sp), np.empty_like(sp)
     check(capi.lib().cugp_poe_finish(ptr(sp), ptr(spm), sp.shape[0], ptr(m), ptr(v)))
+    return m, v
+
+
+def poe_combine(rows, mode, sf2, sn2, with_noise=True):
+    """cugp_poe_combine: the combination rule `mode` ("poe" | "gpoe" | "bcm" | "rbcm", or the CUGP_COMBINE_* number) on
+    latent rows [K, 2, nt] (1/var_f, m/var_f per expert) -> (mean, var); pure host code, needs no GPU."""
+    rows = f64(rows)
+    if rows.ndim != 3 or rows.shape[1] != 2:
+        raise ValueError("rows must be [K, 2, nt]")
+    K, _, nt = rows.shape
+    m, v = np.empty(nt), np.empty(nt)
+    check(capi.lib().cugp_poe_combine(ptr(rows), K, nt, combine_mode(mode) if isinstance(mode, str) else int(mode),
+                                      float(sf2), float(sn2), 1 if with_noise else 0, ptr(m), ptr(v)))
     return m, v
 
 

@@ -32,6 +32,9 @@ def main():
     ap.add_argument("--ard", action="store_true",
                     help="one length scale per input dimension (squared exponential only): the start is "
                          "[hp0] * d + [hp1, hp2]")
+    ap.add_argument("--combine", default=None, choices=["poe", "gpoe", "bcm", "rbcm"],
+                    help="how the held-out prediction combines the experts' LATENT distributions (with the noise added "
+                         "for the NLPP); absent: the reference's product of the noisy predictions")
     args = ap.parse_args()
 
     import torch
@@ -65,7 +68,7 @@ def main():
     if args.test_rows > 0:
         s0 = dataset.load_chunk("%s0.txt" % args.inputs, "%s0.txt" % args.labels)
         Xt, yt = s0[0][args.rows:args.rows + args.test_rows], s0[1][args.rows:args.rows + args.test_rows]
-        m, v = bcm.predict(Xt)
+        m, v = bcm.predict(Xt, combine=args.combine, with_noise=True)
         if rank == 0:
             print("NLPP = %.12g" % Covsum.get_negative_log_predprob(yt, m, v))
     bcm.close()

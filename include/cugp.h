@@ -135,6 +135,11 @@ int cugp_last_quad_logdet(const cugp_gp *gp, double *quad, double *logdet);
  *      noise term, :316) ; compute_k_test :105-116 ; get_negative_log_predprob :649-659 ; testing_phase
  *      cuda_src/cuda_gp.cu:2063 ---- */
 int cugp_predict(cugp_gp *gp, const double *Xt, int nt, double *mean, double *var);
+/* the LATENT function at the test points (no reference counterpart): mean = cugp_predict's, bit for bit, by the same
+ * launches; var = sf2 - |W_t|^2 (W = Ks L^-T), the variance of f without the noise term, computed directly -- never as
+ * cugp_predict's variance minus sn2.  Works on every handle cugp_predict works on (SE, Matern, ARD, padded handles, BCM
+ * experts); a stale handle is evaluated first.  CUGP_ERR_INVALID for a NULL argument or nt <= 0, before any device call. */
+int cugp_predict_latent(cugp_gp *gp, const double *Xt, int nt, double *mean, double *var);
 /* ---- joint predictive distribution: extends the marginal form of Covsum::compute_test_means_and_variances
  *      covkernel.cpp:277-323 (the noise term as at :316) to the covariance between the test points; the reference has
  *      no joint counterpart.  Both work on every handle cugp_predict works on (padded handles, BCM experts), at the
@@ -359,6 +364,44 @@ int cugp_bcm_predict(cugp_bcm *b, const double *Xt, int nt, double *mean, double
 int cugp_bcm_predict_allgather(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt,
                                double *mean, double *var);
 int cugp_bcm_cg_solve(cugp_bcm *b, int budget, double *trace, int trace_cap, int *nevals);
+/* ---- combination rules for the experts' predictions.  The reference has no counterpart: cugp_bcm_predict keeps its plain
+ *      product of the experts' NOISY predictive distributions (BCM.cpp:45-62), whose variance falls to prior / K away from
+ *      the data and below sn2 near it.  The rules below combine the experts' LATENT distributions N(m_k, var_f,k),
+ *      var_f,k = sf2 - |W_t|^2 (cugp_predict_latent), with p_k = 1 / var_f,k and the latent prior variance sf2 = exp(2 theta_f)
+ *      (k(x, x) - sn2 = sf2 for every family):
+ *        CUGP_COMBINE_POE   beta_k = 1,                   prec = sum p_k                      product of experts
+ *        CUGP_COMBINE_GPOE  beta_k = 1 / K,               prec = sum beta_k p_k               Cao & Fleet 2014, generalised PoE
+ *        CUGP_COMBINE_BCM   beta_k = 1,                   prec = sum p_k + (1 - K) / sf2      Tresp 2000, Bayesian committee machine
+ *        CUGP_COMBINE_RBCM  beta_k = 1/2 log(sf2 p_k),    prec = sum beta_k p_k + (1 - sum beta_k) / sf2
+ *                                                                                             Deisenroth & Ng 2015, robust BCM
+ *        var_f = 1 / prec,  mean = var_f sum beta_k p_k m_k,  var = var_f (+ sn2 when with_noise)
+ *      CUGP_COMBINE_POE therefore combines LATENT distributions and differs from cugp_bcm_predict, which keeps the
+ *      reference's noisy product.  Arithmetic, per test point, experts in global order, every operation rounded on its own
+ *      (no contraction): sp += beta_k p_k; spm += beta_k pm_k (pm_k = p_k m_k, rounded when the row is made); sb += beta_k;
+ *      prec = sp, or sp + (1 - sb) / sf2; tv = 1 / prec; mean = tv spm; the gPoE weight is RN(1 / K), computed once.
+ *      var_f,k <= sf2, so beta_k >= 0 and prec >= 1 / sf2 for BCM and rBCM.  A var_f,k that is not positive, or NaN,
+ *      propagates by IEEE: NaN / inf results with CUGP_OK (the header's convention).
+ * cugp_poe_combine: the rule on caller rows [K][2][nt] (expert k: p_k at rows[k][0][t], pm_k at rows[k][1][t]); pure host
+ *      code, no device.  It is the twin of the device kernel k_poe_reduce_mode: the same operations in the same order, so
+ *      modes POE, GPOE and BCM (no transcendental) agree with the device bit for bit; RBCM uses each side's own log and
+ *      agrees to rounding.
+ * cugp_bcm_predict_mode: all experts of b at Xt.  Stale experts are refreshed as cugp_bcm_predict refreshes them.  One
+ *      device set: latent rows by one group of batched launches, the rule on the device, one copy, one host wait.
+ *      Several device sets of one process: the experts' latent predictions into pinned host memory, then cugp_poe_combine.
+ * cugp_bcm_predict_allgather_mode: cugp_bcm_predict_allgather (above: same arguments, same ONE ncclAllGather, one host
+ *      wait, same status protocol and error rules) with latent rows and the rule on the device.  sf2 and sn2 are arguments
+ *      because a rank that owns no expert has no BCM to read them from: every rank passes exp(2 theta_f), exp(2 theta_n).
+ * All work for isotropic BCMs of every kernel kind and for ARD BCMs.  CUGP_ERR_INVALID -- before any device call or
+ * collective -- for an unknown mode, a NULL argument, K <= 0 or nt <= 0. */
+#define CUGP_COMBINE_POE 0
+#define CUGP_COMBINE_GPOE 1
+#define CUGP_COMBINE_BCM 2
+#define CUGP_COMBINE_RBCM 3
+int cugp_poe_combine(const double *rows /* [K][2][nt] */, int K, int nt, int mode, double sf2, double sn2, int with_noise,
+                     double *mean, double *var);
+int cugp_bcm_predict_mode(cugp_bcm *b, const double *Xt, int nt, int mode, int with_noise, double *mean, double *var);
+int cugp_bcm_predict_allgather_mode(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt, int mode,
+                                    int with_noise, double sf2, double sn2, double *mean, double *var);
 /* ---- ARD BCM: every expert an ARD handle (squared exponential, theta as cugp_create_ard's: nh = d + 2 entries shared by
  *      all experts).  The reference has no counterpart.  The experts run as groups of shared launches, over several
  *      devices of one process, or sharded one process per GPU, exactly like isotropic experts; only the rows of an
