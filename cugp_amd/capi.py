@@ -22,6 +22,7 @@ OBJECTIVE_N = C.CFUNCTYPE(None, C.c_void_p, _dp, C.c_int, _dp, _dp)
 CUGP_OK = 0
 CUGP_KERNEL_SE, CUGP_KERNEL_MATERN32, CUGP_KERNEL_MATERN52 = 0, 1, 2
 CUGP_COMBINE_POE, CUGP_COMBINE_GPOE, CUGP_COMBINE_BCM, CUGP_COMBINE_RBCM = 0, 1, 2, 3
+CUGP_COMBINE_REFERENCE = -1      # cugp_bcm_predict_grad / cugp_poe_combine_grad: the reference's product of the noisy predictions
 CUGP_ERR_INVALID, CUGP_ERR_NOMEM, CUGP_ERR_DEVICE, CUGP_ERR_NODEVICE = -1, -2, -3, -4
 ERR_NAMES = {-1: "CUGP_ERR_INVALID", -2: "CUGP_ERR_NOMEM", -3: "CUGP_ERR_DEVICE", -4: "CUGP_ERR_NODEVICE",
              -5: "CUGP_ERR_BUSY"}
@@ -64,6 +65,7 @@ SIGNATURES = {
     "cugp_last_quad_logdet": (C.c_int, [C.c_void_p, _dp, _dp]),
     "cugp_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     "cugp_predict_latent": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
+    "cugp_predict_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "cugp_predict_cov": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
     "cugp_predict_sample": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp]),
     "cugp_nlpp": (C.c_int, [_dp, _dp, _dp, C.c_int, _dp]),
@@ -125,6 +127,8 @@ SIGNATURES = {
     "cugp_bcm_cg_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_poe_combine": (C.c_int, [_dp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp]),
     "cugp_bcm_predict_mode": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_poe_combine_grad": (C.c_int, [_dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp]),
+    "cugp_bcm_predict_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "cugp_bcm_predict_allgather_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
                                                   C.c_double, C.c_double, _dp, _dp]),
     "cugp_bcm_create_ard": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_void_p)]),

@@ -754,6 +754,127 @@ int cugp_bcm_predict_mode(cugp_bcm* b, const double* Xt, int nt, int mode, int w
     return cugp_poe_combine(b->pred_host.p, (int)K, nt, mode, sf2, sn2, with_noise, mean, var);
 }
 
+// ---- gradients of the combined prediction with respect to the test inputs (include/cugp.h: cugp_poe_combine_grad) ----
+// The chain rule of the rules above on the experts' (mean, variance) and their gradients, experts in order, every operation
+// rounded on its own.  Per test point: p_k = 1 / v_k, beta_k and prec as cugp_poe_combine forms them (from v_k here, not from
+// rows); then per input dimension
+//   dp = -dv / v^2,  dbeta = 0 | -1/2 dv / v (rbcm),  a_k = dbeta p + beta dp,  dprec = sum a_k - [bcm, rbcm] (sum dbeta) / sf2
+//   dvar = -dprec / prec^2
+//   dmean = dvar S + dS / prec,  S = sum beta p m,  dS = sum (a_k m_k + beta p dm_k), evaluated as
+//         = sum w_k dm_k + (sum a_k (m_k - mean)) / prec + [bcm, rbcm] mean ((sum dbeta) / sf2) / prec,
+//     w_k = (beta_k p_k) / prec,  mean = sum w_k m_k
+// -- the same expression (dS - mean dprec) / prec with the DIFFERENCE m_k - mean formed first: dvar S and dS / prec are each
+// of the size of |dv p m| and cancel to the size of dm where the experts agree (one expert: w = 1, mean = m and dmean = dm
+// exactly).  CUGP_COMBINE_REFERENCE takes POE's arithmetic: the caller passes the experts' NOISY variances (their gradients
+// are the latent ones').
+int cugp_poe_combine_grad(const double* mean, const double* var, const double* dmean, const double* dvar, int K, int nt,
+                          int d, int mode, double sf2, double* out_dmean, double* out_dvar)
+{
+#pragma clang fp contract(off)
+    if (!mean || !var || !dmean || !dvar || !out_dmean || !out_dvar || K <= 0 || nt <= 0 || d <= 0 ||
+        mode < CUGP_COMBINE_REFERENCE || mode > CUGP_COMBINE_RBCM)
+        return cugp_internal_fail(CUGP_ERR_INVALID,
+                                  "cugp_poe_combine_grad: null argument, K <= 0, nt <= 0, d <= 0 or an unknown mode");
+    const double bg = 1.0 / (double)K;
+    const bool prior = mode >= CUGP_COMBINE_BCM;
+    std::vector<double> pk(K), bk(K), wk(K);
+    for (int t = 0; t < nt; t++) {
+        double sp = 0.0, sb = 0.0;
+        for (int k = 0; k < K; k++) {
+            const double p = 1.0 / var[(size_t)k * nt + t];
+            double beta = 1.0;
+            if (mode == CUGP_COMBINE_GPOE) beta = bg;
+            else if (mode == CUGP_COMBINE_RBCM) beta = 0.5 * std::log(sf2 * p);
+            pk[k] = p;
+            bk[k] = beta;
+            wk[k] = beta * p;
+            sp = sp + wk[k];
+            sb = sb + beta;
+        }
+        double prec = sp;
+        if (prior) prec = sp + (1.0 - sb) / sf2;
+        double mu = 0.0;
+        for (int k = 0; k < K; k++) {
+            wk[k] = wk[k] / prec;
+            mu = mu + wk[k] * mean[(size_t)k * nt + t];
+        }
+        for (int c = 0; c < d; c++) {
+            double dprec = 0.0, sdm = 0.0, sam = 0.0, sdb = 0.0;
+            for (int k = 0; k < K; k++) {
+                const size_t e = ((size_t)k * nt + t) * d + c;
+                const double v = var[(size_t)k * nt + t], dv = dvar[e];
+                double a = bk[k] * -(dv / (v * v));
+                if (mode == CUGP_COMBINE_RBCM) {
+                    const double db = -0.5 * (dv / v);
+                    a = db * pk[k] + a;
+                    sdb = sdb + db;
+                }
+                dprec = dprec + a;
+                sdm = sdm + wk[k] * dmean[e];
+                sam = sam + a * (mean[(size_t)k * nt + t] - mu);
+            }
+            double dmo = sdm + sam / prec;
+            if (prior) {
+                const double pr = sdb / sf2;
+                dprec = dprec - pr;
+                dmo = dmo + (mu * pr) / prec;
+            }
+            out_dvar[(size_t)t * d + c] = -(dprec / (prec * prec));
+            out_dmean[(size_t)t * d + c] = dmo;
+        }
+    }
+    return CUGP_OK;
+}
+
+// cugp_predict_grad expert by expert (each on its own device: a BCM over several devices of one process works), then the
+// rule on the host.  mode >= 0: the experts' latent distributions through rows made as poe_row makes them and
+// cugp_poe_combine; CUGP_COMBINE_REFERENCE: their noisy predictions through the two sums of cugp_bcm_predict_partial and
+// cugp_poe_finish (with_noise is then not read).  Stale experts are refreshed first, as every BCM prediction does.
+int cugp_bcm_predict_grad(cugp_bcm* b, const double* Xt, int nt, int mode, int with_noise, double* mean, double* var,
+                          double* dmean, double* dvar)
+{
+    if (!b || !Xt || nt <= 0 || (!dmean && !dvar) || mode < CUGP_COMBINE_REFERENCE || mode > CUGP_COMBINE_RBCM)
+        return cugp_internal_fail(CUGP_ERR_INVALID,
+                                  "cugp_bcm_predict_grad: null BCM or Xt, nt <= 0, neither dmean nor dvar given, or an unknown mode");
+    const size_t K = b->experts.size(), d = (size_t)b->d, n1 = (size_t)nt, nd = n1 * d;
+    const bool reference = mode == CUGP_COMBINE_REFERENCE;
+    double sf2, sn2;
+    int rc;
+    if ((rc = cugp_bcm_prior_scalars(b, &sf2, &sn2)) || (rc = bcm_refresh(b))) return rc;
+    std::vector<double> m(K * n1), v(K * n1), dm(K * nd), dv(K * nd), rows(K * 2 * n1), om(n1), ov(n1), odm(nd), odv(nd);
+    for (size_t k = 0; k < K; k++)
+        if ((rc = cugp_predict_grad(b->experts[k], Xt, nt, reference ? 1 : 0, m.data() + k * n1, v.data() + k * n1,
+                                    dm.data() + k * nd, dv.data() + k * nd)))
+            return rc;
+    if (reference) {
+        std::vector<double> sp(n1, 0.0), spm(n1, 0.0);
+        for (size_t k = 0; k < K; k++)
+            for (size_t i = 0; i < n1; i++) {                  // BCM.cpp:51-55, as cugp_bcm_predict_partial
+                const double inv = 1.0 / v[k * n1 + i];
+                sp[i] += inv;
+                spm[i] += inv * m[k * n1 + i];
+            }
+        if ((rc = cugp_poe_finish(sp.data(), spm.data(), nt, om.data(), ov.data()))) return rc;
+    } else {
+        for (size_t k = 0; k < K; k++)
+            for (size_t i = 0; i < n1; i++) {                  // poe_row's operations
+#pragma clang fp contract(off)
+                const double inv = 1.0 / v[k * n1 + i], pm = inv * m[k * n1 + i];
+                rows[k * 2 * n1 + i] = inv;
+                rows[k * 2 * n1 + n1 + i] = pm;
+            }
+        if ((rc = cugp_poe_combine(rows.data(), (int)K, nt, mode, sf2, sn2, with_noise, om.data(), ov.data()))) return rc;
+    }
+    if ((rc = cugp_poe_combine_grad(m.data(), v.data(), dm.data(), dv.data(), (int)K, nt, (int)d, mode, sf2, odm.data(),
+                                    odv.data())))
+        return rc;
+    if (mean) memcpy(mean, om.data(), n1 * sizeof(double));
+    if (var) memcpy(var, ov.data(), n1 * sizeof(double));
+    if (dmean) memcpy(dmean, odm.data(), nd * sizeof(double));
+    if (dvar) memcpy(dvar, odv.data(), nd * sizeof(double));
+    return CUGP_OK;
+}
+
 namespace {
 void bcm_objective(void* ctx, const double th[3], double* f, double g[3])
 {

@@ -57,7 +57,7 @@ constexpr int PROF_STRIDE = 16; // profiling level 2 times every 16th step launc
 // kinds of timed launches (cugp_get_kernel_stats_kind): the kernels as rocprofv3 names them
 enum { KIND_STEP = 0, KIND_WIDE = 1, KIND_BORDER4 = 2, KIND_BORDER2 = 3, KIND_LAUUM4 = 4, KIND_LAUUM2 = 5,
        KIND_LEVEL4 = 6, KIND_LEVEL2 = 7, KIND_BLOCK = 8, KIND_PREDICT = 9, KIND_BUILD = 10, KIND_TRSM = 11, KIND_COV = 12,
-       KIND_COUNT = 13 };
+       KIND_PGRAD = 13, KIND_COUNT = 14 };
 
 // One hardware queue per stream up to 16 (the runtime default is 4): the experts of a BCM on one device each
 // drive their own stream, and 16 experts on 4 queues serialise (5.8 ms vs 4.6 ms per evaluation of 16 x 1500
@@ -1511,6 +1511,100 @@ int cugp_predict_latent(cugp_gp* g, const double* Xt, int nt, double* mean, doub
 {
     if (!g || !Xt || !mean || !var || nt <= 0) return fail(CUGP_ERR_INVALID, "cugp_predict_latent: bad argument");
     return predict_host(g, Xt, nt, mean, var, true);
+}
+
+// ---------------------------------------------------------------- gradients with respect to the test inputs
+// Test points per pass of cugp_predict_grad: tuning key TUNE_PRED_CHUNK in 64-row tiles, or (0) as many as keep Ks, W, V
+// and the tiles' partial sums of one pass within 1 GiB, in whole 128-row tiles.  Every test row is computed on its own,
+// so the bits do not depend on it.
+static int grad_chunk_rows(const cugp_gp* g, int nt)
+{
+    long long rows = (long long)g->tune[TUNE_PRED_CHUNK] * 64;
+    if (rows <= 0) {
+        const size_t per_row = ((size_t)3 * g->npad + (size_t)2 * predict_grad_tiles(g->n) * g->d) * sizeof(double);
+        rows = (long long)((((size_t)1 << 30) / per_row) / TILE) * TILE;
+        if (rows < TILE) rows = TILE;
+    }
+    const long long ntr = ((long long)nt + 63) / 64 * 64;
+    return (int)(rows < ntr ? rows : ntr);
+}
+
+// mean, variance and their gradients with respect to the test inputs (include/cugp.h).  Per pass of test points on the
+// handle's stream: k_cross, k_predict_gemm, k_predict_finish exactly as predict_passes launches them (the mean's and the
+// variance's bits are cugp_predict's / cugp_predict_latent's), then -- dvar wanted -- V = W L^-1 by launch_targets_alpha,
+// k_predict_grad (partial sums per training tile) and k_predict_grad_finish.  One path whatever else the handle holds: V
+// is always W L^-1, never Ks K^-1.  All results stay in the scratch until the one copy and the one host wait at the end.
+int cugp_predict_grad(cugp_gp* g, const double* Xt, int nt, int with_noise, double* mean, double* var, double* dmean,
+                      double* dvar)
+{
+    if (!g || !Xt || nt <= 0 || (!dmean && !dvar))
+        return fail(CUGP_ERR_INVALID, "cugp_predict_grad: null handle or Xt, nt <= 0, or neither dmean nor dvar given");
+    int rc;
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // (fetches an evaluation in flight; factor, T, U, alpha for the current hp)
+    if ((rc = use_device(g))) return rc;
+    TuneScope ts(g);
+    hipStream_t s = g->stream;
+    const int chunk = grad_chunk_rows(g, nt), cmax = chunk < nt ? chunk : nt, ntpad = ((cmax + TILE - 1) / TILE) * TILE;
+    const int d = g->d, tiles = predict_grad_tiles(g->n);
+    const size_t nxt = (((size_t)nt * d + 15) / 16) * 16, nks = (size_t)ntpad * g->npad, pstride = (size_t)cmax * d;
+    const size_t npart = (size_t)tiles * 2 * pstride, nout = (size_t)nt * d;
+    if ((rc = g->pred.grow(nxt + 3 * nks + npart + 2 * (size_t)nt + 2 * nout, s))) return rc;
+    double* dXt = g->pred.p;
+    double* dKs = dXt + nxt;
+    double* dW = dKs + nks;
+    double* dV = dW + nks;
+    double* dP = dV + nks;
+    double* dm = dP + npart;
+    double* dv = dm + nt;
+    double* dgm = dv + nt;
+    double* dgv = dgm + nout;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * d * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = reset_stamps(g))) return rc;
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int c = nt - t0 < chunk ? nt - t0 : chunk;
+        const int cpad = ((c + TILE - 1) / TILE) * TILE;
+        const double gemm_flop = (double)cpad * g->npad * g->npad;   // a triangular product: the diagonal k tile counted half
+        CovFn cf;
+        if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+        launch_kcross(g->dX, g->n, d, g->npad, dXt + (size_t)t0 * d, c, cpad, cf, dKs, s);
+        {
+            TimedLaunch tl(g, s, g->prof >= 3);
+            launch_predict_gemm(dKs, g->dT, dW, g->npad, cpad / TILE, g->nt, s);
+            tl.done(KIND_PREDICT, gemm_flop);
+        }
+        HyperScalars hf = cf.h;
+        if (!with_noise) hf.noise_var = 0.0;
+        launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, hf, dm + t0, dv + t0, s);
+        if (dvar) {
+            // V = W L^-1 (row t = K^-1 k*_t): W is zero in its columns >= n and its rows >= c, U's padding is identity.
+            // launch_targets_alpha takes no launch-own events: timed by an event pair around it (levels 3 and 4).
+            const bool timed = (g->prof == 3 || g->prof == 4) && g->kev_used + 2 <= (int)g->kev.size() &&
+                               hipEventRecord(g->kev[g->kev_used], s) == hipSuccess;
+            launch_targets_alpha(dW, g->dU, dV, g->npad, cpad, s);
+            if (timed && hipEventRecord(g->kev[g->kev_used + 1], s) == hipSuccess) {
+                g->kev_prev[g->kev_used / 2] = -1;
+                g->kev_kind[g->kev_used / 2] = KIND_PREDICT;
+                g->kev_flopv[g->kev_used / 2] = gemm_flop;
+                g->kev_used += 2;
+            }
+        }
+        {
+            TimedLaunch tl(g, s, g->prof >= 3);
+            launch_predict_grad(g->dX, g->n, d, g->npad, dXt + (size_t)t0 * d, c, cf, dKs, dvar ? dV : nullptr, g->dalpha,
+                                dP, pstride, s);
+            tl.done(KIND_PGRAD, (dvar ? 2.0 : 1.0) * ((c + 63) / 64 * 64) * (double)tiles * 64 * sizeof(double));
+        }
+        launch_predict_grad_finish(dP, pstride, g->n, c, d, cf, dgm + (size_t)t0 * d, dvar ? dgv + (size_t)t0 * d : nullptr, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && mean) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && dmean) e = hipMemcpyAsync(dmean, dgm, nout * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && dvar) e = hipMemcpyAsync(dvar, dgv, nout * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);                // the one host wait
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return fail(CUGP_ERR_DEVICE, "cugp_predict_grad", e); }
+    if (g->prof >= 2) drain_kernel_events(g);
+    return CUGP_OK;
 }
 
 int cugp_has_inverse(const cugp_gp* g) { return g && !g->pending && g->inverse_valid ? 1 : 0; }

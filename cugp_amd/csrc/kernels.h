@@ -170,6 +170,19 @@ void launch_sample_finish(const double* F, int ld, const double* mean, int nt, i
 void launch_predict_finish(const double* Ks, const double* W, const double* alpha, int n, int npad, int ntest,
                            HyperScalars h, double* mean, double* var, hipStream_t s, double* rows = nullptr,
                            size_t rstride = 0, int rhalf = 0, int ntpad = 0, Batch bt = {});
+// ---- gradients of the prediction with respect to the test inputs (cugp_predict_grad) ----
+// Per 64 x 64 (test x training) tile the partial sums over the tile's training rows of (G alpha_i)(x*_c - x_ic) and, V
+// given, (G V_ti)(x*_c - x_ic):  part[(ti * 2 + q) * pstride + t * d + c], ti < predict_grad_tiles(n), q = 0 mean / 1
+// variance, t < nt, pstride >= nt * d.  Xt: the pass's nt test points; Ks (k_cross's output) and V = W L^-1
+// (launch_targets_alpha(W, U, V, npad, rows of the pass padded to 128)) are [>= nt rounded up to 64][npad]; V null: the
+// mean's sums alone.  The finish adds the tiles in index order and writes dmean = -s_c sum, dvar = 2 s_c sum, packed
+// [nt][d] (either may be null; dvar only where the tile launch had V).
+constexpr int predict_grad_tiles(int n) { return (n + 63) / 64; }
+void launch_predict_grad(const double* X, int n, int d, int npad, const double* Xt, int nt, const CovFn& cf,
+                         const double* Ks, const double* V, const double* alpha, double* part, size_t pstride,
+                         hipStream_t s);
+void launch_predict_grad_finish(const double* part, size_t pstride, int n, int nt, int d, const CovFn& cf, double* dmean,
+                                double* dvar, hipStream_t s);
 // product of experts over a gathered exchange buffer ([world][rstride]: {status, count, [per][2][nt]}): out = [mean nt |
 // var nt | world x {status, count}], experts summed in global order (expert k = rank k mod world's slot k / world)
 void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s);

@@ -2793,6 +2793,190 @@ __global__ __launch_bounds__(256) void k_predict_finish(const double* __restrict
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Gradients of the predictive mean and variance with respect to the test inputs (cugp_predict_grad).  With
+// k_i = k(x*, x_i), dk_i / dx*_c = -G_i (x*_c - x_ic) s_c  (G: SE and ARD k_i, Matern 3/2 sf2 3 e^-a, 5/2 sf2 (5/3)(1 + a) e^-a;
+// s_c = 1 / l^2, ARD w_c^2), v = K^-1 k* = row t of V = W L^-1:
+//   dmean[t][c] = -s_c sum_i (G alpha_i) (x*_c - x_ic),     dvar[t][c] = +2 s_c sum_i (G V_ti) (x*_c - x_ic)
+// One 64 x 64 (test x training) tile per workgroup, the thread's 4 x 4 micro-tile and column pairs as cross_body's (16-byte
+// loads of Ks and V rows).  SE and ARD read G from Ks (k_cross's own exp, no second one: the ARD weights enter through the
+// finish alone, so one instantiation serves both); the Matern kinds accumulate the squared distance as sqdist_4x4 does
+// (difference, square, add, in feature order, no contraction) and take one exp(-a) per entry.  Per feature, X and Xt staged
+// through LDS DC features at a time: the DIFFERENCE x*_c - x_ic is formed first and then multiplied -- the algebraically
+// equal x*_c sum(G alpha) - sum(G alpha x_c) cancels where |x| >> |x - x'|.  A thread adds its four columns in index order,
+// the 16 lanes of a row add by a butterfly of fixed shape (lane distances 1, 2, 4, 8; a + b == b + a, so all 16 hold the same
+// bits), and lane c mod 16 writes the tile's partial sum: part[(ti * 2 + q) * pstride + t * d + c], q = 0 mean, 1 variance.
+// No atomics; a row's sums do not depend on where in a tile or a pass the row lies.  Entries beyond row nt of Xt or row n
+// of X contribute exact zeros (G alpha and G V are set to 0.0 there, the staged coordinates too) and are never read from
+// X or Xt; Ks and V are [.. >= 64 * tiles][npad] and read inside that.
+// k_predict_grad_finish adds the tiles' partial sums in tile order and applies -s_c and +2 s_c once per output.
+// ------------------------------------------------------------------------------------------
+template <int KIND>
+__device__ __forceinline__ void predict_grad_body(const double* __restrict__ X, int n, int d, int npad,
+                                                  const double* __restrict__ Xt, int nt, HyperScalars h,
+                                                  const double* __restrict__ Ks, const double* __restrict__ V,
+                                                  const double* __restrict__ alpha, double* __restrict__ part,
+                                                  size_t pstride)
+{
+#pragma clang fp contract(off)
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    const int tiles_i = (n + KT - 1) / KT;
+    const int tt = blockIdx.x / tiles_i, ti = blockIdx.x % tiles_i;
+    const int t0 = tt * KT, i0 = ti * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    // one chunk of features of the tile's test rows (xs) and training rows (ys) into LDS, zeros beyond nt and n
+    auto stage = [&](int c0, int dc) {
+        __syncthreads();
+        for (int e = t; e < KT * dc; e += 256) {
+            const int r = e / dc, c = e - r * dc;
+            xs[r][c] = (t0 + r < nt) ? Xt[(size_t)(t0 + r) * d + c0 + c] : 0.0;
+            ys[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
+        }
+        __syncthreads();
+    };
+    double G[4][4];
+    if constexpr (KIND != KERNEL_SE) {
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) G[a][b] = 0.0;
+        for (int c0 = 0; c0 < d; c0 += DC) {
+            const int dc = (d - c0 < DC) ? (d - c0) : DC;
+            stage(c0, dc);
+            for (int c = 0; c < dc; c++) {
+                double xv[4], yv[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        const double df = xv[a] - yv[b];
+                        G[a][b] = G[a][b] + df * df;
+                    }
+            }
+        }
+        const DivBy dl = div_prepare(h.ell_sq);
+        const double cc = KIND == KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979;
+#pragma unroll
+        for (int a = 0; a < 4; a++)
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const double av = cc * __builtin_sqrt(div_by(G[a][b], dl));
+                const double e = exp(-av);
+                // (e == 0: a = +inf or an exp that underflowed -- G is 0 exactly, never inf * 0)
+                const double p = KIND == KERNEL_MATERN32 ? 3.0 : 1.6666666666666667 * (1.0 + av);
+                G[a][b] = e == 0.0 ? 0.0 : h.signal_var * (p * e);
+            }
+    }
+    double ga[4][4], gv[4][4];
+    double al[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int i = i0 + col4(tx, b);
+        al[b] = i < n ? alpha[i] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int tr = t0 + ty * 4 + a;
+        const size_t off = (size_t)tr * npad + i0 + tx * 2;
+        double vv[4] = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (KIND == KERNEL_SE) {
+            const d2 k01 = *(const d2*)(Ks + off), k23 = *(const d2*)(Ks + off + 32);
+            G[a][0] = k01[0]; G[a][1] = k01[1]; G[a][2] = k23[0]; G[a][3] = k23[1];
+        }
+        if (V) {
+            const d2 v01 = *(const d2*)(V + off), v23 = *(const d2*)(V + off + 32);
+            vv[0] = v01[0]; vv[1] = v01[1]; vv[2] = v23[0]; vv[3] = v23[1];
+        }
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const bool in = tr < nt && i0 + col4(tx, b) < n;
+            ga[a][b] = in ? G[a][b] * al[b] : 0.0;
+            gv[a][b] = in ? G[a][b] * vv[b] : 0.0;
+        }
+    }
+    double* pm_out = part + (size_t)ti * 2 * pstride;
+    double* pv_out = pm_out + pstride;
+    for (int c0 = 0; c0 < d; c0 += DC) {
+        const int dc = (d - c0 < DC) ? (d - c0) : DC;
+        stage(c0, dc);
+        for (int c = 0; c < dc; c++) {
+            double xv[4], yv[4], pm[4], pv[4];
+#pragma unroll
+            for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                pm[a] = 0.0; pv[a] = 0.0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const double df = xv[a] - yv[b];
+                    pm[a] = pm[a] + ga[a][b] * df;
+                    pv[a] = pv[a] + gv[a][b] * df;
+                }
+            }
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1)
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    pm[a] = pm[a] + __shfl_xor(pm[a], m, 16);
+                    if (V) pv[a] = pv[a] + __shfl_xor(pv[a], m, 16);
+                }
+            if (tx == (c & 15)) {
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    const int tr = t0 + ty * 4 + a;
+                    if (tr < nt) {
+                        pm_out[(size_t)tr * d + c0 + c] = pm[a];
+                        if (V) pv_out[(size_t)tr * d + c0 + c] = pv[a];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// SE and ARD: G is the cross-covariance entry itself (h is not read)
+__global__ __launch_bounds__(256) void k_predict_grad(const double* __restrict__ X, int n, int d, int npad,
+                                                      const double* __restrict__ Xt, int nt, HyperScalars h,
+                                                      const double* __restrict__ Ks, const double* __restrict__ V,
+                                                      const double* __restrict__ alpha, double* __restrict__ part,
+                                                      size_t pstride)
+{
+    predict_grad_body<KERNEL_SE>(X, n, d, npad, Xt, nt, h, Ks, V, alpha, part, pstride);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_predict_grad_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                             const double* __restrict__ Xt, int nt, HyperScalars h,
+                                                             const double* __restrict__ Ks, const double* __restrict__ V,
+                                                             const double* __restrict__ alpha, double* __restrict__ part,
+                                                             size_t pstride)
+{
+    predict_grad_body<KIND>(X, n, d, npad, Xt, nt, h, Ks, V, alpha, part, pstride);
+}
+
+// dmean[t][c] = -s_c (P_0 + P_1 + ...), dvar[t][c] = (2 s_c) (Q_0 + Q_1 + ...): the tiles' partial sums in tile order, packed
+// [nt][d]; s_c = 1 / l^2, or (wts given: ARD) w_c^2.  dvar null: the mean's gradient alone.
+__global__ __launch_bounds__(256) void k_predict_grad_finish(const double* __restrict__ part, size_t pstride, int tiles,
+                                                             int nt, int d, double ell_sq,
+                                                             const double* __restrict__ wts, double* __restrict__ dmean,
+                                                             double* __restrict__ dvar)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)nt * d) return;
+    const int c = (int)(e % d);
+    const double sc = wts ? wts[c] * wts[c] : 1.0 / ell_sq;
+    double sm = part[e], sv = dvar ? part[pstride + e] : 0.0;
+    for (int ti = 1; ti < tiles; ti++) {
+        sm = sm + part[(size_t)ti * 2 * pstride + e];
+        if (dvar) sv = sv + part[((size_t)ti * 2 + 1) * pstride + e];
+    }
+    if (dmean) dmean[e] = -(sc * sm);
+    if (dvar) dvar[e] = (2.0 * sc) * sv;
+}
+
 // Product of experts over the gathered exchange buffer (comm.cpp: cugp_bcm_predict_allgather).  g: [world][rstride]
 // doubles, rank r's block = {status, local expert count, [per][2][nt] rows: 1/v, m/v}.  Test point t sums over the
 // experts k = 0..K-1 in GLOBAL order -- expert k is rank k mod world's (k / world)-th -- then var = 1/sum, mean =
@@ -3541,6 +3725,27 @@ void launch_predict_finish(const double* Ks, const double* W, const double* alph
 {
     hipLaunchKernelGGL(k_predict_finish, dim3((ntest + 3) / 4, bt.count), dim3(256), 0, s, Ks, W, alpha, n, npad,
                        ntest, h, mean, var, rows, rstride, rhalf, ntpad, bt.tab);
+}
+
+void launch_predict_grad(const double* X, int n, int d, int npad, const double* Xt, int nt, const CovFn& cf,
+                         const double* Ks, const double* V, const double* alpha, double* part, size_t pstride,
+                         hipStream_t s)
+{
+    const dim3 grid(((nt + KT - 1) / KT) * predict_grad_tiles(n));
+    if (is_ard(cf))
+        CUGP_LAUNCH(k_predict_grad, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha, part, pstride);
+    else
+        CUGP_LAUNCH(CUGP_ISO_KERNEL(cf, k_predict_grad), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha,
+                    part, pstride);
+}
+
+void launch_predict_grad_finish(const double* part, size_t pstride, int n, int nt, int d, const CovFn& cf, double* dmean,
+                                double* dvar, hipStream_t s)
+{
+    const size_t total = (size_t)nt * d;
+    const double* wts = is_ard(cf) ? (const double*)(cf.hd + 1) : nullptr;   // (the weights behind the hyper-scalars)
+    hipLaunchKernelGGL(k_predict_grad_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, pstride,
+                       predict_grad_tiles(n), nt, d, cf.h.ell_sq, wts, dmean, dvar);
 }
 
 void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s)

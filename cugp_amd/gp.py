@@ -277,6 +277,19 @@ class Covsum:
         check(capi.lib().cugp_predict_latent(self._h, ptr(Xt), Xt.shape[0], ptr(m), ptr(v)))
         return m, v
 
+    def predict_grad(self, Xtest, with_noise=True, want_var_grad=True):
+        """Mean, variance and their gradients with respect to the test inputs (cugp_predict_grad), on the data the handle
+        holds: (mean [nt], var [nt], dmean [nt, d], dvar [nt, d] or None).  mean / var carry the bits of
+        compute_test_means_and_variances (with_noise) or predict_latent; want_var_grad=False skips the second triangular
+        product and returns None for dvar."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        m, v, dm = np.empty(nt), np.empty(nt), np.empty((nt, self.d))
+        dv = np.empty((nt, self.d)) if want_var_grad else None
+        check(capi.lib().cugp_predict_grad(self._h, ptr(Xt), nt, 1 if with_noise else 0, ptr(m), ptr(v), ptr(dm),
+                                           ptr(dv) if want_var_grad else None))
+        return m, v, dm, dv
+
     def compute_test_joint(self, X, y, Xtest, with_noise=True):
         """Joint predictive distribution at the test points (cugp_predict_cov): (mean [nt], cov [nt, nt]), cov =
         k(Xt,Xt) - Ks K^-1 Ks^T (+ sigma_n^2 I with noise), exactly symmetric; mean has cugp_predict's bits."""
@@ -606,6 +619,18 @@ class BCM:
                                                ptr(v)))
         return m, v
 
+    def predict_grad(self, Xt, combine=None, with_noise=True):
+        """(mean, var, dmean [nt, d], dvar [nt, d]) of the combined prediction at Xt (cugp_bcm_predict_grad: the experts'
+        gradients one by one, the chain rule of the rule on the host).  combine=None: the reference's product of the noisy
+        predictions (predict(Xt)'s bits; with_noise is not read); else the rule on the latent distributions, as predict."""
+        mode = capi.CUGP_COMBINE_REFERENCE if combine is None else combine_mode(combine)
+        Xt = f64(Xt).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        m, v, dm, dv = np.empty(nt), np.empty(nt), np.empty((nt, self.d)), np.empty((nt, self.d))
+        check(capi.lib().cugp_bcm_predict_grad(self._h, ptr(Xt), nt, mode, 1 if with_noise else 0, ptr(m), ptr(v),
+                                               ptr(dm), ptr(dv)))
+        return m, v, dm, dv
+
     get_BCM_negative_log_predprob = staticmethod(Covsum.get_negative_log_predprob)
 
     def cg_solve(self, budget=100):
@@ -635,6 +660,24 @@ def poe_combine(rows, mode, sf2, sn2, with_noise=True):
     check(capi.lib().cugp_poe_combine(ptr(rows), K, nt, combine_mode(mode) if isinstance(mode, str) else int(mode),
                                       float(sf2), float(sn2), 1 if with_noise else 0, ptr(m), ptr(v)))
     return m, v
+
+
+def poe_combine_grad(mean, var, dmean, dvar, mode, sf2):
+    """cugp_poe_combine_grad: the chain rule of the combination rule `mode` ("poe" | "gpoe" | "bcm" | "rbcm", None or
+    "reference" for the product of noisy predictions, or the CUGP_COMBINE_* number) on the experts' means and variances
+    [K, nt] and their gradients [K, nt, d] -> (dmean [nt, d], dvar [nt, d]); pure host code, needs no GPU."""
+    mean, var, dmean, dvar = f64(mean), f64(var), f64(dmean), f64(dvar)
+    if mean.ndim != 2 or var.shape != mean.shape or dmean.ndim != 3 or dmean.shape[:2] != mean.shape or dvar.shape != dmean.shape:
+        raise ValueError("mean, var must be [K, nt] and dmean, dvar [K, nt, d]")
+    K, nt, d = dmean.shape
+    if mode is None or mode == "reference":
+        mode = capi.CUGP_COMBINE_REFERENCE
+    elif isinstance(mode, str):
+        mode = combine_mode(mode)
+    om, ov = np.empty((nt, d)), np.empty((nt, d))
+    check(capi.lib().cugp_poe_combine_grad(ptr(mean), ptr(var), ptr(dmean), ptr(dvar), K, nt, d, int(mode), float(sf2),
+                                           ptr(om), ptr(ov)))
+    return om, ov
 
 
 def cg_minimize(fn, theta, budget=100):

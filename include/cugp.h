@@ -140,6 +140,32 @@ int cugp_predict(cugp_gp *gp, const double *Xt, int nt, double *mean, double *va
  * cugp_predict's variance minus sn2.  Works on every handle cugp_predict works on (SE, Matern, ARD, padded handles, BCM
  * experts); a stale handle is evaluated first.  CUGP_ERR_INVALID for a NULL argument or nt <= 0, before any device call. */
 int cugp_predict_latent(cugp_gp *gp, const double *Xt, int nt, double *mean, double *var);
+/* ---- gradients of the prediction with respect to the test inputs (what an acquisition function maximised by L-BFGS,
+ *      active learning or a sensitivity analysis needs).  The reference has no counterpart: neither Covsum
+ *      (cpp_serial_gp/covkernel.h) nor the CUDA code differentiates a prediction.  With k_i = k(x*, x_i), the noise term
+ *      not entering, alpha = K^-1 y and v = K^-1 k* = (W L^-1)^T, W = Ks L^-T as cugp_predict forms it:
+ *        mean(x*) = sum_i alpha_i k_i                    dmean / dx*_c = sum_i alpha_i dk_i / dx*_c
+ *        var(x*)  = sf2 (+ sn2) - k*^T K^-1 k*           dvar / dx*_c  = -2 sum_i v_i dk_i / dx*_c
+ *        dk_i / dx*_c = -G_i (x*_c - x_ic) s_c
+ *          SE          G = k_i,                           s_c = 1 / l^2
+ *          ARD         G = k_i,                           s_c = w_c^2 = 1 / l_c^2
+ *          Matern 3/2  G = sf2 3 exp(-a),                 s_c = 1 / l^2        (a = sqrt(3) r)
+ *          Matern 5/2  G = sf2 (5/3) (1 + a) exp(-a),     s_c = 1 / l^2        (a = sqrt(5) r)
+ *      G is finite at r = 0 and nothing divides by r: at a test point that IS a training row that row contributes G * 0.
+ *      The noisy and the latent variance have the same gradient.  The difference x*_c - x_ic is formed first, then
+ *      multiplied (no cancellation where |x| >> |x - x'|); sums run in a fixed order without atomics: the same bits on
+ *      every call, whatever nt is and whatever else the handle holds (v is always W L^-1, never Ks K^-1).
+ * cugp_predict_grad: mean [nt] and var [nt] (either may be NULL) by cugp_predict's own launches -- with_noise != 0 they
+ *      carry cugp_predict's bits, else cugp_predict_latent's; dmean and dvar [nt][d] row-major (either may be NULL; dvar
+ *      NULL skips the second triangular product: the mean's gradient needs alpha alone).  Works on every handle
+ *      cugp_predict works on (SE, Matern, ARD, padded handles, BCM experts); a stale handle is evaluated first, an
+ *      evaluation in flight is fetched first.  CUGP_ERR_INVALID -- before any device call -- for a NULL gp or Xt, nt <= 0,
+ *      or dmean and dvar both NULL.  Non-finite inputs propagate by IEEE with CUGP_OK (the header's convention).
+ * Not built: gradients of the joint covariance or of draws, of multi-target means, the form across ranks (an all-gather
+ *      of gradient rows), a batched launch for the experts of a BCM. */
+int cugp_predict_grad(cugp_gp *gp, const double *Xt, int nt, int with_noise,
+                      double *mean /* nt, may be NULL */, double *var /* nt, may be NULL */,
+                      double *dmean /* [nt][d], may be NULL */, double *dvar /* [nt][d], may be NULL */);
 /* ---- joint predictive distribution: extends the marginal form of Covsum::compute_test_means_and_variances
  *      covkernel.cpp:277-323 (the noise term as at :316) to the covariance between the test points; the reference has
  *      no joint counterpart.  Both work on every handle cugp_predict works on (padded handles, BCM experts), at the
@@ -241,7 +267,9 @@ int cugp_get_kernel_stats(cugp_gp *gp, double *sum_ms, long long *launches, doub
  * one launch in 16), 8 = k_trtri_block (a hand-over block's own inverse in one launch; every fourth block), 9 =
  * k_predict_gemm (W = Ks L^-T of cugp_predict; levels 3 to 5 only), 10 = k_build (level 5 only; its `flop` is BYTES: the
  * lower 64x64 tiles of K written once + X read), 12 = k_predict_cov<4> / <2> (W W^T of cugp_predict_cov and
- * cugp_predict_sample; levels 3 to 5 only; flop: every launched output tile over the whole k range).  The
+ * cugp_predict_sample; levels 3 to 5 only; flop: every launched output tile over the whole k range), 13 = k_predict_grad
+ * (the tile pass of cugp_predict_grad; levels 3 and 4 only; its `flop` is BYTES: the tiles of Ks and, with dvar, V it reads).
+ * cugp_predict_grad's second triangular product V = W L^-1 (k_targets_alpha) is counted under kind 9 (levels 3 and 4).  The
  * sampling rates are those of level 2; levels 3 to 5 time every launch.  flop = algorithmic
  * (entries on or below the diagonal, a triangular k tile counted half), multiply + add */
 int cugp_get_kernel_stats_kind(cugp_gp *gp, int kind, double *sum_ms, long long *launches, double *flop, int reset);
@@ -402,6 +430,33 @@ int cugp_poe_combine(const double *rows /* [K][2][nt] */, int K, int nt, int mod
 int cugp_bcm_predict_mode(cugp_bcm *b, const double *Xt, int nt, int mode, int with_noise, double *mean, double *var);
 int cugp_bcm_predict_allgather_mode(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt, int mode,
                                     int with_noise, double sf2, double sn2, double *mean, double *var);
+/* ---- gradients of the combined prediction with respect to the test inputs (one process; the reference has no
+ *      counterpart).  The chain rule of the rules above, per test point and input dimension, experts in order, every
+ *      operation rounded on its own, with p = 1 / v:
+ *        dp = -dv / v^2;  dbeta = 0 (POE, GPOE, BCM) | -1/2 dv / v (RBCM)
+ *        dprec = sum (dbeta p + beta dp) - [BCM, RBCM] (sum dbeta) / sf2,      dvar = -dprec / prec^2
+ *        dS = sum (dbeta p m + beta dp m + beta p dm),   S = sum beta p m,      dmean = dvar S + dS / prec
+ *      dmean is evaluated as the same expression with the difference m_k - mean formed first (dvar S and dS / prec cancel
+ *      where the experts agree):  sum w_k dm_k + (sum a_k (m_k - mean)) / prec + [BCM, RBCM] mean ((sum dbeta) / sf2) / prec,
+ *      a_k = dbeta p + beta dp,  w_k = beta_k p_k / prec,  mean = sum w_k m_k; one expert under POE returns its own gradients.
+ * cugp_poe_combine_grad: pure host code, like cugp_poe_combine.  mean, var [K][nt]: the experts' means and variances
+ *      (LATENT ones for the rules, as cugp_predict_grad returns them with with_noise = 0); dmean, dvar [K][nt][d] their
+ *      gradients; out_dmean, out_dvar [nt][d].  CUGP_COMBINE_REFERENCE (-1): the reference's product of the experts' NOISY
+ *      predictions (cugp_bcm_predict, BCM.cpp:45-62): POE's arithmetic on noisy variances, which the caller passes.
+ *      CUGP_ERR_INVALID for a NULL argument, K <= 0, nt <= 0, d <= 0 or an unknown mode.
+ * cugp_bcm_predict_grad: cugp_predict_grad expert by expert (each on its own device, so a BCM over several devices of one
+ *      process works), combined on the host.  mean, var (either may be NULL): from rows made as the device makes them,
+ *      through cugp_poe_combine -- cugp_bcm_predict_mode's values, bit for bit except RBCM's log -- or, mode -1, through
+ *      cugp_poe_finish: cugp_bcm_predict's bits (with_noise is then not read).  dmean, dvar [nt][d] (either may be NULL, not
+ *      both).  CUGP_ERR_INVALID -- before any device call -- for a NULL b or Xt, nt <= 0, dmean and dvar both NULL or an
+ *      unknown mode.  Not built: the form across ranks. */
+#define CUGP_COMBINE_REFERENCE (-1)
+int cugp_poe_combine_grad(const double *mean, const double *var,       /* [K][nt] each */
+                          const double *dmean, const double *dvar,     /* [K][nt][d] each */
+                          int K, int nt, int d, int mode, double sf2,
+                          double *out_dmean, double *out_dvar);        /* [nt][d] each */
+int cugp_bcm_predict_grad(cugp_bcm *b, const double *Xt, int nt, int mode, int with_noise,
+                          double *mean, double *var, double *dmean, double *dvar);
 /* ---- ARD BCM: every expert an ARD handle (squared exponential, theta as cugp_create_ard's: nh = d + 2 entries shared by
  *      all experts).  The reference has no counterpart.  The experts run as groups of shared launches, over several
  *      devices of one process, or sharded one process per GPU, exactly like isotropic experts; only the rows of an
