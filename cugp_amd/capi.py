@@ -52,6 +52,7 @@ SIGNATURES = {
     "cugp_set_loghyper": (C.c_int, [C.c_void_p, _dp]),
     "cugp_get_loghyper": (C.c_int, [C.c_void_p, _dp]),
     "cugp_create_ard": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_create_ard_padded": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_num_hyper": (C.c_int, [C.c_void_p, _ip]),
     "cugp_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "cugp_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
@@ -75,6 +76,9 @@ SIGNATURES = {
     "cugp_get_cholesky": (C.c_int, [C.c_void_p, _dp]),
     "cugp_get_K_inverse": (C.c_int, [C.c_void_p, _dp]),
     "cugp_get_alpha": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_capacity": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_append": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
+    "cugp_append_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     "cugp_set_targets": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "cugp_num_targets": (C.c_int, [C.c_void_p, _ip]),
     "cugp_loglik_grad_targets": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),

@@ -144,6 +144,7 @@ int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int 
         int rc = ard ? cugp_create_ard_padded(rows[k], d, ds.device, pad_to, &g)
                      : cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
         if (rc) { cugp_bcm_destroy(b); return rc; }
+        cugp_mark_bcm_expert(g);                        // (cugp_append refuses the experts of a BCM)
         // several experts on one device already fill each other's idle time; the extra streams only cost launches
         if (nexperts > nsets) cugp_set_overlap(g, 0);
         b->experts.push_back(g);

@@ -185,6 +185,12 @@ struct cugp_gp {
     bool tg_valid = false;         // Z, A and tg_row hold for (data, hp, targets) -- read together with inverse_valid
     std::vector<double> tg_row;
     Scratch tg_pred;               // cugp_predict_targets: test inputs, Ks, W, variance, partial means, means
+    // appending observations (cugp_append)
+    bool bcm_expert = false;       // expert of a cugp_bcm (the experts' common padded size carries n)
+    int groups = 0;                // the live cugp_groups that hold the handle (a group's device table carries n)
+    bool is_factor = false;        // the internal factor handle (cov_f) of another handle
+    bool x_full = false;           // dX holds npad rows (grown by the first append; n rows until then)
+    Scratch app;                   // one pass: B = k(Xb, X), P = B L^-T, V = P L^-1 ([128][npad] each) and Qt ([npad][128])
 };
 
 namespace {
@@ -1186,6 +1192,7 @@ int cugp_destroy(cugp_gp* g)
     g->cov_scr.release();
     g->samp.release();
     g->tg_pred.release();
+    g->app.release();
     if (g->tg_hout) (void)hipHostFree(g->tg_hout);
     double* bufs[] = {g->dX, g->dy, g->dA, g->dT, g->dU, g->dKinv, g->dz, g->dalpha, g->dw, g->d16, g->dlogdet,
                       g->dpart, g->dout, g->d64, g->tg_y, g->tg_z, g->tg_a, g->tg_part, g->tg_out};
@@ -1673,6 +1680,31 @@ int cugp_predict_rows_enqueue_form(cugp_gp* g, const double* Xt, int nt, double*
 }
 
 // ---------------------------------------------------------------- joint predictive distribution
+// g's factor handle (cov_f), created on first use for `tiles` tile rows or more: the joint predictive covariance and the
+// Schur complement of cugp_append are written into its A and factored there
+static int cov_factor_handle(cugp_gp* g, int tiles)
+{
+    int rc;
+    if (!g->cov_f || g->cov_tiles < tiles) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        if (g->cov_f) (void)cugp_destroy(g->cov_f);
+        g->cov_f = nullptr;
+        g->cov_tiles = 0;
+        cugp_gp* f = nullptr;
+        if ((rc = cugp_create(tiles * TILE, 1, g->device, &f))) return rc;
+        // it never builds an inverse, so it launches no barrier grid: it takes no part in the device's budget of them
+        g_live[f->device < 64 ? f->device : 63].fetch_sub(1, std::memory_order_relaxed);
+        f->counted = false;
+        f->overlap = false;
+        f->is_factor = true;
+        if ((rc = ensure_factor_bufs(f))) { cugp_destroy(f); return rc; }
+        g->cov_f = f;
+        g->cov_tiles = tiles;
+        if ((rc = use_device(g))) return rc;
+    }
+    return CUGP_OK;
+}
+
 // The shared half of cugp_predict_cov and cugp_predict_sample: the marginal prediction (predict_device: the same launches
 // as cugp_predict, a stale handle re-evaluated first), then on the handle's stream
 //   Sigma = k(Xt,Xt) (+ sn2 I) + jitter I - W W^T,   W = Ks L^-T
@@ -1687,22 +1719,7 @@ static int predict_cov_device(cugp_gp* g, const double* Xt, int nt, bool with_no
     if ((rc = predict_device(g, Xt, nt, &pb))) return rc;
     TuneScope ts(g);
     const int tiles = (nt + TILE - 1) / TILE, ntpad = tiles * TILE;
-    if (!g->cov_f || g->cov_tiles < tiles) {
-        HIPCHK(hipStreamSynchronize(g->stream));
-        if (g->cov_f) (void)cugp_destroy(g->cov_f);
-        g->cov_f = nullptr;
-        g->cov_tiles = 0;
-        cugp_gp* f = nullptr;
-        if ((rc = cugp_create(nt, 1, g->device, &f))) return rc;
-        // it never builds an inverse, so it launches no barrier grid: it takes no part in the device's budget of them
-        g_live[f->device < 64 ? f->device : 63].fetch_sub(1, std::memory_order_relaxed);
-        f->counted = false;
-        f->overlap = false;
-        if ((rc = ensure_factor_bufs(f))) { cugp_destroy(f); return rc; }
-        g->cov_f = f;
-        g->cov_tiles = tiles;
-        if ((rc = use_device(g))) return rc;
-    }
+    if ((rc = cov_factor_handle(g, tiles))) return rc;
     if (!g->cov_ev) HIPCHK(hipEventCreateWithFlags(&g->cov_ev, hipEventDisableTiming));
     cugp_gp* f = g->cov_f;
     f->n = nt;                                                       // (a smaller problem in the handle's buffers)
@@ -1799,6 +1816,143 @@ int cugp_predict_sample(cugp_gp* g, const double* Xt, int nt, int with_noise, do
         return fail(CUGP_ERR_DEVICE, "cugp_predict_sample", e);
     }
     if (g->prof >= 2) drain_kernel_events(g);
+    return CUGP_OK;
+}
+
+// ---------------------------------------------------------------- appending observations
+// The rows [n, n + k) in passes that never cross a multiple of 128 (include/cugp.h): pure arithmetic
+int cugp_append_plan(int n, int k, int pass, int out[2])
+{
+    if (!out || n < 0 || k <= 0 || pass < 0 || (long long)n + k > 0x7fffffffLL)
+        return fail(CUGP_ERR_INVALID, "cugp_append_plan: null out, n < 0, k <= 0, pass < 0 or n + k beyond int");
+    const int end = n + k;
+    int count = 0;
+    bool found = false;
+    for (int a = n; a < end; count++) {
+        const int edge = (a / TILE + 1) * TILE, b = edge < end ? edge : end;
+        if (count == pass) { out[0] = a; out[1] = b; found = true; }
+        a = b;
+    }
+    if (!found) return fail(CUGP_ERR_INVALID, "cugp_append_plan: pass beyond the last one");
+    return count;
+}
+
+int cugp_capacity(const cugp_gp* g, int* cap)
+{
+    if (!g || !cap) return fail(CUGP_ERR_INVALID, "cugp_capacity: null argument");
+    *cap = g->npad;
+    return CUGP_OK;
+}
+
+// One bordering step by the rows [r0, r1) (already in dX, dy) of a handle whose inverse quantities hold for its first r0
+// rows -- DESIGN.md section 19.  Existing launches up to C and C^-1 in the factor handle, then the two append kernels.
+static int append_pass(cugp_gp* g, cugp_gp* f, int r0, int r1)
+{
+    int rc;
+    hipStream_t s = g->stream;
+    const int kk = r1 - r0, npad = g->npad, d = g->d;
+    const size_t strip = (size_t)TILE * npad;
+    double *dKs = g->app.p, *dW = dKs + strip, *dV = dW + strip, *dQt = dV + strip;
+    const double* Xb = g->dX + (size_t)r0 * d;
+    CovFn cf;
+    if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+    launch_kcross(g->dX, r0, d, npad, Xb, kk, TILE, cf, dKs, s);                    // B = k(Xb, X)
+    launch_predict_gemm(dKs, g->dT, dW, npad, 1, g->nt, s);                         // P = B L^-T
+    launch_targets_alpha(dW, g->dU, dV, npad, kk, s);                               // V = P L^-1 (whole 64-row tiles of the kk rows)
+    const CovShape cs = predict_cov_shape(TILE, r0);
+    if ((rc = g->cov_scr.grow((size_t)(cs.split - 1) * TILE * TILE, s))) return rc;
+    launch_predict_cov(dW, npad, TILE, cs, f->dA, g->cov_scr.p, s);                 // P P^T
+    launch_predict_cov_finish(Xb, kk, d, TILE, cf, true, 0.0, f->dA, g->cov_scr.p, cs.split - 1, nullptr, s);   // S
+    launch_potf2(f->dA, TILE, 0, f->d16, f->d64, f->dlogdet, s);                    // C = chol(S)
+    launch_trtri_diag(f->dA, TILE, 0, 1, f->d64, f->dT, f->dU, s);                  // C^-1
+    launch_append_border(dW, dV, f->dA, f->dT, f->dlogdet, r0, kk, npad, g->dA, g->dT, g->dU, g->dKinv, g->dy, g->dz,
+                         g->dalpha, g->dlogdet, dQt, s);
+    launch_append_kinv(dQt, r0, kk, npad, g->dKinv, g->dz + r0, g->dalpha, s);
+    HIPCHK(hipGetLastError());
+    return CUGP_OK;
+}
+
+int cugp_append(cugp_gp* g, const double* Xnew, const double* ynew, int k)
+{
+    if (!g || !Xnew || !ynew) return fail(CUGP_ERR_INVALID, "cugp_append: null argument");
+    if (k <= 0) return fail(CUGP_ERR_INVALID, "cugp_append: k must be positive");
+    if (g->is_factor) return fail(CUGP_ERR_INVALID, "cugp_append: an internal factor handle takes no observations");
+    if (g->bcm_expert)
+        return fail(CUGP_ERR_INVALID, "cugp_append: the handle is an expert of a cugp_bcm (the experts' common padded size carries n)");
+    if (g->groups > 0)
+        return fail(CUGP_ERR_INVALID, "cugp_append: the handle is a member of a cugp_group (the group's device table carries n)");
+    if (!g->have_data) return fail(CUGP_ERR_INVALID, "cugp_append: no training data set (cugp_set_data comes first)");
+    if (g->tg_m > 0) return fail(CUGP_ERR_INVALID, "cugp_append: the handle has targets set (cugp_set_targets): targets have no new rows");
+    if ((long long)g->n + k > g->npad) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "cugp_append: %d + %d rows exceed the handle's capacity of %d; create it with a larger npad_min",
+                 g->n, k, g->npad);
+        return fail(CUGP_ERR_INVALID, buf);
+    }
+    int rc;
+    if ((rc = use_device(g))) return rc;
+    if ((rc = fetch_eval(g))) return rc;                             // an evaluation in flight is fetched first
+    hipStream_t s = g->stream;
+    const int n0 = g->n, d = g->d;
+    if (!g->x_full) {                                                // dX: n rows until the first append, npad rows from then on
+        double* nx = nullptr;
+        HIPCHK(hipMalloc((void**)&nx, (size_t)g->npad * d * sizeof(double)));
+        hipError_t e = hipMemcpyAsync(nx, g->dX, (size_t)n0 * d * sizeof(double), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { (void)hipFree(nx); return fail(CUGP_ERR_DEVICE, "cugp_append: growing X", e); }
+        (void)hipFree(g->dX);
+        g->dX = nx;
+        g->x_full = true;
+    }
+    const bool update = g->inverse_valid;
+    // from here on the handle holds n0 + k rows; it is stale until the passes and the trace have gone through
+    g->cfg_epoch++;                                                  // captured graphs carry n (and X)
+    g->factor_valid = g->inverse_valid = false;
+    g->tg_valid = false;
+    g->n = n0 + k;
+    HIPCHK(hipMemcpyAsync(g->dX + (size_t)n0 * d, Xnew, (size_t)k * d * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(g->dy + n0, ynew, (size_t)k * sizeof(double), hipMemcpyHostToDevice, s));
+    if (!update) {                                                   // no inverse to extend: the next evaluation factors n0 + k rows
+        HIPCHK(hipStreamSynchronize(s));
+        return CUGP_OK;
+    }
+    TuneScope ts(g);
+    if (const int pe = prepare_kernels())
+        return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
+    if ((rc = g->app.grow((size_t)4 * TILE * g->npad, s))) return rc;
+    if ((rc = cov_factor_handle(g, 1))) return rc;
+    cugp_gp* f = g->cov_f;
+    f->nt = 1;                                                       // (one tile of the factor handle's buffers, ld = 128)
+    f->npad = TILE;
+    int rows[2];
+    const int passes = cugp_append_plan(n0, k, 0, rows);
+    for (int p = 0; p < passes; p++) {
+        (void)cugp_append_plan(n0, k, p, rows);
+        f->n = rows[1] - rows[0];
+        if ((rc = append_pass(g, f, rows[0], rows[1]))) { (void)hipStreamSynchronize(s); return rc; }
+    }
+    // LL and the gradient at the new data: one k_trace launch, its last block finalises (enqueue_continue)
+    HIPCHK(hipMemsetAsync(g->dtickets + 2 * g->nt, 0, sizeof(unsigned), s));
+    CovFn cf;
+    if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+    launch_trace(g->dX, g->n, d, g->npad, cf, g->dKinv, g->dalpha, g->dpart, s, {}, g->dz, g->dlogdet, g->dout, g->hout,
+                 g->dtickets + 2 * g->nt);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return fail(CUGP_ERR_DEVICE, "cugp_append", e); }
+    g->pev_valid = false;
+    (void)read_result_row(g, g->hout, true);
+    // a Schur complement that is not positive definite: NaN results, the data stays extended, and the next ordinary
+    // evaluation factors all rows afresh
+    if (!std::isfinite(g->last_ll)) discard_eval(g);
+    return CUGP_OK;
+}
+
+// (bcm.cpp: the experts' common padded size carries n, so an expert takes no appended rows for the rest of its life)
+int cugp_mark_bcm_expert(cugp_gp* g)
+{
+    if (!g) return CUGP_ERR_INVALID;
+    g->bcm_expert = true;
     return CUGP_OK;
 }
 
@@ -2546,6 +2700,7 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
     cugp_group* gr = new (std::nothrow) cugp_group;
     if (!gr) return fail(CUGP_ERR_NOMEM, "host allocation");
     gr->experts.assign(experts, experts + k);
+    for (cugp_gp* x : gr->experts) x->groups++;             // (cugp_append refuses them while the group lives: the table carries n)
     const int nt = experts[0]->nt;
     const bool ard = experts[0]->ard;
     const size_t row = ard ? (size_t)ARD_ROW_GRAD + experts[0]->nh : 8;
@@ -2583,6 +2738,7 @@ void cugp_group_destroy(cugp_group* gr)
     if (gr->ctx.hout) (void)hipHostFree(gr->ctx.hout);
     if (gr->ctx.hrows) (void)hipHostFree(gr->ctx.hrows);
     gr->pred.release();
+    for (cugp_gp* x : gr->experts) x->groups--;             // (the experts outlive their group)
     delete gr;
 }
 

@@ -25,6 +25,9 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out);
 // cugp_create_ard with the matrices padded to at least npad_min rows (cugp_create_padded's rule): the experts of an ARD BCM
 int cugp_create_ard_padded(int n, int d, int device, int npad_min, cugp_gp** out);
 void cugp_group_destroy(cugp_group* gr);
+// cugp_append refuses an expert of a cugp_bcm (marked here by bcm.cpp, for good) and a handle that a live cugp_group holds
+// (counted by cugp_group_create / cugp_group_destroy, which the experts must outlive)
+int cugp_mark_bcm_expert(cugp_gp* gp);
 
 // Evaluate all experts at their (common) hyper-parameters; ll[k], g[nh k .. nh k + nh - 1] with nh = 3, or d + 2 for ARD
 // experts (g may be null when !want_grad).

@@ -238,6 +238,18 @@ constexpr int TARGETS_MEAN_KSTEP = 512;
 int targets_mean_split(int npad);
 void launch_targets_mean(const double* A, const double* Ks, double* P, int npad, int m, int nt, int ntpad, double* mean,
                          hipStream_t s);
+// ---- appending observations (cugp_append): one bordering step by the k <= 128 new rows [r0, r0 + k) of ONE tile row ----
+// P = B L^-T and V = P L^-1 ([128][ld], zero beyond row k and column r0); Cf = chol(S) and Ci = its inverse (lower, ld =
+// 128, identity beyond k, Ci zero above the diagonal), flog[0] = sum log C_ii -- the factor handle's A, T and logdet.
+// Writes rows [r0, r0 + k) of A (P | C), T (Q | C^-1, Q = -C^-1 V) and Kinv (C^-T Q | C^-T C^-1), the same columns of U,
+// z[r0 ..] = zb = C^-1 (y[r0 ..] - P z), alpha[r0 ..] = C^-T zb, logdet[r0 / 128] += flog[0], and Qt ([npad][128]):
+// Qt[j][i] = Q[i][j], zero beyond k and for the rows j in [r0, r0 rounded up to 64).
+void launch_append_border(const double* P, const double* V, const double* Cf, const double* Ci, const double* flog, int r0,
+                          int k, int ld, double* A, double* T, double* U, double* Kinv, const double* y, double* z,
+                          double* alpha, double* logdet, double* Qt, hipStream_t s);
+// lower 64x64 tiles of Kinv[0, r0) += Q'Q (fp64 MFMA, Qt as both operands, k rounded up to 16) and alpha[0, r0) += Q' zb
+void launch_append_kinv(const double* Qt, int r0, int k, int ld, double* Kinv, const double* zb, double* alpha,
+                        hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -54,7 +54,8 @@ class Covsum:
     ard=True: one length scale per input dimension (cugp_create_ard; GPML covSEard's order): the hyper-parameter
     vector is [log l_1 .. log l_d, log sigma_f, log sigma_n], gradients and cg_solve traces have d + 2 (+ 1) entries.
     kernel="se" | "matern32" | "matern52": the covariance family (cugp_create_kernel; GPML covMaterniso with d = 3, 5),
-    same three hyper-parameters; fixed for the life of the handle.  ARD is squared-exponential only."""
+    same three hyper-parameters; fixed for the life of the handle.  ARD is squared-exponential only.
+    npad_min: rows the handle has room for (capacity); append(X, y) adds observations up to it."""
 
     def __init__(self, n, d, device=0, npad_min=0, ard=False, kernel="se"):
         self.n, self.d, self.device, self.ard = int(n), int(d), int(device), bool(ard)
@@ -68,8 +69,9 @@ class Covsum:
                                                 C.byref(self._h)))
         elif self.ard:
             if npad_min:
-                raise ValueError("an ARD handle cannot be padded (BCM(ard=True) pads its own experts)")
-            check(capi.lib().cugp_create_ard(self.n, self.d, self.device, C.byref(self._h)))
+                check(capi.lib().cugp_create_ard_padded(self.n, self.d, self.device, int(npad_min), C.byref(self._h)))
+            else:
+                check(capi.lib().cugp_create_ard(self.n, self.d, self.device, C.byref(self._h)))
         else:
             check(capi.lib().cugp_create_padded(self.n, self.d, self.device, int(npad_min), C.byref(self._h)))
         self._data_key = None
@@ -104,6 +106,37 @@ class Covsum:
             raise ValueError("expected X %s and y %s" % ((self.n, self.d), (self.n,)))
         check(capi.lib().cugp_set_data(self._h, ptr(X), ptr(y)))
         self._data_key = (X.copy(), y.copy())
+
+    @property
+    def capacity(self):
+        """The rows the handle can hold (cugp_capacity): its padded size, fixed by n and npad_min when it was created."""
+        c = C.c_int()
+        check(capi.lib().cugp_capacity(self._h, C.byref(c)))
+        return c.value
+
+    def append(self, X, y):
+        """Append observations (cugp_append): X [k, d] with y [k], or one row as a 1-d X with a scalar y.  A handle that
+        holds its inverse quantities is extended in place at O(k n^2); any other handle only takes the data and the next
+        evaluation factors all rows.  self.n grows by k; set_data keeps taking the current n rows."""
+        X, y = np.asarray(X, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        if X.ndim == 1 and y.ndim == 0:
+            X, y = X.reshape(1, -1), y.reshape(1)
+        X, y = f64(X), f64(y)                                        # (contiguous; ascontiguousarray alone turns a scalar into 1-d)
+        if X.ndim != 2 or X.shape[1] != self.d or y.shape != (X.shape[0],):
+            raise ValueError("expected X (k, %d) with y (k,), or one row (%d,) with a scalar y" % (self.d, self.d))
+        try:
+            check(capi.lib().cugp_append(self._h, ptr(X), ptr(y), int(X.shape[0])))
+        except capi.CugpError:
+            # a refusal leaves n alone; a device error after the rows were taken leaves a stale handle of n + k rows
+            # whose new rows may not have arrived: follow the library's n and forget the data key, so that the next
+            # bound data is set afresh
+            n, d, npad = C.c_int(), C.c_int(), C.c_int()
+            if capi.lib().cugp_dims(self._h, C.byref(n), C.byref(d), C.byref(npad)) == capi.CUGP_OK and n.value != self.n:
+                self.n, self._data_key = n.value, None
+            raise
+        self.n += int(X.shape[0])
+        k = self._data_key
+        self._data_key = None if k is None else (np.concatenate([k[0], X]), np.concatenate([k[1], y]))
 
     def set_data_device(self, dX_ptr, dy_ptr):
         check(capi.lib().cugp_set_data_device(self._h, C.c_void_p(dX_ptr), C.c_void_p(dy_ptr)))

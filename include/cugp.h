@@ -87,6 +87,9 @@ int cugp_get_loghyper(const cugp_gp *gp, double hp[3]);
  * The number of hyper-parameters of any handle (3, or d + 2) is reported through *nh; set / get copy nh entries;
  * the combined and the fetch form return LL and the nh gradient components (fetch: g may be NULL). */
 int cugp_create_ard(int n, int d, int device, cugp_gp **out);
+/* the same with the matrices padded to at least npad_min rows (cugp_create_padded's rule): the experts of an ARD BCM, and an
+ * ARD handle with room for cugp_append */
+int cugp_create_ard_padded(int n, int d, int device, int npad_min, cugp_gp **out);
 int cugp_num_hyper(const cugp_gp *gp, int *nh);
 int cugp_set_loghyper_ard(cugp_gp *gp, const double *hp, int nh);
 int cugp_get_loghyper_ard(const cugp_gp *gp, double *hp, int nh);
@@ -185,6 +188,39 @@ int cugp_predict_cov(cugp_gp *gp, const double *Xt, int nt, int with_noise, doub
 int cugp_predict_sample(cugp_gp *gp, const double *Xt, int nt, int with_noise, double jitter,
                         int nsamples, const double *normals, double *samples);
 int cugp_nlpp(const double *actual, const double *mean, const double *var, int nt, double *nlpp);
+
+/* ---- appending observations to a factored model (the last step of predict-with-gradients / observe / add; the reference
+ *      has no counterpart: Covsum is rebuilt, cpp_serial_gp/covkernel.cpp:14-37).  A Cholesky factor grows by bordering, so
+ *      everything a handle holds stays valid as the leading block of the larger problem.  With B = k(Xb, X), P = B L^-T,
+ *      V = P L^-1, S = k(Xb, Xb) + sn2 I - P P^T, C = chol(S), Q = -C^-1 V, zb = C^-1 (yb - P z):
+ *        L' = [L 0; P C]   L'^-1 = [L^-1 0; Q C^-1]   K'^-1 = [K^-1 + Q'Q, Q'C^-1; C^-T Q, C^-T C^-1]
+ *        z' = [z; zb]   alpha' = [alpha + Q' zb; C^-T zb]   quad' = quad + zb'zb   log|K'| = log|K| + 2 sum log C_ii
+ *      O(k N^2) per call instead of the N^3 of a fresh evaluation; every sum in a fixed order, no atomics.
+ * cugp_capacity   : *cap <- the rows the handle can hold: its padded size (cugp_dims' npad), fixed when it is created --
+ *                   cugp_create_padded / cugp_create_kernel / cugp_create_ard_padded take it as npad_min.
+ * cugp_append     : k further rows Xnew [k][d], ynew [k] (host).  On a handle that holds its inverse quantities (a gradient
+ *                   evaluation at the current data and hyper-parameters, nothing in flight) they are extended in place on
+ *                   the handle's stream -- factor, inverse, K^-1, z, alpha, log-determinant -- LL and the gradient are
+ *                   taken at the n + k rows, and every call (cugp_loglik_grad, cugp_predict*, cugp_predict_grad,
+ *                   cugp_get_*) then answers for the larger model without further device work beyond its own.  On any
+ *                   other handle (fresh data, changed hyper-parameters, a log-likelihood-only factor) only the data grows
+ *                   and the next evaluation factors n + k rows: the same results, only the cost differs.  An evaluation in
+ *                   flight is fetched first.  Works on SE, Matern and ARD handles.  cugp_set_data keeps taking the
+ *                   handle's CURRENT number of rows.
+ * cugp_append_plan: the passes of an append of k rows to n (pure arithmetic, no device): pass i covers the rows
+ *                   [out[0], out[1]); no pass crosses a multiple of 128, the passes cover [n, n + k) once, ascending; returns
+ *                   the number of passes, or CUGP_ERR_INVALID for a pass beyond the last.  Each pass is one bordering step:
+ *                   its rows lie in one tile row and C inside one diagonal tile.
+ * Refusals, all CUGP_ERR_INVALID before any device call with the reason in cugp_last_error, the handle unchanged: a NULL
+ * argument; k <= 0; n + k beyond the capacity; no data yet; a handle with targets (cugp_set_targets); an expert of a
+ * cugp_bcm, for good, or a handle that a group of shared launches holds, until that group is destroyed.
+ * A Schur complement that is not positive definite (a duplicate row at vanishing noise, non-finite input) gives NaN
+ * results with CUGP_OK (the header's convention); the data stays extended and the next evaluation starts afresh.
+ * Not built: removing rows; append on BCM experts or across ranks; append with targets; an append that skips K^-1 for
+ * callers who only predict; growing beyond the capacity. */
+int cugp_capacity(const cugp_gp *gp, int *cap);
+int cugp_append(cugp_gp *gp, const double *Xnew /* [k][d], host */, const double *ynew /* k */, int k);
+int cugp_append_plan(int n, int k, int pass, int out[2]);
 
 /* ---- intermediates (parity tests; each copies device -> host) ----
  * cugp_compute_K_train : Covsum::compute_K_train covkernel.cpp:64-102 -> full symmetric n x n
