@@ -52,6 +52,8 @@ class ShardedBCM:
     rank owns are touched (the rest may be None).  group=None with world==1 needs no process group.
     kernel: "se" | "matern32" | "matern52" for the library's experts -- every rank must pass the same one (the library
     cannot check that without a collective); an injected expert_factory makes its own experts and is not told.
+    kernel "matern32_ard" | "matern52_ard": ARD experts of that Matern kind (.kernel then reports "matern32" /
+    "matern52" beside .ard); ard=True itself is squared-exponential only.
     ard=True (every rank alike): ARD experts, nh = d + 2 shared hyper-parameters, every row buffer 1 + nh wide; an
     injected expert_factory is then called as factory(n, d, device, ard=True).  d: the input dimension, only needed on
     a rank that sees none of the experts' data (it sizes the rows)."""
@@ -59,10 +61,10 @@ class ShardedBCM:
     def __init__(self, experts, rank=0, world=1, device=0, group=None, expert_factory=None, comm_device=None,
                  kernel="se", ard=False, d=None):
         self.K = len(experts)
-        self.kernel = _gp.KERNEL_NAMES[_gp.kernel_kind(kernel)]
-        self.ard = bool(ard)
-        if self.ard and self.kernel != "se":
-            raise ValueError("ard=True is squared-exponential only (ARD x Matern is not built)")
+        kind, self.ard = _gp.kernel_spec(kernel, ard)
+        self.kernel = _gp.KERNEL_NAMES[kind]
+        # (the spelling Covsum and BCM take: "matern52_ard" sets ard by itself, ard=True goes with "se" alone)
+        self._kernel_arg = self.kernel + "_ard" if self.ard and self.kernel != "se" else self.kernel
         self.nh = 3
         if self.ard:
             if d is None:
@@ -75,7 +77,7 @@ class ShardedBCM:
         self.rank, self.world, self.group = rank, world, group
         self.mine = [k for k in range(self.K) if expert_owner(k, world) == rank]
         if expert_factory is None:
-            factory = lambda n, d, dev: _default_factory(n, d, dev, self.kernel, self.ard)
+            factory = lambda n, d, dev: _default_factory(n, d, dev, self._kernel_arg, self.ard)
         elif self.ard:
             factory = lambda n, d, dev: expert_factory(n, d, dev, ard=True)
         else:
@@ -87,7 +89,7 @@ class ShardedBCM:
             # (csrc/bcm.cpp, group.h); self.local holds borrowed per-expert views for prediction
             data = [(np.ascontiguousarray(experts[k][0], dtype=np.float64),
                      np.ascontiguousarray(experts[k][1], dtype=np.float64)) for k in self.mine]
-            self._group = _gp.BCM([X.shape[0] for X, _ in data], data[0][0].shape[1], device, kernel=self.kernel,
+            self._group = _gp.BCM([X.shape[0] for X, _ in data], data[0][0].shape[1], device, kernel=self._kernel_arg,
                                   ard=self.ard)
             for i, (X, y) in enumerate(data):
                 self._group.set_expert_data(i, X, y)
@@ -120,7 +122,7 @@ class ShardedBCM:
             X, y = (np.ascontiguousarray(a, dtype=np.float64) for a in experts[self.mine[0]])
             for e in self.local.values():
                 e.close()
-            self._group = _gp.BCM([X.shape[0]], X.shape[1], device, kernel=self.kernel, ard=self.ard)
+            self._group = _gp.BCM([X.shape[0]], X.shape[1], device, kernel=self._kernel_arg, ard=self.ard)
             self._group.set_expert_data(0, X, y)
             self.local = {self.mine[0]: self._group.expert(0)}
         # Lean exchange (round 6): the library writes this rank's rows into a compact [per, 4] device tensor, ONE

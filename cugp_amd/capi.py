@@ -53,6 +53,7 @@ SIGNATURES = {
     "cugp_get_loghyper": (C.c_int, [C.c_void_p, _dp]),
     "cugp_create_ard": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_create_ard_padded": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_create_ard_kernel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_num_hyper": (C.c_int, [C.c_void_p, _ip]),
     "cugp_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "cugp_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
@@ -137,6 +138,9 @@ SIGNATURES = {
                                                   C.c_double, C.c_double, _dp, _dp]),
     "cugp_bcm_create_ard": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_bcm_create_split_ard": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_ard_kernel": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_split_ard_kernel": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int,
+                                                   C.POINTER(C.c_void_p)]),
     "cugp_bcm_num_hyper": (C.c_int, [C.c_void_p, _ip]),
     "cugp_bcm_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "cugp_bcm_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),

@@ -106,10 +106,20 @@ int cugp_bcm_create_kernel(int ndev, const int* devices, int nexperts, const int
     return bcm_create(ndev, devices, nexperts, rows, d, kernel, false, out);
 }
 
-// every expert an ARD handle (cugp_create_ard, SE): nh = d + 2 hyper-parameters, the _ard calls below
+// every expert an SE-ARD handle (cugp_create_ard): nh = d + 2 hyper-parameters, the _ard calls below
 int cugp_bcm_create_ard(int ndev, const int* devices, int nexperts, const int* rows, int d, cugp_bcm** out)
 {
     return bcm_create(ndev, devices, nexperts, rows, d, CUGP_KERNEL_SE, true, out);
+}
+
+// ARD experts of any covariance family (cugp_create_ard_kernel); kind 0 is the call above
+int cugp_bcm_create_ard_kernel(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel,
+                               cugp_bcm** out)
+{
+    if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52)
+        return cugp_internal_fail(CUGP_ERR_INVALID,
+                                  "cugp_bcm_create_ard_kernel: unknown kernel kind (0 SE, 1 Matern 3/2, 2 Matern 5/2)");
+    return bcm_create(ndev, devices, nexperts, rows, d, kernel, true, out);
 }
 
 }  // extern "C"
@@ -141,7 +151,7 @@ int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int 
     for (int k = 0; k < nexperts; k++) {
         DeviceSet& ds = b->sets[k % nsets];
         cugp_gp* g = nullptr;
-        int rc = ard ? cugp_create_ard_padded(rows[k], d, ds.device, pad_to, &g)
+        int rc = ard ? cugp_create_ard_kernel(rows[k], d, ds.device, pad_to, kernel, &g)
                      : cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
         if (rc) { cugp_bcm_destroy(b); return rc; }
         cugp_mark_bcm_expert(g);                        // (cugp_append refuses the experts of a BCM)
@@ -212,6 +222,15 @@ int cugp_bcm_create_split_ard(const double* X, const double* y, int N, int D, in
                               cugp_bcm** out)
 {
     return bcm_create_split(X, y, N, D, K, ndev, devices, CUGP_KERNEL_SE, true, out);
+}
+
+int cugp_bcm_create_split_ard_kernel(const double* X, const double* y, int N, int D, int K, int ndev,
+                                     const int* devices, int kernel, cugp_bcm** out)
+{
+    if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52)
+        return cugp_internal_fail(CUGP_ERR_INVALID,
+                                  "cugp_bcm_create_split_ard_kernel: unknown kernel kind (0 SE, 1 Matern 3/2, 2 Matern 5/2)");
+    return bcm_create_split(X, y, N, D, K, ndev, devices, kernel, true, out);
 }
 
 int cugp_bcm_create_split(const double* X, const double* y, int N, int D, int K, int device, cugp_bcm** out)

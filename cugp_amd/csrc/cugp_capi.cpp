@@ -126,7 +126,7 @@ struct cugp_gp {
     bool ard = false;
     int nh = 3;
     std::vector<double> theta = {0, 0, 0}, last_g = {NAN, NAN, NAN};
-    // covariance family (cugp.h CUGP_KERNEL_*, kernels.h KERNEL_*), for life; ARD handles are SE.  Read wherever one of
+    // covariance family (cugp.h CUGP_KERNEL_*, kernels.h KERNEL_*), for life, ARD handles included.  Read wherever one of
     // the four passes that evaluate the kernel function is launched; nothing else depends on it.
     int kernel = KERNEL_SE;
     bool have_data = false;
@@ -1104,6 +1104,14 @@ int cugp_create_ard(int n, int d, int device, cugp_gp** out) { return create_han
 int cugp_create_ard_padded(int n, int d, int device, int npad_min, cugp_gp** out)
 {
     return create_handle(n, d, device, npad_min, true, out);
+}
+
+// one length scale per input dimension with any covariance family (kind 0: cugp_create_ard_padded, the same launches)
+int cugp_create_ard_kernel(int n, int d, int device, int npad_min, int kernel, cugp_gp** out)
+{
+    if (kernel < 0 || kernel >= KERNEL_COUNT)
+        return fail(CUGP_ERR_INVALID, "cugp_create_ard_kernel: unknown kernel kind (0 SE, 1 Matern 3/2, 2 Matern 5/2)");
+    return create_handle(n, d, device, npad_min, true, out, kernel);
 }
 
 static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel)

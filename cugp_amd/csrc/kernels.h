@@ -67,14 +67,15 @@ struct HyperScalars {              // exp(2*theta) evaluated on the host, as the
 // joint-covariance epilogue, gradient trace) take one of these and launch the instantiation it names: k_build / k_cross /
 // k_predict_cov_finish / k_trace for SE, the same bodies as k_*_matern<KIND> for the Matern kinds -- with everything SE's
 // launches carry (batched experts, ticket zeroing, device-resident hyper-scalars, stamps, the fused final sums) -- and
-// k_*_ard for ARD.
+// k_*_ard (SE) or k_*_ard_matern<KIND> for ARD.
 //   h:   the hyper-scalars by value
 //   hd:  (optional) the same in device memory, read INSTEAD of h by the passes a captured graph replays (build, trace,
 //        k_finalize): the graph sees new hyper-parameters by one copy into that buffer
 //   ard: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart):
 //        k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd is
 //        then mandatory and read by every pass: the hyper-scalars (ell_sq unused) directly followed by the d weights --
-//        one staging area, one copy.  Same tiles, stores and padding as the isotropic launches; SE only.  Batched
+//        one staging area, one copy.  Same tiles, stores and padding as the isotropic launches.  kind != KERNEL_SE: the
+//        Matern entry of the same weighted distance (k_*_ard_matern<KIND>, the _ard kernels' argument lists).  Batched
 //        experts (build, cross-covariance, trace; not the joint-covariance epilogue) read the GROUP's one copy -- the lead
 //        expert's hd -- since the experts of a group share their hyper-parameters.  An ARD descriptor without hd is a
 //        programming error -- asserted, so checked only in builds without NDEBUG (the library's own build has none).

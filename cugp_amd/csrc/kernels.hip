@@ -987,14 +987,18 @@ __device__ __forceinline__ void matern_entry(double s, double sf2, double& kf, d
     kf = dead ? 0.0 : sf2 * (p * e);
     dk = dead ? 0.0 : sf2 * (q * e);
 }
-// the value of one entry without the noise term (the three passes that need no derivative).  ARD (SE only): d2 is the
-// WEIGHTED squared distance, so there is no division and dl is not read
+// the value of one entry without the noise term (the three passes that need no derivative).  ARD: d2 is the WEIGHTED
+// squared distance, so there is no division and dl is not read -- SE exp(-d2 / 2), the Matern kinds matern_entry at
+// s = d2 (its roundings and its e == 0 guard)
 template <bool ARD, int KIND>
 __device__ __forceinline__ double kernel_value(double d2, const DivBy& dl, double sf2)
 {
-    if constexpr (ARD) {
-        static_assert(KIND == KERNEL_SE, "ARD handles are SE");
+    if constexpr (ARD && KIND == KERNEL_SE) {
         return sf2 * exp(-0.5 * d2);
+    } else if constexpr (ARD) {
+        double kf, dk;
+        matern_entry<KIND>(d2, sf2, kf, dk);
+        return kf;
     } else if constexpr (KIND == KERNEL_SE) {
         return sf2 * exp(div_by(-d2 * 0.5, dl));                  // covkernel.cpp:89
     } else {
@@ -1094,6 +1098,16 @@ __global__ __launch_bounds__(256) void k_build_matern(const double* __restrict__
     build_body<false, KIND>(X, n, d, npad, h_arg, hd, K, full, tickets, bt, stamp);
 }
 
+// ARD x Matern (GPML covMaternard): k_build_ard's arguments, the Matern entry of the weighted distance
+template <int KIND>
+__global__ __launch_bounds__(256) void k_build_ard_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                          const HyperScalars* __restrict__ hd, double* __restrict__ K,
+                                                          int full, unsigned* __restrict__ tickets,
+                                                          const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
+{
+    build_body<true, KIND>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, bt, stamp);
+}
+
 // Ks[t][i] = sf2 * exp(-0.5 |xt_t - x_i|^2 / l^2) (no noise, covkernel.cpp:105-116); zero padding
 // bt (batched): blockIdx.y selects the expert -- X, n from its table entry, Ks = the expert's [ntpad][npad] slice
 template <bool ARD, int KIND = KERNEL_SE>
@@ -1152,6 +1166,15 @@ __global__ __launch_bounds__(256) void k_cross_matern(const double* __restrict__
                                                       double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
 {
     cross_body<false, KIND>(X, n, d, npad, Xt, nt, ntpad, h, nullptr, Ks, bt);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cross_ard_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                          const double* __restrict__ Xt, int nt, int ntpad,
+                                                          const HyperScalars* __restrict__ hd, double* __restrict__ Ks,
+                                                          const ExpertPtrs* __restrict__ bt)
+{
+    cross_body<true, KIND>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, bt);
 }
 
 // ---- joint predictive covariance (cugp_predict_cov): Sigma = k(Xt,Xt) (+ sn2 I) - W W^T, W = Ks L^-T ----
@@ -1257,6 +1280,18 @@ __global__ __launch_bounds__(256) void k_predict_cov_finish_matern(const double*
 {
     predict_cov_finish_body<false, KIND>(Xt, nt, d, ntpad, h, nullptr, with_noise, jitter, A, scr, pstride, nscr,
                                          tickets);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_predict_cov_finish_ard_matern(const double* __restrict__ Xt, int nt, int d,
+                                                                       int ntpad, const HyperScalars* __restrict__ hd,
+                                                                       int with_noise, double jitter,
+                                                                       double* __restrict__ A,
+                                                                       const double* __restrict__ scr, size_t pstride,
+                                                                       int nscr, unsigned* __restrict__ tickets)
+{
+    predict_cov_finish_body<true, KIND>(Xt, nt, d, ntpad, *hd, ard_weights(hd), with_noise, jitter, A, scr, pstride,
+                                        nscr, tickets);
 }
 
 // The Cholesky writes the lower triangle only: the strict upper part of every 128x128 diagonal tile still holds Sigma,
@@ -3379,6 +3414,290 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize_targets(const double* 
 }
 
 // ------------------------------------------------------------------------------------------
+// ARD x Matern 3/2 and 5/2 (GPML covMaternard): the passes that need a derivative.  With u_c = (x_c - x'_c) w_c,
+// s = sum u_c^2 (sqdist_4x4<true>), a = c sqrt(s), e = exp(-a):
+//   kf = sf2 (p e) as matern_entry's,   dk / dtheta_c = H u_c^2,   dk / dx*_c = -H (x*_c - x_c) w_c^2
+//   3/2:  H = sf2 (3 e)          5/2:  H = sf2 ((RN(5/3) (1 + a)) e)    -- predict_grad_body's G, no singularity at a = 0
+// One exp per entry serves kf and H; e == 0 selects exact zeros for both ((1 + inf) * 0 is NaN).  No FMA contraction.
+// The kernels have bodies of their own: k_trace_ard, k_trace_targets_ard and predict_grad_body keep their instructions.
+// ------------------------------------------------------------------------------------------
+template <int KIND>
+__device__ __forceinline__ void ard_matern_entry(double s, double sf2, double& kf, double& hh)
+{
+#pragma clang fp contract(off)
+    static_assert(KIND == KERNEL_MATERN32 || KIND == KERNEL_MATERN52, "Matern kinds only");
+    const double c = KIND == KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979;
+    const double a = c * __builtin_sqrt(s);
+    const double e = exp(-a);
+    const double p1 = 1.0 + a;
+    double p, q;
+    if (KIND == KERNEL_MATERN32) {
+        p = p1;
+        q = 3.0;
+    } else {
+        p = p1 + (a * a) * 0.3333333333333333;
+        q = 1.6666666666666667 * p1;
+    }
+    const bool dead = e == 0.0;
+    kf = dead ? 0.0 : sf2 * (p * e);
+    hh = dead ? 0.0 : sf2 * (q * e);
+}
+
+// Gradient pass: k_trace_ard's two sweeps, partial layout (part[c * nblocks + block]; d: sum W o K, d + 1: tr W) and
+// summation order.  The 16 registers kept for the second sweep hold 2 (w H) where k_trace_ard keeps 2 (w Kf); sum W o K
+// takes Kf (+ sn2 on the diagonal, which has no share in any g_c).  k_finalize_ard / k_finalize_targets follow as they are.
+// TARGETS: W = m K^-1 - sum_t alpha_t alpha_t^T from the target-major AV ([m][npad]; k_trace_targets_ard's), single
+// handle; else W = K^-1 - alpha alpha^T from the vector AV, batched (blockIdx.y = expert) as k_trace_ard.
+template <int KIND, bool TARGETS>
+__device__ __forceinline__ void trace_ard_matern_body(const double* __restrict__ X, int n, int d, int npad,
+                                                      const HyperScalars* __restrict__ hd,
+                                                      const double* __restrict__ Kinv, const double* __restrict__ AV,
+                                                      int m, double* __restrict__ part,
+                                                      const ExpertPtrs* __restrict__ bt)
+{
+#pragma clang fp contract(off)
+    if (!TARGETS && bt) {
+        const ExpertPtrs& e = bt[blockIdx.y];
+        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); AV = GP(e.alpha); part = GP(e.part);
+    }
+    const HyperScalars h = *hd;
+    const double* __restrict__ wts = ard_weights(hd);
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ __attribute__((aligned(16))) double la[TARGETS ? TGT_CHUNK : 1][KT], lb[TARGETS ? TGT_CHUNK : 1][KT];
+    __shared__ double ws[DC];
+    __shared__ double red[DC][4];
+    int ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    const int i0 = ti * KT, j0 = tj * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const size_t nblocks = gridDim.x;
+    double wk[4][4], S[4][4];
+    sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, wk, wts, ws);
+    double aj[4];
+    if constexpr (TARGETS) {
+        targets_outer_4x4(AV, npad, m, i0, j0, la, lb, S);
+    } else {
+#pragma unroll
+        for (int b = 0; b < 4; b++) aj[b] = AV[j0 + col4(tx, b)];
+    }
+    double s2 = 0.0, s3 = 0.0;
+    const double dm = (double)m;
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int i = i0 + ty * 4 + a;
+        const double ai = TARGETS ? 0.0 : AV[i];
+        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
+        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
+        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const int j = j0 + col4(tx, b);
+            double e = 0.0;
+            if (i < n && j < n && (ti != tj || j <= i)) {
+                const double w = TARGETS ? dm * kv[b] - S[a][b] : kv[b] - ai * aj[b];
+                double kf, hh;
+                ard_matern_entry<KIND>(wk[a][b], h.signal_var, kf, hh);
+                if (i == j) {
+                    kf += h.noise_var;
+                    s2 += w * kf;
+                    s3 += w;
+                } else {
+                    e = 2.0 * (w * hh);
+                    s2 += 2.0 * (w * kf);
+                }
+            }
+            wk[a][b] = e;
+        }
+    }
+    s2 = wave_sum(s2); s3 = wave_sum(s3);
+    if ((t & 63) == 0) { red[0][t >> 6] = s2; red[1][t >> 6] = s3; }
+    __syncthreads();
+    if (t < 2) part[(size_t)(d + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    for (int c0 = 0; c0 < d; c0 += DC) {
+        const int dc = (d - c0 < DC) ? (d - c0) : DC;
+        __syncthreads();
+        for (int e = t; e < KT * dc; e += 256) {
+            int r = e / dc, c = e - r * dc;
+            xs[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
+            ys[r][c] = (j0 + r < n) ? X[(size_t)(j0 + r) * d + c0 + c] : 0.0;
+        }
+        if (t < dc) ws[t] = wts[c0 + t];
+        __syncthreads();
+        double gs[DC];
+#pragma unroll
+        for (int c = 0; c < DC; c++) {
+            gs[c] = 0.0;
+            if (c < dc) {
+                double xv[4], yv[4];
+#pragma unroll
+                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+                const double wc = ws[c];
+                double acc = 0.0;
+#pragma unroll
+                for (int a = 0; a < 4; a++)
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        const double df = (xv[a] - yv[b]) * wc;
+                        acc = acc + wk[a][b] * (df * df);
+                    }
+                gs[c] = wave_sum(acc);
+            }
+        }
+        if ((t & 63) == 0) {
+#pragma unroll
+            for (int c = 0; c < DC; c++) red[c][t >> 6] = gs[c];
+        }
+        __syncthreads();
+        if (t < dc) part[(size_t)(c0 + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_trace_ard_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                          const HyperScalars* __restrict__ hd,
+                                                          const double* __restrict__ Kinv,
+                                                          const double* __restrict__ alpha, double* __restrict__ part,
+                                                          const ExpertPtrs* __restrict__ bt)
+{
+    trace_ard_matern_body<KIND, false>(X, n, d, npad, hd, Kinv, alpha, 1, part, bt);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void k_trace_targets_ard_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                                  const HyperScalars* __restrict__ hd,
+                                                                  const double* __restrict__ Kinv,
+                                                                  const double* __restrict__ A, int m,
+                                                                  double* __restrict__ part)
+{
+    trace_ard_matern_body<KIND, true>(X, n, d, npad, hd, Kinv, A, m, part, nullptr);
+}
+
+// Gradient of the prediction with respect to the test inputs: predict_grad_body's Matern branch with the weighted
+// distance.  First sweep: the chunk's weights staged beside the X tiles, the difference formed first, then weighted,
+// then squared (sqdist_4x4<true>'s order), G = H from a of the weighted distance.  Second sweep, partial layout and
+// butterfly as predict_grad_body's: UNWEIGHTED differences -- k_predict_grad_finish applies w_c^2 once per output.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_predict_grad_ard_matern(const double* __restrict__ X, int n, int d, int npad,
+                                                                 const double* __restrict__ Xt, int nt,
+                                                                 const HyperScalars* __restrict__ hd,
+                                                                 const double* __restrict__ V,
+                                                                 const double* __restrict__ alpha,
+                                                                 double* __restrict__ part, size_t pstride)
+{
+#pragma clang fp contract(off)
+    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ double ws[DC];
+    const double sf2 = hd->signal_var;
+    const double* __restrict__ wts = ard_weights(hd);
+    const int tiles_i = (n + KT - 1) / KT;
+    const int tt = blockIdx.x / tiles_i, ti = blockIdx.x % tiles_i;
+    const int t0 = tt * KT, i0 = ti * KT;
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    // one chunk of features of the tile's test rows (xs) and training rows (ys) and its weights into LDS
+    auto stage = [&](int c0, int dc) {
+        __syncthreads();
+        for (int e = t; e < KT * dc; e += 256) {
+            const int r = e / dc, c = e - r * dc;
+            xs[r][c] = (t0 + r < nt) ? Xt[(size_t)(t0 + r) * d + c0 + c] : 0.0;
+            ys[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
+        }
+        if (t < dc) ws[t] = wts[c0 + t];
+        __syncthreads();
+    };
+    double G[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) G[a][b] = 0.0;
+    for (int c0 = 0; c0 < d; c0 += DC) {
+        const int dc = (d - c0 < DC) ? (d - c0) : DC;
+        stage(c0, dc);
+        for (int c = 0; c < dc; c++) {
+            double xv[4], yv[4];
+#pragma unroll
+            for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+            const double wc = ws[c];
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const double df = (xv[a] - yv[b]) * wc;
+                    G[a][b] = G[a][b] + df * df;
+                }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            double kf, hh;
+            ard_matern_entry<KIND>(G[a][b], sf2, kf, hh);
+            G[a][b] = hh;
+        }
+    double ga[4][4], gv[4][4];
+    double al[4];
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int i = i0 + col4(tx, b);
+        al[b] = i < n ? alpha[i] : 0.0;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+        const int tr = t0 + ty * 4 + a;
+        const size_t off = (size_t)tr * npad + i0 + tx * 2;
+        double vv[4] = {0.0, 0.0, 0.0, 0.0};
+        if (V) {
+            const d2 v01 = *(const d2*)(V + off), v23 = *(const d2*)(V + off + 32);
+            vv[0] = v01[0]; vv[1] = v01[1]; vv[2] = v23[0]; vv[3] = v23[1];
+        }
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            const bool in = tr < nt && i0 + col4(tx, b) < n;
+            ga[a][b] = in ? G[a][b] * al[b] : 0.0;
+            gv[a][b] = in ? G[a][b] * vv[b] : 0.0;
+        }
+    }
+    double* pm_out = part + (size_t)ti * 2 * pstride;
+    double* pv_out = pm_out + pstride;
+    for (int c0 = 0; c0 < d; c0 += DC) {
+        const int dc = (d - c0 < DC) ? (d - c0) : DC;
+        stage(c0, dc);
+        for (int c = 0; c < dc; c++) {
+            double xv[4], yv[4], pm[4], pv[4];
+#pragma unroll
+            for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
+#pragma unroll
+            for (int a = 0; a < 4; a++) {
+                pm[a] = 0.0; pv[a] = 0.0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const double df = xv[a] - yv[b];
+                    pm[a] = pm[a] + ga[a][b] * df;
+                    pv[a] = pv[a] + gv[a][b] * df;
+                }
+            }
+#pragma unroll
+            for (int m = 1; m < 16; m <<= 1)
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    pm[a] = pm[a] + __shfl_xor(pm[a], m, 16);
+                    if (V) pv[a] = pv[a] + __shfl_xor(pv[a], m, 16);
+                }
+            if (tx == (c & 15)) {
+#pragma unroll
+                for (int a = 0; a < 4; a++) {
+                    const int tr = t0 + ty * 4 + a;
+                    if (tr < nt) {
+                        pm_out[(size_t)tr * d + c0 + c] = pm[a];
+                        if (V) pv_out[(size_t)tr * d + c0 + c] = pv[a];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // Appending observations (cugp_append): one bordering step of the factor, its inverse and K^-1 by k <= 128 new rows
 // [r0, r0 + k) that lie in ONE tile row.  The existing launches have left P = B L^-T and V = P L^-1 ([128][ld], zero
 // beyond row k and column r0), and the factor handle holds C = chol(S) (Cf, lower) and C^-1 (Ci, lower, exact zeros
@@ -3553,9 +3872,13 @@ static inline int tri_count(int n) { return n * (n + 1) / 2; }
 #define CUGP_ISO_KERNEL_T(cf, stem)                                                      \
     ((cf).kind == KERNEL_MATERN32   ? stem<KERNEL_MATERN32>                              \
      : (cf).kind == KERNEL_MATERN52 ? stem<KERNEL_MATERN52> : stem<KERNEL_SE>)
+// The table of ARD instantiations: k_<pass>_ard for SE, k_<pass>_ard_matern<KIND> (the same argument list) otherwise.
+#define CUGP_ARD_KERNEL(cf, stem)                                                        \
+    ((cf).kind == KERNEL_MATERN32   ? stem##_ard_matern<KERNEL_MATERN32>                 \
+     : (cf).kind == KERNEL_MATERN52 ? stem##_ard_matern<KERNEL_MATERN52> : stem##_ard)
 static inline bool is_ard(const CovFn& cf)
 {
-    assert(!cf.ard || (cf.hd && cf.kind == KERNEL_SE));
+    assert(!cf.ard || cf.hd);
     return cf.ard;
 }
 
@@ -3564,8 +3887,8 @@ void launch_kbuild(const double* X, int n, int d, int npad, const CovFn& cf, dou
 {
     const dim3 grid(tri_count(npad / KT), bt.count);
     if (is_ard(cf))
-        hipLaunchKernelGGL(k_build_ard, grid, dim3(256), 0, s, X, n, d, npad, cf.hd, K, full ? 1 : 0, tickets, bt.tab,
-                           take_stamp());
+        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.hd, K, full ? 1 : 0,
+                           tickets, bt.tab, take_stamp());
     else
         hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, K, full ? 1 : 0,
                            tickets, bt.tab, take_stamp());
@@ -3584,7 +3907,8 @@ void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, in
 {
     const dim3 grid((ntpad / KT) * (npad / KT), bt.count);
     if (is_ard(cf))
-        hipLaunchKernelGGL(k_cross_ard, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.hd, Ks, bt.tab);
+        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.hd, Ks,
+                           bt.tab);
     else
         hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.h, Ks,
                            bt.tab);
@@ -3835,8 +4159,8 @@ void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, const
 {
     const dim3 grid(tri_count(ntpad / KT));
     if (is_ard(cf))
-        hipLaunchKernelGGL(k_predict_cov_finish_ard, grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.hd, with_noise ? 1 : 0,
-                           jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_predict_cov_finish), grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.hd,
+                           with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
     else
         hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_predict_cov_finish), grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.h,
                            with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
@@ -3866,7 +4190,11 @@ void launch_predict_grad(const double* X, int n, int d, int npad, const double* 
                          hipStream_t s)
 {
     const dim3 grid(((nt + KT - 1) / KT) * predict_grad_tiles(n));
-    if (is_ard(cf))
+    if (is_ard(cf) && cf.kind != KERNEL_SE)     // (SE-ARD reads G from Ks: the isotropic SE kernel serves it)
+        CUGP_LAUNCH((cf.kind == KERNEL_MATERN32 ? k_predict_grad_ard_matern<KERNEL_MATERN32>
+                                                : k_predict_grad_ard_matern<KERNEL_MATERN52>),
+                    grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.hd, V, alpha, part, pstride);
+    else if (is_ard(cf))
         CUGP_LAUNCH(k_predict_grad, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha, part, pstride);
     else
         CUGP_LAUNCH(CUGP_ISO_KERNEL(cf, k_predict_grad), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha,
@@ -3932,8 +4260,8 @@ void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, cons
     const int nblocks = tri_count(npad / KT);
     if (is_ard(cf)) {                          // always both launches: there is no fused form of the ARD final sums
         assert(hout && (out || bt.tab));
-        hipLaunchKernelGGL(k_trace_ard, dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, alpha, part,
-                           bt.tab);
+        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_trace), dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv,
+                           alpha, part, bt.tab);
         hipLaunchKernelGGL(k_finalize_ard, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part,
                            npad / TILE, part, nblocks, cf.hd, out, hout, (size_t)(ARD_ROW_GRAD + d + 2), bt.tab);
         return;
@@ -3967,7 +4295,8 @@ void launch_trace_targets(const double* X, int n, int d, int npad, const CovFn& 
 {
     const dim3 grid(tri_count(npad / KT));
     if (is_ard(cf))
-        hipLaunchKernelGGL(k_trace_targets_ard, grid, dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, A, m, part);
+        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_trace_targets), grid, dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, A, m,
+                           part);
     else
         hipLaunchKernelGGL(CUGP_ISO_KERNEL_T(cf, k_trace_targets), grid, dim3(256), 0, s, X, n, d, npad, cf.h, Kinv, A, m,
                            part);

@@ -15,6 +15,8 @@ from .capi import check, f64, ptr
 
 KERNELS = {"se": capi.CUGP_KERNEL_SE, "matern32": capi.CUGP_KERNEL_MATERN32, "matern52": capi.CUGP_KERNEL_MATERN52}
 KERNEL_NAMES = {v: k for k, v in KERNELS.items()}
+# one length scale per input dimension with a Matern kind (GPML covMaternard): the name sets ard=True by itself
+ARD_KERNELS = {"matern32_ard": capi.CUGP_KERNEL_MATERN32, "matern52_ard": capi.CUGP_KERNEL_MATERN52}
 
 
 COMBINE = {"poe": capi.CUGP_COMBINE_POE, "gpoe": capi.CUGP_COMBINE_GPOE, "bcm": capi.CUGP_COMBINE_BCM,
@@ -46,6 +48,20 @@ def kernel_kind(kernel):
     return int(kernel)
 
 
+def kernel_spec(kernel, ard=False):
+    """(kind, ard) of a kernel= / ard= pair: the isotropic names with ard as given (ard=True is squared-exponential
+    only), or one of ARD_KERNELS' names, which are ARD whatever `ard` says."""
+    if isinstance(kernel, str) and kernel.lower() in ARD_KERNELS:
+        return ARD_KERNELS[kernel.lower()], True
+    if isinstance(kernel, str) and kernel.lower().endswith("_ard"):
+        raise ValueError("kernel must be one of %s, not %r" % (sorted(KERNELS) + sorted(ARD_KERNELS), kernel))
+    kind = kernel_kind(kernel)
+    if ard and kind != capi.CUGP_KERNEL_SE:
+        raise ValueError('ard=True is squared-exponential only; the ARD Matern kernels are kernel="%s_ard"'
+                         % KERNEL_NAMES[kind])
+    return kind, bool(ard)
+
+
 class Covsum:
     """One GP expert on one GPU.  Covsum(n, d) as covkernel.cpp:14-37; X, y are given per call as in
     the reference and uploaded whenever their CONTENTS differ from what the GPU holds (the reference
@@ -54,17 +70,20 @@ class Covsum:
     ard=True: one length scale per input dimension (cugp_create_ard; GPML covSEard's order): the hyper-parameter
     vector is [log l_1 .. log l_d, log sigma_f, log sigma_n], gradients and cg_solve traces have d + 2 (+ 1) entries.
     kernel="se" | "matern32" | "matern52": the covariance family (cugp_create_kernel; GPML covMaterniso with d = 3, 5),
-    same three hyper-parameters; fixed for the life of the handle.  ARD is squared-exponential only.
+    same three hyper-parameters; fixed for the life of the handle.  ard=True is squared-exponential only;
+    kernel="matern32_ard" | "matern52_ard" (GPML covMaternard; cugp_create_ard_kernel) is ARD with a Matern kind: .ard
+    is True, nh = d + 2, and .kernel reports "matern32" / "matern52".
     npad_min: rows the handle has room for (capacity); append(X, y) adds observations up to it."""
 
     def __init__(self, n, d, device=0, npad_min=0, ard=False, kernel="se"):
-        self.n, self.d, self.device, self.ard = int(n), int(d), int(device), bool(ard)
+        self.n, self.d, self.device = int(n), int(d), int(device)
+        self._kind, self.ard = kernel_spec(kernel, ard)
         self.nh = self.d + 2 if self.ard else 3
-        self._kind = kernel_kind(kernel)
-        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
-            raise ValueError("ard=True is squared-exponential only (ARD x Matern is not built)")
         self._h = C.c_void_p()
-        if self._kind != capi.CUGP_KERNEL_SE:
+        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
+            check(capi.lib().cugp_create_ard_kernel(self.n, self.d, self.device, int(npad_min), self._kind,
+                                                    C.byref(self._h)))
+        elif self._kind != capi.CUGP_KERNEL_SE:
             check(capi.lib().cugp_create_kernel(self.n, self.d, self.device, int(npad_min), self._kind,
                                                 C.byref(self._h)))
         elif self.ard:
@@ -497,19 +516,21 @@ class BCM:
     the reference constructor's row partition (BCM.cpp:85-110).
     ard=True: every expert an ARD handle (cugp_bcm_create_ard): the shared hyper-parameter vector is [log l_1 .. log l_d,
     log sigma_f, log sigma_n] (nh = d + 2), gradients have nh entries, rows and cg_solve traces 1 + nh columns.
-    Squared-exponential only, as Covsum."""
+    ard=True is squared-exponential only; kernel="matern32_ard" | "matern52_ard" makes every expert an ARD Matern handle
+    (cugp_bcm_create_ard_kernel), as Covsum."""
 
     def __init__(self, rows, d, device=0, devices=None, kernel="se", ard=False):
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         devs = np.ascontiguousarray([device] if devices is None else list(devices), dtype=np.int32)
         self.rows, self.d, self.device, self.devices = rows.tolist(), int(d), int(devs[0]), devs.tolist()
-        self._kind = kernel_kind(kernel)
-        self.ard = bool(ard)
+        self._kind, self.ard = kernel_spec(kernel, ard)
         self.nh = self.d + 2 if self.ard else 3
-        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
-            raise ValueError("ard=True is squared-exponential only (ARD x Matern is not built)")
         self._h = C.c_void_p()
-        if self.ard:
+        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
+            check(capi.lib().cugp_bcm_create_ard_kernel(len(self.devices), devs.ctypes.data_as(capi._ip),
+                                                        len(self.rows), rows.ctypes.data_as(capi._ip), self.d,
+                                                        self._kind, C.byref(self._h)))
+        elif self.ard:
             check(capi.lib().cugp_bcm_create_ard(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
                                                  rows.ctypes.data_as(capi._ip), self.d, C.byref(self._h)))
         elif self._kind != capi.CUGP_KERNEL_SE:

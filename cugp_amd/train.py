@@ -27,8 +27,9 @@ def main():
     ap.add_argument("--budget", type=int, default=100)
     ap.add_argument("--test-rows", type=int, default=0, help="rows after --rows in chunk 0 used as a held-out set")
     ap.add_argument("--backend", default="nccl")
-    ap.add_argument("--kernel", default="se", choices=["se", "matern32", "matern52"],
-                    help="covariance family of every expert (the same on every rank)")
+    ap.add_argument("--kernel", default="se", choices=["se", "matern32", "matern52", "matern32_ard", "matern52_ard"],
+                    help="covariance family of every expert (the same on every rank); the _ard names: one length scale "
+                         "per input dimension with that Matern kind, the start as --ard's")
     ap.add_argument("--ard", action="store_true",
                     help="one length scale per input dimension (squared exponential only): the start is "
                          "[hp0] * d + [hp1, hp2]")
@@ -58,7 +59,7 @@ def main():
     shards = dataset.load_shards(args.inputs, args.labels, args.numchunks, rows=None, only=mine)
     experts = [None if s is None else (s[0][:args.rows], s[1][:args.rows]) for s in shards]
     bcm = ShardedBCM(experts, rank=rank, world=world, device=local, kernel=args.kernel, ard=args.ard)
-    bcm.set_loghyper([args.hp[0]] * (bcm.nh - 2) + list(args.hp[1:]) if args.ard else args.hp)
+    bcm.set_loghyper([args.hp[0]] * (bcm.nh - 2) + list(args.hp[1:]) if bcm.ard else args.hp)
     t0 = time.perf_counter()
     trace = bcm.cg_solve(args.budget)
     dt = time.perf_counter() - t0

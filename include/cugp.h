@@ -110,14 +110,30 @@ int cugp_loglik_grad_fetch_ard(cugp_gp *gp, double *ll, double *g /* may be NULL
  * bit; an unknown kind is CUGP_ERR_INVALID before any device call.  Every call that works on an isotropic handle works
  * on a Matern one: data, overlap, LL / gradient in all forms, the continuation from a valid factor, the predictions
  * (marginal, joint, draws), K, k_test, the squared-distance intermediate (which does not depend on the kind), factor,
- * inverse, alpha, profiling, tuning, the optimisers, groups and every cugp_bcm_* call.  cugp_create_ard stays SE:
- * ARD x Matern is not built.  Experts of one group (and so of one BCM) must have the same kind; the ranks of a BCM
+ * inverse, alpha, profiling, tuning, the optimisers, groups and every cugp_bcm_* call.  cugp_create_ard stays SE;
+ * cugp_create_ard_kernel below is ARD with a Matern kind.  Experts of one group (and so of one BCM) must have the same
+ * kind; the ranks of a BCM
  * sharded one process per GPU must be created with the same kind -- the caller's duty, like passing the same Xt. */
 #define CUGP_KERNEL_SE 0
 #define CUGP_KERNEL_MATERN32 1
 #define CUGP_KERNEL_MATERN52 2
 int cugp_create_kernel(int n, int d, int device, int npad_min, int kernel, cugp_gp **out);
 int cugp_kernel_kind(const cugp_gp *gp, int *kernel);
+
+/* ---- ARD x covariance family: one length scale per input dimension with a Matern kind (GPML's covMaternard, the
+ *      default kernel of BoTorch and scikit-optimize).  theta, its order and nh = d + 2 are the ARD handle's above.  With
+ *      w_c = exp(-theta_c), u_c = (x_c - x'_c) w_c, s = sum_c u_c^2, a = sqrt(3 s) or sqrt(5 s), e = exp(-a):
+ *        CUGP_KERNEL_MATERN32  Kf = sf2 (1 + a) e              dk/dtheta_c = H u_c^2,  H = 3 sf2 e
+ *        CUGP_KERNEL_MATERN52  Kf = sf2 (1 + a + a^2/3) e      dk/dtheta_c = H u_c^2,  H = (5/3) sf2 (1 + a) e
+ *      Gradients of -LL: g_c = 1/2 sum_ij W_ij H_ij u_c,ij^2, then g_d = sum W o Kf and g_{d+1} = sn2 tr W as for every
+ *      handle.  H has no singularity at a = 0; equal length scales give the isotropic Matern handle's model; k(x, x) =
+ *      sf2 + sn2.  An e that underflows gives exactly 0 for Kf and H.
+ * Kind 0 is cugp_create_ard_padded's handle: the same launches, bit for bit.  An unknown kind is CUGP_ERR_INVALID
+ * before any device call.  cugp_kernel_kind reports the kind; every call that works on an ARD handle works on these
+ * unchanged
+ * (the _ard calls, predictions and their input gradients, targets, cugp_append, groups, cugp_cg_solve_ard).  Experts of
+ * one group must agree in kind and in the ARD flag. */
+int cugp_create_ard_kernel(int n, int d, int device, int npad_min, int kernel, cugp_gp **out);
 
 /* ---- objective ----
  * cugp_loglik       : Covsum::compute_loglikelihood covkernel.cpp:118-129 ; compute_log_likelihood cuda_gp.cu:838-855
@@ -493,12 +509,14 @@ int cugp_poe_combine_grad(const double *mean, const double *var,       /* [K][nt
                           double *out_dmean, double *out_dvar);        /* [nt][d] each */
 int cugp_bcm_predict_grad(cugp_bcm *b, const double *Xt, int nt, int mode, int with_noise,
                           double *mean, double *var, double *dmean, double *dvar);
-/* ---- ARD BCM: every expert an ARD handle (squared exponential, theta as cugp_create_ard's: nh = d + 2 entries shared by
- *      all experts).  The reference has no counterpart.  The experts run as groups of shared launches, over several
+/* ---- ARD BCM: every expert an ARD handle (squared exponential, or through the _ard_kernel calls a Matern kind; theta
+ *      as cugp_create_ard's: nh = d + 2 entries shared by all experts).  The reference has no counterpart.  The experts
+ *      run as groups of shared launches, over several
  *      devices of one process, or sharded one process per GPU, exactly like isotropic experts; only the rows of an
  *      evaluation are wider: {LL_k, g_k[nh]}, 1 + nh doubles, sums in expert order on the host.
  * An ARD BCM is ARD for life.  cugp_bcm_num_hyper reports nh (3, or d + 2) for any BCM.  Data, cugp_bcm_expert, the
- * three predict calls (their rows do not depend on nh) and cugp_bcm_kernel_kind (SE) work on it unchanged.
+ * three predict calls (their rows do not depend on nh) and cugp_bcm_kernel_kind work on it unchanged.  The _ard_kernel
+ * create calls take the experts' kind directly in front of out (kind 0: the _ard calls; unknown: CUGP_ERR_INVALID).
  * cugp_bcm_cg_solve_ard: the loop of cugp_cg_minimize_n from the current hyper-parameters; trace rows of nh + 1 doubles.
  * cugp_bcm_loglik_grad_allgather_ard: rows_out[world * per][1 + nh]; nh is explicit because a rank that owns no expert
  *      passes b == NULL; still one all-gather on the evaluation's stream and one host wait.
@@ -508,6 +526,10 @@ int cugp_bcm_predict_grad(cugp_bcm *b, const double *Xt, int nt, int mode, int w
 int cugp_bcm_create_ard(int ndev, const int *devices, int nexperts, const int *rows, int d, cugp_bcm **out);
 int cugp_bcm_create_split_ard(const double *X, const double *y, int N, int D, int K, int ndev, const int *devices,
                               cugp_bcm **out);
+int cugp_bcm_create_ard_kernel(int ndev, const int *devices, int nexperts, const int *rows, int d, int kernel,
+                               cugp_bcm **out);
+int cugp_bcm_create_split_ard_kernel(const double *X, const double *y, int N, int D, int K, int ndev,
+                                     const int *devices, int kernel, cugp_bcm **out);
 int cugp_bcm_num_hyper(const cugp_bcm *b, int *nh);
 int cugp_bcm_set_loghyper_ard(cugp_bcm *b, const double *hp, int nh);
 int cugp_bcm_get_loghyper_ard(const cugp_bcm *b, double *hp, int nh);
