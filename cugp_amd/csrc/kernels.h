@@ -63,19 +63,20 @@ struct HyperScalars {              // exp(2*theta) evaluated on the host, as the
     double ell_sq, signal_var, noise_var;
 };
 
-// The covariance function of a handle as the launchers see it.  The four passes that evaluate it (build, cross-covariance,
-// joint-covariance epilogue, gradient trace) take one of these and launch the instantiation it names: k_build / k_cross /
-// k_predict_cov_finish / k_trace for SE, the same bodies as k_*_matern<KIND> for the Matern kinds -- with everything SE's
-// launches carry (batched experts, ticket zeroing, device-resident hyper-scalars, stamps, the fused final sums) -- and
-// k_*_ard (SE) or k_*_ard_matern<KIND> for ARD.
+// The covariance function of a handle as the launchers see it.  The passes that evaluate it (build, cross-covariance,
+// joint-covariance epilogue, gradient trace, multi-target gradient trace, test-input gradient) take one of these and launch
+// the instantiation it names: each pass is ONE kernel template with one argument list, k_build / k_cross /
+// k_predict_cov_finish / k_trace / k_trace_targets / k_predict_grad <ARD, KIND>, picked by one table (kernels.hip
+// CUGP_COV_KERNEL) -- every instantiation with everything SE's launches carry (batched experts, ticket zeroing,
+// device-resident hyper-scalars, stamps; the fused final sums are isotropic only).
 //   h:   the hyper-scalars by value
 //   hd:  (optional) the same in device memory, read INSTEAD of h by the passes a captured graph replays (build, trace,
 //        k_finalize): the graph sees new hyper-parameters by one copy into that buffer
 //   ard: one length scale per input dimension (GPML covSEard's convention; the reference has no counterpart):
 //        k(x, x') = sf2 exp(-1/2 sum_c ((x_c - x'_c) w_c)^2) + sn2 delta, w_c = exp(-theta_c) evaluated on the host.  hd is
 //        then mandatory and read by every pass: the hyper-scalars (ell_sq unused) directly followed by the d weights --
-//        one staging area, one copy.  Same tiles, stores and padding as the isotropic launches.  kind != KERNEL_SE: the
-//        Matern entry of the same weighted distance (k_*_ard_matern<KIND>, the _ard kernels' argument lists).  Batched
+//        one staging area, one copy; the kernels ignore h.  Same tiles, stores and padding as the isotropic launches.
+//        kind != KERNEL_SE: the Matern entry of the same weighted distance.  Batched
 //        experts (build, cross-covariance, trace; not the joint-covariance epilogue) read the GROUP's one copy -- the lead
 //        expert's hd -- since the experts of a group share their hyper-parameters.  An ARD descriptor without hd is a
 //        programming error -- asserted, so checked only in builds without NDEBUG (the library's own build has none).
@@ -207,7 +208,7 @@ int trace_num_blocks(int npad);
 // taken from the experts' table, ticket = tickets[2 nt] of every expert
 // ARD: part[(d + 2) * trace_num_blocks(npad)]; results row out / hout (both mandatory, ARD_ROW_GRAD + d + 2 doubles): [0] LL,
 // [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row), [ARD_ROW_GRAD + c] g_c, c = 0 .. d + 1.  Always two
-// launches (k_trace_ard, k_finalize_ard): there is no fused form of the final sums, and ticket is not used.  Batched:
+// launches (k_trace<true, KIND>, k_finalize_ard): there is no fused form of the final sums, and ticket is not used.  Batched:
 // grids (blocks, experts) and (1, experts); part and out from the table, hout[expert][ARD_ROW_GRAD + d + 2].
 constexpr int ARD_ROW_GRAD = 8;
 void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* alpha,

@@ -2,6 +2,9 @@
 //
 // Path (reference file:line each kernel replaces):
 //   k_build        SE+noise covariance          cpp_serial_gp/covkernel.cpp:64-102, cuda_scalingdist/cuda_gp.cu:232-281
+//                  (every pass that evaluates the covariance function -- k_build, k_cross, k_predict_cov_finish, k_trace,
+//                  k_trace_targets, k_predict_grad -- is one template <bool ARD, int KIND>: SE, Matern 3/2 and 5/2, each
+//                  isotropic or with one length scale per dimension, from one body per pass)
 //   potf2 / trsm / syrk_step / syrk_wide   blocked right-looking Cholesky (near window per step, far columns once per
 //                  panel)   common/matrixops.cpp:68-108, cpp_matrixalgebra/blocked_cholesky.cpp:221-262,
 //                  cuda_src/cuda_gp.cu:1237-1308
@@ -955,18 +958,22 @@ __device__ __forceinline__ double div_by(double a, const DivBy& d)
     return __builtin_fma(rem, d.y, q0);
 }
 
-// ---- Matern 3/2 and 5/2 (GPML covMaterniso, d = 3 and 5): KIND as kernels.h's KERNEL_* ----
-// One entry from s = |x - x'|^2 / l^2 (by div_by, as SE's): r = sqrt(s) correctly rounded, a = c r with c = RN(sqrt 3) or
-// RN(sqrt 5), ONE exp(-a), then  kf = sf2 (p e),  dk = dkf / dlog l = sf2 (q e)  with
-//   3/2:  p = 1 + a,               q = a a
-//   5/2:  p = (1 + a) + t,         q = t (1 + a),   t = (a a) RN(1/3)
+// ---- Matern 3/2 and 5/2 (GPML covMaterniso / covMaternard, d = 3 and 5): KIND as kernels.h's KERNEL_* ----
+// One entry from s = |x - x'|^2 / l^2 (by div_by, as SE's; ARD: s = sum u_c^2, u_c = (x_c - x'_c) w_c, sqdist_4x4<true>):
+// r = sqrt(s) correctly rounded, a = c r with c = RN(sqrt 3) or RN(sqrt 5), ONE exp(-a), then
+//   kf = sf2 (p e),   dk = dkf / dlog l = sf2 (q e),   hh = H = sf2 (g e)   with
+//   3/2:  p = 1 + a,               q = a a,          g = 3
+//   5/2:  p = (1 + a) + t,         q = t (1 + a),    g = RN(5/3) (1 + a),    t = (a a) RN(1/3)
+// H is the factor of the per-dimension and the test-input derivatives (no singularity at a = 0):
+//   dk / dtheta_c = H u_c^2,   dk / dx*_c = -H (x*_c - x_c) s_c   (s_c = 1 / l^2, ARD w_c^2)
 // a a / 3 as a multiply by the rounded constant: an fp64 division is ~18 VALU instructions per entry where the multiply
 // is one, and it adds one rounding (of the constant) to a polynomial without cancellation.  No FMA contraction: the
 // CPU copy of these lines (tests/truth_matern.py) takes the same roundings.
 // Extremes: s = 0 -> a = 0, e = 1: kf = sf2 exactly, dk = 0.  s = +inf (l^2 = 0) -> e = 0, and so for a finite a whose
-// exp underflows: both are 0 exactly (the guard: (1 + inf) * 0 and, for a > 1e154, (a a) * 0 would be NaN).
+// exp underflows: all three are 0 exactly (the guard: (1 + inf) * 0 and, for a > 1e154, (a a) * 0 would be NaN).
+// Callers take what they need: an unused output is dead code to the compiler.
 template <int KIND>
-__device__ __forceinline__ void matern_entry(double s, double sf2, double& kf, double& dk)
+__device__ __forceinline__ void matern_entry(double s, double sf2, double& kf, double& dk, double& hh)
 {
 #pragma clang fp contract(off)
     static_assert(KIND == KERNEL_MATERN32 || KIND == KERNEL_MATERN52, "Matern kinds only");
@@ -974,45 +981,60 @@ __device__ __forceinline__ void matern_entry(double s, double sf2, double& kf, d
     const double a = c * __builtin_sqrt(s);
     const double e = exp(-a);
     const double p1 = 1.0 + a;
-    double p, q;
+    double p, q, g;
     if (KIND == KERNEL_MATERN32) {
         p = p1;
         q = a * a;
+        g = 3.0;
     } else {
         const double t = (a * a) * 0.3333333333333333;
         p = p1 + t;
         q = t * p1;
+        g = 1.6666666666666667 * p1;
     }
     const bool dead = e == 0.0;
     kf = dead ? 0.0 : sf2 * (p * e);
     dk = dead ? 0.0 : sf2 * (q * e);
+    hh = dead ? 0.0 : sf2 * (g * e);
 }
-// the value of one entry without the noise term (the three passes that need no derivative).  ARD: d2 is the WEIGHTED
-// squared distance, so there is no division and dl is not read -- SE exp(-d2 / 2), the Matern kinds matern_entry at
-// s = d2 (its roundings and its e == 0 guard)
+// ARD entry from the WEIGHTED squared distance s (no division, ell_sq is not read): kf and the factor H of the
+// per-dimension derivatives -- SE: kf = sf2 exp(-s / 2) and H = kf; the Matern kinds matern_entry at s
+template <int KIND>
+__device__ __forceinline__ void ard_entry(double s, double sf2, double& kf, double& hh)
+{
+    if constexpr (KIND == KERNEL_SE) {
+        kf = sf2 * exp(-0.5 * s);
+        hh = kf;
+    } else {
+        double dk;
+        matern_entry<KIND>(s, sf2, kf, dk, hh);
+    }
+}
+// the value of one entry without the noise term (the three passes that need no derivative)
 template <bool ARD, int KIND>
 __device__ __forceinline__ double kernel_value(double d2, const DivBy& dl, double sf2)
 {
-    if constexpr (ARD && KIND == KERNEL_SE) {
-        return sf2 * exp(-0.5 * d2);
-    } else if constexpr (ARD) {
-        double kf, dk;
-        matern_entry<KIND>(d2, sf2, kf, dk);
-        return kf;
-    } else if constexpr (KIND == KERNEL_SE) {
-        return sf2 * exp(div_by(-d2 * 0.5, dl));                  // covkernel.cpp:89
-    } else {
-        double kf, dk;
-        matern_entry<KIND>(div_by(d2, dl), sf2, kf, dk);
-        return kf;
-    }
+    double kf, dk, hh;
+    if constexpr (ARD)
+        ard_entry<KIND>(d2, sf2, kf, hh);
+    else if constexpr (KIND == KERNEL_SE)
+        kf = sf2 * exp(div_by(-d2 * 0.5, dl));                    // covkernel.cpp:89
+    else
+        matern_entry<KIND>(div_by(d2, dl), sf2, kf, dk, hh);
+    return kf;
 }
 
-// hd (when given): hyper-scalars resident in device memory -- a captured graph of the evaluation is replayed
-// with new hyper-parameters by refreshing that one buffer instead of every kernel's arguments
-// ARD (k_build_ard): per-dimension weights behind the hyper-scalars in device memory (hd is then always given, and
-// ell_sq is not read: K = sf2 exp(-acc / 2) of the weighted squared distance, no division); K only (full < 2)
-template <bool ARD, int KIND = KERNEL_SE>
+// The passes that evaluate the covariance function are ONE kernel template each, k_<pass><ARD, KIND>, with one argument
+// list: the hyper-scalars by value (h) and in device memory (hd).  Isotropic: hd is optional -- when given it is read
+// INSTEAD of h, so that a captured graph of the evaluation is replayed with new hyper-parameters by refreshing that one
+// buffer instead of every kernel's arguments (build and trace; the other passes take h).  ARD: hd is mandatory, h is
+// ignored, the d per-dimension weights lie behind the hyper-scalars and ell_sq is not read: K = sf2 exp(-acc / 2) (or the
+// Matern entry) of the weighted squared distance, no division.  cov_kernel (at the launchers) maps a CovFn to the instantiation.
+//
+// k_build: lower 64x64 tiles of K (+ mirror when full == 1); full == 2 (isotropic SE only): the squared-distance
+// intermediate of launch_sqdist.  Batched experts, ticket zeroing, device-resident hyper-scalars and stamps in every
+// instantiation.
+template <bool ARD, int KIND>
 __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, int d, int npad,
                                            HyperScalars h_arg, const HyperScalars* __restrict__ hd,
                                            double* __restrict__ K, int full, unsigned* __restrict__ tickets,
@@ -1029,7 +1051,7 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
     //  arrival counter of k_trace's fused finalize)
     if (tickets && blockIdx.x == 0)
         for (int i = threadIdx.x; i < ticket_count(npad / TILE); i += 256) tickets[i] = 0u;
-    const HyperScalars h = hd ? *hd : h_arg;
+    const HyperScalars h = (ARD || hd) ? *hd : h_arg;
     __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
     __shared__ double ws[DC];
     int ti, tj;
@@ -1071,46 +1093,18 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
     }
 }
 
+template <bool ARD, int KIND>
 __global__ __launch_bounds__(256) void k_build(const double* __restrict__ X, int n, int d, int npad,
                                                HyperScalars h_arg, const HyperScalars* __restrict__ hd,
                                                double* __restrict__ K, int full, unsigned* __restrict__ tickets,
                                                const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
 {
-    build_body<false>(X, n, d, npad, h_arg, hd, K, full, tickets, bt, stamp);
+    build_body<ARD, KIND>(X, n, d, npad, h_arg, hd, K, full, tickets, bt, stamp);
 }
 
-__global__ __launch_bounds__(256) void k_build_ard(const double* __restrict__ X, int n, int d, int npad,
-                                                   const HyperScalars* __restrict__ hd, double* __restrict__ K,
-                                                   int full, unsigned* __restrict__ tickets,
-                                                   const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
-{
-    build_body<true>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, bt, stamp);
-}
-
-// Matern instantiations: k_build's arguments and everything that rides with it (batched experts, ticket zeroing,
-// device-resident hyper-scalars, stamps); full < 2 (the squared-distance intermediate does not depend on the kind)
-template <int KIND>
-__global__ __launch_bounds__(256) void k_build_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                      HyperScalars h_arg, const HyperScalars* __restrict__ hd,
-                                                      double* __restrict__ K, int full, unsigned* __restrict__ tickets,
-                                                      const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
-{
-    build_body<false, KIND>(X, n, d, npad, h_arg, hd, K, full, tickets, bt, stamp);
-}
-
-// ARD x Matern (GPML covMaternard): k_build_ard's arguments, the Matern entry of the weighted distance
-template <int KIND>
-__global__ __launch_bounds__(256) void k_build_ard_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                          const HyperScalars* __restrict__ hd, double* __restrict__ K,
-                                                          int full, unsigned* __restrict__ tickets,
-                                                          const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
-{
-    build_body<true, KIND>(X, n, d, npad, HyperScalars{}, hd, K, full, tickets, bt, stamp);
-}
-
-// Ks[t][i] = sf2 * exp(-0.5 |xt_t - x_i|^2 / l^2) (no noise, covkernel.cpp:105-116); zero padding
+// k_cross: Ks[t][i] = k(xt_t, x_i) (no noise, covkernel.cpp:105-116); zero padding
 // bt (batched): blockIdx.y selects the expert -- X, n from its table entry, Ks = the expert's [ntpad][npad] slice
-template <bool ARD, int KIND = KERNEL_SE>
+template <bool ARD, int KIND>
 __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, int d, int npad,
                                            const double* __restrict__ Xt, int nt, int ntpad, const HyperScalars& h,
                                            const double* __restrict__ wts,
@@ -1145,36 +1139,13 @@ __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, 
     }
 }
 
+template <bool ARD, int KIND>
 __global__ __launch_bounds__(256) void k_cross(const double* __restrict__ X, int n, int d, int npad,
-                                               const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h,
-                                               double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
+                                               const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h_arg,
+                                               double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt,
+                                               const HyperScalars* __restrict__ hd)
 {
-    cross_body<false>(X, n, d, npad, Xt, nt, ntpad, h, nullptr, Ks, bt);
-}
-
-__global__ __launch_bounds__(256) void k_cross_ard(const double* __restrict__ X, int n, int d, int npad,
-                                                   const double* __restrict__ Xt, int nt, int ntpad,
-                                                   const HyperScalars* __restrict__ hd, double* __restrict__ Ks,
-                                                   const ExpertPtrs* __restrict__ bt)
-{
-    cross_body<true>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, bt);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_cross_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                      const double* __restrict__ Xt, int nt, int ntpad, HyperScalars h,
-                                                      double* __restrict__ Ks, const ExpertPtrs* __restrict__ bt)
-{
-    cross_body<false, KIND>(X, n, d, npad, Xt, nt, ntpad, h, nullptr, Ks, bt);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_cross_ard_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                          const double* __restrict__ Xt, int nt, int ntpad,
-                                                          const HyperScalars* __restrict__ hd, double* __restrict__ Ks,
-                                                          const ExpertPtrs* __restrict__ bt)
-{
-    cross_body<true, KIND>(X, n, d, npad, Xt, nt, ntpad, *hd, ard_weights(hd), Ks, bt);
+    cross_body<ARD, KIND>(X, n, d, npad, Xt, nt, ntpad, ARD ? *hd : h_arg, ARD ? ard_weights(hd) : nullptr, Ks, bt);
 }
 
 // ---- joint predictive covariance (cugp_predict_cov): Sigma = k(Xt,Xt) (+ sn2 I) - W W^T, W = Ks L^-T ----
@@ -1207,7 +1178,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_cov(const double* __restrict
 // diagonal) - (P_0 + P_1 + ...), in place over P_0; kss = sf2 exp(-|xt_i - xt_j|^2 / (2 l^2)) by k_build's formula and
 // squared-distance order; padding rows / columns >= nt become identity.  tickets (when given): the factorisation's
 // arrival counters, zeroed as k_build does.
-template <bool ARD, int KIND = KERNEL_SE>
+template <bool ARD, int KIND>
 __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict__ Xt, int nt, int d, int ntpad,
                                                         const HyperScalars& h, const double* __restrict__ wts,
                                                         int with_noise, double jitter,
@@ -1253,45 +1224,15 @@ __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict
     }
 }
 
+template <bool ARD, int KIND>
 __global__ __launch_bounds__(256) void k_predict_cov_finish(const double* __restrict__ Xt, int nt, int d, int ntpad,
-                                                            HyperScalars h, int with_noise, double jitter,
+                                                            HyperScalars h_arg, int with_noise, double jitter,
                                                             double* __restrict__ A, const double* __restrict__ scr,
-                                                            size_t pstride, int nscr, unsigned* __restrict__ tickets)
+                                                            size_t pstride, int nscr, unsigned* __restrict__ tickets,
+                                                            const HyperScalars* __restrict__ hd)
 {
-    predict_cov_finish_body<false>(Xt, nt, d, ntpad, h, nullptr, with_noise, jitter, A, scr, pstride, nscr, tickets);
-}
-
-__global__ __launch_bounds__(256) void k_predict_cov_finish_ard(const double* __restrict__ Xt, int nt, int d, int ntpad,
-                                                                const HyperScalars* __restrict__ hd, int with_noise,
-                                                                double jitter, double* __restrict__ A,
-                                                                const double* __restrict__ scr, size_t pstride,
-                                                                int nscr, unsigned* __restrict__ tickets)
-{
-    predict_cov_finish_body<true>(Xt, nt, d, ntpad, *hd, ard_weights(hd), with_noise, jitter, A, scr, pstride, nscr,
-                                  tickets);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_predict_cov_finish_matern(const double* __restrict__ Xt, int nt, int d,
-                                                                   int ntpad, HyperScalars h, int with_noise,
-                                                                   double jitter, double* __restrict__ A,
-                                                                   const double* __restrict__ scr, size_t pstride,
-                                                                   int nscr, unsigned* __restrict__ tickets)
-{
-    predict_cov_finish_body<false, KIND>(Xt, nt, d, ntpad, h, nullptr, with_noise, jitter, A, scr, pstride, nscr,
-                                         tickets);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_predict_cov_finish_ard_matern(const double* __restrict__ Xt, int nt, int d,
-                                                                       int ntpad, const HyperScalars* __restrict__ hd,
-                                                                       int with_noise, double jitter,
-                                                                       double* __restrict__ A,
-                                                                       const double* __restrict__ scr, size_t pstride,
-                                                                       int nscr, unsigned* __restrict__ tickets)
-{
-    predict_cov_finish_body<true, KIND>(Xt, nt, d, ntpad, *hd, ard_weights(hd), with_noise, jitter, A, scr, pstride,
-                                        nscr, tickets);
+    predict_cov_finish_body<ARD, KIND>(Xt, nt, d, ntpad, ARD ? *hd : h_arg, ARD ? ard_weights(hd) : nullptr, with_noise,
+                                       jitter, A, scr, pstride, nscr, tickets);
 }
 
 // The Cholesky writes the lower triangle only: the strict upper part of every 128x128 diagonal tile still holds Sigma,
@@ -2490,6 +2431,41 @@ __device__ __forceinline__ void finalize_sums(const double* __restrict__ z, int 
     }
 }
 
+// Multi-target regression (the section further down): S[a][b] = sum_t A[t][i0 + 4 ty + a] A[t][j0 + col4(tx, b)] of the thread's 4x4 micro-tile, t ascending, no contraction.
+// The two 64-entry runs of A per target (contiguous, 512 B each) go through LDS, TGT_CHUNK targets at a time.
+constexpr int TGT_CHUNK = 16;
+__device__ __forceinline__ void targets_outer_4x4(const double* __restrict__ A, int ld, int m, int i0, int j0,
+                                                  double (&la)[TGT_CHUNK][KT], double (&lb)[TGT_CHUNK][KT],
+                                                  double (&S)[4][4])
+{
+#pragma clang fp contract(off)
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) S[a][b] = 0.0;
+    for (int t0 = 0; t0 < m; t0 += TGT_CHUNK) {
+        const int tc = (m - t0 < TGT_CHUNK) ? (m - t0) : TGT_CHUNK;
+        __syncthreads();
+        for (int e = t; e < tc * 64; e += 256) {              // 16-byte pieces: 32 of the row run, 32 of the column run
+            const int r = e >> 6, q = e & 63;
+            const double* row = A + (size_t)(t0 + r) * ld;
+            if (q < 32) *(d2*)&la[r][2 * q] = *(const d2*)(row + i0 + 2 * q);
+            else *(d2*)&lb[r][2 * (q - 32)] = *(const d2*)(row + j0 + 2 * (q - 32));
+        }
+        __syncthreads();
+        for (int r = 0; r < tc; r++) {
+            const d2 a01 = *(const d2*)&la[r][ty * 4], a23 = *(const d2*)&la[r][ty * 4 + 2];
+            const d2 b01 = *(const d2*)&lb[r][tx * 2], b23 = *(const d2*)&lb[r][32 + tx * 2];
+            const double ai[4] = {a01[0], a01[1], a23[0], a23[1]}, aj[4] = {b01[0], b01[1], b23[0], b23[1]};
+#pragma unroll
+            for (int a = 0; a < 4; a++)
+#pragma unroll
+                for (int b = 0; b < 4; b++) S[a][b] = S[a][b] + ai[a] * aj[b];
+        }
+    }
+}
+
 // what the last block of k_trace needs to finish the evaluation (out == nullptr: no fused finalize)
 struct FinalizeArgs {
     const double* z; const double* logdet_part; int nt; double* out; double* hout; unsigned* ticket;
@@ -2499,16 +2475,20 @@ struct FinalizeArgs {
 // W = K^-1 - alpha alpha^T, accumulate  s1 = sum W*K*S, s2 = sum W*K, s3 = sum_i W_ii  (off-diagonal tiles x2)
 // KIND: s1 is sum W o dK/dlog l -- SE's K o S, or a Matern kind's dk of matern_entry (one exp(-a) for k and dk; zero on
 // the diagonal, where a = 0); s2, s3 and everything behind the sums keep their meaning
-template <int KIND>
+// TARGETS (multi-target regression, k_trace_targets): the same tile, thread layout, entry formulas, doubling of the
+// off-diagonal entries, diagonal handling and partial sums (part[3 * block + c]) with W = m K^-1 - sum_t alpha_t alpha_t^T
+// from the target-major AV ([m][npad]) in place of K^-1 - alpha alpha^T.  K^-1 is read once whatever m is; no N x N
+// intermediate is written.  Single handle, h by value, always the separate final sums (bt, hd and fin.out null).
+template <int KIND, bool TARGETS>
 __device__ __forceinline__ void trace_body(const double* __restrict__ X, int n, int d, int npad,
                                            HyperScalars h_arg, const HyperScalars* __restrict__ hd,
-                                           const double* __restrict__ Kinv, const double* __restrict__ alpha,
+                                           const double* __restrict__ Kinv, const double* __restrict__ AV, int m,
                                            double* __restrict__ part, const ExpertPtrs* __restrict__ bt,
                                            FinalizeArgs fin)
 {
-    if (bt) {
+    if (!TARGETS && bt) {
         const ExpertPtrs& e = bt[blockIdx.y];
-        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); alpha = GP(e.alpha); part = GP(e.part);
+        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); AV = GP(e.alpha); part = GP(e.part);
         if (fin.out) {
             fin.z = GP(e.z); fin.logdet_part = GP(e.logdet); fin.out = GP(e.out); fin.ticket = GP(e.tickets) + 2 * fin.nt;
             if (fin.hout) fin.hout += (size_t)blockIdx.y * 8;
@@ -2525,17 +2505,24 @@ __device__ __forceinline__ void trace_body(const double* __restrict__ X, int n, 
     tri_index(blockIdx.x, ti, tj);
     const int i0 = ti * KT, j0 = tj * KT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    double d2v[4][4];
+    double d2v[4][4], S[4][4];
     sqdist_4x4(X, X, n, n, d, i0, j0, xs, ys, d2v);
+    if constexpr (TARGETS) {
+        __shared__ __attribute__((aligned(16))) double la[TGT_CHUNK][KT], lb[TGT_CHUNK][KT];
+        targets_outer_4x4(AV, npad, m, i0, j0, la, lb, S);
+    }
     double s1 = 0.0, s2 = 0.0, s3 = 0.0;
     const DivBy dl = div_prepare(h.ell_sq);
+    const double dm = (double)m;
     double aj[4];
+    if constexpr (!TARGETS) {
 #pragma unroll
-    for (int b = 0; b < 4; b++) aj[b] = alpha[j0 + col4(tx, b)];
+        for (int b = 0; b < 4; b++) aj[b] = AV[j0 + col4(tx, b)];
+    }
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const int i = i0 + ty * 4 + a;
-        const double ai = alpha[i];
+        const double ai = TARGETS ? 0.0 : AV[i];
         const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
         d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
         const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
@@ -2543,7 +2530,9 @@ __device__ __forceinline__ void trace_body(const double* __restrict__ X, int n, 
         for (int b = 0; b < 4; b++) {
             const int j = j0 + col4(tx, b);
             if (i < n && j < n && (ti != tj || j <= i)) {
-                const double w = kv[b] - ai * aj[b];
+                double w;
+                if constexpr (TARGETS) w = dm * kv[b] - S[a][b];
+                else w = kv[b] - ai * aj[b];
                 if constexpr (KIND == KERNEL_SE) {
                     double kse = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
                     const double sd = div_by(d2v[a][b], dl);
@@ -2557,8 +2546,8 @@ __device__ __forceinline__ void trace_body(const double* __restrict__ X, int n, 
                         s2 += 2.0 * (w * kse);
                     }
                 } else {
-                    double kf, dk;
-                    matern_entry<KIND>(div_by(d2v[a][b], dl), h.signal_var, kf, dk);
+                    double kf, dk, hh;
+                    matern_entry<KIND>(div_by(d2v[a][b], dl), h.signal_var, kf, dk, hh);
                     if (i == j) {
                         kf += h.noise_var;
                         s1 += w * dk;
@@ -2597,25 +2586,6 @@ __device__ __forceinline__ void trace_body(const double* __restrict__ X, int n, 
     finalize_sums<256, true>(fin.z, npad, n, fin.logdet_part, fin.nt, part, (int)gridDim.x, h, fin.out, fin.hout, lds);
 }
 
-__global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int n, int d, int npad,
-                                               HyperScalars h_arg, const HyperScalars* __restrict__ hd,
-                                               const double* __restrict__ Kinv, const double* __restrict__ alpha,
-                                               double* __restrict__ part, const ExpertPtrs* __restrict__ bt,
-                                               FinalizeArgs fin)
-{
-    trace_body<KERNEL_SE>(X, n, d, npad, h_arg, hd, Kinv, alpha, part, bt, fin);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_trace_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                      HyperScalars h_arg, const HyperScalars* __restrict__ hd,
-                                                      const double* __restrict__ Kinv,
-                                                      const double* __restrict__ alpha, double* __restrict__ part,
-                                                      const ExpertPtrs* __restrict__ bt, FinalizeArgs fin)
-{
-    trace_body<KIND>(X, n, d, npad, h_arg, hd, Kinv, alpha, part, bt, fin);
-}
-
 // single workgroup: deterministic final sums and the scalar formulas
 //   LL = -0.5 (z'z + 2 sum log L_ii + n * 1.83787)                     covkernel.cpp:127
 //   g0 = s1/2, g1 = (2 s2 - 2 sn2 s3)/2, g2 = (2 sn2 s3)/2              covkernel.cpp:244-261
@@ -2639,29 +2609,36 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize(const double* __restri
     finalize_sums<FIN_THREADS, false>(z, npad, n, logdet_part, nt, part, nblocks, h, out, hout, red);
 }
 
-// ---- ARD (one length scale per input dimension; GPML covSEard's convention; no reference counterpart) ----
-// Gradient pass: g_c = 1/2 sum_ij W_ij Kf_ij ((x_ic - x_jc) w_c)^2 for every dimension c, beside the two sums k_trace takes
-// (sum W o K and tr W).  Per lower 64x64 tile: (1) the weighted squared distances over all feature chunks, K^-1 read
-// once, and the thread's 4x4 entries of W o K kept in registers (off-diagonal tiles doubled, entries outside the lower
-// triangle or the data zero); (2) a second sweep over the feature chunks, the X tiles staged again, DC per-dimension
-// sums at a time in registers; wave sums by shuffles, the four waves added in a fixed order.
+// ---- ARD (one length scale per input dimension; GPML covSEard / covMaternard; no reference counterpart) ----
+// Gradient pass, ONE body for SE and both Matern kinds: g_c = 1/2 sum_ij W_ij H_ij ((x_ic - x_jc) w_c)^2 for every
+// dimension c (ard_entry's H: SE's Kf itself), beside the two sums k_trace takes (sum W o K and tr W).  Per lower 64x64
+// tile: (1) the weighted squared distances over all feature chunks, K^-1 read once, and the thread's 4x4 entries 2 (w H)
+// kept in registers (off-diagonal tiles doubled, entries outside the lower triangle or the data zero; the diagonal's
+// differences are zero: it has no share in any g_c); sum W o K takes Kf (+ sn2 on the diagonal); (2) a second sweep over
+// the feature chunks, the X tiles staged again, DC per-dimension sums at a time in registers; wave sums by shuffles, the
+// four waves added in a fixed order.
 // Partials: part[c * nblocks + block], c = 0 .. d - 1 the dimensions, d: sum W o K, d + 1: tr W (column-major, so that
-// k_finalize_ard's lanes read a column contiguously).  No fused final sums: k_finalize_ard always follows.
-// bt (batched): blockIdx.y selects the expert -- X, n, K^-1, alpha and the expert's OWN partials from its table entry;
-// hyper-scalars and weights are the group's one copy (hd).  The arithmetic and its order per expert are the single launch's.
-__global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X, int n, int d, int npad,
-                                                   const HyperScalars* __restrict__ hd,
-                                                   const double* __restrict__ Kinv, const double* __restrict__ alpha,
-                                                   double* __restrict__ part, const ExpertPtrs* __restrict__ bt)
+// k_finalize_ard's lanes read a column contiguously).  No fused final sums: k_finalize_ard / k_finalize_targets follow.
+// TARGETS: W = m K^-1 - sum_t alpha_t alpha_t^T from the target-major AV ([m][npad]), single handle; else W = K^-1 -
+// alpha alpha^T from the vector AV, and bt (batched): blockIdx.y selects the expert -- X, n, K^-1, alpha and the
+// expert's OWN partials from its table entry; hyper-scalars and weights are the group's one copy (hd).  The arithmetic
+// and its order per expert are the single launch's.
+template <int KIND, bool TARGETS>
+__device__ __forceinline__ void trace_ard_body(const double* __restrict__ X, int n, int d, int npad,
+                                               const HyperScalars* __restrict__ hd,
+                                               const double* __restrict__ Kinv, const double* __restrict__ AV,
+                                               int m, double* __restrict__ part,
+                                               const ExpertPtrs* __restrict__ bt)
 {
 #pragma clang fp contract(off)
-    if (bt) {
+    if (!TARGETS && bt) {
         const ExpertPtrs& e = bt[blockIdx.y];
-        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); alpha = GP(e.alpha); part = GP(e.part);
+        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); AV = GP(e.alpha); part = GP(e.part);
     }
     const HyperScalars h = *hd;
     const double* __restrict__ wts = ard_weights(hd);
     __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
+    __shared__ __attribute__((aligned(16))) double la[TARGETS ? TGT_CHUNK : 1][KT], lb[TARGETS ? TGT_CHUNK : 1][KT];
     __shared__ double ws[DC];
     __shared__ double red[DC][4];
     int ti, tj;
@@ -2669,16 +2646,21 @@ __global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X,
     const int i0 = ti * KT, j0 = tj * KT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const size_t nblocks = gridDim.x;
-    double wk[4][4];
+    double wk[4][4], S[4][4];
     sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, wk, wts, ws);
-    double s2 = 0.0, s3 = 0.0;
     double aj[4];
+    if constexpr (TARGETS) {
+        targets_outer_4x4(AV, npad, m, i0, j0, la, lb, S);
+    } else {
 #pragma unroll
-    for (int b = 0; b < 4; b++) aj[b] = alpha[j0 + col4(tx, b)];
+        for (int b = 0; b < 4; b++) aj[b] = AV[j0 + col4(tx, b)];
+    }
+    double s2 = 0.0, s3 = 0.0;
+    const double dm = (double)m;
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const int i = i0 + ty * 4 + a;
-        const double ai = alpha[i];
+        const double ai = TARGETS ? 0.0 : AV[i];
         const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
         d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
         const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
@@ -2687,15 +2669,16 @@ __global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X,
             const int j = j0 + col4(tx, b);
             double e = 0.0;
             if (i < n && j < n && (ti != tj || j <= i)) {
-                const double w = kv[b] - ai * aj[b];
-                double kse = h.signal_var * exp(-0.5 * wk[a][b]);
+                const double w = TARGETS ? dm * kv[b] - S[a][b] : kv[b] - ai * aj[b];
+                double kf, hh;
+                ard_entry<KIND>(wk[a][b], h.signal_var, kf, hh);
                 if (i == j) {
-                    kse += h.noise_var;
-                    s2 += w * kse;
+                    kf += h.noise_var;
+                    s2 += w * kf;
                     s3 += w;
                 } else {
-                    e = 2.0 * (w * kse);     // (the diagonal's differences are zero: it has no share in any g_c)
-                    s2 += e;
+                    e = 2.0 * (w * hh);
+                    s2 += 2.0 * (w * kf);
                 }
             }
             wk[a][b] = e;
@@ -2742,6 +2725,30 @@ __global__ __launch_bounds__(256) void k_trace_ard(const double* __restrict__ X,
         __syncthreads();
         if (t < dc) part[(size_t)(c0 + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
     }
+}
+
+
+// k_trace: the gradient pass of a single-target evaluation.  ARD: always followed by k_finalize_ard (fin is not read).
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int n, int d, int npad,
+                                               HyperScalars h_arg, const HyperScalars* __restrict__ hd,
+                                               const double* __restrict__ Kinv, const double* __restrict__ alpha,
+                                               double* __restrict__ part, const ExpertPtrs* __restrict__ bt,
+                                               FinalizeArgs fin)
+{
+    if constexpr (ARD) trace_ard_body<KIND, false>(X, n, d, npad, hd, Kinv, alpha, 1, part, bt);
+    else trace_body<KIND, false>(X, n, d, npad, h_arg, hd, Kinv, alpha, 1, part, bt, fin);
+}
+
+// k_trace_targets: the same for the summed objective of m targets (A: [m][npad], row t = alpha_t); k_finalize_targets follows
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_trace_targets(const double* __restrict__ X, int n, int d, int npad,
+                                                       HyperScalars h, const double* __restrict__ Kinv,
+                                                       const double* __restrict__ A, int m, double* __restrict__ part,
+                                                       const HyperScalars* __restrict__ hd)
+{
+    if constexpr (ARD) trace_ard_body<KIND, true>(X, n, d, npad, hd, Kinv, A, m, part, nullptr);
+    else trace_body<KIND, true>(X, n, d, npad, h, nullptr, Kinv, A, m, part, nullptr, FinalizeArgs{});
 }
 
 // Final sums of an ARD gradient evaluation, one workgroup.  LL, y'K^-1y and log|K| by finalize_sums (the isotropic
@@ -2833,10 +2840,11 @@ __global__ __launch_bounds__(256) void k_predict_finish(const double* __restrict
 // k_i = k(x*, x_i), dk_i / dx*_c = -G_i (x*_c - x_ic) s_c  (G: SE and ARD k_i, Matern 3/2 sf2 3 e^-a, 5/2 sf2 (5/3)(1 + a) e^-a;
 // s_c = 1 / l^2, ARD w_c^2), v = K^-1 k* = row t of V = W L^-1:
 //   dmean[t][c] = -s_c sum_i (G alpha_i) (x*_c - x_ic),     dvar[t][c] = +2 s_c sum_i (G V_ti) (x*_c - x_ic)
-// One 64 x 64 (test x training) tile per workgroup, the thread's 4 x 4 micro-tile and column pairs as cross_body's (16-byte
-// loads of Ks and V rows).  SE and ARD read G from Ks (k_cross's own exp, no second one: the ARD weights enter through the
-// finish alone, so one instantiation serves both); the Matern kinds accumulate the squared distance as sqdist_4x4 does
-// (difference, square, add, in feature order, no contraction) and take one exp(-a) per entry.  Per feature, X and Xt staged
+// One 64 x 64 (test x training) tile per workgroup, the thread's 4 x 4 micro-tile and column pairs as k_cross's (16-byte
+// loads of Ks and V rows).  SE, and SE with ARD, read G from Ks (k_cross's own exp, no second one: the ARD weights enter
+// through the finish alone, so the two instantiations are the same code); the Matern kinds take the squared distance --
+// ARD: the weighted one -- from sqdist_4x4<ARD> and G = H of matern_entry, one exp(-a) per entry.  The second sweep takes
+// the UNWEIGHTED differences (k_predict_grad_finish applies s_c once per output).  Per feature, X and Xt staged
 // through LDS DC features at a time: the DIFFERENCE x*_c - x_ic is formed first and then multiplied -- the algebraically
 // equal x*_c sum(G alpha) - sum(G alpha x_c) cancels where |x| >> |x - x'|.  A thread adds its four columns in index order,
 // the 16 lanes of a row add by a butterfly of fixed shape (lane distances 1, 2, 4, 8; a + b == b + a, so all 16 hold the same
@@ -2846,12 +2854,12 @@ __global__ __launch_bounds__(256) void k_predict_finish(const double* __restrict
 // X or Xt; Ks and V are [.. >= 64 * tiles][npad] and read inside that.
 // k_predict_grad_finish adds the tiles' partial sums in tile order and applies -s_c and +2 s_c once per output.
 // ------------------------------------------------------------------------------------------
-template <int KIND>
+template <bool ARD, int KIND>
 __device__ __forceinline__ void predict_grad_body(const double* __restrict__ X, int n, int d, int npad,
-                                                  const double* __restrict__ Xt, int nt, HyperScalars h,
+                                                  const double* __restrict__ Xt, int nt, HyperScalars h_arg,
                                                   const double* __restrict__ Ks, const double* __restrict__ V,
                                                   const double* __restrict__ alpha, double* __restrict__ part,
-                                                  size_t pstride)
+                                                  size_t pstride, const HyperScalars* __restrict__ hd)
 {
 #pragma clang fp contract(off)
     __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
@@ -2859,49 +2867,19 @@ __device__ __forceinline__ void predict_grad_body(const double* __restrict__ X, 
     const int tt = blockIdx.x / tiles_i, ti = blockIdx.x % tiles_i;
     const int t0 = tt * KT, i0 = ti * KT;
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    // one chunk of features of the tile's test rows (xs) and training rows (ys) into LDS, zeros beyond nt and n
-    auto stage = [&](int c0, int dc) {
-        __syncthreads();
-        for (int e = t; e < KT * dc; e += 256) {
-            const int r = e / dc, c = e - r * dc;
-            xs[r][c] = (t0 + r < nt) ? Xt[(size_t)(t0 + r) * d + c0 + c] : 0.0;
-            ys[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
-        }
-        __syncthreads();
-    };
     double G[4][4];
-    if constexpr (KIND != KERNEL_SE) {
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int b = 0; b < 4; b++) G[a][b] = 0.0;
-        for (int c0 = 0; c0 < d; c0 += DC) {
-            const int dc = (d - c0 < DC) ? (d - c0) : DC;
-            stage(c0, dc);
-            for (int c = 0; c < dc; c++) {
-                double xv[4], yv[4];
-#pragma unroll
-                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const double df = xv[a] - yv[b];
-                        G[a][b] = G[a][b] + df * df;
-                    }
-            }
-        }
+    if constexpr (KIND != KERNEL_SE) {                 // (SE reads G from Ks below: h and hd are not read)
+        __shared__ double ws[DC];
+        const HyperScalars& h = ARD ? *hd : h_arg;
+        sqdist_4x4<ARD>(Xt, X, nt, n, d, t0, i0, xs, ys, G, ARD ? ard_weights(hd) : nullptr, ws);
         const DivBy dl = div_prepare(h.ell_sq);
-        const double cc = KIND == KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979;
 #pragma unroll
         for (int a = 0; a < 4; a++)
 #pragma unroll
             for (int b = 0; b < 4; b++) {
-                const double av = cc * __builtin_sqrt(div_by(G[a][b], dl));
-                const double e = exp(-av);
-                // (e == 0: a = +inf or an exp that underflowed -- G is 0 exactly, never inf * 0)
-                const double p = KIND == KERNEL_MATERN32 ? 3.0 : 1.6666666666666667 * (1.0 + av);
-                G[a][b] = e == 0.0 ? 0.0 : h.signal_var * (p * e);
+                double kf, dk, hh;
+                matern_entry<KIND>(ARD ? G[a][b] : div_by(G[a][b], dl), h.signal_var, kf, dk, hh);
+                G[a][b] = hh;
             }
     }
     double ga[4][4], gv[4][4];
@@ -2931,6 +2909,16 @@ __device__ __forceinline__ void predict_grad_body(const double* __restrict__ X, 
             gv[a][b] = in ? G[a][b] * vv[b] : 0.0;
         }
     }
+    // one chunk of features of the tile's test rows (xs) and training rows (ys) into LDS, zeros beyond nt and n
+    auto stage = [&](int c0, int dc) {
+        __syncthreads();
+        for (int e = t; e < KT * dc; e += 256) {
+            const int r = e / dc, c = e - r * dc;
+            xs[r][c] = (t0 + r < nt) ? Xt[(size_t)(t0 + r) * d + c0 + c] : 0.0;
+            ys[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
+        }
+        __syncthreads();
+    };
     double* pm_out = part + (size_t)ti * 2 * pstride;
     double* pv_out = pm_out + pstride;
     for (int c0 = 0; c0 < d; c0 += DC) {
@@ -2971,24 +2959,14 @@ __device__ __forceinline__ void predict_grad_body(const double* __restrict__ X, 
     }
 }
 
-// SE and ARD: G is the cross-covariance entry itself (h is not read)
+template <bool ARD, int KIND>
 __global__ __launch_bounds__(256) void k_predict_grad(const double* __restrict__ X, int n, int d, int npad,
-                                                      const double* __restrict__ Xt, int nt, HyperScalars h,
+                                                      const double* __restrict__ Xt, int nt, HyperScalars h_arg,
                                                       const double* __restrict__ Ks, const double* __restrict__ V,
                                                       const double* __restrict__ alpha, double* __restrict__ part,
-                                                      size_t pstride)
+                                                      size_t pstride, const HyperScalars* __restrict__ hd)
 {
-    predict_grad_body<KERNEL_SE>(X, n, d, npad, Xt, nt, h, Ks, V, alpha, part, pstride);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_predict_grad_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                             const double* __restrict__ Xt, int nt, HyperScalars h,
-                                                             const double* __restrict__ Ks, const double* __restrict__ V,
-                                                             const double* __restrict__ alpha, double* __restrict__ part,
-                                                             size_t pstride)
-{
-    predict_grad_body<KIND>(X, n, d, npad, Xt, nt, h, Ks, V, alpha, part, pstride);
+    predict_grad_body<ARD, KIND>(X, n, d, npad, Xt, nt, h_arg, Ks, V, alpha, part, pstride, hd);
 }
 
 // dmean[t][c] = -s_c (P_0 + P_1 + ...), dvar[t][c] = (2 s_c) (Q_0 + Q_1 + ...): the tiles' partial sums in tile order, packed
@@ -3081,7 +3059,7 @@ __global__ __launch_bounds__(256) void k_poe_reduce_mode(const double* __restric
 // Multi-target regression: m target vectors over the handle's one factorisation (cugp_set_targets).  Everything is
 // target-major, [mpad][npad] with zeros beyond n and beyond m: Y the targets, Z = Y L^-T (k_predict_gemm as it stands),
 // A = Z L^-1 (row t = alpha_t, k_targets_alpha), then ONE pass over K^-1 for the gradient of the summed objective
-// (k_trace_targets / k_trace_targets_ard), the final sums (k_finalize_targets) and the means A Ks^T (k_targets_mean).
+// (k_trace_targets), the final sums (k_finalize_targets) and the means A Ks^T (k_targets_mean).
 // The kernels have bodies of their own: the single-target kernels above keep their instructions.
 // ------------------------------------------------------------------------------------------
 
@@ -3134,199 +3112,6 @@ __global__ __launch_bounds__(256) void k_targets_mean_finish(const double* __res
     double s = p[0];
     for (int c = 1; c < split; c++) s = s + p[(size_t)c * pstride];
     mean[e] = s;
-}
-
-// S[a][b] = sum_t A[t][i0 + 4 ty + a] A[t][j0 + col4(tx, b)] of the thread's 4x4 micro-tile, t ascending, no contraction.
-// The two 64-entry runs of A per target (contiguous, 512 B each) go through LDS, TGT_CHUNK targets at a time.
-constexpr int TGT_CHUNK = 16;
-__device__ __forceinline__ void targets_outer_4x4(const double* __restrict__ A, int ld, int m, int i0, int j0,
-                                                  double (&la)[TGT_CHUNK][KT], double (&lb)[TGT_CHUNK][KT],
-                                                  double (&S)[4][4])
-{
-#pragma clang fp contract(off)
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) S[a][b] = 0.0;
-    for (int t0 = 0; t0 < m; t0 += TGT_CHUNK) {
-        const int tc = (m - t0 < TGT_CHUNK) ? (m - t0) : TGT_CHUNK;
-        __syncthreads();
-        for (int e = t; e < tc * 64; e += 256) {              // 16-byte pieces: 32 of the row run, 32 of the column run
-            const int r = e >> 6, q = e & 63;
-            const double* row = A + (size_t)(t0 + r) * ld;
-            if (q < 32) *(d2*)&la[r][2 * q] = *(const d2*)(row + i0 + 2 * q);
-            else *(d2*)&lb[r][2 * (q - 32)] = *(const d2*)(row + j0 + 2 * (q - 32));
-        }
-        __syncthreads();
-        for (int r = 0; r < tc; r++) {
-            const d2 a01 = *(const d2*)&la[r][ty * 4], a23 = *(const d2*)&la[r][ty * 4 + 2];
-            const d2 b01 = *(const d2*)&lb[r][tx * 2], b23 = *(const d2*)&lb[r][32 + tx * 2];
-            const double ai[4] = {a01[0], a01[1], a23[0], a23[1]}, aj[4] = {b01[0], b01[1], b23[0], b23[1]};
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) S[a][b] = S[a][b] + ai[a] * aj[b];
-        }
-    }
-}
-
-// Gradient pass of the summed objective, isotropic families: k_trace's tile, thread layout, entry formulas, doubling of
-// the off-diagonal entries, diagonal handling and partial sums (part[3 * block + c]) with
-//   W = m K^-1 - sum_t alpha_t alpha_t^T
-// in place of K^-1 - alpha alpha^T.  K^-1 is read once whatever m is; no N x N intermediate is written.
-template <int KIND>
-__global__ __launch_bounds__(256) void k_trace_targets(const double* __restrict__ X, int n, int d, int npad,
-                                                       HyperScalars h, const double* __restrict__ Kinv,
-                                                       const double* __restrict__ A, int m, double* __restrict__ part)
-{
-    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
-    __shared__ __attribute__((aligned(16))) double la[TGT_CHUNK][KT], lb[TGT_CHUNK][KT];
-    __shared__ double red[3][4];
-    int ti, tj;
-    tri_index(blockIdx.x, ti, tj);
-    const int i0 = ti * KT, j0 = tj * KT;
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    double d2v[4][4], S[4][4];
-    sqdist_4x4(X, X, n, n, d, i0, j0, xs, ys, d2v);
-    targets_outer_4x4(A, npad, m, i0, j0, la, lb, S);
-    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    const DivBy dl = div_prepare(h.ell_sq);
-    const double dm = (double)m;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        const int i = i0 + ty * 4 + a;
-        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
-        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
-        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int j = j0 + col4(tx, b);
-            if (i < n && j < n && (ti != tj || j <= i)) {
-                const double w = dm * kv[b] - S[a][b];
-                if constexpr (KIND == KERNEL_SE) {
-                    double kse = h.signal_var * exp(div_by(-d2v[a][b] * 0.5, dl));
-                    const double sd = div_by(d2v[a][b], dl);
-                    if (i == j) {
-                        kse += h.noise_var;
-                        s1 += w * (kse * sd);
-                        s2 += w * kse;
-                        s3 += w;
-                    } else {
-                        s1 += 2.0 * (w * (kse * sd));
-                        s2 += 2.0 * (w * kse);
-                    }
-                } else {
-                    double kf, dk;
-                    matern_entry<KIND>(div_by(d2v[a][b], dl), h.signal_var, kf, dk);
-                    if (i == j) {
-                        kf += h.noise_var;
-                        s1 += w * dk;
-                        s2 += w * kf;
-                        s3 += w;
-                    } else {
-                        s1 += 2.0 * (w * dk);
-                        s2 += 2.0 * (w * kf);
-                    }
-                }
-            }
-        }
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2); s3 = wave_sum(s3);
-    if ((t & 63) == 0) { red[0][t >> 6] = s1; red[1][t >> 6] = s2; red[2][t >> 6] = s3; }
-    __syncthreads();
-    if (t < 3) part[(size_t)blockIdx.x * 3 + t] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-}
-
-// The same for ARD: k_trace_ard's two sweeps and partial layout (part[c * nblocks + block]) with the summed W.
-__global__ __launch_bounds__(256) void k_trace_targets_ard(const double* __restrict__ X, int n, int d, int npad,
-                                                           const HyperScalars* __restrict__ hd,
-                                                           const double* __restrict__ Kinv, const double* __restrict__ A,
-                                                           int m, double* __restrict__ part)
-{
-#pragma clang fp contract(off)
-    const HyperScalars h = *hd;
-    const double* __restrict__ wts = ard_weights(hd);
-    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
-    __shared__ __attribute__((aligned(16))) double la[TGT_CHUNK][KT], lb[TGT_CHUNK][KT];
-    __shared__ double ws[DC];
-    __shared__ double red[DC][4];
-    int ti, tj;
-    tri_index(blockIdx.x, ti, tj);
-    const int i0 = ti * KT, j0 = tj * KT;
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const size_t nblocks = gridDim.x;
-    double wk[4][4], S[4][4];
-    sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, wk, wts, ws);
-    targets_outer_4x4(A, npad, m, i0, j0, la, lb, S);
-    double s2 = 0.0, s3 = 0.0;
-    const double dm = (double)m;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        const int i = i0 + ty * 4 + a;
-        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
-        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
-        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int j = j0 + col4(tx, b);
-            double e = 0.0;
-            if (i < n && j < n && (ti != tj || j <= i)) {
-                const double w = dm * kv[b] - S[a][b];
-                double kse = h.signal_var * exp(-0.5 * wk[a][b]);
-                if (i == j) {
-                    kse += h.noise_var;
-                    s2 += w * kse;
-                    s3 += w;
-                } else {
-                    e = 2.0 * (w * kse);     // (the diagonal's differences are zero: it has no share in any g_c)
-                    s2 += e;
-                }
-            }
-            wk[a][b] = e;
-        }
-    }
-    s2 = wave_sum(s2); s3 = wave_sum(s3);
-    if ((t & 63) == 0) { red[0][t >> 6] = s2; red[1][t >> 6] = s3; }
-    __syncthreads();
-    if (t < 2) part[(size_t)(d + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-    for (int c0 = 0; c0 < d; c0 += DC) {
-        const int dc = (d - c0 < DC) ? (d - c0) : DC;
-        __syncthreads();
-        for (int e = t; e < KT * dc; e += 256) {
-            int r = e / dc, c = e - r * dc;
-            xs[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
-            ys[r][c] = (j0 + r < n) ? X[(size_t)(j0 + r) * d + c0 + c] : 0.0;
-        }
-        if (t < dc) ws[t] = wts[c0 + t];
-        __syncthreads();
-        double gs[DC];
-#pragma unroll
-        for (int c = 0; c < DC; c++) {
-            gs[c] = 0.0;
-            if (c < dc) {
-                double xv[4], yv[4];
-#pragma unroll
-                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
-                const double wc = ws[c];
-                double acc = 0.0;
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const double df = (xv[a] - yv[b]) * wc;
-                        acc = acc + wk[a][b] * (df * df);
-                    }
-                gs[c] = wave_sum(acc);
-            }
-        }
-        if ((t & 63) == 0) {
-#pragma unroll
-            for (int c = 0; c < DC; c++) red[c][t >> 6] = gs[c];
-        }
-        __syncthreads();
-        if (t < dc) part[(size_t)(c0 + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-    }
 }
 
 // Final sums of a multi-target evaluation, one workgroup.  Results row (out, and hout pinned): [0] LL = sum_t LL_t added
@@ -3411,290 +3196,6 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize_targets(const double* 
     }
     for (int i = 1 + t; i < 1 + nh + m; i += FIN_THREADS)
         hout[i] = __hip_atomic_load(out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ------------------------------------------------------------------------------------------
-// ARD x Matern 3/2 and 5/2 (GPML covMaternard): the passes that need a derivative.  With u_c = (x_c - x'_c) w_c,
-// s = sum u_c^2 (sqdist_4x4<true>), a = c sqrt(s), e = exp(-a):
-//   kf = sf2 (p e) as matern_entry's,   dk / dtheta_c = H u_c^2,   dk / dx*_c = -H (x*_c - x_c) w_c^2
-//   3/2:  H = sf2 (3 e)          5/2:  H = sf2 ((RN(5/3) (1 + a)) e)    -- predict_grad_body's G, no singularity at a = 0
-// One exp per entry serves kf and H; e == 0 selects exact zeros for both ((1 + inf) * 0 is NaN).  No FMA contraction.
-// The kernels have bodies of their own: k_trace_ard, k_trace_targets_ard and predict_grad_body keep their instructions.
-// ------------------------------------------------------------------------------------------
-template <int KIND>
-__device__ __forceinline__ void ard_matern_entry(double s, double sf2, double& kf, double& hh)
-{
-#pragma clang fp contract(off)
-    static_assert(KIND == KERNEL_MATERN32 || KIND == KERNEL_MATERN52, "Matern kinds only");
-    const double c = KIND == KERNEL_MATERN32 ? 1.7320508075688772 : 2.23606797749979;
-    const double a = c * __builtin_sqrt(s);
-    const double e = exp(-a);
-    const double p1 = 1.0 + a;
-    double p, q;
-    if (KIND == KERNEL_MATERN32) {
-        p = p1;
-        q = 3.0;
-    } else {
-        p = p1 + (a * a) * 0.3333333333333333;
-        q = 1.6666666666666667 * p1;
-    }
-    const bool dead = e == 0.0;
-    kf = dead ? 0.0 : sf2 * (p * e);
-    hh = dead ? 0.0 : sf2 * (q * e);
-}
-
-// Gradient pass: k_trace_ard's two sweeps, partial layout (part[c * nblocks + block]; d: sum W o K, d + 1: tr W) and
-// summation order.  The 16 registers kept for the second sweep hold 2 (w H) where k_trace_ard keeps 2 (w Kf); sum W o K
-// takes Kf (+ sn2 on the diagonal, which has no share in any g_c).  k_finalize_ard / k_finalize_targets follow as they are.
-// TARGETS: W = m K^-1 - sum_t alpha_t alpha_t^T from the target-major AV ([m][npad]; k_trace_targets_ard's), single
-// handle; else W = K^-1 - alpha alpha^T from the vector AV, batched (blockIdx.y = expert) as k_trace_ard.
-template <int KIND, bool TARGETS>
-__device__ __forceinline__ void trace_ard_matern_body(const double* __restrict__ X, int n, int d, int npad,
-                                                      const HyperScalars* __restrict__ hd,
-                                                      const double* __restrict__ Kinv, const double* __restrict__ AV,
-                                                      int m, double* __restrict__ part,
-                                                      const ExpertPtrs* __restrict__ bt)
-{
-#pragma clang fp contract(off)
-    if (!TARGETS && bt) {
-        const ExpertPtrs& e = bt[blockIdx.y];
-        X = GP(e.X); n = e.n; Kinv = GP(e.Kinv); AV = GP(e.alpha); part = GP(e.part);
-    }
-    const HyperScalars h = *hd;
-    const double* __restrict__ wts = ard_weights(hd);
-    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
-    __shared__ __attribute__((aligned(16))) double la[TARGETS ? TGT_CHUNK : 1][KT], lb[TARGETS ? TGT_CHUNK : 1][KT];
-    __shared__ double ws[DC];
-    __shared__ double red[DC][4];
-    int ti, tj;
-    tri_index(blockIdx.x, ti, tj);
-    const int i0 = ti * KT, j0 = tj * KT;
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    const size_t nblocks = gridDim.x;
-    double wk[4][4], S[4][4];
-    sqdist_4x4<true>(X, X, n, n, d, i0, j0, xs, ys, wk, wts, ws);
-    double aj[4];
-    if constexpr (TARGETS) {
-        targets_outer_4x4(AV, npad, m, i0, j0, la, lb, S);
-    } else {
-#pragma unroll
-        for (int b = 0; b < 4; b++) aj[b] = AV[j0 + col4(tx, b)];
-    }
-    double s2 = 0.0, s3 = 0.0;
-    const double dm = (double)m;
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        const int i = i0 + ty * 4 + a;
-        const double ai = TARGETS ? 0.0 : AV[i];
-        const double* kr = Kinv + (size_t)i * npad + j0 + tx * 2;
-        d2 k01 = *(const d2*)kr, k23 = *(const d2*)(kr + 32);
-        const double kv[4] = {k01[0], k01[1], k23[0], k23[1]};
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const int j = j0 + col4(tx, b);
-            double e = 0.0;
-            if (i < n && j < n && (ti != tj || j <= i)) {
-                const double w = TARGETS ? dm * kv[b] - S[a][b] : kv[b] - ai * aj[b];
-                double kf, hh;
-                ard_matern_entry<KIND>(wk[a][b], h.signal_var, kf, hh);
-                if (i == j) {
-                    kf += h.noise_var;
-                    s2 += w * kf;
-                    s3 += w;
-                } else {
-                    e = 2.0 * (w * hh);
-                    s2 += 2.0 * (w * kf);
-                }
-            }
-            wk[a][b] = e;
-        }
-    }
-    s2 = wave_sum(s2); s3 = wave_sum(s3);
-    if ((t & 63) == 0) { red[0][t >> 6] = s2; red[1][t >> 6] = s3; }
-    __syncthreads();
-    if (t < 2) part[(size_t)(d + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-    for (int c0 = 0; c0 < d; c0 += DC) {
-        const int dc = (d - c0 < DC) ? (d - c0) : DC;
-        __syncthreads();
-        for (int e = t; e < KT * dc; e += 256) {
-            int r = e / dc, c = e - r * dc;
-            xs[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
-            ys[r][c] = (j0 + r < n) ? X[(size_t)(j0 + r) * d + c0 + c] : 0.0;
-        }
-        if (t < dc) ws[t] = wts[c0 + t];
-        __syncthreads();
-        double gs[DC];
-#pragma unroll
-        for (int c = 0; c < DC; c++) {
-            gs[c] = 0.0;
-            if (c < dc) {
-                double xv[4], yv[4];
-#pragma unroll
-                for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
-                const double wc = ws[c];
-                double acc = 0.0;
-#pragma unroll
-                for (int a = 0; a < 4; a++)
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const double df = (xv[a] - yv[b]) * wc;
-                        acc = acc + wk[a][b] * (df * df);
-                    }
-                gs[c] = wave_sum(acc);
-            }
-        }
-        if ((t & 63) == 0) {
-#pragma unroll
-            for (int c = 0; c < DC; c++) red[c][t >> 6] = gs[c];
-        }
-        __syncthreads();
-        if (t < dc) part[(size_t)(c0 + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
-    }
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_trace_ard_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                          const HyperScalars* __restrict__ hd,
-                                                          const double* __restrict__ Kinv,
-                                                          const double* __restrict__ alpha, double* __restrict__ part,
-                                                          const ExpertPtrs* __restrict__ bt)
-{
-    trace_ard_matern_body<KIND, false>(X, n, d, npad, hd, Kinv, alpha, 1, part, bt);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void k_trace_targets_ard_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                                  const HyperScalars* __restrict__ hd,
-                                                                  const double* __restrict__ Kinv,
-                                                                  const double* __restrict__ A, int m,
-                                                                  double* __restrict__ part)
-{
-    trace_ard_matern_body<KIND, true>(X, n, d, npad, hd, Kinv, A, m, part, nullptr);
-}
-
-// Gradient of the prediction with respect to the test inputs: predict_grad_body's Matern branch with the weighted
-// distance.  First sweep: the chunk's weights staged beside the X tiles, the difference formed first, then weighted,
-// then squared (sqdist_4x4<true>'s order), G = H from a of the weighted distance.  Second sweep, partial layout and
-// butterfly as predict_grad_body's: UNWEIGHTED differences -- k_predict_grad_finish applies w_c^2 once per output.
-template <int KIND>
-__global__ __launch_bounds__(256) void k_predict_grad_ard_matern(const double* __restrict__ X, int n, int d, int npad,
-                                                                 const double* __restrict__ Xt, int nt,
-                                                                 const HyperScalars* __restrict__ hd,
-                                                                 const double* __restrict__ V,
-                                                                 const double* __restrict__ alpha,
-                                                                 double* __restrict__ part, size_t pstride)
-{
-#pragma clang fp contract(off)
-    __shared__ double xs[KT][DC + 1], ys[KT][DC + 1];
-    __shared__ double ws[DC];
-    const double sf2 = hd->signal_var;
-    const double* __restrict__ wts = ard_weights(hd);
-    const int tiles_i = (n + KT - 1) / KT;
-    const int tt = blockIdx.x / tiles_i, ti = blockIdx.x % tiles_i;
-    const int t0 = tt * KT, i0 = ti * KT;
-    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
-    // one chunk of features of the tile's test rows (xs) and training rows (ys) and its weights into LDS
-    auto stage = [&](int c0, int dc) {
-        __syncthreads();
-        for (int e = t; e < KT * dc; e += 256) {
-            const int r = e / dc, c = e - r * dc;
-            xs[r][c] = (t0 + r < nt) ? Xt[(size_t)(t0 + r) * d + c0 + c] : 0.0;
-            ys[r][c] = (i0 + r < n) ? X[(size_t)(i0 + r) * d + c0 + c] : 0.0;
-        }
-        if (t < dc) ws[t] = wts[c0 + t];
-        __syncthreads();
-    };
-    double G[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) G[a][b] = 0.0;
-    for (int c0 = 0; c0 < d; c0 += DC) {
-        const int dc = (d - c0 < DC) ? (d - c0) : DC;
-        stage(c0, dc);
-        for (int c = 0; c < dc; c++) {
-            double xv[4], yv[4];
-#pragma unroll
-            for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
-            const double wc = ws[c];
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const double df = (xv[a] - yv[b]) * wc;
-                    G[a][b] = G[a][b] + df * df;
-                }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            double kf, hh;
-            ard_matern_entry<KIND>(G[a][b], sf2, kf, hh);
-            G[a][b] = hh;
-        }
-    double ga[4][4], gv[4][4];
-    double al[4];
-#pragma unroll
-    for (int b = 0; b < 4; b++) {
-        const int i = i0 + col4(tx, b);
-        al[b] = i < n ? alpha[i] : 0.0;
-    }
-#pragma unroll
-    for (int a = 0; a < 4; a++) {
-        const int tr = t0 + ty * 4 + a;
-        const size_t off = (size_t)tr * npad + i0 + tx * 2;
-        double vv[4] = {0.0, 0.0, 0.0, 0.0};
-        if (V) {
-            const d2 v01 = *(const d2*)(V + off), v23 = *(const d2*)(V + off + 32);
-            vv[0] = v01[0]; vv[1] = v01[1]; vv[2] = v23[0]; vv[3] = v23[1];
-        }
-#pragma unroll
-        for (int b = 0; b < 4; b++) {
-            const bool in = tr < nt && i0 + col4(tx, b) < n;
-            ga[a][b] = in ? G[a][b] * al[b] : 0.0;
-            gv[a][b] = in ? G[a][b] * vv[b] : 0.0;
-        }
-    }
-    double* pm_out = part + (size_t)ti * 2 * pstride;
-    double* pv_out = pm_out + pstride;
-    for (int c0 = 0; c0 < d; c0 += DC) {
-        const int dc = (d - c0 < DC) ? (d - c0) : DC;
-        stage(c0, dc);
-        for (int c = 0; c < dc; c++) {
-            double xv[4], yv[4], pm[4], pv[4];
-#pragma unroll
-            for (int a = 0; a < 4; a++) { xv[a] = xs[ty * 4 + a][c]; yv[a] = ys[col4(tx, a)][c]; }
-#pragma unroll
-            for (int a = 0; a < 4; a++) {
-                pm[a] = 0.0; pv[a] = 0.0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const double df = xv[a] - yv[b];
-                    pm[a] = pm[a] + ga[a][b] * df;
-                    pv[a] = pv[a] + gv[a][b] * df;
-                }
-            }
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1)
-#pragma unroll
-                for (int a = 0; a < 4; a++) {
-                    pm[a] = pm[a] + __shfl_xor(pm[a], m, 16);
-                    if (V) pv[a] = pv[a] + __shfl_xor(pv[a], m, 16);
-                }
-            if (tx == (c & 15)) {
-#pragma unroll
-                for (int a = 0; a < 4; a++) {
-                    const int tr = t0 + ty * 4 + a;
-                    if (tr < nt) {
-                        pm_out[(size_t)tr * d + c0 + c] = pm[a];
-                        if (V) pv_out[(size_t)tr * d + c0 + c] = pv[a];
-                    }
-                }
-            }
-        }
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3862,42 +3363,32 @@ thread_local const int* t_tune = g_tune_init;
 
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
 
-// The four passes that evaluate the covariance function launch the instantiation its descriptor names: k_<pass>_ard (its
-// own argument list: everything from cf.hd), else k_<pass> or k_<pass>_matern<KIND>, which share one.
-// The table of isotropic instantiations is this macro and nothing else.
-#define CUGP_ISO_KERNEL(cf, stem)                                                        \
-    ((cf).kind == KERNEL_MATERN32   ? stem##_matern<KERNEL_MATERN32>                     \
-     : (cf).kind == KERNEL_MATERN52 ? stem##_matern<KERNEL_MATERN52> : stem)
-// (the multi-target gradient pass is one template over the three kinds)
-#define CUGP_ISO_KERNEL_T(cf, stem)                                                      \
-    ((cf).kind == KERNEL_MATERN32   ? stem<KERNEL_MATERN32>                              \
-     : (cf).kind == KERNEL_MATERN52 ? stem<KERNEL_MATERN52> : stem<KERNEL_SE>)
-// The table of ARD instantiations: k_<pass>_ard for SE, k_<pass>_ard_matern<KIND> (the same argument list) otherwise.
-#define CUGP_ARD_KERNEL(cf, stem)                                                        \
-    ((cf).kind == KERNEL_MATERN32   ? stem##_ard_matern<KERNEL_MATERN32>                 \
-     : (cf).kind == KERNEL_MATERN52 ? stem##_ard_matern<KERNEL_MATERN52> : stem##_ard)
 static inline bool is_ard(const CovFn& cf)
 {
     assert(!cf.ard || cf.hd);
     return cf.ard;
 }
 
+// The one table of the covariance passes' instantiations: CUGP_COV_KERNEL(cf, k_<pass>) is k_<pass><ARD, KIND> of the
+// descriptor (every instantiation of a pass has one type, so the selection is an expression).
+#define CUGP_COV_KERNEL(cf, stem)                                                                        \
+    (is_ard(cf) ? ((cf).kind == KERNEL_MATERN32   ? stem<true, KERNEL_MATERN32>                          \
+                   : (cf).kind == KERNEL_MATERN52 ? stem<true, KERNEL_MATERN52> : stem<true, KERNEL_SE>) \
+                : ((cf).kind == KERNEL_MATERN32   ? stem<false, KERNEL_MATERN32>                         \
+                   : (cf).kind == KERNEL_MATERN52 ? stem<false, KERNEL_MATERN52> : stem<false, KERNEL_SE>))
+
 void launch_kbuild(const double* X, int n, int d, int npad, const CovFn& cf, double* K, bool full, hipStream_t s,
                    Batch bt, unsigned* tickets)
 {
     const dim3 grid(tri_count(npad / KT), bt.count);
-    if (is_ard(cf))
-        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.hd, K, full ? 1 : 0,
-                           tickets, bt.tab, take_stamp());
-    else
-        hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, K, full ? 1 : 0,
-                           tickets, bt.tab, take_stamp());
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_build), grid, dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, K, full ? 1 : 0,
+                       tickets, bt.tab, take_stamp());
 }
 
 void launch_sqdist(const double* X, int n, int d, int npad, double c, double* S, hipStream_t s)
 {
     HyperScalars h{c, 0.0, 0.0};
-    hipLaunchKernelGGL(k_build, dim3(tri_count(npad / KT)), dim3(256), 0, s, X, n, d, npad, h,
+    hipLaunchKernelGGL((k_build<false, KERNEL_SE>), dim3(tri_count(npad / KT)), dim3(256), 0, s, X, n, d, npad, h,
                        (const HyperScalars*)nullptr, S, 2, (unsigned*)nullptr, (const ExpertPtrs*)nullptr,
                        (unsigned long long*)nullptr);
 }
@@ -3906,12 +3397,8 @@ void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, in
                    double* Ks, hipStream_t s, Batch bt)
 {
     const dim3 grid((ntpad / KT) * (npad / KT), bt.count);
-    if (is_ard(cf))
-        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.hd, Ks,
-                           bt.tab);
-    else
-        hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.h, Ks,
-                           bt.tab);
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_cross), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, ntpad, cf.h, Ks,
+                       bt.tab, cf.hd);
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
@@ -4158,12 +3645,8 @@ void launch_predict_cov_finish(const double* Xt, int nt, int d, int ntpad, const
                                double jitter, double* A, const double* scr, int nscr, unsigned* tickets, hipStream_t s)
 {
     const dim3 grid(tri_count(ntpad / KT));
-    if (is_ard(cf))
-        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_predict_cov_finish), grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.hd,
-                           with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
-    else
-        hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_predict_cov_finish), grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.h,
-                           with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets);
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_predict_cov_finish), grid, dim3(256), 0, s, Xt, nt, d, ntpad, cf.h,
+                       with_noise ? 1 : 0, jitter, A, scr, (size_t)ntpad * ntpad, nscr, tickets, cf.hd);
 }
 
 void launch_zero_upper_diag(double* A, int ld, int nt, hipStream_t s)
@@ -4190,15 +3673,8 @@ void launch_predict_grad(const double* X, int n, int d, int npad, const double* 
                          hipStream_t s)
 {
     const dim3 grid(((nt + KT - 1) / KT) * predict_grad_tiles(n));
-    if (is_ard(cf) && cf.kind != KERNEL_SE)     // (SE-ARD reads G from Ks: the isotropic SE kernel serves it)
-        CUGP_LAUNCH((cf.kind == KERNEL_MATERN32 ? k_predict_grad_ard_matern<KERNEL_MATERN32>
-                                                : k_predict_grad_ard_matern<KERNEL_MATERN52>),
-                    grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.hd, V, alpha, part, pstride);
-    else if (is_ard(cf))
-        CUGP_LAUNCH(k_predict_grad, grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha, part, pstride);
-    else
-        CUGP_LAUNCH(CUGP_ISO_KERNEL(cf, k_predict_grad), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha,
-                    part, pstride);
+    CUGP_LAUNCH(CUGP_COV_KERNEL(cf, k_predict_grad), grid, dim3(256), 0, s, X, n, d, npad, Xt, nt, cf.h, Ks, V, alpha, part,
+                pstride, cf.hd);
 }
 
 void launch_predict_grad_finish(const double* part, size_t pstride, int n, int nt, int d, const CovFn& cf, double* dmean,
@@ -4258,22 +3734,21 @@ void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, cons
                   double* hout, unsigned* ticket)
 {
     const int nblocks = tri_count(npad / KT);
-    if (is_ard(cf)) {                          // always both launches: there is no fused form of the ARD final sums
+    const bool ard = is_ard(cf);
+    // the last block takes the final sums where the launch is small (its 256 threads against k_finalize's 1024: at 8192
+    // rows -- 8256 blocks -- the separate launch is as fast and keeps the blocks' stores plain); TUNE_FINALIZE_FUSE_MAX.
+    // ARD: always both launches -- there is no fused form of the ARD final sums
+    const bool fuse = !ard && out != nullptr && nblocks <= tune(TUNE_FINALIZE_FUSE_MAX);
+    const FinalizeArgs fin{z, logdet_part, npad / TILE, fuse ? out : nullptr, hout, ticket};
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace), dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd,
+                       Kinv, alpha, part, bt.tab, fin);
+    if (ard) {
         assert(hout && (out || bt.tab));
-        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_trace), dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv,
-                           alpha, part, bt.tab);
         hipLaunchKernelGGL(k_finalize_ard, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part,
                            npad / TILE, part, nblocks, cf.hd, out, hout, (size_t)(ARD_ROW_GRAD + d + 2), bt.tab);
-        return;
-    }
-    // the last block takes the final sums where the launch is small (its 256 threads against k_finalize's 1024: at 8192
-    // rows -- 8256 blocks -- the separate launch is as fast and keeps the blocks' stores plain); TUNE_FINALIZE_FUSE_MAX
-    const bool fuse = out != nullptr && nblocks <= tune(TUNE_FINALIZE_FUSE_MAX);
-    const FinalizeArgs fin{z, logdet_part, npad / TILE, fuse ? out : nullptr, hout, ticket};
-    hipLaunchKernelGGL(CUGP_ISO_KERNEL(cf, k_trace), dim3(nblocks, bt.count), dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd,
-                       Kinv, alpha, part, bt.tab, fin);
-    if (out != nullptr && !fuse)
+    } else if (out != nullptr && !fuse) {
         launch_finalize(z, npad, n, logdet_part, npad / TILE, part, nblocks, cf.h, out, hout, s, cf.hd, bt);
+    }
 }
 
 void launch_finalize(const double* z, int npad, int n, const double* logdet_part, int nt, const double* part,
@@ -4294,12 +3769,8 @@ void launch_trace_targets(const double* X, int n, int d, int npad, const CovFn& 
                           int m, double* part, hipStream_t s)
 {
     const dim3 grid(tri_count(npad / KT));
-    if (is_ard(cf))
-        hipLaunchKernelGGL(CUGP_ARD_KERNEL(cf, k_trace_targets), grid, dim3(256), 0, s, X, n, d, npad, cf.hd, Kinv, A, m,
-                           part);
-    else
-        hipLaunchKernelGGL(CUGP_ISO_KERNEL_T(cf, k_trace_targets), grid, dim3(256), 0, s, X, n, d, npad, cf.h, Kinv, A, m,
-                           part);
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_targets), grid, dim3(256), 0, s, X, n, d, npad, cf.h, Kinv, A, m, part,
+                       cf.hd);
 }
 
 void launch_finalize_targets(const double* Z, int npad, int n, int d, int m, double logdet, const double* part,

@@ -1,5 +1,5 @@
 """GPU tests of the ARD product of experts: ARD handles as the experts of a group of shared launches (batched
-k_build_ard, k_cross_ard, k_trace_ard, k_finalize_ard), rows {LL, g[nh]} through cugp_bcm_*_ard, the optimiser, the
+k_build, k_cross, k_trace <true, KERNEL_SE>, k_finalize_ard), rows {LL, g[nh]} through cugp_bcm_*_ard, the optimiser, the
 exchange.
 
 Accuracy is held to fp64 rounding against the extended-precision truth, through tests/truth_ard_bcm.py and the Report of
@@ -352,7 +352,7 @@ def test_cg_solve_equals_the_python_driven_loop(gp_mod):
 @pytest.mark.parametrize("rows", [[300], [300] * 3, [100, 400]], ids=["K1", "K3", "ungrouped"])
 def test_world_of_one_exchange(gp_mod, comm1, rows):
     """loglik_grad_allgather(b, K, nh) equals loglik_grad_rows() bit for bit (rows packed on the device behind the
-    evaluation: two strided copies per group, one per lone expert); predict_allgather (the batched k_cross_ard) equals
+    evaluation: two strided copies per group, one per lone expert); predict_allgather (the batched k_cross<true, KERNEL_SE>) equals
     compute_BCM_test_means_and_var.  An isotropic BCM then uses the same communicator at its own width."""
     K, d = len(rows), 4
     X, y = synth(sum(rows), d=d, seed=11 + K, scale=3.0)

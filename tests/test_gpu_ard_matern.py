@@ -241,18 +241,22 @@ def test_ten_evaluations_identical_bits(gp_mod, kind):
 
 
 # ------------------------------------------------------------------ 8. joint covariance and draws
+JOINT_CASES = [pytest.param("n65_d2", M52, id="n65_d2"), pytest.param("n257_d3", M52, id="n257_d3"),
+               pytest.param("n300_d17", M32, id="n300_d17-matern32")]   # (the last: the nu = 3/2 instantiation of the epilogue)
+
+
 @extended
-@pytest.mark.parametrize("name", ["n65_d2", "n257_d3"])
-def test_joint_covariance_and_draws(gp_mod, oracle, name):
-    """nu = 5/2.  cugp_predict_cov with and without noise against the truth's joint covariance at the bound
+@pytest.mark.parametrize("name, kind", JOINT_CASES)
+def test_joint_covariance_and_draws(gp_mod, oracle, name, kind):
+    """nu = 5/2, and nu = 3/2 once.  cugp_predict_cov with and without noise against the truth's joint covariance at the bound
     tests/test_gpu_matern.py holds it to (the variance's yardstick, the covariance floor; this family's factor); cov exactly
     symmetric, the mean cugp_predict's bits.  Draws: zero normals give the mean's bits, unit normals pick columns of the
     Cholesky factor of the library's own covariance (against LAPACK's factor of the same fp64 matrix: two backward-stable
     factorisations differ by about nt eps cond(cov) relative to the factor's scale)."""
-    c = tam.live(oracle, name, M52)
+    c = tam.live(oracle, name, kind)
     X, y, Xt, hp, t, noise, fl = c["X"], c["y"], c["Xt"], c["cov"].hp, c["t"], c["noise"], c["floor"]
-    rep = Report("%s/%s" % (name, tam.FAMILY[M52]), c["cov"])
-    g = handle(gp_mod, X, y, hp, M52)
+    rep = Report("%s/%s" % (name, tam.FAMILY[kind]), c["cov"])
+    g = handle(gp_mod, X, y, hp, kind)
     m, _ = g.compute_test_means_and_variances(X, y, Xt)
     for with_noise in (True, False):
         tmj, tcov = t.joint(Xt, with_noise)
@@ -309,15 +313,20 @@ def test_predict_grad(gp_mod, oracle, name, kind, nt):
 
 
 # ------------------------------------------------------------------ 10. multi-target regression
+TARGET_CASES = [pytest.param(M52, "n257_d3", 1, id="1"), pytest.param(M52, "n257_d3", 5, id="5"),
+                pytest.param(M52, "n257_d3", 17, id="17"), pytest.param(M32, "n300_d17", 3, id="matern32-n300_d17-m3")]
+
+
 @extended
-@pytest.mark.parametrize("m", [1, 5, 17])
-def test_targets(gp_mod, oracle, m):
+@pytest.mark.parametrize("kind, name, m", TARGET_CASES)
+def test_targets(gp_mod, oracle, kind, name, m):
     """n257_d3, nu = 5/2, through tests/truth_targets.py's truth and bound with this family's descriptor; m = 17 crosses the
-    16-target staging chunk of the gradient pass."""
-    c = tt.case(oracle, tam.FAMILY[M52], "n257_d3", m)
+    16-target staging chunk of the gradient pass.  n300_d17, nu = 3/2: the other instantiation of the gradient pass, across
+    a tile and a feature-chunk boundary."""
+    c = tt.case(oracle, tam.FAMILY[kind], name, m)
     cov = c["cov"]
-    rep = Report("targets/%s/m%d" % (tam.FAMILY[M52], m), cov)
-    g = handle(gp_mod, c["X"], c["y"], cov.hp, M52)
+    rep = Report("targets/%s/m%d" % (tam.FAMILY[kind], m), cov)
+    g = handle(gp_mod, c["X"], c["y"], cov.hp, kind)
     try:
         g.set_targets(np.asarray(c["Y"]).T)
         assert g.num_targets == m

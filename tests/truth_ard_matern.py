@@ -13,7 +13,7 @@ they are.
   yardstick   as truth.Matern.evaluator: K formed in fp64 numpy, handed to the oracle's chol_and_det / K_inverse / Kinvy;
               the gradient has d + 2 entries, so truth.errors_ll_grad compares every g_c.
   per entry   `entry_fp64` restates the kernels' arithmetic (kernels.hip: matern_entry at s = the weighted distance,
-              ard_matern_entry's H) rounding by rounding; `k_entry_bound` is the count it and the GPU's K entries are
+              matern_entry's H) rounding by rounding; `k_entry_bound` is the count it and the GPU's K entries are
               held to.
   families    "matern32_ard" / "matern52_ard" are added to truth.FAMILIES when this module is imported (the cases are
               truth.ARD_CASES' data and theta), so accuracy.live, truth_targets.case and truth_append's helpers take them.

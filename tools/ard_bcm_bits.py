@@ -1,12 +1,17 @@
-"""Results of the paths the ARD product of experts must not change, as hex, for a comparison of two library builds in
-fresh processes:
+"""Results of every covariance pass, as hex, for a comparison of two library builds in fresh processes (a change that
+must not move a bit: the ARD product of experts first, then the merge of the per-family kernel bodies):
 
     python tools/ard_bcm_bits.py [--lib other/libcugp.so] > bits.txt        (once per build)
     python tools/ard_bcm_bits.py --compare parent.txt build.txt             (label | parent | this build | equal)
 
   - a single ARD handle at N = 1500 (captured graph) and at N = 4096 (launch by launch), D = 10: LL, the gradient, a
     64-point prediction;
-  - a squared-exponential and a Matern-5/2 BCM of 2 x 1500 rows: LL, the gradient, the prediction.
+  - a squared-exponential and a Matern-5/2 BCM of 2 x 1500 rows: LL, the gradient, the prediction;
+  - every kind in {SE, Matern 3/2, Matern 5/2} x {isotropic, ARD} at n = 130 (three 64-row tiles: an off-diagonal one and
+    a diagonal one holding two data rows), d = 17 (two feature chunks, the second of one feature) and 70 test points (two
+    test tiles): a single handle's LL and gradient launch by launch and as a captured graph (key 5), isotropic with the
+    fused and the separate final sums (key 12); a 3-target evaluation; a prediction with joint covariance; the
+    test-input gradients of mean and variance; a 2-expert grouped model's LL, gradient and prediction.
 Doubles as C99 hex; arrays longer than 12 as the first 24 hex digits of sha256 over their bytes.
 """
 import argparse
@@ -38,6 +43,70 @@ def compare(pa, pb):
         print("%s | %s | %s | %s" % (label, va, vb, "yes" if va == vb else "NO"))
     print("# %d values, %d differ" % (len(A), bad))
     return 1 if bad else 0
+
+
+def family_cases(gp, synth):
+    """Every instantiation of the covariance passes (build, cross, joint-covariance epilogue, trace, trace-targets,
+    predict-grad) at the smallest shapes that cross a tile and a feature-chunk boundary."""
+    GRAPHS, FINALIZE_FUSE_MAX = 5, 12                    # kernels.h TUNE_*
+    n, d, nt, m = 130, 17, 70, 3
+    X2, y2 = synth(2 * n, d, seed=4711, scale=3.0)
+    X, y = X2[:n], y2[:n]
+    rng = np.random.default_rng(4712)
+    Xt = np.ascontiguousarray(0.5 * X[:nt] + 0.3 * rng.standard_normal((nt, d)))
+    Y = np.ascontiguousarray(np.column_stack([y, np.cos(X[:, 1]) + 0.1 * rng.standard_normal(n), X[:, 2] * 0.3]))
+    assert Y.shape == (n, m)
+    for kind in ("se", "matern32", "matern52"):
+        for ard in (False, True):
+            tag = "%s%s n=%d" % (kind, " ard" if ard else "", n)
+            kw = dict(kernel=kind + "_ard") if ard and kind != "se" else dict(kernel=kind, ard=ard)
+
+            def hyper(i):
+                ell = np.log(4.0) + (np.linspace(-0.3, 0.3, d) if ard else np.zeros(1)) + 0.01 * i
+                return ell.tolist() + [0.1, float(np.log(0.2))]
+
+            g = gp.Covsum(n, d, 0, **kw)
+            g.set_data(X, y)
+            for graphs in (0, 1):
+                for fuse in ((None,) if ard else (0, 1 << 30)):
+                    g.set_tuning(GRAPHS, graphs)
+                    if fuse is not None:
+                        g.set_tuning(FINALIZE_FUSE_MAX, fuse)
+                    for i in range(2):                   # (graphs = 1: the second evaluation replays the captured graph)
+                        g.set_loghyperparam(hyper(i))
+                        ll, gr = g.loglik_grad()
+                        cfg = "graphs=%d fuse=%s @%d" % (graphs, "-" if fuse is None else min(fuse, 1), i)
+                        show("%s ll %s" % (tag, cfg), ll)
+                        show("%s grad %s" % (tag, cfg), gr)
+            g.set_targets(Y)
+            ll, gr, each = g.loglik_grad_targets()
+            show("%s targets ll" % tag, ll)
+            show("%s targets grad" % tag, gr)
+            show("%s targets each" % tag, each)
+            tm, tv = g.predict_targets(Xt)
+            show("%s targets mean" % tag, tm.ravel())
+            mean, cov = g.compute_test_joint(X, y, Xt)
+            show("%s joint mean" % tag, mean)
+            show("%s joint cov" % tag, cov.ravel())
+            for with_var in (True, False):
+                pm, pv, dm, dv = g.predict_grad(Xt, want_var_grad=with_var)
+                show("%s predict_grad mean var=%d" % (tag, with_var), pm)
+                show("%s predict_grad variance var=%d" % (tag, with_var), pv)
+                show("%s predict_grad dmean var=%d" % (tag, with_var), dm.ravel())
+                if with_var:
+                    show("%s predict_grad dvar" % tag, dv.ravel())
+            g.close()
+            b = gp.BCM.split(X2, y2, 2, **kw)
+            for i in range(2):
+                b.set_BCM_log_hyperparam(hyper(i))
+                ll, gr, per = b.loglik_grad()
+                bm, bv = b.compute_BCM_test_means_and_var(Xt)
+                show("%s bcm 2x%d ll@%d" % (tag, n, i), ll)
+                show("%s bcm 2x%d grad@%d" % (tag, n, i), gr)
+                show("%s bcm 2x%d per-expert ll@%d" % (tag, n, i), per)
+                show("%s bcm 2x%d mean@%d" % (tag, n, i), bm)
+                show("%s bcm 2x%d var@%d" % (tag, n, i), bv)
+            b.close()
 
 
 def main():
@@ -86,6 +155,7 @@ def main():
             show("%s bcm 2x1500 mean@%d" % (kernel, i), m)
             show("%s bcm 2x1500 var@%d" % (kernel, i), v)
         b.close()
+    family_cases(gp, synth)
     return 0
 
 

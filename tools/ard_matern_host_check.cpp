@@ -1,4 +1,4 @@
-// Host check of k_trace_ard_matern and k_predict_grad_ard_matern (tools/ard_matern_host_check.py builds and runs this; no
+// Host check of trace_ard_body<KIND, false> (k_trace<true, KIND>) and k_predict_grad<true, KIND> (tools/ard_matern_host_check.py builds and runs this; no
 // GPU).  The kernels' own text -- cut out of cugp_amd/csrc/kernels.hip into body.inc by the script -- runs one workgroup at
 // a time as 256 host threads in lock step: a barrier stands for __syncthreads, an exchange array and two barriers for the
 // shuffles (__shfl_down inside a 64-lane wave, __shfl_xor inside 16 lanes).  Every buffer is a heap block of exactly the
@@ -94,8 +94,8 @@ int main(int argc, char** argv)
         const size_t np = (size_t)(d + 2) * nb;
         double* part = (double*)malloc(np * 8);
         for (size_t i = 0; i < np; i++) part[i] = NAN;
-        if (kind == 1) launch(nb, [&] { k_trace_ard_matern<1>(X, n, d, npad, hd, Kinv, alpha, part, nullptr); });
-        else launch(nb, [&] { k_trace_ard_matern<2>(X, n, d, npad, hd, Kinv, alpha, part, nullptr); });
+        if (kind == 1) launch(nb, [&] { trace_ard_body<1, false>(X, n, d, npad, hd, Kinv, alpha, 1, part, nullptr); });
+        else launch(nb, [&] { trace_ard_body<2, false>(X, n, d, npad, hd, Kinv, alpha, 1, part, nullptr); });
         o = fopen(argv[2], "wb");
         fwrite(part, 8, np, o);
         free(part); free(Kinv); free(alpha);
@@ -108,8 +108,8 @@ int main(int argc, char** argv)
         for (size_t i = 0; i < tiles * 2 * pstride; i++) part[i] = NAN;
         const double* Vp = wantV ? V : nullptr;
         const int blocks = ((nt + 63) / 64) * tiles;
-        if (kind == 1) launch(blocks, [&] { k_predict_grad_ard_matern<1>(X, n, d, npad, Xt, nt, hd, Vp, alpha, part, pstride); });
-        else launch(blocks, [&] { k_predict_grad_ard_matern<2>(X, n, d, npad, Xt, nt, hd, Vp, alpha, part, pstride); });
+        if (kind == 1) launch(blocks, [&] { k_predict_grad<true, 1>(X, n, d, npad, Xt, nt, HyperScalars{}, nullptr, Vp, alpha, part, pstride, hd); });
+        else launch(blocks, [&] { k_predict_grad<true, 2>(X, n, d, npad, Xt, nt, HyperScalars{}, nullptr, Vp, alpha, part, pstride, hd); });
         double* dm = (double*)malloc(pstride * 8);
         double* dv = (double*)malloc(pstride * 8);
         const int fblocks = (int)((pstride + 255) / 256);

@@ -1,4 +1,4 @@
-"""k_trace_ard_matern and k_predict_grad_ard_matern on the CPU, without a GPU: the kernels' own text (cut out of
+"""The ARD Matern instantiations of trace_ard_body (k_trace<true, KIND>) and k_predict_grad<true, KIND> on the CPU, without a GPU: the kernels' own text (cut out of
 cugp_amd/csrc/kernels.hip) in a lock-step host emulation (tools/ard_matern_host_check.cpp) built with
 -fsanitize=address,undefined, on cases of truth.ARD_CASES.  K^-1, alpha and V are padded as the library pads them, but with
 NaN instead of zeros: a missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  The results are
@@ -42,9 +42,15 @@ def build(tmp):
                            between("__device__ __forceinline__ double wave_sum(", "// z[i] = sum_{k < (ti+1)*128}"),
                            between("__global__ __launch_bounds__(256) void k_predict_grad_finish(",
                                    "// Product of experts over the gathered exchange buffer"),
-                           between("constexpr int TGT_CHUNK = 16;", "// Gradient pass of the summed objective, isotropic families"),
-                           between("template <int KIND>\n__device__ __forceinline__ void ard_matern_entry(",
-                                   "// Appending observations (cugp_append): one bordering step"))))
+                           between("constexpr int TGT_CHUNK = 16;", "// what the last block of k_trace needs"),
+                           between("struct DivBy { double b, y; };", "// ARD handles keep the d per-dimension weights"),
+                           between("__device__ __forceinline__ DivBy div_prepare(", "// ---- Matern 3/2 and 5/2 (GPML covMaterniso"),
+                           between("template <int KIND>\n__device__ __forceinline__ void matern_entry(",
+                                   "// the value of one entry without the noise term"),
+                           between("template <int KIND, bool TARGETS>\n__device__ __forceinline__ void trace_ard_body(",
+                                   "// k_trace: the gradient pass of a single-target evaluation"),
+                           between("template <bool ARD, int KIND>\n__device__ __forceinline__ void predict_grad_body(",
+                                   "// dmean[t][c] = -s_c (P_0 + P_1 + ...)"))))
     exe = os.path.join(tmp, "host_check")
     subprocess.check_call([CLANG, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-pthread", "-I", tmp,
                            os.path.join(ROOT, "tools", "ard_matern_host_check.cpp"), "-o", exe])

@@ -10,7 +10,7 @@ own, the program after the double dash):
     python tools/ard_probe.py [--reps 10] [--json profiles/ard_probe.json]
     rocprofv3 --kernel-trace --stats -d out -- python tools/ard_probe.py --reps 3
 
-k_trace_ard reads the lower 64x64 tiles of K^-1 once, as k_trace does: bytes = tiles * 64 * 64 * 8, reported here per
+k_trace<true, 0> (ARD) reads the lower 64x64 tiles of K^-1 once, as k_trace<false, 0> does: bytes = tiles * 64 * 64 * 8, reported here per
 case so that the profiler's time turns into a share of the 8 TB/s HBM peak.
 
 --bcm: the ARD product of experts instead, at 16 x 1500 and 4 x 6000 rows with D = 10, per evaluation (LL + gradient at a
@@ -21,7 +21,7 @@ new theta every time), interleaved call by call in one process:
     c  the isotropic BCM of the same shape
 --variants picks among them (a library without cugp_bcm_create_ard runs b and c); --lib loads another libcugp.so (the
 parent commit's, for the alternating-process comparison); --trace-csv turns a rocprofv3 kernel trace of a --variants ac run
-into mean dispatch times of k_trace_ard, k_finalize_ard and k_trace per shape (the grid's y extent tells the shapes apart):
+into mean dispatch times of k_trace<true, 0>, k_finalize_ard and k_trace<false, 0> per shape (the grid's y extent tells the shapes apart):
 
     python tools/ard_probe.py --bcm [--reps 10] [--json out.json] [--lib other/libcugp.so] [--variants abc]
     rocprofv3 --kernel-trace --output-format csv -d out -- python tools/ard_probe.py --bcm --reps 3 --variants ac
@@ -129,7 +129,7 @@ def trace_report(path):
     acc = {}
     for r in csv.DictReader(open(path)):
         name = re.sub(r"^void |cugp::|\(.*$", "", r["Kernel_Name"])
-        if name not in ("k_trace", "k_trace_ard", "k_finalize_ard", "k_finalize"):
+        if name not in ("k_trace<false, 0>", "k_trace<true, 0>", "k_finalize_ard", "k_finalize"):
             continue
         gy = int(r["Grid_Size_Y"]) // max(1, int(r["Workgroup_Size_Y"]))
         a = acc.setdefault((name, gy), [])
@@ -174,7 +174,7 @@ def main():
             return g.fetch()
         for _ in range(2):
             ri, ra = ev(gi), ev(ga)
-        Xt = np.ascontiguousarray(X[:1000] * 0.5)    # one prediction each: k_cross / k_cross_ard appear in a kernel trace
+        Xt = np.ascontiguousarray(X[:1000] * 0.5)    # one prediction each: k_cross<false, 0> / k_cross<true, 0> appear in a kernel trace
         gi.compute_test_means_and_variances(X, y, Xt)
         ga.compute_test_means_and_variances(X, y, Xt)
         ti, tr = [], []

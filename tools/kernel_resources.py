@@ -3,7 +3,8 @@
 Workgroups per CU = min over the limits: 512 unified VGPRs per SIMD lane (VGPR + AGPR, allocation granule 8),
 160 KiB LDS per CU (static + the dynamic size the launcher asks for), 32 waves per CU.
 --digest: instead of the table, one line per kernel with a sha256 of its instructions (label to .Lfunc_end, without
-comments, .loc / .file lines and blank lines, block labels .LBB<n>_ normalised) -- equal digests before and after a
+comments, .loc / .file / .section / .text lines and blank lines, block labels .LBB<n>_ and the kernel's own symbol
+normalised, so that a renamed kernel or one that became a template keeps its digest) -- equal digests before and after a
 refactor of kernels.hip mean that no kernel's code changed:  python tools/kernel_resources.py --digest [kernels.hip]"""
 import hashlib
 import os
@@ -32,8 +33,8 @@ if "--digest" in sys.argv:
     dems = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
     for name, dem in zip(names, dems):
         body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(name), txt, re.M | re.S).group(1)
-        lines = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r";.*", "", ln)).strip() for ln in body.split("\n")]
-        lines = [ln for ln in lines if ln and not ln.startswith((".loc", ".file"))]
+        lines = [re.sub(r"\.LBB\d+_", ".LBB_", re.sub(r";.*", "", ln)).replace(name, "<kernel>").strip() for ln in body.split("\n")]
+        lines = [ln for ln in lines if ln and not ln.startswith((".loc", ".file", ".section", ".text"))]
         print("%s  %5d  %s" % (hashlib.sha256("\n".join(lines).encode()).hexdigest()[:32], len(lines),
                                re.sub(r"^void |cugp::|\(.*$", "", dem)))
     sys.exit(0)

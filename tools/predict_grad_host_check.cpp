@@ -72,9 +72,9 @@ int main(int argc, char** argv)
     HyperScalars h{hs[0], hs[1], 0.0};
     const double* Vp = wantV ? V : nullptr;
     const int blocks = ((nt + 63) / 64) * tiles;
-    if (kind == 0) launch(blocks, [&] { k_predict_grad(X, n, d, npad, Xt, nt, h, Ks, Vp, alpha, part, pstride); });
-    else if (kind == 1) launch(blocks, [&] { k_predict_grad_matern<1>(X, n, d, npad, Xt, nt, h, Ks, Vp, alpha, part, pstride); });
-    else launch(blocks, [&] { k_predict_grad_matern<2>(X, n, d, npad, Xt, nt, h, Ks, Vp, alpha, part, pstride); });
+    if (kind == 0) launch(blocks, [&] { k_predict_grad<false, 0>(X, n, d, npad, Xt, nt, h, Ks, Vp, alpha, part, pstride, nullptr); });
+    else if (kind == 1) launch(blocks, [&] { k_predict_grad<false, 1>(X, n, d, npad, Xt, nt, h, Ks, Vp, alpha, part, pstride, nullptr); });
+    else launch(blocks, [&] { k_predict_grad<false, 2>(X, n, d, npad, Xt, nt, h, Ks, Vp, alpha, part, pstride, nullptr); });
     double* dm = (double*)malloc(pstride * 8);
     double* dv = (double*)malloc(pstride * 8);
     const int fblocks = (int)((pstride + 255) / 256);

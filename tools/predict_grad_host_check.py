@@ -32,9 +32,11 @@ def build(tmp):
         i = src.index(a)
         return src[i: src.index(b, i)]
     with open(os.path.join(tmp, "body.inc"), "w") as f:
-        f.write("\n".join((between("__device__ __forceinline__ int col4(", "// squared distances of a 4x4 micro-tile"),
+        f.write("\n".join((between("__device__ __forceinline__ int col4(", "// a / b for many a and one b"),
                            between("struct DivBy { double b, y; };", "// ---- Matern 3/2 and 5/2 (GPML covMaterniso"),
-                           between("template <int KIND>\n__device__ __forceinline__ void predict_grad_body(",
+                           between("template <int KIND>\n__device__ __forceinline__ void matern_entry(",
+                                   "// ARD entry from the WEIGHTED squared distance"),
+                           between("template <bool ARD, int KIND>\n__device__ __forceinline__ void predict_grad_body(",
                                    "// Product of experts over the gathered exchange buffer"))))
     exe = os.path.join(tmp, "host_check")
     subprocess.check_call([CLANG, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-pthread", "-I", tmp,

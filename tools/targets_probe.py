@@ -38,7 +38,7 @@ NS = (1500, 4096, 8192)
 MS = (1, 4, 16, 64)
 D = 10
 NT = 1000
-NEW = ("k_targets_alpha", "k_trace_targets", "k_trace_targets_ard", "k_finalize_targets", "k_targets_mean",
+NEW = ("k_targets_alpha", "k_trace_targets", "k_finalize_targets", "k_targets_mean",
        "k_targets_mean_finish")
 
 
