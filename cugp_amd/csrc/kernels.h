@@ -1,7 +1,13 @@
 // kernels.h -- internal launch interface between the C-ABI (cugp_capi.cpp) and
 // the gfx950 kernels (kernels.hip).  Not part of the public boundary.
+//
+// The structs and constants below are also what the host checks of the emulable device code (cov_device.h,
+// append_device.h) see: tools/host_emul.h includes this file without a HIP runtime, with hipStream_t and hipEvent_t as
+// opaque pointers for the launcher prototypes, so no check keeps a copy of HyperScalars, ExpertPtrs, KERNEL_* or TILE.
 #pragma once
+#ifndef CUGP_HOST_EMUL
 #include <hip/hip_runtime.h>
+#endif
 
 namespace cugp {
 

@@ -1,49 +1,15 @@
 // Host check of k_append_border and k_append_kinv (tools/append_host_check.py builds and runs this; no GPU).
-// The kernels' own text -- cut out of cugp_amd/csrc/kernels.hip into body.inc by the script -- runs one workgroup at a time
-// as 256 host threads in lock step: a barrier stands for __syncthreads, an exchange array and a barrier per wave for
-// __shfl_down.  The fp64 MFMA tile product and its accumulate-and-store epilogue (tile_nt, tile_accum_store: existing
+// The kernels' own text -- cugp_amd/csrc/append_device.h, the header kernels.hip includes -- runs behind the emulation
+// shim tools/host_emul.h, one workgroup at a time as 256 host threads in lock step.
+// The fp64 MFMA tile product and its accumulate-and-store epilogue (tile_nt, tile_accum_store: existing
 // code) are stood in for by plain loops over the same pointers and k range, so what is checked of k_append_kinv is its
 // own part: which tiles, which rows of Qt, which k range, the alpha update.  Every buffer is a heap block of exactly the
 // size the library gives it, so a build with -fsanitize=address,undefined sees any access beyond one; the script fills
 // what the kernels must not read with NaN.  A stand-alone program: the sanitizer is linked in, nothing is preloaded.
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-struct Idx { int x = 0, y = 0, z = 0; };
-static thread_local Idx threadIdx;
-static Idx blockIdx;
-static std::barrier<> g_bar(256);
-static std::barrier<> g_wbar[4] = {std::barrier<>(64), std::barrier<>(64), std::barrier<>(64), std::barrier<>(64)};
-static double g_slot[256];
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(...)
-#define __shared__ static
-#define __shfl_down shfl_down_host
-static inline void __syncthreads() { g_bar.arrive_and_wait(); }
-static inline double shfl_down_host(double v, int o, int)
-{
-    const int t = threadIdx.x, w = t >> 6;
-    g_slot[t] = v;
-    g_wbar[w].arrive_and_wait();
-    const double r = (t & 63) + o < 64 ? g_slot[t + o] : v;
-    g_wbar[w].arrive_and_wait();
-    return r;
-}
-constexpr int TILE = 128;
-__device__ __forceinline__ double wave_sum(double v)
-{
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
+#include "host_emul.h"
+namespace cugp {
+#include "cov_device.h"
 // stand-ins for the fp64 MFMA tile machinery: one 64 x 64 accumulator per workgroup, filled and stored by thread 0
-typedef double d4;
 static double g_acc[64][64];
 template <int WM> static void acc_zero(d4 (&)[WM][WM]) { __syncthreads(); if (threadIdx.x == 0) memset(g_acc, 0, sizeof g_acc); __syncthreads(); }
 template <bool NEGA, int WM>
@@ -62,24 +28,9 @@ template <int SIGN, int WM> static void tile_accum_store(double* C, int ldc, con
             for (int j = 0; j < 64; j++) C[(size_t)i * ldc + j] += SIGN * g_acc[i][j];
     __syncthreads();
 }
-static void tri_index(int idx, int& ti, int& tj)
-{
-    int r = 0;
-    while ((r + 1) * (r + 2) / 2 <= idx) r++;
-    ti = r;
-    tj = idx - r * (r + 1) / 2;
+#include "append_device.h"
 }
-#include "body.inc"
-
-template <class F> void launch(int blocks, F f)
-{
-    for (int b = 0; b < blocks; b++) {
-        blockIdx.x = b;
-        std::vector<std::thread> th;
-        for (int t = 0; t < 256; t++) th.emplace_back([=] { threadIdx.x = t; f(); });
-        for (auto& x : th) x.join();
-    }
-}
+using namespace cugp;
 
 int main(int argc, char** argv)
 {

@@ -1,5 +1,5 @@
-"""k_append_border and k_append_kinv on the CPU, without a GPU: the kernels' own text (cut out of
-cugp_amd/csrc/kernels.hip) in a lock-step host emulation (tools/append_host_check.cpp) built with
+"""k_append_border and k_append_kinv on the CPU, without a GPU: the kernels' own text (cugp_amd/csrc/append_device.h,
+the header kernels.hip includes) in a lock-step host emulation (tools/append_host_check.cpp) built with
 -fsanitize=address,undefined.  One bordering pass per case: the state of a handle that holds its inverse quantities for r0
 rows is laid out as the library lays it out (identity padding; NaN where the kernels must not read: the rows of P and V
 beyond k, the strict upper tiles of T and the strict lower tiles of U), P, V, C and C^-1 come from numpy, and what the
@@ -10,33 +10,16 @@ shows as NaN, an access beyond a buffer as a sanitizer report.
 """
 import os
 import struct
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import numpy as np  # noqa: E402
+import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-CLANG = os.environ.get("CLANGXX", "/opt/rocm/lib/llvm/bin/clang++")
 # (r0, k): one row to one row; a pass that ends inside the first 64 rows; old rows in the pass's own tile; a fresh tile row;
 # a full tile; r0 no multiple of 32; the last row of the capacity
 CASES = ((1, 1), (5, 40), (127, 1), (128, 128), (130, 126), (200, 56), (300, 84), (255, 1))
-
-
-def build(tmp):
-    src = open(os.path.join(ROOT, "cugp_amd", "csrc", "kernels.hip")).read()
-    i = src.index("constexpr int APB_COLS = 32;")
-    with open(os.path.join(tmp, "body.inc"), "w") as f:
-        body = src[i: src.index("// launchers", i)].rsplit("// ----", 1)[0]
-        # (the dynamic LDS of the tile product: not used by its stand-in)
-        f.write(body.replace("extern __shared__ __attribute__((aligned(16))) char smem[];", "char* smem = nullptr;"))
-    exe = os.path.join(tmp, "host_check")
-    subprocess.check_call([CLANG, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-pthread", "-I", tmp,
-                           os.path.join(ROOT, "tools", "append_host_check.cpp"), "-o", exe])
-    return exe
 
 
 def run(exe, tmp, r0, k):
@@ -80,9 +63,7 @@ def run(exe, tmp, r0, k):
         f.write(struct.pack("3i", r0, k, npad))
         for arr in bufs:
             f.write(np.ascontiguousarray(arr, dtype=np.float64).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    if r.returncode != 0:
-        print(r0, k, "FAILED with", r.returncode, r.stderr[-3000:])
+    if not host_check.execute(exe, fin, fout, r0, k):
         return False
     out = np.fromfile(fout)
     nn = npad * npad
@@ -112,13 +93,5 @@ def run(exe, tmp, r0, k):
     return ok
 
 
-def main():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp)
-        ok = all([run(exe, tmp, *c) for c in CASES])
-    print("ALL OK" if ok else "SOME BAD")
-    return 0 if ok else 1
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(host_check.main("append_host_check", CASES, run))

@@ -1,72 +1,14 @@
 // Host check of trace_ard_body<KIND, false> (k_trace<true, KIND>) and k_predict_grad<true, KIND> (tools/ard_matern_host_check.py builds and runs this; no
-// GPU).  The kernels' own text -- cut out of cugp_amd/csrc/kernels.hip into body.inc by the script -- runs one workgroup at
-// a time as 256 host threads in lock step: a barrier stands for __syncthreads, an exchange array and two barriers for the
-// shuffles (__shfl_down inside a 64-lane wave, __shfl_xor inside 16 lanes).  Every buffer is a heap block of exactly the
+// GPU).  The kernels' own text -- cugp_amd/csrc/cov_device.h, the header kernels.hip includes -- runs behind the emulation
+// shim tools/host_emul.h, one workgroup at a time as 256 host threads in lock step.  Every buffer is a heap block of exactly the
 // size the library gives it, so a build with -fsanitize=address,undefined sees any read or write beyond one; the script
 // poisons all padding of K^-1, alpha and V with NaN, so a missing mask shows in the results.  A stand-alone program: the
 // sanitizer is linked in, nothing is preloaded.
-#include <barrier>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <thread>
-#include <vector>
-#include <functional>
-typedef double d2 __attribute__((ext_vector_type(2)));
-struct Idx { int x = 0, y = 0, z = 0; };
-static thread_local Idx threadIdx;
-static Idx blockIdx, gridDim;
-static std::barrier<> g_bar(256);
-static double g_slot[256];
-#define __device__
-#define __global__
-#define __forceinline__ inline
-#define __restrict__
-#define __launch_bounds__(...)
-#define __shared__ static
-static inline void __syncthreads() { g_bar.arrive_and_wait(); }
-static inline double __shfl_xor(double v, int m, int w)
-{
-    g_slot[threadIdx.x] = v;
-    g_bar.arrive_and_wait();
-    const double r = g_slot[threadIdx.x ^ m];
-    g_bar.arrive_and_wait();
-    return r;
+#include "host_emul.h"
+namespace cugp {
+#include "cov_device.h"
 }
-static inline double __shfl_down(double v, int o, int w)     // (a lane beyond the wave's end keeps its own value)
-{
-    g_slot[threadIdx.x] = v;
-    g_bar.arrive_and_wait();
-    const int lane = threadIdx.x & 63;
-    const double r = lane + o < 64 ? g_slot[threadIdx.x + o] : v;
-    g_bar.arrive_and_wait();
-    return r;
-}
-using std::exp;
-using std::sqrt;
-struct HyperScalars { double ell_sq, signal_var, noise_var; };
-struct ExpertPtrs {
-    double *A, *T, *U, *Kinv, *d16, *d64, *logdet, *y, *z, *alpha, *w, *part, *out;
-    const double* X;
-    unsigned* tickets;
-    int n;
-};
-template <class T> static inline T* GP(T* p) { return p; }
-enum { KERNEL_SE = 0, KERNEL_MATERN32 = 1, KERNEL_MATERN52 = 2 };
-constexpr int KT = 64, DC = 16;
-#include "body.inc"
-
-template <class F> void launch(int blocks, F f)
-{
-    gridDim.x = blocks;
-    for (int b = 0; b < blocks; b++) {
-        blockIdx.x = b;
-        std::vector<std::thread> th;
-        for (int t = 0; t < 256; t++) th.emplace_back([=] { threadIdx.x = t; f(); });
-        for (auto& x : th) x.join();
-    }
-}
+using namespace cugp;
 
 int main(int argc, char** argv)
 {

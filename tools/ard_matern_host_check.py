@@ -1,5 +1,5 @@
-"""The ARD Matern instantiations of trace_ard_body (k_trace<true, KIND>) and k_predict_grad<true, KIND> on the CPU, without a GPU: the kernels' own text (cut out of
-cugp_amd/csrc/kernels.hip) in a lock-step host emulation (tools/ard_matern_host_check.cpp) built with
+"""The ARD Matern instantiations of trace_ard_body (k_trace<true, KIND>) and k_predict_grad<true, KIND> on the CPU, without a GPU: the kernels' own text (cugp_amd/csrc/cov_device.h,
+the header kernels.hip includes) in a lock-step host emulation (tools/ard_matern_host_check.cpp) built with
 -fsanitize=address,undefined, on cases of truth.ARD_CASES.  K^-1, alpha and V are padded as the library pads them, but with
 NaN instead of zeros: a missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  The results are
 compared with the same formulation in fp64 numpy (tests/truth_ard_matern.py) -- equal up to the order of summation:
@@ -11,50 +11,18 @@ compared with the same formulation in fp64 numpy (tests/truth_ard_matern.py) -- 
 """
 import os
 import struct
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import numpy as np  # noqa: E402
+import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-CLANG = os.environ.get("CLANGXX", "/opt/rocm/lib/llvm/bin/clang++")
 # (kernel, case, kind, nt or None for the case's 64 points, with the variance's sums)
 CASES = (("trace", "n65_d2", 1, None, 1), ("trace", "n65_d2", 2, None, 1), ("trace", "n257_d3_shift", 2, None, 1),
          ("trace", "n300_d17", 1, None, 1), ("trace", "n515_d33", 2, None, 1),
          ("grad", "n65_d2", 1, None, 1), ("grad", "n65_d2", 2, None, 0), ("grad", "n257_d3_shift", 2, None, 1),
          ("grad", "n300_d17", 1, None, 1), ("grad", "n515_d33", 2, None, 1), ("grad", "n257_d3", 2, 129, 1))
-
-
-def build(tmp):
-    src = open(os.path.join(ROOT, "cugp_amd", "csrc", "kernels.hip")).read()
-
-    def between(a, b):
-        i = src.index(a)
-        return src[i: src.index(b, i)]
-    with open(os.path.join(tmp, "body.inc"), "w") as f:
-        f.write("\n".join((between("__device__ __forceinline__ void tri_index(", "// Tiles (ti >= tj) of the tile columns"),
-                           between("__device__ __forceinline__ int col4(", "// a / b for many a and one b"),
-                           between("__device__ __forceinline__ const double* ard_weights(", "__device__ __forceinline__ DivBy div_prepare("),
-                           between("__device__ __forceinline__ double wave_sum(", "// z[i] = sum_{k < (ti+1)*128}"),
-                           between("__global__ __launch_bounds__(256) void k_predict_grad_finish(",
-                                   "// Product of experts over the gathered exchange buffer"),
-                           between("constexpr int TGT_CHUNK = 16;", "// what the last block of k_trace needs"),
-                           between("struct DivBy { double b, y; };", "// ARD handles keep the d per-dimension weights"),
-                           between("__device__ __forceinline__ DivBy div_prepare(", "// ---- Matern 3/2 and 5/2 (GPML covMaterniso"),
-                           between("template <int KIND>\n__device__ __forceinline__ void matern_entry(",
-                                   "// the value of one entry without the noise term"),
-                           between("template <int KIND, bool TARGETS>\n__device__ __forceinline__ void trace_ard_body(",
-                                   "// k_trace: the gradient pass of a single-target evaluation"),
-                           between("template <bool ARD, int KIND>\n__device__ __forceinline__ void predict_grad_body(",
-                                   "// dmean[t][c] = -s_c (P_0 + P_1 + ...)"))))
-    exe = os.path.join(tmp, "host_check")
-    subprocess.check_call([CLANG, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-pthread", "-I", tmp,
-                           os.path.join(ROOT, "tools", "ard_matern_host_check.cpp"), "-o", exe])
-    return exe
 
 
 def run(exe, tmp, kernel, name, kind, nt, want_var):
@@ -89,9 +57,7 @@ def run(exe, tmp, kernel, name, kind, nt, want_var):
             arrays += [Xt, Vp, ap]
         for arr in arrays:
             f.write(np.ascontiguousarray(arr, dtype=np.float64).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    if r.returncode != 0 or r.stderr.strip():
-        print(kernel, name, kind, nt, "FAILED with", r.returncode, r.stderr[-3000:])
+    if not host_check.execute(exe, fin, fout, kernel, name, kind, nt):
         return False
     out = np.fromfile(fout)
     if kernel == "trace":
@@ -118,13 +84,5 @@ def run(exe, tmp, kernel, name, kind, nt, want_var):
     return ok
 
 
-def main():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp)
-        ok = all([run(exe, tmp, *c) for c in CASES])
-    print("ALL OK" if ok else "SOME BAD")
-    return 0 if ok else 1
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(host_check.main("ard_matern_host_check", CASES, run))

@@ -1,4 +1,4 @@
-"""The k_predict_grad family on the CPU, without a GPU: the kernels' own text (cut out of cugp_amd/csrc/kernels.hip) in a
+"""The k_predict_grad family on the CPU, without a GPU: the kernels' own text (cugp_amd/csrc/cov_device.h, the header kernels.hip includes) in a
 lock-step host emulation (tools/predict_grad_host_check.cpp) built with -fsanitize=address,undefined, on cases of
 tests/truth_predict_grad.py.  Ks, V and alpha are padded as the library pads them, but with NaN instead of zeros: a
 missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  The results are compared with the same
@@ -8,40 +8,17 @@ formulation in fp64 numpy (tests/truth_predict_grad.py: gradients) -- equal up t
 """
 import os
 import struct
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import numpy as np  # noqa: E402
+import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-CLANG = os.environ.get("CLANGXX", "/opt/rocm/lib/llvm/bin/clang++")
 CASES = (("se", "n2", None, 1), ("se", "n64", None, 1), ("se", "n65", None, 1), ("se", "n65", None, 0),
          ("matern32", "n65", None, 1), ("ard", "n257_d3_shift", None, 1), ("se", "n300_d17", None, 1),
          ("matern52", "n300_d17", None, 1), ("se", "n515_d33", None, 1), ("ard", "n257_d3", 200, 1),
          ("matern52", "n300_d17", 129, 1))
-
-
-def build(tmp):
-    src = open(os.path.join(ROOT, "cugp_amd", "csrc", "kernels.hip")).read()
-
-    def between(a, b):
-        i = src.index(a)
-        return src[i: src.index(b, i)]
-    with open(os.path.join(tmp, "body.inc"), "w") as f:
-        f.write("\n".join((between("__device__ __forceinline__ int col4(", "// a / b for many a and one b"),
-                           between("struct DivBy { double b, y; };", "// ---- Matern 3/2 and 5/2 (GPML covMaterniso"),
-                           between("template <int KIND>\n__device__ __forceinline__ void matern_entry(",
-                                   "// ARD entry from the WEIGHTED squared distance"),
-                           between("template <bool ARD, int KIND>\n__device__ __forceinline__ void predict_grad_body(",
-                                   "// Product of experts over the gathered exchange buffer"))))
-    exe = os.path.join(tmp, "host_check")
-    subprocess.check_call([CLANG, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-pthread", "-I", tmp,
-                           os.path.join(ROOT, "tools", "predict_grad_host_check.cpp"), "-o", exe])
-    return exe
 
 
 def run(exe, tmp, family, name, nt, want_var):
@@ -68,9 +45,7 @@ def run(exe, tmp, family, name, nt, want_var):
         f.write(struct.pack("2d", 1.0 if ard else float(c64.l2), float(c64.sf2)))
         for arr in (X, Xt, Kp, Vp, ap, c64.w if ard else np.ones(d)):
             f.write(np.ascontiguousarray(arr, dtype=np.float64).tobytes())
-    r = subprocess.run([exe, fin, fout], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
-    if r.returncode != 0:
-        print(family, name, nt, "FAILED with", r.returncode, r.stderr[-3000:])
+    if not host_check.execute(exe, fin, fout, family, name, nt):
         return False
     out = np.fromfile(fout)
     dm = out[: nt * d].reshape(nt, d)
@@ -83,13 +58,5 @@ def run(exe, tmp, family, name, nt, want_var):
     return ok
 
 
-def main():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = build(tmp)
-        ok = all([run(exe, tmp, *c) for c in CASES])
-    print("ALL OK" if ok else "SOME BAD")
-    return 0 if ok else 1
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(host_check.main("predict_grad_host_check", CASES, run))
