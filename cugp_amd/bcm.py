@@ -324,6 +324,60 @@ class ShardedBCM:
             spm += out[k, 1]
         return _gp.poe_finish(sp, spm)
 
+    def predict_grad(self, Xt, combine=None, with_noise=True):
+        """(mean [nt], var [nt], dmean [nt, d], dvar [nt, d]) of the combined prediction and its gradients with respect
+        to the test inputs.  combine=None: the reference's product of the experts' noisy predictions
+        (CUGP_COMBINE_REFERENCE; with_noise is not read); "poe" | "gpoe" | "bcm" | "rbcm": the rule on the latent
+        distributions, as predict.  Library form: cugp_bcm_predict_grad_allgather (batched gradient kernels, one
+        all-gather of gradient rows, the chain rule on the device).  Torch forms: every local expert's predict_grad
+        fills its zero-padded [K][2 + 2 d][nt] rows (m, v, dmean^T, dvar^T), the same all-gather / all-reduce as the
+        objective's rows, then poe_combine / poe_finish and poe_combine_grad on the host -- which needs no GPU.
+        self.predict_form says which path ran."""
+        if combine is not None:
+            _gp.combine_mode(combine)                     # an unknown name: ValueError before any library call
+        Xt = np.ascontiguousarray(Xt, dtype=np.float64)
+        if Xt.ndim != 2:
+            raise ValueError("Xt must be [nt, d]")
+        nt, d = Xt.shape
+        sf2, sn2 = _gp.prior_scalars(self.hp)
+        if self._comm is not None:
+            self.predict_form = "library"
+            return self._comm.predict_grad_allgather(self._group, self._per, self.K, Xt, d, combine, with_noise, sf2, sn2)
+        self.predict_form = "torch"
+        w = 2 + 2 * d
+
+        def rows_of(k):
+            m, v, dm, dv = self.local[k].predict_grad(Xt, with_noise=combine is None)
+            r = np.empty((w, nt))
+            r[0], r[1], r[2:2 + d], r[2 + d:] = m, v, np.asarray(dm).T, np.asarray(dv).T
+            return r
+        if self._lean:
+            mine = np.zeros((self._per, w, nt))
+            for i, k in enumerate(self.mine):
+                mine[i] = rows_of(k)
+            g = torch.zeros((self.world * self._per, w, nt), dtype=torch.float64, device=self.comm_device)
+            g = self._allgather(g, torch.from_numpy(mine).to(self.comm_device)).cpu().numpy()
+            out = np.stack([g[gather_row_index(k, self.world, self._per)] for k in range(self.K)])
+        else:
+            buf = np.zeros((self.K, w, nt))
+            for k in self.mine:
+                buf[k] = rows_of(k)
+            out = self._allreduce(torch.from_numpy(buf).to(self.comm_device)).cpu().numpy()
+        m, v = np.ascontiguousarray(out[:, 0]), np.ascontiguousarray(out[:, 1])
+        dm = np.ascontiguousarray(out[:, 2:2 + d].transpose(0, 2, 1))
+        dv = np.ascontiguousarray(out[:, 2 + d:].transpose(0, 2, 1))
+        inv = 1.0 / v
+        if combine is None:
+            sp, spm = np.zeros(nt), np.zeros(nt)
+            for k in range(self.K):                       # expert order, as cugp_bcm_predict_partial
+                sp += inv[k]
+                spm += inv[k] * m[k]
+            mean, var = _gp.poe_finish(sp, spm)
+        else:
+            mean, var = _gp.poe_combine(np.stack([inv, inv * m], axis=1), combine, sf2, sn2, with_noise)
+        dmean, dvar = _gp.poe_combine_grad(m, v, dm, dv, combine, sf2)
+        return mean, var, dmean, dvar
+
     def objective(self, theta):
         self.set_loghyper(theta)
         ll, g, _ = self.loglik_grad()

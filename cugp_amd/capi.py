@@ -134,6 +134,9 @@ SIGNATURES = {
     "cugp_bcm_predict_mode": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "cugp_poe_combine_grad": (C.c_int, [_dp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _dp, _dp]),
     "cugp_bcm_predict_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "cugp_bcm_predict_grad_form": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_bcm_predict_grad_allgather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
     "cugp_bcm_predict_allgather_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, C.c_int, C.c_int,
                                                   C.c_double, C.c_double, _dp, _dp]),
     "cugp_bcm_create_ard": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.POINTER(C.c_void_p)]),

@@ -26,6 +26,13 @@ struct DeviceSet {
     std::vector<int> idx;            // global expert indices, ascending
     cugp_group* group = nullptr;     // null: a single expert, or shapes differ
     bool grouped_now = false;        // the evaluation in flight was enqueued as a group
+    // cugp_bcm_predict_grad: the set's gradient rows on its device ([local expert][(2 + 2 d) nt]) and, for the experts that
+    // cannot share launches, the stream ordered behind all of theirs (created on first use)
+    Scratch grad_rows;
+    hipStream_t grad_stream = nullptr;
+    // "rows written" per LOCAL expert whose stream wrote some (set_order_after): created on this set's device, so an
+    // event only ever meets streams of the device it was created on
+    std::vector<hipEvent_t> ev;
 };
 
 struct cugp_bcm {
@@ -44,7 +51,8 @@ struct cugp_bcm {
     // world of one), its output [mean nt | var nt | status, count] on the device and pinned, the stream they run on
     Scratch mode_rows, mode_out, mode_hout{nullptr, 0, true};
     hipStream_t mode_stream = nullptr;
-    std::vector<hipEvent_t> pred_ev; // cugp_bcm_predict_rows_enqueue: "rows written" per stream that wrote some
+    Scratch grad_host{nullptr, 0, true};   // pinned: cugp_bcm_predict_grad's rows, set after set
+    int grad_form = 0;               // cugp_bcm_predict_grad_form: 0 no call yet, 1 expert by expert, 2 every set as a group
 };
 
 namespace {
@@ -241,10 +249,16 @@ int cugp_bcm_create_split(const double* X, const double* y, int N, int D, int K,
 int cugp_bcm_destroy(cugp_bcm* b)
 {
     if (!b) return CUGP_OK;
-    for (DeviceSet& ds : b->sets) cugp_group_destroy(ds.group);
+    for (DeviceSet& ds : b->sets) {
+        if (ds.grad_rows.p || ds.grad_stream || !ds.ev.empty()) (void)hipSetDevice(ds.device);
+        for (hipEvent_t e : ds.ev) (void)hipEventDestroy(e);
+        if (ds.grad_stream) { (void)hipStreamSynchronize(ds.grad_stream); (void)hipStreamDestroy(ds.grad_stream); }
+        ds.grad_rows.release();
+        cugp_group_destroy(ds.group);
+    }
+    b->grad_host.release();
     for (cugp_gp* g : b->experts) cugp_destroy(g);
     b->pred_host.release();
-    for (hipEvent_t e : b->pred_ev) (void)hipEventDestroy(e);
     if (b->mode_stream) (void)hipStreamSynchronize(b->mode_stream);
     for (Scratch* sc : {&b->mode_rows, &b->mode_out, &b->mode_hout}) sc->release();
     if (b->mode_stream) (void)hipStreamDestroy(b->mode_stream);
@@ -314,6 +328,7 @@ int cugp_bcm_num_hyper(const cugp_bcm* b, int* nh)
 }
 
 int cugp_bcm_nh(const cugp_bcm* b) { return b ? b->nh : 0; }
+int cugp_bcm_dim(const cugp_bcm* b) { return b ? b->d : 0; }
 int cugp_bcm_is_ard(const cugp_bcm* b) { return b && b->ard ? 1 : 0; }
 
 int cugp_bcm_set_loghyper_ard(cugp_bcm* b, const double* hp, int nh)
@@ -594,6 +609,23 @@ int cugp_bcm_predict_partial(cugp_bcm* b, const double* Xt, int nt, double* sum_
     return CUGP_OK;
 }
 
+// "rows written" on `stream` -> `wait_stream` waits for it.  Event `local` of the device set (its local expert index),
+// created on first use with the SET's device current -- the caller's state -- so it is only ever recorded on streams of
+// the device it belongs to, whatever the device list.  Shared by every row producer of the BCM.
+static int set_order_after(DeviceSet& ds, size_t local, void* stream, void* wait_stream)
+{
+    while (ds.ev.size() <= local) {
+        hipEvent_t ev = nullptr;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
+            return cugp_internal_fail(CUGP_ERR_DEVICE, "hipEventCreateWithFlags");
+        ds.ev.push_back(ev);
+    }
+    if (hipEventRecord(ds.ev[local], (hipStream_t)stream) != hipSuccess ||
+        hipStreamWaitEvent((hipStream_t)wait_stream, ds.ev[local], 0) != hipSuccess)
+        return cugp_internal_fail(CUGP_ERR_DEVICE, "hipEventRecord / hipStreamWaitEvent (prediction rows)");
+    return CUGP_OK;
+}
+
 // The rows of cugp_bcm_predict_allgather (comm.cpp) for the experts of this handle, local order = global order of the
 // handle.  As cugp_bcm_predict_partial: stale experts first brought up to date by ONE evaluation of the whole model.
 // Then the experts of the device predict as ONE group of batched launches where they can, else each on its own stream
@@ -615,29 +647,17 @@ int cugp_bcm_predict_rows_enqueue_form(cugp_bcm* b, int device, const double* Xt
     DeviceSet& ds = b->sets[0];
     const size_t n = ds.idx.size();
     if (hipSetDevice(device) != hipSuccess) return cugp_internal_fail(CUGP_ERR_DEVICE, "hipSetDevice");
-    auto order_after = [&](size_t slot, void* stream) -> int {
-        while (b->pred_ev.size() <= slot) {
-            hipEvent_t ev = nullptr;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess)
-                return cugp_internal_fail(CUGP_ERR_DEVICE, "hipEventCreateWithFlags");
-            b->pred_ev.push_back(ev);
-        }
-        if (hipEventRecord(b->pred_ev[slot], (hipStream_t)stream) != hipSuccess ||
-            hipStreamWaitEvent((hipStream_t)wait_stream, b->pred_ev[slot], 0) != hipSuccess)
-            return cugp_internal_fail(CUGP_ERR_DEVICE, "hipEventRecord / hipStreamWaitEvent (prediction rows)");
-        return CUGP_OK;
-    };
     if (ds.group) {
         void* s = nullptr;
         rc = cugp_group_predict_enqueue_form(ds.group, Xt, nt, dsend, slot_stride, &s, latent);
-        if (rc == CUGP_OK) return order_after(0, s);
+        if (rc == CUGP_OK) return set_order_after(ds, 0, s, wait_stream);
         if (rc != CUGP_ERR_INVALID) return rc;               // INVALID: not possible as a group right now
     }
     for (size_t i = 0; i < n; i++) {
         void* s = nullptr;
         if ((rc = cugp_predict_rows_enqueue_form(b->experts[ds.idx[i]], Xt, nt, dsend + i * slot_stride, &s, latent)))
             return rc;
-        if ((rc = order_after(i, s))) return rc;
+        if ((rc = set_order_after(ds, i, s, wait_stream))) return rc;
     }
     return CUGP_OK;
 }
@@ -846,26 +866,126 @@ int cugp_poe_combine_grad(const double* mean, const double* var, const double* d
     return CUGP_OK;
 }
 
-// cugp_predict_grad expert by expert (each on its own device: a BCM over several devices of one process works), then the
-// rule on the host.  mode >= 0: the experts' latent distributions through rows made as poe_row makes them and
-// cugp_poe_combine; CUGP_COMBINE_REFERENCE: their noisy predictions through the two sums of cugp_bcm_predict_partial and
-// cugp_poe_finish (with_noise is then not read).  Stale experts are refreshed first, as every BCM prediction does.
+// The gradient rows of one device set (its device current), local expert i's at drows + i * slot_stride: ONE group of
+// batched launches where the experts can run as one (*grouped), else each expert on its own stream.  *done: the stream
+// behind which every row is written -- wait_stream, ordered behind the writers by events; wait_stream null: the group's
+// own stream, or (expert by expert) the set's grad_stream, created here.  No host wait.
+static int set_grad_rows_enqueue(cugp_bcm* b, DeviceSet& ds, const double* Xt, int nt, double* drows, size_t slot_stride,
+                                 int latent, int want_dvar, void* wait_stream, void** done, bool* grouped)
+{
+    int rc;
+    *grouped = false;
+    if (ds.group) {
+        void* s = nullptr;
+        rc = cugp_group_predict_grad_enqueue(ds.group, Xt, nt, drows, slot_stride, &s, latent, want_dvar);
+        if (rc == CUGP_OK) {
+            *grouped = true;
+            *done = wait_stream ? wait_stream : s;
+            return wait_stream ? set_order_after(ds, 0, s, wait_stream) : CUGP_OK;
+        }
+        if (rc != CUGP_ERR_INVALID) return rc;               // INVALID: not possible as a group right now
+    }
+    if (!wait_stream) {
+        if (!ds.grad_stream && hipStreamCreateWithFlags(&ds.grad_stream, hipStreamNonBlocking) != hipSuccess)
+            return cugp_internal_fail(CUGP_ERR_DEVICE, "hipStreamCreateWithFlags (cugp_bcm_predict_grad)");
+        wait_stream = ds.grad_stream;
+    }
+    *done = wait_stream;
+    for (size_t i = 0; i < ds.idx.size(); i++) {
+        void* s = nullptr;
+        if ((rc = cugp_predict_grad_rows_enqueue(b->experts[ds.idx[i]], Xt, nt, drows + i * slot_stride, &s, latent, want_dvar)))
+            return rc;
+        if ((rc = set_order_after(ds, i, s, wait_stream))) return rc;
+    }
+    return CUGP_OK;
+}
+
+// cugp_bcm_predict_rows_enqueue_form with gradient rows ([m nt | v nt | dmean nt d | dvar nt d] per slot): the BCM's side of
+// cugp_bcm_predict_grad_allgather (comm.cpp).  cugp_bcm_predict_rows_finish waits for the experts' streams.
+int cugp_bcm_predict_grad_rows_enqueue(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend,
+                                       size_t slot_stride, void* wait_stream, int latent, int want_dvar)
+{
+    if (!b || !Xt || nt <= 0 || !dsend || !wait_stream) return CUGP_ERR_INVALID;
+    if (b->sets.size() != 1 || b->sets[0].device != device)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_grad_allgather: the BCM's experts are not all on the communicator's device");
+    int rc;
+    if ((rc = bcm_refresh(b))) return rc;
+    if (hipSetDevice(device) != hipSuccess) return cugp_internal_fail(CUGP_ERR_DEVICE, "hipSetDevice");
+    void* done = nullptr;
+    bool grouped = false;
+    rc = set_grad_rows_enqueue(b, b->sets[0], Xt, nt, dsend, slot_stride, latent, want_dvar, wait_stream, &done, &grouped);
+    if (rc == CUGP_OK) b->grad_form = grouped ? 2 : 1;
+    return rc;
+}
+
+int cugp_bcm_predict_grad_form(const cugp_bcm* b, int* form)
+{
+    if (!b || !form) return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_grad_form: null argument");
+    *form = b->grad_form;
+    return CUGP_OK;
+}
+
+// Every expert's gradient rows [m nt | v nt | dmean nt d | dvar nt d] in flight before the first wait: per device set ONE
+// group of batched launches (cugp_group_predict_grad_enqueue) where its experts can run as one, else expert by expert on
+// their own streams (cugp_predict_grad_rows_enqueue), and one copy per set into pinned host memory behind them -- a BCM
+// over several devices of one process works.  Then the rule on the host, exactly as before the batched path: mode >= 0:
+// the experts' latent distributions through rows made as poe_row makes them and cugp_poe_combine;
+// CUGP_COMBINE_REFERENCE: their noisy predictions through the two sums of cugp_bcm_predict_partial and cugp_poe_finish
+// (with_noise is then not read); cugp_poe_combine_grad for the gradients -- which reads every expert's dvar for the
+// mean's gradient too, so the experts' V = W L^-1 is always computed.  Stale experts are refreshed first, as every BCM
+// prediction does.
 int cugp_bcm_predict_grad(cugp_bcm* b, const double* Xt, int nt, int mode, int with_noise, double* mean, double* var,
                           double* dmean, double* dvar)
 {
     if (!b || !Xt || nt <= 0 || (!dmean && !dvar) || mode < CUGP_COMBINE_REFERENCE || mode > CUGP_COMBINE_RBCM)
         return cugp_internal_fail(CUGP_ERR_INVALID,
                                   "cugp_bcm_predict_grad: null BCM or Xt, nt <= 0, neither dmean nor dvar given, or an unknown mode");
-    const size_t K = b->experts.size(), d = (size_t)b->d, n1 = (size_t)nt, nd = n1 * d;
+    const size_t K = b->experts.size(), d = (size_t)b->d, n1 = (size_t)nt, nd = n1 * d, slot = 2 * n1 + 2 * nd;
     const bool reference = mode == CUGP_COMBINE_REFERENCE;
     double sf2, sn2;
     int rc;
-    if ((rc = cugp_bcm_prior_scalars(b, &sf2, &sn2)) || (rc = bcm_refresh(b))) return rc;
+    if ((rc = cugp_bcm_prior_scalars(b, &sf2, &sn2)) || (rc = bcm_refresh(b)) || (rc = b->grad_host.grow(K * slot, nullptr)))
+        return rc;
+    const size_t nsets = b->sets.size();
+    std::vector<void*> done(nsets, nullptr);
+    std::vector<size_t> first(nsets, 0);                   // the set's first slot in the pinned buffer
+    bool all_grouped = true;
+    size_t enq = 0, off = 0;
+    for (; enq < nsets && rc == CUGP_OK; enq++) {
+        DeviceSet& ds = b->sets[enq];
+        first[enq] = off;
+        off += ds.idx.size();
+        if (hipSetDevice(ds.device) != hipSuccess) { rc = cugp_internal_fail(CUGP_ERR_DEVICE, "hipSetDevice"); break; }
+        if ((rc = ds.grad_rows.grow(ds.idx.size() * slot, nullptr))) break;
+        bool grouped = false;
+        rc = set_grad_rows_enqueue(b, ds, Xt, nt, ds.grad_rows.p, slot, reference ? 0 : 1, 1, nullptr, &done[enq], &grouped);
+        all_grouped = all_grouped && grouped;
+        if (rc == CUGP_OK && hipMemcpyAsync(b->grad_host.p + first[enq] * slot, ds.grad_rows.p, ds.idx.size() * slot * sizeof(double),
+                                            hipMemcpyDeviceToHost, (hipStream_t)done[enq]) != hipSuccess)
+            rc = cugp_internal_fail(CUGP_ERR_DEVICE, "hipMemcpyAsync (cugp_bcm_predict_grad)");
+    }
+    // the waits: every set's copy, then every expert's own stream (already done: closes its profiling events) -- after a
+    // failure too, so that nothing enqueued still writes rows when the call returns
+    for (size_t si = 0; si < nsets; si++)
+        if (done[si] && (hipSetDevice(b->sets[si].device) != hipSuccess || hipStreamSynchronize((hipStream_t)done[si]) != hipSuccess) &&
+            rc == CUGP_OK)
+            rc = cugp_internal_fail(CUGP_ERR_DEVICE, "hipStreamSynchronize (cugp_bcm_predict_grad)");
+    for (cugp_gp* e : b->experts) {
+        const int rf = cugp_predict_fetch(e);
+        if (rf && rc == CUGP_OK) rc = rf;
+    }
+    if (rc) return rc;
+    b->grad_form = all_grouped ? 2 : 1;
     std::vector<double> m(K * n1), v(K * n1), dm(K * nd), dv(K * nd), rows(K * 2 * n1), om(n1), ov(n1), odm(nd), odv(nd);
-    for (size_t k = 0; k < K; k++)
-        if ((rc = cugp_predict_grad(b->experts[k], Xt, nt, reference ? 1 : 0, m.data() + k * n1, v.data() + k * n1,
-                                    dm.data() + k * nd, dv.data() + k * nd)))
-            return rc;
+    for (size_t si = 0; si < nsets; si++)
+        for (size_t i = 0; i < b->sets[si].idx.size(); i++) {  // expert order for the host sums
+            const size_t k = (size_t)b->sets[si].idx[i];
+            const double* r = b->grad_host.p + (first[si] + i) * slot;
+            memcpy(m.data() + k * n1, r, n1 * sizeof(double));
+            memcpy(v.data() + k * n1, r + n1, n1 * sizeof(double));
+            memcpy(dm.data() + k * nd, r + 2 * n1, nd * sizeof(double));
+            memcpy(dv.data() + k * nd, r + 2 * n1 + nd, nd * sizeof(double));
+        }
     if (reference) {
         std::vector<double> sp(n1, 0.0), spm(n1, 0.0);
         for (size_t k = 0; k < K; k++)

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <new>
 #include <string>
@@ -87,7 +88,7 @@ struct cugp_comm {
     // product-of-experts prediction (cugp_bcm_predict_allgather): this rank's block, everybody's, the reduced
     // [mean | var | status words] on the device and pinned, the pinned header {status, local count}
     hipStream_t stream = nullptr;                // the exchange's own stream on `device`
-    Scratch pdsend, pdrecv, pdout, phout{nullptr, 0, true};
+    Scratch pdsend, pdrecv, pdout, phout{nullptr, 0, true};   // (the gradient form's are the same buffers, wider)
     double* phdr = nullptr;
 };
 
@@ -239,38 +240,55 @@ static int pred_buffers(cugp_comm* c, size_t rstride, size_t nout)
     return CUGP_OK;
 }
 
-static void fill_nan(double* mean, double* var, int nt)
-{
-    for (int i = 0; i < nt; i++) mean[i] = var[i] = NAN;
-}
+// the outputs of a failed call: NaN, every one that was asked for (grad: dmean / dvar of nd entries each)
+struct PredOut {
+    double *mean, *var, *dmean, *dvar;
+    size_t nt, nd;
+    void fill_nan() const
+    {
+        for (size_t i = 0; i < nt; i++) { if (mean) mean[i] = NAN; if (var) var[i] = NAN; }
+        for (size_t i = 0; i < nd; i++) { if (dmean) dmean[i] = NAN; if (dvar) dvar[i] = NAN; }
+    }
+};
 
 // Product-of-experts prediction of a BCM sharded one process per GPU (include/cugp.h).  Every rank sends
-// {status, local expert count, [per][2][nt] rows (1/v, m/v of its i-th expert in slot i)} -- the same count on every
+// {status, local expert count, [per] slots (its i-th expert's rows in slot i)} -- the same count on every
 // rank -- by ONE ncclAllGather on the communicator's own stream, which the prediction kernels' streams are ordered in
-// front of by events; k_poe_reduce sums every test point over the experts in global order, one copy brings mean,
-// variance and the ranks' status words into pinned memory, and the host waits ONCE.  A local failure still joins the
+// front of by events; the reduce kernel combines every test point over the experts in global order, one copy brings the
+// results and the ranks' status words into pinned memory, and the host waits ONCE.  A local failure still joins the
 // collective (nonzero status, NaN rows), so every rank reads every rank's status and all return the same code.
-// The body of both public calls (`call`: the name in the error texts).  mode < 0: cugp_bcm_predict_allgather -- noisy rows,
-// k_poe_reduce.  mode >= 0 (CUGP_COMBINE_*): cugp_bcm_predict_allgather_mode -- latent rows (the same launches, noise_var
-// = 0 in the finish), k_poe_reduce_mode with sf2, sn2, with_noise; everything else is the same sequence.
-static int predict_allgather(const char* call, cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt,
-                             int mode, int with_noise, double sf2, double sn2, double* mean, double* var)
+// The ONE body of the three public calls (`call`: the name in the error texts), parameterised by a PredForm: the slot
+// width, how this rank's experts fill their slots, and the reduce launch.
+//   cugp_bcm_predict_allgather        slots [2][nt] (1/v, m/v of the noisy prediction), k_poe_reduce
+//   cugp_bcm_predict_allgather_mode   the same slots of the latent rows (the same launches, noise_var = 0 in the
+//                                     finish), k_poe_reduce_mode with sf2, sn2, with_noise
+//   cugp_bcm_predict_grad_allgather   slots [m nt | v nt | dmean nt d | dvar nt d] (latent for mode >= 0, noisy for
+//                                     CUGP_COMBINE_REFERENCE), k_poe_reduce_grad; o.mean / o.var may be null
+// The reduce kernel's output is [slot-independent results, `words` doubles | world x {status, count}].
+// The caller has checked the arguments every rank checks alike.
+struct PredForm {
+    size_t slot;                                       // doubles per expert in a rank's block
+    size_t words;                                      // doubles of results in front of the status words
+    // this rank's experts' rows into dsend (slot i at dsend + i * slot), *stream (the communicator's own) ordered behind them
+    std::function<int(cugp_bcm* b, int device, double* dsend, void** stream)> enqueue;
+    // gathered [world][rstride] -> dout on stream
+    std::function<int(const double* src, size_t rstride, int world, double* dout, void* stream)> reduce;
+};
+
+static int predict_allgather(const char* call, cugp_bcm* b, cugp_comm* c, int per, int nexperts, int nt,
+                             const PredForm& f, const PredOut& o)
 {
     char buf[512];
-    // what every rank detects identically from the shared arguments: no collective
-    if (!c || per <= 0 || nexperts <= 0 || nt <= 0 || !Xt || !mean || !var || (long long)per * c->world < nexperts) {
-        snprintf(buf, sizeof buf, "%s: bad argument", call);
-        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
-    }
     hipError_t e = hipSetDevice(c->device);
     if (e != hipSuccess) return hip_fail("hipSetDevice", e);
-    const size_t rstride = 2 + (size_t)per * 2 * nt, nout = 2 * (size_t)nt + 2 * (size_t)c->world;
+    const size_t words = f.words, rstride = 2 + (size_t)per * f.slot, nout = words + 2 * (size_t)c->world;
     int rc = pred_buffers(c, rstride, nout);
     if (rc) return rc;                                 // (no send buffer: this rank cannot take part)
     // ---- this rank's block; from here on every failure becomes the status word
     const int expect = c->rank < nexperts ? (nexperts - c->rank + c->world - 1) / c->world : 0;
     int nlocal = 0, status = CUGP_OK;
     bool enqueued = false;
+    void* sv = (void*)c->stream;                       // the exchange's stream: PredForm::enqueue orders it behind the rows
     if (b && cugp_bcm_num_experts(b, &nlocal)) status = CUGP_ERR_INVALID;
     if (status == CUGP_OK && nlocal != expect) {
         snprintf(buf, sizeof buf, "%s: rank %d holds %d experts, %d of %d expected", call, c->rank,
@@ -279,71 +297,101 @@ static int predict_allgather(const char* call, cugp_bcm* b, cugp_comm* c, int pe
     }
     if (status == CUGP_OK && nlocal > 0) {
         enqueued = true;
-        status = cugp_bcm_predict_rows_enqueue_form(b, c->device, Xt, nt, c->pdsend.p + 2, 2 * (size_t)nt, c->stream,
-                                                    mode >= 0 ? 1 : 0);
+        status = f.enqueue(b, c->device, c->pdsend.p + 2, &sv);
     }
+    const hipStream_t st = (hipStream_t)sv;
     if (status != CUGP_OK) {
         if (enqueued) (void)cugp_bcm_predict_rows_finish(b);   // nothing enqueued still writes into the send buffer
-        e = hipMemsetAsync(c->pdsend.p + 2, 0xff, (rstride - 2) * sizeof(double), c->stream);   // all-ones: NaN rows
+        e = hipMemsetAsync(c->pdsend.p + 2, 0xff, (rstride - 2) * sizeof(double), st);   // all-ones: NaN rows
         (void)e;
     }
     c->phdr[0] = (double)status;                       // (pinned, read by the copy below before the host waits)
     c->phdr[1] = (double)nlocal;
-    e = hipMemcpyAsync(c->pdsend.p, c->phdr, 2 * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    e = hipMemcpyAsync(c->pdsend.p, c->phdr, 2 * sizeof(double), hipMemcpyHostToDevice, st);
     if (e != hipSuccess && status == CUGP_OK) status = hip_fail("hipMemcpyAsync (status word)", e);
     // ---- the exchange
     const double* src = c->pdsend.p;                   // a world of one without an id: this rank's block is all of them
     if (c->comm) {
-        const ncclResult_t r = rccl().AllGather(c->pdsend.p, c->pdrecv.p, rstride, ncclDouble, c->comm, c->stream);
+        const ncclResult_t r = rccl().AllGather(c->pdsend.p, c->pdrecv.p, rstride, ncclDouble, c->comm, st);
         if (r != ncclSuccess) {
             if (enqueued) (void)cugp_bcm_predict_rows_finish(b);
-            (void)hipStreamSynchronize(c->stream);
-            fill_nan(mean, var, nt);
+            (void)hipStreamSynchronize(st);
+            o.fill_nan();
             return nccl_fail("ncclAllGather", r);
         }
         src = c->pdrecv.p;
     }
-    rc = mode < 0 ? cugp_poe_reduce_enqueue(src, rstride, c->world, nexperts, nt, c->pdout.p, c->stream)
-                  : cugp_poe_reduce_mode_enqueue(src, rstride, c->world, nexperts, nt, mode, sf2, sn2, with_noise ? 1 : 0,
-                                                 c->pdout.p, c->stream);
+    rc = f.reduce(src, rstride, c->world, c->pdout.p, st);
     if (rc == CUGP_OK) {
-        e = hipMemcpyAsync(c->phout.p, c->pdout.p, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(c->phout.p, c->pdout.p, nout * sizeof(double), hipMemcpyDeviceToHost, st);
         if (e != hipSuccess) rc = hip_fail("hipMemcpyAsync (prediction)", e);
     }
-    e = hipStreamSynchronize(c->stream);               // the one host wait: prediction, collective, reduction, copy
+    e = hipStreamSynchronize(st);               // the one host wait: prediction, collective, reduction, copy
     if (e != hipSuccess && rc == CUGP_OK) rc = hip_fail("hipStreamSynchronize", e);
     if (enqueued && status == CUGP_OK) status = cugp_bcm_predict_rows_finish(b);   // (streams already done: closes them)
-    if (rc) { fill_nan(mean, var, nt); return rc; }
+    if (rc) { o.fill_nan(); return rc; }
     // ---- every rank reads every rank's status word: the same verdict everywhere
     const double* h = c->phout.p;
     long long total = 0;
     for (int r = 0; r < c->world; r++) {
-        const int st = (int)h[2 * (size_t)nt + 2 * r];
+        const int st = (int)h[words + 2 * r];
         if (st != CUGP_OK) {
             if (r == c->rank) {
                 const std::string last = cugp_last_error();
                 snprintf(buf, sizeof buf, "%s: rank %d failed (%d): %s", call, r, st, last.c_str());
             } else snprintf(buf, sizeof buf, "%s: rank %d failed (%d)", call, r, st);
-            fill_nan(mean, var, nt);
+            o.fill_nan();
             return cugp_internal_fail(st, buf);
         }
-        total += (long long)h[2 * (size_t)nt + 2 * r + 1];
+        total += (long long)h[words + 2 * r + 1];
     }
     if (total != nexperts) {
         snprintf(buf, sizeof buf, "%s: the ranks hold %lld experts, %d expected", call, total, nexperts);
-        fill_nan(mean, var, nt);
+        o.fill_nan();
         return cugp_internal_fail(CUGP_ERR_INVALID, buf);
     }
-    if (status != CUGP_OK) { fill_nan(mean, var, nt); return status; }   // (a failure while closing this rank's streams)
-    memcpy(mean, h, (size_t)nt * sizeof(double));
-    memcpy(var, h + nt, (size_t)nt * sizeof(double));
+    if (status != CUGP_OK) { o.fill_nan(); return status; }   // (a failure while closing this rank's streams)
+    if (o.mean) memcpy(o.mean, h, (size_t)nt * sizeof(double));
+    if (o.var) memcpy(o.var, h + nt, (size_t)nt * sizeof(double));
+    if (o.dmean) memcpy(o.dmean, h + 2 * (size_t)nt, o.nd * sizeof(double));
+    if (o.dvar) memcpy(o.dvar, h + 2 * (size_t)nt + o.nd, o.nd * sizeof(double));
     return CUGP_OK;
+}
+
+// what every rank detects identically from the shared arguments of the two prediction calls: no collective
+static int predict_args(const char* call, const cugp_comm* c, int per, int nexperts, const double* Xt, int nt,
+                        const double* mean, const double* var)
+{
+    if (!c || per <= 0 || nexperts <= 0 || nt <= 0 || !Xt || !mean || !var || (long long)per * c->world < nexperts) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "%s: bad argument", call);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    return CUGP_OK;
+}
+
+// the two prediction forms: slots [2][nt]; mode < 0 the noisy rows and k_poe_reduce, else latent rows and k_poe_reduce_mode
+static PredForm rows_form(const double* Xt, int nt, int nexperts, int mode, int with_noise, double sf2, double sn2)
+{
+    PredForm f;
+    f.slot = f.words = 2 * (size_t)nt;
+    f.enqueue = [=](cugp_bcm* b, int device, double* dsend, void** ws) {
+        return cugp_bcm_predict_rows_enqueue_form(b, device, Xt, nt, dsend, 2 * (size_t)nt, *ws, mode >= 0 ? 1 : 0);
+    };
+    f.reduce = [=](const double* src, size_t rstride, int world, double* dout, void* stream) {
+        return mode < 0 ? cugp_poe_reduce_enqueue(src, rstride, world, nexperts, nt, dout, stream)
+                        : cugp_poe_reduce_mode_enqueue(src, rstride, world, nexperts, nt, mode, sf2, sn2, with_noise ? 1 : 0,
+                                                       dout, stream);
+    };
+    return f;
 }
 
 int cugp_bcm_predict_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt, double* mean,
                                double* var)
 {
-    return predict_allgather("cugp_bcm_predict_allgather", b, c, per, nexperts, Xt, nt, -1, 0, 0.0, 0.0, mean, var);
+    if (const int rc = predict_args("cugp_bcm_predict_allgather", c, per, nexperts, Xt, nt, mean, var)) return rc;
+    return predict_allgather("cugp_bcm_predict_allgather", b, c, per, nexperts, nt, rows_form(Xt, nt, nexperts, -1, 0, 0.0, 0.0),
+                             PredOut{mean, var, nullptr, nullptr, (size_t)nt, 0});
 }
 
 // the same exchange with latent rows and k_poe_reduce_mode; sf2, sn2 are arguments: a rank without experts has no BCM
@@ -352,8 +400,44 @@ int cugp_bcm_predict_allgather_mode(cugp_bcm* b, cugp_comm* c, int per, int nexp
 {
     if (mode < CUGP_COMBINE_POE || mode > CUGP_COMBINE_RBCM)
         return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_predict_allgather_mode: unknown mode");
-    return predict_allgather("cugp_bcm_predict_allgather_mode", b, c, per, nexperts, Xt, nt, mode, with_noise, sf2, sn2,
-                             mean, var);
+    if (const int rc = predict_args("cugp_bcm_predict_allgather_mode", c, per, nexperts, Xt, nt, mean, var)) return rc;
+    return predict_allgather("cugp_bcm_predict_allgather_mode", b, c, per, nexperts, nt,
+                             rows_form(Xt, nt, nexperts, mode, with_noise, sf2, sn2),
+                             PredOut{mean, var, nullptr, nullptr, (size_t)nt, 0});
+}
+
+// The test-input gradients of the combined prediction across the ranks (include/cugp.h): the same exchange with gradient
+// rows and k_poe_reduce_grad.  d, sf2 and sn2 are arguments: a rank without experts has no BCM.
+int cugp_bcm_predict_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexperts, const double* Xt, int nt, int d,
+                                    int mode, int with_noise, double sf2, double sn2, double* mean, double* var,
+                                    double* dmean, double* dvar)
+{
+    const char* why = nullptr;
+    if (!c || !Xt) why = "null communicator or Xt";
+    else if (nt <= 0 || d <= 0 || per <= 0 || nexperts <= 0) why = "nt, d, per or nexperts <= 0";
+    else if ((long long)per * c->world < nexperts) why = "per * world < nexperts";
+    else if (mode < CUGP_COMBINE_REFERENCE || mode > CUGP_COMBINE_RBCM) why = "unknown mode";
+    else if (!dmean && !dvar) why = "neither dmean nor dvar given";
+    else if (b && cugp_bcm_dim(b) != d) why = "d is not the BCM's input dimension";
+    if (why) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "cugp_bcm_predict_grad_allgather: %s", why);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    // The experts' dvar is always asked for: the chain rule reads it for the mean's gradient in every mode.  A NULL dvar
+    // only keeps the reduce kernel from writing, and the call from returning, the combined one.
+    PredForm f;
+    f.slot = f.words = (2 + 2 * (size_t)d) * nt;
+    const int want_out = dvar ? 1 : 0;
+    f.enqueue = [=](cugp_bcm* bb, int device, double* dsend, void** ws) {
+        return cugp_bcm_predict_grad_rows_enqueue(bb, device, Xt, nt, dsend, (2 + 2 * (size_t)d) * nt, *ws, mode >= 0 ? 1 : 0, 1);
+    };
+    f.reduce = [=](const double* src, size_t rstride, int world, double* dout, void* stream) {
+        return cugp_poe_reduce_grad_enqueue(src, rstride, world, nexperts, nt, d, mode, sf2, sn2, with_noise ? 1 : 0, want_out,
+                                            dout, stream);
+    };
+    return predict_allgather("cugp_bcm_predict_grad_allgather", b, c, per, nexperts, nt, f,
+                             PredOut{mean, var, dmean, dvar, (size_t)nt, (size_t)nt * d});
 }
 
 }  // extern "C"

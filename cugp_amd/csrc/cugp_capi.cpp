@@ -1531,12 +1531,13 @@ int cugp_predict_latent(cugp_gp* g, const double* Xt, int nt, double* mean, doub
 // ---------------------------------------------------------------- gradients with respect to the test inputs
 // Test points per pass of cugp_predict_grad: tuning key TUNE_PRED_CHUNK in 64-row tiles, or (0) as many as keep Ks, W, V
 // and the tiles' partial sums of one pass within 1 GiB, in whole 128-row tiles.  Every test row is computed on its own,
-// so the bits do not depend on it.
-static int grad_chunk_rows(const cugp_gp* g, int nt)
+// so the bits do not depend on it.  count, tiles: the experts that share the pass (and the budget) and the most 64-row
+// training tiles of any of them; one handle: 1 and its own.
+static int grad_chunk_rows(const cugp_gp* g, int nt, int count, int tiles)
 {
     long long rows = (long long)g->tune[TUNE_PRED_CHUNK] * 64;
     if (rows <= 0) {
-        const size_t per_row = ((size_t)3 * g->npad + (size_t)2 * predict_grad_tiles(g->n) * g->d) * sizeof(double);
+        const size_t per_row = (size_t)count * ((size_t)3 * g->npad + (size_t)2 * tiles * g->d) * sizeof(double);
         rows = (long long)((((size_t)1 << 30) / per_row) / TILE) * TILE;
         if (rows < TILE) rows = TILE;
     }
@@ -1544,53 +1545,63 @@ static int grad_chunk_rows(const cugp_gp* g, int nt)
     return (int)(rows < ntr ? rows : ntr);
 }
 
-// mean, variance and their gradients with respect to the test inputs (include/cugp.h).  Per pass of test points on the
-// handle's stream: k_cross, k_predict_gemm, k_predict_finish exactly as predict_passes launches them (the mean's and the
-// variance's bits are cugp_predict's / cugp_predict_latent's), then -- dvar wanted -- V = W L^-1 by launch_targets_alpha,
-// k_predict_grad (partial sums per training tile) and k_predict_grad_finish.  One path whatever else the handle holds: V
-// is always W L^-1, never Ks K^-1.  All results stay in the scratch until the one copy and the one host wait at the end.
-int cugp_predict_grad(cugp_gp* g, const double* Xt, int nt, int with_noise, double* mean, double* var, double* dmean,
-                      double* dvar)
+// Mean, variance and their gradients with respect to the test inputs on g's stream, left on the device as ROWS
+//   [m nt | v nt | dmean nt d | dvar nt d]      ((2 + 2 d) nt doubles; the dvar part untouched when !want_var)
+// of g alone (bt = {}), or of every expert of g's group by ONE sequence of batched launches (bt: the group's table,
+// blockIdx.y = expert; tiles: the most 64-row training tiles of any expert).  Per pass of test points: k_cross,
+// k_predict_gemm and the finish exactly as predict_passes launches them (the mean's and the variance's bits are
+// cugp_predict's / cugp_predict_latent's; batched: k_predict_finish_mv, the same sums), then -- want_var -- V = W L^-1
+// (launch_targets_alpha), k_predict_grad (partial sums per training tile) and k_predict_grad_finish.  V is always W L^-1,
+// never Ks K^-1.  rows null: one handle's rows in the scratch behind the partial sums (*rows_out); else expert i's at
+// rows + i * row_stride.  No copy to the host and no host wait.
+static int predict_grad_passes(cugp_gp* g, Batch bt, int tiles, const double* Xt, int nt, bool with_noise, bool want_var,
+                               Scratch& scr, double* rows, size_t row_stride, double** rows_out = nullptr)
 {
-    if (!g || !Xt || nt <= 0 || (!dmean && !dvar))
-        return fail(CUGP_ERR_INVALID, "cugp_predict_grad: null handle or Xt, nt <= 0, or neither dmean nor dvar given");
     int rc;
-    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // (fetches an evaluation in flight; factor, T, U, alpha for the current hp)
-    if ((rc = use_device(g))) return rc;
-    TuneScope ts(g);
     hipStream_t s = g->stream;
-    const int chunk = grad_chunk_rows(g, nt), cmax = chunk < nt ? chunk : nt, ntpad = ((cmax + TILE - 1) / TILE) * TILE;
-    const int d = g->d, tiles = predict_grad_tiles(g->n);
-    const size_t nxt = (((size_t)nt * d + 15) / 16) * 16, nks = (size_t)ntpad * g->npad, pstride = (size_t)cmax * d;
-    const size_t npart = (size_t)tiles * 2 * pstride, nout = (size_t)nt * d;
-    if ((rc = g->pred.grow(nxt + 3 * nks + npart + 2 * (size_t)nt + 2 * nout, s))) return rc;
-    double* dXt = g->pred.p;
+    const int chunk = grad_chunk_rows(g, nt, bt.count, tiles), cmax = chunk < nt ? chunk : nt;
+    const int ntpad = ((cmax + TILE - 1) / TILE) * TILE, d = g->d;
+    const size_t nxt = (((size_t)nt * d + 15) / 16) * 16, nks = (size_t)bt.count * ntpad * g->npad, pstride = (size_t)cmax * d;
+    const size_t npart = (size_t)bt.count * tiles * 2 * pstride, nout = (size_t)nt * d;
+    if ((rc = scr.grow(nxt + 3 * nks + npart + (rows ? 0 : 2 * (size_t)nt + 2 * nout), s))) return rc;
+    double* dXt = scr.p;
     double* dKs = dXt + nxt;
     double* dW = dKs + nks;
     double* dV = dW + nks;
     double* dP = dV + nks;
-    double* dm = dP + npart;
+    if (!rows) rows = dP + npart;
+    double* dm = rows;
     double* dv = dm + nt;
     double* dgm = dv + nt;
     double* dgv = dgm + nout;
     HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * d * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = reset_stamps(g))) return rc;
+    if (!bt.tab && (rc = reset_stamps(g))) return rc;
     for (int t0 = 0; t0 < nt; t0 += chunk) {
         const int c = nt - t0 < chunk ? nt - t0 : chunk;
         const int cpad = ((c + TILE - 1) / TILE) * TILE;
         const double gemm_flop = (double)cpad * g->npad * g->npad;   // a triangular product: the diagonal k tile counted half
         CovFn cf;
         if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
-        launch_kcross(g->dX, g->n, d, g->npad, dXt + (size_t)t0 * d, c, cpad, cf, dKs, s);
+        launch_kcross(g->dX, g->n, d, g->npad, dXt + (size_t)t0 * d, c, cpad, cf, dKs, s, bt);
         {
-            TimedLaunch tl(g, s, g->prof >= 3);
-            launch_predict_gemm(dKs, g->dT, dW, g->npad, cpad / TILE, g->nt, s);
+            TimedLaunch tl(g, s, !bt.tab && g->prof >= 3);
+            launch_predict_gemm(dKs, g->dT, dW, g->npad, cpad / TILE, g->nt, s, bt);
             tl.done(KIND_PREDICT, gemm_flop);
         }
         HyperScalars hf = cf.h;
         if (!with_noise) hf.noise_var = 0.0;
+        double* pgm = dgm + (size_t)t0 * d;
+        double* pgv = want_var ? dgv + (size_t)t0 * d : nullptr;
+        if (bt.tab) {                                     // the group: Ks, W, V [expert][cpad][npad], one launch each
+            launch_predict_finish_mv(dKs, dW, g->npad, c, hf, dm + t0, dv + t0, row_stride, cpad, s, bt);
+            if (want_var) launch_targets_alpha_batched(dW, dV, g->npad, cpad, s, bt);
+            launch_predict_grad_batched(d, g->npad, dXt + (size_t)t0 * d, c, cf, dKs, want_var ? dV : nullptr,
+                                        (size_t)cpad * g->npad, dP, pstride, tiles, s, bt);
+            launch_predict_grad_finish_batched(dP, pstride, tiles, c, d, cf, pgm, pgv, row_stride, s, bt);
+            continue;
+        }
         launch_predict_finish(dKs, dW, g->dalpha, g->n, g->npad, c, hf, dm + t0, dv + t0, s);
-        if (dvar) {
+        if (want_var) {
             // V = W L^-1 (row t = K^-1 k*_t): W is zero in its columns >= n and its rows >= c, U's padding is identity.
             // launch_targets_alpha takes no launch-own events: timed by an event pair around it (levels 3 and 4).
             const bool timed = (g->prof == 3 || g->prof == 4) && g->kev_used + 2 <= (int)g->kev.size() &&
@@ -1605,20 +1616,61 @@ int cugp_predict_grad(cugp_gp* g, const double* Xt, int nt, int with_noise, doub
         }
         {
             TimedLaunch tl(g, s, g->prof >= 3);
-            launch_predict_grad(g->dX, g->n, d, g->npad, dXt + (size_t)t0 * d, c, cf, dKs, dvar ? dV : nullptr, g->dalpha,
+            launch_predict_grad(g->dX, g->n, d, g->npad, dXt + (size_t)t0 * d, c, cf, dKs, want_var ? dV : nullptr, g->dalpha,
                                 dP, pstride, s);
-            tl.done(KIND_PGRAD, (dvar ? 2.0 : 1.0) * ((c + 63) / 64 * 64) * (double)tiles * 64 * sizeof(double));
+            tl.done(KIND_PGRAD, (want_var ? 2.0 : 1.0) * ((c + 63) / 64 * 64) * (double)tiles * 64 * sizeof(double));
         }
-        launch_predict_grad_finish(dP, pstride, g->n, c, d, cf, dgm + (size_t)t0 * d, dvar ? dgv + (size_t)t0 * d : nullptr, s);
+        launch_predict_grad_finish(dP, pstride, g->n, c, d, cf, pgm, pgv, s);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && mean) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
+    HIPCHK(hipGetLastError());
+    if (rows_out) *rows_out = rows;
+    return CUGP_OK;
+}
+
+// mean, variance and their gradients with respect to the test inputs (include/cugp.h): predict_grad_passes on the
+// handle's stream.  All results stay in the scratch until the copies and the one host wait at the end.
+int cugp_predict_grad(cugp_gp* g, const double* Xt, int nt, int with_noise, double* mean, double* var, double* dmean,
+                      double* dvar)
+{
+    if (!g || !Xt || nt <= 0 || (!dmean && !dvar))
+        return fail(CUGP_ERR_INVALID, "cugp_predict_grad: null handle or Xt, nt <= 0, or neither dmean nor dvar given");
+    int rc;
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;     // (fetches an evaluation in flight; factor, T, U, alpha for the current hp)
+    if ((rc = use_device(g))) return rc;
+    TuneScope ts(g);
+    hipStream_t s = g->stream;
+    const size_t nout = (size_t)nt * g->d;
+    double* dm = nullptr;
+    if ((rc = predict_grad_passes(g, {}, predict_grad_tiles(g->n), Xt, nt, with_noise != 0, dvar != nullptr, g->pred, nullptr,
+                                  0, &dm)))
+        return rc;
+    const double *dv = dm + nt, *dgm = dv + nt, *dgv = dgm + nout;
+    hipError_t e = hipSuccess;
+    if (mean) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && dmean) e = hipMemcpyAsync(dmean, dgm, nout * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && dvar) e = hipMemcpyAsync(dvar, dgv, nout * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);                // the one host wait
     if (e != hipSuccess) { (void)hipStreamSynchronize(s); return fail(CUGP_ERR_DEVICE, "cugp_predict_grad", e); }
     if (g->prof >= 2) drain_kernel_events(g);
+    return CUGP_OK;
+}
+
+// cugp_predict_grad's launches with the rows left on the device (drows: (2 + 2 d) nt doubles on the handle's device) and
+// no host wait: the per-expert half of cugp_bcm_predict_grad and of the form across ranks.  latent != 0: noise_var = 0
+// in the finish (cugp_predict_latent's variance).  *stream: the handle's; cugp_predict_fetch waits for it.
+int cugp_predict_grad_rows_enqueue(cugp_gp* g, const double* Xt, int nt, double* drows, void** stream, int latent,
+                                   int want_dvar)
+{
+    if (!g || !Xt || nt <= 0 || !drows || !stream)
+        return fail(CUGP_ERR_INVALID, "cugp_predict_grad_rows_enqueue: bad argument");
+    int rc;
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;
+    if ((rc = use_device(g))) return rc;
+    TuneScope ts(g);
+    if ((rc = predict_grad_passes(g, {}, predict_grad_tiles(g->n), Xt, nt, latent == 0, want_dvar != 0, g->pred, drows, 0)))
+        return rc;
+    *stream = (void*)g->stream;
     return CUGP_OK;
 }
 
@@ -2930,6 +2982,42 @@ int cugp_group_predict_enqueue_form(cugp_group* gr, const double* Xt, int nt, do
                              latent != 0)))
         return rc;
     *stream = (void*)lead->stream;
+    return CUGP_OK;
+}
+
+// The test-input gradients of every expert of the group by ONE sequence of batched launches on the lead expert's stream
+// (returned in *stream): predict_grad_passes with the group's table.  Expert i's rows [m nt | v nt | dmean nt d | dvar nt d]
+// go to drows + i * row_stride.  cugp_group_predict_enqueue_form's preconditions and contract: CUGP_ERR_INVALID without
+// touching anything when the experts cannot run as a group right now -- the caller then goes expert by expert
+// (cugp_predict_grad_rows_enqueue).
+int cugp_group_predict_grad_enqueue(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride,
+                                    void** stream, int latent, int want_dvar)
+{
+    if (!gr || !Xt || nt <= 0 || !drows || !stream) return CUGP_ERR_INVALID;
+    cugp_gp* lead = gr->experts[0];
+    int rc;
+    if (gr->pending) return fail(CUGP_ERR_BUSY, "cugp_group_predict_grad_enqueue: an evaluation is in flight");
+    if (!same_loghyper(gr)) return CUGP_ERR_INVALID;
+    int tiles = 0;
+    for (cugp_gp* e : gr->experts) {
+        if (!cugp_has_inverse(e) || e->prof >= 3) return CUGP_ERR_INVALID;
+        if (predict_grad_tiles(e->n) > tiles) tiles = predict_grad_tiles(e->n);
+    }
+    if ((rc = use_device(lead))) return rc;
+    TuneScope ts(lead);                                       // the group runs on the lead expert's tuning
+    if (!gr->tab_valid && (rc = write_group_table(gr))) return rc;
+    if ((rc = predict_grad_passes(lead, gr->ctx.bt, tiles, Xt, nt, latent == 0, want_dvar != 0, gr->pred, drows, row_stride)))
+        return rc;
+    *stream = (void*)lead->stream;
+    return CUGP_OK;
+}
+
+int cugp_poe_reduce_grad_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, int d, int mode,
+                                 double sf2, double sn2, int with_noise, int want_dvar, double* dout, void* stream)
+{
+    launch_poe_reduce_grad(gathered, rstride, world, nexperts, nt, d, mode, sf2, sn2, with_noise, want_dvar, dout,
+                           (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return CUGP_OK;
 }
 

@@ -102,6 +102,30 @@ int cugp_bcm_predict_rows_enqueue_form(cugp_bcm* b, int device, const double* Xt
 // k_poe_reduce_mode on `stream`: cugp_poe_reduce_enqueue's buffers, the rows latent, rule `mode` (CUGP_COMBINE_*)
 int cugp_poe_reduce_mode_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, int mode,
                                  double sf2, double sn2, int with_noise, double* dout, void* stream);
+
+// ---- test-input gradients of a product of experts (cugp_bcm_predict_grad, cugp_bcm_predict_grad_allgather) ----
+// Rows of one expert, on the device: [m nt | v nt | dmean nt d | dvar nt d], (2 + 2 d) nt doubles; m, v carry cugp_predict's
+// bits (latent != 0: cugp_predict_latent's); want_dvar == 0 skips V = W L^-1 and leaves the dvar part untouched.
+// (No caller passes want_dvar == 0 today: cugp_bcm_predict_grad and the form across ranks need every expert's dvar for
+// the combined MEAN's gradient in every mode.  In the group form that branch -- the gradient launch with V null, the
+// finish with dvar null -- has so far run only in the host emulation, tools/bcm_predict_grad_host_check.py; the
+// per-expert form's is cugp_predict_grad's own with dvar NULL.)
+// group: ONE sequence of batched launches on the lead expert's stream (*stream), expert i's rows at drows + i *
+// row_stride; preconditions and contract of cugp_group_predict_enqueue_form -- CUGP_ERR_INVALID without touching anything
+// when the experts cannot run as a group right now (the caller then goes expert by expert)
+int cugp_group_predict_grad_enqueue(cugp_group* gr, const double* Xt, int nt, double* drows, size_t row_stride,
+                                    void** stream, int latent, int want_dvar);
+// one expert by cugp_predict_grad's own launches on its own stream (*stream), no host wait; cugp_predict_fetch waits
+int cugp_predict_grad_rows_enqueue(cugp_gp* gp, const double* Xt, int nt, double* drows, void** stream, int latent,
+                                   int want_dvar);
+// the BCM's side of the form across ranks: cugp_bcm_predict_rows_enqueue_form with gradient rows (slots of (2 + 2 d) nt)
+int cugp_bcm_predict_grad_rows_enqueue(cugp_bcm* b, int device, const double* Xt, int nt, double* dsend,
+                                       size_t slot_stride, void* wait_stream, int latent, int want_dvar);
+int cugp_bcm_dim(const cugp_bcm* b);             // the input dimension; 0 for null
+// k_poe_reduce_grad on `stream`: gathered [world][rstride] -> dout [mean nt | var nt | dmean nt d | dvar nt d | world x
+// {status, count}]; mode CUGP_COMBINE_REFERENCE .. CUGP_COMBINE_RBCM
+int cugp_poe_reduce_grad_enqueue(const double* gathered, size_t rstride, int world, int nexperts, int nt, int d, int mode,
+                                 double sf2, double sn2, int with_noise, int want_dvar, double* dout, void* stream);
 // sf2 = exp(2 theta_f), sn2 = exp(2 theta_n) of the BCM's shared hyper-parameters, as the experts' kernels take them
 int cugp_bcm_prior_scalars(const cugp_bcm* b, double* sf2, double* sn2);
 }  // extern "C"

@@ -191,6 +191,27 @@ void launch_predict_grad(const double* X, int n, int d, int npad, const double* 
                          hipStream_t s);
 void launch_predict_grad_finish(const double* part, size_t pstride, int n, int nt, int d, const CovFn& cf, double* dmean,
                                 double* dvar, hipStream_t s);
+// The same for the experts of a group in ONE launch each (blockIdx.y = expert; X, n, alpha, U from the table bt), the
+// passes of cugp_group_predict_grad_enqueue.  Ks, W, V: [expert][cpad][npad] slices (kslice = cpad * npad doubles);
+// partial sums: [expert][tiles_max * 2][pstride], tiles_max = the most 64-row training tiles of any expert -- every
+// expert sums its own count.  Rows: expert e's outputs at (pointer) + e * row_stride.
+//   finish_mv:     m and v themselves (k_predict_finish's sums) -> mean[e * row_stride + t], var[...]
+//   targets_alpha: V = W L^-1 per expert (k_targets_alpha's tile pairing and k ranges; m = cpad)
+//   grad:          k_predict_grad_batched<ARD, KIND>; V null: the mean's sums alone
+//   grad_finish:   dmean / dvar (dvar may be null) packed [nt][d] per expert
+void launch_predict_finish_mv(const double* Ks, const double* W, int npad, int ntest, HyperScalars h, double* mean,
+                              double* var, size_t row_stride, int ntpad, hipStream_t s, Batch bt);
+void launch_targets_alpha_batched(const double* Z, double* A, int npad, int m, hipStream_t s, Batch bt);
+void launch_predict_grad_batched(int d, int npad, const double* Xt, int nt, const CovFn& cf, const double* Ks,
+                                 const double* V, size_t kslice, double* part, size_t pstride, int tiles_max,
+                                 hipStream_t s, Batch bt);
+void launch_predict_grad_finish_batched(const double* part, size_t pstride, int tiles_max, int nt, int d, const CovFn& cf,
+                                        double* dmean, double* dvar, size_t row_stride, hipStream_t s, Batch bt);
+// combined prediction and its test-input gradients over a gathered buffer of gradient rows ([world][rstride]: {status,
+// count, [per] x [m nt | v nt | dmean nt d | dvar nt d]}): out = [mean nt | var nt | dmean nt d | dvar nt d | world x
+// {status, count}]; mode -1 .. 3 (CUGP_COMBINE_REFERENCE .. CUGP_COMBINE_RBCM)
+void launch_poe_reduce_grad(const double* g, size_t rstride, int world, int K, int nt, int d, int mode, double sf2,
+                            double sn2, int with_noise, int want_dvar, double* out, hipStream_t s);
 // product of experts over a gathered exchange buffer ([world][rstride]: {status, count, [per][2][nt]}): out = [mean nt |
 // var nt | world x {status, count}], experts summed in global order (expert k = rank k mod world's slot k / world)
 void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s);

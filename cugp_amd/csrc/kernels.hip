@@ -127,6 +127,8 @@ struct LaunchStamp {
 // kernel_value; TGT_CHUNK, targets_outer_4x4; trace_ard_body; predict_grad_body, k_predict_grad, k_predict_grad_finish.
 // Needs kernels.h, d2, d4 and GP (above) and nothing below.
 #include "cov_device.h"
+// k_predict_grad_batched, k_predict_grad_finish_batched, k_poe_reduce_grad: the product of experts' test-input gradient
+#include "bcm_grad_device.h"
 
 // ------------------------------------------------------------------------------------------
 // fp64 MFMA tile product
@@ -2542,6 +2544,36 @@ __global__ __launch_bounds__(256) void k_predict_finish(const double* __restrict
     }
 }
 
+// k_predict_finish for the experts of a group, leaving m and v THEMSELVES in the expert's rows (the batched form above
+// writes only 1/v and m/v): blockIdx.y selects the expert -- alpha from its table entry, Ks and W its [ntpad][npad]
+// slices -- and row t's mean goes to mean[blockIdx.y * row_stride + t], its variance to var[...] alike.  The sums are
+// k_predict_finish's own, the same loop and the same wave_sum (repeated, not shared through a function: inlining one
+// into k_predict_finish reordered its instructions, and the kernels that exist keep theirs): every expert's m and v
+// carry cugp_predict's bits, with noise_var = 0 in h cugp_predict_latent's.
+__global__ __launch_bounds__(256) void k_predict_finish_mv(const double* __restrict__ Ks, const double* __restrict__ W,
+                                                           int npad, int ntest, HyperScalars h, double* __restrict__ mean,
+                                                           double* __restrict__ var, size_t row_stride, int ntpad,
+                                                           const ExpertPtrs* __restrict__ bt)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= ntest) return;
+    const size_t off = (size_t)blockIdx.y * ntpad * npad + (size_t)row * npad;
+    const double* __restrict__ alpha = GP(bt[blockIdx.y].alpha);
+    const double* kr = Ks + off;
+    const double* wr = W + off;
+    double m = 0.0, q = 0.0;
+    for (int k = lane * 2; k < npad; k += 128) {
+        d2 kv = *(const d2*)(kr + k), av = *(const d2*)(alpha + k), wv = *(const d2*)(wr + k);
+        m += kv[0] * av[0] + kv[1] * av[1];
+        q += wv[0] * wv[0] + wv[1] * wv[1];
+    }
+    m = wave_sum(m); q = wave_sum(q);
+    if (lane == 0) {
+        mean[(size_t)blockIdx.y * row_stride + row] = m;
+        var[(size_t)blockIdx.y * row_stride + row] = h.signal_var + h.noise_var - q;
+    }
+}
+
 // Product of experts over the gathered exchange buffer (comm.cpp: cugp_bcm_predict_allgather).  g: [world][rstride]
 // doubles, rank r's block = {status, local expert count, [per][2][nt] rows: 1/v, m/v}.  Test point t sums over the
 // experts k = 0..K-1 in GLOBAL order -- expert k is rank k mod world's (k / world)-th -- then var = 1/sum, mean =
@@ -2625,6 +2657,27 @@ __global__ __launch_bounds__(256, 2) void k_targets_alpha(const double* __restri
                                                           double* __restrict__ A, int ld, int m64, int n64)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tt = blockIdx.x % m64, p = blockIdx.x / m64;
+#pragma unroll 1
+    for (int h = 0; h < 2; h++) {
+        const int tj = h == 0 ? p : n64 - 1 - p;
+        d4 acc[2][2];
+        acc_zero(acc);
+        tile_nt<false>(Z + (size_t)tt * 64 * ld, ld, U + (size_t)tj * 64 * ld, ld, tj * 64, n64 * 64, acc, smem);
+        tile_store(A + (size_t)tt * 64 * ld + tj * 64, ld, acc, 1.0);
+    }
+}
+
+// k_targets_alpha for the experts of a group (V = W L^-1 of cugp_bcm_predict_grad): the same tile pairing and k ranges,
+// blockIdx.y selects the expert -- U from its table entry, Z and A its [m64 * 64][ld] slices.
+__global__ __launch_bounds__(256, 2) void k_targets_alpha_batched(const double* __restrict__ Z, double* __restrict__ A,
+                                                                  int ld, int m64, int n64,
+                                                                  const ExpertPtrs* __restrict__ bt)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t off = (size_t)blockIdx.y * m64 * 64 * ld;
+    const double* __restrict__ U = GP(bt[blockIdx.y].U);
+    Z += off; A += off;
     const int tt = blockIdx.x % m64, p = blockIdx.x / m64;
 #pragma unroll 1
     for (int h = 0; h < 2; h++) {
@@ -3109,6 +3162,47 @@ void launch_predict_grad_finish(const double* part, size_t pstride, int n, int n
     const double* wts = is_ard(cf) ? (const double*)(cf.hd + 1) : nullptr;   // (the weights behind the hyper-scalars)
     hipLaunchKernelGGL(k_predict_grad_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, pstride,
                        predict_grad_tiles(n), nt, d, cf.h.ell_sq, wts, dmean, dvar);
+}
+
+// ---- the batched launches of cugp_group_predict_grad_enqueue (blockIdx.y = expert) ----
+void launch_predict_finish_mv(const double* Ks, const double* W, int npad, int ntest, HyperScalars h, double* mean,
+                              double* var, size_t row_stride, int ntpad, hipStream_t s, Batch bt)
+{
+    hipLaunchKernelGGL(k_predict_finish_mv, dim3((ntest + 3) / 4, bt.count), dim3(256), 0, s, Ks, W, npad, ntest, h, mean,
+                       var, row_stride, ntpad, bt.tab);
+}
+
+void launch_targets_alpha_batched(const double* Z, double* A, int npad, int m, hipStream_t s, Batch bt)
+{
+    const int m64 = (m + 63) / 64, n64 = npad / 64;
+    hipLaunchKernelGGL(k_targets_alpha_batched, dim3(m64 * (n64 / 2), bt.count), dim3(256), Geo<2>::LDS, s, Z, A, npad, m64,
+                       n64, bt.tab);
+}
+
+void launch_predict_grad_batched(int d, int npad, const double* Xt, int nt, const CovFn& cf, const double* Ks,
+                                 const double* V, size_t kslice, double* part, size_t pstride, int tiles_max,
+                                 hipStream_t s, Batch bt)
+{
+    const dim3 grid(((nt + KT - 1) / KT) * tiles_max, bt.count);
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_predict_grad_batched), grid, dim3(256), 0, s, d, npad, Xt, nt, cf.h, Ks, V,
+                       kslice, part, pstride, (size_t)tiles_max * 2 * pstride, cf.hd, bt.tab);
+}
+
+void launch_predict_grad_finish_batched(const double* part, size_t pstride, int tiles_max, int nt, int d, const CovFn& cf,
+                                        double* dmean, double* dvar, size_t row_stride, hipStream_t s, Batch bt)
+{
+    const size_t total = (size_t)nt * d;
+    const double* wts = is_ard(cf) ? (const double*)(cf.hd + 1) : nullptr;   // (the weights behind the hyper-scalars)
+    hipLaunchKernelGGL(k_predict_grad_finish_batched, dim3((unsigned)((total + 255) / 256), bt.count), dim3(256), 0, s, part,
+                       pstride, (size_t)tiles_max * 2 * pstride, nt, d, cf.h.ell_sq, wts, dmean, dvar, row_stride, bt.tab);
+}
+
+void launch_poe_reduce_grad(const double* g, size_t rstride, int world, int K, int nt, int d, int mode, double sf2,
+                            double sn2, int with_noise, int want_dvar, double* out, hipStream_t s)
+{
+    const size_t total = (size_t)nt * d;
+    hipLaunchKernelGGL(k_poe_reduce_grad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, g, rstride, world, K, nt,
+                       d, mode, sf2, sn2, with_noise, want_dvar, out);
 }
 
 void launch_poe_reduce(const double* g, size_t rstride, int world, int K, int nt, double* out, hipStream_t s)

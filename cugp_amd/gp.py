@@ -498,6 +498,33 @@ class Comm:
                                                     int(nexperts), ptr(Xt), nt, ptr(m), ptr(v)))
         return m, v
 
+    def predict_grad_allgather(self, bcm, per, nexperts, Xt, d, combine=None, with_noise=True, sf2=None, sn2=None,
+                               want_var_grad=True):
+        """The combined prediction and its gradients with respect to the test inputs across the ranks
+        (cugp_bcm_predict_grad_allgather): this rank's experts (`bcm`, or None on a rank that owns none) fill their
+        gradient rows, one all-gather moves every rank's, the chain rule of the rule on the device -> (mean [nt],
+        var [nt], dmean [nt, d], dvar [nt, d] or None).  Every rank passes the same per, nexperts, Xt, d, combine and
+        want_var_grad.  combine: None -- the reference's product of the noisy predictions -- or "poe" | "gpoe" | "bcm" |
+        "rbcm"; sf2, sn2 as predict_allgather's (not read for combine=None)."""
+        mode = capi.CUGP_COMBINE_REFERENCE if combine is None else combine_mode(combine)
+        d = int(d)
+        Xt = f64(Xt).reshape(-1, d)
+        nt = Xt.shape[0]
+        if sf2 is None or sn2 is None:
+            if bcm is not None:
+                sf2, sn2 = bcm.prior_scalars()
+            elif combine is None:
+                sf2, sn2 = 0.0, 0.0
+            else:
+                raise ValueError("a rank without experts must pass sf2 and sn2")
+        m, v, dm = np.empty(nt), np.empty(nt), np.empty((nt, d))
+        dv = np.empty((nt, d)) if want_var_grad else None
+        check(capi.lib().cugp_bcm_predict_grad_allgather(bcm._h if bcm is not None else None, self._h, int(per),
+                                                         int(nexperts), ptr(Xt), nt, d, mode, 1 if with_noise else 0,
+                                                         float(sf2), float(sn2), ptr(m), ptr(v), ptr(dm),
+                                                         ptr(dv) if want_var_grad else None))
+        return m, v, dm, dv
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             capi.lib().cugp_comm_destroy(self._h)
@@ -673,9 +700,17 @@ class BCM:
                                                ptr(v)))
         return m, v
 
+    @property
+    def predict_grad_form(self):
+        """How the last predict_grad ran (cugp_bcm_predict_grad_form): 0 no call yet, 1 expert by expert, 2 every
+        device set as one group of batched launches."""
+        f = C.c_int()
+        check(capi.lib().cugp_bcm_predict_grad_form(self._h, C.byref(f)))
+        return f.value
+
     def predict_grad(self, Xt, combine=None, with_noise=True):
         """(mean, var, dmean [nt, d], dvar [nt, d]) of the combined prediction at Xt (cugp_bcm_predict_grad: the experts'
-        gradients one by one, the chain rule of the rule on the host).  combine=None: the reference's product of the noisy
+        gradients by one group of batched launches per device set, the chain rule of the rule on the host).  combine=None: the reference's product of the noisy
         predictions (predict(Xt)'s bits; with_noise is not read); else the rule on the latent distributions, as predict."""
         mode = capi.CUGP_COMBINE_REFERENCE if combine is None else combine_mode(combine)
         Xt = f64(Xt).reshape(-1, self.d)

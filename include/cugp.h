@@ -180,8 +180,8 @@ int cugp_predict_latent(cugp_gp *gp, const double *Xt, int nt, double *mean, dou
  *      cugp_predict works on (SE, Matern, ARD, padded handles, BCM experts); a stale handle is evaluated first, an
  *      evaluation in flight is fetched first.  CUGP_ERR_INVALID -- before any device call -- for a NULL gp or Xt, nt <= 0,
  *      or dmean and dvar both NULL.  Non-finite inputs propagate by IEEE with CUGP_OK (the header's convention).
- * Not built: gradients of the joint covariance or of draws, of multi-target means, the form across ranks (an all-gather
- *      of gradient rows), a batched launch for the experts of a BCM. */
+ * Not built: gradients of the joint covariance or of draws, of multi-target means.  (The experts of a BCM run as one
+ *      batched sequence of launches in cugp_bcm_predict_grad; the form across ranks is cugp_bcm_predict_grad_allgather.) */
 int cugp_predict_grad(cugp_gp *gp, const double *Xt, int nt, int with_noise,
                       double *mean /* nt, may be NULL */, double *var /* nt, may be NULL */,
                       double *dmean /* [nt][d], may be NULL */, double *dvar /* [nt][d], may be NULL */);
@@ -496,12 +496,35 @@ int cugp_bcm_predict_allgather_mode(cugp_bcm *b, cugp_comm *c, int per, int nexp
  *      gradients; out_dmean, out_dvar [nt][d].  CUGP_COMBINE_REFERENCE (-1): the reference's product of the experts' NOISY
  *      predictions (cugp_bcm_predict, BCM.cpp:45-62): POE's arithmetic on noisy variances, which the caller passes.
  *      CUGP_ERR_INVALID for a NULL argument, K <= 0, nt <= 0, d <= 0 or an unknown mode.
- * cugp_bcm_predict_grad: cugp_predict_grad expert by expert (each on its own device, so a BCM over several devices of one
- *      process works), combined on the host.  mean, var (either may be NULL): from rows made as the device makes them,
- *      through cugp_poe_combine -- cugp_bcm_predict_mode's values, bit for bit except RBCM's log -- or, mode -1, through
- *      cugp_poe_finish: cugp_bcm_predict's bits (with_noise is then not read).  dmean, dvar [nt][d] (either may be NULL, not
- *      both).  CUGP_ERR_INVALID -- before any device call -- for a NULL b or Xt, nt <= 0, dmean and dvar both NULL or an
- *      unknown mode.  Not built: the form across ranks. */
+ * cugp_bcm_predict_grad: every expert's mean, variance and gradients, combined on the host.  Per device set the experts
+ *      run as ONE group of batched launches (one launch per pass and kernel, the expert a grid dimension) where they can
+ *      -- equal padded size, equal hyper-parameters, profiling below level 3 --, else expert by expert by
+ *      cugp_predict_grad's own launches; either way every expert of every device set is in flight before the first wait,
+ *      and the rows of a set reach pinned host memory by one copy (a BCM over several devices of one process works).
+ *      Rows of one expert: [m nt | v nt | dmean nt*d | dvar nt*d], (2 + 2 d) nt doubles; m, v carry cugp_predict's bits
+ *      (mode -1) or cugp_predict_latent's, the gradients cugp_predict_grad's.  mean, var (either may be NULL): from rows made
+ *      as the device makes them, through cugp_poe_combine -- cugp_bcm_predict_mode's values, bit for bit except RBCM's log
+ *      -- or, mode -1, through cugp_poe_finish: cugp_bcm_predict's bits (with_noise is then not read).  dmean, dvar [nt][d]
+ *      (either may be NULL, not both; the experts' dvar is computed either way: the mean's gradient reads it).  The results
+ *      do not depend on which of the two paths ran.  CUGP_ERR_INVALID -- before any device call -- for a NULL b or Xt,
+ *      nt <= 0, dmean and dvar both NULL or an unknown mode.
+ * cugp_bcm_predict_grad_form: how the last cugp_bcm_predict_grad (or cugp_bcm_predict_grad_allgather) on b ran: 0 no call
+ *      yet, 1 expert by expert, 2 every device set as a group.  CUGP_ERR_INVALID for a NULL b or form.
+ * cugp_bcm_predict_grad_allgather: the form across ranks, cugp_bcm_predict_allgather's sequence and rules (above) with
+ *      gradient rows: every rank sends {status, local expert count, [per] slots of (2 + 2 d) nt doubles -- its i-th
+ *      expert's rows [m nt | v nt | dmean nt*d | dvar nt*d] in slot i} by ONE ncclAllGather on the communicator's stream;
+ *      the kernel k_poe_reduce_grad, device twin of the host path of cugp_bcm_predict_grad (one thread per test point and
+ *      dimension, experts in GLOBAL order, the same operations in the same order), leaves [mean nt | var nt | dmean nt*d |
+ *      dvar nt*d | world x {status, count}]; one copy, one host wait.  Modes CUGP_COMBINE_REFERENCE .. CUGP_COMBINE_RBCM;
+ *      the results carry cugp_bcm_predict_grad's bits except RBCM's, whose log is the device's (agreement to rounding).
+ *      d, sf2 = exp(2 theta_f) and sn2 = exp(2 theta_n) are arguments because a rank that owns no expert passes b == NULL.
+ *      mean, var: nt each, either may be NULL; dmean, dvar: [nt][d], either may be NULL, not both -- and whether dvar is
+ *      given must be the same on every rank (the caller's duty, like Xt).  A world of one without an id uses no RCCL.
+ *      Refusals, CUGP_ERR_INVALID before any collective or device call with the call's name in cugp_last_error, for what
+ *      every rank detects from the shared arguments: NULL c or Xt; nt, d, per or nexperts <= 0; per * world < nexperts; an
+ *      unknown mode; dmean and dvar both NULL; d different from a non-NULL b's.  Every other failure is local: the rank
+ *      still joins the collective with a nonzero status word and NaN rows, every rank reads every rank's status and ALL
+ *      return the same code, with all four outputs NaN; BCM and communicator stay usable. */
 #define CUGP_COMBINE_REFERENCE (-1)
 int cugp_poe_combine_grad(const double *mean, const double *var,       /* [K][nt] each */
                           const double *dmean, const double *dvar,     /* [K][nt][d] each */
@@ -509,6 +532,12 @@ int cugp_poe_combine_grad(const double *mean, const double *var,       /* [K][nt
                           double *out_dmean, double *out_dvar);        /* [nt][d] each */
 int cugp_bcm_predict_grad(cugp_bcm *b, const double *Xt, int nt, int mode, int with_noise,
                           double *mean, double *var, double *dmean, double *dvar);
+int cugp_bcm_predict_grad_form(const cugp_bcm *b, int *form);
+int cugp_bcm_predict_grad_allgather(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt, int d,
+                                    int mode /* CUGP_COMBINE_REFERENCE .. CUGP_COMBINE_RBCM */, int with_noise,
+                                    double sf2, double sn2,
+                                    double *mean, double *var,     /* nt each, either may be NULL */
+                                    double *dmean, double *dvar);  /* [nt][d], either may be NULL, not both */
 /* ---- ARD BCM: every expert an ARD handle (squared exponential, or through the _ard_kernel calls a Matern kind; theta
  *      as cugp_create_ard's: nh = d + 2 entries shared by all experts).  The reference has no counterpart.  The experts
  *      run as groups of shared launches, over several
