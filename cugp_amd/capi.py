@@ -86,6 +86,9 @@ SIGNATURES = {
     "cugp_predict_targets": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp]),
     "cugp_get_alpha_targets": (C.c_int, [C.c_void_p, _dp]),
     "cugp_cg_solve_targets": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_loo": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
+    "cugp_loo_predict": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "cugp_cg_solve_loo": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_potrf": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_potri": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_chol_and_det": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_int]),

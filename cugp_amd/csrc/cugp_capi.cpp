@@ -57,7 +57,7 @@ constexpr int PROF_STRIDE = 16; // profiling level 2 times every 16th step launc
 // kinds of timed launches (cugp_get_kernel_stats_kind): the kernels as rocprofv3 names them
 enum { KIND_STEP = 0, KIND_WIDE = 1, KIND_BORDER4 = 2, KIND_BORDER2 = 3, KIND_LAUUM4 = 4, KIND_LAUUM2 = 5,
        KIND_LEVEL4 = 6, KIND_LEVEL2 = 7, KIND_BLOCK = 8, KIND_PREDICT = 9, KIND_BUILD = 10, KIND_TRSM = 11, KIND_COV = 12,
-       KIND_PGRAD = 13, KIND_COUNT = 14 };
+       KIND_PGRAD = 13, KIND_LOO = 14, KIND_COUNT = 15 };
 
 // One hardware queue per stream up to 16 (the runtime default is 4): the experts of a BCM on one device each
 // drive their own stream, and 16 experts on 4 queues serialise (5.8 ms vs 4.6 ms per evaluation of 16 x 1500
@@ -191,6 +191,11 @@ struct cugp_gp {
     bool is_factor = false;        // the internal factor handle (cov_f) of another handle
     bool x_full = false;           // dX holds npad rows (grown by the first append; n rows until then)
     Scratch app;                   // one pass: B = k(Xb, X), P = B L^-T, V = P L^-1 ([128][npad] each) and Qt ([npad][128])
+    // leave-one-out cross-validation (cugp_loo): buffers of its own, created on first use -- no buffer any other call reads is written
+    double *loo_pt = nullptr;      // [LOO_PT_ROWS][npad] per-point results, then b [npad], the tiles' shares of b [npad / 64][npad]
+                                   // and the trace partials [nh][nblocks_trace]: one allocation
+    double *loo_out = nullptr, *loo_hout = nullptr;   // results row [L_LOO, g (nh)], device and pinned
+    double *loo_B = nullptr, *loo_P = nullptr;        // npad^2 each: K^-1 diag(sqrt c) and its product; first gradient call
 };
 
 namespace {
@@ -1202,6 +1207,9 @@ int cugp_destroy(cugp_gp* g)
     g->tg_pred.release();
     g->app.release();
     if (g->tg_hout) (void)hipHostFree(g->tg_hout);
+    if (g->loo_hout) (void)hipHostFree(g->loo_hout);
+    for (double* p : {g->loo_pt, g->loo_out, g->loo_B, g->loo_P})
+        if (p) (void)hipFree(p);
     double* bufs[] = {g->dX, g->dy, g->dA, g->dT, g->dU, g->dKinv, g->dz, g->dalpha, g->dw, g->d16, g->dlogdet,
                       g->dpart, g->dout, g->d64, g->tg_y, g->tg_z, g->tg_a, g->tg_part, g->tg_out};
     for (double* p : bufs)
@@ -2325,6 +2333,138 @@ int cugp_cg_solve_targets(cugp_gp* g, int budget, double* trace, int trace_cap, 
     if ((rc = tg_ready(g, call))) return rc;
     std::vector<double> th(g->theta);
     if ((rc = cugp_cg_minimize_n(targets_objective, g, th.data(), g->nh, budget, trace, trace_cap, nevals))) return rc;
+    return set_theta(g, th.data());
+}
+
+// ---------------------------------------------------------------- leave-one-out cross-validation
+// From K^-1 and alpha of the handle's own evaluation (untouched): the objective and the per-point predictions are two
+// launches behind it, the gradient five more -- DESIGN.md section 24.  Argument errors come first, then "no device", then
+// what only the handle can tell.  Nothing is kept between calls: every call launches, and equal inputs give equal bits.
+namespace {
+size_t loo_small_count(const cugp_gp* g)
+{
+    return (size_t)(LOO_PT_ROWS + 1 + g->npad / 64) * g->npad + (size_t)g->nh * g->nblocks_trace;
+}
+
+// the evaluation that leaves K^-1 and alpha (a stale handle: re-evaluated, as predict_device does), then the LOO launches
+// and ONE host wait.  The results row is in g->loo_hout ([0] L_LOO, [1 ..] the gradient when wanted); NaN where the
+// covariance is not positive definite (the header's convention).
+int loo_eval(cugp_gp* g, bool want_grad, const char* call)
+{
+    int rc;
+    if (!g->have_data) return tg_invalid(call, "no training data set (cugp_set_data)");
+    if ((rc = cugp_loglik_grad(g, nullptr, nullptr))) return rc;
+    if ((rc = use_device(g))) return rc;
+    const size_t nn = (size_t)g->npad * g->npad, row = (size_t)1 + g->nh;
+    if ((rc = ensure(&g->loo_pt, loo_small_count(g))) || (rc = ensure(&g->loo_out, row))) return rc;
+    if (!g->loo_hout) HIPCHK(hipHostMalloc((void**)&g->loo_hout, row * sizeof(double), hipHostMallocDefault));
+    if (want_grad && !g->loo_P) {                                    // both or neither: a failure leaves the handle as it was
+        if ((rc = ensure(&g->loo_B, nn))) return rc;
+        if ((rc = ensure(&g->loo_P, nn))) { (void)hipFree(g->loo_B); g->loo_B = nullptr; return rc; }
+    }
+    for (size_t i = 0; i < row; i++) g->loo_hout[i] = NAN;
+    if (!g->inverse_valid) return CUGP_OK;                           // (NaN evaluation: nothing to read K^-1 from)
+    TuneScope ts(g);
+    hipStream_t s = g->stream;
+    double* pt = g->loo_pt;
+    double* b = pt + (size_t)LOO_PT_ROWS * g->npad;
+    double* bpart = b + g->npad;
+    double* part = bpart + (size_t)(g->npad / 64) * g->npad;
+    launch_loo_point(g->dKinv, g->dalpha, g->dy, g->n, g->npad, pt, g->loo_out, g->loo_hout, s);
+    if (want_grad) {
+        if (const int pe = prepare_kernels())
+            return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
+        launch_loo_mirror_scale(g->dKinv, pt, g->n, g->npad, g->loo_B, bpart, b, s);
+        {
+            TimedLaunch tl(g, s, g->prof >= 2 && g->prof <= 4);      // (no stamp slot in k_loo_product: level 5 does not time it)
+            launch_loo_product(g->loo_B, g->loo_P, g->npad, s);
+            tl.done(KIND_LOO, (double)tri_tiles(g->nt) * 2.0 * TILE * TILE * g->npad);
+        }
+        CovFn cf;
+        if ((rc = cov_fn(g, s, nullptr, &cf))) return rc;
+        launch_trace_loo(g->dX, g->n, g->d, g->npad, cf, g->loo_P, g->dalpha, b, part, g->loo_out, g->loo_hout, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return fail(CUGP_ERR_DEVICE, call, e); }
+    if (g->prof >= 2) drain_kernel_events(g);
+    return CUGP_OK;
+}
+
+// f = -L_LOO and its gradient at th (NaN where the evaluation fails)
+void loo_objective(void* ctx, const double* th, int nh, double* f, double* gr)
+{
+    cugp_gp* g = (cugp_gp*)ctx;
+    if (set_theta(g, th) == CUGP_OK && loo_eval(g, true, "cugp_cg_solve_loo") == CUGP_OK) {
+        *f = -1.0 * g->loo_hout[0];
+        std::copy(g->loo_hout + 1, g->loo_hout + 1 + nh, gr);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nh, NAN);
+    }
+}
+}  // namespace
+
+int cugp_loo(cugp_gp* g, double* lpl, double* gr, int nh)
+{
+    const char* call = "cugp_loo";
+    if (!g) return tg_invalid(call, "null handle");
+    if (!lpl) return tg_invalid(call, "lpl is NULL");
+    if (nh < 3) return tg_invalid(call, "nh is not the handle's (cugp_num_hyper)");
+    int rc;
+    if ((rc = tg_device(call))) return rc;
+    if (nh != g->nh) return tg_invalid(call, "nh is not the handle's (cugp_num_hyper)");
+    if ((rc = loo_eval(g, gr != nullptr, call))) return rc;
+    *lpl = g->loo_hout[0];
+    if (gr) std::copy(g->loo_hout + 1, g->loo_hout + 1 + nh, gr);
+    return CUGP_OK;
+}
+
+int cugp_loo_predict(cugp_gp* g, double* mean, double* var, double* logp)
+{
+    const char* call = "cugp_loo_predict";
+    if (!g) return tg_invalid(call, "null handle");
+    if (!mean || !var) return tg_invalid(call, "mean or var is NULL");
+    int rc;
+    if ((rc = tg_device(call))) return rc;
+    if ((rc = loo_eval(g, false, call))) return rc;
+    const size_t bytes = (size_t)g->n * sizeof(double);
+    if (!g->inverse_valid) {
+        std::fill(mean, mean + g->n, NAN);
+        std::fill(var, var + g->n, NAN);
+        if (logp) std::fill(logp, logp + g->n, NAN);
+        return CUGP_OK;
+    }
+    hipStream_t s = g->stream;
+    hipError_t e = hipMemcpyAsync(mean, g->loo_pt, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(var, g->loo_pt + g->npad, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && logp) e = hipMemcpyAsync(logp, g->loo_pt + 2 * (size_t)g->npad, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(s); return fail(CUGP_ERR_DEVICE, call, e); }
+    return CUGP_OK;
+}
+
+// (minimize.cpp; internal) cugp_cg_minimize_n's loop with the iterates as its record
+int cugp_cg_minimize_n_iterates(cugp_objective_n_fn fn, void* ctx, double* theta, int nh, int budget, double* rows,
+                                int rows_cap, int* nevals, int* nrows);
+
+// conjugate gradients on -L_LOO from the current hyper-parameters: the loop of cugp_cg_minimize_n over the handle's nh
+// entries; the end point stays set, as cugp_cg_solve leaves it.  The trace holds the ITERATES, rows of nh + 1: the start
+// and the point each line search ended at -- the objective never rises along it; the row behind the last one written
+// (when there is room) carries NaN in every entry, so a caller can count them.  *nevals: evaluations made.
+int cugp_cg_solve_loo(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
+{
+    const char* call = "cugp_cg_solve_loo";
+    if (!g) return tg_invalid(call, "null handle");
+    if (budget <= 0) return tg_invalid(call, "budget must be positive");
+    int rc;
+    if ((rc = tg_device(call))) return rc;
+    if (!g->have_data) return tg_invalid(call, "no training data set (cugp_set_data)");
+    std::vector<double> th(g->theta);
+    int nrows = 0;
+    if ((rc = cugp_cg_minimize_n_iterates(loo_objective, g, th.data(), g->nh, budget, trace, trace_cap, nevals, &nrows)))
+        return rc;
+    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (g->nh + 1), trace + (size_t)(nrows + 1) * (g->nh + 1), NAN);
     return set_theta(g, th.data());
 }
 

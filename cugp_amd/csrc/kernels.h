@@ -279,6 +279,22 @@ void launch_append_border(const double* P, const double* V, const double* Cf, co
 // lower 64x64 tiles of Kinv[0, r0) += Q'Q (fp64 MFMA, Qt as both operands, k rounded up to 16) and alpha[0, r0) += Q' zb
 void launch_append_kinv(const double* Qt, int r0, int k, int ld, double* Kinv, const double* zb, double* alpha,
                         hipStream_t s);
+// ---- leave-one-out cross-validation (cugp_loo; loo_device.h): plain launches on s, fixed-order sums ----
+// pt: [LOO_PT_ROWS][npad] -- mean, variance, log predictive density, a = alpha / kappa, s = sqrt(c), zero beyond n; then
+// one workgroup adds the densities: out[0] = hout[0] = L_LOO (out: device row, hout: pinned)
+constexpr int LOO_PT_ROWS = 5;
+void launch_loo_point(const double* Kinv, const double* alpha, const double* y, int n, int npad, double* pt, double* out,
+                      double* hout, hipStream_t s);
+// Bm (full npad x npad) = K^-1 diag(s) from the lower 64x64 tiles of K^-1, zero beyond n; b = K^-1 a through the tiles'
+// shares bpart ([npad / 64][npad]), added in tile order
+void launch_loo_mirror_scale(const double* Kinv, const double* pt, int n, int npad, double* Bm, double* bpart, double* b,
+                             hipStream_t s);
+// P (lower 128-tiles, diagonal tiles complete) = Bm Bm^T, K = npad for every tile; returns the tile edge in 32s (4 or 2)
+int launch_loo_product(const double* Bm, double* P, int npad, hipStream_t s);
+// gradient pass over the lower tiles of P with W_loo = P - b alpha^T - alpha b^T (part: (nl + 2) * trace_num_blocks(npad),
+// nl = 1 or ARD's d) and its final sums: out[1 ..] = hout[1 ..] = the nh components of d(-L_LOO) / dtheta
+void launch_trace_loo(const double* X, int n, int d, int npad, const CovFn& cf, const double* P, const double* alpha,
+                      const double* b, double* part, double* out, double* hout, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

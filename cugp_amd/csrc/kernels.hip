@@ -2811,6 +2811,45 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize_targets(const double* 
 #include "append_device.h"
 
 // ------------------------------------------------------------------------------------------
+// Leave-one-out cross-validation (cugp_loo): k_loo_point, k_loo_sum, k_loo_mirror_scale, k_loo_bsum, k_trace_loo,
+// k_loo_finalize (loo_device.h: a host can emulate them) and the one product that needs the device, k_loo_product
+// ------------------------------------------------------------------------------------------
+#include "loo_device.h"
+
+// P (lower tiles, diagonal tiles complete) = B B^T over the whole k range: lauum_tile's shape with a = 0, w = nt and a
+// uniform K = ld for every tile.  Plain stores (tile_store): nothing is accumulated, no tile is touched twice.
+template <int WM>
+__device__ __forceinline__ void loo_product_tile(const double* __restrict__ Bm, double* __restrict__ P, int ld, int tile,
+                                                 int sub, char* smem)
+{
+    constexpr int SUB = 4 / WM, BT = 32 * WM;
+    int ti, tj;
+    tri_index(tile, ti, tj);
+    const int si = (sub / SUB) * BT, sj = (sub % SUB) * BT;
+    d4 acc[WM][WM];
+    acc_zero(acc);
+    tile_nt<false>(Bm + (size_t)(ti * TILE + si) * ld, ld, Bm + (size_t)(tj * TILE + sj) * ld, ld, 0, ld, acc, smem);
+    tile_store(P + (size_t)(ti * TILE + si) * ld + tj * TILE + sj, ld, acc, 1.0);
+}
+
+// k_lauum's two tile sizes: WM = 2 -- every tile as four 64x64 workgroups; WM = 4 -- the first nfull tiles as 128x128
+// workgroups, the partly empty last round as 64x64 quarters (split_round)
+template <int WM>
+__global__ __launch_bounds__(256, 2) void k_loo_product(const double* __restrict__ Bm, double* __restrict__ P, int ld,
+                                                        int nfull)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (WM == 2) {
+        loo_product_tile<2>(Bm, P, ld, blockIdx.x >> 2, blockIdx.x & 3, smem);
+    } else if ((int)blockIdx.x < nfull) {
+        loo_product_tile<4>(Bm, P, ld, blockIdx.x, 0, smem);
+    } else {
+        const int y = blockIdx.x - nfull;
+        loo_product_tile<2>(Bm, P, ld, nfull + (y >> 2), y & 3, smem);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 // Per-launch timing without extra packets on the stream (profiling level 4, cugp_capi.cpp TimedLaunch): the next launch
@@ -2897,7 +2936,7 @@ static void set_big_lds()
     attr((const void*)k_syrk_step, STEP_LDS);
     attr((const void*)k_syrk_wide, GEMM_LDS);
     const void* gemm4[] = {(const void*)k_trtri_level<4>, (const void*)k_trtri_border<4>, (const void*)k_lauum<4>,
-                           (const void*)k_test_gemm, (const void*)k_predict_cov<4>};
+                           (const void*)k_test_gemm, (const void*)k_predict_cov<4>, (const void*)k_loo_product<4>};
     for (const void* f : gemm4) attr(f, GEMM_LDS);
     attr((const void*)k_trtri_diag, TRTRI_LDS);
     attr((const void*)k_trtri_block, TRTRI_BLOCK_LDS);
@@ -3328,6 +3367,45 @@ void launch_append_kinv(const double* Qt, int r0, int k, int ld, double* Kinv, c
     const int n64 = (r0 + 63) / 64, lower = tri_count(n64), tiles = lower + n64 / 2, k16 = (k + BK - 1) / BK * BK;
     hipLaunchKernelGGL(k_append_kinv, dim3(tiles + (r0 + 255) / 256), dim3(256), Geo<2>::LDS, s, Qt, k16, k, r0, ld, lower,
                        tiles, Kinv, zb, alpha);
+}
+
+// ---- leave-one-out cross-validation ----
+void launch_loo_point(const double* Kinv, const double* alpha, const double* y, int n, int npad, double* pt, double* out,
+                      double* hout, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_loo_point, dim3(npad / 256 + (npad % 256 ? 1 : 0)), dim3(256), 0, s, Kinv, alpha, y, n, npad, pt);
+    hipLaunchKernelGGL(k_loo_sum, dim3(1), dim3(256), 0, s, (const double*)pt, npad, out, hout);
+}
+
+void launch_loo_mirror_scale(const double* Kinv, const double* pt, int n, int npad, double* Bm, double* bpart, double* b,
+                             hipStream_t s)
+{
+    const int nb = npad / KT;
+    hipLaunchKernelGGL(k_loo_mirror_scale, dim3(nb * nb), dim3(256), 0, s, Kinv, pt, n, npad, Bm, bpart);
+    hipLaunchKernelGGL(k_loo_bsum, dim3(npad / 256 + (npad % 256 ? 1 : 0)), dim3(256), 0, s, (const double*)bpart, npad, b);
+}
+
+int launch_loo_product(const double* Bm, double* P, int npad, hipStream_t s)
+{
+    set_big_lds();
+    const int tiles = tri_count(npad / TILE);
+    if (tiles <= tune(TUNE_LAUUM_WM2_MAX)) {
+        CUGP_LAUNCH(k_loo_product<2>, dim3(tiles * 4), dim3(256), Geo<2>::LDS, s, Bm, P, npad, 0);
+        return 2;
+    }
+    const int nfull = split_round(tiles, 1);                 // (uniform K: a short last round is worth splitting)
+    CUGP_LAUNCH(k_loo_product<4>, dim3(nfull + 4 * (tiles - nfull)), dim3(256), GEMM_LDS, s, Bm, P, npad, nfull);
+    return 4;
+}
+
+void launch_trace_loo(const double* X, int n, int d, int npad, const CovFn& cf, const double* P, const double* alpha,
+                      const double* b, double* part, double* out, double* hout, hipStream_t s)
+{
+    const int nblocks = tri_count(npad / KT);
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_loo), dim3(nblocks), dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, P, alpha,
+                       b, part);
+    hipLaunchKernelGGL(k_loo_finalize, dim3(1), dim3(256), 0, s, (const double*)part, nblocks, is_ard(cf) ? d : 1,
+                       cf.h.noise_var, out, hout);
 }
 
 void launch_test_gemm_nt(const double* A, const double* B, double* C, int m, int n, int k, hipStream_t s)

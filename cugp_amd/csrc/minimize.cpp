@@ -102,7 +102,22 @@ public:
     }
     int count() const { return count_; }
     int grads() const { return (fn_ || nf_) ? count_ : grads_; }
+    // optional second record (cugp_cg_minimize_n_iterates): the points the loop MOVES to -- the start and where each line
+    // search ends -- as rows [theta, f]; the objective never rises along them.  Without it iterate() does nothing.
+    void keep_iterates(double* rows, int cap) { iters_ = rows; icap_ = cap; }
+    void iterate(const Vec& X, double f)
+    {
+        if (iters_ && icount_ < icap_) {
+            double* r = iters_ + (X.size() + 1) * (long)icount_;
+            for (int i = 0; i < X.size(); i++) r[i] = X[i];
+            r[X.size()] = f;
+        }
+        ++icount_;
+    }
+    int iterates() const { return icount_; }
 private:
+    double* iters_ = nullptr;
+    int icap_ = 0, icount_ = 0;
     cugp_objective_n_fn nf_ = nullptr;
     cugp_objective_fn fn_ = nullptr;
     cugp_value_fn vf_ = nullptr;
@@ -138,6 +153,21 @@ extern "C" int cugp_cg_minimize_n(cugp_objective_n_fn fn, void* ctx, double* the
     return rc;
 }
 
+// Internal (cugp_capi.cpp: cugp_cg_solve_loo; not in cugp.h): cugp_cg_minimize_n's loop, bit for bit, with the ITERATES as
+// its record instead of every evaluation -- rows [theta, f] of the start and of the point each line search ended at when
+// that moved (the accepted step, or the best probe of a failed search); *nrows <- their number, *nevals <- evaluations.
+extern "C" int cugp_cg_minimize_n_iterates(cugp_objective_n_fn fn, void* ctx, double* theta, int nh, int budget,
+                                           double* rows, int rows_cap, int* nevals, int* nrows)
+{
+    if (!fn || !theta || nh <= 0 || budget < 0) return CUGP_ERR_INVALID;
+    Probe probe(fn, ctx, nullptr, 0);
+    probe.keep_iterates(rows, rows ? rows_cap : 0);
+    const int rc = cg_loop(probe, theta, nh, budget);
+    if (nevals) *nevals = probe.count();
+    if (nrows) *nrows = probe.iterates() < rows_cap ? probe.iterates() : rows_cap;
+    return rc;
+}
+
 extern "C" int cugp_cg_minimize_sparing(cugp_value_fn value, cugp_gradient_fn gradient, void* ctx, double theta[3],
                                         int budget, double* trace, int trace_cap, int* nevals, int* ngrads)
 {
@@ -160,6 +190,7 @@ static int cg_loop(Probe& probe, double* theta, int nh, int budget)
     Vec df0(nh), df3(nh), s(nh);
     double f0;
     probe.at(X, f0, df0, INFINITY);          // covkernel.cpp:438-439
+    probe.iterate(X, f0);
     s = neg(df0);
     df3 = df0;
     double d0 = -dot(s, s);
@@ -219,6 +250,7 @@ static int cg_loop(Probe& probe, double* theta, int nh, int budget)
         if (std::fabs(d3) < -kSig * d0 && f3 < f0 + x3 * kRho * d0) {
             X = axpy(X, s, x3);
             f0 = f3;
+            probe.iterate(X, f0);
             const double beta = (dot(df3, df3) - dot(df0, df3)) / (dot(df0, df0));
             for (int j = 0; j < nh; j++) s[j] = beta * s[j] - df3[j];
             df0 = df3;
@@ -229,7 +261,9 @@ static int cg_loop(Probe& probe, double* theta, int nh, int budget)
             x3 = x3 * (kRatio < ratio ? kRatio : ratio);
             prev_failed = false;
         } else {
+            const bool moved = bestF < f0;
             X = bestX; f0 = bestF; df0 = bestG;
+            if (moved) probe.iterate(X, f0);
             if (prev_failed || i >= n) break;
             s = neg(df0);
             d0 = -dot(s, s);

@@ -313,6 +313,35 @@ class Covsum:
         check(capi.lib().cugp_cg_solve_targets(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
         return tr[: ne.value]
 
+    # -- leave-one-out cross-validation from the factored model (GPML 5.10-5.13), on the data the handle holds --
+    def loo(self, want_grad=True):
+        """(L_LOO, g): the sum of the leave-one-out log predictive densities and the gradient of -L_LOO [nh] in
+        loglik_grad's convention and order (cugp_loo); want_grad=False: (L_LOO, None), no N^2 scratch."""
+        lpl = C.c_double()
+        g = np.empty(self.nh) if want_grad else None
+        check(capi.lib().cugp_loo(self._h, C.byref(lpl), ptr(g) if want_grad else None, self.nh))
+        return lpl.value, g
+
+    def loo_predict(self):
+        """(mean, var, logp), n each: every training row predicted from the other n - 1 (cugp_loo_predict); var is the
+        variance of y_i, noise included; logp sums to loo()'s L_LOO."""
+        m, v, lp = np.empty(self.n), np.empty(self.n), np.empty(self.n)
+        check(capi.lib().cugp_loo_predict(self._h, ptr(m), ptr(v), ptr(lp)))
+        return m, v, lp
+
+    def cg_solve_loo(self, budget=100):
+        """Conjugate gradients on -L_LOO from the current hyper-parameters (cugp_cg_solve_loo), every family; the trace
+        [n_iterates, nh + 1] = (theta, -L_LOO) of the start and of the point every line search ended at: the objective
+        never rises along it, and the last row is the end point (rejected probes are not recorded)."""
+        budget = int(budget)
+        tr = np.full((4 * max(budget, 0) + 8, self.nh + 1), np.nan)
+        ne = C.c_int()
+        check(capi.lib().cugp_cg_solve_loo(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        rows = 1
+        while rows < min(ne.value, tr.shape[0]) and not np.isnan(tr[rows, 0]):
+            rows += 1
+        return tr[:rows]
+
     # -- prediction --
     def compute_test_means_and_variances(self, X, y, Xtest):
         self._bind(X, y)

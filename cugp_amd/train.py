@@ -17,7 +17,32 @@ import time
 import numpy as np
 
 
-def main():
+def train_loo(args, local):
+    """One expert, conjugate gradients on -L_LOO (Covsum.cg_solve_loo); prints what the default objective's run prints."""
+    from . import dataset
+    from .gp import Covsum, kernel_spec
+    X, y = dataset.load_chunk("%s0.txt" % args.inputs, "%s0.txt" % args.labels)
+    Xt, yt = X[args.rows:args.rows + args.test_rows], y[args.rows:args.rows + args.test_rows]
+    X, y = X[:args.rows], y[:args.rows]
+    ard = kernel_spec(args.kernel, args.ard)[1]
+    g = Covsum(X.shape[0], X.shape[1], local, ard=args.ard, kernel=args.kernel)
+    g.set_loghyperparam([args.hp[0]] * (g.nh - 2) + list(args.hp[1:]) if ard else args.hp)
+    g.set_data(X, y)
+    t0 = time.perf_counter()
+    trace = g.cg_solve_loo(args.budget)
+    dt = time.perf_counter() - t0
+    hp = g.get_loghyperparam()
+    print("\n\n PLEASE-SEE %d : %s\n" % (g.nh, ", ".join("%f" % v for v in hp)))
+    print("TOTAL training time = %f  (%d iterates, final -L_LOO %.9g)" % (dt, trace.shape[0], trace[-1, -1]))
+    if args.test_rows > 0:
+        m, v = g.compute_test_means_and_variances(X, y, Xt)
+        print("NLPP = %.12g" % Covsum.get_negative_log_predprob(yt, m, v))
+    g.close()
+
+
+def main(argv=None, parse_only=False):
+    """parse_only: -> the parsed arguments (--objective loo is refused there, before any device is touched, where it is
+    not built)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--numchunks", type=int, required=True)
     ap.add_argument("--rows", type=int, required=True, help="training rows per chunk (numtrain)")
@@ -36,7 +61,15 @@ def main():
     ap.add_argument("--combine", default=None, choices=["poe", "gpoe", "bcm", "rbcm"],
                     help="how the held-out prediction combines the experts' LATENT distributions (with the noise added "
                          "for the NLPP); absent: the reference's product of the noisy predictions")
-    args = ap.parse_args()
+    ap.add_argument("--objective", default="ll", choices=["ll", "loo"],
+                    help="what cg_solve minimises: ll, the negative marginal log-likelihood (the reference's), or loo, the "
+                         "negative sum of the leave-one-out log predictive densities (GPML 5.4.2) -- one expert in one "
+                         "process only (--numchunks 1): there is no LOO for a product of experts")
+    args = ap.parse_args(argv)
+    if args.objective == "loo" and (args.numchunks != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1):
+        ap.error("--objective loo needs --numchunks 1 and one process: leave-one-out is built for a single expert")
+    if parse_only:
+        return args
 
     import torch
     import torch.distributed as dist
@@ -48,6 +81,8 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(local)
+    if args.objective == "loo":
+        return train_loo(args, local)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if args.backend == "nccl":

@@ -288,6 +288,39 @@ int cugp_predict_targets(cugp_gp *gp, const double *Xt, int nt, double *mean /* 
 int cugp_get_alpha_targets(cugp_gp *gp, double *alpha /* [m][n] */);
 int cugp_cg_solve_targets(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals);
 
+/* ---- leave-one-out cross-validation (LOO) from the factored model (Rasmussen & Williams, GPML 5.10-5.13; GPML's infLOO).
+ *      After an evaluation that forms the inverse the handle holds K^-1 and alpha; with kappa_i = [K^-1]_ii the LOO predictive
+ *      distribution of training point i, from the other n - 1 points, is
+ *        mu_i = y_i - alpha_i / kappa_i,   var_i = 1 / kappa_i   (the variance of y_i, noise included)
+ *        logp_i = 1/2 log kappa_i - alpha_i^2 / (2 kappa_i) - 1/2 * 1.83787,   L_LOO = sum_i logp_i
+ *      (1.83787: the literal LL uses for log 2 pi).  O(n) beyond the evaluation.  The gradient costs one symmetric N^3 tile
+ *      product whatever the number of hyper-parameters:  a_i = alpha_i / kappa_i,  c_i = (1 + alpha_i^2 / kappa_i) / kappa_i,
+ *      b = K^-1 a,  W_loo = K^-1 diag(c) K^-1 - b alpha' - alpha b',  d(-L_LOO)/dtheta_j = 1/2 tr(W_loo dK/dtheta_j) --
+ *      the marginal likelihood's gradient pass with W_loo in the place of K^-1 - alpha alpha'.
+ * cugp_loo          : *lpl <- L_LOO; g (may be NULL) <- the nh components of the gradient of -L_LOO, the convention, order
+ *                     and nh of cugp_loglik_grad / cugp_loglik_grad_ard (nh must equal cugp_num_hyper).  g == NULL launches
+ *                     the objective alone and allocates no N^2 scratch; the first call with g allocates two npad^2 matrices,
+ *                     kept until cugp_destroy (CUGP_ERR_NOMEM, the handle as it was, when they do not fit).
+ * cugp_loo_predict  : mean, var and logp (may be NULL) of every training row, n each, in cugp_set_data's row order
+ * cugp_cg_solve_loo : the loop of cugp_cg_minimize_n on f = -L_LOO from the current hyper-parameters, for every family
+ *                     (isotropic handles: nh = 3); the end point stays set.  trace (may be NULL): rows of nh + 1 doubles
+ *                     [theta, f] as cugp_cg_solve_ard writes them, but of the ITERATES, not of every evaluation: the
+ *                     start, then the point each line search ended at (the accepted step, or the best probe of a search
+ *                     that failed), so f never rises along the trace and its last row is the end point; rejected
+ *                     probes are not recorded.  The row behind the last one written is all NaN where trace_cap leaves
+ *                     room for it.  *nevals <- evaluations made (at least the number of rows).
+ * A stale handle (new data or hyper-parameters, or only cugp_loglik behind it) is evaluated first, as cugp_predict does;
+ * a handle extended by cugp_append answers for all its rows.  Every call launches again: equal inputs give equal bits.
+ * No result of any other call changes: the LOO passes write buffers of their own.
+ * Errors: CUGP_ERR_INVALID with the call's name in cugp_last_error, before any launch, for a NULL gp, lpl, mean or var,
+ * an nh that is not the handle's, budget <= 0, no data; CUGP_ERR_NODEVICE without a GPU; CUGP_ERR_DEVICE as everywhere.
+ * A covariance that is not positive definite gives NaN results with CUGP_OK (the header's convention).
+ * Not built: LOO over the m targets of cugp_set_targets (the calls read the handle's own y); a batched or sharded LOO
+ * for a product of experts (cugp_bcm, cugp_group); a C++ Covsum method in cugp_amd/host/. */
+int cugp_loo(cugp_gp *gp, double *lpl, double *g /* nh, may be NULL */, int nh);
+int cugp_loo_predict(cugp_gp *gp, double *mean /* n */, double *var /* n */, double *logp /* n, may be NULL */);
+int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals);
+
 /* ---- stand-alone dense LA on a caller matrix (common/matrixops.h:5-25) ----
  * cugp_potrf        : get_cholesky            (L lower, upper zeroed)
  * cugp_potri        : compute_K_inverse
@@ -321,6 +354,7 @@ int cugp_get_kernel_stats(cugp_gp *gp, double *sum_ms, long long *launches, doub
  * lower 64x64 tiles of K written once + X read), 12 = k_predict_cov<4> / <2> (W W^T of cugp_predict_cov and
  * cugp_predict_sample; levels 3 to 5 only; flop: every launched output tile over the whole k range), 13 = k_predict_grad
  * (the tile pass of cugp_predict_grad; levels 3 and 4 only; its `flop` is BYTES: the tiles of Ks and, with dvar, V it reads).
+ * 14 = k_loo_product<4> / <2> (P = B B^T of cugp_loo's gradient; levels 2 to 4, every launch).
  * cugp_predict_grad's second triangular product V = W L^-1 (k_targets_alpha) is counted under kind 9 (levels 3 and 4).  The
  * sampling rates are those of level 2; levels 3 to 5 time every launch.  flop = algorithmic
  * (entries on or below the diagonal, a triangular k tile counted half), multiply + add */
