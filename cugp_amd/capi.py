@@ -89,6 +89,20 @@ SIGNATURES = {
     "cugp_loo": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
     "cugp_loo_predict": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "cugp_cg_solve_loo": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_sparse_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                     C.POINTER(C.c_void_p)]),
+    "cugp_sparse_destroy": (C.c_int, [C.c_void_p]),
+    "cugp_sparse_dims": (C.c_int, [C.c_void_p, _ip, _ip, _ip, _ip, _ip]),
+    "cugp_sparse_num_hyper": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_sparse_set_data": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "cugp_sparse_set_inducing": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_sparse_set_loghyper": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_sparse_get_loghyper": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_sparse_bound": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_sparse_bound_grad": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
+    "cugp_sparse_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_sparse_cg_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_sparse_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "cugp_potrf": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_potri": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_chol_and_det": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_int]),

@@ -2563,6 +2563,394 @@ int cugp_potrs_vec(int n, const double* K, const double* y, double* x, int devic
     return la_solve(n, K, y, x, nullptr, nullptr, device);
 }
 
+// ---------------------------------------------------------------- sparse variational GP regression on inducing points
+// include/cugp.h and DESIGN.md section 25.  The M x M side is two ordinary handles: `u` over Z with the noise slot holding
+// the jitter (its own evaluation: Lu, Lu^-1, Lu^-T) and `b`, a factor handle whose A receives B = I + P / s2 and goes the
+// way cugp_potri's does (LB, LB^-1, LB^-T, B^-1).  The N side streams the data in chunks through u's cross-covariance and
+// triangular-product launches on u's stream; the new passes are kernels.h's launch_sparse_* / launch_trace_cross.
+struct cugp_sparse {
+    int n = 0, m = 0, d = 0, mpad = 0, device = 0, kernel = KERNEL_SE, nh = 3, chunk_rows = 0;
+    bool ard = false;
+    double jitter = 1e-6;
+    cugp_gp *u = nullptr, *b = nullptr;
+    double *dX = nullptr, *dy = nullptr;            // [n][d], y zero padded to the chunks' 128-row tiles
+    double *dyy = nullptr;                          // y'y
+    bool have_data = false, have_z = false;
+    std::vector<double> theta;
+    bool valid = false, pd = false;                 // b, cp hold for (data, Z, theta); ... and both matrices were positive definite
+    std::vector<double> row;                        // [F, g (nh)] of the last evaluation
+    bool row_grad = false;
+    // scratch, created on first use
+    double *dS = nullptr, *dW = nullptr, *dG = nullptr;      // one chunk: k(X_c, Z), W_c, G_c^T ([chunk pad][mpad])
+    double *dP = nullptr, *dscr = nullptr;                   // P and the Gram launch's partial tiles
+    double *dvec = nullptr;                                  // q, c', gamma', beta', beta' / s2^2 (mpad each), then the slabs' shares of q
+    double *dM[4] = {nullptr, nullptr, nullptr, nullptr};    // H, H2, a product, R (mpad^2 each): the gradient's
+    double *dpart = nullptr;                                 // trace partials: the rectangle's, then the square's
+    double *dout = nullptr, *hout = nullptr;                 // results row, device and pinned
+    Scratch pred;
+};
+
+namespace {
+int sp_chunk_max(const cugp_sparse* s)
+{
+    const int rows = s->chunk_rows > 0 ? s->chunk_rows : SPARSE_CHUNK_DEFAULT;
+    return ((s->n < rows ? s->n : rows) + TILE - 1) / TILE * TILE;
+}
+
+size_t sp_blocks_uf(const cugp_sparse* s)
+{
+    size_t nb = 0;
+    const int chunks = sparse_shape(s->n, s->mpad, s->chunk_rows, 0).chunks;
+    for (int c = 0; c < chunks; c++) nb += (size_t)(sparse_shape(s->n, s->mpad, s->chunk_rows, c).cpad / 64) * (s->mpad / 64);
+    return nb;
+}
+
+int sp_ensure(cugp_sparse* s, bool want_grad)
+{
+    int rc;
+    const size_t cm = (size_t)sp_chunk_max(s) * s->mpad, mm = (size_t)s->mpad * s->mpad;
+    int split = 1;
+    const int chunks = sparse_shape(s->n, s->mpad, s->chunk_rows, 0).chunks;
+    for (int c = 0; c < chunks; c++) split = std::max(split, sparse_shape(s->n, s->mpad, s->chunk_rows, c).split);
+    if ((rc = ensure(&s->dS, cm)) || (rc = ensure(&s->dW, cm)) || (rc = ensure(&s->dP, mm)) ||
+        (rc = ensure(&s->dscr, (size_t)split * mm)) ||
+        (rc = ensure(&s->dvec, (size_t)(5 + sp_chunk_max(s) / TILE) * s->mpad)) || (rc = ensure(&s->dout, (size_t)1 + s->nh)))
+        return rc;
+    if (!s->hout) HIPCHK(hipHostMalloc((void**)&s->hout, ((size_t)1 + s->nh) * sizeof(double), hipHostMallocDefault));
+    if (want_grad) {
+        if ((rc = ensure(&s->dG, cm))) return rc;
+        for (double*& p : s->dM)
+            if ((rc = ensure(&p, mm))) return rc;
+        const size_t nb = sp_blocks_uf(s) + (size_t)(s->mpad / 64) * (s->mpad / 64);
+        if ((rc = ensure(&s->dpart, (size_t)(s->nh - 1) * nb))) return rc;
+    }
+    return CUGP_OK;
+}
+
+// S_c = k(X_c, Z) and W_c = S_c Lu^-T of one chunk on u's stream: the launches of a prediction with the chunk as test rows
+void sp_chunk_w(cugp_sparse* s, const CovFn& cf, const SparseShape& c)
+{
+    cugp_gp* u = s->u;
+    launch_kcross(u->dX, s->m, s->d, s->mpad, s->dX + (size_t)c.r0 * s->d, c.count, c.cpad, cf, s->dS, u->stream);
+    launch_predict_gemm(s->dS, u->dT, s->dW, s->mpad, c.cpad / TILE, u->nt, u->stream);
+}
+
+// The bound (and its gradient) at the current hyper-parameters.  The results land in s->row: NaN where Kuu or B is not
+// positive definite (the header's convention).  Two host waits beyond the inner evaluation's: in front of B's
+// factorisation, which runs on the factor handle's own stream, and at the end.
+int sp_eval(cugp_sparse* s, bool want_grad, const char* call)
+{
+    int rc;
+    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
+    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
+    if (s->valid && (s->row_grad || !want_grad)) return CUGP_OK;
+    cugp_gp *u = s->u, *b = s->b;
+    s->valid = s->pd = false;
+    s->row.assign((size_t)1 + s->nh, NAN);
+    s->row_grad = want_grad;
+    std::vector<double> th(s->theta);
+    th[s->nh - 1] = 0.5 * std::log(s->jitter);                        // the noise slot of the inner handle: Kuu = k(Z, Z) + eps I
+    if ((rc = set_theta(u, th.data()))) return rc;
+    if ((rc = cugp_loglik_grad(u, nullptr, nullptr))) return rc;       // Lu, Lu^-1, Lu^-T
+    if ((rc = use_device(u))) return rc;
+    if ((rc = sp_ensure(s, want_grad))) return rc;
+    if (!std::isfinite(u->last_ll)) { s->valid = true; return CUGP_OK; }      // Kuu is not positive definite: NaN results
+    if (const int pe = prepare_kernels())
+        return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
+    hipStream_t st = u->stream;
+    const int mp = s->mpad, nl = s->nh - 2;
+    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
+    double *q = s->dvec, *cp = q + mp, *gp = cp + mp, *bp = gp + mp, *bsc = bp + mp, *qpart = bsc + mp;
+    const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
+    CovFn cf;
+    {
+        TuneScope ts(u);
+        if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
+        for (int c = 0; c < chunks; c++) {
+            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
+            sp_chunk_w(s, cf, sh);
+            launch_sparse_gram(s->dW, mp, sh, s->dP, s->dscr, c == 0, st);
+            launch_sparse_wty(s->dW, mp, sh.cpad, s->dy + sh.r0, qpart, q, c == 0, st);
+        }
+        launch_sparse_form_b(s->dP, mp, s2, b->dA, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if ((rc = la_factor_inverse(b, true))) return rc;                  // LB, LB^-1, LB^-T, B^-1 (cugp_potri's route)
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    launch_trmv_lower(b->dT, mp, mp, q, cp, st);                       // c' = LB^-1 q
+    const size_t nb_uf = sp_blocks_uf(s), nb_uu = (size_t)(mp / 64) * (mp / 64);
+    double *part_uf = s->dpart, *part_uu = want_grad ? s->dpart + (size_t)(nl + 1) * nb_uf : nullptr;
+    if (want_grad) {
+        launch_trmv_upper(b->dU, mp, mp, cp, gp, st);                  // gamma' = LB^-T c'
+        launch_trmv_upper(u->dU, mp, mp, gp, bp, st);                  // beta' = Lu^-T gamma'
+        double *H = s->dM[0], *H2 = s->dM[1], *X1 = s->dM[2], *R = s->dM[3];
+        launch_sparse_h(b->dKinv, s->dP, gp, bp, s->m, mp, s2, H, H2, bsc, st);
+        launch_targets_alpha(H, u->dU, X1, mp, mp, st);                // H Lu^-1
+        launch_sparse_transpose(X1, R, mp, 1.0 / s2, st);              // R = Lu^-T H / s2
+        launch_targets_alpha(H2, u->dU, X1, mp, mp, st);               // H2 Lu^-1
+        launch_sparse_transpose(X1, H, mp, 1.0, st);                   // Lu^-T H2
+        launch_targets_alpha(H, u->dU, H2, mp, mp, st);                // 2 G_uu = Lu^-T H2 Lu^-1
+        size_t pofs = 0;
+        for (int c = 0; c < chunks; c++) {
+            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
+            if (chunks > 1) sp_chunk_w(s, cf, sh);                     // (one chunk: W is still there)
+            launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
+            launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
+                               s->dy + sh.r0, bsc, part_uf, nb_uf, pofs, st);
+            pofs += (size_t)(sh.cpad / 64) * (mp / 64);
+        }
+        launch_trace_cross(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, part_uu, nb_uu, 0, st);
+    }
+    const SparseFinal fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->dyy, s->m, mp, b->nt, (double)s->n, sf2, s2,
+                          s->theta[s->nh - 1] * 2};
+    for (int i = 0; i <= s->nh; i++) s->hout[i] = NAN;
+    launch_sparse_finalize(fin, want_grad ? part_uf : nullptr, nb_uf, part_uu, nb_uu, nl, s->dout, s->hout, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
+    s->row[0] = s->hout[0];
+    if (want_grad) std::copy(s->hout + 1, s->hout + 1 + s->nh, s->row.begin() + 1);
+    s->pd = std::isfinite(s->row[0]);
+    s->valid = true;
+    return CUGP_OK;
+}
+
+int sp_set_theta(cugp_sparse* s, const double* th)
+{
+    bool changed = false;
+    for (int i = 0; i < s->nh; i++) changed = changed || th[i] != s->theta[i] || std::isnan(th[i]);
+    if (!changed) return CUGP_OK;
+    s->theta.assign(th, th + s->nh);
+    s->valid = false;
+    return CUGP_OK;
+}
+
+// f = -F and its gradient at th (NaN where the evaluation fails)
+void sp_objective(void* ctx, const double* th, int nh, double* f, double* gr)
+{
+    cugp_sparse* s = (cugp_sparse*)ctx;
+    if (sp_set_theta(s, th) == CUGP_OK && sp_eval(s, true, "cugp_sparse_cg_solve") == CUGP_OK) {
+        *f = -1.0 * s->row[0];
+        std::copy(s->row.begin() + 1, s->row.begin() + 1 + nh, gr);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nh, NAN);
+    }
+}
+}  // namespace
+
+int cugp_sparse_plan(int n, int m, int chunk_rows, int pass, int out[5])
+{
+    const char* call = "cugp_sparse_plan";
+    if (!out) return tg_invalid(call, "out is NULL");
+    if (n < 1 || m < 1 || m > CUGP_SPARSE_MAX_M) return tg_invalid(call, "n < 1, m < 1 or m beyond CUGP_SPARSE_MAX_M");
+    if (chunk_rows < 0 || chunk_rows % TILE) return tg_invalid(call, "chunk_rows must be 0 or a multiple of 128");
+    const SparseShape c = sparse_shape(n, (m + TILE - 1) / TILE * TILE, chunk_rows, pass < 0 ? 0 : pass);
+    if (pass < 0 || pass >= c.chunks) return tg_invalid(call, "pass beyond the last one");
+    out[0] = c.r0; out[1] = c.count; out[2] = c.cpad; out[3] = c.split; out[4] = c.kstep;
+    return c.chunks;
+}
+
+int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, cugp_sparse** out)
+{
+    const char* call = "cugp_sparse_create";
+    if (!out) return tg_invalid(call, "out is NULL");
+    if (n < 1 || d < 1) return tg_invalid(call, "n and d must be positive");
+    if (m < 1) return tg_invalid(call, "m < 1: at least one inducing input");
+    if (m > CUGP_SPARSE_MAX_M) return tg_invalid(call, "m beyond CUGP_SPARSE_MAX_M");
+    if (kernel < 0 || kernel >= KERNEL_COUNT) return tg_invalid(call, "unknown kernel kind");
+    if (chunk_rows < 0 || chunk_rows % TILE) return tg_invalid(call, "chunk_rows must be 0 or a multiple of 128");
+    if (!(jitter > 0.0) || !std::isfinite(jitter)) return tg_invalid(call, "jitter must be positive and finite");
+    int rc;
+    if ((rc = tg_device(call))) return rc;
+    cugp_sparse* s = new (std::nothrow) cugp_sparse;
+    if (!s) return fail(CUGP_ERR_NOMEM, "host allocation");
+    *out = nullptr;
+    s->n = n; s->m = m; s->d = d; s->device = device; s->kernel = kernel; s->ard = ard != 0;
+    s->nh = s->ard ? d + 2 : 3;
+    s->jitter = jitter; s->chunk_rows = chunk_rows;
+    s->mpad = (m + TILE - 1) / TILE * TILE;
+    s->theta.assign(s->nh, 0.0);
+    s->row.assign((size_t)1 + s->nh, NAN);
+    if ((rc = create_handle(m, d, device, 0, s->ard, &s->u, kernel)) || (rc = cugp_create(m, 1, device, &s->b)) ||
+        (rc = ensure_factor_bufs(s->b)) || (rc = ensure_inverse_bufs(s->b))) { cugp_sparse_destroy(s); return rc; }
+    const size_t ny = ((size_t)n + TILE - 1) / TILE * TILE;
+    hipError_t e = hipMalloc((void**)&s->dX, (size_t)n * d * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&s->dy, ny * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&s->dyy, sizeof(double));
+    if (e == hipSuccess) e = hipMemset(s->b->dy, 0, (size_t)s->b->npad * sizeof(double));
+    if (e != hipSuccess) {
+        rc = fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, call, e);
+        cugp_sparse_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return CUGP_OK;
+}
+
+int cugp_sparse_destroy(cugp_sparse* s)
+{
+    if (!s) return CUGP_OK;
+    (void)hipSetDevice(s->device);
+    if (s->u && s->u->stream) (void)hipStreamSynchronize(s->u->stream);
+    if (s->u) (void)cugp_destroy(s->u);
+    if (s->b) (void)cugp_destroy(s->b);
+    for (double* p : {s->dX, s->dy, s->dyy, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dvec, s->dM[0], s->dM[1], s->dM[2], s->dM[3],
+                      s->dpart, s->dout})
+        if (p) (void)hipFree(p);
+    if (s->hout) (void)hipHostFree(s->hout);
+    s->pred.release();
+    delete s;
+    return CUGP_OK;
+}
+
+int cugp_sparse_dims(const cugp_sparse* s, int* n, int* m, int* d, int* mpad, int* chunk_rows)
+{
+    if (!s) return tg_invalid("cugp_sparse_dims", "null handle");
+    if (n) *n = s->n;
+    if (m) *m = s->m;
+    if (d) *d = s->d;
+    if (mpad) *mpad = s->mpad;
+    if (chunk_rows) *chunk_rows = s->chunk_rows > 0 ? s->chunk_rows : SPARSE_CHUNK_DEFAULT;
+    return CUGP_OK;
+}
+
+int cugp_sparse_num_hyper(const cugp_sparse* s, int* nh)
+{
+    if (!s || !nh) return tg_invalid("cugp_sparse_num_hyper", "null argument");
+    *nh = s->nh;
+    return CUGP_OK;
+}
+
+int cugp_sparse_set_data(cugp_sparse* s, const double* X, const double* y)
+{
+    const char* call = "cugp_sparse_set_data";
+    if (!s || !X || !y) return tg_invalid(call, "null argument");
+    int rc;
+    if ((rc = use_device(s->u))) return rc;
+    hipStream_t st = s->u->stream;
+    const size_t ny = ((size_t)s->n + TILE - 1) / TILE * TILE;
+    HIPCHK(hipMemcpyAsync(s->dX, X, (size_t)s->n * s->d * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(s->dy, 0, ny * sizeof(double), st));
+    HIPCHK(hipMemcpyAsync(s->dy, y, (size_t)s->n * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_sparse_yy(s->dy, s->n, s->dyy, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    s->have_data = true;
+    s->valid = false;
+    return CUGP_OK;
+}
+
+int cugp_sparse_set_inducing(cugp_sparse* s, const double* Z)
+{
+    if (!s || !Z) return tg_invalid("cugp_sparse_set_inducing", "null argument");
+    const std::vector<double> zero((size_t)s->m, 0.0);                 // (the inner handle's labels are never read by this model)
+    if (const int rc = cugp_set_data(s->u, Z, zero.data())) return rc;
+    s->have_z = true;
+    s->valid = false;
+    return CUGP_OK;
+}
+
+int cugp_sparse_set_loghyper(cugp_sparse* s, const double* hp, int nh)
+{
+    const char* call = "cugp_sparse_set_loghyper";
+    if (!s || !hp) return tg_invalid(call, "null argument");
+    if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
+    return sp_set_theta(s, hp);
+}
+
+int cugp_sparse_get_loghyper(const cugp_sparse* s, double* hp, int nh)
+{
+    const char* call = "cugp_sparse_get_loghyper";
+    if (!s || !hp) return tg_invalid(call, "null argument");
+    if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
+    std::copy(s->theta.begin(), s->theta.end(), hp);
+    return CUGP_OK;
+}
+
+int cugp_sparse_bound(cugp_sparse* s, double* F)
+{
+    const char* call = "cugp_sparse_bound";
+    if (!s || !F) return tg_invalid(call, "null argument");
+    if (const int rc = sp_eval(s, false, call)) return rc;
+    *F = s->row[0];
+    return CUGP_OK;
+}
+
+int cugp_sparse_bound_grad(cugp_sparse* s, double* F, double* g, int nh)
+{
+    const char* call = "cugp_sparse_bound_grad";
+    if (!s || !F || !g) return tg_invalid(call, "null argument");
+    if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
+    if (const int rc = sp_eval(s, true, call)) return rc;
+    *F = s->row[0];
+    std::copy(s->row.begin() + 1, s->row.end(), g);
+    return CUGP_OK;
+}
+
+int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* var)
+{
+    const char* call = "cugp_sparse_predict";
+    if (!s || !Xt || !mean || !var) return tg_invalid(call, "null argument");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    int rc;
+    if ((rc = sp_eval(s, false, call))) return rc;                     // (answers from the last evaluation's state when it holds)
+    if (!s->pd) {
+        std::fill(mean, mean + nt, NAN);
+        std::fill(var, var + nt, NAN);
+        return CUGP_OK;
+    }
+    cugp_gp *u = s->u, *b = s->b;
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    hipStream_t st = u->stream;
+    const int mp = s->mpad;
+    // test rows per pass: whole 128-row tiles whose Ks, Wt and Vt stay within 1 GiB
+    int chunk = (int)std::min<size_t>(((size_t)1 << 30) / ((size_t)3 * mp * sizeof(double)) / TILE * TILE, (size_t)1 << 20);
+    if (chunk < TILE) chunk = TILE;
+    const int cmax = ((nt < chunk ? nt : chunk) + TILE - 1) / TILE * TILE;
+    const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)cmax * mp;
+    if ((rc = s->pred.grow(nxt + 3 * nks + 2 * (size_t)nt, st))) return rc;
+    double *dXt = s->pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dm = dVt + nks, *dv = dm + nt;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * s->d * sizeof(double), hipMemcpyHostToDevice, st));
+    CovFn cf;
+    if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
+    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
+    const double* cp = s->dvec + mp;
+    for (int t0 = 0; t0 < nt; t0 += chunk) {
+        const int c = nt - t0 < chunk ? nt - t0 : chunk, cpad = (c + TILE - 1) / TILE * TILE;
+        launch_kcross(u->dX, s->m, s->d, mp, dXt + (size_t)t0 * s->d, c, cpad, cf, dKs, st);
+        launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
+        launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T
+        launch_sparse_predict_finish(dWt, dVt, cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, dm + t0, dv + t0, st);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
+    return CUGP_OK;
+}
+
+// conjugate gradients on -F from the current hyper-parameters: cugp_cg_minimize_n's loop over the handle's nh entries with
+// the iterates as its record, as cugp_cg_solve_loo keeps it; the end point stays set
+int cugp_sparse_cg_solve(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)
+{
+    const char* call = "cugp_sparse_cg_solve";
+    if (!s) return tg_invalid(call, "null handle");
+    if (budget <= 0) return tg_invalid(call, "budget must be positive");
+    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
+    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
+    int rc, nrows = 0;
+    std::vector<double> th(s->theta);
+    if ((rc = cugp_cg_minimize_n_iterates(sp_objective, s, th.data(), s->nh, budget, trace, trace_cap, nevals, &nrows)))
+        return rc;
+    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
+    return sp_set_theta(s, th.data());
+}
+
 // ---------------------------------------------------------------- timing
 int cugp_set_profiling(cugp_gp* g, int level)
 {
@@ -2794,7 +3182,7 @@ int cugp_bench_la(int op, int n, int device, int reps, double* ms)
 // that the timed launches produced the right factor
 int cugp_bench_la_check(int op, int n, int device, int reps, double* ms, double* logdet)
 {
-    if (!ms || n <= 0 || op < 0 || op > 4 || reps <= 0) return CUGP_ERR_INVALID;
+    if (!ms || n <= 0 || op < 0 || op > 5 || reps <= 0) return CUGP_ERR_INVALID;
     cugp_gp* g = nullptr;
     const int d = 4;
     int rc = cugp_create(n, d, device, &g);
@@ -2810,13 +3198,23 @@ int cugp_bench_la_check(int op, int n, int device, int reps, double* ms, double*
     if (e == hipSuccess) e = hipEventCreate(&e1);
     double best = 1e300;
     TuneScope ts(g);
+    // op 5: the sparse model's Gram product on one chunk of SPARSE_CHUNK_DEFAULT rows against n inducing points: W is that
+    // many rows of the (full) matrix K, its rows taken round and round; the partial tiles and their fixed-order sum are timed
+    const SparseShape gs = sparse_shape(SPARSE_CHUNK_DEFAULT, g->npad, 0, 0);
+    double *gw = nullptr, *gscr = nullptr;
+    if (op == 5 && e == hipSuccess) e = hipMalloc((void**)&gw, (size_t)gs.cpad * g->npad * sizeof(double));
+    if (op == 5 && e == hipSuccess) e = hipMalloc((void**)&gscr, (size_t)gs.split * g->npad * g->npad * sizeof(double));
     for (int r = 0; r < reps + 1 && e == hipSuccess && rc == CUGP_OK; r++) {
-        launch_kbuild(g->dX, g->n, g->d, g->npad, CovFn{KERNEL_SE, false, scalars(g), nullptr}, g->dA, op == 4, g->stream);
+        launch_kbuild(g->dX, g->n, g->d, g->npad, CovFn{KERNEL_SE, false, scalars(g), nullptr}, g->dA, op >= 4, g->stream);
+        for (int r0 = 0; op == 5 && r == 0 && r0 < gs.cpad && e == hipSuccess; r0 += g->npad)
+            e = hipMemcpyAsync(gw + (size_t)r0 * g->npad, g->dA, (size_t)std::min(g->npad, gs.cpad - r0) * g->npad * sizeof(double),
+                               hipMemcpyDeviceToDevice, g->stream);
         if (op == 1 || op == 2) rc = enqueue_potrf(g, false);
         if (op == 2 && !rc) rc = enqueue_trtri(g);
         if (rc) break;
         e = hipEventRecord(e0, g->stream);
         if (op == 4) launch_test_gemm_nt(g->dA, g->dA, g->dKinv, g->npad, g->npad, g->npad, g->stream);   // uniform tiles
+        if (op == 5) launch_sparse_gram(gw, g->npad, gs, g->dKinv, gscr, true, g->stream);
         if (op == 0) rc = enqueue_potrf(g, false);
         if (op == 1) rc = enqueue_trtri(g);
         if (op == 2) launch_lauum(g->dU, g->dKinv, g->npad, 0, g->nt, g->stream);
@@ -2839,6 +3237,8 @@ int cugp_bench_la_check(int op, int n, int device, int reps, double* ms, double*
         }
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (gw) (void)hipFree(gw);
+    if (gscr) (void)hipFree(gscr);
     cugp_destroy(g);
     if (rc) return rc;
     if (e != hipSuccess) return fail(CUGP_ERR_DEVICE, "cugp_bench_la", e);

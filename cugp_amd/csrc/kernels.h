@@ -295,6 +295,51 @@ int launch_loo_product(const double* Bm, double* P, int npad, hipStream_t s);
 // nl = 1 or ARD's d) and its final sums: out[1 ..] = hout[1 ..] = the nh components of d(-L_LOO) / dtheta
 void launch_trace_loo(const double* X, int n, int d, int npad, const CovFn& cf, const double* P, const double* alpha,
                       const double* b, double* part, double* out, double* hout, hipStream_t s);
+// ---- sparse variational GP regression on inducing points (cugp_sparse_*; sparse_device.h) ----
+// The schedule of pass `pass` over n data rows in chunks of chunk_rows (0: SPARSE_CHUNK_DEFAULT) against mpad padded
+// inducing points -- what cugp_sparse_plan reports: the chunk's rows [r0, r0 + count), cpad = count rounded up to 128
+// (the k range of its Gram launch), and that launch's split: workgroup (tile, s) sums k in [s kstep, min((s + 1) kstep,
+// cpad)).  The split aims at SPARSE_GRAM_SLOTS 128x128 workgroups (two per CU) with at least 256 k each, at most 64 ways,
+// its scratch (split * mpad^2 doubles) within 1 GiB.  Pure arithmetic.
+constexpr int SPARSE_CHUNK_DEFAULT = 16384;
+constexpr int SPARSE_GRAM_SLOTS = 512;
+struct SparseShape { int chunks, r0, count, cpad, split, kstep; };
+SparseShape sparse_shape(int n, int mpad, int chunk_rows, int pass);
+// P (lower 128-tiles of mpad^2, diagonal tiles complete) = (first ? 0 : P) + W^T W, W: [c.cpad][mpad] (k_sparse_gram: the
+// split-k partial tiles into scr, c.split * mpad^2 doubles; k_sparse_gram_finish adds them in index order)
+void launch_sparse_gram(const double* W, int mpad, const SparseShape& c, double* P, double* scr, bool first, hipStream_t s);
+// q (mpad) = (first ? 0 : q) + W^T y through the 128-row slabs' shares part ([cpad / 128][mpad]), added in slab order
+void launch_sparse_wty(const double* W, int mpad, int cpad, const double* y, double* part, double* q, bool first,
+                       hipStream_t s);
+void launch_sparse_yy(const double* y, int n, double* out, hipStream_t s);                     // out[0] = y'y, one workgroup
+// Bm (lower 128-tiles, diagonal tiles complete) = I + P / s2
+void launch_sparse_form_b(const double* P, int mpad, double s2, double* Bm, hipStream_t s);
+// H = I - B^-1 - gamma gamma^T, H2 = H - P / s2 (full mpad^2, zero beyond m; gamma = gp / s2), bsc = bp / s2^2
+void launch_sparse_h(const double* Binv, const double* P, const double* gp, const double* bp, int m, int mpad, double s2,
+                     double* H, double* H2, double* bsc, hipStream_t s);
+void launch_sparse_transpose(const double* src, double* dst, int mpad, double scale, hipStream_t s);   // dst = scale src^T
+// G ([cpad][mpad]) = W R^T: the plain NT product on the tile (k_test_gemm), K = mpad
+void launch_sparse_weights(const double* W, const double* R, double* G, int cpad, int mpad, hipStream_t s);
+// the rectangular gradient pass (k_trace_cross<ARD, KIND>) over the rows_pad / 64 x mpad / 64 tiles of G, w = G + yv bv^T
+// (yv null: none); partials part[c * pstride + pofs + block], c = 0 .. nl (nl = 1 or ARD's d; column nl: sum w o K)
+void launch_trace_cross(const double* Xr, int nr, int rows_pad, const double* Z, int m, int d, int mpad, const CovFn& cf,
+                        const double* G, const double* yv, const double* bv, double* part, size_t pstride, size_t pofs,
+                        hipStream_t s);
+// what the last launch of an evaluation reads beside the trace partials
+struct SparseFinal {
+    const double *P, *Binv;        // ld x ld: their diagonals
+    const double *cp, *gp;         // c' = LB^-1 q and gamma' = LB^-T c' (gp is read for the gradient only)
+    const double *logdet;          // the factor of B: one share sum log L_ii per 128-tile
+    const double *yy;              // y'y
+    int m, ld, nt;
+    double n, sf2, s2, log_s2;     // N as a double, exp(2 theta_f), exp(2 theta_n), 2 theta_n
+};
+// one workgroup: out[0] = hout[0] = F and (part_uf given) out[1 ..] = hout[1 ..] = the nl + 2 components of d(-F) / dtheta
+void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t nb_uf, const double* part_uu, size_t nb_uu,
+                            int nl, double* out, double* hout, hipStream_t s);
+// mean = Vt c' / s2, var = sf2 - |Wt_t|^2 + |Vt_t|^2 + noise per test row (Wt, Vt: [>= nt][mpad])
+void launch_sparse_predict_finish(const double* Wt, const double* Vt, const double* cp, int mpad, int nt, double sf2,
+                                  double s2, double noise, double* mean, double* var, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -2850,6 +2850,116 @@ __global__ __launch_bounds__(256, 2) void k_loo_product(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
+// Sparse variational GP regression on inducing points (cugp_sparse_*): k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty,
+// k_sparse_wty_finish, k_sparse_yy, k_sparse_h, k_sparse_transpose, k_trace_cross, k_sparse_finalize,
+// k_sparse_predict_finish (sparse_device.h: a host can emulate them) and the one new product, k_sparse_gram
+// ------------------------------------------------------------------------------------------
+#include "sparse_device.h"
+
+// acc[m][n] += sum_{k in [kbeg, kend)} W[k][i0 + ..] W[k][j0 + ..]: the TN sibling of tile_nt -- the contraction index k is
+// the SLOW index of the one row-major operand W ([k][ld]; Ag -> W[0][i0], Bg -> W[0][j0]).  The LDS image, the fragment
+// reads and the MFMA loop are tile_nt's (tile_stage_mma: one per-lane base + immediates, no address arithmetic between
+// MFMAs); only the staging differs.  A thread takes one k PAIR (rows 2 kp, 2 kp + 1 of the stage) and one column pair per
+// 64 output rows: two 16-byte loads -- the 8 lanes of a column pair read 16 B of 16 different rows, a wave 128 contiguous
+// bytes of each of 16 rows, whole cache lines -- are turned in registers into the two 16-byte LDS entries
+// [plane kp][row i][k even, k odd] of the columns i, i + 1.  The 8 lanes of a ds_write_b128 group hold the 8 planes of ONE
+// row, 16 B apart modulo 128 (PLANE = rows * 16 + 16): no bank conflict, where lanes on consecutive rows of one plane
+// (32 B apart) would pair up on every bank.  The global addresses advance by one pointer add per row and stage.
+// kbeg, kend multiples of BK.  All 256 threads must call (barriers inside).
+template <int WM>
+__device__ __forceinline__ void tile_tn(const double* __restrict__ Ag, const double* __restrict__ Bg, int ld, int kbeg,
+                                        int kend, d4 (&acc)[WM][WM], char* smem)
+{
+    typedef Geo<WM> G;
+    constexpr int NQ = WM / 2;                            // column pairs per thread and operand: 64 rows of the tile each
+    const int t = opaque_tid();
+    const int lane = t & 63, wave = t >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int skp = t & 7, sip = t >> 3;
+    int wa[NQ][2], wb[NQ][2];                             // LDS byte offsets of my entries
+#pragma unroll
+    for (int q = 0; q < NQ; q++)
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const int row = 2 * (sip + 32 * q) + e;
+            wa[q][e] = skp * G::PLANE + row * 16;
+            wb[q][e] = G::OPER + skp * G::PLANE + bpos<WM>(row) * 16;
+        }
+    const int fr = lane & 15, fk = lane >> 4;
+    const int abase = (fk >> 1) * G::PLANE + (wr * 16 * WM + fr) * 16 + (fk & 1) * 8;
+    const int bbase = G::OPER + (fk >> 1) * G::PLANE + (wc * 16 * WM + fr) * 16 + (fk & 1) * 8;
+
+    const int nk = (kend - kbeg) / BK;
+    if (nk <= 0) return;
+    const size_t step = (size_t)BK * ld;
+    const double* pa0 = Ag + (size_t)(kbeg + 2 * skp) * ld + 2 * sip;
+    const double* pa1 = pa0 + ld;
+    const double* pb0 = Bg + (size_t)(kbeg + 2 * skp) * ld + 2 * sip;
+    const double* pb1 = pb0 + ld;
+    d2 ra[NQ][2], rb[NQ][2];
+
+#define CUGP_TN_LOAD()                                                                             \
+    do {                                                                                           \
+        _Pragma("unroll") for (int q = 0; q < NQ; q++) {                                           \
+            ra[q][0] = *(const d2*)(pa0 + 64 * q); ra[q][1] = *(const d2*)(pa1 + 64 * q);          \
+            rb[q][0] = *(const d2*)(pb0 + 64 * q); rb[q][1] = *(const d2*)(pb1 + 64 * q);          \
+        }                                                                                          \
+        pa0 += step; pa1 += step; pb0 += step; pb1 += step;                                        \
+    } while (0)
+#define CUGP_TN_STORE(buf)                                                                         \
+    do {                                                                                           \
+        _Pragma("unroll") for (int q = 0; q < NQ; q++)                                             \
+            _Pragma("unroll") for (int e = 0; e < 2; e++) {                                        \
+                *(d2*)((buf) + wa[q][e]) = (d2){ra[q][0][e], ra[q][1][e]};                         \
+                *(d2*)((buf) + wb[q][e]) = (d2){rb[q][0][e], rb[q][1][e]};                         \
+            }                                                                                      \
+    } while (0)
+#define CUGP_TN_STAGE(HALF, MORE)                                                                  \
+    do {                                                                                           \
+        const char* cur_ = smem + (HALF) * G::STAGE;                                               \
+        char* nxt_ = smem + (1 - (HALF)) * G::STAGE;                                               \
+        const bool more_ = (MORE);                                                                 \
+        if (more_) CUGP_TN_LOAD();                                                                 \
+        tile_stage_mma<WM>(cur_, abase, bbase, acc);                                               \
+        if (more_) CUGP_TN_STORE(nxt_);                                                            \
+        __syncthreads();                                                                           \
+    } while (0)
+
+    CUGP_TN_LOAD();
+    CUGP_TN_STORE(smem);
+    __syncthreads();
+    int kt = 0;
+    for (; kt + 1 < nk; kt += 2) {
+        CUGP_TN_STAGE(0, true);
+        CUGP_TN_STAGE(1, kt + 2 < nk);
+    }
+    if (kt < nk) CUGP_TN_STAGE(0, false);
+#undef CUGP_TN_STAGE
+#undef CUGP_TN_STORE
+#undef CUGP_TN_LOAD
+}
+
+// Gram product of one chunk of data rows: S_s(ti, tj) = sum_{k in split s} W[k][ti ..] W[k][tj ..] over the lower
+// 128-tiles of mp x mp, W = k(X_c, Z) Lu^-T ([kend][ld], k_predict_gemm's output: exact zeros in its rows beyond the
+// chunk and its columns beyond M).  Few output tiles (36 at M = 1024) and a long k: workgroup (tile, s) takes the k range
+// [s kstep, min((s + 1) kstep, kend)) and writes its partial tile to scratch slot s (pstride doubles apart, ld = the
+// matrix's); k_sparse_gram_finish adds the slots in index order: no atomics, the bits do not depend on which workgroup
+// ends first.  Grid: lower tiles * split.
+__global__ __launch_bounds__(256, 2) void k_sparse_gram(const double* __restrict__ W, int ld, int kend, int kstep,
+                                                        int split, double* __restrict__ scr, size_t pstride)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tile = blockIdx.x / split, s = blockIdx.x % split;
+    int ti, tj;
+    tri_index(tile, ti, tj);
+    const int k0 = s * kstep, k1 = k0 + kstep < kend ? k0 + kstep : kend;
+    d4 acc[4][4];
+    acc_zero(acc);
+    tile_tn<4>(W + ti * TILE, W + tj * TILE, ld, k0, k1, acc, smem);
+    tile_store(scr + (size_t)s * pstride + (size_t)ti * TILE * ld + tj * TILE, ld, acc, 1.0);
+}
+
+// ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
 // Per-launch timing without extra packets on the stream (profiling level 4, cugp_capi.cpp TimedLaunch): the next launch
@@ -2936,7 +3046,8 @@ static void set_big_lds()
     attr((const void*)k_syrk_step, STEP_LDS);
     attr((const void*)k_syrk_wide, GEMM_LDS);
     const void* gemm4[] = {(const void*)k_trtri_level<4>, (const void*)k_trtri_border<4>, (const void*)k_lauum<4>,
-                           (const void*)k_test_gemm, (const void*)k_predict_cov<4>, (const void*)k_loo_product<4>};
+                           (const void*)k_test_gemm, (const void*)k_predict_cov<4>, (const void*)k_loo_product<4>,
+                           (const void*)k_sparse_gram};
     for (const void* f : gemm4) attr(f, GEMM_LDS);
     attr((const void*)k_trtri_diag, TRTRI_LDS);
     attr((const void*)k_trtri_block, TRTRI_BLOCK_LDS);
@@ -3406,6 +3517,99 @@ void launch_trace_loo(const double* X, int n, int d, int npad, const CovFn& cf, 
                        b, part);
     hipLaunchKernelGGL(k_loo_finalize, dim3(1), dim3(256), 0, s, (const double*)part, nblocks, is_ard(cf) ? d : 1,
                        cf.h.noise_var, out, hout);
+}
+
+// ---- sparse variational GP regression on inducing points ----
+SparseShape sparse_shape(int n, int mpad, int chunk_rows, int pass)
+{
+    SparseShape c;
+    const int rows = chunk_rows > 0 ? chunk_rows : SPARSE_CHUNK_DEFAULT;
+    c.chunks = (int)(((long long)n + rows - 1) / rows);
+    c.r0 = (int)((long long)pass * rows < n ? (long long)pass * rows : n);
+    c.count = n - c.r0 < rows ? n - c.r0 : rows;
+    c.cpad = (c.count + TILE - 1) / TILE * TILE;
+    const int tiles = tri_count(mpad / TILE);
+    int split = SPARSE_GRAM_SLOTS / tiles;                // (128x128 workgroups, two per CU)
+    const int kmax = c.cpad / 256;                        // chunks of at least 256 k
+    if (split > kmax) split = kmax;
+    if (split > 64) split = 64;
+    const size_t pstride = (size_t)mpad * mpad;
+    while (split > 1 && (size_t)split * pstride * sizeof(double) > ((size_t)1 << 30)) split--;   // scratch <= 1 GiB
+    if (split < 1) split = 1;
+    c.kstep = ((c.cpad + split - 1) / split + BK - 1) / BK * BK;
+    c.split = c.kstep > 0 ? (c.cpad + c.kstep - 1) / c.kstep : 1;
+    if (c.split < 1) c.split = 1;
+    return c;
+}
+
+void launch_sparse_gram(const double* W, int mpad, const SparseShape& c, double* P, double* scr, bool first, hipStream_t s)
+{
+    set_big_lds();
+    const int tiles = tri_count(mpad / TILE);
+    const size_t pstride = (size_t)mpad * mpad;
+    CUGP_LAUNCH(k_sparse_gram, dim3(tiles * c.split), dim3(256), GEMM_LDS, s, W, mpad, c.cpad, c.kstep, c.split, scr,
+                pstride);
+    hipLaunchKernelGGL(k_sparse_gram_finish, dim3(tiles * 16), dim3(256), 0, s, P, mpad, (const double*)scr, pstride,
+                       c.split, first ? 1 : 0);
+}
+
+void launch_sparse_wty(const double* W, int mpad, int cpad, const double* y, double* part, double* q, bool first,
+                       hipStream_t s)
+{
+    const int slabs = cpad / TILE;
+    hipLaunchKernelGGL(k_sparse_wty, dim3((mpad / KT) * slabs), dim3(256), 0, s, W, mpad, y, part);
+    hipLaunchKernelGGL(k_sparse_wty_finish, dim3((mpad + 255) / 256), dim3(256), 0, s, (const double*)part, slabs, mpad, q,
+                       first ? 1 : 0);
+}
+
+void launch_sparse_yy(const double* y, int n, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_yy, dim3(1), dim3(256), 0, s, y, n, out);
+}
+
+void launch_sparse_form_b(const double* P, int mpad, double s2, double* Bm, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_form_b, dim3(tri_count(mpad / TILE) * 16), dim3(256), 0, s, P, mpad, s2, Bm);
+}
+
+void launch_sparse_h(const double* Binv, const double* P, const double* gp, const double* bp, int m, int mpad, double s2,
+                     double* H, double* H2, double* bsc, hipStream_t s)
+{
+    const int nb = mpad / KT;
+    hipLaunchKernelGGL(k_sparse_h, dim3(nb * nb), dim3(256), 0, s, Binv, P, gp, bp, m, mpad, s2, H, H2, bsc);
+}
+
+void launch_sparse_transpose(const double* src, double* dst, int mpad, double scale, hipStream_t s)
+{
+    const int nb = mpad / KT;
+    hipLaunchKernelGGL(k_sparse_transpose, dim3(nb * nb), dim3(256), 0, s, src, dst, mpad, scale);
+}
+
+void launch_sparse_weights(const double* W, const double* R, double* G, int cpad, int mpad, hipStream_t s)
+{
+    launch_test_gemm_nt(W, R, G, cpad, mpad, mpad, s);       // k_test_gemm: the plain NT product on the tile
+}
+
+void launch_trace_cross(const double* Xr, int nr, int rows_pad, const double* Z, int m, int d, int mpad, const CovFn& cf,
+                        const double* G, const double* yv, const double* bv, double* part, size_t pstride, size_t pofs,
+                        hipStream_t s)
+{
+    const dim3 grid((rows_pad / KT) * (mpad / KT));
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_cross), grid, dim3(256), 0, s, Xr, nr, Z, m, d, mpad, cf.h, cf.hd, G, yv,
+                       bv, part, pstride, pofs);
+}
+
+void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t nb_uf, const double* part_uu, size_t nb_uu,
+                            int nl, double* out, double* hout, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_finalize, dim3(1), dim3(256), 0, s, f, part_uf, nb_uf, part_uu, nb_uu, nl, out, hout);
+}
+
+void launch_sparse_predict_finish(const double* Wt, const double* Vt, const double* cp, int mpad, int nt, double sf2,
+                                  double s2, double noise, double* mean, double* var, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_predict_finish, dim3((nt + 3) / 4), dim3(256), 0, s, Wt, Vt, cp, mpad, nt, sf2, s2, noise,
+                       mean, var);
 }
 
 void launch_test_gemm_nt(const double* A, const double* B, double* C, int m, int n, int k, hipStream_t s)

@@ -467,6 +467,121 @@ class Covsum:
         return {"sum_ms": s.value, "launches": n.value, "flop": f.value, "disp_ms": dms.value}
 
 
+class SparseGP:
+    """Sparse variational GP regression on m inducing inputs (cugp_sparse_*; Titsias 2009): n data rows streamed in
+    chunks of chunk_rows (0: the library's choice) against Z [m, d], given by the caller and fixed.  kernel / ard as
+    Covsum's; the hyper-parameter vector is Covsum's ([log l, log sf, log sn], ARD [log l_1 .. log l_d, log sf, log sn]);
+    jitter is the absolute eps of Kuu = k(Z, Z) + eps I.  bound() is a lower bound on the exact log marginal likelihood
+    of all n rows; gradients are those of -bound, in loglik_grad's convention and order."""
+
+    def __init__(self, n, m, d, device=0, kernel="se", ard=False, jitter=1e-6, chunk_rows=0):
+        self.n, self.m, self.d, self.device = int(n), int(m), int(d), int(device)
+        self._kind, self.ard = kernel_spec(kernel, ard)
+        self.nh = self.d + 2 if self.ard else 3
+        self.jitter, self.chunk_rows = float(jitter), int(chunk_rows)
+        self._h = C.c_void_p()
+        check(capi.lib().cugp_sparse_create(self.n, self.m, self.d, self.device, self._kind, 1 if self.ard else 0,
+                                            self.jitter, self.chunk_rows, C.byref(self._h)))
+
+    @classmethod
+    def from_subset(cls, X, y, m, seed=0, **kw):
+        """A model over (X, y) whose inducing inputs are m rows of X drawn without replacement (numpy default_rng(seed)),
+        in ascending row order; data and Z are set."""
+        X, y = f64(X), f64(y)
+        rows = np.sort(np.random.default_rng(seed).choice(X.shape[0], int(m), replace=False))
+        s = cls(X.shape[0], int(m), X.shape[1], **kw)
+        s.set_data(X, y)
+        s.set_inducing(X[rows])
+        return s
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            capi.lib().cugp_sparse_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def handle(self):
+        return self._h
+
+    def set_data(self, X, y):
+        X, y = f64(X), f64(y)
+        if X.shape != (self.n, self.d) or y.shape != (self.n,):
+            raise ValueError("expected X %s and y %s" % ((self.n, self.d), (self.n,)))
+        check(capi.lib().cugp_sparse_set_data(self._h, ptr(X), ptr(y)))
+
+    def set_inducing(self, Z):
+        Z = f64(Z)
+        if Z.shape != (self.m, self.d):
+            raise ValueError("expected Z %s" % ((self.m, self.d),))
+        check(capi.lib().cugp_sparse_set_inducing(self._h, ptr(Z)))
+
+    def set_loghyperparam(self, hp):
+        hp = f64(hp)
+        if hp.shape != (self.nh,):
+            raise ValueError("expected %d log-hyper-parameters" % self.nh)
+        check(capi.lib().cugp_sparse_set_loghyper(self._h, ptr(hp), self.nh))
+
+    def get_loghyperparam(self):
+        out = np.empty(self.nh)
+        check(capi.lib().cugp_sparse_get_loghyper(self._h, ptr(out), self.nh))
+        return out
+
+    def bound(self):
+        """F, the variational lower bound on the log marginal likelihood (cugp_sparse_bound)."""
+        F = C.c_double()
+        check(capi.lib().cugp_sparse_bound(self._h, C.byref(F)))
+        return F.value
+
+    def bound_grad(self):
+        """(F, g): the bound and the gradient of -F [nh] (cugp_sparse_bound_grad)."""
+        F, g = C.c_double(), np.empty(self.nh)
+        check(capi.lib().cugp_sparse_bound_grad(self._h, C.byref(F), ptr(g), self.nh))
+        return F.value, g
+
+    def predict(self, Xtest, with_noise=True):
+        """(mean, var) at the test points (cugp_sparse_predict); with_noise adds exp(2 theta_n) to the variance."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        m, v = np.empty(Xt.shape[0]), np.empty(Xt.shape[0])
+        check(capi.lib().cugp_sparse_predict(self._h, ptr(Xt), Xt.shape[0], 1 if with_noise else 0, ptr(m), ptr(v)))
+        return m, v
+
+    def cg_solve(self, budget=100):
+        """Conjugate gradients on -F from the current hyper-parameters (cugp_sparse_cg_solve); the trace [n_iterates,
+        nh + 1] = (theta, -F) of the start and of the point every line search ended at, as Covsum.cg_solve_loo's."""
+        budget = int(budget)
+        tr = np.full((4 * max(budget, 0) + 8, self.nh + 1), np.nan)
+        ne = C.c_int()
+        check(capi.lib().cugp_sparse_cg_solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        rows = 1
+        while rows < min(ne.value, tr.shape[0]) and not np.isnan(tr[rows, 0]):
+            rows += 1
+        return tr[:rows]
+
+    def plan(self):
+        """The schedule (cugp_sparse_plan): one (row0, rows, rows_padded, split, kstep) per pass over the data."""
+        return sparse_plan(self.n, self.m, self.chunk_rows)
+
+
+def sparse_plan(n, m, chunk_rows=0):
+    """cugp_sparse_plan's passes for n rows against m inducing inputs: [(row0, rows, rows_padded, split, kstep)]."""
+    out = (C.c_int * 5)()
+    passes, i = [], 0
+    while True:
+        count = capi.lib().cugp_sparse_plan(int(n), int(m), int(chunk_rows), i, out)
+        if count < 0:
+            check(count)
+        passes.append(tuple(out))
+        i += 1
+        if i >= count:
+            return passes
+
+
 class Comm:
     """The library's own RCCL communicator (cugp_comm_*, csrc/comm.cpp): one process per GPU, expert k on rank k mod W.
     `unique_id`: the 128 bytes rank 0 got from Comm.unique_id(), handed to every rank by the caller (ShardedBCM

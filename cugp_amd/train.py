@@ -40,9 +40,32 @@ def train_loo(args, local):
     g.close()
 
 
+def train_sparse(args, local):
+    """One model over chunk 0's rows with --inducing M inducing inputs drawn from them (SparseGP.from_subset), conjugate
+    gradients on the negative variational bound; prints what the default objective's run prints."""
+    from . import dataset
+    from .gp import Covsum, SparseGP, kernel_spec
+    X, y = dataset.load_chunk("%s0.txt" % args.inputs, "%s0.txt" % args.labels)
+    Xt, yt = X[args.rows:args.rows + args.test_rows], y[args.rows:args.rows + args.test_rows]
+    X, y = X[:args.rows], y[:args.rows]
+    ard = kernel_spec(args.kernel, args.ard)[1]
+    g = SparseGP.from_subset(X, y, args.inducing, device=local, kernel=args.kernel, ard=args.ard)
+    g.set_loghyperparam([args.hp[0]] * (g.nh - 2) + list(args.hp[1:]) if ard else args.hp)
+    t0 = time.perf_counter()
+    trace = g.cg_solve(args.budget)
+    dt = time.perf_counter() - t0
+    hp = g.get_loghyperparam()
+    print("\n\n PLEASE-SEE %d : %s\n" % (g.nh, ", ".join("%f" % v for v in hp)))
+    print("TOTAL training time = %f  (%d iterates, final -F %.9g)" % (dt, trace.shape[0], trace[-1, -1]))
+    if args.test_rows > 0:
+        m, v = g.predict(Xt, with_noise=True)
+        print("NLPP = %.12g" % Covsum.get_negative_log_predprob(yt, m, v))
+    g.close()
+
+
 def main(argv=None, parse_only=False):
-    """parse_only: -> the parsed arguments (--objective loo is refused there, before any device is touched, where it is
-    not built)."""
+    """parse_only: -> the parsed arguments (--objective loo and --inducing are refused there, before any device is
+    touched, where they are not built)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--numchunks", type=int, required=True)
     ap.add_argument("--rows", type=int, required=True, help="training rows per chunk (numtrain)")
@@ -65,7 +88,16 @@ def main(argv=None, parse_only=False):
                     help="what cg_solve minimises: ll, the negative marginal log-likelihood (the reference's), or loo, the "
                          "negative sum of the leave-one-out log predictive densities (GPML 5.4.2) -- one expert in one "
                          "process only (--numchunks 1): there is no LOO for a product of experts")
+    ap.add_argument("--inducing", type=int, default=0, metavar="M",
+                    help="sparse variational GP regression on M inducing inputs, a random subset of the training rows, "
+                         "instead of the exact model: cg_solve maximises the variational bound -- one model in one process "
+                         "only (--numchunks 1, --objective ll)")
     args = ap.parse_args(argv)
+    if args.inducing < 0 or args.inducing > args.rows:
+        ap.error("--inducing must lie between 1 and --rows")
+    if args.inducing and (args.numchunks != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.objective != "ll"):
+        ap.error("--inducing needs --numchunks 1, one process and --objective ll: the sparse model is built for a single "
+                 "model over all rows")
     if args.objective == "loo" and (args.numchunks != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1):
         ap.error("--objective loo needs --numchunks 1 and one process: leave-one-out is built for a single expert")
     if parse_only:
@@ -83,6 +115,8 @@ def main(argv=None, parse_only=False):
     torch.cuda.set_device(local)
     if args.objective == "loo":
         return train_loo(args, local)
+    if args.inducing:
+        return train_sparse(args, local)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if args.backend == "nccl":

@@ -321,6 +321,69 @@ int cugp_loo(cugp_gp *gp, double *lpl, double *g /* nh, may be NULL */, int nh);
 int cugp_loo_predict(cugp_gp *gp, double *mean /* n */, double *var /* n */, double *logp /* n, may be NULL */);
 int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int *nevals);
 
+/* ---- sparse variational GP regression on M inducing inputs (SGPR: Titsias 2009, "Variational learning of inducing
+ *      variables in sparse Gaussian processes"; GPML ch. 8 for the family; GPflow's SGPR).  No reference counterpart.
+ *      Data X [N][d], y [N]; inducing inputs Z [M][d], given by the caller and fixed; the hyper-parameters, their order
+ *      and nh (3, ARD d + 2) and the five covariance families are those of a cugp_gp; s2 = exp(2 theta_n), sf2 =
+ *      exp(2 theta_f); eps an absolute jitter fixed at creation (not a hyper-parameter, no gradient).  With
+ *        Kuu = k(Z,Z) + eps I,  Kuf = k(Z,X),  Qff = Kfu Kuu^-1 Kuf
+ *        F(theta) = -N/2 log 2 pi - 1/2 log|Qff + s2 I| - 1/2 y'(Qff + s2 I)^-1 y - (N sf2 - tr Qff) / (2 s2)
+ *      a lower bound on the exact log marginal likelihood of all N rows (log 2 pi exactly here, not LL's literal), computed as
+ *        Lu = chol(Kuu),  A = Lu^-1 Kuf / s,  B = I + A A',  LB = chol(B),  c = LB^-1 A y / s
+ *        F = -N/2 log 2 pi - 1/2 log|B| - N/2 log s2 - y'y / (2 s2) + 1/2 c'c - N sf2 / (2 s2) + 1/2 tr(A A')
+ *      in O(N M^2) time and O(M^2 + chunk_rows M) memory: the data is streamed in chunks of chunk_rows rows, A A' and A y
+ *      are sums over the rows (a split-k Gram product on the MFMA tile, partial tiles added in a fixed order: equal inputs
+ *      and chunk_rows give equal bits).  Prediction at x*, ks = k(Z, x*):
+ *        mean = (Lu^-1 ks)' LB^-T c,   var_f = sf2 - |Lu^-1 ks|^2 + |LB^-1 Lu^-1 ks|^2   (+ s2 with noise)
+ *      Gradient: with Phi = Kuf Kfu, v = Kuf y, Sigma = Kuu + Phi / s2, beta = Sigma^-1 v / s2,
+ *        G_Phi = (Kuu^-1 - Sigma^-1 - beta beta') / (2 s2),  G_uu = Kuu^-1 / 2 - (Sigma^-1 + beta beta') / 2 - Kuu^-1 Phi Kuu^-1 / (2 s2)
+ *        G_uf = 2 G_Phi Kuf + (beta / s2) y'   [M x N]
+ *        dF/dtheta_j = sum G_uu o dKuu/dtheta_j + sum G_uf o dKuf/dtheta_j   (- N sf2 / s2 for theta_f)
+ *        dF/dtheta_n = 2 s2 [-N / (2 s2) + tr(Sigma^-1 Phi) / (2 s2^2) + y'y / (2 s2^2) - v'beta / s2^2 + beta'Phi beta / (2 s2^2)
+ *                            + (N sf2 - tr Kuu^-1 Phi) / (2 s2^2)]
+ *      through Lu and LB (Sigma^-1 = Lu^-T B^-1 Lu^-1), one weight product and one rectangular trace pass per chunk for any nh.
+ * cugp_sparse_create      : kernel CUGP_KERNEL_*; ard != 0: one length scale per dimension; jitter > 0 (1e-6 is customary);
+ *                           chunk_rows 0 (the library's choice, 16384) or a multiple of 128.  m <= CUGP_SPARSE_MAX_M: the padded
+ *                           m^2 stays below 2^31, so every element offset of the inner factorisation's kernels fits an int.
+ * cugp_sparse_dims        : any pointer may be NULL; chunk_rows as resolved
+ * cugp_sparse_set_data    : X [n][d], y [n], host; kept on the device.  cugp_sparse_set_inducing: Z [m][d], host.
+ * cugp_sparse_set_loghyper / _get_loghyper: nh entries (nh must equal cugp_sparse_num_hyper), all zero after creation
+ * cugp_sparse_bound       : *F <- the bound.  cugp_sparse_bound_grad: also g <- the nh components of the gradient of -F, in
+ *                           cugp_loglik_grad's convention and order.  The results of one (data, Z, theta) are kept.
+ * cugp_sparse_predict     : mean and var at nt test points (host), with_noise != 0 adds s2; the test points are taken in
+ *                           passes of whole 128-row tiles; it reuses the state of the last bound evaluation and evaluates
+ *                           first when that is stale.
+ * cugp_sparse_cg_solve    : the loop of cugp_cg_minimize_n on f = -F from the current hyper-parameters; the end point stays
+ *                           set.  trace (may be NULL): rows of nh + 1 doubles [theta, f] of the ITERATES, as
+ *                           cugp_cg_solve_loo records them (f never rises along it; the row behind the last is NaN where
+ *                           trace_cap leaves room).  *nevals <- evaluations made.
+ * cugp_sparse_plan        : the schedule, pure arithmetic (no device): pass i streams the rows [out[0], out[0] + out[1]),
+ *                           padded to out[2] (a multiple of 128); its Gram launch splits the k range [0, out[2]) of every
+ *                           output tile out[3] ways, split s taking [s out[4], min((s + 1) out[4], out[2])); returns the
+ *                           number of passes, CUGP_ERR_INVALID for a pass beyond the last.
+ * Refusals, all CUGP_ERR_INVALID with the call's name in cugp_last_error before any device work: a NULL argument; n, d or
+ * m < 1; m > CUGP_SPARSE_MAX_M; an unknown kernel kind; chunk_rows negative or not a multiple of 128; a jitter that is not
+ * positive and finite; an nh that is not the handle's; nt <= 0; budget <= 0; an evaluation, prediction or solve before the
+ * data or the inducing inputs are set.  CUGP_ERR_NODEVICE from cugp_sparse_create without a GPU.  A Kuu or B that is not
+ * positive definite gives NaN results with CUGP_OK (the header's convention).
+ * Not built: gradients with respect to Z; data sharded across GPUs (A A' and A y are sums over rows: one all-reduce); FITC;
+ * multi-target; a C++ mirror in cugp_amd/host/. */
+#define CUGP_SPARSE_MAX_M 32768
+typedef struct cugp_sparse cugp_sparse;
+int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, cugp_sparse **out);
+int cugp_sparse_destroy(cugp_sparse *sp);
+int cugp_sparse_dims(const cugp_sparse *sp, int *n, int *m, int *d, int *mpad, int *chunk_rows);
+int cugp_sparse_num_hyper(const cugp_sparse *sp, int *nh);
+int cugp_sparse_set_data(cugp_sparse *sp, const double *X /* [n][d], host */, const double *y /* n */);
+int cugp_sparse_set_inducing(cugp_sparse *sp, const double *Z /* [m][d], host */);
+int cugp_sparse_set_loghyper(cugp_sparse *sp, const double *hp, int nh);
+int cugp_sparse_get_loghyper(const cugp_sparse *sp, double *hp, int nh);
+int cugp_sparse_bound(cugp_sparse *sp, double *F);
+int cugp_sparse_bound_grad(cugp_sparse *sp, double *F, double *g /* nh */, int nh);
+int cugp_sparse_predict(cugp_sparse *sp, const double *Xt, int nt, int with_noise, double *mean /* nt */, double *var /* nt */);
+int cugp_sparse_cg_solve(cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals);
+int cugp_sparse_plan(int n, int m, int chunk_rows, int pass, int out[5]);
+
 /* ---- stand-alone dense LA on a caller matrix (common/matrixops.h:5-25) ----
  * cugp_potrf        : get_cholesky            (L lower, upper zeroed)
  * cugp_potri        : compute_K_inverse
@@ -607,7 +670,8 @@ int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, dou
 int cugp_mfma_peak_tflops(int device, double *tflops);
 /* stand-alone LA timings on a device-built SPD matrix (ms, best of reps): op 0 Cholesky (cuda_src/
  * cholesky_cu_solver.cpp), 1 triangular inverse of the factor (tmi_cu_solver.cpp), 2 K^-1 from it, 3 all three,
- * 4 plain C = K K^T with uniform tiles (cublas_matrix_multiply.cpp) */
+ * 4 plain C = K K^T with uniform tiles (cublas_matrix_multiply.cpp), 5 the sparse model's Gram product of one chunk:
+ * P = W^T W over the lower tiles for W [16384][n] (k_sparse_gram's split-k partial tiles and their fixed-order sum) */
 int cugp_bench_la(int op, int n, int device, int reps, double *ms);
 /* the same, and for ops 0 and 3 log|K| taken from the factor the timed launches produced (NaN otherwise) */
 int cugp_bench_la_check(int op, int n, int device, int reps, double *ms, double *logdet);
