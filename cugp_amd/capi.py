@@ -174,6 +174,8 @@ SIGNATURES = {
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),
     "cugp_set_handle_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "cugp_get_handle_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+    "cugp_chain_first": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_pipe_block_for": (C.c_int, [C.c_int]),
     "cugp_bench_la": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "cugp_bench_la_check": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "cugp_potrf_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip]),

@@ -162,10 +162,11 @@ int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int 
         int rc = ard ? cugp_create_ard_kernel(rows[k], d, ds.device, pad_to, kernel, &g)
                      : cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
         if (rc) { cugp_bcm_destroy(b); return rc; }
-        cugp_mark_bcm_expert(g);                        // (cugp_append refuses the experts of a BCM)
+        b->experts.push_back(g);                        // (owned by b from here on: cugp_bcm_destroy)
+        rc = cugp_mark_bcm_expert(g);                   // (cugp_append refuses the experts of a BCM; no stream priorities)
         // several experts on one device already fill each other's idle time; the extra streams only cost launches
-        if (nexperts > nsets) cugp_set_overlap(g, 0);
-        b->experts.push_back(g);
+        if (!rc && nexperts > nsets) rc = cugp_set_overlap(g, 0);
+        if (rc) { cugp_bcm_destroy(b); return rc; }
         b->rows.push_back(rows[k]);
         ds.idx.push_back(k);
     }

@@ -110,6 +110,8 @@ struct cugp_gp {
     hipStream_t aux = nullptr;      // ... except the inverse blocks that run beside the factorisation (fork/join by events):
     hipStream_t aux2 = nullptr;     // aux = the large products, aux2 = each block's own small inverse,
     hipStream_t lq = nullptr;       // lq = each block's share of K^-1 (beside the next block's bordering)
+    int prio_main = 0, prio_inv = 0;   // priorities the streams were created with (stream, the other three): apply_stream_prio
+    bool chain_first = false;       // ... stream runs at the device's highest priority (cugp_chain_first)
     std::vector<hipEvent_t> bev;    // fork events, one per inverse block; last: "Wt of the last block rows complete" (aux -> main)
     std::vector<hipEvent_t> oev;    // "block's own inverse done" events (aux2 -> aux); last block: z, alpha done (aux2 -> main)
     std::vector<hipEvent_t> lev;    // "block's inverse rows final" events (aux -> lq / main -> aux2); last: K^-1 shares so far (-> main)
@@ -406,15 +408,78 @@ int barrier_cap(cugp_gp* g)
     return g->overlap && share >= 16 ? share / 2 : share;
 }
 
-// block rows per hand-over to the other streams: about a sixteenth of the matrix, at least 2 tiles (interleaved
-// A/B at 16, 32, 64 and 79 tiles: 2, 2-3, 4, 5 were the best), single tiles up to 8 tiles (600 and 1000 rows: -9 %
-// and -3 % against 2), or as tuned; 0 = no hand-over (everything on the main stream after the factorisation)
+// block rows per hand-over to the other streams, or as tuned; 0 = no hand-over (everything on the main stream after the
+// factorisation).  A handle evaluated alone: by size, cugp_pipe_block_for.  Expert groups and the experts of a BCM (a
+// lone BCM expert is a group of one, and an expert gives the same bits grouped or not): about a sixteenth of the
+// matrix, at least 2 tiles, single tiles up to 8 tiles -- the rule their A/B runs were made under (16 x 1500,
+// 8 x 3000, 4 x 6000 rows), left as it was.
 int pipe_block(const cugp_gp* g, bool with_inverse)
 {
     const bool overlap = g->grp ? g->grp->overlap : g->overlap;
     int w = (with_inverse && overlap) ? g->tune[TUNE_PIPE_BLOCK] : 0;
-    if (w < 0) w = g->nt <= 8 ? 1 : ((g->nt + 8) / 16 > 2 ? (g->nt + 8) / 16 : 2);
+    if (w < 0) w = !g->grp && !g->bcm_expert ? cugp_pipe_block_for(g->nt)
+                                            : g->nt <= 8 ? 1 : ((g->nt + 8) / 16 > 2 ? (g->nt + 8) / 16 : 2);
     return w >= g->nt ? 0 : w;
+}
+
+// ---- stream priorities ----
+// The factorisation is a chain of ~2 nt launches, most of them small (k_trsm_inv64: 30 workgroups, 7 us alone); the
+// inverse streams beside it launch 1000-2000 workgroups of 134 us each, and a chain launch that arrives behind one waits
+// for a whole round of them to drain (8192 rows: a dozen times per evaluation, 140-190 us each).  With the chain's
+// stream at the highest priority those waits get shorter and fewer, not none (k_trsm_inv64 3.05 -> 2.62 ms per
+// evaluation, 14 -> 11 launches over 100 us), and the inverse launches longer.  That pays only where the chain competes with
+// large launches of the same handle: not in expert groups or BCMs (prioritised streams share few hardware queues, which
+// serialised the experts of a BCM evaluated on one device: 8 x 3000 rows 6.6 -> 17.4 ms), not without the hand-over,
+// and not below TUNE_PRIO_MIN_NT tile rows.  Results never depend on it: the order on every stream is fixed.
+bool want_chain_first(const cugp_gp* g)
+{
+    const int v = g->tune[TUNE_STREAM_PRIO];
+    if (v != 0) return (v & 4) == 0 && (v & 1) != 0;
+    return !g->bcm_expert && g->groups == 0 && !g->is_factor && g->overlap && g->tune[TUNE_PIPE_BLOCK] != 0 &&
+           g->nt >= g->tune[TUNE_PRIO_MIN_NT];
+}
+
+// Create the handle's four streams, or re-create them where the priorities they were created with are no longer the
+// ones the handle's tuning, membership and size ask for.  Called with no evaluation in flight and never from inside
+// one (creation, cugp_set_data, cugp_set_handle_tuning, cugp_set_overlap, joining a group or a BCM, becoming another
+// handle's factor handle); without a change it costs two comparisons.  Leaving a group (cugp_group_destroy) is NOT such a
+// place: a former expert stays at default priorities until its next cugp_set_data.  Captured graphs are captured again (they replay on the stream they are launched into, but
+// the epoch is the one rule for "the handle's launch set-up changed").
+int apply_stream_prio(cugp_gp* g)
+{
+    const int v = g->tune[TUNE_STREAM_PRIO];
+    const bool first = want_chain_first(g), inv_low = (v & 4) == 0 && (v & 2) != 0;
+    int plo = 0, phi = 0;
+    if (first || inv_low) HIPCHK(hipDeviceGetStreamPriorityRange(&plo, &phi));
+    const int pmain = first ? phi : 0, pinv = inv_low ? plo : 0;
+    hipStream_t* const all[4] = {&g->stream, &g->aux, &g->aux2, &g->lq};
+    if (g->stream && pmain == g->prio_main && pinv == g->prio_inv) return CUGP_OK;
+    // The new set is created first and the old one given up only when all four exist: a failure leaves the handle on
+    // the streams it had (never on a null stream, which would be the device's default stream).
+    hipStream_t fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 4 && e == hipSuccess; i++) {
+        const int p = i == 0 ? pmain : pinv;
+        // (default priorities everywhere: the plain call, as before there was a rule)
+        e = pmain == 0 && pinv == 0 ? hipStreamCreateWithFlags(&fresh[i], hipStreamNonBlocking)
+                                    : hipStreamCreateWithPriority(&fresh[i], hipStreamNonBlocking, p);
+    }
+    for (int i = 0; i < 4 && e == hipSuccess; i++)
+        if (*all[i]) e = hipStreamSynchronize(*all[i]);
+    if (e != hipSuccess) {
+        for (hipStream_t s : fresh)
+            if (s) (void)hipStreamDestroy(s);
+        return fail(CUGP_ERR_DEVICE, "apply_stream_prio: the handle keeps the streams it had", e);
+    }
+    for (int i = 0; i < 4; i++) {
+        if (*all[i]) (void)hipStreamDestroy(*all[i]);
+        *all[i] = fresh[i];
+    }
+    g->prio_main = pmain;
+    g->prio_inv = pinv;
+    g->chain_first = first;
+    g->cfg_epoch++;
+    return CUGP_OK;
 }
 
 // one timed launch: event pair + bookkeeping.  Levels 2 and 3 record an event in front of and behind the launch on its
@@ -1145,21 +1210,9 @@ static int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_
     g_live[device < 64 ? device : 63].fetch_add(1, std::memory_order_relaxed);
     g->counted = true;
     hipError_t e = hipSetDevice(device);
-    // default priority everywhere: prioritised streams share few hardware queues, which serialises the
-    // experts of a BCM evaluated on one device
-    // (TUNE_STREAM_PRIO, an A/B hook: the factorisation's stream at the highest and / or the inverse streams at the
-    //  lowest priority)
-    int plo = 0, phi = 0;
-    if (e == hipSuccess && g->tune[TUNE_STREAM_PRIO] != 0) e = hipDeviceGetStreamPriorityRange(&plo, &phi);
-    const int pmain = (g->tune[TUNE_STREAM_PRIO] & 1) ? phi : 0, pinv = (g->tune[TUNE_STREAM_PRIO] & 2) ? plo : 0;
-    auto mkstream = [&](hipStream_t* s, int prio) {
-        return g->tune[TUNE_STREAM_PRIO] != 0 ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, prio)
-                                             : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-    };
-    if (e == hipSuccess) e = mkstream(&g->stream, pmain);
-    if (e == hipSuccess) e = mkstream(&g->aux, pinv);
-    if (e == hipSuccess) e = mkstream(&g->aux2, pinv);
-    if (e == hipSuccess) e = mkstream(&g->lq, pinv);
+    // the four streams, at the priorities the handle's size and tuning ask for (want_chain_first; a handle that joins a
+    // group or a BCM later gets them re-created there)
+    if (e == hipSuccess && apply_stream_prio(g) != CUGP_OK) e = hipErrorUnknown;
     for (std::vector<hipEvent_t>* v : {&g->bev, &g->oev, &g->lev}) {
         v->assign((size_t)g->nt + 2, nullptr);
         for (size_t i = 0; i < v->size() && e == hipSuccess; i++) e = hipEventCreateWithFlags(&(*v)[i], hipEventDisableTiming);
@@ -1239,8 +1292,10 @@ int cugp_destroy(cugp_gp* g)
 int cugp_set_overlap(cugp_gp* g, int enable)
 {
     if (!g) return CUGP_ERR_INVALID;
-    g->overlap = enable != 0;
-    return CUGP_OK;                                          // (a captured graph is only used without hand-over)
+    int rc;
+    if ((rc = use_device(g)) || (rc = fetch_eval(g))) return rc;
+    g->overlap = enable != 0;                                // (a captured graph is only used without hand-over)
+    return apply_stream_prio(g);                             // (without the hand-over nothing runs beside the chain)
 }
 
 int cugp_dims(const cugp_gp* g, int* n, int* d, int* npad)
@@ -1258,6 +1313,8 @@ static int set_data_common(cugp_gp* g, const double* X, const double* y, hipMemc
     int rc;
     if ((rc = use_device(g))) return rc;
     if ((rc = fetch_eval(g))) return rc;
+    sync_tuning(g);                                        // (the process defaults may have moved since the handle was created)
+    if ((rc = apply_stream_prio(g))) return rc;
     HIPCHK(hipMemcpyAsync(g->dX, X, (size_t)g->n * g->d * sizeof(double), kind, g->stream));
     HIPCHK(hipMemsetAsync(g->dy, 0, (size_t)g->npad * sizeof(double), g->stream));
     HIPCHK(hipMemcpyAsync(g->dy, y, (size_t)g->n * sizeof(double), kind, g->stream));
@@ -1765,7 +1822,8 @@ static int cov_factor_handle(cugp_gp* g, int tiles)
         f->counted = false;
         f->overlap = false;
         f->is_factor = true;
-        if ((rc = ensure_factor_bufs(f))) { cugp_destroy(f); return rc; }
+        // (created before the two flags were set: a factor handle of TUNE_PRIO_MIN_NT tile rows got a prioritised stream)
+        if ((rc = apply_stream_prio(f)) || (rc = ensure_factor_bufs(f))) { cugp_destroy(f); return rc; }
         g->cov_f = f;
         g->cov_tiles = tiles;
         if ((rc = use_device(g))) return rc;
@@ -2021,7 +2079,9 @@ int cugp_mark_bcm_expert(cugp_gp* g)
 {
     if (!g) return CUGP_ERR_INVALID;
     g->bcm_expert = true;
-    return CUGP_OK;
+    int rc;
+    if ((rc = use_device(g)) || (rc = fetch_eval(g))) return rc;
+    return apply_stream_prio(g);                             // (an expert's streams carry no priority)
 }
 
 // ---------------------------------------------------------------- intermediates
@@ -3121,7 +3181,40 @@ int cugp_set_handle_tuning(cugp_gp* g, int key, int value, int own)
         g->tune[key] = value;
         if (key != TUNE_GRAPHS) g->cfg_epoch++;
     }
+    if (key != TUNE_STREAM_PRIO && key != TUNE_PRIO_MIN_NT && key != TUNE_PIPE_BLOCK) return CUGP_OK;
+    if (!own) sync_tuning(g);
+    if ((rc = use_device(g))) return rc;
+    return apply_stream_prio(g);
+}
+
+// 1: the handle's factorisation stream is at the device's highest priority (kernels.h TUNE_STREAM_PRIO: the rule, or the
+// key's explicit bit 0), so its next evaluation runs chain-first; 0: default priority
+int cugp_chain_first(const cugp_gp* g, int* on)
+{
+    if (!g || !on) return fail(CUGP_ERR_INVALID, "cugp_chain_first: null argument");
+    *on = g->chain_first ? 1 : 0;
     return CUGP_OK;
+}
+
+// Tile rows per hand-over of the inverse to the other streams for a matrix of nt tile rows evaluated alone (what
+// TUNE_PIPE_BLOCK < 0 means; pure arithmetic, no device).  From interleaved A/B runs of uniform blocks of 2 ... 8 tiles
+// at 32, 47, 64, 79 and 128 tile rows, with and without the factorisation's stream prioritised
+// (profiles/r07_sweep_handover_prio.txt; against "about nt / 16", in % of the evaluation, without / with priority):
+//   32 tiles: 2 and 4 equal, 5 and more +3 %;  47 tiles: 3, 4 and 6 within the spread, 2 +3 %   -> nt / 16 stays
+//   64 tiles: 5 -0.8 / -1.2 %, 8 -0.2 / -1.6 %, 6 +1.5 / -0.2 %  -> 5: the one size that gains either way
+//   79 tiles: 8 -2.1 / -2.2 %, 4 to 6 within +-0.5 %;  128 tiles: 8 (= nt / 16), 4 to 6 +0.4 ... +2.3 %  -> at least 8
+// So: single tiles up to 8 tile rows (600 and 1000 rows: -9 % and -3 % against 2), about a sixteenth of the matrix with
+// at least 2 below 60 tile rows, 5 from 60 to 71, at least 8 from 72 on; never more than 16.  Non-decreasing in nt.
+// The band's edges are guesses: nothing between 47 and 64 or between 64 and 79 tile rows was swept, 5 rests on the one
+// measured size 64 (its neighbours there: 4 +-0, 6 +1.5 %), 72 is half-way to 79 and 60 is simply close to 64.
+int cugp_pipe_block_for(int nt)
+{
+    if (nt <= 8) return 1;
+    int w = (nt + 8) / 16;
+    if (w < 2) w = 2;
+    if (nt >= 60 && w < 5) w = 5;
+    if (nt >= 72 && w < 8) w = 8;
+    return w > 16 ? 16 : w;
 }
 
 int cugp_get_handle_tuning(cugp_gp* g, int key, int* value)
@@ -3301,6 +3394,11 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
     if (!gr) return fail(CUGP_ERR_NOMEM, "host allocation");
     gr->experts.assign(experts, experts + k);
     for (cugp_gp* x : gr->experts) x->groups++;             // (cugp_append refuses them while the group lives: the table carries n)
+    for (cugp_gp* x : gr->experts)                          // grouped experts run at default priorities (want_chain_first)
+        if (hipSetDevice(x->device) != hipSuccess || fetch_eval(x) != CUGP_OK || apply_stream_prio(x) != CUGP_OK) {
+            cugp_group_destroy(gr);
+            return fail(CUGP_ERR_DEVICE, "cugp_group_create: the experts' streams");
+        }
     const int nt = experts[0]->nt;
     const bool ard = experts[0]->ard;
     const size_t row = ard ? (size_t)ARD_ROW_GRAD + experts[0]->nh : 8;
@@ -3338,7 +3436,7 @@ void cugp_group_destroy(cugp_group* gr)
     if (gr->ctx.hout) (void)hipHostFree(gr->ctx.hout);
     if (gr->ctx.hrows) (void)hipHostFree(gr->ctx.hrows);
     gr->pred.release();
-    for (cugp_gp* x : gr->experts) x->groups--;             // (the experts outlive their group)
+    for (cugp_gp* x : gr->experts) x->groups--;             // (the experts outlive their group; their streams stay as they are: apply_stream_prio)
     delete gr;
 }
 

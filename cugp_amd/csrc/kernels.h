@@ -20,7 +20,7 @@ constexpr int TILE = 128;          // tile edge of every fp64 MFMA product and o
 enum { TUNE_LAUUM_WM2_MAX = 0,   // K^-1 product: use 64x64 tiles when there are at most this many 128-tiles
        TUNE_TRTRI_WM2_MAX = 1,   // inverse level: same rule
        TUNE_SYRK_REM_MAX = 2,    // trailing update: split the last partial round into 64x64 quarters when it has at most this many tiles
-       TUNE_PIPE_BLOCK = 3,      // inverse rows (tiles) handed to the other streams at a time while the factorisation runs; 0 = after it, < 0 = about nt/16 (1 up to 8 tiles)
+       TUNE_PIPE_BLOCK = 3,      // inverse rows (tiles) handed to the other streams at a time while the factorisation runs; 0 = after it, < 0 = by size (cugp_pipe_block_for; expert groups: about nt/16)
        TUNE_BORDER_WM2_MAX = 4,  // bordering step 1 (uniform K): 64x64 tiles when there are at most this many 128-tiles
        TUNE_GRAPHS = 5,          // replay single-stream evaluations as a captured HIP graph (1) or launch by launch (0)
        TUNE_GROUP_OVERLAP = 6,   // grouped experts: inverse blocks on the other streams beside the factorisation (1) or after it (0)
@@ -32,7 +32,11 @@ enum { TUNE_LAUUM_WM2_MAX = 0,   // K^-1 product: use 64x64 tiles when there are
        TUNE_FINALIZE_FUSE_MAX = 12, // gradient evaluations: the last block of k_trace takes the final sums (no k_finalize launch) when the trace launch has at most this many blocks; 0 = always the separate launch
        TUNE_SPLIT_REM_MAX = 13,  // uniform-K launches (block-wise K^-1 share, bordering, wide update): a last round of at most this many tiles runs as 64x64 quarters
        TUNE_STEP_QUARTER_MAX = 14, // step kernel: launches of at most this many 64x64 workgroups run ALL their tiles as quarters (chain-bound tail)
-       TUNE_STREAM_PRIO = 15,    // read when a handle is created: bit 0 = the factorisation's stream at the highest priority, bit 1 = the inverse streams at the lowest (default 0: prioritised streams serialised grouped experts in round 3)
+       TUNE_STREAM_PRIO = 15,    // stream priorities of a handle (its streams are created with the handle and re-created, where the answer changes, by cugp_set_data,
+                                 // cugp_set_handle_tuning, cugp_set_overlap and on joining a group or a BCM -- never inside an evaluation).  0 = by the rule: the
+                                 // factorisation's stream at the highest priority for a handle that is evaluated alone with the inverse beside the factorisation and
+                                 // has at least TUNE_PRIO_MIN_NT tile rows.  Explicit: bit 0 = the factorisation's stream at the highest priority, bit 1 = the inverse
+                                 // streams at the lowest, 4 = no priorities whatever the rule says (prioritised streams serialised grouped experts in round 3)
        TUNE_BARRIER_SPIN = 16,   // polls a workgroup of k_trtri_block spends at a stage barrier before it gives up (the evaluation then fails with CUGP_ERR_DEVICE instead of hanging); 0 = give up at once (test hook)
        TUNE_SUBPANEL = 17,       // near window in sub-panels of this many steps (1 to 4; must divide the panel, else 1): the step launch of a sub-panel's last step
                                  // updates the window with K = 128*this in ONE pass over its C tiles, the steps before it only the next column (left-looking inside the sub-panel)
@@ -42,7 +46,13 @@ enum { TUNE_LAUUM_WM2_MAX = 0,   // K^-1 product: use 64x64 tiles when there are
        TUNE_COV_SPLIT = 20,      // joint predictive covariance (k_predict_cov): 64x64 workgroup slots the launch aims to fill by splitting each
                                  // output tile's k range (128x128 workgroups count as two); 64x64 output tiles while the lower 128-tiles
                                  // are at most a quarter of it; 0 = 128x128 tiles, no split
-       TUNE_COUNT = 21 };
+       TUNE_PRIO_MIN_NT = 21,    // TUNE_STREAM_PRIO = 0: tile rows from which a lone handle's factorisation stream gets the highest priority (the chain's small launches
+                                 // then wait less behind the 1000-workgroup launches of the inverse streams: 64 tiles -0.5 %, 79 -1.2 %, 128 -0.9 %; 32 and 47 tiles
+                                 // gained nothing beyond their run-to-run spread)
+       TUNE_WAVES8 = 22,         // the whole 128x128 tiles of the uniform-K launches (k_syrk_wide, k_lauum<4>, k_trtri_border<4> step 1) on eight waves
+                                 // (512 threads, 32x64 outputs per wave; the last round's 64x64 quarters follow in a four-wave launch of their own): the same
+                                 // bits; default 0 (measured: profiles/r07_ab_parts.txt)
+       TUNE_COUNT = 23 };
 extern const int g_tune_init[TUNE_COUNT];     // built-in defaults
 extern thread_local const int* t_tune;        // the tuning the launchers on this thread read (a handle's copy, or the built-in defaults)
 inline int tune(int key) { return t_tune[key]; }

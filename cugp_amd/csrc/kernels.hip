@@ -593,6 +593,177 @@ __global__ __launch_bounds__(256, 2) void k_trtri_border(const double* __restric
     }
 }
 
+// ---- the 128x128 product's second geometry: 8 waves (TUNE_WAVES8) ----
+// 512 threads, waves 4 x 2, 32 x 64 outputs per wave (2 x 4 MFMA tiles, 32 accumulators), the LDS image of the 4-wave
+// product (Geo<4>, the same dynamic LDS).  Two such workgroups put FOUR waves on every SIMD, so while one workgroup is
+// in its prologue or epilogue the other still has two waves per SIMD issuing MFMAs.  Every output entry is the same
+// chain of MFMA accumulations over k as in the 4-wave product and meets C in the same epilogue expression: the same
+// bits.  Used by the uniform-K launches (k_syrk_wide8, k_lauum8, k_trtri_border8: bordering step 1); the 64x64 quarters
+// of a launch's last round (split_round) stay on four waves, in a launch of their own behind it (k_*_rest).
+template <bool NEGA>
+__device__ __forceinline__ void tile_nt8(const double* __restrict__ Ag, int lda, const double* __restrict__ Bg, int ldb,
+                                         int kbeg, int kend, d4 (&acc)[2][4], char* smem)
+{
+    typedef Geo<4> G;
+    const int t = opaque_tid();
+    const int lane = t & 63, wave = t >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+    const int srow = t >> 3, skp = t & 7;                 // 64 rows per pass, 2 passes
+    const double* ag = Ag + (size_t)srow * lda + 2 * skp;
+    const double* bg = Bg + (size_t)srow * ldb + 2 * skp;
+    d2 ra[2], rb[2];
+    int wa[2], wb[2];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        wa[q] = skp * G::PLANE + (srow + 64 * q) * 16;
+        wb[q] = G::OPER + skp * G::PLANE + bpos<4>(srow + 64 * q) * 16;
+    }
+    const int fr = lane & 15, fk = lane >> 4;
+    const int abase = (fk >> 1) * G::PLANE + (wr * 32 + fr) * 16 + (fk & 1) * 8;
+    const int bbase = G::OPER + (fk >> 1) * G::PLANE + (wc * 64 + fr) * 16 + (fk & 1) * 8;
+    const int nk = (kend - kbeg) / BK;
+    if (nk <= 0) return;
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        ra[q] = *(const d2*)(ag + (size_t)(64 * q) * lda + kbeg);
+        rb[q] = *(const d2*)(bg + (size_t)(64 * q) * ldb + kbeg);
+    }
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        *(d2*)(smem + wa[q]) = NEGA ? -ra[q] : ra[q];
+        *(d2*)(smem + wb[q]) = rb[q];
+    }
+    __syncthreads();
+#define CUGP_STAGE8(HALF, MORE, KNEXT)                                                              \
+    do {                                                                                            \
+        const char* cur_ = smem + (HALF) * G::STAGE;                                                \
+        char* nxt_ = smem + (1 - (HALF)) * G::STAGE;                                                \
+        const bool more_ = (MORE);                                                                  \
+        if (more_) {                                                                                \
+            const int k_ = (KNEXT);                                                                 \
+            _Pragma("unroll") for (int q = 0; q < 2; q++) {                                         \
+                ra[q] = *(const d2*)(ag + (size_t)(64 * q) * lda + k_);                             \
+                rb[q] = *(const d2*)(bg + (size_t)(64 * q) * ldb + k_);                             \
+            }                                                                                       \
+        }                                                                                           \
+        _Pragma("unroll") for (int kk = 0; kk < BK / 4; kk++) {                                     \
+            double a[2], b[4];                                                                      \
+            _Pragma("unroll") for (int m = 0; m < 2; m++) a[m] = *(const double*)(cur_ + abase + kk * 2 * G::PLANE + m * 256); \
+            _Pragma("unroll") for (int n = 0; n < 4; n++) b[n] = *(const double*)(cur_ + bbase + kk * 2 * G::PLANE + n * 256); \
+            _Pragma("unroll") for (int m = 0; m < 2; m++)                                           \
+                _Pragma("unroll") for (int n = 0; n < 4; n++)                                       \
+                    acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0); \
+        }                                                                                           \
+        if (more_) {                                                                                \
+            _Pragma("unroll") for (int q = 0; q < 2; q++) {                                         \
+                *(d2*)(nxt_ + wa[q]) = NEGA ? -ra[q] : ra[q];                                       \
+                *(d2*)(nxt_ + wb[q]) = rb[q];                                                       \
+            }                                                                                       \
+        }                                                                                           \
+        __syncthreads();                                                                            \
+    } while (0)
+    int kt = 0;
+    for (; kt + 1 < nk; kt += 2) {
+        CUGP_STAGE8(0, true, kbeg + (kt + 1) * BK);
+        CUGP_STAGE8(1, kt + 2 < nk, kbeg + (kt + 2) * BK);
+    }
+    if (kt < nk) CUGP_STAGE8(0, false, 0);
+#undef CUGP_STAGE8
+}
+
+// the 8-wave epilogues.  SIGN 0: C = acc (tile_store with alpha = 1); +1 / -1: C += / -= acc, the C tile read here, one
+// row group of the wave at a time (tile_accum_store)
+template <int SIGN>
+__device__ __forceinline__ void tile_out8(double* __restrict__ C, int ldc, const d4 (&acc)[2][4])
+{
+    const int tid = opaque_tid();
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 1, wc = wave & 1;
+#pragma unroll
+    for (int m = 0; m < 2; m++) {
+        double* const c0 = C + (size_t)(wr * 32 + m * 16 + (lane >> 4)) * ldc + wc * 64 + 2 * (lane & 15);
+        d2 v[4][2];
+        if (SIGN != 0) {
+#pragma unroll
+            for (int r = 0; r < 4; r++)
+#pragma unroll
+                for (int np = 0; np < 2; np++) v[r][np] = *(const d2*)(c0 + (size_t)(4 * r) * ldc + np * 32);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+#pragma unroll
+            for (int np = 0; np < 2; np++) {
+                d2* dst = (d2*)(c0 + (size_t)(4 * r) * ldc + np * 32);
+                if (SIGN == 0) *dst = (d2){acc[m][2 * np][r], acc[m][2 * np + 1][r]};
+                else if (SIGN > 0) *dst = (d2){v[r][np][0] + acc[m][2 * np][r], v[r][np][1] + acc[m][2 * np + 1][r]};
+                else *dst = (d2){v[r][np][0] - acc[m][2 * np][r], v[r][np][1] - acc[m][2 * np + 1][r]};
+            }
+    }
+}
+
+__device__ __forceinline__ void acc_zero8(d4 (&acc)[2][4])
+{
+#pragma unroll
+    for (int m = 0; m < 2; m++)
+#pragma unroll
+        for (int n = 0; n < 4; n++) acc[m][n] = (d4){0.0, 0.0, 0.0, 0.0};
+}
+
+// k_lauum<4>'s whole tiles [0, gridDim.x) on eight waves (lauum_tile<4>)
+__global__ __launch_bounds__(512, 4) void k_lauum8(const double* __restrict__ U, double* __restrict__ Kinv, int ld, int a,
+                                                   int w, const ExpertPtrs* __restrict__ bt, unsigned long long* stamp)
+{
+    LaunchStamp stamp_(stamp);
+    if (bt) { U = GP(bt[blockIdx.y].U); Kinv = GP(bt[blockIdx.y].Kinv); }
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    double* C = Kinv + (size_t)(ti * TILE) * ld + tj * TILE;
+    d4 acc[2][4];
+    acc_zero8(acc);
+    tile_nt8<false>(U + (size_t)(ti * TILE) * ld, ld, U + (size_t)(tj * TILE) * ld, ld, (ti < a ? a : ti) * TILE,
+                    (a + w) * TILE, acc, smem);
+    if (ti < a) tile_out8<1>(C, ld, acc);
+    else tile_out8<0>(C, ld, acc);
+}
+
+// ... and the tiles from x0 on as 64x64 quarters on four waves (the quarter branch of k_lauum<4>)
+__global__ __launch_bounds__(256, 2) void k_lauum_rest(const double* __restrict__ U, double* __restrict__ Kinv, int ld,
+                                                       int a, int w, int x0, const ExpertPtrs* __restrict__ bt)
+{
+    if (bt) { U = GP(bt[blockIdx.y].U); Kinv = GP(bt[blockIdx.y].Kinv); }
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    lauum_tile<2>(U, Kinv, ld, a, w, x0 + (blockIdx.x >> 2), blockIdx.x & 3, smem);
+}
+
+// step 1 of the bordering (border_tile, step 1): whole tiles [0, gridDim.x) on eight waves
+__global__ __launch_bounds__(512, 4) void k_trtri_border8(const double* __restrict__ L, double* __restrict__ T,
+                                                          const double* __restrict__ U, int ld, int a, int w, int c0,
+                                                          int c1, const ExpertPtrs* __restrict__ bt,
+                                                          unsigned long long* stamp)
+{
+    LaunchStamp stamp_(stamp);
+    if (bt) { L = GP(bt[blockIdx.y].A); T = GP(bt[blockIdx.y].T); U = GP(bt[blockIdx.y].U); }
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tj = blockIdx.x / w, ti = a + blockIdx.x % w;             // tj < c1
+    double* W = T + (size_t)(tj * TILE) * ld + ti * TILE;
+    d4 acc[2][4];
+    acc_zero8(acc);
+    tile_nt8<false>(U + (size_t)(tj * TILE) * ld, ld, L + (size_t)(ti * TILE) * ld, ld, (tj > c0 ? tj : c0) * TILE,
+                    c1 * TILE, acc, smem);
+    if (tj < c0) tile_out8<1>(W, ld, acc);
+    else tile_out8<0>(W, ld, acc);
+}
+
+__global__ __launch_bounds__(256, 2) void k_trtri_border_rest(const double* __restrict__ L, double* __restrict__ T,
+                                                              double* __restrict__ U, int ld, int a, int w, int c0,
+                                                              int c1, int x0, const ExpertPtrs* __restrict__ bt)
+{
+    if (bt) { L = GP(bt[blockIdx.y].A); T = GP(bt[blockIdx.y].T); U = GP(bt[blockIdx.y].U); }
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    border_tile<2>(L, T, U, ld, a, w, 1, c0, c1, x0 + (blockIdx.x >> 2), blockIdx.x & 3, smem);
+}
+
 // ---- prediction: W[t][i] = sum_{k <= i} Ks[t][k] * T[i][k] ----
 // T = L^-1 is lower triangular: row tile i needs k < (i + 1) * tile only, so the work per output tile grows linearly
 // with i.  Rounds 1-4 gave every 128x128 output tile a workgroup of its own: 512 workgroups for 1000 test points at
@@ -1980,6 +2151,45 @@ __global__ __launch_bounds__(256, 2) void k_syrk_wide(double* __restrict__ A, in
     tile_accum_store<-1>(A + (size_t)i0 * ld + j0, ld, acc);
 }
 
+// k_syrk_wide's whole tiles [0, nfull = gridDim.x) on eight waves (tile_nt8), the same walk over the tile list
+__global__ __launch_bounds__(512, 4) void k_syrk_wide8(double* __restrict__ A, int ld, int k0, int kw, int ca, int cb,
+                                                       int rev, const ExpertPtrs* __restrict__ bt,
+                                                       unsigned long long* stamp)
+{
+    LaunchStamp stamp_(stamp);
+    if (bt) A = GP(bt[blockIdx.y].A);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __builtin_amdgcn_s_setprio(1);
+    const int nfull = gridDim.x;
+    const int xg = blockIdx.x & 7;
+    const int xq = nfull >> 3, xr = nfull & 7;
+    const int tlin = (xg < xr ? xg * (xq + 1) : xr * (xq + 1) + (xg - xr) * xq) + (blockIdx.x >> 3);
+    int ti, tj;
+    trap_index(rev ? nfull - 1 - tlin : tlin, cb - ca, ti, tj);
+    const int i0 = (ca + ti) * TILE, j0 = (ca + tj) * TILE;
+    d4 acc[2][4];
+    acc_zero8(acc);
+    tile_nt8<false>(A + (size_t)i0 * ld, ld, A + (size_t)j0 * ld, ld, k0 * TILE, (k0 + kw) * TILE, acc, smem);
+    tile_out8<-1>(A + (size_t)i0 * ld + j0, ld, acc);
+}
+
+// ... and the tiles from x0 on as 64x64 quarters on four waves (the quarter branch of k_syrk_wide)
+__global__ __launch_bounds__(256, 2) void k_syrk_wide_rest(double* __restrict__ A, int ld, int k0, int kw, int ca, int cb,
+                                                           int x0, const ExpertPtrs* __restrict__ bt)
+{
+    if (bt) A = GP(bt[blockIdx.y].A);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __builtin_amdgcn_s_setprio(1);
+    const int y = blockIdx.x;
+    int ti, tj;
+    trap_index(x0 + (y >> 2), cb - ca, ti, tj);
+    const int i0 = (ca + ti) * TILE + ((y >> 1) & 1) * 64, j0 = (ca + tj) * TILE + (y & 1) * 64;
+    d4 acc[2][2];
+    acc_zero(acc);
+    tile_nt<false>(A + (size_t)i0 * ld, ld, A + (size_t)j0 * ld, ld, k0 * TILE, (k0 + kw) * TILE, acc, smem);
+    tile_accum_store<-1>(A + (size_t)i0 * ld + j0, ld, acc);
+}
+
 // inverse of a 128x128 diagonal factor block from the two 64x64 inverses potf2 left in d64 (one doubling
 // step, T10 = -T11 (L10 T00), on 16x16 micro tiles: wave = micro-tile column of T10); writes T (lower, zeros
 // above) and U = T^T (upper, zeros below).  blockIdx.x = block offset from kb.  ~6 us (the blocked
@@ -2985,7 +3195,7 @@ static inline unsigned long long* take_stamp() { unsigned long long* p = t_stamp
     } while (0)
 
 const int g_tune_init[TUNE_COUNT] = {768, 1200, 384, -1, 511, 1, 1, 1 << 20, 16, 500, 32, 1, 2100, 256, 1536, 0, 1 << 21, 1, 1, 0,
-                                      1024};   // defaults chosen by interleaved A/B runs (tools/ab.py)
+                                      1024, 64, 0};   // defaults chosen by interleaved A/B runs (tools/ab.py)
 thread_local const int* t_tune = g_tune_init;
 
 static inline int tri_count(int n) { return n * (n + 1) / 2; }
@@ -3049,6 +3259,7 @@ static void set_big_lds()
                            (const void*)k_test_gemm, (const void*)k_predict_cov<4>, (const void*)k_loo_product<4>,
                            (const void*)k_sparse_gram};
     for (const void* f : gemm4) attr(f, GEMM_LDS);
+    for (const void* f : {(const void*)k_syrk_wide8, (const void*)k_lauum8, (const void*)k_trtri_border8}) attr(f, GEMM_LDS);
     attr((const void*)k_trtri_diag, TRTRI_LDS);
     attr((const void*)k_trtri_block, TRTRI_BLOCK_LDS);
     attr((const void*)k_trsm_inv64, TRSM_LDS);
@@ -3146,6 +3357,14 @@ int launch_syrk_wide(double* A, int ld, int nt, int k0, int kw, int ca, int cb, 
     set_big_lds();
     const int ntiles = trap_count(nt - ca, cb - ca);
     const int nfull = split_round(ntiles, bt.count);
+    if (tune(TUNE_WAVES8) != 0 && nfull > 0) {
+        CUGP_LAUNCH(k_syrk_wide8, dim3(nfull, bt.count), dim3(512), GEMM_LDS, s, A, ld, k0, kw, ca, cb, rev, bt.tab,
+                    take_stamp());
+        if (ntiles > nfull)
+            hipLaunchKernelGGL(k_syrk_wide_rest, dim3(4 * (ntiles - nfull), bt.count), dim3(256), Geo<2>::LDS, s, A, ld, k0,
+                               kw, ca, cb, nfull, bt.tab);
+        return ntiles;
+    }
     CUGP_LAUNCH(k_syrk_wide, dim3(nfull + 4 * (ntiles - nfull), bt.count), dim3(256), GEMM_LDS, s, A, ld, k0, kw, ca,
                        cb, ntiles, nfull, rev, bt.tab, take_stamp());
     return ntiles;
@@ -3188,6 +3407,14 @@ int launch_trtri_border1(const double* L, double* T, double* U, int ld, int ra, 
         return 2;
     }
     const int nfull = split_round(tiles, bt.count);
+    if (tune(TUNE_WAVES8) != 0 && nfull > 0) {
+        CUGP_LAUNCH(k_trtri_border8, dim3(nfull, bt.count), dim3(512), GEMM_LDS, st, L, T, U, ld, ra, rw, c0, c1, bt.tab,
+                    take_stamp());
+        if (tiles > nfull)
+            hipLaunchKernelGGL(k_trtri_border_rest, dim3(4 * (tiles - nfull), bt.count), dim3(256), Geo<2>::LDS, st, L, T,
+                               U, ld, ra, rw, c0, c1, nfull, bt.tab);
+        return 4;
+    }
     CUGP_LAUNCH(k_trtri_border<4>, dim3(nfull + 4 * (tiles - nfull), bt.count), dim3(256), GEMM_LDS, st, L, T,
                        U, ld, ra, rw, 1, c0, c1, nfull, bt.tab, take_stamp());
     return 4;
@@ -3221,6 +3448,13 @@ int launch_lauum(const double* U, double* Kinv, int ld, int a, int w, hipStream_
         // (a whole-matrix product, a = 0, has k ranges from 1 to a+w tiles, longest first: its tail is short tiles
         //  already; the split is for the block-wise calls, whose tiles all take w k tiles)
         const int nfull = a > 0 ? split_round(tiles, bt.count) : tiles;
+        if (tune(TUNE_WAVES8) != 0 && nfull > 0) {
+            CUGP_LAUNCH(k_lauum8, dim3(nfull, bt.count), dim3(512), GEMM_LDS, s, U, Kinv, ld, a, w, bt.tab, take_stamp());
+            if (tiles > nfull)
+                hipLaunchKernelGGL(k_lauum_rest, dim3(4 * (tiles - nfull), bt.count), dim3(256), Geo<2>::LDS, s, U, Kinv, ld,
+                                   a, w, nfull, bt.tab);
+            return 4;
+        }
         CUGP_LAUNCH(k_lauum<4>, dim3(nfull + 4 * (tiles - nfull), bt.count), dim3(256), GEMM_LDS, s, U, Kinv, ld,
                            a, w, nfull, bt.tab, take_stamp());
         return 4;

@@ -450,6 +450,12 @@ class Covsum:
         check(capi.lib().cugp_get_handle_tuning(self._h, int(key), C.byref(v)))
         return v.value
 
+    def chain_first(self):
+        """True where the handle's factorisation stream runs at the device's highest priority (cugp_chain_first)."""
+        v = C.c_int()
+        check(capi.lib().cugp_chain_first(self._h, C.byref(v)))
+        return bool(v.value)
+
     def phase_ms(self):
         """Main-stream phases of the last evaluation.  With the overlap on, "potrf" includes the inverse blocks
         running beside it and "trtri" is what was left of them when the factorisation ended ("lauum" ~ 0)."""

@@ -684,6 +684,14 @@ int cugp_bench_la_check(int op, int n, int device, int reps, double *ms, double 
 int cugp_set_tuning(int key, int value);
 int cugp_set_handle_tuning(cugp_gp *gp, int key, int value, int own);
 int cugp_get_handle_tuning(cugp_gp *gp, int key, int *value);
+/* 1 where the handle's factorisation stream runs at the device's highest priority (kernels.h TUNE_STREAM_PRIO: a handle
+ * evaluated alone, with the inverse beside the factorisation, of at least TUNE_PRIO_MIN_NT tile rows -- or the key's
+ * explicit bit 0), else 0.  Decided when the handle is created and again by cugp_set_data, cugp_set_handle_tuning,
+ * cugp_set_overlap and on joining a group or a BCM; results never depend on it. */
+int cugp_chain_first(const cugp_gp *gp, int *on);
+/* tile rows handed to the inverse streams at a time for a matrix of nt tile rows evaluated alone (TUNE_PIPE_BLOCK < 0):
+ * 1 ... 16, non-decreasing in nt (pure arithmetic, no device) */
+int cugp_pipe_block_for(int nt);
 /* the launches of step kb of the two-speed Cholesky with panels of P steps and a near window of about `near_tiles`
  * tiles (pure arithmetic, no device): out = {wide k0, wide k tiles, wide columns [a0,a1), step-launch width in tile
  * columns from kb+1}; tests/test_host_logic.py replays it: every tile sees every k exactly once, ascending */
