@@ -2647,6 +2647,11 @@ struct cugp_sparse {
     double *dM[4] = {nullptr, nullptr, nullptr, nullptr};    // H, H2, a product, R (mpad^2 each): the gradient's
     double *dpart = nullptr;                                 // trace partials: the rectangle's, then the square's
     double *dout = nullptr, *hout = nullptr;                 // results row, device and pinned
+    // the gradient with respect to Z (cugp_sparse_bound_grad_z): created on its first use
+    std::vector<double> z;                                   // Z as set, [m][d] (the host copy cugp_sparse_get_inducing returns)
+    std::vector<double> gz;                                  // [m][d] of the last evaluation that took it
+    bool row_z = false;
+    double *dzpart = nullptr, *dzacc = nullptr, *dzout = nullptr, *hz = nullptr;   // partial blocks, running sums, result, its pinned copy
     Scratch pred;
 };
 
@@ -2687,6 +2692,29 @@ int sp_ensure(cugp_sparse* s, bool want_grad)
     return CUGP_OK;
 }
 
+// the buffers of the Z gradient, all or none: a failed allocation leaves the handle as it was
+int sp_ensure_z(cugp_sparse* s)
+{
+    if (s->hz) return CUGP_OK;
+    const size_t md = (size_t)s->m * s->d;
+    int slots = sparse_z_shape(s->mpad, s->mpad, s->d).ranges;                    // the square's pass
+    const int chunks = sparse_shape(s->n, s->mpad, s->chunk_rows, 0).chunks;
+    for (int c = 0; c < chunks; c++)
+        slots = std::max(slots, sparse_z_shape(sparse_shape(s->n, s->mpad, s->chunk_rows, c).cpad, s->mpad, s->d).ranges);
+    double *part = nullptr, *acc = nullptr, *out = nullptr, *h = nullptr;
+    hipError_t e = hipMalloc((void**)&part, (size_t)slots * md * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&acc, md * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&out, md * sizeof(double));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h, md * sizeof(double), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        for (double* p : {part, acc, out})
+            if (p) (void)hipFree(p);
+        return fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, "the inducing-input gradient's partial blocks", e);
+    }
+    s->dzpart = part; s->dzacc = acc; s->dzout = out; s->hz = h;
+    return CUGP_OK;
+}
+
 // S_c = k(X_c, Z) and W_c = S_c Lu^-T of one chunk on u's stream: the launches of a prediction with the chunk as test rows
 void sp_chunk_w(cugp_sparse* s, const CovFn& cf, const SparseShape& c)
 {
@@ -2698,16 +2726,24 @@ void sp_chunk_w(cugp_sparse* s, const CovFn& cf, const SparseShape& c)
 // The bound (and its gradient) at the current hyper-parameters.  The results land in s->row: NaN where Kuu or B is not
 // positive definite (the header's convention).  Two host waits beyond the inner evaluation's: in front of B's
 // factorisation, which runs on the factor handle's own stream, and at the end.
-int sp_eval(cugp_sparse* s, bool want_grad, const char* call)
+// want_z (with want_grad): the same sequence with the Z pass behind every k_trace_cross, on the weights that launch read
+// -- no launch of the sequence changes, so F and the hyper-parameter components keep their bits -- and no further host wait.
+int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = false)
 {
     int rc;
     if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
     if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
-    if (s->valid && (s->row_grad || !want_grad)) return CUGP_OK;
+    if (s->valid && (s->row_grad || !want_grad) && (s->row_z || !want_z)) return CUGP_OK;
     cugp_gp *u = s->u, *b = s->b;
+    if (want_z) {
+        if ((rc = use_device(u))) return rc;
+        if ((rc = sp_ensure_z(s))) return rc;
+    }
     s->valid = s->pd = false;
     s->row.assign((size_t)1 + s->nh, NAN);
     s->row_grad = want_grad;
+    s->row_z = want_z;
+    if (want_z) s->gz.assign((size_t)s->m * s->d, NAN);
     std::vector<double> th(s->theta);
     th[s->nh - 1] = 0.5 * std::log(s->jitter);                        // the noise slot of the inner handle: Kuu = k(Z, Z) + eps I
     if ((rc = set_theta(u, th.data()))) return rc;
@@ -2759,9 +2795,17 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call)
             launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
             launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
                                s->dy + sh.r0, bsc, part_uf, nb_uf, pofs, st);
+            if (want_z)
+                launch_trace_cross_z(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
+                                     s->dy + sh.r0, bsc, s->dzpart, s->dzacc, c == 0, false, s->dzout, s->hz, st);
             pofs += (size_t)(sh.cpad / 64) * (mp / 64);
         }
         launch_trace_cross(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, part_uu, nb_uu, 0, st);
+        if (want_z) {
+            for (size_t i = 0; i < (size_t)s->m * s->d; i++) s->hz[i] = NAN;
+            launch_trace_cross_z(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, s->dzpart, s->dzacc, false,
+                                 true, s->dzout, s->hz, st);
+        }
     }
     const SparseFinal fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->dyy, s->m, mp, b->nt, (double)s->n, sf2, s2,
                           s->theta[s->nh - 1] * 2};
@@ -2772,6 +2816,10 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call)
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
     s->row[0] = s->hout[0];
     if (want_grad) std::copy(s->hout + 1, s->hout + 1 + s->nh, s->row.begin() + 1);
+    if (want_z) {
+        std::copy(s->hz, s->hz + (size_t)s->m * s->d, s->gz.begin());
+        if (!std::isfinite(s->row[0])) std::fill(s->gz.begin(), s->gz.end(), NAN);    // (B is not positive definite: NaN results)
+    }
     s->pd = std::isfinite(s->row[0]);
     s->valid = true;
     return CUGP_OK;
@@ -2858,9 +2906,10 @@ int cugp_sparse_destroy(cugp_sparse* s)
     if (s->u) (void)cugp_destroy(s->u);
     if (s->b) (void)cugp_destroy(s->b);
     for (double* p : {s->dX, s->dy, s->dyy, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dvec, s->dM[0], s->dM[1], s->dM[2], s->dM[3],
-                      s->dpart, s->dout})
+                      s->dpart, s->dout, s->dzpart, s->dzacc, s->dzout})
         if (p) (void)hipFree(p);
     if (s->hout) (void)hipHostFree(s->hout);
+    if (s->hz) (void)hipHostFree(s->hz);
     s->pred.release();
     delete s;
     return CUGP_OK;
@@ -2908,6 +2957,7 @@ int cugp_sparse_set_inducing(cugp_sparse* s, const double* Z)
     if (!s || !Z) return tg_invalid("cugp_sparse_set_inducing", "null argument");
     const std::vector<double> zero((size_t)s->m, 0.0);                 // (the inner handle's labels are never read by this model)
     if (const int rc = cugp_set_data(s->u, Z, zero.data())) return rc;
+    s->z.assign(Z, Z + (size_t)s->m * s->d);
     s->have_z = true;
     s->valid = false;
     return CUGP_OK;
@@ -3009,6 +3059,76 @@ int cugp_sparse_cg_solve(cugp_sparse* s, int budget, double* trace, int trace_ca
         return rc;
     if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
     return sp_set_theta(s, th.data());
+}
+
+// ---- the inducing inputs as variables
+int cugp_sparse_get_inducing(const cugp_sparse* s, double* Z)
+{
+    const char* call = "cugp_sparse_get_inducing";
+    if (!s || !Z) return tg_invalid(call, "null argument");
+    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
+    std::copy(s->z.begin(), s->z.end(), Z);
+    return CUGP_OK;
+}
+
+int cugp_sparse_bound_grad_z(cugp_sparse* s, double* F, double* g, int nh, double* gZ)
+{
+    const char* call = "cugp_sparse_bound_grad_z";
+    if (!s || !F || !g || !gZ) return tg_invalid(call, "null argument");
+    if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
+    if (const int rc = sp_eval(s, true, call, true)) return rc;
+    *F = s->row[0];
+    std::copy(s->row.begin() + 1, s->row.end(), g);
+    std::copy(s->gz.begin(), s->gz.end(), gZ);
+    return CUGP_OK;
+}
+
+namespace {
+// f = -F and its gradient at v = [theta, vec Z] (NaN where the evaluation fails); a Z that differs goes to the handle
+void sp_objective_z(void* ctx, const double* v, int nv, double* f, double* gr)
+{
+    cugp_sparse* s = (cugp_sparse*)ctx;
+    const double* zv = v + s->nh;
+    const size_t md = (size_t)s->m * s->d;
+    bool moved = false;
+    for (size_t i = 0; i < md && !moved; i++) moved = zv[i] != s->z[i] || std::isnan(zv[i]);
+    if ((!moved || cugp_sparse_set_inducing(s, zv) == CUGP_OK) && sp_set_theta(s, v) == CUGP_OK &&
+        sp_eval(s, true, "cugp_sparse_cg_solve_z", true) == CUGP_OK) {
+        *f = -1.0 * s->row[0];
+        std::copy(s->row.begin() + 1, s->row.begin() + 1 + s->nh, gr);
+        std::copy(s->gz.begin(), s->gz.end(), gr + s->nh);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nv, NAN);
+    }
+}
+}  // namespace
+
+// cugp_sparse_cg_solve's loop over the nh + m d variables [theta, vec Z]; the record keeps [theta, f] of the iterates
+int cugp_sparse_cg_solve_z(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)
+{
+    const char* call = "cugp_sparse_cg_solve_z";
+    if (!s) return tg_invalid(call, "null handle");
+    if (budget <= 0) return tg_invalid(call, "budget must be positive");
+    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
+    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
+    int rc, nrows = 0;
+    if ((rc = use_device(s->u)) || (rc = sp_ensure_z(s))) return rc;
+    const int nv = s->nh + s->m * s->d, cap = trace ? std::max(trace_cap, 0) : 0;
+    std::vector<double> v(s->theta), rows((size_t)cap * (nv + 1), NAN);
+    v.insert(v.end(), s->z.begin(), s->z.end());
+    if ((rc = cugp_cg_minimize_n_iterates(sp_objective_z, s, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals,
+                                          &nrows)))
+        return rc;
+    for (int r = 0; r < nrows; r++) {
+        std::copy(rows.begin() + (size_t)r * (nv + 1), rows.begin() + (size_t)r * (nv + 1) + s->nh, trace + (size_t)r * (s->nh + 1));
+        trace[(size_t)r * (s->nh + 1) + s->nh] = rows[(size_t)r * (nv + 1) + nv];
+    }
+    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
+    bool moved = false;
+    for (size_t i = 0; i < s->z.size() && !moved; i++) moved = v[s->nh + i] != s->z[i];
+    if (moved && (rc = cugp_sparse_set_inducing(s, v.data() + s->nh))) return rc;
+    return sp_set_theta(s, v.data());
 }
 
 // ---------------------------------------------------------------- timing

@@ -335,6 +335,18 @@ void launch_sparse_weights(const double* W, const double* R, double* G, int cpad
 void launch_trace_cross(const double* Xr, int nr, int rows_pad, const double* Z, int m, int d, int mpad, const CovFn& cf,
                         const double* G, const double* yv, const double* bv, double* part, size_t pstride, size_t pofs,
                         hipStream_t s);
+// The gradient with respect to the inducing inputs (sparse_z_device.h): one pass of
+// k_trace_cross_z<ARD, KIND> over the rows_pad / 64 x mpad / 64 tiles of G (w = G + yv bv^T; yv null: none) and
+// k_trace_cross_z_finish behind it.  Workgroup (column tile, range) sums `per` consecutive row tiles; the ranges per column
+// tile aim at SPARSE_Z_SLOTS workgroups (two per CU) of at least 256 rows, their partial blocks (ranges * m * d doubles in part) within 1 GiB:
+// sparse_z_shape is a pure function of (rows_pad, mpad, d).  acc ([m][d]): the running sums over the passes (first: it
+// starts from zero); last: out[j d + c] = hout[..] = -(s_c acc), the gradient of -F.
+constexpr int SPARSE_Z_SLOTS = 512;
+struct SparseZShape { int row_tiles, per, ranges; };
+SparseZShape sparse_z_shape(int rows_pad, int mpad, int d);
+void launch_trace_cross_z(const double* Xr, int nr, int rows_pad, const double* Z, int m, int d, int mpad, const CovFn& cf,
+                          const double* G, const double* yv, const double* bv, double* part, double* acc, bool first,
+                          bool last, double* out, double* hout, hipStream_t s);
 // what the last launch of an evaluation reads beside the trace partials
 struct SparseFinal {
     const double *P, *Binv;        // ld x ld: their diagonals

@@ -3062,9 +3062,11 @@ __global__ __launch_bounds__(256, 2) void k_loo_product(const double* __restrict
 // ------------------------------------------------------------------------------------------
 // Sparse variational GP regression on inducing points (cugp_sparse_*): k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty,
 // k_sparse_wty_finish, k_sparse_yy, k_sparse_h, k_sparse_transpose, k_trace_cross, k_sparse_finalize,
-// k_sparse_predict_finish (sparse_device.h: a host can emulate them) and the one new product, k_sparse_gram
+// k_sparse_predict_finish (sparse_device.h: a host can emulate them) and the one new product, k_sparse_gram; the gradient
+// with respect to the inducing inputs: k_trace_cross_z, k_trace_cross_z_finish (sparse_z_device.h, emulable as well)
 // ------------------------------------------------------------------------------------------
 #include "sparse_device.h"
+#include "sparse_z_device.h"
 
 // acc[m][n] += sum_{k in [kbeg, kend)} W[k][i0 + ..] W[k][j0 + ..]: the TN sibling of tile_nt -- the contraction index k is
 // the SLOW index of the one row-major operand W ([k][ld]; Ag -> W[0][i0], Bg -> W[0][j0]).  The LDS image, the fragment
@@ -3831,6 +3833,33 @@ void launch_trace_cross(const double* Xr, int nr, int rows_pad, const double* Z,
     const dim3 grid((rows_pad / KT) * (mpad / KT));
     hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_cross), grid, dim3(256), 0, s, Xr, nr, Z, m, d, mpad, cf.h, cf.hd, G, yv,
                        bv, part, pstride, pofs);
+}
+
+SparseZShape sparse_z_shape(int rows_pad, int mpad, int d)
+{
+    SparseZShape z;
+    z.row_tiles = rows_pad / KT;
+    const int nct = mpad / KT;
+    int ranges = SPARSE_Z_SLOTS / nct;                    // (64-column workgroups, two per CU)
+    if (ranges > rows_pad / 256) ranges = rows_pad / 256; // ranges of at least 256 rows, as the Gram product's splits
+    if (ranges < 1) ranges = 1;
+    while (ranges > 1 && (size_t)ranges * mpad * d * sizeof(double) > ((size_t)1 << 30)) ranges--;   // scratch <= 1 GiB
+    z.per = (z.row_tiles + ranges - 1) / ranges;
+    z.ranges = (z.row_tiles + z.per - 1) / z.per;         // (no empty range)
+    return z;
+}
+
+void launch_trace_cross_z(const double* Xr, int nr, int rows_pad, const double* Z, int m, int d, int mpad, const CovFn& cf,
+                          const double* G, const double* yv, const double* bv, double* part, double* acc, bool first,
+                          bool last, double* out, double* hout, hipStream_t s)
+{
+    const SparseZShape z = sparse_z_shape(rows_pad, mpad, d);
+    const size_t sstride = (size_t)m * d;
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_cross_z), dim3((mpad / KT) * z.ranges), dim3(256), 0, s, Xr, nr, Z, m, d,
+                       mpad, cf.h, cf.hd, G, yv, bv, z.row_tiles, z.per, z.ranges, part, sstride);
+    const double* wts = is_ard(cf) ? (const double*)(cf.hd + 1) : nullptr;   // (the weights behind the hyper-scalars)
+    hipLaunchKernelGGL(k_trace_cross_z_finish, dim3((unsigned)((sstride + 255) / 256)), dim3(256), 0, s, (const double*)part,
+                       sstride, z.ranges, m, d, first ? 1 : 0, last ? 1 : 0, cf.h.ell_sq, wts, acc, out, hout);
 }
 
 void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t nb_uf, const double* part_uu, size_t nb_uu,

@@ -557,13 +557,29 @@ class SparseGP:
         check(capi.lib().cugp_sparse_predict(self._h, ptr(Xt), Xt.shape[0], 1 if with_noise else 0, ptr(m), ptr(v)))
         return m, v
 
-    def cg_solve(self, budget=100):
+    def get_inducing(self):
+        """Z [m, d] as the handle holds it (cugp_sparse_get_inducing): what was set, or where cg_solve(inducing=True) ended."""
+        Z = np.empty((self.m, self.d))
+        check(capi.lib().cugp_sparse_get_inducing(self._h, ptr(Z)))
+        return Z
+
+    def bound_grad_z(self):
+        """(F, g, gZ): the bound, the gradient of -F [nh] with bound_grad's bits, and the gradient of -F with respect to
+        the inducing inputs [m, d] in set_inducing's layout (cugp_sparse_bound_grad_z)."""
+        F, g, gZ = C.c_double(), np.empty(self.nh), np.empty((self.m, self.d))
+        check(capi.lib().cugp_sparse_bound_grad_z(self._h, C.byref(F), ptr(g), self.nh, ptr(gZ)))
+        return F.value, g, gZ
+
+    def cg_solve(self, budget=100, inducing=False):
         """Conjugate gradients on -F from the current hyper-parameters (cugp_sparse_cg_solve); the trace [n_iterates,
-        nh + 1] = (theta, -F) of the start and of the point every line search ended at, as Covsum.cg_solve_loo's."""
+        nh + 1] = (theta, -F) of the start and of the point every line search ended at, as Covsum.cg_solve_loo's.
+        inducing: the inducing inputs are variables too (cugp_sparse_cg_solve_z over [theta, vec Z]; the trace keeps
+        (theta, -F), get_inducing() reads Z back)."""
         budget = int(budget)
         tr = np.full((4 * max(budget, 0) + 8, self.nh + 1), np.nan)
         ne = C.c_int()
-        check(capi.lib().cugp_sparse_cg_solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        solve = capi.lib().cugp_sparse_cg_solve_z if inducing else capi.lib().cugp_sparse_cg_solve
+        check(solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
         rows = 1
         while rows < min(ne.value, tr.shape[0]) and not np.isnan(tr[rows, 0]):
             rows += 1

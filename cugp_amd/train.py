@@ -52,7 +52,7 @@ def train_sparse(args, local):
     g = SparseGP.from_subset(X, y, args.inducing, device=local, kernel=args.kernel, ard=args.ard)
     g.set_loghyperparam([args.hp[0]] * (g.nh - 2) + list(args.hp[1:]) if ard else args.hp)
     t0 = time.perf_counter()
-    trace = g.cg_solve(args.budget)
+    trace = g.cg_solve(args.budget, inducing=args.learn_inducing)
     dt = time.perf_counter() - t0
     hp = g.get_loghyperparam()
     print("\n\n PLEASE-SEE %d : %s\n" % (g.nh, ", ".join("%f" % v for v in hp)))
@@ -92,7 +92,12 @@ def main(argv=None, parse_only=False):
                     help="sparse variational GP regression on M inducing inputs, a random subset of the training rows, "
                          "instead of the exact model: cg_solve maximises the variational bound -- one model in one process "
                          "only (--numchunks 1, --objective ll)")
+    ap.add_argument("--learn-inducing", action="store_true",
+                    help="with --inducing: the inducing inputs are learned together with the hyper-parameters (conjugate "
+                         "gradients over both) instead of staying on the rows they were drawn from")
     args = ap.parse_args(argv)
+    if args.learn_inducing and not args.inducing:
+        ap.error("--learn-inducing needs --inducing M")
     if args.inducing < 0 or args.inducing > args.rows:
         ap.error("--inducing must lie between 1 and --rows")
     if args.inducing and (args.numchunks != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.objective != "ll"):

@@ -323,7 +323,7 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
 
 /* ---- sparse variational GP regression on M inducing inputs (SGPR: Titsias 2009, "Variational learning of inducing
  *      variables in sparse Gaussian processes"; GPML ch. 8 for the family; GPflow's SGPR).  No reference counterpart.
- *      Data X [N][d], y [N]; inducing inputs Z [M][d], given by the caller and fixed; the hyper-parameters, their order
+ *      Data X [N][d], y [N]; inducing inputs Z [M][d], given by the caller (cugp_sparse_cg_solve_z moves them); the hyper-parameters, their order
  *      and nh (3, ARD d + 2) and the five covariance families are those of a cugp_gp; s2 = exp(2 theta_n), sf2 =
  *      exp(2 theta_f); eps an absolute jitter fixed at creation (not a hyper-parameter, no gradient).  With
  *        Kuu = k(Z,Z) + eps I,  Kuf = k(Z,X),  Qff = Kfu Kuu^-1 Kuf
@@ -342,6 +342,14 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  *        dF/dtheta_n = 2 s2 [-N / (2 s2) + tr(Sigma^-1 Phi) / (2 s2^2) + y'y / (2 s2^2) - v'beta / s2^2 + beta'Phi beta / (2 s2^2)
  *                            + (N sf2 - tr Kuu^-1 Phi) / (2 s2^2)]
  *      through Lu and LB (Sigma^-1 = Lu^-T B^-1 Lu^-1), one weight product and one rectangular trace pass per chunk for any nh.
+ *      Gradient with respect to the inducing inputs: with H the factor of the input derivatives (SE and SE-ARD: k itself,
+ *      Matern 3/2: 3 sf2 e^-a, Matern 5/2: (5/3) sf2 (1 + a) e^-a) and s_c = 1 / l^2 (ARD: w_c^2),
+ *        dk(z_j, x) / dz_jc = -H(z_j, x) (z_jc - x_c) s_c
+ *        dF/dz_jc = -s_c sum_i G_uf[j,i] H(z_j,x_i) (z_jc - x_ic) - s_c sum_b (2 G_uu)[j,b] H(z_j,z_b) (z_jc - z_bc)
+ *      (row j and column j of Kuu both move with z_j: the symmetric 2 G_uu has weight 1 here, not the 1/2 of the trace; the
+ *      diagonal of Kuu and the jitter have no derivative; H is finite at zero distance and the difference exactly zero
+ *      there, so a z_j on a data row is no special case).  One more O(N M d) rectangular pass per chunk on the weights the
+ *      hyper-parameter gradient forms, differences before products, every sum in a fixed order; no N M^2 product is added.
  * cugp_sparse_create      : kernel CUGP_KERNEL_*; ard != 0: one length scale per dimension; jitter > 0 (1e-6 is customary);
  *                           chunk_rows 0 (the library's choice, 16384) or a multiple of 128.  m <= CUGP_SPARSE_MAX_M: the padded
  *                           m^2 stays below 2^31, so every element offset of the inner factorisation's kernels fits an int.
@@ -357,6 +365,14 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  *                           set.  trace (may be NULL): rows of nh + 1 doubles [theta, f] of the ITERATES, as
  *                           cugp_cg_solve_loo records them (f never rises along it; the row behind the last is NaN where
  *                           trace_cap leaves room).  *nevals <- evaluations made.
+ * cugp_sparse_bound_grad_z: cugp_sparse_bound_grad -- *F and g carry ITS bits -- and gZ [m][d] <- the gradient of -F with respect
+ *                           to the inducing inputs, in cugp_sparse_set_inducing's layout.  Kept like the other results.
+ * cugp_sparse_get_inducing: Z [m][d] <- the inducing inputs as the handle holds them.
+ * cugp_sparse_cg_solve_z  : cugp_sparse_cg_solve's loop over the nh + m d variables [theta, vec Z] from the current state; the
+ *                           end point stays set, theta and Z (read Z back with cugp_sparse_get_inducing).  trace: rows
+ *                           [theta, f] (nh + 1 doubles) of the iterates, under cugp_sparse_cg_solve's rules; a probe whose
+ *                           Kuu or B is not positive definite is a NaN probe to the loop.  CUGP_ERR_NOMEM when the partial
+ *                           blocks of the Z pass cannot be allocated: the handle stays as it was.
  * cugp_sparse_plan        : the schedule, pure arithmetic (no device): pass i streams the rows [out[0], out[0] + out[1]),
  *                           padded to out[2] (a multiple of 128); its Gram launch splits the k range [0, out[2]) of every
  *                           output tile out[3] ways, split s taking [s out[4], min((s + 1) out[4], out[2])); returns the
@@ -366,7 +382,7 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  * positive and finite; an nh that is not the handle's; nt <= 0; budget <= 0; an evaluation, prediction or solve before the
  * data or the inducing inputs are set.  CUGP_ERR_NODEVICE from cugp_sparse_create without a GPU.  A Kuu or B that is not
  * positive definite gives NaN results with CUGP_OK (the header's convention).
- * Not built: gradients with respect to Z; data sharded across GPUs (A A' and A y are sums over rows: one all-reduce); FITC;
+ * Not built: gradients with respect to Z of the predictions (the bound's: cugp_sparse_bound_grad_z); data sharded across GPUs (A A' and A y are sums over rows: one all-reduce); FITC;
  * multi-target; a C++ mirror in cugp_amd/host/. */
 #define CUGP_SPARSE_MAX_M 32768
 typedef struct cugp_sparse cugp_sparse;
@@ -383,6 +399,9 @@ int cugp_sparse_bound_grad(cugp_sparse *sp, double *F, double *g /* nh */, int n
 int cugp_sparse_predict(cugp_sparse *sp, const double *Xt, int nt, int with_noise, double *mean /* nt */, double *var /* nt */);
 int cugp_sparse_cg_solve(cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals);
 int cugp_sparse_plan(int n, int m, int chunk_rows, int pass, int out[5]);
+int cugp_sparse_bound_grad_z(cugp_sparse *sp, double *F, double *g /* nh */, int nh, double *gZ /* [m][d] */);
+int cugp_sparse_get_inducing(const cugp_sparse *sp, double *Z /* [m][d] */);
+int cugp_sparse_cg_solve_z(cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals);
 
 /* ---- stand-alone dense LA on a caller matrix (common/matrixops.h:5-25) ----
  * cugp_potrf        : get_cholesky            (L lower, upper zeroed)
