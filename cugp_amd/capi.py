@@ -103,6 +103,7 @@ SIGNATURES = {
     "cugp_sparse_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
     "cugp_sparse_cg_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_sparse_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
+    "cugp_sparse_predict_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     "cugp_sparse_bound_grad_z": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
     "cugp_sparse_get_inducing": (C.c_int, [C.c_void_p, _dp]),
     "cugp_sparse_cg_solve_z": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),

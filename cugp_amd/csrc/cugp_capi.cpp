@@ -2861,6 +2861,27 @@ int cugp_sparse_plan(int n, int m, int chunk_rows, int pass, int out[5])
     return c.chunks;
 }
 
+// test rows per prediction pass: whole 128-row tiles whose Ks, Wt and Vt ([rows][mpad] each) stay within 1 GiB, at most 2^20
+static int sparse_predict_rows(int mpad)
+{
+    const int rows = (int)std::min<size_t>(((size_t)1 << 30) / ((size_t)3 * mpad * sizeof(double)) / TILE * TILE, (size_t)1 << 20);
+    return rows < TILE ? TILE : rows;
+}
+
+int cugp_sparse_predict_plan(int m, int nt, int pass, int out[2])
+{
+    const char* call = "cugp_sparse_predict_plan";
+    if (!out) return tg_invalid(call, "out is NULL");
+    if (m < 1 || m > CUGP_SPARSE_MAX_M) return tg_invalid(call, "m < 1 or m beyond CUGP_SPARSE_MAX_M");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    const int rows = sparse_predict_rows((m + TILE - 1) / TILE * TILE);
+    const int passes = (int)(((long long)nt + rows - 1) / rows);
+    if (pass < 0 || pass >= passes) return tg_invalid(call, "pass beyond the last one");
+    out[0] = pass * rows;                                               // (< nt: no overflow)
+    out[1] = nt - out[0] < rows ? nt - out[0] : rows;
+    return passes;
+}
+
 int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, cugp_sparse** out)
 {
     const char* call = "cugp_sparse_create";
@@ -3017,10 +3038,10 @@ int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise
     TuneScope ts(u);
     hipStream_t st = u->stream;
     const int mp = s->mpad;
-    // test rows per pass: whole 128-row tiles whose Ks, Wt and Vt stay within 1 GiB
-    int chunk = (int)std::min<size_t>(((size_t)1 << 30) / ((size_t)3 * mp * sizeof(double)) / TILE * TILE, (size_t)1 << 20);
-    if (chunk < TILE) chunk = TILE;
-    const int cmax = ((nt < chunk ? nt : chunk) + TILE - 1) / TILE * TILE;
+    int pr[2];                                                         // the passes of cugp_sparse_predict_plan: the first is the largest
+    const int passes = cugp_sparse_predict_plan(s->m, nt, 0, pr);
+    if (passes < 1) return passes;
+    const int cmax = (pr[1] + TILE - 1) / TILE * TILE;
     const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)cmax * mp;
     if ((rc = s->pred.grow(nxt + 3 * nks + 2 * (size_t)nt, st))) return rc;
     double *dXt = s->pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dm = dVt + nks, *dv = dm + nt;
@@ -3029,8 +3050,9 @@ int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise
     if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
     const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
     const double* cp = s->dvec + mp;
-    for (int t0 = 0; t0 < nt; t0 += chunk) {
-        const int c = nt - t0 < chunk ? nt - t0 : chunk, cpad = (c + TILE - 1) / TILE * TILE;
+    for (int p = 0; p < passes; p++) {
+        (void)cugp_sparse_predict_plan(s->m, nt, p, pr);
+        const int t0 = pr[0], c = pr[1], cpad = (c + TILE - 1) / TILE * TILE;
         launch_kcross(u->dX, s->m, s->d, mp, dXt + (size_t)t0 * s->d, c, cpad, cf, dKs, st);
         launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
         launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T

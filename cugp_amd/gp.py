@@ -589,6 +589,10 @@ class SparseGP:
         """The schedule (cugp_sparse_plan): one (row0, rows, rows_padded, split, kstep) per pass over the data."""
         return sparse_plan(self.n, self.m, self.chunk_rows)
 
+    def predict_plan(self, nt):
+        """The passes predict() takes nt test points in (cugp_sparse_predict_plan): one (row0, rows) per pass."""
+        return sparse_predict_plan(self.m, nt)
+
 
 def sparse_plan(n, m, chunk_rows=0):
     """cugp_sparse_plan's passes for n rows against m inducing inputs: [(row0, rows, rows_padded, split, kstep)]."""
@@ -596,6 +600,20 @@ def sparse_plan(n, m, chunk_rows=0):
     passes, i = [], 0
     while True:
         count = capi.lib().cugp_sparse_plan(int(n), int(m), int(chunk_rows), i, out)
+        if count < 0:
+            check(count)
+        passes.append(tuple(out))
+        i += 1
+        if i >= count:
+            return passes
+
+
+def sparse_predict_plan(m, nt):
+    """cugp_sparse_predict_plan's passes for nt test points against m inducing inputs: [(row0, rows)]."""
+    out = (C.c_int * 2)()
+    passes, i = [], 0
+    while True:
+        count = capi.lib().cugp_sparse_predict_plan(int(m), int(nt), i, out)
         if count < 0:
             check(count)
         passes.append(tuple(out))

@@ -359,7 +359,7 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  * cugp_sparse_bound       : *F <- the bound.  cugp_sparse_bound_grad: also g <- the nh components of the gradient of -F, in
  *                           cugp_loglik_grad's convention and order.  The results of one (data, Z, theta) are kept.
  * cugp_sparse_predict     : mean and var at nt test points (host), with_noise != 0 adds s2; the test points are taken in
- *                           passes of whole 128-row tiles; it reuses the state of the last bound evaluation and evaluates
+ *                           passes of whole 128-row tiles (cugp_sparse_predict_plan's); it reuses the state of the last bound evaluation and evaluates
  *                           first when that is stale.
  * cugp_sparse_cg_solve    : the loop of cugp_cg_minimize_n on f = -F from the current hyper-parameters; the end point stays
  *                           set.  trace (may be NULL): rows of nh + 1 doubles [theta, f] of the ITERATES, as
@@ -377,6 +377,12 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  *                           padded to out[2] (a multiple of 128); its Gram launch splits the k range [0, out[2]) of every
  *                           output tile out[3] ways, split s taking [s out[4], min((s + 1) out[4], out[2])); returns the
  *                           number of passes, CUGP_ERR_INVALID for a pass beyond the last.
+ * cugp_sparse_predict_plan: the passes cugp_sparse_predict takes nt test points in against m inducing inputs, pure arithmetic
+ *                           (no device): pass i takes the test rows [out[0], out[0] + out[1]).  Every pass but the last has
+ *                           the same number of rows: whole 128-row tiles whose three [rows][mpad] matrices (Ks, Wt, Vt; mpad:
+ *                           m rounded up to 128) stay within 1 GiB, at most 2^20 rows (349440 rows at mpad 128).  Returns the
+ *                           number of passes, CUGP_ERR_INVALID for m < 1, m > CUGP_SPARSE_MAX_M, nt <= 0, a NULL out or a
+ *                           pass beyond the last.
  * Refusals, all CUGP_ERR_INVALID with the call's name in cugp_last_error before any device work: a NULL argument; n, d or
  * m < 1; m > CUGP_SPARSE_MAX_M; an unknown kernel kind; chunk_rows negative or not a multiple of 128; a jitter that is not
  * positive and finite; an nh that is not the handle's; nt <= 0; budget <= 0; an evaluation, prediction or solve before the
@@ -399,6 +405,7 @@ int cugp_sparse_bound_grad(cugp_sparse *sp, double *F, double *g /* nh */, int n
 int cugp_sparse_predict(cugp_sparse *sp, const double *Xt, int nt, int with_noise, double *mean /* nt */, double *var /* nt */);
 int cugp_sparse_cg_solve(cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals);
 int cugp_sparse_plan(int n, int m, int chunk_rows, int pass, int out[5]);
+int cugp_sparse_predict_plan(int m, int nt, int pass, int out[2]);
 int cugp_sparse_bound_grad_z(cugp_sparse *sp, double *F, double *g /* nh */, int nh, double *gZ /* [m][d] */);
 int cugp_sparse_get_inducing(const cugp_sparse *sp, double *Z /* [m][d] */);
 int cugp_sparse_cg_solve_z(cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals);

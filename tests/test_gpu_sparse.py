@@ -18,6 +18,16 @@ What the accuracy cases cover (truth_sparse.CASES: family, N, M, d, chunk_rows):
   ard 300 / 130 / 17 / 256          two feature chunks, two M tiles
   matern52_ard 257 / 64 / 3 / 128
   se 300 / 2 x 60 / 2 / 128         Z = 60 rows and the same rows shifted by 1e-4: cond(Kuu) ~ sf2 M / eps
+  se 800 / 65 / 3 / 0               the default chunk: one 896-row pass, the Gram launch split in 3 at kstep 304 -- 19, 19 and
+                                    18 stages of 16: the odd-stage tail of the double-buffered loop, a shorter last split
+  matern52 800 / 65 / 3 / 0         the same shape on isotropic Matern 5/2
+  matern32_ard 1000 / 130 / 3 / 896 Matern-3/2-ARD; two passes (896 rows split in 3, then 104 added to P), two M tiles
+  matern32_ard 257 / 64 / 3 / 128   its sibling with a central-difference check of the truth (tests/test_truth_sparse_cpu.py)
+  se 1300 / 260 / 6 / 0             mpad 384: six lower output tiles, 6 x 6 grids of the 64-wide passes, the products over
+                                    k = 384; one 1408-row pass split in 5 at kstep 288 (18, 18, 18, 18 and 16 stages)
+  matern52 300 / 65 / 32 / 128      d an exact multiple of the feature chunk of 16
+  ard 300 / 65 / 33 / 128           three feature chunks, the last of one feature
+  se 300 / 16 / 3 / 0               the model of the two-pass prediction (tests/test_gpu_sparse_wide.py)
 """
 import ctypes as C
 
@@ -77,7 +87,7 @@ def everything(s, Xt):
 def test_accuracy(gp_mod, name):
     c = ts.case(name)
     s, (X, y, Z, Xt, cov) = make(gp_mod, name)
-    assert len(s.plan()) == -(-len(y) // c["chunk"])
+    assert len(s.plan()) == -(-len(y) // ts.chunk_of(c["chunk"]))
     only = s.bound()
     F, g, m, v = everything(s, Xt)
     assert same_bits([only], [F])                              # the bound alone carries the bits of the full call
@@ -93,7 +103,7 @@ def test_accuracy(gp_mod, name):
 
 
 # ------------------------------------------------------------------ 2. determinism
-@pytest.mark.parametrize("name", ["se_n1300_m200", "ard_n300_m130_d17"])
+@pytest.mark.parametrize("name", ["se_n1300_m200", "ard_n300_m130_d17", "se_n800_m65_d3_c0", "se_n1300_m260_c0"])
 def test_bit_identical_on_repeat_and_on_a_second_handle(gp_mod, name):
     s, (X, y, Z, Xt, cov) = make(gp_mod, name)
     first = everything(s, Xt)
@@ -131,6 +141,29 @@ def test_chunk_rows_128_against_256(gp_mod):
         outs.append(out)
         s.close()
     print("CHUNK F 128: %.17g  256: %.17g" % (outs[0][0], outs[1][0]))
+
+
+@extended
+def test_chunk_rows_at_the_odd_split(gp_mod):
+    """The default chunk (0) and 896 give the same plan -- one 896-row pass split in 3 at kstep 304 -- and so the same bits;
+    512 and 128 give other partial sums in another order: each is held to the bound."""
+    name = "se_n800_m65_d3_c0"
+    c = ts.case(name)
+    rows = {0: [800], 896: [800], 512: [512, 288], 128: [128] * 6 + [32]}
+    outs = {}
+    for chunk in (0, 896, 512, 128):
+        s, (X, y, Z, Xt, cov) = make(gp_mod, name, chunk_rows=chunk)
+        if chunk in (0, 896):
+            assert s.plan() == [(0, 800, 896, 3, 304)]
+        assert [p[1] for p in s.plan()] == rows[chunk]
+        out = everything(s, Xt)
+        rep = Report("sparse/%s/chunk%d" % (name, chunk), cov)
+        ts.hold(rep, c, *out)
+        rep.check()
+        outs[chunk] = out
+        s.close()
+    print("CHUNK F " + "  ".join("%d: %.17g" % (k, v[0]) for k, v in outs.items()))
+    assert same_bits(outs[0], outs[896])
 
 
 # ------------------------------------------------------------------ 4. staleness

@@ -12,7 +12,10 @@ form in fp64 numpy / LAPACK over the data as given and truth.permutations; F_SPA
 
 What the cases reach (truth_sparse_z.CASES): no padding anywhere and two chunks; a ragged last chunk with mp padding beyond
 column 65; several row tiles per workgroup range with four column tiles; Matern 3/2; Matern 5/2; two feature chunks
-(d = 17); Matern-ARD.
+(d = 17); Matern-ARD; the default chunk (chunk_rows 0) with one 896-row pass in row ranges of 5, 5 and 4 tiles, on SE and
+on Matern 5/2; Matern-3/2-ARD over two passes and two column tiles, and on 257 rows; mpad 384 with one 1408-row pass in
+ranges of 5, 5, 5, 5 and 2 tiles and six column tiles; d = 32, an exact multiple of the feature chunk; d = 33, three feature
+chunks with the last of one feature; M = 16.
 """
 import ctypes as C
 
@@ -80,7 +83,8 @@ def test_accuracy(gp_mod, name):
 
 
 # ------------------------------------------------------------------ 2. F and g carry bound_grad's bits
-@pytest.mark.parametrize("name", ["se_n300_m65_d3", "se_n1300_m200", "ard_n300_m130_d17", "matern32_n300_m65"])
+@pytest.mark.parametrize("name", ["se_n300_m65_d3", "se_n1300_m200", "ard_n300_m130_d17", "matern32_n300_m65",
+                                  "se_n800_m65_d3_c0", "se_n1300_m260_c0"])
 def test_bound_and_hyper_gradient_keep_their_bits(gp_mod, name):
     s, _ = make(gp_mod, name)
     twin, _ = make(gp_mod, name)
@@ -97,7 +101,7 @@ def test_bound_and_hyper_gradient_keep_their_bits(gp_mod, name):
 
 
 # ------------------------------------------------------------------ 3. determinism
-@pytest.mark.parametrize("name", ["se_n1300_m200", "ard_n300_m130_d17"])
+@pytest.mark.parametrize("name", ["se_n1300_m200", "ard_n300_m130_d17", "se_n800_m65_d3_c0", "se_n1300_m260_c0"])
 def test_bit_identical_on_repeat_second_handle_and_after_a_detour(gp_mod, name):
     s, (X, y, Z, cov) = make(gp_mod, name)
     first = all_three(s)
@@ -130,8 +134,29 @@ def test_chunk_rows_128_against_256(gp_mod):
         s.close()
 
 
+@extended
+def test_chunk_rows_at_the_ragged_ranges(gp_mod):
+    """The default chunk (0) and 896 give the same plan -- one 896-row pass, row ranges of 5, 5 and 4 tiles -- and so the
+    same bits; 512 and 128 give other partial sums: each is held to the bound."""
+    name = "se_n800_m65_d3_c0"
+    c = tz.case(name)
+    rows = {0: [800], 896: [800], 512: [512, 288], 128: [128] * 6 + [32]}
+    outs = {}
+    for chunk in (0, 896, 512, 128):
+        s, (X, y, Z, cov) = make(gp_mod, name, chunk_rows=chunk)
+        if chunk in (0, 896):
+            assert s.plan() == [(0, 800, 896, 3, 304)]
+        assert [p[1] for p in s.plan()] == rows[chunk]
+        outs[chunk] = all_three(s)
+        rep = Report("sparse-z/%s/chunk%d" % (name, chunk), cov)
+        tz.hold(rep, c, outs[chunk][2])
+        rep.check()
+        s.close()
+    assert same_bits(outs[0], outs[896])
+
+
 # ------------------------------------------------------------------ 5. nothing beyond m d doubles is written
-@pytest.mark.parametrize("name", ["se_n300_m65_d3", "ard_n300_m130_d17"])
+@pytest.mark.parametrize("name", ["se_n300_m65_d3", "ard_n300_m130_d17", "se_n800_m65_d3_c0"])
 def test_guard_band_stays_intact(gp_mod, name):
     s, (X, y, Z, cov) = make(gp_mod, name)
     want = s.bound_grad_z()[2]

@@ -3,8 +3,8 @@ compiles for gfx950 -- runs behind tools/host_emul.h as 256 host threads per wor
 -fsanitize=address,undefined (tools/sparse_host_check.cpp; nothing is loaded into Python, nothing preloaded), on exact-size
 heap buffers with NaN where the kernels must not read, and is compared with numpy by the script's own run(): the trace sums
 of k_trace_cross<ARD, KIND> on a ragged chunk and on the square, k_sparse_finalize's results, and the small passes around
-the products.  The program is built once per module; the cases are the script's whole list (chunks of 44, 128, 1, 44, 1 and
-200 rows; M = 65, 128, 130, 64, 200; SE, Matern 3/2, SE-ARD with two feature chunks, Matern-5/2-ARD).  A case fails on a
+the products.  The program is built once per module; the cases are the script's whole list (chunks of 44, 128, 1, 44, 1,
+200 and 257 rows; M = 65, 128, 130, 64, 200 and 260 -- mpad 384 with five Gram partials --; SE, Matern 3/2, SE-ARD with two feature chunks, Matern-5/2-ARD).  A case fails on a
 non-zero exit, on anything a sanitizer writes to stderr, and on a result beyond its tolerance."""
 import os
 import sys
@@ -33,9 +33,11 @@ def test_the_list_covers_the_shapes_and_families():
     ms = {ts.CASES[name][2] for name, _ in sparse_host_check.CASES}
     assert {65, 128, 130, 200} <= ms                        # identity padding, none, two tiles (ragged), two tiles
     assert {rows for _, rows in sparse_host_check.CASES} >= {None, 1, 200}
+    # mpad 384 (three M tiles), 257 rows (three test tiles of the prediction), five Gram partials
+    assert sparse_host_check.CASES_MPAD384 == (("se_n1300_m260_c0", 257, 5),) and ts.CASES["se_n1300_m260_c0"][2] == 260
 
 
-@pytest.mark.parametrize("case", sparse_host_check.CASES, ids=lambda c: "-".join(str(v) for v in c))
+@pytest.mark.parametrize("case", sparse_host_check.CASES + sparse_host_check.CASES_MPAD384, ids=lambda c: "-".join(str(v) for v in c))
 def test_sparse(program, capfd, case):
     exe, tmp = program
     ok = sparse_host_check.run(exe, tmp, *case)

@@ -4,7 +4,7 @@ program built with -fsanitize=address,undefined (tools/sparse_z_host_check.cpp; 
 preloaded), on exact-size heap buffers with NaN where the kernels must not read, and is compared by the script's own run():
 bit for bit with a plain double loop in the kernels' summation order, and with the formula in numpy.  The program is built
 once per module; the cases are the script's whole list (a ragged chunk with the rank-one part and the square in every case;
-d = 2, 3, 6 and 17; one and two row ranges per column tile, four on the square; SE, Matern 3/2 and 5/2, SE-ARD with two
+d = 2, 3, 6 and 17; one and two row ranges per column tile, four on the square, ragged ranges of 5, 5, 4 and 5, 5, 5, 5, 2 tiles; SE, Matern 3/2 and 5/2, SE-ARD with two
 feature chunks, Matern-5/2-ARD).  A case fails on a non-zero exit, on anything a sanitizer writes to stderr, and on a
 result that differs."""
 import os
@@ -35,9 +35,12 @@ def test_the_list_covers_the_shapes_and_families():
     assert {c[2] for c in cases} >= {1, 2} and {c[3] for c in cases} >= {1, 2}  # one and two row ranges per column tile
     assert {c[1] for c in cases} >= {None, 1, 200}                              # ragged chunks; 200 rows: two tiles per range
     assert {tz.CASES[c[0]][2] for c in cases} >= {64, 65, 128, 130, 200}        # padding beyond column m, none, two column tiles
+    # the default chunk's ragged row ranges: 14 tiles in 3 ranges (5, 5, 4); 22 in 5 (5, 5, 5, 5, 2) with six column tiles
+    assert sparse_z_host_check.CASES_DEFAULT_CHUNK == (("se_n800_m65_d3_c0", None, 3, 1), ("se_n1300_m260_c0", None, 5, 3))
+    assert tz.z_ranges(896, 128, 3) == [5, 5, 4] and tz.z_ranges(1408, 384, 6) == [5, 5, 5, 5, 2]
 
 
-@pytest.mark.parametrize("case", sparse_z_host_check.CASES, ids=lambda c: "-".join(str(v) for v in c))
+@pytest.mark.parametrize("case", sparse_z_host_check.CASES + sparse_z_host_check.CASES_DEFAULT_CHUNK, ids=lambda c: "-".join(str(v) for v in c))
 def test_sparse_z(program, capfd, case):
     exe, tmp = program
     ok = sparse_z_host_check.run(exe, tmp, *case)

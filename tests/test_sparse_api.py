@@ -29,6 +29,7 @@ NEW = {
     "cugp_sparse_predict": [_vp, _dp, C.c_int, C.c_int, _dp, _dp],
     "cugp_sparse_cg_solve": [_vp, C.c_int, _dp, C.c_int, _ip],
     "cugp_sparse_plan": [C.c_int, C.c_int, C.c_int, C.c_int, _ip],
+    "cugp_sparse_predict_plan": [C.c_int, C.c_int, C.c_int, _ip],
 }
 DECLS = {
     "cugp_sparse_create": "int n, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, cugp_sparse **out",
@@ -44,6 +45,7 @@ DECLS = {
     "cugp_sparse_predict": "cugp_sparse *sp, const double *Xt, int nt, int with_noise, double *mean, double *var",
     "cugp_sparse_cg_solve": "cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals",
     "cugp_sparse_plan": "int n, int m, int chunk_rows, int pass, int out[5]",
+    "cugp_sparse_predict_plan": "int m, int nt, int pass, int out[2]",
 }
 INV = capi.CUGP_ERR_INVALID
 
@@ -128,6 +130,38 @@ def test_null_handles_and_plan_arguments():
     assert L.cugp_sparse_plan(300, 10, 128, 2, iv) == 3 and list(iv) == [256, 44, 128, 1, 128]
 
 
+def test_predict_plan_refusals():
+    """cugp_sparse_plan's conventions: CUGP_ERR_INVALID with the call's name, out untouched, no device looked for."""
+    L = capi.lib()
+    iv = (C.c_int * 2)(7, 7)
+    for m, nt, p in ((0, 10, 0), (-1, 10, 0), (32769, 10, 0), (16, 0, 0), (16, -5, 0), (16, 10, -1), (16, 10, 1),
+                     (16, 349440, 1), (16, 349441, 2), (32768, 5000, 4)):
+        assert refused(L.cugp_sparse_predict_plan(m, nt, p, iv), "cugp_sparse_predict_plan"), (m, nt, p)
+    assert refused(L.cugp_sparse_predict_plan(16, 10, 0, None), "cugp_sparse_predict_plan")
+    assert list(iv) == [7, 7]
+    assert L.cugp_sparse_predict_plan(16, 349441, 1, iv) == 2 and list(iv) == [349440, 1]
+    assert L.cugp_sparse_predict_plan(32768, 2 ** 31 - 1, 0, iv) == -(-(2 ** 31 - 1) // 1280) and list(iv) == [0, 1280]
+
+
+@pytest.mark.parametrize("m, nt", [(16, 20), (16, 349569), (2048, 1000000), (32768, 5000)])
+def test_predict_plan_covers_every_test_row_once(m, nt):
+    """Every test row lies in exactly one pass, the passes ascend, no pass but the last is ragged, and a pass is the rule's:
+    whole 128-row tiles whose three [rows][mpad] matrices of doubles stay within 1 GiB, at most 2^20 rows."""
+    passes = gp.sparse_predict_plan(m, nt)
+    mpad = -(-m // 128) * 128
+    full = max(128, min((1 << 30) // (3 * mpad * 8) // 128 * 128, 1 << 20))
+    assert len(passes) == -(-nt // full)
+    nxt = 0
+    for i, (r0, cnt) in enumerate(passes):
+        assert r0 == nxt and cnt > 0
+        assert cnt == full if i < len(passes) - 1 else cnt <= full
+        assert r0 % 128 == 0 and 3 * (-(-cnt // 128) * 128) * mpad * 8 <= 1 << 30
+        nxt = r0 + cnt
+    assert nxt == nt
+    first = {(16, 20): (1, 20), (16, 349569): (2, 349440), (2048, 1000000): (46, 21760), (32768, 5000): (4, 1280)}[m, nt]
+    assert (len(passes), passes[0][1]) == first
+
+
 def test_no_device_is_never_a_handle():
     L = capi.lib()
     cnt = C.c_int()
@@ -199,6 +233,11 @@ class _Lib:
         out[0], out[1], out[2], out[3], out[4] = p * 128, 128, 128, 1, 128
         return 2
 
+    def cugp_sparse_predict_plan(self, m, nt, p, out):
+        self.calls.append(("predict_plan", m, nt, p))
+        out[0], out[1] = p * 256, min(256, nt - p * 256)
+        return -(-nt // 256)
+
 
 @pytest.mark.parametrize("kernel, ard, nh, kind", [("se", False, 3, 0), ("se", True, 6, 0), ("matern52_ard", False, 6, 2),
                                                    ("matern32", False, 3, 1)])
@@ -227,6 +266,7 @@ def test_sparsegp_plumbing(monkeypatch, kernel, ard, nh, kind):
     assert m.shape == v.shape == (7,) and (m[0], v[0]) == (1.0, 2.0) and fake.calls[-1] == ("predict", 7, 0)
     assert s.cg_solve(budget=7).shape == (2, nh + 1) and fake.calls[-1] == ("cg_solve", 7, 36)
     assert s.plan() == [(0, 128, 128, 1, 128), (128, 128, 128, 1, 128)]
+    assert s.predict_plan(600) == [(0, 256), (256, 256), (512, 88)] and fake.calls[-1] == ("predict_plan", 3, 600, 2)
     s.close()
     assert fake.calls[-1] == ("destroy",)
 

@@ -6,7 +6,10 @@
   - the stand-in -- the library's formulation, chunked by cugp_sparse_plan -- within F_SPARSE of the yardstick, and
     F_SPARSE is the larger of the family's factor and truth.factor_rule of the largest ratio measured here
   - two mutations of the stand-in leave the bound: F without its trace term, G_uf without the factor 2
-  - cugp_sparse_plan replayed: every data row in exactly one chunk, every k of a Gram tile in exactly one split, ascending
+  - cugp_sparse_plan replayed: every data row in exactly one chunk, every k of a Gram tile in exactly one split, ascending;
+    the two default-chunk SE cases sit on the odd-stage, shorter-last-split shapes they were chosen for
+  - beyond one test tile (tests/test_gpu_sparse_wide.py): at 129, 200 and 257 test points, and at the two-pass prediction's
+    P + 129, the yardstick is sane and the stand-in within the family's factor, which truth.factor_rule confirms
 """
 import numpy as np
 import pytest
@@ -17,8 +20,9 @@ import truth_sparse as ts
 LD = truth.LD
 pytestmark = pytest.mark.skipif(not truth.EXTENDED, reason="numpy.longdouble is not an extended-precision type here")
 NAMES = list(ts.CASES)
-# central differences evaluate the N x N definition 2 nh times: every case but the 1300-row one (its six evaluations of a
-# 1300 x 1300 longdouble factorisation would take minutes; its gradient runs through the same code as the other SE cases)
+# central differences evaluate the N x N definition 2 nh times: every case of up to 300 rows (six evaluations of a
+# 1300 x 1300 longdouble factorisation would take minutes; the gradients of the larger cases run through the same code as
+# their families' small ones -- matern32_ard_n257_m64 is there for matern32_ard_n1000_m130)
 CD_NAMES = [n for n in NAMES if ts.CASES[n][1] <= 300]
 
 
@@ -111,7 +115,7 @@ def test_factors_follow_the_rule():
               % (fam, w, rule, ts.EXISTING[fam], ts.F_SPARSE[fam]))
         assert rule <= ts.F_SPARSE[fam], (fam, w, rule)
         assert ts.F_SPARSE[fam] >= ts.EXISTING[fam], fam
-    assert set(worst) == set(ts.F_SPARSE) - {"matern52"}         # (every family of the case list; matern52 has no case of its own)
+    assert set(worst) == set(ts.F_SPARSE)                        # every family has a case of its own
 
 
 @pytest.mark.parametrize("mutate, quantity", [("drop_tr", 0), ("guf_without_2", 1)])
@@ -126,7 +130,8 @@ def test_mutations_leave_the_bound(name, mutate, quantity):
 
 
 @pytest.mark.parametrize("n, m, chunk_rows", [(128, 128, 128), (300, 65, 128), (1300, 200, 512), (300, 130, 256),
-                                              (257, 64, 128), (5000, 1024, 0), (100000, 2048, 0), (70000, 128, 16384)])
+                                              (257, 64, 128), (5000, 1024, 0), (100000, 2048, 0), (70000, 128, 16384),
+                                              (800, 65, 0), (1000, 130, 896), (1300, 260, 0)])
 def test_plan_covers_rows_and_k_once(n, m, chunk_rows):
     passes = ts.plan(n, m, chunk_rows)
     rows = np.zeros(n, dtype=int)
@@ -150,3 +155,74 @@ def test_plan_splits_where_the_cases_say():
     assert [p[3] for p in ts.plan(1300, 200, 512)] == [2, 2, 1]          # three output tiles: the 512-row chunks split in 2
     assert [p[1] for p in ts.plan(300, 65, 128)] == [128, 128, 44]
     assert all(p[3] == 1 for p in ts.plan(300, 65, 128))
+    # the two default-chunk SE cases: an odd stage count (304 / 16 = 19) with a shorter last split; five splits of 18, 18,
+    # 18, 18 and 16 stages -- a change of the split rule must not move them off these paths silently
+    for name, want in (("se_n800_m65_d3_c0", (0, 800, 896, 3, 304)), ("se_n1300_m260_c0", (0, 1300, 1408, 5, 288))):
+        _, N, M, _, chunk = ts.CASES[name][:5]
+        assert chunk == 0 and ts.plan(N, M, chunk) == [want], name
+    assert [min(304, 896 - s * 304) // 16 for s in range(3)] == [19, 19, 18]
+    assert [min(288, 1408 - s * 288) // 16 for s in range(5)] == [18, 18, 18, 18, 16]
+    assert ts.plan(1000, 130, 896) == [(0, 896, 896, 3, 304), (896, 104, 128, 1, 128)]
+
+
+# ------------------------------------------------------------------ beyond one test tile (tests/test_gpu_sparse_wide.py)
+WIDE = [(name, nt) for name in ts.WIDE_NAMES for nt in ts.WIDE_NTS]
+_WIDE_RATIOS = {}
+
+
+def wide_standin_ratios(name, nt):
+    if (name, nt) not in _WIDE_RATIOS:
+        c, w = ts.case(name), ts.wide_case(name, nt)
+        out = ts.standin(c["cov"], c["X"], c["y"], c["Z"], w["Xt"], c["chunk"])
+        _WIDE_RATIOS[name, nt] = ts.wide_ratios(c, w, out[2], out[3])
+    return _WIDE_RATIOS[name, nt]
+
+
+@pytest.mark.parametrize("name, nt", WIDE)
+def test_wide_points_yardstick_and_standin(name, nt):
+    """At 129, 200 and 257 test points: the training row and the inducing input are where the GPU test needs them, the
+    yardstick is sane under truth_sparse.assert_yardstick_is_sane's two conditions, and the stand-in stays within the
+    family's factor."""
+    c, w = ts.case(name), ts.wide_case(name, nt)
+    Xt = w["Xt"]
+    assert Xt.shape == (nt, c["X"].shape[1]) and ts.WIDE_Z_ROW >= 128
+    assert np.array_equal(Xt[ts.WIDE_Z_ROW], c["Z"][0]) and np.array_equal(Xt[nt - 2], c["X"][len(c["X"]) // 2])
+    for q in ("mean", "var"):
+        assert w["first"][q] <= c["cov"].F * max(w["rest"][q], c["floor"][q]), (name, nt, q, w["first"][q], w["rest"][q])
+        assert w["noise"][q] <= truth.YARDSTICK_CAP * c["floor"][q] / truth.U4, (name, nt, q, w["noise"][q])
+    r = wide_standin_ratios(name, nt)
+    print("STANDIN-WIDE %-24s nt %-3d " % (name, nt) + "  ".join("%s %.2f (yardstick %.2e)" % (q, v, w["noise"][q])
+                                                                for q, v in r.items()))
+    assert max(r.values()) <= ts.F_SPARSE[c["family"]], r
+
+
+def test_wide_factors_follow_the_rule():
+    worst = {}
+    for name, nt in WIDE:
+        fam = ts.CASES[name][0]
+        worst[fam] = max(worst.get(fam, 0.0), max(wide_standin_ratios(name, nt).values()))
+    for fam, w in worst.items():
+        rule = truth.factor_rule(w)
+        print("F_SPARSE wide %-12s largest stand-in ratio %.2f  factor_rule %d  F_SPARSE %d" % (fam, w, rule, ts.F_SPARSE[fam]))
+        assert rule <= ts.F_SPARSE[fam], (fam, w, rule)
+
+
+def test_two_pass_prediction_yardstick_and_standin():
+    """The prediction that takes two passes (tests/test_gpu_sparse_wide.py): nt = P + 129 with P cugp_sparse_predict_plan's
+    first pass; the row behind the pass boundary is Z[0], the one before it a data row; yardstick and stand-in on ALL rows."""
+    import cugp_amd.gp as gp
+    name = ts.TWO_PASS_NAME
+    c = ts.case(name)
+    P = gp.sparse_predict_plan(ts.CASES[name][2], 1 << 30)[0][1]
+    nt = P + 129
+    assert P == 349440 and gp.sparse_predict_plan(ts.CASES[name][2], nt) == [(0, P), (P, 129)]
+    w = ts.wide_case(name, nt, z_row=P, data_row=P - 1)
+    assert np.array_equal(w["Xt"][P], c["Z"][0]) and np.any(np.all(c["X"] == w["Xt"][P - 1], axis=1))
+    for q in ("mean", "var"):
+        assert w["first"][q] <= c["cov"].F * max(w["rest"][q], c["floor"][q]), (q, w["first"][q], w["rest"][q])
+        assert w["noise"][q] <= truth.YARDSTICK_CAP * c["floor"][q] / truth.U4, (q, w["noise"][q])
+    out = ts.standin(c["cov"], c["X"], c["y"], c["Z"], w["Xt"], c["chunk"])
+    r = ts.wide_ratios(c, w, out[2], out[3])
+    print("STANDIN-TWO-PASS %s nt %d " % (name, nt) + "  ".join("%s %.2f (yardstick %.2e)" % (q, v, w["noise"][q])
+                                                               for q, v in r.items()))
+    assert truth.factor_rule(max(r.values())) <= ts.F_SPARSE[c["family"]], r

@@ -94,8 +94,27 @@ def test_mutations_leave_the_bound(name, mutate):
     assert r > 1000 * tz.F_SPARSE_Z[c["family"]]
 
 
+def test_row_ranges_where_the_cases_say():
+    """The Z pass's row ranges of the default-chunk cases are ragged -- 5, 5, 4 and 5, 5, 5, 5, 2 tiles --, those of the
+    earlier cases equal; the replay's constant is the library's."""
+    import os
+    import re
+    from conftest import ROOT
+    with open(os.path.join(ROOT, "cugp_amd", "csrc", "kernels.h")) as f:
+        assert int(re.search(r"constexpr int SPARSE_Z_SLOTS = (\d+);", f.read()).group(1)) == tz.Z_SLOTS
+
+    def of(name):
+        _, N, M, d, chunk, _ = tz.CASES[name]
+        return [tz.z_ranges(p[2], -(-M // 128) * 128, d) for p in ts.plan(N, M, chunk)]
+    assert of("se_n800_m65_d3_c0") == of("matern52_n800_m65_d3_c0") == [[5, 5, 4]]
+    assert of("se_n1300_m260_c0") == [[5, 5, 5, 5, 2]]
+    assert of("matern32_ard_n1000_m130") == [[5, 5, 4], [2]]
+    assert of("se_n1300_m200") == [[4, 4], [4, 4], [6]] and of("se_n300_m65_d3") == [[2], [2], [2]]
+    assert tz.z_ranges(384, 384, 6) == [6]                       # the square of mpad 384: six column tiles, one range
+
+
 def test_the_cases_and_what_is_left_out():
     assert set(tz.MUTATIONS) == {"square_half", "no_rank_one", "s0_for_all"}
-    assert {tz.CASES[n][0] for n in NAMES} == {"se", "matern32", "matern52", "ard", "matern52_ard"}
+    assert {tz.CASES[n][0] for n in NAMES} == {"se", "matern32", "matern52", "ard", "matern32_ard", "matern52_ard"}
     for left_out in ("se_n300_m65", "se_n300_dup60", "se_n128_m128"):
         assert left_out in ts.CASES and left_out not in tz.CASES and left_out in tz.__doc__

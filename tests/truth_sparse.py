@@ -37,6 +37,9 @@ LOG2PI = np.log(LD(8) * np.arctan(LD(1)))      # log 2 pi in longdouble
 
 _ARD17 = truth.ARD_CASES["n300_d17"]
 _ARD3 = truth.ARD_CASES["n257_d3"]
+_ARD33 = truth.ARD_CASES["n515_d33"]
+_LIVE33 = truth.LIVE_CASES["n515_d33"]
+CHUNK_DEFAULT = 16384                          # what chunk_rows = 0 stands for (include/cugp.h: cugp_sparse_create)
 # name -> (family, N, M, d, chunk_rows, hyper-parameters (of the existing case tables), box half-width of synth, duplicates)
 CASES = {
     "se_n128_m128": ("se", 128, 128, 2, 128, HP_DEFAULT, 4.0, False),         # no padding anywhere, one chunk
@@ -46,16 +49,35 @@ CASES = {
     "ard_n300_m130_d17": ("ard", 300, 130, 17, 256, list(_ARD17[2]) + [_ARD17[3], _ARD17[4]], _ARD17[5], False),
     "matern52_ard_n257_m64": ("matern52_ard", 257, 64, 3, 128, list(_ARD3[2]) + [_ARD3[3], _ARD3[4]], _ARD3[5], False),
     "se_n300_dup60": ("se", 300, 120, 2, 128, HP_DEFAULT, 4.0, True),         # Z = 60 rows and the same rows + 1e-4
+    # chunk_rows 0 (the library's 16384): one 896-row pass, the Gram launch split in 3 with kstep 304 -- 19, 19 and 18
+    # stages of 16, an odd count and a shorter last split --, row ranges of 5, 5 and 4 tiles in the Z pass
+    "se_n800_m65_d3_c0": ("se", 800, 65, 3, 0, HP_DEFAULT, 4.0, False),
+    "matern52_n800_m65_d3_c0": ("matern52", 800, 65, 3, 0, HP_DEFAULT, 4.0, False),
+    # two passes (896 rows split in 3, then 104 accumulated behind them), two M tiles
+    "matern32_ard_n1000_m130": ("matern32_ard", 1000, 130, 3, 896, list(_ARD3[2]) + [_ARD3[3], _ARD3[4]], _ARD3[5], False),
+    "matern32_ard_n257_m64": ("matern32_ard", 257, 64, 3, 128, list(_ARD3[2]) + [_ARD3[3], _ARD3[4]], _ARD3[5], False),
+    # mpad 384 (six lower output tiles): one 1408-row pass split in 5 with kstep 288, Z ranges of 5, 5, 5, 5 and 2 tiles
+    "se_n1300_m260_c0": ("se", 1300, 260, 6, 0, truth.HP_A, 2.5, False),
+    # d an exact multiple of the feature chunk DC = 16; three feature chunks, the last of one feature
+    "matern52_n300_m65_d32": ("matern52", 300, 65, 32, 128, _LIVE33[2], _LIVE33[3], False),
+    "ard_n300_m65_d33": ("ard", 300, 65, 33, 128, list(_ARD33[2]) + [_ARD33[3], _ARD33[4]], _ARD33[5], False),
+    "se_n300_m16_d3": ("se", 300, 16, 3, 0, HP_DEFAULT, 4.0, False),          # the model of the two-pass prediction
 }
 DUP_SHIFT = 1e-4
 
 EXISTING = {"se": truth.F, "matern32": truth.F_MATERN, "matern52": truth.F_MATERN, "ard": truth.F_ARD,
-            "matern52_ard": truth.F_ARD}
+            "matern52_ard": truth.F_ARD, "matern32_ard": truth.F_ARD}
 # The larger of the family's existing factor and truth.factor_rule of the largest stand-in / yardstick ratio over CASES
 # (tests/test_truth_sparse_cpu.py measures and asserts; docs/ACCURACY.md: the table).
-# Largest stand-in ratios measured: se 3.07 (g0 of se_n1300_m200; factor_rule 8), matern32 1.13, ard 2.35, matern52_ard
-# 1.60 (factor_rule 4 to 8): every family's existing factor stands.
+# Largest stand-in ratios measured: se 3.07 (g0 of se_n1300_m200; factor_rule 8), matern32 1.13, matern52 0.78, ard 2.35,
+# matern52_ard 1.60, matern32_ard 2.27 (gf of matern32_ard_n1000_m130) (factor_rule 2 to 8); at the wide test points 1.63
+# at most (the variance of se_n1300_m260_c0 at nt = 257; factor_rule 4): every family's existing factor stands.
 F_SPARSE = dict(EXISTING)
+
+
+def chunk_of(chunk_rows):
+    """chunk_rows as the library resolves it: 0 is its default (cugp_sparse_dims reports the same)."""
+    return chunk_rows if chunk_rows > 0 else CHUNK_DEFAULT
 
 
 def inputs(name):
@@ -298,6 +320,59 @@ def case(name):
                             noise={q: max(e[q] for e in E) for q in Q}, first={q: E[0][q] for q in Q},
                             rest={q: max(e[q] for e in E[1:]) for q in Q}, floor={q: fl[q] for q in Q})
     return _CASES[name]
+
+
+# ---------------------------------------------------------------------------------------- beyond one test tile
+# tests/test_gpu_sparse_wide.py: NT = 20 runs one 128-row test tile, and rows below 128 of k_sparse_predict_finish only.
+WIDE_NTS = truth.WIDE_NTS                      # two tiles, one row into the second; two tiles, ragged; three tiles
+WIDE_NAMES = ("se_n800_m65_d3_c0", "se_n1300_m260_c0", "matern32_ard_n1000_m130", "ard_n300_m65_d33")
+WIDE_Z_ROW = 128                               # the test row that is Z[0]: the first row of the second tile at every size
+TWO_PASS_NAME = "se_n300_m16_d3"               # the model of the prediction that takes two passes
+_WIDE = {}
+
+
+def wide_points(name, nt, z_row=WIDE_Z_ROW, data_row=None):
+    """truth.wide_points of the case's data (the last but one a training row) with row z_row replaced by Z[0] -- a test point
+    that is an inducing input --, and, where given, row data_row by a data row."""
+    X, _, Z, _, _, _ = inputs(name)
+    Xt = truth.wide_points(X, nt, CASES[name][6])
+    Xt[z_row] = Z[0]
+    if data_row is not None:
+        Xt[data_row] = X[len(X) // 3]
+    return np.ascontiguousarray(Xt)
+
+
+def wide_case(name, nt, z_row=WIDE_Z_ROW, data_row=None):
+    """The case at nt test points: Xt, the truth's mean and variance (with noise) there and the yardstick -- computed_form at
+    the same points over the data as given and truth.permutations --, once per process.  The floors are case()'s."""
+    key = (name, nt, z_row, data_row)
+    if key not in _WIDE:
+        c = case(name)
+        Xt = wide_points(name, nt, z_row, data_row)
+        tm, tv = c["t"].predict(Xt)
+        E = [truth.errors_pred(*computed_form(c["cov"], c["X"][idx], c["y"][idx], c["Z"], Xt)[2:], tm, tv)
+             for idx in truth.permutations(len(c["y"]))]
+        _WIDE[key] = dict(Xt=Xt, tm=tm, tv=tv, noise={q: max(e[q] for e in E) for q in ("mean", "var")},
+                          first={q: E[0][q] for q in ("mean", "var")}, rest={q: max(e[q] for e in E[1:]) for q in ("mean", "var")})
+    return _WIDE[key]
+
+
+def wide_ratios(c, w, mean, var):
+    """error / max(yardstick, floor) of the means and variances at a wide_case's points."""
+    e = truth.errors_pred(mean, var, w["tm"], w["tv"])
+    return {q: e[q] / max(w["noise"][q], c["floor"][q]) for q in ("mean", "var")}
+
+
+def hold_wide(rep, c, w, mean, var, latent_var=None, tag=""):
+    """Adds the means and variances (with noise) at a wide_case's points to the accuracy.Report `rep` under the bound
+    F_SPARSE[family]; with latent_var also the variances without noise against the truth's."""
+    e = truth.errors_pred(mean, var, w["tm"], w["tv"])
+    F = F_SPARSE[c["family"]]
+    for q in ("mean", "var"):
+        rep.add(tag + q, e[q], w["noise"][q], c["floor"][q], F)
+    if latent_var is not None:
+        el = float(np.max(np.abs(np.asarray(latent_var).astype(LD) - (w["tv"] - c["cov"].sn2))))
+        rep.add(tag + "latent_var", el, w["noise"]["var"], c["floor"]["var"], F)
 
 
 def ratios(c, out):

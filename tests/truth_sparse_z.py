@@ -49,12 +49,21 @@ CASES = {
     "matern52_n300_m65_d3": ("matern52", 300, 65, 3, 128, "Matern 5/2"),
     "ard_n300_m130_d17": ("ard", 300, 130, 17, 256, "two feature chunks (d = 17 > DC)"),
     "matern52_ard_n257_m64": ("matern52_ard", 257, 64, 3, 128, "Matern-ARD"),
+    "se_n800_m65_d3_c0": ("se", 800, 65, 3, 0, "the default chunk: one 896-row pass, row ranges of 5, 5 and 4 tiles"),
+    "matern52_n800_m65_d3_c0": ("matern52", 800, 65, 3, 0, "the same shape, Matern 5/2"),
+    "matern32_ard_n1000_m130": ("matern32_ard", 1000, 130, 3, 896, "Matern-3/2-ARD: two passes, two M tile rows"),
+    "matern32_ard_n257_m64": ("matern32_ard", 257, 64, 3, 128, "Matern-3/2-ARD"),
+    "se_n1300_m260_c0": ("se", 1300, 260, 6, 0, "mpad 384: row ranges of 5, 5, 5, 5 and 2 tiles, six column tiles"),
+    "matern52_n300_m65_d32": ("matern52", 300, 65, 32, 128, "d an exact multiple of DC: the last chunk stays staged, full"),
+    "ard_n300_m65_d33": ("ard", 300, 65, 33, 128, "three feature chunks, the last of one feature"),
+    "se_n300_m16_d3": ("se", 300, 16, 3, 0, "the model of the two-pass prediction"),
 }
 
 # The larger of F_SPARSE[family] and truth.factor_rule of the largest stand-in / yardstick ratio over CASES
 # (tests/test_truth_sparse_z_cpu.py measures and asserts; docs/ACCURACY.md: the table).
-# Largest stand-in ratios measured: se 1.21 (se_n256_m128_d3; factor_rule 4), matern32 0.94, matern52 1.01, ard 1.21,
-# matern52_ard 0.99 (factor_rule 2 to 4): every family's F_SPARSE (8, 16, 16, 32, 32) stands.
+# Largest stand-in ratios measured: se 1.21 (se_n256_m128_d3; factor_rule 4), matern32 0.94, matern52 1.19
+# (matern52_n300_m65_d32), ard 1.21, matern52_ard 0.99, matern32_ard 0.71 (factor_rule 2 to 4): every family's F_SPARSE
+# (8, 16, 16, 32, 32, 32) stands.
 F_SPARSE_Z = dict(ts.F_SPARSE)
 
 
@@ -68,6 +77,20 @@ def inputs(name):
     X, y = synth(N, d=d, seed=3 * N + d, scale=4.0)
     rows = np.sort(np.random.default_rng(1000 + M).choice(N, M, replace=False))
     return X, y, np.ascontiguousarray(X[rows]), truth.FAMILIES[family][1](list(HP_DEFAULT)), chunk
+
+
+Z_SLOTS = 512                     # SPARSE_Z_SLOTS of cugp_amd/csrc/kernels.h (tests/test_truth_sparse_z_cpu.py reads it there)
+
+
+def z_ranges(rows_pad, mpad, d, slots=Z_SLOTS):
+    """sparse_z_shape (cugp_amd/csrc/kernels.hip) replayed: the 64-row tiles of each row range of one k_trace_cross_z launch
+    over rows_pad rows -- the last range is what the clamp to the tile count leaves."""
+    tiles = rows_pad // 64
+    ranges = max(1, min(slots // (mpad // 64), rows_pad // 256))
+    while ranges > 1 and ranges * mpad * d * 8 > 1 << 30:
+        ranges -= 1
+    per = -(-tiles // ranges)
+    return [min(per, tiles - t0) for t0 in range(0, tiles, per)]
 
 
 # ---------------------------------------------------------------------------------------- the formula

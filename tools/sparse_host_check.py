@@ -3,10 +3,12 @@ k_trace_cross<ARD, KIND> (one chunk with the rank-one part; the square (Z, Z)), 
 around the products (k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty and its finish, k_sparse_yy, k_sparse_h,
 k_sparse_transpose, k_sparse_predict_finish) -- the text kernels.hip includes -- in a lock-step host emulation
 (tools/sparse_host_check.cpp) built with -fsanitize=address,undefined.  The MFMA product k_sparse_gram is not emulated.
-The chunk is the LAST chunk of a case of tests/truth_sparse.py (ragged: 44, 1 or 128 rows of a 128-row pad), its weight
-matrix random; rows beyond the chunk and columns beyond M are NaN in every input a kernel must mask, and so are the strict
-upper 128-tiles of P and B^-1: a missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  Compared with
-numpy on the same inputs:
+The chunk is the LAST chunk of a case of tests/truth_sparse.py (ragged: 44, 1 or 128 rows of a 128-row pad; 257 rows of a
+384-row pad at mpad 384, where k_sparse_gram_finish adds five partial tiles, k_sparse_h and k_sparse_transpose run 6 x 6
+blocks and k_sparse_predict_finish three test tiles; chunk_rows 0 is the library's 16384), its weight matrix random; rows
+beyond the chunk and columns beyond M are NaN in every input a kernel must mask, and so are the strict upper 128-tiles of P
+and B^-1: a missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  Compared with numpy on the same
+inputs:
   trace sums  per column, the blocks' partial sums added in longdouble against sum w o dK: 1e-13 of sum |w o dK|
   results     F and the nh gradient components against k_sparse_finalize's formulas in numpy: 1e-13 of their scale
   small       P, B, q, y'y, H, H2, beta / s2^2, the transpose, mean and var: 4 ulp of the largest entry (sums: 1e-13)
@@ -22,16 +24,20 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-# (case of truth_sparse.CASES, rows of the chunk or None for the case's last chunk)
+# (case of truth_sparse.CASES, rows of the chunk or None for the case's last chunk); three partial tiles in k_sparse_gram_finish
 CASES = (("se_n300_m65", None), ("se_n128_m128", None), ("matern32_n300_m65", 1), ("ard_n300_m130_d17", None),
          ("matern52_ard_n257_m64", None), ("se_n1300_m200", 200))
+# the same with the number of partial tiles k_sparse_gram_finish adds: mpad 384, five partials, 257 rows (three test tiles)
+CASES_MPAD384 = (("se_n1300_m260_c0", 257, 5),)
 ULP4 = 4 * 2.0 ** -52
+CHUNK_DEFAULT = 16384                   # what chunk_rows = 0 stands for in the library (include/cugp.h: cugp_sparse_create)
 
 
-def run(exe, tmp, name, rows):
+def run(exe, tmp, name, rows, nscr=3):
     import truth_sparse as ts
     X, y, Z, _, cov, chunk = ts.inputs(name)
     c64 = cov.fp64()
+    chunk = chunk if chunk > 0 else CHUNK_DEFAULT
     r0 = (len(y) - 1) // chunk * chunk
     Xr, yr = X[r0:], y[r0:]
     if rows is not None:
@@ -39,7 +45,7 @@ def run(exe, tmp, name, rows):
     nr, (m, d) = len(yr), Z.shape
     ld, rows_pad = (m + 127) // 128 * 128, (nr + 127) // 128 * 128
     ard, kind = hasattr(c64, "w"), getattr(c64, "kind", 0)
-    nl, nscr = (d if ard else 1), 3
+    nl = d if ard else 1
     rng = np.random.default_rng(nr + m)
     sf2, s2 = float(c64.sf2), float(c64.sn2)
 
@@ -109,7 +115,9 @@ def run(exe, tmp, name, rows):
     inner = np.zeros((ld, ld), dtype=bool)
     inner[:m, :m] = True
     Pfull, Bfull = sym[0], sym[1]
-    acc = P + scr[0] + scr[1] + scr[2]
+    acc = P
+    for a in scr:
+        acc = acc + a
     small = dict(
         gram=rel(Pacc[lower128], acc[lower128]) / ULP4,
         form_b=rel(Bm[lower128], (np.eye(ld) + P / s2)[lower128]) / ULP4,
@@ -125,11 +133,11 @@ def run(exe, tmp, name, rows):
     finite = bool(np.all(np.isfinite(row)) and np.all(np.isfinite(puf[:, 3:])) and np.all(np.isfinite(puu))
                   and np.all(np.isfinite(mean)) and np.all(np.isfinite(var)) and np.all(np.isfinite(q[:m])))
     ok = et < 1e-13 and er < 1e-13 and same_f and offset_kept and zeros and finite and max(small.values()) <= 1.0
-    print("sparse %-22s rows %-3d m %-3d ld %-3d  against numpy: trace sums %.2e  results %.2e  small passes %.2f (of their "
+    print("sparse %-22s rows %-3d m %-3d ld %-3d nscr %d  against numpy: trace sums %.2e  results %.2e  small passes %.2f (of their "
           "tolerances; worst: %s)  padding zero %s  offset kept %s  %s"
-          % (name, nr, m, ld, et, er, max(small.values()), max(small, key=small.get), zeros, offset_kept, "ok" if ok else "BAD"))
+          % (name, nr, m, ld, nscr, et, er, max(small.values()), max(small, key=small.get), zeros, offset_kept, "ok" if ok else "BAD"))
     return ok
 
 
 if __name__ == "__main__":
-    sys.exit(host_check.main("sparse_host_check", CASES, run))
+    sys.exit(host_check.main("sparse_host_check", CASES + CASES_MPAD384, run))

@@ -2,9 +2,10 @@
 the rank-one part (the first pass) and over the square (Z, Z, 2 G_uu) (the last pass), k_trace_cross_z_finish behind each --
 the text kernels.hip includes -- in a lock-step host emulation (tools/sparse_z_host_check.cpp) built with
 -fsanitize=address,undefined.  The chunk is the LAST chunk of a case of tests/truth_sparse_z.py (ragged: 44, 128, 1 or 200 rows
-of a padded block), its weight matrices random; rows beyond the chunk and columns beyond M are NaN in every G entry, label and
-rank-one weight the kernel must mask, and the points are heap blocks of exactly nr x d and m x d doubles: a missing mask shows
-as NaN, an access beyond a buffer as a sanitizer report.  Compared:
+of a padded block; 800 rows in ranges of 5, 5 and 4 tiles and 1300 rows in ranges of 5, 5, 5, 5 and 2, as chunk_rows 0 -- the
+library's 16384 -- gives them), its weight matrices random; rows beyond the chunk and columns beyond M are NaN in every G
+entry, label and rank-one weight the kernel must mask, and the points are heap blocks of exactly nr x d and m x d doubles: a
+missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  Compared:
   bits     the partial blocks of both passes, the running sums after each and the result against the program's plain double
            loop in the same summation order: identical; the pinned copy identical to the device result
   numpy    the result against the formula in numpy on the same inputs: 1e-13 of max_j,c s_c sum |w H (x - z)|
@@ -24,12 +25,16 @@ import host_check  # noqa: E402  (also puts the repository root and tests/ on th
 CASES = (("se_n300_m65_d3", None, 1, 1), ("se_n256_m128_d3", None, 2, 2), ("matern32_n300_m65", 1, 1, 2),
          ("matern52_n300_m65_d3", None, 2, 1), ("ard_n300_m130_d17", None, 1, 2), ("matern52_ard_n257_m64", None, 2, 1),
          ("se_n1300_m200", 200, 2, 4))
+# the same at the default chunk (chunk_rows 0): 14 row tiles in ranges of 5, 5 and 4; 22 in 5, 5, 5, 5 and 2, six column tiles
+CASES_DEFAULT_CHUNK = (("se_n800_m65_d3_c0", None, 3, 1), ("se_n1300_m260_c0", None, 5, 3))
+CHUNK_DEFAULT = 16384                   # what chunk_rows = 0 stands for in the library (include/cugp.h: cugp_sparse_create)
 
 
 def run(exe, tmp, name, rows, ranges_uf, ranges_uu):
     import truth_sparse_z as tz
     X, y, Z, cov, chunk = tz.inputs(name)
     c64 = cov.fp64()
+    chunk = chunk if chunk > 0 else CHUNK_DEFAULT
     r0 = (len(y) - 1) // chunk * chunk
     Xr, yr = X[r0:], y[r0:]
     if rows is not None:
@@ -78,11 +83,11 @@ def run(exe, tmp, name, rows, ranges_uf, ranges_uu):
             + (np.abs(Wu) * np.abs(Z[:, c][None, :] - Z[:, c][:, None])).sum(1)
     en = float(np.max(np.abs(got[-md:].reshape(m, d) - want)) / np.max(mag * sc[None, :]))
     ok = same and pinned and finite and en < 1e-13 and (n_uf, n_uu) == (ranges_uf, ranges_uu)
-    print("sparse-z %-22s rows %-3d m %-3d d %-2d ranges %d / %d  plain loop: %s  pinned copy: %s  against numpy %.2e  finite %s  %s"
+    print("sparse-z %-22s rows %-4d m %-3d d %-2d ranges %d / %d  plain loop: %s  pinned copy: %s  against numpy %.2e  finite %s  %s"
           % (name, nr, m, d, n_uf, n_uu, "same bits" if same else "DIFFERENT", "same bits" if pinned else "DIFFERENT", en,
              finite, "ok" if ok else "BAD"))
     return ok
 
 
 if __name__ == "__main__":
-    sys.exit(host_check.main("sparse_z_host_check", CASES, run))
+    sys.exit(host_check.main("sparse_z_host_check", CASES + CASES_DEFAULT_CHUNK, run))
