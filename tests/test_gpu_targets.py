@@ -8,7 +8,10 @@ Accuracy is held to fp64 rounding against the extended-precision truth of tests/
 with F, F_MATERN, F_ARD and F_SOLVE as they stand in tests/truth.py, the yardstick from the family's own fp64 evaluator
 run per target and summed in target order, and the case list pinned on the CPU by tests/test_truth_targets_cpu.py -- never
 from the GPU.  Every figure is printed before it is asserted ("ACC <case> <quantity> err noise floor ratio"; run with -s).
-Everything else is bit equality: independence of the targets from each other, determinism, the existing single-target
+The same bound holds beyond one 64-row test tile (test_wide_accuracy), on handles padded beyond their rows
+(test_padded_handle) and, with truth_append.F_APPEND, on a handle that cugp_append has grown.
+Everything else is bit equality: independence of the targets from each other and of the test points from each other, the
+scratch of cugp_predict_targets growing, shrinking and running without a variance, determinism, the existing single-target
 results of a handle that has seen targets, staleness against fresh handles, the optimiser against the same loop driven
 from Python.  One process, one device; nothing outside the tree is read.
 """
@@ -20,6 +23,7 @@ import pytest
 import accuracy
 import golden_jobs
 import truth
+import truth_append as ta
 import truth_targets as tt
 from accuracy import Report
 from conftest import synth
@@ -37,9 +41,11 @@ def gp_mod():
     return gp
 
 
-def make(gp_mod, family, X, y, hp, overlap=None, Y=None):
-    """A handle of the family with data, hyper-parameters and (Y [m][n] target-major) targets set."""
-    g = gp_mod.Covsum(X.shape[0], X.shape[1], ard=family == "ard", kernel=family if family.startswith("matern") else "se")
+def make(gp_mod, family, X, y, hp, overlap=None, Y=None, npad_min=0):
+    """A handle of the family with data, hyper-parameters and (Y [m][n] target-major) targets set; npad_min: room for
+    that many rows (identity-padded beyond n)."""
+    g = gp_mod.Covsum(X.shape[0], X.shape[1], npad_min=npad_min, ard=family == "ard",
+                      kernel=family if family.startswith("matern") else "se")
     if overlap is not None:
         g.set_overlap(overlap)
     g.set_data(X, y)
@@ -98,6 +104,87 @@ def test_accuracy(gp_mod, oracle, family, name, m):
     rep.check()
 
 
+@extended
+@pytest.mark.parametrize("case", tt.WIDE_CASES, ids=[tt.wide_id(c) for c in tt.WIDE_CASES])
+def test_wide_accuracy(gp_mod, oracle, case):
+    """Prediction beyond one 64-row test tile (k_targets_mean's grid is m64 * nt64 * split, ntpad = nt rounded to 128):
+      se n65 m=3 nt=129                nt > n; nt64 = 3, one row into the third test tile; ntpad 256
+      se n257_d3 m=129 nt=257          m64 = 3 x nt64 = 5; ntpad 384; mpad 256
+      se n515_d33 m=65 nt=129, subset  m64 = 2 x nt64 = 3 x split = 2 (npad 640: k chunks [0, 512) and [512, 640)): all
+                                       three factors of the grid above 1.  The yardstick is that of targets (0, 1, 63, 64)
+                                       and only the means are held -- every column of them (tests/truth_targets.py)
+      ard n257_d3 m=5 nt=200           a ragged second 128-row tile on an ARD handle
+      matern52 n300_d17 m=17 nt=200    two feature chunks through k_cross at width
+    The last test point but one is a training row.  LL, the gradient and LL_t do not depend on nt and are held again."""
+    family, name, m, nt, subset = case
+    c = tt.wide_case(oracle, *case)
+    cov = c["cov"]
+    rep = Report("%s/%s/m%d/nt%d" % (family, name, m, nt), cov)
+    g = make(gp_mod, family, c["X"], c["y"], cov.hp, Y=c["Y"])
+    ll, gr, each, A, mean, var = everything(g, c["Xt"])
+    assert mean.shape == (nt, m) and var.shape == (nt,) and each.shape == (m,)
+    tt.hold(rep, c, ll, gr, mean, each)
+    v1 = g.compute_test_means_and_variances(None, None, c["Xt"])[1]
+    assert same_bits([var], [v1])                      # the variance is cugp_predict's, launch for launch
+    g.close()
+    rep.check()
+
+
+@extended
+@pytest.mark.parametrize("name, m, npad_min", [("n257_d3", 17, 640), ("n65", 3, 256)])
+def test_padded_handle(gp_mod, oracle, name, m, npad_min):
+    """A handle with room beyond its rows (npad_min > n): identity-padded tile rows in k_targets_alpha's k ranges and in
+    k_finalize_targets' sums of squares; at npad 640 k_targets_mean's second k chunk [512, 640) is nothing but padding.
+    The 64 test points and the yardstick of the unpadded case, the same bound."""
+    c = tt.case(oracle, "se", name, m)
+    cov = c["cov"]
+    rep = Report("se/%s/m%d/npad%d" % (name, m, npad_min), cov)
+    g = make(gp_mod, "se", c["X"], c["y"], cov.hp, Y=c["Y"], npad_min=npad_min)
+    assert g.capacity == npad_min > len(c["y"])
+    ll, gr, each, A, mean, var = everything(g, c["Xt"])
+    assert A.shape == (len(c["y"]), m) and mean.shape == (len(c["Xt"]), m)
+    tt.hold(rep, c, ll, gr, mean, each)
+    rep.add("alpha", tt.alpha_error(c, A.T), c["solve"]["alpha"], truth.U4, truth.F_SOLVE)
+    assert same_bits([var], [g.compute_test_means_and_variances(None, None, c["Xt"])[1]])
+    g.close()
+    rep.check()
+
+
+@extended
+def test_targets_on_a_grown_handle(gp_mod, oracle):
+    """cugp_set_targets on a handle that cugp_append has grown: 127 rows with room for 257, evaluated, (2, 128) appended as
+    in truth_append.CASES, then 5 targets over all 257 rows.  LL, the gradient, LL_t and the means against the case on
+    all rows with truth_append.F_APPEND in place of F (the factor and the inverse are the bordered ones; the stand-in is
+    pinned by tests/test_truth_targets_cpu.py), alpha with F_SOLVE.  A further append is then refused -- targets have no
+    new rows -- and leaves every result as it was, bit for bit."""
+    (family, name, n0, chunks), m = tt.GROWN_CASE
+    c = tt.case(oracle, family, name, m)
+    X, y, Xt, cov = c["X"], c["y"], c["Xt"], c["cov"]
+    rep = Report("grown/%s/%s/m%d" % (family, name, m), cov)
+    g = gp_mod.Covsum(n0, X.shape[1], npad_min=len(y))
+    g.set_loghyperparam(cov.hp)
+    g.set_data(X[:n0], y[:n0])
+    g.loglik_grad()
+    at = n0
+    for k in chunks:
+        g.append(X[at: at + k], y[at: at + k])
+        at += k
+    assert g.n == at == len(y) and g.num_targets == 0
+    g.set_targets(c["Y"].T)
+    out = everything(g, Xt)
+    ll, gr, each, A, mean, var = out
+    tt.hold(rep, c, ll, gr, mean, each, F=ta.F_APPEND[family])
+    rep.add("alpha", tt.alpha_error(c, A.T), c["solve"]["alpha"], truth.U4, ta.F_SOLVE)
+    assert same_bits([var], [g.compute_test_means_and_variances(None, None, Xt)[1]])
+    assert g.capacity >= len(y) + 1                    # (room is not what refuses the next row)
+    with pytest.raises(capi.CugpError, match="targets"):
+        g.append(X[0], y[0])
+    assert g.n == len(y)
+    assert same_bits(everything(g, Xt), out)
+    g.close()
+    rep.check()
+
+
 # ------------------------------------------------------------------ 2. one target
 @extended
 @pytest.mark.parametrize("family, name", [("se", "n257_d3"), ("ard", "n257_d3"), ("matern52", "n65")])
@@ -152,19 +239,30 @@ def test_n3200_against_the_single_target_path(gp_mod):
 
 # ------------------------------------------------------------------ 4. independence and determinism
 def test_targets_do_not_see_each_other_and_bits_repeat(gp_mod):
-    X, y, Xt, hp = truth.live_inputs("n257_d3")
-    Y = tt.targets(y, 17)
+    """At 129 test points (three 64-row test tiles) and up to 129 targets (m64 = 1, 2, 3 on either side of 64 and 128):
+    a target's LL_t, alpha and means carry the same bits whatever other targets stand beside it and wherever it stands."""
+    X, y, _, hp = truth.live_inputs("n257_d3")
+    Xw = truth.wide_points(X, 257, truth.LIVE_CASES["n257_d3"][3])
+    Xt = np.ascontiguousarray(Xw[:129])
+    Y = tt.targets(y, 129)
     g = make(gp_mod, "se", X, y, hp, Y=Y[:3])
     base = everything(g, Xt)
 
     def column(out, t):
         return out[2][t], out[3][:, t], out[4][:, t]
-    for keep in ([1], [2, 0, 1], [2, 1], list(range(17)), [16, 3, 1, 0]):
+    for keep in ([1], [2, 0, 1], [2, 1], list(range(17)), [16, 3, 1, 0], list(range(64)), list(range(65)),
+                 [128, 2, 1, 0] + list(range(3, 127)), list(range(129))):
         g.set_targets(Y[keep].T)
+        assert g.num_targets == len(keep)
         out = everything(g, Xt)
         for pos, t in enumerate(keep):
             if t < 3:
-                assert same_bits(column(out, pos), column(base, t)), (keep, t)
+                assert same_bits(column(out, pos), column(base, t)), (len(keep), t)
+    # 129 targets are set: nt = 64, then 257 (the scratch grows), then 64 and 257 again (it is reused as it stands)
+    p64, p257 = g.predict_targets(Xw[:64]), g.predict_targets(Xw)
+    assert p257[0].shape == (257, 129) and same_bits([p257[0][:129, :3]], [base[4]])
+    assert same_bits(g.predict_targets(Xw[:64]), p64)
+    assert same_bits(g.predict_targets(Xw), p257)
     # ten evaluations at one theta (the targets set again each time: a kept result would repeat trivially)
     g.set_targets(Y[:3].T)
     first = everything(g, Xt)
@@ -178,6 +276,44 @@ def test_targets_do_not_see_each_other_and_bits_repeat(gp_mod):
     assert not np.array_equal(other[2], first[2])
     g.set_loghyperparam(hp)
     assert same_bits(everything(g, Xt), first)
+    g.close()
+
+
+def test_rows_do_not_see_each_other(gp_mod):
+    """n515_d33 (two k chunks), m = 65: a test point's means carry the same bits whether it is predicted among 257 points
+    or in a slice of them that starts on a 128-row tile (Xt[128:257]), inside one (Xt[65:130]), or alone (Xt[256:257]).
+    Every element of the mean matrix is one sum over k per chunk, in tile_nt's order: BK columns of k at a time from the
+    chunk's k0, the MFMA's fixed order inside, whichever lane and 64 x 64 tile the element falls into; the chunks
+    (TARGETS_MEAN_KSTEP wide, a function of npad alone) are added in chunk order.  Neither the tile position nor nt enters."""
+    X, y, _, hp = truth.live_inputs("n515_d33")
+    Xt = truth.wide_points(X, 257, truth.LIVE_CASES["n515_d33"][3])
+    g = make(gp_mod, "se", X, y, hp, Y=tt.targets(y, 65))
+    wide, _ = g.predict_targets(Xt)
+    assert wide.shape == (257, 65) and np.all(np.isfinite(wide))
+    for a, b in ((128, 257), (65, 130), (256, 257)):
+        part, _ = g.predict_targets(Xt[a:b])
+        assert part.shape == (b - a, 65)
+        assert same_bits([part], [wide[a:b]]), (a, b)
+    g.close()
+
+
+def test_var_is_optional(gp_mod):
+    """cugp_predict_targets with var = NULL, first on a fresh handle (it sizes the scratch): CUGP_OK and the means' bits
+    of the call with var, at nt = 200; the handle's cugp_predict returns its earlier bits afterwards."""
+    X, y, _, hp = truth.live_inputs("n257_d3")
+    m, nt = 5, 200
+    Xt = truth.wide_points(X, nt, truth.LIVE_CASES["n257_d3"][3])
+    L = capi.lib()
+    g = make(gp_mod, "se", X, y, hp, Y=tt.targets(y, m))
+    before = g.compute_test_means_and_variances(None, None, Xt)
+    mean0, mean1, var1 = np.full((m, nt), np.nan), np.full((m, nt), np.nan), np.full(nt, np.nan)
+    assert L.cugp_predict_targets(g.handle, capi.ptr(Xt), nt, capi.ptr(mean0), None) == capi.CUGP_OK
+    assert L.cugp_predict_targets(g.handle, capi.ptr(Xt), nt, capi.ptr(mean1), capi.ptr(var1)) == capi.CUGP_OK
+    assert np.all(np.isfinite(mean0)) and same_bits([mean0], [mean1])
+    assert same_bits([var1], [before[1]])
+    assert L.cugp_predict_targets(g.handle, capi.ptr(Xt), nt, capi.ptr(mean1), None) == capi.CUGP_OK
+    assert same_bits([mean0], [mean1])
+    assert same_bits(g.compute_test_means_and_variances(None, None, Xt), before)
     g.close()
 
 

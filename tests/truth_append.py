@@ -59,8 +59,9 @@ def plan(n, k):
     return out
 
 
-def standin_append(cov, X, y, Xt, n0, chunks, mutate=None):
-    """-> (ll, grad, mean, var, alpha, K^-1) of all n0 + sum(chunks) rows, by bordering in fp64.
+def standin_append(cov, X, y, Xt, n0, chunks, mutate=None, factors=False):
+    """-> (ll, grad, mean, var, alpha, K^-1) of all n0 + sum(chunks) rows, by bordering in fp64; factors=True: -> (T, K^-1,
+    log|K|) as the bordering leaves them (tests/truth_targets.py: targets set on a grown handle).
     mutate "drop_qtq": K^-1's leading block is not updated; "plus_q": Q = +C^-1 V -- the CPU suite shows that either
     leaves the bound by orders of magnitude."""
     import scipy.linalg as sl
@@ -94,6 +95,8 @@ def standin_append(cov, X, y, Xt, n0, chunks, mutate=None):
             logdet = logdet + 2 * np.log(np.diag(Cf)).sum()
         n += k
     assert n == len(y)
+    if factors:
+        return T, Ki, logdet
     ll = -0.5 * (z @ z + logdet + n * truth.LL_CONST)
     Kf, terms = c.train(X)
     W = Ki - np.outer(a, a)
