@@ -107,6 +107,13 @@ SIGNATURES = {
     "cugp_sparse_bound_grad_z": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
     "cugp_sparse_get_inducing": (C.c_int, [C.c_void_p, _dp]),
     "cugp_sparse_cg_solve_z": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_sparse_set_targets": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_sparse_num_targets": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_sparse_bound_targets": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "cugp_sparse_bound_grad_targets": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
+    "cugp_sparse_bound_grad_z_targets": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp]),
+    "cugp_sparse_predict_targets": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_sparse_cg_solve_targets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, _ip]),
     "cugp_potrf": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_potri": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_chol_and_det": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_int]),

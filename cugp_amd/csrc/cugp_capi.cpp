@@ -2653,6 +2653,17 @@ struct cugp_sparse {
     bool row_z = false;
     double *dzpart = nullptr, *dzacc = nullptr, *dzout = nullptr, *hz = nullptr;   // partial blocks, running sums, result, its pinned copy
     Scratch pred;
+    // p targets over the same rows, hyper-parameters and inducing inputs (cugp_sparse_set_targets)
+    int tg_p = 0, tg_ppad = 0;                               // targets, and their count rounded up to 128 (0: none set)
+    size_t tg_ypad = 0;                                      // the row stride of tg_y: n rounded up to 128
+    double *tg_y = nullptr, *tg_yy = nullptr;                // Y [p][ypad] zero padded as dy, and y_t'y_t
+    double *tg_vec = nullptr;                                // Q, C', Gamma', Beta', Bs: [ppad][mpad] each
+    double *tg_part = nullptr;                               // the slabs' shares of Q: [p][chunk pad / 128][mpad]
+    double *tg_out = nullptr, *tg_hout = nullptr;            // results row [F, g (nh), F_t (p)], device and pinned
+    bool tg_valid = false, tg_pd = false;                    // b and C' hold for (data, Z, theta, targets); ... positive definite
+    bool tg_row_grad = false, tg_row_z = false;
+    std::vector<double> tg_row, tg_gz;                       // [F, g (nh), F_t (p)] and gZ of the last targets evaluation
+    Scratch tg_pred;
 };
 
 namespace {
@@ -2740,6 +2751,7 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = fals
         if ((rc = sp_ensure_z(s))) return rc;
     }
     s->valid = s->pd = false;
+    s->tg_valid = false;                                               // (b and P are about to be rewritten)
     s->row.assign((size_t)1 + s->nh, NAN);
     s->row_grad = want_grad;
     s->row_z = want_z;
@@ -2831,7 +2843,7 @@ int sp_set_theta(cugp_sparse* s, const double* th)
     for (int i = 0; i < s->nh; i++) changed = changed || th[i] != s->theta[i] || std::isnan(th[i]);
     if (!changed) return CUGP_OK;
     s->theta.assign(th, th + s->nh);
-    s->valid = false;
+    s->valid = s->tg_valid = false;
     return CUGP_OK;
 }
 
@@ -2927,9 +2939,11 @@ int cugp_sparse_destroy(cugp_sparse* s)
     if (s->u) (void)cugp_destroy(s->u);
     if (s->b) (void)cugp_destroy(s->b);
     for (double* p : {s->dX, s->dy, s->dyy, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dvec, s->dM[0], s->dM[1], s->dM[2], s->dM[3],
-                      s->dpart, s->dout, s->dzpart, s->dzacc, s->dzout})
+                      s->dpart, s->dout, s->dzpart, s->dzacc, s->dzout, s->tg_y, s->tg_yy, s->tg_vec, s->tg_part, s->tg_out})
         if (p) (void)hipFree(p);
     if (s->hout) (void)hipHostFree(s->hout);
+    if (s->tg_hout) (void)hipHostFree(s->tg_hout);
+    s->tg_pred.release();
     if (s->hz) (void)hipHostFree(s->hz);
     s->pred.release();
     delete s;
@@ -2969,7 +2983,7 @@ int cugp_sparse_set_data(cugp_sparse* s, const double* X, const double* y)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     s->have_data = true;
-    s->valid = false;
+    s->valid = s->tg_valid = false;
     return CUGP_OK;
 }
 
@@ -2980,7 +2994,7 @@ int cugp_sparse_set_inducing(cugp_sparse* s, const double* Z)
     if (const int rc = cugp_set_data(s->u, Z, zero.data())) return rc;
     s->z.assign(Z, Z + (size_t)s->m * s->d);
     s->have_z = true;
-    s->valid = false;
+    s->valid = s->tg_valid = false;
     return CUGP_OK;
 }
 
@@ -3140,6 +3154,339 @@ int cugp_sparse_cg_solve_z(cugp_sparse* s, int budget, double* trace, int trace_
     std::vector<double> v(s->theta), rows((size_t)cap * (nv + 1), NAN);
     v.insert(v.end(), s->z.begin(), s->z.end());
     if ((rc = cugp_cg_minimize_n_iterates(sp_objective_z, s, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals,
+                                          &nrows)))
+        return rc;
+    for (int r = 0; r < nrows; r++) {
+        std::copy(rows.begin() + (size_t)r * (nv + 1), rows.begin() + (size_t)r * (nv + 1) + s->nh, trace + (size_t)r * (s->nh + 1));
+        trace[(size_t)r * (s->nh + 1) + s->nh] = rows[(size_t)r * (nv + 1) + nv];
+    }
+    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
+    bool moved = false;
+    for (size_t i = 0; i < s->z.size() && !moved; i++) moved = v[s->nh + i] != s->z[i];
+    if (moved && (rc = cugp_sparse_set_inducing(s, v.data() + s->nh))) return rc;
+    return sp_set_theta(s, v.data());
+}
+
+// ---- p targets over one set of inducing points (include/cugp.h)
+// Everything that costs O(N M^2) is sp_eval's own launch, once for all targets; the targets enter through Q (one pass over
+// W_c per group of targets), three small triangular products on the M side, the rank-p terms of H and of the chunk's
+// weights, and the final sums.  The evaluation writes the shared factor handle b and P, so it takes the single-target
+// evaluation's validity, as that one takes this one's.
+namespace {
+void sp_free_targets(cugp_sparse* s)
+{
+    for (double** q : {&s->tg_y, &s->tg_yy, &s->tg_vec, &s->tg_part, &s->tg_out}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    if (s->tg_hout) (void)hipHostFree(s->tg_hout);
+    s->tg_hout = nullptr;
+    s->tg_p = s->tg_ppad = 0;
+    s->tg_valid = false;
+}
+
+// the checks every evaluating targets call shares, behind its own argument checks and in front of any device work
+int sp_targets_ready(const cugp_sparse* s, const char* call)
+{
+    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
+    if (s->tg_p <= 0) return tg_invalid(call, "no targets set (cugp_sparse_set_targets)");
+    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
+    return CUGP_OK;
+}
+
+// sp_eval's sibling: F = sum_t F_t, the F_t and (want_grad) the gradient of -F, (want_z) also in Z, at the current
+// hyper-parameters.  The results land in s->tg_row / s->tg_gz: NaN where Kuu or B is not positive definite.  The host waits
+// are sp_eval's two.
+int sp_eval_targets(cugp_sparse* s, bool want_grad, const char* call, bool want_z = false)
+{
+    int rc;
+    if ((rc = sp_targets_ready(s, call))) return rc;
+    if (s->tg_valid && (s->tg_row_grad || !want_grad) && (s->tg_row_z || !want_z)) return CUGP_OK;
+    cugp_gp *u = s->u, *b = s->b;
+    if (want_z) {
+        if ((rc = use_device(u))) return rc;
+        if ((rc = sp_ensure_z(s))) return rc;
+    }
+    const int p = s->tg_p, nrow = 1 + s->nh + p;
+    s->valid = s->pd = false;                                          // (b and P are about to be rewritten)
+    s->tg_valid = s->tg_pd = false;
+    s->tg_row.assign((size_t)nrow, NAN);
+    s->tg_row_grad = want_grad;
+    s->tg_row_z = want_z;
+    if (want_z) s->tg_gz.assign((size_t)s->m * s->d, NAN);
+    std::vector<double> th(s->theta);
+    th[s->nh - 1] = 0.5 * std::log(s->jitter);
+    if ((rc = set_theta(u, th.data()))) return rc;
+    if ((rc = cugp_loglik_grad(u, nullptr, nullptr))) return rc;       // Lu, Lu^-1, Lu^-T
+    if ((rc = use_device(u))) return rc;
+    if ((rc = sp_ensure(s, want_grad))) return rc;
+    if (!std::isfinite(u->last_ll)) { s->tg_valid = true; return CUGP_OK; }   // Kuu is not positive definite: NaN results
+    if (const int pe = prepare_kernels())
+        return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
+    hipStream_t st = u->stream;
+    const int mp = s->mpad, nl = s->nh - 2;
+    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
+    const size_t vec = (size_t)s->tg_ppad * mp;
+    double *Q = s->tg_vec, *Cp = Q + vec, *Gm = Cp + vec, *Bt = Gm + vec, *Bs = Bt + vec;
+    const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
+    CovFn cf;
+    {
+        TuneScope ts(u);
+        if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
+        for (int c = 0; c < chunks; c++) {
+            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
+            sp_chunk_w(s, cf, sh);
+            launch_sparse_gram(s->dW, mp, sh, s->dP, s->dscr, c == 0, st);
+            launch_sparse_wty_targets(s->dW, mp, sh.cpad, s->tg_y + sh.r0, s->tg_ypad, p, s->tg_part, Q, c == 0, st);
+        }
+        launch_sparse_form_b(s->dP, mp, s2, b->dA, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if ((rc = la_factor_inverse(b, true))) return rc;                  // LB, LB^-1, LB^-T, B^-1
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    launch_predict_gemm(Q, b->dT, Cp, mp, s->tg_ppad / TILE, b->nt, st);       // C' = Q LB^-T: row t = LB^-1 q_t
+    const size_t nb_uf = sp_blocks_uf(s), nb_uu = (size_t)(mp / 64) * (mp / 64);
+    double *part_uf = s->dpart, *part_uu = want_grad ? s->dpart + (size_t)(nl + 1) * nb_uf : nullptr;
+    if (want_grad) {
+        launch_targets_alpha(Cp, b->dU, Gm, mp, p, st);                // Gamma' = C' LB^-1: row t = LB^-T c'_t
+        launch_targets_alpha(Gm, u->dU, Bt, mp, p, st);                // Beta' = Gamma' Lu^-1: row t = Lu^-T gamma'_t
+        double *H = s->dM[0], *H2 = s->dM[1], *X1 = s->dM[2], *R = s->dM[3];
+        launch_sparse_h_targets(b->dKinv, s->dP, Gm, Bt, p, s->m, mp, s2, H, H2, Bs, st);
+        launch_targets_alpha(H, u->dU, X1, mp, mp, st);                // H Lu^-1
+        launch_sparse_transpose(X1, R, mp, 1.0 / s2, st);              // R = Lu^-T H / s2
+        launch_targets_alpha(H2, u->dU, X1, mp, mp, st);               // H2 Lu^-1
+        launch_sparse_transpose(X1, H, mp, 1.0, st);                   // Lu^-T H2
+        launch_targets_alpha(H, u->dU, H2, mp, mp, st);                // 2 G_uu = Lu^-T H2 Lu^-1
+        size_t pofs = 0;
+        for (int c = 0; c < chunks; c++) {
+            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
+            if (chunks > 1) sp_chunk_w(s, cf, sh);                     // (one chunk: W is still there)
+            launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
+            launch_sparse_weights_targets(s->dG, sh.cpad, mp, s->tg_y + sh.r0, s->tg_ypad, Bs, p, sh.count, s->m, st);
+            launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG, nullptr,
+                               nullptr, part_uf, nb_uf, pofs, st);     // (the rank-p part is in G already)
+            if (want_z)
+                launch_trace_cross_z(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
+                                     nullptr, nullptr, s->dzpart, s->dzacc, c == 0, false, s->dzout, s->hz, st);
+            pofs += (size_t)(sh.cpad / 64) * (mp / 64);
+        }
+        launch_trace_cross(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, part_uu, nb_uu, 0, st);
+        if (want_z) {
+            for (size_t i = 0; i < (size_t)s->m * s->d; i++) s->hz[i] = NAN;
+            launch_trace_cross_z(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, s->dzpart, s->dzacc, false,
+                                 true, s->dzout, s->hz, st);
+        }
+    }
+    const SparseFinalTargets fin{s->dP, b->dKinv, Cp, Gm, b->dlogdet, s->tg_yy, s->m, mp, b->nt, p, (double)s->n, sf2, s2,
+                                 s->theta[s->nh - 1] * 2};
+    for (int i = 0; i < nrow; i++) s->tg_hout[i] = NAN;
+    launch_sparse_finalize_targets(fin, want_grad ? part_uf : nullptr, nb_uf, part_uu, nb_uu, nl, s->tg_out, s->tg_hout, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
+    s->tg_pd = std::isfinite(s->tg_hout[0]);
+    if (s->tg_pd) {                                                    // (B is not positive definite: NaN results)
+        s->tg_row[0] = s->tg_hout[0];
+        if (want_grad) std::copy(s->tg_hout + 1, s->tg_hout + 1 + s->nh, s->tg_row.begin() + 1);
+        std::copy(s->tg_hout + 1 + s->nh, s->tg_hout + nrow, s->tg_row.begin() + 1 + s->nh);
+        if (want_z) std::copy(s->hz, s->hz + (size_t)s->m * s->d, s->tg_gz.begin());
+    }
+    s->tg_valid = true;
+    return CUGP_OK;
+}
+
+void sp_copy_targets_row(const cugp_sparse* s, double* F, double* g, double* F_each)
+{
+    *F = s->tg_row[0];
+    if (g) std::copy(s->tg_row.begin() + 1, s->tg_row.begin() + 1 + s->nh, g);
+    if (F_each) std::copy(s->tg_row.begin() + 1 + s->nh, s->tg_row.end(), F_each);
+}
+
+// f = -sum_t F_t and its gradient at th (NaN where the evaluation fails)
+void sp_objective_targets(void* ctx, const double* th, int nh, double* f, double* gr)
+{
+    cugp_sparse* s = (cugp_sparse*)ctx;
+    if (sp_set_theta(s, th) == CUGP_OK && sp_eval_targets(s, true, "cugp_sparse_cg_solve_targets") == CUGP_OK) {
+        *f = -1.0 * s->tg_row[0];
+        std::copy(s->tg_row.begin() + 1, s->tg_row.begin() + 1 + nh, gr);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nh, NAN);
+    }
+}
+
+// the same at v = [theta, vec Z]; a Z that differs goes to the handle
+void sp_objective_z_targets(void* ctx, const double* v, int nv, double* f, double* gr)
+{
+    cugp_sparse* s = (cugp_sparse*)ctx;
+    const double* zv = v + s->nh;
+    const size_t md = (size_t)s->m * s->d;
+    bool moved = false;
+    for (size_t i = 0; i < md && !moved; i++) moved = zv[i] != s->z[i] || std::isnan(zv[i]);
+    if ((!moved || cugp_sparse_set_inducing(s, zv) == CUGP_OK) && sp_set_theta(s, v) == CUGP_OK &&
+        sp_eval_targets(s, true, "cugp_sparse_cg_solve_targets", true) == CUGP_OK) {
+        *f = -1.0 * s->tg_row[0];
+        std::copy(s->tg_row.begin() + 1, s->tg_row.begin() + 1 + s->nh, gr);
+        std::copy(s->tg_gz.begin(), s->tg_gz.end(), gr + s->nh);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nv, NAN);
+    }
+}
+}  // namespace
+
+int cugp_sparse_set_targets(cugp_sparse* s, const double* Y, int p)
+{
+    const char* call = "cugp_sparse_set_targets";
+    if (!s || !Y) return tg_invalid(call, "null argument");
+    if (p < 1) return tg_invalid(call, "p must be positive");
+    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data comes first: it supplies X)");
+    int rc;
+    if ((rc = use_device(s->u))) return rc;
+    hipStream_t st = s->u->stream;
+    HIPCHK(hipStreamSynchronize(st));
+    s->tg_valid = false;
+    const int mp = s->mpad, ppad = (p + TILE - 1) / TILE * TILE;
+    const size_t ypad = ((size_t)s->n + TILE - 1) / TILE * TILE, vec = (size_t)ppad * mp, row = (size_t)1 + s->nh + p;
+    if (p != s->tg_p) {
+        sp_free_targets(s);
+        rc = ensure(&s->tg_y, (size_t)p * ypad);
+        if (!rc) rc = ensure(&s->tg_yy, (size_t)p);
+        if (!rc) rc = ensure(&s->tg_vec, 5 * vec);
+        if (!rc) rc = ensure(&s->tg_part, (size_t)p * (sp_chunk_max(s) / TILE) * mp);
+        if (!rc) rc = ensure(&s->tg_out, row);
+        if (!rc && hipHostMalloc((void**)&s->tg_hout, row * sizeof(double), hipHostMallocDefault) != hipSuccess)
+            rc = fail(CUGP_ERR_NOMEM, "cugp_sparse_set_targets: the pinned results row");
+        if (rc) { sp_free_targets(s); return rc; }                    // (all or none: the handle is left without targets)
+        s->tg_ppad = ppad;
+        s->tg_ypad = ypad;
+    }
+    HIPCHK(hipMemsetAsync(s->tg_y, 0, (size_t)p * ypad * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(s->tg_vec, 0, 5 * vec * sizeof(double), st));
+    HIPCHK(hipMemcpy2DAsync(s->tg_y, ypad * sizeof(double), Y, (size_t)s->n * sizeof(double), (size_t)s->n * sizeof(double), p,
+                            hipMemcpyHostToDevice, st));
+    launch_sparse_yy_targets(s->tg_y, ypad, s->n, p, s->tg_yy, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    s->tg_p = p;
+    return CUGP_OK;
+}
+
+int cugp_sparse_num_targets(const cugp_sparse* s, int* p)
+{
+    if (!s || !p) return tg_invalid("cugp_sparse_num_targets", "null argument");
+    *p = s->tg_p;
+    return CUGP_OK;
+}
+
+int cugp_sparse_bound_targets(cugp_sparse* s, double* F, double* F_each)
+{
+    const char* call = "cugp_sparse_bound_targets";
+    if (!s || !F) return tg_invalid(call, "null argument");
+    if (const int rc = sp_eval_targets(s, false, call)) return rc;
+    sp_copy_targets_row(s, F, nullptr, F_each);
+    return CUGP_OK;
+}
+
+int cugp_sparse_bound_grad_targets(cugp_sparse* s, double* F, double* g, int nh, double* F_each)
+{
+    const char* call = "cugp_sparse_bound_grad_targets";
+    if (!s || !F || !g) return tg_invalid(call, "null argument");
+    if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
+    if (const int rc = sp_eval_targets(s, true, call)) return rc;
+    sp_copy_targets_row(s, F, g, F_each);
+    return CUGP_OK;
+}
+
+int cugp_sparse_bound_grad_z_targets(cugp_sparse* s, double* F, double* g, int nh, double* gZ, double* F_each)
+{
+    const char* call = "cugp_sparse_bound_grad_z_targets";
+    if (!s || !F || !g || !gZ) return tg_invalid(call, "null argument");
+    if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
+    if (const int rc = sp_eval_targets(s, true, call, true)) return rc;
+    sp_copy_targets_row(s, F, g, F_each);
+    std::copy(s->tg_gz.begin(), s->tg_gz.end(), gZ);
+    return CUGP_OK;
+}
+
+// Means of every target and (var given) the variance, which no target enters: cugp_sparse_predict's own launches give Ks,
+// Wt, Vt and the variance of a pass; the means are (C' / s2) Vt^T (launch_targets_mean), each pass's rows copied to their
+// place in the target-major result.
+int cugp_sparse_predict_targets(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* var)
+{
+    const char* call = "cugp_sparse_predict_targets";
+    if (!s || !Xt || !mean) return tg_invalid(call, "null argument");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    int rc;
+    if ((rc = sp_eval_targets(s, false, call))) return rc;             // (answers from the last evaluation's state when it holds)
+    const int p = s->tg_p;
+    if (!s->tg_pd) {
+        std::fill(mean, mean + (size_t)p * nt, NAN);
+        if (var) std::fill(var, var + nt, NAN);
+        return CUGP_OK;
+    }
+    cugp_gp *u = s->u, *b = s->b;
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    hipStream_t st = u->stream;
+    const int mp = s->mpad, p64 = (p + 63) / 64 * 64;
+    int pr[2];
+    const int passes = cugp_sparse_predict_plan(s->m, nt, 0, pr);
+    if (passes < 1) return passes;
+    const int cmax = (pr[1] + TILE - 1) / TILE * TILE;
+    const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)cmax * mp, ncs = (size_t)p64 * mp;
+    const size_t npp = (size_t)targets_mean_split(mp) * p64 * cmax, nm = (size_t)p * pr[1];
+    if ((rc = s->tg_pred.grow(nxt + 3 * nks + ncs + npp + nm + (size_t)cmax + nt, st))) return rc;
+    double *dXt = s->tg_pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dCs = dVt + nks, *dPp = dCs + ncs;
+    double *dM = dPp + npp, *dm1 = dM + nm, *dv = dm1 + cmax;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * s->d * sizeof(double), hipMemcpyHostToDevice, st));
+    CovFn cf;
+    if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
+    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
+    const double* Cp = s->tg_vec + (size_t)s->tg_ppad * mp;
+    launch_sparse_scale_targets(Cp, p, p64, s->m, mp, s2, dCs, st);
+    hipError_t e = hipGetLastError();
+    for (int ps = 0; ps < passes && e == hipSuccess; ps++) {
+        (void)cugp_sparse_predict_plan(s->m, nt, ps, pr);
+        const int t0 = pr[0], c = pr[1], cpad = (c + TILE - 1) / TILE * TILE;
+        launch_kcross(u->dX, s->m, s->d, mp, dXt + (size_t)t0 * s->d, c, cpad, cf, dKs, st);
+        launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
+        launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T
+        if (var) launch_sparse_predict_finish(dWt, dVt, Cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, dm1, dv + t0, st);
+        launch_targets_mean(dCs, dVt, dPp, mp, p, c, cpad, dM, st);            // [p][c], packed
+        e = hipGetLastError();
+        if (e == hipSuccess)                                                   // row t of the pass to mean[t * nt + t0 ..]
+            e = hipMemcpy2DAsync(mean + t0, (size_t)nt * sizeof(double), dM, (size_t)c * sizeof(double),
+                                 (size_t)c * sizeof(double), p, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
+    return CUGP_OK;
+}
+
+// cugp_sparse_cg_solve (inducing 0) or cugp_sparse_cg_solve_z (otherwise) on -sum_t F_t: the same loop, record and end point
+int cugp_sparse_cg_solve_targets(cugp_sparse* s, int budget, int inducing, double* trace, int trace_cap, int* nevals)
+{
+    const char* call = "cugp_sparse_cg_solve_targets";
+    if (!s) return tg_invalid(call, "null handle");
+    if (budget <= 0) return tg_invalid(call, "budget must be positive");
+    int rc, nrows = 0;
+    if ((rc = sp_targets_ready(s, call))) return rc;
+    if (!inducing) {
+        std::vector<double> th(s->theta);
+        if ((rc = cugp_cg_minimize_n_iterates(sp_objective_targets, s, th.data(), s->nh, budget, trace, trace_cap, nevals, &nrows)))
+            return rc;
+        if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
+        return sp_set_theta(s, th.data());
+    }
+    if ((rc = use_device(s->u)) || (rc = sp_ensure_z(s))) return rc;
+    const int nv = s->nh + s->m * s->d, cap = trace ? std::max(trace_cap, 0) : 0;
+    std::vector<double> v(s->theta), rows((size_t)cap * (nv + 1), NAN);
+    v.insert(v.end(), s->z.begin(), s->z.end());
+    if ((rc = cugp_cg_minimize_n_iterates(sp_objective_z_targets, s, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals,
                                           &nrows)))
         return rc;
     for (int r = 0; r < nrows; r++) {

@@ -362,6 +362,35 @@ void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t 
 // mean = Vt c' / s2, var = sf2 - |Wt_t|^2 + |Vt_t|^2 + noise per test row (Wt, Vt: [>= nt][mpad])
 void launch_sparse_predict_finish(const double* Wt, const double* Vt, const double* cp, int mpad, int nt, double sf2,
                                   double s2, double noise, double* mean, double* var, hipStream_t s);
+// ---- multi-target regression over one set of inducing points (cugp_sparse_*_targets; sparse_targets_device.h, DESIGN.md
+// section 27): Y [p][ystride] target-major, zero padded as the handle's y; Q, C', Gamma', Beta', Bs [>= p][mpad] ----
+// Q[t] (mpad) = (first ? 0 : Q[t]) + W^T y_t for every target, W read once per group of 8 targets; Y: the chunk's first row
+// of target 0; part: p * (cpad / 128) * mpad doubles, the slabs' shares, added in slab order
+void launch_sparse_wty_targets(const double* W, int mpad, int cpad, const double* Y, size_t ystride, int p, double* part,
+                               double* Q, bool first, hipStream_t s);
+void launch_sparse_yy_targets(const double* Y, size_t ystride, int n, int p, double* out, hipStream_t s);   // out[t] = y_t'y_t
+// H = p (I - B^-1) - sum_t gamma_t gamma_t^T, H2 = H - p P / s2 (full mpad^2, zero beyond m; gamma_t = Gm[t] / s2),
+// Bs[t] = Bt[t] / s2^2
+void launch_sparse_h_targets(const double* Binv, const double* P, const double* Gm, const double* Bt, int p, int m, int mpad,
+                             double s2, double* H, double* H2, double* Bs, hipStream_t s);
+// G ([cpad][mpad], in place) += sum_t y_t Bs[t]^T over its first nr rows and m columns, t ascending
+void launch_sparse_weights_targets(double* G, int cpad, int mpad, const double* Y, size_t ystride, const double* Bs, int p,
+                                   int nr, int m, hipStream_t s);
+// Cs ([rows][mpad], rows = p rounded up to 64) = C' / s2, zero beyond p: the first operand of launch_targets_mean
+void launch_sparse_scale_targets(const double* Cm, int p, int rows, int m, int mpad, double s2, double* Cs, hipStream_t s);
+// what the last launch of a targets evaluation reads beside the trace partials
+struct SparseFinalTargets {
+    const double *P, *Binv;        // ld x ld: their diagonals
+    const double *Cp, *Gm;         // C' and Gamma', [p][ld] (Gm is read for the gradient only)
+    const double *logdet;          // the factor of B: one share sum log L_ii per 128-tile
+    const double *yy;              // y_t'y_t, p of them
+    int m, ld, nt, p;
+    double n, sf2, s2, log_s2;     // N as a double, exp(2 theta_f), exp(2 theta_n), 2 theta_n
+};
+// one workgroup: out / hout [0] F = sum_t F_t, (part_uf given) [1 ..] the nl + 2 components of d(-F) / dtheta,
+// [1 + nl + 2 + t] F_t
+void launch_sparse_finalize_targets(const SparseFinalTargets& f, const double* part_uf, size_t nb_uf, const double* part_uu,
+                                    size_t nb_uu, int nl, double* out, double* hout, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -3067,6 +3067,9 @@ __global__ __launch_bounds__(256, 2) void k_loo_product(const double* __restrict
 // ------------------------------------------------------------------------------------------
 #include "sparse_device.h"
 #include "sparse_z_device.h"
+// p targets over one set of inducing points: k_sparse_wty_targets and its finish, k_sparse_yy_targets, k_sparse_h_targets,
+// k_sparse_weights_targets, k_sparse_scale_targets, k_sparse_finalize_targets (emulable as well)
+#include "sparse_targets_device.h"
 
 // acc[m][n] += sum_{k in [kbeg, kend)} W[k][i0 + ..] W[k][j0 + ..]: the TN sibling of tile_nt -- the contraction index k is
 // the SLOW index of the one row-major operand W ([k][ld]; Ag -> W[0][i0], Bg -> W[0][j0]).  The LDS image, the fragment
@@ -3873,6 +3876,49 @@ void launch_sparse_predict_finish(const double* Wt, const double* Vt, const doub
 {
     hipLaunchKernelGGL(k_sparse_predict_finish, dim3((nt + 3) / 4), dim3(256), 0, s, Wt, Vt, cp, mpad, nt, sf2, s2, noise,
                        mean, var);
+}
+
+// ---- multi-target regression over one set of inducing points ----
+void launch_sparse_wty_targets(const double* W, int mpad, int cpad, const double* Y, size_t ystride, int p, double* part,
+                               double* Q, bool first, hipStream_t s)
+{
+    const int slabs = cpad / TILE, groups = (p + SPT_GROUP - 1) / SPT_GROUP;
+    hipLaunchKernelGGL(k_sparse_wty_targets, dim3((unsigned)((mpad / KT) * slabs) * groups), dim3(256), 0, s, W, mpad, slabs, Y,
+                       ystride, p, part);
+    hipLaunchKernelGGL(k_sparse_wty_targets_finish, dim3((unsigned)p * ((mpad + 255) / 256)), dim3(256), 0, s,
+                       (const double*)part, slabs, mpad, p, Q, first ? 1 : 0);
+}
+
+void launch_sparse_yy_targets(const double* Y, size_t ystride, int n, int p, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_yy_targets, dim3(p), dim3(256), 0, s, Y, ystride, n, out);
+}
+
+void launch_sparse_h_targets(const double* Binv, const double* P, const double* Gm, const double* Bt, int p, int m, int mpad,
+                             double s2, double* H, double* H2, double* Bs, hipStream_t s)
+{
+    const int nb = mpad / KT;
+    hipLaunchKernelGGL(k_sparse_h_targets, dim3(nb * nb), dim3(256), 0, s, Binv, P, Gm, Bt, p, m, mpad, s2, H, H2, Bs);
+}
+
+void launch_sparse_weights_targets(double* G, int cpad, int mpad, const double* Y, size_t ystride, const double* Bs, int p,
+                                   int nr, int m, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_weights_targets, dim3((cpad / KT) * (mpad / KT)), dim3(256), 0, s, G, mpad, Y, ystride, Bs, p,
+                       nr, m);
+}
+
+void launch_sparse_scale_targets(const double* Cm, int p, int rows, int m, int mpad, double s2, double* Cs, hipStream_t s)
+{
+    const size_t total = (size_t)rows * mpad;
+    hipLaunchKernelGGL(k_sparse_scale_targets, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, Cm,
+                       p, rows, m, mpad, s2, Cs);
+}
+
+void launch_sparse_finalize_targets(const SparseFinalTargets& f, const double* part_uf, size_t nb_uf, const double* part_uu,
+                                    size_t nb_uu, int nl, double* out, double* hout, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_finalize_targets, dim3(1), dim3(256), 0, s, f, part_uf, nb_uf, part_uu, nb_uu, nl, out, hout);
 }
 
 void launch_test_gemm_nt(const double* A, const double* B, double* C, int m, int n, int k, hipStream_t s)

@@ -585,6 +585,61 @@ class SparseGP:
             rows += 1
         return tr[:rows]
 
+    # -- multi-target regression: p target vectors over the same X, hyper-parameters and inducing inputs --
+    def set_targets(self, Y):
+        """Y [n, p], one column per target (cugp_sparse_set_targets; handed over target-major).  set_data is still
+        required: it supplies X, and its y is unrelated to the targets."""
+        Y = f64(Y)
+        if Y.ndim != 2 or Y.shape[0] != self.n or Y.shape[1] < 1:
+            raise ValueError("expected Y of shape (%d, p), p >= 1" % self.n)
+        Yt = f64(Y.T)
+        check(capi.lib().cugp_sparse_set_targets(self._h, ptr(Yt), Yt.shape[0]))
+
+    @property
+    def num_targets(self):
+        p = C.c_int()
+        check(capi.lib().cugp_sparse_num_targets(self._h, C.byref(p)))
+        return p.value
+
+    def bound_targets(self):
+        """(F = sum_t F_t, F_t [p]) from one pass over the data (cugp_sparse_bound_targets)."""
+        F, each = C.c_double(), np.empty(self.num_targets)
+        check(capi.lib().cugp_sparse_bound_targets(self._h, C.byref(F), ptr(each)))
+        return F.value, each
+
+    def bound_grad_targets(self):
+        """(F = sum_t F_t, gradient of -F [nh], F_t [p]) (cugp_sparse_bound_grad_targets)."""
+        F, g, each = C.c_double(), np.empty(self.nh), np.empty(self.num_targets)
+        check(capi.lib().cugp_sparse_bound_grad_targets(self._h, C.byref(F), ptr(g), self.nh, ptr(each)))
+        return F.value, g, each
+
+    def bound_grad_z_targets(self):
+        """(F, g [nh], gZ [m, d], F_t [p]): bound_grad_targets and the gradient of -F with respect to the inducing inputs
+        in set_inducing's layout (cugp_sparse_bound_grad_z_targets)."""
+        F, g, gZ, each = C.c_double(), np.empty(self.nh), np.empty((self.m, self.d)), np.empty(self.num_targets)
+        check(capi.lib().cugp_sparse_bound_grad_z_targets(self._h, C.byref(F), ptr(g), self.nh, ptr(gZ), ptr(each)))
+        return F.value, g, gZ, each
+
+    def predict_targets(self, Xtest, with_noise=True):
+        """(mean [p, nt], var [nt]) at the test points (cugp_sparse_predict_targets); the variance is predict's own."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        mean, var = np.empty((self.num_targets, nt)), np.empty(nt)
+        check(capi.lib().cugp_sparse_predict_targets(self._h, ptr(Xt), nt, 1 if with_noise else 0, ptr(mean), ptr(var)))
+        return mean, var
+
+    def cg_solve_targets(self, budget=100, inducing=False):
+        """Conjugate gradients on -sum_t F_t (cugp_sparse_cg_solve_targets); the trace [n_iterates, nh + 1] = (theta, -F)
+        as cg_solve's.  inducing: the inducing inputs are variables too (get_inducing() reads Z back)."""
+        budget = int(budget)
+        tr = np.full((4 * max(budget, 0) + 8, self.nh + 1), np.nan)
+        ne = C.c_int()
+        check(capi.lib().cugp_sparse_cg_solve_targets(self._h, budget, 1 if inducing else 0, ptr(tr), tr.shape[0], C.byref(ne)))
+        rows = 1
+        while rows < min(ne.value, tr.shape[0]) and not np.isnan(tr[rows, 0]):
+            rows += 1
+        return tr[:rows]
+
     def plan(self):
         """The schedule (cugp_sparse_plan): one (row0, rows, rows_padded, split, kstep) per pass over the data."""
         return sparse_plan(self.n, self.m, self.chunk_rows)

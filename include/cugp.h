@@ -389,7 +389,47 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  * data or the inducing inputs are set.  CUGP_ERR_NODEVICE from cugp_sparse_create without a GPU.  A Kuu or B that is not
  * positive definite gives NaN results with CUGP_OK (the header's convention).
  * Not built: gradients with respect to Z of the predictions (the bound's: cugp_sparse_bound_grad_z); data sharded across GPUs (A A' and A y are sums over rows: one all-reduce); FITC;
- * multi-target; a C++ mirror in cugp_amd/host/. */
+ * a C++ mirror in cugp_amd/host/.
+ *
+ * ---- multi-target regression over one set of inducing points (the sparse sibling of cugp_set_targets; GPflow's SGPR takes
+ *      Y [N, R]).  p targets y_1 .. y_p share the rows X, the hyper-parameters, the inducing inputs Z and the jitter; the
+ *      objective is F = sum_t F_t, F_t the bound above for y_t.  Everything that costs O(N M^2) -- W_c = k(X_c, Z) Lu^-T,
+ *      P = sum_c W_c'W_c, B = I + P / s2, its factor and inverse, the weight product, both trace passes -- does not depend on
+ *      y and runs ONCE for all targets.  With Q = [q_1 .. q_p], q_t = sum_c W_c'y_t,c, C' = LB^-1 Q, Gamma' = LB^-T C',
+ *      Beta' = Lu^-T Gamma' (one column per target):
+ *        F_t = ((((-N/2 log 2 pi - sum log LB_ii) - N/2 log s2) - y_t'y_t / (2 s2)) + c'_t'c'_t / (2 s2^2)) - (N sf2 - tr P) / (2 s2)
+ *        F = sum_t F_t, summed in target order
+ *        H = p (I - B^-1) - sum_t gamma'_t gamma'_t' / s2^2,  H2 = H - p P / s2,  R = Lu^-T H / s2,  2 G_uu = Lu^-T H2 Lu^-1
+ *        G_c' = W_c R' + sum_t y_t,c (beta'_t / s2^2)'   per chunk: the rank-one part becomes rank p
+ *        g_c = -(S_uf,c + S_uu,c / 2),  g_f = -(2 (S_uf,nl + S_uu,nl / 2) - p N sf2 / s2)
+ *        g_n = -(((p sum_i (1 - [B^-1]_ii) - p N) + (((sum_t y_t'y_t - sum_t c'_t'c'_t / s2) + p (N sf2 - tr P)) / s2)) - sum_t gamma'_t'gamma'_t / s2^2)
+ *        gZ: the pass of cugp_sparse_bound_grad_z over the same G_c and 2 G_uu
+ *        mean_t = Vt c'_t / s2, one row per target; the variance does not depend on y
+ *      (S_uf, S_uu: the trace sums of the rectangle and of the square, as for one target).  Every sum has a fixed order, over
+ *      the targets always ascending: equal inputs give equal bits, and F_t and mean_t of a target do not depend on how many
+ *      targets there are or where it stands.
+ * cugp_sparse_set_targets        : Y [p][n] target-major, host; kept on the device.  cugp_sparse_set_data is still required: it
+ *                                  supplies X, and its y is unrelated to the targets.  Targets persist until replaced; a
+ *                                  second call may change p.  p has no cap other than memory (CUGP_ERR_NOMEM: the handle is
+ *                                  left without targets).
+ * cugp_sparse_num_targets        : *p <- the number of targets, 0 before cugp_sparse_set_targets
+ * cugp_sparse_bound_targets      : *F <- sum_t F_t, F_each (may be NULL) <- the p values F_t
+ * cugp_sparse_bound_grad_targets : also g <- the nh components of the gradient of -F.  cugp_sparse_bound_grad_z_targets:
+ *                                  also gZ [m][d] <- the gradient of -F with respect to the inducing inputs.
+ * cugp_sparse_predict_targets    : mean [p][nt] target-major and var [nt] (may be NULL) at nt test points, in
+ *                                  cugp_sparse_predict_plan's passes; var has the bits of cugp_sparse_predict at the same
+ *                                  theta, Z and data: it reads nothing of y.
+ * cugp_sparse_cg_solve_targets   : cugp_sparse_cg_solve (inducing == 0) or cugp_sparse_cg_solve_z (inducing != 0) on f = -F of
+ *                                  the targets: the same loop, trace and end point.
+ *      The single-target calls are untouched, in bits and in launches.  A targets evaluation writes the shared factor of B, so
+ *      it makes the single-target results stale and the reverse: each is evaluated again when next asked for, with the same
+ *      bits.  cugp_sparse_set_loghyper, _set_inducing, _set_data and _set_targets make the targets' results stale.
+ *      Refusals, all CUGP_ERR_INVALID with the call's name in cugp_last_error before any device work: a NULL handle, Y or F;
+ *      p < 1; cugp_sparse_set_targets before cugp_sparse_set_data; any targets call before cugp_sparse_set_targets or
+ *      cugp_sparse_set_inducing; an nh that is not the handle's; nt <= 0; budget <= 0; a NULL Xt, mean, g or gZ where one is
+ *      required.  A Kuu or B that is not positive definite gives NaN results with CUGP_OK.
+ *      Not built for the targets: per-target hyper-parameters; leave-one-out over targets; reusing B between a single-target
+ *      and a targets evaluation at equal theta. */
 #define CUGP_SPARSE_MAX_M 32768
 typedef struct cugp_sparse cugp_sparse;
 int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, cugp_sparse **out);
@@ -409,6 +449,14 @@ int cugp_sparse_predict_plan(int m, int nt, int pass, int out[2]);
 int cugp_sparse_bound_grad_z(cugp_sparse *sp, double *F, double *g /* nh */, int nh, double *gZ /* [m][d] */);
 int cugp_sparse_get_inducing(const cugp_sparse *sp, double *Z /* [m][d] */);
 int cugp_sparse_cg_solve_z(cugp_sparse *sp, int budget, double *trace, int trace_cap, int *nevals);
+int cugp_sparse_set_targets(cugp_sparse *sp, const double *Y /* [p][n], target-major, host */, int p);
+int cugp_sparse_num_targets(const cugp_sparse *sp, int *p);          /* 0 before set_targets */
+int cugp_sparse_bound_targets(cugp_sparse *sp, double *F, double *F_each /* p, may be NULL */);
+int cugp_sparse_bound_grad_targets(cugp_sparse *sp, double *F, double *g /* nh */, int nh, double *F_each);
+int cugp_sparse_bound_grad_z_targets(cugp_sparse *sp, double *F, double *g, int nh, double *gZ /* [m][d] */, double *F_each);
+int cugp_sparse_predict_targets(cugp_sparse *sp, const double *Xt, int nt, int with_noise,
+                                double *mean /* [p][nt] */, double *var /* nt, may be NULL */);
+int cugp_sparse_cg_solve_targets(cugp_sparse *sp, int budget, int inducing, double *trace, int trace_cap, int *nevals);
 
 /* ---- stand-alone dense LA on a caller matrix (common/matrixops.h:5-25) ----
  * cugp_potrf        : get_cholesky            (L lower, upper zeroed)
