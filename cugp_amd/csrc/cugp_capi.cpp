@@ -2628,6 +2628,16 @@ int cugp_potrs_vec(int n, const double* K, const double* y, double* x, int devic
 // the jitter (its own evaluation: Lu, Lu^-1, Lu^-T) and `b`, a factor handle whose A receives B = I + P / s2 and goes the
 // way cugp_potri's does (LB, LB^-1, LB^-T, B^-1).  The N side streams the data in chunks through u's cross-covariance and
 // triangular-product launches on u's stream; the new passes are kernels.h's launch_sparse_* / launch_trace_cross.
+// The results of one side of the model -- the handle's own y, or the targets -- from that side's last evaluation.  Both
+// sides share P and the factor handle b, so evaluating one clears the other's `valid`.
+struct SparseSide {
+    bool valid = false, pd = false;                 // b, c' / C' hold for (data, Z, theta[, targets]); ... and both matrices were positive definite
+    bool row_grad = false, row_z = false;           // the row holds the gradient; gz holds the gradient in Z
+    std::vector<double> row, gz;                    // [F, g (nh)[, F_t (p)]] and gZ [m][d]
+    double *dout = nullptr, *hout = nullptr;        // results row, device and pinned
+    Scratch pred;
+};
+
 struct cugp_sparse {
     int n = 0, m = 0, d = 0, mpad = 0, device = 0, kernel = KERNEL_SE, nh = 3, chunk_rows = 0;
     bool ard = false;
@@ -2637,33 +2647,22 @@ struct cugp_sparse {
     double *dyy = nullptr;                          // y'y
     bool have_data = false, have_z = false;
     std::vector<double> theta;
-    bool valid = false, pd = false;                 // b, cp hold for (data, Z, theta); ... and both matrices were positive definite
-    std::vector<double> row;                        // [F, g (nh)] of the last evaluation
-    bool row_grad = false;
+    SparseSide own, tg;                             // the handle's own y; the targets (cugp_sparse_set_targets)
     // scratch, created on first use
     double *dS = nullptr, *dW = nullptr, *dG = nullptr;      // one chunk: k(X_c, Z), W_c, G_c^T ([chunk pad][mpad])
     double *dP = nullptr, *dscr = nullptr;                   // P and the Gram launch's partial tiles
     double *dvec = nullptr;                                  // q, c', gamma', beta', beta' / s2^2 (mpad each), then the slabs' shares of q
     double *dM[4] = {nullptr, nullptr, nullptr, nullptr};    // H, H2, a product, R (mpad^2 each): the gradient's
     double *dpart = nullptr;                                 // trace partials: the rectangle's, then the square's
-    double *dout = nullptr, *hout = nullptr;                 // results row, device and pinned
     // the gradient with respect to Z (cugp_sparse_bound_grad_z): created on its first use
     std::vector<double> z;                                   // Z as set, [m][d] (the host copy cugp_sparse_get_inducing returns)
-    std::vector<double> gz;                                  // [m][d] of the last evaluation that took it
-    bool row_z = false;
     double *dzpart = nullptr, *dzacc = nullptr, *dzout = nullptr, *hz = nullptr;   // partial blocks, running sums, result, its pinned copy
-    Scratch pred;
     // p targets over the same rows, hyper-parameters and inducing inputs (cugp_sparse_set_targets)
     int tg_p = 0, tg_ppad = 0;                               // targets, and their count rounded up to 128 (0: none set)
     size_t tg_ypad = 0;                                      // the row stride of tg_y: n rounded up to 128
     double *tg_y = nullptr, *tg_yy = nullptr;                // Y [p][ypad] zero padded as dy, and y_t'y_t
     double *tg_vec = nullptr;                                // Q, C', Gamma', Beta', Bs: [ppad][mpad] each
     double *tg_part = nullptr;                               // the slabs' shares of Q: [p][chunk pad / 128][mpad]
-    double *tg_out = nullptr, *tg_hout = nullptr;            // results row [F, g (nh), F_t (p)], device and pinned
-    bool tg_valid = false, tg_pd = false;                    // b and C' hold for (data, Z, theta, targets); ... positive definite
-    bool tg_row_grad = false, tg_row_z = false;
-    std::vector<double> tg_row, tg_gz;                       // [F, g (nh), F_t (p)] and gZ of the last targets evaluation
-    Scratch tg_pred;
 };
 
 namespace {
@@ -2690,9 +2689,9 @@ int sp_ensure(cugp_sparse* s, bool want_grad)
     for (int c = 0; c < chunks; c++) split = std::max(split, sparse_shape(s->n, s->mpad, s->chunk_rows, c).split);
     if ((rc = ensure(&s->dS, cm)) || (rc = ensure(&s->dW, cm)) || (rc = ensure(&s->dP, mm)) ||
         (rc = ensure(&s->dscr, (size_t)split * mm)) ||
-        (rc = ensure(&s->dvec, (size_t)(5 + sp_chunk_max(s) / TILE) * s->mpad)) || (rc = ensure(&s->dout, (size_t)1 + s->nh)))
+        (rc = ensure(&s->dvec, (size_t)(5 + sp_chunk_max(s) / TILE) * s->mpad)) || (rc = ensure(&s->own.dout, (size_t)1 + s->nh)))
         return rc;
-    if (!s->hout) HIPCHK(hipHostMalloc((void**)&s->hout, ((size_t)1 + s->nh) * sizeof(double), hipHostMallocDefault));
+    if (!s->own.hout) HIPCHK(hipHostMalloc((void**)&s->own.hout, ((size_t)1 + s->nh) * sizeof(double), hipHostMallocDefault));
     if (want_grad) {
         if ((rc = ensure(&s->dG, cm))) return rc;
         for (double*& p : s->dM)
@@ -2734,41 +2733,59 @@ void sp_chunk_w(cugp_sparse* s, const CovFn& cf, const SparseShape& c)
     launch_predict_gemm(s->dS, u->dT, s->dW, s->mpad, c.cpad / TILE, u->nt, u->stream);
 }
 
-// The bound (and its gradient) at the current hyper-parameters.  The results land in s->row: NaN where Kuu or B is not
+// the checks every evaluating call shares, behind its own argument checks and in front of any device work
+int sp_ready(const cugp_sparse* s, bool targets, const char* call)
+{
+    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
+    if (targets && s->tg_p <= 0) return tg_invalid(call, "no targets set (cugp_sparse_set_targets)");
+    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
+    return CUGP_OK;
+}
+
+// The bound (and its gradient) of one side at the current hyper-parameters: the handle's own y, or (targets) F = sum_t F_t
+// with the F_t behind the gradient's slots.  The results land in that side's row and gz: NaN where Kuu or B is not
 // positive definite (the header's convention).  Two host waits beyond the inner evaluation's: in front of B's
 // factorisation, which runs on the factor handle's own stream, and at the end.
+// Everything that costs O(N M^2) is the same launch for both sides.  The side decides five steps: how q / Q is summed
+// (one pass over W_c per group of targets), how c' / C' is solved, how gamma', beta' and H are formed (three small
+// triangular products on the M side, the rank-p terms of H), what the chunk's weights get beyond W_c R^T and which yv / bv
+// the trace passes are handed, and which kernel forms the final sums.
 // want_z (with want_grad): the same sequence with the Z pass behind every k_trace_cross, on the weights that launch read
 // -- no launch of the sequence changes, so F and the hyper-parameter components keep their bits -- and no further host wait.
-int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = false)
+int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool want_z = false)
 {
     int rc;
-    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
-    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
-    if (s->valid && (s->row_grad || !want_grad) && (s->row_z || !want_z)) return CUGP_OK;
+    if ((rc = sp_ready(s, targets, call))) return rc;
+    SparseSide &r = targets ? s->tg : s->own, &other = targets ? s->own : s->tg;
+    if (r.valid && (r.row_grad || !want_grad) && (r.row_z || !want_z)) return CUGP_OK;
     cugp_gp *u = s->u, *b = s->b;
     if (want_z) {
         if ((rc = use_device(u))) return rc;
         if ((rc = sp_ensure_z(s))) return rc;
     }
-    s->valid = s->pd = false;
-    s->tg_valid = false;                                               // (b and P are about to be rewritten)
-    s->row.assign((size_t)1 + s->nh, NAN);
-    s->row_grad = want_grad;
-    s->row_z = want_z;
-    if (want_z) s->gz.assign((size_t)s->m * s->d, NAN);
+    const int p = targets ? s->tg_p : 0, nrow = 1 + s->nh + p;
+    r.valid = r.pd = false;
+    other.valid = false;                                               // (b and P are about to be rewritten)
+    r.row.assign((size_t)nrow, NAN);
+    r.row_grad = want_grad;
+    r.row_z = want_z;
+    if (want_z) r.gz.assign((size_t)s->m * s->d, NAN);
     std::vector<double> th(s->theta);
     th[s->nh - 1] = 0.5 * std::log(s->jitter);                        // the noise slot of the inner handle: Kuu = k(Z, Z) + eps I
     if ((rc = set_theta(u, th.data()))) return rc;
     if ((rc = cugp_loglik_grad(u, nullptr, nullptr))) return rc;       // Lu, Lu^-1, Lu^-T
     if ((rc = use_device(u))) return rc;
     if ((rc = sp_ensure(s, want_grad))) return rc;
-    if (!std::isfinite(u->last_ll)) { s->valid = true; return CUGP_OK; }      // Kuu is not positive definite: NaN results
+    if (!std::isfinite(u->last_ll)) { r.valid = true; return CUGP_OK; }       // Kuu is not positive definite: NaN results
     if (const int pe = prepare_kernels())
         return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
     hipStream_t st = u->stream;
     const int mp = s->mpad, nl = s->nh - 2;
     const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    double *q = s->dvec, *cp = q + mp, *gp = cp + mp, *bp = gp + mp, *bsc = bp + mp, *qpart = bsc + mp;
+    // q, c', gamma', beta', beta' / s2^2: one vector each, or one row per target each (Q, C', Gamma', Beta', Bs)
+    const size_t vec = targets ? (size_t)s->tg_ppad * mp : (size_t)mp;
+    double *q = targets ? s->tg_vec : s->dvec, *cp = q + vec, *gp = cp + vec, *bp = gp + vec, *bsc = bp + vec;
+    double* qpart = targets ? s->tg_part : bsc + vec;
     const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
     CovFn cf;
     {
@@ -2778,7 +2795,8 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = fals
             const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
             sp_chunk_w(s, cf, sh);
             launch_sparse_gram(s->dW, mp, sh, s->dP, s->dscr, c == 0, st);
-            launch_sparse_wty(s->dW, mp, sh.cpad, s->dy + sh.r0, qpart, q, c == 0, st);
+            if (targets) launch_sparse_wty_targets(s->dW, mp, sh.cpad, s->tg_y + sh.r0, s->tg_ypad, p, qpart, q, c == 0, st);
+            else launch_sparse_wty(s->dW, mp, sh.cpad, s->dy + sh.r0, qpart, q, c == 0, st);
         }
         launch_sparse_form_b(s->dP, mp, s2, b->dA, st);
         HIPCHK(hipGetLastError());
@@ -2787,14 +2805,21 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = fals
     if ((rc = la_factor_inverse(b, true))) return rc;                  // LB, LB^-1, LB^-T, B^-1 (cugp_potri's route)
     if ((rc = use_device(u))) return rc;
     TuneScope ts(u);
-    launch_trmv_lower(b->dT, mp, mp, q, cp, st);                       // c' = LB^-1 q
+    if (targets) launch_predict_gemm(q, b->dT, cp, mp, s->tg_ppad / TILE, b->nt, st);  // C' = Q LB^-T: row t = LB^-1 q_t
+    else launch_trmv_lower(b->dT, mp, mp, q, cp, st);                  // c' = LB^-1 q
     const size_t nb_uf = sp_blocks_uf(s), nb_uu = (size_t)(mp / 64) * (mp / 64);
     double *part_uf = s->dpart, *part_uu = want_grad ? s->dpart + (size_t)(nl + 1) * nb_uf : nullptr;
     if (want_grad) {
-        launch_trmv_upper(b->dU, mp, mp, cp, gp, st);                  // gamma' = LB^-T c'
-        launch_trmv_upper(u->dU, mp, mp, gp, bp, st);                  // beta' = Lu^-T gamma'
         double *H = s->dM[0], *H2 = s->dM[1], *X1 = s->dM[2], *R = s->dM[3];
-        launch_sparse_h(b->dKinv, s->dP, gp, bp, s->m, mp, s2, H, H2, bsc, st);
+        if (targets) {
+            launch_targets_alpha(cp, b->dU, gp, mp, p, st);            // Gamma' = C' LB^-1: row t = LB^-T c'_t
+            launch_targets_alpha(gp, u->dU, bp, mp, p, st);            // Beta' = Gamma' Lu^-1: row t = Lu^-T gamma'_t
+            launch_sparse_h_targets(b->dKinv, s->dP, gp, bp, p, s->m, mp, s2, H, H2, bsc, st);
+        } else {
+            launch_trmv_upper(b->dU, mp, mp, cp, gp, st);              // gamma' = LB^-T c'
+            launch_trmv_upper(u->dU, mp, mp, gp, bp, st);              // beta' = Lu^-T gamma'
+            launch_sparse_h(b->dKinv, s->dP, gp, bp, s->m, mp, s2, H, H2, bsc, st);
+        }
         launch_targets_alpha(H, u->dU, X1, mp, mp, st);                // H Lu^-1
         launch_sparse_transpose(X1, R, mp, 1.0 / s2, st);              // R = Lu^-T H / s2
         launch_targets_alpha(H2, u->dU, X1, mp, mp, st);               // H2 Lu^-1
@@ -2805,11 +2830,14 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = fals
             const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
             if (chunks > 1) sp_chunk_w(s, cf, sh);                     // (one chunk: W is still there)
             launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
-            launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
-                               s->dy + sh.r0, bsc, part_uf, nb_uf, pofs, st);
+            if (targets)                                               // (the rank-p part goes into G: the traces get no yv, bv)
+                launch_sparse_weights_targets(s->dG, sh.cpad, mp, s->tg_y + sh.r0, s->tg_ypad, bsc, p, sh.count, s->m, st);
+            const double *yv = targets ? nullptr : s->dy + sh.r0, *bv = targets ? nullptr : bsc;
+            launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG, yv, bv,
+                               part_uf, nb_uf, pofs, st);
             if (want_z)
-                launch_trace_cross_z(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
-                                     s->dy + sh.r0, bsc, s->dzpart, s->dzacc, c == 0, false, s->dzout, s->hz, st);
+                launch_trace_cross_z(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG, yv, bv,
+                                     s->dzpart, s->dzacc, c == 0, false, s->dzout, s->hz, st);
             pofs += (size_t)(sh.cpad / 64) * (mp / 64);
         }
         launch_trace_cross(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, part_uu, nb_uu, 0, st);
@@ -2819,21 +2847,27 @@ int sp_eval(cugp_sparse* s, bool want_grad, const char* call, bool want_z = fals
                                  true, s->dzout, s->hz, st);
         }
     }
-    const SparseFinal fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->dyy, s->m, mp, b->nt, (double)s->n, sf2, s2,
-                          s->theta[s->nh - 1] * 2};
-    for (int i = 0; i <= s->nh; i++) s->hout[i] = NAN;
-    launch_sparse_finalize(fin, want_grad ? part_uf : nullptr, nb_uf, part_uu, nb_uu, nl, s->dout, s->hout, st);
+    for (int i = 0; i < nrow; i++) r.hout[i] = NAN;
+    const double* puf = want_grad ? part_uf : nullptr;
+    const double ls2 = s->theta[s->nh - 1] * 2;
+    if (targets) {
+        const SparseFinalTargets fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->tg_yy, s->m, mp, b->nt, p, (double)s->n, sf2, s2, ls2};
+        launch_sparse_finalize_targets(fin, puf, nb_uf, part_uu, nb_uu, nl, r.dout, r.hout, st);
+    } else {
+        const SparseFinal fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->dyy, s->m, mp, b->nt, (double)s->n, sf2, s2, ls2};
+        launch_sparse_finalize(fin, puf, nb_uf, part_uu, nb_uu, nl, r.dout, r.hout, st);
+    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
-    s->row[0] = s->hout[0];
-    if (want_grad) std::copy(s->hout + 1, s->hout + 1 + s->nh, s->row.begin() + 1);
-    if (want_z) {
-        std::copy(s->hz, s->hz + (size_t)s->m * s->d, s->gz.begin());
-        if (!std::isfinite(s->row[0])) std::fill(s->gz.begin(), s->gz.end(), NAN);    // (B is not positive definite: NaN results)
+    r.pd = std::isfinite(r.hout[0]);
+    if (r.pd) {                                                        // (B is not positive definite: NaN results)
+        r.row[0] = r.hout[0];
+        if (want_grad) std::copy(r.hout + 1, r.hout + 1 + s->nh, r.row.begin() + 1);
+        std::copy(r.hout + 1 + s->nh, r.hout + nrow, r.row.begin() + 1 + s->nh);      // the F_t
+        if (want_z) std::copy(s->hz, s->hz + (size_t)s->m * s->d, r.gz.begin());
     }
-    s->pd = std::isfinite(s->row[0]);
-    s->valid = true;
+    r.valid = true;
     return CUGP_OK;
 }
 
@@ -2843,21 +2877,100 @@ int sp_set_theta(cugp_sparse* s, const double* th)
     for (int i = 0; i < s->nh; i++) changed = changed || th[i] != s->theta[i] || std::isnan(th[i]);
     if (!changed) return CUGP_OK;
     s->theta.assign(th, th + s->nh);
-    s->valid = s->tg_valid = false;
+    s->own.valid = s->tg.valid = false;
     return CUGP_OK;
 }
 
-// f = -F and its gradient at th (NaN where the evaluation fails)
+// [F, g, F_t] of a side's last evaluation to wherever the caller wants them
+void sp_copy_row(const SparseSide& r, int nh, double* F, double* g, double* F_each)
+{
+    *F = r.row[0];
+    if (g) std::copy(r.row.begin() + 1, r.row.begin() + 1 + nh, g);
+    if (F_each) std::copy(r.row.begin() + 1 + nh, r.row.end(), F_each);
+}
+
+bool sp_z_moved(const cugp_sparse* s, const double* zv)                // (a NaN counts as moved)
+{
+    for (size_t i = 0; i < s->z.size(); i++)
+        if (zv[i] != s->z[i]) return true;
+    return false;
+}
+
+struct SpObjective {                                                    // what the two callbacks below are handed
+    cugp_sparse* s;
+    bool targets;
+    const char* call;
+};
+
+// f = -F of the side and its gradient at th (NaN where the evaluation fails)
 void sp_objective(void* ctx, const double* th, int nh, double* f, double* gr)
 {
-    cugp_sparse* s = (cugp_sparse*)ctx;
-    if (sp_set_theta(s, th) == CUGP_OK && sp_eval(s, true, "cugp_sparse_cg_solve") == CUGP_OK) {
-        *f = -1.0 * s->row[0];
-        std::copy(s->row.begin() + 1, s->row.begin() + 1 + nh, gr);
+    const SpObjective* o = (const SpObjective*)ctx;
+    const SparseSide& r = o->targets ? o->s->tg : o->s->own;
+    if (sp_set_theta(o->s, th) == CUGP_OK && sp_eval(o->s, o->targets, true, o->call) == CUGP_OK) {
+        *f = -1.0 * r.row[0];
+        std::copy(r.row.begin() + 1, r.row.begin() + 1 + nh, gr);
     } else {
         *f = NAN;
         std::fill(gr, gr + nh, NAN);
     }
+}
+
+// the same at v = [theta, vec Z]; a Z that differs goes to the handle
+void sp_objective_z(void* ctx, const double* v, int nv, double* f, double* gr)
+{
+    const SpObjective* o = (const SpObjective*)ctx;
+    cugp_sparse* s = o->s;
+    const SparseSide& r = o->targets ? s->tg : s->own;
+    if ((!sp_z_moved(s, v + s->nh) || cugp_sparse_set_inducing(s, v + s->nh) == CUGP_OK) && sp_set_theta(s, v) == CUGP_OK &&
+        sp_eval(s, o->targets, true, o->call, true) == CUGP_OK) {
+        *f = -1.0 * r.row[0];
+        std::copy(r.row.begin() + 1, r.row.begin() + 1 + s->nh, gr);
+        std::copy(r.gz.begin(), r.gz.end(), gr + s->nh);
+    } else {
+        *f = NAN;
+        std::fill(gr, gr + nv, NAN);
+    }
+}
+
+// Conjugate gradients on -F of a side from the current hyper-parameters: cugp_cg_minimize_n's loop over the handle's nh
+// entries with the iterates as its record, as cugp_cg_solve_loo keeps it; the end point stays set
+int sp_cg_theta(cugp_sparse* s, SpObjective* o, int budget, double* trace, int trace_cap, int* nevals)
+{
+    int rc, nrows = 0;
+    std::vector<double> th(s->theta);
+    if ((rc = cugp_cg_minimize_n_iterates(sp_objective, o, th.data(), s->nh, budget, trace, trace_cap, nevals, &nrows))) return rc;
+    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
+    return sp_set_theta(s, th.data());
+}
+
+// the same loop over the nh + m d variables [theta, vec Z]; the record keeps [theta, f] of the iterates
+int sp_cg_theta_z(cugp_sparse* s, SpObjective* o, int budget, double* trace, int trace_cap, int* nevals)
+{
+    int rc, nrows = 0;
+    if ((rc = use_device(s->u)) || (rc = sp_ensure_z(s))) return rc;
+    const int nv = s->nh + s->m * s->d, cap = trace ? std::max(trace_cap, 0) : 0;
+    std::vector<double> v(s->theta), rows((size_t)cap * (nv + 1), NAN);
+    v.insert(v.end(), s->z.begin(), s->z.end());
+    if ((rc = cugp_cg_minimize_n_iterates(sp_objective_z, o, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals, &nrows)))
+        return rc;
+    for (int r = 0; r < nrows; r++) {
+        std::copy(rows.begin() + (size_t)r * (nv + 1), rows.begin() + (size_t)r * (nv + 1) + s->nh, trace + (size_t)r * (s->nh + 1));
+        trace[(size_t)r * (s->nh + 1) + s->nh] = rows[(size_t)r * (nv + 1) + nv];
+    }
+    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
+    if (sp_z_moved(s, v.data() + s->nh) && (rc = cugp_sparse_set_inducing(s, v.data() + s->nh))) return rc;
+    return sp_set_theta(s, v.data());
+}
+
+// the three cg calls: the argument checks, then the driver of the side
+int sp_cg(cugp_sparse* s, bool targets, bool inducing, const char* call, int budget, double* trace, int trace_cap, int* nevals)
+{
+    if (!s) return tg_invalid(call, "null handle");
+    if (budget <= 0) return tg_invalid(call, "budget must be positive");
+    if (const int rc = sp_ready(s, targets, call)) return rc;
+    SpObjective o{s, targets, call};
+    return inducing ? sp_cg_theta_z(s, &o, budget, trace, trace_cap, nevals) : sp_cg_theta(s, &o, budget, trace, trace_cap, nevals);
 }
 }  // namespace
 
@@ -2914,7 +3027,7 @@ int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, dou
     s->jitter = jitter; s->chunk_rows = chunk_rows;
     s->mpad = (m + TILE - 1) / TILE * TILE;
     s->theta.assign(s->nh, 0.0);
-    s->row.assign((size_t)1 + s->nh, NAN);
+    s->own.row.assign((size_t)1 + s->nh, NAN);
     if ((rc = create_handle(m, d, device, 0, s->ard, &s->u, kernel)) || (rc = cugp_create(m, 1, device, &s->b)) ||
         (rc = ensure_factor_bufs(s->b)) || (rc = ensure_inverse_bufs(s->b))) { cugp_sparse_destroy(s); return rc; }
     const size_t ny = ((size_t)n + TILE - 1) / TILE * TILE;
@@ -2939,13 +3052,13 @@ int cugp_sparse_destroy(cugp_sparse* s)
     if (s->u) (void)cugp_destroy(s->u);
     if (s->b) (void)cugp_destroy(s->b);
     for (double* p : {s->dX, s->dy, s->dyy, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dvec, s->dM[0], s->dM[1], s->dM[2], s->dM[3],
-                      s->dpart, s->dout, s->dzpart, s->dzacc, s->dzout, s->tg_y, s->tg_yy, s->tg_vec, s->tg_part, s->tg_out})
+                      s->dpart, s->own.dout, s->dzpart, s->dzacc, s->dzout, s->tg_y, s->tg_yy, s->tg_vec, s->tg_part, s->tg.dout})
         if (p) (void)hipFree(p);
-    if (s->hout) (void)hipHostFree(s->hout);
-    if (s->tg_hout) (void)hipHostFree(s->tg_hout);
-    s->tg_pred.release();
+    for (SparseSide* r : {&s->own, &s->tg}) {
+        if (r->hout) (void)hipHostFree(r->hout);
+        r->pred.release();
+    }
     if (s->hz) (void)hipHostFree(s->hz);
-    s->pred.release();
     delete s;
     return CUGP_OK;
 }
@@ -2983,7 +3096,7 @@ int cugp_sparse_set_data(cugp_sparse* s, const double* X, const double* y)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     s->have_data = true;
-    s->valid = s->tg_valid = false;
+    s->own.valid = s->tg.valid = false;
     return CUGP_OK;
 }
 
@@ -2994,7 +3107,7 @@ int cugp_sparse_set_inducing(cugp_sparse* s, const double* Z)
     if (const int rc = cugp_set_data(s->u, Z, zero.data())) return rc;
     s->z.assign(Z, Z + (size_t)s->m * s->d);
     s->have_z = true;
-    s->valid = s->tg_valid = false;
+    s->own.valid = s->tg.valid = false;
     return CUGP_OK;
 }
 
@@ -3019,8 +3132,8 @@ int cugp_sparse_bound(cugp_sparse* s, double* F)
 {
     const char* call = "cugp_sparse_bound";
     if (!s || !F) return tg_invalid(call, "null argument");
-    if (const int rc = sp_eval(s, false, call)) return rc;
-    *F = s->row[0];
+    if (const int rc = sp_eval(s, false, false, call)) return rc;
+    sp_copy_row(s->own, s->nh, F, nullptr, nullptr);
     return CUGP_OK;
 }
 
@@ -3029,72 +3142,82 @@ int cugp_sparse_bound_grad(cugp_sparse* s, double* F, double* g, int nh)
     const char* call = "cugp_sparse_bound_grad";
     if (!s || !F || !g) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval(s, true, call)) return rc;
-    *F = s->row[0];
-    std::copy(s->row.begin() + 1, s->row.end(), g);
+    if (const int rc = sp_eval(s, false, true, call)) return rc;
+    sp_copy_row(s->own, s->nh, F, g, nullptr);
     return CUGP_OK;
 }
 
-int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* var)
+namespace {
+// The prediction of one side, behind the call's own argument checks.  Per pass of cugp_sparse_predict_plan Ks, Wt and Vt;
+// the variance, which no y enters, by k_sparse_predict_finish.  The handle's own mean comes from that launch too; the
+// targets' means are (C' / s2) Vt^T (launch_targets_mean), each pass's rows copied to their place in the target-major
+// result, and their `var` may be NULL (then the launch is left out).
+int sp_predict(cugp_sparse* s, bool targets, const char* call, const double* Xt, int nt, int with_noise, double* mean, double* var)
 {
-    const char* call = "cugp_sparse_predict";
-    if (!s || !Xt || !mean || !var) return tg_invalid(call, "null argument");
-    if (nt <= 0) return tg_invalid(call, "nt must be positive");
     int rc;
-    if ((rc = sp_eval(s, false, call))) return rc;                     // (answers from the last evaluation's state when it holds)
-    if (!s->pd) {
-        std::fill(mean, mean + nt, NAN);
-        std::fill(var, var + nt, NAN);
+    if ((rc = sp_eval(s, targets, false, call))) return rc;            // (answers from the last evaluation's state when it holds)
+    SparseSide& r = targets ? s->tg : s->own;
+    const int p = targets ? s->tg_p : 1;
+    if (!r.pd) {
+        std::fill(mean, mean + (size_t)p * nt, NAN);
+        if (var) std::fill(var, var + nt, NAN);
         return CUGP_OK;
     }
     cugp_gp *u = s->u, *b = s->b;
     if ((rc = use_device(u))) return rc;
     TuneScope ts(u);
     hipStream_t st = u->stream;
-    const int mp = s->mpad;
+    const int mp = s->mpad, p64 = (p + 63) / 64 * 64;
     int pr[2];                                                         // the passes of cugp_sparse_predict_plan: the first is the largest
     const int passes = cugp_sparse_predict_plan(s->m, nt, 0, pr);
     if (passes < 1) return passes;
     const int cmax = (pr[1] + TILE - 1) / TILE * TILE;
     const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)cmax * mp;
-    if ((rc = s->pred.grow(nxt + 3 * nks + 2 * (size_t)nt, st))) return rc;
-    double *dXt = s->pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dm = dVt + nks, *dv = dm + nt;
+    // the targets' own: C' / s2, launch_targets_mean's partial sums, a pass's means [p][rows]; their dm is one pass's, unread
+    const size_t ncs = targets ? (size_t)p64 * mp : 0, npp = targets ? (size_t)targets_mean_split(mp) * p64 * cmax : 0;
+    const size_t nm = targets ? (size_t)p * pr[1] : 0, ndm = targets ? (size_t)cmax : (size_t)nt;
+    if ((rc = r.pred.grow(nxt + 3 * nks + ncs + npp + nm + ndm + nt, st))) return rc;
+    double *dXt = r.pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dCs = dVt + nks, *dPp = dCs + ncs;
+    double *dM = dPp + npp, *dm = dM + nm, *dv = dm + ndm;
     HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * s->d * sizeof(double), hipMemcpyHostToDevice, st));
     CovFn cf;
     if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
     const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    const double* cp = s->dvec + mp;
-    for (int p = 0; p < passes; p++) {
-        (void)cugp_sparse_predict_plan(s->m, nt, p, pr);
+    const double* cp = targets ? s->tg_vec + (size_t)s->tg_ppad * mp : s->dvec + mp;     // c', or C'
+    if (targets) launch_sparse_scale_targets(cp, p, p64, s->m, mp, s2, dCs, st);
+    hipError_t e = hipGetLastError();
+    for (int ps = 0; ps < passes && e == hipSuccess; ps++) {
+        (void)cugp_sparse_predict_plan(s->m, nt, ps, pr);
         const int t0 = pr[0], c = pr[1], cpad = (c + TILE - 1) / TILE * TILE;
         launch_kcross(u->dX, s->m, s->d, mp, dXt + (size_t)t0 * s->d, c, cpad, cf, dKs, st);
         launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
         launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T
-        launch_sparse_predict_finish(dWt, dVt, cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, dm + t0, dv + t0, st);
+        if (var) launch_sparse_predict_finish(dWt, dVt, cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, targets ? dm : dm + t0, dv + t0, st);
+        if (targets) launch_targets_mean(dCs, dVt, dPp, mp, p, c, cpad, dM, st);       // [p][c], packed
+        e = hipGetLastError();
+        if (e == hipSuccess && targets)                                        // row t of the pass to mean[t * nt + t0 ..]
+            e = hipMemcpy2DAsync(mean + t0, (size_t)nt * sizeof(double), dM, (size_t)c * sizeof(double),
+                                 (size_t)c * sizeof(double), p, hipMemcpyDeviceToHost, st);
     }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !targets) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
     return CUGP_OK;
 }
+}  // namespace
 
-// conjugate gradients on -F from the current hyper-parameters: cugp_cg_minimize_n's loop over the handle's nh entries with
-// the iterates as its record, as cugp_cg_solve_loo keeps it; the end point stays set
+int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* var)
+{
+    const char* call = "cugp_sparse_predict";
+    if (!s || !Xt || !mean || !var) return tg_invalid(call, "null argument");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    return sp_predict(s, false, call, Xt, nt, with_noise, mean, var);
+}
+
 int cugp_sparse_cg_solve(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)
 {
-    const char* call = "cugp_sparse_cg_solve";
-    if (!s) return tg_invalid(call, "null handle");
-    if (budget <= 0) return tg_invalid(call, "budget must be positive");
-    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
-    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
-    int rc, nrows = 0;
-    std::vector<double> th(s->theta);
-    if ((rc = cugp_cg_minimize_n_iterates(sp_objective, s, th.data(), s->nh, budget, trace, trace_cap, nevals, &nrows)))
-        return rc;
-    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
-    return sp_set_theta(s, th.data());
+    return sp_cg(s, false, false, "cugp_sparse_cg_solve", budget, trace, trace_cap, nevals);
 }
 
 // ---- the inducing inputs as variables
@@ -3112,228 +3235,32 @@ int cugp_sparse_bound_grad_z(cugp_sparse* s, double* F, double* g, int nh, doubl
     const char* call = "cugp_sparse_bound_grad_z";
     if (!s || !F || !g || !gZ) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval(s, true, call, true)) return rc;
-    *F = s->row[0];
-    std::copy(s->row.begin() + 1, s->row.end(), g);
-    std::copy(s->gz.begin(), s->gz.end(), gZ);
+    if (const int rc = sp_eval(s, false, true, call, true)) return rc;
+    sp_copy_row(s->own, s->nh, F, g, nullptr);
+    std::copy(s->own.gz.begin(), s->own.gz.end(), gZ);
     return CUGP_OK;
 }
 
-namespace {
-// f = -F and its gradient at v = [theta, vec Z] (NaN where the evaluation fails); a Z that differs goes to the handle
-void sp_objective_z(void* ctx, const double* v, int nv, double* f, double* gr)
-{
-    cugp_sparse* s = (cugp_sparse*)ctx;
-    const double* zv = v + s->nh;
-    const size_t md = (size_t)s->m * s->d;
-    bool moved = false;
-    for (size_t i = 0; i < md && !moved; i++) moved = zv[i] != s->z[i] || std::isnan(zv[i]);
-    if ((!moved || cugp_sparse_set_inducing(s, zv) == CUGP_OK) && sp_set_theta(s, v) == CUGP_OK &&
-        sp_eval(s, true, "cugp_sparse_cg_solve_z", true) == CUGP_OK) {
-        *f = -1.0 * s->row[0];
-        std::copy(s->row.begin() + 1, s->row.begin() + 1 + s->nh, gr);
-        std::copy(s->gz.begin(), s->gz.end(), gr + s->nh);
-    } else {
-        *f = NAN;
-        std::fill(gr, gr + nv, NAN);
-    }
-}
-}  // namespace
-
-// cugp_sparse_cg_solve's loop over the nh + m d variables [theta, vec Z]; the record keeps [theta, f] of the iterates
 int cugp_sparse_cg_solve_z(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)
 {
-    const char* call = "cugp_sparse_cg_solve_z";
-    if (!s) return tg_invalid(call, "null handle");
-    if (budget <= 0) return tg_invalid(call, "budget must be positive");
-    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
-    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
-    int rc, nrows = 0;
-    if ((rc = use_device(s->u)) || (rc = sp_ensure_z(s))) return rc;
-    const int nv = s->nh + s->m * s->d, cap = trace ? std::max(trace_cap, 0) : 0;
-    std::vector<double> v(s->theta), rows((size_t)cap * (nv + 1), NAN);
-    v.insert(v.end(), s->z.begin(), s->z.end());
-    if ((rc = cugp_cg_minimize_n_iterates(sp_objective_z, s, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals,
-                                          &nrows)))
-        return rc;
-    for (int r = 0; r < nrows; r++) {
-        std::copy(rows.begin() + (size_t)r * (nv + 1), rows.begin() + (size_t)r * (nv + 1) + s->nh, trace + (size_t)r * (s->nh + 1));
-        trace[(size_t)r * (s->nh + 1) + s->nh] = rows[(size_t)r * (nv + 1) + nv];
-    }
-    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
-    bool moved = false;
-    for (size_t i = 0; i < s->z.size() && !moved; i++) moved = v[s->nh + i] != s->z[i];
-    if (moved && (rc = cugp_sparse_set_inducing(s, v.data() + s->nh))) return rc;
-    return sp_set_theta(s, v.data());
+    return sp_cg(s, false, true, "cugp_sparse_cg_solve_z", budget, trace, trace_cap, nevals);
 }
 
 // ---- p targets over one set of inducing points (include/cugp.h)
-// Everything that costs O(N M^2) is sp_eval's own launch, once for all targets; the targets enter through Q (one pass over
-// W_c per group of targets), three small triangular products on the M side, the rank-p terms of H and of the chunk's
-// weights, and the final sums.  The evaluation writes the shared factor handle b and P, so it takes the single-target
-// evaluation's validity, as that one takes this one's.
+// The calls below are the single-target ones with sp_eval, sp_predict and sp_cg asked for the targets' side; what is
+// theirs alone is the targets' data.  Either side's evaluation writes the shared factor handle b and P, so it takes the
+// other side's validity.
 namespace {
 void sp_free_targets(cugp_sparse* s)
 {
-    for (double** q : {&s->tg_y, &s->tg_yy, &s->tg_vec, &s->tg_part, &s->tg_out}) {
+    for (double** q : {&s->tg_y, &s->tg_yy, &s->tg_vec, &s->tg_part, &s->tg.dout}) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
-    if (s->tg_hout) (void)hipHostFree(s->tg_hout);
-    s->tg_hout = nullptr;
+    if (s->tg.hout) (void)hipHostFree(s->tg.hout);
+    s->tg.hout = nullptr;
     s->tg_p = s->tg_ppad = 0;
-    s->tg_valid = false;
-}
-
-// the checks every evaluating targets call shares, behind its own argument checks and in front of any device work
-int sp_targets_ready(const cugp_sparse* s, const char* call)
-{
-    if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
-    if (s->tg_p <= 0) return tg_invalid(call, "no targets set (cugp_sparse_set_targets)");
-    if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
-    return CUGP_OK;
-}
-
-// sp_eval's sibling: F = sum_t F_t, the F_t and (want_grad) the gradient of -F, (want_z) also in Z, at the current
-// hyper-parameters.  The results land in s->tg_row / s->tg_gz: NaN where Kuu or B is not positive definite.  The host waits
-// are sp_eval's two.
-int sp_eval_targets(cugp_sparse* s, bool want_grad, const char* call, bool want_z = false)
-{
-    int rc;
-    if ((rc = sp_targets_ready(s, call))) return rc;
-    if (s->tg_valid && (s->tg_row_grad || !want_grad) && (s->tg_row_z || !want_z)) return CUGP_OK;
-    cugp_gp *u = s->u, *b = s->b;
-    if (want_z) {
-        if ((rc = use_device(u))) return rc;
-        if ((rc = sp_ensure_z(s))) return rc;
-    }
-    const int p = s->tg_p, nrow = 1 + s->nh + p;
-    s->valid = s->pd = false;                                          // (b and P are about to be rewritten)
-    s->tg_valid = s->tg_pd = false;
-    s->tg_row.assign((size_t)nrow, NAN);
-    s->tg_row_grad = want_grad;
-    s->tg_row_z = want_z;
-    if (want_z) s->tg_gz.assign((size_t)s->m * s->d, NAN);
-    std::vector<double> th(s->theta);
-    th[s->nh - 1] = 0.5 * std::log(s->jitter);
-    if ((rc = set_theta(u, th.data()))) return rc;
-    if ((rc = cugp_loglik_grad(u, nullptr, nullptr))) return rc;       // Lu, Lu^-1, Lu^-T
-    if ((rc = use_device(u))) return rc;
-    if ((rc = sp_ensure(s, want_grad))) return rc;
-    if (!std::isfinite(u->last_ll)) { s->tg_valid = true; return CUGP_OK; }   // Kuu is not positive definite: NaN results
-    if (const int pe = prepare_kernels())
-        return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
-    hipStream_t st = u->stream;
-    const int mp = s->mpad, nl = s->nh - 2;
-    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    const size_t vec = (size_t)s->tg_ppad * mp;
-    double *Q = s->tg_vec, *Cp = Q + vec, *Gm = Cp + vec, *Bt = Gm + vec, *Bs = Bt + vec;
-    const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
-    CovFn cf;
-    {
-        TuneScope ts(u);
-        if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
-        for (int c = 0; c < chunks; c++) {
-            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
-            sp_chunk_w(s, cf, sh);
-            launch_sparse_gram(s->dW, mp, sh, s->dP, s->dscr, c == 0, st);
-            launch_sparse_wty_targets(s->dW, mp, sh.cpad, s->tg_y + sh.r0, s->tg_ypad, p, s->tg_part, Q, c == 0, st);
-        }
-        launch_sparse_form_b(s->dP, mp, s2, b->dA, st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if ((rc = la_factor_inverse(b, true))) return rc;                  // LB, LB^-1, LB^-T, B^-1
-    if ((rc = use_device(u))) return rc;
-    TuneScope ts(u);
-    launch_predict_gemm(Q, b->dT, Cp, mp, s->tg_ppad / TILE, b->nt, st);       // C' = Q LB^-T: row t = LB^-1 q_t
-    const size_t nb_uf = sp_blocks_uf(s), nb_uu = (size_t)(mp / 64) * (mp / 64);
-    double *part_uf = s->dpart, *part_uu = want_grad ? s->dpart + (size_t)(nl + 1) * nb_uf : nullptr;
-    if (want_grad) {
-        launch_targets_alpha(Cp, b->dU, Gm, mp, p, st);                // Gamma' = C' LB^-1: row t = LB^-T c'_t
-        launch_targets_alpha(Gm, u->dU, Bt, mp, p, st);                // Beta' = Gamma' Lu^-1: row t = Lu^-T gamma'_t
-        double *H = s->dM[0], *H2 = s->dM[1], *X1 = s->dM[2], *R = s->dM[3];
-        launch_sparse_h_targets(b->dKinv, s->dP, Gm, Bt, p, s->m, mp, s2, H, H2, Bs, st);
-        launch_targets_alpha(H, u->dU, X1, mp, mp, st);                // H Lu^-1
-        launch_sparse_transpose(X1, R, mp, 1.0 / s2, st);              // R = Lu^-T H / s2
-        launch_targets_alpha(H2, u->dU, X1, mp, mp, st);               // H2 Lu^-1
-        launch_sparse_transpose(X1, H, mp, 1.0, st);                   // Lu^-T H2
-        launch_targets_alpha(H, u->dU, H2, mp, mp, st);                // 2 G_uu = Lu^-T H2 Lu^-1
-        size_t pofs = 0;
-        for (int c = 0; c < chunks; c++) {
-            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
-            if (chunks > 1) sp_chunk_w(s, cf, sh);                     // (one chunk: W is still there)
-            launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
-            launch_sparse_weights_targets(s->dG, sh.cpad, mp, s->tg_y + sh.r0, s->tg_ypad, Bs, p, sh.count, s->m, st);
-            launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG, nullptr,
-                               nullptr, part_uf, nb_uf, pofs, st);     // (the rank-p part is in G already)
-            if (want_z)
-                launch_trace_cross_z(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG,
-                                     nullptr, nullptr, s->dzpart, s->dzacc, c == 0, false, s->dzout, s->hz, st);
-            pofs += (size_t)(sh.cpad / 64) * (mp / 64);
-        }
-        launch_trace_cross(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, part_uu, nb_uu, 0, st);
-        if (want_z) {
-            for (size_t i = 0; i < (size_t)s->m * s->d; i++) s->hz[i] = NAN;
-            launch_trace_cross_z(u->dX, s->m, mp, u->dX, s->m, s->d, mp, cf, H2, nullptr, nullptr, s->dzpart, s->dzacc, false,
-                                 true, s->dzout, s->hz, st);
-        }
-    }
-    const SparseFinalTargets fin{s->dP, b->dKinv, Cp, Gm, b->dlogdet, s->tg_yy, s->m, mp, b->nt, p, (double)s->n, sf2, s2,
-                                 s->theta[s->nh - 1] * 2};
-    for (int i = 0; i < nrow; i++) s->tg_hout[i] = NAN;
-    launch_sparse_finalize_targets(fin, want_grad ? part_uf : nullptr, nb_uf, part_uu, nb_uu, nl, s->tg_out, s->tg_hout, st);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
-    s->tg_pd = std::isfinite(s->tg_hout[0]);
-    if (s->tg_pd) {                                                    // (B is not positive definite: NaN results)
-        s->tg_row[0] = s->tg_hout[0];
-        if (want_grad) std::copy(s->tg_hout + 1, s->tg_hout + 1 + s->nh, s->tg_row.begin() + 1);
-        std::copy(s->tg_hout + 1 + s->nh, s->tg_hout + nrow, s->tg_row.begin() + 1 + s->nh);
-        if (want_z) std::copy(s->hz, s->hz + (size_t)s->m * s->d, s->tg_gz.begin());
-    }
-    s->tg_valid = true;
-    return CUGP_OK;
-}
-
-void sp_copy_targets_row(const cugp_sparse* s, double* F, double* g, double* F_each)
-{
-    *F = s->tg_row[0];
-    if (g) std::copy(s->tg_row.begin() + 1, s->tg_row.begin() + 1 + s->nh, g);
-    if (F_each) std::copy(s->tg_row.begin() + 1 + s->nh, s->tg_row.end(), F_each);
-}
-
-// f = -sum_t F_t and its gradient at th (NaN where the evaluation fails)
-void sp_objective_targets(void* ctx, const double* th, int nh, double* f, double* gr)
-{
-    cugp_sparse* s = (cugp_sparse*)ctx;
-    if (sp_set_theta(s, th) == CUGP_OK && sp_eval_targets(s, true, "cugp_sparse_cg_solve_targets") == CUGP_OK) {
-        *f = -1.0 * s->tg_row[0];
-        std::copy(s->tg_row.begin() + 1, s->tg_row.begin() + 1 + nh, gr);
-    } else {
-        *f = NAN;
-        std::fill(gr, gr + nh, NAN);
-    }
-}
-
-// the same at v = [theta, vec Z]; a Z that differs goes to the handle
-void sp_objective_z_targets(void* ctx, const double* v, int nv, double* f, double* gr)
-{
-    cugp_sparse* s = (cugp_sparse*)ctx;
-    const double* zv = v + s->nh;
-    const size_t md = (size_t)s->m * s->d;
-    bool moved = false;
-    for (size_t i = 0; i < md && !moved; i++) moved = zv[i] != s->z[i] || std::isnan(zv[i]);
-    if ((!moved || cugp_sparse_set_inducing(s, zv) == CUGP_OK) && sp_set_theta(s, v) == CUGP_OK &&
-        sp_eval_targets(s, true, "cugp_sparse_cg_solve_targets", true) == CUGP_OK) {
-        *f = -1.0 * s->tg_row[0];
-        std::copy(s->tg_row.begin() + 1, s->tg_row.begin() + 1 + s->nh, gr);
-        std::copy(s->tg_gz.begin(), s->tg_gz.end(), gr + s->nh);
-    } else {
-        *f = NAN;
-        std::fill(gr, gr + nv, NAN);
-    }
+    s->tg.valid = false;
 }
 }  // namespace
 
@@ -3347,7 +3274,7 @@ int cugp_sparse_set_targets(cugp_sparse* s, const double* Y, int p)
     if ((rc = use_device(s->u))) return rc;
     hipStream_t st = s->u->stream;
     HIPCHK(hipStreamSynchronize(st));
-    s->tg_valid = false;
+    s->tg.valid = false;
     const int mp = s->mpad, ppad = (p + TILE - 1) / TILE * TILE;
     const size_t ypad = ((size_t)s->n + TILE - 1) / TILE * TILE, vec = (size_t)ppad * mp, row = (size_t)1 + s->nh + p;
     if (p != s->tg_p) {
@@ -3356,8 +3283,8 @@ int cugp_sparse_set_targets(cugp_sparse* s, const double* Y, int p)
         if (!rc) rc = ensure(&s->tg_yy, (size_t)p);
         if (!rc) rc = ensure(&s->tg_vec, 5 * vec);
         if (!rc) rc = ensure(&s->tg_part, (size_t)p * (sp_chunk_max(s) / TILE) * mp);
-        if (!rc) rc = ensure(&s->tg_out, row);
-        if (!rc && hipHostMalloc((void**)&s->tg_hout, row * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        if (!rc) rc = ensure(&s->tg.dout, row);
+        if (!rc && hipHostMalloc((void**)&s->tg.hout, row * sizeof(double), hipHostMallocDefault) != hipSuccess)
             rc = fail(CUGP_ERR_NOMEM, "cugp_sparse_set_targets: the pinned results row");
         if (rc) { sp_free_targets(s); return rc; }                    // (all or none: the handle is left without targets)
         s->tg_ppad = ppad;
@@ -3385,8 +3312,8 @@ int cugp_sparse_bound_targets(cugp_sparse* s, double* F, double* F_each)
 {
     const char* call = "cugp_sparse_bound_targets";
     if (!s || !F) return tg_invalid(call, "null argument");
-    if (const int rc = sp_eval_targets(s, false, call)) return rc;
-    sp_copy_targets_row(s, F, nullptr, F_each);
+    if (const int rc = sp_eval(s, true, false, call)) return rc;
+    sp_copy_row(s->tg, s->nh, F, nullptr, F_each);
     return CUGP_OK;
 }
 
@@ -3395,8 +3322,8 @@ int cugp_sparse_bound_grad_targets(cugp_sparse* s, double* F, double* g, int nh,
     const char* call = "cugp_sparse_bound_grad_targets";
     if (!s || !F || !g) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval_targets(s, true, call)) return rc;
-    sp_copy_targets_row(s, F, g, F_each);
+    if (const int rc = sp_eval(s, true, true, call)) return rc;
+    sp_copy_row(s->tg, s->nh, F, g, F_each);
     return CUGP_OK;
 }
 
@@ -3405,99 +3332,25 @@ int cugp_sparse_bound_grad_z_targets(cugp_sparse* s, double* F, double* g, int n
     const char* call = "cugp_sparse_bound_grad_z_targets";
     if (!s || !F || !g || !gZ) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval_targets(s, true, call, true)) return rc;
-    sp_copy_targets_row(s, F, g, F_each);
-    std::copy(s->tg_gz.begin(), s->tg_gz.end(), gZ);
+    if (const int rc = sp_eval(s, true, true, call, true)) return rc;
+    sp_copy_row(s->tg, s->nh, F, g, F_each);
+    std::copy(s->tg.gz.begin(), s->tg.gz.end(), gZ);
     return CUGP_OK;
 }
 
-// Means of every target and (var given) the variance, which no target enters: cugp_sparse_predict's own launches give Ks,
-// Wt, Vt and the variance of a pass; the means are (C' / s2) Vt^T (launch_targets_mean), each pass's rows copied to their
-// place in the target-major result.
+// means of every target [p][nt] and (var given) the variance, which no target enters
 int cugp_sparse_predict_targets(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* var)
 {
     const char* call = "cugp_sparse_predict_targets";
     if (!s || !Xt || !mean) return tg_invalid(call, "null argument");
     if (nt <= 0) return tg_invalid(call, "nt must be positive");
-    int rc;
-    if ((rc = sp_eval_targets(s, false, call))) return rc;             // (answers from the last evaluation's state when it holds)
-    const int p = s->tg_p;
-    if (!s->tg_pd) {
-        std::fill(mean, mean + (size_t)p * nt, NAN);
-        if (var) std::fill(var, var + nt, NAN);
-        return CUGP_OK;
-    }
-    cugp_gp *u = s->u, *b = s->b;
-    if ((rc = use_device(u))) return rc;
-    TuneScope ts(u);
-    hipStream_t st = u->stream;
-    const int mp = s->mpad, p64 = (p + 63) / 64 * 64;
-    int pr[2];
-    const int passes = cugp_sparse_predict_plan(s->m, nt, 0, pr);
-    if (passes < 1) return passes;
-    const int cmax = (pr[1] + TILE - 1) / TILE * TILE;
-    const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)cmax * mp, ncs = (size_t)p64 * mp;
-    const size_t npp = (size_t)targets_mean_split(mp) * p64 * cmax, nm = (size_t)p * pr[1];
-    if ((rc = s->tg_pred.grow(nxt + 3 * nks + ncs + npp + nm + (size_t)cmax + nt, st))) return rc;
-    double *dXt = s->tg_pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dCs = dVt + nks, *dPp = dCs + ncs;
-    double *dM = dPp + npp, *dm1 = dM + nm, *dv = dm1 + cmax;
-    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * s->d * sizeof(double), hipMemcpyHostToDevice, st));
-    CovFn cf;
-    if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
-    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    const double* Cp = s->tg_vec + (size_t)s->tg_ppad * mp;
-    launch_sparse_scale_targets(Cp, p, p64, s->m, mp, s2, dCs, st);
-    hipError_t e = hipGetLastError();
-    for (int ps = 0; ps < passes && e == hipSuccess; ps++) {
-        (void)cugp_sparse_predict_plan(s->m, nt, ps, pr);
-        const int t0 = pr[0], c = pr[1], cpad = (c + TILE - 1) / TILE * TILE;
-        launch_kcross(u->dX, s->m, s->d, mp, dXt + (size_t)t0 * s->d, c, cpad, cf, dKs, st);
-        launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
-        launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T
-        if (var) launch_sparse_predict_finish(dWt, dVt, Cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, dm1, dv + t0, st);
-        launch_targets_mean(dCs, dVt, dPp, mp, p, c, cpad, dM, st);            // [p][c], packed
-        e = hipGetLastError();
-        if (e == hipSuccess)                                                   // row t of the pass to mean[t * nt + t0 ..]
-            e = hipMemcpy2DAsync(mean + t0, (size_t)nt * sizeof(double), dM, (size_t)c * sizeof(double),
-                                 (size_t)c * sizeof(double), p, hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
-    return CUGP_OK;
+    return sp_predict(s, true, call, Xt, nt, with_noise, mean, var);
 }
 
 // cugp_sparse_cg_solve (inducing 0) or cugp_sparse_cg_solve_z (otherwise) on -sum_t F_t: the same loop, record and end point
 int cugp_sparse_cg_solve_targets(cugp_sparse* s, int budget, int inducing, double* trace, int trace_cap, int* nevals)
 {
-    const char* call = "cugp_sparse_cg_solve_targets";
-    if (!s) return tg_invalid(call, "null handle");
-    if (budget <= 0) return tg_invalid(call, "budget must be positive");
-    int rc, nrows = 0;
-    if ((rc = sp_targets_ready(s, call))) return rc;
-    if (!inducing) {
-        std::vector<double> th(s->theta);
-        if ((rc = cugp_cg_minimize_n_iterates(sp_objective_targets, s, th.data(), s->nh, budget, trace, trace_cap, nevals, &nrows)))
-            return rc;
-        if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
-        return sp_set_theta(s, th.data());
-    }
-    if ((rc = use_device(s->u)) || (rc = sp_ensure_z(s))) return rc;
-    const int nv = s->nh + s->m * s->d, cap = trace ? std::max(trace_cap, 0) : 0;
-    std::vector<double> v(s->theta), rows((size_t)cap * (nv + 1), NAN);
-    v.insert(v.end(), s->z.begin(), s->z.end());
-    if ((rc = cugp_cg_minimize_n_iterates(sp_objective_z_targets, s, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals,
-                                          &nrows)))
-        return rc;
-    for (int r = 0; r < nrows; r++) {
-        std::copy(rows.begin() + (size_t)r * (nv + 1), rows.begin() + (size_t)r * (nv + 1) + s->nh, trace + (size_t)r * (s->nh + 1));
-        trace[(size_t)r * (s->nh + 1) + s->nh] = rows[(size_t)r * (nv + 1) + nv];
-    }
-    if (trace && nrows < trace_cap) std::fill(trace + (size_t)nrows * (s->nh + 1), trace + (size_t)(nrows + 1) * (s->nh + 1), NAN);
-    bool moved = false;
-    for (size_t i = 0; i < s->z.size() && !moved; i++) moved = v[s->nh + i] != s->z[i];
-    if (moved && (rc = cugp_sparse_set_inducing(s, v.data() + s->nh))) return rc;
-    return sp_set_theta(s, v.data());
+    return sp_cg(s, true, inducing != 0, "cugp_sparse_cg_solve_targets", budget, trace, trace_cap, nevals);
 }
 
 // ---------------------------------------------------------------- timing

@@ -343,7 +343,14 @@ def test_not_positive_definite_gives_nan_with_ok(gp_mod):
     m, v = s.predict_targets(Xt)
     assert np.isnan(F) and np.all(np.isnan(g)) and np.all(np.isnan(gZ)) and np.all(np.isnan(each)) and each.shape == (p,)
     assert np.all(np.isnan(m)) and np.all(np.isnan(v)) and m.shape == (p, ts.NT)
-    s.set_inducing(Z)                                           # a usable handle afterwards
+    # the handle's own y at the same theta: one rule for both sides, nothing is copied out of a failed evaluation
+    F1, g1 = s.bound_grad()
+    Fz, gz1, gZ1 = s.bound_grad_z()
+    m1, v1 = s.predict(Xt)
+    assert np.isnan(F1) and np.all(np.isnan(g1)) and g1.shape == (len(cov.hp),)
+    assert np.isnan(Fz) and np.all(np.isnan(gz1)) and np.all(np.isnan(gZ1)) and gZ1.shape == Z.shape
+    assert np.all(np.isnan(m1)) and np.all(np.isnan(v1)) and m1.shape == (ts.NT,) and v1.shape == (ts.NT,)
+    s.set_inducing(Z)                                        # a usable handle afterwards
     s2, _ = make(gp_mod, name, p)
     s2.close()
     s.close()
