@@ -114,6 +114,10 @@ SIGNATURES = {
     "cugp_sparse_bound_grad_z_targets": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp]),
     "cugp_sparse_predict_targets": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
     "cugp_sparse_cg_solve_targets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_sparse_predict_cov_plan": (C.c_int, [C.c_int, C.c_int, _ip]),
+    "cugp_sparse_predict_cov": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_sparse_predict_sample": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp]),
+    "cugp_sparse_predict_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "cugp_potrf": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_potri": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_chol_and_det": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_int]),

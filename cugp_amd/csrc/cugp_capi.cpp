@@ -1903,15 +1903,13 @@ int cugp_predict_cov_device(cugp_gp* g, const double* Xt, int nt, int with_noise
     return CUGP_OK;
 }
 
-int cugp_predict_sample(cugp_gp* g, const double* Xt, int nt, int with_noise, double jitter, int nsamples,
-                        const double* normals, double* samples)
+// The draws behind a joint covariance, shared by cugp_predict_sample and cugp_sparse_predict_sample: Sigma (+ jitter I) of
+// nt test points lies in the lower tiles of f, g's factor handle, enqueued on g's stream with the tickets zeroed; dm: the
+// device mean.  C = chol(Sigma) by the library's blocked Cholesky on f's stream, F = normals C^T, samples = mean + F.
+static int sample_tail(cugp_gp* g, cugp_gp* f, const double* dm, int nt, int nsamples, const double* normals, double* samples,
+                       const char* call)
 {
-    if (!g || !Xt || !normals || !samples || nt <= 0 || nsamples <= 0 || !std::isfinite(jitter) || !(jitter >= 0.0))
-        return fail(CUGP_ERR_INVALID, "cugp_predict_sample: bad argument");
-    double* dm = nullptr;
-    cugp_gp* f = nullptr;
-    int rc = predict_cov_device(g, Xt, nt, with_noise != 0, jitter, &dm, &f);
-    if (rc) { (void)hipStreamSynchronize(g->stream); return rc; }
+    int rc;
     const int ntpad = f->npad, nspad = (nsamples + TILE - 1) / TILE * TILE;
     const size_t nz = (size_t)nspad * ntpad;
     if ((rc = g->samp.grow(2 * nz + (size_t)nsamples * nt, g->stream))) return rc;
@@ -1939,10 +1937,22 @@ int cugp_predict_sample(cugp_gp* g, const double* Xt, int nt, int with_noise, do
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(fs);
         (void)hipStreamSynchronize(g->stream);
-        return fail(CUGP_ERR_DEVICE, "cugp_predict_sample", e);
+        return fail(CUGP_ERR_DEVICE, call, e);
     }
     if (g->prof >= 2) drain_kernel_events(g);
     return CUGP_OK;
+}
+
+int cugp_predict_sample(cugp_gp* g, const double* Xt, int nt, int with_noise, double jitter, int nsamples,
+                        const double* normals, double* samples)
+{
+    if (!g || !Xt || !normals || !samples || nt <= 0 || nsamples <= 0 || !std::isfinite(jitter) || !(jitter >= 0.0))
+        return fail(CUGP_ERR_INVALID, "cugp_predict_sample: bad argument");
+    double* dm = nullptr;
+    cugp_gp* f = nullptr;
+    int rc = predict_cov_device(g, Xt, nt, with_noise != 0, jitter, &dm, &f);
+    if (rc) { (void)hipStreamSynchronize(g->stream); return rc; }
+    return sample_tail(g, f, dm, nt, nsamples, normals, samples, "cugp_predict_sample");
 }
 
 // ---------------------------------------------------------------- appending observations
@@ -3213,6 +3223,225 @@ int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise
     if (!s || !Xt || !mean || !var) return tg_invalid(call, "null argument");
     if (nt <= 0) return tg_invalid(call, "nt must be positive");
     return sp_predict(s, false, call, Xt, nt, with_noise, mean, var);
+}
+
+// ---- joint covariance, draws and input gradients of the prediction (include/cugp.h)
+// The product launch of cugp_sparse_predict_cov at the process's current tuning, and where it refuses: pure arithmetic
+int cugp_sparse_predict_cov_plan(int m, int nt, int out[4])
+{
+    const char* call = "cugp_sparse_predict_cov_plan";
+    if (!out) return tg_invalid(call, "out is NULL");
+    if (m < 1 || m > CUGP_SPARSE_MAX_M) return tg_invalid(call, "m < 1 or m beyond CUGP_SPARSE_MAX_M");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    if (nt > CUGP_SPARSE_MAX_M) return tg_invalid(call, "nt beyond CUGP_SPARSE_MAX_M: the padded nt^2 must fit an int in the factor handle's kernels");
+    const int mpad = (m + TILE - 1) / TILE * TILE, ntpad = (nt + TILE - 1) / TILE * TILE;
+    if (nt > sparse_predict_rows(mpad))
+        return tg_invalid(call, "nt beyond the first pass of cugp_sparse_predict_plan: Wt and Vt must be whole");
+    int tn[TUNE_COUNT];                                                // the process defaults: what a handle without keys of its own takes over
+    {
+        std::lock_guard<std::mutex> lk(g_tune_mu);
+        tune_defaults_locked();
+        std::copy(g_tune_default, g_tune_default + TUNE_COUNT, tn);
+    }
+    const int* prev = t_tune;
+    t_tune = tn;
+    const CovShape cs = predict_cov_shape(ntpad, mpad);
+    t_tune = prev;
+    out[0] = ntpad; out[1] = 32 * cs.wm; out[2] = cs.split; out[3] = cs.kstep;
+    return CUGP_OK;
+}
+
+namespace {
+// The shared half of cugp_sparse_predict_cov and cugp_sparse_predict_sample, behind their argument checks: the own side's
+// state (evaluated first when stale), Ks, Wt and Vt of all nt points in ONE pass, the marginal prediction by
+// cugp_sparse_predict's launch (the mean's bits), then into the lower tiles of the factor handle of the inner handle u
+//   Sigma = k(Xt,Xt) (+ s2 I) + jitter I - (Wt Wt^T - Vt Vt^T)
+// by k_sparse_predict_cov (both products on one set of accumulators, split over k as k_predict_cov's) and
+// k_predict_cov_finish as it stands.  The inner handle keeps eps in its noise slot -- an ARD handle's scalars are read from
+// the device, where that slot cannot be replaced for one launch --, so the finish is told there is no noise and s2 rides in
+// its jitter argument: the same single addition to the diagonal, and nothing of eps reaches Sigma.
+// *pd false: Kuu or B is not positive definite (nothing was enqueued; the caller writes NaN).
+int sp_predict_cov_device(cugp_sparse* s, const char* call, const double* Xt, int nt, bool with_noise, double jitter,
+                          double** dmean, cugp_gp** fout, bool* pd)
+{
+    int rc;
+    if ((rc = sp_eval(s, false, false, call))) return rc;
+    *pd = s->own.pd;
+    if (!*pd) return CUGP_OK;
+    cugp_gp *u = s->u, *b = s->b;
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    hipStream_t st = u->stream;
+    const int mp = s->mpad, tiles = (nt + TILE - 1) / TILE, ntpad = tiles * TILE;
+    if ((rc = cov_factor_handle(u, tiles))) return rc;
+    if (!u->cov_ev) HIPCHK(hipEventCreateWithFlags(&u->cov_ev, hipEventDisableTiming));
+    cugp_gp* f = u->cov_f;
+    f->n = nt;                                                         // (a smaller problem in the handle's buffers)
+    f->nt = tiles;
+    f->npad = ntpad;
+    const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)ntpad * mp;
+    if ((rc = s->own.pred.grow(nxt + 3 * nks + 2 * (size_t)ntpad, st))) return rc;
+    double *dXt = s->own.pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dm = dVt + nks, *dv = dm + ntpad;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * s->d * sizeof(double), hipMemcpyHostToDevice, st));
+    CovFn cf;
+    if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
+    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
+    launch_kcross(u->dX, s->m, s->d, mp, dXt, nt, ntpad, cf, dKs, st);
+    launch_predict_gemm(dKs, u->dT, dWt, mp, tiles, u->nt, st);        // Wt = Ks Lu^-T
+    launch_predict_gemm(dWt, b->dT, dVt, mp, tiles, b->nt, st);        // Vt = Wt LB^-T
+    launch_sparse_predict_finish(dWt, dVt, s->dvec + mp, mp, nt, sf2, s2, with_noise ? s2 : 0.0, dm, dv, st);
+    const CovShape cs = predict_cov_shape(ntpad, mp);
+    if ((rc = u->cov_scr.grow((size_t)(cs.split - 1) * ntpad * ntpad, st))) return rc;
+    launch_sparse_predict_cov(dWt, dVt, mp, ntpad, cs, f->dA, u->cov_scr.p, st);
+    cf.h.noise_var = s2;                                               // (by value; unread: with_noise is off, see above)
+    launch_predict_cov_finish(dXt, nt, s->d, ntpad, cf, false, with_noise ? s2 + jitter : jitter, f->dA, u->cov_scr.p,
+                              cs.split - 1, f->dtickets, st);
+    HIPCHK(hipGetLastError());
+    *dmean = dm;
+    *fout = f;
+    return CUGP_OK;
+}
+
+// the refusals the covariance and the draws share, in front of any device work: cugp_sparse_predict_cov_plan's
+int sp_cov_refuse(const cugp_sparse* s, const char* call, int nt)
+{
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    if (nt > CUGP_SPARSE_MAX_M) return tg_invalid(call, "nt beyond CUGP_SPARSE_MAX_M (cugp_sparse_predict_cov_plan)");
+    if (nt > sparse_predict_rows(s->mpad))
+        return tg_invalid(call, "nt beyond the first pass of cugp_sparse_predict_plan (cugp_sparse_predict_cov_plan)");
+    return sp_ready(s, false, call);
+}
+}  // namespace
+
+int cugp_sparse_predict_cov(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* cov)
+{
+    const char* call = "cugp_sparse_predict_cov";
+    if (!s || !Xt || !cov) return tg_invalid(call, "null argument");
+    int rc;
+    if ((rc = sp_cov_refuse(s, call, nt))) return rc;
+    double* dm = nullptr;
+    cugp_gp* f = nullptr;
+    bool pd = false;
+    hipStream_t st = s->u->stream;
+    if ((rc = sp_predict_cov_device(s, call, Xt, nt, with_noise != 0, 0.0, &dm, &f, &pd))) { (void)hipStreamSynchronize(st); return rc; }
+    if (!pd) {
+        if (mean) std::fill(mean, mean + nt, NAN);
+        std::fill(cov, cov + (size_t)nt * nt, NAN);
+        return CUGP_OK;
+    }
+    hipError_t e = hipSuccess;
+    if (mean) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess)
+        e = hipMemcpy2DAsync(cov, (size_t)nt * sizeof(double), f->dA, (size_t)f->npad * sizeof(double),
+                             (size_t)nt * sizeof(double), nt, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
+    // lower triangle, mirrored (cugp_predict_cov's result), in 32 x 32 blocks read along their rows: a column walk over the
+    // whole matrix lands on a few cache sets where nt is a multiple of 512 (measured: 530 ms of 535 at nt = 4096)
+    constexpr int MB = 32;
+    for (int i0 = 0; i0 < nt; i0 += MB)
+        for (int j0 = i0; j0 < nt; j0 += MB)
+            for (int j = j0; j < j0 + MB && j < nt; j++) {
+                const double* lo = cov + (size_t)j * nt;
+                for (int i = i0; i < i0 + MB && i < j; i++) cov[(size_t)i * nt + j] = lo[i];
+            }
+    return CUGP_OK;
+}
+
+int cugp_sparse_predict_sample(cugp_sparse* s, const double* Xt, int nt, int with_noise, double jitter, int nsamples,
+                               const double* normals, double* samples)
+{
+    const char* call = "cugp_sparse_predict_sample";
+    if (!s || !Xt || !normals || !samples) return tg_invalid(call, "null argument");
+    if (nsamples <= 0) return tg_invalid(call, "nsamples must be positive");
+    if (!std::isfinite(jitter) || !(jitter >= 0.0)) return tg_invalid(call, "jitter must be finite and not negative");
+    int rc;
+    if ((rc = sp_cov_refuse(s, call, nt))) return rc;
+    double* dm = nullptr;
+    cugp_gp* f = nullptr;
+    bool pd = false;
+    if ((rc = sp_predict_cov_device(s, call, Xt, nt, with_noise != 0, jitter, &dm, &f, &pd))) {
+        (void)hipStreamSynchronize(s->u->stream);
+        return rc;
+    }
+    if (!pd) {
+        std::fill(samples, samples + (size_t)nsamples * nt, NAN);
+        return CUGP_OK;
+    }
+    return sample_tail(s->u, f, dm, nt, nsamples, normals, samples, call);
+}
+
+// Mean, variance and their gradients with respect to the test inputs, in cugp_sparse_predict's passes.  Per pass Ks, Wt, Vt
+// and the marginal prediction by cugp_sparse_predict's launches, then -- dvar asked for -- T = Vt LB^-1, D = Wt - T
+// (k_sparse_predict_diff, into Vt's place: the prediction has read it) and U = D Lu^-1, both products
+// launch_targets_alpha's; then k_predict_grad and its finish, the exact model's instantiations, with (X, n, npad) :=
+// (Z, m, mpad), a = beta' / s2 for alpha and U for V.  gamma' and beta' are formed here, by the evaluation's own two
+// launches, into this call's scratch whether or not the last evaluation was a gradient one: the same kernels on the same
+// inputs give the bits bound_grad's hold, and bound_grad's are not written.
+int cugp_sparse_predict_grad(cugp_sparse* s, const double* Xt, int nt, int with_noise, double* mean, double* var, double* dmean,
+                             double* dvar)
+{
+    const char* call = "cugp_sparse_predict_grad";
+    if (!s || !Xt) return tg_invalid(call, "null argument");
+    if (!dmean && !dvar) return tg_invalid(call, "dmean and dvar are both NULL");
+    if (nt <= 0) return tg_invalid(call, "nt must be positive");
+    int rc;
+    if ((rc = sp_eval(s, false, false, call))) return rc;
+    const size_t nout = (size_t)nt * s->d;
+    if (!s->own.pd) {
+        if (mean) std::fill(mean, mean + nt, NAN);
+        if (var) std::fill(var, var + nt, NAN);
+        if (dmean) std::fill(dmean, dmean + nout, NAN);
+        if (dvar) std::fill(dvar, dvar + nout, NAN);
+        return CUGP_OK;
+    }
+    cugp_gp *u = s->u, *b = s->b;
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    hipStream_t st = u->stream;
+    const int mp = s->mpad, d = s->d;
+    const bool want_var = dvar != nullptr;
+    int pr[2];
+    const int passes = cugp_sparse_predict_plan(s->m, nt, 0, pr);
+    if (passes < 1) return passes;
+    const int cmax = (pr[1] + TILE - 1) / TILE * TILE;
+    const size_t nxt = (((size_t)nt * d + 15) / 16) * 16, nks = (size_t)cmax * mp, pstride = (size_t)pr[1] * d;
+    const size_t npart = (size_t)predict_grad_tiles(s->m) * 2 * pstride;
+    if ((rc = s->own.pred.grow(nxt + (want_var ? 4 : 3) * nks + npart + 3 * (size_t)mp + 2 * (size_t)nt + 2 * nout, st))) return rc;
+    double *dXt = s->own.pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dT = dVt + nks;
+    double *dP = dT + (want_var ? nks : 0), *dgam = dP + npart, *dbet = dgam + mp, *da = dbet + mp;
+    double *dm = da + mp, *dv = dm + nt, *dgm = dv + nt, *dgv = dgm + nout;
+    HIPCHK(hipMemcpyAsync(dXt, Xt, (size_t)nt * d * sizeof(double), hipMemcpyHostToDevice, st));
+    CovFn cf;
+    if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
+    const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
+    const double* cp = s->dvec + mp;                                   // c'
+    launch_trmv_upper(b->dU, mp, mp, cp, dgam, st);                    // gamma' = LB^-T c'
+    launch_trmv_upper(u->dU, mp, mp, dgam, dbet, st);                  // beta' = Lu^-T gamma'
+    hipError_t e = hipGetLastError();
+    for (int ps = 0; ps < passes && e == hipSuccess; ps++) {
+        (void)cugp_sparse_predict_plan(s->m, nt, ps, pr);
+        const int t0 = pr[0], c = pr[1], cpad = (c + TILE - 1) / TILE * TILE;
+        const double* xt = dXt + (size_t)t0 * d;
+        launch_kcross(u->dX, s->m, d, mp, xt, c, cpad, cf, dKs, st);
+        launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
+        launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T
+        launch_sparse_predict_finish(dWt, dVt, cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, dm + t0, dv + t0, st);
+        if (want_var) launch_targets_alpha(dVt, b->dU, dT, mp, cpad, st);      // T = Vt LB^-1
+        if (want_var || ps == 0)                                               // D = Wt - T over Vt; a = beta' / s2 once
+            launch_sparse_predict_diff(dWt, dT, want_var ? dVt : nullptr, mp, cpad, dbet, s2, s->m, ps == 0 ? da : nullptr, st);
+        if (want_var) launch_targets_alpha(dVt, u->dU, dT, mp, cpad, st);      // U = D Lu^-1
+        launch_predict_grad(u->dX, s->m, d, mp, xt, c, cf, dKs, want_var ? dT : nullptr, da, dP, pstride, st);
+        launch_predict_grad_finish(dP, pstride, s->m, c, d, cf, dgm + (size_t)t0 * d, want_var ? dgv + (size_t)t0 * d : nullptr, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && mean) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dmean) e = hipMemcpyAsync(dmean, dgm, nout * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && dvar) e = hipMemcpyAsync(dvar, dgv, nout * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
+    return CUGP_OK;
 }
 
 int cugp_sparse_cg_solve(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)

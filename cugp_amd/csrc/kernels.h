@@ -362,6 +362,14 @@ void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t 
 // mean = Vt c' / s2, var = sf2 - |Wt_t|^2 + |Vt_t|^2 + noise per test row (Wt, Vt: [>= nt][mpad])
 void launch_sparse_predict_finish(const double* Wt, const double* Vt, const double* cp, int mpad, int nt, double sf2,
                                   double s2, double noise, double* mean, double* var, hipStream_t s);
+// ---- joint covariance and input gradients of the sparse prediction ----
+// partial products Wt Wt^T - Vt Vt^T of the lower tiles in launch_predict_cov's layout and split (c from
+// predict_cov_shape(ntpad, mpad)); launch_predict_cov_finish follows it.  Wt, Vt: [ntpad][ld], zero beyond row nt and column m
+void launch_sparse_predict_cov(const double* Wt, const double* Vt, int ld, int ntpad, const CovShape& c, double* A,
+                               double* scr, hipStream_t s);
+// D = Wt - T over `rows` rows of mpad (D null: left out) and (a given) a[i] = bp[i] / s2 for i < m, 0 up to mpad
+void launch_sparse_predict_diff(const double* Wt, const double* T, double* D, int mpad, int rows, const double* bp, double s2,
+                                int m, double* a, hipStream_t s);
 // ---- multi-target regression over one set of inducing points (cugp_sparse_*_targets; sparse_targets_device.h, DESIGN.md
 // section 27): Y [p][ystride] target-major, zero padded as the handle's y; Q, C', Gamma', Beta', Bs [>= p][mpad] ----
 // Q[t] (mpad) = (first ? 0 : Q[t]) + W^T y_t for every target, W read once per group of 8 targets; Y: the chunk's first row

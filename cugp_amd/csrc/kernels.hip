@@ -3070,6 +3070,38 @@ __global__ __launch_bounds__(256, 2) void k_loo_product(const double* __restrict
 // p targets over one set of inducing points: k_sparse_wty_targets and its finish, k_sparse_yy_targets, k_sparse_h_targets,
 // k_sparse_weights_targets, k_sparse_scale_targets, k_sparse_finalize_targets (emulable as well)
 #include "sparse_targets_device.h"
+// the input gradients of the sparse prediction: k_sparse_predict_diff (emulable as well)
+#include "sparse_predict_device.h"
+
+// ---- joint predictive covariance of the sparse model (cugp_sparse_predict_cov):
+//      cov = k(Xt,Xt) (+ s2 I) - (Wt Wt^T - Vt Vt^T),  Wt = Ks Lu^-T,  Vt = Wt LB^-T ----
+// The sibling of k_predict_cov: the same lower BT-tiles, split of the k range, partial products to P (s = 0) or to scratch
+// slot s - 1, and k_predict_cov_finish behind it unchanged.  One set of accumulators takes both products of a workgroup's
+// k range, + Wt[ti] Wt[tj]^T first, then - Vt[ti] Vt[tj]^T (tile_nt<true> negates the A operand while staging it: the MFMA
+// loop is the same code, no VALU work between the MFMAs is added, and the accumulators are neither stored nor reloaded in
+// between).  Wt and Vt ([ntpad][ld], k_predict_gemm's outputs) are exact zeros in their columns >= m (Ks is zero there and
+// the padding rows of Lu^-1 and LB^-1 are identity: DESIGN.md section 25 says so for W_c) and in their rows >= nt: relied
+// on, not masked.
+template <int WM>
+__global__ __launch_bounds__(256, 2) void k_sparse_predict_cov(const double* __restrict__ Wt, const double* __restrict__ Vt,
+                                                               int ld, int kend, int kstep, int split,
+                                                               double* __restrict__ P, double* __restrict__ scr,
+                                                               size_t pstride, int ldp, unsigned long long* stamp)
+{
+    LaunchStamp stamp_(stamp);
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int BT = 32 * WM;
+    const int tile = blockIdx.x / split, s = blockIdx.x % split;
+    int ti, tj;
+    tri_index(tile, ti, tj);
+    const int k0 = s * kstep, k1 = k0 + kstep < kend ? k0 + kstep : kend;
+    d4 acc[WM][WM];
+    acc_zero(acc);
+    tile_nt<false>(Wt + (size_t)ti * BT * ld, ld, Wt + (size_t)tj * BT * ld, ld, k0, k1, acc, smem);
+    tile_nt<true>(Vt + (size_t)ti * BT * ld, ld, Vt + (size_t)tj * BT * ld, ld, k0, k1, acc, smem);
+    double* C = s == 0 ? P : scr + (size_t)(s - 1) * pstride;
+    tile_store(C + (size_t)ti * BT * ldp + tj * BT, ldp, acc, 1.0);
+}
 
 // acc[m][n] += sum_{k in [kbeg, kend)} W[k][i0 + ..] W[k][j0 + ..]: the TN sibling of tile_nt -- the contraction index k is
 // the SLOW index of the one row-major operand W ([k][ld]; Ag -> W[0][i0], Bg -> W[0][j0]).  The LDS image, the fragment
@@ -3262,7 +3294,7 @@ static void set_big_lds()
     attr((const void*)k_syrk_wide, GEMM_LDS);
     const void* gemm4[] = {(const void*)k_trtri_level<4>, (const void*)k_trtri_border<4>, (const void*)k_lauum<4>,
                            (const void*)k_test_gemm, (const void*)k_predict_cov<4>, (const void*)k_loo_product<4>,
-                           (const void*)k_sparse_gram};
+                           (const void*)k_sparse_gram, (const void*)k_sparse_predict_cov<4>};
     for (const void* f : gemm4) attr(f, GEMM_LDS);
     for (const void* f : {(const void*)k_syrk_wide8, (const void*)k_lauum8, (const void*)k_trtri_border8}) attr(f, GEMM_LDS);
     attr((const void*)k_trtri_diag, TRTRI_LDS);
@@ -3876,6 +3908,28 @@ void launch_sparse_predict_finish(const double* Wt, const double* Vt, const doub
 {
     hipLaunchKernelGGL(k_sparse_predict_finish, dim3((nt + 3) / 4), dim3(256), 0, s, Wt, Vt, cp, mpad, nt, sf2, s2, noise,
                        mean, var);
+}
+
+// ---- joint covariance and input gradients of the sparse prediction ----
+void launch_sparse_predict_cov(const double* Wt, const double* Vt, int ld, int ntpad, const CovShape& c, double* A,
+                               double* scr, hipStream_t s)
+{
+    set_big_lds();
+    const size_t pstride = (size_t)ntpad * ntpad;
+    if (c.wm == 2)
+        CUGP_LAUNCH(k_sparse_predict_cov<2>, dim3(c.tiles * c.split), dim3(256), Geo<2>::LDS, s, Wt, Vt, ld, c.kend, c.kstep,
+                    c.split, A, scr, pstride, ntpad, take_stamp());
+    else
+        CUGP_LAUNCH(k_sparse_predict_cov<4>, dim3(c.tiles * c.split), dim3(256), GEMM_LDS, s, Wt, Vt, ld, c.kend, c.kstep,
+                    c.split, A, scr, pstride, ntpad, take_stamp());
+}
+
+void launch_sparse_predict_diff(const double* Wt, const double* T, double* D, int mpad, int rows, const double* bp, double s2,
+                                int m, double* a, hipStream_t s)
+{
+    const size_t total = std::max<size_t>(D ? (size_t)rows * mpad : 0, (size_t)mpad);
+    hipLaunchKernelGGL(k_sparse_predict_diff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, Wt, T, D, mpad, rows, bp,
+                       s2, m, a);
 }
 
 // ---- multi-target regression over one set of inducing points ----

@@ -640,6 +640,50 @@ class SparseGP:
             rows += 1
         return tr[:rows]
 
+    # -- the joint distribution at test points, draws from it and gradients with respect to the test inputs --
+    def predict_joint(self, Xtest, with_noise=True):
+        """Joint predictive distribution at the test points (cugp_sparse_predict_cov): (mean [nt], cov [nt, nt]), cov =
+        k(Xt,Xt) - Wt Wt^T + Vt Vt^T (+ exp(2 theta_n) I with noise), exactly symmetric; mean has predict's bits."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        m, cov = np.empty(nt), np.empty((nt, nt))
+        check(capi.lib().cugp_sparse_predict_cov(self._h, ptr(Xt), nt, 1 if with_noise else 0, ptr(m), ptr(cov)))
+        return m, cov
+
+    def sample_posterior(self, Xtest, nsamples, with_noise=False, jitter=None, rng=None, normals=None):
+        """Posterior draws at the test points (cugp_sparse_predict_sample): [nsamples, nt] = mean + normals C^T, C the
+        lower Cholesky factor of cov + jitter I (cov as predict_joint).  normals [nsamples, nt] default to
+        rng.standard_normal (rng: a numpy Generator or a seed); jitter None: 1e-8 sf2 for latent draws, 0 with noise."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt, ns = Xt.shape[0], int(nsamples)
+        if normals is None:
+            gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+            normals = gen.standard_normal((ns, nt))
+        Z = f64(normals).reshape(ns, nt)
+        if jitter is None:
+            jitter = 0.0 if with_noise else 1e-8 * float(np.exp(2.0 * self.get_loghyperparam()[-2]))
+        out = np.empty((ns, nt))
+        check(capi.lib().cugp_sparse_predict_sample(self._h, ptr(Xt), nt, 1 if with_noise else 0, float(jitter), ns,
+                                                    ptr(Z), ptr(out)))
+        return out
+
+    def predict_grad(self, Xtest, with_noise=True, want_var_grad=True):
+        """Mean, variance and their gradients with respect to the test inputs (cugp_sparse_predict_grad): (mean [nt],
+        var [nt], dmean [nt, d], dvar [nt, d] or None).  mean / var carry predict's bits for the same with_noise;
+        want_var_grad=False skips U and its two triangular products and returns None for dvar."""
+        Xt = f64(Xtest).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        m, v, dm = np.empty(nt), np.empty(nt), np.empty((nt, self.d))
+        dv = np.empty((nt, self.d)) if want_var_grad else None
+        check(capi.lib().cugp_sparse_predict_grad(self._h, ptr(Xt), nt, 1 if with_noise else 0, ptr(m), ptr(v), ptr(dm),
+                                                  ptr(dv) if want_var_grad else None))
+        return m, v, dm, dv
+
+    def predict_cov_plan(self, nt):
+        """The product launch of predict_joint at nt test points (cugp_sparse_predict_cov_plan), at the process's current
+        tuning: (nt padded to 128, tile edge 64 or 128, k ranges per tile, their length)."""
+        return sparse_predict_cov_plan(self.m, nt)
+
     def plan(self):
         """The schedule (cugp_sparse_plan): one (row0, rows, rows_padded, split, kstep) per pass over the data."""
         return sparse_plan(self.n, self.m, self.chunk_rows)
@@ -675,6 +719,13 @@ def sparse_predict_plan(m, nt):
         i += 1
         if i >= count:
             return passes
+
+
+def sparse_predict_cov_plan(m, nt):
+    """cugp_sparse_predict_cov_plan for nt test points against m inducing inputs: (ntpad, tile edge, split, kstep)."""
+    out = (C.c_int * 4)()
+    check(capi.lib().cugp_sparse_predict_cov_plan(int(m), int(nt), out))
+    return tuple(out)
 
 
 class Comm:

@@ -388,8 +388,9 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  * positive and finite; an nh that is not the handle's; nt <= 0; budget <= 0; an evaluation, prediction or solve before the
  * data or the inducing inputs are set.  CUGP_ERR_NODEVICE from cugp_sparse_create without a GPU.  A Kuu or B that is not
  * positive definite gives NaN results with CUGP_OK (the header's convention).
- * Not built: gradients with respect to Z of the predictions (the bound's: cugp_sparse_bound_grad_z); data sharded across GPUs (A A' and A y are sums over rows: one all-reduce); FITC;
- * a C++ mirror in cugp_amd/host/.
+ * Not built: gradients with respect to Z of the predictions (the bound's: cugp_sparse_bound_grad_z); gradients of the joint
+ * covariance or of draws (cugp_sparse_predict_cov, _sample and _grad are below); data sharded across GPUs (A A' and A y are
+ * sums over rows: one all-reduce); FITC; a C++ mirror in cugp_amd/host/.
  *
  * ---- multi-target regression over one set of inducing points (the sparse sibling of cugp_set_targets; GPflow's SGPR takes
  *      Y [N, R]).  p targets y_1 .. y_p share the rows X, the hyper-parameters, the inducing inputs Z and the jitter; the
@@ -429,7 +430,41 @@ int cugp_cg_solve_loo(cugp_gp *gp, int budget, double *trace, int trace_cap, int
  *      cugp_sparse_set_inducing; an nh that is not the handle's; nt <= 0; budget <= 0; a NULL Xt, mean, g or gZ where one is
  *      required.  A Kuu or B that is not positive definite gives NaN results with CUGP_OK.
  *      Not built for the targets: per-target hyper-parameters; leave-one-out over targets; reusing B between a single-target
- *      and a targets evaluation at equal theta. */
+ *      and a targets evaluation at equal theta; input gradients and draws per target (the joint covariance reads no y, so
+ *      cugp_sparse_predict_cov's cov serves every target already).
+ *
+ * ---- joint predictive covariance, posterior draws and input gradients of the sparse model (the sparse siblings of
+ *      cugp_predict_cov, cugp_predict_sample and cugp_predict_grad).  With Wt = k(Xt,Z) Lu^-T, Vt = Wt LB^-T, s2, sf2 as above,
+ *      c' = LB^-1 q, gamma' = LB^-T c', beta' = Lu^-T gamma':
+ *        mean = cugp_sparse_predict's, bit for bit (the same launch)
+ *        cov  = k(Xt,Xt) - Wt Wt^T + Vt Vt^T   (+ s2 I with noise)     nt x nt row-major, the lower triangle mirrored:
+ *               exactly symmetric; diag(cov) equals cugp_sparse_predict's variance up to rounding, not bit for bit (the
+ *               summation orders differ).  The jitter eps of Kuu enters Lu alone: nothing of it is added to cov.
+ *        samples[s nt + t] = mean[t] + sum_{k <= t} C[t][k] normals[s nt + k],  C = chol(cov + jitter I) by the library's
+ *               blocked Cholesky (cugp_predict_sample's definition and launches); the normals are the caller's; a matrix
+ *               that is not positive definite gives NaN with CUGP_OK.
+ *        dk(x*, z_j) / dx*_c = -G_j (x*_c - z_jc) s_c,  G and s_c per family exactly as stated above cugp_predict_grad;
+ *        a = beta' / s2                       (mean = sum_j a_j k_j -- the same number as Vt c' / s2)
+ *        U = (Wt - Vt LB^-1) Lu^-1            (row t = Lu^-T (I - B^-1) Lu^-1 ks_t;  var_f = sf2 - ks_t^T U_t)
+ *        dmean / dx*_c = -s_c sum_j a_j G_j (x*_c - z_jc)
+ *        dvar  / dx*_c = +2 s_c sum_j U_tj G_j (x*_c - z_jc)
+ *      a replaces the exact model's alpha and U its V; the tile pass and its finish are cugp_predict_grad's own kernels over
+ *      (Z, m).  The noisy and the latent variance have the same gradient.  Sums run in a fixed order without atomics: the
+ *      same bits on every call, and a row's gradient does not depend on nt.
+ * cugp_sparse_predict_cov_plan: pure arithmetic, no device: out = {nt rounded up to 128, the product's tile edge (64 or
+ *      128), the number of k ranges a tile's product is split into, their length} at the process's current tuning.
+ *      CUGP_ERR_INVALID for m < 1, m > CUGP_SPARSE_MAX_M, nt <= 0, nt > CUGP_SPARSE_MAX_M (the padded nt^2 must fit an int
+ *      in the factor handle's kernels, the reason m is capped), an nt beyond the first pass of cugp_sparse_predict_plan(m,
+ *      nt, ..) (Wt and Vt must be whole), a NULL out.
+ * cugp_sparse_predict_cov   : mean [nt] (may be NULL) and cov [nt][nt], host.  cugp_sparse_predict_sample: samples
+ *      [nsamples][nt] from normals [nsamples][nt].  Both refuse exactly where the plan does.
+ * cugp_sparse_predict_grad  : mean and var [nt] (either may be NULL; cugp_sparse_predict's bits for the same with_noise),
+ *      dmean and dvar [nt][d] row-major (either may be NULL, not both; a NULL dvar skips U and its two triangular
+ *      products); the test points go in cugp_sparse_predict_plan's passes: any nt.
+ *      All three reuse the state of the last evaluation of the handle's own y and evaluate first when it is stale (new
+ *      theta, Z or data, or a targets evaluation in between).  A Kuu or B that is not positive definite gives NaN outputs
+ *      with CUGP_OK.  Refusals, all CUGP_ERR_INVALID with the call's name in cugp_last_error before any device work: those
+ *      of cugp_sparse_predict; a jitter that is negative or not finite; nsamples <= 0; dmean and dvar both NULL. */
 #define CUGP_SPARSE_MAX_M 32768
 typedef struct cugp_sparse cugp_sparse;
 int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, cugp_sparse **out);
@@ -457,6 +492,14 @@ int cugp_sparse_bound_grad_z_targets(cugp_sparse *sp, double *F, double *g, int 
 int cugp_sparse_predict_targets(cugp_sparse *sp, const double *Xt, int nt, int with_noise,
                                 double *mean /* [p][nt] */, double *var /* nt, may be NULL */);
 int cugp_sparse_cg_solve_targets(cugp_sparse *sp, int budget, int inducing, double *trace, int trace_cap, int *nevals);
+int cugp_sparse_predict_cov_plan(int m, int nt, int out[4]);
+int cugp_sparse_predict_cov(cugp_sparse *sp, const double *Xt, int nt, int with_noise,
+                            double *mean /* nt, may be NULL */, double *cov /* nt x nt */);
+int cugp_sparse_predict_sample(cugp_sparse *sp, const double *Xt, int nt, int with_noise, double jitter,
+                               int nsamples, const double *normals, double *samples);
+int cugp_sparse_predict_grad(cugp_sparse *sp, const double *Xt, int nt, int with_noise,
+                             double *mean /* nt, may be NULL */, double *var /* nt, may be NULL */,
+                             double *dmean /* [nt][d], may be NULL */, double *dvar /* [nt][d], may be NULL */);
 
 /* ---- stand-alone dense LA on a caller matrix (common/matrixops.h:5-25) ----
  * cugp_potrf        : get_cholesky            (L lower, upper zeroed)

@@ -22,6 +22,7 @@ DYN = {"k_lauum<4>": GEMM4, "k_lauum<2>": GEMM2, "k_trtri_level<4>": GEMM4, "k_t
        "k_syrk_wide": GEMM4, "k_syrk_step": POTF2, "k_potf2": POTF2, "k_trtri_diag": TRTRI,
        "k_predict_cov<4>": GEMM4, "k_predict_cov<2>": GEMM2, "k_targets_alpha": GEMM2, "k_targets_alpha_batched": GEMM2, "k_targets_mean": GEMM2, "k_append_kinv": GEMM2,
        "k_loo_product<4>": GEMM4, "k_loo_product<2>": GEMM2, "k_sparse_gram": GEMM4,
+       "k_sparse_predict_cov<4>": GEMM4, "k_sparse_predict_cov<2>": GEMM2,
        "k_syrk_wide8": GEMM4, "k_lauum8": GEMM4, "k_trtri_border8": GEMM4,
        "k_syrk_wide_rest": GEMM2, "k_lauum_rest": GEMM2, "k_trtri_border_rest": GEMM2}
 
