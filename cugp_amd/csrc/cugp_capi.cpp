@@ -2638,14 +2638,28 @@ int cugp_potrs_vec(int n, const double* K, const double* y, double* x, int devic
 // the jitter (its own evaluation: Lu, Lu^-1, Lu^-T) and `b`, a factor handle whose A receives B = I + P / s2 and goes the
 // way cugp_potri's does (LB, LB^-1, LB^-T, B^-1).  The N side streams the data in chunks through u's cross-covariance and
 // triangular-product launches on u's stream; the new passes are kernels.h's launch_sparse_* / launch_trace_cross.
-// The results of one side of the model -- the handle's own y, or the targets -- from that side's last evaluation.  Both
-// sides share P and the factor handle b, so evaluating one clears the other's `valid`.
+// One side of the model: a set of p label vectors over the handle's rows -- the handle's own y (p = 1 from creation on), or
+// the targets (cugp_sparse_set_targets) -- with everything that depends on them and the results of
+// that side's last evaluation.  Both sides share P and the factor handle b, so evaluating one clears the other's `valid`.
 struct SparseSide {
-    bool valid = false, pd = false;                 // b, c' / C' hold for (data, Z, theta[, targets]); ... and both matrices were positive definite
+    // The route of three steps: the three small solves (true: launch_trmv_lower / _upper on one vector; false: products on
+    // the tile over the rows of a matrix), the rank-p term of the weights (true: yv, bv in k_trace_cross's registers;
+    // false: k_sparse_weights_targets into G first) and the mean of a prediction (true: k_sparse_predict_finish's; false:
+    // launch_targets_mean).  Everything else is one kernel family that the own y runs with p = 1.  The routes stay apart
+    // because each is another summation order -- other bits -- for no shared benefit; the flag is the side's, not p == 1's:
+    // one target keeps the matrix route and its bits.
+    bool vector = false;
+    int p = 0, rows = 0;                            // label vectors (0: none set); rows of each of the five vectors: 1, or p rounded up to 128
+    size_t ystride = 0;                             // the row stride of y: n rounded up to 128
+    double *y = nullptr, *yy = nullptr;             // [p][ystride], zero padded to the chunks' 128-row tiles, and y_t'y_t
+    double *vec = nullptr;                          // q, c', gamma', beta', beta' / s2^2: [rows][mpad] each
+    double *part = nullptr;                         // the slabs' shares of q: [p][chunk pad / 128][mpad]
+    bool valid = false, pd = false;                 // b, c' hold for (data, Z, theta, labels); ... and both matrices were positive definite
     bool row_grad = false, row_z = false;           // the row holds the gradient; gz holds the gradient in Z
-    std::vector<double> row, gz;                    // [F, g (nh)[, F_t (p)]] and gZ [m][d]
+    std::vector<double> row, gz;                    // [F, g (nh), F_t (p)] and gZ [m][d]
     double *dout = nullptr, *hout = nullptr;        // results row, device and pinned
     Scratch pred;
+    double* v(int k, int mpad) const { return vec + (size_t)k * rows * mpad; }     // vector k of the five
 };
 
 struct cugp_sparse {
@@ -2653,26 +2667,18 @@ struct cugp_sparse {
     bool ard = false;
     double jitter = 1e-6;
     cugp_gp *u = nullptr, *b = nullptr;
-    double *dX = nullptr, *dy = nullptr;            // [n][d], y zero padded to the chunks' 128-row tiles
-    double *dyy = nullptr;                          // y'y
+    double *dX = nullptr;                           // [n][d]
     bool have_data = false, have_z = false;
     std::vector<double> theta;
     SparseSide own, tg;                             // the handle's own y; the targets (cugp_sparse_set_targets)
     // scratch, created on first use
     double *dS = nullptr, *dW = nullptr, *dG = nullptr;      // one chunk: k(X_c, Z), W_c, G_c^T ([chunk pad][mpad])
     double *dP = nullptr, *dscr = nullptr;                   // P and the Gram launch's partial tiles
-    double *dvec = nullptr;                                  // q, c', gamma', beta', beta' / s2^2 (mpad each), then the slabs' shares of q
     double *dM[4] = {nullptr, nullptr, nullptr, nullptr};    // H, H2, a product, R (mpad^2 each): the gradient's
     double *dpart = nullptr;                                 // trace partials: the rectangle's, then the square's
     // the gradient with respect to Z (cugp_sparse_bound_grad_z): created on its first use
     std::vector<double> z;                                   // Z as set, [m][d] (the host copy cugp_sparse_get_inducing returns)
     double *dzpart = nullptr, *dzacc = nullptr, *dzout = nullptr, *hz = nullptr;   // partial blocks, running sums, result, its pinned copy
-    // p targets over the same rows, hyper-parameters and inducing inputs (cugp_sparse_set_targets)
-    int tg_p = 0, tg_ppad = 0;                               // targets, and their count rounded up to 128 (0: none set)
-    size_t tg_ypad = 0;                                      // the row stride of tg_y: n rounded up to 128
-    double *tg_y = nullptr, *tg_yy = nullptr;                // Y [p][ypad] zero padded as dy, and y_t'y_t
-    double *tg_vec = nullptr;                                // Q, C', Gamma', Beta', Bs: [ppad][mpad] each
-    double *tg_part = nullptr;                               // the slabs' shares of Q: [p][chunk pad / 128][mpad]
 };
 
 namespace {
@@ -2698,10 +2704,8 @@ int sp_ensure(cugp_sparse* s, bool want_grad)
     const int chunks = sparse_shape(s->n, s->mpad, s->chunk_rows, 0).chunks;
     for (int c = 0; c < chunks; c++) split = std::max(split, sparse_shape(s->n, s->mpad, s->chunk_rows, c).split);
     if ((rc = ensure(&s->dS, cm)) || (rc = ensure(&s->dW, cm)) || (rc = ensure(&s->dP, mm)) ||
-        (rc = ensure(&s->dscr, (size_t)split * mm)) ||
-        (rc = ensure(&s->dvec, (size_t)(5 + sp_chunk_max(s) / TILE) * s->mpad)) || (rc = ensure(&s->own.dout, (size_t)1 + s->nh)))
+        (rc = ensure(&s->dscr, (size_t)split * mm)))
         return rc;
-    if (!s->own.hout) HIPCHK(hipHostMalloc((void**)&s->own.hout, ((size_t)1 + s->nh) * sizeof(double), hipHostMallocDefault));
     if (want_grad) {
         if ((rc = ensure(&s->dG, cm))) return rc;
         for (double*& p : s->dM)
@@ -2743,37 +2747,67 @@ void sp_chunk_w(cugp_sparse* s, const CovFn& cf, const SparseShape& c)
     launch_predict_gemm(s->dS, u->dT, s->dW, s->mpad, c.cpad / TILE, u->nt, u->stream);
 }
 
+void sp_side_free(SparseSide& r)
+{
+    for (double** q : {&r.y, &r.yy, &r.vec, &r.part, &r.dout}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    if (r.hout) (void)hipHostFree(r.hout);
+    r.hout = nullptr;
+    r.p = r.rows = 0;
+    r.valid = false;
+}
+
+// a side's buffers for p label vectors, all or none: a failed allocation leaves the side without labels
+int sp_side_alloc(cugp_sparse* s, SparseSide& r, int p)
+{
+    sp_side_free(r);
+    const int rows = r.vector ? 1 : (p + TILE - 1) / TILE * TILE;
+    const size_t ypad = ((size_t)s->n + TILE - 1) / TILE * TILE, nrow = (size_t)1 + s->nh + p;
+    int rc = ensure(&r.y, (size_t)p * ypad);
+    if (!rc) rc = ensure(&r.yy, (size_t)p);
+    if (!rc) rc = ensure(&r.vec, (size_t)5 * rows * s->mpad);
+    if (!rc) rc = ensure(&r.part, (size_t)p * (sp_chunk_max(s) / TILE) * s->mpad);
+    if (!rc) rc = ensure(&r.dout, nrow);
+    if (!rc && hipHostMalloc((void**)&r.hout, nrow * sizeof(double), hipHostMallocDefault) != hipSuccess)
+        rc = fail(CUGP_ERR_NOMEM, "cugp_sparse: the pinned results row");
+    if (rc) { sp_side_free(r); return rc; }
+    r.p = p;
+    r.rows = rows;
+    r.ystride = ypad;
+    return CUGP_OK;
+}
+
 // the checks every evaluating call shares, behind its own argument checks and in front of any device work
-int sp_ready(const cugp_sparse* s, bool targets, const char* call)
+int sp_ready(const cugp_sparse* s, const SparseSide& r, const char* call)
 {
     if (!s->have_data) return tg_invalid(call, "no data set (cugp_sparse_set_data)");
-    if (targets && s->tg_p <= 0) return tg_invalid(call, "no targets set (cugp_sparse_set_targets)");
+    if (r.p <= 0) return tg_invalid(call, "no targets set (cugp_sparse_set_targets)");
     if (!s->have_z) return tg_invalid(call, "no inducing inputs set (cugp_sparse_set_inducing)");
     return CUGP_OK;
 }
 
-// The bound (and its gradient) of one side at the current hyper-parameters: the handle's own y, or (targets) F = sum_t F_t
+// The bound (and its gradient) of one side at the current hyper-parameters: F = sum_t F_t over the side's p label vectors,
 // with the F_t behind the gradient's slots.  The results land in that side's row and gz: NaN where Kuu or B is not
 // positive definite (the header's convention).  Two host waits beyond the inner evaluation's: in front of B's
 // factorisation, which runs on the factor handle's own stream, and at the end.
-// Everything that costs O(N M^2) is the same launch for both sides.  The side decides five steps: how q / Q is summed
-// (one pass over W_c per group of targets), how c' / C' is solved, how gamma', beta' and H are formed (three small
-// triangular products on the M side, the rank-p terms of H), what the chunk's weights get beyond W_c R^T and which yv / bv
-// the trace passes are handed, and which kernel forms the final sums.
+// One sequence and one kernel family for both sides; a side's `vector` picks the route of the small solves and of the
+// weights' rank-p term (SparseSide).
 // want_z (with want_grad): the same sequence with the Z pass behind every k_trace_cross, on the weights that launch read
 // -- no launch of the sequence changes, so F and the hyper-parameter components keep their bits -- and no further host wait.
-int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool want_z = false)
+int sp_eval(cugp_sparse* s, SparseSide& r, bool want_grad, const char* call, bool want_z = false)
 {
     int rc;
-    if ((rc = sp_ready(s, targets, call))) return rc;
-    SparseSide &r = targets ? s->tg : s->own, &other = targets ? s->own : s->tg;
+    if ((rc = sp_ready(s, r, call))) return rc;
+    SparseSide& other = &r == &s->own ? s->tg : s->own;
     if (r.valid && (r.row_grad || !want_grad) && (r.row_z || !want_z)) return CUGP_OK;
     cugp_gp *u = s->u, *b = s->b;
     if (want_z) {
         if ((rc = use_device(u))) return rc;
         if ((rc = sp_ensure_z(s))) return rc;
     }
-    const int p = targets ? s->tg_p : 0, nrow = 1 + s->nh + p;
+    const int p = r.p, nrow = 1 + s->nh + p;
     r.valid = r.pd = false;
     other.valid = false;                                               // (b and P are about to be rewritten)
     r.row.assign((size_t)nrow, NAN);
@@ -2792,10 +2826,7 @@ int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool
     hipStream_t st = u->stream;
     const int mp = s->mpad, nl = s->nh - 2;
     const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    // q, c', gamma', beta', beta' / s2^2: one vector each, or one row per target each (Q, C', Gamma', Beta', Bs)
-    const size_t vec = targets ? (size_t)s->tg_ppad * mp : (size_t)mp;
-    double *q = targets ? s->tg_vec : s->dvec, *cp = q + vec, *gp = cp + vec, *bp = gp + vec, *bsc = bp + vec;
-    double* qpart = targets ? s->tg_part : bsc + vec;
+    double *q = r.v(0, mp), *cp = r.v(1, mp), *gp = r.v(2, mp), *bp = r.v(3, mp), *bsc = r.v(4, mp);
     const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
     CovFn cf;
     {
@@ -2805,8 +2836,7 @@ int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool
             const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
             sp_chunk_w(s, cf, sh);
             launch_sparse_gram(s->dW, mp, sh, s->dP, s->dscr, c == 0, st);
-            if (targets) launch_sparse_wty_targets(s->dW, mp, sh.cpad, s->tg_y + sh.r0, s->tg_ypad, p, qpart, q, c == 0, st);
-            else launch_sparse_wty(s->dW, mp, sh.cpad, s->dy + sh.r0, qpart, q, c == 0, st);
+            launch_sparse_wty_targets(s->dW, mp, sh.cpad, r.y + sh.r0, r.ystride, p, r.part, q, c == 0, st);
         }
         launch_sparse_form_b(s->dP, mp, s2, b->dA, st);
         HIPCHK(hipGetLastError());
@@ -2815,21 +2845,20 @@ int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool
     if ((rc = la_factor_inverse(b, true))) return rc;                  // LB, LB^-1, LB^-T, B^-1 (cugp_potri's route)
     if ((rc = use_device(u))) return rc;
     TuneScope ts(u);
-    if (targets) launch_predict_gemm(q, b->dT, cp, mp, s->tg_ppad / TILE, b->nt, st);  // C' = Q LB^-T: row t = LB^-1 q_t
-    else launch_trmv_lower(b->dT, mp, mp, q, cp, st);                  // c' = LB^-1 q
+    if (r.vector) launch_trmv_lower(b->dT, mp, mp, q, cp, st);         // c' = LB^-1 q
+    else launch_predict_gemm(q, b->dT, cp, mp, r.rows / TILE, b->nt, st);      // C' = Q LB^-T: row t = LB^-1 q_t
     const size_t nb_uf = sp_blocks_uf(s), nb_uu = (size_t)(mp / 64) * (mp / 64);
     double *part_uf = s->dpart, *part_uu = want_grad ? s->dpart + (size_t)(nl + 1) * nb_uf : nullptr;
     if (want_grad) {
         double *H = s->dM[0], *H2 = s->dM[1], *X1 = s->dM[2], *R = s->dM[3];
-        if (targets) {
-            launch_targets_alpha(cp, b->dU, gp, mp, p, st);            // Gamma' = C' LB^-1: row t = LB^-T c'_t
-            launch_targets_alpha(gp, u->dU, bp, mp, p, st);            // Beta' = Gamma' Lu^-1: row t = Lu^-T gamma'_t
-            launch_sparse_h_targets(b->dKinv, s->dP, gp, bp, p, s->m, mp, s2, H, H2, bsc, st);
-        } else {
+        if (r.vector) {
             launch_trmv_upper(b->dU, mp, mp, cp, gp, st);              // gamma' = LB^-T c'
             launch_trmv_upper(u->dU, mp, mp, gp, bp, st);              // beta' = Lu^-T gamma'
-            launch_sparse_h(b->dKinv, s->dP, gp, bp, s->m, mp, s2, H, H2, bsc, st);
+        } else {
+            launch_targets_alpha(cp, b->dU, gp, mp, p, st);            // Gamma' = C' LB^-1: row t = LB^-T c'_t
+            launch_targets_alpha(gp, u->dU, bp, mp, p, st);            // Beta' = Gamma' Lu^-1: row t = Lu^-T gamma'_t
         }
+        launch_sparse_h_targets(b->dKinv, s->dP, gp, bp, p, s->m, mp, s2, H, H2, bsc, st);
         launch_targets_alpha(H, u->dU, X1, mp, mp, st);                // H Lu^-1
         launch_sparse_transpose(X1, R, mp, 1.0 / s2, st);              // R = Lu^-T H / s2
         launch_targets_alpha(H2, u->dU, X1, mp, mp, st);               // H2 Lu^-1
@@ -2840,9 +2869,9 @@ int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool
             const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
             if (chunks > 1) sp_chunk_w(s, cf, sh);                     // (one chunk: W is still there)
             launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
-            if (targets)                                               // (the rank-p part goes into G: the traces get no yv, bv)
-                launch_sparse_weights_targets(s->dG, sh.cpad, mp, s->tg_y + sh.r0, s->tg_ypad, bsc, p, sh.count, s->m, st);
-            const double *yv = targets ? nullptr : s->dy + sh.r0, *bv = targets ? nullptr : bsc;
+            if (!r.vector)                                             // (the rank-p part goes into G: the traces get no yv, bv)
+                launch_sparse_weights_targets(s->dG, sh.cpad, mp, r.y + sh.r0, r.ystride, bsc, p, sh.count, s->m, st);
+            const double *yv = r.vector ? r.y + sh.r0 : nullptr, *bv = r.vector ? bsc : nullptr;
             launch_trace_cross(s->dX + (size_t)sh.r0 * s->d, sh.count, sh.cpad, u->dX, s->m, s->d, mp, cf, s->dG, yv, bv,
                                part_uf, nb_uf, pofs, st);
             if (want_z)
@@ -2860,13 +2889,8 @@ int sp_eval(cugp_sparse* s, bool targets, bool want_grad, const char* call, bool
     for (int i = 0; i < nrow; i++) r.hout[i] = NAN;
     const double* puf = want_grad ? part_uf : nullptr;
     const double ls2 = s->theta[s->nh - 1] * 2;
-    if (targets) {
-        const SparseFinalTargets fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->tg_yy, s->m, mp, b->nt, p, (double)s->n, sf2, s2, ls2};
-        launch_sparse_finalize_targets(fin, puf, nb_uf, part_uu, nb_uu, nl, r.dout, r.hout, st);
-    } else {
-        const SparseFinal fin{s->dP, b->dKinv, cp, gp, b->dlogdet, s->dyy, s->m, mp, b->nt, (double)s->n, sf2, s2, ls2};
-        launch_sparse_finalize(fin, puf, nb_uf, part_uu, nb_uu, nl, r.dout, r.hout, st);
-    }
+    const SparseFinalTargets fin{s->dP, b->dKinv, cp, gp, b->dlogdet, r.yy, s->m, mp, b->nt, p, (double)s->n, sf2, s2, ls2};
+    launch_sparse_finalize_targets(fin, puf, nb_uf, part_uu, nb_uu, nl, r.dout, r.hout, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
@@ -2908,7 +2932,7 @@ bool sp_z_moved(const cugp_sparse* s, const double* zv)                // (a NaN
 
 struct SpObjective {                                                    // what the two callbacks below are handed
     cugp_sparse* s;
-    bool targets;
+    SparseSide* side;
     const char* call;
 };
 
@@ -2916,8 +2940,8 @@ struct SpObjective {                                                    // what 
 void sp_objective(void* ctx, const double* th, int nh, double* f, double* gr)
 {
     const SpObjective* o = (const SpObjective*)ctx;
-    const SparseSide& r = o->targets ? o->s->tg : o->s->own;
-    if (sp_set_theta(o->s, th) == CUGP_OK && sp_eval(o->s, o->targets, true, o->call) == CUGP_OK) {
+    SparseSide& r = *o->side;
+    if (sp_set_theta(o->s, th) == CUGP_OK && sp_eval(o->s, r, true, o->call) == CUGP_OK) {
         *f = -1.0 * r.row[0];
         std::copy(r.row.begin() + 1, r.row.begin() + 1 + nh, gr);
     } else {
@@ -2931,9 +2955,9 @@ void sp_objective_z(void* ctx, const double* v, int nv, double* f, double* gr)
 {
     const SpObjective* o = (const SpObjective*)ctx;
     cugp_sparse* s = o->s;
-    const SparseSide& r = o->targets ? s->tg : s->own;
+    SparseSide& r = *o->side;
     if ((!sp_z_moved(s, v + s->nh) || cugp_sparse_set_inducing(s, v + s->nh) == CUGP_OK) && sp_set_theta(s, v) == CUGP_OK &&
-        sp_eval(s, o->targets, true, o->call, true) == CUGP_OK) {
+        sp_eval(s, r, true, o->call, true) == CUGP_OK) {
         *f = -1.0 * r.row[0];
         std::copy(r.row.begin() + 1, r.row.begin() + 1 + s->nh, gr);
         std::copy(r.gz.begin(), r.gz.end(), gr + s->nh);
@@ -2974,12 +2998,13 @@ int sp_cg_theta_z(cugp_sparse* s, SpObjective* o, int budget, double* trace, int
 }
 
 // the three cg calls: the argument checks, then the driver of the side
-int sp_cg(cugp_sparse* s, bool targets, bool inducing, const char* call, int budget, double* trace, int trace_cap, int* nevals)
+int sp_cg(cugp_sparse* s, SparseSide cugp_sparse::*side, bool inducing, const char* call, int budget, double* trace, int trace_cap,
+          int* nevals)
 {
     if (!s) return tg_invalid(call, "null handle");
     if (budget <= 0) return tg_invalid(call, "budget must be positive");
-    if (const int rc = sp_ready(s, targets, call)) return rc;
-    SpObjective o{s, targets, call};
+    if (const int rc = sp_ready(s, s->*side, call)) return rc;
+    SpObjective o{s, &(s->*side), call};
     return inducing ? sp_cg_theta_z(s, &o, budget, trace, trace_cap, nevals) : sp_cg_theta(s, &o, budget, trace, trace_cap, nevals);
 }
 }  // namespace
@@ -3037,13 +3062,12 @@ int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, dou
     s->jitter = jitter; s->chunk_rows = chunk_rows;
     s->mpad = (m + TILE - 1) / TILE * TILE;
     s->theta.assign(s->nh, 0.0);
-    s->own.row.assign((size_t)1 + s->nh, NAN);
+    s->own.vector = true;
+    s->own.row.assign((size_t)2 + s->nh, NAN);
     if ((rc = create_handle(m, d, device, 0, s->ard, &s->u, kernel)) || (rc = cugp_create(m, 1, device, &s->b)) ||
         (rc = ensure_factor_bufs(s->b)) || (rc = ensure_inverse_bufs(s->b))) { cugp_sparse_destroy(s); return rc; }
-    const size_t ny = ((size_t)n + TILE - 1) / TILE * TILE;
+    if ((rc = sp_side_alloc(s, s->own, 1))) { cugp_sparse_destroy(s); return rc; }
     hipError_t e = hipMalloc((void**)&s->dX, (size_t)n * d * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->dy, ny * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->dyy, sizeof(double));
     if (e == hipSuccess) e = hipMemset(s->b->dy, 0, (size_t)s->b->npad * sizeof(double));
     if (e != hipSuccess) {
         rc = fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, call, e);
@@ -3061,11 +3085,11 @@ int cugp_sparse_destroy(cugp_sparse* s)
     if (s->u && s->u->stream) (void)hipStreamSynchronize(s->u->stream);
     if (s->u) (void)cugp_destroy(s->u);
     if (s->b) (void)cugp_destroy(s->b);
-    for (double* p : {s->dX, s->dy, s->dyy, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dvec, s->dM[0], s->dM[1], s->dM[2], s->dM[3],
-                      s->dpart, s->own.dout, s->dzpart, s->dzacc, s->dzout, s->tg_y, s->tg_yy, s->tg_vec, s->tg_part, s->tg.dout})
+    for (double* p : {s->dX, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dM[0], s->dM[1], s->dM[2], s->dM[3], s->dpart, s->dzpart,
+                      s->dzacc, s->dzout})
         if (p) (void)hipFree(p);
     for (SparseSide* r : {&s->own, &s->tg}) {
-        if (r->hout) (void)hipHostFree(r->hout);
+        sp_side_free(*r);
         r->pred.release();
     }
     if (s->hz) (void)hipHostFree(s->hz);
@@ -3098,11 +3122,11 @@ int cugp_sparse_set_data(cugp_sparse* s, const double* X, const double* y)
     int rc;
     if ((rc = use_device(s->u))) return rc;
     hipStream_t st = s->u->stream;
-    const size_t ny = ((size_t)s->n + TILE - 1) / TILE * TILE;
+    SparseSide& r = s->own;
     HIPCHK(hipMemcpyAsync(s->dX, X, (size_t)s->n * s->d * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(s->dy, 0, ny * sizeof(double), st));
-    HIPCHK(hipMemcpyAsync(s->dy, y, (size_t)s->n * sizeof(double), hipMemcpyHostToDevice, st));
-    launch_sparse_yy(s->dy, s->n, s->dyy, st);
+    HIPCHK(hipMemsetAsync(r.y, 0, r.ystride * sizeof(double), st));
+    HIPCHK(hipMemcpyAsync(r.y, y, (size_t)s->n * sizeof(double), hipMemcpyHostToDevice, st));
+    launch_sparse_yy_targets(r.y, r.ystride, s->n, 1, r.yy, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     s->have_data = true;
@@ -3142,7 +3166,7 @@ int cugp_sparse_bound(cugp_sparse* s, double* F)
 {
     const char* call = "cugp_sparse_bound";
     if (!s || !F) return tg_invalid(call, "null argument");
-    if (const int rc = sp_eval(s, false, false, call)) return rc;
+    if (const int rc = sp_eval(s, s->own, false, call)) return rc;
     sp_copy_row(s->own, s->nh, F, nullptr, nullptr);
     return CUGP_OK;
 }
@@ -3152,22 +3176,22 @@ int cugp_sparse_bound_grad(cugp_sparse* s, double* F, double* g, int nh)
     const char* call = "cugp_sparse_bound_grad";
     if (!s || !F || !g) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval(s, false, true, call)) return rc;
+    if (const int rc = sp_eval(s, s->own, true, call)) return rc;
     sp_copy_row(s->own, s->nh, F, g, nullptr);
     return CUGP_OK;
 }
 
 namespace {
 // The prediction of one side, behind the call's own argument checks.  Per pass of cugp_sparse_predict_plan Ks, Wt and Vt;
-// the variance, which no y enters, by k_sparse_predict_finish.  The handle's own mean comes from that launch too; the
-// targets' means are (C' / s2) Vt^T (launch_targets_mean), each pass's rows copied to their place in the target-major
-// result, and their `var` may be NULL (then the launch is left out).
-int sp_predict(cugp_sparse* s, bool targets, const char* call, const double* Xt, int nt, int with_noise, double* mean, double* var)
+// the variance, which no y enters, by k_sparse_predict_finish.  A vector side's mean comes from that launch too; a matrix
+// side's means are (C' / s2) Vt^T (launch_targets_mean), each pass's rows copied to their place in the target-major
+// result, and its `var` may be NULL (then the launch is left out).
+int sp_predict(cugp_sparse* s, SparseSide& r, const char* call, const double* Xt, int nt, int with_noise, double* mean, double* var)
 {
     int rc;
-    if ((rc = sp_eval(s, targets, false, call))) return rc;            // (answers from the last evaluation's state when it holds)
-    SparseSide& r = targets ? s->tg : s->own;
-    const int p = targets ? s->tg_p : 1;
+    if ((rc = sp_eval(s, r, false, call))) return rc;                  // (answers from the last evaluation's state when it holds)
+    const int p = r.p;
+    const bool matrix = !r.vector;
     if (!r.pd) {
         std::fill(mean, mean + (size_t)p * nt, NAN);
         if (var) std::fill(var, var + nt, NAN);
@@ -3183,9 +3207,9 @@ int sp_predict(cugp_sparse* s, bool targets, const char* call, const double* Xt,
     if (passes < 1) return passes;
     const int cmax = (pr[1] + TILE - 1) / TILE * TILE;
     const size_t nxt = (((size_t)nt * s->d + 15) / 16) * 16, nks = (size_t)cmax * mp;
-    // the targets' own: C' / s2, launch_targets_mean's partial sums, a pass's means [p][rows]; their dm is one pass's, unread
-    const size_t ncs = targets ? (size_t)p64 * mp : 0, npp = targets ? (size_t)targets_mean_split(mp) * p64 * cmax : 0;
-    const size_t nm = targets ? (size_t)p * pr[1] : 0, ndm = targets ? (size_t)cmax : (size_t)nt;
+    // the matrix route's own: C' / s2, launch_targets_mean's partial sums, a pass's means [p][rows]; its dm is one pass's, unread
+    const size_t ncs = matrix ? (size_t)p64 * mp : 0, npp = matrix ? (size_t)targets_mean_split(mp) * p64 * cmax : 0;
+    const size_t nm = matrix ? (size_t)p * pr[1] : 0, ndm = matrix ? (size_t)cmax : (size_t)nt;
     if ((rc = r.pred.grow(nxt + 3 * nks + ncs + npp + nm + ndm + nt, st))) return rc;
     double *dXt = r.pred.p, *dKs = dXt + nxt, *dWt = dKs + nks, *dVt = dWt + nks, *dCs = dVt + nks, *dPp = dCs + ncs;
     double *dM = dPp + npp, *dm = dM + nm, *dv = dm + ndm;
@@ -3193,8 +3217,8 @@ int sp_predict(cugp_sparse* s, bool targets, const char* call, const double* Xt,
     CovFn cf;
     if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
     const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    const double* cp = targets ? s->tg_vec + (size_t)s->tg_ppad * mp : s->dvec + mp;     // c', or C'
-    if (targets) launch_sparse_scale_targets(cp, p, p64, s->m, mp, s2, dCs, st);
+    const double* cp = r.v(1, mp);                                     // c', or C'
+    if (matrix) launch_sparse_scale_targets(cp, p, p64, s->m, mp, s2, dCs, st);
     hipError_t e = hipGetLastError();
     for (int ps = 0; ps < passes && e == hipSuccess; ps++) {
         (void)cugp_sparse_predict_plan(s->m, nt, ps, pr);
@@ -3202,14 +3226,14 @@ int sp_predict(cugp_sparse* s, bool targets, const char* call, const double* Xt,
         launch_kcross(u->dX, s->m, s->d, mp, dXt + (size_t)t0 * s->d, c, cpad, cf, dKs, st);
         launch_predict_gemm(dKs, u->dT, dWt, mp, cpad / TILE, u->nt, st);      // Wt = Ks Lu^-T
         launch_predict_gemm(dWt, b->dT, dVt, mp, cpad / TILE, b->nt, st);      // Vt = Wt LB^-T
-        if (var) launch_sparse_predict_finish(dWt, dVt, cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, targets ? dm : dm + t0, dv + t0, st);
-        if (targets) launch_targets_mean(dCs, dVt, dPp, mp, p, c, cpad, dM, st);       // [p][c], packed
+        if (var) launch_sparse_predict_finish(dWt, dVt, cp, mp, c, sf2, s2, with_noise ? s2 : 0.0, matrix ? dm : dm + t0, dv + t0, st);
+        if (matrix) launch_targets_mean(dCs, dVt, dPp, mp, p, c, cpad, dM, st);       // [p][c], packed
         e = hipGetLastError();
-        if (e == hipSuccess && targets)                                        // row t of the pass to mean[t * nt + t0 ..]
+        if (e == hipSuccess && matrix)                                         // row t of the pass to mean[t * nt + t0 ..]
             e = hipMemcpy2DAsync(mean + t0, (size_t)nt * sizeof(double), dM, (size_t)c * sizeof(double),
                                  (size_t)c * sizeof(double), p, hipMemcpyDeviceToHost, st);
     }
-    if (e == hipSuccess && !targets) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && !matrix) e = hipMemcpyAsync(mean, dm, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess && var) e = hipMemcpyAsync(var, dv, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { (void)hipStreamSynchronize(st); return fail(CUGP_ERR_DEVICE, call, e); }
@@ -3222,7 +3246,7 @@ int cugp_sparse_predict(cugp_sparse* s, const double* Xt, int nt, int with_noise
     const char* call = "cugp_sparse_predict";
     if (!s || !Xt || !mean || !var) return tg_invalid(call, "null argument");
     if (nt <= 0) return tg_invalid(call, "nt must be positive");
-    return sp_predict(s, false, call, Xt, nt, with_noise, mean, var);
+    return sp_predict(s, s->own, call, Xt, nt, with_noise, mean, var);
 }
 
 // ---- joint covariance, draws and input gradients of the prediction (include/cugp.h)
@@ -3265,7 +3289,7 @@ int sp_predict_cov_device(cugp_sparse* s, const char* call, const double* Xt, in
                           double** dmean, cugp_gp** fout, bool* pd)
 {
     int rc;
-    if ((rc = sp_eval(s, false, false, call))) return rc;
+    if ((rc = sp_eval(s, s->own, false, call))) return rc;
     *pd = s->own.pd;
     if (!*pd) return CUGP_OK;
     cugp_gp *u = s->u, *b = s->b;
@@ -3289,7 +3313,7 @@ int sp_predict_cov_device(cugp_sparse* s, const char* call, const double* Xt, in
     launch_kcross(u->dX, s->m, s->d, mp, dXt, nt, ntpad, cf, dKs, st);
     launch_predict_gemm(dKs, u->dT, dWt, mp, tiles, u->nt, st);        // Wt = Ks Lu^-T
     launch_predict_gemm(dWt, b->dT, dVt, mp, tiles, b->nt, st);        // Vt = Wt LB^-T
-    launch_sparse_predict_finish(dWt, dVt, s->dvec + mp, mp, nt, sf2, s2, with_noise ? s2 : 0.0, dm, dv, st);
+    launch_sparse_predict_finish(dWt, dVt, s->own.v(1, mp), mp, nt, sf2, s2, with_noise ? s2 : 0.0, dm, dv, st);
     const CovShape cs = predict_cov_shape(ntpad, mp);
     if ((rc = u->cov_scr.grow((size_t)(cs.split - 1) * ntpad * ntpad, st))) return rc;
     launch_sparse_predict_cov(dWt, dVt, mp, ntpad, cs, f->dA, u->cov_scr.p, st);
@@ -3309,7 +3333,7 @@ int sp_cov_refuse(const cugp_sparse* s, const char* call, int nt)
     if (nt > CUGP_SPARSE_MAX_M) return tg_invalid(call, "nt beyond CUGP_SPARSE_MAX_M (cugp_sparse_predict_cov_plan)");
     if (nt > sparse_predict_rows(s->mpad))
         return tg_invalid(call, "nt beyond the first pass of cugp_sparse_predict_plan (cugp_sparse_predict_cov_plan)");
-    return sp_ready(s, false, call);
+    return sp_ready(s, s->own, call);
 }
 }  // namespace
 
@@ -3386,7 +3410,7 @@ int cugp_sparse_predict_grad(cugp_sparse* s, const double* Xt, int nt, int with_
     if (!dmean && !dvar) return tg_invalid(call, "dmean and dvar are both NULL");
     if (nt <= 0) return tg_invalid(call, "nt must be positive");
     int rc;
-    if ((rc = sp_eval(s, false, false, call))) return rc;
+    if ((rc = sp_eval(s, s->own, false, call))) return rc;
     const size_t nout = (size_t)nt * s->d;
     if (!s->own.pd) {
         if (mean) std::fill(mean, mean + nt, NAN);
@@ -3415,7 +3439,7 @@ int cugp_sparse_predict_grad(cugp_sparse* s, const double* Xt, int nt, int with_
     CovFn cf;
     if ((rc = cov_fn(u, st, nullptr, &cf))) return rc;
     const double sf2 = std::exp(s->theta[s->nh - 2] * 2), s2 = std::exp(s->theta[s->nh - 1] * 2);
-    const double* cp = s->dvec + mp;                                   // c'
+    const double* cp = s->own.v(1, mp);                                   // c'
     launch_trmv_upper(b->dU, mp, mp, cp, dgam, st);                    // gamma' = LB^-T c'
     launch_trmv_upper(u->dU, mp, mp, dgam, dbet, st);                  // beta' = Lu^-T gamma'
     hipError_t e = hipGetLastError();
@@ -3446,7 +3470,7 @@ int cugp_sparse_predict_grad(cugp_sparse* s, const double* Xt, int nt, int with_
 
 int cugp_sparse_cg_solve(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)
 {
-    return sp_cg(s, false, false, "cugp_sparse_cg_solve", budget, trace, trace_cap, nevals);
+    return sp_cg(s, &cugp_sparse::own, false, "cugp_sparse_cg_solve", budget, trace, trace_cap, nevals);
 }
 
 // ---- the inducing inputs as variables
@@ -3464,7 +3488,7 @@ int cugp_sparse_bound_grad_z(cugp_sparse* s, double* F, double* g, int nh, doubl
     const char* call = "cugp_sparse_bound_grad_z";
     if (!s || !F || !g || !gZ) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval(s, false, true, call, true)) return rc;
+    if (const int rc = sp_eval(s, s->own, true, call, true)) return rc;
     sp_copy_row(s->own, s->nh, F, g, nullptr);
     std::copy(s->own.gz.begin(), s->own.gz.end(), gZ);
     return CUGP_OK;
@@ -3472,27 +3496,13 @@ int cugp_sparse_bound_grad_z(cugp_sparse* s, double* F, double* g, int nh, doubl
 
 int cugp_sparse_cg_solve_z(cugp_sparse* s, int budget, double* trace, int trace_cap, int* nevals)
 {
-    return sp_cg(s, false, true, "cugp_sparse_cg_solve_z", budget, trace, trace_cap, nevals);
+    return sp_cg(s, &cugp_sparse::own, true, "cugp_sparse_cg_solve_z", budget, trace, trace_cap, nevals);
 }
 
 // ---- p targets over one set of inducing points (include/cugp.h)
 // The calls below are the single-target ones with sp_eval, sp_predict and sp_cg asked for the targets' side; what is
 // theirs alone is the targets' data.  Either side's evaluation writes the shared factor handle b and P, so it takes the
 // other side's validity.
-namespace {
-void sp_free_targets(cugp_sparse* s)
-{
-    for (double** q : {&s->tg_y, &s->tg_yy, &s->tg_vec, &s->tg_part, &s->tg.dout}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    if (s->tg.hout) (void)hipHostFree(s->tg.hout);
-    s->tg.hout = nullptr;
-    s->tg_p = s->tg_ppad = 0;
-    s->tg.valid = false;
-}
-}  // namespace
-
 int cugp_sparse_set_targets(cugp_sparse* s, const double* Y, int p)
 {
     const char* call = "cugp_sparse_set_targets";
@@ -3503,37 +3513,23 @@ int cugp_sparse_set_targets(cugp_sparse* s, const double* Y, int p)
     if ((rc = use_device(s->u))) return rc;
     hipStream_t st = s->u->stream;
     HIPCHK(hipStreamSynchronize(st));
-    s->tg.valid = false;
-    const int mp = s->mpad, ppad = (p + TILE - 1) / TILE * TILE;
-    const size_t ypad = ((size_t)s->n + TILE - 1) / TILE * TILE, vec = (size_t)ppad * mp, row = (size_t)1 + s->nh + p;
-    if (p != s->tg_p) {
-        sp_free_targets(s);
-        rc = ensure(&s->tg_y, (size_t)p * ypad);
-        if (!rc) rc = ensure(&s->tg_yy, (size_t)p);
-        if (!rc) rc = ensure(&s->tg_vec, 5 * vec);
-        if (!rc) rc = ensure(&s->tg_part, (size_t)p * (sp_chunk_max(s) / TILE) * mp);
-        if (!rc) rc = ensure(&s->tg.dout, row);
-        if (!rc && hipHostMalloc((void**)&s->tg.hout, row * sizeof(double), hipHostMallocDefault) != hipSuccess)
-            rc = fail(CUGP_ERR_NOMEM, "cugp_sparse_set_targets: the pinned results row");
-        if (rc) { sp_free_targets(s); return rc; }                    // (all or none: the handle is left without targets)
-        s->tg_ppad = ppad;
-        s->tg_ypad = ypad;
-    }
-    HIPCHK(hipMemsetAsync(s->tg_y, 0, (size_t)p * ypad * sizeof(double), st));
-    HIPCHK(hipMemsetAsync(s->tg_vec, 0, 5 * vec * sizeof(double), st));
-    HIPCHK(hipMemcpy2DAsync(s->tg_y, ypad * sizeof(double), Y, (size_t)s->n * sizeof(double), (size_t)s->n * sizeof(double), p,
+    SparseSide& r = s->tg;
+    r.valid = false;
+    if (p != r.p && (rc = sp_side_alloc(s, r, p))) return rc;          // (all or none: the handle is left without targets)
+    HIPCHK(hipMemsetAsync(r.y, 0, (size_t)p * r.ystride * sizeof(double), st));
+    HIPCHK(hipMemsetAsync(r.vec, 0, (size_t)5 * r.rows * s->mpad * sizeof(double), st));
+    HIPCHK(hipMemcpy2DAsync(r.y, r.ystride * sizeof(double), Y, (size_t)s->n * sizeof(double), (size_t)s->n * sizeof(double), p,
                             hipMemcpyHostToDevice, st));
-    launch_sparse_yy_targets(s->tg_y, ypad, s->n, p, s->tg_yy, st);
+    launch_sparse_yy_targets(r.y, r.ystride, s->n, p, r.yy, st);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
-    s->tg_p = p;
     return CUGP_OK;
 }
 
 int cugp_sparse_num_targets(const cugp_sparse* s, int* p)
 {
     if (!s || !p) return tg_invalid("cugp_sparse_num_targets", "null argument");
-    *p = s->tg_p;
+    *p = s->tg.p;
     return CUGP_OK;
 }
 
@@ -3541,7 +3537,7 @@ int cugp_sparse_bound_targets(cugp_sparse* s, double* F, double* F_each)
 {
     const char* call = "cugp_sparse_bound_targets";
     if (!s || !F) return tg_invalid(call, "null argument");
-    if (const int rc = sp_eval(s, true, false, call)) return rc;
+    if (const int rc = sp_eval(s, s->tg, false, call)) return rc;
     sp_copy_row(s->tg, s->nh, F, nullptr, F_each);
     return CUGP_OK;
 }
@@ -3551,7 +3547,7 @@ int cugp_sparse_bound_grad_targets(cugp_sparse* s, double* F, double* g, int nh,
     const char* call = "cugp_sparse_bound_grad_targets";
     if (!s || !F || !g) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval(s, true, true, call)) return rc;
+    if (const int rc = sp_eval(s, s->tg, true, call)) return rc;
     sp_copy_row(s->tg, s->nh, F, g, F_each);
     return CUGP_OK;
 }
@@ -3561,7 +3557,7 @@ int cugp_sparse_bound_grad_z_targets(cugp_sparse* s, double* F, double* g, int n
     const char* call = "cugp_sparse_bound_grad_z_targets";
     if (!s || !F || !g || !gZ) return tg_invalid(call, "null argument");
     if (nh != s->nh) return tg_invalid(call, "nh is not the handle's (cugp_sparse_num_hyper)");
-    if (const int rc = sp_eval(s, true, true, call, true)) return rc;
+    if (const int rc = sp_eval(s, s->tg, true, call, true)) return rc;
     sp_copy_row(s->tg, s->nh, F, g, F_each);
     std::copy(s->tg.gz.begin(), s->tg.gz.end(), gZ);
     return CUGP_OK;
@@ -3573,13 +3569,13 @@ int cugp_sparse_predict_targets(cugp_sparse* s, const double* Xt, int nt, int wi
     const char* call = "cugp_sparse_predict_targets";
     if (!s || !Xt || !mean) return tg_invalid(call, "null argument");
     if (nt <= 0) return tg_invalid(call, "nt must be positive");
-    return sp_predict(s, true, call, Xt, nt, with_noise, mean, var);
+    return sp_predict(s, s->tg, call, Xt, nt, with_noise, mean, var);
 }
 
 // cugp_sparse_cg_solve (inducing 0) or cugp_sparse_cg_solve_z (otherwise) on -sum_t F_t: the same loop, record and end point
 int cugp_sparse_cg_solve_targets(cugp_sparse* s, int budget, int inducing, double* trace, int trace_cap, int* nevals)
 {
-    return sp_cg(s, true, inducing != 0, "cugp_sparse_cg_solve_targets", budget, trace, trace_cap, nevals);
+    return sp_cg(s, &cugp_sparse::tg, inducing != 0, "cugp_sparse_cg_solve_targets", budget, trace, trace_cap, nevals);
 }
 
 // ---------------------------------------------------------------- timing

@@ -318,15 +318,8 @@ SparseShape sparse_shape(int n, int mpad, int chunk_rows, int pass);
 // P (lower 128-tiles of mpad^2, diagonal tiles complete) = (first ? 0 : P) + W^T W, W: [c.cpad][mpad] (k_sparse_gram: the
 // split-k partial tiles into scr, c.split * mpad^2 doubles; k_sparse_gram_finish adds them in index order)
 void launch_sparse_gram(const double* W, int mpad, const SparseShape& c, double* P, double* scr, bool first, hipStream_t s);
-// q (mpad) = (first ? 0 : q) + W^T y through the 128-row slabs' shares part ([cpad / 128][mpad]), added in slab order
-void launch_sparse_wty(const double* W, int mpad, int cpad, const double* y, double* part, double* q, bool first,
-                       hipStream_t s);
-void launch_sparse_yy(const double* y, int n, double* out, hipStream_t s);                     // out[0] = y'y, one workgroup
 // Bm (lower 128-tiles, diagonal tiles complete) = I + P / s2
 void launch_sparse_form_b(const double* P, int mpad, double s2, double* Bm, hipStream_t s);
-// H = I - B^-1 - gamma gamma^T, H2 = H - P / s2 (full mpad^2, zero beyond m; gamma = gp / s2), bsc = bp / s2^2
-void launch_sparse_h(const double* Binv, const double* P, const double* gp, const double* bp, int m, int mpad, double s2,
-                     double* H, double* H2, double* bsc, hipStream_t s);
 void launch_sparse_transpose(const double* src, double* dst, int mpad, double scale, hipStream_t s);   // dst = scale src^T
 // G ([cpad][mpad]) = W R^T: the plain NT product on the tile (k_test_gemm), K = mpad
 void launch_sparse_weights(const double* W, const double* R, double* G, int cpad, int mpad, hipStream_t s);
@@ -347,18 +340,6 @@ SparseZShape sparse_z_shape(int rows_pad, int mpad, int d);
 void launch_trace_cross_z(const double* Xr, int nr, int rows_pad, const double* Z, int m, int d, int mpad, const CovFn& cf,
                           const double* G, const double* yv, const double* bv, double* part, double* acc, bool first,
                           bool last, double* out, double* hout, hipStream_t s);
-// what the last launch of an evaluation reads beside the trace partials
-struct SparseFinal {
-    const double *P, *Binv;        // ld x ld: their diagonals
-    const double *cp, *gp;         // c' = LB^-1 q and gamma' = LB^-T c' (gp is read for the gradient only)
-    const double *logdet;          // the factor of B: one share sum log L_ii per 128-tile
-    const double *yy;              // y'y
-    int m, ld, nt;
-    double n, sf2, s2, log_s2;     // N as a double, exp(2 theta_f), exp(2 theta_n), 2 theta_n
-};
-// one workgroup: out[0] = hout[0] = F and (part_uf given) out[1 ..] = hout[1 ..] = the nl + 2 components of d(-F) / dtheta
-void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t nb_uf, const double* part_uu, size_t nb_uu,
-                            int nl, double* out, double* hout, hipStream_t s);
 // mean = Vt c' / s2, var = sf2 - |Wt_t|^2 + |Vt_t|^2 + noise per test row (Wt, Vt: [>= nt][mpad])
 void launch_sparse_predict_finish(const double* Wt, const double* Vt, const double* cp, int mpad, int nt, double sf2,
                                   double s2, double noise, double* mean, double* var, hipStream_t s);
@@ -370,8 +351,9 @@ void launch_sparse_predict_cov(const double* Wt, const double* Vt, int ld, int n
 // D = Wt - T over `rows` rows of mpad (D null: left out) and (a given) a[i] = bp[i] / s2 for i < m, 0 up to mpad
 void launch_sparse_predict_diff(const double* Wt, const double* T, double* D, int mpad, int rows, const double* bp, double s2,
                                 int m, double* a, hipStream_t s);
-// ---- multi-target regression over one set of inducing points (cugp_sparse_*_targets; sparse_targets_device.h, DESIGN.md
-// section 27): Y [p][ystride] target-major, zero padded as the handle's y; Q, C', Gamma', Beta', Bs [>= p][mpad] ----
+// ---- what reads the labels of the sparse model: p targets over one set of inducing points (cugp_sparse_*_targets), and
+// the handle's own y as p = 1 (sparse_targets_device.h): Y [p][ystride] target-major, every row zero
+// padded to the chunks' 128-row tiles; Q, C', Gamma', Beta', Bs [>= p][mpad] ----
 // Q[t] (mpad) = (first ? 0 : Q[t]) + W^T y_t for every target, W read once per group of 8 targets; Y: the chunk's first row
 // of target 0; part: p * (cpad / 128) * mpad doubles, the slabs' shares, added in slab order
 void launch_sparse_wty_targets(const double* W, int mpad, int cpad, const double* Y, size_t ystride, int p, double* part,
@@ -386,7 +368,7 @@ void launch_sparse_weights_targets(double* G, int cpad, int mpad, const double* 
                                    int nr, int m, hipStream_t s);
 // Cs ([rows][mpad], rows = p rounded up to 64) = C' / s2, zero beyond p: the first operand of launch_targets_mean
 void launch_sparse_scale_targets(const double* Cm, int p, int rows, int m, int mpad, double s2, double* Cs, hipStream_t s);
-// what the last launch of a targets evaluation reads beside the trace partials
+// what the last launch of an evaluation reads beside the trace partials
 struct SparseFinalTargets {
     const double *P, *Binv;        // ld x ld: their diagonals
     const double *Cp, *Gm;         // C' and Gamma', [p][ld] (Gm is read for the gradient only)

@@ -3060,15 +3060,16 @@ __global__ __launch_bounds__(256, 2) void k_loo_product(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------
-// Sparse variational GP regression on inducing points (cugp_sparse_*): k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty,
-// k_sparse_wty_finish, k_sparse_yy, k_sparse_h, k_sparse_transpose, k_trace_cross, k_sparse_finalize,
-// k_sparse_predict_finish (sparse_device.h: a host can emulate them) and the one new product, k_sparse_gram; the gradient
-// with respect to the inducing inputs: k_trace_cross_z, k_trace_cross_z_finish (sparse_z_device.h, emulable as well)
+// Sparse variational GP regression on inducing points (cugp_sparse_*): k_sparse_gram_finish, k_sparse_form_b,
+// k_sparse_transpose, k_trace_cross, k_sparse_predict_finish (sparse_device.h: a host can emulate them) and the one new
+// product, k_sparse_gram; the gradient with respect to the inducing inputs: k_trace_cross_z, k_trace_cross_z_finish
+// (sparse_z_device.h, emulable as well)
 // ------------------------------------------------------------------------------------------
 #include "sparse_device.h"
 #include "sparse_z_device.h"
-// p targets over one set of inducing points: k_sparse_wty_targets and its finish, k_sparse_yy_targets, k_sparse_h_targets,
-// k_sparse_weights_targets, k_sparse_scale_targets, k_sparse_finalize_targets (emulable as well)
+// what reads the labels -- the handle's own y as one target, or p targets over the same inducing points: k_sparse_wty_targets
+// and its finish, k_sparse_yy_targets, k_sparse_h_targets, k_sparse_weights_targets, k_sparse_scale_targets,
+// k_sparse_finalize_targets (emulable as well)
 #include "sparse_targets_device.h"
 // the input gradients of the sparse prediction: k_sparse_predict_diff (emulable as well)
 #include "sparse_predict_device.h"
@@ -3824,30 +3825,9 @@ void launch_sparse_gram(const double* W, int mpad, const SparseShape& c, double*
                        c.split, first ? 1 : 0);
 }
 
-void launch_sparse_wty(const double* W, int mpad, int cpad, const double* y, double* part, double* q, bool first,
-                       hipStream_t s)
-{
-    const int slabs = cpad / TILE;
-    hipLaunchKernelGGL(k_sparse_wty, dim3((mpad / KT) * slabs), dim3(256), 0, s, W, mpad, y, part);
-    hipLaunchKernelGGL(k_sparse_wty_finish, dim3((mpad + 255) / 256), dim3(256), 0, s, (const double*)part, slabs, mpad, q,
-                       first ? 1 : 0);
-}
-
-void launch_sparse_yy(const double* y, int n, double* out, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_sparse_yy, dim3(1), dim3(256), 0, s, y, n, out);
-}
-
 void launch_sparse_form_b(const double* P, int mpad, double s2, double* Bm, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sparse_form_b, dim3(tri_count(mpad / TILE) * 16), dim3(256), 0, s, P, mpad, s2, Bm);
-}
-
-void launch_sparse_h(const double* Binv, const double* P, const double* gp, const double* bp, int m, int mpad, double s2,
-                     double* H, double* H2, double* bsc, hipStream_t s)
-{
-    const int nb = mpad / KT;
-    hipLaunchKernelGGL(k_sparse_h, dim3(nb * nb), dim3(256), 0, s, Binv, P, gp, bp, m, mpad, s2, H, H2, bsc);
 }
 
 void launch_sparse_transpose(const double* src, double* dst, int mpad, double scale, hipStream_t s)
@@ -3895,12 +3875,6 @@ void launch_trace_cross_z(const double* Xr, int nr, int rows_pad, const double* 
     const double* wts = is_ard(cf) ? (const double*)(cf.hd + 1) : nullptr;   // (the weights behind the hyper-scalars)
     hipLaunchKernelGGL(k_trace_cross_z_finish, dim3((unsigned)((sstride + 255) / 256)), dim3(256), 0, s, (const double*)part,
                        sstride, z.ranges, m, d, first ? 1 : 0, last ? 1 : 0, cf.h.ell_sq, wts, acc, out, hout);
-}
-
-void launch_sparse_finalize(const SparseFinal& f, const double* part_uf, size_t nb_uf, const double* part_uu, size_t nb_uu,
-                            int nl, double* out, double* hout, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_sparse_finalize, dim3(1), dim3(256), 0, s, f, part_uf, nb_uf, part_uu, nb_uu, nl, out, hout);
 }
 
 void launch_sparse_predict_finish(const double* Wt, const double* Vt, const double* cp, int mpad, int nt, double sf2,

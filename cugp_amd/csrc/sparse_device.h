@@ -1,11 +1,12 @@
 // sparse_device.h -- sparse variational GP regression on inducing points (cugp_sparse_*; Titsias 2009, DESIGN.md section
-// 25): every pass of it except the products on the MFMA tile (k_sparse_gram and the existing tile kernels: kernels.hip).
-// Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no inline assembly, no stamps, and no
+// 25): every pass of it except the products on the MFMA tile (k_sparse_gram and the existing tile kernels: kernels.hip)
+// and what reads the labels -- q, y'y, H and the final sums: sparse_targets_device.h, which the handle's own y runs with
+// p = 1.  Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no inline assembly, no stamps, and no
 // #ifdef around arithmetic -- the host check (tools/sparse_host_check.cpp) runs this text behind tools/host_emul.h under
 // -fsanitize=address,undefined.
 //
 // Include-point contract.  Included INSIDE namespace cugp, after these are declared -- the file declares none of them:
-//   kernels.h                      TILE, HyperScalars, KERNEL_*, SparseFinal
+//   kernels.h                      TILE, HyperScalars, KERNEL_*
 //   kernels.hip / host_emul.h      the d2 typedef and the device vocabulary (__device__, __global__, __shared__, threadIdx,
 //                                  blockIdx, gridDim, __syncthreads, __shfl_xor, __shfl_down)
 //   cov_device.h                   tri_index, wave_sum, KT, DC, col4, sqdist_4x4, DivBy, div_prepare, div_by, ard_weights,
@@ -63,78 +64,6 @@ __global__ __launch_bounds__(256) void k_sparse_form_b(const double* __restrict_
     const size_t off = (size_t)i * ld + j0;
 #pragma unroll
     for (int e = 0; e < 4; e++) Bm[off + e] = (i == j0 + e ? 1.0 : 0.0) + P[off + e] / s2;
-}
-
-// The slab's share of q = W^T y: part[sl * ld + col] = sum over the 128 rows r of slab sl of W[r][col] y[r] -- thread
-// (col, g) adds the rows g, g + 4, ... of the slab ascending, the four groups as (g0 + g1) + (g2 + g3).
-// W: [slabs * 128][ld], y: the chunk's labels (zero beyond its rows, as W is).  Grid: (ld / 64) * slabs.
-__global__ __launch_bounds__(256) void k_sparse_wty(const double* __restrict__ W, int ld, const double* __restrict__ y,
-                                                    double* __restrict__ part)
-{
-#pragma clang fp contract(off)
-    __shared__ double red[4][KT];
-    const int ncb = ld / KT, cb = blockIdx.x % ncb, sl = blockIdx.x / ncb;
-    const int t = threadIdx.x, col = cb * KT + (t & 63), g = t >> 6;
-    double acc = 0.0;
-    for (int j = 0; j < TILE / 4; j++) {
-        const int r = sl * TILE + g + 4 * j;
-        acc = acc + W[(size_t)r * ld + col] * y[r];
-    }
-    red[g][t & 63] = acc;
-    __syncthreads();
-    if (g == 0) part[(size_t)sl * ld + col] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-}
-
-// q = (first ? 0 : q) + part_0 + part_1 + ... in slab order; grid ld / 256
-__global__ __launch_bounds__(256) void k_sparse_wty_finish(const double* __restrict__ part, int slabs, int ld,
-                                                           double* __restrict__ q, int first)
-{
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= ld) return;
-    double s = first ? 0.0 : q[i];
-    for (int j = 0; j < slabs; j++) s = s + part[(size_t)j * ld + i];
-    q[i] = s;
-}
-
-// one workgroup: out[0] = y'y -- thread t adds the squares t, t + 256, ... ascending, the lanes by wave_sum, the four waves
-// as (w0 + w1) + (w2 + w3)
-__global__ __launch_bounds__(256) void k_sparse_yy(const double* __restrict__ y, int n, double* __restrict__ out)
-{
-#pragma clang fp contract(off)
-    __shared__ double red[4];
-    const int t = threadIdx.x;
-    double s = 0.0;
-    for (int i = t; i < n; i += 256) s = s + y[i] * y[i];
-    s = wave_sum(s);
-    if ((t & 63) == 0) red[t >> 6] = s;
-    __syncthreads();
-    if (t == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// H = I - B^-1 - gamma gamma^T and H2 = H - P / s2, full row-major ld x ld and zero beyond m, from the lower triangles of
-// B^-1 and P (entry (i, k) is read at (max, min)); gamma = gp / s2.  Workgroup 0 also writes bsc = bp / s2^2.
-// One 64x64 tile per workgroup, grid (ld / 64)^2.
-__global__ __launch_bounds__(256) void k_sparse_h(const double* __restrict__ Binv, const double* __restrict__ P,
-                                                  const double* __restrict__ gp, const double* __restrict__ bp, int m,
-                                                  int ld, double s2, double* __restrict__ H, double* __restrict__ H2,
-                                                  double* __restrict__ bsc)
-{
-#pragma clang fp contract(off)
-    const int nb = ld / KT, bi = blockIdx.x / nb, bj = blockIdx.x % nb, t = threadIdx.x;
-    if (blockIdx.x == 0)
-        for (int i = t; i < ld; i += 256) bsc[i] = i < m ? (bp[i] / s2) / s2 : 0.0;
-    for (int e = t; e < KT * KT; e += 256) {
-        const int i = bi * KT + (e >> 6), k = bj * KT + (e & 63);
-        double h = 0.0, h2 = 0.0;
-        if (i < m && k < m) {
-            const size_t src = i >= k ? (size_t)i * ld + k : (size_t)k * ld + i;
-            h = ((i == k ? 1.0 : 0.0) - Binv[src]) - (gp[i] / s2) * (gp[k] / s2);
-            h2 = h - P[src] / s2;
-        }
-        H[(size_t)i * ld + k] = h;
-        H2[(size_t)i * ld + k] = h2;
-    }
 }
 
 // dst[i][k] = src[k][i] * scale, ld x ld; one 64x64 tile per workgroup through LDS (rows padded to 65), grid (ld / 64)^2
@@ -270,72 +199,6 @@ __global__ __launch_bounds__(256) void k_trace_cross(const double* __restrict__ 
                                                      double* __restrict__ part, size_t pstride, size_t pofs)
 {
     trace_cross_body<ARD, KIND>(Xr, nr, Z, m, d, ld, h_arg, hd, G, yv, bv, part, pstride, pofs);
-}
-
-// One workgroup (f: kernels.h SparseFinal): F and (part_uf given) the nh = nl + 2 components of d(-F) / dtheta in the handle's order.
-//   columns   wave w takes the columns w, w + 4, ... of the trace partials: lane l adds the blocks l, l + 64, ...
-//             ascending, the lanes by wave_sum -- first of the rectangle (uf), then of the square (uu)
-//   scalars   tr P, sum_i (1 - [B^-1]_ii), c''c', gamma''gamma' over i < m and the log-determinant shares: thread t adds
-//             the entries t, t + 256, ... ascending, lanes by wave_sum, the four waves as (w0 + w1) + (w2 + w3)
-//   F    = ((((-N/2 log 2 pi - ld) - N/2 log s2) - y'y / (2 s2)) + c''c' / (2 s2^2)) - (N sf2 - tr P) / (2 s2),  ld = sum of the shares
-//   g_c  = -(S_uf,c + S_uu,c / 2)                          (c < nl)
-//   g_f  = -(2 (S_uf,nl + S_uu,nl / 2) - N sf2 / s2)
-//   g_n  = -(((sum_i (1 - [B^-1]_ii) - N) + (((y'y - c''c' / s2) + (N sf2 - tr P)) / s2)) - gamma''gamma' / s2^2)
-// out / hout (pinned): [0] F, [1 ..] the gradient.
-__global__ __launch_bounds__(256) void k_sparse_finalize(SparseFinal f, const double* __restrict__ part_uf, size_t nb_uf,
-                                                         const double* __restrict__ part_uu, size_t nb_uu, int nl,
-                                                         double* __restrict__ out, double* __restrict__ hout)
-{
-#pragma clang fp contract(off)
-    __shared__ double red[5][4];
-    __shared__ double tail;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    if (part_uf) {
-        for (int c = wave; c <= nl; c += 4) {
-            const double* cf = part_uf + (size_t)c * nb_uf;
-            const double* cu = part_uu + (size_t)c * nb_uu;
-            double a = 0.0, b = 0.0;
-            for (size_t i = lane; i < nb_uf; i += 64) a = a + cf[i];
-            for (size_t i = lane; i < nb_uu; i += 64) b = b + cu[i];
-            a = wave_sum(a);
-            b = wave_sum(b);
-            const double s = a + b / 2.0;
-            if (lane == 0 && c < nl) { out[1 + c] = -s; hout[1 + c] = -s; }
-            if (lane == 0 && c == nl) tail = s;
-        }
-    }
-    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int i = t; i < f.m; i += 256) {
-        const size_t dg = (size_t)i * f.ld + i;
-        v[0] = v[0] + f.P[dg];
-        v[1] = v[1] + (1.0 - f.Binv[dg]);
-        v[2] = v[2] + f.cp[i] * f.cp[i];
-        if (part_uf) v[3] = v[3] + f.gp[i] * f.gp[i];
-    }
-    for (int i = t; i < f.nt; i += 256) v[4] = v[4] + f.logdet[i];
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        v[k] = wave_sum(v[k]);
-        if (lane == 0) red[k][wave] = v[k];
-    }
-    __syncthreads();
-    if (t == 0) {
-        double r[5];
-#pragma unroll
-        for (int k = 0; k < 5; k++) r[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
-        const double trp = r[0], tb = r[1], cc = r[2], gg = r[3], ld = r[4];
-        const double yy = f.yy[0], nsf = f.n * f.sf2;
-        const double F = ((((-0.5 * f.n * 1.8378770664093453 - ld) - 0.5 * f.n * f.log_s2) - yy / (2.0 * f.s2))
-                          + cc / (2.0 * f.s2 * f.s2)) - (nsf - trp) / (2.0 * f.s2);
-        out[0] = F;
-        hout[0] = F;
-        if (part_uf) {
-            const double gf = -(2.0 * tail - nsf / f.s2);
-            const double gn = -(((tb - f.n) + (((yy - cc / f.s2) + (nsf - trp)) / f.s2)) - gg / (f.s2 * f.s2));
-            out[1 + nl] = gf; out[2 + nl] = gn;
-            hout[1 + nl] = gf; hout[2 + nl] = gn;
-        }
-    }
 }
 
 // Prediction at the test rows of one pass: Wt = k(Xt, Z) Lu^-T and Vt = Wt LB^-T ([>= nt][ld], zero beyond column m),

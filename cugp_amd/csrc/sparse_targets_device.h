@@ -1,14 +1,14 @@
-// sparse_targets_device.h -- multi-target regression over one set of inducing points (cugp_sparse_*_targets; DESIGN.md
-// section 27): the passes of the sparse model that depend on the targets.  Everything that costs O(N M^2) -- W_c, P, B and
-// its inverse, W_c R^T, both trace passes -- is shared by the p targets and runs as it does for one (sparse_device.h,
-// kernels.hip); only what is below reads Y.  Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no
+// sparse_targets_device.h -- the passes of the sparse model that depend on the labels: p targets over one set of inducing
+// points (cugp_sparse_*_targets), and the handle's own y, which is the case p = 1 (section 25).
+// Everything that costs O(N M^2) -- W_c, P, B and its inverse, W_c R^T, both trace passes -- is shared by the p targets
+// (sparse_device.h, kernels.hip); only what is below reads Y.  Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no
 // inline assembly and no #ifdef around arithmetic -- the host check (tools/sparse_targets_host_check.cpp) runs this text
 // behind tools/host_emul.h under -fsanitize=address,undefined.
 //
 // Include-point contract: sparse_device.h's (inside namespace cugp, behind kernels.h, the device vocabulary and
 // cov_device.h); SparseFinalTargets is kernels.h's.
 //
-// Y: [p][ystride] target-major, each row zero beyond its n rows up to the chunks' 128-row tiles, as the handle's own y.
+// Y: [p][ystride] target-major, each row zero beyond its n rows up to the chunks' 128-row tiles.
 // Q = [q_1 .. q_p], C' = Q LB^-T, Gamma' = C' LB^-1, Beta' = Gamma' Lu^-1: [>= p][ld] target-major, one row per target.
 //   H = p (I - B^-1) - sum_t gamma_t gamma_t^T   (gamma_t = gamma'_t / s2),   H2 = H - p P / s2,
 //   G_c^T = W_c R^T + sum_t y_t,c (beta'_t / s2^2)^T,   F = sum_t F_t
@@ -21,8 +21,8 @@ constexpr int SPT_GROUP = 8;     // targets per workgroup of k_sparse_wty_target
 constexpr int SPT_STAGE = 16;    // targets staged per round of k_sparse_h_targets and k_sparse_weights_targets
 
 // The slab's share of q_t = W^T y_t for the SPT_GROUP targets of a group, W read once for all of them:
-// part[(t * slabs + sl) * ld + col] = sum over the 128 rows r of slab sl of W[r][col] Y[t][r], each target's sum in
-// k_sparse_wty's order -- thread (col, g) adds the rows g, g + 4, ... ascending, the four groups as (g0 + g1) + (g2 + g3).
+// part[(t * slabs + sl) * ld + col] = sum over the 128 rows r of slab sl of W[r][col] Y[t][r], each target's sum in one
+// order -- thread (col, g) adds the rows g, g + 4, ... ascending, the four groups as (g0 + g1) + (g2 + g3).
 // The targets' slab values are staged through LDS; targets beyond p are neither read nor written.
 // W: [slabs * 128][ld], Y: the chunk's first row of target 0.  Grid: (ld / 64) * slabs * groups, groups = ceil(p / 8).
 __global__ __launch_bounds__(256) void k_sparse_wty_targets(const double* __restrict__ W, int ld, int slabs,
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void k_sparse_wty_targets_finish(const double*
     Q[(size_t)tt * ld + i] = s;
 }
 
-// out[t] = y_t'y_t, one workgroup per target in k_sparse_yy's order: thread v adds the squares v, v + 256, ... ascending,
+// out[t] = y_t'y_t, one workgroup per target: thread v adds the squares v, v + 256, ... ascending,
 // the lanes by wave_sum, the four waves as (w0 + w1) + (w2 + w3).  Grid: p.
 __global__ __launch_bounds__(256) void k_sparse_yy_targets(const double* __restrict__ Y, size_t ystride, int n,
                                                            double* __restrict__ out)
@@ -90,7 +90,8 @@ __global__ __launch_bounds__(256) void k_sparse_yy_targets(const double* __restr
 // H = p (I - B^-1) - sum_t gamma_t gamma_t^T (t ascending) and H2 = H - p (P / s2), full row-major ld x ld and zero
 // beyond m, from the lower triangles of B^-1 and P (entry (i, k) is read at (max, min)); gamma_t = Gm[t] / s2, its two
 // 64-entry pieces of a tile staged through LDS, SPT_STAGE targets per round.  Every workgroup also writes its share of
-// Bs[t][j] = (Bt[t][j] / s2) / s2 (zero beyond m), t < p.  With p = 1 every entry has k_sparse_h's bits.
+// Bs[t][j] = (Bt[t][j] / s2) / s2 (zero beyond m), t < p.  With p = 1 the factor p is an exact 1.0: H = (I - B^-1) - gamma
+// gamma^T and H2 = H - P / s2, as section 25 writes them.
 // One 64x64 tile per workgroup in four passes of 16 rows -- thread v holds the entries (16 q + v / 64 + 4 a, v % 64), a < 4,
 // of pass q, and every pass stages its rounds again: four divisions in flight, not sixteen --, grid (ld / 64)^2.
 __global__ __launch_bounds__(256) void k_sparse_h_targets(const double* __restrict__ Binv, const double* __restrict__ P,
@@ -205,8 +206,8 @@ __global__ __launch_bounds__(256) void k_sparse_scale_targets(const double* __re
 
 // One workgroup (f: kernels.h SparseFinalTargets): F = sum_t F_t, (part_uf given) the nh = nl + 2 components of
 // d(-F) / dtheta in the handle's order, and every F_t.
-//   columns   k_sparse_finalize's: wave w takes the columns w, w + 4, ... of the trace partials, lane l the blocks l,
-//             l + 64, ... ascending, the lanes by wave_sum -- first of the rectangle (uf), then of the square (uu)
+//   columns   wave w takes the columns w, w + 4, ... of the trace partials, lane l the blocks l, l + 64, ... ascending,
+//             the lanes by wave_sum -- first of the rectangle (uf), then of the square (uu)
 //   scalars   tr P, sum_i (1 - [B^-1]_ii) and the log-determinant shares; then target after target c'_t'c'_t and
 //             gamma'_t'gamma'_t over i < m: thread v adds the entries v, v + 256, ... ascending, lanes by wave_sum, the
 //             four waves as (w0 + w1) + (w2 + w3)

@@ -30,6 +30,9 @@ What the accuracy cases cover (truth_sparse.CASES: family, N, M, d, chunk_rows):
   se 300 / 16 / 3 / 0               the model of the two-pass prediction (tests/test_gpu_sparse_wide.py)
 """
 import ctypes as C
+import json
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -38,6 +41,11 @@ import truth
 import truth_sparse as ts
 from accuracy import Report
 from cugp_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import sparse_bits_record  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 extended = pytest.mark.skipif(not truth.EXTENDED, reason="numpy.longdouble is not an extended-precision type here")
@@ -287,3 +295,21 @@ def test_refusals(gp_mod):
     assert same_bits([nodata.bound()], [s.bound()])
     for e in (s, a, nodata, noz):
         e.close()
+
+
+# ------------------------------------------------------------------ 9. the recorded bits
+@pytest.mark.parametrize("model", sorted(sparse_bits_record.MODELS))
+def test_own_y_and_targets_keep_the_recorded_bits(model):
+    """tests/golden/sparse_own_bits.json holds the fp64 words of bound, bound_grad, bound_grad_z, predict, predict_joint and
+    predict_grad for the handle's own y on two small models, and of bound_grad_targets with p = 1 and p = 3 on the first
+    (tools/sparse_bits_record.py: the models, and what each reaches), recorded on an MI355X at the last commit that had a
+    kernel family of its own for the handle's y.  The one family that serves both sides now gives every one of these words:
+    equality to the bit, no tolerance."""
+    with open(os.path.join(ROOT, "tests", "golden", "sparse_own_bits.json")) as f:
+        want = json.load(f)[model]
+    got = sparse_bits_record.results(model)
+    assert sorted(got) == sorted(want)
+    differ = {k: sum(a != b for a, b in zip(got[k], want[k])) for k in want if got[k] != want[k]}
+    for k in sorted(want):
+        print("BITS %s %-28s %4d words  %s" % (model, k, len(want[k]), "same" if k not in differ else "%d DIFFER" % differ[k]))
+    assert all(len(got[k]) == len(want[k]) for k in want) and not differ, differ

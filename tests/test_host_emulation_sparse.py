@@ -1,8 +1,8 @@
-"""The host check of the sparse-GP kernels as a test, without a GPU: cugp_amd/csrc/sparse_device.h -- the text kernels.hip
-compiles for gfx950 -- runs behind tools/host_emul.h as 256 host threads per workgroup in a stand-alone program built with
+"""The host check of the sparse-GP kernels as a test, without a GPU: cugp_amd/csrc/sparse_device.h and, as the handle's own y
+runs it (p = 1), sparse_targets_device.h -- the text kernels.hip compiles for gfx950 -- run behind tools/host_emul.h as 256 host threads per workgroup in a stand-alone program built with
 -fsanitize=address,undefined (tools/sparse_host_check.cpp; nothing is loaded into Python, nothing preloaded), on exact-size
 heap buffers with NaN where the kernels must not read, and is compared with numpy by the script's own run(): the trace sums
-of k_trace_cross<ARD, KIND> on a ragged chunk and on the square, k_sparse_finalize's results, and the small passes around
+of k_trace_cross<ARD, KIND> on a ragged chunk and on the square, k_sparse_finalize_targets' results, and the small passes around
 the products.  The program is built once per module; the cases are the script's whole list (chunks of 44, 128, 1, 44, 1,
 200 and 257 rows; M = 65, 128, 130, 64, 200 and 260 -- mpad 384 with five Gram partials --; SE, Matern 3/2, SE-ARD with two feature chunks, Matern-5/2-ARD).  A case fails on a
 non-zero exit, on anything a sanitizer writes to stderr, and on a result beyond its tolerance."""

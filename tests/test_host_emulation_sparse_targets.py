@@ -3,8 +3,8 @@ text kernels.hip compiles for gfx950 -- runs behind tools/host_emul.h as 256 hos
 program built with -fsanitize=address,undefined (tools/sparse_targets_host_check.cpp; nothing is loaded into Python, nothing
 preloaded), on exact-size heap buffers with NaN where the kernels must mask (rows beyond the chunk's count, columns beyond M;
 the targets' buffers end at target p, so a read beyond it in the last group is a sanitizer report), and is compared BIT FOR
-BIT with plain numpy loops in the kernels' stated order by the script's own run().  The program itself holds every target's
-slab shares to k_sparse_wty's bits, every y_t'y_t to k_sparse_yy's and, with p = 1, H, H2 and Bs to k_sparse_h's.  The program
+BIT with plain numpy loops in the kernels' stated order by the script's own run(): every target's slab shares, y_t'y_t and,
+with p = 1 too, H, H2 and Bs in the one order that the handle's own y has as well.  The program
 is built once per module; the cases are the script's whole list.  A case fails on a non-zero exit, on anything a sanitizer
 writes to stderr, and on any differing bit."""
 import os

@@ -15,7 +15,7 @@ With Kuu = k(Z, Z) + eps I, Kuf = k(Z, X), Qff = Kfu Kuu^-1 Kuf, s2 = exp(2 thet
              and derivative matrices -- what GPflow's SGPR does --, over the data as given and truth.permutations.
   stand-in   `standin`: the library's formulation in fp64 on other arithmetic: explicit triangular inverses, the data in
              cugp_sparse_plan's chunks, the Gram partials of a chunk added in plan order, q through 128-row slabs, the
-             gradient through H, R = Lu^-T H / s2 and 2 G_uu = Lu^-T H2 Lu^-1 -- k_sparse_finalize's final formulas.
+             gradient through H, R = Lu^-T H / s2 and 2 G_uu = Lu^-T H2 Lu^-1 -- k_sparse_finalize_targets' final formulas at p = 1.
   errors     F relative; every gradient component relative to max|g| (truth.errors_ll_grad's quantities); the mean the
              largest absolute error; the variance the largest absolute error, floored at 4 ulp of sf2 + s2
   bound      F_SPARSE[family] max(yardstick, 4 ulp of the quantity's scale); F_SPARSE is fixed below from the stand-in's

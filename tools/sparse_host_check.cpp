@@ -1,9 +1,10 @@
 // Host check of the sparse-GP kernels (tools/sparse_host_check.py builds and runs this; no GPU).  The kernels' own text --
-// cugp_amd/csrc/sparse_device.h with cov_device.h, the headers kernels.hip includes -- runs behind the emulation shim
-// tools/host_emul.h, one workgroup at a time as 256 host threads in lock step: the rectangular gradient pass
-// k_trace_cross<ARD, KIND> over one chunk (with the rank-one part, its partials behind an offset of 3 blocks) and over the
-// square (Z, Z), k_sparse_finalize on both, and the small passes around the products (k_sparse_gram_finish,
-// k_sparse_form_b, k_sparse_wty with its finish, k_sparse_yy, k_sparse_h, k_sparse_transpose, k_sparse_predict_finish).
+// cugp_amd/csrc/sparse_device.h and sparse_targets_device.h with cov_device.h, the headers kernels.hip includes -- runs
+// behind the emulation shim tools/host_emul.h, one workgroup at a time as 256 host threads in lock step: the rectangular
+// gradient pass k_trace_cross<ARD, KIND> over one chunk (with the rank-one part, its partials behind an offset of 3
+// blocks) and over the square (Z, Z), and as the handle's own y runs them, with p = 1: k_sparse_finalize_targets on both
+// and the small passes around the products (k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty_targets with its finish,
+// k_sparse_yy_targets, k_sparse_h_targets, k_sparse_transpose, k_sparse_predict_finish).
 // The MFMA product k_sparse_gram is not emulated: its partial tiles are an input.  Every buffer is a heap block of exactly
 // the size the library gives it, so a build with -fsanitize=address,undefined sees any access beyond one; the script puts
 // NaN wherever a kernel must not read.  A stand-alone program: the sanitizer is linked in, nothing is preloaded.
@@ -11,6 +12,7 @@
 namespace cugp {
 #include "cov_device.h"
 #include "sparse_device.h"
+#include "sparse_targets_device.h"
 }
 using namespace cugp;
 
@@ -39,7 +41,7 @@ int main(int argc, char** argv)
     // input: ints nr m d ld rows_pad kind ard nscr, then doubles: ell_sq sf2 sn2 w[d] | n s2 log_s2 yy | Xr[nr*d] Z[m*d]
     //        G[rows_pad*ld] yv[rows_pad] bv[ld] Guu[ld*ld] P[ld*ld] Binv[ld*ld] cp[ld] gp[ld] bp[ld] logdet[ld/128]
     //        scr[nscr*ld*ld]
-    // output: part_uf[(nl+1)*(nb_uf+3)] part_uu[(nl+1)*nb_uu] row[1+nh] rowF[1] Pacc[ld*ld] Bm[ld*ld] q[ld] yy[1] H[ld*ld]
+    // output: part_uf[(nl+1)*(nb_uf+3)] part_uu[(nl+1)*nb_uu] row[1+nh] (its F_1 slot is compared here) rowF[1] Pacc[ld*ld] Bm[ld*ld] q[ld] yy[1] H[ld*ld]
     //         H2[ld*ld] bsc[ld] Gt[ld*ld] mean[nr] var[nr]
     if (argc < 3) return 2;
     FILE* f = fopen(argv[1], "rb");
@@ -61,19 +63,20 @@ int main(int argc, char** argv)
     const size_t ps_uf = (size_t)nb_uf + 3;
     auto nan_block = [](size_t cnt) { double* p = (double*)malloc(cnt * 8 ? cnt * 8 : 8); for (size_t i = 0; i < cnt; i++) p[i] = NAN; return p; };
     double *part_uf = nan_block((size_t)(nl + 1) * ps_uf), *part_uu = nan_block((size_t)(nl + 1) * nb_uu);
-    double *row = nan_block(1 + nh), *hrow = nan_block(1 + nh), *rowF = nan_block(1 + nh), *hrowF = nan_block(1 + nh);
+    double *row = nan_block(2 + nh), *hrow = nan_block(2 + nh), *rowF = nan_block(2 + nh), *hrowF = nan_block(2 + nh);
 
     trace_any(sel, nb_uf, Xr, nr, Z, m, d, ld, h, hd, G, yv, bv, part_uf, ps_uf, 3);
     trace_any(sel, nb_uu, Z, m, Z, m, d, ld, h, hd, Guu, nullptr, nullptr, part_uu, nb_uu, 0);
-    const SparseFinal fin{P, Binv, cp, gp, logdet, sc + 3, m, ld, ntl, sc[0], h.signal_var, sc[1], sc[2]};
+    const SparseFinalTargets fin{P, Binv, cp, gp, logdet, sc + 3, m, ld, ntl, 1, sc[0], h.signal_var, sc[1], sc[2]};
     // (the finalize of the check sums the rectangle's blocks behind the offset: its columns start 3 entries in)
     double* uf = nan_block((size_t)(nl + 1) * nb_uf);
     for (int c = 0; c <= nl; c++) memcpy(uf + (size_t)c * nb_uf, part_uf + (size_t)c * ps_uf + 3, (size_t)nb_uf * 8);
-    launch(1, [&] { k_sparse_finalize(fin, uf, nb_uf, part_uu, nb_uu, nl, row, hrow); });
-    launch(1, [&] { k_sparse_finalize(fin, nullptr, 0, nullptr, 0, nl, rowF, hrowF); });
-    for (int i = 0; i < 1 + nh; i++)
+    launch(1, [&] { k_sparse_finalize_targets(fin, uf, nb_uf, part_uu, nb_uu, nl, row, hrow); });
+    launch(1, [&] { k_sparse_finalize_targets(fin, nullptr, 0, nullptr, 0, nl, rowF, hrowF); });
+    for (int i = 0; i < 2 + nh; i++)
         if (memcmp(&row[i], &hrow[i], 8) != 0) return 4;  // the device row and its pinned copy carry the same bits
     if (memcmp(&rowF[0], &hrowF[0], 8) != 0 || memcmp(&rowF[0], &row[0], 8) != 0) return 4;
+    if (memcmp(&row[1 + nh], &row[0], 8) != 0 || memcmp(&rowF[1 + nh], &row[0], 8) != 0) return 4;   // F_1, the one target's share, is F
 
     double *Pacc = (double*)malloc(ll * 8), *Bm = nan_block(ll), *q = nan_block(ld), *qpart = nan_block((size_t)(rows_pad / TILE) * ld);
     memcpy(Pacc, P, ll * 8);
@@ -84,12 +87,12 @@ int main(int argc, char** argv)
     double *Wz = (double*)malloc((size_t)rows_pad * ld * 8), *yz = (double*)malloc((size_t)rows_pad * 8);
     for (size_t i = 0; i < (size_t)rows_pad * ld; i++) Wz[i] = std::isnan(G[i]) ? 0.0 : G[i];
     for (int i = 0; i < rows_pad; i++) yz[i] = std::isnan(yv[i]) ? 0.0 : yv[i];
-    launch((ld / KT) * (rows_pad / TILE), [&] { k_sparse_wty(Wz, ld, yz, qpart); });
-    launch((ld + 255) / 256, [&] { k_sparse_wty_finish(qpart, rows_pad / TILE, ld, q, 1); });
+    launch((ld / KT) * (rows_pad / TILE), [&] { k_sparse_wty_targets(Wz, ld, rows_pad / TILE, yz, (size_t)rows_pad, 1, qpart); });
+    launch((ld + 255) / 256, [&] { k_sparse_wty_targets_finish(qpart, rows_pad / TILE, ld, 1, q, 1); });
     double* yy = nan_block(1);
-    launch(1, [&] { k_sparse_yy(yv, nr, yy); });
+    launch(1, [&] { k_sparse_yy_targets(yv, (size_t)rows_pad, nr, yy); });
     double *H = nan_block(ll), *H2 = nan_block(ll), *bsc = nan_block(ld), *Gt = nan_block(ll);
-    launch(nb_uu, [&] { k_sparse_h(Binv, P, gp, bp, m, ld, sc[1], H, H2, bsc); });
+    launch(nb_uu, [&] { k_sparse_h_targets(Binv, P, gp, bp, 1, m, ld, sc[1], H, H2, bsc); });
     launch(nb_uu, [&] { k_sparse_transpose(Guu, Gt, ld, 0.5); });
     double *mean = nan_block(nr), *var = nan_block(nr);
     launch((nr + 3) / 4, [&] { k_sparse_predict_finish(Wz, Wz, cp, ld, nr, h.signal_var, sc[1], sc[1], mean, var); });

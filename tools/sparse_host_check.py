@@ -1,16 +1,17 @@
-"""The sparse-GP kernels of cugp_amd/csrc/sparse_device.h on the CPU, without a GPU: the rectangular gradient pass
-k_trace_cross<ARD, KIND> (one chunk with the rank-one part; the square (Z, Z)), k_sparse_finalize, and the small passes
-around the products (k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty and its finish, k_sparse_yy, k_sparse_h,
+"""The sparse-GP kernels of cugp_amd/csrc/sparse_device.h on the CPU, without a GPU, and those of sparse_targets_device.h
+as the handle's own y runs them (p = 1): the rectangular gradient pass k_trace_cross<ARD, KIND> (one chunk with the
+rank-one part; the square (Z, Z)), k_sparse_finalize_targets, and the small passes around the products
+(k_sparse_gram_finish, k_sparse_form_b, k_sparse_wty_targets and its finish, k_sparse_yy_targets, k_sparse_h_targets,
 k_sparse_transpose, k_sparse_predict_finish) -- the text kernels.hip includes -- in a lock-step host emulation
 (tools/sparse_host_check.cpp) built with -fsanitize=address,undefined.  The MFMA product k_sparse_gram is not emulated.
 The chunk is the LAST chunk of a case of tests/truth_sparse.py (ragged: 44, 1 or 128 rows of a 128-row pad; 257 rows of a
-384-row pad at mpad 384, where k_sparse_gram_finish adds five partial tiles, k_sparse_h and k_sparse_transpose run 6 x 6
+384-row pad at mpad 384, where k_sparse_gram_finish adds five partial tiles, k_sparse_h_targets and k_sparse_transpose run 6 x 6
 blocks and k_sparse_predict_finish three test tiles; chunk_rows 0 is the library's 16384), its weight matrix random; rows
 beyond the chunk and columns beyond M are NaN in every input a kernel must mask, and so are the strict upper 128-tiles of P
 and B^-1: a missing mask shows as NaN, an access beyond a buffer as a sanitizer report.  Compared with numpy on the same
 inputs:
   trace sums  per column, the blocks' partial sums added in longdouble against sum w o dK: 1e-13 of sum |w o dK|
-  results     F and the nh gradient components against k_sparse_finalize's formulas in numpy: 1e-13 of their scale
+  results     F and the nh gradient components against k_sparse_finalize_targets' formulas at p = 1 in numpy: 1e-13 of their scale
   small       P, B, q, y'y, H, H2, beta / s2^2, the transpose, mean and var: 4 ulp of the largest entry (sums: 1e-13)
 
     python tools/sparse_host_check.py          # builds into a temporary directory; about a minute
@@ -99,7 +100,7 @@ def run(exe, tmp, name, rows, nscr=3):
     s_uf, s_uu = puf[:, 3:].astype(LDT).sum(1), puu.astype(LDT).sum(1)
     et = max(max(float(abs(s - wv)) / mg for s, wv, mg in zip(s_uf, want_uf, mag_uf)),
              max(float(abs(s - wv)) / mg for s, wv, mg in zip(s_uu, want_uu, mag_uu)))
-    # k_sparse_finalize's formulas on the kernel's own sums
+    # k_sparse_finalize_targets' formulas at p = 1 on the kernel's own sums
     N = float(len(y))
     S = np.asarray(s_uf + s_uu / 2, dtype=np.float64)
     Pd, Bd = np.diag(P)[:m], np.diag(Binv)[:m]

@@ -6,8 +6,8 @@ shape (p targets, m inducing points padded to ld, nr rows of a rows_pad chunk); 
 beyond the chunk's count, columns beyond m, the strict upper 128-tiles of P and B^-1 --, and the targets' buffers hold
 exactly p rows, so a read of a target beyond p in the last group is a sanitizer report.  Every result is compared BIT FOR BIT
 with plain numpy loops in the kernels' stated order (numpy's elementwise products and sums round once each, as the kernels
-do under fp contract(off)); the program itself compares every target's slab shares with k_sparse_wty, every y_t'y_t with
-k_sparse_yy and, with p = 1, H, H2 and Bs with k_sparse_h, to the bit.
+do under fp contract(off)): per target the slab shares (wpart), y_t'y_t (wyy) and H (h) are the sums the handle's own y
+has, which runs these kernels with p = 1 (tools/sparse_host_check.py holds that case against its own numpy forms).
 
     python tools/sparse_targets_host_check.py          # builds into a temporary directory; about a minute
 """
