@@ -83,7 +83,10 @@ def test_accuracy(gp_mod, oracle, family, name, m):
       se n257_d3 m=129       a third 64-row target tile of the products, mpad > 128
       matern32 n65 m=17, matern52 n300_d17 m=5 (two feature chunks), ard n257_d3 m=5
       ard n300_d17 m=3       two feature chunks in the ARD second sweep
-      se n1300_d6 m=2        hand-over blocks of the inverse; the inverse streams on and off"""
+      se n1300_d6 m=2        hand-over blocks of the inverse; the inverse streams on and off
+      se n1 m=2, n2 m=3, n2 m=129, n63 m=17, matern32 n63 m=5, ard n63_d2 m=3
+                             below one 64-row build tile: the lower tiles of the outer product all padding, more targets
+                             than rows, two target tiles over two rows"""
     c = tt.case(oracle, family, name, m)
     cov = c["cov"]
     rep = Report("%s/%s/m%d" % (family, name, m), cov)
@@ -115,6 +118,7 @@ def test_wide_accuracy(gp_mod, oracle, case):
                                        and only the means are held -- every column of them (tests/truth_targets.py)
       ard n257_d3 m=5 nt=200           a ragged second 128-row tile on an ARD handle
       matern52 n300_d17 m=17 nt=200    two feature chunks through k_cross at width
+      se n2 m=3 nt=129                 two test tiles over two training rows
     The last test point but one is a training row.  LL, the gradient and LL_t do not depend on nt and are held again."""
     family, name, m, nt, subset = case
     c = tt.wide_case(oracle, *case)
@@ -187,7 +191,7 @@ def test_targets_on_a_grown_handle(gp_mod, oracle):
 
 # ------------------------------------------------------------------ 2. one target
 @extended
-@pytest.mark.parametrize("family, name", [("se", "n257_d3"), ("ard", "n257_d3"), ("matern52", "n65")])
+@pytest.mark.parametrize("family, name", [("se", "n257_d3"), ("ard", "n257_d3"), ("matern52", "n65"), ("se", "n2")])
 def test_one_target_is_the_handles_own_problem(gp_mod, oracle, family, name):
     """Y = y: log|K| is the handle's own, bit for bit; LL, the gradient and the mean meet the bound that cugp_loglik_grad
     and cugp_predict meet at that case."""

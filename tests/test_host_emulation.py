@@ -21,10 +21,13 @@ import predict_grad_host_check  # noqa: E402
 pytestmark = pytest.mark.skipif(not os.path.exists(host_check.CLANG), reason="no host compiler at " + host_check.CLANG)
 
 PREDICT_GRAD = [("se", "n2", None, 1), ("se", "n64", None, 1), ("se", "n65", None, 1), ("se", "n65", None, 0),
-                ("matern32", "n65", None, 1), ("ard", "n257_d3_shift", None, 1), ("matern52", "n300_d17", 129, 1)]
+                ("matern32", "n65", None, 1), ("ard", "n257_d3_shift", None, 1), ("matern52", "n300_d17", 129, 1),
+                ("matern32", "n2", None, 1), ("ard", "n2_d2", None, 1), ("se", "n63", 1, 1)]
 ARD_MATERN = [("trace", "n65_d2", 1, None, 1), ("trace", "n65_d2", 2, None, 1), ("trace", "n257_d3_shift", 2, None, 1),
               ("grad", "n65_d2", 1, None, 1), ("grad", "n65_d2", 2, None, 0), ("grad", "n257_d3_shift", 2, None, 1),
-              ("grad", "n257_d3", 2, 129, 1)]
+              ("grad", "n257_d3", 2, 129, 1),
+              ("trace", "n2_d2", 1, None, 1), ("trace", "n63_d2", 2, None, 1), ("grad", "n2_d2", 2, None, 1),
+              ("grad", "n63_d2", 1, None, 1)]
 APPEND = list(append_host_check.CASES)
 CHECKS = {"predict_grad": predict_grad_host_check, "ard_matern": ard_matern_host_check, "append": append_host_check}
 ident = lambda case: "-".join(str(v) for v in case)

@@ -5,6 +5,7 @@ cov_device.h -- the text kernels.hip compiles for gfx950 -- behind tools/host_em
   grad    three experts of one padded size with n = 64, 64, 66 (1, 1 and 2 training tiles), nt = 65, d = 3 and 17, with and
           without V, SE-ARD / Matern-5/2-ARD / isotropic SE (d = 3 also with the two-tile expert first): every expert's slot carries the bits of the existing
           single-expert kernels run in the same emulation; NaN wherever the kernels must not read or write
+          and at d = 3 three experts of 1, 2 and 63 rows (below one 64-row build tile) in one padded size
   reduce  k_poe_reduce_grad against cugp_poe_combine / cugp_poe_finish / cugp_poe_combine_grad, K = 1, 3, 5, world = 1, 2,
           nt = 1 and 257, all five modes, bit for bit in all four outputs
 

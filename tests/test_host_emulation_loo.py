@@ -3,8 +3,8 @@ compiles for gfx950 -- runs behind tools/host_emul.h as 256 host threads per wor
 -fsanitize=address,undefined (tools/loo_host_check.cpp; nothing is loaded into Python, nothing preloaded), on exact-size
 heap buffers with NaN where the kernels must not read, and is compared with numpy by the script's own run(): per-point
 outputs, B and L_LOO to 4 ulp of scale, b and the gradient to 1e-13, the padding exact zeros.  The program is built once
-per module; the cases are the script's whole list (npad 128, 256, 384; n = 65, 128, 129, 257, 300; SE, Matern 5/2, SE-ARD,
-Matern-3/2-ARD).  A case fails on a non-zero exit, on anything a sanitizer writes to stderr, and on a result beyond its
+per module; the cases are the script's whole list (npad 128, 256, 384; n = 1, 2, 63, 64, 65, 128, 129, 257, 300; SE,
+Matern 5/2, SE-ARD, Matern-3/2-ARD).  A case fails on a non-zero exit, on anything a sanitizer writes to stderr, and on a result beyond its
 tolerance."""
 import os
 import sys
@@ -32,7 +32,9 @@ def test_the_list_covers_the_sizes_and_families():
     for family, name, rows in loo_host_check.CASES:
         n = rows if rows is not None else len(tl.inputs(family, name)[1])
         sizes.add((n, (n + 127) // 128 * 128))
-    assert {n for n, _ in sizes} == {65, 128, 129, 257, 300}
+    assert {n for n, _ in sizes} == {1, 2, 63, 64, 65, 128, 129, 257, 300}
+    small = {(f, rows) for f, _, rows in loo_host_check.CASES if rows is not None and rows <= 64}
+    assert small == {("se", 1), ("se", 2), ("se", 63), ("se", 64), ("ard", 2), ("ard", 63), ("matern52", 2), ("matern52", 63)}
     assert {p for _, p in sizes} == {128, 256, 384}
     assert {f for f, _, _ in loo_host_check.CASES} == {"se", "matern52", "ard", "matern32_ard"}
 

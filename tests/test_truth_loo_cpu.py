@@ -84,7 +84,9 @@ def table(oracle):
 def test_case_list():
     assert tl.CASES == (("se", "n65"), ("se", "n128"), ("se", "n257_d3"), ("se", "n384_cond1e6"), ("matern32", "n65"),
                         ("matern52", "n300_d17"), ("ard", "n257_d3"), ("ard", "n300_d17"), ("matern52_ard", "n257_d3"),
-                        ("se", "n1300_d6"))
+                        ("se", "n1300_d6"),
+                        ("se", "n1"), ("se", "n2"), ("se", "n63"), ("se", "n64"), ("matern32", "n63"), ("ard", "n1_d2"),
+                        ("ard", "n2_d2"), ("ard", "n63_d2"), ("matern52_ard", "n63_d2"))
     assert set(tl.F_LOO) == {f for f, _ in tl.CASES}
 
 

@@ -75,9 +75,11 @@ def table(oracle):
 
 
 def test_case_list():
-    assert tpg.CASES == {"se": ("n2", "n63", "n64", "n65", "n257_d3", "n300_d17", "n515_d33", "n384_cond1e6"),
-                         "matern32": ("n65", "n257_d3"), "matern52": ("n300_d17", "n384_cond1e6"),
-                         "ard": ("n65_d2", "n257_d3", "n300_d17", "n257_d3_shift", "n384_cond1e6")}
+    assert tpg.CASES == {"se": ("n1", "n2", "n63", "n64", "n65", "n257_d3", "n300_d17", "n515_d33", "n384_cond1e6"),
+                         "matern32": ("n1", "n2", "n63", "n64", "n65", "n257_d3"),
+                         "matern52": ("n1", "n63", "n300_d17", "n384_cond1e6"),
+                         "ard": ("n1_d2", "n2_d2", "n63_d2", "n64_d2", "n65_d2", "n257_d3", "n300_d17", "n257_d3_shift",
+                                 "n384_cond1e6")}
     assert tpg.F_GRAD is None
 
 

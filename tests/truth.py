@@ -544,6 +544,7 @@ HP_A = [0.9, 0.2, -1.0]
 
 # name -> (n, d, hyper-parameters, box half-width of synth: chosen so that K is far from diagonal)
 LIVE_CASES = {
+    "n1": (1, 2, HP_DEFAULT, 4.0),                   # one row: every off-diagonal sum is empty
     "n2": (2, 2, HP_DEFAULT, 4.0),
     "n63": (63, 2, HP_DEFAULT, 4.0),                 # below / at / over one 64-row build tile; one 128 MFMA tile,
     "n64": (64, 2, HP_DEFAULT, 4.0),                 # identity padding
@@ -556,11 +557,15 @@ LIVE_CASES = {
     "n1025_dense": (1025, 10, HP_DENSE, 10.0),       # nine tiles; overlap on and off
     "n1300_d6": (1300, 6, HP_A, 2.5),                # hand-over blocks of the inverse
 }
-JOINT_CASES = ("n2", "n63", "n64", "n1025_dense", "n1300_d6")     # the three smallest and the two largest
-MATERN_CASES = tuple(list(LIVE_CASES)[list(LIVE_CASES).index("n65"):])     # LIVE_CASES from n65 up, both kinds
+JOINT_CASES = ("n1", "n2", "n63", "n64", "n1025_dense", "n1300_d6")     # the four smallest and the two largest
+MATERN_CASES = tuple(LIVE_CASES)                     # every live case, both kinds
 
 # name -> (n, d, theta_l, theta_f, theta_n, box half-width of synth, shift added to X and Xt)
 ARD_CASES = {
+    "n1_d2": (1, 2, [0.5, 1.2], 0.5, 0.5, 4.0, 0.0),                                    # below / at one 64-row build tile,
+    "n2_d2": (2, 2, [0.5, 1.2], 0.5, 0.5, 4.0, 0.0),                                    # n65_d2's parameters
+    "n63_d2": (63, 2, [0.5, 1.2], 0.5, 0.5, 4.0, 0.0),
+    "n64_d2": (64, 2, [0.5, 1.2], 0.5, 0.5, 4.0, 0.0),
     "n65_d2": (65, 2, [0.5, 1.2], 0.5, 0.5, 4.0, 0.0),
     "n257_d3": (257, 3, [0.9, 0.3, 1.6], 0.2, -1.0, 4.0, 0.0),
     "n300_d17": (300, 17, np.linspace(0.7, 1.9, 17).tolist(), 0.3, -0.8, 1.8, 0.0),      # two feature chunks

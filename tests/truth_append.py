@@ -35,6 +35,11 @@ CASES = (
     ("ard", "n384_cond1e6", 300, (1,) * 84),
     ("matern52", "n300_d17", 128, (128, 44)),
     ("matern32", "n384_cond1e6", 300, (84,)),
+    ("matern32", "n2", 1, (1,)),                    # below one build tile, the other families
+    ("ard", "n2_d2", 1, (1,)),
+    ("ard", "n65_d2", 63, (1, 1)),
+    ("matern52", "n65", 63, (1, 1)),
+    ("se", "n64", 1, (62, 1)),                      # from one row up to a full build tile
 )
 
 # family -> factor.  The larger of the family's own factor and truth.factor_rule of the largest stand-in ratio over the

@@ -43,6 +43,15 @@ CASES = (
     ("ard", "n300_d17"),
     ("matern52_ard", "n257_d3"),
     ("se", "n1300_d6"),
+    ("se", "n1"),                     # below / at one 64-row build tile: whole tiles of the padded matrix are padding
+    ("se", "n2"),
+    ("se", "n63"),
+    ("se", "n64"),
+    ("matern32", "n63"),
+    ("ard", "n1_d2"),
+    ("ard", "n2_d2"),
+    ("ard", "n63_d2"),
+    ("matern52_ard", "n63_d2"),
 )
 POINT_QUANTITIES = ("mu", "var", "logp")
 
@@ -110,7 +119,7 @@ def truth_of(t, y):
     W = fused(t.Kinv, t.alpha, product=lambda B: truth._mm(B, np.ascontiguousarray(B.T)))
     _, terms = t.cov.train(t.X)
     grad = np.array(terms(W) + (t.sn2 * np.trace(W),), dtype=LD)
-    return dict(mu=mu, var=var, logp=logp, ll=ll, grad=grad)
+    return dict(mu=mu, var=var, logp=logp, ll=ll, grad=grad, y=yl)
 
 
 def brute(X, y, cov):
@@ -213,9 +222,14 @@ def quantities(cov):
 
 
 def floors(cov, tt):
-    """4 ulp of each quantity's scale: 1 for L_LOO and the gradient (relative errors), max|mu|, sf2 + sn2, max|logp|."""
+    """4 ulp of each quantity's scale: 1 for L_LOO and the gradient (relative errors), max|mu|, sf2 + sn2, max|logp|.
+    At n = 1 every mu is exactly 0 (nothing is left to predict from): its scale is then that of the cancelling
+    y - alpha / kappa, max|y|."""
     fl = {q: U4 for q in cov.quantities[:4]}
-    fl.update(mu=U4 * float(np.max(np.abs(tt["mu"]))), var=U4 * float(cov.sf2 + cov.sn2),
+    mu_scale = float(np.max(np.abs(tt["mu"])))
+    if mu_scale == 0:
+        mu_scale = float(np.max(np.abs(tt["y"])))
+    fl.update(mu=U4 * mu_scale, var=U4 * float(cov.sf2 + cov.sn2),
               logp=U4 * float(np.max(np.abs(tt["logp"]))))
     return fl
 

@@ -74,6 +74,12 @@ def inputs(name, nt):
     return X, y, np.ascontiguousarray(Xt), descriptor(family), K
 
 
+def rows_of(c):
+    """The experts' [(offset, rows)] of a case: its own "parts" (explicit rows: tests/truth_small_bcm.py), else the
+    reference's split of len(y) into K."""
+    return c["parts"] if "parts" in c else truth.bcm_rows(len(c["y"]), c["K"])
+
+
 def combine(m, v, mode, sf2, half=True, prior=True):
     """The rule `mode` on per-expert latent means m[K][nt] and variances v[K][nt], in the arrays' own precision, experts
     in order, one operation at a time -> (mean, var_f).  half / prior: the mutations of the CPU test (beta without the
@@ -129,7 +135,7 @@ def yardsticks(oracle, c):
     """-> {mode: {"mean": ., "var": .}}: truth.noise_level of the fp64 evaluator per expert, latent variance = noisy - sn2
     in fp64, combined in fp64 in expert order, the rows permuted inside their own expert."""
     cov, K = c["cov"], c["K"]
-    parts = truth.bcm_rows(len(c["y"]), K)
+    parts = rows_of(c)
     Xe, ev = cov.evaluator(oracle, c["X"], c["Xt"])
     c64 = cov.fp64()
     nh = len(cov.hp)
@@ -189,7 +195,7 @@ def standin_experts(c, noisy_rows=False):
     c64 = c["cov"].fp64()
     Xt = np.asarray(c["Xt"], dtype=np.float64)
     ms, vs = [], []
-    for o, r in truth.bcm_rows(len(c["y"]), c["K"]):
+    for o, r in rows_of(c):
         X, y = c["X"][o: o + r], c["y"][o: o + r]
         Kf, _ = c64.train(X)
         L = np.linalg.cholesky(Kf + c64.sn2 * np.eye(r))

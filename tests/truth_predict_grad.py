@@ -38,10 +38,10 @@ F_GRAD = None                     # a factor of its own is not needed (docs/ACCU
 # family -> its cases: the smallest shapes at which the tile pass can go wrong (one tile with identity padding and the
 # boundary at 64; two training tiles; ragged n; two and three feature chunks; ill conditioning; |x| >> |x - x'|)
 CASES = {
-    "se": ("n2", "n63", "n64", "n65", "n257_d3", "n300_d17", "n515_d33", "n384_cond1e6"),
-    "matern32": ("n65", "n257_d3"),
-    "matern52": ("n300_d17", "n384_cond1e6"),
-    "ard": ("n65_d2", "n257_d3", "n300_d17", "n257_d3_shift", "n384_cond1e6"),
+    "se": ("n1", "n2", "n63", "n64", "n65", "n257_d3", "n300_d17", "n515_d33", "n384_cond1e6"),
+    "matern32": ("n1", "n2", "n63", "n64", "n65", "n257_d3"),
+    "matern52": ("n1", "n63", "n300_d17", "n384_cond1e6"),
+    "ard": ("n1_d2", "n2_d2", "n63_d2", "n64_d2", "n65_d2", "n257_d3", "n300_d17", "n257_d3_shift", "n384_cond1e6"),
 }
 CASE_LIST = [(f, n) for f, names in CASES.items() for n in names]
 WIDE_CASES = (("se", "n257_d3"), ("ard", "n257_d3"), ("matern52", "n300_d17"))
@@ -243,13 +243,17 @@ def combine_all(ex, mode, cov):
 def bcm_case(oracle, name, nt=BCM_NT):
     """A case of truth_poe_modes.CASES at nt points: truth, yardstick and floor of the combined gradients per mode of
     BCM_MODES.  -> dict(X, y, Xt, cov, K, modes={mode: dict(tdm, tdv, noise, floor)})."""
-    if ("bcm", name, nt) in _CASES:
-        return _CASES["bcm", name, nt]
-    X, y, Xt, cov, K = tpm.inputs(name, nt)
-    parts = truth.bcm_rows(len(y), K)
+    if ("bcm", name, nt) not in _CASES:
+        X, y, Xt, cov, K = tpm.inputs(name, nt)
+        _CASES["bcm", name, nt] = bcm_case_at(oracle, X, y, Xt, cov, truth.bcm_rows(len(y), K), tpm.expert_truths(name))
+    return _CASES["bcm", name, nt]
+
+
+def bcm_case_at(oracle, X, y, Xt, cov, parts, truths):
+    """bcm_case's body for experts on the rows `parts` [(offset, rows)] of (X, y) with their truth.Truth `truths`."""
     c64 = cov.fp64()
     ex = []
-    for (o, r), t in zip(parts, tpm.expert_truths(name)):
+    for (o, r), t in zip(parts, truths):
         # (the experts' truths are kept without K^-1: V = (Ks T^T) T in longdouble)
         Xl = Xt.astype(LD)
         _, Ks, Wt = t._cross(Xt)
@@ -270,8 +274,7 @@ def bcm_case(oracle, name, nt=BCM_NT):
         errs = [errors(*combine_all(e, mode, c64), tdm, tdv) for e in E]
         modes[mode] = dict(tdm=tdm, tdv=tdv, noise={q: max(e[q] for e in errs) for q in QUANTITIES},
                            floor=dict(dmean=truth.U4 * float(np.max(np.abs(tdm))), dvar=truth.U4 * float(np.max(np.abs(tdv)))))
-    _CASES["bcm", name, nt] = dict(X=X, y=y, Xt=Xt, cov=cov, K=K, modes=modes)
-    return _CASES["bcm", name, nt]
+    return dict(X=X, y=y, Xt=Xt, cov=cov, K=len(parts), parts=parts, modes=modes)
 
 
 def bcm_standin(c, mode):
@@ -279,7 +282,7 @@ def bcm_standin(c, mode):
     cov = c["cov"]
     ms, vs = tpm.standin_experts(c)
     ex = [(ms[k], vs[k]) + standin(cov, c["X"][o: o + r], c["y"][o: o + r], c["Xt"])
-          for k, (o, r) in enumerate(truth.bcm_rows(len(c["y"]), c["K"]))]
+          for k, (o, r) in enumerate(tpm.rows_of(c))]
     return combine_all(ex, mode, cov.fp64())
 
 

@@ -40,6 +40,12 @@ CASES = (
     ("ard", "n257_d3", 5),
     ("ard", "n300_d17", 3),
     ("se", "n1300_d6", 2),
+    ("se", "n1", 2),                  # below one 64-row build tile: every off-diagonal sum empty,
+    ("se", "n2", 3),                  # more targets than rows,
+    ("se", "n2", 129),                # two target tiles over one mostly-padding tile,
+    ("se", "n63", 17),
+    ("matern32", "n63", 5),
+    ("ard", "n63_d2", 3),
 )
 # the stand-in is pinned on the CPU at these (the issue's list: the cases above without the two that only add size)
 STANDIN_CASES = (
@@ -50,6 +56,12 @@ STANDIN_CASES = (
     ("matern32", "n65", 17),
     ("matern52", "n300_d17", 5),
     ("ard", "n257_d3", 5),
+    ("se", "n1", 2),
+    ("se", "n2", 3),
+    ("se", "n2", 129),
+    ("se", "n63", 17),
+    ("matern32", "n63", 5),
+    ("ard", "n63_d2", 3),
 )
 # (family, case, m, nt, subset): prediction beyond one 64-row test tile.  What each reaches is in tests/test_gpu_targets.py
 WIDE_CASES = (
@@ -58,6 +70,7 @@ WIDE_CASES = (
     ("se", "n515_d33", 65, 129, (0, 1, 63, 64)),
     ("ard", "n257_d3", 5, 200, None),
     ("matern52", "n300_d17", 17, 200, None),
+    ("se", "n2", 3, 129, None),                      # two test tiles over two rows
 )
 # cugp_set_targets on a grown handle: (family, case, n0, chunks) of truth_append.CASES, m
 GROWN_CASE = (("se", "n257_d3", 127, (2, 128)), 5)

@@ -22,7 +22,9 @@ import host_check  # noqa: E402  (also puts the repository root and tests/ on th
 CASES = (("trace", "n65_d2", 1, None, 1), ("trace", "n65_d2", 2, None, 1), ("trace", "n257_d3_shift", 2, None, 1),
          ("trace", "n300_d17", 1, None, 1), ("trace", "n515_d33", 2, None, 1),
          ("grad", "n65_d2", 1, None, 1), ("grad", "n65_d2", 2, None, 0), ("grad", "n257_d3_shift", 2, None, 1),
-         ("grad", "n300_d17", 1, None, 1), ("grad", "n515_d33", 2, None, 1), ("grad", "n257_d3", 2, 129, 1))
+         ("grad", "n300_d17", 1, None, 1), ("grad", "n515_d33", 2, None, 1), ("grad", "n257_d3", 2, 129, 1),
+         ("trace", "n2_d2", 1, None, 1), ("trace", "n63_d2", 2, None, 1),                  # below one 64-row build tile
+         ("grad", "n2_d2", 2, None, 1), ("grad", "n63_d2", 1, None, 1))
 
 
 def run(exe, tmp, kernel, name, kind, nt, want_var):

@@ -33,9 +33,11 @@ NPAD, NT = 128, 65
 # n per expert.  "last": the expert with two training tiles last; "first": the same experts with it first, so that the
 # surplus workgroups of the LAST expert -- the ones the early return of k_predict_grad_batched stops -- would read Ks and V
 # past the end of the heap blocks, where AddressSanitizer sees a missing guard (with it last they would stay inside)
-ORDERS = {"last": (64, 64, 66), "first": (66, 64, 64)}
+# "small": experts of 1, 2 and 63 rows -- one live training row, two, and one short of a build tile, in one padded size
+ORDERS = {"last": (64, 64, 66), "first": (66, 64, 64), "small": (1, 2, 63)}
 CASES = tuple(("grad", inst, d, want_v, "last") for inst in INSTANCES for d in (3, 17) for want_v in (1, 0)) + \
         tuple(("grad", inst, 3, want_v, "first") for inst in INSTANCES for want_v in (1, 0)) + \
+        tuple(("grad", inst, 3, 1, "small") for inst in INSTANCES) + \
         tuple(("reduce", K, world, nt) for K in (1, 3, 5) for world in (1, 2) for nt in (1, 257))
 MODES = (-1, 0, 1, 2, 3)
 SF2, SN2, ELL2 = 1.4918246976412703, 0.1353352832366127, 2.25

@@ -21,9 +21,12 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-# (family, case, rows taken from the case or None for all): npad 128, 256 and 384; n = 65, 128, 129, 257 and 300
+# (family, case, rows taken from the case or None for all): npad 128, 256 and 384; n = 65, 128, 129, 257 and 300; and below
+# and at one 64-row build tile: n = 1, 2, 63, 64
 CASES = (("se", "n65", None), ("se", "n128", None), ("se", "n257_d3", 129), ("matern52", "n300_d17", None),
-         ("ard", "n257_d3", None), ("matern32_ard", "n65_d2", None), ("matern32_ard", "n257_d3", None))
+         ("ard", "n257_d3", None), ("matern32_ard", "n65_d2", None), ("matern32_ard", "n257_d3", None),
+         ("se", "n65", 1), ("se", "n65", 2), ("se", "n65", 63), ("se", "n65", 64),
+         ("ard", "n257_d3", 2), ("ard", "n257_d3", 63), ("matern52", "n300_d17", 2), ("matern52", "n300_d17", 63))
 ULP4 = 4 * 2.0 ** -52
 
 
@@ -68,7 +71,8 @@ def run(exe, tmp, family, name, rows):
     mu, var, logp = tl.point_quantities(kap, a, y, truth.LL_CONST)
     av = a / kap
     sv = np.sqrt((1 + a * av) / kap)
-    point = max(float(np.max(np.abs(got[:n] - want)) / np.max(np.abs(want)))
+    # (n = 1: mu = y - alpha / kappa is 0 up to the rounding of the quotient: its scale is then |y|, that of the difference)
+    point = max(float(np.max(np.abs(got[:n] - want)) / (np.max(np.abs(want)) or np.max(np.abs(y))))
                 for got, want in zip(pt, (mu, var, logp, av, sv))) / ULP4
     eb = float(np.max(np.abs(b[:n] - Ki @ av)) / np.max(np.abs(Ki @ av)))
     lsum = np.sum(pt[2, :n].astype(np.longdouble))

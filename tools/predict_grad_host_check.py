@@ -18,14 +18,17 @@ import host_check  # noqa: E402  (also puts the repository root and tests/ on th
 CASES = (("se", "n2", None, 1), ("se", "n64", None, 1), ("se", "n65", None, 1), ("se", "n65", None, 0),
          ("matern32", "n65", None, 1), ("ard", "n257_d3_shift", None, 1), ("se", "n300_d17", None, 1),
          ("matern52", "n300_d17", None, 1), ("se", "n515_d33", None, 1), ("ard", "n257_d3", 200, 1),
-         ("matern52", "n300_d17", 129, 1))
+         ("matern52", "n300_d17", 129, 1),
+         ("matern32", "n2", None, 1), ("ard", "n2_d2", None, 1), ("se", "n63", 1, 1))      # below one build tile; one test point
 
 
 def run(exe, tmp, family, name, nt, want_var):
     import scipy.linalg as sl
     import truth
     import truth_predict_grad as tpg
-    X, y, Xt, cov = truth.family_inputs(family, name) if nt is None else truth.wide_inputs(name, nt, family)
+    X, y, Xt, cov = truth.family_inputs(family, name) if nt in (None, 1) else truth.wide_inputs(name, nt, family)
+    if nt == 1:
+        Xt = np.ascontiguousarray(Xt[:1])                     # (one test point: the first of the case's 64)
     c64 = cov.fp64()
     n, d = X.shape
     nt = len(Xt)
