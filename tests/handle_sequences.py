@@ -28,11 +28,16 @@ distinction:
   * an optimiser leaves the handle at the point of its last probe or stale at its end point, which only its own run can
     tell: the optimiser call itself becomes part of the route, and so does every level call behind it, until the next
     call that makes the handle stale or evaluates it from scratch.
+
+The poison shapes (docs/ACCURACY.md, "When the covariance cannot be factored") run the same decks with steps that take a
+handle into the failed state -- a covariance that cannot be factored: NaN results with CUGP_OK -- and out again.  On
+them alone NaN agrees with NaN whatever its payload; the shapes, decks, seeds and op lists shipped before are unchanged.
 """
 import zlib
 
 import numpy as np
 
+import numerical_failure as nf
 from conftest import synth
 
 REFUSED = -1                     # CUGP_ERR_INVALID: the one error code that is an observation ("the call was refused")
@@ -75,8 +80,10 @@ def bits(v):
     return np.ascontiguousarray(a, dtype=np.float64).ravel().view(np.uint64)
 
 
-def first_difference(got, want):
-    """None when two observations agree bit for bit, else a description of the first output that does not."""
+def first_difference(got, want, nan_equal=False):
+    """None when two observations agree bit for bit, else a description of the first output that does not.
+    nan_equal (the poison shapes alone): NaN on both sides agrees whatever its sign and payload (nf.same_bits_nan);
+    every finite value still agrees in bits."""
     if got[0] != want[0]:
         return "the long-lived handle %s, the twin %s" % (_brief(got), _brief(want))
     if got[0] == "refused":
@@ -87,7 +94,10 @@ def first_difference(got, want):
         if np.shape(a) != np.shape(b):
             return "output %r: shape %r against %r" % (label, np.shape(a), np.shape(b))
         ba, bb = bits(a), bits(b)
-        bad = np.flatnonzero(ba != bb)
+        differ = ba != bb
+        if nan_equal and np.asarray(a).dtype.kind == "f" and np.asarray(b).dtype.kind == "f":
+            differ &= ~(np.isnan(ba.view(np.float64)) & np.isnan(bb.view(np.float64)))
+        bad = np.flatnonzero(differ)
         if bad.size:
             i = int(bad[0])
             fa, fb = ba[i:i + 1].view(np.float64)[0], bb[i:i + 1].view(np.float64)[0]
@@ -128,6 +138,7 @@ class Subject:
     def __init__(self, name, kind, deck, seeds, steps, **shape):
         self.name, self.kind, self.deck, self.seeds, self.steps = name, kind, deck, tuple(seeds), steps
         self.salt = zlib.crc32(name.encode()) % 1000
+        self.poison, self.hp_bad = False, None       # a poison shape: its deck has the *_bad steps; NaN agrees with NaN
         self.__dict__.update(shape)
 
     # -- arrays from integers
@@ -142,6 +153,8 @@ class Subject:
     def targets(self, X, seed, m):
         rng = np.random.default_rng(400000 + 1000 * self.salt + seed)
         A = rng.standard_normal((self.d, m)) * (0.5 / np.sqrt(self.d))
+        if self.poison:                              # targets stay finite over a poisoned row of X: the repair of X is a repair
+            X = np.nan_to_num(X)
         return np.ascontiguousarray(np.sin(X @ A) + 0.1 * rng.standard_normal((X.shape[0], m)))
 
     def normals(self, seed, ns, nt):
@@ -193,7 +206,7 @@ def run(sub, factory, seed, steps=None, log=print):
                 want = observe(lambda: apply(sub, twin, model, **op.kw))
             finally:
                 twin.close()
-            diff = first_difference(got, want)
+            diff = first_difference(got, want, nan_equal=sub.poison)
             if diff is not None:
                 raise Mismatch(
                     "%s seed %d step %d: %r\n  %s\n  ops so far:\n    %s\n  route of the twin (%s):\n    %s" % (
@@ -214,6 +227,20 @@ def _res(result, label):
     if result is None or result[0] != "ok":
         return None
     return dict(result[1]).get(label)
+
+
+def _stays_put(model, result):
+    """An optimiser started on a poisoned handle: its first evaluation is NaN, so is its search direction and every probe
+    (minimize.cpp: cg_loop's start, :192-197, and the halving of a NaN step, :210-215), no probe is better than the start
+    and the handle ends where it began -- hp (and Z) keep their bits, which the generator's dry run can rely on.  -> True
+    then (checked against the run's own end point where there is one); False for a healthy start."""
+    if not model.poisoned:
+        return False
+    for label, held in (("end", model.hp), ("Z", getattr(model, "Z", None))):
+        seen = _res(result, label)
+        if seen is not None and not nf.same_bits_nan(seen, held):
+            raise AssertionError("an optimiser started on a poisoned handle moved %r: %r against %r" % (label, seen, held))
+    return True
 
 
 def _cycle(gen, key, values):
@@ -239,10 +266,13 @@ class CovsumModel:
         self.sub = sub
         self.X, self.y = sub.rows(0, sub.n0)
         self.hp, self.hp_idx = sub.hp_of(0), 0
+        self.hp_poison = False                       # the hyper-parameters are the subject's hp_bad (hp_idx -1)
         self.Y = None
         self._reset()
 
     n = property(lambda self: len(self.y))
+    # K cannot be factored: every evaluation is a failed one (NaN results, CUGP_OK) until a repair
+    poisoned = property(lambda self: self.hp_poison or bool(np.isnan(self.X).any()))
     cap = property(lambda self: (max(self.sub.n0, self.sub.npad_min) + TILE - 1) // TILE * TILE)
 
     def _reset(self):
@@ -298,12 +328,18 @@ class CovsumModel:
 
     def advance(self, op, result):
         name, kw, s = op.name, op.kw, self.sub
-        if name == "set_data":
+        if name in ("set_data", "set_data_bad"):
             self.X, self.y = s.rows(kw["seed"], self.n)
+            if name == "set_data_bad":
+                self.X = nf.poison_row(self.X, kw["row"])
             self._reset()
         elif name == "set_hp":
             if self.hp_idx != kw["idx"]:
-                self.hp, self.hp_idx = s.hp_of(kw["idx"]), kw["idx"]
+                self.hp, self.hp_idx, self.hp_poison = s.hp_of(kw["idx"]), kw["idx"], False
+                self._reset()
+        elif name == "set_hp_bad":
+            if self.hp_idx != -1:
+                self.hp, self.hp_idx, self.hp_poison = np.array(s.hp_bad, dtype=np.float64), -1, True
                 self._reset()
         elif name in ("compute_K_train", "compute_squared_dist", "detour"):
             self._reset()
@@ -321,13 +357,16 @@ class CovsumModel:
                 lo = self.n
                 Xa, ya = s.rows(kw["seed"], kw["k"], stream=2)
                 self.X, self.y = np.concatenate([self.X, Xa]), np.concatenate([self.y, ya])
-                if self.level in ("full", "full_cont", "opt"):
+                # (a poisoned handle that holds its -- NaN -- inverse borders it, finds LL not finite and keeps nothing:
+                #  cugp_append's discard_eval, cugp_capi.cpp:2081-2083; behind an optimiser the twin replays the append)
+                if self.level == "opt" or (self.level in ("full", "full_cont") and not self.poisoned):
                     self.tail.append(("append", (lo, self.n)))
                 else:
                     self._reset()
         elif name in ("cg_solve", "cg_solve_loo"):
             self.tail.append(call(name, budget=kw["budget"]))
-            self.hp, self.hp_idx = _res(result, "end"), None
+            if not _stays_put(self, result):
+                self.hp, self.hp_idx = _res(result, "end"), None
 
 
 NEEDS_INVERSE = ("loglik_grad", "compute_gradient_loghyperparam", "predict", "predict_latent", "predict_grad",
@@ -452,6 +491,26 @@ DECK_COVSUM_FIXED_N = _COVSUM_ONCE + ["set_hp", "compute_loglikelihood", "predic
 DECK_COVSUM = DECK_COVSUM_FIXED_N + ["compute_squared_dist"] + ["append"] * 4
 
 
+# -- the poison steps (docs/ACCURACY.md, "When the covariance cannot be factored"): into the failed state and, by the
+# existing set_hp / set_data, out of it.  Added behind the decks above, which list the table: those stay as they were.
+def _bad_rows(rng, m, gen):
+    return {"seed": int(rng.integers(1, 1000)), "row": int(rng.integers(m.n))}
+
+
+def _set_hp_bad(setter):
+    return (_none, _nothing(lambda s, h, m: getattr(h, setter)(np.array(s.hp_bad, dtype=np.float64))))
+
+
+POISON_OPS = ("set_hp_bad", "set_data_bad", "set_expert_data_bad", "set_inducing_bad")
+COVSUM_OPS.update({
+    "set_hp_bad": _set_hp_bad("set_loghyperparam"),
+    "set_data_bad": (_bad_rows, _nothing(lambda s, h, m, seed, row: h.set_data(
+        nf.poison_row(s.rows(seed, m.n)[0], row), s.rows(seed, m.n)[1]))),
+})
+# the existing deck, the poison steps and as many repairs again
+DECK_COVSUM_POISON = DECK_COVSUM + ["set_hp_bad"] * 3 + ["set_data_bad"] * 3 + ["set_hp"] * 3 + ["set_data"] * 3
+
+
 # ================================================================================================ SparseGP
 SP_NT = (257, 1, 65)
 SP_NT_JOINT = (65, 1)
@@ -472,9 +531,17 @@ class SparseModel:
         self.hp, self.hp_idx = sub.hp_of(0), 0
         self.Y = None
         self.last_side = None
+        self.hp_poison = False
+
+    # Kuu (a NaN row of Z, hp_bad) or B (a NaN row of X) cannot be factored.  A failed evaluation of a side is an evaluation:
+    # it leaves the side valid over a NaN row and the other side stale (sp_eval, cugp_capi.cpp:2811-2823 for Kuu,
+    # :2897-2904 for B), and predictions of a side that is not `pd` are NaN (:3195) -- nothing the twin's route lacks.
+    # (Z is None in the generator's dry run behind an optimiser over Z that started healthy: it ended at finite values)
+    poisoned = property(lambda self: self.hp_poison or bool(np.isnan(self.X).any()) or
+                        (self.Z is not None and bool(np.isnan(self.Z).any())))
 
     def describe(self):
-        return "targets %s" % ("none" if self.Y is None else self.Y.shape[1])
+        return "targets %s%s" % ("none" if self.Y is None else self.Y.shape[1], ", poisoned" if self.poisoned else "")
 
     def creation(self):
         s = self.sub
@@ -492,18 +559,25 @@ class SparseModel:
 
     def advance(self, op, result):
         name, kw, s = op.name, op.kw, self.sub
-        if name == "set_data":
+        if name in ("set_data", "set_data_bad"):
             self.X, self.y = s.rows(kw["seed"], s.n)
-        elif name == "set_inducing":
+            if name == "set_data_bad":
+                self.X = nf.poison_row(self.X, kw["row"])
+        elif name in ("set_inducing", "set_inducing_bad"):
             self.Z = self.X[s.zrows(kw["seed"])] + kw["shift"]
+            if name == "set_inducing_bad":
+                self.Z = nf.poison_row(self.Z, kw["row"])
         elif name == "set_hp":
-            self.hp, self.hp_idx = s.hp_of(kw["idx"]), kw["idx"]
+            self.hp, self.hp_idx, self.hp_poison = s.hp_of(kw["idx"]), kw["idx"], False
+        elif name == "set_hp_bad":
+            self.hp, self.hp_idx, self.hp_poison = np.array(s.hp_bad, dtype=np.float64), -1, True
         elif name == "set_targets":
             self.Y = s.targets(self.X, kw["seed"], kw["p"])
         elif name.startswith("cg_solve") and (name != "cg_solve_targets" or self.Y is not None):
-            self.hp, self.hp_idx = _res(result, "end"), None
-            if name == "cg_solve_z" or kw.get("inducing"):
-                self.Z = _res(result, "Z")
+            if not _stays_put(self, result):
+                self.hp, self.hp_idx = _res(result, "end"), None
+                if name == "cg_solve_z" or kw.get("inducing"):
+                    self.Z = _res(result, "Z")
 
 
 def _sp_cg(method, inducing):
@@ -561,6 +635,19 @@ DECK_SPARSE = list(SPARSE_OPS) + ["set_data", "set_inducing", "set_hp", "bound",
                                   "set_targets", "set_targets", "bound_targets", "bound_grad_targets",
                                   "bound_grad_z_targets", "predict_targets", "predict_targets", "get_inducing"]
 
+SPARSE_OPS.update({
+    "set_hp_bad": _set_hp_bad("set_loghyperparam"),
+    "set_data_bad": (lambda rng, m, gen: {"seed": int(rng.integers(1, 1000)), "row": int(rng.integers(m.sub.n))},
+                     _nothing(lambda s, h, m, seed, row: h.set_data(nf.poison_row(s.rows(seed, s.n)[0], row),
+                                                                    s.rows(seed, s.n)[1]))),
+    "set_inducing_bad": (lambda rng, m, gen: {"seed": int(rng.integers(1000)), "shift": float(rng.integers(0, 3)) / 8,
+                                              "row": int(rng.integers(m.sub.m))},
+                         _nothing(lambda s, h, m, seed, shift, row: h.set_inducing(
+                             nf.poison_row(m.X[s.zrows(seed)] + shift, row)))),
+})
+DECK_SPARSE_POISON = (DECK_SPARSE + ["set_hp_bad"] * 2 + ["set_data_bad"] * 2 + ["set_inducing_bad"] * 2 +
+                      ["set_hp"] * 2 + ["set_data"] * 2 + ["set_inducing"] * 2)
+
 
 # ================================================================================================ BCM
 BCM_NT = (130, 1, 65, 64)
@@ -580,15 +667,23 @@ class BCMModel:
     def __init__(self, sub):
         self.sub = sub
         self.K = len(sub.rows_per_expert)
-        self.seeds = [0] * self.K
+        self.seeds = [0] * self.K                    # per expert: its data seed, or (seed, row) with that row of X NaN
         self.hp, self.hp_idx = sub.hp_of(0), 0
+        self.hp_poison = False
         self._reset()
+
+    # one expert that cannot be factored: the sums of an evaluation are NaN, that expert's level moves as any other's
+    # (read_result_row, cugp_capi.cpp:1095-1112, sets factor_valid and inverse_valid whatever the row holds)
+    poisoned = property(lambda self: self.hp_poison or any(isinstance(sd, tuple) for sd in self.seeds))
 
     def _reset(self, tail=()):
         self.base_seeds, self.base_hp, self.tail = list(self.seeds), self.hp, list(tail)
         self.levels = ["full" if tail else "stale"] * self.K
 
     def data(self, k, seed):
+        if isinstance(seed, tuple):
+            X, y = self.data(k, seed[0])
+            return nf.poison_row(X, seed[1]), y
         return self.sub.rows(1000 * (k + 1) + seed, self.sub.rows_per_expert[k])
 
     def describe(self):
@@ -623,19 +718,24 @@ class BCMModel:
 
     def advance(self, op, result):
         name, kw = op.name, op.kw
-        if name == "set_expert_data":
+        if name in ("set_expert_data", "set_expert_data_bad"):
             k = kw["k"]
-            self.seeds[k] = kw["seed"]
+            seed = kw["seed"] if name == "set_expert_data" else (kw["seed"], kw["row"])
+            self.seeds[k] = seed
             if not self.tail:
-                self.base_seeds[k] = kw["seed"]
+                self.base_seeds[k] = seed
             else:
                 if not self.opt:                                   # (behind an optimiser its path needs every call, in order)
                     self.tail = [c for c in self.tail if not (c[0] in ("view", "data") and c[1][0] == k)]
-                self.tail.append(("data", (k, kw["seed"])))
+                self.tail.append(("data", (k, seed)))
             self.levels[k] = "stale"
         elif name == "set_hp":
             if self.hp_idx != kw["idx"]:
-                self.hp, self.hp_idx = self.sub.hp_of(kw["idx"]), kw["idx"]
+                self.hp, self.hp_idx, self.hp_poison = self.sub.hp_of(kw["idx"]), kw["idx"], False
+                self._reset()
+        elif name == "set_hp_bad":
+            if self.hp_idx != -1:
+                self.hp, self.hp_idx, self.hp_poison = np.array(self.sub.hp_bad, dtype=np.float64), -1, True
                 self._reset()
         elif name in ("loglik_grad", "loglik_grad_rows"):
             self._reset([EVAL])
@@ -651,7 +751,8 @@ class BCMModel:
         elif name == "cg_solve":
             self.tail.append(call("cg_solve", budget=kw["budget"]))
             self.levels = ["opt"] * self.K
-            self.hp, self.hp_idx = _res(result, "end"), None
+            if not _stays_put(self, result):
+                self.hp, self.hp_idx = _res(result, "end"), None
 
 
 def _bcm_k(rng, m, gen):
@@ -697,6 +798,14 @@ DECK_BCM = (["set_expert_data"] * 5 + ["set_hp"] * 2 + ["set_hp_same"] * 2 + ["l
             ["bcm_predict"] * 3 + ["predict"] * 4 + ["predict_grad"] * 4 + ["view_loglik"] * 4 + ["view_loglik_grad"] * 3 +
             ["view_predict"] * 3 + ["cg_solve"] * 2)
 
+BCM_OPS.update({
+    "set_hp_bad": _set_hp_bad("set_BCM_log_hyperparam"),
+    "set_expert_data_bad": (lambda rng, m, gen: (lambda k: {"k": k, "seed": int(rng.integers(1, 1000)), "row": int(
+        rng.integers(m.sub.rows_per_expert[k]))})(int(rng.integers(m.K))),
+                            _nothing(lambda s, h, m, k, seed, row: h.set_expert_data(k, *m.data(k, (seed, row))))),
+})
+DECK_BCM_POISON = DECK_BCM + ["set_hp_bad"] * 3 + ["set_expert_data_bad"] * 3 + ["set_hp"] * 2 + ["set_expert_data"] * 3
+
 MODELS = {"covsum": CovsumModel, "sparse": SparseModel, "bcm": BCMModel}
 TABLES = {"covsum": COVSUM_OPS, "sparse": SPARSE_OPS, "bcm": BCM_OPS}
 
@@ -723,6 +832,11 @@ def _zrows(n, m):
     return lambda seed: np.sort(np.random.default_rng(600000 + seed).choice(n, m, replace=False))
 
 
+# a length scale of exp(-800) = 0: K = k(X, X) has NaN on its diagonal (0 / 0) and zeros beside it -- no pivot is healthy
+_HP_BAD = [-800.0, 0.2, -1.0]
+# (a greedy search over the seeds 1 .. 399 for poison_coverage's conditions, from the generator alone)
+_SEEDS_POISON = {"covsum": (16, 33, 173, 122, 36, 317), "sparse": (92, 25, 68, 211, 321), "bcm": (191, 391, 124)}
+
 SUBJECTS = {s.name: s for s in (
     # (a) three tiles of capacity, the captured graph, an append across the 256-row tile boundary
     Subject("covsum_se_n193", "covsum", DECK_COVSUM, seeds=(5, 6, 65), steps=40, d=3, n0=193, nmax=257, npad_min=384,
@@ -747,6 +861,17 @@ SUBJECTS = {s.name: s for s in (
     # very unequal experts: no group, every expert on its own stream
     Subject("bcm_ard_100_400", "bcm", DECK_BCM, seeds=(1,), steps=16, d=3, rows_per_expert=(100, 400), ard=True,
             kernel="se", scale=4.0, hps=[_HP_ARD3, _near(_HP_ARD3), _shifted(_HP_ARD3, -0.1), _shifted(_HP_ARD3, 0.1)]),
+    # the poison shapes: the shapes of (a), the first sparse and the first BCM shape above, their decks with the steps
+    # into the failed state and as many repairs again; seeds chosen for poison_coverage's conditions
+    Subject("covsum_se_n193_poison", "covsum", DECK_COVSUM_POISON, seeds=_SEEDS_POISON["covsum"],
+            steps=len(DECK_COVSUM_POISON), d=3, n0=193, nmax=257, npad_min=384, ard=False, kernel="se", scale=4.0,
+            hps=_HPS_SE, poison=True, hp_bad=_HP_BAD),
+    Subject("sparse_se_poison", "sparse", DECK_SPARSE_POISON, seeds=_SEEDS_POISON["sparse"],
+            steps=len(DECK_SPARSE_POISON), d=2, n=300, m=65, chunk_rows=128, ard=False, kernel="se", scale=4.0,
+            hps=[[0.5, 0.5, 0.5], [0.4, 0.45, 0.4], [0.6, 0.55, 0.3]], zrows=_zrows(300, 65), poison=True,
+            hp_bad=[-800.0, 0.5, 0.5]),
+    Subject("bcm_se_poison", "bcm", DECK_BCM_POISON, seeds=_SEEDS_POISON["bcm"], steps=len(DECK_BCM_POISON), d=3,
+            rows_per_expert=(64, 64, 66), ard=False, kernel="se", scale=4.0, hps=_HPS_SE, poison=True, hp_bad=_HP_BAD),
 )}
 
 CASES = [(s.name, seed) for s in SUBJECTS.values() for seed in s.seeds]
@@ -766,13 +891,13 @@ def walk(sub, seed, steps=None):
 
 def coverage(kind):
     """The coverage conditions of one handle type over its shipped seeds -> {condition: bool}."""
-    subs = [s for s in SUBJECTS.values() if s.kind == kind]
+    subs = [s for s in SUBJECTS.values() if s.kind == kind and not s.poison]      # (the poison shapes: poison_coverage)
     walks = [(s, seed, walk(s, seed)) for s in subs for seed in s.seeds]
     counts = {}
     for _, _, w in walks:
         for op, _, _ in w:
             counts[op.name] = counts.get(op.name, 0) + 1
-    cond = {"every op class at least twice": all(counts.get(n, 0) >= 2 for n in TABLES[kind])}
+    cond = {"every op class at least twice": all(counts.get(n, 0) >= 2 for n in TABLES[kind] if n not in POISON_OPS)}
 
     def in_order(seq, tests):
         """some consecutive entries of seq pass tests[0], tests[1], ... in that order"""
@@ -834,3 +959,58 @@ def _with_targets(w):
         if op.name == "set_targets":
             return w[i:]
     return []
+
+
+# ================================================================================================ coverage of the poison shapes
+# the op classes that evaluate the model when it is stale (the target side's: once targets are set)
+EVALUATING = {
+    "covsum": NEEDS_INVERSE + ("compute_loglikelihood", "enqueue_fetch", "detour", "cg_solve", "cg_solve_loo"),
+    "sparse": SP_OWN,
+    "bcm": ("loglik_grad", "loglik_grad_rows", "bcm_predict", "predict", "predict_grad", "view_loglik", "view_loglik_grad",
+            "view_predict", "cg_solve"),
+}
+EVALUATING_WITH_TARGETS = {"covsum": NEEDS_TARGETS, "sparse": SP_TG, "bcm": ()}
+
+
+def poison_walk(sub, seed, steps=None):
+    """[(op, poisoned before the op, poisoned after it, targets set before it)] of the generator's dry run."""
+    out, model = [], sub.model()
+    for op in generate(sub, seed, steps):
+        before, targets = model.poisoned, getattr(model, "Y", None) is not None
+        model.advance(op, None)
+        out.append((op, before, model.poisoned, targets))
+    return out
+
+
+def poison_sets(sub, seed):
+    """(op classes seen while the handle was poisoned, op classes seen as the first evaluating call after a repair) of
+    one sequence.  A repair is a step that takes a poisoned handle to a healthy one; the first evaluating call after it
+    counts only if nothing poisoned the handle again in between."""
+    evaluating = EVALUATING[sub.kind]
+    while_poisoned, after_repair, waiting = set(), set(), False
+    for op, before, after, targets in poison_walk(sub, seed):
+        if before:
+            while_poisoned.add(op.name)
+        if waiting and not before and (op.name in evaluating or
+                                       (targets and op.name in EVALUATING_WITH_TARGETS[sub.kind])):
+            after_repair.add(op.name)
+            waiting = False
+        if before and not after:
+            waiting = True
+        elif after:
+            waiting = False
+    return while_poisoned, after_repair
+
+
+def poison_coverage(name):
+    """The coverage conditions of one poison shape over its shipped seeds -> {condition: bool}."""
+    sub = SUBJECTS[name]
+    seen, first = set(), set()
+    for seed in sub.seeds:
+        a, b = poison_sets(sub, seed)
+        seen |= a
+        first |= b
+    classes = set(sub.deck)
+    evaluating = set(EVALUATING[sub.kind] + EVALUATING_WITH_TARGETS[sub.kind]) & classes
+    return {"every op class while the handle is poisoned": classes <= seen,
+            "every evaluating op class as the first evaluating call after a repair": evaluating <= first}

@@ -9,11 +9,17 @@ truth_targets.standin_from, truth_sparse_targets.standin, truth_sparse_joint.sta
 no new numerics.  The gradient continued from a valid factor takes alpha = K^-1 y (truth.standin's order), the combined
 evaluation alpha = T' (T y) (truth_predict_grad.standin's): two routes that agree to rounding only, as in the library.
 
+A covariance that cannot be factored (the poison steps of the harness) gives NaN results, never an exception: the
+factorisations fall back on numerical_failure.nan_flow_cholesky, and finite input takes the route it always took.
+
 MUTATIONS: names that, when in the module's set ACTIVE, switch one invalidation off.  Every handle created while a name is
 active carries it -- the twin too: a mutation shows only through what the long-lived handle has lived through.
 """
+import functools
+
 import numpy as np
 
+import numerical_failure as nf
 import truth
 import truth_append
 import truth_ard_matern as tam
@@ -35,6 +41,8 @@ MUTATIONS = (
     "set_inducing_keeps_row_z",  # set_inducing keeps row_z
     "expert_data_keeps_sum",     # BCM: set_expert_data on one expert keeps the cached sum
     "view_taken_for_group",      # BCM: an expert view's own evaluation at the BCM's hp is taken for the group's
+    "failed_eval_keeps_gradient",    # an evaluation whose LL is not finite leaves the previous evaluation's gradient in place
+    "sparse_kuu_failure_keeps_row",  # a side keeps its previous result row when Kuu cannot be factored
 )
 ACTIVE = set()
 
@@ -72,6 +80,33 @@ def _cg(fn, theta, budget):
     """The library's own conjugate-gradient loop (host code, no device) on a Python objective."""
     from cugp_amd import gp
     return gp.cg_minimize_n(fn, theta, budget)
+
+
+# -- a covariance that cannot be factored is no error (include/cugp.h): NaN results, never an exception.  Every helper
+# takes the route it always took on finite input, so the healthy sequences keep their bits.
+def _quiet(fn):
+    """NaN and inf are results here, not warnings."""
+    @functools.wraps(fn)
+    def wrapped(*a, **kw):
+        with np.errstate(all="ignore"):
+            return fn(*a, **kw)
+    return wrapped
+
+
+def _chol(K):
+    """The lower factor; of a matrix that has none, nf.nan_flow_cholesky's: healthy columns, then NaN."""
+    try:
+        return np.linalg.cholesky(K)
+    except np.linalg.LinAlgError:
+        return nf.nan_flow_cholesky(K)
+
+
+def _trisolve(L, B):
+    """L^-1 B; NaN throughout once L holds a NaN (every result the handles report from it sums over a NaN row)."""
+    import scipy.linalg as sl
+    if not np.all(np.isfinite(L)):
+        return np.full(np.shape(B), np.nan)
+    return sl.solve_triangular(L, B, lower=True)
 
 
 # ================================================================================================ Covsum
@@ -144,8 +179,12 @@ class Covsum:
         self._stale()
         if update:                                                   # the bordering of truth_append, from the factors held
             self._border(n0, k)
+            if not np.isfinite(self.last_ll):                        # a Schur complement that cannot be factored: nothing of the
+                self.factor_valid = self.inverse_valid = False       # evaluation is kept (cugp_append's discard_eval)
+                self.last_ll, self.last_g = np.nan, np.full(self.nh, np.nan)
 
     # -- the evaluations
+    @_quiet
     def _finish(self, alpha):
         """ll and the gradient from T, K^-1, log|K| and alpha (truth.standin's formulas)."""
         n, c = self.n, self.cov
@@ -154,13 +193,15 @@ class Covsum:
         self.last_ll = -0.5 * (self.z @ self.z + self.logdet + n * truth.LL_CONST)
         _, terms = c.train(self.X[:n])
         W = self.Ki - np.outer(alpha, alpha)
-        self.last_g = np.array(terms(W) + (c.sn2 * np.trace(W),))
+        if not ("failed_eval_keeps_gradient" in self.mut and not np.isfinite(self.last_ll)):
+            self.last_g = np.array(terms(W) + (c.sn2 * np.trace(W),))
         self.factor_valid = self.inverse_valid = True
 
     def _build_factor(self):
         n, c = self.n, self.cov
-        self.A = np.linalg.cholesky(c.train(self.X[:n])[0] + c.sn2 * np.eye(n))
+        self.A = _chol(c.train(self.X[:n])[0] + c.sn2 * np.eye(n))
 
+    @_quiet
     def _eval(self, grad):
         """An evaluation from the covariance build on (enqueue_eval)."""
         import scipy.linalg as sl
@@ -170,24 +211,26 @@ class Covsum:
         L = self.A
         self.logdet = 2 * np.log(np.diag(L)).sum()
         if not grad:
-            self.z = sl.solve_triangular(L, self.y[:n], lower=True)
+            self.z = _trisolve(L, self.y[:n])
             self.last_ll = -0.5 * (self.z @ self.z + self.logdet + n * truth.LL_CONST)
             self.factor_valid = True
             return
-        self.T = sl.solve_triangular(L, np.eye(n), lower=True)
+        self.T = _trisolve(L, np.eye(n))
         self.Ki = self.T.T @ self.T
         self._finish(self.T.T @ (self.T @ self.y[:n]))
 
+    @_quiet
     def _continue(self):
         """The inverse quantities from the factor A holds (enqueue_continue): whatever A holds."""
         import scipy.linalg as sl
         n = self.n
         L = np.tril(self.A)
-        self.T = sl.solve_triangular(L, np.eye(n), lower=True)
+        self.T = _trisolve(L, np.eye(n))
         self.Ki = self.T.T @ self.T
         self.logdet = 2 * np.log(np.abs(np.diag(L))).sum()
         self._finish(self.Ki @ self.y[:n])
 
+    @_quiet
     def _border(self, n0, k):
         """truth_append.standin_append's pass over the new rows, on the T, K^-1, z, alpha the handle holds."""
         import scipy.linalg as sl
@@ -199,8 +242,8 @@ class Covsum:
             P = B @ T.T
             V = P @ T
             S = c.k(X[r0:r1], X[r0:r1]) + c.sn2 * np.eye(kk) - P @ P.T
-            Cf = np.linalg.cholesky(S)
-            Ci = sl.solve_triangular(Cf, np.eye(kk), lower=True)
+            Cf = _chol(S)
+            Ci = _trisolve(Cf, np.eye(kk))
             Q = -(Ci @ V)
             zb = Ci @ (y[r0:r1] - P @ z)
             T = np.block([[T, np.zeros((r0, kk))], [Q, Ci]])
@@ -252,6 +295,7 @@ class Covsum:
         return self.z @ self.z, self.logdet
 
     # -- intermediates
+    @_quiet
     def compute_K_train(self, X=None):
         n, c = self.n, self.cov
         K = c.train(self.X[:n])[0] + c.sn2 * np.eye(n)
@@ -269,6 +313,7 @@ class Covsum:
         self._stale(loo=False)
         return S
 
+    @_quiet
     def compute_k_test(self, Xt):
         return self.cov.k(np.asarray(Xt, dtype=np.float64).reshape(-1, self.d), self.X[:self.n])
 
@@ -300,6 +345,7 @@ class Covsum:
         self.pred_nt = nt
         return [self.pred[:nt, j].copy() for j in range(len(cols))]
 
+    @_quiet
     def _predict(self, Xtest, latent):
         self._need_inverse()
         c = self.cov
@@ -316,6 +362,7 @@ class Covsum:
         _, _, _, m, v = self._predict(Xtest, True)
         return tuple(self._through_scratch([m, v]))
 
+    @_quiet
     def predict_grad(self, Xtest, with_noise=True, want_var_grad=True):
         Xt, Ks, Wt, m, v = self._predict(Xtest, not with_noise)
         c = self.cov
@@ -325,12 +372,14 @@ class Covsum:
         d = self.d
         return cols[0], cols[1], np.array(cols[2:2 + d]).T.copy(), np.array(cols[2 + d:]).T.copy()
 
+    @_quiet
     def compute_test_joint(self, X, y, Xtest, with_noise=True):
         Xt, _, Wt, m, _ = self._predict(Xtest, True)
         c = self.cov
         cov = c.k(Xt, Xt) - Wt @ Wt.T
         return m, cov + c.sn2 * np.eye(len(Xt)) if with_noise else cov
 
+    @_quiet
     def sample_posterior(self, X, y, Xtest, nsamples, with_noise=False, jitter=None, rng=None, normals=None):
         m, cov = self.compute_test_joint(None, None, Xtest, with_noise)
         try:
@@ -340,6 +389,7 @@ class Covsum:
         return m[None, :] + np.asarray(normals, dtype=np.float64).reshape(int(nsamples), len(m)) @ Cf.T
 
     # -- leave-one-out (truth_loo.standin's formulas on the K^-1 and alpha held); the results are kept until the handle is stale
+    @_quiet
     def _loo(self, want_grad):
         self._need_inverse()
         if self.loo_valid and (self.loo_row[1] is not None or not want_grad):
@@ -382,6 +432,7 @@ class Covsum:
     def num_targets(self):
         return self.tg_m
 
+    @_quiet
     def _targets(self):
         if self.tg_m <= 0:
             raise Refused("no targets set")
@@ -407,6 +458,7 @@ class Covsum:
         self._targets()
         return self.tg_out[3].T.copy()
 
+    @_quiet
     def predict_targets(self, Xtest):
         self._targets()
         Xt, Ks, Wt, _, v = self._predict(Xtest, False)
@@ -517,13 +569,34 @@ class SparseGP:
             other.valid = False
         F, g, each, _, _, gz = self._standin(side.Y)
         self.work = side.Y                                           # the work area now holds this side's solves
+        if ("sparse_kuu_failure_keeps_row" in self.mut and side.row is not None and len(side.row[2]) == len(each)
+                and not np.isfinite(F) and not self._kuu_finite()):
+            side.row_grad, side.valid = want_grad, True              # (the row of the evaluation before stays)
+            if want_z:
+                side.gz, side.row_z = gz if side.gz is None else side.gz, True
+            return
         side.row, side.row_grad, side.valid = (F, g, each), want_grad, True
         if want_z:
             side.gz, side.row_z = gz, True
 
+    @_quiet
+    def _kuu_finite(self):
+        return bool(np.all(np.isfinite(self.cov.k(self.Z, self.Z))))
+
+    @_quiet
     def _standin(self, Y, Xt=None):
+        """tst.standin; NaN throughout where Kuu or B cannot be factored (scipy refuses a matrix that is not finite, LAPACK
+        one that is not positive definite), or where the bound comes out not finite: the library's `pd`."""
         Xt = self.X[:1] if Xt is None else Xt
-        return tst.standin(self.cov, self.X, Y, self.Z, Xt, self.chunk_rows, self.jitter)
+        try:
+            out = tst.standin(self.cov, self.X, Y, self.Z, Xt, self.chunk_rows, self.jitter)
+        except (np.linalg.LinAlgError, ValueError):
+            out = None
+        if out is None or not np.isfinite(out[0]):
+            p, nt = len(Y), len(Xt)
+            return (np.nan, np.full(self.nh, np.nan), np.full(p, np.nan), np.full((p, nt), np.nan), np.full(nt, np.nan),
+                    np.full(self.Z.shape, np.nan))
+        return out
 
     # -- the handle's own y
     def bound(self):
@@ -551,10 +624,16 @@ class SparseGP:
         m, v = self._predict(self.own, Xtest, with_noise)
         return m[0], v
 
+    @_quiet
     def _joint(self, Xtest):
         self._eval(self.own)
         Xt = self._points(Xtest)
-        return tsj.standin(self.cov, self.X, self.work[0], self.Z, Xt, self.chunk_rows, self.jitter)
+        nan = (np.full((len(Xt), len(Xt)), np.nan), np.full(Xt.shape, np.nan), np.full(Xt.shape, np.nan))
+        try:                                                         # (a side that is not `pd` predicts NaN)
+            out = tsj.standin(self.cov, self.X, self.work[0], self.Z, Xt, self.chunk_rows, self.jitter)
+        except (np.linalg.LinAlgError, ValueError):
+            return nan
+        return out if all(np.all(np.isfinite(v)) for v in out) else nan
 
     def predict_joint(self, Xtest, with_noise=True):
         mean = self.predict(Xtest, with_noise)[0]
@@ -652,6 +731,7 @@ class BCM:
     def get_loghyperparam(self):
         return self.hp.copy()
 
+    @_quiet
     def _evaluate(self):
         if self.sum_valid:
             return
@@ -684,6 +764,7 @@ class BCM:
         out = [e._predict(Xt, latent) for e in self.experts]
         return np.array([o[3] for o in out]), np.array([o[4] for o in out]), out
 
+    @_quiet
     def compute_BCM_test_means_and_var(self, Xt):
         m, v, _ = self._experts_at(Xt, False)
         sp = spm = np.zeros(m.shape[1])
@@ -691,6 +772,7 @@ class BCM:
             sp, spm = sp + 1 / v[k], spm + m[k] / v[k]
         return spm / sp, 1 / sp
 
+    @_quiet
     def predict(self, Xt, combine=None, with_noise=True):
         if combine is None:
             return self.compute_BCM_test_means_and_var(Xt)
@@ -699,6 +781,7 @@ class BCM:
         mean, var = tpm.combine(m, v, combine, c.sf2)
         return mean, var + c.sn2 if with_noise else var
 
+    @_quiet
     def predict_grad(self, Xt, combine=None, with_noise=True):
         mean, var = self.predict(Xt, combine, with_noise)
         m, v, out = self._experts_at(Xt, combine is not None)
