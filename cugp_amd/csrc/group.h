@@ -1,4 +1,4 @@
-// group.h -- internal interface between the BCM layer (bcm.cpp) and the evaluation engine (cugp_capi.cpp):
+// group.h -- internal interface between the BCM layer (bcm.cpp) and the evaluation engine (cugp_capi.cpp, group.cpp, predict.cpp):
 // several experts of equal shape on one device evaluated by ONE sequence of launches (blockIdx.y = expert).
 // Not part of the public boundary (include/cugp.h).
 #pragma once

@@ -1,4 +1,4 @@
-// kernels.h -- internal launch interface between the C-ABI (cugp_capi.cpp) and
+// kernels.h -- internal launch interface between the C-ABI (cugp_capi.cpp and the files of DESIGN.md's source map) and
 // the gfx950 kernels (kernels.hip).  Not part of the public boundary.
 //
 // The structs and constants below are also what the host checks of the emulable device code (cov_device.h,

@@ -98,7 +98,7 @@ unsigned wgt_fetch(unsigned long long* out, unsigned cap)
 enum { WGT_TRSM = 0, WGT_DIAGUPD = 1, WGT_POTF2 = 2, WGT_STEPTILE = 3, WGT_BORDER = 4, WGT_LAUUM = 5, WGT_LEVEL = 6,
        WGT_TRTRI_DIAG = 7, WGT_WIDE = 8 };
 
-// Profiling level 5 (cugp_capi.cpp TimedLaunch): a timed launch carries a slot in a device buffer and every workgroup
+// Profiling level 5 (handle.h TimedLaunch): a timed launch carries a slot in a device buffer and every workgroup
 // of it leaves its start in slot[0] (atomic min) and its end in slot[STAMP_STRIDE] (atomic max), on the chip-wide 100 MHz
 // clock (s_memrealtime): launch duration = first workgroup's first instruction .. last workgroup's last, with NOTHING
 // added to the stream -- the schedule is the untimed one (an event pair around a launch costs ~5 us of device time and
@@ -3210,7 +3210,7 @@ __global__ __launch_bounds__(256, 2) void k_sparse_gram(const double* __restrict
 // ------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------
-// Per-launch timing without extra packets on the stream (profiling level 4, cugp_capi.cpp TimedLaunch): the next launch
+// Per-launch timing without extra packets on the stream (profiling level 4, handle.h TimedLaunch): the next launch
 // of a timed kernel on this thread goes out through hipExtLaunchKernelGGL with a start / stop event pair, which take
 // the dispatch's OWN begin / end timestamps -- what rocprofv3 --kernel-trace reports for it.  (An event pair recorded
 // around the launch, level 3, brackets the ~6 us between the record in front of it and its first workgroup as well

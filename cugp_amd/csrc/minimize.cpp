@@ -153,7 +153,7 @@ extern "C" int cugp_cg_minimize_n(cugp_objective_n_fn fn, void* ctx, double* the
     return rc;
 }
 
-// Internal (cugp_capi.cpp: cugp_cg_solve_loo; not in cugp.h): cugp_cg_minimize_n's loop, bit for bit, with the ITERATES as
+// Internal (cugp_capi.cpp: cg_iterates; not in cugp.h): cugp_cg_minimize_n's loop, bit for bit, with the ITERATES as
 // its record instead of every evaluation -- rows [theta, f] of the start and of the point each line search ended at when
 // that moved (the accepted step, or the best probe of a failed search); *nrows <- their number, *nevals <- evaluations.
 extern "C" int cugp_cg_minimize_n_iterates(cugp_objective_n_fn fn, void* ctx, double* theta, int nh, int budget,

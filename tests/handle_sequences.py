@@ -309,7 +309,7 @@ class CovsumModel:
             r.append(call("set_targets", self.Y))
         return r
 
-    # -- the transitions (cugp_capi.cpp: cugp_loglik, cugp_loglik_grad, enqueue_eval, cugp_append, set_theta)
+    # -- the transitions (cugp_capi.cpp: cugp_loglik, cugp_loglik_grad, enqueue_eval, set_theta; dense_features.cpp: cugp_append)
     def _loglik(self):
         if self.level == "stale":
             self.tail = [LL]
@@ -358,7 +358,7 @@ class CovsumModel:
                 Xa, ya = s.rows(kw["seed"], kw["k"], stream=2)
                 self.X, self.y = np.concatenate([self.X, Xa]), np.concatenate([self.y, ya])
                 # (a poisoned handle that holds its -- NaN -- inverse borders it, finds LL not finite and keeps nothing:
-                #  cugp_append's discard_eval, cugp_capi.cpp:2081-2083; behind an optimiser the twin replays the append)
+                #  the discard_eval at the end of cugp_append, dense_features.cpp; behind an optimiser the twin replays the append)
                 if self.level == "opt" or (self.level in ("full", "full_cont") and not self.poisoned):
                     self.tail.append(("append", (lo, self.n)))
                 else:
@@ -521,7 +521,7 @@ SP_TG = ("bound_targets", "bound_grad_targets", "bound_grad_z_targets", "predict
 
 
 class SparseModel:
-    """(X, y), Z, hp, targets.  Every evaluation of a side starts from the covariance of Z (sp_eval, cugp_capi.cpp: a side
+    """(X, y), Z, hp, targets.  Every evaluation of a side starts from the covariance of Z (sp_eval, sparse.cpp: a side
     is valid or evaluated afresh; evaluating one marks the other stale), so the twin is: fresh, data, Z, hp, targets."""
 
     def __init__(self, sub):
@@ -534,8 +534,8 @@ class SparseModel:
         self.hp_poison = False
 
     # Kuu (a NaN row of Z, hp_bad) or B (a NaN row of X) cannot be factored.  A failed evaluation of a side is an evaluation:
-    # it leaves the side valid over a NaN row and the other side stale (sp_eval, cugp_capi.cpp:2811-2823 for Kuu,
-    # :2897-2904 for B), and predictions of a side that is not `pd` are NaN (:3195) -- nothing the twin's route lacks.
+    # it leaves the side valid over a NaN row and the other side stale (sp_eval, sparse.cpp: the early return for Kuu,
+    # the end of the function for B), and predictions of a side that is not `pd` are NaN (sp_predict) -- nothing the twin's route lacks.
     # (Z is None in the generator's dry run behind an optimiser over Z that started healthy: it ended at finite values)
     poisoned = property(lambda self: self.hp_poison or bool(np.isnan(self.X).any()) or
                         (self.Z is not None and bool(np.isnan(self.Z).any())))
@@ -673,7 +673,7 @@ class BCMModel:
         self._reset()
 
     # one expert that cannot be factored: the sums of an evaluation are NaN, that expert's level moves as any other's
-    # (read_result_row, cugp_capi.cpp:1095-1112, sets factor_valid and inverse_valid whatever the row holds)
+    # (read_result_row, cugp_capi.cpp, sets factor_valid and inverse_valid whatever the row holds)
     poisoned = property(lambda self: self.hp_poison or any(isinstance(sd, tuple) for sd in self.seeds))
 
     def _reset(self, tail=()):

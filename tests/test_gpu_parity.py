@@ -600,7 +600,7 @@ def test_squared_dist_vs_oracle(gp_mod, oracle, n, d, c):
 
 
 def _bench_la_points(n, d=4):
-    """The inputs cugp_bench_la builds on the device (xorshift64, cugp_capi.cpp)."""
+    """The inputs cugp_bench_la builds on the device (xorshift64, la.cpp: cugp_bench_la_check)."""
     st = 88172645463325252
     m = (1 << 64) - 1
     out = np.empty(n * d)

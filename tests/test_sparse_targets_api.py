@@ -221,3 +221,13 @@ def test_the_build_knows_every_header_the_sources_include():
         with open(os.path.join(build.CSRC, f)) as fh:
             for inc in re.findall(r'^#include "([^"/]+)"', fh.read(), flags=re.M):
                 assert inc in listed, (f, inc)
+
+
+def test_the_build_lists_every_source_file():
+    """A file of csrc/ that build.SOURCES + build.HEADERS leaves out is not compiled or not hashed: an edit of it would
+    leave a stale library in place."""
+    from cugp_amd import build
+    listed = set(build.SOURCES + build.HEADERS)
+    assert len(listed) == len(build.SOURCES + build.HEADERS)
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith((".cpp", ".hip", ".h"))}
+    assert on_disk == listed, (sorted(on_disk - listed), sorted(listed - on_disk))

@@ -2,8 +2,9 @@
 // workgroups are dispatched late: no free slot) or SLOWED EXECUTION (dispatched at once, but each workgroup runs long on
 // CUs it shares with tile products)?  Diagnostic build of the whole library with -DCUGP_WGTIMES: every workgroup of the
 // chain and tile kernels stamps s_memrealtime (100 MHz) at its start and end (kernels.hip, WgTimer).
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCUGP_WGTIMES -w -x hip tools/wgtimes.hip cugp_amd/csrc/cugp_capi.cpp \
-//         cugp_amd/csrc/bcm.cpp cugp_amd/csrc/minimize.cpp -o tools/bin/wgtimes          (kernels.hip is included here)
+//   S=cugp_amd/csrc; hipcc --offload-arch=gfx950 -O3 -std=c++17 -DCUGP_WGTIMES -w -x hip tools/wgtimes.hip $S/cugp_capi.cpp \
+//         $S/predict.cpp $S/dense_features.cpp $S/sparse.cpp $S/la.cpp $S/group.cpp $S/bcm.cpp $S/minimize.cpp \
+//         -o tools/bin/wgtimes                                                      (kernels.hip is included here)
 //   tools/bin/wgtimes [n=8192] [detail=0] [key=value ...]     (tuning keys of kernels.h, e.g. 16=224)
 #pragma clang diagnostic ignored "-Wunused-result"
 #pragma clang diagnostic ignored "-Wunused-value"
