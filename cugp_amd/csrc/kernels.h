@@ -117,6 +117,7 @@ void launch_kcross(const double* X, int n, int d, int npad, const double* Xt, in
                    const CovFn& cf, double* Ks, hipStream_t s, Batch bt = {});
 
 // ---- blocked right-looking Cholesky (N4) on the lower triangle of A (npad x npad, ld = npad) ----
+// (definitions: chol_gfx950.h, each launcher behind its kernel)
 // d16: 16x16 diagonal inverses [nt][8][256]; d64: the two 64x64 diagonal inverses of each block [nt][2][4096]
 void launch_potf2(double* A, int ld, int kb, double* d16, double* d64, double* logdet_part, hipStream_t s,
                   Batch bt = {});
@@ -124,6 +125,19 @@ void launch_potf2(double* A, int ld, int kb, double* d16, double* d64, double* l
 // from the block's 64x64 inverses (w: the running right-hand side, y at first); kb = nt - 1 launches that workgroup alone
 void launch_trsm_inv64(double* A, const double* d64, int ld, int kb, int nt, hipStream_t s, Batch bt = {},
                        double* zv = nullptr, const double* wv = nullptr);   // 3-phase, 64x64 inverses
+// trailing update of step kb fused with the factorisation of diagonal block kb+1 (tickets[kb] must be 0)
+// wcol > 0: only the tile columns [kb+1, kb+1+wcol) (two-speed form: the near window)
+// ks: first k tile of the pass (sub-panels: the k tiles [ks, kb], at most SUBPANEL_MAX of them); < 0: kb alone
+constexpr int SUBPANEL_MAX = 4;
+void launch_syrk_step(double* A, int ld, int kb, int nt, double* d16, double* d64, double* logdet_part,
+                      unsigned* tickets, hipStream_t s, Batch bt = {}, int wcol = 0, int ks = -1,
+                      const double* zv = nullptr, double* wv = nullptr);
+                      // zv / wv (when given): nt - kb - 1 more workgroups apply w_i -= L(i,kb) z_kb to the rows below
+// wide trailing update: tile columns [ca, cb) (rows >= column) -= L(., k tiles [k0, k0+kw)) L(.)^T; returns tiles
+int launch_syrk_wide(double* A, int ld, int nt, int k0, int kw, int ca, int cb, int rev, hipStream_t s, Batch bt = {});
+
+// ---- triangular inverse by recursive doubling (N7) and K^-1 = U U^T (N8) ----
+// (definitions: inverse_gfx950.h, each launcher behind its kernel)
 void launch_trtri_diag(const double* A, int ld, int kb, int nblocks, const double* d64, double* T, double* U,
                        hipStream_t s, Batch bt = {});
 // inverse of the hand-over block of rows [a, a + wb) in one launch: diagonal-tile inverses + every doubling level inside
@@ -137,18 +151,6 @@ constexpr int TRTRI_BLOCK_MAXWG = 64;
 int launch_trtri_block(const double* L, const double* d64, double* T, double* U, int ld, int a, int wb, unsigned* ctr,
                        double* poison, int ctr_off, hipStream_t s, Batch bt = {}, int gcap = TRTRI_BLOCK_MAXWG,
                        double* hstat = nullptr);
-// trailing update of step kb fused with the factorisation of diagonal block kb+1 (tickets[kb] must be 0)
-// wcol > 0: only the tile columns [kb+1, kb+1+wcol) (two-speed form: the near window)
-// ks: first k tile of the pass (sub-panels: the k tiles [ks, kb], at most SUBPANEL_MAX of them); < 0: kb alone
-constexpr int SUBPANEL_MAX = 4;
-void launch_syrk_step(double* A, int ld, int kb, int nt, double* d16, double* d64, double* logdet_part,
-                      unsigned* tickets, hipStream_t s, Batch bt = {}, int wcol = 0, int ks = -1,
-                      const double* zv = nullptr, double* wv = nullptr);
-                      // zv / wv (when given): nt - kb - 1 more workgroups apply w_i -= L(i,kb) z_kb to the rows below
-// wide trailing update: tile columns [ca, cb) (rows >= column) -= L(., k tiles [k0, k0+kw)) L(.)^T; returns tiles
-int launch_syrk_wide(double* A, int ld, int nt, int k0, int kw, int ca, int cb, int rev, hipStream_t s, Batch bt = {});
-
-// ---- triangular inverse by recursive doubling (N7) and K^-1 = U U^T (N8) ----
 // off: element offset of the diagonal sub-matrix (nt tiles) the level works on inside L, T, U
 // (these four return the edge of the output tiles they launched with, in 32s: 4 = 128x128, 2 = 64x64, 0 = nothing)
 int launch_trtri_level(const double* L, double* T, double* U, int ld, int nt, int s, int step, hipStream_t st,

@@ -13,7 +13,7 @@ tests/test_gpu_numerical_failure.py asserts of the library.
 """
 import numpy as np
 
-MICRO, BUILD, TILE = 16, 64, 128            # kernels.hip: the micro tile of panel_factor, the build tile, the MFMA tile
+MICRO, BUILD, TILE = 16, 64, 128            # chol_gfx950.h: the micro tile of panel_factor, the build tile, the MFMA tile
 KINDS = ("negative", "zero", "minus_one")
 
 
@@ -59,7 +59,7 @@ def positions(n):
 def nan_flow_cholesky(K):
     """The unblocked (left-looking, column by column) lower factor of K in fp64 under np.errstate(all="ignore"), which never
     raises.  Column j is scaled by r = 1 / sqrt(pivot), the diagonal entry included (pivot * r), as every implementation
-    that multiplies by a reciprocal square root does (kernels.hip: panel_factor): a negative pivot gives r = NaN, a zero
+    that multiplies by a reciprocal square root does (chol_gfx950.h: panel_factor): a negative pivot gives r = NaN, a zero
     pivot r = inf and 0 * inf = NaN on the diagonal and below it -- with a division by sqrt(pivot) instead, a zero pivot
     would leave a finite 0 on the diagonal.  NaN flows on through every later column.  The strict upper triangle is zero.
     The reference for what IEEE arithmetic alone gives."""

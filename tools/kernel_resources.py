@@ -1,7 +1,11 @@
 """Registers, LDS and scratch of every kernel of libcugp.so, from the code-object notes hipcc writes for gfx950
-(no GPU needed):  python tools/kernel_resources.py > profiles/r03_kernel_resources.txt
+(no GPU needed):  python tools/kernel_resources.py > profiles/kernel_resources.txt
 Workgroups per CU = min over the limits: 512 unified VGPRs per SIMD lane (VGPR + AGPR, allocation granule 8),
 160 KiB LDS per CU (static + the dynamic size the launcher asks for), 32 waves per CU.
+The dynamic size is read from the source text, which states it once: the LDS argument of the kernel's launch line
+(CUGP_LAUNCH / hipLaunchKernelGGL in kernels.hip and the headers it includes) names a constant, and a static_assert beside
+that constant's definition pins its number.  A launch whose LDS argument has no such static_assert, or a kernel launched
+with two different sizes, ends the run with a message that names the kernel.
 --digest: instead of the table, one line per kernel with a sha256 of its instructions (label to .Lfunc_end, without
 comments, .loc / .file / .section / .text lines and blank lines, block labels .LBB<n>_ and the kernel's own symbol
 normalised, so that a renamed kernel or one that became a template keeps its digest) -- equal digests before and after a
@@ -14,23 +18,71 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "cugp_amd", "csrc", "kernels.hip")
-# dynamic LDS per launch (kernels.hip: set_big_lds / the launchers): Geo<4>::LDS, Geo<2>::LDS, POTF2_LDS, TRTRI_LDS
-GEMM4, GEMM2, POTF2, TRTRI = 66048, 33280, 79360, 78336
-DYN = {"k_lauum<4>": GEMM4, "k_lauum<2>": GEMM2, "k_trtri_level<4>": GEMM4, "k_trtri_level<2>": GEMM2,
-       "k_trtri_border<4>": GEMM4, "k_trtri_border<2>": GEMM2, "k_predict_gemm": GEMM4, "k_test_gemm": GEMM4,
-       "k_syrk_wide": GEMM4, "k_syrk_step": POTF2, "k_potf2": POTF2, "k_trtri_diag": TRTRI,
-       "k_predict_cov<4>": GEMM4, "k_predict_cov<2>": GEMM2, "k_targets_alpha": GEMM2, "k_targets_alpha_batched": GEMM2, "k_targets_mean": GEMM2, "k_append_kinv": GEMM2,
-       "k_loo_product<4>": GEMM4, "k_loo_product<2>": GEMM2, "k_sparse_gram": GEMM4,
-       "k_sparse_predict_cov<4>": GEMM4, "k_sparse_predict_cov<2>": GEMM2,
-       "k_syrk_wide8": GEMM4, "k_lauum8": GEMM4, "k_trtri_border8": GEMM4,
-       "k_syrk_wide_rest": GEMM2, "k_lauum_rest": GEMM2, "k_trtri_border_rest": GEMM2}
+SRC = sys.argv[-1] if sys.argv[-1].endswith(".hip") else os.path.join(ROOT, "cugp_amd", "csrc", "kernels.hip")
 
+
+def source_text(path, seen=None):
+    """the file and, in place of each #include "x.h" line, the text of x.h beside it; macro definitions dropped (the body of
+    CUGP_LAUNCH is a launch line of its own parameters)"""
+    seen = set() if seen is None else seen
+    out, in_macro = [], False
+    for ln in open(path).read().split("\n"):
+        if in_macro or ln.startswith("#define"):
+            in_macro = ln.endswith("\\")
+            continue
+        m = re.match(r'#include "([^"]+)"', ln)
+        inc = os.path.join(os.path.dirname(path), m.group(1)) if m else None
+        if inc and os.path.exists(inc) and inc not in seen:
+            seen.add(inc)
+            out.append(source_text(inc, seen))
+        else:
+            out.append(ln)
+    return "\n".join(out)
+
+
+def call_args(txt, start):
+    """top-level arguments of the call whose opening parenthesis is at txt[start]"""
+    args, depth, cur = [], 0, ""
+    for ch in txt[start:]:
+        if ch in "([{":
+            depth += 1
+            if depth == 1:
+                continue
+        elif ch in ")]}":
+            depth -= 1
+            if depth == 0:
+                break
+        if ch == "," and depth == 1:
+            args.append(cur)
+            cur = ""
+        else:
+            cur += ch
+    return [" ".join(a.split()) for a in args + [cur]]
+
+
+def dynamic_lds(txt):
+    """{kernel as the code object's demangled name spells it, or a template's stem: bytes of dynamic LDS it is launched with}"""
+    txt = re.sub(r"//[^\n]*", "", txt)
+    pinned = {m.group(1): int(m.group(2)) for m in re.finditer(r"static_assert\(([\w<>:]+) == (\d+),", txt)}
+    dyn = {}
+    for m in re.finditer(r"\b(?:CUGP_LAUNCH|hipLaunchKernelGGL)\(", txt):
+        a = call_args(txt, m.end() - 1)
+        kernel, lds = a[0], a[3]
+        cov = re.match(r"CUGP_COV_KERNEL\(\w+, (\w+)\)$", kernel)          # every <ARD, KIND> of the pass: the stem
+        kernel = cov.group(1) if cov else re.sub(r"^\((.*)\)$", r"\1", kernel)
+        if lds != "0" and lds not in pinned:
+            sys.exit("kernel_resources: %s is launched with dynamic LDS '%s', which no static_assert pins to a number" % (kernel, lds))
+        size = 0 if lds == "0" else pinned[lds]
+        if dyn.setdefault(kernel, size) != size:
+            sys.exit("kernel_resources: %s is launched with two dynamic LDS sizes, %d and %d" % (kernel, dyn[kernel], size))
+    return dyn
+
+
+DYN = {} if "--digest" in sys.argv else dynamic_lds(source_text(SRC))      # (before the compile: a launch it cannot read ends the run at once)
 with tempfile.TemporaryDirectory() as td:
     out = os.path.join(td, "k.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-x", "hip", "-S",
-                           "--cuda-device-only", "-o", out, sys.argv[-1] if sys.argv[-1].endswith(".hip") else SRC],
-                          stderr=subprocess.DEVNULL)
+                           "--cuda-device-only", "-o", out, SRC], stderr=subprocess.DEVNULL)
     txt = open(out).read()
 if "--digest" in sys.argv:
     names = sorted(re.findall(r"^    \.name:\s+(\S+)$", txt[txt.index("amdhsa.kernels:"):], re.M))
@@ -54,7 +106,7 @@ for b in blocks[1:]:
     short = re.sub(r"^void |cugp::|\(.*$", "", dem)
     vg, sg = int(f("vgpr_count")), int(f("sgpr_count"))
     lds, scr, thr = int(f("group_segment_fixed_size")), int(f("private_segment_fixed_size")), int(f("max_flat_workgroup_size"))
-    dyn = DYN.get(short, 0)
+    dyn = DYN.get(short, DYN.get(short.split("<")[0], 0))
     waves = thr // 64
     regs = -(-(-(-vg // 4) * 4 + agpr) // 8) * 8   # unified file: accumulation registers follow the (4-aligned) VGPRs
     by_reg = (512 // regs) * 4 // waves if regs else 99

@@ -97,79 +97,8 @@ __device__ __forceinline__ void tile_sub_store_all(double* __restrict__ C, int l
 }
 
 // ---- round 5: the 8-wave tile product once more, now with the C tile in the epilogue ----
-// 512 threads, waves 4 x 2, 32 x 64 outputs per wave (2 x 4 MFMA tiles, 32 accumulators), the LDS image of the 4-wave
-// product; two such workgroups put FOUR waves on every SIMD, so while one workgroup is in its prologue or epilogue the
-// other still has two waves per SIMD -- what the fp64 MFMA pipe needs to run at its full rate.
-template <bool NEGA>
-__device__ __forceinline__ void tile_nt8(const double* __restrict__ Ag, int lda, const double* __restrict__ Bg, int ldb,
-                                         int kbeg, int kend, d4 (&acc)[2][4], char* smem)
-{
-    typedef Geo<4> G;
-    const int t = opaque_tid();
-    const int lane = t & 63, wave = t >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int srow = t >> 3, skp = t & 7;                 // 64 rows per pass, 2 passes
-    const double* ag = Ag + (size_t)srow * lda + 2 * skp;
-    const double* bg = Bg + (size_t)srow * ldb + 2 * skp;
-    d2 ra[2], rb[2];
-    int wa[2], wb[2];
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        wa[q] = skp * G::PLANE + (srow + 64 * q) * 16;
-        wb[q] = G::OPER + skp * G::PLANE + bpos<4>(srow + 64 * q) * 16;
-    }
-    const int fr = lane & 15, fk = lane >> 4;
-    const int abase = (fk >> 1) * G::PLANE + (wr * 32 + fr) * 16 + (fk & 1) * 8;
-    const int bbase = G::OPER + (fk >> 1) * G::PLANE + (wc * 64 + fr) * 16 + (fk & 1) * 8;
-    const int nk = (kend - kbeg) / BK;
-    if (nk <= 0) return;
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        ra[q] = *(const d2*)(ag + (size_t)(64 * q) * lda + kbeg);
-        rb[q] = *(const d2*)(bg + (size_t)(64 * q) * ldb + kbeg);
-    }
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-        *(d2*)(smem + wa[q]) = NEGA ? -ra[q] : ra[q];
-        *(d2*)(smem + wb[q]) = rb[q];
-    }
-    __syncthreads();
-#define STAGE8(HALF, MORE, KNEXT)                                                                   \
-    do {                                                                                            \
-        const char* cur_ = smem + (HALF) * G::STAGE;                                                \
-        char* nxt_ = smem + (1 - (HALF)) * G::STAGE;                                                \
-        const bool more_ = (MORE);                                                                  \
-        if (more_) {                                                                                \
-            const int k_ = (KNEXT);                                                                 \
-            _Pragma("unroll") for (int q = 0; q < 2; q++) {                                         \
-                ra[q] = *(const d2*)(ag + (size_t)(64 * q) * lda + k_);                             \
-                rb[q] = *(const d2*)(bg + (size_t)(64 * q) * ldb + k_);                             \
-            }                                                                                       \
-        }                                                                                           \
-        _Pragma("unroll") for (int kk = 0; kk < BK / 4; kk++) {                                     \
-            double a[2], b[4];                                                                      \
-            _Pragma("unroll") for (int m = 0; m < 2; m++) a[m] = *(const double*)(cur_ + abase + kk * 2 * G::PLANE + m * 256); \
-            _Pragma("unroll") for (int n = 0; n < 4; n++) b[n] = *(const double*)(cur_ + bbase + kk * 2 * G::PLANE + n * 256); \
-            _Pragma("unroll") for (int m = 0; m < 2; m++)                                           \
-                _Pragma("unroll") for (int n = 0; n < 4; n++)                                       \
-                    acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[m], b[n], acc[m][n], 0, 0, 0); \
-        }                                                                                           \
-        if (more_) {                                                                                \
-            _Pragma("unroll") for (int q = 0; q < 2; q++) {                                         \
-                *(d2*)(nxt_ + wa[q]) = NEGA ? -ra[q] : ra[q];                                       \
-                *(d2*)(nxt_ + wb[q]) = rb[q];                                                       \
-            }                                                                                       \
-        }                                                                                           \
-        __syncthreads();                                                                            \
-    } while (0)
-    int kt = 0;
-    for (; kt + 1 < nk; kt += 2) {
-        STAGE8(0, true, kbeg + (kt + 1) * BK);
-        STAGE8(1, kt + 2 < nk, kbeg + (kt + 2) * BK);
-    }
-    if (kt < nk) STAGE8(0, false, 0);
-#undef STAGE8
-}
+// (tile_nt8 itself went into the library with the eight-wave launches -- tile_gfx950.h -- and is used from there: the
+//  copy this file carried made the call below ambiguous)
 
 // MODE: 0 C -= acc in the epilogue (plain), 1 plain product store (no C read: C = -acc), 2 neither
 template <int MODE>
