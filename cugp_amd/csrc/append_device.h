@@ -7,7 +7,8 @@
 //   cov_device.h                   tri_index, wave_sum
 //   kernels.hip / host_emul.h      the d4 typedef, the device vocabulary, and CUGP_DYN_LDS(name): the workgroup's dynamic
 //                                  LDS (kernels.hip: the extern __shared__ declaration; the shim: a null pointer)
-//   kernels.hip / the check        the tile product: acc_zero, tile_nt, tile_accum_store
+//   tile_gfx950.h / the check      the tile product: acc_zero, tile_nt, tile_accum_store
+// The launchers (launch_append_border, launch_append_kinv) are in dense_features_gfx950.h.
 #pragma once
 
 // ------------------------------------------------------------------------------------------

@@ -695,7 +695,7 @@ int cugp_bcm_predict(cugp_bcm* b, const double* Xt, int nt, double* mean, double
 }
 
 // ---- combination rules on latent expert distributions (include/cugp.h: CUGP_COMBINE_*) ----
-// Host twin of k_poe_reduce_mode (kernels.hip): the same operations in the same order, every one rounded on its own.
+// Host twin of k_poe_reduce_mode (predict_gfx950.h): the same operations in the same order, every one rounded on its own.
 int cugp_poe_combine(const double* rows, int K, int nt, int mode, double sf2, double sn2, int with_noise, double* mean,
                      double* var)
 {

@@ -9,10 +9,18 @@
 //   kernels.h        TILE, ExpertPtrs, Batch, SUBPANEL_MAX, tune and the TUNE_* keys, the launcher prototypes
 //   kernels.hip      d2, d4, GP, WGT and the WGT_* kinds, LaunchStamp, CUGP_LAUNCH, take_stamp, tri_count, set_big_lds
 //   cov_device.h     tri_index, wave_sum
-//   kernels.hip      (the tile product) Geo, GEMM_LDS, MT, MTS, NMT, NLT, POTF2_LDS, tile_nt, tile_nt8 and their epilogues
-// Declares for inverse_gfx950.h: TRTRI_LDS, mt_off, micro_mma_nn, micro_mma_acc_b, micro_store; for the other uniform-K
-// launchers (inverse_gfx950.h, launch_loo_product in kernels.hip): split_round.
+//   tile_gfx950.h    Geo, GEMM_LDS, tile_nt, tile_nt8 and their epilogues
+// Declares for inverse_gfx950.h: MT, TRTRI_LDS, mt_off, micro_mma_nn, micro_mma_acc_b, micro_store; for the other uniform-K
+// launchers (inverse_gfx950.h, launch_loo_product in dense_features_gfx950.h): split_round.
 #pragma once
+
+// diagonal-block kernels work on 16x16 micro tiles (one MFMA tile)
+constexpr int MT = 16;                             // micro tile (one MFMA tile)
+constexpr int MTS = MT * (MT + 1);                 // doubles per LDS micro tile, rows padded to 17
+constexpr int NMT = TILE / MT;                     // 8 micro tiles per edge
+constexpr int NLT = NMT * (NMT + 1) / 2;           // 36 lower micro tiles
+constexpr int POTF2_LDS = (NLT * MTS + TILE) * 8;  // tiles + 1/L_ii  = 79360 B
+static_assert(POTF2_LDS == 79360, "dynamic LDS of the diagonal-block Cholesky");
 
 // Tiles (ti >= tj) of the tile columns [0, wcol) of a lower triangle, row by row: row r holds min(r + 1, wcol)
 // tiles.  idx -> (ti, tj), both relative to the region's first column.  wcol >= the triangle's size gives the

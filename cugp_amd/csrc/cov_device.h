@@ -9,9 +9,9 @@
 //   kernels.h                      TILE, HyperScalars, ExpertPtrs, KERNEL_*
 //   kernels.hip / host_emul.h      the d2 and d4 typedefs, GP, and the device vocabulary (__device__, __global__,
 //                                  __shared__, threadIdx, blockIdx, gridDim, __syncthreads, __shfl_xor, __shfl_down)
-// What stays in kernels.hip although it uses the helpers below: trace_body with finalize_sums (agent-scope atomics,
-// s_waitcnt, a fence: the device only) and build_body (the launch stamp), with its siblings cross_body and
-// predict_cov_finish_body beside it.
+// What needs the device although it uses the helpers below: trace_body with finalize_sums (agent-scope atomics,
+// s_waitcnt, a fence) and build_body (the launch stamp) with its sibling cross_body, in eval_gfx950.h;
+// predict_cov_finish_body in predict_gfx950.h.  The launchers of the kernels below are in predict_gfx950.h.
 #pragma once
 
 // lower-triangular tile index: idx -> (ti >= tj)

@@ -7,8 +7,8 @@
 //   kernels.h        TILE, ExpertPtrs, Batch, TRTRI_BLOCK_MAXWG, tune and the TUNE_* keys, the launcher prototypes
 //   kernels.hip      d2, d4, GP, WGT and the WGT_* kinds, LaunchStamp, CUGP_LAUNCH, take_stamp, tri_count, set_big_lds
 //   cov_device.h     tri_index
-//   kernels.hip      (the tile product) Geo, GEMM_LDS, MT, tile_nt, tile_nt8, tile_store_t and their epilogues
-//   chol_gfx950.h    TRTRI_LDS, mt_off, micro_mma_nn, micro_mma_acc_b, micro_store, split_round
+//   tile_gfx950.h    Geo, GEMM_LDS, tile_nt, tile_nt8, tile_store_t and their epilogues
+//   chol_gfx950.h    MT, TRTRI_LDS, mt_off, micro_mma_nn, micro_mma_acc_b, micro_store, split_round
 #pragma once
 
 // ---- triangular inverse.  [A 0; C B]^-1 = [TA 0; -TB C TA, TB] with A = tiles [.., b0), B = tiles [b0, ..):

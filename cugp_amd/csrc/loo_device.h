@@ -1,5 +1,5 @@
 // loo_device.h -- leave-one-out cross-validation from the factored model (cugp_loo, cugp_loo_predict):
-// every pass of it except the one tile product (k_loo_product: kernels.hip).  Plain fp64 arithmetic, __syncthreads and
+// every pass of it except the one tile product (k_loo_product: dense_features_gfx950.h, with the launchers).  Plain fp64 arithmetic, __syncthreads and
 // wave shuffles: no MFMA, no atomics, no inline assembly, no stamps, and no #ifdef around arithmetic -- the host check
 // (tools/loo_host_check.cpp) runs this text behind tools/host_emul.h under -fsanitize=address,undefined.
 //

@@ -1,5 +1,5 @@
 // sparse_device.h -- sparse variational GP regression on inducing points (cugp_sparse_*; Titsias 2009, DESIGN.md section
-// 25): every pass of it except the products on the MFMA tile (k_sparse_gram and the existing tile kernels: kernels.hip)
+// 25): every pass of it except the products on the MFMA tile (k_sparse_gram: sparse_gfx950.h, with the launchers)
 // and what reads the labels -- q, y'y, H and the final sums: sparse_targets_device.h, which the handle's own y runs with
 // p = 1.  Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no inline assembly, no stamps, and no
 // #ifdef around arithmetic -- the host check (tools/sparse_host_check.cpp) runs this text behind tools/host_emul.h under

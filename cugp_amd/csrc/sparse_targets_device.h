@@ -1,7 +1,7 @@
 // sparse_targets_device.h -- the passes of the sparse model that depend on the labels: p targets over one set of inducing
 // points (cugp_sparse_*_targets), and the handle's own y, which is the case p = 1 (section 25).
 // Everything that costs O(N M^2) -- W_c, P, B and its inverse, W_c R^T, both trace passes -- is shared by the p targets
-// (sparse_device.h, kernels.hip); only what is below reads Y.  Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no
+// (sparse_device.h, sparse_gfx950.h); only what is below reads Y.  Plain fp64 arithmetic, __syncthreads and wave shuffles: no MFMA, no atomics, no
 // inline assembly and no #ifdef around arithmetic -- the host check (tools/sparse_targets_host_check.cpp) runs this text
 // behind tools/host_emul.h under -fsanitize=address,undefined.
 //

@@ -260,7 +260,7 @@ def test_classic_schedule_at_33_tiles(gp_mod, oracle):
 @pytest.mark.parametrize("n", [1500, 4200])
 def test_fused_finalize_equals_separate_launch(gp_mod, n):
     """Key 12: the last block of k_trace takes the final sums (1 << 30: always) or k_finalize does (0): the same sums
-    in the same order (kernels.hip finalize_sums), so the same bits -- replayed from a captured graph (key 5 = 1; the
+    in the same order (eval_gfx950.h finalize_sums), so the same bits -- replayed from a captured graph (key 5 = 1; the
     inverse after the factorisation, key 3 = 0, so the evaluation is one stream) and launch by launch."""
     g = single(gp_mod, n, {PIPE_BLOCK: 0})
     for graphs in (1, 0):

@@ -54,7 +54,7 @@ def same_bits(a, b):
 
 
 def cov_forms(nt):
-    """Values of tuning key 20 -> the form of the covariance product they select (kernels.hip: predict_cov_shape, with
+    """Values of tuning key 20 -> the form of the covariance product they select (predict_gfx950.h: predict_cov_shape, with
     t128 lower 128-tiles of the padded nt x nt result): None, the default 1024: 64x64 tiles, the k range split as far
     as n allows; 0: 128x128 tiles (k_predict_cov<4>), no split; 4 t128: the smallest value that still takes 64x64
     tiles -- there are more than 2 t128 of them, so the quotient that sets the split is 1: no split."""

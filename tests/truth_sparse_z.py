@@ -83,7 +83,7 @@ Z_SLOTS = 512                     # SPARSE_Z_SLOTS of cugp_amd/csrc/kernels.h (t
 
 
 def z_ranges(rows_pad, mpad, d, slots=Z_SLOTS):
-    """sparse_z_shape (cugp_amd/csrc/kernels.hip) replayed: the 64-row tiles of each row range of one k_trace_cross_z launch
+    """sparse_z_shape (cugp_amd/csrc/sparse_gfx950.h) replayed: the 64-row tiles of each row range of one k_trace_cross_z launch
     over rows_pad rows -- the last range is what the clamp to the tile count leaves."""
     tiles = rows_pad // 64
     ranges = max(1, min(slots // (mpad // 64), rows_pad // 256))

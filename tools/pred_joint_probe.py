@@ -45,7 +45,7 @@ def timed(fn):
 
 
 def cov_shape(nt, n, aim):
-    """the launch shape kernels.hip predict_cov_shape picks (tile edge, lower tiles, kend, split)"""
+    """the launch shape predict_cov_shape (predict_gfx950.h) picks (tile edge, lower tiles, kend, split)"""
     ntpad = (nt + 127) // 128 * 128
     t128 = (ntpad // 128) * (ntpad // 128 + 1) // 2
     wm = 2 if (aim > 0 and 4 * t128 <= aim) else 4

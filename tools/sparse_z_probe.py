@@ -35,7 +35,7 @@ def median_ms(fn, reps):
 
 
 def z_shape(rows_pad, mpad, d):
-    """kernels.hip's sparse_z_shape: (row tiles, per workgroup, ranges per column tile)."""
+    """sparse_z_shape of sparse_gfx950.h: (row tiles, per workgroup, ranges per column tile)."""
     tiles, nct = rows_pad // 64, mpad // 64
     ranges = max(1, min(512 // nct, rows_pad // 256))
     while ranges > 1 and ranges * mpad * d * 8 > 1 << 30:
