@@ -54,6 +54,7 @@ class ShardedBCM:
     cannot check that without a collective); an injected expert_factory makes its own experts and is not told.
     kernel "matern32_ard" | "matern52_ard": ARD experts of that Matern kind (.kernel then reports "matern32" /
     "matern52" beside .ard); ard=True itself is squared-exponential only.
+    kernel "rq" | "rq_ard": rational quadratic experts (.kernel "rq"; nh = 4 with .ard False, or d + 3 with .ard True).
     ard=True (every rank alike): ARD experts, nh = d + 2 shared hyper-parameters, every row buffer 1 + nh wide; an
     injected expert_factory is then called as factory(n, d, device, ard=True).  d: the input dimension, only needed on
     a rank that sees none of the experts' data (it sizes the rows)."""
@@ -62,9 +63,11 @@ class ShardedBCM:
                  kernel="se", ard=False, d=None):
         self.K = len(experts)
         kind, self.ard = _gp.kernel_spec(kernel, ard)
-        self.kernel = _gp.KERNEL_NAMES[kind]
-        # (the spelling Covsum and BCM take: "matern52_ard" sets ard by itself, ard=True goes with "se" alone)
+        self.kernel = _gp.REPORTED_NAMES[kind]
+        # (the spelling Covsum and BCM take: "matern52_ard" / "rq_ard" set ard by themselves, ard=True goes with "se" alone)
         self._kernel_arg = self.kernel + "_ard" if self.ard and self.kernel != "se" else self.kernel
+        # nh-wide rows and calls: ARD, or rational quadratic in either form ("rq": nh = 4, .ard False)
+        self._wide = _gp.is_wide(kind, self.ard)
         self.nh = 3
         if self.ard:
             if d is None:
@@ -72,7 +75,8 @@ class ShardedBCM:
                 if not seen:
                     raise ValueError("ard=True on a rank without any expert's data needs d")
                 d = np.asarray(seen[0][0]).shape[1]
-            self.nh = int(d) + 2
+        if self._wide:
+            self.nh = _gp.num_hyper(kind, self.ard, d if self.ard else 1)
         self._w = 1 + self.nh
         self.rank, self.world, self.group = rank, world, group
         self.mine = [k for k in range(self.K) if expert_owner(k, world) == rank]
@@ -386,7 +390,7 @@ class ShardedBCM:
     def cg_solve(self, budget=100):
         """cg_solve(BCM) (distributed_ver1.cpp:13-232) -- the library's host loop on the all-reduced
         objective; every rank runs it on identical numbers, so no hyper-parameter broadcast."""
-        theta, trace = (_gp.cg_minimize_n if self.ard else _gp.cg_minimize)(self.objective, self.hp, budget)
+        theta, trace = (_gp.cg_minimize_n if self._wide else _gp.cg_minimize)(self.objective, self.hp, budget)
         self.set_loghyper(theta)
         return trace
 

@@ -21,6 +21,7 @@ OBJECTIVE_N = C.CFUNCTYPE(None, C.c_void_p, _dp, C.c_int, _dp, _dp)
 
 CUGP_OK = 0
 CUGP_KERNEL_SE, CUGP_KERNEL_MATERN32, CUGP_KERNEL_MATERN52 = 0, 1, 2
+CUGP_KERNEL_RQ = 3          # rational quadratic: create calls of its own (cugp_create_rq), not a kind= of the others
 CUGP_COMBINE_POE, CUGP_COMBINE_GPOE, CUGP_COMBINE_BCM, CUGP_COMBINE_RBCM = 0, 1, 2, 3
 CUGP_COMBINE_REFERENCE = -1      # cugp_bcm_predict_grad / cugp_poe_combine_grad: the reference's product of the noisy predictions
 CUGP_ERR_INVALID, CUGP_ERR_NOMEM, CUGP_ERR_DEVICE, CUGP_ERR_NODEVICE = -1, -2, -3, -4
@@ -54,6 +55,7 @@ SIGNATURES = {
     "cugp_create_ard": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_create_ard_padded": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_create_ard_kernel": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_create_rq": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_num_hyper": (C.c_int, [C.c_void_p, _ip]),
     "cugp_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "cugp_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
@@ -176,6 +178,9 @@ SIGNATURES = {
     "cugp_bcm_create_ard_kernel": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "cugp_bcm_create_split_ard_kernel": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int,
                                                    C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_rq": (C.c_int, [C.c_int, _ip, C.c_int, _ip, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_bcm_create_split_rq": (C.c_int, [_dp, _dp, C.c_int, C.c_int, C.c_int, C.c_int, _ip, C.c_int,
+                                           C.POINTER(C.c_void_p)]),
     "cugp_bcm_num_hyper": (C.c_int, [C.c_void_p, _ip]),
     "cugp_bcm_set_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "cugp_bcm_get_loghyper_ard": (C.c_int, [C.c_void_p, _dp, C.c_int]),

@@ -41,7 +41,7 @@ struct cugp_bcm {
     std::vector<int> rows;
     int d = 0;
     // ARD (cugp_bcm_create_ard; for life): every expert is an ARD handle, nh = d + 2, and the rows of an evaluation are
-    // {LL, g[nh]}.  Every body below runs at the row width 1 + nh -- 4 for the isotropic calls, whose bits it keeps.
+    // {LL, g[nh]}.  Rational quadratic (cugp_bcm_create_rq): nh-wide too, nh = d + 3, or 4 with one tied length scale.  Every body below runs at the row width 1 + nh -- 4 for the isotropic calls, whose bits it keeps.
     bool ard = false;
     int nh = 3;
     std::vector<double> hp = {0, 0, 0};
@@ -63,7 +63,8 @@ int refuse_ard_bcm(const cugp_bcm* b, const char* call, const char* use)
 {
     if (!b->ard) return CUGP_OK;
     char buf[256];
-    snprintf(buf, sizeof buf, "%s: the BCM is ARD (d + 2 hyper-parameters); use %s", call, use);
+    if (b->kernel == CUGP_KERNEL_RQ) snprintf(buf, sizeof buf, "%s: the BCM is rational quadratic (%d hyper-parameters); use %s", call, b->nh, use);
+    else snprintf(buf, sizeof buf, "%s: the BCM is ARD (d + 2 hyper-parameters); use %s", call, use);
     return cugp_internal_fail(CUGP_ERR_INVALID, buf);
 }
 
@@ -80,7 +81,8 @@ int want_ard_bcm(const cugp_bcm* b, int nh, const char* call, bool pointers_ok =
         return cugp_internal_fail(CUGP_ERR_INVALID, buf);
     }
     if (nh != b->nh) {
-        snprintf(buf, sizeof buf, "%s: nh = %d, the BCM has d + 2 = %d hyper-parameters", call, nh, b->nh);
+        if (b->kernel == CUGP_KERNEL_RQ) snprintf(buf, sizeof buf, "%s: nh = %d, the rational quadratic BCM has %d hyper-parameters", call, nh, b->nh);
+        else snprintf(buf, sizeof buf, "%s: nh = %d, the BCM has d + 2 = %d hyper-parameters", call, nh, b->nh);
         return cugp_internal_fail(CUGP_ERR_INVALID, buf);
     }
     return CUGP_OK;
@@ -91,7 +93,10 @@ int expert_fetch(cugp_bcm* b, cugp_gp* e, double* ll, double* g)
     return b->ard ? cugp_loglik_grad_fetch_ard(e, ll, g, b->nh) : cugp_loglik_grad_fetch(e, ll, g);
 }
 
-int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel, bool ard, cugp_bcm** out);
+int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel, bool ard, cugp_bcm** out,
+               bool tied = false);
+int bcm_create_split(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices, int kernel,
+                     bool ard, cugp_bcm** out, bool tied = false);
 
 }  // namespace
 
@@ -130,19 +135,45 @@ int cugp_bcm_create_ard_kernel(int ndev, const int* devices, int nexperts, const
     return bcm_create(ndev, devices, nexperts, rows, d, kernel, true, out);
 }
 
+// every expert a rational quadratic handle (cugp_create_rq): ard = 1 nh = d + 3, ard = 0 (one length scale) nh = 4; the
+// _ard calls below with the BCM's nh.  The arguments are checked here, before any device call.
+int cugp_bcm_create_rq(int ndev, const int* devices, int nexperts, const int* rows, int d, int ard, cugp_bcm** out)
+{
+    if (!out || ndev <= 0 || !devices || nexperts <= 0 || !rows || d <= 0)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_create_rq: null argument, or ndev, nexperts, d not positive");
+    for (int k = 0; k < nexperts; k++)
+        if (rows[k] <= 0) return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_create_rq: an expert without rows");
+    if (ard != 0 && ard != 1)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_create_rq: ard must be 0 (one length scale) or 1 (one per dimension)");
+    return bcm_create(ndev, devices, nexperts, rows, d, CUGP_KERNEL_RQ, true, out, ard == 0);
+}
+
+int cugp_bcm_create_split_rq(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices, int ard,
+                             cugp_bcm** out)
+{
+    if (!X || !y || !out || !devices || N <= 0 || D <= 0 || K <= 0 || K > N || ndev <= 0)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_create_split_rq: null argument, or N, D, K, ndev not positive, or K > N");
+    if (ard != 0 && ard != 1)
+        return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_bcm_create_split_rq: ard must be 0 (one length scale) or 1 (one per dimension)");
+    return bcm_create_split(X, y, N, D, K, ndev, devices, CUGP_KERNEL_RQ, true, out, ard == 0);
+}
+
 }  // extern "C"
 
 namespace {
-int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel, bool ard, cugp_bcm** out)
+// kernel == CUGP_KERNEL_RQ comes from the two calls above alone (ard set; tied: one length scale)
+int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int d, int kernel, bool ard, cugp_bcm** out,
+               bool tied)
 {
     if (!out || ndev <= 0 || !devices || nexperts <= 0 || !rows || d <= 0) return CUGP_ERR_INVALID;
-    if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52) return CUGP_ERR_INVALID;
+    const bool rq = kernel == CUGP_KERNEL_RQ && ard;
+    if (!rq && (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52)) return CUGP_ERR_INVALID;
     cugp_bcm* b = new (std::nothrow) cugp_bcm;
     if (!b) return CUGP_ERR_NOMEM;
     b->d = d;
     b->kernel = kernel;
     b->ard = ard;
-    if (ard) { b->nh = d + 2; b->hp.assign(b->nh, 0.0); }
+    if (ard) { b->nh = (rq && tied ? 1 : d) + (rq ? 1 : 0) + 2; b->hp.assign(b->nh, 0.0); }
     // Common padded size (identity padding) so that the experts can share launches -- unless their row counts
     // differ by more than a tile or ~6 %: then padding the small ones would cost more than it gains.
     int nmax = 0, nmin = rows[0];
@@ -159,8 +190,9 @@ int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int 
     for (int k = 0; k < nexperts; k++) {
         DeviceSet& ds = b->sets[k % nsets];
         cugp_gp* g = nullptr;
-        int rc = ard ? cugp_create_ard_kernel(rows[k], d, ds.device, pad_to, kernel, &g)
-                     : cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
+        int rc = rq    ? cugp_create_rq(rows[k], d, ds.device, pad_to, tied ? 0 : 1, &g)
+                 : ard ? cugp_create_ard_kernel(rows[k], d, ds.device, pad_to, kernel, &g)
+                       : cugp_create_kernel(rows[k], d, ds.device, pad_to, kernel, &g);
         if (rc) { cugp_bcm_destroy(b); return rc; }
         b->experts.push_back(g);                        // (owned by b from here on: cugp_bcm_destroy)
         rc = cugp_mark_bcm_expert(g);                   // (cugp_append refuses the experts of a BCM; no stream priorities)
@@ -186,10 +218,10 @@ int bcm_create(int ndev, const int* devices, int nexperts, const int* rows, int 
 
 // BCM.cpp:85-110 -- expert k gets rows [k*floor(N/K), ...), the last one also the remainder
 int bcm_create_split(const double* X, const double* y, int N, int D, int K, int ndev, const int* devices, int kernel,
-                     bool ard, cugp_bcm** out)
+                     bool ard, cugp_bcm** out, bool tied)
 {
     if (!X || !y || N <= 0 || D <= 0 || K <= 0 || K > N) return CUGP_ERR_INVALID;
-    if (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52) return CUGP_ERR_INVALID;
+    if (!(kernel == CUGP_KERNEL_RQ && ard) && (kernel < CUGP_KERNEL_SE || kernel > CUGP_KERNEL_MATERN52)) return CUGP_ERR_INVALID;
     std::vector<int> rows(K), off(K);
     const int part = N / K;
     int start = 0;
@@ -198,7 +230,7 @@ int bcm_create_split(const double* X, const double* y, int N, int D, int K, int 
         rows[k] = (k == K - 1) ? (N - start) : part;
         start += part;
     }
-    int rc = bcm_create(ndev, devices, K, rows.data(), D, kernel, ard, out);
+    int rc = bcm_create(ndev, devices, K, rows.data(), D, kernel, ard, out, tied);
     if (rc) return rc;
     for (int k = 0; k < K; k++) {
         rc = cugp_bcm_set_expert_data(*out, k, X + (size_t)off[k] * D, y + off[k]);

@@ -163,7 +163,7 @@ static int comm_buffers(cugp_comm* c, int per, int w)
 // none), all-gather everybody's rows, -> rows_out[world * per][4]: rank r's i-th expert (global expert r + i * world)
 // in row r * per + i, {LL, g0, g1, g2}; slots beyond a rank's experts are zero.  Everything between the first kernel of
 // the evaluation and the pinned copy of the gathered rows is ONE in-order sequence on the evaluation's stream.
-// nh: the gradient's entries -- rows of 1 + nh doubles (3 from the isotropic call, d + 2 from the _ard call)
+// nh: the gradient's entries -- rows of 1 + nh doubles (3 from the isotropic call, the BCM's nh from the _ard call)
 static int allgather_rows(cugp_bcm* b, cugp_comm* c, int per, int nh, double* rows_out)
 {
     int nlocal = 0;

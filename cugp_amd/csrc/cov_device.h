@@ -154,12 +154,59 @@ __device__ __forceinline__ void ard_entry(double s, double sf2, double& kf, doub
         matern_entry<KIND>(s, sf2, kf, dk, hh);
     }
 }
+// ---- rational quadratic (GPML covRQiso / covRQard), KERNEL_RQ: the ARD route only ----
+// One entry from the WEIGHTED squared distance s = sum u_c^2 (sqdist_4x4<true>), alpha = exp(theta_alpha) and h2a =
+// RN(0.5 / alpha), both evaluated on the host.  One log1p, one exp and one division per entry, every line one rounding:
+//   u  = RN(s h2a)                      s / (2 alpha)
+//   L  = log1p(u)
+//   e  = exp(-RN(alpha L))              (1 + u)^-alpha
+//   kf = RN(sf2 e)
+//   r  = RN(1 / RN(1 + u))
+//   hh = RN(kf r)                       H = Kf / (1 + u):  dK / dtheta_c = H u_c^2,  dk / dx*_c = -H (x*_c - x_c) w_c^2
+//   da = RN(kf RN(alpha RN(RN(u r) - L)))   A = dK / dtheta_alpha = Kf alpha (u / (1 + u) - L)
+// u r - L cancels to -u^2 / 2 for small u: its error is absolute, ~2 eps u, and A's ~Kf alpha 2 eps u (tests/truth_rq.py
+// counts it).  No FMA contraction: the CPU copy of these lines (tests/truth_rq.py entry_fp64) takes the same roundings.
+// Extremes: s = 0 -> u = 0, L = 0, e = 1, r = 1: kf = hh = sf2 and da = 0 exactly.  alpha -> inf approaches SE's
+// sf2 exp(-s / 2).  An alpha whose exp overflowed (inf, h2a = 0) gives inf * 0 = NaN in every output.
+struct ShapeArgs { double alpha, h2a; };
+// the shape parameters of a handle's family, which lie behind the d weights (wts) in the staging area
+template <int KIND>
+__device__ __forceinline__ ShapeArgs shape_args(const double* __restrict__ wts, int d)
+{
+    if constexpr (KIND == KERNEL_RQ) return ShapeArgs{wts[d], wts[d + 1]};
+    else return ShapeArgs{0.0, 0.0};
+}
+__device__ __forceinline__ void rq_entry(double s, double sf2, double alpha, double h2a, double& kf, double& hh, double& da)
+{
+#pragma clang fp contract(off)
+    const double u = s * h2a;
+    const double L = log1p(u);
+    const double e = exp(-(alpha * L));
+    kf = sf2 * e;
+    const double r = 1.0 / (1.0 + u);
+    hh = kf * r;
+    da = kf * (alpha * (u * r - L));
+}
+// the same with the family's shape parameters: da = dK / dtheta_shape (RQ; the other kinds have none: 0, dead code)
+template <int KIND>
+__device__ __forceinline__ void ard_entry(double s, double sf2, const ShapeArgs& sh, double& kf, double& hh, double& da)
+{
+    if constexpr (KIND == KERNEL_RQ) {
+        rq_entry(s, sf2, sh.alpha, sh.h2a, kf, hh, da);
+    } else {
+        ard_entry<KIND>(s, sf2, kf, hh);
+        da = 0.0;
+    }
+}
 // the value of one entry without the noise term (the three passes that need no derivative)
 template <bool ARD, int KIND>
-__device__ __forceinline__ double kernel_value(double d2, const DivBy& dl, double sf2)
+__device__ __forceinline__ double kernel_value(double d2, const DivBy& dl, double sf2, const ShapeArgs& sh = ShapeArgs{0.0, 0.0})
 {
     double kf, dk, hh;
-    if constexpr (ARD)
+    if constexpr (KIND == KERNEL_RQ) {
+        static_assert(ARD || KIND != KERNEL_RQ, "the rational quadratic kernel has ARD instantiations only");
+        rq_entry(d2, sf2, sh.alpha, sh.h2a, kf, hh, dk);
+    } else if constexpr (ARD)
         ard_entry<KIND>(d2, sf2, kf, hh);
     else if constexpr (KIND == KERNEL_SE)
         kf = sf2 * exp(div_by(-d2 * 0.5, dl));                    // covkernel.cpp:89
@@ -211,8 +258,9 @@ __device__ __forceinline__ void targets_outer_4x4(const double* __restrict__ A, 
 // differences are zero: it has no share in any g_c); sum W o K takes Kf (+ sn2 on the diagonal); (2) a second sweep over
 // the feature chunks, the X tiles staged again, DC per-dimension sums at a time in registers; wave sums by shuffles, the
 // four waves added in a fixed order.
-// Partials: part[c * nblocks + block], c = 0 .. d - 1 the dimensions, d: sum W o K, d + 1: tr W (column-major, so that
-// k_finalize_ard's lanes read a column contiguously).  No fused final sums: k_finalize_ard / k_finalize_targets follow.
+// Partials: part[c * nblocks + block], c = 0 .. d - 1 the dimensions, then the family's shape columns (RQ: one, sum W o
+// dK/dtheta_alpha, off-diagonal entries doubled, reduced as the next two; the other kinds: none), then sum W o K and tr W
+// (column-major, so that k_finalize_ard's lanes read a column contiguously).  No fused final sums: k_finalize_ard / k_finalize_targets follow.
 // TARGETS: W = m K^-1 - sum_t alpha_t alpha_t^T from the target-major AV ([m][npad]), single handle; else W = K^-1 -
 // alpha alpha^T from the vector AV, and bt (batched): blockIdx.y selects the expert -- X, n, K^-1, alpha and the
 // expert's OWN partials from its table entry; hyper-scalars and weights are the group's one copy (hd).  The arithmetic
@@ -249,7 +297,9 @@ __device__ __forceinline__ void trace_ard_body(const double* __restrict__ X, int
 #pragma unroll
         for (int b = 0; b < 4; b++) aj[b] = AV[j0 + col4(tx, b)];
     }
-    double s2 = 0.0, s3 = 0.0;
+    double s2 = 0.0, s3 = 0.0, s4 = 0.0;                 // s4: sum W o dK/dtheta_shape (NS columns; RQ: one)
+    constexpr int NS = shape_count(KIND);
+    const ShapeArgs sh = shape_args<KIND>(wts, d);
     const double dm = (double)m;
 #pragma unroll
     for (int a = 0; a < 4; a++) {
@@ -265,7 +315,13 @@ __device__ __forceinline__ void trace_ard_body(const double* __restrict__ X, int
             if (i < n && j < n && (ti != tj || j <= i)) {
                 const double w = TARGETS ? dm * kv[b] - S[a][b] : kv[b] - ai * aj[b];
                 double kf, hh;
-                ard_entry<KIND>(wk[a][b], h.signal_var, kf, hh);
+                if constexpr (NS == 0) {
+                    ard_entry<KIND>(wk[a][b], h.signal_var, kf, hh);
+                } else {
+                    double da;
+                    ard_entry<KIND>(wk[a][b], h.signal_var, sh, kf, hh, da);
+                    if (i != j) s4 += 2.0 * (w * da);      // (the diagonal's da is zero: no share)
+                }
                 if (i == j) {
                     kf += h.noise_var;
                     s2 += w * kf;
@@ -280,8 +336,15 @@ __device__ __forceinline__ void trace_ard_body(const double* __restrict__ X, int
     }
     s2 = wave_sum(s2); s3 = wave_sum(s3);
     if ((t & 63) == 0) { red[0][t >> 6] = s2; red[1][t >> 6] = s3; }
+    if constexpr (NS > 0) {
+        s4 = wave_sum(s4);
+        if ((t & 63) == 0) red[2][t >> 6] = s4;
+    }
     __syncthreads();
-    if (t < 2) part[(size_t)(d + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    if (t < 2) part[(size_t)(d + NS + t) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    if constexpr (NS > 0) {
+        if (t == 2) part[(size_t)d * nblocks + blockIdx.x] = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
+    }
     for (int c0 = 0; c0 < d; c0 += DC) {
         const int dc = (d - c0 < DC) ? (d - c0) : DC;
         __syncthreads();
@@ -329,7 +392,7 @@ __device__ __forceinline__ void trace_ard_body(const double* __restrict__ X, int
 // One 64 x 64 (test x training) tile per workgroup, the thread's 4 x 4 micro-tile and column pairs as k_cross's (16-byte
 // loads of Ks and V rows).  SE, and SE with ARD, read G from Ks (k_cross's own exp, no second one: the ARD weights enter
 // through the finish alone, so the two instantiations are the same code); the Matern kinds take the squared distance --
-// ARD: the weighted one -- from sqdist_4x4<ARD> and G = H of matern_entry, one exp(-a) per entry.  The second sweep takes
+// ARD: the weighted one -- from sqdist_4x4<ARD> and G = H of matern_entry (RQ: of rq_entry), one exp per entry.  The second sweep takes
 // the UNWEIGHTED differences (k_predict_grad_finish applies s_c once per output).  Per feature, X and Xt staged
 // through LDS DC features at a time: the DIFFERENCE x*_c - x_ic is formed first and then multiplied -- the algebraically
 // equal x*_c sum(G alpha) - sum(G alpha x_c) cancels where |x| >> |x - x'|.  A thread adds its four columns in index order,
@@ -359,12 +422,15 @@ __device__ __forceinline__ void predict_grad_body(const double* __restrict__ X, 
         const HyperScalars& h = ARD ? *hd : h_arg;
         sqdist_4x4<ARD>(Xt, X, nt, n, d, t0, i0, xs, ys, G, ARD ? ard_weights(hd) : nullptr, ws);
         const DivBy dl = div_prepare(h.ell_sq);
+        ShapeArgs sh = ShapeArgs{0.0, 0.0};
+        if constexpr (KIND == KERNEL_RQ) sh = shape_args<KIND>(ard_weights(hd), d);
 #pragma unroll
         for (int a = 0; a < 4; a++)
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 double kf, dk, hh;
-                matern_entry<KIND>(ARD ? G[a][b] : div_by(G[a][b], dl), h.signal_var, kf, dk, hh);
+                if constexpr (KIND == KERNEL_RQ) rq_entry(G[a][b], h.signal_var, sh.alpha, sh.h2a, kf, hh, dk);
+                else matern_entry<KIND>(ARD ? G[a][b] : div_by(G[a][b], dl), h.signal_var, kf, dk, hh);
                 G[a][b] = hh;
             }
     }

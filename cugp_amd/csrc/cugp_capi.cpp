@@ -104,7 +104,11 @@ HyperScalars scalars(const cugp_gp* g)
     return HyperScalars{g->ard ? 1.0 : std::exp(g->theta[0] * 2), std::exp(sf[0] * 2), std::exp(sf[1] * 2)};
 }
 
-static size_t hs_bytes(const cugp_gp* g) { return sizeof(HyperScalars) + (g->ard ? (size_t)g->d * sizeof(double) : 0); }
+// (behind the d weights: the family's shape parameters as the kernels read them -- RQ: alpha and 0.5 / alpha)
+static size_t hs_bytes(const cugp_gp* g)
+{
+    return sizeof(HyperScalars) + (g->ard ? (size_t)(g->d + 2 * shape_count(g->kernel)) * sizeof(double) : 0);
+}
 
 // ARD: the pinned staging area always holds the current theta's scalars and weights (written where theta is set, with
 // the handle's stream idle), so every user of the ARD kernels only has to enqueue the copy in front of its launches
@@ -112,7 +116,12 @@ static void stage_ard(cugp_gp* g)
 {
     *g->hhs = scalars(g);
     double* w = (double*)(g->hhs + 1);
-    for (int c = 0; c < g->d; c++) w[c] = std::exp(-g->theta[c]);
+    for (int c = 0; c < g->d; c++) w[c] = std::exp(-g->theta[g->tied ? 0 : c]);
+    if (g->kernel == KERNEL_RQ) {
+        const double alpha = std::exp(g->theta[g->nh - 3]);
+        w[g->d] = alpha;
+        w[g->d + 1] = 0.5 / alpha;
+    }
 }
 
 static int upload_hs(cugp_gp* g, hipStream_t s)
@@ -127,7 +136,7 @@ static int upload_hs(cugp_gp* g, hipStream_t s)
 int cov_fn(cugp_gp* g, hipStream_t s, const HyperScalars* hd, CovFn* cf)
 {
     if (g->ard) hd = g->dhs;
-    *cf = CovFn{g->kernel, g->ard, scalars(g), hd};
+    *cf = CovFn{g->kernel, g->ard, scalars(g), hd, g->tied};
     return hd ? upload_hs(g, s) : CUGP_OK;
 }
 
@@ -135,7 +144,8 @@ static int refuse_ard(const cugp_gp* g, const char* call, const char* use)
 {
     if (!g->ard) return CUGP_OK;
     char buf[256];
-    snprintf(buf, sizeof buf, "%s: the handle is ARD (d + 2 hyper-parameters); use %s", call, use);
+    if (g->kernel == KERNEL_RQ) snprintf(buf, sizeof buf, "%s: the handle is rational quadratic (%d hyper-parameters); use %s", call, g->nh, use);
+    else snprintf(buf, sizeof buf, "%s: the handle is ARD (d + 2 hyper-parameters); use %s", call, use);
     return fail(CUGP_ERR_INVALID, buf);
 }
 
@@ -1081,7 +1091,17 @@ int cugp_create_ard_kernel(int n, int d, int device, int npad_min, int kernel, c
     return create_handle(n, d, device, npad_min, true, out, kernel);
 }
 
-int cugp::create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel)
+// Rational quadratic (GPML covRQiso / covRQard; cugp.h): ard = 1 one length scale per dimension (nh = d + 3), ard = 0 one
+// for all (nh = 4).  Either runs the ARD route.
+int cugp_create_rq(int n, int d, int device, int npad_min, int ard, cugp_gp** out)
+{
+    if (!out || n <= 0 || d <= 0 || npad_min < 0)
+        return fail(CUGP_ERR_INVALID, "cugp_create_rq: null out, or n, d not positive, or npad_min negative");
+    if (ard != 0 && ard != 1) return fail(CUGP_ERR_INVALID, "cugp_create_rq: ard must be 0 (one length scale) or 1 (one per dimension)");
+    return create_handle(n, d, device, npad_min, true, out, KERNEL_RQ, ard == 0);
+}
+
+int cugp::create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel, bool tied)
 {
     if (!out || n <= 0 || d <= 0) return fail(CUGP_ERR_INVALID, "cugp_create: n, d must be positive");
     int cnt = 0;
@@ -1093,8 +1113,13 @@ int cugp::create_handle(int n, int d, int device, int npad_min, bool ard, cugp_g
     g->n = n; g->d = d; g->device = device;
     g->ard = ard;
     g->kernel = kernel;
-    if (ard) { g->nh = d + 2; g->theta.assign(g->nh, 0.0); g->last_g.assign(g->nh, NAN); }
-    const size_t nrow = ard ? (size_t)ARD_ROW_GRAD + g->nh : 8, ncol = g->nh;
+    g->tied = ard && tied;
+    if (ard) {
+        g->nh = (g->tied ? 1 : d) + shape_count(kernel) + 2;
+        g->ncol = d + shape_count(kernel) + 2;
+        g->theta.assign(g->nh, 0.0); g->last_g.assign(g->nh, NAN);
+    }
+    const size_t nrow = ard ? (size_t)ARD_ROW_GRAD + g->nh : 8, ncol = g->ncol;
     g->nt = ((n > npad_min ? n : npad_min) + TILE - 1) / TILE;
     g->npad = g->nt * TILE;
     g->nblocks_trace = trace_num_blocks(g->npad);
@@ -1261,7 +1286,7 @@ int cugp_get_loghyper(const cugp_gp* g, double hp[3])
 }
 
 // the _ard calls' common argument check, before any device call: no null argument and a possible nh (the handle is not
-// looked at before that), then an ARD handle and nh == d + 2
+// looked at before that), then an nh-wide handle (ARD, or rational quadratic in either form) and nh == the handle's
 static int want_ard(const cugp_gp* g, int nh, const char* call, bool pointers_ok = true)
 {
     char buf[256];
@@ -1273,8 +1298,9 @@ static int want_ard(const cugp_gp* g, int nh, const char* call, bool pointers_ok
         snprintf(buf, sizeof buf, "%s: the handle is isotropic (3 hyper-parameters); create it with cugp_create_ard", call);
         return fail(CUGP_ERR_INVALID, buf);
     }
-    if (nh != g->d + 2) {
-        snprintf(buf, sizeof buf, "%s: nh = %d, the handle has d + 2 = %d hyper-parameters", call, nh, g->d + 2);
+    if (nh != g->nh) {
+        if (g->kernel == KERNEL_RQ) snprintf(buf, sizeof buf, "%s: nh = %d, the rational quadratic handle has %d hyper-parameters", call, nh, g->nh);
+        else snprintf(buf, sizeof buf, "%s: nh = %d, the handle has d + 2 = %d hyper-parameters", call, nh, g->nh);
         return fail(CUGP_ERR_INVALID, buf);
     }
     return CUGP_OK;
@@ -1670,7 +1696,7 @@ void gp_gradient(void* ctx, const double th[3], double gr[3])
 int cugp_cg_solve_ard(cugp_gp* g, int budget, double* trace, int trace_cap, int* nevals)
 {
     if (!g) return fail(CUGP_ERR_INVALID, "cugp_cg_solve_ard: null handle");
-    if (const int rc = want_ard(g, g->d + 2, "cugp_cg_solve_ard")) return rc;
+    if (const int rc = want_ard(g, g->nh, "cugp_cg_solve_ard")) return rc;
     return cg_solve(g, budget, trace, trace_cap, nevals);
 }
 

@@ -204,7 +204,7 @@ int cugp_set_targets(cugp_gp* g, const double* Y, int m)
         HIPCHK(hipHostMalloc((void**)&g->tg.hout, row * sizeof(double), hipHostMallocDefault));
         g->tg.mpad = mpad;
     }
-    if ((rc = ensure(&g->tg.part, (size_t)g->nblocks_trace * g->nh))) return rc;
+    if ((rc = ensure(&g->tg.part, (size_t)g->nblocks_trace * g->ncol))) return rc;
     hipStream_t s = g->stream;
     HIPCHK(hipMemsetAsync(g->tg.y, 0, cnt * sizeof(double), s));
     HIPCHK(hipMemsetAsync(g->tg.z, 0, cnt * sizeof(double), s));
@@ -311,7 +311,7 @@ int cugp_cg_solve_targets(cugp_gp* g, int budget, double* trace, int trace_cap, 
 namespace {
 size_t loo_small_count(const cugp_gp* g)
 {
-    return (size_t)(LOO_PT_ROWS + 1 + g->npad / 64) * g->npad + (size_t)g->nh * g->nblocks_trace;
+    return (size_t)(LOO_PT_ROWS + 1 + g->npad / 64) * g->npad + (size_t)g->ncol * g->nblocks_trace;
 }
 
 // the evaluation that leaves K^-1 and alpha (a stale handle: re-evaluated, as predict_device does), then the LOO launches

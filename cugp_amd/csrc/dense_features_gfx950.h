@@ -225,11 +225,84 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize_targets(const double* 
         hout[i] = __hip_atomic_load(out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The same for a handle with ONE tied length scale over dlen length columns (nl: length and shape columns; nh = nl - dlen
+// + 3): k_finalize_ard_tied's order for the columns (all waves, then the index-order sum by thread 0), this kernel's for everything else.  Lines repeated, not shared, so
+// that k_finalize_targets keeps its instructions.
+__global__ __launch_bounds__(FIN_THREADS) void k_finalize_targets_tied(const double* __restrict__ Z, int npad, int n, int m,
+                                                                       double logdet, const double* __restrict__ part,
+                                                                       int nblocks, int nl, int dlen,
+                                                                       const HyperScalars* __restrict__ hd,
+                                                                       double* __restrict__ out, double* __restrict__ hout)
+{
+#pragma clang fp contract(off)
+    const HyperScalars h = *hd;
+    const int o = nl - dlen + 1, nh = o + 2;
+    __shared__ double red[FIN_THREADS];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const bool dead = logdet != logdet;
+    double* ll_each = out + 1 + nh;
+    for (int tg = wave; tg < m; tg += FIN_THREADS / 64) {
+        const double* zr = Z + (size_t)tg * npad;
+        double q = 0.0;
+        for (int i = lane; i < npad; i += 64) q = q + zr[i] * zr[i];
+        q = wave_sum(q);
+        if (lane == 0) ll_each[tg] = -0.5 * (q + logdet + n * 1.83787);
+    }
+    double g0 = 0.0, s2 = 0.0;                             // (thread 0's)
+    for (int c0 = 0; c0 < nl + 2; c0 += FIN_THREADS) {     // k_finalize_ard_tied's order: every column on its wave, FIN_THREADS at a time
+        const int cc = (nl + 2 - c0 < FIN_THREADS) ? (nl + 2 - c0) : FIN_THREADS;
+        __syncthreads();
+        for (int c = wave; c < cc; c += FIN_THREADS / 64) {
+            const double* col = part + (size_t)(c0 + c) * nblocks;
+            double s = 0.0;
+            for (int i = lane; i < nblocks; i += 64) s += col[i];
+            s = wave_sum(s);
+            if (lane == 0) red[c] = s;
+        }
+        __syncthreads();
+        if (t == 0)
+            for (int c = c0; c < c0 + cc; c++) {
+                const double s = red[c - c0];
+                if (c < dlen) g0 = c == 0 ? s / 2.0 : g0 + s / 2.0;
+                else if (c < nl) out[2 + (c - dlen)] = dead ? logdet : s / 2.0;
+                else if (c == nl) s2 = s;
+                else {
+                    const double s3 = s;
+                    out[1 + o] = dead ? logdet : (2.0 * s2 - 2.0 * h.noise_var * s3) / 2.0;
+                    out[2 + o] = dead ? logdet : (2.0 * h.noise_var * s3) / 2.0;
+                }
+            }
+    }
+    if (t == 0) out[1] = dead ? logdet : g0;
+    __syncthreads();
+    double ll = 0.0;
+    for (int t0 = 0; t0 < m; t0 += FIN_THREADS) {
+        __syncthreads();
+        if (t0 + t < m) red[t] = __hip_atomic_load(ll_each + t0 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        if (t == 0) {
+            const int cnt = (m - t0 < FIN_THREADS) ? (m - t0) : FIN_THREADS;
+            for (int i = 0; i < cnt; i++) ll = ll + red[i];
+        }
+    }
+    if (t == 0) {
+        out[0] = ll;
+        hout[0] = ll;
+    }
+    for (int i = 1 + t; i < 1 + nh + m; i += FIN_THREADS)
+        hout[i] = __hip_atomic_load(out + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 void launch_finalize_targets(const double* Z, int npad, int n, int d, int m, double logdet, const double* part,
                              const CovFn& cf, double* out, double* hout, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_finalize_targets, dim3(1), dim3(FIN_THREADS), 0, s, Z, npad, n, m, logdet, part,
-                       tri_count(npad / KT), is_ard(cf) ? d : -1, cf.h, is_ard(cf) ? cf.hd : nullptr, out, hout);
+    const int nl = d + shape_count(cf.kind);
+    if (is_ard(cf) && cf.tied)
+        hipLaunchKernelGGL(k_finalize_targets_tied, dim3(1), dim3(FIN_THREADS), 0, s, Z, npad, n, m, logdet, part,
+                           tri_count(npad / KT), nl, d, cf.hd, out, hout);
+    else
+        hipLaunchKernelGGL(k_finalize_targets, dim3(1), dim3(FIN_THREADS), 0, s, Z, npad, n, m, logdet, part,
+                           tri_count(npad / KT), is_ard(cf) ? nl : -1, cf.h, is_ard(cf) ? cf.hd : nullptr, out, hout);
 }
 
 // ---- appending observations: the launchers of append_device.h's kernels ----
@@ -318,6 +391,11 @@ void launch_trace_loo(const double* X, int n, int d, int npad, const CovFn& cf, 
     const int nblocks = tri_count(npad / KT);
     hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_loo), dim3(nblocks), dim3(256), 0, s, X, n, d, npad, cf.h, cf.hd, P, alpha,
                        b, part);
-    hipLaunchKernelGGL(k_loo_finalize, dim3(1), dim3(256), 0, s, (const double*)part, nblocks, is_ard(cf) ? d : 1,
-                       cf.h.noise_var, out, hout);
+    const int nl = is_ard(cf) ? d + shape_count(cf.kind) : 1;
+    if (is_ard(cf) && cf.tied)
+        hipLaunchKernelGGL(k_loo_finalize_tied, dim3(1), dim3(256), 0, s, (const double*)part, nblocks, nl, d,
+                           cf.h.noise_var, out, hout);
+    else
+        hipLaunchKernelGGL(k_loo_finalize, dim3(1), dim3(256), 0, s, (const double*)part, nblocks, nl, cf.h.noise_var, out,
+                           hout);
 }

@@ -54,6 +54,7 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
     sqdist_4x4<ARD>(X, X, n, n, d, i0, j0, xs, ys, d2v, ARD ? ard_weights(hd) : nullptr, ws);
     double out[4][4];
     const DivBy dl = div_prepare(h.ell_sq);
+    const ShapeArgs sh = shape_args<KIND>(ARD ? ard_weights(hd) : nullptr, d);
 #pragma unroll
     for (int a = 0; a < 4; a++)
 #pragma unroll
@@ -64,7 +65,7 @@ __device__ __forceinline__ void build_body(const double* __restrict__ X, int n, 
             if (!ARD && full == 2) {
                 v = (i == j) ? 0.0 : div_by(d2v[a][b], dl);    // covkernel.cpp:143-151 (squared distance / c)
             } else {
-                v = kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var);   // covkernel.cpp:89
+                v = kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var, sh);   // covkernel.cpp:89
                 if (i == j) v += h.noise_var;                            // covkernel.cpp:93-94
             }
             out[a][b] = in ? v : ((i == j) ? 1.0 : 0.0);                // identity padding
@@ -132,6 +133,7 @@ __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, 
     __shared__ double ws[DC];
     sqdist_4x4<ARD>(Xt, X, nt, n, d, t0, i0, xs, ys, d2v, wts, ws);
     const DivBy dl = div_prepare(h.ell_sq);
+    const ShapeArgs sh = shape_args<KIND>(wts, d);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const int tr = t0 + ty * 4 + a;
@@ -139,7 +141,7 @@ __device__ __forceinline__ void cross_body(const double* __restrict__ X, int n, 
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int i = i0 + col4(tx, b);
-            o[b] = (tr < nt && i < n) ? kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var) : 0.0;
+            o[b] = (tr < nt && i < n) ? kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var, sh) : 0.0;
         }
         double* p = Ks + (size_t)tr * npad + i0 + tx * 2;
         *(d2*)p = (d2){o[0], o[1]};
@@ -517,7 +519,8 @@ __global__ __launch_bounds__(256) void k_trace(const double* __restrict__ X, int
 // Final sums of an ARD gradient evaluation, one workgroup.  LL, y'K^-1y and log|K| by finalize_sums (the isotropic
 // order and bits); then wave w takes the columns w, w + 16, ... of the trace partials: lane l adds the blocks l, l + 64,
 // ... ascending, the lanes by wave_sum -- a fixed order whatever the timing.  Results row (out, hout): [0] LL, [4] quad,
-// [5] log|K|, [6] status word, [8 + c] the d + 2 gradient components:
+// [5] log|K|, [6] status word, [8 + c] the d + 2 gradient components (d: the columns
+// with g_c = S_c / 2 -- a family's shape columns, RQ's one, count with the length columns: the launcher passes d + 1):
 //   g_c = S_c / 2 (c < d), g_d = (2 s2 - 2 sn2 s3) / 2, g_{d+1} = (2 sn2 s3) / 2   (the last two as k_finalize's g1, g2)
 // bt (batched): grid (1, experts) -- z, n, logdet_part, part and out from the expert's table entry, hout + expert * hstride
 __global__ __launch_bounds__(FIN_THREADS) void k_finalize_ard(const double* __restrict__ z, int npad, int n, int d,
@@ -554,6 +557,60 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize_ard(const double* __re
     }
 }
 
+// The same for a handle whose d length columns belong to ONE tied length scale (nh = nl - d + 3; nl: length and shape
+// columns).  Every column is summed as above -- wave w takes the columns w, w + 16, ..., lane l the blocks l, l + 64, ... --
+// TIED_COLS of them at a time into LDS; thread 0 then adds the d length columns' finished results S_c / 2 in index order
+// into g_0 (the chain rule at equal scales, and bit for bit the index-order sum of the untied handle's components); the
+// remaining columns' results move up to g_1 ...  The lines are k_finalize_ard's, repeated rather than shared through a
+// function, so that the kernel that exists keeps its instructions.
+constexpr int TIED_COLS = 1024;
+__global__ __launch_bounds__(FIN_THREADS) void k_finalize_ard_tied(const double* __restrict__ z, int npad, int n, int nl,
+                                                                   int d, const double* __restrict__ logdet_part, int nt,
+                                                                   const double* __restrict__ part, int nblocks,
+                                                                   const HyperScalars* __restrict__ hd,
+                                                                   double* __restrict__ out, double* __restrict__ hout,
+                                                                   size_t hstride, const ExpertPtrs* __restrict__ bt)
+{
+    if (bt) {
+        const ExpertPtrs& e = bt[blockIdx.y];
+        z = GP(e.z); n = e.n; logdet_part = GP(e.logdet); part = GP(e.part); out = GP(e.out);
+        hout += (size_t)blockIdx.y * hstride;
+    }
+    const HyperScalars h = *hd;
+    __shared__ double red[5 * FIN_THREADS];
+    static_assert(TIED_COLS <= 5 * FIN_THREADS, "the columns' sums reuse the final sums' LDS");
+    finalize_sums<FIN_THREADS, false>(z, npad, n, logdet_part, nt, nullptr, 0, h, out, hout, red);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int o = nl - d + 1;                              // components in front of g_f: the tied scale and the shape columns
+    double g0 = 0.0, s2 = 0.0;                             // (thread 0's)
+    for (int c0 = 0; c0 < nl + 2; c0 += TIED_COLS) {
+        const int cc = (nl + 2 - c0 < TIED_COLS) ? (nl + 2 - c0) : TIED_COLS;
+        __syncthreads();
+        for (int c = wave; c < cc; c += FIN_THREADS / 64) {
+            const double* col = part + (size_t)(c0 + c) * nblocks;
+            double s = 0.0;
+            for (int i = lane; i < nblocks; i += 64) s += col[i];
+            s = wave_sum(s);
+            if (lane == 0) red[c] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int c = c0; c < c0 + cc; c++) {
+                const double s = red[c - c0];
+                if (c < d) g0 = c == 0 ? s / 2.0 : g0 + s / 2.0;
+                else if (c < nl) { out[9 + (c - d)] = s / 2.0; hout[9 + (c - d)] = s / 2.0; }
+                else if (c == nl) s2 = s;
+                else {
+                    const double s3 = s;
+                    const double gf = (2.0 * s2 - 2.0 * h.noise_var * s3) / 2.0, gn = (2.0 * h.noise_var * s3) / 2.0;
+                    out[8 + o] = gf; out[9 + o] = gn;
+                    hout[8 + o] = gf; hout[9 + o] = gn;
+                }
+            }
+    }
+    if (threadIdx.x == 0) { out[8] = g0; hout[8] = g0; }
+}
+
 int trace_num_blocks(int npad) { return tri_count(npad / KT); }
 
 void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* alpha,
@@ -571,8 +628,14 @@ void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, cons
                        Kinv, alpha, part, bt.tab, fin);
     if (ard) {
         assert(hout && (out || bt.tab));
-        hipLaunchKernelGGL(k_finalize_ard, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, d, logdet_part,
-                           npad / TILE, part, nblocks, cf.hd, out, hout, (size_t)(ARD_ROW_GRAD + d + 2), bt.tab);
+        const int nl = d + shape_count(cf.kind);
+        const size_t hstride = (size_t)(ARD_ROW_GRAD + ard_num_hyper(cf, d));
+        if (cf.tied)
+            hipLaunchKernelGGL(k_finalize_ard_tied, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, nl, d,
+                               logdet_part, npad / TILE, part, nblocks, cf.hd, out, hout, hstride, bt.tab);
+        else
+            hipLaunchKernelGGL(k_finalize_ard, dim3(1, bt.count), dim3(FIN_THREADS), 0, s, z, npad, n, nl, logdet_part,
+                               npad / TILE, part, nblocks, cf.hd, out, hout, hstride, bt.tab);
     } else if (out != nullptr && !fuse) {
         launch_finalize(z, npad, n, logdet_part, npad / TILE, part, nblocks, cf.h, out, hout, s, cf.hd, bt);
     }

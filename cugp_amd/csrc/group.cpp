@@ -21,6 +21,9 @@ int cugp_group_create(cugp_gp* const* experts, int k, cugp_group** out)
     for (int i = 0; i < k; i++)
         if (experts[i]->ard != experts[0]->ard)
             return fail(CUGP_ERR_INVALID, "cugp_group_create: ARD and isotropic handles in one group (the experts of a group are all ARD or all isotropic)");
+    for (int i = 0; i < k; i++)
+        if (experts[i]->tied != experts[0]->tied)
+            return fail(CUGP_ERR_INVALID, "cugp_group_create: rational quadratic handles with one length scale and with one per dimension in one group (their result rows differ in width)");
     cugp_group* gr = new (std::nothrow) cugp_group;
     if (!gr) return fail(CUGP_ERR_NOMEM, "host allocation");
     gr->experts.assign(experts, experts + k);

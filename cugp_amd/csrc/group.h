@@ -29,7 +29,7 @@ void cugp_group_destroy(cugp_group* gr);
 // (counted by cugp_group_create / cugp_group_destroy, which the experts must outlive)
 int cugp_mark_bcm_expert(cugp_gp* gp);
 
-// Evaluate all experts at their (common) hyper-parameters; ll[k], g[nh k .. nh k + nh - 1] with nh = 3, or d + 2 for ARD
+// Evaluate all experts at their (common) hyper-parameters; ll[k], g[nh k .. nh k + nh - 1] with nh = 3, or the handles' nh (ARD d + 2, rational quadratic d + 3 or 4)
 // experts (g may be null when !want_grad).
 // Returns CUGP_ERR_INVALID without touching anything when the experts cannot be evaluated as a group right now
 // (different hyper-parameters, profiling on, missing data): the caller then evaluates them one by one.
@@ -52,7 +52,7 @@ int cugp_internal_fail(int code, const char* what);
 // halves of cugp_bcm_loglik_grad_allgather (comm.cpp; defined in bcm.cpp)
 // (dsend: [local expert][1 + nh], nh = the BCM's)
 int cugp_bcm_enqueue_rows_packed(cugp_bcm* b, double* dsend, void** stream);
-int cugp_bcm_nh(const cugp_bcm* b);              // 3, or d + 2 for an ARD BCM; 0 for null
+int cugp_bcm_nh(const cugp_bcm* b);              // 3, d + 2 for an ARD BCM, d + 3 or 4 for a rational quadratic one; 0 for null
 int cugp_bcm_is_ard(const cugp_bcm* b);
 int cugp_bcm_finish_rows(cugp_bcm* b);
 // {LL, g0, g1, g2} of the evaluation a single expert has in flight -> dst (device), on the expert's stream (an ARD

@@ -113,13 +113,19 @@ struct cugp_gp {
     double* dout = nullptr;
     unsigned* dtickets = nullptr;  // [0, nt): one arrival counter per factorisation step (k_syrk_step); [nt, 2 nt): the stage
                                    // counter of the hand-over block that starts at that tile row (k_trtri_block)
-    double* hout = nullptr;        // pinned, 8 doubles (ARD: 8 + d + 2)
+    double* hout = nullptr;        // pinned, 8 doubles (ARD: 8 + nh)
     int nblocks_trace = 0;
     // the nh log hyper-parameters and the gradient of the last evaluation: {log l, log sigma_f, log sigma_n}, or on an ARD
     // handle (cugp_create_ard; for life) [log l_1 .. log l_d, log sigma_f, log sigma_n].  hhs / dhs then hold the
-    // hyper-scalars FOLLOWED by the d weights exp(-theta_c); result rows are 8 + d + 2 doubles (kernels.h: ARD_ROW_GRAD)
+    // hyper-scalars FOLLOWED by the d weights exp(-theta_c); result rows are 8 + nh doubles (kernels.h: ARD_ROW_GRAD)
+    // A rational quadratic handle (cugp_create_rq, kernel == KERNEL_RQ) runs the ARD route whichever form it has: ard is
+    // true, theta is [log l_1 .. log l_d | log l (tied), log alpha, log sigma_f, log sigma_n], and alpha with 0.5 / alpha
+    // follow the d weights in hhs / dhs.  tied: one length scale, written into all d weights (nh = 4); the gradient
+    // partials keep their d + 1 + 2 columns (ncol), only the final sums add the length columns up.
     bool ard = false;
+    bool tied = false;
     int nh = 3;
+    int ncol = 3;                  // columns of the trace partials: 3, ARD d + shape_count(kernel) + 2
     std::vector<double> theta = {0, 0, 0}, last_g = {NAN, NAN, NAN};
     // covariance family (cugp.h CUGP_KERNEL_*, kernels.h KERNEL_*), for life, ARD handles included.  Read wherever one of
     // the four passes that evaluate the kernel function is launched; nothing else depends on it.
@@ -184,7 +190,7 @@ HyperScalars scalars(const cugp_gp* g);
 int cov_fn(cugp_gp* g, hipStream_t s, const HyperScalars* hd, CovFn* cf);
 int ensure_factor_bufs(cugp_gp* g);
 int ensure_inverse_bufs(cugp_gp* g);
-int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel = KERNEL_SE);
+int create_handle(int n, int d, int device, int npad_min, bool ard, cugp_gp** out, int kernel = KERNEL_SE, bool tied = false);
 int cov_factor_handle(cugp_gp* g, int tiles);
 int apply_stream_prio(cugp_gp* g);
 void sync_tuning(cugp_gp* g);

@@ -58,7 +58,12 @@ extern thread_local const int* t_tune;        // the tuning the launchers on thi
 inline int tune(int key) { return t_tune[key]; }
 
 // covariance family of a handle (cugp.h: CUGP_KERNEL_*), fixed when it is created
-enum { KERNEL_SE = 0, KERNEL_MATERN32 = 1, KERNEL_MATERN52 = 2, KERNEL_COUNT = 3 };
+// KERNEL_COUNT: the kinds the isotropic / ARD / sparse create calls take.  KERNEL_RQ (rational quadratic) lies beyond it: it
+// has a create call of its own (cugp_create_rq) because it carries a shape parameter, and no isotropic instantiation.
+enum { KERNEL_SE = 0, KERNEL_MATERN32 = 1, KERNEL_MATERN52 = 2, KERNEL_COUNT = 3, KERNEL_RQ = 3 };
+// hyper-parameters of a family that are neither a length scale nor a variance (RQ: alpha).  In theta they stand behind
+// the length scales and in front of sigma_f, sigma_n; their device values follow the d weights in the staging area.
+constexpr int shape_count(int kind) { return kind == KERNEL_RQ ? 1 : 0; }
 
 // Batched launches: the experts of a BCM on one device have the same shapes, so one launch can serve all of
 // them -- blockIdx.y picks the expert and the kernel takes its buffers from a device-resident table instead
@@ -96,11 +101,17 @@ struct HyperScalars {              // exp(2*theta) evaluated on the host, as the
 //        experts (build, cross-covariance, trace; not the joint-covariance epilogue) read the GROUP's one copy -- the lead
 //        expert's hd -- since the experts of a group share their hyper-parameters.  An ARD descriptor without hd is a
 //        programming error -- asserted, so checked only in builds without NDEBUG (the library's own build has none).
+//   kind == KERNEL_RQ: k = sf2 (1 + s / (2 alpha))^-alpha of the weighted squared distance s (cov_device.h rq_entry); always
+//        the ARD route.  Staging area: [HyperScalars][w_1 .. w_d][alpha, 0.5 / alpha], still one copy.  Gradient partials:
+//        [d length columns][shape_count(kind) shape columns][sum W o K][tr W].
+//   tied: the d weights are one length scale's (theta holds it once: nh = 1 + shape_count + 2).  The N^2 passes are the ARD
+//        ones; the final sums add the d length columns' results in index order into the one component.
 struct CovFn {
     int kind = KERNEL_SE;
     bool ard = false;
     HyperScalars h = {};
     const HyperScalars* hd = nullptr;
+    bool tied = false;
 };
 
 // ---- covariance (N1) ----
@@ -245,11 +256,15 @@ int trace_num_blocks(int npad);
 // out (when given): the launch also FINISHES the evaluation -- its last block (an arrival ticket, zero before the launch)
 // takes the final sums and writes out[0..5] (and hout) as launch_finalize would: z, logdet_part as there; batched:
 // taken from the experts' table, ticket = tickets[2 nt] of every expert
-// ARD: part[(d + 2) * trace_num_blocks(npad)]; results row out / hout (both mandatory, ARD_ROW_GRAD + d + 2 doubles): [0] LL,
-// [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row), [ARD_ROW_GRAD + c] g_c, c = 0 .. d + 1.  Always two
-// launches (k_trace<true, KIND>, k_finalize_ard): there is no fused form of the final sums, and ticket is not used.  Batched:
-// grids (blocks, experts) and (1, experts); part and out from the table, hout[expert][ARD_ROW_GRAD + d + 2].
+// ARD: part[ard_part_columns(cf, d) * trace_num_blocks(npad)]; results row out / hout (both mandatory, ARD_ROW_GRAD + nh
+// doubles, nh = ard_num_hyper(cf, d)): [0] LL, [4] y'K^-1y, [5] log|K|, [6] status word (as the isotropic row),
+// [ARD_ROW_GRAD + c] g_c, c = 0 .. nh - 1.  Always two launches (k_trace<true, KIND>, k_finalize_ard or its tied form):
+// there is no fused form of the final sums, and ticket is not used.  Batched: grids (blocks, experts) and (1, experts);
+// part and out from the table, hout[expert][ARD_ROW_GRAD + nh].
 constexpr int ARD_ROW_GRAD = 8;
+// columns of an nh-wide handle's gradient partials, and the entries of its theta
+inline int ard_part_columns(const CovFn& cf, int d) { return d + shape_count(cf.kind) + 2; }
+inline int ard_num_hyper(const CovFn& cf, int d) { return (cf.tied ? 1 : d) + shape_count(cf.kind) + 2; }
 void launch_trace(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* alpha,
                   double* part, hipStream_t s, Batch bt = {}, const double* z = nullptr,
                   const double* logdet_part = nullptr, double* out = nullptr, double* hout = nullptr,
@@ -265,11 +280,11 @@ void launch_finalize(const double* z, int npad, int n, const double* logdet_part
 // A[t][j] = sum_{k >= j} Z[t][k] U[j][k]: row t = alpha_t = K^-1 y_t (64-row target tiles: the first (m + 63) / 64 of them)
 void launch_targets_alpha(const double* Z, const double* U, double* A, int npad, int m, hipStream_t s);
 // gradient traces of the summed objective, W = m K^-1 - sum_t alpha_t alpha_t^T, K^-1 read once: partial sums per block in
-// launch_trace's layouts (isotropic part[3 * nblocks], ARD part[(d + 2) * nblocks]; nblocks = trace_num_blocks(npad))
+// launch_trace's layouts (isotropic part[3 * nblocks], ARD part[ard_part_columns * nblocks]; nblocks = trace_num_blocks(npad))
 void launch_trace_targets(const double* X, int n, int d, int npad, const CovFn& cf, const double* Kinv, const double* A,
                           int m, double* part, hipStream_t s);
 // one workgroup: out / hout (pinned) [0] LL = sum_t LL_t, [1 + c] the nh components of the gradient of -LL (nh = 3, ARD
-// d + 2), [1 + nh + t] LL_t = -0.5 (z_t'z_t + logdet + n * 1.83787); logdet NaN (no factor): every entry NaN
+// ard_num_hyper), [1 + nh + t] LL_t = -0.5 (z_t'z_t + logdet + n * 1.83787); logdet NaN (no factor): every entry NaN
 void launch_finalize_targets(const double* Z, int npad, int n, int d, int m, double logdet, const double* part,
                              const CovFn& cf, double* out, double* hout, hipStream_t s);
 // mean[t * nt + i] = sum_k A[t][k] Ks[i][k] (Ks [ntpad][npad], pad = 0): 64x64 output tiles, the k range in chunks of
@@ -304,7 +319,7 @@ void launch_loo_mirror_scale(const double* Kinv, const double* pt, int n, int np
 // P (lower 128-tiles, diagonal tiles complete) = Bm Bm^T, K = npad for every tile; returns the tile edge in 32s (4 or 2)
 int launch_loo_product(const double* Bm, double* P, int npad, hipStream_t s);
 // gradient pass over the lower tiles of P with W_loo = P - b alpha^T - alpha b^T (part: (nl + 2) * trace_num_blocks(npad),
-// nl = 1 or ARD's d) and its final sums: out[1 ..] = hout[1 ..] = the nh components of d(-L_LOO) / dtheta
+// nl = 1 or ARD's d + shape_count) and its final sums: out[1 ..] = hout[1 ..] = the nh components of d(-L_LOO) / dtheta
 void launch_trace_loo(const double* X, int n, int d, int npad, const CovFn& cf, const double* P, const double* alpha,
                       const double* b, double* part, double* out, double* hout, hipStream_t s);
 // ---- sparse variational GP regression on inducing points (cugp_sparse_*; sparse_device.h) ----

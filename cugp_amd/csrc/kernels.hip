@@ -172,7 +172,11 @@ static inline const double* ard_weights_ptr(const CovFn& cf) { return is_ard(cf)
 
 // The one table of the covariance passes' instantiations: CUGP_COV_KERNEL(cf, k_<pass>) is k_<pass><ARD, KIND> of the
 // descriptor (every instantiation of a pass has one type, so the selection is an expression).
-#define CUGP_COV_KERNEL(cf, stem)                                                                        \
+// CUGP_COV_KERNEL3 is the table of the three families that have isotropic and ARD instantiations alike; the sparse
+// passes, which no rational quadratic model launches, pick from it.  CUGP_COV_KERNEL adds <true, KERNEL_RQ> (an RQ
+// descriptor is always ARD: its isotropic form ties the weights, it has no kernels of its own).
+#define CUGP_COV_KERNEL(cf, stem) ((cf).kind == KERNEL_RQ ? (assert(is_ard(cf)), stem<true, KERNEL_RQ>) : CUGP_COV_KERNEL3(cf, stem))
+#define CUGP_COV_KERNEL3(cf, stem)                                                                       \
     (is_ard(cf) ? ((cf).kind == KERNEL_MATERN32   ? stem<true, KERNEL_MATERN32>                          \
                    : (cf).kind == KERNEL_MATERN52 ? stem<true, KERNEL_MATERN52> : stem<true, KERNEL_SE>) \
                 : ((cf).kind == KERNEL_MATERN32   ? stem<false, KERNEL_MATERN32>                         \
@@ -187,7 +191,7 @@ static void set_big_lds();
 // _store_t; tile_nt8, tile_out8, acc_zero8; tile_tn; k_test_gemm, k_mfma_peak and their launchers
 #include "tile_gfx950.h"
 // tri_index, wave_sum; KT, DC, col4, sqdist_4x4, DivBy, ard_weights, div_prepare, div_by, matern_entry, ard_entry,
-// kernel_value; TGT_CHUNK, targets_outer_4x4; trace_ard_body; predict_grad_body, k_predict_grad, k_predict_grad_finish
+// ShapeArgs, shape_args, rq_entry, kernel_value; TGT_CHUNK, targets_outer_4x4; trace_ard_body; predict_grad_body, k_predict_grad, k_predict_grad_finish
 #include "cov_device.h"
 // k_predict_grad_batched, k_predict_grad_finish_batched, k_poe_reduce_grad: the product of experts' test-input gradient
 #include "bcm_grad_device.h"

@@ -132,7 +132,8 @@ __global__ __launch_bounds__(256) void k_loo_bsum(const double* __restrict__ bpa
 //   W_loo(i, j) = (P(i, j) - b_i alpha_j) - alpha_i b_j
 // formed per 4x4 block in registers.  Isotropic: the three sums of k_trace (sum W o dK/dlog l, sum W o K, tr W); ARD:
 // trace_ard_body's two sweeps (d per-dimension sums, then the same two).  Partial sums column-major for both:
-// part[c * nblocks + block], c = 0 .. nl - 1 the length-scale columns (nl = 1, ARD d), nl: sum W o K, nl + 1: tr W.
+// part[c * nblocks + block], c = 0 .. nl - 1 the length-scale columns (nl = 1, ARD d), nl: sum W o K, nl + 1: tr W; a
+// family with a shape parameter (RQ) has its column sum W o dK/dtheta_shape between the length columns and sum W o K.
 // h_arg: the hyper-scalars by value (isotropic); hd: the same in device memory followed by the d weights (ARD, mandatory).
 template <bool ARD, int KIND>
 __device__ __forceinline__ void trace_loo_body(const double* __restrict__ X, int n, int d, int npad, HyperScalars h_arg,
@@ -159,6 +160,8 @@ __device__ __forceinline__ void trace_loo_body(const double* __restrict__ X, int
     for (int b = 0; b < 4; b++) { aj[b] = alpha[j0 + col4(tx, b)]; bj[b] = bv[j0 + col4(tx, b)]; }
     const DivBy dl = div_prepare(h.ell_sq);
     double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    constexpr int NS = ARD ? shape_count(KIND) : 0;      // shape columns behind the length columns (RQ: one); their sum rides in s1
+    const ShapeArgs sh = shape_args<KIND>(wts, d);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const int i = i0 + ty * 4 + a;
@@ -173,7 +176,9 @@ __device__ __forceinline__ void trace_loo_body(const double* __restrict__ X, int
             if (i < n && j < n && (ti != tj || j <= i)) {
                 const double w = (pv[b] - bi * aj[b]) - ai * bj[b];
                 double kf, dk, hh;
-                if constexpr (ARD) {
+                if constexpr (NS > 0) {
+                    ard_entry<KIND>(wk[a][b], h.signal_var, sh, kf, hh, dk);   // dk: dK / dtheta_shape, zero on the diagonal
+                } else if constexpr (ARD) {
                     ard_entry<KIND>(wk[a][b], h.signal_var, kf, hh);
                     dk = 0.0;
                 } else if constexpr (KIND == KERNEL_SE) {
@@ -201,6 +206,9 @@ __device__ __forceinline__ void trace_loo_body(const double* __restrict__ X, int
     if ((t & 63) == 0) { red[0][t >> 6] = s1; red[1][t >> 6] = s2; red[2][t >> 6] = s3; }
     __syncthreads();
     // (t = 0: the isotropic length-scale column; the ARD ones follow below)
+    if constexpr (NS > 0) {                              // [d length columns][shape column = s1][sum W o K][tr W]
+        if (t < 3) part[(size_t)(t == 0 ? d : d + NS + t - 1) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
+    } else
     if (t < 3 && (t > 0 || !ARD))
         part[(size_t)(t == 0 ? 0 : nl + t - 1) * nblocks + blockIdx.x] = (red[t][0] + red[t][1]) + (red[t][2] + red[t][3]);
     if constexpr (ARD) {
@@ -278,4 +286,45 @@ __global__ __launch_bounds__(256) void k_loo_finalize(const double* __restrict__
         out[1 + nl] = gf; out[2 + nl] = gn;
         hout[1 + nl] = gf; hout[2 + nl] = gn;
     }
+}
+
+// The same for a handle with ONE tied length scale over dlen length columns (nl counts a family's shape columns with the
+// length columns; nh = nl - dlen + 3): every column summed on its wave as above, 256 at a time into LDS; thread 0 adds the
+// dlen finished results S_c / 2 in index order into g_0, the other columns' results move up behind it (k_finalize_ard_tied's order).  Lines repeated, not
+// shared, so that k_loo_finalize keeps its instructions.
+__global__ __launch_bounds__(256) void k_loo_finalize_tied(const double* __restrict__ part, int nblocks, int nl, int dlen,
+                                                           double sn2, double* __restrict__ out, double* __restrict__ hout)
+{
+#pragma clang fp contract(off)
+    constexpr int COLS = 256;                              // columns summed per round: wave w takes w, w + 4, ...
+    __shared__ double cols[COLS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int o = nl - dlen + 1;
+    double g0 = 0.0, s2 = 0.0;                             // (thread 0's)
+    for (int c0 = 0; c0 < nl + 2; c0 += COLS) {
+        const int cc = (nl + 2 - c0 < COLS) ? (nl + 2 - c0) : COLS;
+        __syncthreads();
+        for (int c = wave; c < cc; c += 4) {
+            const double* col = part + (size_t)(c0 + c) * nblocks;
+            double s = 0.0;
+            for (int i = lane; i < nblocks; i += 64) s = s + col[i];
+            s = wave_sum(s);
+            if (lane == 0) cols[c] = s;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int c = c0; c < c0 + cc; c++) {
+                const double s = cols[c - c0];
+                if (c < dlen) g0 = c == 0 ? s / 2.0 : g0 + s / 2.0;
+                else if (c < nl) { out[2 + (c - dlen)] = s / 2.0; hout[2 + (c - dlen)] = s / 2.0; }
+                else if (c == nl) s2 = s;
+                else {
+                    const double s3 = s;
+                    const double gf = (2.0 * s2 - 2.0 * sn2 * s3) / 2.0, gn = (2.0 * sn2 * s3) / 2.0;
+                    out[1 + o] = gf; out[2 + o] = gn;
+                    hout[1 + o] = gf; hout[2 + o] = gn;
+                }
+            }
+    }
+    if (threadIdx.x == 0) { out[1] = g0; hout[1] = g0; }
 }

@@ -132,6 +132,7 @@ __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict
     __shared__ double ws[DC];
     sqdist_4x4<ARD>(Xt, Xt, nt, nt, d, i0, j0, xs, ys, d2v, wts, ws);
     const DivBy dl = div_prepare(h.ell_sq);
+    const ShapeArgs sh = shape_args<KIND>(wts, d);
 #pragma unroll
     for (int a = 0; a < 4; a++) {
         const int i = i0 + ty * 4 + a;
@@ -147,7 +148,7 @@ __device__ __forceinline__ void predict_cov_finish_body(const double* __restrict
 #pragma unroll
         for (int b = 0; b < 4; b++) {
             const int j = j0 + col4(tx, b);
-            double v = kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var);
+            double v = kernel_value<ARD, KIND>(d2v[a][b], dl, h.signal_var, sh);
             if (i == j) {
                 if (with_noise) v += h.noise_var;
                 v += jitter;

@@ -8,7 +8,7 @@
 // after these are declared -- the file includes nothing and declares none of them:
 //   kernels.h        TILE, CovFn, CovShape, SparseShape, SparseZShape, SparseFinalTargets, SPARSE_CHUNK_DEFAULT,
 //                    SPARSE_GRAM_SLOTS, SPARSE_Z_SLOTS, SPT_GROUP, the launcher prototypes (launch_test_gemm_nt among them)
-//   kernels.hip      d4, LaunchStamp, CUGP_LAUNCH, take_stamp, tri_count, ard_weights_ptr, CUGP_COV_KERNEL, set_big_lds
+//   kernels.hip      d4, LaunchStamp, CUGP_LAUNCH, take_stamp, tri_count, ard_weights_ptr, CUGP_COV_KERNEL3, set_big_lds
 //   tile_gfx950.h    BK, Geo, GEMM_LDS, tile_nt, tile_tn, acc_zero, tile_store, plan_ksplit
 //   cov_device.h     tri_index, KT
 //   sparse_device.h, sparse_z_device.h, sparse_targets_device.h, sparse_predict_device.h   the kernels launched below
@@ -127,7 +127,7 @@ void launch_trace_cross(const double* Xr, int nr, int rows_pad, const double* Z,
                         hipStream_t s)
 {
     const dim3 grid((rows_pad / KT) * (mpad / KT));
-    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_cross), grid, dim3(256), 0, s, Xr, nr, Z, m, d, mpad, cf.h, cf.hd, G, yv,
+    hipLaunchKernelGGL(CUGP_COV_KERNEL3(cf, k_trace_cross), grid, dim3(256), 0, s, Xr, nr, Z, m, d, mpad, cf.h, cf.hd, G, yv,
                        bv, part, pstride, pofs);
 }
 
@@ -151,7 +151,7 @@ void launch_trace_cross_z(const double* Xr, int nr, int rows_pad, const double* 
 {
     const SparseZShape z = sparse_z_shape(rows_pad, mpad, d);
     const size_t sstride = (size_t)m * d;
-    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_trace_cross_z), dim3((mpad / KT) * z.ranges), dim3(256), 0, s, Xr, nr, Z, m, d,
+    hipLaunchKernelGGL(CUGP_COV_KERNEL3(cf, k_trace_cross_z), dim3((mpad / KT) * z.ranges), dim3(256), 0, s, Xr, nr, Z, m, d,
                        mpad, cf.h, cf.hd, G, yv, bv, z.row_tiles, z.per, z.ranges, part, sstride);
     const double* wts = ard_weights_ptr(cf);
     hipLaunchKernelGGL(k_trace_cross_z_finish, dim3((unsigned)((sstride + 255) / 256)), dim3(256), 0, s, (const double*)part,

@@ -17,6 +17,22 @@ KERNELS = {"se": capi.CUGP_KERNEL_SE, "matern32": capi.CUGP_KERNEL_MATERN32, "ma
 KERNEL_NAMES = {v: k for k, v in KERNELS.items()}
 # one length scale per input dimension with a Matern kind (GPML covMaternard): the name sets ard=True by itself
 ARD_KERNELS = {"matern32_ard": capi.CUGP_KERNEL_MATERN32, "matern52_ard": capi.CUGP_KERNEL_MATERN52}
+# rational quadratic (GPML covRQiso / covRQard; cugp_create_rq): the name -> one length scale per dimension?  Both forms
+# carry the shape parameter alpha in front of sigma_f, sigma_n and use the nh-wide (_ard) calls; the number 3 is not a kernel=
+RQ_KERNELS = {"rq": False, "rq_ard": True}
+REPORTED_NAMES = dict(KERNEL_NAMES)
+REPORTED_NAMES[capi.CUGP_KERNEL_RQ] = "rq"
+
+
+def num_hyper(kind, ard, d):
+    """entries of the log-hyper-parameter vector: length scales (1, ARD d), the family's shape parameters (RQ: alpha),
+    sigma_f, sigma_n"""
+    return (int(d) if ard else 1) + (1 if kind == capi.CUGP_KERNEL_RQ else 0) + 2
+
+
+def is_wide(kind, ard):
+    """the handle takes the nh-wide (_ard) calls: ARD, or rational quadratic in either form"""
+    return bool(ard) or kind == capi.CUGP_KERNEL_RQ
 
 
 COMBINE = {"poe": capi.CUGP_COMBINE_POE, "gpoe": capi.CUGP_COMBINE_GPOE, "bcm": capi.CUGP_COMBINE_BCM,
@@ -53,8 +69,13 @@ def kernel_spec(kernel, ard=False):
     only), or one of ARD_KERNELS' names, which are ARD whatever `ard` says."""
     if isinstance(kernel, str) and kernel.lower() in ARD_KERNELS:
         return ARD_KERNELS[kernel.lower()], True
+    if isinstance(kernel, str) and kernel.lower() in RQ_KERNELS:
+        if ard and not RQ_KERNELS[kernel.lower()]:
+            raise ValueError('ard=True is squared-exponential only; the ARD rational quadratic kernel is kernel="rq_ard"')
+        return capi.CUGP_KERNEL_RQ, RQ_KERNELS[kernel.lower()]
     if isinstance(kernel, str) and kernel.lower().endswith("_ard"):
-        raise ValueError("kernel must be one of %s, not %r" % (sorted(KERNELS) + sorted(ARD_KERNELS), kernel))
+        raise ValueError("kernel must be one of %s, not %r"
+                         % (sorted(KERNELS) + sorted(ARD_KERNELS) + sorted(RQ_KERNELS), kernel))
     kind = kernel_kind(kernel)
     if ard and kind != capi.CUGP_KERNEL_SE:
         raise ValueError('ard=True is squared-exponential only; the ARD Matern kernels are kernel="%s_ard"'
@@ -73,14 +94,20 @@ class Covsum:
     same three hyper-parameters; fixed for the life of the handle.  ard=True is squared-exponential only;
     kernel="matern32_ard" | "matern52_ard" (GPML covMaternard; cugp_create_ard_kernel) is ARD with a Matern kind: .ard
     is True, nh = d + 2, and .kernel reports "matern32" / "matern52".
+    kernel="rq" | "rq_ard" (rational quadratic, GPML covRQiso / covRQard; cugp_create_rq): the hyper-parameter vector is
+    [log l, log alpha, log sigma_f, log sigma_n] (nh = 4, .ard False) or [log l_1 .. log l_d, log alpha, log sigma_f,
+    log sigma_n] (nh = d + 3, .ard True); .kernel reports "rq".  Everything an ARD handle does works on both.
     npad_min: rows the handle has room for (capacity); append(X, y) adds observations up to it."""
 
     def __init__(self, n, d, device=0, npad_min=0, ard=False, kernel="se"):
         self.n, self.d, self.device = int(n), int(d), int(device)
         self._kind, self.ard = kernel_spec(kernel, ard)
-        self.nh = self.d + 2 if self.ard else 3
+        self.nh = num_hyper(self._kind, self.ard, self.d)
         self._h = C.c_void_p()
-        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
+        if self._kind == capi.CUGP_KERNEL_RQ:
+            check(capi.lib().cugp_create_rq(self.n, self.d, self.device, int(npad_min), 1 if self.ard else 0,
+                                            C.byref(self._h)))
+        elif self.ard and self._kind != capi.CUGP_KERNEL_SE:
             check(capi.lib().cugp_create_ard_kernel(self.n, self.d, self.device, int(npad_min), self._kind,
                                                     C.byref(self._h)))
         elif self._kind != capi.CUGP_KERNEL_SE:
@@ -108,6 +135,11 @@ class Covsum:
             pass
 
     @property
+    def _wide(self):
+        """takes the nh-wide (_ard) calls: ARD, or rational quadratic in either form"""
+        return is_wide(self._kind, self.ard)
+
+    @property
     def handle(self):
         return self._h
 
@@ -116,7 +148,7 @@ class Covsum:
         """The handle's covariance family as the library reports it: "se", "matern32" or "matern52"."""
         k = C.c_int()
         check(capi.lib().cugp_kernel_kind(self._h, C.byref(k)))
-        return KERNEL_NAMES[k.value]
+        return REPORTED_NAMES[k.value]
 
     # -- data --
     def set_data(self, X, y):
@@ -173,7 +205,7 @@ class Covsum:
     # -- hyper-parameters --
     def set_loghyperparam(self, hp):
         hp = f64(hp)
-        if self.ard:
+        if self._wide:
             if hp.shape != (self.nh,):
                 raise ValueError("expected %d log-hyper-parameters" % self.nh)
             check(capi.lib().cugp_set_loghyper_ard(self._h, ptr(hp), self.nh))
@@ -184,14 +216,14 @@ class Covsum:
 
     def get_loghyperparam(self):
         out = np.empty(self.nh)
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_get_loghyper_ard(self._h, ptr(out), self.nh))
         else:
             check(capi.lib().cugp_get_loghyper(self._h, ptr(out)))
         return out
 
     def get_param_dim(self):
-        return self.d + 2 if self.ard else self.d   # covkernel.cpp:661-663 returns numdim; ARD: the number of hyper-parameters
+        return self.nh if self._wide else self.d   # covkernel.cpp:661-663 returns numdim; ARD: the number of hyper-parameters
 
     # -- objective --
     def compute_loglikelihood(self, X=None, y=None):
@@ -202,7 +234,7 @@ class Covsum:
 
     def compute_gradient_loghyperparam(self, X=None, y=None):
         self._bind(X, y)
-        if self.ard:
+        if self._wide:
             return self.loglik_grad()[1]
         g = np.empty(3)
         check(capi.lib().cugp_grad(self._h, ptr(g)))
@@ -212,7 +244,7 @@ class Covsum:
         self._bind(X, y)
         ll = C.c_double()
         g = np.empty(self.nh)
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_loglik_grad_ard(self._h, C.byref(ll), ptr(g), self.nh))
         else:
             check(capi.lib().cugp_loglik_grad(self._h, C.byref(ll), ptr(g)))
@@ -224,7 +256,7 @@ class Covsum:
     def fetch(self):
         ll = C.c_double()
         g = np.empty(self.nh)
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_loglik_grad_fetch_ard(self._h, C.byref(ll), ptr(g), self.nh))
         else:
             check(capi.lib().cugp_loglik_grad_fetch(self._h, C.byref(ll), ptr(g)))
@@ -412,7 +444,7 @@ class Covsum:
         self._bind(X, y)
         tr = np.zeros((4 * budget + 8, self.nh + 1))
         ne = C.c_int()
-        solve = capi.lib().cugp_cg_solve_ard if self.ard else capi.lib().cugp_cg_solve
+        solve = capi.lib().cugp_cg_solve_ard if self._wide else capi.lib().cugp_cg_solve
         check(solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
         return tr[: ne.value]
 
@@ -483,6 +515,8 @@ class SparseGP:
     def __init__(self, n, m, d, device=0, kernel="se", ard=False, jitter=1e-6, chunk_rows=0):
         self.n, self.m, self.d, self.device = int(n), int(m), int(d), int(device)
         self._kind, self.ard = kernel_spec(kernel, ard)
+        if self._kind == capi.CUGP_KERNEL_RQ:
+            raise ValueError("SparseGP: the rational quadratic kernel is not built for the sparse model")
         self.nh = self.d + 2 if self.ard else 3
         self.jitter, self.chunk_rows = float(jitter), int(chunk_rows)
         self._h = C.c_void_p()
@@ -756,7 +790,7 @@ class Comm:
         nh = int(nh)
         out = np.empty((self.world * int(per), 1 + nh))
         h = bcm._h if bcm is not None else None
-        if bcm.ard if bcm is not None else nh != 3:
+        if bcm._wide if bcm is not None else nh != 3:
             check(capi.lib().cugp_bcm_loglik_grad_allgather_ard(h, self._h, int(per), nh, ptr(out)))
         else:
             if nh != 3:
@@ -841,9 +875,13 @@ class BCM:
         devs = np.ascontiguousarray([device] if devices is None else list(devices), dtype=np.int32)
         self.rows, self.d, self.device, self.devices = rows.tolist(), int(d), int(devs[0]), devs.tolist()
         self._kind, self.ard = kernel_spec(kernel, ard)
-        self.nh = self.d + 2 if self.ard else 3
+        self.nh = num_hyper(self._kind, self.ard, self.d)
         self._h = C.c_void_p()
-        if self.ard and self._kind != capi.CUGP_KERNEL_SE:
+        if self._kind == capi.CUGP_KERNEL_RQ:
+            check(capi.lib().cugp_bcm_create_rq(len(self.devices), devs.ctypes.data_as(capi._ip), len(self.rows),
+                                                rows.ctypes.data_as(capi._ip), self.d, 1 if self.ard else 0,
+                                                C.byref(self._h)))
+        elif self.ard and self._kind != capi.CUGP_KERNEL_SE:
             check(capi.lib().cugp_bcm_create_ard_kernel(len(self.devices), devs.ctypes.data_as(capi._ip),
                                                         len(self.rows), rows.ctypes.data_as(capi._ip), self.d,
                                                         self._kind, C.byref(self._h)))
@@ -859,11 +897,16 @@ class BCM:
                                                    rows.ctypes.data_as(capi._ip), self.d, C.byref(self._h)))
 
     @property
+    def _wide(self):
+        """takes the nh-wide (_ard) calls: ARD, or rational quadratic in either form"""
+        return is_wide(self._kind, self.ard)
+
+    @property
     def kernel(self):
         """The covariance family of every expert: "se", "matern32" or "matern52"."""
         k = C.c_int()
         check(capi.lib().cugp_bcm_kernel_kind(self._h, C.byref(k)))
-        return KERNEL_NAMES[k.value]
+        return REPORTED_NAMES[k.value]
 
     @classmethod
     def split(cls, X, y, K, device=0, devices=None, kernel="se", ard=False):
@@ -895,7 +938,7 @@ class BCM:
 
     def set_BCM_log_hyperparam(self, hp):
         hp = f64(hp)
-        if self.ard:
+        if self._wide:
             if hp.shape != (self.nh,):
                 raise ValueError("expected %d log-hyper-parameters" % self.nh)
             check(capi.lib().cugp_bcm_set_loghyper_ard(self._h, ptr(hp), self.nh))
@@ -906,7 +949,7 @@ class BCM:
 
     def get_loghyperparam(self):
         out = np.empty(self.nh)
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_bcm_get_loghyper_ard(self._h, ptr(out), self.nh))
         else:
             check(capi.lib().cugp_bcm_get_loghyper(self._h, ptr(out)))
@@ -917,7 +960,7 @@ class BCM:
         ll = C.c_double()
         g = np.empty(self.nh)
         per = np.empty(len(self.rows))
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_bcm_loglik_grad_ard(self._h, C.byref(ll), ptr(g), self.nh, ptr(per)))
         else:
             check(capi.lib().cugp_bcm_loglik_grad(self._h, C.byref(ll), ptr(g), ptr(per)))
@@ -926,7 +969,7 @@ class BCM:
     def loglik_grad_rows(self):
         """-> [K, 1 + nh] rows (LL_k, gradient of -LL_k): what a multi-GPU BCM all-reduces."""
         rows = np.empty((len(self.rows), 1 + self.nh))
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_bcm_loglik_grad_rows_ard(self._h, ptr(rows), self.nh))
         else:
             check(capi.lib().cugp_bcm_loglik_grad_rows(self._h, ptr(rows)))
@@ -936,7 +979,7 @@ class BCM:
         """Leave every local expert's (LL_k, gradient) row in DEVICE memory: row slots[k] of the [., 1 + nh] buffer at
         dev_rows_ptr (same GPU) -- the payload of an all-reduce that never touches the host."""
         slots = np.ascontiguousarray(slots, dtype=np.int32)
-        if self.ard:
+        if self._wide:
             check(capi.lib().cugp_bcm_loglik_grad_rows_device_ard(self._h, C.c_void_p(dev_rows_ptr),
                                                                   slots.ctypes.data_as(capi._ip), self.nh))
         else:
@@ -1016,7 +1059,7 @@ class BCM:
         """-> the evaluation trace [n_evals, 1 + nh] = (theta, -LL)."""
         tr = np.zeros((4 * budget + 8, 1 + self.nh))
         ne = C.c_int()
-        solve = capi.lib().cugp_bcm_cg_solve_ard if self.ard else capi.lib().cugp_bcm_cg_solve
+        solve = capi.lib().cugp_bcm_cg_solve_ard if self._wide else capi.lib().cugp_bcm_cg_solve
         check(solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
         return tr[: ne.value]
 

@@ -17,16 +17,23 @@ import time
 import numpy as np
 
 
+def start_vector(hp, nh, kernel, ard=False):
+    """The start [log l, log sigma_f, log sigma_n] of --hp widened to a handle's nh entries: the length scale repeated,
+    a rational quadratic kernel's log alpha = 0 behind the length scales, then the two variances."""
+    from .gp import kernel_spec, num_hyper
+    shape = num_hyper(kernel_spec(kernel, ard)[0], False, 1) - 3          # the family's shape parameters
+    return [hp[0]] * (nh - 2 - shape) + [0.0] * shape + list(hp[1:])
+
+
 def train_loo(args, local):
     """One expert, conjugate gradients on -L_LOO (Covsum.cg_solve_loo); prints what the default objective's run prints."""
     from . import dataset
-    from .gp import Covsum, kernel_spec
+    from .gp import Covsum
     X, y = dataset.load_chunk("%s0.txt" % args.inputs, "%s0.txt" % args.labels)
     Xt, yt = X[args.rows:args.rows + args.test_rows], y[args.rows:args.rows + args.test_rows]
     X, y = X[:args.rows], y[:args.rows]
-    ard = kernel_spec(args.kernel, args.ard)[1]
     g = Covsum(X.shape[0], X.shape[1], local, ard=args.ard, kernel=args.kernel)
-    g.set_loghyperparam([args.hp[0]] * (g.nh - 2) + list(args.hp[1:]) if ard else args.hp)
+    g.set_loghyperparam(start_vector(args.hp, g.nh, args.kernel, args.ard))
     g.set_data(X, y)
     t0 = time.perf_counter()
     trace = g.cg_solve_loo(args.budget)
@@ -75,9 +82,10 @@ def main(argv=None, parse_only=False):
     ap.add_argument("--budget", type=int, default=100)
     ap.add_argument("--test-rows", type=int, default=0, help="rows after --rows in chunk 0 used as a held-out set")
     ap.add_argument("--backend", default="nccl")
-    ap.add_argument("--kernel", default="se", choices=["se", "matern32", "matern52", "matern32_ard", "matern52_ard"],
+    ap.add_argument("--kernel", default="se", choices=["se", "matern32", "matern52", "matern32_ard", "matern52_ard", "rq", "rq_ard"],
                     help="covariance family of every expert (the same on every rank); the _ard names: one length scale "
-                         "per input dimension with that Matern kind, the start as --ard's")
+                         "per input dimension with that kind, the start as --ard's; rq / rq_ard: rational quadratic, "
+                         "log alpha starts at 0 (not with --sparse)")
     ap.add_argument("--ard", action="store_true",
                     help="one length scale per input dimension (squared exponential only): the start is "
                          "[hp0] * d + [hp1, hp2]")
@@ -133,7 +141,7 @@ def main(argv=None, parse_only=False):
     shards = dataset.load_shards(args.inputs, args.labels, args.numchunks, rows=None, only=mine)
     experts = [None if s is None else (s[0][:args.rows], s[1][:args.rows]) for s in shards]
     bcm = ShardedBCM(experts, rank=rank, world=world, device=local, kernel=args.kernel, ard=args.ard)
-    bcm.set_loghyper([args.hp[0]] * (bcm.nh - 2) + list(args.hp[1:]) if bcm.ard else args.hp)
+    bcm.set_loghyper(start_vector(args.hp, bcm.nh, args.kernel, bcm.ard))
     t0 = time.perf_counter()
     trace = bcm.cg_solve(args.budget)
     dt = time.perf_counter() - t0

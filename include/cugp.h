@@ -135,6 +135,36 @@ int cugp_kernel_kind(const cugp_gp *gp, int *kernel);
  * one group must agree in kind and in the ARD flag. */
 int cugp_create_ard_kernel(int n, int d, int device, int npad_min, int kernel, cugp_gp **out);
 
+/* ---- rational quadratic covariance (GPML covRQiso / covRQard, scikit-learn's RationalQuadratic): a scale mixture of
+ *      squared exponentials whose shape alpha is learned -- the first hyper-parameter that is neither a length scale nor
+ *      a variance.  sigma_f and sigma_n stay the last two entries of theta.
+ *      ard = 1:  nh = d + 3, theta = [log l_1 .. log l_d, log alpha, log sigma_f, log sigma_n]
+ *        w_c = exp(-theta_c),  u_c = (x_c - x'_c) w_c,  s = sum_c u_c^2   (differences weighted before squaring)
+ *        alpha = exp(theta_d),  u = s / (2 alpha),  L = log1p(u)
+ *        Kf = sf2 exp(-alpha L)                     (= sf2 (1 + u)^-alpha;  K = Kf + sn2 delta)
+ *        H  = Kf / (1 + u)                          dK/dtheta_c = H u_c^2 (c < d),   dk/dx*_c = -H (x*_c - x_c) w_c^2
+ *        A  = Kf alpha (u / (1 + u) - L)            dK/dtheta_d = A   (zero on the diagonal)
+ *      Gradient of -LL with W = K^-1 - alpha alpha':  g_c = 1/2 sum W o H o u_c^2 (c < d),  g_d = 1/2 sum W o A,
+ *        g_{d+1} = sum W o Kf,  g_{d+2} = sn2 tr W.
+ *      s = 0 gives Kf = H = sf2 and A = 0 exactly; alpha -> inf approaches the SE-ARD entry (4e-14 apart at theta_alpha =
+ *      30).  An alpha whose exp overflows gives NaN results with CUGP_OK, the convention of a covariance that cannot be
+ *      factored: not an error.
+ *      ard = 0:  nh = 4, theta = [log l, log alpha, log sigma_f, log sigma_n]: the form above with all d weights equal to
+ *        exp(-theta_0).  g_0 = g_l1 + ... + g_ld added in index order (the chain rule at equal scales); LL, K, the
+ *        predictions and the other three components are the ard = 1 handle's at equal scales, bit for bit.
+ * cugp_kernel_kind reports CUGP_KERNEL_RQ, cugp_num_hyper 4 or d + 3.  Both forms are nh-wide handles: every call that
+ * works on an ARD handle works on them unchanged with the handle's nh -- the _ard hyper-parameter, gradient and fetch
+ * calls, cugp_loglik and the split enqueue, the marginal, latent and joint predictions and the draws, cugp_predict_grad,
+ * cugp_set_targets and the _targets calls, cugp_append / cugp_capacity, cugp_loo, cugp_loo_predict, cugp_cg_solve_loo,
+ * cugp_cg_solve_ard, cugp_cg_solve_targets, K, k_test, factor, inverse, alpha, profiling, tuning, groups and captured
+ * graphs (a new alpha reaches a captured graph by the same one copy as new weights).  The 3-entry calls refuse them as
+ * they refuse ARD handles and name the call to use.  Experts of one group must agree in kind AND in `ard`.
+ * CUGP_ERR_INVALID before any device call, with "cugp_create_rq" in cugp_last_error: out NULL, n or d not positive,
+ * npad_min negative, ard outside {0, 1}.  The kind is NOT accepted by cugp_create_kernel, cugp_create_ard_kernel, the
+ * cugp_bcm_create*_kernel calls or cugp_sparse_create*: a sparse model with this kernel is not built. */
+#define CUGP_KERNEL_RQ 3
+int cugp_create_rq(int n, int d, int device, int npad_min, int ard, cugp_gp **out);
+
 /* ---- objective ----
  * cugp_loglik       : Covsum::compute_loglikelihood covkernel.cpp:118-129 ; compute_log_likelihood cuda_gp.cu:838-855
  * cugp_loglik_grad  : the pair compute_loglikelihood + compute_gradient_loghyperparam (covkernel.cpp:162-263 ;
@@ -773,6 +803,13 @@ int cugp_bcm_create_ard_kernel(int ndev, const int *devices, int nexperts, const
                                cugp_bcm **out);
 int cugp_bcm_create_split_ard_kernel(const double *X, const double *y, int N, int D, int K, int ndev,
                                      const int *devices, int kernel, cugp_bcm **out);
+/* every expert a rational quadratic handle (cugp_create_rq; ard as there): nh = d + 3 or 4, rows {LL, g[nh]}, every
+ * cugp_bcm_*_ard call, the four combination rules, cugp_bcm_predict_grad and the three all-gather exchanges with the BCM's
+ * nh.  cugp_bcm_kernel_kind reports CUGP_KERNEL_RQ.  CUGP_ERR_INVALID before any device call, the call's name in
+ * cugp_last_error: a NULL argument, a count that is not positive, K > N, ard outside {0, 1}. */
+int cugp_bcm_create_rq(int ndev, const int *devices, int nexperts, const int *rows, int d, int ard, cugp_bcm **out);
+int cugp_bcm_create_split_rq(const double *X, const double *y, int N, int D, int K, int ndev, const int *devices,
+                             int ard, cugp_bcm **out);
 int cugp_bcm_num_hyper(const cugp_bcm *b, int *nh);
 int cugp_bcm_set_loghyper_ard(cugp_bcm *b, const double *hp, int nh);
 int cugp_bcm_get_loghyper_ard(const cugp_bcm *b, double *hp, int nh);

@@ -68,7 +68,7 @@ def dynamic_lds(txt):
     for m in re.finditer(r"\b(?:CUGP_LAUNCH|hipLaunchKernelGGL)\(", txt):
         a = call_args(txt, m.end() - 1)
         kernel, lds = a[0], a[3]
-        cov = re.match(r"CUGP_COV_KERNEL\(\w+, (\w+)\)$", kernel)          # every <ARD, KIND> of the pass: the stem
+        cov = re.match(r"CUGP_COV_KERNEL3?\(\w+, (\w+)\)$", kernel)          # every <ARD, KIND> of the pass: the stem
         kernel = cov.group(1) if cov else re.sub(r"^\((.*)\)$", r"\1", kernel)
         if lds != "0" and lds not in pinned:
             sys.exit("kernel_resources: %s is launched with dynamic LDS '%s', which no static_assert pins to a number" % (kernel, lds))
