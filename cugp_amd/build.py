@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libcugp.so")
 SOURCES = ["kernels.hip", "cugp_capi.cpp", "predict.cpp", "dense_features.cpp", "sparse.cpp", "la.cpp", "group.cpp", "bcm.cpp",
            "minimize.cpp", "comm.cpp"]
 HEADERS = ["kernels.h", "cov_device.h", "bcm_grad_device.h", "append_device.h", "loo_device.h", "sparse_device.h",
-           "sparse_z_device.h", "sparse_targets_device.h", "sparse_predict_device.h", "tile_gfx950.h", "predict_gfx950.h", "eval_gfx950.h",
+           "sparse_z_device.h", "sparse_targets_device.h", "sparse_predict_device.h", "sparse_shard_device.h", "tile_gfx950.h", "predict_gfx950.h", "eval_gfx950.h",
            "chol_gfx950.h", "inverse_gfx950.h", "dense_features_gfx950.h", "sparse_gfx950.h", "group.h", "handle.h"]
 PUBLIC_HEADER = os.path.join(os.path.dirname(HERE), "include", "cugp.h")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

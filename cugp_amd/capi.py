@@ -120,6 +120,13 @@ SIGNATURES = {
     "cugp_sparse_predict_cov": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
     "cugp_sparse_predict_sample": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, C.c_double, C.c_int, _dp, _dp]),
     "cugp_sparse_predict_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "cugp_sparse_create_shard": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_sparse_shard_info": (C.c_int, [C.c_void_p, _ip, _ip, C.POINTER(C.c_longlong)]),
+    "cugp_sparse_sharded_bound_grad": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, _dp,
+                                                 _dp, C.c_int, _dp]),
+    "cugp_sparse_sharded_cg_solve": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               _dp, C.c_int, _ip]),
     "cugp_potrf": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_potri": (C.c_int, [C.c_int, _dp, _dp, C.c_int]),
     "cugp_chol_and_det": (C.c_int, [C.c_int, _dp, _dp, _dp, _dp, C.c_int]),

@@ -13,6 +13,7 @@
 // process that has torch loaded the handle is torch's own copy of the library (same SONAME).
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -27,6 +28,7 @@
 
 #include "../../include/cugp.h"
 #include "group.h"
+#include "handle.h"
 
 namespace {
 
@@ -90,6 +92,9 @@ struct cugp_comm {
     hipStream_t stream = nullptr;                // the exchange's own stream on `device`
     Scratch pdsend, pdrecv, pdout, phout{nullptr, 0, true};   // (the gradient form's are the same buffers, wider)
     double* phdr = nullptr;
+    // the sparse model with its rows sharded over ranks (cugp_sparse_sharded_bound_grad): this rank's block and everybody's
+    // -- both exchanges use them in turn -- and the pinned headers [SHARD_HDR + per | world * SHARD_HDR]
+    Scratch sdsend, sdrecv, shh{nullptr, 0, true};
 };
 
 extern "C" {
@@ -135,7 +140,7 @@ int cugp_comm_destroy(cugp_comm* c)
     if (c->comm) (void)rccl().CommDestroy(c->comm);
     for (Scratch* b : {&c->dsend, &c->drecv, &c->hrecv}) b->release();
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (Scratch* b : {&c->pdsend, &c->pdrecv, &c->pdout, &c->phout}) b->release();
+    for (Scratch* b : {&c->pdsend, &c->pdrecv, &c->pdout, &c->phout, &c->sdsend, &c->sdrecv, &c->shh}) b->release();
     if (c->phdr) (void)hipHostFree(c->phdr);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -438,6 +443,186 @@ int cugp_bcm_predict_grad_allgather(cugp_bcm* b, cugp_comm* c, int per, int nexp
     };
     return predict_allgather("cugp_bcm_predict_grad_allgather", b, c, per, nexperts, nt, f,
                              PredOut{mean, var, dmean, dvar, (size_t)nt, (size_t)nt * d});
+}
+
+// ---- the sparse variational model with its rows sharded over ranks (include/cugp.h).  The phases are
+// sparse.cpp's (handle.h: ShardEval); here are the two exchanges between them, each ONE ncclAllGather on the evaluation's
+// stream (a world of one without an id hands its own block on), and the order that keeps the ranks in step: a rank's own
+// failure in front of exchange 1 rides in its header, every rank reads every header behind the wait sp_shard_solve makes
+// anyway, and a failure behind that verdict (a HIP error: nothing the ranks could disagree about) still joins exchange 2
+// with all-ones rows before it is returned.
+static int shard_eval(const char* call, cugp_sparse* const* sh, int nlocal, cugp_comm* c, int per, int nshards, int what,
+                      double* F, double* g, int nh, double* gZ)
+{
+    char buf[256];
+    const char* why = nullptr;
+    if (!c || !sh || !F) why = "comm, shards or F is NULL";
+    else if (nlocal < 1 || per < 1) why = "nlocal < 1 or per < 1";
+    else if (what < 0 || what > 2) why = "what must be 0 (F), 1 (F, g) or 2 (F, g, gZ)";
+    else if ((what >= 1 && !g) || (what == 2 && !gZ)) why = "g (what >= 1) or gZ (what == 2) is NULL";
+    else if (nshards < c->world) why = "nshards < world: a rank without a shard";
+    else if ((long long)per * c->world < nshards) why = "per * world < nshards";
+    if (why) {
+        snprintf(buf, sizeof buf, "%s: %s", call, why);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    cugp::ShardEval e;
+    e.sh = sh; e.nlocal = nlocal; e.rank = c->rank; e.world = c->world; e.per = per; e.nshards = nshards; e.what = what;
+    e.device = c->device; e.call = call;
+    int rc = cugp::sp_shard_begin(e);
+    if (rc) return rc;
+    if (e.status == CUGP_OK && what >= 1 && nh != e.nh) {
+        snprintf(buf, sizeof buf, "%s: nh is not the handles' (cugp_sparse_num_hyper)", call);
+        e.status = cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    hipError_t he = hipSetDevice(c->device);
+    if (he != hipSuccess) return hip_fail("hipSetDevice", he);
+    // ---- the exchange buffers.  A failure here (hipSetDevice above included) returns at once: without a send block the rank
+    // cannot join exchange 1, and the other ranks wait for it -- the one failure of a rank that is not its status
+    const size_t n1 = cugp::SHARD_HDR + (size_t)per * e.slot1, n2 = (size_t)per * e.slot2, nsend = n1 > n2 ? n1 : n2;
+    if (nsend > c->sdsend.cap) {
+        if ((rc = c->sdsend.grow(nsend, nullptr))) return rc;
+        // initialised once, so that no allocator's leftovers travel: P's upper tiles and the slots beyond a rank's shards are
+        // sent but never read.  They do not stay zero -- exchange 2 reuses the block from its start, failures fill it with ones
+        he = hipMemset(c->sdsend.p, 0, nsend * sizeof(double));
+        if (he != hipSuccess) { c->sdsend.release(); return hip_fail("shard exchange buffers", he); }
+    }
+    if ((c->comm && (rc = c->sdrecv.grow((size_t)c->world * nsend, nullptr))) ||
+        (rc = c->shh.grow(cugp::SHARD_HDR + (size_t)per + (size_t)c->world * cugp::SHARD_HDR, nullptr)))
+        return rc;
+    e.hsend = c->shh.p;
+    e.hall = c->shh.p + cugp::SHARD_HDR + per;
+    double* send = c->sdsend.p;
+    // ---- phase 1 and exchange 1
+    cugp::sp_shard_stats(e, send);
+    const double* src = send;
+    if (c->comm) {
+        const ncclResult_t r = rccl().AllGather(send, c->sdrecv.p, n1, ncclDouble, c->comm, e.stream);
+        if (r != ncclSuccess) { (void)hipStreamSynchronize(e.stream); return nccl_fail("ncclAllGather", r); }
+        src = c->sdrecv.p;
+    }
+    rc = cugp::sp_shard_solve(e, src, n1);
+    if (rc && !e.agreed) return rc;                       // (every rank returns here alike, or the stream itself failed)
+    // ---- phase 2 and exchange 2
+    if (!e.done && what >= 1) {
+        if (rc == CUGP_OK) rc = cugp::sp_shard_rows(e, send);
+        if (rc) (void)hipMemsetAsync(send, 0xff, n2 * sizeof(double), e.stream);
+        src = send;
+        if (c->comm) {
+            const ncclResult_t r = rccl().AllGather(send, c->sdrecv.p, n2, ncclDouble, c->comm, e.stream);
+            if (r != ncclSuccess) { (void)hipStreamSynchronize(e.stream); return nccl_fail("ncclAllGather", r); }
+            src = c->sdrecv.p;
+        }
+    }
+    if (rc) { (void)hipStreamSynchronize(e.stream); return rc; }
+    if (!e.done && (rc = cugp::sp_shard_finish(e, src, n2))) return rc;
+    return cugp::sp_shard_results(e, F, g, gZ);
+}
+
+int cugp_sparse_sharded_bound_grad(cugp_sparse* const* shards, int nlocal, cugp_comm* comm, int per, int nshards, int what,
+                                   double* F, double* g, int nh, double* gZ)
+{
+    return shard_eval("cugp_sparse_sharded_bound_grad", shards, nlocal, comm, per, nshards, what, F, g, nh, gZ);
+}
+
+namespace {
+struct ShardObjective {
+    cugp_sparse* const* sh;
+    int nlocal, per, nshards, nh, md;
+    cugp_comm* c;
+    bool inducing;
+    std::vector<double> z;                             // Z as the shards hold it
+    bool first = true;                                 // the start point: nothing is written into the shards
+    int rc = CUGP_OK;                                  // the first evaluation that failed
+    std::string err;                                   // ... and its text
+};
+
+// f = -F of the sharded model and its gradient at v = [theta] or [theta, vec Z]: sp_objective / sp_objective_z over every
+// local shard.  Every rank is handed the same v by the same loop, so the collectives inside line up.
+void shard_objective(void* ctx, const double* v, int nv, double* f, double* gr)
+{
+    ShardObjective* o = (ShardObjective*)ctx;
+    bool ok = true;
+    // The start point is the first shard's own state.  It is not written into the others: local shards that disagree in theta
+    // or Z are refused by the evaluation, as cugp_sparse_sharded_bound_grad refuses them, not brought into line in passing.
+    // Behind the first failure nothing is written either: the call will return that failure and leave the shards as they were
+    // (the evaluations go on, so that the ranks' collectives stay matched).
+    const bool write = !o->first && o->rc == CUGP_OK;
+    o->first = false;
+    if (write && o->inducing && memcmp(o->z.data(), v + o->nh, (size_t)o->md * sizeof(double))) {
+        for (int i = 0; i < o->nlocal && ok; i++) ok = cugp_sparse_set_inducing(o->sh[i], v + o->nh) == CUGP_OK;
+        if (ok) o->z.assign(v + o->nh, v + o->nh + o->md);
+    }
+    for (int i = 0; i < o->nlocal && ok && write; i++) ok = cugp_sparse_set_loghyper(o->sh[i], v, o->nh) == CUGP_OK;
+    double F = NAN;
+    // (a rank whose own set_ call failed still evaluates: the others are on their way into the exchange)
+    const int rc = shard_eval("cugp_sparse_sharded_cg_solve", o->sh, o->nlocal, o->c, o->per, o->nshards, o->inducing ? 2 : 1, &F,
+                              gr, o->nh, gr + o->nh);
+    if (rc != CUGP_OK && o->rc == CUGP_OK) {
+        o->rc = rc;
+        o->err = cugp_last_error();
+    }
+    ok = ok && rc == CUGP_OK;
+    if (ok) *f = -1.0 * F;
+    else {
+        *f = NAN;
+        std::fill(gr, gr + nv, NAN);
+    }
+}
+}  // namespace
+
+int cugp_sparse_sharded_cg_solve(cugp_sparse* const* sh, int nlocal, cugp_comm* c, int per, int nshards, int budget, int inducing,
+                                 double* trace, int trace_cap, int* nevals)
+{
+    const char* call = "cugp_sparse_sharded_cg_solve";
+    const char* why = nullptr;
+    if (!c || !sh) why = "comm or shards is NULL";
+    else if (nlocal < 1 || per < 1) why = "nlocal < 1 or per < 1";
+    else if (budget <= 0) why = "budget must be positive";
+    else if (nshards < c->world) why = "nshards < world: a rank without a shard";
+    else if ((long long)per * c->world < nshards) why = "per * world < nshards";
+    else if (!sh[0]) why = "the first shard handle is NULL";
+    if (why) {
+        char buf[200];
+        snprintf(buf, sizeof buf, "%s: %s", call, why);
+        return cugp_internal_fail(CUGP_ERR_INVALID, buf);
+    }
+    int rc, m = 0, d = 0, nh = 0, ns = 0;
+    if ((rc = cugp_sparse_shard_info(sh[0], nullptr, &ns, nullptr)) || (rc = cugp_sparse_dims(sh[0], nullptr, &m, &d, nullptr, nullptr)) ||
+        (rc = cugp_sparse_num_hyper(sh[0], &nh)))
+        return rc;
+    if (ns == 0) return cugp_internal_fail(CUGP_ERR_INVALID, "cugp_sparse_sharded_cg_solve: the first handle is an ordinary one (cugp_sparse_create)");
+    ShardObjective o{sh, nlocal, per, nshards, nh, m * d, c, inducing != 0, {}};
+    std::vector<double> v((size_t)nh);
+    if ((rc = cugp_sparse_get_loghyper(sh[0], v.data(), nh))) return rc;
+    // An evaluation that fails gives the loop NaN, as cugp_sparse_cg_solve's does, and the loop goes on -- the ranks stay in
+    // step --; but the first failure is what the call returns, and then nothing is written into the shards: a failed rank, a
+    // mismatch between ranks or local shards that disagree are errors here as in cugp_sparse_sharded_bound_grad.
+    if (!o.inducing) {
+        if ((rc = cugp::cg_iterates(shard_objective, &o, v.data(), nh, budget, trace, trace_cap, nevals))) return rc;
+        if (o.rc) return cugp_internal_fail(o.rc, o.err.c_str());
+    } else {
+        // cugp_sparse_cg_solve_z's record: [theta, f] of the iterates, the NaN row behind the last one
+        o.z.resize((size_t)o.md);
+        if ((rc = cugp_sparse_get_inducing(sh[0], o.z.data()))) return rc;
+        const int nv = nh + o.md, cap = trace ? std::max(trace_cap, 0) : 0;
+        int nrows = 0;
+        std::vector<double> rows((size_t)cap * (nv + 1), NAN);
+        v.insert(v.end(), o.z.begin(), o.z.end());
+        if ((rc = cugp::cg_iterates(shard_objective, &o, v.data(), nv, budget, cap ? rows.data() : nullptr, cap, nevals, &nrows)))
+            return rc;
+        for (int r = 0; r < nrows + (nrows < cap); r++) {
+            std::copy(rows.begin() + (size_t)r * (nv + 1), rows.begin() + (size_t)r * (nv + 1) + nh, trace + (size_t)r * (nh + 1));
+            trace[(size_t)r * (nh + 1) + nh] = rows[(size_t)r * (nv + 1) + nv];
+        }
+        if (o.rc) return cugp_internal_fail(o.rc, o.err.c_str());
+        if (memcmp(o.z.data(), v.data() + nh, (size_t)o.md * sizeof(double)))
+            for (int i = 0; i < nlocal; i++)
+                if ((rc = cugp_sparse_set_inducing(sh[i], v.data() + nh))) return rc;
+    }
+    for (int i = 0; i < nlocal; i++)
+        if ((rc = cugp_sparse_set_loghyper(sh[i], v.data(), nh))) return rc;
+    return CUGP_OK;
 }
 
 }  // extern "C"

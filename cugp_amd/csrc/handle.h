@@ -230,6 +230,36 @@ int predict_grad_passes(cugp_gp* g, Batch bt, int tiles, const double* Xt, int n
 int sample_tail(cugp_gp* g, cugp_gp* f, const double* dm, int nt, int nsamples, const double* normals, double* samples,
                 const char* call);
 
+// ---- sparse.cpp: one evaluation of the sparse model with its rows sharded over ranks, in the phases that lie around the
+// two exchanges of comm.cpp (cugp_sparse_sharded_bound_grad).  Everything runs on one stream, the
+// lead's (the first local shard's inner handle's).
+constexpr int SHARD_HDR = 16;      // doubles in front of a rank's block of exchange 1: ShardEval::header
+struct ShardEval {
+    cugp_sparse* const* sh = nullptr;   // this rank's shards, slot order; sh[0] is the lead
+    int nlocal = 0, rank = 0, world = 1, per = 0, nshards = 0, what = 0, device = 0;
+    const char* call = "";
+    int m = 0, d = 0, mpad = 0, nh = 0;
+    size_t slot1 = 0, slot2 = 0;        // doubles per shard in exchange 1: [P mpad^2 | q mpad | y'y | n]; in exchange 2: [S_uf nl + 1 | gZ m d]
+    hipStream_t stream = nullptr;
+    double* hsend = nullptr;            // pinned [SHARD_HDR + per]: this rank's header, its shards' row counts
+    double* hall = nullptr;             // pinned [world][SHARD_HDR]: every rank's header as gathered
+    int status = 0;                     // this rank's own failure so far: it still joins exchange 1
+    bool kuu_pd = false, done = false;  // Kuu was positive definite; the results stand (no exchange 2 follows)
+    bool agreed = false;                // every rank's header was read and found in order: the ranks go on in step
+    CovFn cf;                           // the lead's inner handle's covariance descriptor, taken in phase 1
+};
+// the checks on this rank's list that need the lead's shape: nonzero only where the rank cannot even size its block
+int sp_shard_begin(ShardEval& e);
+// Kuu, every local shard's chunk loop into its slot of `send`, the header; a failure becomes e.status and all-ones slots
+void sp_shard_stats(ShardEval& e, double* send);
+// the sums over the shards, B, the wait, every rank's header read by every rank, B's factorisation, c'
+int sp_shard_solve(ShardEval& e, const double* gathered, size_t rstride);
+// the M-side products, every local shard's trace passes and its row of `send`
+int sp_shard_rows(ShardEval& e, double* send);
+// the sums over the shards' rows, the square's Z pass, the final sums, the wait; then (also behind e.done) the results
+int sp_shard_finish(ShardEval& e, const double* gathered, size_t rstride);
+int sp_shard_results(const ShardEval& e, double* F, double* g, double* gZ);
+
 // While an API call enqueues for handle g the launchers of kernels.hip read g's tuning (thread-local pointer).
 struct TuneScope {
     const int* prev;

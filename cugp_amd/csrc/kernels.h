@@ -398,6 +398,23 @@ struct SparseFinalTargets {
 // [1 + nl + 2 + t] F_t
 void launch_sparse_finalize_targets(const SparseFinalTargets& f, const double* part_uf, size_t nb_uf, const double* part_uu,
                                     size_t nb_uu, int nl, double* out, double* hout, hipStream_t s);
+// ---- the sparse model with its rows sharded over ranks (cugp_sparse_sharded_*; sparse_shard_device.h)
+// out[e] = sum over the shards k = 0 .. nshards - 1, in that order, of entry off + e of shard k's slot (rank k % world's
+// block at src + (k % world) * rstride: [hdr | slots of `slot` doubles], slot k / world), e < len
+void launch_sparse_shard_reduce(const double* src, size_t rstride, size_t hdr, size_t slot, size_t off, size_t len, int world,
+                                int nshards, double* out, hipStream_t s);
+// out[c] = the sum of column c of a shard's trace partials (c <= nl) in k_sparse_finalize_targets' order; one workgroup
+void launch_sparse_shard_sums(const double* part_uf, size_t nb_uf, int nl, double* out, hipStream_t s);
+// SparseFinalTargets at p = 1 with y'y and N on the device: yyn = {y'y, N}, both summed over the shards
+struct SparseFinalSharded {
+    const double *P, *Binv, *Cp, *Gm, *logdet, *yyn;
+    int m, ld, nt;
+    double sf2, s2, log_s2;
+};
+// one workgroup: launch_sparse_finalize_targets' results at p = 1 from the reduced sums suf[nl + 1] of the rectangle
+// (NULL: F only) and the square's partials
+void launch_sparse_finalize_sharded(const SparseFinalSharded& f, const double* suf, const double* part_uu, size_t nb_uu, int nl,
+                                    double* out, double* hout, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

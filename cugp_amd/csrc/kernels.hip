@@ -222,7 +222,9 @@ static void set_big_lds();
 #include "sparse_targets_device.h"
 // the input gradients of the sparse prediction: k_sparse_predict_diff (emulable)
 #include "sparse_predict_device.h"
-// k_sparse_predict_cov, k_sparse_gram, sparse_shape, sparse_z_shape and every sparse launcher, those of the four emulable
+// the rows sharded over ranks: k_sparse_shard_reduce, k_sparse_shard_sums, k_sparse_finalize_sharded (emulable)
+#include "sparse_shard_device.h"
+// k_sparse_predict_cov, k_sparse_gram, sparse_shape, sparse_z_shape and every sparse launcher, those of the five emulable
 // headers above included
 #include "sparse_gfx950.h"
 

@@ -1,7 +1,12 @@
 // sparse.cpp -- cugp_sparse: sparse variational GP regression on inducing points, a client of the dense handle.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <memory>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "handle.h"
@@ -37,6 +42,13 @@ struct SparseSide {
     double* v(int k, int mpad) const { return vec + (size_t)k * rows * mpad; }     // vector k of the five
 };
 
+// What the local shards of one sharded evaluation share: who the lead is and whether the global M
+// side it holds still stands.  Any set_ call on, or the end of, one of the shards clears `valid`.
+struct ShardGroup {
+    const cugp_sparse* lead = nullptr;
+    bool valid = false;
+};
+
 struct cugp_sparse {
     int n = 0, m = 0, d = 0, mpad = 0, device = 0, kernel = KERNEL_SE, nh = 3, chunk_rows = 0;
     bool ard = false;
@@ -54,6 +66,11 @@ struct cugp_sparse {
     // the gradient with respect to Z (cugp_sparse_bound_grad_z): created on its first use
     std::vector<double> z;                                   // Z as set, [m][d] (the host copy cugp_sparse_get_inducing returns)
     double *dzpart = nullptr, *dzacc = nullptr, *dzout = nullptr, *hz = nullptr;   // partial blocks, running sums, result, its pinned copy
+    // a member of a model whose rows are sharded over ranks (cugp_sparse_create_shard; nshards 0: an ordinary handle)
+    int shard = -1, nshards = 0;
+    long long rows_total = 0;                                // N of the last sharded evaluation
+    std::shared_ptr<ShardGroup> grp;                         // the last sharded evaluation this handle took part in
+    double *dglob = nullptr;                                 // the lead's: {y'y, N} and S_uf [nh - 1], summed over the shards
 };
 
 namespace {
@@ -163,6 +180,18 @@ int sp_ready(const cugp_sparse* s, const SparseSide& r, const char* call)
     return CUGP_OK;
 }
 
+// a shard handle in a call that would evaluate its own rows alone
+int sp_shard_refuse(const char* call)
+{
+    return invalid_arg(call, "the handle is a shard of a sharded model (cugp_sparse_create_shard): its rows alone are another "
+                             "model; evaluate with cugp_sparse_sharded_bound_grad");
+}
+
+void sp_touch(cugp_sparse* s)                                          // (data, Z or theta of a shard changed)
+{
+    if (s->grp) s->grp->valid = false;
+}
+
 // The bound (and its gradient) of one side at the current hyper-parameters: F = sum_t F_t over the side's p label vectors,
 // with the F_t behind the gradient's slots.  The results land in that side's row and gz: NaN where Kuu or B is not
 // positive definite (the header's convention).  Two host waits beyond the inner evaluation's: in front of B's
@@ -174,6 +203,7 @@ int sp_ready(const cugp_sparse* s, const SparseSide& r, const char* call)
 int sp_eval(cugp_sparse* s, SparseSide& r, bool want_grad, const char* call, bool want_z = false)
 {
     int rc;
+    if (s->nshards > 0) return sp_shard_refuse(call);
     if ((rc = sp_ready(s, r, call))) return rc;
     SparseSide& other = &r == &s->own ? s->tg : s->own;
     if (r.valid && (r.row_grad || !want_grad) && (r.row_z || !want_z)) return CUGP_OK;
@@ -278,11 +308,28 @@ int sp_eval(cugp_sparse* s, SparseSide& r, bool want_grad, const char* call, boo
     return CUGP_OK;
 }
 
+// The state a prediction reads: an ordinary handle is evaluated where stale (sp_eval); a shard handle is never evaluated
+// -- the lead of the last sharded evaluation answers from the global M side it holds while that stands, every other
+// shard handle and a stale lead refuse.
+int sp_state(cugp_sparse* s, SparseSide& r, const char* call)
+{
+    if (s->nshards == 0) return sp_eval(s, r, false, call);
+    if (&r != &s->own) return sp_shard_refuse(call);
+    if (!s->grp || s->grp->lead != s)
+        return invalid_arg(call, "the handle is a shard that does not hold the model: predict from the first local shard of "
+                                 "cugp_sparse_sharded_bound_grad");
+    if (!s->grp->valid || !r.valid)
+        return invalid_arg(call, "the sharded model is stale (hyper-parameters, Z or data changed since): evaluate with "
+                                 "cugp_sparse_sharded_bound_grad first");
+    return CUGP_OK;
+}
+
 int sp_set_theta(cugp_sparse* s, const double* th)
 {
     bool changed = false;
     for (int i = 0; i < s->nh; i++) changed = changed || th[i] != s->theta[i] || std::isnan(th[i]);
     if (!changed) return CUGP_OK;
+    sp_touch(s);
     s->theta.assign(th, th + s->nh);
     s->own.valid = s->tg.valid = false;
     return CUGP_OK;
@@ -367,6 +414,7 @@ int sp_cg(cugp_sparse* s, SparseSide cugp_sparse::*side, bool inducing, const ch
 {
     if (!s) return invalid_arg(call, "null handle");
     if (budget <= 0) return invalid_arg(call, "budget must be positive");
+    if (s->nshards > 0) return sp_shard_refuse(call);
     if (const int rc = sp_ready(s, s->*side, call)) return rc;
     SpObjective o{s, &(s->*side), call};
     return inducing ? sp_cg_theta_z(s, &o, budget, trace, trace_cap, nevals) : sp_cg_theta(s, &o, budget, trace, trace_cap, nevals);
@@ -445,12 +493,13 @@ int cugp_sparse_create(int n, int m, int d, int device, int kernel, int ard, dou
 int cugp_sparse_destroy(cugp_sparse* s)
 {
     if (!s) return CUGP_OK;
+    sp_touch(s);
     (void)hipSetDevice(s->device);
     if (s->u && s->u->stream) (void)hipStreamSynchronize(s->u->stream);
     if (s->u) (void)cugp_destroy(s->u);
     if (s->b) (void)cugp_destroy(s->b);
     for (double* p : {s->dX, s->dS, s->dW, s->dG, s->dP, s->dscr, s->dM[0], s->dM[1], s->dM[2], s->dM[3], s->dpart, s->dzpart,
-                      s->dzacc, s->dzout})
+                      s->dzacc, s->dzout, s->dglob})
         if (p) (void)hipFree(p);
     for (SparseSide* r : {&s->own, &s->tg}) {
         sp_side_free(*r);
@@ -494,6 +543,7 @@ int cugp_sparse_set_data(cugp_sparse* s, const double* X, const double* y)
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     s->have_data = true;
+    sp_touch(s);
     s->own.valid = s->tg.valid = false;
     return CUGP_OK;
 }
@@ -505,6 +555,7 @@ int cugp_sparse_set_inducing(cugp_sparse* s, const double* Z)
     if (const int rc = cugp_set_data(s->u, Z, zero.data())) return rc;
     s->z.assign(Z, Z + (size_t)s->m * s->d);
     s->have_z = true;
+    sp_touch(s);
     s->own.valid = s->tg.valid = false;
     return CUGP_OK;
 }
@@ -553,7 +604,7 @@ namespace {
 int sp_predict(cugp_sparse* s, SparseSide& r, const char* call, const double* Xt, int nt, int with_noise, double* mean, double* var)
 {
     int rc;
-    if ((rc = sp_eval(s, r, false, call))) return rc;                  // (answers from the last evaluation's state when it holds)
+    if ((rc = sp_state(s, r, call))) return rc;                        // (answers from the last evaluation's state when it holds)
     const int p = r.p;
     const bool matrix = !r.vector;
     if (!r.pd) {
@@ -647,7 +698,7 @@ int sp_predict_cov_device(cugp_sparse* s, const char* call, const double* Xt, in
                           double** dmean, cugp_gp** fout, bool* pd)
 {
     int rc;
-    if ((rc = sp_eval(s, s->own, false, call))) return rc;
+    if ((rc = sp_state(s, s->own, call))) return rc;
     *pd = s->own.pd;
     if (!*pd) return CUGP_OK;
     cugp_gp *u = s->u, *b = s->b;
@@ -767,7 +818,7 @@ int cugp_sparse_predict_grad(cugp_sparse* s, const double* Xt, int nt, int with_
     if (!dmean && !dvar) return invalid_arg(call, "dmean and dvar are both NULL");
     if (nt <= 0) return invalid_arg(call, "nt must be positive");
     int rc;
-    if ((rc = sp_eval(s, s->own, false, call))) return rc;
+    if ((rc = sp_state(s, s->own, call))) return rc;
     const size_t nout = (size_t)nt * s->d;
     if (!s->own.pd) {
         if (mean) std::fill(mean, mean + nt, NAN);
@@ -863,6 +914,7 @@ int cugp_sparse_set_targets(cugp_sparse* s, const double* Y, int p)
     const char* call = "cugp_sparse_set_targets";
     if (!s || !Y) return invalid_arg(call, "null argument");
     if (p < 1) return invalid_arg(call, "p must be positive");
+    if (s->nshards > 0) return sp_shard_refuse(call);
     if (!s->have_data) return invalid_arg(call, "no data set (cugp_sparse_set_data comes first: it supplies X)");
     int rc;
     if ((rc = use_device(s->u))) return rc;
@@ -932,3 +984,351 @@ int cugp_sparse_cg_solve_targets(cugp_sparse* s, int budget, int inducing, doubl
 {
     return sp_cg(s, &cugp_sparse::tg, inducing != 0, "cugp_sparse_cg_solve_targets", budget, trace, trace_cap, nevals);
 }
+
+// ---- the data rows sharded over ranks (include/cugp.h)
+// A shard handle is an ordinary one that knows its place; what it adds is in the phases below, which are sp_eval cut at the
+// two points where the shards meet.  The public evaluating calls and both exchanges are comm.cpp's.
+int cugp_sparse_create_shard(int n_local, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows, int shard,
+                             int nshards, cugp_sparse** out)
+{
+    const char* call = "cugp_sparse_create_shard";
+    if (!out) return invalid_arg(call, "out is NULL");
+    if (nshards < 1 || shard < 0 || shard >= nshards) return invalid_arg(call, "nshards < 1 or shard outside [0, nshards)");
+    int rc;
+    if ((rc = cugp_sparse_create(n_local, m, d, device, kernel, ard, jitter, chunk_rows, out))) return rc;
+    cugp_sparse* s = *out;
+    if ((rc = ensure(&s->dglob, (size_t)2 + s->nh))) {
+        cugp_sparse_destroy(s);
+        *out = nullptr;
+        return rc;
+    }
+    s->shard = shard;
+    s->nshards = nshards;
+    return CUGP_OK;
+}
+
+int cugp_sparse_shard_info(const cugp_sparse* s, int* shard, int* nshards, long long* rows_total)
+{
+    if (!s) return invalid_arg("cugp_sparse_shard_info", "null handle");
+    if (shard) *shard = s->shard;
+    if (nshards) *nshards = s->nshards;
+    if (rows_total) *rows_total = s->rows_total;
+    return CUGP_OK;
+}
+
+namespace {
+uint64_t fnv1a(uint64_t h, const void* p, size_t bytes)
+{
+    const unsigned char* b = (const unsigned char*)p;
+    for (size_t i = 0; i < bytes; i++) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+
+void halves(uint64_t v, double* out)                                   // two doubles that are exact integers below 2^32
+{
+    out[0] = (double)(v >> 32);
+    out[1] = (double)(v & 0xffffffffull);
+}
+
+// the header's fields behind {status, local shard count}, for the error texts
+const char* const SHARD_FIELD[SHARD_HDR] = {"status", "shard count", "m", "d", "the kernel", "ard", "nh", "nshards", "per", "what",
+                                            "the jitter", "the jitter", "the hyper-parameters or Z", "the hyper-parameters or Z",
+                                            "rows", ""};
+
+// S_c and W_c of a chunk of shard s against the lead's inner handle (sp_chunk_w with the M side of another handle)
+void shard_chunk_w(cugp_sparse* lead, cugp_sparse* s, const CovFn& cf, const SparseShape& c)
+{
+    cugp_gp* u = lead->u;
+    launch_kcross(u->dX, s->m, s->d, s->mpad, s->dX + (size_t)c.r0 * s->d, c.count, c.cpad, cf, s->dS, u->stream);
+    launch_predict_gemm(s->dS, u->dT, s->dW, s->mpad, c.cpad / TILE, u->nt, u->stream);
+}
+
+int shard_stats_enqueue(ShardEval& e, double* send)
+{
+    int rc;
+    cugp_sparse* L = e.sh[0];
+    cugp_gp* u = L->u;
+    const bool want_grad = e.what >= 1, want_z = e.what == 2;
+    auto grp = std::make_shared<ShardGroup>();
+    grp->lead = L;
+    for (int i = 0; i < e.nlocal; i++) {
+        cugp_sparse* s = e.sh[i];
+        sp_touch(s);
+        s->grp = grp;
+        s->own.valid = s->tg.valid = s->own.pd = false;
+    }
+    SparseSide& r = L->own;
+    r.row.assign((size_t)2 + L->nh, NAN);
+    r.row_grad = want_grad;
+    r.row_z = want_z;
+    if (want_z) r.gz.assign((size_t)L->m * L->d, NAN);
+    if ((rc = use_device(u))) return rc;
+    for (int i = 0; i < e.nlocal; i++) {                               // every buffer of the evaluation, in front of exchange 1
+        if ((rc = sp_ensure(e.sh[i], want_grad))) return rc;
+        if (want_z && (rc = sp_ensure_z(e.sh[i]))) return rc;
+    }
+    std::vector<double> th(L->theta);
+    th[L->nh - 1] = 0.5 * std::log(L->jitter);
+    if ((rc = set_theta(u, th.data()))) return rc;
+    if ((rc = cugp_loglik_grad(u, nullptr, nullptr))) return rc;       // Lu, Lu^-1, Lu^-T: the same on every rank
+    if ((rc = use_device(u))) return rc;
+    e.kuu_pd = std::isfinite(u->last_ll);
+    if (!e.kuu_pd) return CUGP_OK;                                     // (every rank alike: NaN results behind exchange 1)
+    if (const int pe = prepare_kernels())
+        return fail(CUGP_ERR_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)", (hipError_t)pe);
+    hipStream_t st = e.stream;
+    const int mp = e.mpad;
+    TuneScope ts(u);
+    if ((rc = cov_fn(u, st, nullptr, &e.cf))) return rc;
+    for (int i = 0; i < e.nlocal; i++) {
+        cugp_sparse* s = e.sh[i];
+        double *P = send + SHARD_HDR + (size_t)i * e.slot1, *q = P + (size_t)mp * mp;
+        const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
+        for (int c = 0; c < chunks; c++) {
+            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
+            shard_chunk_w(L, s, e.cf, sh);
+            launch_sparse_gram(s->dW, mp, sh, P, s->dscr, c == 0, st);
+            launch_sparse_wty_targets(s->dW, mp, sh.cpad, s->own.y + sh.r0, s->own.ystride, 1, s->own.part, q, c == 0, st);
+        }
+        HIPCHK(hipMemcpyAsync(q + mp, s->own.yy, sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(q + mp + 1, e.hsend + SHARD_HDR + i, sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipGetLastError());
+    return CUGP_OK;
+}
+}  // namespace
+
+namespace cugp {
+
+int sp_shard_begin(ShardEval& e)
+{
+    const char* call = e.call;
+    cugp_sparse* L = e.sh[0];
+    if (!L) return invalid_arg(call, "the first shard handle is NULL");
+    if (L->nshards == 0)
+        return invalid_arg(call, "the first handle is an ordinary one (cugp_sparse_create): a sharded model takes the handles "
+                                 "of cugp_sparse_create_shard");
+    if (L->device != e.device) return invalid_arg(call, "the first shard is on another device than the communicator");
+    e.m = L->m; e.d = L->d; e.mpad = L->mpad; e.nh = L->nh;
+    e.slot1 = (size_t)L->mpad * L->mpad + L->mpad + 2;
+    e.slot2 = e.what >= 1 ? (size_t)(L->nh - 1) + (e.what == 2 ? (size_t)L->m * L->d : 0) : 0;
+    e.stream = L->u->stream;
+    char buf[256];
+    const int expect = (e.nshards - e.rank + e.world - 1) / e.world;
+    int st = CUGP_OK;
+    if (e.nlocal != expect || e.nlocal > e.per) {
+        snprintf(buf, sizeof buf, "rank %d holds %d shards, %d of %d expected (per = %d)", e.rank, e.nlocal, expect, e.nshards, e.per);
+        st = invalid_arg(call, buf);
+    }
+    for (int i = 0; i < e.nlocal && st == CUGP_OK; i++) {
+        const cugp_sparse* s = e.sh[i];
+        const char* why = nullptr;
+        if (!s) why = "a shard handle is NULL";
+        else if (s->nshards == 0) why = "an ordinary handle (cugp_sparse_create) in the list of shards";
+        else if (s->nshards != e.nshards || s->shard != e.rank + i * e.world)
+            why = "a handle's shard index or count is not its place in the list (slot i holds shard rank + i * world)";
+        else if (s->device != e.device) why = "a shard on another device than the communicator";
+        else if (s->m != L->m || s->d != L->d || s->kernel != L->kernel || s->ard != L->ard ||
+                 memcmp(&s->jitter, &L->jitter, sizeof(double)))
+            why = "the local shards disagree in m, d, kernel, ard or jitter";
+        else if (!s->have_data) why = "a shard without data (cugp_sparse_set_data)";
+        else if (!s->have_z) why = "a shard without inducing inputs (cugp_sparse_set_inducing)";
+        else if (memcmp(s->theta.data(), L->theta.data(), (size_t)L->nh * sizeof(double)))
+            why = "the local shards disagree in the bits of the hyper-parameters";
+        else if (memcmp(s->z.data(), L->z.data(), L->z.size() * sizeof(double)))
+            why = "the local shards disagree in the bits of Z";
+        if (why) st = invalid_arg(call, why);
+    }
+    e.status = st;
+    return CUGP_OK;
+}
+
+void sp_shard_stats(ShardEval& e, double* send)
+{
+    cugp_sparse* L = e.sh[0];
+    double* h = e.hsend;
+    double rows = 0.0;
+    for (int i = 0; i < e.nlocal && e.status == CUGP_OK; i++) {
+        h[SHARD_HDR + i] = (double)e.sh[i]->n;
+        rows = rows + (double)e.sh[i]->n;
+    }
+    if (e.status == CUGP_OK) e.status = shard_stats_enqueue(e, send);
+    if (e.status != CUGP_OK)                                           // all-ones slots: NaN wherever they are added
+        (void)hipMemsetAsync(send + SHARD_HDR, 0xff, (size_t)e.per * e.slot1 * sizeof(double), e.stream);
+    std::fill(h, h + SHARD_HDR, 0.0);
+    h[0] = (double)e.status; h[1] = (double)e.nlocal; h[2] = L->m; h[3] = L->d; h[4] = L->kernel; h[5] = L->ard ? 1.0 : 0.0;
+    h[6] = L->nh; h[7] = e.nshards; h[8] = e.per; h[9] = e.what;
+    uint64_t jb;
+    memcpy(&jb, &L->jitter, sizeof jb);
+    halves(jb, h + 10);
+    uint64_t fp = fnv1a(14695981039346656037ull, L->theta.data(), L->theta.size() * sizeof(double));
+    halves(fnv1a(fp, L->z.data(), L->z.size() * sizeof(double)), h + 12);
+    h[14] = rows;
+    const hipError_t err = hipMemcpyAsync(send, h, SHARD_HDR * sizeof(double), hipMemcpyHostToDevice, e.stream);
+    if (err != hipSuccess && e.status == CUGP_OK) e.status = fail(CUGP_ERR_DEVICE, "hipMemcpyAsync (the shard header)", err);
+}
+
+int sp_shard_solve(ShardEval& e, const double* g, size_t rstride)
+{
+    cugp_sparse* L = e.sh[0];
+    cugp_gp *u = L->u, *b = L->b;
+    hipStream_t st = e.stream;
+    SparseSide& r = L->own;
+    const int mp = e.mpad;
+    const size_t mm = (size_t)mp * mp;
+    double *q = r.v(0, mp), *cp = r.v(1, mp);
+    const double s2 = std::exp(L->theta[L->nh - 1] * 2);
+    int rc;
+    if ((rc = use_device(u))) return rc;
+    {
+        TuneScope ts(u);
+        if (e.status == CUGP_OK && e.kuu_pd) {                         // (else: nothing of this rank's is read again)
+            launch_sparse_shard_reduce(g, rstride, SHARD_HDR, e.slot1, 0, mm, e.world, e.nshards, L->dP, st);
+            launch_sparse_shard_reduce(g, rstride, SHARD_HDR, e.slot1, mm, (size_t)mp, e.world, e.nshards, q, st);
+            launch_sparse_shard_reduce(g, rstride, SHARD_HDR, e.slot1, mm + mp, 2, e.world, e.nshards, L->dglob, st);
+            launch_sparse_form_b(L->dP, mp, s2, b->dA, st);
+        }
+        HIPCHK(hipMemcpy2DAsync(e.hall, SHARD_HDR * sizeof(double), g, rstride * sizeof(double), SHARD_HDR * sizeof(double),
+                                (size_t)e.world, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    // ---- every rank reads every rank's header: the same verdict everywhere
+    char buf[640];
+    double total = 0.0, rows = 0.0;
+    for (int k = 0; k < e.world; k++) {
+        const double* h = e.hall + (size_t)k * SHARD_HDR;
+        const int code = (int)h[0];
+        if (h[0] != 0.0) {
+            if (k == e.rank) {
+                const std::string last = cugp_last_error();
+                snprintf(buf, sizeof buf, "%s: rank %d failed (%d): %s", e.call, k, code, last.c_str());
+            } else snprintf(buf, sizeof buf, "%s: rank %d failed (%d)", e.call, k, code);
+            return fail(code < 0 ? code : CUGP_ERR_DEVICE, buf);
+        }
+        for (int f = 2; f < 14; f++)
+            if (memcmp(h + f, e.hall + f, sizeof(double))) {
+                snprintf(buf, sizeof buf, "%s: rank %d disagrees with rank 0 in %s", e.call, k, SHARD_FIELD[f]);
+                return fail(CUGP_ERR_INVALID, buf);
+            }
+        total = total + h[1];
+        rows = rows + h[14];
+    }
+    if (total != (double)e.nshards) {
+        snprintf(buf, sizeof buf, "%s: the ranks hold %.0f shards, %d expected", e.call, total, e.nshards);
+        return fail(CUGP_ERR_INVALID, buf);
+    }
+    e.agreed = true;
+    for (int i = 0; i < e.nlocal; i++) e.sh[i]->rows_total = (long long)rows;
+    if (!e.kuu_pd) {                                                   // Kuu is not positive definite: NaN results
+        r.valid = true;
+        L->grp->valid = true;
+        e.done = true;
+        return CUGP_OK;
+    }
+    if ((rc = la_factor_inverse(b, true))) return rc;                  // LB, LB^-1, LB^-T, B^-1 (cugp_potri's route)
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    launch_trmv_lower(b->dT, mp, mp, q, cp, st);                       // c' = LB^-1 q
+    HIPCHK(hipGetLastError());
+    return CUGP_OK;
+}
+
+int sp_shard_rows(ShardEval& e, double* send)
+{
+    cugp_sparse* L = e.sh[0];
+    cugp_gp *u = L->u, *b = L->b;
+    hipStream_t st = e.stream;
+    SparseSide& r = L->own;
+    const int mp = e.mpad, nl = L->nh - 2, m = L->m, d = L->d;
+    const bool want_z = e.what == 2;
+    const double s2 = std::exp(L->theta[L->nh - 1] * 2);
+    int rc;
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    double *cp = r.v(1, mp), *gp = r.v(2, mp), *bp = r.v(3, mp), *bsc = r.v(4, mp);
+    double *H = L->dM[0], *H2 = L->dM[1], *X1 = L->dM[2], *R = L->dM[3];
+    launch_trmv_upper(b->dU, mp, mp, cp, gp, st);                      // gamma' = LB^-T c'
+    launch_trmv_upper(u->dU, mp, mp, gp, bp, st);                      // beta' = Lu^-T gamma'
+    launch_sparse_h_targets(b->dKinv, L->dP, gp, bp, 1, m, mp, s2, H, H2, bsc, st);
+    launch_targets_alpha(H, u->dU, X1, mp, mp, st);                    // H Lu^-1
+    launch_sparse_transpose(X1, R, mp, 1.0 / s2, st);                  // R = Lu^-T H / s2
+    launch_targets_alpha(H2, u->dU, X1, mp, mp, st);                   // H2 Lu^-1
+    launch_sparse_transpose(X1, H, mp, 1.0, st);                       // Lu^-T H2
+    launch_targets_alpha(H, u->dU, H2, mp, mp, st);                    // 2 G_uu = Lu^-T H2 Lu^-1
+    for (int i = 0; i < e.nlocal; i++) {
+        cugp_sparse* s = e.sh[i];
+        double *row = send + (size_t)i * e.slot2, *zacc = row + nl + 1;  // [S_uf,k | the shard's running sums of the Z pass]
+        const size_t nb_uf = sp_blocks_uf(s);
+        const int chunks = sparse_shape(s->n, mp, s->chunk_rows, 0).chunks;
+        size_t pofs = 0;
+        for (int c = 0; c < chunks; c++) {
+            const SparseShape sh = sparse_shape(s->n, mp, s->chunk_rows, c);
+            if (chunks > 1) shard_chunk_w(L, s, e.cf, sh);             // (one chunk: the shard's W is still there)
+            launch_sparse_weights(s->dW, R, s->dG, sh.cpad, mp, st);
+            const double *xr = s->dX + (size_t)sh.r0 * d, *yv = s->own.y + sh.r0;
+            launch_trace_cross(xr, sh.count, sh.cpad, u->dX, m, d, mp, e.cf, s->dG, yv, bsc, s->dpart, nb_uf, pofs, st);
+            if (want_z)
+                launch_trace_cross_z(xr, sh.count, sh.cpad, u->dX, m, d, mp, e.cf, s->dG, yv, bsc, s->dzpart, zacc, c == 0, false,
+                                     s->dzout, s->hz, st);
+            pofs += (size_t)(sh.cpad / 64) * (mp / 64);
+        }
+        launch_sparse_shard_sums(s->dpart, nb_uf, nl, row, st);
+    }
+    const size_t nb_uu = (size_t)(mp / 64) * (mp / 64);
+    launch_trace_cross(u->dX, m, mp, u->dX, m, d, mp, e.cf, H2, nullptr, nullptr, L->dpart + (size_t)(nl + 1) * sp_blocks_uf(L), nb_uu,
+                       0, st);
+    HIPCHK(hipGetLastError());
+    return CUGP_OK;
+}
+
+int sp_shard_finish(ShardEval& e, const double* g, size_t rstride)
+{
+    cugp_sparse* L = e.sh[0];
+    cugp_gp *u = L->u, *b = L->b;
+    hipStream_t st = e.stream;
+    SparseSide& r = L->own;
+    const int mp = e.mpad, nl = L->nh - 2, m = L->m, d = L->d, nrow = 2 + L->nh;
+    const bool want_grad = e.what >= 1, want_z = e.what == 2;
+    const double sf2 = std::exp(L->theta[L->nh - 2] * 2), s2 = std::exp(L->theta[L->nh - 1] * 2), ls2 = L->theta[L->nh - 1] * 2;
+    int rc;
+    if ((rc = use_device(u))) return rc;
+    TuneScope ts(u);
+    const size_t nb_uu = (size_t)(mp / 64) * (mp / 64);
+    const double* part_uu = want_grad ? L->dpart + (size_t)(nl + 1) * sp_blocks_uf(L) : nullptr;
+    double* suf = want_grad ? L->dglob + 2 : nullptr;
+    if (want_grad) launch_sparse_shard_reduce(g, rstride, 0, e.slot2, 0, (size_t)nl + 1, e.world, e.nshards, suf, st);
+    if (want_z) {
+        launch_sparse_shard_reduce(g, rstride, 0, e.slot2, (size_t)nl + 1, (size_t)m * d, e.world, e.nshards, L->dzacc, st);
+        for (size_t i = 0; i < (size_t)m * d; i++) L->hz[i] = NAN;
+        launch_trace_cross_z(u->dX, m, mp, u->dX, m, d, mp, e.cf, L->dM[1], nullptr, nullptr, L->dzpart, L->dzacc, false, true,
+                             L->dzout, L->hz, st);
+    }
+    for (int i = 0; i < nrow; i++) r.hout[i] = NAN;
+    const SparseFinalSharded fin{L->dP, b->dKinv, r.v(1, mp), r.v(2, mp), b->dlogdet, L->dglob, m, mp, b->nt, sf2, s2, ls2};
+    launch_sparse_finalize_sharded(fin, suf, part_uu, nb_uu, nl, r.dout, r.hout, st);
+    if ((rc = sync_or_fail(st, e.call, hipGetLastError()))) return rc;
+    r.pd = std::isfinite(r.hout[0]);
+    if (r.pd) {                                                        // (B is not positive definite, or a NaN in the data: NaN results)
+        r.row[0] = r.hout[0];
+        if (want_grad) std::copy(r.hout + 1, r.hout + 1 + L->nh, r.row.begin() + 1);
+        r.row[1 + L->nh] = r.hout[1 + L->nh];
+        if (want_z) std::copy(L->hz, L->hz + (size_t)m * d, r.gz.begin());
+    }
+    r.valid = true;
+    L->grp->valid = true;
+    e.done = true;
+    return CUGP_OK;
+}
+
+int sp_shard_results(const ShardEval& e, double* F, double* g, double* gZ)
+{
+    const cugp_sparse* L = e.sh[0];
+    const SparseSide& r = L->own;
+    *F = r.row[0];
+    if (e.what >= 1) std::copy(r.row.begin() + 1, r.row.begin() + 1 + L->nh, g);
+    if (e.what == 2) std::copy(r.gz.begin(), r.gz.end(), gZ);
+    return CUGP_OK;
+}
+
+}  // namespace cugp

@@ -1,8 +1,8 @@
 // sparse_gfx950.h -- sparse variational GP regression on inducing points (sparse.cpp): the two products that need the
 // device, k_sparse_predict_cov (k_predict_cov's sibling) and k_sparse_gram (the TN product), each with its launcher and
 // its launch plan; behind them the launchers of the emulable sparse kernels (sparse_device.h, sparse_z_device.h,
-// sparse_targets_device.h, sparse_predict_device.h): a *_device.h header is compiled by the host checks and cannot hold a
-// launcher.
+// sparse_targets_device.h, sparse_predict_device.h, sparse_shard_device.h): a *_device.h header is compiled by the host
+// checks and cannot hold a launcher.
 //
 // Include-point contract.  Needs the device; also holds launchers.  Included by kernels.hip alone, INSIDE namespace cugp,
 // after these are declared -- the file includes nothing and declares none of them:
@@ -214,4 +214,24 @@ void launch_sparse_finalize_targets(const SparseFinalTargets& f, const double* p
                                     size_t nb_uu, int nl, double* out, double* hout, hipStream_t s)
 {
     hipLaunchKernelGGL(k_sparse_finalize_targets, dim3(1), dim3(256), 0, s, f, part_uf, nb_uf, part_uu, nb_uu, nl, out, hout);
+}
+
+// ---- the rows sharded over ranks (sparse_shard_device.h) ----
+void launch_sparse_shard_reduce(const double* src, size_t rstride, size_t hdr, size_t slot, size_t off, size_t len, int world,
+                                int nshards, double* out, hipStream_t s)
+{
+    if (len == 0) return;
+    hipLaunchKernelGGL(k_sparse_shard_reduce, dim3((unsigned)std::min<size_t>((len + 255) / 256, 2048)), dim3(256), 0, s, src,
+                       rstride, hdr, slot, off, len, world, nshards, out);
+}
+
+void launch_sparse_shard_sums(const double* part_uf, size_t nb_uf, int nl, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_shard_sums, dim3(1), dim3(256), 0, s, part_uf, nb_uf, nl, out);
+}
+
+void launch_sparse_finalize_sharded(const SparseFinalSharded& f, const double* suf, const double* part_uu, size_t nb_uu, int nl,
+                                    double* out, double* hout, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_sparse_finalize_sharded, dim3(1), dim3(256), 0, s, f, suf, part_uu, nb_uu, nl, out, hout);
 }

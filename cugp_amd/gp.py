@@ -849,6 +849,34 @@ class Comm:
                                                          ptr(dv) if want_var_grad else None))
         return m, v, dm, dv
 
+    @staticmethod
+    def _shard_list(shards):
+        return (C.c_void_p * len(shards))(*[getattr(s, "value", s) for s in shards])
+
+    def sparse_sharded_bound_grad(self, shards, per, nshards, what, nh, m, d):
+        """One evaluation of a sparse model whose rows are sharded over the ranks (cugp_sparse_sharded_bound_grad).
+        shards: this rank's shard handles (cugp_sparse_create_shard's) in slot order; what: 0 -> F, 1 -> (F, g [nh]),
+        2 -> (F, g, gZ [m, d]).  Every rank passes the same per, nshards and what."""
+        what = int(what)
+        F, g, gZ = C.c_double(), np.empty(int(nh)), np.empty((int(m), int(d)))
+        check(capi.lib().cugp_sparse_sharded_bound_grad(self._shard_list(shards), len(shards), self._h, int(per), int(nshards),
+                                                        what, C.byref(F), ptr(g) if what >= 1 else None, int(nh),
+                                                        ptr(gZ) if what == 2 else None))
+        return (F.value,) + ((g,) if what >= 1 else ()) + ((gZ,) if what == 2 else ())
+
+    def sparse_sharded_cg_solve(self, shards, per, nshards, budget, nh, inducing=False):
+        """Conjugate gradients on -F of the sharded sparse model (cugp_sparse_sharded_cg_solve), run by every rank alike;
+        the trace [n_iterates, nh + 1] = (theta, -F) as SparseGP.cg_solve's."""
+        budget = int(budget)
+        tr = np.full((4 * max(budget, 0) + 8, int(nh) + 1), np.nan)
+        ne = C.c_int()
+        check(capi.lib().cugp_sparse_sharded_cg_solve(self._shard_list(shards), len(shards), self._h, int(per), int(nshards),
+                                                      budget, 1 if inducing else 0, ptr(tr), tr.shape[0], C.byref(ne)))
+        rows = 1
+        while rows < min(ne.value, tr.shape[0]) and not np.isnan(tr[rows, 0]):
+            rows += 1
+        return tr[:rows]
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             capi.lib().cugp_comm_destroy(self._h)

@@ -70,6 +70,43 @@ def train_sparse(args, local):
     g.close()
 
 
+def train_sparse_sharded(args, rank, local, world):
+    """--inducing M under WORLD_SIZE > 1: ONE sparse model over the rows of all chunks, chunk r on rank r
+    (ShardedSparseGP, one shard per rank; the process group is up).  The inducing inputs are M of chunk 0's rows, drawn as
+    train_sparse draws them and broadcast from rank 0; every rank runs the same conjugate gradients; rank 0 prints."""
+    import torch
+    import torch.distributed as dist
+    from . import dataset
+    from .gp import Covsum, kernel_spec
+    from .sparse_sharded import ShardedSparseGP
+    X, y = dataset.load_chunk("%s%d.txt" % (args.inputs, rank), "%s%d.txt" % (args.labels, rank))
+    Xt, yt = X[args.rows:args.rows + args.test_rows], y[args.rows:args.rows + args.test_rows]
+    X, y = X[:args.rows], y[:args.rows]
+    Zt = torch.zeros((args.inducing, X.shape[1]), dtype=torch.float64, device=torch.device("cuda", local))
+    if rank == 0:
+        rows = np.sort(np.random.default_rng(0).choice(X.shape[0], args.inducing, replace=False))
+        Zt.copy_(torch.from_numpy(np.ascontiguousarray(X[rows])))
+    dist.broadcast(Zt, src=0)
+    shards = [(X, y) if k == rank else None for k in range(world)]
+    g = ShardedSparseGP(shards, Zt.cpu().numpy(), rank=rank, world=world, device=local, kernel=args.kernel, ard=args.ard)
+    ard = kernel_spec(args.kernel, args.ard)[1]
+    g.set_loghyper([args.hp[0]] * (g.nh - 2) + list(args.hp[1:]) if ard else args.hp)
+    t0 = time.perf_counter()
+    trace = g.cg_solve(args.budget, inducing=args.learn_inducing)
+    dt = time.perf_counter() - t0
+    if rank == 0:
+        print("\n\n PLEASE-SEE %d : %s\n" % (g.nh, ", ".join("%f" % v for v in g.get_loghyper())))
+        print("TOTAL training time = %f  (%d iterates, final -F %.9g, %d ranks)" % (dt, trace.shape[0], trace[-1, -1], world))
+    if args.test_rows > 0:
+        g.bound()                                                     # the end point's state on every rank's lead
+        if rank == 0:
+            m, v = g.predict(Xt, with_noise=True)
+            print("NLPP = %.12g" % Covsum.get_negative_log_predprob(yt, m, v))
+    g.close()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 def main(argv=None, parse_only=False):
     """parse_only: -> the parsed arguments (--objective loo and --inducing are refused there, before any device is
     touched, where they are not built)."""
@@ -98,8 +135,9 @@ def main(argv=None, parse_only=False):
                          "process only (--numchunks 1): there is no LOO for a product of experts")
     ap.add_argument("--inducing", type=int, default=0, metavar="M",
                     help="sparse variational GP regression on M inducing inputs, a random subset of the training rows, "
-                         "instead of the exact model: cg_solve maximises the variational bound -- one model in one process "
-                         "only (--numchunks 1, --objective ll)")
+                         "instead of the exact model: cg_solve maximises the variational bound -- one model (--objective ll): "
+                         "--numchunks 1 in one process, or under WORLD_SIZE > 1 one chunk per rank, the rows of all "
+                         "chunks sharded over the ranks")
     ap.add_argument("--learn-inducing", action="store_true",
                     help="with --inducing: the inducing inputs are learned together with the hyper-parameters (conjugate "
                          "gradients over both) instead of staying on the rows they were drawn from")
@@ -108,9 +146,10 @@ def main(argv=None, parse_only=False):
         ap.error("--learn-inducing needs --inducing M")
     if args.inducing < 0 or args.inducing > args.rows:
         ap.error("--inducing must lie between 1 and --rows")
-    if args.inducing and (args.numchunks != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1 or args.objective != "ll"):
-        ap.error("--inducing needs --numchunks 1, one process and --objective ll: the sparse model is built for a single "
-                 "model over all rows")
+    nproc = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.inducing and (args.numchunks != nproc or args.objective != "ll"):
+        ap.error("--inducing needs --objective ll and --numchunks 1 in one process, or one chunk per process under "
+                 "WORLD_SIZE > 1 (the rows sharded over the ranks): the sparse model is built for a single model over all rows")
     if args.objective == "loo" and (args.numchunks != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1):
         ap.error("--objective loo needs --numchunks 1 and one process: leave-one-out is built for a single expert")
     if parse_only:
@@ -128,7 +167,7 @@ def main(argv=None, parse_only=False):
     torch.cuda.set_device(local)
     if args.objective == "loo":
         return train_loo(args, local)
-    if args.inducing:
+    if args.inducing and world == 1:
         return train_sparse(args, local)
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -137,6 +176,8 @@ def main(argv=None, parse_only=False):
         else:
             dist.init_process_group(args.backend, rank=rank, world_size=world)
 
+    if args.inducing:
+        return train_sparse_sharded(args, rank, local, world)
     mine = {k for k in range(args.numchunks) if expert_owner(k, world) == rank}
     shards = dataset.load_shards(args.inputs, args.labels, args.numchunks, rows=None, only=mine)
     experts = [None if s is None else (s[0][:args.rows], s[1][:args.rows]) for s in shards]

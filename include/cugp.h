@@ -688,6 +688,68 @@ int cugp_bcm_predict(cugp_bcm *b, const double *Xt, int nt, double *mean, double
 int cugp_bcm_predict_allgather(cugp_bcm *b, cugp_comm *c, int per, int nexperts, const double *Xt, int nt,
                                double *mean, double *var);
 int cugp_bcm_cg_solve(cugp_bcm *b, int budget, double *trace, int trace_cap, int *nevals);
+/* ---- the sparse variational model (cugp_sparse_*) with its DATA ROWS sharded over ranks: K shards hold disjoint row
+ *      blocks (X_k, y_k), n_k >= 1 each and unequal where the caller likes, of ONE data set of N = sum n_k rows; Z, the
+ *      hyper-parameters, kernel, ard, jitter and m are the same on every shard.  Shard k lives on rank k mod W in slot k / W
+ *      of that rank (per = ceil(K / W) slots; K >= W: every rank owns a shard).  The objective is the bound F of all N rows
+ *      and the gradients of -F: what cugp_sparse_bound_grad_z returns for the concatenated data -- one coherent model, not a
+ *      product of experts.  Own y only: no targets.
+ * One evaluation is cugp_sparse_bound*'s sequence cut at the two points where the shards meet:
+ *   1  every local shard's chunk loop writes P_k = sum W_c'W_c, q_k = sum W_c'y_c, y_k'y_k and n_k into its slot;
+ *      ONE ncclAllGather of [header | per slots] on the evaluation's stream; the slots are summed in GLOBAL SHARD ORDER
+ *      k = 0 .. K - 1 (first term copied, then a = a + b; no atomics, never ncclAllReduce): every rank holds P, q, y'y and N
+ *      with the same bits, and those depend on (data, K), not on W or per.  Then B, its factorisation and the small solves
+ *      as cugp_sparse_bound's, on every rank alike.
+ *   2  (what >= 1) every local shard's trace passes give its row [S_uf,k (nh - 1) | gZ_uf,k (m d; what == 2)]; ONE
+ *      ncclAllGather of the rows, the same sum in shard order, the square's passes and the final sums.
+ * With K = 1 every sum hands the one shard's numbers on: F, g, gZ and the predictions are bit for bit cugp_sparse_bound*'s
+ * and cugp_sparse_predict*'s of an ordinary handle over the same data.  No host wait beyond those two of
+ * cugp_sparse_bound_grad.
+ * The header of exchange 1 carries the rank's status, its shard count, m, d, kernel, ard, nh, K, per, what, the bits of the
+ * jitter and a fingerprint of the bits of the hyper-parameters and of Z.  A rank's own failure still joins exchange 1
+ * (nonzero status, all-ones slots); behind the wait in front of B's factorisation every rank reads every rank's header, and
+ * on a nonzero status, a mismatch or shard counts that do not add up to K ALL ranks return the same error naming the rank
+ * and none enters exchange 2.  Everything later is decided from bits every rank holds alike: Kuu or B not positive
+ * definite (NaN results with CUGP_OK, every rank), a NaN in one shard's data (P is NaN everywhere: NaN results, every rank).
+ * cugp_sparse_create_shard : cugp_sparse_create for shard `shard` of `nshards` with n_local rows.  On such a handle
+ *      set_data, set_inducing, set_loghyper, the get_ calls, dims and plan work as they stand; cugp_sparse_bound*,
+ *      cugp_sparse_cg_solve*, cugp_sparse_set_targets and the _targets calls return CUGP_ERR_INVALID and name
+ *      cugp_sparse_sharded_bound_grad.  After a sharded evaluation the FIRST local shard (the lead) holds the global M
+ *      side: cugp_sparse_predict, _predict_cov, _predict_sample and _predict_grad run on it as they stand and add nothing
+ *      to the collectives.  On another shard, or on a lead whose state is stale (the hyper-parameters, Z or the data of any
+ *      local shard changed since), they return CUGP_ERR_INVALID: they never evaluate -- the local rows alone would be a
+ *      different model.  (A change on another rank's shard cannot be seen from here: evaluate on every rank alike.)
+ * cugp_sparse_shard_info   : membership; nshards = 0 (shard = -1, rows_total = 0) on an ordinary handle.  rows_total: N
+ *      of the last sharded evaluation the handle took part in, 0 before.
+ * cugp_sparse_sharded_bound_grad : one evaluation.  shards[nlocal]: this rank's shards in slot order (global shards rank,
+ *      rank + W, ...), all on comm's device; comm: cugp_comm_create's, a world of one without an id included (no RCCL);
+ *      what: 0 F, 1 F and g[nh], 2 F, g[nh] and gZ[m d].  Every rank passes the same per, nshards and what.
+ *      CUGP_ERR_INVALID on every rank alike, before any collective: comm / shards / F NULL, g (what >= 1) or gZ (what == 2)
+ *      NULL, nlocal < 1, per < 1, nshards < world, per * world < nshards, what outside 0..2.  A first handle that is NULL or
+ *      no shard handle returns at once too (the rank cannot size its block).  Everything else -- an ordinary or NULL handle
+ *      further down the list, local shards that disagree in m, d, kernel, ard, jitter, the bits of the hyper-parameters
+ *      or of Z (refused before any launch), a wrong local count or shard index, missing data, nh not the handle's, a
+ *      failure to allocate one of the handles' buffers, a HIP error of the evaluation -- is the rank's status.
+ *      What the header cannot turn into a clean error: (a) per and the PADDED m (m rounded up to 128) size the block a rank
+ *      sends, and ncclAllGather with counts that differ between ranks is undefined (a hang, or a write beyond the receive
+ *      block) -- callers MUST pass the same per and m everywhere; the header catches a per or m that differs only where the
+ *      counts happen to agree, and d, kernel, ard, nh, K, what, the jitter, the hyper-parameters and Z always; (b) a failure
+ *      to allocate the COMMUNICATOR's own exchange blocks (first call, or a larger per / m / what), or of hipSetDevice,
+ *      returns at once without joining exchange 1, and the other ranks wait: as cugp_bcm_predict_allgather's.
+ * cugp_sparse_sharded_cg_solve : cugp_sparse_cg_solve's (inducing == 0) or cugp_sparse_cg_solve_z's (otherwise) loop on the
+ *      sharded objective, run by every rank on identical numbers: identical trajectories by construction.  The start is
+ *      the first local shard's state and is written nowhere: local shards that disagree in the hyper-parameters or Z are
+ *      refused as cugp_sparse_sharded_bound_grad refuses them.  An evaluation that fails gives the loop NaN and the loop goes
+ *      on (the ranks stay in step), but the call then returns that first failure's code and text -- a failed rank, a
+ *      mismatch between ranks -- and writes nothing into the shards; not positive definite is no failure (NaN, CUGP_OK).
+ *      Otherwise the end point and a moved Z are written into every local shard; trace, trace_cap and nevals as there. */
+int cugp_sparse_create_shard(int n_local, int m, int d, int device, int kernel, int ard, double jitter, int chunk_rows,
+                             int shard, int nshards, cugp_sparse **out);
+int cugp_sparse_shard_info(const cugp_sparse *sp, int *shard, int *nshards, long long *rows_total);
+int cugp_sparse_sharded_bound_grad(cugp_sparse *const *shards, int nlocal, cugp_comm *comm, int per, int nshards, int what,
+                                   double *F, double *g, int nh, double *gZ);
+int cugp_sparse_sharded_cg_solve(cugp_sparse *const *shards, int nlocal, cugp_comm *comm, int per, int nshards, int budget,
+                                 int inducing, double *trace, int trace_cap, int *nevals);
 /* ---- combination rules for the experts' predictions.  The reference has no counterpart: cugp_bcm_predict keeps its plain
  *      product of the experts' NOISY predictive distributions (BCM.cpp:45-62), whose variance falls to prior / K away from
  *      the data and below sn2 near it.  The rules below combine the experts' LATENT distributions N(m_k, var_f,k),
