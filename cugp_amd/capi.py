@@ -22,6 +22,7 @@ OBJECTIVE_N = C.CFUNCTYPE(None, C.c_void_p, _dp, C.c_int, _dp, _dp)
 CUGP_OK = 0
 CUGP_KERNEL_SE, CUGP_KERNEL_MATERN32, CUGP_KERNEL_MATERN52 = 0, 1, 2
 CUGP_KERNEL_RQ = 3          # rational quadratic: create calls of its own (cugp_create_rq), not a kind= of the others
+CUGP_ITER_MAX_N = 2147482623     # cugp_iter_*: most rows of a matrix-free handle or of a product's output
 CUGP_COMBINE_POE, CUGP_COMBINE_GPOE, CUGP_COMBINE_BCM, CUGP_COMBINE_RBCM = 0, 1, 2, 3
 CUGP_COMBINE_REFERENCE = -1      # cugp_bcm_predict_grad / cugp_poe_combine_grad: the reference's product of the noisy predictions
 CUGP_ERR_INVALID, CUGP_ERR_NOMEM, CUGP_ERR_DEVICE, CUGP_ERR_NODEVICE = -1, -2, -3, -4
@@ -196,6 +197,20 @@ SIGNATURES = {
     "cugp_bcm_loglik_grad_rows_device_ard": (C.c_int, [C.c_void_p, C.c_void_p, _ip, C.c_int]),
     "cugp_bcm_loglik_grad_allgather_ard": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _dp]),
     "cugp_bcm_cg_solve_ard": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
+    "cugp_iter_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_iter_destroy": (C.c_int, [C.c_void_p]),
+    "cugp_iter_num_hyper": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_iter_set_data": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "cugp_iter_set_loghyper": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_iter_set_split": (C.c_int, [C.c_void_p, C.c_int]),
+    "cugp_iter_apply": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
+    "cugp_iter_apply_cross": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, C.c_int, _dp]),
+    "cugp_iter_solve": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_iter_fit": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, _dp]),
+    "cugp_iter_get_alpha": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_iter_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, _dp]),
+    "cugp_iter_apply_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
+    "cugp_iter_apply_plan_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

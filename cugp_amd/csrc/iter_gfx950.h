@@ -1,0 +1,265 @@
+// iter_gfx950.h -- the fused covariance-times-vectors product of the matrix-free exact GP (cugp_iter_*; DESIGN.md section
+// 33), and the launchers of it and of iter_device.h's vector kernels.
+//
+// Include-point contract.  Included INSIDE namespace cugp by kernels.hip, after kernels.h (ITER_*, IterPlan, CovFn), the
+// d2 / d4 typedefs, CUGP_COV_KERNEL, cov_device.h (DC, DivBy, div_prepare, ard_weights, ShapeArgs, shape_args,
+// kernel_value) and iter_device.h (the vector kernels).
+//
+// k_cov_apply<ARD, KIND>:  out[i][c] = sum_j k(a_i, b_j) V[j][c]  (+ sn2 V[i][c], square form), K in registers only.
+//   v_mfma_f64_16x16x4_f64 takes A from lane (fr = lane & 15, fk = lane >> 4) as A[row fr][k fk]: the lane computes the
+//   ONE entry k(a_{i0 + fr}, b_{j + fk}) and hands it to the MFMA as it is.  B is V[j + fk][16 ct + fr] out of the LDS image
+//   of the stage's V rows; the entry feeds NCT MFMAs (column tiles).  C/D: lane holds rows fk + 4 r, column fr.
+//   Workgroup: 4 waves x 16 rows = ITER_ROWS output rows; the wave's 16 a rows sit in registers, DC features at a time (d <=
+//   DC: loaded once).  It sweeps its stages of ITER_JT b rows in ascending j: per stage 8 squared distances per lane --
+//   differences before squares, (x - x') w squared and added in feature order, no contraction, sqdist_4x4's arithmetic
+//   -- then 8 kernel_value, then 8 NCT MFMAs.  The next stage's b rows (first feature chunk) and V rows are in flight in
+//   registers meanwhile and go into the other LDS buffer behind the MFMAs: one barrier per stage.  Feature chunks beyond
+//   the first are staged through a third buffer inside the stage (two barriers per chunk: d > 16 only).
+//   Rows of b and V beyond nb are staged as zeros: k 0 = 0.  No two waves share an output: no atomics; a column's sums
+//   run j ascending, 4 per MFMA, and do not depend on the other columns.
+//   LDS: ys [2][32][16], yc [32][16], vs [2][32][TPL] doubles, TPL = 16 (one column tile) | 80 (four; 64 + 16: the row stride
+//   is 128 B mod 256 B so that the two k rows of a half-wave's ds_read_b64 fall on different banks): 16 KiB | 52 KiB.
+//   grid (row blocks, split): workgroup (., s) sums the stages [s per, (s + 1) per) and, split > 1, writes its partial block
+//   part[s][na][tp]; k_cov_apply_finish adds the blocks in ascending s (first copied, then a = a + b) and applies the noise
+//   term.  sn2 V[i][c] enters once, by one fma: one rounding.
+#pragma once
+
+template <bool ARD, int KIND, int NCT>
+__device__ __forceinline__ void cov_apply_body(const double* __restrict__ A, int na, const double* __restrict__ B, int nb, int d,
+                                               const HyperScalars* __restrict__ hd, const double* __restrict__ V,
+                                               double* __restrict__ out, int per, int square)
+{
+#pragma clang fp contract(off)
+    constexpr int TP = NCT * 16, TPL = (TP % 32 == 0) ? TP + 16 : TP, NK = ITER_JT / 4;
+    static_assert(ITER_JT * DC == 2 * 256 && ITER_JT * TP == 2 * 256 * NCT, "one d2 of b and NCT d2 of V per thread and stage");
+    __shared__ __attribute__((aligned(16))) double ys[2][ITER_JT][DC];
+    __shared__ __attribute__((aligned(16))) double yc[ITER_JT][DC];
+    __shared__ __attribute__((aligned(16))) double vs[2][ITER_JT][TPL];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const int row = blockIdx.x * ITER_ROWS + wave * 16 + fr;
+    const HyperScalars h = *hd;
+    const double* __restrict__ wts = ard_weights(hd);
+    const DivBy dl = div_prepare(h.ell_sq);
+    ShapeArgs sh = ShapeArgs{0.0, 0.0};
+    if constexpr (KIND == KERNEL_RQ) sh = shape_args<KIND>(wts, d);
+    const int nst = (nb + ITER_JT - 1) / ITER_JT, nch = (d + DC - 1) / DC;
+    const int s0 = blockIdx.y * per, s1 = s0 + per < nst ? s0 + per : nst;
+
+    d4 acc[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++) acc[ct] = (d4){0.0, 0.0, 0.0, 0.0};
+    double ar[DC];
+    auto load_a = [&](int c0) {
+#pragma unroll
+        for (int c = 0; c < DC; c++) ar[c] = (row < na && c0 + c < d) ? A[(size_t)row * d + c0 + c] : 0.0;
+    };
+    // the thread's share of a stage: one feature pair of one b row, NCT column pairs of V rows
+    const int br = tid >> 3, bc = (tid & 7) * 2;
+    d2 rb, rv[NCT];
+    auto fetch_b = [&](int j0, int c0) {
+        const int j = j0 + br, c = c0 + bc;
+        rb[0] = (j < nb && c < d) ? B[(size_t)j * d + c] : 0.0;
+        rb[1] = (j < nb && c + 1 < d) ? B[(size_t)j * d + c + 1] : 0.0;
+    };
+    auto fetch = [&](int st) {
+        const int j0 = st * ITER_JT;
+        fetch_b(j0, 0);
+#pragma unroll
+        for (int q = 0; q < NCT; q++) {
+            const int e = tid + 256 * q, j = j0 + e / (TP / 2);
+            rv[q] = j < nb ? *(const d2*)(V + (size_t)j * TP + 2 * (e % (TP / 2))) : (d2){0.0, 0.0};
+        }
+    };
+    auto put = [&](int buf) {
+        *(d2*)&ys[buf][br][bc] = rb;
+#pragma unroll
+        for (int q = 0; q < NCT; q++) {
+            const int e = tid + 256 * q;
+            *(d2*)&vs[buf][e / (TP / 2)][2 * (e % (TP / 2))] = rv[q];
+        }
+    };
+    double sq[NK];
+    // sq[kk] += the chunk's terms of |(a_row - b_{4 kk + fk}) w|^2, features ascending (a feature beyond d: 0 - 0)
+    auto accumulate = [&](double (*yb)[DC], int c0) {
+#pragma unroll
+        for (int cp = 0; cp < DC / 2; cp++) {
+            const int c = 2 * cp;
+            if (c0 + c < d) {
+                const double w0 = ARD ? wts[c0 + c] : 1.0, w1 = (ARD && c0 + c + 1 < d) ? wts[c0 + c + 1] : 1.0;
+#pragma unroll
+                for (int kk = 0; kk < NK; kk++) {
+                    const d2 yv = *(const d2*)&yb[kk * 4 + fk][c];
+                    double df = ar[c] - yv[0];
+                    if (ARD) df = df * w0;
+                    sq[kk] = sq[kk] + df * df;
+                    df = ar[c + 1] - yv[1];
+                    if (ARD) df = df * w1;
+                    sq[kk] = sq[kk] + df * df;
+                }
+            }
+        }
+    };
+
+    load_a(0);
+    fetch(s0);
+    put(0);
+    __syncthreads();
+    for (int st = s0; st < s1; st++) {
+        const int cur = (st - s0) & 1;
+        const bool more = st + 1 < s1;
+        if (more) fetch(st + 1);
+#pragma unroll
+        for (int kk = 0; kk < NK; kk++) sq[kk] = 0.0;
+        accumulate(ys[cur], 0);
+        for (int ch = 1; ch < nch; ch++) {
+            const d2 keep = rb;
+            fetch_b(st * ITER_JT, ch * DC);
+            __syncthreads();
+            *(d2*)&yc[br][bc] = rb;
+            rb = keep;
+            load_a(ch * DC);
+            __syncthreads();
+            accumulate(yc, ch * DC);
+        }
+        if (nch > 1) load_a(0);
+#pragma unroll
+        for (int kk = 0; kk < NK; kk++) {
+            const double kv = kernel_value<ARD, KIND>(sq[kk], dl, h.signal_var, sh);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ct++)
+                acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(kv, vs[cur][kk * 4 + fk][ct * 16 + fr], acc[ct], 0, 0, 0);
+        }
+        if (more) put(cur ^ 1);
+        __syncthreads();
+    }
+    const bool direct = gridDim.y == 1;
+    double* __restrict__ o = out + (size_t)blockIdx.y * na * TP;
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int i = blockIdx.x * ITER_ROWS + wave * 16 + fk + 4 * r;
+            if (i < na) {
+                const size_t e = (size_t)i * TP + ct * 16 + fr;
+                double v = acc[ct][r];
+                if (square && direct) v = __builtin_fma(h.noise_var, V[e], v);
+                o[e] = v;
+            }
+        }
+}
+
+// one column tile (t <= 16) and four (t <= 64): the two instantiations of the body per covariance family
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_cov_apply(const double* __restrict__ A, int na, const double* __restrict__ B, int nb,
+                                                   int d, const HyperScalars* __restrict__ hd, const double* __restrict__ V,
+                                                   double* __restrict__ out, int per, int square)
+{
+    cov_apply_body<ARD, KIND, 1>(A, na, B, nb, d, hd, V, out, per, square);
+}
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_cov_apply4(const double* __restrict__ A, int na, const double* __restrict__ B, int nb,
+                                                    int d, const HyperScalars* __restrict__ hd, const double* __restrict__ V,
+                                                    double* __restrict__ out, int per, int square)
+{
+    cov_apply_body<ARD, KIND, 4>(A, na, B, nb, d, hd, V, out, per, square);
+}
+
+// out[e] = part[0][e] + part[1][e] + ... in range order (+ sn2 V[e] by one fma: square), e < cnt = na * tp
+__global__ __launch_bounds__(256) void k_cov_apply_finish(const double* __restrict__ part, int split, size_t cnt,
+                                                          const HyperScalars* __restrict__ hd, const double* __restrict__ V,
+                                                          int square, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cnt) return;
+    double s = part[e];
+    for (int k = 1; k < split; k++) s = s + part[(size_t)k * cnt + e];
+    out[e] = square ? __builtin_fma(hd->noise_var, V[e], s) : s;
+}
+
+IterPlan iter_apply_plan(int na, int nb, int force)
+{
+    IterPlan p;
+    p.row_blocks = (int)(((size_t)na + ITER_ROWS - 1) / ITER_ROWS);
+    p.stages = (int)(((size_t)nb + ITER_JT - 1) / ITER_JT);
+    int want = force;
+    if (want <= 0) {
+        want = p.row_blocks >= ITER_SLOTS ? 1 : (ITER_SLOTS + p.row_blocks - 1) / p.row_blocks;
+        want = std::min(want, std::min(ITER_MAX_SPLIT, p.stages / ITER_MIN_STAGES));
+    }
+    want = std::max(1, std::min(want, std::min(p.stages, 65535)));     // (gridDim.y; cugp.h CUGP_ITER_MAX_SPLIT)
+    p.per = (p.stages + want - 1) / want;
+    p.split = (p.stages + p.per - 1) / p.per;          // no empty range
+    return p;
+}
+
+void launch_cov_apply(const double* A, int na, const double* B, int nb, int d, const CovFn& cf, const double* V, int tp,
+                      double* out, double* part, const IterPlan& pl, bool square, hipStream_t s)
+{
+    assert(cf.hd && (tp == 16 || tp == IT_MAXT) && (pl.split == 1 || part));
+    auto kern = tp == 16 ? CUGP_COV_KERNEL(cf, k_cov_apply) : CUGP_COV_KERNEL(cf, k_cov_apply4);
+    hipLaunchKernelGGL(kern, dim3(pl.row_blocks, pl.split), dim3(256), 0, s, A, na, B, nb, d, cf.hd, V,
+                       pl.split > 1 ? part : out, pl.per, square ? 1 : 0);
+    if (pl.split > 1) {
+        const size_t cnt = (size_t)na * tp;
+        hipLaunchKernelGGL(k_cov_apply_finish, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, part, pl.split, cnt, cf.hd, V,
+                           square ? 1 : 0, out);
+    }
+}
+
+void launch_iter_cross_rhs(const double* X, int n, int d, const double* Xt, int count, int tp, const CovFn& cf, double* R,
+                           hipStream_t s)
+{
+    assert(cf.hd);
+    const size_t cnt = (size_t)n * tp;
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_iter_cross_rhs), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, X, n, d, Xt,
+                       count, tp, cf.hd, R);
+}
+
+void launch_iter_dot(const double* a, const double* b, int n, int tp, double* part, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_dot, dim3(iter_blocks(n)), dim3(256), 0, s, a, b, n, tp, part);
+}
+void launch_iter_sum(const double* part, int n, int tp, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_sum, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, out);
+}
+void launch_iter_start(const double* b, double* x, double* r, double* p, int n, int tp, hipStream_t s)
+{
+    const size_t cnt = (size_t)n * tp;
+    hipLaunchKernelGGL(k_iter_start, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, b, x, r, p, cnt);
+}
+void launch_iter_init(const double* part, int n, int tp, double tol, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_init, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, tol, sc);
+}
+void launch_iter_step_a(const double* part, int n, int tp, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_a, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, sc);
+}
+void launch_iter_update(double* x, double* r, const double* p, const double* q, int n, int tp, const double* sc, double* part,
+                        hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_update, dim3(iter_blocks(n)), dim3(256), 0, s, x, r, p, q, n, tp, sc, part);
+}
+void launch_iter_step_b(const double* part, int n, int tp, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_b, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, sc);
+}
+void launch_iter_dir(double* p, const double* r, int n, int tp, const double* sc, int restart_only, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_dir, dim3(iter_blocks(n)), dim3(256), 0, s, p, r, n, tp, sc, restart_only);
+}
+void launch_iter_resid(const double* b, const double* q, double* r, int n, int tp, const double* sc, int final, double* part,
+                       hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_resid, dim3(iter_blocks(n)), dim3(256), 0, s, b, q, r, n, tp, sc, final, part);
+}
+void launch_iter_step_v(const double* part, int n, int tp, int final, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_v, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, final, sc);
+}
+void launch_iter_poison(double* x, int n, int tp, const double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_poison, dim3(iter_blocks(n)), dim3(256), 0, s, x, n, tp, sc);
+}

@@ -415,6 +415,49 @@ struct SparseFinalSharded {
 // (NULL: F only) and the square's partials
 void launch_sparse_finalize_sharded(const SparseFinalSharded& f, const double* suf, const double* part_uu, size_t nb_uu, int nl,
                                     double* out, double* hout, hipStream_t s);
+// ---- matrix-free exact GP (cugp_iter_*; iter_device.h, iter_gfx950.h): nothing of size n^2 ----
+// Vector blocks are [n][tp] row-major, tp = iter_tp(t) columns (t <= ITER_MAXT per launch), zero beyond column t.
+constexpr int ITER_ROWS = 64;        // output rows of a workgroup of k_cov_apply: 4 waves of 16
+constexpr int ITER_JT = 32;          // b and V rows per LDS stage: 8 MFMA steps of 4
+constexpr int ITER_SLOTS = 512;      // workgroups the split aims at (two per CU)
+constexpr int ITER_MIN_STAGES = 8;   // ... with at least this many stages (256 columns) per range
+constexpr int ITER_MAX_SPLIT = 64;
+constexpr int IT_MAXT = 64;          // columns of a vector block at most; the stride of the scalar rows
+constexpr int IT_ROWS = 512;         // rows of a workgroup of the vector kernels
+constexpr int IT_LANES = 16;         // ... whose dot products sum the rows in this many interleaved classes
+inline int iter_tp(int t) { return t <= 16 ? 16 : IT_MAXT; }
+inline int iter_blocks(int n) { return (int)(((size_t)n + IT_ROWS - 1) / IT_ROWS); }
+// the scalars of the t recurrences, sc[SC_ROWS][IT_MAXT] doubles: r'r of the recurrence, b'b, the step length, the ratio,
+// the state (ST_*), sweeps taken while active, the latest TRUE |b - K x|^2, (tol |b|)^2
+enum { SC_RR = 0, SC_BB = 1, SC_A = 2, SC_B = 3, SC_STATE = 4, SC_ITERS = 5, SC_TRUE = 6, SC_TOL2 = 7, SC_ROWS = 8 };
+constexpr double ST_ACTIVE = 0.0, ST_CANDIDATE = 1.0, ST_DONE = 2.0, ST_BROKEN = 3.0, ST_RESTART = 4.0;
+// The split of out = k(A, B) V over the j range (what cugp_iter_apply_plan reports; pure arithmetic): workgroup (row block,
+// s) sums the stages [s per, min((s + 1) per, stages)), stage = ITER_JT columns.  split = 1 where the row blocks alone
+// reach ITER_SLOTS; force > 0 asks for that many ranges (at most one per stage).  t does not enter: a column's bits do not
+// depend on how many columns travel with it.
+struct IterPlan { int split, per, stages, row_blocks; };
+IterPlan iter_apply_plan(int na, int nb, int force);
+// out[i][c] = sum_j k(a_i, b_j) V[j][c] (+ sn2 V[i][c]: square, A == B), i < na, j < nb, c < tp; K is never stored.
+// part: pl.split * na * tp doubles when pl.split > 1 (the ranges' partial blocks, added in range order by a second launch)
+void launch_cov_apply(const double* A, int na, const double* B, int nb, int d, const CovFn& cf, const double* V, int tp,
+                      double* out, double* part, const IterPlan& pl, bool square, hipStream_t s);
+// R[j][c] = k(x_j, xt_c), c < count <= tp, zero columns beyond
+void launch_iter_cross_rhs(const double* X, int n, int d, const double* Xt, int count, int tp, const CovFn& cf, double* R,
+                           hipStream_t s);
+// the recurrences (iter_device.h: each launcher is its kernel's name); part: iter_blocks(n) * tp doubles
+void launch_iter_dot(const double* a, const double* b, int n, int tp, double* part, hipStream_t s);
+void launch_iter_sum(const double* part, int n, int tp, double* out, hipStream_t s);
+void launch_iter_start(const double* b, double* x, double* r, double* p, int n, int tp, hipStream_t s);
+void launch_iter_init(const double* part, int n, int tp, double tol, double* sc, hipStream_t s);
+void launch_iter_step_a(const double* part, int n, int tp, double* sc, hipStream_t s);
+void launch_iter_update(double* x, double* r, const double* p, const double* q, int n, int tp, const double* sc, double* part,
+                        hipStream_t s);
+void launch_iter_step_b(const double* part, int n, int tp, double* sc, hipStream_t s);
+void launch_iter_dir(double* p, const double* r, int n, int tp, const double* sc, int restart_only, hipStream_t s);
+void launch_iter_resid(const double* b, const double* q, double* r, int n, int tp, const double* sc, int final, double* part,
+                       hipStream_t s);
+void launch_iter_step_v(const double* part, int n, int tp, int final, double* sc, hipStream_t s);
+void launch_iter_poison(double* x, int n, int tp, const double* sc, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -227,6 +227,12 @@ static void set_big_lds();
 // k_sparse_predict_cov, k_sparse_gram, sparse_shape, sparse_z_shape and every sparse launcher, those of the five emulable
 // headers above included
 #include "sparse_gfx950.h"
+// the matrix-free exact GP (cugp_iter_*): k_iter_dot .. k_iter_poison, the t conjugate-gradient recurrences, and
+// k_iter_cross_rhs (emulable)
+#include "iter_device.h"
+// k_cov_apply, k_cov_apply4 (K V with K in registers: the entry is the MFMA's A operand), k_cov_apply_finish, iter_apply_plan
+// and the launchers of these and of the emulable header above
+#include "iter_gfx950.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
 // failure is kept (the launch that follows would be rejected) and reported by prepare_kernels().

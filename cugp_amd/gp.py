@@ -727,6 +727,106 @@ class SparseGP:
         return sparse_predict_plan(self.m, nt)
 
 
+class IterativeGP:
+    """The exact GP of all n rows without any n x n matrix (cugp_iter_*): products with K = Kf + sn2 I whose entries are
+    computed in registers, conjugate gradients on them, exact predictive mean and variance at O(n t) memory.  kernel / ard
+    as Covsum's (the rational quadratic names included), the hyper-parameter vector too.  No likelihood, no gradient:
+    hyper-parameters come from elsewhere.  Vectors are target-major, [t, n]."""
+
+    def __init__(self, n, d, kernel="se", ard=False, device=0):
+        self.n, self.d, self.device = int(n), int(d), int(device)
+        self._kind, self.ard = kernel_spec(kernel, ard)
+        self.nh = num_hyper(self._kind, self.ard, self.d)
+        self._h = C.c_void_p()
+        check(capi.lib().cugp_iter_create(self.n, self.d, self.device, self._kind, 1 if self.ard else 0, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            capi.lib().cugp_iter_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_data(self, X, y):
+        X, y = f64(X), f64(y)
+        if X.shape != (self.n, self.d) or y.shape != (self.n,):
+            raise ValueError("expected X %s and y %s" % ((self.n, self.d), (self.n,)))
+        check(capi.lib().cugp_iter_set_data(self._h, ptr(X), ptr(y)))
+
+    def set_loghyper(self, hp):
+        hp = f64(hp)
+        if hp.shape != (self.nh,):
+            raise ValueError("expected %d log-hyper-parameters" % self.nh)
+        check(capi.lib().cugp_iter_set_loghyper(self._h, ptr(hp), self.nh))
+
+    def set_split(self, split):
+        """Ask for `split` ranges of the products' j range (0: the library's rule; plan() shows what is taken)."""
+        check(capi.lib().cugp_iter_set_split(self._h, int(split)))
+
+    def _block(self, V):
+        V = f64(V)
+        V = V.reshape(1, -1) if V.ndim == 1 else V
+        if V.ndim != 2 or V.shape[1] != self.n or V.shape[0] < 1:
+            raise ValueError("expected vectors [t, %d]" % self.n)
+        return V
+
+    def apply(self, V):
+        """(Kf + sn2 I) V for V [t, n] (cugp_iter_apply)."""
+        V = self._block(V)
+        out = np.empty_like(V)
+        check(capi.lib().cugp_iter_apply(self._h, ptr(V), V.shape[0], ptr(out)))
+        return out
+
+    def apply_cross(self, Xt, V):
+        """k(Xt, X) V [t, nt], no noise term (cugp_iter_apply_cross)."""
+        Xt, V = f64(Xt).reshape(-1, self.d), self._block(V)
+        out = np.empty((V.shape[0], Xt.shape[0]))
+        check(capi.lib().cugp_iter_apply_cross(self._h, ptr(Xt), Xt.shape[0], ptr(V), V.shape[0], ptr(out)))
+        return out
+
+    def solve(self, B, tol=1e-10, max_iter=1000, check_every=10):
+        """(X [t, n], info [t, 4]) with K X = B; info per column: sweeps, true |b - K x| / |b|, converged, breakdown."""
+        B = self._block(B)
+        X, info = np.empty_like(B), np.empty((B.shape[0], 4))
+        check(capi.lib().cugp_iter_solve(self._h, ptr(B), B.shape[0], float(tol), int(max_iter), int(check_every), ptr(X),
+                                         ptr(info)))
+        return X, info
+
+    def fit(self, tol=1e-10, max_iter=1000, check_every=10):
+        """alpha = K^-1 y, kept on the device until data or hyper-parameters change; -> info [4] as solve's."""
+        info = np.empty(4)
+        check(capi.lib().cugp_iter_fit(self._h, float(tol), int(max_iter), int(check_every), ptr(info)))
+        return info
+
+    def alpha(self):
+        a = np.empty(self.n)
+        check(capi.lib().cugp_iter_get_alpha(self._h, ptr(a)))
+        return a
+
+    def predict(self, Xt, var=True, tol=1e-10, max_iter=1000, check_every=10):
+        """(mean, var, info [nt, 4]) at the test points, var with sn2 as Covsum's; var=False: (mean, None, None), no solve."""
+        Xt = f64(Xt).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        mean = np.empty(nt)
+        v, info = (np.empty(nt), np.empty((nt, 4))) if var else (None, None)
+        check(capi.lib().cugp_iter_predict(self._h, ptr(Xt), nt, ptr(mean), ptr(v) if var else None, float(tol), int(max_iter),
+                                           int(check_every), ptr(info) if var else None))
+        return mean, v, info
+
+    @staticmethod
+    def plan(na, nb, t=1, split=0):
+        """{split, per, stages, row_blocks} of a product of na x nb entries (cugp_iter_apply_plan_split; no device)."""
+        out = (C.c_int * 4)()
+        rc = capi.lib().cugp_iter_apply_plan_split(int(na), int(nb), int(t), int(split), out)
+        if rc < 0:
+            check(rc)
+        return dict(zip(("split", "per", "stages", "row_blocks"), out))
+
+
 def sparse_plan(n, m, chunk_rows=0):
     """cugp_sparse_plan's passes for n rows against m inducing inputs: [(row0, rows, rows_padded, split, kstep)]."""
     out = (C.c_int * 5)()

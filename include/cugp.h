@@ -881,6 +881,62 @@ int cugp_bcm_loglik_grad_rows_device_ard(cugp_bcm *b, double *dev_rows, const in
 int cugp_bcm_loglik_grad_allgather_ard(cugp_bcm *b, cugp_comm *c, int per, int nh, double *rows_out);
 int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap, int *nevals);
 
+/* ---- matrix-free exact GP: products with K whose entries are never stored, conjugate gradients on them ----
+ * Every other exact call stores n^2 numbers (four npad x npad matrices per cugp_gp).  A cugp_iter handle holds X [n][d], y,
+ * theta and a handful of n x 64 vectors: K = Kf + sn2 I of ALL n rows is applied to blocks of vectors with its entries
+ * computed in registers (k_cov_apply, fp64 MFMA), and K^-1 b comes from conjugate gradients on that product -- the exact
+ * predictive mean and variance at O(n t) memory, for hyper-parameters trained elsewhere (a subset, a BCM, the sparse
+ * model).  No log marginal likelihood, no gradient, no preconditioner: the iteration count grows with cond(K).
+ *
+ * Model: kernel in {CUGP_KERNEL_SE, _MATERN32, _MATERN52, CUGP_KERNEL_RQ}, ard in {0, 1}; theta as the dense handles'
+ * ([log l | log l_1 .. log l_d, (RQ: log alpha,) log sigma_f, log sigma_n], nh = (ard ? d : 1) + (RQ ? 1 : 0) + 2).
+ * Conventions: vectors cross the ABI target-major, [t][n] as cugp_set_targets' Y; any t (64 columns travel per launch).
+ * Sums run in a fixed order: two calls give the same bits, and a column's bits do not depend on the columns beside it.
+ *
+ * cugp_iter_apply       : out [t][n] = (Kf + sn2 I) V.
+ * cugp_iter_apply_cross : out [t][nt] = k(Xt, X) V, no noise term.
+ * cugp_iter_solve       : Xout [t][n] = K^-1 B by t independent recurrences that share each product (not block CG: every
+ *      column has its own step length; a finished or broken column is frozen).  The host reads the columns' status every
+ *      check_every sweeps and waits nowhere else.  A column is converged only on its TRUE residual: when its recurrence
+ *      reaches |r| <= tol |b| the solver forms b - K x with one more product; if that passes too, the column is done, else
+ *      it goes on from the true residual.  info (may be NULL) [t][4] per column: sweeps taken, |b - K x| / |b| of the
+ *      returned x, converged (1 / 0), breakdown (1 / 0).  A zero column returns zeros in 0 sweeps.  max_iter sweeps without
+ *      convergence: the iterate so far, converged 0.  p'Kp <= 0 or a NaN (a covariance that cannot be factored, as an alpha
+ *      that overflowed): that column is NaN with breakdown 1, and the call returns CUGP_OK.
+ * cugp_iter_fit         : alpha = K^-1 y, kept on the device until the data or theta change (info [4], may be NULL);
+ *      cugp_iter_get_alpha reads it back.
+ * cugp_iter_predict     : mean = k(Xt, X) alpha; var (may be NULL: the mean alone) = sf2 + sn2 - ks' K^-1 ks, sn2 included
+ *      as in cugp_predict, the solves in batches of 64 test points (info [nt][4], may be NULL: theirs).
+ * cugp_iter_apply_plan  : how a product of na x nb entries is split over the j range (pure arithmetic, no device): out =
+ *      {S, stages per range, stages, row blocks}; range s of row block i sums the columns [32 s out[1], 32 (s + 1) out[1]) in
+ *      ascending order, the ranges are added in ascending s.  S = 1 where the row blocks alone fill the device.  Returns S.
+ *      _split: with S asked for (0: the rule); cugp_iter_set_split asks it of a handle's products (test and tuning hook).
+ *
+ * Refusals, all CUGP_ERR_INVALID before any device call with the call's name in cugp_last_error: a NULL argument (other
+ * than info and var); n, d, t, nt < 1; n or nt beyond CUGP_ITER_MAX_N; an unknown kernel; ard outside {0, 1}; a negative
+ * device; a split outside [0, CUGP_ITER_MAX_SPLIT]; nh that is not the handle's; tol not positive and finite; max_iter or check_every < 1; a product or
+ * solve before both cugp_iter_set_data and cugp_iter_set_loghyper; cugp_iter_predict or cugp_iter_get_alpha without a
+ * cugp_iter_fit since the data or theta last changed.  CUGP_ERR_NODEVICE from cugp_iter_create without a GPU. */
+#define CUGP_ITER_MAX_N 2147482623   /* INT_MAX - 1024: row indices are ints, offsets size_t */
+#define CUGP_ITER_MAX_SPLIT 65535    /* the ranges of a product are the second dimension of its launch grid */
+typedef struct cugp_iter cugp_iter;
+int cugp_iter_create(int n, int d, int device, int kernel, int ard, cugp_iter **out);
+int cugp_iter_destroy(cugp_iter *h);
+int cugp_iter_num_hyper(const cugp_iter *h, int *nh);
+int cugp_iter_set_data(cugp_iter *h, const double *X, const double *y);
+int cugp_iter_set_loghyper(cugp_iter *h, const double *theta, int nh);
+int cugp_iter_set_split(cugp_iter *h, int split);
+int cugp_iter_apply(cugp_iter *h, const double *V, int t, double *out);
+int cugp_iter_apply_cross(cugp_iter *h, const double *Xt, int nt, const double *V, int t, double *out);
+int cugp_iter_solve(cugp_iter *h, const double *B, int t, double tol, int max_iter, int check_every, double *Xout,
+                    double *info /* may be NULL */);
+int cugp_iter_fit(cugp_iter *h, double tol, int max_iter, int check_every, double *info /* may be NULL */);
+int cugp_iter_get_alpha(cugp_iter *h, double *alpha);
+int cugp_iter_predict(cugp_iter *h, const double *Xt, int nt, double *mean, double *var /* may be NULL */, double tol,
+                      int max_iter, int check_every, double *info /* may be NULL */);
+int cugp_iter_apply_plan(int na, int nb, int t, int out[4]);
+int cugp_iter_apply_plan_split(int na, int nb, int t, int split, int out[4]);
+
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);
 int cugp_mfma_peak_tflops(int device, double *tflops);

@@ -1,0 +1,107 @@
+"""Timings of the matrix-free exact GP (gp.IterativeGP) on one GPU -> profiles/iter_probe.json.  D = 10, SE and RQ-ARD.
+apply at N for t = 1, 16 and 64, one after the other (not interleaved): each the median of --reps calls after one warm-up
+call of its own, in seconds and covariance entries per second, host packing and copies included -- the call as a user makes
+it.  fit, predict (the mean at --nt points, the variance at the first --ntvar of them) and the 8192-row comparison of
+fit's alpha with Covsum.get_alpha() are SINGLE calls without a warm-up: their times include first-use allocations, and
+exact_seconds_first_call the exact handle's first evaluation.  Read them as orders of magnitude, with the sweep counts.
+
+    python tools/iter_probe.py [--n 100000] [--reps 3] [--big 0] [--out profiles/iter_probe.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from conftest import synth  # noqa: E402
+from cugp_amd import capi, gp  # noqa: E402
+
+D = 10
+THETA = {"se": [1.5, 0.0, -1.0], "rq_ard": np.linspace(1.3, 1.7, D).tolist() + [0.4, 0.0, -1.0]}
+
+
+def timed(fn, reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        out = fn()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=100000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--big", type=int, default=0, help="one apply (t = 16, SE) at this many rows, e.g. 1000000")
+    ap.add_argument("--nt", type=int, default=1000, help="test points of the predictions")
+    ap.add_argument("--ntvar", type=int, default=64, help="... of which the first ntvar get a variance (64 share one solve)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "iter_probe.json"))
+    a = ap.parse_args()
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "nt": a.nt, "ntvar": a.ntvar, "d": D, "reps": a.reps, "families": {}}
+    X, y = synth(a.n, d=D)
+    Xt = synth(a.nt, d=D, seed=7)[0]
+    rng = np.random.default_rng(0)
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        r = {"plan": g.plan(a.n, a.n), "apply": {}}
+        for t in (1, 16, 64):
+            V = rng.standard_normal((t, a.n))
+            s, _ = timed(lambda: g.apply(V), a.reps)
+            r["apply"][str(t)] = {"seconds": s, "entries_per_s": float(a.n) * a.n / s}
+            print(fam, "apply t", t, r["apply"][str(t)], flush=True)
+        t0 = time.perf_counter()
+        info = g.fit(1e-8, 1000, 10)
+        r["fit"] = {"seconds": time.perf_counter() - t0, "sweeps": info[0], "rel_residual": info[1], "converged": info[2]}
+        print(fam, "fit", r["fit"], flush=True)
+        t0 = time.perf_counter()
+        g.predict(Xt, var=False)
+        r["predict_mean"] = {"seconds": time.perf_counter() - t0}
+        t0 = time.perf_counter()
+        _, _, pi = g.predict(Xt[:a.ntvar], True, 1e-8, 1000, 10)
+        r["predict_var"] = {"seconds": time.perf_counter() - t0, "sweeps_max": float(pi[:, 0].max()),
+                                 "converged": float(pi[:, 2].min())}
+        print(fam, "predict", r["predict_mean"], r["predict_var"], flush=True)
+        g.close()
+        res["families"][fam] = r
+    n8 = 8192
+    X8, y8 = synth(n8, d=D)
+    c = gp.Covsum(n8, D)
+    c.set_loghyperparam(THETA["se"])
+    t0 = time.perf_counter()
+    c.loglik_grad(X8, y8)
+    a8 = c.get_alpha()
+    exact_s = time.perf_counter() - t0
+    g = gp.IterativeGP(n8, D, kernel="se")
+    g.set_data(X8, y8)
+    g.set_loghyper(THETA["se"])
+    t0 = time.perf_counter()
+    info = g.fit(1e-10, 1000, 10)
+    res["n8192"] = {"fit_seconds": time.perf_counter() - t0, "exact_seconds_first_call": exact_s, "sweeps": info[0],
+                    "alpha_max_abs_diff": float(np.max(np.abs(g.alpha() - a8))), "alpha_max_abs": float(np.max(np.abs(a8)))}
+    if a.big:
+        Xb, yb = synth(a.big, d=D)
+        g = gp.IterativeGP(a.big, D, kernel="se")
+        g.set_data(Xb, yb)
+        g.set_loghyper(THETA["se"])
+        V = rng.standard_normal((16, a.big))
+        t0 = time.perf_counter()
+        g.apply(V)
+        s = time.perf_counter() - t0
+        res["big"] = {"n": a.big, "t": 16, "seconds_first_call": s, "entries_per_s": float(a.big) ** 2 / s}
+    res["not_measured"] = ["k_build / k_cross entries per second at 8192 rows (kernel time alone)", "device time without the host's packing"]
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
