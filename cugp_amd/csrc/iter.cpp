@@ -25,6 +25,14 @@ struct cugp_iter {
     int split = 0;                 // ranges of the product's j split; 0: iter_apply_plan's rule
     Scratch vb, vx, vr, vp, vq, vk, alpha, apart, dpart, xt, res;
     std::vector<double> host;      // packing: [t][n] target-major <-> [n][tp]
+    // the preconditioner (cugp_iter_set_precond): M = L L' + sn2 I from a pivoted Cholesky factor of Kf
+    int pc_rank = 0, pc_got = 0, pc_rp = 0;       // asked for, achieved, padded (pc_plan)
+    bool pc_built = false;         // L, Q hold for (data, theta, pc_rank); a rank of 0 is built as it stands
+    Scratch pL, pQ, pdres, pshv, pint, ppart, pT, vz;   // L, Q [n][rp]; residual diagonal; argmax shares; piv, ctl and the
+                                   // shares' rows (ints); partial blocks of Q'R; T = Q'R; z = M^-1 r
+    cugp_gp* pf = nullptr;         // the r x r side: an ordinary handle whose A receives C = sn2 I + L'L (as sparse.cpp's B)
+    int pf_n = 0;                  // ... the size it was created for
+    std::vector<int> hpiv;         // the pivots and ctl as read back: [rp + 2]
 };
 
 namespace {
@@ -98,25 +106,104 @@ int read_status(cugp_iter* h, int tp, const char* call, Counts* k)
     return CUGP_OK;
 }
 
+// The factor and the r x r side for the handle's data, theta and rank as they stand; one wait behind the factor's launches
+// (the device decides where it ends), one around the small factorisation.
+int precond_build(cugp_iter* h, const char* call)
+{
+    if (h->pc_built) return CUGP_OK;
+    const int n = h->n, rank = h->pc_rank;
+    h->pc_got = h->pc_rp = 0;
+    if (rank == 0) { h->pc_built = true; return CUGP_OK; }
+    const CovFn cf = cov_of(h);
+    hipStream_t s = h->stream;
+    const PcPlan pl = pc_plan(n, rank);
+    const int rp = pl.rp, nwg = pchol_blocks(n);
+    int rc;
+    if ((rc = h->pL.grow((size_t)n * rp, s)) || (rc = h->pQ.grow((size_t)n * rp, s)) || (rc = h->pdres.grow(n, s)) ||
+        (rc = h->pshv.grow((size_t)2 * nwg, s)) || (rc = h->pint.grow(((size_t)rp + 2 + 2 * (size_t)nwg + 1) / 2, s)) ||
+        (rc = h->ppart.grow((size_t)pl.blocks * rp * IT_MAXT, s)) || (rc = h->pT.grow((size_t)rp * IT_MAXT, s)))
+        return rc;
+    int *piv = (int*)h->pint.p, *ctl = piv + rp, *shi = ctl + 2;
+    double* L = h->pL.p;
+    launch_pchol_init(cf, h->d, n, rp, L, h->pdres.p, piv, ctl, s);
+    for (int k = 0; k <= rank; k++) launch_pchol_step(h->dX, n, h->d, cf, L, rp, h->pdres.p, piv, ctl, h->pshv.p, shi, k, rank, s);
+    h->hpiv.assign(rp + 2, -1);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->hpiv.data(), piv, (size_t)(rp + 2) * sizeof(int), hipMemcpyDeviceToHost, s);
+    if ((rc = sync_or_fail(s, call, e))) return rc;
+    int got = std::max(0, std::min(h->hpiv[rp], rank));
+    if (h->hpiv[rp + 1]) {                                // a NaN residual: no factor at all, the recurrences run plain
+        got = 0;
+        HIPCHK(hipMemsetAsync(L, 0, (size_t)n * rp * sizeof(double), s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    h->pc_got = got;
+    h->pc_rp = rp;
+    if (got == 0) { h->pc_built = true; return CUGP_OK; }
+    if (!h->pf || h->pf_n != rp) {
+        if (h->pf) cugp_destroy(h->pf);
+        h->pf = nullptr;
+        if ((rc = cugp_create(rp, 1, h->device, &h->pf))) return rc;
+        h->pf_n = rp;
+        if ((rc = ensure_factor_bufs(h->pf)) || (rc = ensure_inverse_bufs(h->pf))) return rc;
+    }
+    cugp_gp* f = h->pf;
+    launch_pc_eye(f->dA, f->npad, s);
+    for (int c0 = 0; c0 < rp; c0 += 64) {                 // C = sn2 I + L'L, a 64-column group at a time
+        launch_pc_project(L, L + c0, rp, IT_MAXT, n, pl, h->ppart.p, s);
+        launch_pc_gram_finish(h->ppart.p, pl.blocks, rp, cf.hd, f->dA, f->npad, c0, s);
+    }
+    if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
+    if ((rc = la_factor_inverse(f, true))) return rc;    // Lc, Lc^-1, Lc^-T (its own stream, waited for)
+    for (int c0 = 0; c0 < rp; c0 += 64) launch_pc_correct(L, rp, f->dU, f->npad, c0, nullptr, cf.hd, n, IT_MAXT, h->pQ.p, rp, s);
+    if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
+    h->pc_built = true;
+    return CUGP_OK;
+}
+
+// Z [n][tp] = M^-1 R = (R - Q (Q'R)) / sn2 on the handle's stream (built, achieved rank > 0)
+int precond_apply_dev(cugp_iter* h, const double* R, int tp, double* Z)
+{
+    const PcPlan pl = pc_plan(h->n, h->pc_rank);
+    launch_pc_project(h->pQ.p, R, tp, tp, h->n, pl, h->ppart.p, h->stream);
+    launch_pc_project_finish(h->ppart.p, pl.blocks, (size_t)pl.rp * tp, h->pT.p, h->stream);
+    launch_pc_correct(h->pQ.p, pl.rp, h->pT.p, tp, 0, R, h->dhs, h->n, tp, Z, tp, h->stream);
+    return CUGP_OK;
+}
+
 // x (h->vx) = K^-1 B for the tp columns of the device block B by tp independent recurrences; the scalars stay in h->hsc
 int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol, int max_iter, int check_every, const char* call)
 {
     const int n = h->n;
     hipStream_t s = h->stream;
     int rc;
+    if ((rc = precond_build(h, call))) return rc;
+    const bool pc = h->pc_got > 0;                     // else: the plain recurrence, launch for launch
     for (Scratch* v : {&h->vx, &h->vr, &h->vp, &h->vq})
         if ((rc = v->grow((size_t)n * tp, s))) return rc;
+    if (pc && (rc = h->vz.grow((size_t)n * tp, s))) return rc;
     if ((rc = h->dpart.grow((size_t)iter_blocks(n) * IT_MAXT, s))) return rc;
-    double *x = h->vx.p, *r = h->vr.p, *p = h->vp.p, *q = h->vq.p, *part = h->dpart.p, *sc = h->dsc;
+    double *x = h->vx.p, *r = h->vr.p, *p = h->vp.p, *q = h->vq.p, *z = h->vz.p, *part = h->dpart.p, *sc = h->dsc;
+    // z = M^-1 r and r'z behind it; fresh: the start and a restart (r'z alone), else a sweep (the ratio too)
+    auto precondition = [&](int fresh) {
+        precond_apply_dev(h, r, tp, z);
+        launch_iter_dot(r, z, n, tp, part, s);
+        launch_iter_step_z(part, n, tp, fresh, sc, s);
+    };
     launch_iter_dot(B, B, n, tp, part, s);
     launch_iter_init(part, n, tp, tol, sc, s);
     launch_iter_start(B, x, r, p, n, tp, s);
+    if (pc) {
+        precondition(1);
+        launch_iter_dir(p, z, n, tp, sc, 0, s);        // (the ratio is 0 from k_iter_init: p = z)
+    }
     // the true residual of the columns that wait for it (final: of the active ones too)
     auto verify = [&](int final) {
         if (const int e = product(h, cf, h->dX, n, x, tp, q, true)) return e;
         launch_iter_resid(B, q, r, n, tp, sc, final, part, s);
         launch_iter_step_v(part, n, tp, final, sc, s);
-        if (!final) launch_iter_dir(p, r, n, tp, sc, 1, s);
+        if (!final && pc) precondition(1);
+        if (!final) launch_iter_dir(p, pc ? z : r, n, tp, sc, 1, s);
         return (int)CUGP_OK;
     };
     Counts k;
@@ -132,10 +219,12 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
         for (int j = 0; j < m; j++) {
             if ((rc = product(h, cf, h->dX, n, p, tp, q, true))) return rc;
             launch_iter_dot(p, q, n, tp, part, s);
-            launch_iter_step_a(part, n, tp, sc, s);
+            if (pc) launch_iter_step_a_pc(part, n, tp, sc, s);
+            else launch_iter_step_a(part, n, tp, sc, s);
             launch_iter_update(x, r, p, q, n, tp, sc, part, s);
             launch_iter_step_b(part, n, tp, sc, s);
-            launch_iter_dir(p, r, n, tp, sc, 0, s);
+            if (pc) precondition(0);
+            launch_iter_dir(p, pc ? z : r, n, tp, sc, 0, s);
         }
         it += m;
     }
@@ -202,8 +291,8 @@ int cugp_iter_create(int n, int d, int device, int kernel, int ard, cugp_iter** 
     if (e == hipSuccess) e = hipMalloc((void**)&h->dyb, (size_t)n * 16 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&h->dhs, hs_bytes(h));
     if (e == hipSuccess) e = hipHostMalloc((void**)&h->hhs, hs_bytes(h), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void**)&h->dsc, (size_t)(SC_ROWS + 1) * IT_MAXT * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&h->hsc, (size_t)(SC_ROWS + 1) * IT_MAXT * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dsc, (size_t)SC_ALLOC * IT_MAXT * sizeof(double));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->hsc, (size_t)SC_ALLOC * IT_MAXT * sizeof(double), hipHostMallocDefault);
     if (e != hipSuccess) {
         rc = fail(e == hipErrorOutOfMemory ? CUGP_ERR_NOMEM : CUGP_ERR_DEVICE, call, e);
         cugp_iter_destroy(h);
@@ -218,7 +307,10 @@ int cugp_iter_destroy(cugp_iter* h)
     if (!h) return CUGP_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res}) v->release();
+    for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res, &h->pL,
+                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz})
+        v->release();
+    if (h->pf) cugp_destroy(h->pf);
     for (void* p : {(void*)h->dX, (void*)h->dyb, (void*)h->dhs, (void*)h->dsc})
         if (p) (void)hipFree(p);
     if (h->hhs) (void)hipHostFree(h->hhs);
@@ -250,6 +342,7 @@ int cugp_iter_set_data(cugp_iter* h, const double* X, const double* y)
     HIPCHK(hipSetDevice(h->device));
     h->fit_valid = false;
     h->have_data = false;
+    h->pc_built = false;
     HIPCHK(hipMemcpyAsync(h->dX, X, (size_t)h->n * h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h->host.assign((size_t)h->n * 16, 0.0);
     for (size_t i = 0; i < (size_t)h->n; i++) h->host[i * 16] = y[i];
@@ -267,6 +360,7 @@ int cugp_iter_set_loghyper(cugp_iter* h, const double* theta, int nh)
     HIPCHK(hipSetDevice(h->device));
     h->fit_valid = false;
     h->have_theta = false;
+    h->pc_built = false;
     h->theta.assign(theta, theta + nh);
     const double* sf = theta + nh - 2;
     *h->hhs = HyperScalars{h->route ? 1.0 : std::exp(theta[0] * 2), std::exp(sf[0] * 2), std::exp(sf[1] * 2)};
@@ -278,6 +372,80 @@ int cugp_iter_set_loghyper(cugp_iter* h, const double* theta, int nh)
     HIPCHK(hipMemcpyAsync(h->dhs, h->hhs, hs_bytes(h), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_theta = true;
+    return CUGP_OK;
+}
+
+int cugp_iter_set_precond(cugp_iter* h, int rank)
+{
+    const char* call = "cugp_iter_set_precond";
+    if (!h) return invalid_arg(call, "null handle");
+    if (rank < 0 || rank > std::min(h->n, CUGP_ITER_MAX_RANK)) return invalid_arg(call, "rank must lie in [0, min(n, CUGP_ITER_MAX_RANK)]");
+    h->pc_rank = rank;
+    h->pc_built = false;
+    return CUGP_OK;
+}
+
+int cugp_iter_precond_plan(int n, int rank, int out[4])
+{
+    const char* call = "cugp_iter_precond_plan";
+    if (!out) return invalid_arg(call, "out is NULL");
+    if (n < 1 || n > CUGP_ITER_MAX_N) return invalid_arg(call, "n must lie in [1, CUGP_ITER_MAX_N]");
+    if (rank < 0 || rank > std::min(n, CUGP_ITER_MAX_RANK)) return invalid_arg(call, "rank must lie in [0, min(n, CUGP_ITER_MAX_RANK)]");
+    const PcPlan p = pc_plan(n, rank);
+    out[0] = p.rp; out[1] = p.per; out[2] = p.blocks; out[3] = p.per / 4;
+    return p.blocks;
+}
+
+// the factor for the handle as it stands (a rank of 0 needs neither data nor theta)
+static int precond_ready(cugp_iter* h, const char* call)
+{
+    int rc;
+    if (h->pc_rank > 0 && (rc = ready(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    return precond_build(h, call);
+}
+
+int cugp_iter_precond_info(cugp_iter* h, int out[4])
+{
+    const char* call = "cugp_iter_precond_info";
+    if (!h || !out) return invalid_arg(call, "null argument");
+    if (const int rc = precond_ready(h, call)) return rc;
+    out[0] = h->pc_rank; out[1] = h->pc_got; out[2] = h->pc_rp; out[3] = h->pc_built ? 1 : 0;
+    return CUGP_OK;
+}
+
+int cugp_iter_get_precond(cugp_iter* h, double* L, int* piv)
+{
+    const char* call = "cugp_iter_get_precond";
+    if (!h || !L || !piv) return invalid_arg(call, "null argument");
+    if (const int rc = precond_ready(h, call)) return rc;
+    const size_t n = h->n, rp = h->pc_rp, got = h->pc_got;
+    if (got == 0) return CUGP_OK;
+    h->host.resize(n * rp);
+    HIPCHK(hipMemcpyAsync(h->host.data(), h->pL.p, n * rp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; i++)
+        for (size_t m = 0; m < got; m++) L[i * got + m] = h->host[i * rp + m];
+    for (size_t m = 0; m < got; m++) piv[m] = h->hpiv[m];
+    return CUGP_OK;
+}
+
+int cugp_iter_precond_apply(cugp_iter* h, const double* V, int t, double* out)
+{
+    const char* call = "cugp_iter_precond_apply";
+    if (!h || !V || !out) return invalid_arg(call, "null argument");
+    if (t < 1) return invalid_arg(call, "t must be positive");
+    if (h->pc_rank == 0) return invalid_arg(call, "no preconditioner asked for (cugp_iter_set_precond)");
+    int rc;
+    if ((rc = precond_ready(h, call))) return rc;
+    if (h->pc_got == 0) return invalid_arg(call, "the factor ended at rank 0: there is no preconditioner to apply");
+    for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
+        if ((rc = pack(h, V, h->n, c0, cnt, tp, h->vb)) || (rc = h->vz.grow((size_t)h->n * tp, h->stream))) return rc;
+        precond_apply_dev(h, h->vb.p, tp, h->vz.p);
+        if ((rc = sync_or_fail(h->stream, call, hipGetLastError()))) return rc;
+        if ((rc = unpack(h, h->vz.p, h->n, c0, cnt, tp, out))) return rc;
+    }
     return CUGP_OK;
 }
 

@@ -225,3 +225,181 @@ __global__ __launch_bounds__(256) void k_iter_cross_rhs(const double* __restrict
     }
     R[e] = v;
 }
+
+// ---- the preconditioned recurrences: z = M^-1 r, p = z + b p, a = r'z / p'Kp, b = r'z_new / r'z ----
+// The plain recurrence's kernels serve wherever the arithmetic is the same: k_iter_update (x, r and the shares of r'r),
+// k_iter_step_b (the sweep counted, the candidate test on r'r; the ratio it leaves in SC_B is overwritten by k_iter_step_z
+// before anything reads it), k_iter_dir with z in r's place (p = z + b p, restart: p = z), k_iter_resid, k_iter_step_v.
+// r'z lives in row SC_RZ, behind the rows the host reads.
+
+// one workgroup, behind the shares of p'q: a = r'z / p'Kp; p'Kp <= 0 or NaN: the column is broken
+__global__ __launch_bounds__(256) void k_iter_step_a_pc(const double* __restrict__ part, int nblk, int tp, double* __restrict__ sc)
+{
+    const int c = threadIdx.x;
+    if (c >= tp) return;
+    double st = sc[SC_STATE * IT_MAXT + c];
+    if (st == ST_RESTART) st = ST_ACTIVE;
+    if (st == ST_ACTIVE) {
+        const double pq = iter_sum_parts(part, nblk, tp, c);
+        if (pq > 0.0 && pq - pq == 0.0) sc[SC_A * IT_MAXT + c] = sc[SC_RZ * IT_MAXT + c] / pq;
+        else st = ST_BROKEN;
+    }
+    sc[SC_STATE * IT_MAXT + c] = st;
+}
+
+// one workgroup, behind the shares of r'z for a fresh z = M^-1 r.  Active columns: b = r'z / (the r'z before it) unless
+// `first` (the start: b stays 0, so that k_iter_dir leaves p = z); columns that go on from their true residual: r'z alone.
+// r'z <= 0 or NaN: the column is broken
+__global__ __launch_bounds__(256) void k_iter_step_z(const double* __restrict__ part, int nblk, int tp, int first,
+                                                     double* __restrict__ sc)
+{
+    const int c = threadIdx.x;
+    if (c >= tp) return;
+    const double st = sc[SC_STATE * IT_MAXT + c];
+    if (st != ST_ACTIVE && st != ST_RESTART) return;
+    const double rz = iter_sum_parts(part, nblk, tp, c);
+    if (!(rz > 0.0 && rz - rz == 0.0)) { sc[SC_STATE * IT_MAXT + c] = ST_BROKEN; return; }
+    if (st == ST_ACTIVE && !first) sc[SC_B * IT_MAXT + c] = rz / sc[SC_RZ * IT_MAXT + c];
+    sc[SC_RZ * IT_MAXT + c] = rz;
+}
+
+// ---- the pivoted Cholesky factor L L' ~ Kf of the preconditioner, one launch per step ----
+// State: L [n][rp] row-major (zero beyond the achieved rank), the residual diagonal dres [n] (-inf: the row is a pivot),
+// piv [rp], ctl = {achieved rank, -1 while the factor runs; NaN seen}, and the workgroups' argmax shares of the step before
+// (value, row), two sets used in turn.  A workgroup owns PCH_ROWS rows, one per thread.
+
+// the better of two argmax candidates: the larger value, the lower row on equal values (a total order: the tree's shape
+// does not matter); `bad` collects NaN residuals
+__device__ __forceinline__ void pchol_argmax(double* rv, int* ri, int* rb, int tid)
+{
+    for (int h = PCH_ROWS / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (tid < h) {
+            const double v = rv[tid + h];
+            const int i = ri[tid + h];
+            if (v > rv[tid] || (v == rv[tid] && i < ri[tid])) { rv[tid] = v; ri[tid] = i; }
+            rb[tid] |= rb[tid + h];
+        }
+    }
+    __syncthreads();
+}
+
+// L = 0, dres = k(x, x) (the family's kernel_value at distance 0), piv = -1, ctl = {-1, 0}; e over n * rp entries
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_pchol_init(const HyperScalars* __restrict__ hd, int d, int n, int rp,
+                                                    double* __restrict__ L, double* __restrict__ dres, int* __restrict__ piv,
+                                                    int* __restrict__ ctl)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)n * rp) return;
+    L[e] = 0.0;
+    if (e < (size_t)n) {
+        const HyperScalars h = *hd;
+        ShapeArgs sh = ShapeArgs{0.0, 0.0};
+        if constexpr (KIND == KERNEL_RQ) sh = shape_args<KIND>(ard_weights(hd), d);
+        dres[e] = kernel_value<ARD, KIND>(0.0, div_prepare(h.ell_sq), h.signal_var, sh);
+    }
+    if (e < (size_t)rp) piv[e] = -1;
+    if (e < 2) ctl[e] = e == 0 ? -1 : 0;
+}
+
+// Step k (k == kmax: the closing launch, which only decides).  Every workgroup reduces the shares of the step before --
+// in ascending order, the largest residual wins, the lowest row on ties -- and so knows the pivot p without a second
+// launch or a host wait.  The factor ends here (ctl[0] = k; every later launch returns at once) when the largest residual
+// is NaN, or not above PCH_FLOOR (k + 1) u sf2.  Else thread i forms c = k(x_i, x_p) - sum_{m < k} L[i][m] L[p][m] (the
+// distance as k_iter_cross_rhs: differences before squares, features ascending, no contraction; the sum m ascending,
+// unfused; L[p][0 .. k) and x_p staged in LDS), L[i][k] = c / sqrt(dres_p), dres_i = dres_i - L[i][k]^2; rows that are pivots
+// get 0, the pivot row sqrt(dres_p); and the workgroup writes its share of the next argmax
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(PCH_ROWS) void k_pchol_step(const double* __restrict__ X, int n, int d,
+                                                         const HyperScalars* __restrict__ hd, double* __restrict__ L, int rp,
+                                                         double* __restrict__ dres, int* __restrict__ piv, int* __restrict__ ctl,
+                                                         const double* __restrict__ shv_in, const int* __restrict__ shi_in,
+                                                         double* __restrict__ shv_out, int* __restrict__ shi_out, int nwg, int k,
+                                                         int kmax)
+{
+#pragma clang fp contract(off)
+    __shared__ double rv[PCH_ROWS];
+    __shared__ int ri[PCH_ROWS], rb[PCH_ROWS];
+    __shared__ double lp[PCH_MAX_RANK];
+    __shared__ double xs[PCH_ROWS];
+    __shared__ int ended;
+    const int tid = threadIdx.x;
+    if (tid == 0) ended = ctl[0];
+    __syncthreads();
+    if (ended >= 0) return;
+    const double ninf = -__builtin_inf();
+    // the pivot: step 0 has no shares, every residual is k(x, x) and row 0 is the lowest
+    double bv = ninf;
+    int bi = PCH_NO_ROW, bad = 0;
+    if (k == 0) {
+        if (tid == 0) { bv = dres[0]; bi = 0; bad = bv != bv; }
+    } else {
+        for (int b = tid; b < nwg; b += PCH_ROWS) {
+            const double v = shv_in[b];
+            if (v != v) bad = 1;
+            else if (v > bv) { bv = v; bi = shi_in[b]; }
+        }
+    }
+    rv[tid] = bad ? ninf : bv; ri[tid] = bi; rb[tid] = bad;
+    pchol_argmax(rv, ri, rb, tid);
+    const double dp = rv[0];
+    const int p = ri[0], nan_seen = rb[0];
+    __syncthreads();                                   // (rv, ri, rb are written again below)
+    const HyperScalars h = *hd;
+    const bool stop = nan_seen || !(dp > PCH_FLOOR * (double)(k + 1) * 1.1102230246251565e-16 * h.signal_var);
+    if (stop || k == kmax) {
+        if (blockIdx.x == 0 && tid == 0) { ctl[0] = k; if (nan_seen) ctl[1] = 1; }
+        return;
+    }
+    if (blockIdx.x == 0 && tid == 0) piv[k] = p;
+    const double* __restrict__ wts = ard_weights(hd);
+    ShapeArgs sh = ShapeArgs{0.0, 0.0};
+    if constexpr (KIND == KERNEL_RQ) sh = shape_args<KIND>(wts, d);
+    for (int m = tid; m < k; m += PCH_ROWS) lp[m] = L[(size_t)p * rp + m];
+    const size_t i = (size_t)blockIdx.x * PCH_ROWS + tid;
+    const bool live = i < (size_t)n;
+    double acc = 0.0;
+    for (int c0 = 0; c0 < d; c0 += PCH_ROWS) {
+        __syncthreads();
+        if (c0 + tid < d) xs[tid] = X[(size_t)p * d + c0 + tid];
+        __syncthreads();
+        const int cnt = d - c0 < PCH_ROWS ? d - c0 : PCH_ROWS;
+        if (live)
+            for (int f = 0; f < cnt; f++) {
+                double df = X[i * d + c0 + f] - xs[f];
+                if (ARD) df = df * wts[c0 + f];
+                acc = acc + df * df;
+            }
+    }
+    double mine = ninf;
+    bad = 0;
+    if (live) {
+        const double kv = kernel_value<ARD, KIND>(acc, div_prepare(h.ell_sq), h.signal_var, sh);
+        const double di = dres[i], root = __builtin_sqrt(dp);
+        const double* __restrict__ li = L + i * rp;
+        double s = 0.0;
+        int m = 0;
+        for (; m + 4 <= k; m += 4) {                   // (rp is a multiple of 64: a row starts on a 512-byte boundary)
+            const double l0 = li[m], l1 = li[m + 1], l2 = li[m + 2], l3 = li[m + 3];
+            s = s + l0 * lp[m];
+            s = s + l1 * lp[m + 1];
+            s = s + l2 * lp[m + 2];
+            s = s + l3 * lp[m + 3];
+        }
+        for (; m < k; m++) s = s + li[m] * lp[m];
+        double l = (kv - s) / root;
+        if (i == (size_t)p) { l = root; mine = ninf; }
+        else if (di == ninf) l = 0.0;
+        else mine = di - l * l;
+        L[i * rp + k] = l;
+        dres[i] = mine;
+        bad = mine != mine;
+    }
+    rv[tid] = bad ? ninf : mine; ri[tid] = live ? (int)i : PCH_NO_ROW; rb[tid] = bad;
+    pchol_argmax(rv, ri, rb, tid);
+    if (tid == 0) {
+        shv_out[blockIdx.x] = rb[0] ? __builtin_nan("") : rv[0];
+        shi_out[blockIdx.x] = ri[0];
+    }
+}

@@ -263,3 +263,223 @@ void launch_iter_poison(double* x, int n, int tp, const double* sc, hipStream_t 
 {
     hipLaunchKernelGGL(k_iter_poison, dim3(iter_blocks(n)), dim3(256), 0, s, x, n, tp, sc);
 }
+
+// ---- the preconditioner's products: M^-1 R = (R - Q (Q'R)) / sn2, Q [n][rp], rp a multiple of 64 ----
+//
+// k_pc_project<NCT>:  part[b] [rp][TP] = sum over the block's rows i of A[i][m] R[i][c], TP = 16 NCT.  The contraction runs
+//   over the rows, so both MFMA operands are read as they lie in memory: A[row m = fr][k = fk] = A[i0 + fk][m0 + fr] and
+//   B[k = fk][col fr] = R[i0 + fk][16 ct + fr] are 16 consecutive doubles per k -- 128-byte segments, no LDS.  The rp / 16 row
+//   tiles of T are dealt to the four waves in turn (tile 4 q + wave, q < rp / 64 <= MQ); a wave holds MQ x NCT accumulators
+//   (MQ = 1, 2, 4, 8: the smallest that holds rp; 128 registers at rp = 512, TP = 64, where one workgroup fits a CU) and
+//   reads its R operands once per four rows for all its tiles.  Rows beyond
+//   the block enter as zeros.  No two workgroups share an output: no atomics; k_pc_project_finish adds the blocks in
+//   ascending order (first copied, then a = a + b).  With R = a 64-column group of A itself it is the Gram product L'L.
+template <int NCT, int MQ>
+__global__ __launch_bounds__(256) void k_pc_project(const double* __restrict__ A, int rp, const double* __restrict__ R, int ldr,
+                                                    int n, int per, double* __restrict__ part)
+{
+    constexpr int TP = NCT * 16;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const int nq = rp / 64;
+    const size_t r0 = (size_t)blockIdx.x * per, r1 = r0 + per < (size_t)n ? r0 + per : (size_t)n;
+    d4 acc[MQ][NCT];
+#pragma unroll
+    for (int q = 0; q < MQ; q++)
+#pragma unroll
+        for (int ct = 0; ct < NCT; ct++) acc[q][ct] = (d4){0.0, 0.0, 0.0, 0.0};
+    for (size_t i0 = r0; i0 < r1; i0 += 4) {
+        const size_t i = i0 + fk;
+        const bool in = i < r1;
+        double b[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ct++) b[ct] = in ? R[i * ldr + ct * 16 + fr] : 0.0;
+        const double* __restrict__ ai = A + i * rp + wave * 16 + fr;
+#pragma unroll
+        for (int q = 0; q < MQ; q++)
+            if (q < nq) {
+                const double a = in ? ai[q * 64] : 0.0;
+#pragma unroll
+                for (int ct = 0; ct < NCT; ct++) acc[q][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b[ct], acc[q][ct], 0, 0, 0);
+            }
+    }
+    double* __restrict__ o = part + (size_t)blockIdx.x * rp * TP;
+#pragma unroll
+    for (int q = 0; q < MQ; q++)
+        if (q < nq)
+#pragma unroll
+            for (int ct = 0; ct < NCT; ct++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) o[(size_t)(q * 64 + wave * 16 + fk + 4 * r) * TP + ct * 16 + fr] = acc[q][ct][r];
+}
+
+// out[e] = part[0][e] + part[1][e] + ... in block order, e < cnt = rp * tp
+__global__ __launch_bounds__(256) void k_pc_project_finish(const double* __restrict__ part, int blocks, size_t cnt,
+                                                           double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cnt) return;
+    double s = part[e];
+    for (int k = 1; k < blocks; k++) s = s + part[(size_t)k * cnt + e];
+    out[e] = s;
+}
+
+// the Gram product's finish: C[i][c0 + c] = the blocks' sum, + sn2 on the diagonal; i < rp, c < 64
+__global__ __launch_bounds__(256) void k_pc_gram_finish(const double* __restrict__ part, int blocks, int rp,
+                                                        const HyperScalars* __restrict__ hd, double* __restrict__ C, int ldc, int c0)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x, cnt = (size_t)rp * 64;
+    if (e >= cnt) return;
+    const int i = (int)(e / 64), c = c0 + (int)(e % 64);
+    double s = part[e];
+    for (int k = 1; k < blocks; k++) s = s + part[(size_t)k * cnt + e];
+    if (i == c) s = s + hd->noise_var;
+    C[(size_t)i * ldc + c] = s;
+}
+
+// C = I over ld x ld: the padding of the r x r side's matrix
+__global__ __launch_bounds__(256) void k_pc_eye(double* __restrict__ C, int ld)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < (size_t)ld * ld) C[e] = e / ld == e % ld ? 1.0 : 0.0;
+}
+
+// k_pc_correct<NCT, FORM>:  out = (R - Q T) / sn2, or (FORM) out = Q T.  A workgroup owns 64 rows, a wave 16 of them and all
+//   NCT column tiles.  Stage = PC_KC = 16 values of k: the 64 x 16 piece of Q (a thread reads one d4 of a row: the global reads
+//   are row-contiguous) and the 16 x TP piece of T go through two LDS images each; the next stage's pieces are in flight in
+//   registers behind the MFMAs and go into the other image: one barrier per stage.  qs rows are 18 doubles apart (144 B:
+//   the 32 lanes of a ds_read_b64 fall on 32 different 8-byte bank pairs), ts rows TP + 16 at TP = 64 as k_cov_apply's vs.
+//   A[row fr][k fk] = qs[16 wave + fr][4 kk + fk], B[k fk][col fr] = ts[4 kk + fk][16 ct + fr]; k runs ascending, 4 per MFMA;
+//   the subtraction and the division (IEEE, one rounding each) happen once, in the epilogue.  FORM: T is the upper
+//   triangular Lc^-T of the r x r side read at column c0 with its own row stride, entries below the diagonal taken as
+//   zeros whatever the buffer holds there; out is the 64-column group at c0 of Q = L Lc^-T.
+template <int NCT, bool FORM>
+__global__ __launch_bounds__(256) void k_pc_correct(const double* __restrict__ Q, int rp, const double* __restrict__ T, int ldt,
+                                                    int c0, const double* __restrict__ R, const HyperScalars* __restrict__ hd,
+                                                    int n, double* __restrict__ out, int ldo)
+{
+#pragma clang fp contract(off)
+    constexpr int TP = NCT * 16, TPL = (TP % 32 == 0) ? TP + 16 : TP, QL = PC_KC + 2, TV = PC_KC * TP / 4;
+    __shared__ __attribute__((aligned(32))) double qs[2][64][QL];
+    __shared__ __attribute__((aligned(32))) double ts[2][PC_KC][TPL];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const size_t i0 = (size_t)blockIdx.x * 64;
+    const int nst = rp / PC_KC;
+    const int qr = tid >> 2, qc = (tid & 3) * 4, tr = tid / (TP / 4), tc = (tid % (TP / 4)) * 4;
+    d4 rq, rt;
+    auto fetch = [&](int st) {
+        rq = i0 + qr < (size_t)n ? *(const d4*)(Q + (i0 + qr) * rp + st * PC_KC + qc) : (d4){0.0, 0.0, 0.0, 0.0};
+        if (tid < TV) {
+            const int m = st * PC_KC + tr;
+            rt = *(const d4*)(T + (size_t)m * ldt + c0 + tc);
+            if constexpr (FORM) {
+#pragma unroll
+                for (int x = 0; x < 4; x++)
+                    if (m > c0 + tc + x) rt[x] = 0.0;
+            }
+        }
+    };
+    auto put = [&](int buf) {
+        qs[buf][qr][qc] = rq[0]; qs[buf][qr][qc + 1] = rq[1]; qs[buf][qr][qc + 2] = rq[2]; qs[buf][qr][qc + 3] = rq[3];
+        if (tid < TV) *(d4*)&ts[buf][tr][tc] = rt;
+    };
+    d4 acc[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++) acc[ct] = (d4){0.0, 0.0, 0.0, 0.0};
+    fetch(0);
+    put(0);
+    __syncthreads();
+    for (int st = 0; st < nst; st++) {
+        const int cur = st & 1;
+        const bool more = st + 1 < nst;
+        if (more) fetch(st + 1);
+#pragma unroll
+        for (int kk = 0; kk < PC_KC / 4; kk++) {
+            const double a = qs[cur][wave * 16 + fr][kk * 4 + fk];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ct++)
+                acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, ts[cur][kk * 4 + fk][ct * 16 + fr], acc[ct], 0, 0, 0);
+        }
+        if (more) put(cur ^ 1);
+        __syncthreads();
+    }
+    double sn2 = 1.0;
+    if constexpr (!FORM) sn2 = hd->noise_var;
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const size_t i = i0 + wave * 16 + fk + 4 * r;
+            if (i < (size_t)n) {
+                const int c = ct * 16 + fr;
+                if constexpr (FORM) out[i * ldo + c0 + c] = acc[ct][r];
+                else out[i * ldo + c] = (R[i * TP + c] - acc[ct][r]) / sn2;
+            }
+        }
+}
+
+PcPlan pc_plan(int n, int rank)
+{
+    PcPlan p;
+    p.rp = (rank + PC_RANK_PAD - 1) / PC_RANK_PAD * PC_RANK_PAD;
+    const size_t want = std::min<size_t>(ITER_SLOTS, ((size_t)n + PC_MIN_ROWS - 1) / PC_MIN_ROWS);
+    const size_t per = (((size_t)n + want - 1) / want + 15) / 16 * 16;
+    p.per = (int)per;
+    p.blocks = (int)(((size_t)n + per - 1) / per);      // no empty block
+    return p;
+}
+
+void launch_pchol_init(const CovFn& cf, int d, int n, int rp, double* L, double* dres, int* piv, int* ctl, hipStream_t s)
+{
+    assert(cf.hd);
+    const size_t cnt = (size_t)n * rp;
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_pchol_init), dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, cf.hd, d, n, rp, L,
+                       dres, piv, ctl);
+}
+void launch_pchol_step(const double* X, int n, int d, const CovFn& cf, double* L, int rp, double* dres, int* piv, int* ctl,
+                       double* shv, int* shi, int k, int kmax, hipStream_t s)
+{
+    assert(cf.hd && kmax <= PCH_MAX_RANK && kmax <= rp);
+    const int nwg = pchol_blocks(n), in = ((k + 1) & 1) * nwg, out = (k & 1) * nwg;
+    hipLaunchKernelGGL(CUGP_COV_KERNEL(cf, k_pchol_step), dim3(nwg), dim3(PCH_ROWS), 0, s, X, n, d, cf.hd, L, rp, dres, piv, ctl,
+                       shv + in, shi + in, shv + out, shi + out, nwg, k, kmax);
+}
+void launch_pc_project(const double* A, const double* R, int ldr, int tp, int n, const PcPlan& pl, double* part, hipStream_t s)
+{
+    assert((tp == 16 || tp == IT_MAXT) && pl.rp % 64 == 0 && pl.rp <= PCH_MAX_RANK);
+    const int nq = pl.rp / 64, w = tp == 16 ? 0 : 1;
+    auto kern = nq <= 1 ? (w ? k_pc_project<4, 1> : k_pc_project<1, 1>) : nq <= 2 ? (w ? k_pc_project<4, 2> : k_pc_project<1, 2>)
+                : nq <= 4 ? (w ? k_pc_project<4, 4> : k_pc_project<1, 4>) : (w ? k_pc_project<4, 8> : k_pc_project<1, 8>);
+    hipLaunchKernelGGL(kern, dim3(pl.blocks), dim3(256), 0, s, A, pl.rp, R, ldr, n, pl.per, part);
+}
+void launch_pc_project_finish(const double* part, int blocks, size_t cnt, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pc_project_finish, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, part, blocks, cnt, out);
+}
+void launch_pc_gram_finish(const double* part, int blocks, int rp, const HyperScalars* hd, double* C, int ldc, int c0, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pc_gram_finish, dim3((unsigned)(((size_t)rp * 64 + 255) / 256)), dim3(256), 0, s, part, blocks, rp, hd, C,
+                       ldc, c0);
+}
+void launch_pc_eye(double* C, int ld, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pc_eye, dim3((unsigned)(((size_t)ld * ld + 255) / 256)), dim3(256), 0, s, C, ld);
+}
+void launch_pc_correct(const double* Q, int rp, const double* T, int ldt, int c0, const double* R, const HyperScalars* hd, int n,
+                       int tp, double* out, int ldo, hipStream_t s)
+{
+    assert((tp == 16 || tp == IT_MAXT) && rp % 64 == 0 && (R || tp == IT_MAXT));
+    const dim3 grid((unsigned)(((size_t)n + 63) / 64));
+    if (!R) hipLaunchKernelGGL((k_pc_correct<4, true>), grid, dim3(256), 0, s, Q, rp, T, ldt, c0, R, hd, n, out, ldo);
+    else if (tp == 16) hipLaunchKernelGGL((k_pc_correct<1, false>), grid, dim3(256), 0, s, Q, rp, T, ldt, c0, R, hd, n, out, ldo);
+    else hipLaunchKernelGGL((k_pc_correct<4, false>), grid, dim3(256), 0, s, Q, rp, T, ldt, c0, R, hd, n, out, ldo);
+}
+void launch_iter_step_a_pc(const double* part, int n, int tp, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_a_pc, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, sc);
+}
+void launch_iter_step_z(const double* part, int n, int tp, int first, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_z, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, first, sc);
+}

@@ -458,6 +458,37 @@ void launch_iter_resid(const double* b, const double* q, double* r, int n, int t
                        hipStream_t s);
 void launch_iter_step_v(const double* part, int n, int tp, int final, double* sc, hipStream_t s);
 void launch_iter_poison(double* x, int n, int tp, const double* sc, hipStream_t s);
+// ---- the pivoted-Cholesky preconditioner of the recurrences: M = L L' + sn2 I, M^-1 = (I - Q Q') / sn2
+constexpr int SC_RZ = SC_ROWS + 1;   // r'z of the preconditioned recurrence: a row behind the host's (SC_ROWS: the variance's sums)
+constexpr int SC_ALLOC = SC_ROWS + 2;
+constexpr int PCH_ROWS = 256;        // rows (= threads) of a workgroup of k_pchol_step
+constexpr int PCH_MAX_RANK = 512;    // cugp.h CUGP_ITER_MAX_RANK
+constexpr int PCH_NO_ROW = 2147483647;
+constexpr double PCH_FLOOR = 5.0;    // the factor ends at a residual <= PCH_FLOOR (k + 1) u sf2
+constexpr int PC_RANK_PAD = 64;      // rp = rank rounded up: four waves of 16 rows of T, 64-column groups of L and Q
+constexpr int PC_MIN_ROWS = 64;      // rows of a workgroup of k_pc_project at least
+constexpr int PC_KC = 16;            // k per LDS stage of k_pc_correct
+inline int pchol_blocks(int n) { return (int)(((size_t)n + PCH_ROWS - 1) / PCH_ROWS); }
+// T = Q'R over n rows: workgroup b sums the rows [b per, min((b + 1) per, n)) in ascending order, 4 per MFMA, and the
+// partial blocks are added in ascending b.  Neither t nor tp enters (what cugp_iter_precond_plan reports; pure arithmetic)
+struct PcPlan { int rp, per, blocks; };
+PcPlan pc_plan(int n, int rank);
+void launch_pchol_init(const CovFn& cf, int d, int n, int rp, double* L, double* dres, int* piv, int* ctl, hipStream_t s);
+// step k of kmax (k == kmax: the closing launch); shv / shi: two sets of pchol_blocks(n) argmax shares, used in turn
+void launch_pchol_step(const double* X, int n, int d, const CovFn& cf, double* L, int rp, double* dres, int* piv, int* ctl,
+                       double* shv, int* shi, int k, int kmax, hipStream_t s);
+// part[b][rp][tp] = the block's share of A'R, A [n][rp], R [n][.] with row stride ldr; tp = 16 | 64 columns
+void launch_pc_project(const double* A, const double* R, int ldr, int tp, int n, const PcPlan& pl, double* part, hipStream_t s);
+void launch_pc_project_finish(const double* part, int blocks, size_t cnt, double* out, hipStream_t s);
+// C[i][c0 + c] = the blocks' sum (+ sn2 on the diagonal), i < rp, c < 64; launch_pc_eye: C = I over ld x ld
+void launch_pc_gram_finish(const double* part, int blocks, int rp, const HyperScalars* hd, double* C, int ldc, int c0, hipStream_t s);
+void launch_pc_eye(double* C, int ld, hipStream_t s);
+// out = (R - Q T) / sn2 (R given), or out = Q T with T's entries below the diagonal read as zeros (R NULL: Q = L Lc^-T, a
+// 64-column group at c0 of an upper-triangular T); T row stride ldt, out row stride ldo
+void launch_pc_correct(const double* Q, int rp, const double* T, int ldt, int c0, const double* R, const HyperScalars* hd, int n,
+                       int tp, double* out, int ldo, hipStream_t s);
+void launch_iter_step_a_pc(const double* part, int n, int tp, double* sc, hipStream_t s);
+void launch_iter_step_z(const double* part, int n, int tp, int first, double* sc, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -817,6 +817,41 @@ class IterativeGP:
                                            int(check_every), ptr(info) if var else None))
         return mean, v, info
 
+    def set_precond(self, rank):
+        """Ask for a pivoted-Cholesky preconditioner of that rank for solve / fit / predict (0: none, the default).  Built by
+        the next call that needs it, and again after set_data, set_loghyper or another set_precond."""
+        check(capi.lib().cugp_iter_set_precond(self._h, int(rank)))
+
+    def precond_info(self):
+        """{rank, achieved, rp, built} (cugp_iter_precond_info); builds a stale factor first."""
+        out = (C.c_int * 4)()
+        check(capi.lib().cugp_iter_precond_info(self._h, out))
+        return dict(zip(("rank", "achieved", "rp", "built"), out))
+
+    def precond_factor(self):
+        """(L [n, achieved], piv [achieved]) of L L' ~ Kf, the pivots in the order taken (cugp_iter_get_precond)."""
+        r = self.precond_info()["achieved"]
+        L, piv = np.zeros((self.n, r)), np.zeros(max(r, 1), dtype=np.int32)
+        check(capi.lib().cugp_iter_get_precond(self._h, ptr(L) if r else ptr(np.zeros(1)),
+                                               piv.ctypes.data_as(C.POINTER(C.c_int))))
+        return L, piv[:r]
+
+    def precond_apply(self, V):
+        """M^-1 V = (L L' + sn2 I)^-1 V for V [t, n] (cugp_iter_precond_apply)."""
+        V = self._block(V)
+        out = np.empty_like(V)
+        check(capi.lib().cugp_iter_precond_apply(self._h, ptr(V), V.shape[0], ptr(out)))
+        return out
+
+    @staticmethod
+    def precond_plan(n, rank):
+        """{rp, per, blocks, steps} of the projection Q'R over n rows (cugp_iter_precond_plan; no device)."""
+        out = (C.c_int * 4)()
+        rc = capi.lib().cugp_iter_precond_plan(int(n), int(rank), out)
+        if rc < 0:
+            check(rc)
+        return dict(zip(("rp", "per", "blocks", "steps"), out))
+
     @staticmethod
     def plan(na, nb, t=1, split=0):
         """{split, per, stages, row_blocks} of a product of na x nb entries (cugp_iter_apply_plan_split; no device)."""

@@ -886,7 +886,7 @@ int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap,
  * theta and a handful of n x 64 vectors: K = Kf + sn2 I of ALL n rows is applied to blocks of vectors with its entries
  * computed in registers (k_cov_apply, fp64 MFMA), and K^-1 b comes from conjugate gradients on that product -- the exact
  * predictive mean and variance at O(n t) memory, for hyper-parameters trained elsewhere (a subset, a BCM, the sparse
- * model).  No log marginal likelihood, no gradient, no preconditioner: the iteration count grows with cond(K).
+ * model).  No log marginal likelihood, no gradient.  Without a preconditioner (below) the sweep count grows with cond(K).
  *
  * Model: kernel in {CUGP_KERNEL_SE, _MATERN32, _MATERN52, CUGP_KERNEL_RQ}, ard in {0, 1}; theta as the dense handles'
  * ([log l | log l_1 .. log l_d, (RQ: log alpha,) log sigma_f, log sigma_n], nh = (ard ? d : 1) + (RQ ? 1 : 0) + 2).
@@ -912,13 +912,30 @@ int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap,
  *      ascending order, the ranges are added in ascending s.  S = 1 where the row blocks alone fill the device.  Returns S.
  *      _split: with S asked for (0: the rule); cugp_iter_set_split asks it of a handle's products (test and tuning hook).
  *
+ * Preconditioner (off by default).  cugp_iter_set_precond(h, rank) asks for M = L L' + sn2 I with L a
+ *      pivoted Cholesky factor of Kf of that rank (0: none -- every call then launches what it launched before and returns
+ *      the same bits).  The call only records the request; the factor is built by the next call that needs it and again
+ *      after cugp_iter_set_data, cugp_iter_set_loghyper or another cugp_iter_set_precond.  The factor ends early where the
+ *      largest residual diagonal entry is not above 5 (k + 1) 2^-53 sf2 (the achieved rank is then k, possibly 0: no
+ *      preconditioner), and a NaN residual gives rank 0; neither is an error.  cugp_iter_solve, _fit and _predict's
+ *      variance then run preconditioned conjugate gradients; what info certifies does not change (convergence is claimed
+ *      on the true residual only), r'z <= 0 counts as a breakdown beside p'Kp <= 0.
+ * cugp_iter_precond_info : out = {rank asked for, rank achieved, padded rank rp (a multiple of 64), built (1)}; builds a stale
+ *      factor first.
+ * cugp_iter_get_precond : L [n][achieved] row-major and the pivots piv [achieved] in the order they were taken.
+ * cugp_iter_precond_apply: out [t][n] = M^-1 V = (V - Q Q'V) / sn2, any t, 64 columns a launch; refused at rank 0.
+ * cugp_iter_precond_plan : the projection's split (pure arithmetic, no device): out = {rp, rows per workgroup, workgroups,
+ *      MFMA steps per workgroup}; workgroup b sums the rows [b out[1], min((b + 1) out[1], n)) ascending, the workgroups'
+ *      blocks are added in ascending b; t does not enter.  Returns the workgroup count.
+ *
  * Refusals, all CUGP_ERR_INVALID before any device call with the call's name in cugp_last_error: a NULL argument (other
- * than info and var); n, d, t, nt < 1; n or nt beyond CUGP_ITER_MAX_N; an unknown kernel; ard outside {0, 1}; a negative
+ * than info and var); a rank outside [0, min(n, CUGP_ITER_MAX_RANK)] (the handle stays as it was); n, d, t, nt < 1; n or nt beyond CUGP_ITER_MAX_N; an unknown kernel; ard outside {0, 1}; a negative
  * device; a split outside [0, CUGP_ITER_MAX_SPLIT]; nh that is not the handle's; tol not positive and finite; max_iter or check_every < 1; a product or
  * solve before both cugp_iter_set_data and cugp_iter_set_loghyper; cugp_iter_predict or cugp_iter_get_alpha without a
  * cugp_iter_fit since the data or theta last changed.  CUGP_ERR_NODEVICE from cugp_iter_create without a GPU. */
 #define CUGP_ITER_MAX_N 2147482623   /* INT_MAX - 1024: row indices are ints, offsets size_t */
 #define CUGP_ITER_MAX_SPLIT 65535    /* the ranges of a product are the second dimension of its launch grid */
+#define CUGP_ITER_MAX_RANK 512       /* columns of the preconditioner's factor at most */
 typedef struct cugp_iter cugp_iter;
 int cugp_iter_create(int n, int d, int device, int kernel, int ard, cugp_iter **out);
 int cugp_iter_destroy(cugp_iter *h);
@@ -936,6 +953,11 @@ int cugp_iter_predict(cugp_iter *h, const double *Xt, int nt, double *mean, doub
                       int max_iter, int check_every, double *info /* may be NULL */);
 int cugp_iter_apply_plan(int na, int nb, int t, int out[4]);
 int cugp_iter_apply_plan_split(int na, int nb, int t, int split, int out[4]);
+int cugp_iter_set_precond(cugp_iter *h, int rank);
+int cugp_iter_precond_info(cugp_iter *h, int out[4]);
+int cugp_iter_get_precond(cugp_iter *h, double *L, int *piv);
+int cugp_iter_precond_apply(cugp_iter *h, const double *V, int t, double *out);
+int cugp_iter_precond_plan(int n, int rank, int out[4]);
 
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);

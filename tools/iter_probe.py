@@ -6,6 +6,14 @@ fit's alpha with Covsum.get_alpha() are SINGLE calls without a warm-up: their ti
 exact_seconds_first_call the exact handle's first evaluation.  Read them as orders of magnitude, with the sweep counts.
 
     python tools/iter_probe.py [--n 100000] [--reps 3] [--big 0] [--out profiles/iter_probe.json]
+
+--precond r [r ...]: instead of the above, the pivoted-Cholesky preconditioner at each rank r (0: none)
+-> profiles/iter_precond_probe.json.  Per family and rank: the build (set_precond + precond_info: factor, Gram product, the
+r x r factorisation and Q, with their two host waits; the first call with its allocations, then the median of --reps
+rebuilds), one M^-1 V at t = 16 and one K V beside it (medians, host packing included), fit at tol 1e-8 and the variance at
+--ntvar points (single calls: sweeps and wall time).  --dims sets D (the length scales stay those of D = 10).
+
+    python tools/iter_probe.py --precond 0 64 256 [--dims 10] [--n 100000]
 """
 import argparse
 import json
@@ -35,8 +43,50 @@ def timed(fn, reps):
     return float(np.median(ts)), out
 
 
+def precond_probe(a):
+    d = a.dims
+    theta = {"se": THETA["se"], "rq_ard": np.linspace(1.3, 1.7, d).tolist() + [0.4, 0.0, -1.0]}
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": d, "ntvar": a.ntvar, "reps": a.reps, "tol": 1e-8,
+           "families": {}}
+    X, y = synth(a.n, d=d)
+    Xt = synth(a.ntvar, d=d, seed=7)[0]
+    V = np.random.default_rng(0).standard_normal((16, a.n))
+    for fam, th in theta.items():
+        g = gp.IterativeGP(a.n, d, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        res["families"][fam] = {}
+        for rank in a.precond:
+            def build():
+                g.set_precond(rank)
+                return g.precond_info()
+            t0 = time.perf_counter()
+            info = build()
+            r = {"info": info, "plan": g.precond_plan(a.n, rank), "build_seconds_first_call": time.perf_counter() - t0}
+            r["apply_K_t16_seconds"] = timed(lambda: g.apply(V), a.reps)[0]
+            if info["achieved"]:
+                r["build_seconds"] = timed(build, a.reps)[0]
+                r["apply_Minv_t16_seconds"] = timed(lambda: g.precond_apply(V), a.reps)[0]
+            t0 = time.perf_counter()
+            fi = g.fit(1e-8, 2000, 10)
+            r["fit"] = {"seconds": time.perf_counter() - t0, "sweeps": fi[0], "rel_residual": fi[1], "converged": fi[2]}
+            t0 = time.perf_counter()
+            pi = g.predict(Xt, True, 1e-8, 2000, 10)[2]
+            r["predict_var"] = {"seconds": time.perf_counter() - t0, "sweeps_max": float(pi[:, 0].max()), "converged": float(pi[:, 2].min())}
+            print(fam, "rank", rank, r, flush=True)
+            res["families"][fam][str(rank)] = r
+        g.close()
+    res["not_measured"] = ["the build split into factor / Gram / Q (one wall time per build)",
+                           "device time of k_pc_project + finish + k_pc_correct without the host's packing and copies"]
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_precond_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--precond", type=int, nargs="+", default=None, help="ranks of the preconditioner probe (its own mode)")
+    ap.add_argument("--dims", type=int, default=D, help="input dimension of the preconditioner probe")
     ap.add_argument("--n", type=int, default=100000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--big", type=int, default=0, help="one apply (t = 16, SE) at this many rows, e.g. 1000000")
@@ -44,6 +94,8 @@ def main():
     ap.add_argument("--ntvar", type=int, default=64, help="... of which the first ntvar get a variance (64 share one solve)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "iter_probe.json"))
     a = ap.parse_args()
+    if a.precond is not None:
+        return precond_probe(a)
     res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "nt": a.nt, "ntvar": a.ntvar, "d": D, "reps": a.reps, "families": {}}
     X, y = synth(a.n, d=D)
     Xt = synth(a.nt, d=D, seed=7)[0]
