@@ -24,6 +24,8 @@ struct cugp_iter {
     bool have_data = false, have_theta = false, fit_valid = false;
     int split = 0;                 // ranges of the product's j split; 0: iter_apply_plan's rule
     Scratch vb, vx, vr, vp, vq, vk, alpha, apart, dpart, xt, res;
+    Scratch gpart, gout, ghost;    // the gradient forms: k_cov_grad's partial rows; their sums and the
+                                   // columns' u'v behind them; the pinned copy of those
     std::vector<double> host;      // packing: [t][n] target-major <-> [n][tp]
     // the preconditioner (cugp_iter_set_precond): M = L L' + sn2 I from a pivoted Cholesky factor of Kf
     int pc_rank = 0, pc_got = 0, pc_rp = 0;       // asked for, achieved, padded (pc_plan)
@@ -247,6 +249,73 @@ void fill_info(const cugp_iter* h, int c0, int cnt, double* info)
     }
 }
 
+// alpha = K^-1 y into h->alpha: what cugp_iter_fit runs behind its checks
+int fit_run(cugp_iter* h, double tol, int max_iter, int check_every, double* info, const char* call)
+{
+    int rc;
+    h->fit_valid = false;
+    if ((rc = h->alpha.grow((size_t)h->n * 16, h->stream))) return rc;
+    if ((rc = solve_dev(h, cov_of(h), h->dyb, 16, tol, max_iter, check_every, call))) return rc;
+    fill_info(h, 0, 1, info);
+    HIPCHK(hipMemcpyAsync(h->alpha.p, h->vx.p, (size_t)h->n * 16 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->fit_valid = true;
+    return CUGP_OK;
+}
+
+// The raw sums of one pair of device blocks U, V [n][tp] with cnt live columns: raw[c] for the cov_grad_columns of
+// k_cov_grad, raw[nc] = sum_c u_c'v_c (k_iter_dot / k_iter_sum per column, the columns added in ascending order on the
+// host).  first: copied, else raw = raw + the block's.  One wait.
+int forms_dev(cugp_iter* h, const CovFn& cf, const double* U, const double* V, int cnt, int tp, bool first,
+              std::vector<double>& raw, const char* call)
+{
+    const int n = h->n, nc = cov_grad_columns(cf, h->d);
+    const IterPlan pl = iter_apply_plan(n, n, h->split);
+    hipStream_t s = h->stream;
+    int rc;
+    if ((rc = h->gpart.grow((size_t)pl.row_blocks * pl.split * nc, s)) || (rc = h->gout.grow((size_t)nc + IT_MAXT, s)) ||
+        (rc = h->ghost.grow((size_t)nc + IT_MAXT, s)) || (rc = h->dpart.grow((size_t)iter_blocks(n) * IT_MAXT, s)))
+        return rc;
+    launch_cov_grad(h->dX, n, h->d, cf, U, V, tp, h->gpart.p, h->gout.p, pl, s);
+    launch_iter_dot(U, V, n, tp, h->dpart.p, s);
+    launch_iter_sum(h->dpart.p, n, tp, h->gout.p + nc, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->ghost.p, h->gout.p, (size_t)(nc + tp) * sizeof(double), hipMemcpyDeviceToHost, s);
+    if ((rc = sync_or_fail(s, call, e))) return rc;
+    const double* got = h->ghost.p;
+    double dot = got[nc];
+    for (int c = 1; c < cnt; c++) dot = dot + got[nc + c];
+    raw.resize(nc + 1);
+    for (int c = 0; c < nc; c++) raw[c] = first ? got[c] : raw[c] + got[c];
+    raw[nc] = first ? dot : raw[nc] + dot;
+    return CUGP_OK;
+}
+
+// out[nh] = sum W o dK/dtheta_h from the raw sums: the length scales (a tied handle: the d columns added in index order, as
+// k_finalize_ard_tied does), the shape columns, 2 sum W o Kf, 2 sn2 tr W
+void forms_out(const cugp_iter* h, const std::vector<double>& raw, double* out)
+{
+    const int nc = (int)raw.size() - 1, nl = h->route ? h->d : 1;
+    int o = 0;
+    if (h->route && !h->ard) {
+        double g0 = raw[0];
+        for (int c = 1; c < nl; c++) g0 = g0 + raw[c];
+        out[o++] = g0;
+    } else {
+        for (int c = 0; c < nl; c++) out[o++] = raw[c];
+    }
+    for (int c = nl; c < nc - 1; c++) out[o++] = raw[c];
+    out[o++] = 2.0 * raw[nc - 1];
+    out[o] = 2.0 * h->hhs->noise_var * raw[nc];
+}
+
+// the launch grid's third dimension is the feature chunk of k_cov_grad's per-dimension sums
+int grad_dims(const cugp_iter* h, const char* call)
+{
+    if (h->route && (h->d + 15) / 16 > 65535) return invalid_arg(call, "more than 65535 * 16 input dimensions on the ARD route");
+    return CUGP_OK;
+}
+
 int plan_out(const char* call, int na, int nb, int t, int split, int out[4])
 {
     if (!out) return invalid_arg(call, "out is NULL");
@@ -285,6 +354,7 @@ int cugp_iter_create(int n, int d, int device, int kernel, int ard, cugp_iter** 
     h->route = h->ard || kernel == KERNEL_RQ;
     h->nh = (h->ard ? d : 1) + shape_count(kernel) + 2;
     h->theta.assign(h->nh, 0.0);
+    h->ghost.pinned = true;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc((void**)&h->dX, (size_t)n * d * sizeof(double));
@@ -308,7 +378,7 @@ int cugp_iter_destroy(cugp_iter* h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res, &h->pL,
-                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz})
+                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost})
         v->release();
     if (h->pf) cugp_destroy(h->pf);
     for (void* p : {(void*)h->dX, (void*)h->dyb, (void*)h->dhs, (void*)h->dsc})
@@ -517,13 +587,62 @@ int cugp_iter_fit(cugp_iter* h, double tol, int max_iter, int check_every, doubl
     int rc;
     if ((rc = solver_args(call, tol, max_iter, check_every)) || (rc = ready(h, call))) return rc;
     HIPCHK(hipSetDevice(h->device));
-    h->fit_valid = false;
-    if ((rc = h->alpha.grow((size_t)h->n * 16, h->stream))) return rc;
-    if ((rc = solve_dev(h, cov_of(h), h->dyb, 16, tol, max_iter, check_every, call))) return rc;
-    fill_info(h, 0, 1, info);
-    HIPCHK(hipMemcpyAsync(h->alpha.p, h->vx.p, (size_t)h->n * 16 * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->fit_valid = true;
+    return fit_run(h, tol, max_iter, check_every, info, call);
+}
+
+int cugp_iter_grad_forms(cugp_iter* h, const double* U, const double* V, int t, double* out)
+{
+    const char* call = "cugp_iter_grad_forms";
+    if (!h || !U || !V || !out) return invalid_arg(call, "null argument");
+    if (t < 1) return invalid_arg(call, "t must be positive");
+    int rc;
+    if ((rc = ready(h, call)) || (rc = grad_dims(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    std::vector<double> raw;
+    for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
+        if ((rc = pack(h, U, h->n, c0, cnt, tp, h->vb)) || (rc = pack(h, V, h->n, c0, cnt, tp, h->vk))) return rc;
+        if ((rc = forms_dev(h, cf, h->vb.p, h->vk.p, cnt, tp, c0 == 0, raw, call))) return rc;
+    }
+    forms_out(h, raw, out);
+    return CUGP_OK;
+}
+
+int cugp_iter_loglik_grad(cugp_iter* h, const double* Z, int t, double tol, int max_iter, int check_every, double* g,
+                          double* quad, double* info)
+{
+    const char* call = "cugp_iter_loglik_grad";
+    if (!h || !Z || !g) return invalid_arg(call, "null argument");
+    if (t < 1) return invalid_arg(call, "t must be positive");
+    int rc;
+    if ((rc = solver_args(call, tol, max_iter, check_every)) || (rc = ready(h, call)) || (rc = grad_dims(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    if (!h->fit_valid && (rc = fit_run(h, tol, max_iter, check_every, nullptr, call))) return rc;
+    const CovFn cf = cov_of(h);
+    hipStream_t s = h->stream;
+    // the probes: u_p = K^-1 z_p, 64 a solve; both blocks stay on the device for their forms
+    std::vector<double> raw, rawa;
+    for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
+        if ((rc = pack(h, Z, h->n, c0, cnt, tp, h->vb))) return rc;
+        if ((rc = solve_dev(h, cf, h->vb.p, tp, tol, max_iter, check_every, call))) return rc;
+        fill_info(h, c0, cnt, info);
+        if ((rc = forms_dev(h, cf, h->vx.p, h->vb.p, cnt, tp, c0 == 0, raw, call))) return rc;
+    }
+    if ((rc = forms_dev(h, cf, h->alpha.p, h->alpha.p, 1, 16, true, rawa, call))) return rc;
+    std::vector<double> fp(h->nh), fa(h->nh);
+    forms_out(h, raw, fp.data());
+    forms_out(h, rawa, fa.data());
+    for (int k = 0; k < h->nh; k++) g[k] = 0.5 * (fp[k] / (double)t - fa[k]);
+    if (quad) {
+        launch_iter_dot(h->dyb, h->alpha.p, h->n, 16, h->dpart.p, s);
+        launch_iter_sum(h->dpart.p, h->n, 16, h->gout.p, s);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h->ghost.p, h->gout.p, sizeof(double), hipMemcpyDeviceToHost, s);
+        if ((rc = sync_or_fail(s, call, e))) return rc;
+        *quad = h->ghost.p[0];
+    }
     return CUGP_OK;
 }
 

@@ -207,6 +207,260 @@ void launch_cov_apply(const double* A, int na, const double* B, int nb, int d, c
     }
 }
 
+// ---- the bilinear forms of dKf / dtheta (cugp_iter_grad_forms, cugp_iter_loglik_grad) ----
+//
+// k_cov_grad<ARD, KIND>:  G_h = sum_ij W_ij dKf_ij / dtheta_h with W_ij = sum_c U[i][c] V[j][c], neither K nor W stored.
+//   k_cov_apply's decomposition with the MFMA's roles swapped: there the lane computes an entry and the MFMA multiplies it
+//   with V; here the MFMA forms the weights and the lane multiplies them with the entries' derivative factors.  The wave
+//   computes the TRANSPOSED weight tile D[j][i] = sum_c V[j][c] U[i][c]: A[row fr][k fk] = V[j0 + fr][4 kk + fk] out of the LDS
+//   image of the stage's V rows, B[k fk][col fr] = U[i0 + fr][4 kk + fk], fixed for the whole sweep and held in registers
+//   (TP / 4 doubles per lane); c ascending, 4 per MFMA.  In the C/D layout the lane then holds j = j0 + fk + 4 r and the one
+//   i = i0 + fr -- the 8 entries per stage (two 16-row j tiles; entry kk = 4 jt + r is b row 4 kk + fk) whose squared
+//   distances k_cov_apply's lane computes against the a row it keeps in registers: the same lines, the same bits.  Per entry:
+//   the family's factors once (cov_device.h: ard_entry, rq_entry, matern_entry; isotropic SE kernel_value and the quotient
+//   k_trace takes), times the weight.  ARD route: e = w H is kept for the 8 entries and a second loop over the features of
+//   the workgroup's chunk (blockIdx.z; read again from the stage's LDS image) adds e ((a_c - b_c) w_c)^2 into DC per-lane sums
+//   that live across the sweep; every z recomputes the whole distance (d > DC is served, not tuned), z = 0 alone writes the
+//   scalar columns.  The full square: W is not symmetric.
+//   LDS: ys, yc as k_cov_apply's, yz [32][16] (the z-th chunk of a stage with d > DC), vs [2][32][TP + 2] (rows 144 B | 528 B
+//   apart: the 32 lanes of a half-wave's ds_read_b64 -- fr x two fk -- fall on 32 different 8-byte bank pairs): 21 | 46 KiB.
+//   Sums: a lane adds its entries in ascending j (kk ascending, stages ascending), wave_sum, the four waves (0 + 1) + (2 + 3):
+//   one partial row part[(row block * split + s)][nc] per workgroup, nc = d + shape columns + 1 (sum W o Kf) on the ARD route,
+//   2 (sum W o dKf/dlog l, sum W o Kf) else; k_cov_grad_finish adds the rows in ascending order (first copied, then a = a + b).
+//   Rows beyond n enter as zeros with zero weight; padding columns of U and V add exact zeros.  No atomics.
+template <bool ARD, int KIND, int NCT>
+__device__ __forceinline__ void cov_grad_body(const double* __restrict__ X, int n, int d, const HyperScalars* __restrict__ hd,
+                                              const double* __restrict__ U, const double* __restrict__ V,
+                                              double* __restrict__ part, int per)
+{
+#pragma clang fp contract(off)
+    constexpr int TP = NCT * 16, TPL = TP + 2, NK = ITER_JT / 4, NS = shape_count(KIND);
+    static_assert(ITER_JT * DC == 2 * 256 && ITER_JT * TP == 2 * 256 * NCT, "one d2 of b and NCT d2 of V per thread and stage");
+    static_assert(ITER_JT == 32 && ITER_ROWS == 64, "two 16-row j tiles per stage, four waves of 16 i rows");
+    __shared__ __attribute__((aligned(16))) double ys[2][ITER_JT][DC];
+    __shared__ __attribute__((aligned(16))) double yc[ITER_JT][DC];
+    __shared__ __attribute__((aligned(16))) double yz[ARD ? ITER_JT : 1][DC];
+    __shared__ __attribute__((aligned(16))) double vs[2][ITER_JT][TPL];
+    __shared__ double red[DC + 2][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const int row = blockIdx.x * ITER_ROWS + wave * 16 + fr;
+    const HyperScalars h = *hd;
+    const double* __restrict__ wts = ard_weights(hd);
+    [[maybe_unused]] const DivBy dl = div_prepare(h.ell_sq);   // isotropic route only
+    const ShapeArgs sh = shape_args<KIND>(wts, d);
+    const int nst = (n + ITER_JT - 1) / ITER_JT, nch = (d + DC - 1) / DC;
+    const int s0 = blockIdx.y * per, s1 = s0 + per < nst ? s0 + per : nst;
+    const int cz = ARD ? blockIdx.z : 0;               // the feature chunk of this workgroup's per-dimension sums
+
+    double ub[TP / 4];                                 // the MFMA's B operand: U[row][4 kk + fk]
+#pragma unroll
+    for (int kk = 0; kk < TP / 4; kk++) ub[kk] = row < n ? U[(size_t)row * TP + kk * 4 + fk] : 0.0;
+    double ar[DC];
+    auto load_a = [&](int c0) {
+#pragma unroll
+        for (int c = 0; c < DC; c++) ar[c] = (row < n && c0 + c < d) ? X[(size_t)row * d + c0 + c] : 0.0;
+    };
+    // the thread's share of a stage: one feature pair of one b row, NCT column pairs of V rows
+    const int br = tid >> 3, bc = (tid & 7) * 2;
+    d2 rb, rv[NCT];
+    auto fetch_b = [&](int j0, int c0) {
+        const int j = j0 + br, c = c0 + bc;
+        rb[0] = (j < n && c < d) ? X[(size_t)j * d + c] : 0.0;
+        rb[1] = (j < n && c + 1 < d) ? X[(size_t)j * d + c + 1] : 0.0;
+    };
+    auto fetch = [&](int st) {
+        const int j0 = st * ITER_JT;
+        fetch_b(j0, 0);
+#pragma unroll
+        for (int q = 0; q < NCT; q++) {
+            const int e = tid + 256 * q, j = j0 + e / (TP / 2);
+            rv[q] = j < n ? *(const d2*)(V + (size_t)j * TP + 2 * (e % (TP / 2))) : (d2){0.0, 0.0};
+        }
+    };
+    auto put = [&](int buf) {
+        *(d2*)&ys[buf][br][bc] = rb;
+#pragma unroll
+        for (int q = 0; q < NCT; q++) {
+            const int e = tid + 256 * q;
+            *(d2*)&vs[buf][e / (TP / 2)][2 * (e % (TP / 2))] = rv[q];
+        }
+    };
+    double sq[NK];
+    // sq[kk] += the chunk's terms of |(a_row - b_{4 kk + fk}) w|^2, features ascending: k_cov_apply's lines
+    auto accumulate = [&](double (*yb)[DC], int c0) {
+#pragma unroll
+        for (int cp = 0; cp < DC / 2; cp++) {
+            const int c = 2 * cp;
+            if (c0 + c < d) {
+                const double w0 = ARD ? wts[c0 + c] : 1.0, w1 = (ARD && c0 + c + 1 < d) ? wts[c0 + c + 1] : 1.0;
+#pragma unroll
+                for (int kk = 0; kk < NK; kk++) {
+                    const d2 yv = *(const d2*)&yb[kk * 4 + fk][c];
+                    double df = ar[c] - yv[0];
+                    if (ARD) df = df * w0;
+                    sq[kk] = sq[kk] + df * df;
+                    df = ar[c + 1] - yv[1];
+                    if (ARD) df = df * w1;
+                    sq[kk] = sq[kk] + df * df;
+                }
+            }
+        }
+    };
+    double sk = 0.0;                                   // sum W o Kf
+    [[maybe_unused]] double sl = 0.0;                  // isotropic route only: sum W o dk
+    [[maybe_unused]] double sa = 0.0;                  // ARD route, RQ only: sum W o da
+    [[maybe_unused]] double gs[ARD ? DC : 1];          // ARD route only: sum W o H o u_c^2 for the DC dimensions of chunk cz
+#pragma unroll
+    for (int c = 0; c < (ARD ? DC : 1); c++) gs[c] = 0.0;
+
+    load_a(0);
+    fetch(s0);
+    put(0);
+    __syncthreads();
+    for (int st = s0; st < s1; st++) {
+        const int cur = (st - s0) & 1;
+        const bool more = st + 1 < s1;
+        if (more) fetch(st + 1);
+#pragma unroll
+        for (int kk = 0; kk < NK; kk++) sq[kk] = 0.0;
+        accumulate(ys[cur], 0);
+        for (int ch = 1; ch < nch; ch++) {
+            const d2 keep = rb;
+            fetch_b(st * ITER_JT, ch * DC);
+            __syncthreads();
+            *(d2*)&yc[br][bc] = rb;
+            if (ARD && ch == cz) *(d2*)&yz[br][bc] = rb;
+            rb = keep;
+            load_a(ch * DC);
+            __syncthreads();
+            accumulate(yc, ch * DC);
+        }
+        if (nch > 1) load_a(cz * DC);
+        d4 wt[2];                                      // W[i0 + fr][j0 + 16 jt + fk + 4 r]
+#pragma unroll
+        for (int jt = 0; jt < 2; jt++) {
+            wt[jt] = (d4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int kk = 0; kk < TP / 4; kk++)
+                wt[jt] = __builtin_amdgcn_mfma_f64_16x16x4f64(vs[cur][jt * 16 + fr][kk * 4 + fk], ub[kk], wt[jt], 0, 0, 0);
+        }
+        [[maybe_unused]] double e[ARD ? NK : 1];       // ARD route only: w H of the 8 entries, for the per-dimension sums
+#pragma unroll
+        for (int kk = 0; kk < NK; kk++) {
+            const double w = wt[kk >> 2][kk & 3];
+            if constexpr (ARD) {
+                double kf, hh, da;
+                ard_entry<KIND>(sq[kk], h.signal_var, sh, kf, hh, da);
+                sk = sk + w * kf;
+                if constexpr (NS > 0) sa = sa + w * da;
+                e[kk] = w * hh;
+            } else {
+                double kf, dk;
+                if constexpr (KIND == KERNEL_SE) {
+                    kf = kernel_value<false, KERNEL_SE>(sq[kk], dl, h.signal_var);
+                    dk = kf * div_by(sq[kk], dl);
+                } else {
+                    double hh;                         // matern_entry's third output: the ARD route's factor
+                    matern_entry<KIND>(div_by(sq[kk], dl), h.signal_var, kf, dk, hh);
+                }
+                sk = sk + w * kf;
+                sl = sl + w * dk;
+            }
+        }
+        if constexpr (ARD) {
+            double (*yb)[DC] = cz == 0 ? ys[cur] : yz;
+#pragma unroll
+            for (int cp = 0; cp < DC / 2; cp++) {
+                const int c = 2 * cp, f = cz * DC + c;
+                if (f < d) {
+                    const double w0 = wts[f], w1 = f + 1 < d ? wts[f + 1] : 1.0;
+#pragma unroll
+                    for (int kk = 0; kk < NK; kk++) {
+                        const d2 yv = *(const d2*)&yb[kk * 4 + fk][c];
+                        double df = (ar[c] - yv[0]) * w0;
+                        gs[c] = gs[c] + e[kk] * (df * df);
+                        df = (ar[c + 1] - yv[1]) * w1;
+                        gs[c + 1] = gs[c + 1] + e[kk] * (df * df);
+                    }
+                }
+            }
+            if (cz != 0) load_a(0);
+        }
+        if (more) put(cur ^ 1);
+        __syncthreads();
+    }
+    // the workgroup's partial row: lanes by wave_sum, the four waves in a fixed order
+    sk = wave_sum(sk);
+    if constexpr (ARD) {
+#pragma unroll
+        for (int c = 0; c < DC; c++) gs[c] = wave_sum(gs[c]);
+        if constexpr (NS > 0) sa = wave_sum(sa);
+    } else {
+        sl = wave_sum(sl);
+    }
+    if (lane == 0) {
+        if constexpr (ARD) {
+#pragma unroll
+            for (int c = 0; c < DC; c++) red[c][wave] = gs[c];
+            if constexpr (NS > 0) red[DC][wave] = sa;
+            red[DC + NS][wave] = sk;
+        } else {
+            red[0][wave] = sl;
+            red[1][wave] = sk;
+        }
+    }
+    __syncthreads();
+    const int nc = ARD ? d + NS + 1 : 2;
+    double* __restrict__ o = part + ((size_t)blockIdx.x * gridDim.y + blockIdx.y) * nc;
+    if (tid < (ARD ? DC + NS + 1 : 2)) {
+        const double s = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+        if constexpr (ARD) {
+            if (tid < DC) { if (cz * DC + tid < d) o[cz * DC + tid] = s; }
+            else if (cz == 0) o[d + tid - DC] = s;
+        } else {
+            o[tid] = s;
+        }
+    }
+}
+
+// one column tile of U and V (t <= 16) and four (t <= 64), as k_cov_apply's two
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_cov_grad(const double* __restrict__ X, int n, int d, const HyperScalars* __restrict__ hd,
+                                                  const double* __restrict__ U, const double* __restrict__ V,
+                                                  double* __restrict__ part, int per)
+{
+    cov_grad_body<ARD, KIND, 1>(X, n, d, hd, U, V, part, per);
+}
+template <bool ARD, int KIND>
+__global__ __launch_bounds__(256) void k_cov_grad4(const double* __restrict__ X, int n, int d, const HyperScalars* __restrict__ hd,
+                                                   const double* __restrict__ U, const double* __restrict__ V,
+                                                   double* __restrict__ part, int per)
+{
+    cov_grad_body<ARD, KIND, 4>(X, n, d, hd, U, V, part, per);
+}
+
+// out[c] = part[0][c] + part[1][c] + ... in row order, c < nc
+__global__ __launch_bounds__(256) void k_cov_grad_finish(const double* __restrict__ part, size_t rows, int nc, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= nc) return;
+    double s = part[c];
+    for (size_t k = 1; k < rows; k++) s = s + part[k * nc + c];
+    out[c] = s;
+}
+
+void launch_cov_grad(const double* X, int n, int d, const CovFn& cf, const double* U, const double* V, int tp, double* part,
+                     double* out, const IterPlan& pl, hipStream_t s)
+{
+    assert(cf.hd && (tp == 16 || tp == IT_MAXT));
+    auto kern = tp == 16 ? CUGP_COV_KERNEL(cf, k_cov_grad) : CUGP_COV_KERNEL(cf, k_cov_grad4);
+    const int nz = is_ard(cf) ? (d + DC - 1) / DC : 1, nc = cov_grad_columns(cf, d);
+    assert(nz <= 65535);
+    hipLaunchKernelGGL(kern, dim3(pl.row_blocks, pl.split, nz), dim3(256), 0, s, X, n, d, cf.hd, U, V, part, pl.per);
+    hipLaunchKernelGGL(k_cov_grad_finish, dim3((nc + 255) / 256), dim3(256), 0, s, part, (size_t)pl.row_blocks * pl.split, nc, out);
+}
+
 void launch_iter_cross_rhs(const double* X, int n, int d, const double* Xt, int count, int tp, const CovFn& cf, double* R,
                            hipStream_t s)
 {

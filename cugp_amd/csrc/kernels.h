@@ -441,6 +441,12 @@ IterPlan iter_apply_plan(int na, int nb, int force);
 // part: pl.split * na * tp doubles when pl.split > 1 (the ranges' partial blocks, added in range order by a second launch)
 void launch_cov_apply(const double* A, int na, const double* B, int nb, int d, const CovFn& cf, const double* V, int tp,
                       double* out, double* part, const IterPlan& pl, bool square, hipStream_t s);
+// out[c] = sum_ij (sum_k U[i][k] V[j][k]) F_c(x_i, x_j) over the full n x n square, c < cov_grad_columns: on the ARD route the d
+// factors H u_c^2, the family's shape columns, then Kf; else dKf / dlog l, then Kf (k_cov_grad).
+// pl = iter_apply_plan(n, n, .); part: pl.row_blocks * pl.split rows of cov_grad_columns doubles, added in row order
+inline int cov_grad_columns(const CovFn& cf, int d) { return cf.ard ? d + shape_count(cf.kind) + 1 : 2; }
+void launch_cov_grad(const double* X, int n, int d, const CovFn& cf, const double* U, const double* V, int tp, double* part,
+                     double* out, const IterPlan& pl, hipStream_t s);
 // R[j][c] = k(x_j, xt_c), c < count <= tp, zero columns beyond
 void launch_iter_cross_rhs(const double* X, int n, int d, const double* Xt, int count, int tp, const CovFn& cf, double* R,
                            hipStream_t s);

@@ -730,8 +730,8 @@ class SparseGP:
 class IterativeGP:
     """The exact GP of all n rows without any n x n matrix (cugp_iter_*): products with K = Kf + sn2 I whose entries are
     computed in registers, conjugate gradients on them, exact predictive mean and variance at O(n t) memory.  kernel / ard
-    as Covsum's (the rational quadratic names included), the hyper-parameter vector too.  No likelihood, no gradient:
-    hyper-parameters come from elsewhere.  Vectors are target-major, [t, n]."""
+    as Covsum's (the rational quadratic names included), the hyper-parameter vector too.  loglik_grad estimates the
+    log-likelihood's gradient from probe vectors; its value is not provided.  Vectors are target-major, [t, n]."""
 
     def __init__(self, n, d, kernel="se", ard=False, device=0):
         self.n, self.d, self.device = int(n), int(d), int(device)
@@ -807,6 +807,32 @@ class IterativeGP:
         check(capi.lib().cugp_iter_get_alpha(self._h, ptr(a)))
         return a
 
+    def grad_forms(self, U, V):
+        """[nh]: sum_ij (sum_c U[c, i] V[c, j]) dK_ij / dtheta_h for U, V [t, n] (cugp_iter_grad_forms); needs no fit."""
+        U, V = self._block(U), self._block(V)
+        if U.shape != V.shape:
+            raise ValueError("U and V must have one shape")
+        out = np.empty(self.nh)
+        check(capi.lib().cugp_iter_grad_forms(self._h, ptr(U), ptr(V), U.shape[0], ptr(out)))
+        return out
+
+    def loglik_grad(self, probes, rng=None, tol=1e-10, max_iter=1000, check_every=10):
+        """(g [nh], info): the gradient of the log marginal likelihood with Hutchinson's estimate of its trace term over the
+        probes (cugp_iter_loglik_grad) -- an array [t, n], or an int t: that many Rademacher +-1 rows drawn on the host from
+        rng (a numpy.random.Generator).  The same probes give the same bits.  Fits first where the handle has no valid fit;
+        that fit's convergence is not reported (call fit() first where alpha has to be certified).
+        info: {"solves": [t, 4] as solve's, "quad": y'alpha}."""
+        if isinstance(probes, (int, np.integer)):
+            if rng is None:
+                raise ValueError("drawing the probes needs rng, a numpy.random.Generator")
+            Z = rademacher(rng, int(probes), self.n)
+        else:
+            Z = self._block(probes)
+        g, solves, quad = np.empty(self.nh), np.empty((Z.shape[0], 4)), C.c_double()
+        check(capi.lib().cugp_iter_loglik_grad(self._h, ptr(Z), Z.shape[0], float(tol), int(max_iter), int(check_every), ptr(g),
+                                               C.byref(quad), ptr(solves)))
+        return g, {"solves": solves, "quad": quad.value}
+
     def predict(self, Xt, var=True, tol=1e-10, max_iter=1000, check_every=10):
         """(mean, var, info [nt, 4]) at the test points, var with sn2 as Covsum's; var=False: (mean, None, None), no solve."""
         Xt = f64(Xt).reshape(-1, self.d)
@@ -860,6 +886,13 @@ class IterativeGP:
         if rc < 0:
             check(rc)
         return dict(zip(("split", "per", "stages", "row_blocks"), out))
+
+
+def rademacher(rng, t, n):
+    """[t, n] of +-1.0 with equal probability from rng: IterativeGP.loglik_grad's probes for an int."""
+    if t < 1:
+        raise ValueError("at least one probe")
+    return 2.0 * rng.integers(0, 2, size=(t, n)).astype(np.float64) - 1.0
 
 
 def sparse_plan(n, m, chunk_rows=0):

@@ -885,8 +885,9 @@ int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap,
  * Every other exact call stores n^2 numbers (four npad x npad matrices per cugp_gp).  A cugp_iter handle holds X [n][d], y,
  * theta and a handful of n x 64 vectors: K = Kf + sn2 I of ALL n rows is applied to blocks of vectors with its entries
  * computed in registers (k_cov_apply, fp64 MFMA), and K^-1 b comes from conjugate gradients on that product -- the exact
- * predictive mean and variance at O(n t) memory, for hyper-parameters trained elsewhere (a subset, a BCM, the sparse
- * model).  No log marginal likelihood, no gradient.  Without a preconditioner (below) the sweep count grows with cond(K).
+ * predictive mean and variance at O(n t) memory.  The gradient of the log marginal likelihood comes as a Hutchinson
+ * estimate from the caller's probe vectors (cugp_iter_loglik_grad below); its value (the log-determinant) is not provided.
+ * Without a preconditioner (below) the sweep count grows with cond(K).
  *
  * Model: kernel in {CUGP_KERNEL_SE, _MATERN32, _MATERN52, CUGP_KERNEL_RQ}, ard in {0, 1}; theta as the dense handles'
  * ([log l | log l_1 .. log l_d, (RQ: log alpha,) log sigma_f, log sigma_n], nh = (ard ? d : 1) + (RQ ? 1 : 0) + 2).
@@ -928,8 +929,27 @@ int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap,
  *      MFMA steps per workgroup}; workgroup b sums the rows [b out[1], min((b + 1) out[1], n)) ascending, the workgroups'
  *      blocks are added in ascending b; t does not enter.  Returns the workgroup count.
  *
+ * Gradient.  theta_h in the handle's order; dK/dtheta_h of K = Kf + sn2 I.
+ * cugp_iter_grad_forms  : out [nh], out_h = sum_ij (sum_c U_c[i] V_c[j]) dK_ij/dtheta_h for U, V [t][n], any t (64 columns
+ *      travel per launch, the blocks' sums added in ascending order).  K's entries and the weights live in registers only
+ *      (k_cov_grad: the weight tile by fp64 MFMA).  Needs data and theta, no fit.  A tied rational quadratic handle's out_0 is
+ *      the index-order sum of the d per-dimension sums.
+ * cugp_iter_loglik_grad : g [nh], the estimate of dLL/dtheta_h = 1/2 sum_ij (K^-1 - alpha alpha')_ij dK_ij/dtheta_h -- sign and
+ *      scaling as cugp_loglik_grad's -- in which tr(K^-1 dK/dtheta_h) is replaced by Hutchinson's (1/t) sum_p u_p' (dK/dtheta_h)
+ *      z_p, u_p = K^-1 z_p, over the caller's probes Z [t][n]:
+ *          g_h = 1/2 [ (1/t) sum_p u_p' (dK/dtheta_h) z_p - alpha' (dK/dtheta_h) alpha ].
+ *      The library draws nothing: g is a deterministic function of (X, y, theta, Z, tol, max_iter, check_every, the
+ *      preconditioner's rank), the same bits on every call.  Probes with E[z z'] = I (Rademacher +-1, standard normals) make
+ *      it unbiased; Z = sqrt(n) I (t = n) makes it exact.  Without a valid fit the call first runs cugp_iter_fit's own path
+ *      (same tol, max_iter, check_every; alpha is then cugp_iter_fit's in bits and stays).  That
+ *      fit's convergence is NOT reported -- info covers the probes only: an alpha that stopped at max_iter enters as it
+ *      is, one that broke down is NaN and so is g; call cugp_iter_fit first where alpha has to be certified.  The probes are solved 64 at a
+ *      time as cugp_iter_solve solves them, with the preconditioner as set; info (may be NULL) [t][4] reports them in its
+ *      format.  A probe that did not converge enters with the iterate it reached (info says so); one that broke down is
+ *      NaN and so is g; the call returns CUGP_OK either way.  quad (may be NULL) receives y'alpha.
+ *
  * Refusals, all CUGP_ERR_INVALID before any device call with the call's name in cugp_last_error: a NULL argument (other
- * than info and var); a rank outside [0, min(n, CUGP_ITER_MAX_RANK)] (the handle stays as it was); n, d, t, nt < 1; n or nt beyond CUGP_ITER_MAX_N; an unknown kernel; ard outside {0, 1}; a negative
+ * than info, var and quad); more than 65535 * 16 input dimensions in a gradient call on an ARD or rational quadratic handle; a rank outside [0, min(n, CUGP_ITER_MAX_RANK)] (the handle stays as it was); n, d, t, nt < 1; n or nt beyond CUGP_ITER_MAX_N; an unknown kernel; ard outside {0, 1}; a negative
  * device; a split outside [0, CUGP_ITER_MAX_SPLIT]; nh that is not the handle's; tol not positive and finite; max_iter or check_every < 1; a product or
  * solve before both cugp_iter_set_data and cugp_iter_set_loghyper; cugp_iter_predict or cugp_iter_get_alpha without a
  * cugp_iter_fit since the data or theta last changed.  CUGP_ERR_NODEVICE from cugp_iter_create without a GPU. */
@@ -949,6 +969,9 @@ int cugp_iter_solve(cugp_iter *h, const double *B, int t, double tol, int max_it
                     double *info /* may be NULL */);
 int cugp_iter_fit(cugp_iter *h, double tol, int max_iter, int check_every, double *info /* may be NULL */);
 int cugp_iter_get_alpha(cugp_iter *h, double *alpha);
+int cugp_iter_grad_forms(cugp_iter *h, const double *U, const double *V, int t, double *out);
+int cugp_iter_loglik_grad(cugp_iter *h, const double *Z, int t, double tol, int max_iter, int check_every, double *g,
+                          double *quad /* may be NULL */, double *info /* may be NULL */);
 int cugp_iter_predict(cugp_iter *h, const double *Xt, int nt, double *mean, double *var /* may be NULL */, double tol,
                       int max_iter, int check_every, double *info /* may be NULL */);
 int cugp_iter_apply_plan(int na, int nb, int t, int out[4]);

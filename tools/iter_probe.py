@@ -14,6 +14,13 @@ rebuilds), one M^-1 V at t = 16 and one K V beside it (medians, host packing inc
 --ntvar points (single calls: sweeps and wall time).  --dims sets D (the length scales stay those of D = 10).
 
     python tools/iter_probe.py --precond 0 64 256 [--dims 10] [--n 100000]
+
+--grad: instead of the above, the gradient -> profiles/iter_grad_probe.json.  Per family: grad_forms and
+apply at t = 16 and t = 64 (tp = 16 | 64), medians of --reps calls after a warm-up call, wall time with the host's packing
+(grad_forms packs two blocks, apply one and unpacks one); fit, then loglik_grad with 15 and with 63 Rademacher probes at tol
+1e-8: SINGLE calls without a warm-up.  --kernel-stats DIR adds the device times of k_cov_grad* and k_cov_apply* from the
+*kernel_stats.csv files a separate `rocprofv3 --kernel-trace --stats -d DIR -- python tools/iter_probe.py --grad --forms-only`
+left there (average per launch, the warm-up launch included), as covariance entries per second.
 """
 import argparse
 import json
@@ -83,8 +90,67 @@ def precond_probe(a):
         json.dump(res, f, indent=1)
 
 
+def kernel_stats(root, n):
+    """{kernel: {calls, average_seconds, entries_per_s}} of the k_cov_grad* / k_cov_apply* rows of rocprofv3's kernel statistics"""
+    import csv
+    import glob
+    out = {}
+    for path in glob.glob(os.path.join(root, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                name = row.get("Name", "")
+                if ("k_cov_grad" in name or "k_cov_apply" in name) and "finish" not in name:
+                    avg = float(row["AverageNs"]) * 1e-9
+                    out[name.replace("cugp::", "").split("(")[0].replace("void ", "")] = {
+                        "calls": int(row["Calls"]), "average_seconds": avg, "entries_per_s": float(n) * n / avg}
+    return out
+
+
+def grad_probe(a):
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": D, "reps": a.reps, "tol": 1e-8, "families": {}}
+    X, y = synth(a.n, d=D)
+    rng = np.random.default_rng(0)
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        r = {"plan": g.plan(a.n, a.n)}
+        for t in (16, 64):
+            U, V = rng.standard_normal((t, a.n)), rng.standard_normal((t, a.n))
+            sg, sa = timed(lambda: g.grad_forms(U, V), a.reps)[0], timed(lambda: g.apply(V), a.reps)[0]
+            r["t%d" % t] = {"grad_forms_seconds": sg, "grad_forms_entries_per_s": float(a.n) * a.n / sg, "apply_seconds": sa,
+                            "apply_entries_per_s": float(a.n) * a.n / sa}
+            print(fam, "t", t, r["t%d" % t], flush=True)
+        if not a.forms_only:
+            t0 = time.perf_counter()
+            fi = g.fit(1e-8, 2000, 10)
+            r["fit"] = {"seconds": time.perf_counter() - t0, "sweeps": fi[0], "converged": fi[2]}
+            for probes in (15, 63):
+                t0 = time.perf_counter()
+                gr, info = g.loglik_grad(probes, np.random.default_rng(1), 1e-8, 2000, 10)
+                r["loglik_grad_%d" % probes] = {"seconds": time.perf_counter() - t0, "sweeps_max": float(info["solves"][:, 0].max()),
+                                                "converged": float(info["solves"][:, 2].min()), "g": gr.tolist()}
+            print(fam, {k: v for k, v in r.items() if k.startswith(("fit", "loglik"))}, flush=True)
+        g.close()
+        res["families"][fam] = r
+    if a.kernel_stats:
+        res["kernels"] = kernel_stats(a.kernel_stats, a.n)
+    res["single_unwarmed_calls"] = ["fit", "loglik_grad_15", "loglik_grad_63"]
+    res["not_measured"] = ["counters", "the device time of the probes' solves apart from the forms",
+                           "d > 16 (the feature-chunk grid dimension)"]
+    if a.forms_only:
+        return
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_grad_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grad", action="store_true", help="the gradient probe (its own mode)")
+    ap.add_argument("--forms-only", action="store_true", help="... grad_forms and apply alone, nothing written (for a kernel trace)")
+    ap.add_argument("--kernel-stats", default=None, help="... a directory with rocprofv3's kernel statistics of such a run")
     ap.add_argument("--precond", type=int, nargs="+", default=None, help="ranks of the preconditioner probe (its own mode)")
     ap.add_argument("--dims", type=int, default=D, help="input dimension of the preconditioner probe")
     ap.add_argument("--n", type=int, default=100000)
@@ -96,6 +162,8 @@ def main():
     a = ap.parse_args()
     if a.precond is not None:
         return precond_probe(a)
+    if a.grad:
+        return grad_probe(a)
     res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "nt": a.nt, "ntvar": a.ntvar, "d": D, "reps": a.reps, "families": {}}
     X, y = synth(a.n, d=D)
     Xt = synth(a.nt, d=D, seed=7)[0]
