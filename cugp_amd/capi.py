@@ -24,6 +24,7 @@ CUGP_KERNEL_SE, CUGP_KERNEL_MATERN32, CUGP_KERNEL_MATERN52 = 0, 1, 2
 CUGP_KERNEL_RQ = 3          # rational quadratic: create calls of its own (cugp_create_rq), not a kind= of the others
 CUGP_ITER_MAX_N = 2147482623     # cugp_iter_*: most rows of a matrix-free handle or of a product's output
 CUGP_ITER_MAX_RANK = 512         # ... most columns of its preconditioner's factor
+CUGP_ITER_FP64, CUGP_ITER_MIXED = 0, 1   # cugp_iter_set_precision: the product inside a solver's sweep
 CUGP_COMBINE_POE, CUGP_COMBINE_GPOE, CUGP_COMBINE_BCM, CUGP_COMBINE_RBCM = 0, 1, 2, 3
 CUGP_COMBINE_REFERENCE = -1      # cugp_bcm_predict_grad / cugp_poe_combine_grad: the reference's product of the noisy predictions
 CUGP_ERR_INVALID, CUGP_ERR_NOMEM, CUGP_ERR_DEVICE, CUGP_ERR_NODEVICE = -1, -2, -3, -4
@@ -219,6 +220,9 @@ SIGNATURES = {
     "cugp_iter_get_precond": (C.c_int, [C.c_void_p, _dp, _ip]),
     "cugp_iter_precond_apply": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
     "cugp_iter_precond_plan": (C.c_int, [C.c_int, C.c_int, _ip]),
+    "cugp_iter_set_precision": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "cugp_iter_apply32": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
+    "cugp_iter_solve_stats": (C.c_int, [C.c_void_p, _ip]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

@@ -23,6 +23,10 @@ struct cugp_iter {
     std::vector<double> theta;
     bool have_data = false, have_theta = false, fit_valid = false;
     int split = 0;                 // ranges of the product's j split; 0: iter_apply_plan's rule
+    // the solver's precision (cugp_iter_set_precision): mixed runs the sweeps on k_cov_apply32
+    bool mixed = false;
+    double cycle_drop = CUGP_ITER_CYCLE_DROP;
+    int stats[4] = {0, 0, 0, 0};   // fp32 products, fp64 products, verifications, fell back: the last solving call's
     Scratch vb, vx, vr, vp, vq, vk, alpha, apart, dpart, xt, res;
     Scratch gpart, gout, ghost;    // the gradient forms: k_cov_grad's partial rows; their sums and the
                                    // columns' u'v behind them; the pinned copy of those
@@ -82,28 +86,32 @@ int unpack(cugp_iter* h, const double* src, size_t rows, int c0, int cnt, int tp
     return CUGP_OK;
 }
 
-// out [na][tp] = k(A, X) V (+ sn2 V: square, A == X) on the handle's stream
-int product(cugp_iter* h, const CovFn& cf, const double* A, int na, const double* V, int tp, double* out, bool square)
+// out [na][tp] = k(A, X) V (+ sn2 V: square, A == X) on the handle's stream; f32: the mixed mode's product
+int product(cugp_iter* h, const CovFn& cf, const double* A, int na, const double* V, int tp, double* out, bool square,
+            bool f32 = false)
 {
     const IterPlan pl = iter_apply_plan(na, h->n, h->split);
     int rc;
     if (pl.split > 1 && (rc = h->apart.grow((size_t)pl.split * na * tp, h->stream))) return rc;
-    launch_cov_apply(A, na, h->dX, h->n, h->d, cf, V, tp, out, h->apart.p, pl, square, h->stream);
+    if (f32) launch_cov_apply32(A, na, h->dX, h->n, h->d, cf, V, tp, out, h->apart.p, pl, square, h->stream);
+    else launch_cov_apply(A, na, h->dX, h->n, h->d, cf, V, tp, out, h->apart.p, pl, square, h->stream);
     return CUGP_OK;
 }
 
-struct Counts { int active, waiting; };
-int read_status(cugp_iter* h, int tp, const char* call, Counts* k)
+struct Counts { int active, waiting, stalled; };
+// rows: SC_ROWS, or SC_ALLOC while the mixed mode's sweeps run (the stall flags lie behind the rows of the fp64 mode)
+int read_status(cugp_iter* h, int tp, const char* call, Counts* k, int rows = SC_ROWS)
 {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
-        e = hipMemcpyAsync(h->hsc, h->dsc, (size_t)SC_ROWS * IT_MAXT * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+        e = hipMemcpyAsync(h->hsc, h->dsc, (size_t)rows * IT_MAXT * sizeof(double), hipMemcpyDeviceToHost, h->stream);
     if (const int rc = sync_or_fail(h->stream, call, e)) return rc;
-    k->active = k->waiting = 0;
+    k->active = k->waiting = k->stalled = 0;
     for (int c = 0; c < tp; c++) {
         const double st = h->hsc[SC_STATE * IT_MAXT + c];
         k->active += st == ST_ACTIVE || st == ST_RESTART;
         k->waiting += st == ST_CANDIDATE;
+        if (rows > SC_STALL) k->stalled += h->hsc[SC_STALL * IT_MAXT + c] != 0.0;
     }
     return CUGP_OK;
 }
@@ -195,6 +203,11 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
     launch_iter_dot(B, B, n, tp, part, s);
     launch_iter_init(part, n, tp, tol, sc, s);
     launch_iter_start(B, x, r, p, n, tp, s);
+    // mixed: the sweeps' product in fp32 and cycle goals, until a verification finds a column stalled (then, and in the
+    // fp64 mode from the start, the launches below are the fp64 mode's)
+    bool f32 = h->mixed;
+    const double rho2 = h->cycle_drop * h->cycle_drop;
+    if (f32) launch_iter_goal_init(tp, rho2, sc, s);
     if (pc) {
         precondition(1);
         launch_iter_dir(p, z, n, tp, sc, 0, s);        // (the ratio is 0 from k_iter_init: p = z)
@@ -202,8 +215,11 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
     // the true residual of the columns that wait for it (final: of the active ones too)
     auto verify = [&](int final) {
         if (const int e = product(h, cf, h->dX, n, x, tp, q, true)) return e;
+        h->stats[1]++;
+        h->stats[2]++;
         launch_iter_resid(B, q, r, n, tp, sc, final, part, s);
-        launch_iter_step_v(part, n, tp, final, sc, s);
+        if (f32) launch_iter_step_v_mx(part, n, tp, final, rho2, sc, s);
+        else launch_iter_step_v(part, n, tp, final, sc, s);
         if (!final && pc) precondition(1);
         if (!final) launch_iter_dir(p, pc ? z : r, n, tp, sc, 1, s);
         return (int)CUGP_OK;
@@ -211,7 +227,15 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
     Counts k;
     int it = 0;
     for (;;) {
-        if ((rc = read_status(h, tp, call, &k))) return rc;
+        if ((rc = read_status(h, tp, call, &k, f32 ? SC_ALLOC : SC_ROWS))) return rc;
+        if (f32 && k.stalled) {                        // fp32 cannot refine this K: the rest of the call in fp64,
+            f32 = false;                               // the unfinished columns again from x = 0 (k_iter_again)
+            h->stats[3] = 1;
+            launch_iter_again(B, x, r, n, tp, sc, s);
+            if (pc) precondition(1);
+            launch_iter_dir(p, pc ? z : r, n, tp, sc, 1, s);
+            continue;
+        }
         if (k.waiting) {
             if ((rc = verify(0))) return rc;
             continue;
@@ -219,12 +243,14 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
         if (!k.active || it >= max_iter) break;
         const int m = std::min(check_every, max_iter - it);
         for (int j = 0; j < m; j++) {
-            if ((rc = product(h, cf, h->dX, n, p, tp, q, true))) return rc;
+            if ((rc = product(h, cf, h->dX, n, p, tp, q, true, f32))) return rc;
+            h->stats[f32 ? 0 : 1]++;
             launch_iter_dot(p, q, n, tp, part, s);
             if (pc) launch_iter_step_a_pc(part, n, tp, sc, s);
             else launch_iter_step_a(part, n, tp, sc, s);
             launch_iter_update(x, r, p, q, n, tp, sc, part, s);
-            launch_iter_step_b(part, n, tp, sc, s);
+            if (f32) launch_iter_step_b_mx(part, n, tp, sc, s);
+            else launch_iter_step_b(part, n, tp, sc, s);
             if (pc) precondition(0);
             launch_iter_dir(p, pc ? z : r, n, tp, sc, 0, s);
         }
@@ -538,6 +564,43 @@ int cugp_iter_apply(cugp_iter* h, const double* V, int t, double* out)
     return CUGP_OK;
 }
 
+int cugp_iter_apply32(cugp_iter* h, const double* V, int t, double* out)
+{
+    const char* call = "cugp_iter_apply32";
+    if (!h || !V || !out) return invalid_arg(call, "null argument");
+    if (t < 1) return invalid_arg(call, "t must be positive");
+    int rc;
+    if ((rc = ready(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
+        if ((rc = pack(h, V, h->n, c0, cnt, tp, h->vb)) || (rc = h->vq.grow((size_t)h->n * tp, h->stream))) return rc;
+        if ((rc = product(h, cf, h->dX, h->n, h->vb.p, tp, h->vq.p, true, true))) return rc;
+        if ((rc = sync_or_fail(h->stream, call, hipGetLastError()))) return rc;
+        if ((rc = unpack(h, h->vq.p, h->n, c0, cnt, tp, out))) return rc;
+    }
+    return CUGP_OK;
+}
+
+int cugp_iter_set_precision(cugp_iter* h, int mode, double cycle_drop)
+{
+    const char* call = "cugp_iter_set_precision";
+    if (mode != CUGP_ITER_FP64 && mode != CUGP_ITER_MIXED) return invalid_arg(call, "mode must be CUGP_ITER_FP64 or CUGP_ITER_MIXED");
+    if (!(cycle_drop == 0.0 || (cycle_drop > 0.0 && cycle_drop < 1.0))) return invalid_arg(call, "cycle_drop must lie in (0, 1), or be 0");
+    if (!h) return invalid_arg(call, "null handle");
+    h->mixed = mode == CUGP_ITER_MIXED;
+    h->cycle_drop = cycle_drop == 0.0 ? CUGP_ITER_CYCLE_DROP : cycle_drop;
+    return CUGP_OK;
+}
+
+int cugp_iter_solve_stats(const cugp_iter* h, int out[4])
+{
+    if (!h || !out) return invalid_arg("cugp_iter_solve_stats", "null argument");
+    std::copy(h->stats, h->stats + 4, out);
+    return CUGP_OK;
+}
+
 int cugp_iter_apply_cross(cugp_iter* h, const double* Xt, int nt, const double* V, int t, double* out)
 {
     const char* call = "cugp_iter_apply_cross";
@@ -569,6 +632,7 @@ int cugp_iter_solve(cugp_iter* h, const double* B, int t, double tol, int max_it
     int rc;
     if ((rc = solver_args(call, tol, max_iter, check_every)) || (rc = ready(h, call))) return rc;
     HIPCHK(hipSetDevice(h->device));
+    std::fill(h->stats, h->stats + 4, 0);
     const CovFn cf = cov_of(h);
     for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
         const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
@@ -587,6 +651,7 @@ int cugp_iter_fit(cugp_iter* h, double tol, int max_iter, int check_every, doubl
     int rc;
     if ((rc = solver_args(call, tol, max_iter, check_every)) || (rc = ready(h, call))) return rc;
     HIPCHK(hipSetDevice(h->device));
+    std::fill(h->stats, h->stats + 4, 0);
     return fit_run(h, tol, max_iter, check_every, info, call);
 }
 
@@ -618,6 +683,7 @@ int cugp_iter_loglik_grad(cugp_iter* h, const double* Z, int t, double tol, int 
     int rc;
     if ((rc = solver_args(call, tol, max_iter, check_every)) || (rc = ready(h, call)) || (rc = grad_dims(h, call))) return rc;
     HIPCHK(hipSetDevice(h->device));
+    std::fill(h->stats, h->stats + 4, 0);
     if (!h->fit_valid && (rc = fit_run(h, tol, max_iter, check_every, nullptr, call))) return rc;
     const CovFn cf = cov_of(h);
     hipStream_t s = h->stream;
@@ -675,6 +741,7 @@ int cugp_iter_predict(cugp_iter* h, const double* Xt, int nt, double* mean, doub
     if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
     if ((rc = unpack(h, h->res.p, nt, 0, 1, 16, mean))) return rc;
     if (!var) return CUGP_OK;
+    std::fill(h->stats, h->stats + 4, 0);
     // var_c = sf2 + sn2 - ks_c' K^-1 ks_c, IT_MAXT test points a solve
     const double prior = h->hhs->signal_var + h->hhs->noise_var;
     double *dsum = h->dsc + (size_t)SC_ROWS * IT_MAXT, *hsum = h->hsc + (size_t)SC_ROWS * IT_MAXT;

@@ -263,6 +263,96 @@ __global__ __launch_bounds__(256) void k_iter_step_z(const double* __restrict__ 
     sc[SC_RZ * IT_MAXT + c] = rz;
 }
 
+// ---- the mixed mode's cycles: the sweeps run on an fp32 product, so the recurrence's residual goes
+// on falling after the true one has stalled.  A column therefore also waits for its true residual once r'r has fallen to
+// rho2 times its value at the last true residual (b'b at the start): row SC_GOAL.  Rows SC_PREV and SC_STALL let the host see
+// a column whose true r'r fell by less than a factor 4 between two verifications.  The kernels above keep their text.
+
+// one workgroup, behind k_iter_init: the first cycle's goal
+__global__ __launch_bounds__(256) void k_iter_goal_init(int tp, double rho2, double* __restrict__ sc)
+{
+    const int c = threadIdx.x;
+    if (c >= tp) return;
+    const double bb = sc[SC_BB * IT_MAXT + c];
+    sc[SC_GOAL * IT_MAXT + c] = rho2 * bb;
+    sc[SC_PREV * IT_MAXT + c] = bb;
+    sc[SC_STALL * IT_MAXT + c] = 0.0;
+}
+
+// k_iter_step_b with the cycle goal beside the tolerance, and a growth limit
+__global__ __launch_bounds__(256) void k_iter_step_b_mx(const double* __restrict__ part, int nblk, int tp, double* __restrict__ sc)
+{
+    const int c = threadIdx.x;
+    if (c >= tp || sc[SC_STATE * IT_MAXT + c] != ST_ACTIVE) return;
+    const double rn = iter_sum_parts(part, nblk, tp, c);
+    sc[SC_ITERS * IT_MAXT + c] += 1.0;
+    if (!(rn - rn == 0.0)) { sc[SC_STATE * IT_MAXT + c] = ST_BROKEN; return; }
+    sc[SC_B * IT_MAXT + c] = rn / sc[SC_RR * IT_MAXT + c];
+    sc[SC_RR * IT_MAXT + c] = rn;
+    // |r|^2 <= cond(K) |r_0|^2 along exact CG: r'r grown 2^20-fold since the last true residual shows a K beyond what fp32
+    // refines (or a recurrence that has lost the truth) without waiting for a goal that will not come
+    if (rn <= sc[SC_TOL2 * IT_MAXT + c] || rn <= sc[SC_GOAL * IT_MAXT + c] || rn > 1048576.0 * sc[SC_PREV * IT_MAXT + c])
+        sc[SC_STATE * IT_MAXT + c] = ST_CANDIDATE;
+}
+
+// k_iter_step_v; a column that goes on from its true residual gets the next cycle's goal, and its stall flag where the
+// true r'r has not fallen by a factor 4 since the previous verification (by less where less was asked: below)
+__global__ __launch_bounds__(256) void k_iter_step_v_mx(const double* __restrict__ part, int nblk, int tp, int final, double rho2,
+                                                        double* __restrict__ sc)
+{
+#pragma clang fp contract(off)
+    const int c = threadIdx.x;
+    if (c >= tp) return;
+    const double st = sc[SC_STATE * IT_MAXT + c];
+    if (!(st == ST_CANDIDATE || (final && st == ST_ACTIVE))) return;
+    const double rt = iter_sum_parts(part, nblk, tp, c);
+    sc[SC_TRUE * IT_MAXT + c] = rt;
+    if (!(rt - rt == 0.0)) sc[SC_STATE * IT_MAXT + c] = ST_BROKEN;
+    else if (rt <= sc[SC_TOL2 * IT_MAXT + c]) sc[SC_STATE * IT_MAXT + c] = ST_DONE;
+    else if (!final) {
+        sc[SC_RR * IT_MAXT + c] = rt;
+        sc[SC_STATE * IT_MAXT + c] = ST_RESTART;
+        // the cycle asked r'r to fall from prev to max(goal, tol^2): a last leg that starts close above the tolerance is
+        // not asked for a factor 4, and is held to the root of what it was asked for instead
+        const double prev = sc[SC_PREV * IT_MAXT + c];
+        const double goal = sc[SC_GOAL * IT_MAXT + c], tol2 = sc[SC_TOL2 * IT_MAXT + c];
+        const double asked = prev / (goal > tol2 ? goal : tol2);
+        const double need = asked < 16.0 ? __builtin_sqrt(asked) : 4.0;
+        if (need * rt > prev) sc[SC_STALL * IT_MAXT + c] = 1.0;
+        sc[SC_PREV * IT_MAXT + c] = rt;
+        sc[SC_GOAL * IT_MAXT + c] = rho2 * rt;
+    }
+}
+
+// The fall back to the fp64 product.  Conjugate gradients on a K32 that fp32 cannot refine drive x along directions in which
+// K32 and K differ, and the true residual of such an x can lie orders of magnitude above |b|: going on from it would ask fp64
+// CG for that much more than the tolerance.  So every unfinished column starts again -- x = 0, r = b, the sweeps spent stay
+// counted -- and the rest of the call is the fp64 mode's solve.  k_iter_again: the vectors; k_iter_again_sc, one workgroup
+// behind it: r'r = b'b, and ST_RESTART, so that k_iter_dir's restart pass sets p = r (or z) as after a failed verification
+__global__ __launch_bounds__(256) void k_iter_again(const double* __restrict__ bv, double* __restrict__ x, double* __restrict__ r,
+                                                    int n, int tp, const double* __restrict__ sc)
+{
+    const int t = threadIdx.x, c = t % tp, g = t / tp, G = 256 / tp;
+    const double st = sc[SC_STATE * IT_MAXT + c];
+    if (st != ST_ACTIVE && st != ST_RESTART) return;
+    const size_t r0 = (size_t)blockIdx.x * IT_ROWS, r1 = r0 + IT_ROWS < (size_t)n ? r0 + IT_ROWS : (size_t)n;
+    for (size_t i = r0 + g; i < r1; i += G) {
+        const size_t e = i * tp + c;
+        x[e] = 0.0;
+        r[e] = bv[e];
+    }
+}
+__global__ __launch_bounds__(256) void k_iter_again_sc(int tp, double* __restrict__ sc)
+{
+    const int c = threadIdx.x;
+    if (c >= tp) return;
+    const double st = sc[SC_STATE * IT_MAXT + c];
+    if (st != ST_ACTIVE && st != ST_RESTART) return;
+    sc[SC_RR * IT_MAXT + c] = sc[SC_BB * IT_MAXT + c];
+    sc[SC_TRUE * IT_MAXT + c] = sc[SC_BB * IT_MAXT + c];
+    sc[SC_STATE * IT_MAXT + c] = ST_RESTART;
+}
+
 // ---- the pivoted Cholesky factor L L' ~ Kf of the preconditioner, one launch per step ----
 // State: L [n][rp] row-major (zero beyond the achieved rank), the residual diagonal dres [n] (-inf: the row is a pivot),
 // piv [rp], ctl = {achieved rank, -1 while the factor runs; NaN seen}, and the workgroups' argmax shares of the step before

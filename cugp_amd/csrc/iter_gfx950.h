@@ -737,3 +737,21 @@ void launch_iter_step_z(const double* part, int n, int tp, int first, double* sc
 {
     hipLaunchKernelGGL(k_iter_step_z, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, first, sc);
 }
+// the mixed mode's cycle kernels (iter_device.h; the fp32 product and its launcher: iter32_gfx950.h)
+void launch_iter_goal_init(int tp, double rho2, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_goal_init, dim3(1), dim3(256), 0, s, tp, rho2, sc);
+}
+void launch_iter_step_b_mx(const double* part, int n, int tp, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_b_mx, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, sc);
+}
+void launch_iter_step_v_mx(const double* part, int n, int tp, int final, double rho2, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_step_v_mx, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, final, rho2, sc);
+}
+void launch_iter_again(const double* b, double* x, double* r, int n, int tp, double* sc, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_again, dim3(iter_blocks(n)), dim3(256), 0, s, b, x, r, n, tp, sc);
+    hipLaunchKernelGGL(k_iter_again_sc, dim3(1), dim3(256), 0, s, tp, sc);
+}

@@ -466,7 +466,10 @@ void launch_iter_step_v(const double* part, int n, int tp, int final, double* sc
 void launch_iter_poison(double* x, int n, int tp, const double* sc, hipStream_t s);
 // ---- the pivoted-Cholesky preconditioner of the recurrences: M = L L' + sn2 I, M^-1 = (I - Q Q') / sn2
 constexpr int SC_RZ = SC_ROWS + 1;   // r'z of the preconditioned recurrence: a row behind the host's (SC_ROWS: the variance's sums)
-constexpr int SC_ALLOC = SC_ROWS + 2;
+// the mixed mode's rows behind it: the cycle goal on r'r, the true r'r of the column's previous
+// verification, 1 where a verification found it fallen by less than a factor 4
+constexpr int SC_GOAL = SC_ROWS + 2, SC_PREV = SC_ROWS + 3, SC_STALL = SC_ROWS + 4;
+constexpr int SC_ALLOC = SC_ROWS + 5;
 constexpr int PCH_ROWS = 256;        // rows (= threads) of a workgroup of k_pchol_step
 constexpr int PCH_MAX_RANK = 512;    // cugp.h CUGP_ITER_MAX_RANK
 constexpr int PCH_NO_ROW = 2147483647;
@@ -495,6 +498,14 @@ void launch_pc_correct(const double* Q, int rp, const double* T, int ldt, int c0
                        int tp, double* out, int ldo, hipStream_t s);
 void launch_iter_step_a_pc(const double* part, int n, int tp, double* sc, hipStream_t s);
 void launch_iter_step_z(const double* part, int n, int tp, int first, double* sc, hipStream_t s);
+// ---- the mixed mode (iter32_gfx950.h): launch_cov_apply with entries, V and the MFMA in fp32, the
+// sums folded into fp64 every 128 terms; and the recurrences' step kernels with a cycle goal (rho2 = cycle_drop^2)
+void launch_cov_apply32(const double* A, int na, const double* B, int nb, int d, const CovFn& cf, const double* V, int tp,
+                        double* out, double* part, const IterPlan& pl, bool square, hipStream_t s);
+void launch_iter_goal_init(int tp, double rho2, double* sc, hipStream_t s);
+void launch_iter_step_b_mx(const double* part, int n, int tp, double* sc, hipStream_t s);
+void launch_iter_step_v_mx(const double* part, int n, int tp, int final, double rho2, double* sc, hipStream_t s);
+void launch_iter_again(const double* b, double* x, double* r, int n, int tp, double* sc, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

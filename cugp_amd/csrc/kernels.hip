@@ -233,6 +233,9 @@ static void set_big_lds();
 // k_cov_apply, k_cov_apply4 (K V with K in registers: the entry is the MFMA's A operand), k_cov_apply_finish, iter_apply_plan
 // and the launchers of these and of the emulable header above
 #include "iter_gfx950.h"
+// k_cov_apply32, k_cov_apply32_4 (the mixed mode's product: fp32 entries and MFMA, folded into fp64 every 128 terms),
+// kernel_value32 and launch_cov_apply32
+#include "iter32_gfx950.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
 // failure is kept (the launch that follows would be rejected) and reported by prepare_kernels().

@@ -774,12 +774,31 @@ class IterativeGP:
             raise ValueError("expected vectors [t, %d]" % self.n)
         return V
 
-    def apply(self, V):
-        """(Kf + sn2 I) V for V [t, n] (cugp_iter_apply)."""
+    def apply(self, V, precision="fp64"):
+        """(Kf + sn2 I) V for V [t, n] (cugp_iter_apply); precision="fp32": the mixed mode's product, entries and V rounded
+        to single precision, sums folded into fp64 every 128 terms (cugp_iter_apply32)."""
+        if precision not in ("fp64", "fp32"):
+            raise ValueError('precision must be "fp64" or "fp32"')
         V = self._block(V)
         out = np.empty_like(V)
-        check(capi.lib().cugp_iter_apply(self._h, ptr(V), V.shape[0], ptr(out)))
+        call = capi.lib().cugp_iter_apply if precision == "fp64" else capi.lib().cugp_iter_apply32
+        check(call(self._h, ptr(V), V.shape[0], ptr(out)))
         return out
+
+    def set_precision(self, mode, cycle_drop=None):
+        """"fp64" (the default) or "mixed": solve, fit, predict's variance and loglik_grad's probe solves then run their
+        sweeps on the fp32 product and verify every column on the fp64 one, so info certifies what it certifies in "fp64".
+        cycle_drop in (0, 1): the fall of the recurrence's residual after which a column is verified (None: 2^-10)."""
+        if mode not in ("fp64", "mixed"):
+            raise ValueError('mode must be "fp64" or "mixed"')
+        check(capi.lib().cugp_iter_set_precision(self._h, capi.CUGP_ITER_MIXED if mode == "mixed" else capi.CUGP_ITER_FP64,
+                                                 0.0 if cycle_drop is None else float(cycle_drop)))
+
+    def solve_stats(self):
+        """{fp32_products, fp64_products, verifications, fell_back} of the last solving call (cugp_iter_solve_stats)."""
+        out = (C.c_int * 4)()
+        check(capi.lib().cugp_iter_solve_stats(self._h, out))
+        return dict(zip(("fp32_products", "fp64_products", "verifications", "fell_back"), out))
 
     def apply_cross(self, Xt, V):
         """k(Xt, X) V [t, nt], no noise term (cugp_iter_apply_cross)."""

@@ -981,6 +981,35 @@ int cugp_iter_precond_info(cugp_iter *h, int out[4]);
 int cugp_iter_get_precond(cugp_iter *h, double *L, int *piv);
 int cugp_iter_precond_apply(cugp_iter *h, const double *V, int t, double *out);
 int cugp_iter_precond_plan(int n, int rank, int out[4]);
+/* Mixed precision (off by default; DESIGN.md section 36, docs/ACCURACY.md "The fp32 product").
+ * cugp_iter_set_precision(h, mode, cycle_drop): mode CUGP_ITER_FP64 (the default: every call launches what it launched
+ *      before the mode existed and returns the same bits) or CUGP_ITER_MIXED.  In the mixed mode cugp_iter_solve, _fit,
+ *      _predict's variance and _loglik_grad's probe solves run their sweeps on the fp32 product (k_cov_apply32: entries, V and
+ *      the MFMA in single precision, the sums folded into fp64 every 128 terms), while every verification -- the only place
+ *      where a column becomes converged -- keeps the fp64 product: info certifies |b - K x| / |b| with the fp64 K, as in the
+ *      fp64 mode.  Vectors, dot products, updates and the preconditioner stay fp64.  A column is verified when its
+ *      recurrence reaches tol |b|, and also when its r'r has fallen to cycle_drop^2 times its value at the last
+ *      verification (iterative refinement); cycle_drop in (0, 1), 0: the default 2^-10.  It moves the number of sweeps,
+ *      never what is certified.  Where a verification finds a column's true r'r fallen by less than a factor 4 since its
+ *      previous one (cond(K) beyond what fp32 refines), the rest of that solve runs on the fp64 product for all its
+ *      columns, the unfinished ones again from x = 0 (their sweeps so far stay counted).  max_iter counts sweeps of either kind; breakdown keeps its contract.  cugp_iter_apply, _apply_cross, the
+ *      mean, _grad_forms and the gradient's forms stay fp64.  The call invalidates nothing: a fit certified in either mode
+ *      is a fit.
+ * cugp_iter_apply32    : out [t][n] = sum_j fl32(k_ij) fl32(V_j) + sn2 V (the noise term in fp64), any t, 64 columns a launch,
+ *      as cugp_iter_apply; needs data and theta.  Two calls give the same bits, a column's bits do not depend on its
+ *      neighbours, and the operator is symmetric in bits.
+ * cugp_iter_solve_stats: out = {fp32 products, fp64 products, verifications, fell back (0 / 1)} of the last cugp_iter_solve,
+ *      _fit, _loglik_grad or variance-bearing _predict on the handle (all its 64-column batches).  Each of these clears the
+ *      counters on entry; a _predict without a variance needs a certified fit, solves nothing and leaves them as they are.
+ * Refused with CUGP_ERR_INVALID before any device call: a mode other than the two, cycle_drop outside (0, 1) and not 0
+ *      (both before the handle is looked at; the handle stays as it was), a NULL argument, t < 1, cugp_iter_apply32 before
+ *      data and theta. */
+#define CUGP_ITER_FP64 0
+#define CUGP_ITER_MIXED 1
+#define CUGP_ITER_CYCLE_DROP 0.0009765625   /* 2^-10 */
+int cugp_iter_set_precision(cugp_iter *h, int mode, double cycle_drop);
+int cugp_iter_apply32(cugp_iter *h, const double *V, int t, double *out);
+int cugp_iter_solve_stats(const cugp_iter *h, int out[4]);
 
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);

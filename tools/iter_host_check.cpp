@@ -3,7 +3,7 @@
 // of exactly the library's sizes, under -fsanitize=address,undefined.  One sweep of the t recurrences -- b'b, the start, p'q
 // and the step length, the update with r'r, the ratio, the new direction, then the true-residual pass, the poisoning of
 // broken columns, the closing pass over the still-active columns and k_iter_sum -- on a q the caller supplies (the product itself needs the MFMA), and k_iter_cross_rhs for one
-// isotropic and the rational quadratic instantiation.  Every output is compared BIT FOR BIT with the plain loops below in
+// isotropic and the rational quadratic instantiation; then the mixed mode's cycle kernels (check_mixed below).  Every output is compared BIT FOR BIT with the plain loops below in
 // the kernels' order of summation: the 16 row classes of a workgroup each in row order, the classes ascending, the
 // workgroups ascending.  Exit code 4: a mismatch.  A stand-alone program: the sanitizer is linked in, nothing is preloaded.
 #include "host_emul.h"
@@ -59,6 +59,103 @@ bool check_rhs(const double* X, int n, int d, const double* Xt, int count, int t
         }
     return same_bits(R, ref.data(), cnt, ARD ? "rhs rq" : "rhs se");
 }
+
+// ---- the mixed mode's one-workgroup kernels (k_iter_goal_init, k_iter_step_b_mx, k_iter_step_v_mx): two cycles and a closing
+// pass on shares the program lays out itself, one scenario per column, everything in units of the column's b'b.
+// T = tol^2 = 2^-10, R = rho^2 = 2^-4; every figure is dyadic, so the shares add up exactly and `equal` cases are equal.
+constexpr int MX_STAGES = 6, MX_CASES = 11;
+constexpr double MX_T = 0x1p-10, MX_R = 0x1p-4, MX_NAN = __builtin_nan("");
+enum { MX_RN1, MX_RT1, MX_PQ, MX_RN2, MX_RT2, MX_RT3 };
+// column:                        0 tol   1 goal,  2 grown, 3 stays  4 NaN   5 b = 0 6 goal,  7 at the 8 last leg 9 last leg 10 b NaN
+//                                reached   stalls   stalls   active   r'r             NaN true goal     not flagged flagged
+const double MX_TAB[MX_STAGES][MX_CASES] = {
+    /* r'r, sweep 1        */ {MX_T / 2, MX_R / 2, 0x1p21,  0.5,     MX_NAN, 1.0,    MX_R / 2, MX_R,    MX_R / 2,   MX_R / 2,  1.0},
+    /* true r'r, check 1   */ {MX_T,     0.5,      2.0,     1.0,     1.0,    1.0,    MX_NAN,   0.125,   3 * MX_T,   3 * MX_T,  1.0},
+    /* p'q                 */ {2.0,      2.0,      2.0,     2.0,     2.0,    2.0,    2.0,      2.0,     2.0,        2.0,       2.0},
+    /* r'r, sweep 2        */ {1.0,      0.25,     1.0,     0.25,    1.0,    1.0,    1.0,      0x1p-7,  MX_T / 2,   MX_T / 2,  1.0},
+    /* true r'r, check 2   */ {1.0,      1.0,      1.0,     1.0,     1.0,    1.0,    1.0,      MX_T / 2, 1.5 * MX_T, 2 * MX_T, 1.0},
+    /* true r'r, final = 1 */ {1.0,      MX_T / 4, 0.5,     MX_NAN,  1.0,    1.0,    1.0,      1.0,     1.0,        1.0,       1.0}};
+const double MX_REST[MX_STAGES] = {0.5, 1.0, 2.0, 0.25, 1.0, 0.25};        // columns 11 and up: active to the end
+
+double mx_bb(int c) { return c == 5 ? 0.0 : c == 10 ? MX_NAN : 4.0 * (double)(1 << (c % 3)); }
+double mx_value(int stage, int c) { return (c < MX_CASES ? MX_TAB[stage][c] : MX_REST[stage]) * (stage == MX_PQ ? 1.0 : mx_bb(c)); }
+// the value v in nblk shares that add up to it exactly: half in the first block, the rest in equal parts
+void mx_shares(double* part, int nblk, int tp, int stage)
+{
+    for (int c = 0; c < tp; c++) {
+        const double v = stage < 0 ? mx_bb(c) : mx_value(stage, c);
+        for (int b = 0; b < nblk; b++) part[(size_t)b * tp + c] = nblk == 1 ? v : (b == 0 ? v * 0.5 : v * 0.5 / (nblk - 1));
+    }
+}
+double mx_sum(const double* part, int nblk, int tp, int c)
+{
+    double s = part[c];
+    for (int b = 1; b < nblk; b++) s = s + part[(size_t)b * tp + c];
+    return s;
+}
+bool check_mixed(int nblk, int tp, double* sc)
+{
+    const double tol = 0x1p-5, rho2 = MX_R;
+    double* part = (double*)malloc((size_t)nblk * tp * 8);
+    std::vector<double> rs(SC_ALLOC * IT_MAXT, -7.0);                 // (-7: a row or column no kernel may touch)
+    for (int e = 0; e < SC_ALLOC * IT_MAXT; e++) sc[e] = -7.0;
+    auto stage = [&](int st, auto&& kernel) { mx_shares(part, nblk, tp, st); launch(1, kernel); };
+    stage(-1, [&] { k_iter_init(part, nblk, tp, tol, sc); });
+    launch(1, [&] { k_iter_goal_init(tp, rho2, sc); });
+    stage(MX_RN1, [&] { k_iter_step_b_mx(part, nblk, tp, sc); });
+    stage(MX_RT1, [&] { k_iter_step_v_mx(part, nblk, tp, 0, rho2, sc); });
+    stage(MX_PQ, [&] { k_iter_step_a(part, nblk, tp, sc); });
+    stage(MX_RN2, [&] { k_iter_step_b_mx(part, nblk, tp, sc); });
+    stage(MX_RT2, [&] { k_iter_step_v_mx(part, nblk, tp, 0, rho2, sc); });
+    stage(MX_RT3, [&] { k_iter_step_v_mx(part, nblk, tp, 1, rho2, sc); });
+    // the same, column by column
+    for (int c = 0; c < tp; c++) {
+        auto at = [&](int row) -> double& { return rs[row * IT_MAXT + c]; };
+        auto sum = [&](int st) { mx_shares(part, nblk, tp, st); return mx_sum(part, nblk, tp, c); };
+        const double bb = sum(-1);
+        at(SC_RR) = at(SC_BB) = at(SC_TRUE) = at(SC_PREV) = bb;
+        at(SC_TOL2) = (tol * tol) * bb;
+        at(SC_A) = at(SC_B) = at(SC_ITERS) = at(SC_STALL) = 0.0;
+        at(SC_GOAL) = rho2 * bb;
+        double st = bb == 0.0 ? ST_DONE : (bb - bb == 0.0 ? ST_ACTIVE : ST_BROKEN);
+        auto sweep = [&](int which) {
+            if (st != ST_ACTIVE) return;
+            const double rn = sum(which);
+            at(SC_ITERS) = at(SC_ITERS) + 1.0;
+            if (!(rn - rn == 0.0)) { st = ST_BROKEN; return; }
+            at(SC_B) = rn / at(SC_RR);
+            at(SC_RR) = rn;
+            if (rn <= at(SC_TOL2)) st = ST_CANDIDATE;                 // the tolerance
+            else if (rn <= at(SC_GOAL)) st = ST_CANDIDATE;            // the cycle's goal
+            else if (rn > 1048576.0 * at(SC_PREV)) st = ST_CANDIDATE; // grown 2^20-fold since the last true residual
+        };
+        auto verify = [&](int which, bool final) {
+            if (!(st == ST_CANDIDATE || (final && st == ST_ACTIVE))) return;
+            const double rt = sum(which);
+            at(SC_TRUE) = rt;
+            if (!(rt - rt == 0.0)) { st = ST_BROKEN; return; }
+            if (rt <= at(SC_TOL2)) { st = ST_DONE; return; }
+            if (final) return;
+            const double low = at(SC_GOAL) > at(SC_TOL2) ? at(SC_GOAL) : at(SC_TOL2), asked = at(SC_PREV) / low;
+            double need = 4.0;
+            if (asked < 16.0) need = __builtin_sqrt(asked);
+            if (need * rt > at(SC_PREV)) at(SC_STALL) = 1.0;
+            at(SC_RR) = at(SC_PREV) = rt;
+            at(SC_GOAL) = rho2 * rt;
+            st = ST_RESTART;
+        };
+        sweep(MX_RN1);
+        verify(MX_RT1, false);
+        if (st == ST_RESTART) st = ST_ACTIVE;
+        if (st == ST_ACTIVE) at(SC_A) = at(SC_RR) / sum(MX_PQ);      // (p'q = 2 > 0 in every column)
+        sweep(MX_RN2);
+        verify(MX_RT2, false);
+        verify(MX_RT3, true);
+        at(SC_STATE) = st;
+    }
+    free(part);
+    return same_bits(sc, rs.data(), SC_ALLOC * IT_MAXT, "mixed scalar");
+}
 }  // namespace
 
 int main(int argc, char** argv)
@@ -95,6 +192,11 @@ int main(int argc, char** argv)
     launch(nblk, [&] { k_iter_resid(b, q, r, n, tp, sc, 1, part); });
     launch(1, [&] { k_iter_step_v(part, nblk, tp, 1, sc); });
     launch(1, [&] { k_iter_sum(part, nblk, tp, sums); });
+    // the mixed mode's fall back, on copies: the unfinished columns start again, the finished and the broken ones stay
+    double *x2 = blk(cnt), *r2 = blk(cnt), *sc2 = blk(SC_ROWS * IT_MAXT);
+    memcpy(x2, x, cnt * 8); memcpy(r2, r, cnt * 8); memcpy(sc2, sc, SC_ROWS * IT_MAXT * 8);
+    launch(nblk, [&] { k_iter_again(b, x2, r2, n, tp, sc2); });
+    launch(1, [&] { k_iter_again_sc(tp, sc2); });
     // the same sweep, column by column
     std::vector<double> rx(cnt), rr(cnt), rp(cnt), rs(SC_ROWS * IT_MAXT, 0.0);
     bool ok = true;
@@ -151,14 +253,29 @@ int main(int argc, char** argv)
         for (int row = 0; row < SC_ROWS; row++) ok = ok && same_bits(sc + row * IT_MAXT + c, &at(row), 1, "scalar");
     }
     ok = ok && same_bits(x, rx.data(), cnt, "x") && same_bits(r, rr.data(), cnt, "r") && same_bits(p, rp.data(), cnt, "p");
+    int again = 0;
+    for (int c = 0; c < tp; c++) {
+        auto at = [&](int row) -> double& { return rs[row * IT_MAXT + c]; };
+        if (at(SC_STATE) != ST_ACTIVE && at(SC_STATE) != ST_RESTART) continue;
+        for (int i = 0; i < n; i++) { rx[(size_t)i * tp + c] = 0.0; rr[(size_t)i * tp + c] = b[(size_t)i * tp + c]; }
+        at(SC_RR) = at(SC_TRUE) = at(SC_BB);
+        at(SC_STATE) = ST_RESTART;
+        again++;
+    }
+    ok = ok && same_bits(x2, rx.data(), cnt, "x again") && same_bits(r2, rr.data(), cnt, "r again");
+    for (int row = 0; row < SC_ROWS; row++) ok = ok && same_bits(sc2 + row * IT_MAXT, rs.data() + row * IT_MAXT, tp, "scalar again");
+    ok = ok && (n == 1 || again > 0);
     ok = check_rhs<false, KERNEL_SE>(X, n, d, Xt, count, tp, hdw, Rs) && ok;
     ok = check_rhs<true, KERNEL_RQ>(X, n, d, Xt, count, tp, hdw, Rq) && ok;
+    double* scm = blk(SC_ALLOC * IT_MAXT);
+    ok = check_mixed(nblk, tp, scm) && ok;
     FILE* o = fopen(argv[2], "wb");
     for (const double* v : {x, r, p}) fwrite(v, 8, cnt, o);
     fwrite(sc, 8, SC_ROWS * IT_MAXT, o);
     fwrite(Rs, 8, cnt, o);
     fwrite(Rq, 8, cnt, o);
+    fwrite(scm, 8, SC_ALLOC * IT_MAXT, o);
     fclose(o);
-    for (double* v : {hdw, X, Xt, b, q, x, r, p, part, sc, Rs, Rq, sums}) free(v);
+    for (double* v : {hdw, X, Xt, b, q, x, r, p, part, sc, Rs, Rq, sums, scm, x2, r2, sc2}) free(v);
     return ok ? 0 : 4;
 }

@@ -4,7 +4,10 @@ built as a stand-alone program with -fsanitize=address,undefined.  The program c
 loops in the same order of summation (exit code 4 on a mismatch); this script checks the arithmetic of one sweep against
 numpy and the right-hand sides against tests/truth_rq.py's fp64 entry.  Columns: random, one zero (done at once), one NaN
 (broken), one whose q makes p'q negative (broken), and with q = b the recurrence residual vanishes after one step (a
-candidate whose true residual passes); columns 8 and up stay active and meet the closing pass.
+candidate whose true residual passes); columns 8 and up stay active and meet the closing pass.  The mixed mode's
+one-workgroup kernels (k_iter_goal_init, k_iter_step_b_mx, k_iter_step_v_mx) run two cycles and a closing pass on a table of
+the program's own, a scenario per column: the tolerance reached, the goal reached (and exactly met), r'r grown 2^20-fold, a
+stall flagged, a last leg close above the tolerance flagged and not flagged, NaN in r'r, in a true residual and in b, final = 1.
 
     python tools/iter_host_check.py          # builds into a temporary directory; about a minute
 """
@@ -62,7 +65,12 @@ def run(exe, tmp, n, tp, d, count):
     se = sf2 * np.exp(-0.5 * ((X[:, None, :] - Xt[None, :, :]) ** 2).sum(2) / 2.25)
     ok = ok and np.allclose(Rq[:, :count], want, rtol=1e-13) and np.allclose(Rs[:, :count], se, rtol=1e-13)
     ok = ok and np.all(Rq[:, count:] == 0) and np.all(Rs[:, count:] == 0) and Rq[n // 2, 0] == sf2
-    print("n %-4d tp %-2d d %-2d test points %-2d  bits equal the plain loops; one sweep and the right-hand sides against numpy  %s"
+    # the mixed mode's cycle kernels (check_mixed's table): the state and the stall flag each scenario must end in
+    scm = out[-13 * 64:].reshape(13, 64)
+    ok = ok and list(scm[4, :11]) == [2, 2, 0, 3, 3, 2, 3, 2, 4, 4, 3] and np.all(scm[4, 11:tp] == 0)
+    ok = ok and list(scm[12, :11]) == [0, 1, 1, 0, 0, 0, 0, 0, 0, 1, 0] and np.all(scm[12, 11:tp] == 0)
+    ok = ok and scm[6, 2] == 0.5 * scm[1, 2] and scm[11, 8] == 1.5 * scm[7, 8] and np.all(scm[:, tp:] == -7) and np.all(scm[8:10] == -7)
+    print("n %-4d tp %-2d d %-2d test points %-2d  bits equal the plain loops; one sweep, the right-hand sides and the mixed cycles against numpy  %s"
           % (n, tp, d, count, "ok" if ok else "BAD"))
     return bool(ok)
 

@@ -21,6 +21,15 @@ apply at t = 16 and t = 64 (tp = 16 | 64), medians of --reps calls after a warm-
 1e-8: SINGLE calls without a warm-up.  --kernel-stats DIR adds the device times of k_cov_grad* and k_cov_apply* from the
 *kernel_stats.csv files a separate `rocprofv3 --kernel-trace --stats -d DIR -- python tools/iter_probe.py --grad --forms-only`
 left there (average per launch, the warm-up launch included), as covariance entries per second.
+
+--precision: instead of the above, the mixed mode -> profiles/iter_mixed_probe.json.  Per family:
+apply(precision="fp32") beside apply at t = 1, 16 and 64, alternating in one process, medians of --reps calls after a
+warm-up call each (wall time with the host's packing); fit at tol 1e-8 in the fp64 and in the mixed mode with solve_stats
+(SINGLE calls; the fp64 one pays the first-use allocations).  --applies-only: the products alone, nothing written (for a
+kernel trace; --ts 16 64 there, so that the 16-column kernels' averages are those of t = 16); --kernel-stats DIR adds the
+device times of k_cov_apply* and their fp64 / fp32 ratios from the *kernel_stats.csv files a separate
+`rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/iter_probe.py --precision --applies-only --ts 16 64` left
+there (-f csv: rocprofv3's default output is a rocpd database, which kernel_stats does not read).
 """
 import argparse
 import json
@@ -146,8 +155,61 @@ def grad_probe(a):
     print(json.dumps(res))
 
 
+def precision_probe(a):
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": D, "reps": a.reps, "tol": 1e-8, "families": {}}
+    X, y = synth(a.n, d=D)
+    rng = np.random.default_rng(0)
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        r = {"plan": g.plan(a.n, a.n), "apply": {}}
+        for t in a.ts:
+            V = rng.standard_normal((t, a.n))
+            g.apply(V), g.apply(V, precision="fp32")
+            t64, t32 = [], []
+            for _ in range(a.reps):
+                for ts, prec in ((t64, "fp64"), (t32, "fp32")):
+                    t0 = time.perf_counter()
+                    g.apply(V, precision=prec)
+                    ts.append(time.perf_counter() - t0)
+            s64, s32 = float(np.median(t64)), float(np.median(t32))
+            r["apply"][str(t)] = {"fp64_seconds": s64, "fp32_seconds": s32, "ratio": s64 / s32}
+            print(fam, "t", t, r["apply"][str(t)], flush=True)
+        if not a.applies_only:
+            for mode in ("fp64", "mixed"):
+                g.set_precision(mode)
+                t0 = time.perf_counter()
+                fi = g.fit(1e-8, 4000, 10)
+                r["fit_" + mode] = {"seconds": time.perf_counter() - t0, "sweeps": fi[0], "residual": fi[1], "converged": fi[2],
+                                    "stats": g.solve_stats()}
+                print(fam, mode, r["fit_" + mode], flush=True)
+            r["fit_ratio"] = r["fit_fp64"]["seconds"] / r["fit_mixed"]["seconds"]
+        g.close()
+        res["families"][fam] = r
+    if a.applies_only:
+        return
+    res["not_measured"] = ["counters", "the variance and loglik_grad in the mixed mode", "d > 16", "other families than SE and RQ-ARD",
+                           "cycle_drop other than the default"]
+    if a.kernel_stats:
+        res["kernels"] = ks = kernel_stats(a.kernel_stats, a.n)
+        # k_cov_apply32<...> beside k_cov_apply<...> of the same instantiation: device time fp64 / fp32, the warm-up launch included
+        twin = {k: k.replace("k_cov_apply4", "k_cov_apply32_4").replace("k_cov_apply<", "k_cov_apply32<") for k in ks if "apply32" not in k}
+        res["kernel_ratios"] = {k: ks[k]["average_seconds"] / ks[t]["average_seconds"] for k, t in twin.items() if t in ks}
+    else:
+        res["not_measured"].insert(0, "device times of the two product kernels (no --kernel-stats): the ratios are wall times "
+                                      "with the host's packing and copies")
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_mixed_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", action="store_true", help="the mixed-mode probe (its own mode)")
+    ap.add_argument("--applies-only", action="store_true", help="... the products alone, nothing written (for a kernel trace)")
+    ap.add_argument("--ts", type=int, nargs="+", default=[1, 16, 64], help="... the products' column counts")
     ap.add_argument("--grad", action="store_true", help="the gradient probe (its own mode)")
     ap.add_argument("--forms-only", action="store_true", help="... grad_forms and apply alone, nothing written (for a kernel trace)")
     ap.add_argument("--kernel-stats", default=None, help="... a directory with rocprofv3's kernel statistics of such a run")
@@ -164,6 +226,8 @@ def main():
         return precond_probe(a)
     if a.grad:
         return grad_probe(a)
+    if a.precision:
+        return precision_probe(a)
     res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "nt": a.nt, "ntvar": a.ntvar, "d": D, "reps": a.reps, "families": {}}
     X, y = synth(a.n, d=D)
     Xt = synth(a.nt, d=D, seed=7)[0]
