@@ -223,6 +223,9 @@ SIGNATURES = {
     "cugp_iter_set_precision": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
     "cugp_iter_apply32": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp]),
     "cugp_iter_solve_stats": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_iter_input_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, C.c_int, _dp]),
+    "cugp_iter_predict_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_int, C.c_int,
+                                         _dp]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

@@ -28,6 +28,7 @@ struct cugp_iter {
     double cycle_drop = CUGP_ITER_CYCLE_DROP;
     int stats[4] = {0, 0, 0, 0};   // fp32 products, fp64 products, verifications, fell back: the last solving call's
     Scratch vb, vx, vr, vp, vq, vk, alpha, apart, dpart, xt, res;
+    Scratch xpart, xout;           // the test-input gradients: k_cov_xgrad's partial sums; dmean, dvar [nt][d]
     Scratch gpart, gout, ghost;    // the gradient forms: k_cov_grad's partial rows; their sums and the
                                    // columns' u'v behind them; the pinned copy of those
     std::vector<double> host;      // packing: [t][n] target-major <-> [n][tp]
@@ -342,6 +343,42 @@ int grad_dims(const cugp_iter* h, const char* call)
     return CUGP_OK;
 }
 
+// the launch grid's third dimension is the feature chunk of k_cov_xgrad's sums, for every family
+int xgrad_dims(const cugp_iter* h, const char* call)
+{
+    if ((h->d + 15) / 16 > 65535) return invalid_arg(call, "more than 65535 * 16 input dimensions");
+    return CUGP_OK;
+}
+
+// Xt [nt][d] into h->xt, and h->xout grown to `blocks` result blocks of nt * d
+int xgrad_inputs(cugp_iter* h, const double* Xt, int nt, int blocks)
+{
+    int rc;
+    if ((rc = h->xt.grow((size_t)nt * h->d, h->stream)) || (rc = h->xout.grow((size_t)blocks * nt * h->d, h->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(h->xt.p, Xt, (size_t)nt * h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CUGP_OK;
+}
+
+// One k_cov_xgrad launch with its finish on the handle's stream, for the cnt test rows from row c0 of h->xt.  Wv null: the
+// mean form over wm into outm, any cnt; else cnt <= tp rows against the columns of Wv [n][tp] into outv (and wm into outm)
+int xgrad_dev(cugp_iter* h, const CovFn& cf, int c0, int cnt, const double* wm, const double* Wv, int tp, double* outm,
+              double* outv, double fv)
+{
+    const IterPlan pl = iter_apply_plan(cnt, h->n, h->split);
+    if (const int rc = h->xpart.grow((size_t)pl.split * (Wv ? 2 : 1) * cnt * h->d, h->stream)) return rc;
+    launch_cov_xgrad(h->xt.p + (size_t)c0 * h->d, cnt, h->dX, h->n, h->d, cf, wm, Wv, tp, h->xpart.p, outm, outv, fv, pl, h->stream);
+    return CUGP_OK;
+}
+
+// the device block src [nt][d] -> the caller's array (null: nothing); the stream is waited for
+int xgrad_fetch(cugp_iter* h, const double* src, int nt, double* dst)
+{
+    if (dst) HIPCHK(hipMemcpyAsync(dst, src, (size_t)nt * h->d * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return CUGP_OK;
+}
+
 int plan_out(const char* call, int na, int nb, int t, int split, int out[4])
 {
     if (!out) return invalid_arg(call, "out is NULL");
@@ -404,7 +441,7 @@ int cugp_iter_destroy(cugp_iter* h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res, &h->pL,
-                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost})
+                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost, &h->xpart, &h->xout})
         v->release();
     if (h->pf) cugp_destroy(h->pf);
     for (void* p : {(void*)h->dX, (void*)h->dyb, (void*)h->dhs, (void*)h->dsc})
@@ -759,4 +796,90 @@ int cugp_iter_predict(cugp_iter* h, const double* Xt, int nt, double* mean, doub
         for (int c = 0; c < cnt; c++) var[c0 + c] = prior - hsum[c];
     }
     return CUGP_OK;
+}
+
+int cugp_iter_input_grad(cugp_iter* h, const double* Xt, int nt, const double* W, int t, double* out)
+{
+    const char* call = "cugp_iter_input_grad";
+    if (!h || !Xt || !W || !out) return invalid_arg(call, "null argument");
+    if (nt < 1) return invalid_arg(call, "nt must be positive");
+    if (nt > CUGP_ITER_MAX_N) return invalid_arg(call, "nt beyond CUGP_ITER_MAX_N");
+    if (t != 1 && t != nt) return invalid_arg(call, "t must be 1 (one weight vector for every test point) or nt (one per test point)");
+    int rc;
+    if ((rc = ready(h, call)) || (rc = xgrad_dims(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    if ((rc = xgrad_inputs(h, Xt, nt, 1))) return rc;
+    if (t == 1) {
+        if ((rc = pack(h, W, h->n, 0, 1, 16, h->vb)) || (rc = xgrad_dev(h, cf, 0, nt, h->vb.p, nullptr, 16, h->xout.p, nullptr, 0.0)))
+            return rc;
+    } else {
+        // test point c0 + c takes column c of the batch's block: IT_MAXT points a launch, the form's sign by fv = -1
+        for (int c0 = 0; c0 < nt; c0 += IT_MAXT) {
+            const int cnt = std::min(IT_MAXT, nt - c0), tp = iter_tp(cnt);
+            if ((rc = pack(h, W, h->n, c0, cnt, tp, h->vb))) return rc;
+            if ((rc = xgrad_dev(h, cf, c0, cnt, nullptr, h->vb.p, tp, nullptr, h->xout.p + (size_t)c0 * h->d, -1.0))) return rc;
+        }
+    }
+    if ((rc = sync_or_fail(h->stream, call, hipGetLastError()))) return rc;
+    return xgrad_fetch(h, h->xout.p, nt, out);
+}
+
+int cugp_iter_predict_grad(cugp_iter* h, const double* Xt, int nt, int with_noise, double* mean, double* var, double* dmean,
+                           double* dvar, double tol, int max_iter, int check_every, double* info)
+{
+    const char* call = "cugp_iter_predict_grad";
+    if (!h || !Xt) return invalid_arg(call, "null argument");
+    if (!dmean && !dvar) return invalid_arg(call, "dmean and dvar are both NULL (cugp_iter_predict gives the mean and the variance alone)");
+    if (nt < 1) return invalid_arg(call, "nt must be positive");
+    if (nt > CUGP_ITER_MAX_N) return invalid_arg(call, "nt beyond CUGP_ITER_MAX_N");
+    const bool solve = var || dvar;
+    int rc;
+    if (solve && (rc = solver_args(call, tol, max_iter, check_every))) return rc;
+    if ((rc = ready(h, call)) || (rc = xgrad_dims(h, call))) return rc;
+    if (!h->fit_valid) return invalid_arg(call, "no fit for the data and hyper-parameters as they stand (cugp_iter_fit)");
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    hipStream_t s = h->stream;
+    const size_t nd = (size_t)nt * h->d;
+    if ((rc = xgrad_inputs(h, Xt, nt, 2))) return rc;
+    double *dm = h->xout.p, *dv = h->xout.p + nd;
+    if (mean) {                                         // cugp_iter_predict's own launches: its bits
+        if ((rc = h->res.grow((size_t)nt * 16, s))) return rc;
+        if ((rc = product(h, cf, h->xt.p, nt, h->alpha.p, 16, h->res.p, false))) return rc;
+        if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
+        if ((rc = unpack(h, h->res.p, nt, 0, 1, 16, mean))) return rc;
+    }
+    if (!solve) {                                       // the mean's gradient alone: one launch over all nt rows, no solve
+        if ((rc = xgrad_dev(h, cf, 0, nt, h->alpha.p, nullptr, 16, dm, nullptr, 0.0))) return rc;
+        if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
+        return xgrad_fetch(h, dm, nt, dmean);
+    }
+    std::fill(h->stats, h->stats + 4, 0);
+    // cugp_iter_predict's variance loop; the batch's v = K^-1 ks stay in h->vx for the gradients' one launch
+    const double prior = h->hhs->signal_var + h->hhs->noise_var;
+    double *dsum = h->dsc + (size_t)SC_ROWS * IT_MAXT, *hsum = h->hsc + (size_t)SC_ROWS * IT_MAXT;
+    for (int c0 = 0; c0 < nt; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, nt - c0), tp = iter_tp(cnt);
+        if ((rc = h->vk.grow((size_t)h->n * tp, s))) return rc;
+        launch_iter_cross_rhs(h->dX, h->n, h->d, h->xt.p + (size_t)c0 * h->d, cnt, tp, cf, h->vk.p, s);
+        if ((rc = solve_dev(h, cf, h->vk.p, tp, tol, max_iter, check_every, call))) return rc;
+        fill_info(h, c0, cnt, info);
+        if (var) {
+            launch_iter_dot(h->vk.p, h->vx.p, h->n, tp, h->dpart.p, s);
+            launch_iter_sum(h->dpart.p, h->n, tp, dsum, s);
+            hipError_t e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(hsum, dsum, (size_t)IT_MAXT * sizeof(double), hipMemcpyDeviceToHost, s);
+            if ((rc = sync_or_fail(s, call, e))) return rc;
+            for (int c = 0; c < cnt; c++) {
+                const double v = prior - hsum[c];
+                var[c0 + c] = with_noise ? v : v - h->hhs->noise_var;
+            }
+        }
+        const size_t o = (size_t)c0 * h->d;
+        if ((rc = xgrad_dev(h, cf, c0, cnt, h->alpha.p, h->vx.p, tp, dmean ? dm + o : nullptr, dvar ? dv + o : nullptr, 2.0))) return rc;
+    }
+    if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
+    if ((rc = xgrad_fetch(h, dm, nt, dmean))) return rc;
+    return xgrad_fetch(h, dv, nt, dvar);
 }

@@ -461,6 +461,25 @@ void launch_cov_grad(const double* X, int n, int d, const CovFn& cf, const doubl
     hipLaunchKernelGGL(k_cov_grad_finish, dim3((nc + 255) / 256), dim3(256), 0, s, part, (size_t)pl.row_blocks * pl.split, nc, out);
 }
 
+// ---- the test-input gradients (iter_xgrad_device.h) ----
+// k_cov_xgrad<ARD, KIND, VAR> under CUGP_COV_KERNEL's two-parameter table: the mean-only and the mean-and-variance forms
+template <bool ARD, int KIND> constexpr auto k_cov_xgrad_mean = k_cov_xgrad<ARD, KIND, false>;
+template <bool ARD, int KIND> constexpr auto k_cov_xgrad_var = k_cov_xgrad<ARD, KIND, true>;
+
+void launch_cov_xgrad(const double* Xt, int nt, const double* X, int n, int d, const CovFn& cf, const double* wm, const double* Wv,
+                      int tp, double* part, double* outm, double* outv, double fv, const IterPlan& pl, hipStream_t s)
+{
+    const bool var = Wv != nullptr;
+    const int nz = (d + DC - 1) / DC, nq = var ? 2 : 1;
+    assert(cf.hd && nz <= 65535 && (var ? pl.row_blocks == 1 && nt <= tp && (tp == 16 || tp == IT_MAXT) : wm && !outv));
+    auto kern = var ? CUGP_COV_KERNEL(cf, k_cov_xgrad_var) : CUGP_COV_KERNEL(cf, k_cov_xgrad_mean);
+    hipLaunchKernelGGL(kern, dim3(pl.row_blocks, pl.split, nz), dim3(256), 0, s, Xt, nt, X, n, d, cf.hd, wm, Wv, var ? tp : 16, part,
+                       pl.per);
+    const size_t cnt = (size_t)nt * d;
+    hipLaunchKernelGGL(k_cov_xgrad_finish, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s, part, pl.split, nq, cnt, d, cf.hd,
+                       is_ard(cf) ? 1 : 0, fv, outm, outv);
+}
+
 void launch_iter_cross_rhs(const double* X, int n, int d, const double* Xt, int count, int tp, const CovFn& cf, double* R,
                            hipStream_t s)
 {

@@ -447,6 +447,13 @@ void launch_cov_apply(const double* A, int na, const double* B, int nb, int d, c
 inline int cov_grad_columns(const CovFn& cf, int d) { return cf.ard ? d + shape_count(cf.kind) + 1 : 2; }
 void launch_cov_grad(const double* X, int n, int d, const CovFn& cf, const double* U, const double* V, int tp, double* part,
                      double* out, const IterPlan& pl, hipStream_t s);
+// The test-input gradients (k_cov_xgrad, iter_xgrad_device.h), i < nt, a < d, dk_ij / dx*_ia of k(xt_i, x_j):
+//   outm[i][a] = sum_j wm[j] dk_ij / dx*_ia,  wm column 0 of an [n][16] block (null: outm must be null too);
+//   outv[i][a] = -fv sum_j Wv[j][i] dk_ij / dx*_ia,  Wv [n][tp], tp = 16 | 64 >= nt: one row block (null: the mean form alone, any nt).
+// fv = 2: the variance's gradient for Wv's columns K^-1 k*; fv = -1: the plain form.  pl = iter_apply_plan(nt, n, .);
+// part: pl.split * (Wv ? 2 : 1) * nt * d doubles, the ranges' partial sums, added in range order by a second launch
+void launch_cov_xgrad(const double* Xt, int nt, const double* X, int n, int d, const CovFn& cf, const double* wm, const double* Wv,
+                      int tp, double* part, double* outm, double* outv, double fv, const IterPlan& pl, hipStream_t s);
 // R[j][c] = k(x_j, xt_c), c < count <= tp, zero columns beyond
 void launch_iter_cross_rhs(const double* X, int n, int d, const double* Xt, int count, int tp, const CovFn& cf, double* R,
                            hipStream_t s);

@@ -230,8 +230,10 @@ static void set_big_lds();
 // the matrix-free exact GP (cugp_iter_*): k_iter_dot .. k_iter_poison, the t conjugate-gradient recurrences, and
 // k_iter_cross_rhs (emulable)
 #include "iter_device.h"
+// k_cov_xgrad, k_cov_xgrad_finish: the sums of dk / dx* over all n rows behind the test-input gradients (emulable; no MFMA)
+#include "iter_xgrad_device.h"
 // k_cov_apply, k_cov_apply4 (K V with K in registers: the entry is the MFMA's A operand), k_cov_apply_finish, iter_apply_plan
-// and the launchers of these and of the emulable header above
+// and the launchers of these and of the two emulable headers above
 #include "iter_gfx950.h"
 // k_cov_apply32, k_cov_apply32_4 (the mixed mode's product: fp32 entries and MFMA, folded into fp64 every 128 terms),
 // kernel_value32 and launch_cov_apply32

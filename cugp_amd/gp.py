@@ -862,6 +862,33 @@ class IterativeGP:
                                            int(check_every), ptr(info) if var else None))
         return mean, v, info
 
+    def input_grad(self, Xt, W):
+        """[nt, d]: sum_j W[col(i), j] dk(xt_i, x_j) / dxt_i over all n rows (cugp_iter_input_grad) for W [t, n]: t == 1, one
+        weight vector for every test point; t == nt, test point i takes row i.  Needs data and hyper-parameters, no fit."""
+        Xt, W = f64(Xt).reshape(-1, self.d), self._block(W)
+        nt = Xt.shape[0]
+        if W.shape[0] not in (1, nt):
+            raise ValueError("expected weights [1, %d] or [%d, %d]" % (self.n, nt, self.n))
+        out = np.empty((nt, self.d))
+        check(capi.lib().cugp_iter_input_grad(self._h, ptr(Xt), nt, ptr(W), W.shape[0], ptr(out)))
+        return out
+
+    def predict_grad(self, Xt, with_noise=True, want_var=True, want_var_grad=True, tol=1e-10, max_iter=1000, check_every=10):
+        """(mean [nt], var [nt], dmean [nt, d], dvar [nt, d], info [nt, 4]): the prediction and its gradients with respect to
+        the test inputs (cugp_iter_predict_grad).  mean / var carry predict's bits (with_noise=False: var - sn2);
+        want_var=False / want_var_grad=False put None there; both False: no solve, info is None."""
+        Xt = f64(Xt).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        solve = want_var or want_var_grad
+        mean, dm = np.empty(nt), np.empty((nt, self.d))
+        v = np.empty(nt) if want_var else None
+        dv = np.empty((nt, self.d)) if want_var_grad else None
+        info = np.empty((nt, 4)) if solve else None
+        check(capi.lib().cugp_iter_predict_grad(self._h, ptr(Xt), nt, 1 if with_noise else 0, ptr(mean),
+                                                ptr(v) if want_var else None, ptr(dm), ptr(dv) if want_var_grad else None,
+                                                float(tol), int(max_iter), int(check_every), ptr(info) if solve else None))
+        return mean, v, dm, dv, info
+
     def set_precond(self, rank):
         """Ask for a pivoted-Cholesky preconditioner of that rank for solve / fit / predict (0: none, the default).  Built by
         the next call that needs it, and again after set_data, set_loghyper or another set_precond."""

@@ -1010,6 +1010,30 @@ int cugp_iter_precond_plan(int n, int rank, int out[4]);
 int cugp_iter_set_precision(cugp_iter *h, int mode, double cycle_drop);
 int cugp_iter_apply32(cugp_iter *h, const double *V, int t, double *out);
 int cugp_iter_solve_stats(const cugp_iter *h, int out[4]);
+/* Gradients with respect to the test inputs: the cugp_predict_grad block's formulas over ALL n rows,
+ * dk_i/dx*_c = -G_i (x*_c - x_ic) s_c, with G computed in registers (k_cov_xgrad; fp64 in either precision mode, no matrix
+ * instruction: the difference x*_c - x_ic is formed first, then multiplied).  Sums run in a fixed order: two calls give the
+ * same bits, and a test point's bits depend on (X, theta, its own x*, its own weights, the split) only -- not on nt or on
+ * the points beside it.
+ * cugp_iter_input_grad  : out [nt][d] row-major, out_ia = sum_j W[col(i)][j] dk(x*_i, x_j)/dx*_ia for W [t][n]: t == 1, one
+ *      weight vector for every test point; t == nt, test point i takes row i (64 points a launch).  Needs data and theta, no
+ *      fit: the forms call of this block, and the gradient of multi-target means from a caller's own K^-1 Y.
+ * cugp_iter_predict_grad: dmean [nt][d] = sum_i alpha_i dk_i/dx*, dvar [nt][d] = -2 sum_i v_i dk_i/dx* with v = K^-1 k*; mean,
+ *      var, dmean and dvar may each be NULL (not dmean and dvar both).  mean and var come by cugp_iter_predict's own
+ *      launches and carry its bits; with_noise == 0 returns var - sn2 (one more host subtraction from the same sf2 + sn2 -
+ *      ks' K^-1 ks), and dvar does not depend on it.  With var or dvar each batch of 64 test points is solved once, as
+ *      cugp_iter_predict solves it -- the preconditioner and the precision mode as set, info [nt][4] (may be NULL) and
+ *      cugp_iter_solve_stats as there -- and dmean and dvar of the batch come from one launch over alpha and the batch's v.
+ *      Without var and dvar there is no solve: one launch over all nt rows, tol, max_iter and check_every are not looked
+ *      at, info is not written and the counters stay as they were.
+ * Refused with CUGP_ERR_INVALID before any device call: a NULL h, Xt, W or out; dmean and dvar both NULL; nt < 1 or beyond
+ *      CUGP_ITER_MAX_N; t other than 1 and nt; more than 65535 * 16 input dimensions (every family); tol, max_iter or
+ *      check_every as in cugp_iter_predict where a solve is asked for; a call before data and theta; cugp_iter_predict_grad
+ *      without a cugp_iter_fit since the data or theta last changed. */
+int cugp_iter_input_grad(cugp_iter *h, const double *Xt, int nt, const double *W, int t, double *out);
+int cugp_iter_predict_grad(cugp_iter *h, const double *Xt, int nt, int with_noise, double *mean /* may be NULL */,
+                           double *var /* may be NULL */, double *dmean /* may be NULL */, double *dvar /* may be NULL */,
+                           double tol, int max_iter, int check_every, double *info /* may be NULL */);
 
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);

@@ -3,13 +3,15 @@
 // of exactly the library's sizes, under -fsanitize=address,undefined.  One sweep of the t recurrences -- b'b, the start, p'q
 // and the step length, the update with r'r, the ratio, the new direction, then the true-residual pass, the poisoning of
 // broken columns, the closing pass over the still-active columns and k_iter_sum -- on a q the caller supplies (the product itself needs the MFMA), and k_iter_cross_rhs for one
-// isotropic and the rational quadratic instantiation; then the mixed mode's cycle kernels (check_mixed below).  Every output is compared BIT FOR BIT with the plain loops below in
+// isotropic and the rational quadratic instantiation; then the mixed mode's cycle kernels (check_mixed below) and the test-input
+// gradients' kernel with its finish (iter_xgrad_device.h; check_xgrad below).  Every output is compared BIT FOR BIT with the plain loops below in
 // the kernels' order of summation: the 16 row classes of a workgroup each in row order, the classes ascending, the
 // workgroups ascending.  Exit code 4: a mismatch.  A stand-alone program: the sanitizer is linked in, nothing is preloaded.
 #include "host_emul.h"
 namespace cugp {
 #include "cov_device.h"
 #include "iter_device.h"
+#include "iter_xgrad_device.h"
 }
 using namespace cugp;
 
@@ -156,11 +158,89 @@ bool check_mixed(int nblk, int tp, double* sc)
     free(part);
     return same_bits(sc, rs.data(), SC_ALLOC * IT_MAXT, "mixed scalar");
 }
+
+// ---- k_cov_xgrad and its finish (iter_xgrad_device.h) on data of the program's own: ragged nt and n, d = 17 (two feature
+// chunks: blockIdx.z), two ranges (blockIdx.y), against plain loops in the kernel's stated order -- per output the four fk
+// groups each over their entries j = 32 st + 4 kk + fk in ascending order (rows beyond n as the zeros they are staged as),
+// (0 + 1) + (2 + 3), the ranges ascending, then the scale and the sign.  VAR: nt <= tp points against their own columns of Wv.
+double xg_rand(unsigned& s) { s = s * 1664525u + 1013904223u; return (double)(s >> 8) / 8388608.0 - 1.0; }
+template <bool ARD, int KIND, bool VAR>
+bool check_xgrad(int nt, int n, int d, int tp, int split, const char* what)
+{
+    unsigned seed = 12345u + nt + n;
+    auto blk = [&](size_t c) { double* p = (double*)malloc(c * 8); for (size_t i = 0; i < c; i++) p[i] = xg_rand(seed); return p; };
+    double *Xt = blk((size_t)nt * d), *X = blk((size_t)n * d), *wm = blk((size_t)n * 16), *Wv = blk((size_t)n * tp), *hdw = blk(3 + d + 2);
+    hdw[0] = ARD ? 1.0 : 2.25; hdw[1] = 1.5; hdw[2] = 0.2;
+    for (int c = 0; c < d + 2; c++) hdw[3 + c] = 0.6 + 0.4 * std::fabs(hdw[3 + c]);
+    hdw[3 + d + 1] = 0.5 / hdw[3 + d];
+    for (int c = 0; c < d; c++) Xt[c] = X[(size_t)(n / 2) * d + c];          // one test point on a training point
+    const int nq = VAR ? 2 : 1, nst = (n + ITER_JT - 1) / ITER_JT, per = (nst + split - 1) / split, nz = (d + DC - 1) / DC;
+    const int row_blocks = (nt + ITER_ROWS - 1) / ITER_ROWS;
+    const size_t cnt = (size_t)nt * d;
+    double *part = blk((size_t)split * nq * cnt), *om = blk(cnt), *ov = blk(cnt);
+    const HyperScalars* hd = (const HyperScalars*)hdw;
+    gridDim.y = split; gridDim.z = nz;
+    for (int s = 0; s < split; s++)
+        for (int z = 0; z < nz; z++) {
+            blockIdx.y = s; blockIdx.z = z;
+            launch(row_blocks, [&] { k_cov_xgrad<ARD, KIND, VAR>(Xt, nt, X, n, d, hd, wm, VAR ? Wv : nullptr, tp, part, per); });
+        }
+    blockIdx.y = blockIdx.z = 0; gridDim.y = gridDim.z = 1;
+    launch((int)((cnt + 255) / 256), [&] { k_cov_xgrad_finish(part, split, nq, cnt, d, hd, ARD ? 1 : 0, 2.0, om, VAR ? ov : nullptr); });
+    std::vector<double> rm(cnt), rv(cnt);
+    const double* w = hdw + 3;
+    const DivBy dl = div_prepare(hdw[0]);
+    const ShapeArgs sh{w[d], w[d + 1]};
+    for (int i = 0; i < nt; i++)
+        for (int a = 0; a < d; a++) {
+            double tm = 0.0, tv = 0.0;
+            for (int s = 0; s < split; s++) {
+                double gm[4], gv[4];
+                for (int fk = 0; fk < 4; fk++) {
+                    gm[fk] = gv[fk] = 0.0;
+                    for (int st = s * per; st < std::min((s + 1) * per, nst); st++)
+                        for (int kk = 0; kk < ITER_JT / 4; kk++) {
+                            const int j = st * ITER_JT + 4 * kk + fk;
+                            double sq = 0.0;
+                            for (int f = 0; f < d; f++) {
+                                double df = Xt[(size_t)i * d + f] - (j < n ? X[(size_t)j * d + f] : 0.0);
+                                if (ARD) df = df * w[f];
+                                sq = sq + df * df;
+                            }
+                            const double g = xgrad_factor<ARD, KIND>(sq, dl, hdw[1], sh);
+                            const double df = Xt[(size_t)i * d + a] - (j < n ? X[(size_t)j * d + a] : 0.0);
+                            gm[fk] = gm[fk] + (g * (j < n ? wm[(size_t)j * 16] : 0.0)) * df;
+                            if (VAR) gv[fk] = gv[fk] + (g * (j < n ? Wv[(size_t)j * tp + i] : 0.0)) * df;
+                        }
+                }
+                const double pm = (gm[0] + gm[1]) + (gm[2] + gm[3]), pv = (gv[0] + gv[1]) + (gv[2] + gv[3]);
+                tm = s == 0 ? pm : tm + pm;
+                tv = s == 0 ? pv : tv + pv;
+            }
+            const double sc = ARD ? w[a] * w[a] : 1.0 / hdw[0];
+            rm[(size_t)i * d + a] = -(sc * tm);
+            rv[(size_t)i * d + a] = (2.0 * sc) * tv;
+        }
+    bool ok = same_bits(om, rm.data(), cnt, what) && (!VAR || same_bits(ov, rv.data(), cnt, what));
+    double big = 0.0;
+    for (size_t e = 0; e < cnt; e++) big = std::max(big, std::fabs(om[e]));
+    ok = ok && big > 0.0;                                                    // (not a comparison of zeros)
+    for (double* v : {Xt, X, wm, Wv, hdw, part, om, ov}) free(v);
+    return ok;
+}
 }  // namespace
 
 int main(int argc, char** argv)
 {
     // input: ints n tp d count, doubles hd[3 + d + 2] X[n d] Xt[count d] b[n tp] q[n tp] -> output: x r p sc R_se R_rq
+    // `--xgrad` (a mode of its own: the data is the program's, no files): k_cov_xgrad and its finish, (nt, n, d, tp, split)
+    if (argc == 2 && strcmp(argv[1], "--xgrad") == 0) {
+        bool ok = check_xgrad<true, KERNEL_RQ, true>(21, 77, 17, 64, 2, "xgrad rq var");
+        ok = check_xgrad<true, KERNEL_MATERN32, true>(17, 40, 3, 64, 1, "xgrad matern32 ard var") && ok;
+        ok = check_xgrad<false, KERNEL_MATERN52, true>(5, 33, 3, 16, 1, "xgrad matern52 var") && ok;
+        ok = check_xgrad<false, KERNEL_SE, false>(70, 77, 17, 16, 2, "xgrad se mean") && ok;
+        return ok ? 0 : 4;
+    }
     if (argc < 3) return 2;
     FILE* f = fopen(argv[1], "rb");
     int hdr[4];

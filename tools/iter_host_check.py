@@ -8,6 +8,8 @@ candidate whose true residual passes); columns 8 and up stay active and meet the
 one-workgroup kernels (k_iter_goal_init, k_iter_step_b_mx, k_iter_step_v_mx) run two cycles and a closing pass on a table of
 the program's own, a scenario per column: the tolerance reached, the goal reached (and exactly met), r'r grown 2^20-fold, a
 stall flagged, a last leg close above the tolerance flagged and not flagged, NaN in r'r, in a true residual and in b, final = 1.
+k_cov_xgrad and k_cov_xgrad_finish (iter_xgrad_device.h) run once, on data of the program's own: ragged nt and n, d = 17, two
+ranges, the mean-and-variance and the mean-only forms, bit for bit against plain loops in the kernel's order of summation.
 
     python tools/iter_host_check.py          # builds into a temporary directory; about a minute
 """
@@ -20,10 +22,21 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-CASES = ((1, 16, 3, 1), (65, 16, 3, 5), (513, 16, 17, 16), (1100, 64, 3, 33))      # (n, tp, d, test points)
+XGRAD = ("--xgrad",)                 # the program's mode of its own for k_cov_xgrad: no input file
+CASES = ((1, 16, 3, 1), (65, 16, 3, 5), (513, 16, 17, 16), (1100, 64, 3, 33), XGRAD)      # (n, tp, d, test points)
 
 
-def run(exe, tmp, n, tp, d, count):
+def run_xgrad(exe):
+    import subprocess
+    r = subprocess.run([exe, XGRAD[0]], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    ok = r.returncode == 0 and not r.stderr.strip()
+    print("k_cov_xgrad, four instantiations: bits equal the plain loops  %s" % ("ok" if ok else "BAD"), r.stdout[-2000:], r.stderr[-3000:])
+    return ok
+
+
+def run(exe, tmp, n, tp=0, d=0, count=0):
+    if n == XGRAD[0]:
+        return run_xgrad(exe)
     import truth_ard_matern as tam
     import truth_rq as trq
     rng = np.random.default_rng(n + tp)

@@ -30,6 +30,15 @@ kernel trace; --ts 16 64 there, so that the 16-column kernels' averages are thos
 device times of k_cov_apply* and their fp64 / fp32 ratios from the *kernel_stats.csv files a separate
 `rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/iter_probe.py --precision --applies-only --ts 16 64` left
 there (-f csv: rocprofv3's default output is a rocpd database, which kernel_stats does not read).
+
+--xgrad: instead of the above, the test-input gradients -> profiles/iter_xgrad_probe.json.  Per family:
+input_grad at 64 test points with a weight vector each (one mean-and-variance launch of k_cov_xgrad), input_grad at --nt
+points with one weight vector (one mean-only launch) and apply at t = 16 beside them: medians of --reps calls after a warm-up
+call, wall time with the host's packing; then fit and predict_grad at 64 points at tol 1e-8 beside predict's variance there
+(SINGLE calls).  --launches-only: the three launches alone, nothing written (for a kernel trace, with --reps 12 or more);
+--kernel-stats DIR adds the device times of k_cov_xgrad* and k_cov_apply* from such a trace's *kernel_trace.csv: per kernel the
+median, smallest and largest of its launches with the FIRST one (the warm-up call's) dropped, and covariance entries per
+second from the median -- the common unit: each kernel computes one entry per (i, j).
 """
 import argparse
 import json
@@ -112,6 +121,30 @@ def kernel_stats(root, n):
                     avg = float(row["AverageNs"]) * 1e-9
                     out[name.replace("cugp::", "").split("(")[0].replace("void ", "")] = {
                         "calls": int(row["Calls"]), "average_seconds": avg, "entries_per_s": float(n) * n / avg}
+    return out
+
+
+def kernel_trace_times(root, entries):
+    """{kernel: {timed_launches, median_seconds, min_seconds, max_seconds, entries_per_s}} of the k_cov_xgrad* / k_cov_apply*
+    dispatches in rocprofv3's kernel trace, each kernel's FIRST launch (the warm-up call's) dropped; entries: kernel name ->
+    the entries one launch computes; entries_per_s from the median"""
+    import csv
+    import glob
+    runs = {}
+    for path in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                name = row.get("Kernel_Name", "")
+                if ("k_cov_xgrad" in name or "k_cov_apply" in name) and "finish" not in name:
+                    short = name.replace("cugp::", "").split("(")[0].replace("void ", "")
+                    runs.setdefault(short, []).append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
+    out = {}
+    for short, r in runs.items():
+        secs = [(e - s) * 1e-9 for s, e in sorted(r)[1:]]
+        if secs:
+            med = float(np.median(secs))
+            out[short] = {"timed_launches": len(secs), "median_seconds": med, "min_seconds": min(secs), "max_seconds": max(secs),
+                          "entries_per_s": entries(short) / med}
     return out
 
 
@@ -205,8 +238,57 @@ def precision_probe(a):
     print(json.dumps(res))
 
 
+def xgrad_probe(a):
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": D, "nt": a.nt, "reps": a.reps, "tol": 1e-8, "families": {}}
+    X, y = synth(a.n, d=D)
+    Xt = synth(a.nt, d=D, seed=7)[0]
+    rng = np.random.default_rng(0)
+    W, V = rng.standard_normal((64, a.n)), rng.standard_normal((16, a.n))
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        r = {"plan_var": g.plan(64, a.n), "plan_mean": g.plan(a.nt, a.n), "plan_apply": g.plan(a.n, a.n)}
+        for key, fn, ent in (("var_nt64", lambda: g.input_grad(Xt[:64], W), 64.0 * a.n),
+                             ("mean_nt%d" % a.nt, lambda: g.input_grad(Xt, W[:1]), float(a.nt) * a.n),
+                             ("apply_t16", lambda: g.apply(V), float(a.n) * a.n)):
+            sec = timed(fn, a.reps)[0]
+            r[key] = {"seconds": sec, "entries_per_s": ent / sec}
+        print(fam, r, flush=True)
+        if not a.launches_only:
+            t0 = time.perf_counter()
+            fi = g.fit(1e-8, 2000, 10)
+            r["fit"] = {"seconds": time.perf_counter() - t0, "sweeps": fi[0], "converged": fi[2]}
+            for key, fn in (("predict_var_nt64", lambda: g.predict(Xt[:64], True, 1e-8, 2000, 10)[2]),
+                            ("predict_grad_nt64", lambda: g.predict_grad(Xt[:64], tol=1e-8, max_iter=2000, check_every=10)[4]),
+                            ("predict_grad_mean_only_nt%d" % a.nt, lambda: g.predict_grad(Xt, want_var=False, want_var_grad=False)[4])):
+                t0 = time.perf_counter()
+                info = fn()
+                r[key] = {"seconds": time.perf_counter() - t0}
+                if info is not None:
+                    r[key].update(sweeps_max=float(info[:, 0].max()), converged=float(info[:, 2].min()), stats=g.solve_stats())
+            print(fam, {k: v for k, v in r.items() if k.startswith(("fit", "predict"))}, flush=True)
+        g.close()
+        res["families"][fam] = r
+    if a.launches_only:
+        return
+    if a.kernel_stats:
+        # (the trace holds three launch shapes: the kernel's name tells them apart)
+        res["kernels"] = kernel_trace_times(a.kernel_stats, lambda k: (float(a.n) * a.n if "apply" in k else 64.0 * a.n
+                                                                      if k.endswith("true>") else float(a.nt) * a.n))
+    res["single_unwarmed_calls"] = ["fit", "predict_var_nt64", "predict_grad_nt64", "predict_grad_mean_only_nt%d" % a.nt]
+    res["not_measured"] = ["counters", "d > 16 (the feature-chunk grid dimension)", "other families than SE and RQ-ARD",
+                           "forced splits"] + ([] if a.kernel_stats else ["device times (no --kernel-stats): wall times with the host's packing"])
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_xgrad_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--xgrad", action="store_true", help="the test-input gradients' probe (its own mode)")
+    ap.add_argument("--launches-only", action="store_true", help="... the three launches alone, nothing written (for a kernel trace)")
     ap.add_argument("--precision", action="store_true", help="the mixed-mode probe (its own mode)")
     ap.add_argument("--applies-only", action="store_true", help="... the products alone, nothing written (for a kernel trace)")
     ap.add_argument("--ts", type=int, nargs="+", default=[1, 16, 64], help="... the products' column counts")
@@ -228,6 +310,8 @@ def main():
         return grad_probe(a)
     if a.precision:
         return precision_probe(a)
+    if a.xgrad:
+        return xgrad_probe(a)
     res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "nt": a.nt, "ntvar": a.ntvar, "d": D, "reps": a.reps, "families": {}}
     X, y = synth(a.n, d=D)
     Xt = synth(a.nt, d=D, seed=7)[0]
