@@ -31,6 +31,8 @@ struct cugp_iter {
     Scratch xpart, xout;           // the test-input gradients: k_cov_xgrad's partial sums; dmean, dvar [nt][d]
     Scratch gpart, gout, ghost;    // the gradient forms: k_cov_grad's partial rows; their sums and the
                                    // columns' u'v behind them; the pinned copy of those
+    Scratch fom, fb, forg, fw, fout;   // the pathwise draws: Omega [m][d], b [m], the origin [d], W [m][tp];
+                                   // Phi W [nq][tp]
     std::vector<double> host;      // packing: [t][n] target-major <-> [n][tp]
     // the preconditioner (cugp_iter_set_precond): M = L L' + sn2 I from a pivoted Cholesky factor of Kf
     int pc_rank = 0, pc_got = 0, pc_rp = 0;       // asked for, achieved, padded (pc_plan)
@@ -379,6 +381,43 @@ int xgrad_fetch(cugp_iter* h, const double* src, int nt, double* dst)
     return CUGP_OK;
 }
 
+// the refusals the three calls of the pathwise draws share (before any device work)
+int features_args(const cugp_iter* h, const char* call, const double* Omega, const double* b, int m, const double* W, int s)
+{
+    if (!h || !Omega || !b || !W) return invalid_arg(call, "null argument");
+    if (s < 1 || s > IT_MAXT) return invalid_arg(call, "s must lie in [1, 64]");
+    if (m < 1) return invalid_arg(call, "m must be positive");
+    if (m > CUGP_ITER_MAX_N) return invalid_arg(call, "m beyond CUGP_ITER_MAX_N");
+    return ready(h, call);
+}
+
+// Omega [m][d], b [m], the origin [d] (null: zeros) and W [s][m] as [m][tp] into the handle's feature buffers
+int features_stage(cugp_iter* h, const double* Omega, const double* b, int m, const double* W, int s, int tp, const double* origin)
+{
+    hipStream_t st = h->stream;
+    const size_t d = h->d;
+    int rc;
+    if ((rc = h->fom.grow((size_t)m * d, st)) || (rc = h->fb.grow(m, st)) || (rc = h->forg.grow(d, st))) return rc;
+    HIPCHK(hipMemcpyAsync(h->fom.p, Omega, (size_t)m * d * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(h->fb.p, b, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+    const std::vector<double> zero(origin ? 0 : d, 0.0);
+    HIPCHK(hipMemcpyAsync(h->forg.p, origin ? origin : zero.data(), d * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return pack(h, W, m, 0, s, tp, h->fw);
+}
+
+// h->fout [nq][tp] = Phi(A) W for the staged features on the handle's stream; always fp64
+int features_dev(cugp_iter* h, const CovFn& cf, const double* A, int nq, int m, int tp)
+{
+    const IterPlan pl = rff_apply_plan(nq, m, h->split);
+    int rc;
+    if ((rc = h->fout.grow((size_t)nq * tp, h->stream))) return rc;
+    if (pl.split > 1 && (rc = h->apart.grow((size_t)pl.split * nq * tp, h->stream))) return rc;
+    const double amp = std::sqrt(2.0 * h->hhs->signal_var / (double)m);
+    launch_rff_apply(A, nq, h->d, cf, h->fom.p, h->fb.p, m, h->forg.p, h->fw.p, tp, amp, h->fout.p, h->apart.p, pl, h->stream);
+    return CUGP_OK;
+}
+
 int plan_out(const char* call, int na, int nb, int t, int split, int out[4])
 {
     if (!out) return invalid_arg(call, "out is NULL");
@@ -441,7 +480,8 @@ int cugp_iter_destroy(cugp_iter* h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res, &h->pL,
-                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost, &h->xpart, &h->xout})
+                       &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost, &h->xpart, &h->xout,
+                       &h->fom, &h->fb, &h->forg, &h->fw, &h->fout})
         v->release();
     if (h->pf) cugp_destroy(h->pf);
     for (void* p : {(void*)h->dX, (void*)h->dyb, (void*)h->dhs, (void*)h->dsc})
@@ -882,4 +922,74 @@ int cugp_iter_predict_grad(cugp_iter* h, const double* Xt, int nt, int with_nois
     if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
     if ((rc = xgrad_fetch(h, dm, nt, dmean))) return rc;
     return xgrad_fetch(h, dv, nt, dvar);
+}
+
+int cugp_iter_features_apply(cugp_iter* h, const double* Xq, int nq, const double* Omega, const double* b, int m, const double* W,
+                             int s, const double* origin, double* out)
+{
+    const char* call = "cugp_iter_features_apply";
+    int rc;
+    if ((rc = features_args(h, call, Omega, b, m, W, s))) return rc;
+    if (!out) return invalid_arg(call, "null argument");
+    if (nq < 1) return invalid_arg(call, "nq must be positive");
+    if (nq > CUGP_ITER_MAX_N) return invalid_arg(call, "nq beyond CUGP_ITER_MAX_N");
+    if (!Xq && nq != h->n) return invalid_arg(call, "Xq is NULL (the training rows): nq must be the handle's n");
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    const int tp = iter_tp(s);
+    if ((rc = features_stage(h, Omega, b, m, W, s, tp, origin))) return rc;
+    const double* A = h->dX;
+    if (Xq) {
+        if ((rc = h->xt.grow((size_t)nq * h->d, h->stream))) return rc;
+        HIPCHK(hipMemcpyAsync(h->xt.p, Xq, (size_t)nq * h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        A = h->xt.p;
+    }
+    if ((rc = features_dev(h, cf, A, nq, m, tp))) return rc;
+    if ((rc = sync_or_fail(h->stream, call, hipGetLastError()))) return rc;
+    return unpack(h, h->fout.p, nq, 0, s, tp, out);
+}
+
+int cugp_iter_paths_fit(cugp_iter* h, const double* Omega, const double* b, int m, const double* W, const double* Eps, int s,
+                        const double* origin, double tol, int max_iter, int check_every, double* V, double* info)
+{
+    const char* call = "cugp_iter_paths_fit";
+    int rc;
+    if ((rc = features_args(h, call, Omega, b, m, W, s))) return rc;
+    if (!V) return invalid_arg(call, "null argument");
+    if ((rc = solver_args(call, tol, max_iter, check_every))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    std::fill(h->stats, h->stats + 4, 0);
+    const CovFn cf = cov_of(h);
+    const int n = h->n, tp = iter_tp(s);
+    if ((rc = features_stage(h, Omega, b, m, W, s, tp, origin))) return rc;
+    if (Eps && (rc = pack(h, Eps, n, 0, s, tp, h->vk))) return rc;
+    if ((rc = h->vb.grow((size_t)n * tp, h->stream)) || (rc = features_dev(h, cf, h->dX, n, m, tp))) return rc;
+    launch_iter_paths_rhs(h->dyb, h->fout.p, Eps ? h->vk.p : nullptr, std::exp(h->theta[h->nh - 1]), s, n, tp, h->vb.p, h->stream);
+    if ((rc = solve_dev(h, cf, h->vb.p, tp, tol, max_iter, check_every, call))) return rc;
+    fill_info(h, 0, s, info);
+    return unpack(h, h->vx.p, n, 0, s, tp, V);
+}
+
+int cugp_iter_paths_eval(cugp_iter* h, const double* Xt, int nt, const double* Omega, const double* b, int m, const double* W,
+                         const double* V, int s, const double* origin, double* out)
+{
+    const char* call = "cugp_iter_paths_eval";
+    int rc;
+    if ((rc = features_args(h, call, Omega, b, m, W, s))) return rc;
+    if (!Xt || !V || !out) return invalid_arg(call, "null argument");
+    if (nt < 1) return invalid_arg(call, "nt must be positive");
+    if (nt > CUGP_ITER_MAX_N) return invalid_arg(call, "nt beyond CUGP_ITER_MAX_N");
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    hipStream_t st = h->stream;
+    const int tp = iter_tp(s);
+    if ((rc = features_stage(h, Omega, b, m, W, s, tp, origin)) || (rc = pack(h, V, h->n, 0, s, tp, h->vb))) return rc;
+    if ((rc = h->xt.grow((size_t)nt * h->d, st)) || (rc = h->res.grow((size_t)nt * tp, st))) return rc;
+    HIPCHK(hipMemcpyAsync(h->xt.p, Xt, (size_t)nt * h->d * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = features_dev(h, cf, h->xt.p, nt, m, tp)) || (rc = product(h, cf, h->xt.p, nt, h->vb.p, tp, h->res.p, false))) return rc;
+    launch_iter_paths_add(h->fout.p, h->res.p, (size_t)nt * tp, st);
+    if ((rc = sync_or_fail(st, call, hipGetLastError()))) return rc;
+    return unpack(h, h->res.p, nt, 0, s, tp, out);
 }

@@ -226,6 +226,32 @@ __global__ __launch_bounds__(256) void k_iter_cross_rhs(const double* __restrict
     R[e] = v;
 }
 
+// ---- the pathwise posterior draws: the vector arithmetic around the feature product k_rff_apply ----
+
+// The right-hand sides of the paths' solve: r[i][c] = (y_i - f[i][c]) - sn E[i][c] in exactly that order, no contraction
+// (E null: the first difference alone), c < count; columns count .. tp - 1 zero.  yb: y as column 0 of an [n][16] block
+__global__ __launch_bounds__(256) void k_iter_paths_rhs(const double* __restrict__ yb, const double* __restrict__ f,
+                                                        const double* __restrict__ E, double sn, int count, int tp, size_t cnt,
+                                                        double* __restrict__ r)
+{
+#pragma clang fp contract(off)
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= cnt) return;
+    double v = 0.0;
+    if ((int)(e % tp) < count) {
+        v = yb[e / tp * 16] - f[e];
+        if (E) v = v - sn * E[e];
+    }
+    r[e] = v;
+}
+
+// A path at the test points: k = f + k, the feature term first, one addition per entry
+__global__ __launch_bounds__(256) void k_iter_paths_add(const double* __restrict__ f, double* __restrict__ k, size_t cnt)
+{
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < cnt) k[e] = f[e] + k[e];
+}
+
 // ---- the preconditioned recurrences: z = M^-1 r, p = z + b p, a = r'z / p'Kp, b = r'z_new / r'z ----
 // The plain recurrence's kernels serve wherever the arithmetic is the same: k_iter_update (x, r and the shares of r'r),
 // k_iter_step_b (the sweep counted, the candidate test on r'r; the ratio it leaves in SC_B is overwritten by k_iter_step_z

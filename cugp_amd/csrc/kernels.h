@@ -513,6 +513,17 @@ void launch_iter_goal_init(int tp, double rho2, double* sc, hipStream_t s);
 void launch_iter_step_b_mx(const double* part, int n, int tp, double* sc, hipStream_t s);
 void launch_iter_step_v_mx(const double* part, int n, int tp, int final, double rho2, double* sc, hipStream_t s);
 void launch_iter_again(const double* b, double* x, double* r, int n, int tp, double* sc, hipStream_t s);
+// ---- the pathwise posterior draws (iter_rff_gfx950.h): out[i][c] = amp sum_k cos(b_k + sum_f (xq_if -
+// org_f) Om[k][f] s_f) W[k][c], i < nq, k < m, c < tp = 16 | 64; s_f the handle's weights (ARD descriptor) or 1 / sqrt(ell_sq);
+// Phi is never stored.  org: d doubles in device memory (zeros for no origin).  pl = rff_apply_plan(nq, m, .): iter_apply_plan's
+// rule with two stages per range at least; part: pl.split * nq * tp doubles when pl.split > 1
+IterPlan rff_apply_plan(int nq, int m, int force);
+void launch_rff_apply(const double* Xq, int nq, int d, const CovFn& cf, const double* Om, const double* ph, int m, const double* org,
+                      const double* W, int tp, double amp, double* out, double* part, const IterPlan& pl, hipStream_t s);
+// r[i][c] = (yb[i][0] - f[i][c]) - sn E[i][c] (E null: the difference alone), c < count; zero columns beyond; yb [n][16]
+void launch_iter_paths_rhs(const double* yb, const double* f, const double* E, double sn, int count, int n, int tp, double* r,
+                           hipStream_t s);
+void launch_iter_paths_add(const double* f, double* k, size_t cnt, hipStream_t s);   // k = f + k
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

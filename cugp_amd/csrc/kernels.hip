@@ -238,6 +238,9 @@ static void set_big_lds();
 // k_cov_apply32, k_cov_apply32_4 (the mixed mode's product: fp32 entries and MFMA, folded into fp64 every 128 terms),
 // kernel_value32 and launch_cov_apply32
 #include "iter32_gfx950.h"
+// k_rff_apply, k_rff_apply4 (the random-feature product Phi(Xq) W of the pathwise draws: the entry cos(phase) is the MFMA's A
+// operand), rff_apply_plan, launch_rff_apply and the launchers of iter_device.h's k_iter_paths_rhs and k_iter_paths_add
+#include "iter_rff_gfx950.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
 // failure is kept (the launch that follows would be rejected) and reported by prepare_kernels().

@@ -756,12 +756,14 @@ class IterativeGP:
         if X.shape != (self.n, self.d) or y.shape != (self.n,):
             raise ValueError("expected X %s and y %s" % ((self.n, self.d), (self.n,)))
         check(capi.lib().cugp_iter_set_data(self._h, ptr(X), ptr(y)))
+        self._origin = X.mean(axis=0)                  # sample_paths' default origin
 
     def set_loghyper(self, hp):
         hp = f64(hp)
         if hp.shape != (self.nh,):
             raise ValueError("expected %d log-hyper-parameters" % self.nh)
         check(capi.lib().cugp_iter_set_loghyper(self._h, ptr(hp), self.nh))
+        self._hp = hp.copy()                           # sample_paths reads the rational quadratic's alpha
 
     def set_split(self, split):
         """Ask for `split` ranges of the products' j range (0: the library's rule; plan() shows what is taken)."""
@@ -889,6 +891,74 @@ class IterativeGP:
                                                 float(tol), int(max_iter), int(check_every), ptr(info) if solve else None))
         return mean, v, dm, dv, info
 
+    def _features(self, Omega, b, W, origin):
+        Omega, b, W = f64(Omega), f64(b), f64(W)
+        W = W.reshape(1, -1) if W.ndim == 1 else W
+        m = b.shape[0] if b.ndim == 1 else -1
+        if m < 1 or Omega.shape != (m, self.d) or W.ndim != 2 or W.shape[1] != m or not 1 <= W.shape[0] <= 64:
+            raise ValueError("expected Omega [m, %d], b [m] and W [s, m] with 1 <= s <= 64 and m >= 1" % self.d)
+        if origin is not None:
+            origin = f64(origin)
+            if origin.shape != (self.d,):
+                raise ValueError("expected an origin [%d]" % self.d)
+        return Omega, b, W, origin
+
+    def features_apply(self, Xq, Omega, b, W, origin=None):
+        """Phi(Xq) W [s, nq] for the random features phi_k(x) = sqrt(2 sf2 / m) cos(sum_f (x_f - origin_f) Omega[k, f] / l_f + b_k)
+        (cugp_iter_features_apply; Phi is never stored).  Omega [m, d] in units of 1 / l (spectral_frequencies), b [m],
+        W [s, m] with s <= 64; Xq None: the training rows; origin None: zeros."""
+        Omega, b, W, origin = self._features(Omega, b, W, origin)
+        Xq = None if Xq is None else f64(Xq).reshape(-1, self.d)
+        nq = self.n if Xq is None else Xq.shape[0]
+        out = np.empty((W.shape[0], nq))
+        check(capi.lib().cugp_iter_features_apply(self._h, None if Xq is None else ptr(Xq), nq, ptr(Omega), ptr(b), b.shape[0],
+                                                  ptr(W), W.shape[0], None if origin is None else ptr(origin), ptr(out)))
+        return out
+
+    def sample_paths(self, s, features=1024, rng=None, Omega=None, b=None, W=None, Eps=None, origin=None, tol=1e-10,
+                     max_iter=1000, check_every=10):
+        """s functions drawn from the posterior by pathwise conditioning (cugp_iter_paths_fit): a SamplePaths object, which
+        evaluates them at any points -- paths(Xt) -> [s, nt] -- and carries .info [s, 4] as solve's.  The conditioning on the
+        data is exact (one certified solve per 64 paths); the prior draw uses `features` random features (error of order
+        1 / sqrt(features) in the prior covariance).
+        The caller's arrays win over draws: Omega [m, d] (spectral_frequencies), b [m] in [0, 2 pi), W [s, m] and Eps [s, n]
+        standard normal; whichever of Omega, b, W is None is drawn from rng (a numpy.random.Generator, in that order, then
+        Eps).  Eps None: drawn where rng is given; without rng the conditioning is noise-free (no sn eps term).  The result
+        is a deterministic function of (X, y, theta, Omega, b, W, Eps, origin): equal arrays give equal bits.
+        origin None: the column mean of the training inputs.  The paths belong to the data and the hyper-parameters of this
+        call: draw again after set_data or set_loghyper."""
+        s = int(s)
+        if s < 1:
+            raise ValueError("at least one path")
+        if rng is None and (Omega is None or b is None or W is None):
+            raise ValueError("drawing Omega, b or W needs rng, a numpy.random.Generator")
+        given = [np.shape(a)[i] for a, i in ((Omega, 0), (b, 0), (W, -1)) if a is not None]
+        m = given[0] if given else int(features)           # (the caller's arrays set m; they must agree: _features)
+        if Omega is None:
+            alpha = math.exp(float(self._hp[self.nh - 3])) if self._kind == capi.CUGP_KERNEL_RQ else None
+            Omega = spectral_frequencies(self._kind, self.d, m, rng, alpha)
+        if b is None:
+            b = rng.uniform(0.0, 2.0 * math.pi, size=m)
+        if W is None:
+            W = rng.standard_normal((s, m))
+        if Eps is None and rng is not None:
+            Eps = rng.standard_normal((s, self.n))
+        W = f64(W).reshape(s, -1)
+        Eps = None if Eps is None else self._block(Eps)
+        if Eps is not None and Eps.shape[0] != s:
+            raise ValueError("expected Eps [%d, %d]" % (s, self.n))
+        origin = getattr(self, "_origin", None) if origin is None else origin
+        V, info = np.empty((s, self.n)), np.empty((s, 4))
+        for c0 in range(0, s, 64):
+            Om, bb, Wc, org = self._features(Omega, b, W[c0:c0 + 64], origin)
+            Ec = None if Eps is None else np.ascontiguousarray(Eps[c0:c0 + 64])
+            Vc, ic = np.empty((Wc.shape[0], self.n)), np.empty((Wc.shape[0], 4))
+            check(capi.lib().cugp_iter_paths_fit(self._h, ptr(Om), ptr(bb), bb.shape[0], ptr(Wc), None if Ec is None else ptr(Ec),
+                                                 Wc.shape[0], None if org is None else ptr(org), float(tol), int(max_iter), int(check_every), ptr(Vc),
+                                                 ptr(ic)))
+            V[c0:c0 + 64], info[c0:c0 + 64] = Vc, ic
+        return SamplePaths(self, Om, bb, W, V, org, info)
+
     def set_precond(self, rank):
         """Ask for a pivoted-Cholesky preconditioner of that rank for solve / fit / predict (0: none, the default).  Built by
         the next call that needs it, and again after set_data, set_loghyper or another set_precond."""
@@ -932,6 +1002,52 @@ class IterativeGP:
         if rc < 0:
             check(rc)
         return dict(zip(("split", "per", "stages", "row_blocks"), out))
+
+
+class SamplePaths:
+    """Posterior sample paths of an IterativeGP (IterativeGP.sample_paths): paths(Xt) -> [s, nt], f_s(x) = phi(x)' w_s +
+    k(x, X) v_s (cugp_iter_paths_eval), 64 paths a call.  .info [s, 4] reports the solves as IterativeGP.solve does; .V [s, n],
+    .Omega, .b, .W and .origin are the arrays the paths are functions of."""
+
+    def __init__(self, model, Omega, b, W, V, origin, info):
+        self.model, self.Omega, self.b, self.W, self.V, self.origin, self.info = model, Omega, b, W, V, origin, info
+
+    def __call__(self, Xt):
+        g = self.model
+        Xt = f64(Xt).reshape(-1, g.d)
+        nt, s = Xt.shape[0], self.W.shape[0]
+        out = np.empty((s, nt))
+        for c0 in range(0, s, 64):
+            Wc, Vc = np.ascontiguousarray(self.W[c0:c0 + 64]), np.ascontiguousarray(self.V[c0:c0 + 64])
+            oc = np.empty((Wc.shape[0], nt))
+            check(capi.lib().cugp_iter_paths_eval(g._h, ptr(Xt), nt, ptr(self.Omega), ptr(self.b), self.b.shape[0], ptr(Wc), ptr(Vc),
+                                                  Wc.shape[0], None if self.origin is None else ptr(self.origin), ptr(oc)))
+            out[c0:c0 + 64] = oc
+        return out
+
+
+def spectral_frequencies(kernel, d, m, rng, alpha=None):
+    """Omega [m, d]: m frequencies drawn from rng (a numpy.random.Generator) from the spectral density of a covariance family
+    at unit length scale and unit variance -- in units of 1 / l, as IterativeGP.features_apply takes them -- so that
+    E cos(omega . r) = k(r) / sf2.  kernel: a name as IterativeGP's (the _ard names draw as their isotropic forms: the length
+    scales enter on the device) or a CUGP_KERNEL_* number.  z ~ N(0, I) throughout; squared exponential: z; Matern nu = 3/2,
+    5/2: z sqrt(2 nu / g), g ~ chi^2(2 nu) (a multivariate t with 2 nu degrees of freedom); rational quadratic with shape alpha
+    (required; k = (1 + r^2 / (2 alpha))^-alpha): z sqrt(tau), tau ~ Gamma(alpha, scale 1 / alpha)."""
+    kind = kernel_spec(kernel)[0] if isinstance(kernel, str) else int(kernel)
+    d, m = int(d), int(m)
+    if d < 1 or m < 1:
+        raise ValueError("d and m must be positive")
+    z = rng.standard_normal((m, d))
+    if kind == capi.CUGP_KERNEL_SE:
+        return z
+    if kind in (capi.CUGP_KERNEL_MATERN32, capi.CUGP_KERNEL_MATERN52):
+        dof = 3.0 if kind == capi.CUGP_KERNEL_MATERN32 else 5.0
+        return z * np.sqrt(dof / rng.chisquare(dof, size=(m, 1)))
+    if kind == capi.CUGP_KERNEL_RQ:
+        if alpha is None or not float(alpha) > 0.0:
+            raise ValueError("the rational quadratic kernel needs its shape alpha > 0")
+        return z * np.sqrt(rng.gamma(float(alpha), 1.0 / float(alpha), size=(m, 1)))
+    raise ValueError("unknown kernel kind %r" % (kernel,))
 
 
 def rademacher(rng, t, n):

@@ -1034,6 +1034,42 @@ int cugp_iter_input_grad(cugp_iter *h, const double *Xt, int nt, const double *W
 int cugp_iter_predict_grad(cugp_iter *h, const double *Xt, int nt, int with_noise, double *mean /* may be NULL */,
                            double *var /* may be NULL */, double *dmean /* may be NULL */, double *dvar /* may be NULL */,
                            double tol, int max_iter, int check_every, double *info /* may be NULL */);
+/* Pathwise posterior draws on random features (Matheron's rule, Wilson et al. 2020): s FUNCTIONS drawn
+ * from the posterior, each of which evaluates, and re-evaluates, at any points for the price of cugp_iter_predict's mean:
+ *      f_s(x) = phi(x)' w_s + k(x, X) v_s,     v_s = K^-1 (y - Phi(X) w_s - sn eps_s),     K = Kf + sn2 I,  sn = exp(theta_n),
+ *      phi_k(x) = sqrt(2 sf2 / m) cos(sum_f (x_f - c_f) omega_kf / l_f + b_k),   k = 0 .. m - 1.
+ * The caller supplies every random quantity: Omega [m][d] row-major, drawn from the family's spectral density IN UNITS OF 1 / l
+ * (squared exponential: N(0, I); the handle's length scales, one per dimension on an ARD handle, and sf2 are applied here),
+ * b [m] uniform on [0, 2 pi), W [s][m] and Eps [s][n] standard normal, and an origin c [d] (NULL: zeros; it does not change
+ * the distribution, b being uniform, and keeps the phases small for data far from zero).  The results are deterministic
+ * functions of (X, y, theta, Omega, b, W, Eps, c): two calls give the same bits, and a path's bits depend neither on s nor
+ * on the paths beside it.
+ * What is exact and what is not.  The conditioning on the data is exact -- the same certified solve as cugp_iter_solve, over
+ * all n rows --: a path interpolates the data as the posterior does whatever m is.  Only the PRIOR draw phi' w is approximate:
+ * m features reproduce the prior covariance with an error of order 1 / sqrt(m).  Phi (n x m) is never stored.  The feature
+ * product is fp64 in either precision mode; its cosine is the device library's fp64 cos, whose argument reduction holds for
+ * every finite phase: there is no bound on |phase| beyond finiteness (a non-finite phase gives NaN in that row).
+ * cugp_iter_features_apply: out [s][nq] = Phi(Xq) W, 1 <= s <= 64, m >= 1.  Xq [nq][d] row-major; NULL: the training rows (nq
+ *      must then be the handle's n).  Needs data and theta, no fit.
+ * cugp_iter_paths_fit     : V [s][n] = K^-1 (y - Phi(X) W - sn Eps), the right-hand side formed in exactly that order; Eps NULL:
+ *      noise-free conditioning (the second difference is not formed).  The solve is cugp_iter_solve's own path -- the
+ *      preconditioner and the precision mode as set, info [s][4] (may be NULL) and cugp_iter_solve_stats as there; a column that
+ *      broke down is NaN and the call returns CUGP_OK.  With W = 0 and Eps NULL every column of V is cugp_iter_fit's alpha
+ *      in bits (same tol, max_iter, check_every).  Neither reads nor changes the handle's fit.
+ * cugp_iter_paths_eval    : out [s][nt] = Phi(Xt) W + k(Xt, X) V, the second term by cugp_iter_apply_cross's launches, the two
+ *      added by one addition per output, the feature term first.  V BELONGS TO THE DATA AND THETA OF THE MOMENT IT WAS
+ *      COMPUTED, and to (Omega, b, W, c): the library keeps none of them and cannot check; evaluate with the arguments of
+ *      the fit, on a handle whose data and theta have not changed since.
+ * Refused with CUGP_ERR_INVALID before any device work: a NULL h, Omega, b, W, out, V or Xt (cugp_iter_paths_eval); s outside
+ *      [1, 64] (more paths: more calls); m < 1 or beyond CUGP_ITER_MAX_N; nq or nt < 1 or beyond CUGP_ITER_MAX_N; Xq NULL with
+ *      nq != n; tol, max_iter or check_every as in cugp_iter_solve; a call before data and theta. */
+int cugp_iter_features_apply(cugp_iter *h, const double *Xq /* may be NULL */, int nq, const double *Omega, const double *b, int m,
+                             const double *W, int s, const double *origin /* may be NULL */, double *out);
+int cugp_iter_paths_fit(cugp_iter *h, const double *Omega, const double *b, int m, const double *W,
+                        const double *Eps /* may be NULL */, int s, const double *origin /* may be NULL */, double tol,
+                        int max_iter, int check_every, double *V, double *info /* may be NULL */);
+int cugp_iter_paths_eval(cugp_iter *h, const double *Xt, int nt, const double *Omega, const double *b, int m, const double *W,
+                         const double *V, int s, const double *origin /* may be NULL */, double *out);
 
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);

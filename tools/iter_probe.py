@@ -39,6 +39,15 @@ call, wall time with the host's packing; then fit and predict_grad at 64 points 
 --kernel-stats DIR adds the device times of k_cov_xgrad* and k_cov_apply* from such a trace's *kernel_trace.csv: per kernel the
 median, smallest and largest of its launches with the FIRST one (the warm-up call's) dropped, and covariance entries per
 second from the median -- the common unit: each kernel computes one entry per (i, j).
+
+--paths: instead of the above, the pathwise posterior draws -> profiles/iter_paths_probe.json.  Per
+family and feature count m (--features), s = 64 paths: features_apply over the n training rows and over --nt test rows with
+apply and apply_cross at t = 64 beside them (medians of --reps calls after a warm-up call, wall time with the host's packing;
+feature entries n m and covariance entries n n per second); then fit beside sample_paths (paths_fit: one 64-column solve) at
+tol 1e-8 -- SINGLE calls --, and paths(Xt) beside predict's mean at --nt points (medians after a warm-up).  --launches-only:
+the products alone, nothing written (for a kernel trace); --kernel-stats DIR adds the device times of k_rff_apply* and
+k_cov_apply* from such traces' *kernel_trace.csv, per kernel and launch shape (the grid tells the shapes apart): DIR/m<m>
+holds the trace of `... --paths --launches-only --features <m>`, one run per feature count.
 """
 import argparse
 import json
@@ -285,8 +294,88 @@ def xgrad_probe(a):
     print(json.dumps(res))
 
 
+def paths_trace_times(root, shapes, m, n):
+    """{kernel @ shape: {timed_launches, median_seconds, min_seconds, max_seconds, entries_per_s}} of the k_rff_apply* / k_cov_apply*
+    dispatches of a kernel trace; shapes: workgroups of the grid's x dimension (row blocks) -> (label, rows); entries: rows * m
+    feature entries, rows * n covariance entries; each shape's first launch (the warm-up call's) dropped"""
+    import csv
+    import glob
+    runs = {}
+    for path in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                name = row.get("Kernel_Name", "")
+                blocks = int(row["Grid_Size_X"]) // int(row["Workgroup_Size_X"])
+                if ("k_rff_apply" in name or "k_cov_apply" in name) and "finish" not in name and blocks in shapes:
+                    short = name.replace("cugp::", "").split("(")[0].replace("void ", "")
+                    runs.setdefault((short, blocks, int(row["Grid_Size_Y"])), []).append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
+    out = {}
+    for (short, blocks, split), r in sorted(runs.items()):
+        secs = [(e - s) * 1e-9 for s, e in sorted(r)[1:]]
+        if secs:
+            med = float(np.median(secs))
+            out["%s @ %s, split %d" % (short, shapes[blocks][0], split)] = {
+                "timed_launches": len(secs), "median_seconds": med, "min_seconds": min(secs), "max_seconds": max(secs),
+                "entries_per_s": float(shapes[blocks][1]) * (m if "rff" in short else n) / med}
+    return out
+
+
+def paths_probe(a):
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": D, "nt": a.nt, "s": 64, "reps": a.reps, "tol": 1e-8,
+           "families": {}}
+    X, y = synth(a.n, d=D)
+    Xt = synth(a.nt, d=D, seed=7)[0]
+    rng = np.random.default_rng(0)
+    V = rng.standard_normal((64, a.n))
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        r = {"apply_t64_seconds": timed(lambda: g.apply(V), a.reps)[0], "apply_cross_t64_seconds": timed(lambda: g.apply_cross(Xt, V), a.reps)[0]}
+        r["apply_t64_entries_per_s"] = float(a.n) * a.n / r["apply_t64_seconds"]
+        draws = {}
+        for m in a.features:
+            Om = gp.spectral_frequencies(fam, D, m, rng, np.exp(th[-3]) if fam.startswith("rq") else None)
+            draws[m] = (Om, rng.uniform(0, 2 * np.pi, m), rng.standard_normal((64, m)))
+            st = timed(lambda: g.features_apply(None, *draws[m], g._origin), a.reps)[0]
+            sq = timed(lambda: g.features_apply(Xt, *draws[m], g._origin), a.reps)[0]
+            r["m%d" % m] = {"features_train_seconds": st, "features_train_entries_per_s": float(a.n) * m / st,
+                            "features_test_seconds": sq, "features_test_entries_per_s": float(a.nt) * m / sq}
+            print(fam, "m", m, r["m%d" % m], flush=True)
+        if not a.launches_only:
+            t0 = time.perf_counter()
+            fi = g.fit(1e-8, 2000, 10)
+            r["fit"] = {"seconds": time.perf_counter() - t0, "sweeps": fi[0], "converged": fi[2]}
+            r["predict_mean_seconds"] = timed(lambda: g.predict(Xt, var=False), a.reps)[0]
+            Eps = rng.standard_normal((64, a.n))
+            for m in a.features:
+                t0 = time.perf_counter()
+                paths = g.sample_paths(64, Omega=draws[m][0], b=draws[m][1], W=draws[m][2], Eps=Eps, tol=1e-8, max_iter=2000, check_every=10)
+                r["m%d" % m]["paths_fit"] = {"seconds": time.perf_counter() - t0, "sweeps_max": float(paths.info[:, 0].max()),
+                                             "converged": float(paths.info[:, 2].min()), "stats": g.solve_stats()}
+                r["m%d" % m]["paths_eval_seconds"] = timed(lambda: paths(Xt), a.reps)[0]
+                print(fam, "m", m, r["m%d" % m]["paths_fit"], r["m%d" % m]["paths_eval_seconds"], flush=True)
+            print(fam, r["fit"], r["predict_mean_seconds"], flush=True)
+        g.close()
+        res["families"][fam] = r
+    if a.launches_only:
+        return
+    if a.kernel_stats:
+        shapes = {(a.n + 63) // 64: ("%d training rows" % a.n, a.n), (a.nt + 63) // 64: ("%d test rows" % a.nt, a.nt)}
+        res["kernels"] = {"m%d" % m: paths_trace_times(os.path.join(a.kernel_stats, "m%d" % m), shapes, m, a.n) for m in a.features}
+    res["single_unwarmed_calls"] = ["fit", "paths_fit"]
+    res["not_measured"] = ["counters", "d > 16 (the feature chunk loop)", "other families than SE and RQ-ARD", "forced splits",
+                           "s other than 64"] + ([] if a.kernel_stats else ["device times (no --kernel-stats): wall times with the host's packing"])
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_paths_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--paths", action="store_true", help="the pathwise draws' probe (its own mode)")
+    ap.add_argument("--features", type=int, nargs="+", default=[1024, 4096], help="... feature counts m")
     ap.add_argument("--xgrad", action="store_true", help="the test-input gradients' probe (its own mode)")
     ap.add_argument("--launches-only", action="store_true", help="... the three launches alone, nothing written (for a kernel trace)")
     ap.add_argument("--precision", action="store_true", help="the mixed-mode probe (its own mode)")
@@ -312,6 +401,8 @@ def main():
         return precision_probe(a)
     if a.xgrad:
         return xgrad_probe(a)
+    if a.paths:
+        return paths_probe(a)
     res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "nt": a.nt, "ntvar": a.ntvar, "d": D, "reps": a.reps, "families": {}}
     X, y = synth(a.n, d=D)
     Xt = synth(a.nt, d=D, seed=7)[0]
