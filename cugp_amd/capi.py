@@ -230,6 +230,7 @@ SIGNATURES = {
     "cugp_iter_paths_fit": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, C.c_double, C.c_int, C.c_int, _dp,
                                       _dp]),
     "cugp_iter_paths_eval": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
+    "cugp_iter_paths_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

@@ -993,3 +993,37 @@ int cugp_iter_paths_eval(cugp_iter* h, const double* Xt, int nt, const double* O
     if ((rc = sync_or_fail(st, call, hipGetLastError()))) return rc;
     return unpack(h, h->res.p, nt, 0, s, tp, out);
 }
+
+int cugp_iter_paths_grad(cugp_iter* h, const double* Xt, int nt, const double* Omega, const double* b, int m, const double* W,
+                         const double* V, int s, const double* origin, double* out)
+{
+    const char* call = "cugp_iter_paths_grad";
+    if (!W && !V) return invalid_arg(call, "W and V are both NULL (neither term is asked for)");
+    if (s < 1 || s > IT_MAXT) return invalid_arg(call, "s must lie in [1, 64]");
+    if (nt < 1) return invalid_arg(call, "nt must be positive");
+    if (nt > CUGP_ITER_MAX_N) return invalid_arg(call, "nt beyond CUGP_ITER_MAX_N");
+    if (!h || !Xt || !out) return invalid_arg(call, "null argument");
+    int rc;
+    if ((rc = W ? features_args(h, call, Omega, b, m, W, s) : ready(h, call)) || (rc = xgrad_dims(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    hipStream_t st = h->stream;
+    const int tp = iter_tp(s), d = h->d;
+    const IterPlan pd = iter_apply_plan(nt, h->n, h->split), pf = rff_apply_plan(nt, W ? m : 1, h->split);
+    if (W && (rc = features_stage(h, Omega, b, m, W, s, tp, origin))) return rc;
+    if (V && (rc = pack(h, V, h->n, 0, s, tp, h->vb))) return rc;
+    const size_t cnt = (size_t)nt * d * tp;
+    if ((rc = h->xt.grow((size_t)nt * d, st)) || (rc = h->xout.grow(cnt, st))) return rc;
+    if (V && (rc = h->xpart.grow(pd.split * cnt, st))) return rc;
+    if (W && (rc = h->apart.grow(pf.split * cnt, st))) return rc;
+    HIPCHK(hipMemcpyAsync(h->xt.p, Xt, (size_t)nt * d * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const double amp = W ? std::sqrt(2.0 * h->hhs->signal_var / (double)m) : 0.0;
+    launch_paths_grad(h->xt.p, nt, d, cf, h->dX, h->n, V ? h->vb.p : nullptr, pd, h->xpart.p, h->fom.p, h->fb.p, m, h->forg.p,
+                      W ? h->fw.p : nullptr, amp, pf, h->apart.p, tp, h->xout.p, st);
+    if ((rc = sync_or_fail(st, call, hipGetLastError()))) return rc;
+    // the device block is [tp][nt][d]: its first s slabs are the caller's array
+    HIPCHK(hipMemcpyAsync(out, h->xout.p, (size_t)s * nt * d * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return CUGP_OK;
+}

@@ -524,6 +524,14 @@ void launch_rff_apply(const double* Xq, int nq, int d, const CovFn& cf, const do
 void launch_iter_paths_rhs(const double* yb, const double* f, const double* E, double sn, int count, int n, int tp, double* r,
                            hipStream_t s);
 void launch_iter_paths_add(const double* f, double* k, size_t cnt, hipStream_t s);   // k = f + k
+// ---- the input gradients of the sample paths (iter_paths_grad_gfx950.h), i < nt, a < d, c < tp = 16 | 64:
+//   out[c][i][a] = -amp sum_k sin(phase_ik) (Om[k][a] s_a') W[k][c]  +  -s_a sum_j G_ij (xt[i][a] - x[j][a]) V[j][c],
+// phase and s_a' as launch_rff_apply's, G and s_a as launch_cov_xgrad's; the feature term first, one addition.  W null: the
+// second term alone (Om, ph, org, partf are not read); V null: the first alone.  pd = iter_apply_plan(nt, n, .), pf =
+// rff_apply_plan(nt, m, .); partd, partf: split * nt * d * tp doubles each (always written: the finish scales and transposes)
+void launch_paths_grad(const double* Xt, int nt, int d, const CovFn& cf, const double* X, int n, const double* V, const IterPlan& pd,
+                       double* partd, const double* Om, const double* ph, int m, const double* org, const double* W, double amp,
+                       const IterPlan& pf, double* partf, int tp, double* out, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

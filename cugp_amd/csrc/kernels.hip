@@ -241,6 +241,9 @@ static void set_big_lds();
 // k_rff_apply, k_rff_apply4 (the random-feature product Phi(Xq) W of the pathwise draws: the entry cos(phase) is the MFMA's A
 // operand), rff_apply_plan, launch_rff_apply and the launchers of iter_device.h's k_iter_paths_rhs and k_iter_paths_add
 #include "iter_rff_gfx950.h"
+// k_cov_xgrad_cols, k_cov_xgrad_cols4, k_rff_grad, k_rff_grad4 (the input gradients of the sample paths: the entry times a
+// per-dimension factor is the MFMA's A operand, s shared columns B), k_paths_grad_finish and launch_paths_grad
+#include "iter_paths_grad_gfx950.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
 // failure is kept (the launch that follows would be rejected) and reported by prepare_kernels().

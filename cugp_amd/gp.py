@@ -1006,7 +1006,8 @@ class IterativeGP:
 
 class SamplePaths:
     """Posterior sample paths of an IterativeGP (IterativeGP.sample_paths): paths(Xt) -> [s, nt], f_s(x) = phi(x)' w_s +
-    k(x, X) v_s (cugp_iter_paths_eval), 64 paths a call.  .info [s, 4] reports the solves as IterativeGP.solve does; .V [s, n],
+    k(x, X) v_s (cugp_iter_paths_eval), 64 paths a call; paths.grad(Xt) -> [s, nt, d], their gradients with respect to x
+    (cugp_iter_paths_grad).  .info [s, 4] reports the solves as IterativeGP.solve does; .V [s, n],
     .Omega, .b, .W and .origin are the arrays the paths are functions of."""
 
     def __init__(self, model, Omega, b, W, V, origin, info):
@@ -1021,6 +1022,24 @@ class SamplePaths:
             Wc, Vc = np.ascontiguousarray(self.W[c0:c0 + 64]), np.ascontiguousarray(self.V[c0:c0 + 64])
             oc = np.empty((Wc.shape[0], nt))
             check(capi.lib().cugp_iter_paths_eval(g._h, ptr(Xt), nt, ptr(self.Omega), ptr(self.b), self.b.shape[0], ptr(Wc), ptr(Vc),
+                                                  Wc.shape[0], None if self.origin is None else ptr(self.origin), ptr(oc)))
+            out[c0:c0 + 64] = oc
+        return out
+
+    def grad(self, Xt, part="both"):
+        """[s, nt, d]: the gradient of every path with respect to the point, at each of the points Xt (cugp_iter_paths_grad), 64
+        paths a call.  part="prior": the feature term d(phi(x)' w_s)/dx alone; "update": the data term d(k(x, X) v_s)/dx alone."""
+        if part not in ("both", "prior", "update"):
+            raise ValueError('part must be "both", "prior" or "update"')
+        g = self.model
+        Xt = f64(Xt).reshape(-1, g.d)
+        nt, s = Xt.shape[0], self.W.shape[0]
+        out = np.empty((s, nt, g.d))
+        for c0 in range(0, s, 64):
+            Wc, Vc = np.ascontiguousarray(self.W[c0:c0 + 64]), np.ascontiguousarray(self.V[c0:c0 + 64])
+            oc = np.empty((Wc.shape[0], nt, g.d))
+            check(capi.lib().cugp_iter_paths_grad(g._h, ptr(Xt), nt, ptr(self.Omega), ptr(self.b), self.b.shape[0],
+                                                  None if part == "update" else ptr(Wc), None if part == "prior" else ptr(Vc),
                                                   Wc.shape[0], None if self.origin is None else ptr(self.origin), ptr(oc)))
             out[c0:c0 + 64] = oc
         return out

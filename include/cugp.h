@@ -1060,9 +1060,20 @@ int cugp_iter_predict_grad(cugp_iter *h, const double *Xt, int nt, int with_nois
  *      added by one addition per output, the feature term first.  V BELONGS TO THE DATA AND THETA OF THE MOMENT IT WAS
  *      COMPUTED, and to (Omega, b, W, c): the library keeps none of them and cannot check; evaluate with the arguments of
  *      the fit, on a handle whose data and theta have not changed since.
+ * cugp_iter_paths_grad    : out [s][nt][d] row-major = the gradients of the s paths with respect to the point, at each of the nt
+ *      points Xt [nt][d] (what L-BFGS over a path asks for):
+ *          df_c / dx_a (x) = -sqrt(2 sf2 / m) sum_k sin(phase_k(x)) (omega_ka / l_a) W[c][k]  +  sum_j V[c][j] dk(x, x_j) / dx_a,
+ *      the feature term first, one addition per output.  One sweep over the n training rows serves all s paths: every
+ *      covariance entry is computed once per group of four dimensions and handed to the fp64 matrix instruction against the
+ *      s shared columns (cugp_iter_input_grad takes one weight vector, or one per point).  The difference x_a - x_ja is formed
+ *      before it is multiplied: data far from zero costs no accuracy.  W NULL: the data term alone -- Omega, b, m and origin
+ *      are not looked at; V NULL: the feature term alone; both NULL is refused.  fp64 in either precision mode.  Two calls
+ *      give the same bits; a path's bits depend neither on s nor on the paths beside it, a point's neither on nt nor on the
+ *      points beside it (cugp_iter_set_split fixed).  V belongs to its fit as for cugp_iter_paths_eval.
  * Refused with CUGP_ERR_INVALID before any device work: a NULL h, Omega, b, W, out, V or Xt (cugp_iter_paths_eval); s outside
  *      [1, 64] (more paths: more calls); m < 1 or beyond CUGP_ITER_MAX_N; nq or nt < 1 or beyond CUGP_ITER_MAX_N; Xq NULL with
- *      nq != n; tol, max_iter or check_every as in cugp_iter_solve; a call before data and theta. */
+ *      nq != n; tol, max_iter or check_every as in cugp_iter_solve; a call before data and theta; for cugp_iter_paths_grad W and
+ *      V both NULL, and Omega or b NULL where W is given. */
 int cugp_iter_features_apply(cugp_iter *h, const double *Xq /* may be NULL */, int nq, const double *Omega, const double *b, int m,
                              const double *W, int s, const double *origin /* may be NULL */, double *out);
 int cugp_iter_paths_fit(cugp_iter *h, const double *Omega, const double *b, int m, const double *W,
@@ -1070,6 +1081,9 @@ int cugp_iter_paths_fit(cugp_iter *h, const double *Omega, const double *b, int 
                         int max_iter, int check_every, double *V, double *info /* may be NULL */);
 int cugp_iter_paths_eval(cugp_iter *h, const double *Xt, int nt, const double *Omega, const double *b, int m, const double *W,
                          const double *V, int s, const double *origin /* may be NULL */, double *out);
+int cugp_iter_paths_grad(cugp_iter *h, const double *Xt, int nt, const double *Omega, const double *b, int m,
+                         const double *W /* may be NULL */, const double *V /* may be NULL */, int s,
+                         const double *origin /* may be NULL */, double *out /* [s][nt][d] */);
 
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);

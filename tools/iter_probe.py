@@ -48,6 +48,17 @@ tol 1e-8 -- SINGLE calls --, and paths(Xt) beside predict's mean at --nt points 
 the products alone, nothing written (for a kernel trace); --kernel-stats DIR adds the device times of k_rff_apply* and
 k_cov_apply* from such traces' *kernel_trace.csv, per kernel and launch shape (the grid tells the shapes apart): DIR/m<m>
 holds the trace of `... --paths --launches-only --features <m>`, one run per feature count.
+
+--paths-grad: instead of the above, the input gradients of the sample paths ->
+profiles/iter_paths_grad_probe.json.  Per family, s = 64 paths over --nt points with m = the first of --features: paths.grad's
+data term ("update") and feature term ("prior"), apply_cross at t = 64 (k_cov_apply4's cross product of the same call shape)
+and input_grad with ONE weight vector (one k_cov_xgrad launch: a caller without paths.grad needs s of them): medians of
+--reps calls after a warm-up call, wall time with the host's packing.  --launches-only: the calls alone, nothing written (for a
+kernel trace, with --reps 12); --lib PATH loads another libcugp.so (the parent commit's) and runs what it has.
+--kernel-stats DIR adds the device times from the *kernel_trace.csv under DIR/new and DIR/parent (one traced run of
+`... --paths-grad --launches-only --reps 12` each, the second with --lib): per kernel the median, smallest and largest of its
+launches with the FIRST dropped; the data term's entry rate (nt n entries; every entry is computed once per chunk of four
+dimensions) beside k_cov_apply4's, and s times the parent's k_cov_xgrad launch with its finish beside the one new launch.
 """
 import argparse
 import json
@@ -372,8 +383,77 @@ def paths_probe(a):
     print(json.dumps(res))
 
 
+def grad_trace_times(root):
+    """{kernel: {timed_launches, median_seconds, min_seconds, max_seconds}} of the gradient kernels and k_cov_apply4 in a kernel
+    trace, each kernel's first launch dropped"""
+    import csv
+    import glob
+    runs = {}
+    for path in glob.glob(os.path.join(root, "**", "*kernel_trace.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                name = row.get("Kernel_Name", "")
+                if any(k in name for k in ("k_cov_xgrad", "k_rff_grad", "k_paths_grad_finish", "k_cov_apply4")):
+                    short = name.replace("cugp::", "").split("(")[0].replace("void ", "")
+                    runs.setdefault(short, []).append((int(row["Start_Timestamp"]), int(row["End_Timestamp"])))
+    out = {}
+    for short, r in sorted(runs.items()):
+        secs = [(e - s) * 1e-9 for s, e in sorted(r)[1:]]
+        if secs:
+            out[short] = {"timed_launches": len(secs), "median_seconds": float(np.median(secs)), "min_seconds": min(secs),
+                          "max_seconds": max(secs)}
+    return out
+
+
+def paths_grad_probe(a):
+    new, m = "cugp_iter_paths_grad" in capi.SIGNATURES, a.features[0]
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": D, "nt": a.nt, "s": 64, "m": m, "reps": a.reps, "families": {}}
+    X, y = synth(a.n, d=D)
+    Xt = synth(a.nt, d=D, seed=7)[0]
+    rng = np.random.default_rng(0)
+    V = rng.standard_normal((64, a.n))
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        Om = gp.spectral_frequencies(fam, D, m, rng, np.exp(th[-3]) if fam.startswith("rq") else None)
+        r = {"apply_cross_t64_seconds": timed(lambda: g.apply_cross(Xt, V), a.reps)[0],
+             "input_grad_one_vector_seconds": timed(lambda: g.input_grad(Xt, V[:1]), a.reps)[0]}
+        if new:
+            paths = gp.SamplePaths(g, Om, rng.uniform(0, 2 * np.pi, m), rng.standard_normal((64, m)), V, g._origin, None)
+            r["grad_update_seconds"] = timed(lambda: paths.grad(Xt, "update"), a.reps)[0]
+            r["grad_prior_seconds"] = timed(lambda: paths.grad(Xt, "prior"), a.reps)[0]
+        print(fam, r, flush=True)
+        g.close()
+        res["families"][fam] = r
+    if a.launches_only:
+        return
+    if a.kernel_stats:
+        k = {w: grad_trace_times(os.path.join(a.kernel_stats, w)) for w in ("new", "parent")}
+        res["kernels"] = k
+        res["data_term"] = {}
+        for fam, tag in (("se", "<false, 0>"), ("rq_ard", "<true, 3>")):
+            cols, app = k["new"].get("k_cov_xgrad_cols4" + tag), k["new"].get("k_cov_apply4" + tag)
+            one, fin = k["parent"].get("k_cov_xgrad" + tag[:-1] + ", false>"), k["parent"].get("k_cov_xgrad_finish")
+            if cols and app and one and fin:
+                route = 64 * (one["median_seconds"] + fin["median_seconds"])
+                res["data_term"][fam] = {
+                    "entries_per_s": float(a.nt) * a.n / cols["median_seconds"], "cov_apply4_entries_per_s": float(a.nt) * a.n / app["median_seconds"],
+                    "seconds": cols["median_seconds"], "cov_apply4_seconds": app["median_seconds"],
+                    "s_launches_of_k_cov_xgrad_seconds": route, "s_launches_over_one_launch": route / cols["median_seconds"]}
+    res["not_measured"] = ["counters", "d > 16 at scale (the chunk loop)", "other families than SE and RQ-ARD", "forced splits",
+                           "s other than 64", "k_paths_grad_finish per call kind (one median over both)"] + (
+                               [] if a.kernel_stats else ["device times (no --kernel-stats): wall times with the host's packing"])
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_paths_grad_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--paths-grad", action="store_true", help="the sample paths' input gradients (its own mode)")
+    ap.add_argument("--lib", default="", help="... another libcugp.so to load instead of the tree's (the parent commit's)")
     ap.add_argument("--paths", action="store_true", help="the pathwise draws' probe (its own mode)")
     ap.add_argument("--features", type=int, nargs="+", default=[1024, 4096], help="... feature counts m")
     ap.add_argument("--xgrad", action="store_true", help="the test-input gradients' probe (its own mode)")
@@ -393,6 +473,14 @@ def main():
     ap.add_argument("--ntvar", type=int, default=64, help="... of which the first ntvar get a variance (64 share one solve)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "iter_probe.json"))
     a = ap.parse_args()
+    if a.lib:                                          # another build: bind what it has
+        import ctypes
+        capi.LIB_PATH = os.path.abspath(a.lib)
+        capi._share_torch_hip_runtime()
+        other = ctypes.CDLL(capi.LIB_PATH)
+        capi.SIGNATURES = {k: v for k, v in capi.SIGNATURES.items() if hasattr(other, k)}
+    if a.paths_grad:
+        return paths_grad_probe(a)
     if a.precond is not None:
         return precond_probe(a)
     if a.grad:
