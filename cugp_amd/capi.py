@@ -212,6 +212,8 @@ SIGNATURES = {
     "cugp_iter_get_alpha": (C.c_int, [C.c_void_p, _dp]),
     "cugp_iter_grad_forms": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
     "cugp_iter_loglik_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "cugp_iter_loglik": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "cugp_iter_precond_sample": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int, _dp]),
     "cugp_iter_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int, _dp]),
     "cugp_iter_apply_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, _ip]),
     "cugp_iter_apply_plan_split": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _ip]),

@@ -42,6 +42,9 @@ struct cugp_iter {
     cugp_gp* pf = nullptr;         // the r x r side: an ordinary handle whose A receives C = sn2 I + L'L (as sparse.cpp's B)
     int pf_n = 0;                  // ... the size it was created for
     std::vector<int> hpiv;         // the pivots and ctl as read back: [rp + 2]
+    // the Lanczos quadrature (cugp_iter_loglik): a solve's log of (a_j, b_j) with its lengths and start
+    // weights, k_slq_quad's scratch, the probes' quadratures [t], the call's three sums, their pinned copy, G1 [r][tp]
+    Scratch lrec, lmeta, lwork, lquad, lout, lhost, pg1;
 };
 
 namespace {
@@ -185,7 +188,10 @@ int precond_apply_dev(cugp_iter* h, const double* R, int tp, double* Z)
 }
 
 // x (h->vx) = K^-1 B for the tp columns of the device block B by tp independent recurrences; the scalars stay in h->hsc
-int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol, int max_iter, int check_every, const char* call)
+// record: every column's (a_j, b_j) go into h->lrec, max_iter rows (k_iter_record behind each sweep's last scalar kernel; fp64
+// mode only); off, the launches are exactly the ones without it
+int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol, int max_iter, int check_every, const char* call,
+              bool record = false)
 {
     const int n = h->n;
     hipStream_t s = h->stream;
@@ -196,6 +202,7 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
         if ((rc = v->grow((size_t)n * tp, s))) return rc;
     if (pc && (rc = h->vz.grow((size_t)n * tp, s))) return rc;
     if ((rc = h->dpart.grow((size_t)iter_blocks(n) * IT_MAXT, s))) return rc;
+    if (record && ((rc = h->lrec.grow((size_t)2 * max_iter * IT_MAXT, s)) || (rc = h->lmeta.grow((size_t)ML_ROWS * IT_MAXT, s)))) return rc;
     double *x = h->vx.p, *r = h->vr.p, *p = h->vp.p, *q = h->vq.p, *z = h->vz.p, *part = h->dpart.p, *sc = h->dsc;
     // z = M^-1 r and r'z behind it; fresh: the start and a restart (r'z alone), else a sweep (the ratio too)
     auto precondition = [&](int fresh) {
@@ -215,6 +222,7 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
         precondition(1);
         launch_iter_dir(p, z, n, tp, sc, 0, s);        // (the ratio is 0 from k_iter_init: p = z)
     }
+    if (record) launch_iter_record(sc, tp, 1, pc ? SC_RZ : SC_BB, max_iter, h->lrec.p, h->lmeta.p, s);
     // the true residual of the columns that wait for it (final: of the active ones too)
     auto verify = [&](int final) {
         if (const int e = product(h, cf, h->dX, n, x, tp, q, true)) return e;
@@ -255,6 +263,7 @@ int solve_dev(cugp_iter* h, const CovFn& cf, const double* B, int tp, double tol
             if (f32) launch_iter_step_b_mx(part, n, tp, sc, s);
             else launch_iter_step_b(part, n, tp, sc, s);
             if (pc) precondition(0);
+            if (record) launch_iter_record(sc, tp, 0, 0, max_iter, h->lrec.p, h->lmeta.p, s);
             launch_iter_dir(p, pc ? z : r, n, tp, sc, 0, s);
         }
         it += m;
@@ -457,6 +466,7 @@ int cugp_iter_create(int n, int d, int device, int kernel, int ard, cugp_iter** 
     h->nh = (h->ard ? d : 1) + shape_count(kernel) + 2;
     h->theta.assign(h->nh, 0.0);
     h->ghost.pinned = true;
+    h->lhost.pinned = true;
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc((void**)&h->dX, (size_t)n * d * sizeof(double));
@@ -481,7 +491,7 @@ int cugp_iter_destroy(cugp_iter* h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res, &h->pL,
                        &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost, &h->xpart, &h->xout,
-                       &h->fom, &h->fb, &h->forg, &h->fw, &h->fout})
+                       &h->fom, &h->fb, &h->forg, &h->fw, &h->fout, &h->lrec, &h->lmeta, &h->lwork, &h->lquad, &h->lout, &h->lhost, &h->pg1})
         v->release();
     if (h->pf) cugp_destroy(h->pf);
     for (void* p : {(void*)h->dX, (void*)h->dyb, (void*)h->dhs, (void*)h->dsc})
@@ -785,6 +795,94 @@ int cugp_iter_loglik_grad(cugp_iter* h, const double* Z, int t, double tol, int 
         if (e == hipSuccess) e = hipMemcpyAsync(h->ghost.p, h->gout.p, sizeof(double), hipMemcpyDeviceToHost, s);
         if ((rc = sync_or_fail(s, call, e))) return rc;
         *quad = h->ghost.p[0];
+    }
+    return CUGP_OK;
+}
+
+int cugp_iter_loglik(cugp_iter* h, const double* Z, const double* G1, int t, double tol, int max_iter, int check_every, double* ll,
+                     double* g, double* quad, double* logdet_precond, double* y_alpha, double* info)
+{
+    const char* call = "cugp_iter_loglik";
+    if (!h || !Z || !ll) return invalid_arg(call, "null argument");
+    if (t < 1) return invalid_arg(call, "t must be positive");
+    int rc;
+    if ((rc = solver_args(call, tol, max_iter, check_every))) return rc;
+    if (max_iter > CUGP_ITER_MAX_LOG) return invalid_arg(call, "max_iter beyond CUGP_ITER_MAX_LOG (the recurrence's log)");
+    if ((rc = ready(h, call)) || (g && (rc = grad_dims(h, call)))) return rc;
+    if (h->mixed) return invalid_arg(call, "refused in the mixed mode: fp32 sweeps and cycle restarts are not one Lanczos process");
+    HIPCHK(hipSetDevice(h->device));
+    std::fill(h->stats, h->stats + 4, 0);
+    if (!h->fit_valid && (rc = fit_run(h, tol, max_iter, check_every, nullptr, call))) return rc;
+    if ((rc = precond_build(h, call))) return rc;
+    const int n = h->n, r = h->pc_got;
+    if (r > 0 && !G1) return invalid_arg(call, "a preconditioned handle needs G1 [t][achieved rank] beside the probes");
+    const CovFn cf = cov_of(h);
+    hipStream_t s = h->stream;
+    if ((rc = h->lquad.grow(t, s)) || (rc = h->lout.grow(3, s)) || (rc = h->lhost.grow((size_t)t + 3, s)) ||
+        (rc = h->lwork.grow((size_t)3 * max_iter * IT_MAXT, s)))
+        return rc;
+    // the probes: z_p (preconditioned L g1 + sn g2), u_p = K^-1 z_p with the recurrence logged, its quadrature, and for the
+    // gradient v_p = M^-1 z_p: E[u v'] = K^-1
+    std::vector<double> raw, rawa;
+    for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
+        if ((rc = pack(h, Z, n, c0, cnt, tp, h->vb))) return rc;
+        const double* B = h->vb.p;
+        if (r > 0) {
+            if ((rc = pack(h, G1, r, c0, cnt, tp, h->pg1)) || (rc = h->vk.grow((size_t)n * tp, s))) return rc;
+            launch_pc_sample(h->pL.p, h->pc_rp, h->pg1.p, r, h->vb.p, h->dhs, n, tp, h->vk.p, s);
+            B = h->vk.p;
+        }
+        if ((rc = solve_dev(h, cf, B, tp, tol, max_iter, check_every, call, true))) return rc;
+        fill_info(h, c0, cnt, info);
+        launch_slq_quad(h->lrec.p, h->lmeta.p, cnt, max_iter, h->lwork.p, h->lquad.p + c0, s);
+        if (g) {
+            if (r > 0) precond_apply_dev(h, B, tp, h->vz.p);
+            if ((rc = forms_dev(h, cf, h->vx.p, r > 0 ? h->vz.p : B, cnt, tp, c0 == 0, raw, call))) return rc;
+        }
+    }
+    if (g) {
+        if ((rc = forms_dev(h, cf, h->alpha.p, h->alpha.p, 1, 16, true, rawa, call))) return rc;
+        std::vector<double> fp(h->nh), fa(h->nh);
+        forms_out(h, raw, fp.data());
+        forms_out(h, rawa, fa.data());
+        for (int k = 0; k < h->nh; k++) g[k] = 0.5 * (fp[k] / (double)t - fa[k]);
+    }
+    // the call's one wait of its own: y'alpha, the probes' mean and the factor's diagonal in one launch, read back with quad
+    if ((rc = h->dpart.grow((size_t)iter_blocks(n) * IT_MAXT, s))) return rc;
+    launch_iter_dot(h->dyb, h->alpha.p, n, 16, h->dpart.p, s);
+    launch_slq_finish(h->dpart.p, n, h->lquad.p, t, r > 0 ? h->pf->dU : nullptr, r > 0 ? h->pf->npad : 0, r, h->lout.p, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->lhost.p, h->lout.p, 3 * sizeof(double), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->lhost.p + 3, h->lquad.p, (size_t)t * sizeof(double), hipMemcpyDeviceToHost, s);
+    if ((rc = sync_or_fail(s, call, e))) return rc;
+    const double ya = h->lhost.p[0], mean = h->lhost.p[1];
+    const double ldm = r > 0 ? (double)(n - r) * std::log(h->hhs->noise_var) + h->lhost.p[2] : 0.0;
+    *ll = -0.5 * (ya + (ldm + mean) + (double)n * 1.83787);
+    if (quad) std::copy(h->lhost.p + 3, h->lhost.p + 3 + t, quad);
+    if (logdet_precond) *logdet_precond = ldm;
+    if (y_alpha) *y_alpha = ya;
+    return CUGP_OK;
+}
+
+int cugp_iter_precond_sample(cugp_iter* h, const double* G1, const double* G2, int t, double* out)
+{
+    const char* call = "cugp_iter_precond_sample";
+    if (!h || !G1 || !G2 || !out) return invalid_arg(call, "null argument");
+    if (t < 1) return invalid_arg(call, "t must be positive");
+    if (h->pc_rank == 0) return invalid_arg(call, "no preconditioner asked for (cugp_iter_set_precond)");
+    int rc;
+    if ((rc = precond_ready(h, call))) return rc;
+    const int n = h->n, r = h->pc_got;
+    if (r == 0) return invalid_arg(call, "the factor ended at rank 0: there is no preconditioner to sample from");
+    for (int c0 = 0; c0 < t; c0 += IT_MAXT) {
+        const int cnt = std::min(IT_MAXT, t - c0), tp = iter_tp(cnt);
+        if ((rc = pack(h, G2, n, c0, cnt, tp, h->vb)) || (rc = pack(h, G1, r, c0, cnt, tp, h->pg1)) ||
+            (rc = h->vk.grow((size_t)n * tp, h->stream)))
+            return rc;
+        launch_pc_sample(h->pL.p, h->pc_rp, h->pg1.p, r, h->vb.p, h->dhs, n, tp, h->vk.p, h->stream);
+        if ((rc = sync_or_fail(h->stream, call, hipGetLastError()))) return rc;
+        if ((rc = unpack(h, h->vk.p, n, c0, cnt, tp, out))) return rc;
     }
     return CUGP_OK;
 }

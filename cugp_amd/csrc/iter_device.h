@@ -519,3 +519,150 @@ __global__ __launch_bounds__(PCH_ROWS) void k_pchol_step(const double* __restric
         shi_out[blockIdx.x] = ri[0];
     }
 }
+
+// ---- the log marginal likelihood's value by Lanczos quadrature (cugp_iter_loglik) ----
+// A column's conjugate-gradient coefficients (a_j, b_j) are the Lanczos tridiagonal of K (preconditioned: of M^-1/2 K M^-1/2)
+// started at its right-hand side.  The recording mode of solve_dev logs them, k_slq_quad turns a log into the Gauss
+// quadrature of log.  No kernel above changes its text; without the mode nothing below is launched.
+// rec[2][cap][IT_MAXT]: a_j in plane 0, b_j in plane 1, sweep j in row j.  meta[ML_ROWS][IT_MAXT]: the log's length, 1 once it
+// is closed, 1 where the column broke down, the start weight (z'z, preconditioned r0' M^-1 r0).
+
+// one workgroup, thread c is column c.  start: behind the solve's first scalar kernels -- an empty open log and the weight
+// (row wrow of sc: SC_BB, preconditioned SC_RZ).  Else behind a sweep's last scalar kernel (k_iter_step_b, preconditioned the
+// k_iter_step_z of that sweep): an active column appends (a_j, b_j); a column found outside ST_ACTIVE closes its log for the
+// rest of the solve -- a candidate's last step length still counts (its sweep ran; T needs no b behind it), a broken column
+// is marked.  A closed log never reopens: the sweeps after a failed true-residual check restart another Krylov space
+__global__ __launch_bounds__(256) void k_iter_record(const double* __restrict__ sc, int tp, int start, int wrow, int cap,
+                                                     double* __restrict__ rec, double* __restrict__ meta)
+{
+    const int c = threadIdx.x;
+    if (c >= tp) return;
+    if (start) {
+        meta[ML_LEN * IT_MAXT + c] = 0.0;
+        meta[ML_CLOSED * IT_MAXT + c] = 0.0;
+        meta[ML_BROKEN * IT_MAXT + c] = 0.0;
+        meta[ML_W * IT_MAXT + c] = sc[wrow * IT_MAXT + c];
+        return;
+    }
+    if (meta[ML_CLOSED * IT_MAXT + c] != 0.0) return;
+    const double st = sc[SC_STATE * IT_MAXT + c];
+    const int j = (int)meta[ML_LEN * IT_MAXT + c];
+    if (st != ST_ACTIVE) {
+        meta[ML_CLOSED * IT_MAXT + c] = 1.0;
+        if (st == ST_BROKEN) meta[ML_BROKEN * IT_MAXT + c] = 1.0;
+        if (st != ST_CANDIDATE) return;
+    }
+    if (j >= cap) return;
+    rec[(size_t)j * IT_MAXT + c] = sc[SC_A * IT_MAXT + c];
+    rec[((size_t)cap + j) * IT_MAXT + c] = st == ST_ACTIVE ? sc[SC_B * IT_MAXT + c] : 0.0;
+    meta[ML_LEN * IT_MAXT + c] = (double)(j + 1);
+}
+
+// one workgroup, thread c < cnt is column c: quad[c] = w_c sum_i tau_i^2 log lambda_i for the Jacobi matrix T of the column's
+// log of length m,  T_00 = 1 / a_0,  T_jj = 1 / a_j + b_(j-1) / a_(j-1),  T_j,j+1 = sqrt(b_j) / a_j  (j + 1 < m):  lambda its
+// eigenvalues, tau the first components of its eigenvectors (Golub-Welsch).  Implicit-shift QL on (dg, of) carrying the first
+// row of the eigenvector matrix only: work[3][cap][IT_MAXT] doubles of device memory (dg, of, tau; a column strides IT_MAXT),
+// no LDS, no barrier.  The eigenvalues are then sorted ascending (insertion, tau with them) and the terms added in ascending
+// i: the first copied, then s = s + term.  m = 0 (z = 0): 0.  NaN: a broken column, an eigenvalue that is not positive and
+// finite, or an eigenvalue that has not split off after 30 QL sweeps
+__global__ __launch_bounds__(256) void k_slq_quad(const double* __restrict__ rec, const double* __restrict__ meta, int cnt, int cap,
+                                                  double* __restrict__ work, double* __restrict__ quad)
+{
+#pragma clang fp contract(off)
+    const int c = threadIdx.x;
+    if (c >= cnt) return;
+    const int m = (int)meta[ML_LEN * IT_MAXT + c];
+    const double nan = __builtin_nan("");
+    if (meta[ML_BROKEN * IT_MAXT + c] != 0.0) { quad[c] = nan; return; }
+    if (m == 0) { quad[c] = 0.0; return; }
+    double* __restrict__ dg = work + c;
+    double* __restrict__ of = work + (size_t)cap * IT_MAXT + c;
+    double* __restrict__ tau = work + (size_t)2 * cap * IT_MAXT + c;
+    const double* __restrict__ ra = rec + c;
+    const double* __restrict__ rb = rec + (size_t)cap * IT_MAXT + c;
+#define AT(v, i) v[(size_t)(i) * IT_MAXT]
+    for (int j = 0; j < m; j++) {
+        const double a = AT(ra, j);
+        AT(dg, j) = j == 0 ? 1.0 / a : 1.0 / a + AT(rb, j - 1) / AT(ra, j - 1);
+        AT(of, j) = j + 1 < m ? __builtin_sqrt(AT(rb, j)) / a : 0.0;
+        AT(tau, j) = j == 0 ? 1.0 : 0.0;
+    }
+    bool bad = false;
+    for (int l = 0; l < m && !bad; l++) {
+        int iter = 0, mm;
+        do {
+            for (mm = l; mm < m - 1; mm++) {
+                const double dd = __builtin_fabs(AT(dg, mm)) + __builtin_fabs(AT(dg, mm + 1));
+                if (__builtin_fabs(AT(of, mm)) + dd == dd) break;
+            }
+            if (mm == l) break;
+            if (iter++ == 30) { bad = true; break; }
+            double g = (AT(dg, l + 1) - AT(dg, l)) / (2.0 * AT(of, l));
+            double r = __builtin_sqrt(g * g + 1.0);
+            g = AT(dg, mm) - AT(dg, l) + AT(of, l) / (g + (g >= 0.0 ? r : -r));
+            double s = 1.0, cs = 1.0, p = 0.0;
+            int i;
+            for (i = mm - 1; i >= l; i--) {
+                double f = s * AT(of, i);
+                const double b = cs * AT(of, i);
+                r = __builtin_sqrt(f * f + g * g);
+                AT(of, i + 1) = r;
+                if (r == 0.0) { AT(dg, i + 1) = AT(dg, i + 1) - p; AT(of, mm) = 0.0; break; }
+                s = f / r;
+                cs = g / r;
+                g = AT(dg, i + 1) - p;
+                r = (AT(dg, i) - g) * s + 2.0 * cs * b;
+                p = s * r;
+                AT(dg, i + 1) = g + p;
+                g = cs * r - b;
+                f = AT(tau, i + 1);
+                AT(tau, i + 1) = s * AT(tau, i) + cs * f;
+                AT(tau, i) = cs * AT(tau, i) - s * f;
+            }
+            if (r == 0.0 && i >= l) continue;
+            AT(dg, l) = AT(dg, l) - p;
+            AT(of, l) = g;
+            AT(of, mm) = 0.0;
+        } while (true);
+    }
+    if (bad) { quad[c] = nan; return; }
+    for (int i = 1; i < m; i++) {                          // ascending eigenvalues, their weights with them
+        const double v = AT(dg, i), w = AT(tau, i);
+        int k = i - 1;
+        for (; k >= 0 && AT(dg, k) > v; k--) { AT(dg, k + 1) = AT(dg, k); AT(tau, k + 1) = AT(tau, k); }
+        AT(dg, k + 1) = v;
+        AT(tau, k + 1) = w;
+    }
+    double s = 0.0;
+    for (int i = 0; i < m; i++) {
+        const double lam = AT(dg, i);
+        if (!(lam > 0.0 && lam - lam == 0.0)) { quad[c] = nan; return; }
+        const double term = (AT(tau, i) * AT(tau, i)) * log(lam);
+        s = i == 0 ? term : s + term;
+    }
+#undef AT
+    quad[c] = meta[ML_W * IT_MAXT + c] * s;
+}
+
+// one workgroup, the call's last launch: out[0] = y'alpha from the shares of k_iter_dot over (y, alpha) (column 0 of two
+// [n][16] blocks), out[1] = (1 / t) sum_p quad[p] in probe order, out[2] = -2 sum_(j < r) log U[j][j] (U = Lc^-T of the
+// preconditioner's r x r side, row stride ldu: 2 sum log diag Lc; r = 0: 0).  First term copied, then s = s + term
+__global__ __launch_bounds__(64) void k_slq_finish(const double* __restrict__ part, int nblk, const double* __restrict__ quad, int t,
+                                                   const double* __restrict__ Ud, int ldu, int r, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+    if (threadIdx.x == 0) out[0] = iter_sum_parts(part, nblk, 16, 0);
+    if (threadIdx.x == 1) {
+        double s = quad[0];
+        for (int p = 1; p < t; p++) s = s + quad[p];
+        out[1] = s / (double)t;
+    }
+    if (threadIdx.x == 2) {
+        double s = 0.0;
+        for (int j = 0; j < r; j++) {
+            const double term = log(Ud[(size_t)j * ldu + j]);
+            s = j == 0 ? term : s + term;
+        }
+        out[2] = -2.0 * s;
+    }
+}

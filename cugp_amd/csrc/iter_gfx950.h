@@ -692,6 +692,73 @@ __global__ __launch_bounds__(256) void k_pc_correct(const double* __restrict__ Q
         }
 }
 
+// k_pc_sample<NCT>:  Z = L G1 + sn G2, the probes of the preconditioner's own distribution (rows of Z' ~ (0, M) for standard
+//   G1, G2).  k_pc_correct's sibling: a workgroup owns ITER_ROWS = 64 rows, a wave 16 of them and all NCT
+//   column tiles; a stage is PC_KC = 16 values of k, the 64 x 16 piece of L and the 16 x TP piece of G1 pass through two LDS
+//   images each (the same pitches: 18 doubles, TP + 16 at TP = 64), the next stage's pieces in flight in registers behind the
+//   MFMAs, one barrier per stage.  A[row fr][k fk] = ls[16 wave + fr][4 kk + fk], B[k fk][col fr] = gs[4 kk + fk][16 ct + fr].
+//   Only the ceil(r / 16) stages that hold a row of G1 run; G1 has exactly r rows: a row m >= r of the last stage enters LDS
+//   as zeros and is never read from memory (L's columns r .. rp - 1 are zeros of the build).  Order of the sum: k ascending, 4
+//   per MFMA, into one fp64 accumulator from 0; then Z = acc + (sn G2), sn = sqrt(sn2) once per thread, the product and the
+//   sum rounded once each.
+template <int NCT>
+__global__ __launch_bounds__(256) void k_pc_sample(const double* __restrict__ L, int rp, const double* __restrict__ G1, int r,
+                                                   const double* __restrict__ G2, const HyperScalars* __restrict__ hd, int n,
+                                                   double* __restrict__ Z)
+{
+#pragma clang fp contract(off)
+    constexpr int TP = NCT * 16, TPL = (TP % 32 == 0) ? TP + 16 : TP, QL = PC_KC + 2, TV = PC_KC * TP / 4;
+    __shared__ __attribute__((aligned(32))) double ls[2][ITER_ROWS][QL];
+    __shared__ __attribute__((aligned(32))) double gs[2][PC_KC][TPL];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fk = lane >> 4;
+    const size_t i0 = (size_t)blockIdx.x * ITER_ROWS;
+    const int nst = (r + PC_KC - 1) / PC_KC;
+    const int qr = tid >> 2, qc = (tid & 3) * 4, tr = tid / (TP / 4), tc = (tid % (TP / 4)) * 4;
+    d4 rl, rg;
+    auto fetch = [&](int st) {
+        rl = i0 + qr < (size_t)n ? *(const d4*)(L + (i0 + qr) * rp + st * PC_KC + qc) : (d4){0.0, 0.0, 0.0, 0.0};
+        if (tid < TV) {
+            const int m = st * PC_KC + tr;
+            rg = m < r ? *(const d4*)(G1 + (size_t)m * TP + tc) : (d4){0.0, 0.0, 0.0, 0.0};
+        }
+    };
+    auto put = [&](int buf) {
+        ls[buf][qr][qc] = rl[0]; ls[buf][qr][qc + 1] = rl[1]; ls[buf][qr][qc + 2] = rl[2]; ls[buf][qr][qc + 3] = rl[3];
+        if (tid < TV) *(d4*)&gs[buf][tr][tc] = rg;
+    };
+    d4 acc[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++) acc[ct] = (d4){0.0, 0.0, 0.0, 0.0};
+    fetch(0);
+    put(0);
+    __syncthreads();
+    for (int st = 0; st < nst; st++) {
+        const int cur = st & 1;
+        const bool more = st + 1 < nst;
+        if (more) fetch(st + 1);
+#pragma unroll
+        for (int kk = 0; kk < PC_KC / 4; kk++) {
+            const double a = ls[cur][wave * 16 + fr][kk * 4 + fk];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ct++)
+                acc[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, gs[cur][kk * 4 + fk][ct * 16 + fr], acc[ct], 0, 0, 0);
+        }
+        if (more) put(cur ^ 1);
+        __syncthreads();
+    }
+    const double sn = __builtin_sqrt(hd->noise_var);
+#pragma unroll
+    for (int ct = 0; ct < NCT; ct++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const size_t i = i0 + wave * 16 + fk + 4 * q;
+            if (i < (size_t)n) {
+                const size_t e = i * TP + ct * 16 + fr;
+                Z[e] = acc[ct][q] + sn * G2[e];
+            }
+        }
+}
+
 PcPlan pc_plan(int n, int rank)
 {
     PcPlan p;
@@ -755,6 +822,29 @@ void launch_iter_step_a_pc(const double* part, int n, int tp, double* sc, hipStr
 void launch_iter_step_z(const double* part, int n, int tp, int first, double* sc, hipStream_t s)
 {
     hipLaunchKernelGGL(k_iter_step_z, dim3(1), dim3(256), 0, s, part, iter_blocks(n), tp, first, sc);
+}
+// the Lanczos quadrature's kernels (iter_device.h) and the probes' product
+void launch_iter_record(const double* sc, int tp, int start, int wrow, int cap, double* rec, double* meta, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_iter_record, dim3(1), dim3(256), 0, s, sc, tp, start, wrow, cap, rec, meta);
+}
+void launch_slq_quad(const double* rec, const double* meta, int cnt, int cap, double* work, double* quad, hipStream_t s)
+{
+    assert(cnt >= 1 && cnt <= IT_MAXT);
+    hipLaunchKernelGGL(k_slq_quad, dim3(1), dim3(256), 0, s, rec, meta, cnt, cap, work, quad);
+}
+void launch_slq_finish(const double* part, int n, const double* quad, int t, const double* U, int ldu, int r, double* out,
+                       hipStream_t s)
+{
+    hipLaunchKernelGGL(k_slq_finish, dim3(1), dim3(64), 0, s, part, iter_blocks(n), quad, t, U, ldu, r, out);
+}
+void launch_pc_sample(const double* L, int rp, const double* G1, int r, const double* G2, const HyperScalars* hd, int n, int tp,
+                      double* Z, hipStream_t s)
+{
+    assert((tp == 16 || tp == IT_MAXT) && rp % 64 == 0 && r >= 1 && r <= rp);
+    const dim3 grid((unsigned)(((size_t)n + ITER_ROWS - 1) / ITER_ROWS));
+    if (tp == 16) hipLaunchKernelGGL(k_pc_sample<1>, grid, dim3(256), 0, s, L, rp, G1, r, G2, hd, n, Z);
+    else hipLaunchKernelGGL(k_pc_sample<4>, grid, dim3(256), 0, s, L, rp, G1, r, G2, hd, n, Z);
 }
 // the mixed mode's cycle kernels (iter_device.h; the fp32 product and its launcher: iter32_gfx950.h)
 void launch_iter_goal_init(int tp, double rho2, double* sc, hipStream_t s)

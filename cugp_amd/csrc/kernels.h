@@ -513,6 +513,20 @@ void launch_iter_goal_init(int tp, double rho2, double* sc, hipStream_t s);
 void launch_iter_step_b_mx(const double* part, int n, int tp, double* sc, hipStream_t s);
 void launch_iter_step_v_mx(const double* part, int n, int tp, int final, double rho2, double* sc, hipStream_t s);
 void launch_iter_again(const double* b, double* x, double* r, int n, int tp, double* sc, hipStream_t s);
+// ---- the log marginal likelihood's value by Lanczos quadrature (iter_device.h, k_pc_sample: iter_gfx950.h)
+// a column's log of conjugate-gradient coefficients: rec [2][cap][IT_MAXT] (a_j, b_j), meta [ML_ROWS][IT_MAXT]
+enum { ML_LEN = 0, ML_CLOSED = 1, ML_BROKEN = 2, ML_W = 3, ML_ROWS = 4 };
+// start: an empty log and the start weight sc[wrow]; else the sweep's (a_j, b_j) appended, or the log closed
+void launch_iter_record(const double* sc, int tp, int start, int wrow, int cap, double* rec, double* meta, hipStream_t s);
+// quad[c] = w_c sum_i tau_i^2 log lambda_i of the Jacobi matrix of column c's log, c < cnt; work: 3 * cap * IT_MAXT doubles
+void launch_slq_quad(const double* rec, const double* meta, int cnt, int cap, double* work, double* quad, hipStream_t s);
+// out[0] = y'alpha from part (k_iter_dot's shares over n rows of [n][16] blocks), out[1] = (1 / t) sum quad[p] in probe order,
+// out[2] = -2 sum_(j < r) log U[j][j] (row stride ldu)
+void launch_slq_finish(const double* part, int n, const double* quad, int t, const double* U, int ldu, int r, double* out,
+                       hipStream_t s);
+// Z [n][tp] = L G1 + sn G2: L [n][rp] (rp a multiple of 64), G1 [r][tp] (r <= rp rows, none read beyond), G2 [n][tp], tp = 16 | 64
+void launch_pc_sample(const double* L, int rp, const double* G1, int r, const double* G2, const HyperScalars* hd, int n, int tp,
+                      double* Z, hipStream_t s);
 // ---- the pathwise posterior draws (iter_rff_gfx950.h): out[i][c] = amp sum_k cos(b_k + sum_f (xq_if -
 // org_f) Om[k][f] s_f) W[k][c], i < nq, k < m, c < tp = 16 | 64; s_f the handle's weights (ARD descriptor) or 1 / sqrt(ell_sq);
 // Phi is never stored.  org: d doubles in device memory (zeros for no origin).  pl = rff_apply_plan(nq, m, .): iter_apply_plan's

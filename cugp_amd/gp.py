@@ -731,7 +731,7 @@ class IterativeGP:
     """The exact GP of all n rows without any n x n matrix (cugp_iter_*): products with K = Kf + sn2 I whose entries are
     computed in registers, conjugate gradients on them, exact predictive mean and variance at O(n t) memory.  kernel / ard
     as Covsum's (the rational quadratic names included), the hyper-parameter vector too.  loglik_grad estimates the
-    log-likelihood's gradient from probe vectors; its value is not provided.  Vectors are target-major, [t, n]."""
+    log-likelihood's gradient from probe vectors, loglik its value too (Lanczos quadrature).  Vectors are target-major, [t, n]."""
 
     def __init__(self, n, d, kernel="se", ard=False, device=0):
         self.n, self.d, self.device = int(n), int(d), int(device)
@@ -853,6 +853,46 @@ class IterativeGP:
         check(capi.lib().cugp_iter_loglik_grad(self._h, ptr(Z), Z.shape[0], float(tol), int(max_iter), int(check_every), ptr(g),
                                                C.byref(quad), ptr(solves)))
         return g, {"solves": solves, "quad": quad.value}
+
+    def loglik(self, probes, probes_factor=None, rng=None, grad=True, tol=1e-10, max_iter=1000, check_every=10):
+        """The log marginal likelihood's value by stochastic Lanczos quadrature, and its gradient, from ONE set of probe
+        solves (cugp_iter_loglik): {"ll", "g" [nh] or None, "quad" [t], "logdet_precond", "solves" [t, 4], "y_alpha"}.
+        Rank 0: probes [t, n] are the z_p (E[z z'] = I), g is loglik_grad's in bits.  With a preconditioner of achieved rank
+        r the probes are z = L g1 + sn g2 ~ (0, M): probes is G2 [t, n], probes_factor G1 [t, r].  An int t with rng draws
+        Rademacher rows for both.  The same arrays give the same bits; fits first where there is no valid fit."""
+        r = self.precond_info()["achieved"]
+        if isinstance(probes, (int, np.integer)):
+            if rng is None:
+                raise ValueError("drawing the probes needs rng, a numpy.random.Generator")
+            G2 = rademacher(rng, int(probes), self.n)
+            G1 = rademacher(rng, int(probes), r) if r else None
+        else:
+            G2 = self._block(probes)
+            G1 = None
+            if r:
+                if probes_factor is None:
+                    raise ValueError("a preconditioned handle needs probes_factor [t, %d] beside the probes" % r)
+                G1 = f64(probes_factor).reshape(-1, r)
+                if G1.shape[0] != G2.shape[0]:
+                    raise ValueError("expected probes_factor [%d, %d]" % (G2.shape[0], r))
+        t = G2.shape[0]
+        g, quad, solves = (np.empty(self.nh) if grad else None), np.empty(t), np.empty((t, 4))
+        ll, ldm, ya = C.c_double(), C.c_double(), C.c_double()
+        check(capi.lib().cugp_iter_loglik(self._h, ptr(G2), None if G1 is None else ptr(G1), t, float(tol), int(max_iter),
+                                          int(check_every), C.byref(ll), ptr(g) if grad else None, ptr(quad), C.byref(ldm),
+                                          C.byref(ya), ptr(solves)))
+        return {"ll": ll.value, "g": g, "quad": quad, "logdet_precond": ldm.value, "solves": solves, "y_alpha": ya.value}
+
+    def precond_sample(self, G1, G2):
+        """Z [t, n] = L G1 + sn G2, rows distributed as (0, M) for standard G1 [t, r], G2 [t, n] (cugp_iter_precond_sample);
+        r the achieved rank, above 0."""
+        G2 = self._block(G2)
+        G1 = f64(G1).reshape(G2.shape[0], -1)
+        if G1.shape[1] != self.precond_info()["achieved"]:
+            raise ValueError("expected G1 [%d, achieved rank]" % G2.shape[0])
+        out = np.empty_like(G2)
+        check(capi.lib().cugp_iter_precond_sample(self._h, ptr(G1), ptr(G2), G2.shape[0], ptr(out)))
+        return out
 
     def predict(self, Xt, var=True, tol=1e-10, max_iter=1000, check_every=10):
         """(mean, var, info [nt, 4]) at the test points, var with sn2 as Covsum's; var=False: (mean, None, None), no solve."""

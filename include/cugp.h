@@ -886,7 +886,7 @@ int cugp_bcm_cg_solve_ard(cugp_bcm *b, int budget, double *trace, int trace_cap,
  * theta and a handful of n x 64 vectors: K = Kf + sn2 I of ALL n rows is applied to blocks of vectors with its entries
  * computed in registers (k_cov_apply, fp64 MFMA), and K^-1 b comes from conjugate gradients on that product -- the exact
  * predictive mean and variance at O(n t) memory.  The gradient of the log marginal likelihood comes as a Hutchinson
- * estimate from the caller's probe vectors (cugp_iter_loglik_grad below); its value (the log-determinant) is not provided.
+ * estimate from the caller's probe vectors (cugp_iter_loglik_grad below), its value by Lanczos quadrature on the same solves (cugp_iter_loglik).
  * Without a preconditioner (below) the sweep count grows with cond(K).
  *
  * Model: kernel in {CUGP_KERNEL_SE, _MATERN32, _MATERN52, CUGP_KERNEL_RQ}, ard in {0, 1}; theta as the dense handles'
@@ -981,6 +981,40 @@ int cugp_iter_precond_info(cugp_iter *h, int out[4]);
 int cugp_iter_get_precond(cugp_iter *h, double *L, int *piv);
 int cugp_iter_precond_apply(cugp_iter *h, const double *V, int t, double *out);
 int cugp_iter_precond_plan(int n, int rank, int out[4]);
+/* The value of the log marginal likelihood by stochastic Lanczos quadrature.
+ * cugp_iter_loglik : from ONE set of probe solves,
+ *          *ll = -1/2 y'alpha - 1/2 logdet - (n/2) 1.83787,   logdet = log|M| + (1/t) sum_p quad_p,
+ *      (1.83787: the literal for log 2 pi that cugp_loglik uses) and, g not NULL, g [nh] as cugp_iter_loglik_grad's.  Each probe
+ *      solve u_p = K^-1 z_p is a conjugate-gradient recurrence whose coefficients (a_j, b_j) are the Lanczos tridiagonal T_p of
+ *      K started at z_p (preconditioned: of M^-1/2 K M^-1/2 started at M^-1/2 z_p); they are logged on the device
+ *      (k_iter_record) and quad_p = w_p sum_i tau_i^2 log lambda_i is the Gauss quadrature of z~' log(.) z~ from T_p's
+ *      eigenvalues lambda and first eigenvector components tau (k_slq_quad; w_p = z_p'z_p, preconditioned z_p' M^-1 z_p).
+ *      Rank 0: Z [t][n] are the probes z_p (E[z z'] = I makes the estimate unbiased, Z = sqrt(n) I exact up to quadrature
+ *      convergence), G1 is not read, log|M| = 0 and g equals cugp_iter_loglik_grad's g for the same Z bit for bit.  Achieved
+ *      rank r > 0: the probes are z_p = L g1_p + sn g2_p ~ (0, M) (cugp_iter_precond_sample's product) from Z = G2 [t][n] and
+ *      G1 [t][r]; the gradient's trace term is (1/t) sum_p u_p' (dK/dtheta_h) v_p with v_p = M^-1 z_p (E[u v'] = K^-1); and
+ *      log|M| = (n - r) log sn2 + 2 sum log diag(Lc), Lc the Cholesky factor of sn2 I + L'L the build keeps.
+ *      Truncation rule: a column's log closes the first time the column is found outside the active state -- when its
+ *      recurrence reaches tol |z| (that sweep's step length still counts), at a breakdown, or never opened (z = 0: quad 0) --
+ *      and never reopens: sweeps after a failed true-residual check restart another Krylov space and are not logged.  A column
+ *      still active after max_iter sweeps is quadratured on all of them (info says it did not converge; *ll is finite).  A
+ *      broken column, an eigenvalue that is not positive and finite, or a QL iteration that has not split an eigenvalue off
+ *      in 30 sweeps gives quad_p = NaN, hence *ll = NaN, with CUGP_OK.  quad [t], logdet_precond (log|M|), y_alpha (y'alpha)
+ *      and info [t][4] (cugp_iter_solve's format) may be NULL.  A deterministic function of (X, y, theta, Z, G1, the solver's
+ *      arguments, the rank): equal bits on every call; cugp_iter_solve and cugp_iter_fit return the bits they returned before
+ *      it.  Fits first without a valid fit, as cugp_iter_loglik_grad does.  One host wait beyond the solves' status reads and
+ *      (g not NULL) the gradient forms' own.
+ * cugp_iter_precond_sample : out [t][n] = L G1 + sn G2 for G1 [t][r], G2 [t][n], r the achieved rank (k_pc_sample: fp64 MFMA,
+ *      k ascending 4 per instruction; then one product and one sum); any t, 64 columns a launch.
+ * Refused with CUGP_ERR_INVALID before any device call: a NULL h, Z, ll (G1, G2, out of _precond_sample); t < 1; bad solver
+ *      arguments; max_iter > CUGP_ITER_MAX_LOG; no data or theta; cugp_iter_loglik in the mixed mode (CUGP_ITER_MIXED: fp32
+ *      sweeps and cycle restarts do not form one Lanczos process); and, once the factor is built, G1 NULL at an achieved rank
+ *      above 0, cugp_iter_precond_sample at rank 0. */
+#define CUGP_ITER_MAX_LOG 16384      /* sweeps a recurrence's log holds: cugp_iter_loglik's max_iter at most */
+int cugp_iter_loglik(cugp_iter *h, const double *Z, const double *G1 /* NULL at rank 0 */, int t, double tol, int max_iter,
+                     int check_every, double *ll, double *g /* may be NULL: no gradient */, double *quad /* may be NULL */,
+                     double *logdet_precond /* may be NULL */, double *y_alpha /* may be NULL */, double *info /* may be NULL */);
+int cugp_iter_precond_sample(cugp_iter *h, const double *G1, const double *G2, int t, double *out);
 /* Mixed precision (off by default; DESIGN.md section 36, docs/ACCURACY.md "The fp32 product").
  * cugp_iter_set_precision(h, mode, cycle_drop): mode CUGP_ITER_FP64 (the default: every call launches what it launched
  *      before the mode existed and returns the same bits) or CUGP_ITER_MIXED.  In the mixed mode cugp_iter_solve, _fit,

@@ -4,7 +4,7 @@
 // and the step length, the update with r'r, the ratio, the new direction, then the true-residual pass, the poisoning of
 // broken columns, the closing pass over the still-active columns and k_iter_sum -- on a q the caller supplies (the product itself needs the MFMA), and k_iter_cross_rhs for one
 // isotropic and the rational quadratic instantiation; then the mixed mode's cycle kernels (check_mixed below) and the test-input
-// gradients' kernel with its finish (iter_xgrad_device.h; check_xgrad below).  Every output is compared BIT FOR BIT with the plain loops below in
+// gradients' kernel with its finish (iter_xgrad_device.h; check_xgrad below), and the Lanczos quadrature's k_iter_record and k_slq_quad (check_slq below).  Every output is compared BIT FOR BIT with the plain loops below in
 // the kernels' order of summation: the 16 row classes of a workgroup each in row order, the classes ascending, the
 // workgroups ascending.  Exit code 4: a mismatch.  A stand-alone program: the sanitizer is linked in, nothing is preloaded.
 #include "host_emul.h"
@@ -228,10 +228,130 @@ bool check_xgrad(int nt, int n, int d, int tp, int split, const char* what)
     for (double* v : {Xt, X, wm, Wv, hdw, part, om, ov}) free(v);
     return ok;
 }
+
+// ---- the Lanczos quadrature's one-workgroup kernels (k_iter_record, k_slq_quad; iter_device.h): eight sweeps of scalars the
+// program lays out itself, a scenario per column -- active to the end, a candidate at sweep 3 that restarts and runs on (its
+// later sweeps must not be logged), broken at sweep 2, done and broken from the start, a candidate at sweep 0, the rest closing
+// at sweep c mod 8 -- then every log's quadrature, bit for bit against the plain loops below (the same QL iteration on
+// contiguous arrays).  The quadrature's first two moments (sum tau^2 = 1, sum tau^2 lambda = T_00) are checked beside the bits.
+constexpr int SQ_CAP = 12, SQ_SWEEPS = 8;
+double sq_a(int c, int j) { return 0.5 + 0.03125 * (double)((c + 1) * (j + 1) % 7); }
+double sq_b(int c, int j) { return 0.75 / (double)(j + 1 + c % 5); }
+double sq_state(int c, int j)      // the column's state as k_iter_record finds it behind sweep j (-1: the start)
+{
+    if (c == 3) return ST_DONE;
+    if (c == 4) return ST_BROKEN;
+    if (c == 2) return j >= 2 ? ST_BROKEN : ST_ACTIVE;
+    if (c == 0) return ST_ACTIVE;
+    const int close = c == 1 ? 3 : c == 5 ? 0 : c % SQ_SWEEPS;
+    if (j < close) return ST_ACTIVE;
+    return j == close ? ST_CANDIDATE : (j == close + 1 ? ST_RESTART : ST_ACTIVE);
+}
+double ref_quad(const std::vector<double>& a, const std::vector<double>& b, double w, bool broken, bool* moments)
+{
+    const int m = (int)a.size();
+    if (broken) return __builtin_nan("");
+    if (m == 0) return 0.0;
+    std::vector<double> dg(m), of(m), tau(m, 0.0);
+    for (int j = 0; j < m; j++) {
+        dg[j] = j == 0 ? 1.0 / a[j] : 1.0 / a[j] + b[j - 1] / a[j - 1];
+        of[j] = j + 1 < m ? __builtin_sqrt(b[j]) / a[j] : 0.0;
+    }
+    tau[0] = 1.0;
+    const double t00 = dg[0];
+    for (int l = 0; l < m; l++)
+        for (int iter = 0;; iter++) {
+            int mm = l;
+            for (; mm < m - 1; mm++) {
+                const double dd = std::fabs(dg[mm]) + std::fabs(dg[mm + 1]);
+                if (std::fabs(of[mm]) + dd == dd) break;
+            }
+            if (mm == l) break;
+            if (iter == 30) return __builtin_nan("");
+            double g = (dg[l + 1] - dg[l]) / (2.0 * of[l]), r = __builtin_sqrt(g * g + 1.0);
+            g = dg[mm] - dg[l] + of[l] / (g + (g >= 0.0 ? r : -r));
+            double s = 1.0, cs = 1.0, p = 0.0;
+            int i = mm - 1;
+            for (; i >= l; i--) {
+                double f = s * of[i];
+                const double bb = cs * of[i];
+                r = __builtin_sqrt(f * f + g * g);
+                of[i + 1] = r;
+                if (r == 0.0) { dg[i + 1] = dg[i + 1] - p; of[mm] = 0.0; break; }
+                s = f / r; cs = g / r;
+                g = dg[i + 1] - p;
+                r = (dg[i] - g) * s + 2.0 * cs * bb;
+                p = s * r;
+                dg[i + 1] = g + p;
+                g = cs * r - bb;
+                f = tau[i + 1];
+                tau[i + 1] = s * tau[i] + cs * f;
+                tau[i] = cs * tau[i] - s * f;
+            }
+            if (r == 0.0 && i >= l) continue;
+            dg[l] = dg[l] - p; of[l] = g; of[mm] = 0.0;
+        }
+    for (int i = 1; i < m; i++)
+        for (int k = i; k > 0 && dg[k - 1] > dg[k]; k--) { std::swap(dg[k - 1], dg[k]); std::swap(tau[k - 1], tau[k]); }
+    double s = 0.0, m0 = 0.0, m1 = 0.0;
+    for (int i = 0; i < m; i++) {
+        if (!(dg[i] > 0.0 && dg[i] - dg[i] == 0.0)) return __builtin_nan("");
+        const double term = (tau[i] * tau[i]) * log(dg[i]);
+        s = i == 0 ? term : s + term;
+        m0 += tau[i] * tau[i]; m1 += tau[i] * tau[i] * dg[i];
+    }
+    *moments = *moments && std::fabs(m0 - 1.0) < 1e-13 && std::fabs(m1 - t00) < 1e-13 * t00;
+    return w * s;
+}
+bool check_slq(int tp)
+{
+    auto blk = [&](size_t c) { double* p = (double*)malloc(c * 8); for (size_t i = 0; i < c; i++) p[i] = -7.0; return p; };
+    double *sc = blk(SC_ALLOC * IT_MAXT), *rec = blk((size_t)2 * SQ_CAP * IT_MAXT), *meta = blk(ML_ROWS * IT_MAXT);
+    double *work = blk((size_t)3 * SQ_CAP * IT_MAXT), *quad = blk(IT_MAXT);
+    std::vector<double> rrec((size_t)2 * SQ_CAP * IT_MAXT, -7.0), rmeta(ML_ROWS * IT_MAXT, -7.0), rquad(IT_MAXT, -7.0);
+    for (int c = 0; c < tp; c++) { sc[SC_STATE * IT_MAXT + c] = sq_state(c, -1); sc[SC_RZ * IT_MAXT + c] = 3.0 + c; }
+    launch(1, [&] { k_iter_record(sc, tp, 1, SC_RZ, SQ_CAP, rec, meta); });
+    for (int j = 0; j < SQ_SWEEPS; j++) {
+        for (int c = 0; c < tp; c++) {
+            sc[SC_STATE * IT_MAXT + c] = sq_state(c, j);
+            sc[SC_A * IT_MAXT + c] = sq_a(c, j);
+            sc[SC_B * IT_MAXT + c] = sq_b(c, j);
+        }
+        launch(1, [&] { k_iter_record(sc, tp, 0, 0, SQ_CAP, rec, meta); });
+    }
+    launch(1, [&] { k_slq_quad(rec, meta, tp, SQ_CAP, work, quad); });
+    bool moments = true;
+    int lens = 0;
+    for (int c = 0; c < tp; c++) {
+        std::vector<double> a, b;
+        bool closed = false, broken = false;
+        for (int j = 0; j < SQ_SWEEPS && !closed; j++) {
+            const double st = sq_state(c, j);
+            if (st == ST_ACTIVE) { a.push_back(sq_a(c, j)); b.push_back(sq_b(c, j)); continue; }
+            closed = true;
+            broken = st == ST_BROKEN;
+            if (st == ST_CANDIDATE) { a.push_back(sq_a(c, j)); b.push_back(0.0); }
+        }
+        for (size_t j = 0; j < a.size(); j++) { rrec[j * IT_MAXT + c] = a[j]; rrec[(SQ_CAP + j) * IT_MAXT + c] = b[j]; }
+        rmeta[ML_LEN * IT_MAXT + c] = (double)a.size();
+        rmeta[ML_CLOSED * IT_MAXT + c] = closed ? 1.0 : 0.0;
+        rmeta[ML_BROKEN * IT_MAXT + c] = broken ? 1.0 : 0.0;
+        rmeta[ML_W * IT_MAXT + c] = 3.0 + c;
+        rquad[c] = ref_quad(a, b, 3.0 + c, broken, &moments);
+        lens += (int)a.size();
+    }
+    bool ok = same_bits(rec, rrec.data(), rrec.size(), "log") && same_bits(meta, rmeta.data(), rmeta.size(), "log meta") &&
+              same_bits(quad, rquad.data(), IT_MAXT, "quadrature");
+    ok = ok && moments && lens > 3 * tp && quad[3] == 0.0 && quad[2] != quad[2] && quad[4] != quad[4] && rmeta[ML_LEN * IT_MAXT + 1] == 4.0;
+    for (double* v : {sc, rec, meta, work, quad}) free(v);
+    return ok;
+}
 }  // namespace
 
 int main(int argc, char** argv)
 {
+    // `--slq` (a mode of its own, no files): k_iter_record and k_slq_quad at both block widths
+    if (argc == 2 && strcmp(argv[1], "--slq") == 0) return check_slq(16) && check_slq(IT_MAXT) ? 0 : 4;
     // input: ints n tp d count, doubles hd[3 + d + 2] X[n d] Xt[count d] b[n tp] q[n tp] -> output: x r p sc R_se R_rq
     // `--xgrad` (a mode of its own: the data is the program's, no files): k_cov_xgrad and its finish, (nt, n, d, tp, split)
     if (argc == 2 && strcmp(argv[1], "--xgrad") == 0) {

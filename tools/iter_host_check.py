@@ -10,6 +10,9 @@ the program's own, a scenario per column: the tolerance reached, the goal reache
 stall flagged, a last leg close above the tolerance flagged and not flagged, NaN in r'r, in a true residual and in b, final = 1.
 k_cov_xgrad and k_cov_xgrad_finish (iter_xgrad_device.h) run once, on data of the program's own: ragged nt and n, d = 17, two
 ranges, the mean-and-variance and the mean-only forms, bit for bit against plain loops in the kernel's order of summation.
+The Lanczos quadrature's k_iter_record and k_slq_quad run eight sweeps of a scenario per column -- logs
+that stay open, close as candidates and never reopen after a restart, break down, or never open -- and every log's quadrature,
+bit for bit against plain loops, with the quadrature's first two moments checked beside the bits.
 
     python tools/iter_host_check.py          # builds into a temporary directory; about a minute
 """
@@ -22,21 +25,22 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np  # noqa: E402
 import host_check  # noqa: E402  (also puts the repository root and tests/ on the path)
 
-XGRAD = ("--xgrad",)                 # the program's mode of its own for k_cov_xgrad: no input file
-CASES = ((1, 16, 3, 1), (65, 16, 3, 5), (513, 16, 17, 16), (1100, 64, 3, 33), XGRAD)      # (n, tp, d, test points)
+XGRAD, SLQ = ("--xgrad",), ("--slq",)   # the program's modes of their own for k_cov_xgrad and the Lanczos quadrature: no input file
+CASES = ((1, 16, 3, 1), (65, 16, 3, 5), (513, 16, 17, 16), (1100, 64, 3, 33), XGRAD, SLQ)      # (n, tp, d, test points)
+MODES = {XGRAD[0]: "k_cov_xgrad, four instantiations", SLQ[0]: "k_iter_record and k_slq_quad, a scenario per column, tp 16 and 64"}
 
 
-def run_xgrad(exe):
+def run_xgrad(exe, mode=XGRAD[0]):
     import subprocess
-    r = subprocess.run([exe, XGRAD[0]], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    r = subprocess.run([exe, mode], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
     ok = r.returncode == 0 and not r.stderr.strip()
-    print("k_cov_xgrad, four instantiations: bits equal the plain loops  %s" % ("ok" if ok else "BAD"), r.stdout[-2000:], r.stderr[-3000:])
+    print("%s: bits equal the plain loops  %s" % (MODES[mode], "ok" if ok else "BAD"), r.stdout[-2000:], r.stderr[-3000:])
     return ok
 
 
 def run(exe, tmp, n, tp=0, d=0, count=0):
-    if n == XGRAD[0]:
-        return run_xgrad(exe)
+    if n in MODES:
+        return run_xgrad(exe, n)
     import truth_ard_matern as tam
     import truth_rq as trq
     rng = np.random.default_rng(n + tp)
