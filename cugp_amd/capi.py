@@ -233,6 +233,10 @@ SIGNATURES = {
                                       _dp]),
     "cugp_iter_paths_eval": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "cugp_iter_paths_grad": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
+    "cugp_iter_varcache_build": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _ip]),
+    "cugp_iter_varcache_info": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_iter_varcache_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "cugp_iter_predict_cached": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

@@ -45,6 +45,12 @@ struct cugp_iter {
     // the Lanczos quadrature (cugp_iter_loglik): a solve's log of (a_j, b_j) with its lengths and start
     // weights, k_slq_quad's scratch, the probes' quadratures [t], the call's three sums, their pinned copy, G1 [r][tp]
     Scratch lrec, lmeta, lwork, lquad, lout, lhost, pg1;
+    // the variance cache (cugp_iter_varcache_build): Q, R [n][rp]; the working blocks W, W2, P [n][16];
+    // C = Q'W [rp][16] and its partial blocks; both passes' coefficients Hc [rp][16]; H, its factor S [rp][rp]; the small side
+    // (Ti [16][16], the columns' norms [16], a unit HyperScalars for k_pc_correct's division, ctl); k_cov_var's sums
+    bool vc_valid = false;         // Q, R, H hold for (data, theta); dropped by set_data, set_loghyper and a new build
+    int vc_rank = 0, vc_got = 0, vc_rp = 0, vc_products = 0, vc_reason = 0, vc_bw = 1;
+    Scratch vcQ, vcR, vcW, vcW2, vcP, vcC, vcpart, vcHc, vcH, vcS, vcsm, vcg;
 };
 
 namespace {
@@ -491,7 +497,8 @@ int cugp_iter_destroy(cugp_iter* h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (Scratch* v : {&h->vb, &h->vx, &h->vr, &h->vp, &h->vq, &h->vk, &h->alpha, &h->apart, &h->dpart, &h->xt, &h->res, &h->pL,
                        &h->pQ, &h->pdres, &h->pshv, &h->pint, &h->ppart, &h->pT, &h->vz, &h->gpart, &h->gout, &h->ghost, &h->xpart, &h->xout,
-                       &h->fom, &h->fb, &h->forg, &h->fw, &h->fout, &h->lrec, &h->lmeta, &h->lwork, &h->lquad, &h->lout, &h->lhost, &h->pg1})
+                       &h->fom, &h->fb, &h->forg, &h->fw, &h->fout, &h->lrec, &h->lmeta, &h->lwork, &h->lquad, &h->lout, &h->lhost, &h->pg1,
+                       &h->vcQ, &h->vcR, &h->vcW, &h->vcW2, &h->vcP, &h->vcC, &h->vcpart, &h->vcHc, &h->vcH, &h->vcS, &h->vcsm, &h->vcg})
         v->release();
     if (h->pf) cugp_destroy(h->pf);
     for (void* p : {(void*)h->dX, (void*)h->dyb, (void*)h->dhs, (void*)h->dsc})
@@ -526,6 +533,7 @@ int cugp_iter_set_data(cugp_iter* h, const double* X, const double* y)
     h->fit_valid = false;
     h->have_data = false;
     h->pc_built = false;
+    h->vc_valid = false;
     HIPCHK(hipMemcpyAsync(h->dX, X, (size_t)h->n * h->d * sizeof(double), hipMemcpyHostToDevice, h->stream));
     h->host.assign((size_t)h->n * 16, 0.0);
     for (size_t i = 0; i < (size_t)h->n; i++) h->host[i * 16] = y[i];
@@ -544,6 +552,7 @@ int cugp_iter_set_loghyper(cugp_iter* h, const double* theta, int nh)
     h->fit_valid = false;
     h->have_theta = false;
     h->pc_built = false;
+    h->vc_valid = false;
     h->theta.assign(theta, theta + nh);
     const double* sf = theta + nh - 2;
     *h->hhs = HyperScalars{h->route ? 1.0 : std::exp(theta[0] * 2), std::exp(sf[0] * 2), std::exp(sf[1] * 2)};
@@ -1123,5 +1132,176 @@ int cugp_iter_paths_grad(cugp_iter* h, const double* Xt, int nt, const double* O
     // the device block is [tp][nt][d]: its first s slabs are the caller's array
     HIPCHK(hipMemcpyAsync(out, h->xout.p, (size_t)s * nt * d * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
+    return CUGP_OK;
+}
+
+// ---- the variance cache ----
+
+int cugp_iter_varcache_build(cugp_iter* h, const double* B, int tb, int rank, int out[4])
+{
+    const char* call = "cugp_iter_varcache_build";
+    if (!h || !B || !out) return invalid_arg(call, "null argument");
+    if (tb < 1 || tb > 16) return invalid_arg(call, "tb must lie in [1, 16]");
+    if (rank < 1 || rank > CUGP_ITER_MAX_RANK) return invalid_arg(call, "rank must lie in [1, CUGP_ITER_MAX_RANK]");
+    if (rank > h->n) return invalid_arg(call, "rank beyond n");
+    int rc;
+    if ((rc = ready(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    h->vc_valid = false;
+    const CovFn cf = cov_of(h);
+    hipStream_t s = h->stream;
+    const int n = h->n, bw = tb, nblk = (rank + bw - 1) / bw;
+    const PcPlan pl = pc_plan(n, rank);
+    const int rp = pl.rp;
+    const size_t nb16 = (size_t)n * 16, small = 256 + 16 + 4 + 2;
+    if ((rc = h->vcQ.grow((size_t)n * rp, s)) || (rc = h->vcR.grow((size_t)n * rp, s)) || (rc = h->vcW2.grow(nb16, s)) ||
+        (rc = h->vcP.grow(nb16, s)) || (rc = h->vcC.grow((size_t)rp * 16, s)) || (rc = h->vcpart.grow((size_t)pl.blocks * rp * 16, s)) ||
+        (rc = h->vcHc.grow((size_t)rp * 16, s)) || (rc = h->vcH.grow((size_t)rp * rp, s)) || (rc = h->vcS.grow((size_t)rp * rp, s)) ||
+        (rc = h->vcsm.grow(small, s)) || (rc = h->dpart.grow((size_t)iter_blocks(n) * IT_MAXT, s)))
+        return rc;
+    if ((rc = pack(h, B, n, 0, tb, 16, h->vcW))) return rc;          // the start block: [n][16], zero beyond tb
+    double *Q = h->vcQ.p, *W = h->vcW.p, *W2 = h->vcW2.p, *P = h->vcP.p, *C = h->vcC.p, *Hc = h->vcHc.p, *H = h->vcH.p;
+    double *Ti = h->vcsm.p, *nrm0 = Ti + 256;
+    HyperScalars* unit = (HyperScalars*)(nrm0 + 16);
+    int* ctl = (int*)(nrm0 + 16 + 4);
+    const HyperScalars one{1.0, 1.0, 1.0};
+    HIPCHK(hipMemcpyAsync(unit, &one, sizeof one, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(Q, 0, (size_t)n * rp * sizeof(double), s));
+    HIPCHK(hipMemsetAsync(H, 0, (size_t)rp * rp * sizeof(double), s));
+    launch_vc_init(ctl, s);
+    // C = Q'V over all rp columns (those not yet filled are zeros)
+    auto project = [&](const double* V) {
+        launch_pc_project(Q, V, 16, 16, n, pl, h->vcpart.p, s);
+        launch_pc_project_finish(h->vcpart.p, pl.blocks, (size_t)rp * 16, C, s);
+    };
+    auto norms = [&](const double* V) {
+        launch_iter_dot(V, V, n, 16, h->dpart.p, s);
+        launch_iter_sum(h->dpart.p, n, 16, nrm0, s);
+    };
+    // CholQR twice on the cw columns of src at slot c0: -> P, and Q's slot; the second round records block column c0p of H
+    auto orthonormalise = [&](double* src, double* tmp, int c0, int cw, int record, int c0p) {
+        launch_vc_place(src, Q, rp, c0, cw, n, s);
+        project(src);
+        launch_vc_factor(C, c0, cw, 0, 0, nrm0, Ti, Hc, H, rp, c0p, ctl, s);
+        launch_vc_scale(src, Ti, tmp, Q, rp, c0, cw, n, s);
+        project(tmp);
+        launch_vc_factor(C, c0, cw, 1, record, nrm0, Ti, Hc, H, rp, c0p, ctl, s);
+        launch_vc_scale(tmp, Ti, P, Q, rp, c0, cw, n, s);
+    };
+    norms(W);
+    orthonormalise(W, W2, 0, std::min(bw, rank), 0, 0);
+    const IterPlan ap = iter_apply_plan(n, n, h->split);
+    if (ap.split > 1 && (rc = h->apart.grow((size_t)ap.split * n * 16, s))) return rc;
+    for (int j = 0; j < nblk; j++) {
+        const int c0p = j * bw, c0 = std::min(rank, c0p + bw);       // the block multiplied; where the next one starts
+        launch_cov_apply(h->dX, n, h->dX, n, h->d, cf, P, 16, W, h->apart.p, ap, true, s);
+        norms(W);
+        project(W);
+        launch_vc_hacc(C, Hc, rp, 1, ctl, s);
+        if (j == nblk - 1) {                                         // the last block column of H: nothing to orthonormalise
+            launch_vc_factor(C, c0, 0, 2, 1, nrm0, Ti, Hc, H, rp, c0p, ctl, s);
+            break;
+        }
+        launch_pc_correct(Q, rp, C, 16, 0, W, unit, n, 16, W2, 16, s);
+        project(W2);
+        launch_vc_hacc(C, Hc, rp, 0, ctl, s);
+        launch_pc_correct(Q, rp, C, 16, 0, W2, unit, n, 16, W, 16, s);
+        orthonormalise(W, W2, c0, std::min(bw, rank - c0), 1, c0p);
+    }
+    launch_vc_finish(H, h->vcS.p, Q, h->vcR.p, rp, bw, n, ctl, s);
+    int hctl[VC_CTL] = {0, 0, 0, 0};
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(hctl, ctl, sizeof hctl, hipMemcpyDeviceToHost, s);
+    if ((rc = sync_or_fail(s, call, e))) return rc;
+    h->vc_rank = rank;
+    h->vc_got = std::max(0, std::min(hctl[VC_GOT], rank));
+    h->vc_rp = rp;
+    h->vc_bw = bw;
+    h->vc_products = hctl[VC_PRODUCTS];
+    h->vc_reason = hctl[VC_REASON];
+    h->vc_valid = true;
+    out[0] = h->vc_got; out[1] = rp; out[2] = h->vc_products; out[3] = h->vc_reason;
+    return CUGP_OK;
+}
+
+int cugp_iter_varcache_info(cugp_iter* h, int out[4])
+{
+    if (!h || !out) return invalid_arg("cugp_iter_varcache_info", "null argument");
+    out[0] = h->vc_valid ? h->vc_got : 0;
+    out[1] = h->vc_valid ? h->vc_rp : 0;
+    out[2] = h->vc_valid ? h->vc_products : 0;
+    out[3] = h->vc_valid ? h->vc_reason : 0;
+    return CUGP_OK;
+}
+
+int cugp_iter_varcache_get(cugp_iter* h, double* Q, double* R, double* H)
+{
+    const char* call = "cugp_iter_varcache_get";
+    if (!h) return invalid_arg(call, "null handle");
+    if (!h->vc_valid) return invalid_arg(call, "no cache for the data and hyper-parameters as they stand (cugp_iter_varcache_build)");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = h->n, rp = h->vc_rp, got = h->vc_got;
+    if (got == 0) return CUGP_OK;
+    for (int which = 0; which < 2; which++) {
+        double* dst = which ? R : Q;
+        if (!dst) continue;
+        h->host.resize(n * rp);
+        HIPCHK(hipMemcpyAsync(h->host.data(), which ? h->vcR.p : h->vcQ.p, n * rp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (size_t m = 0; m < got; m++)
+            for (size_t i = 0; i < n; i++) dst[m * n + i] = h->host[i * rp + m];
+    }
+    if (H) {                                            // what was factored: k_vc_hsym's arithmetic on the coefficients
+        h->host.resize(rp * rp);
+        HIPCHK(hipMemcpyAsync(h->host.data(), h->vcH.p, rp * rp * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        const size_t bw = h->vc_bw;
+        for (size_t i = 0; i < got; i++)
+            for (size_t j = 0; j < got; j++) {
+                const double hij = h->host[i * rp + j], hji = h->host[j * rp + i];
+                H[i * got + j] = i / bw == j / bw ? (hij + hji) * 0.5 : i / bw < j / bw ? hij : hji;
+            }
+    }
+    return CUGP_OK;
+}
+
+int cugp_iter_predict_cached(cugp_iter* h, const double* Xt, int nt, int with_noise, double* mean, double* var)
+{
+    const char* call = "cugp_iter_predict_cached";
+    if (!h || !Xt || !var) return invalid_arg(call, "null argument");
+    if (nt < 1) return invalid_arg(call, "nt must be positive");
+    if (nt > CUGP_ITER_MAX_N) return invalid_arg(call, "nt beyond CUGP_ITER_MAX_N");
+    if (!h->vc_valid) return invalid_arg(call, "no cache for the data and hyper-parameters as they stand (cugp_iter_varcache_build)");
+    if (mean && !h->fit_valid) return invalid_arg(call, "the mean needs a fit for the data and hyper-parameters as they stand (cugp_iter_fit)");
+    int rc;
+    if ((rc = ready(h, call))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    const CovFn cf = cov_of(h);
+    hipStream_t s = h->stream;
+    if ((rc = h->xt.grow((size_t)nt * h->d, s))) return rc;
+    HIPCHK(hipMemcpyAsync(h->xt.p, Xt, (size_t)nt * h->d * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (mean) {                                         // cugp_iter_predict's own launches: its bits
+        if ((rc = h->res.grow((size_t)nt * 16, s))) return rc;
+        if ((rc = product(h, cf, h->xt.p, nt, h->alpha.p, 16, h->res.p, false))) return rc;
+        if ((rc = sync_or_fail(s, call, hipGetLastError()))) return rc;
+        if ((rc = unpack(h, h->res.p, nt, 0, 1, 16, mean))) return rc;
+    }
+    const double prior = h->hhs->signal_var + (with_noise ? h->hhs->noise_var : 0.0);
+    if (h->vc_got == 0) {                               // an empty basis: the prior, no launch
+        std::fill(var, var + nt, prior);
+        return CUGP_OK;
+    }
+    const IterPlan pl = iter_apply_plan(nt, h->n, h->split);
+    const int rp = h->vc_rp, nz = (rp + VC_NCT * 16 - 1) / (VC_NCT * 16);
+    if ((rc = h->vcg.grow((size_t)(nz + 1) * nt, s))) return rc;
+    if (pl.split > 1 && (rc = h->vcpart.grow((size_t)pl.split * nt * rp, s))) return rc;
+    double* sq = h->vcg.p + (size_t)nz * nt;
+    launch_cov_var(h->xt.p, nt, h->dX, h->n, h->d, cf, h->vcR.p, rp, h->vcpart.p, h->vcg.p, sq, pl, s);
+    h->host.resize(nt);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->host.data(), sq, (size_t)nt * sizeof(double), hipMemcpyDeviceToHost, s);
+    if ((rc = sync_or_fail(s, call, e))) return rc;
+    for (int i = 0; i < nt; i++) var[i] = prior - h->host[i];
     return CUGP_OK;
 }

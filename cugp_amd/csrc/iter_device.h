@@ -666,3 +666,161 @@ __global__ __launch_bounds__(64) void k_slq_finish(const double* __restrict__ pa
         out[2] = -2.0 * s;
     }
 }
+
+// ---- the variance cache's small kernels (cugp_iter_varcache_build; the tall kernels and every
+// launcher: iter_varcache_gfx950.h).  ctl: VC_GOT columns accepted so far, VC_REASON 0 | 1 basis ended | 2 pivot ended,
+// VC_PRODUCTS products whose block was live, VC_LIVE live columns of the block orthonormalised last ----
+
+__global__ __launch_bounds__(64) void k_vc_init(int* __restrict__ ctl)
+{
+    if (threadIdx.x < VC_CTL) ctl[threadIdx.x] = 0;
+}
+
+// Hc = C (first; a live block's product is counted) or Hc = Hc + C: the two Gram-Schmidt passes' coefficients, [rp][16]
+__global__ __launch_bounds__(256) void k_vc_hacc(const double* __restrict__ Cm, double* __restrict__ Hc, int cnt, int first,
+                                                 int* __restrict__ ctl)
+{
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < cnt) Hc[e] = first ? Cm[e] : Hc[e] + Cm[e];
+    if (first && e == 0 && ctl[VC_LIVE] > 0) ctl[VC_PRODUCTS] = ctl[VC_PRODUCTS] + 1;
+}
+
+// One workgroup: a round of CholQR on the block of cw columns at c0, and the block column of H behind the second round.
+//   G = rows [c0, c0 + cw) of C = Q'W (the block lies in its slot of Q: its Gram matrix) = T'T, T upper triangular, by thread 0
+//   in column order; Ti = T^-1 (zero beyond the live columns) for k_vc_scale.
+//   mode 0, first round: pivot c is the column's squared norm after both projection passes and the block's earlier columns; the
+//     basis ends at the first c with pivot <= VC_FLOOR (c0 + c + 1) u nrm0[c] (nrm0: the squared norm before projection), or not
+//     finite: VC_GOT = c0 + c, VC_REASON = 1.  A basis that ended before: no live column.
+//   mode 1, second round on the VC_LIVE columns of the first: ends only at a pivot that is not positive and finite.
+//   mode 2: no round (the last block's product: nothing is orthonormalised behind it).
+//   record (modes 1, 2): block column c0p of H, rows r < c0 and columns c0p + b < c0, from Hc -- both passes' Q'(K P), the
+//     product's block P measured against every column up to its own.  The rows below, of the block orthonormalised here, are
+//     not taken from T: a ragged last block keeps fewer columns than the product has, and the entry's mirror image in the block
+//     column of the NEXT product is complete (k_vc_hsym).
+__global__ __launch_bounds__(256) void k_vc_factor(const double* __restrict__ Cm, int c0, int cw, int mode, int record,
+                                                   const double* __restrict__ nrm0, double* __restrict__ Ti,
+                                                   const double* __restrict__ Hc, double* __restrict__ H, int rp, int c0p,
+                                                   int* __restrict__ ctl)
+{
+#pragma clang fp contract(off)
+    __shared__ double G[16][17], T[16][17], V[16][17];
+    __shared__ int live_s;
+    const int tid = threadIdx.x, a = tid >> 4, b = tid & 15;
+    if (mode == 1) cw = ctl[VC_LIVE] < cw ? ctl[VC_LIVE] : cw;
+    if (mode == 0 && ctl[VC_REASON] != 0) cw = 0;
+    if (mode == 2) cw = 0;
+    G[a][b] = (a < cw && b < cw) ? Cm[(size_t)(c0 + a) * 16 + b] : 0.0;
+    T[a][b] = 0.0;
+    V[a][b] = 0.0;
+    __syncthreads();
+    if (tid == 0) {
+        int live = cw;
+        for (int c = 0; c < cw; c++) {
+            double p = G[c][c];
+            for (int m = 0; m < c; m++) p = p - T[m][c] * T[m][c];
+            const double floor = mode == 0 ? VC_FLOOR * (double)(c0 + c + 1) * 1.1102230246251565e-16 * nrm0[c] : 0.0;
+            if (!(p > floor) || !(p < INFINITY)) { live = c; break; }
+            const double t = __builtin_sqrt(p);
+            T[c][c] = t;
+            for (int q = c + 1; q < cw; q++) {
+                double v = G[c][q];
+                for (int m = 0; m < c; m++) v = v - T[m][c] * T[m][q];
+                T[c][q] = v / t;
+            }
+        }
+        for (int q = 0; q < live; q++) {               // V = T^-1 over the live columns, column q upwards from the diagonal
+            V[q][q] = 1.0 / T[q][q];
+            for (int r = q - 1; r >= 0; r--) {
+                double s = 0.0;
+                for (int m = r + 1; m <= q; m++) s = s + T[r][m] * V[m][q];
+                V[r][q] = -s / T[r][r];
+            }
+        }
+        live_s = live;
+        if (mode != 2) {
+            if (live < cw) { ctl[VC_GOT] = c0 + live; ctl[VC_REASON] = 1; }
+            else if (mode == 0 && cw > 0) ctl[VC_GOT] = c0 + cw;
+            ctl[VC_LIVE] = live;
+        }
+    }
+    __syncthreads();
+    const int live = live_s;
+    if (mode != 2) Ti[tid] = (a < live && b < live) ? V[a][b] : 0.0;
+    if (!record) return;
+    for (int e = tid; e < c0 * 16; e += 256)
+        if (c0p + (e & 15) < c0) H[(size_t)(e >> 4) * rp + c0p + (e & 15)] = Hc[e];
+}
+
+// S = the symmetric matrix the factor is taken of, over the leading VC_GOT rows and columns (blocks of bw): a diagonal block
+// is (H + H') / 2 (the sum is commutative: S is symmetric to the bit), every other entry the one of H's UPPER block triangle --
+// Q_i'(K P_j), i < j, measured by the projections -- on both sides.  Beyond VC_GOT: the identity.
+__global__ __launch_bounds__(256) void k_vc_hsym(const double* __restrict__ H, double* __restrict__ S, int rp, int bw,
+                                                 const int* __restrict__ ctl)
+{
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * 256 + threadIdx.x, got = ctl[VC_GOT];
+    if (e >= rp * rp) return;
+    const int i = e / rp, j = e % rp, bi = i / bw, bj = j / bw;
+    const double hij = H[(size_t)i * rp + j], hji = H[(size_t)j * rp + i];
+    S[e] = (i < got && j < got) ? (bi == bj ? (hij + hji) * 0.5 : bi < bj ? hij : hji) : (i == j ? 1.0 : 0.0);
+}
+
+// One workgroup: S = L L' in place over the leading VC_GOT columns (lower triangle; right-looking, a column at a time, every
+// entry's updates in ascending column order).  Column c's scaled entries go through LDS; the trailing update walks rows four
+// at a time per wave (wave w: rows c + 1 + w, + 4, ...), a wave's lanes along the row: row-contiguous reads and writes.
+// A pivot that is not positive and finite ends the factor there: VC_GOT = c, VC_REASON = 2; k_vc_rsolve reads no column beyond.
+__global__ __launch_bounds__(256) void k_vc_chol(double* __restrict__ S, int rp, int* __restrict__ ctl)
+{
+#pragma clang fp contract(off)
+    __shared__ double col[PCH_MAX_RANK];
+    const int tid = threadIdx.x, ty = tid >> 6, tx = tid & 63;
+    const int got = ctl[VC_GOT];
+    for (int c = 0; c < got; c++) {
+        __syncthreads();
+        const double piv = S[(size_t)c * rp + c];
+        if (!(piv > 0.0) || !(piv < INFINITY)) {
+            if (tid == 0) { ctl[VC_GOT] = c; ctl[VC_REASON] = 2; }
+            return;
+        }
+        const double l = __builtin_sqrt(piv);
+        for (int i = c + 1 + tid; i < got; i += 256) {
+            const double v = S[(size_t)i * rp + c] / l;
+            S[(size_t)i * rp + c] = v;
+            col[i] = v;
+        }
+        __syncthreads();
+        if (tid == 0) S[(size_t)c * rp + c] = l;
+        for (int i = c + 1 + ty; i < got; i += 4) {
+            const double li = col[i];
+            for (int j = c + 1 + tx; j <= i; j += 64) S[(size_t)i * rp + j] = S[(size_t)i * rp + j] - li * col[j];
+        }
+    }
+}
+
+// s[i] = the squared norm of R'k*_i from k_cov_var's sums, i < nt.  split == 1: g[z][i] holds the column group's sum of squares;
+// else part[k][i][c] the ranges' shares of u_ic: added in range order, squared and summed in column order inside the group
+// (from 0, as the kernel does).  The groups are added in ascending order, first copied.
+__global__ __launch_bounds__(256) void k_cov_var_finish(const double* __restrict__ part, int split, const double* __restrict__ g,
+                                                        int nz, int gw, int nt, int rp, double* __restrict__ s)
+{
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= nt) return;
+    double tot = 0.0;
+    for (int z = 0; z < nz; z++) {
+        double sz;
+        if (split == 1) {
+            sz = g[(size_t)z * nt + i];
+        } else {
+            sz = 0.0;
+            for (int c = z * gw; c < (z + 1) * gw && c < rp; c++) {
+                double u = part[(size_t)i * rp + c];
+                for (int k = 1; k < split; k++) u = u + part[((size_t)k * nt + i) * rp + c];
+                sz = sz + u * u;
+            }
+        }
+        tot = z == 0 ? sz : tot + sz;
+    }
+    s[i] = tot;
+}

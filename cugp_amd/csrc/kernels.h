@@ -546,6 +546,31 @@ void launch_iter_paths_add(const double* f, double* k, size_t cnt, hipStream_t s
 void launch_paths_grad(const double* Xt, int nt, int d, const CovFn& cf, const double* X, int n, const double* V, const IterPlan& pd,
                        double* partd, const double* Om, const double* ph, int m, const double* org, const double* W, double amp,
                        const IterPlan& pf, double* partf, int tp, double* out, hipStream_t s);
+// ---- the variance cache (iter_varcache_gfx950.h, the one-workgroup kernels: iter_device.h): an orthonormal
+// basis Q [n][rp] of a block Krylov space of K, H = Q'KQ = L L', R = Q L^-T, and var(x*) = prior - |R'k*|^2
+enum { VC_GOT = 0, VC_REASON = 1, VC_PRODUCTS = 2, VC_LIVE = 3, VC_CTL = 4 };
+// A column ends the basis when its squared norm after both projection passes is <= VC_FLOOR (k + 1) u times its squared norm
+// before them.  A column that lies in the span of the k before it leaves twice-applied classical Gram-Schmidt with a relative
+// norm of about k u, a squared ratio of (k u)^2: far below the floor at every k <= 512.  A column that is kept has a ratio above
+// VC_FLOOR k u, so the first pass loses at most half of the 53 bits and the second restores orthogonality to a few u (the
+// "twice is enough" argument needs a ratio well above u^2 only).  The numpy stand-in (tools/varcache_standin.py) reports both
+// sides on the test cases: the smallest ratio of a kept column and the largest of an ended one lie many decades apart, and
+// PCH_FLOOR's 5 separates them with room on either side; the cache takes the same constant.
+constexpr double VC_FLOOR = 5.0;
+constexpr int VC_NCT = 8;            // column tiles of R per pass of k_cov_var: 128 columns
+void launch_vc_init(int* ctl, hipStream_t s);
+void launch_vc_place(const double* W, double* Q, int rp, int c0, int cw, int n, hipStream_t s);   // Q[:, c0 .. c0 + cw) = W[:, 0 .. cw)
+void launch_vc_hacc(const double* C, double* Hc, int rp, int first, int* ctl, hipStream_t s);
+void launch_vc_factor(const double* C, int c0, int cw, int mode, int record, const double* nrm0, double* Ti, const double* Hc,
+                      double* H, int rp, int c0p, int* ctl, hipStream_t s);
+// out [n][16] = W Ti, and its first cw columns into Q's slot at c0
+void launch_vc_scale(const double* W, const double* Ti, double* out, double* Q, int rp, int c0, int cw, int n, hipStream_t s);
+// S = H symmetrised over blocks of bw (identity beyond VC_GOT), factored in place; R = Q L^-T in 16-column groups, zero beyond VC_GOT
+void launch_vc_finish(const double* H, double* S, const double* Q, double* R, int rp, int bw, int n, int* ctl, hipStream_t s);
+// sq[i] = |R'k(xt_i, X)|^2, i < nt; pl = iter_apply_plan(nt, n, .); part: pl.split * nt * rp doubles when pl.split > 1;
+// g: ceil(rp / 128) * nt doubles
+void launch_cov_var(const double* Xt, int nt, const double* X, int n, int d, const CovFn& cf, const double* R, int rp, double* part,
+                    double* g, double* sq, const IterPlan& pl, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -244,6 +244,9 @@ static void set_big_lds();
 // k_cov_xgrad_cols, k_cov_xgrad_cols4, k_rff_grad, k_rff_grad4 (the input gradients of the sample paths: the entry times a
 // per-dimension factor is the MFMA's A operand, s shared columns B), k_paths_grad_finish and launch_paths_grad
 #include "iter_paths_grad_gfx950.h"
+// k_cov_var (the cached predictive variance: one entry feeds eight column tiles of the cache's factor R, squared and summed in
+// the launch), k_vc_place, k_vc_scale, k_vc_rsolve and the launchers of these and of iter_device.h's k_vc_* (the block Arnoldi build)
+#include "iter_varcache_gfx950.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
 // failure is kept (the launch that follows would be rejected) and reported by prepare_kernels().

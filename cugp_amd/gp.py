@@ -757,6 +757,7 @@ class IterativeGP:
             raise ValueError("expected X %s and y %s" % ((self.n, self.d), (self.n,)))
         check(capi.lib().cugp_iter_set_data(self._h, ptr(X), ptr(y)))
         self._origin = X.mean(axis=0)                  # sample_paths' default origin
+        self._y = y.copy()                             # variance_cache's default start block
 
     def set_loghyper(self, hp):
         hp = f64(hp)
@@ -895,14 +896,51 @@ class IterativeGP:
         return out
 
     def predict(self, Xt, var=True, tol=1e-10, max_iter=1000, check_every=10):
-        """(mean, var, info [nt, 4]) at the test points, var with sn2 as Covsum's; var=False: (mean, None, None), no solve."""
+        """(mean, var, info [nt, 4]) at the test points, var with sn2 as Covsum's; var=False: (mean, None, None), no solve.
+        var="cached": (mean, var, None) with the variance from the variance cache (variance_cache; cugp_iter_predict_cached):
+        one fused launch, no solve, never below the exact variance; raises where no cache stands."""
         Xt = f64(Xt).reshape(-1, self.d)
         nt = Xt.shape[0]
         mean = np.empty(nt)
+        if isinstance(var, str):
+            if var != "cached":
+                raise ValueError('var must be True, False or "cached"')
+            v = np.empty(nt)
+            check(capi.lib().cugp_iter_predict_cached(self._h, ptr(Xt), nt, 1, ptr(mean), ptr(v)))
+            return mean, v, None
         v, info = (np.empty(nt), np.empty((nt, 4))) if var else (None, None)
         check(capi.lib().cugp_iter_predict(self._h, ptr(Xt), nt, ptr(mean), ptr(v) if var else None, float(tol), int(max_iter),
                                            int(check_every), ptr(info) if var else None))
         return mean, v, info
+
+    def variance_cache(self, rank, start=None, rng=None):
+        """Build the variance cache of that rank (cugp_iter_varcache_build) for the data and hyper-parameters as they stand:
+        {achieved, rp, products, reason} -- reason 0: the asked rank, 1: the basis ended, 2: a pivot ended it.  start [tb, n],
+        tb <= 16, is the block Krylov space's start block; None: y and 15 Rademacher rows drawn on the host from rng (a
+        numpy.random.Generator).  Equal inputs give equal bits.  set_data, set_loghyper and a new build drop the cache."""
+        if start is None:
+            if rng is None:
+                raise ValueError("drawing the start block needs rng, a numpy.random.Generator")
+            start = np.vstack([self._y[None, :], rademacher(rng, 15, self.n)])
+        B = self._block(start)
+        out = (C.c_int * 4)()
+        check(capi.lib().cugp_iter_varcache_build(self._h, ptr(B), B.shape[0], int(rank), out))
+        return dict(zip(("achieved", "rp", "products", "reason"), out))
+
+    def variance_cache_info(self):
+        """{achieved, rp, products, reason} of the cache that stands (cugp_iter_varcache_info); achieved 0: none."""
+        out = (C.c_int * 4)()
+        check(capi.lib().cugp_iter_varcache_info(self._h, out))
+        return dict(zip(("achieved", "rp", "products", "reason"), out))
+
+    def variance_cache_factor(self):
+        """(Q [k, n], R [k, n], H [k, k]) of the cache, k the achieved rank (cugp_iter_varcache_get): Q orthonormal rows,
+        H = Q K Q' as factored, R = L^-1 Q with H = L L'."""
+        k = self.variance_cache_info()["achieved"]
+        Q, R, H = np.zeros((k, self.n)), np.zeros((k, self.n)), np.zeros((k, k))
+        z = np.zeros(1)
+        check(capi.lib().cugp_iter_varcache_get(self._h, ptr(Q if k else z), ptr(R if k else z), ptr(H if k else z)))
+        return Q, R, H
 
     def input_grad(self, Xt, W):
         """[nt, d]: sum_j W[col(i), j] dk(xt_i, x_j) / dxt_i over all n rows (cugp_iter_input_grad) for W [t, n]: t == 1, one

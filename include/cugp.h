@@ -1119,6 +1119,37 @@ int cugp_iter_paths_grad(cugp_iter *h, const double *Xt, int nt, const double *O
                          const double *W /* may be NULL */, const double *V /* may be NULL */, int s,
                          const double *origin /* may be NULL */, double *out /* [s][nt][d] */);
 
+/* ---- cached predictive variances ----
+ * cugp_iter_predict pays a 64-column solve per 64 variances.  The cache is computed once per (data, theta): an orthonormal basis
+ * Q (n x k, k <= CUGP_ITER_MAX_RANK) of the block Krylov space span{B, K B, K^2 B, ...} of K = Kf + sn2 I, the projected matrix
+ * H = Q'KQ = L L', and R = Q L^-T.  K^-1 is replaced by its Galerkin projection Q H^-1 Q' = R R':
+ *      var_k(x*) = sf2 + sn2 - |R' k*|^2 .
+ * Q H^-1 Q' <= K^-1 in the Loewner order, so var_k is never below the exact variance (up to rounding), does not grow when the
+ * space grows, and is exact at k = n.  How close a given k comes at a given (data, theta) is a property of K, not of this code.
+ *
+ * cugp_iter_varcache_build : B [tb][n], 1 <= tb <= 16, is the start block (its columns are orthonormalised first); each of the
+ *      ceil(rank / tb) steps multiplies the newest block by K on the fp64 product (the preconditioner and the mixed mode do not
+ *      enter; cugp_iter_solve_stats is left alone), orthogonalises against ALL earlier columns twice and orthonormalises inside
+ *      the block; the device decides where the basis ends: at a column whose squared norm after projection is at most
+ *      5 (k + 1) 2^-53 times the one before it, or at a pivot of H's factor that is not positive.  Everything before that column
+ *      is kept and the call still returns CUGP_OK.  out = {achieved rank, padded rank (a multiple of 64), products with a live
+ *      block, reason: 0 the asked rank, 1 the basis ended, 2 a pivot ended it}.  A start block of zeros gives rank 0.  The
+ *      result is a deterministic function of (X, y, theta, B, rank, split): equal inputs, equal bits.  One host wait per build;
+ *      memory 2 n rp doubles (Q and R are both kept).  cugp_iter_set_data, cugp_iter_set_loghyper and a new build drop the cache.
+ * cugp_iter_varcache_info  : out as above for the cache that stands; achieved rank 0 where there is none.
+ * cugp_iter_varcache_get   : Q [rank][n], R [rank][n], H [rank][rank] (symmetrised as factored); each may be NULL.
+ * cugp_iter_predict_cached : var [nt] (required) = prior - |R' k*|^2 from ONE fused launch over all nt points (k_cov_var: the
+ *      entries of K(Xt, X) live in registers, no [nt][k] intermediate); with_noise != 0: the prior is sf2 + sn2, as
+ *      cugp_iter_predict's, else sf2.  mean (may be NULL) is cugp_iter_predict's product with alpha, in its bits; it needs a fit.
+ *      A point's bits do not depend on the other points.
+ * CUGP_ERR_INVALID, before a device is looked for: a NULL handle (or B, out, Xt, var); tb outside [1, 16]; rank outside
+ *      [1, CUGP_ITER_MAX_RANK] or beyond n; nt outside [1, CUGP_ITER_MAX_N]; no cache for the data and hyper-parameters as they
+ *      stand (get, predict_cached); mean asked for without a fit. */
+int cugp_iter_varcache_build(cugp_iter *h, const double *B, int tb, int rank, int out[4]);
+int cugp_iter_varcache_info(cugp_iter *h, int out[4]);
+int cugp_iter_varcache_get(cugp_iter *h, double *Q /* may be NULL */, double *R /* may be NULL */, double *H /* may be NULL */);
+int cugp_iter_predict_cached(cugp_iter *h, const double *Xt, int nt, int with_noise, double *mean /* may be NULL */, double *var);
+
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);
 int cugp_mfma_peak_tflops(int device, double *tflops);

@@ -59,6 +59,10 @@ kernel trace, with --reps 12); --lib PATH loads another libcugp.so (the parent c
 `... --paths-grad --launches-only --reps 12` each, the second with --lib): per kernel the median, smallest and largest of its
 launches with the FIRST dropped; the data term's entry rate (nt n entries; every entry is computed once per chunk of four
 dimensions) beside k_cov_apply4's, and s times the parent's k_cov_xgrad launch with its finish beside the one new launch.
+
+--varcache: instead of the above, the variance cache -> profiles/iter_varcache_probe.json.  Per family
+and rank (--ranks): the build's wall time and predict(var="cached") at --nt points (medians of --reps after a warm-up), the
+products taken, and at the first --ntvar points (var_cached - var_exact) / var_exact against predict(var=True).
 """
 import argparse
 import json
@@ -450,8 +454,44 @@ def paths_grad_probe(a):
     print(json.dumps(res))
 
 
+def varcache_probe(a):
+    """--varcache: the variance cache -> profiles/iter_varcache_probe.json.  Per family and rank: the
+    build's wall time (median of --reps after a warm-up), products taken, predict(var="cached") at --nt points (the same), and
+    at the first --ntvar points the exact variance of predict(var=True) (one unwarmed call per family) beside the cached one:
+    the largest and the median (var_cached - var_exact) / var_exact."""
+    res = {"build_id": capi.lib().cugp_build_id().decode(), "n": a.n, "d": D, "nt": a.nt, "ntvar": a.ntvar, "reps": a.reps,
+           "tol": 1e-8, "families": {}}
+    X, y = synth(a.n, d=D)
+    Xt = synth(a.nt, d=D, seed=7)[0]
+    for fam, th in THETA.items():
+        g = gp.IterativeGP(a.n, D, kernel=fam)
+        g.set_data(X, y)
+        g.set_loghyper(th)
+        g.fit(1e-8, 2000, 10)
+        t0 = time.perf_counter()
+        exact = g.predict(Xt[:a.ntvar], True, 1e-8, 2000, 10)[1]
+        r = {"exact_var_seconds": time.perf_counter() - t0, "ranks": {}}
+        for rank in a.ranks:
+            sec, info = timed(lambda: g.variance_cache(rank, rng=np.random.default_rng(0)), a.reps)
+            psec, out = timed(lambda: g.predict(Xt, var="cached"), a.reps)
+            rel = (out[1][:a.ntvar] - exact) / exact
+            r["ranks"][rank] = {"build_seconds": sec, "info": info, "predict_cached_seconds": psec, "rel_excess_max": float(rel.max()),
+                                "rel_excess_median": float(np.median(rel)), "rel_excess_min": float(rel.min())}
+            print(fam, rank, r["ranks"][rank], flush=True)
+        g.close()
+        res["families"][fam] = r
+    res["not_measured"] = ["device times of k_cov_var (no kernel trace)", "the 16-tile width of k_cov_var (not built)",
+                           "k_cov_var against four apply_cross launches", "other families than SE and RQ-ARD", "nt = 1e5"]
+    out = a.out if not a.out.endswith("iter_probe.json") else os.path.join(ROOT, "profiles", "iter_varcache_probe.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--varcache", action="store_true", help="the variance cache's probe (its own mode)")
+    ap.add_argument("--ranks", type=int, nargs="+", default=[64, 256, 512], help="... the cache's ranks")
     ap.add_argument("--paths-grad", action="store_true", help="the sample paths' input gradients (its own mode)")
     ap.add_argument("--lib", default="", help="... another libcugp.so to load instead of the tree's (the parent commit's)")
     ap.add_argument("--paths", action="store_true", help="the pathwise draws' probe (its own mode)")
@@ -479,6 +519,8 @@ def main():
         capi._share_torch_hip_runtime()
         other = ctypes.CDLL(capi.LIB_PATH)
         capi.SIGNATURES = {k: v for k, v in capi.SIGNATURES.items() if hasattr(other, k)}
+    if a.varcache:
+        return varcache_probe(a)
     if a.paths_grad:
         return paths_grad_probe(a)
     if a.precond is not None:
