@@ -24,6 +24,7 @@ CUGP_KERNEL_SE, CUGP_KERNEL_MATERN32, CUGP_KERNEL_MATERN52 = 0, 1, 2
 CUGP_KERNEL_RQ = 3          # rational quadratic: create calls of its own (cugp_create_rq), not a kind= of the others
 CUGP_ITER_MAX_N = 2147482623     # cugp_iter_*: most rows of a matrix-free handle or of a product's output
 CUGP_ITER_MAX_RANK = 512         # ... most columns of its preconditioner's factor
+CUGP_NN_MAX_M = 63               # cugp_nn_*: most neighbours of a row
 CUGP_ITER_FP64, CUGP_ITER_MIXED = 0, 1   # cugp_iter_set_precision: the product inside a solver's sweep
 CUGP_COMBINE_POE, CUGP_COMBINE_GPOE, CUGP_COMBINE_BCM, CUGP_COMBINE_RBCM = 0, 1, 2, 3
 CUGP_COMBINE_REFERENCE = -1      # cugp_bcm_predict_grad / cugp_poe_combine_grad: the reference's product of the noisy predictions
@@ -237,6 +238,17 @@ SIGNATURES = {
     "cugp_iter_varcache_info": (C.c_int, [C.c_void_p, _ip]),
     "cugp_iter_varcache_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "cugp_iter_predict_cached": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "cugp_nn_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "cugp_nn_destroy": (C.c_int, [C.c_void_p]),
+    "cugp_nn_num_hyper": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_nn_check_neighbors": (C.c_int, [_ip, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "cugp_nn_set_data": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "cugp_nn_set_neighbors": (C.c_int, [C.c_void_p, _ip]),
+    "cugp_nn_set_loghyper": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "cugp_nn_loglik": (C.c_int, [C.c_void_p, _dp]),
+    "cugp_nn_loglik_grad": (C.c_int, [C.c_void_p, _dp, _dp, C.c_int]),
+    "cugp_nn_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, _ip, C.c_int, _dp, _dp]),
+    "cugp_nn_cg_solve": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_int, _ip]),
     "cugp_test_gemm_nt": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int]),
     "cugp_mfma_peak_tflops": (C.c_int, [C.c_int, _dp]),
     "cugp_set_tuning": (C.c_int, [C.c_int, C.c_int]),

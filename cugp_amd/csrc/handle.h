@@ -179,6 +179,22 @@ struct cugp_group {
     Scratch pred;                   // grouped prediction scratch (predict_passes: test inputs, [expert][ntpad][npad] Ks and W)
 };
 
+// the nearest-neighbour (Vecchia) GP (nn.cpp; include/cugp.h cugp_nn_*): X, y and the index rows on
+// the device, theta with its staging area, the workgroups' partial rows and one stream
+struct cugp_nn {
+    int n = 0, m = 0, d = 0, device = 0, kernel = cugp::KERNEL_SE, nh = 3;
+    bool ard = false;              // one length scale per dimension in theta
+    bool route = false;            // the kernels' ARD route: ard, or rational quadratic in either form (tied weights)
+    hipStream_t stream = nullptr;
+    double *dX = nullptr, *dy = nullptr;
+    int* didx = nullptr;           // [n][m], -1: no neighbour
+    cugp::HyperScalars *dhs = nullptr, *hhs = nullptr;   // [HyperScalars][w_1 .. w_d][alpha, h2a]: device, pinned
+    std::vector<double> theta;
+    bool have_data = false, have_idx = false, have_theta = false;
+    Scratch part, out, hout;       // partial rows; the result row [l, g (nh)] with k_nn_finish's work behind it; its pinned copy
+    Scratch xt, tidx, pred, hpred; // prediction: test points; their index rows [nt][m] (ints); mean and var [2][nt]; pinned copy
+};
+
 namespace cugp {
 
 // ---- cugp_capi.cpp

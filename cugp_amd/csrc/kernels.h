@@ -571,6 +571,21 @@ void launch_vc_finish(const double* H, double* S, const double* Q, double* R, in
 // g: ceil(rp / 128) * nt doubles
 void launch_cov_var(const double* Xt, int nt, const double* X, int n, int d, const CovFn& cf, const double* R, int rp, double* part,
                     double* g, double* sq, const IterPlan& pl, hipStream_t s);
+// ---- the nearest-neighbour (Vecchia) GP (cugp_nn_*; nn_gfx950.h) ----
+// One wavefront factors one conditioning block: `rows` blocks of the own point (training row b; NN_PREDICT: row b of Xt, y =
+// 0) behind the up to m training rows idx[b][0 .. m) (-1: none), m <= NN_MAX_M.  mode NN_VALUE: part[nn_workgroups][1], the
+// workgroups' sums of l; NN_GRAD: part[nn_workgroups][1 + nn_part_columns] = [l][length: 1, ARD route d][shape][sf][sn];
+// NN_PREDICT: mean and var [rows] directly (with_noise 0: the latent variance).  idx must hold validated indices.
+enum { NN_VALUE = 0, NN_GRAD = 1, NN_PREDICT = 2 };
+constexpr int NN_MAX_M = 63;
+int nn_block_size(int m);                                  // the padded block: 16, 32 or 64 rows
+int nn_workgroups(int rows, int m);
+inline int nn_part_columns(const CovFn& cf, int d) { return (cf.ard ? d : 1) + shape_count(cf.kind) + 2; }
+void launch_nn_block(int mode, const double* X, const double* y, const int* idx, const double* Xt, int rows, int m, int d,
+                     const CovFn& cf, double* part, double* mean, double* var, int with_noise, hipStream_t s);
+// out[0] = the rows' l added in ascending order; out[1 ..] = -(the columns' sums), the first `fold` columns (a tied handle's
+// d length columns; else 0) added in index order into out[1].  nc = 1 + columns; work: nc doubles.
+void launch_nn_finish(const double* part, int nparts, int nc, int fold, double* out, double* work, hipStream_t s);
 // profiling level 4: the NEXT launch of a timed kernel (trailing updates, inverse products, k_trtri_block,
 // k_predict_gemm) on this thread carries these events as the dispatch's own start / stop (hipExtLaunchKernelGGL)
 void time_next_launch(hipEvent_t start, hipEvent_t stop);

@@ -247,6 +247,9 @@ static void set_big_lds();
 // k_cov_var (the cached predictive variance: one entry feeds eight column tiles of the cache's factor R, squared and summed in
 // the launch), k_vc_place, k_vc_scale, k_vc_rsolve and the launchers of these and of iter_device.h's k_vc_* (the block Arnoldi build)
 #include "iter_varcache_gfx950.h"
+// the nearest-neighbour (Vecchia) GP (cugp_nn_*): k_nn_block (one wavefront per conditioning block, the factor in registers),
+// k_nn_finish and their launchers
+#include "nn_gfx950.h"
 
 // hipFuncAttributeMaxDynamicSharedMemorySize applies to the CURRENT device only: one flag per device, and a
 // failure is kept (the launch that follows would be rejected) and reported by prepare_kernels().

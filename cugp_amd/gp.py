@@ -1082,6 +1082,127 @@ class IterativeGP:
         return dict(zip(("split", "per", "stages", "row_blocks"), out))
 
 
+def nn_neighbors(X, m, Xt=None, weights=None):
+    """The index rows of NeighborGP, int32 [rows, m], each row's neighbours in order of distance and padded with -1.
+    Without Xt: for every row i of X its min(i, m) nearest EARLIER rows; with Xt: for every test point its m nearest rows of
+    X.  The distance is Euclidean, with `weights` [d] multiplied into the differences; ties go to the smaller index.  Brute
+    force in row chunks, by torch on the GPU where one is visible and by numpy otherwise: plumbing, not HIP."""
+    X = f64(X)
+    Q = X if Xt is None else f64(Xt).reshape(-1, X.shape[1])
+    n, m = X.shape[0], int(m)
+    w = np.ones(X.shape[1]) if weights is None else f64(weights)
+    out = np.full((Q.shape[0], m), -1, dtype=np.int32)
+    try:
+        import torch
+        dev = torch.device("cuda") if torch.cuda.is_available() else None
+    except ImportError:
+        dev = None
+    Xw = X * w
+    if dev is not None:
+        Xd = torch.from_numpy(Xw).to(dev)
+    step = max(1, (1 << 22) // max(n, 1))
+    for r0 in range(0, Q.shape[0], step):
+        Qw = Q[r0:r0 + step] * w
+        rows = np.arange(r0, r0 + len(Qw))
+        if dev is not None:
+            qd = torch.from_numpy(Qw).to(dev)
+            D = ((qd[:, None, :] - Xd[None, :, :]) ** 2).sum(-1)
+            if Xt is None:
+                D[torch.arange(n, device=dev)[None, :] >= torch.from_numpy(rows).to(dev)[:, None]] = float("inf")
+            order = torch.sort(D, dim=1, stable=True)[1][:, :m].cpu().numpy()
+            D = D.cpu().numpy()
+        else:
+            D = ((Qw[:, None, :] - Xw[None, :, :]) ** 2).sum(-1)
+            if Xt is None:
+                D[np.arange(n)[None, :] >= rows[:, None]] = np.inf
+            order = np.argsort(D, axis=1, kind="stable")[:, :m]
+        keep = np.isfinite(np.take_along_axis(D, order, axis=1))
+        out[r0:r0 + len(Qw), :order.shape[1]] = np.where(keep, order, -1)
+    return out
+
+
+class NeighborGP:
+    """The nearest-neighbour (Vecchia) GP (cugp_nn_*): LL = sum_i log p(y_i | y_N(i)) over at most m earlier rows N(i) per
+    row, in the order the rows are given (permute them at random first), one wavefront per conditioning block.  kernel / ard
+    and the hyper-parameter vector as IterativeGP's.  It trains the hyper-parameters IterativeGP then predicts with exactly;
+    predict is the cheap local prediction from m neighbours."""
+
+    def __init__(self, n, m, d, kernel="se", ard=False, device=0):
+        self.n, self.m, self.d, self.device = int(n), int(m), int(d), int(device)
+        self._kind, self.ard = kernel_spec(kernel, ard)
+        self.nh = num_hyper(self._kind, self.ard, self.d)
+        self._h = C.c_void_p()
+        check(capi.lib().cugp_nn_create(self.n, self.m, self.d, self.device, self._kind, 1 if self.ard else 0, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            capi.lib().cugp_nn_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _idx(idx, rows, m):
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.shape != (rows, m):
+            raise ValueError("expected index rows %s" % ((rows, m),))
+        return idx, idx.ctypes.data_as(C.POINTER(C.c_int))
+
+    def set_data(self, X, y):
+        X, y = f64(X), f64(y)
+        if X.shape != (self.n, self.d) or y.shape != (self.n,):
+            raise ValueError("expected X %s and y %s" % ((self.n, self.d), (self.n,)))
+        check(capi.lib().cugp_nn_set_data(self._h, ptr(X), ptr(y)))
+        self._X = X.copy()                             # predict's default neighbour search
+
+    def set_neighbors(self, idx):
+        """idx [n, m]: row i's earlier rows, -1 where there is none (nn_neighbors(X, m) makes them)."""
+        idx, p = self._idx(idx, self.n, self.m)
+        check(capi.lib().cugp_nn_set_neighbors(self._h, p))
+
+    def set_loghyper(self, hp):
+        hp = f64(hp)
+        if hp.shape != (self.nh,):
+            raise ValueError("expected %d log-hyper-parameters" % self.nh)
+        check(capi.lib().cugp_nn_set_loghyper(self._h, ptr(hp), self.nh))
+
+    def loglik(self):
+        ll = C.c_double()
+        check(capi.lib().cugp_nn_loglik(self._h, C.byref(ll)))
+        return ll.value
+
+    def loglik_grad(self):
+        """(LL, g): the value and the gradient of -LL [nh] (cugp_nn_loglik_grad)."""
+        ll, g = C.c_double(), np.empty(self.nh)
+        check(capi.lib().cugp_nn_loglik_grad(self._h, C.byref(ll), ptr(g), self.nh))
+        return ll.value, g
+
+    def predict(self, Xt, idx=None, with_noise=True):
+        """(mean, var) at the test points from the training rows idx [nt, m] (default: nn_neighbors(X, m, Xt))."""
+        Xt = f64(Xt).reshape(-1, self.d)
+        nt = Xt.shape[0]
+        idx, p = self._idx(nn_neighbors(self._X, self.m, Xt) if idx is None else idx, nt, self.m)
+        mean, var = np.empty(nt), np.empty(nt)
+        check(capi.lib().cugp_nn_predict(self._h, ptr(Xt), nt, p, 1 if with_noise else 0, ptr(mean), ptr(var)))
+        return mean, var
+
+    def cg_solve(self, budget=100):
+        """Conjugate gradients on -LL from the current hyper-parameters (cugp_nn_cg_solve); the trace [n_iterates, nh + 1]
+        = (theta, -LL) as SparseGP.cg_solve's; the end point stays set."""
+        budget = int(budget)
+        tr = np.full((4 * max(budget, 0) + 8, self.nh + 1), np.nan)
+        ne = C.c_int()
+        check(capi.lib().cugp_nn_cg_solve(self._h, budget, ptr(tr), tr.shape[0], C.byref(ne)))
+        rows = 1
+        while rows < min(ne.value, tr.shape[0]) and not np.isnan(tr[rows, 0]):
+            rows += 1
+        return tr[:rows]
+
+
 class SamplePaths:
     """Posterior sample paths of an IterativeGP (IterativeGP.sample_paths): paths(Xt) -> [s, nt], f_s(x) = phi(x)' w_s +
     k(x, X) v_s (cugp_iter_paths_eval), 64 paths a call; paths.grad(Xt) -> [s, nt, d], their gradients with respect to x

@@ -1150,6 +1150,56 @@ int cugp_iter_varcache_info(cugp_iter *h, int out[4]);
 int cugp_iter_varcache_get(cugp_iter *h, double *Q /* may be NULL */, double *R /* may be NULL */, double *H /* may be NULL */);
 int cugp_iter_predict_cached(cugp_iter *h, const double *Xt, int nt, int with_noise, double *mean /* may be NULL */, double *var);
 
+/* ---- the nearest-neighbour (Vecchia) GP (cugp_nn_*): the joint density as a product of n small conditionals,
+ *        p(y) ~ prod_i p(y_i | y_N(i)),
+ *      N(i) at most m EARLIER rows, in the order the caller gives the rows (Vecchia 1988; Datta et al. 2016).  A proper density,
+ *      exact at m = n - 1 with N(i) = {0 .. i - 1}, O(n m^3) time and O(n m) memory, no iterative solver and no probes: value
+ *      and gradient are deterministic.  It trains the hyper-parameters that cugp_iter_* then predicts with exactly, and its
+ *      own prediction is a cheap local one.  kernel, ard and theta's layout per family are cugp_iter_create's and
+ *      cugp_iter_set_loghyper's.
+ *      The model.  Row i conditions on the rows idx[i][0 .. m) (-1: no neighbour there; c_i <= min(i, m) of them).  With
+ *        C_i = k([X_N(i); x_i], .) + sn2 I     ((c_i + 1) x (c_i + 1), the row's own point LAST),   L its Cholesky factor,
+ *        z = L^-1 [y_N(i); y_i]:
+ *        l_i = -1/2 z_last^2 - log L_last,last - 1/2 c,     LL = sum_i l_i        (c = 1.83787, cugp_loglik's literal for log 2 pi)
+ *      One factorisation serves the joint block and its leading neighbour block: with u = L^-T e_last and p = L^-T [z_N; 0] (=
+ *      K_NN^-1 y_N, padded), C^-1 - pad(C_NN^-1) = u u^T and C^-1 [y_N; y_i] = p + z_last u, so that
+ *        dl_i / dtheta_h = 1/2 sum_ab dW_ab dC_ab / dtheta_h,   dW = z_last (p u^T + u p^T) + (z_last^2 - 1) u u^T
+ *      and no inverse is formed.  g [nh] is the gradient of -LL, in cugp_loglik_grad's sign, convention and order (as
+ *      cugp_sparse_bound_grad states it for its bound).  Sums run in a fixed order without atomics: equal inputs give equal
+ *      bits, and cugp_nn_loglik returns cugp_nn_loglik_grad's value bit for bit.
+ *      Prediction at x* conditions on the m training rows idx_t[t][0 .. m) (any training rows; -1: none): the same block with
+ *      x* last and y* = 0 gives  mean = -z_last L_last,last,  var = L_last,last^2  (with_noise 0: - sn2).  A row's result
+ *      does not depend on the other test rows.
+ *      A block that is not positive definite -- a pivot that is not above 2^-44 (sf2 + sn2): no digit of it is left -- or NaN
+ *      data gives NaN results with CUGP_OK; the next healthy theta or data gives a fresh handle's bits.
+ * cugp_nn_check_neighbors: pure host, no device: CUGP_OK where every entry of idx [rows][m] is -1 or a row in [0, n) --
+ *      training != 0: in [0, i), earlier than its own row i -- and no row holds an index twice.  cugp_nn_set_neighbors and
+ *      cugp_nn_predict run this check on what they are given before anything reaches a device: no launch reads out of bounds.
+ * cugp_nn_cg_solve: cugp_cg_minimize_n's loop on f = -LL from the current theta, with cugp_sparse_cg_solve's trace ([.][nh + 1]
+ *      rows (theta, f) of the start and of every line search's end, a NaN row behind the last where there is room) and end-point
+ *      rule (the end point stays set).
+ *      Refusals, all CUGP_ERR_INVALID with the call's name in cugp_last_error, before the handle is read or a device is looked
+ *      for: a NULL handle or argument; n, d, rows or nt < 1; n or nt beyond CUGP_ITER_MAX_N; m outside [1, CUGP_NN_MAX_M]; an
+ *      unknown kernel; ard, training or with_noise outside {0, 1}; a negative device; an nh that is not the handle's; an index
+ *      that is out of range, not earlier than its row (training) or twice in a row; budget <= 0; a call before the data, the
+ *      neighbours (not needed by cugp_nn_predict) or the hyper-parameters it needs are set.
+ *      Not built: the latent (noise-free) form, grouped conditioning sets, reordering (the caller's order stands: permute the rows
+ *      at random first), a neighbour search on the device, targets, input gradients, rows sharded across devices, m > 63. */
+#define CUGP_NN_MAX_M 63
+typedef struct cugp_nn cugp_nn;
+int cugp_nn_create(int n, int m, int d, int device, int kernel, int ard, cugp_nn **out);
+int cugp_nn_destroy(cugp_nn *h);
+int cugp_nn_num_hyper(const cugp_nn *h, int *nh);
+int cugp_nn_check_neighbors(const int *idx /* [rows][m] */, int rows, int m, int n, int training);
+int cugp_nn_set_data(cugp_nn *h, const double *X /* [n][d], host */, const double *y /* n */);
+int cugp_nn_set_neighbors(cugp_nn *h, const int *idx /* [n][m], -1 beyond c_i */);
+int cugp_nn_set_loghyper(cugp_nn *h, const double *theta, int nh);
+int cugp_nn_loglik(cugp_nn *h, double *ll);
+int cugp_nn_loglik_grad(cugp_nn *h, double *ll, double *g /* nh */, int nh);
+int cugp_nn_predict(cugp_nn *h, const double *Xt /* [nt][d] */, int nt, const int *idx_t /* [nt][m] */, int with_noise,
+                    double *mean /* nt */, double *var /* nt */);
+int cugp_nn_cg_solve(cugp_nn *h, int budget, double *trace, int trace_cap, int *nevals);
+
 /* ---- test / bench hooks ---- */
 int cugp_test_gemm_nt(int m, int n, int k, const double *A, const double *B, double *C, int device);
 int cugp_mfma_peak_tflops(int device, double *tflops);
